@@ -96,6 +96,28 @@ def measure_traffic(n, kind, timeout=180):
                  "tools/kbench.py on the same workload; KiB x 1024, FETCH_SIZE x 2 (gfx950 128-byte requests)")
 
 
+def native_oracle(params_type):
+    """the CPU baseline's oracle: oracle/x3_oracle.c built for THIS host by oracle/Makefile's `native` target (-O3
+    -march=native -flto), in a temporary directory -- the tree the benchmark runs from may be read-only, and a build made on
+    another host is not native to this one.  Only x3o_time_roundtrip is bound (params_type: the oracle's parameter struct)."""
+    import shutil
+    import subprocess
+    import tempfile
+    d = tempfile.mkdtemp(prefix="x3oracle_")
+    try:
+        for f in ("Makefile", "x3_oracle.c", "x3_oracle.h"):
+            shutil.copy(os.path.join(ROOT, "oracle", f), d)
+        subprocess.run(["make", "-s", "-C", d, "native"], check=True)
+        L = C.CDLL(os.path.join(d, "libx3oracle_native.so"))
+    finally:
+        shutil.rmtree(d, ignore_errors=True)   # (a loaded library stays mapped)
+    L.x3o_time_roundtrip.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(params_type), C.c_int, C.POINTER(C.c_double),
+                                     C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+    L.x3o_init.restype = None
+    L.x3o_init()
+    return L
+
+
 COMPACT_MAX = 4000   # characters of the contract line (tests/test_bench_contract.py holds it to this)
 
 
@@ -170,6 +192,58 @@ def compact_line(res):
     return c
 
 
+# --dump-outputs: an output longer than its share of the budget is written as a seeded sample of windows of DUMP_WINDOW
+# consecutive elements (the first and the last window always among them), so that two builds can be compared output for output
+DUMP_MAX_BYTES = 64_000_000      # all files of one dump together
+DUMP_WINDOW = 4096
+DUMP_STREAM_ELEMS = 4 << 20      # float32: 16 MiB
+DUMP_DECODED_ELEMS = 4 << 20     # float32: 16 MiB
+DUMP_OFFSETS_ELEMS = 2 << 20     # float64: 16 MiB (config 3 has 69 121 offsets: all of them)
+
+
+def dump_sample(t, max_elems):
+    """a 1-D device tensor -> (a copy of it on the device, None), or (its sampled windows, shape (windows, DUMP_WINDOW), the
+    windows' first indexes) when it is longer than max_elems.  The windows depend on the length alone."""
+    import numpy as np
+    import torch
+    m = t.numel()
+    if m <= max_elems:
+        return t.clone(), None
+    rng = np.random.default_rng([SEED, m])
+    last = m - DUMP_WINDOW
+    starts = np.unique(np.concatenate([[0, last], rng.integers(0, last + 1, max_elems // DUMP_WINDOW - 2)])).astype(np.int64)
+    idx = torch.from_numpy(starts).to(t.device)[:, None] + torch.arange(DUMP_WINDOW, dtype=torch.int64, device=t.device)
+    return t[idx], starts
+
+
+def write_dump(d, arrays):
+    """{name: (device tensor or numpy array, window starts or None)} -> d/<name>.npy (+ d/<name>_window_starts.npy) in float32
+    (8- and 16-bit integers) or float64 (wider ones, exact below 2**53); returns what was written"""
+    import numpy as np
+    import torch
+    files = {}
+    for name, (a, starts) in arrays.items():
+        a = a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        if a.dtype.itemsize <= 2:
+            files[name] = a.astype(np.float32)
+        else:
+            assert a.size == 0 or np.abs(a.astype(np.float64)).max() < 2 ** 53, name
+            files[name] = a.astype(np.float64)
+        if starts is not None:
+            files[name + "_window_starts"] = starts.astype(np.float64)
+    total = sum(v.nbytes for v in files.values())
+    assert total <= DUMP_MAX_BYTES, total
+    if not os.path.isdir(d):
+        os.makedirs(d)
+        # (a directory this run creates stays out of version control wherever it lies)
+        with open(os.path.join(d, ".gitignore"), "w") as fh:
+            fh.write("*\n")
+    for name, v in files.items():
+        np.save(os.path.join(d, name + ".npy"), v)
+    return {"dir": d, "bytes": int(total),
+            "arrays": {name: {"shape": list(arrays[name][0].shape), "sampled": arrays[name][1] is not None} for name in arrays}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -212,7 +286,14 @@ def main():
     ap.add_argument("--spawn", action="store_true",
                     help="start the ranks as a child process (torch.distributed.run) even for --gpus 1; --gpus N > 1 without "
                          "WORLD_SIZE in the environment does so by itself")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step handed its caller (the stream, its frame offsets, the encoder's "
+                         "block-type counts, the decoded samples) as DIR/<name>.npy in float32 / float64, at most 64 MB in all: "
+                         "an output longer than its share is a seeded sample of windows (DIR/<name>_window_starts.npy says "
+                         "where they start).  Rank 0's outputs with --gpus N > 1")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # `python3 bench.py --gpus N` outside torch.distributed.run: start the N ranks ourselves, as a CHILD process and before
     # anything here has touched the GPU (a process that has initialised HIP must never be replaced by another program);
@@ -530,7 +611,7 @@ def main():
         t = torch.tensor([elapsed_untimed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed_untimed = float(t.item())
-    rc, pos_u, _ = ctx.encode_result()
+    rc, pos_u, stats_u = ctx.encode_result()
     assert rc == 0 and pos_u == pos, (rc, pos_u, pos)
     rc, first_bad, st, before = ctx.decode_result()
     assert (rc, first_bad, st, before) == (0, F, 0, n), (rc, first_bad, st, before)
@@ -550,6 +631,16 @@ def main():
                     "achieved_us_per_block": [round(e["achieved_ticks16"] / 1600.0, 4) for e in dlog],
                     "note": "per timed step: the decoder's pace controller (x3_decode_split_kernel.h); a launch that misses its "
                             "target by more than a few per cent has all its waves at one priority = the unpaced kernel"}
+    # --dump-outputs: what the last timed step (the last of the pass above) handed its caller, before anything else
+    # overwrites the buffers
+    dump_info = None
+    if args.dump_outputs and rank == 0:
+        # (the buffer the last step wrote: only the overlapped mode rotates them, and every pass of it starts at the first)
+        lb = (args.steps - 1) % NB if gather_mode == "overlapped" else 0
+        dump_info = write_dump(args.dump_outputs, {"stream": dump_sample(outs[lb][:pos], DUMP_STREAM_ELEMS),
+                                                   "frame_offsets": dump_sample(offs_b[lb][:F + 1], DUMP_OFFSETS_ELEMS),
+                                                   "decoded": dump_sample(back[:n], DUMP_DECODED_ELEMS),
+                                                   "encode_stats": (stats_u, None)})
 
     # ---- bit-exactness of the timed output: decode(encode(x)) == x, and the stream == the CPU oracle's
     assert torch.equal(back, wav), "decode(encode(x)) != x"
@@ -691,7 +782,7 @@ def main():
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         m = min(args.cpu_sample, n)
         sample = wav[:m].cpu().numpy()
-        OL = O.lib(native=True)
+        OL = native_oracle(O.Params)
         po = O.Params.default()
         es, ds, sl = C.c_double(0), C.c_double(0), C.c_uint64(0)
         rc = OL.x3o_time_roundtrip(sample.ctypes.data, m, C.byref(po), args.cpu_reps, C.byref(es), C.byref(ds),
@@ -1225,6 +1316,8 @@ def main():
             res["rccl"] = rccl
         if placement is not None:
             res["placement"] = placement
+        if dump_info is not None:
+            res["dump_outputs"] = dump_info
         # ONE line on stdout, as the contract says, and short (<= 4 KB, so that the tail of the driver's
         # record holds every number it judges by: kernels_ms, encode_read_frac, roofline_all, the clocks, the CPU baseline,
         # configs 2 and 5); everything else -- notes, per-step arrays, the wider measurements -- goes to a FILE beside it

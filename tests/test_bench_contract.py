@@ -180,3 +180,104 @@ def test_bench_spawn_builds_the_launcher_command(monkeypatch):
     assert cmd[1:3] == ["-m", "torch.distributed.run"] and "--nproc-per-node" in cmd and cmd[cmd.index("--nproc-per-node") + 1] == "4"
     assert cmd[cmd.index("--master-addr") + 1] == "127.0.0.1" and cmd[-6:] == ["--gpus", "4", "--steps", "3", "--warmup", "1"]
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("x3_bench_mod", BENCH)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_bench_dump_samples_windows_within_the_budget(tmp_path):
+    """CPU: --dump-outputs keeps a short output whole and a long one as seeded windows that depend on its length alone (the
+    first and the last among them); outputs at every cap together stay within 64 MB, in float32 / float64"""
+    import numpy as np
+    import torch
+    b = _bench_module()
+    short = torch.arange(1000, dtype=torch.int16)
+    v, starts = b.dump_sample(short, b.DUMP_DECODED_ELEMS)
+    assert starts is None and torch.equal(v, short)
+    g = torch.Generator().manual_seed(3)
+    stream = torch.randint(0, 256, (b.DUMP_STREAM_ELEMS + 12345,), dtype=torch.uint8, generator=g)
+    v, starts = b.dump_sample(stream, b.DUMP_STREAM_ELEMS)
+    assert v.shape == (starts.size, b.DUMP_WINDOW) and starts.size * b.DUMP_WINDOW <= b.DUMP_STREAM_ELEMS
+    assert starts[0] == 0 and starts[-1] == stream.numel() - b.DUMP_WINDOW and np.all(np.diff(starts) > 0)
+    for i in (0, starts.size // 2, starts.size - 1):
+        assert torch.equal(v[i], stream[starts[i]:starts[i] + b.DUMP_WINDOW])
+    assert np.array_equal(b.dump_sample(stream.clone(), b.DUMP_STREAM_ELEMS)[1], starts)
+    arrays = {"stream": (v, starts),
+              "frame_offsets": b.dump_sample(torch.arange(b.DUMP_OFFSETS_ELEMS + 1, dtype=torch.int64) << 20, b.DUMP_OFFSETS_ELEMS),
+              "decoded": b.dump_sample(torch.zeros(b.DUMP_DECODED_ELEMS + 1, dtype=torch.int16) - 7, b.DUMP_DECODED_ELEMS),
+              "encode_stats": (np.arange(6, dtype=np.uint64), None)}
+    info = b.write_dump(str(tmp_path / "d"), arrays)
+    files = sorted(os.listdir(tmp_path / "d"))
+    assert files == [".gitignore", "decoded.npy", "decoded_window_starts.npy", "encode_stats.npy", "frame_offsets.npy",
+                     "frame_offsets_window_starts.npy", "stream.npy", "stream_window_starts.npy"]
+    assert sum(os.path.getsize(tmp_path / "d" / f) for f in files) <= 64_000_000 and info["bytes"] <= 64_000_000
+    got = {f[:-4]: np.load(tmp_path / "d" / f) for f in files if f.endswith(".npy")}
+    assert got["stream"].dtype == np.float32 and np.array_equal(got["stream"], v.numpy().astype(np.float32))
+    assert got["decoded"].dtype == np.float32 and np.all(got["decoded"] == -7)
+    assert got["frame_offsets"].dtype == np.float64 and got["encode_stats"].dtype == np.float64
+    assert np.array_equal(got["frame_offsets"], arrays["frame_offsets"][0].numpy().astype(np.float64))
+    assert np.array_equal(got["stream_window_starts"], starts.astype(np.float64))
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_timed_steps_outputs(tmp_path):
+    """--dump-outputs: two runs with the same arguments write the same arrays, and they are what the timed path computed --
+    the oracle's stream, frame offsets and block-type counts of the seeded input, and that input decoded back; --steps is the
+    number of timed steps and ms_per_step is in the line"""
+    import numpy as np
+    import oracle_lib as O
+    import x3hip
+    b = _bench_module()
+    n, steps = 20_000_000, 3
+    dumps = []
+    for run in ("a", "b"):
+        d = str(tmp_path / run)
+        r = subprocess.run([sys.executable, BENCH, "--steps", str(steps), "--warmup", "1", "--samples", str(n), "--no-cpu-baseline",
+                            "--no-measure-traffic", "--no-extras", "--place", "1", "--details", "", "--dump-outputs", d],
+                           capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        last = json.loads(lines[-1])
+        assert len(lines) == 1 and last["steps"] == steps and len(last["kernels_ms"]) and last["ms_per_step"] > 0
+        files = sorted(f for f in os.listdir(d) if f.endswith(".npy"))
+        assert sum(os.path.getsize(os.path.join(d, f)) for f in files) <= 64_000_000
+        dumps.append({f[:-4]: np.load(os.path.join(d, f)) for f in files})
+    a, b2 = dumps
+    assert sorted(a) == sorted(b2) == ["decoded", "decoded_window_starts", "encode_stats", "frame_offsets", "stream",
+                                       "stream_window_starts"]
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and np.array_equal(a[k], b2[k]), k
+    wav = x3hip.synth(x3hip.SYNTH_HYDROPHONE, b.SEED, 0, n)
+    rc, ref, stats = O.encode(wav)
+    assert rc == 0
+    offs = a["frame_offsets"].astype(np.int64)
+    assert offs.size == n // 10000 + 1 and offs[0] == 0 and offs[-1] == ref.size
+    assert np.array_equal(a["encode_stats"], stats.astype(np.float64))
+    for name, full in (("stream", ref), ("decoded", wav)):
+        starts = a[name + "_window_starts"].astype(np.int64)
+        assert starts[0] == 0 and starts[-1] == full.size - b.DUMP_WINDOW
+        want = full[starts[:, None] + np.arange(b.DUMP_WINDOW)]
+        assert np.array_equal(a[name], want.astype(np.float32)), name
+
+
+def test_bench_builds_its_cpu_baseline_outside_the_tree():
+    """CPU: the CPU baseline's native oracle is compiled in a temporary directory, so that bench.py runs from a tree it
+    cannot write to; oracle/ is left as it was, and the library times a round trip of the default parameters"""
+    import ctypes as C
+    import numpy as np
+    import oracle_lib as O
+    b = _bench_module()
+    odir = os.path.join(ROOT, "oracle")
+    before = {f: os.path.getmtime(os.path.join(odir, f)) for f in os.listdir(odir)}
+    L = b.native_oracle(O.Params)
+    assert {f: os.path.getmtime(os.path.join(odir, f)) for f in os.listdir(odir)} == before
+    wav = (np.arange(30000) % 200 - 100).astype(np.int16)
+    p = O.Params.default()
+    es, ds, sl = C.c_double(0), C.c_double(0), C.c_uint64(0)
+    assert L.x3o_time_roundtrip(wav.ctypes.data, wav.size, C.byref(p), 2, C.byref(es), C.byref(ds), C.byref(sl)) == 0
+    assert es.value > 0 and ds.value > 0 and sl.value == O.encode(wav)[1].size
