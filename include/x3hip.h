@@ -527,6 +527,41 @@ int x3_index_dev(x3_ctx* ctx, const uint8_t* d_x3, uint64_t len, uint64_t max_fr
 int x3_decode_stream_dev(x3_ctx* ctx, const uint8_t* d_x3, uint64_t len, const x3_params* p, int16_t* d_wav,
                          uint64_t wav_cap, uint64_t* n_out, uint64_t* frames_ok, uint64_t* frame_errors);
 
+/* ---- RANDOM ACCESS (no counterpart in the reference: decodefile.rs reads frame after frame).  A WINDOW is (start, L): the
+ * samples at positions [start, start + L) of a mono stream, where the position of sample i of frame f is
+ * sample_offsets[f] + i -- frames' samples back to back, what x3_decode_stream returns for a clean stream.  The work of a
+ * call follows its windows, not the stream: per window the frames that cover it, each checked (header, payload CRC, and its
+ * header's sample count against sample_offsets[f + 1] - sample_offsets[f]: a mismatch means the offsets are not this
+ * stream's, X3_ERR_BAD_ARG, as is a frame whose offset or payload lies past x3_len) and decoded by the stretches of the
+ * segment index (x3_decode_dev_seg) -- every stretch of a covering frame, those in front of the window being the proof
+ * chain of those inside it.  The index is a hint as there:
+ * without it (NULL, or a header word that says "none") frames decode whole, one lane each, with the same results.
+ * Window status (d_status, one int32 per window): 0 when every covering frame checks and decodes; otherwise the status
+ * x3_decode_dev gives the FIRST covering frame that fails -- the window's samples in front of that frame are exact, the
+ * rest are 0.  A window off the end (start + L > total, any wild start) is X3_ERR_BAD_ARG and zeros; the call itself does
+ * not fail.  Offsets, starts and index are untrusted: a wild value is a frame error or a slower path, never a read outside
+ * [d_x3, d_x3 + x3_len) or a write outside d_out.  Multi-channel frames fail as in x3_decode_dev.  DESIGN.md section 10. */
+/* Fill sample_offsets[0..n_frames] (n_frames + 1 words: exclusive prefix of the frame headers' sample counts, last = total)
+ * for frames whose byte offsets are known (the encoder's d_frame_offsets, or x3_index_dev's); a header that does not lie
+ * inside the stream counts 0.  Asynchronous. */
+int x3_sample_offsets_dev(x3_ctx* ctx, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
+                          uint64_t n_frames, uint64_t* d_sample_offsets);
+/* n_windows windows of window_len samples each, window w = positions [d_starts[w], d_starts[w] + window_len), written
+ * row-major to d_out (n_windows x window_len; out_format X3_WINDOW_I16 / X3_WINDOW_F32, d_out aligned to the sample size);
+ * d_status: n_windows int32.  d_seg_index / seg_blocks as for x3_decode_dev_seg (NULL / 0: none).  Asynchronous on the
+ * context's stream, one launch set and no host round trip; the pending state of an earlier x3_decode_dev is left as it
+ * is.  X3_ERR_BAD_ARG (nothing enqueued) for window_len == 0, n_windows == 0, an unknown format, a misaligned pointer,
+ * and seg_blocks as x3_decode_dev_seg refuses it. */
+int x3_decode_windows_dev(x3_ctx* ctx, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
+                          const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
+                          const uint64_t* d_seg_index, uint32_t seg_blocks, const uint64_t* d_starts,
+                          uint64_t n_windows, uint32_t window_len, void* d_out, int out_format, int32_t* d_status);
+/* Waits for the last x3_decode_windows_dev: windows with status != 0, the first of them (n_windows if none) and its status. */
+int x3_decode_windows_result(x3_ctx* ctx, uint64_t* n_bad, uint64_t* first_bad, int* first_bad_status);
+/* out_format of x3_decode_windows_dev */
+#define X3_WINDOW_I16 0     /* int16 samples */
+#define X3_WINDOW_F32 1     /* float32 samples, s / 32768.0f (exact) */
+
 /* ------------------------------------------------------------------ multi-GPU (no reference analogue) */
 
 /* Frames are independent and 20 + even bytes long, so GPU g encodes a contiguous range of whole frames into its own

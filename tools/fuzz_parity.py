@@ -9,7 +9,9 @@ Families: (e) the single-pass encoders on block_len 20 with mixed content, many 
           (x3_encode_frames_dev); (a) .x3a archives in memory and
           the incremental reader; (f) decode_frame frame by frame, with and without x3_decode_prefetch; (w) WAV and .x3a FILES through the
           chunked pipeline (not in the default family set: file I/O); (s) the segment index: the encoder's against the one a
-          decode records, decode by it with the stream and the index intact or damaged."""
+          decode records, decode by it with the stream and the index intact or damaged; (c) random access: batches of
+          windows (x3_decode_windows_dev) of random streams, geometries and lengths, with damaged frames, damaged indexes
+          and wild starts, against the oracle's frame verdicts (not in the default family set)."""
 import argparse, ctypes as C, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "x3-rust_amd"))
@@ -628,6 +630,132 @@ def fam_s(rng, tag):
 fams["s"] = fam_s
 
 
+def _frame_verdicts(stream, offs, p):
+    """per frame (oracle): (status, samples) -- header CRC, key, channels, the walk's length checks, payload CRC, then
+    decoder::decode_frame: the statuses x3_decode_dev gives"""
+    out = []
+    for f, off in enumerate(offs):
+        h = stream[off:off + 20]
+        samples, plen = int(h[4]) << 8 | int(h[5]), int(h[6]) << 8 | int(h[7])
+        payload = stream[off + 20:off + 20 + plen]
+        if O.crc16(h[:16]) != (int(h[16]) << 8 | int(h[17])):
+            out.append((13, None))
+        elif (int(h[0]) << 8 | int(h[1])) != 0x7833:
+            out.append((11, None))
+        elif int(h[3]) > 1:
+            out.append((6, None))
+        elif plen >= 0x7fe0:
+            out.append((10, None))
+        elif off + 20 + plen > stream.size:   # (a payload past the stream's end: the offsets are not this stream's)
+            out.append((24, None))
+        elif plen > 24576:             # (the reader's buffer, decodefile.rs:118-121: x3_decode_dev checks it too)
+            out.append((12, None))
+        elif O.crc16(payload) != (int(h[18]) << 8 | int(h[19])):
+            out.append((14, None))
+        elif samples == 0 or plen < 2:
+            out.append((24, None))
+        else:
+            rc, w = O.decode_frame(payload, samples, oparams(p))
+            out.append((rc, w if rc == 0 else None))
+    return out
+
+
+def fam_c(rng, tag):
+    """random access: windows of a random stream against the oracle's verdict of every frame that covers them"""
+    r = rng.random()
+    if r < 0.6:
+        p = x3hip.Params.default()
+    elif r < 0.8:
+        p = x3hip.Params.make(int(rng.choice([10, 40])), int(rng.choice([100, 256, 500])))
+    else:
+        bl = int(rng.integers(2, 61))
+        codes = (0, 1, 3) if rng.random() < 0.5 else tuple(int(c) for c in rng.integers(0, 4, size=3))
+        p = x3hip.Params.make(bl, int(rng.integers(1, max(2, 30000 // bl))), codes)
+        if x3hip.lib().x3_params_validate(C.byref(p)) != 0:
+            return
+    spf = p.block_len * p.blocks_per_frame
+    n = int(rng.integers(1, 12 * spf + 100))
+    wav = content(rng, n)
+    rc, stream, _ = O.encode(wav, oparams(p))
+    if rc != 0:
+        return
+    offs = frame_offsets(stream)
+    so = [0]
+    for off in offs:
+        so.append(so[-1] + (int(stream[off + 4]) << 8 | int(stream[off + 5])))
+    if so[-1] != n:   # (frames whose payload outgrows the header's length field: not a stream the reader can walk)
+        return
+    bad = stream.copy()
+    if rng.random() < 0.4:
+        for _ in range(int(rng.integers(1, 4))):
+            off = offs[int(rng.integers(0, len(offs)))]
+            plen = int(stream[off + 6]) << 8 | int(stream[off + 7])
+            kind = int(rng.integers(0, 4))
+            if kind == 0 and plen > 2:      # payload bits, CRC refreshed (a decode error or other samples) or not
+                q = off + 20 + int(rng.integers(2, plen))
+                k = min(int(rng.integers(1, 12)), off + 20 + plen - q)
+                bad[q:q + k] = 0 if rng.random() < 0.5 else rng.integers(0, 256, size=k, dtype=np.uint8)
+                if rng.random() < 0.7:
+                    refresh_crcs(bad, off)
+            elif kind == 1:                 # a header byte other than the sample count
+                q = off + int(rng.choice([0, 1, 2, 3, 6, 7, 8, 12, 16, 17, 18, 19]))
+                bad[q] ^= np.uint8(1 << int(rng.integers(0, 8)))
+            elif kind == 2 and plen > 2:    # one payload bit
+                bad[off + 20 + int(rng.integers(0, plen))] ^= np.uint8(1 << int(rng.integers(0, 8)))
+    verdicts = _frame_verdicts(bad, offs, p)
+    d = []
+    try:
+        d_off = ctx.alloc(8 * (len(offs) + 1)); d.append(d_off)
+        ctx.upload(d_off, np.array(offs + [stream.size], dtype=np.uint64))
+        sb = int(rng.choice([0, 4, 32, 64]))
+        src = x3hip.WindowSource(ctx, bad, p, seg_blocks=sb, frame_offsets=d_off, n_frames=len(offs))
+        d.extend(src._own); src._own = []
+        assert src.total == n, (tag, "total", src.total, n)
+        if src.d_seg_index is not None and rng.random() < 0.3:   # a damaged index: a hint, never trusted
+            ne = x3hip.lib().x3_seg_index_entries(len(offs), C.byref(p), src.seg_blocks)
+            idx = ctx.download(src.d_seg_index, 8 * ne, np.uint64)
+            if ne > 1:
+                sel = rng.random(ne) < 0.2; sel[0] = False
+                idx[sel] = rng.integers(0, 1 << 49, int(sel.sum()), dtype=np.uint64)
+                if rng.random() < 0.3:
+                    idx[1:] = np.roll(idx[1:], int(rng.integers(1, 5)))
+            ctx.upload(src.d_seg_index, idx)
+        L = int(rng.choice([1, 2, 19, 20, 21, 333, spf, int(rng.integers(1, n + 1))]))
+        L = max(1, min(L, n))
+        nw = int(rng.integers(1, 40))
+        starts = [int(v) for v in rng.integers(0, n - L + 1, nw)]
+        wild = [n - L + 1, n, 2 ** 63, 2 ** 64 - 1, 2 ** 64 - L, int(rng.integers(n - L + 1, 2 ** 62))]
+        for _ in range(int(rng.integers(0, 3))):
+            starts.insert(int(rng.integers(0, len(starts) + 1)), wild[int(rng.integers(0, len(wild)))])
+        fmt = int(rng.integers(0, 2))
+        rows, st = src.decode(starts, L, fmt)
+        for w, s0 in enumerate(starts):
+            want = np.zeros(L, dtype=np.int16)
+            wst = 0
+            if s0 > n - L:
+                wst = 24
+            else:
+                f = int(np.searchsorted(so, s0, side="right")) - 1
+                while f < len(offs) and so[f] < s0 + L:
+                    v, samples = verdicts[f]
+                    if v:
+                        wst = v
+                        break
+                    lo, hi = max(so[f], s0), min(so[f + 1], s0 + L)
+                    want[lo - s0:hi - s0] = samples[lo - so[f]:hi - so[f]]
+                    f += 1
+            assert st[w] == wst, (tag, "status", w, s0, L, int(st[w]), wst)
+            got = rows[w].view(np.uint32) if fmt else rows[w]
+            exp = (want.astype(np.float32) / np.float32(32768.0)).view(np.uint32) if fmt else want
+            assert np.array_equal(got, exp), (tag, "samples", w, s0, L, fmt, np.flatnonzero(got != exp)[:8].tolist())
+    finally:
+        for q in d:
+            ctx.free(q)
+
+
+fams["c"] = fam_c
+
+
 def run(seed=1, minutes=None, trials=None, families="egdbaf", only=-1, context=None):
     """draw and check cases until the time or the trial budget is used up -> {family: trials}"""
     global ctx
@@ -696,7 +824,12 @@ if __name__ == "__main__":
     ap.add_argument("--only", type=int, default=-1)
     ap.add_argument("--families", default="egdbaf")
     ap.add_argument("--start", type=int, default=0, help="begin the sequence of trials at this trial number (a fresh context)")
+    ap.add_argument("--out", default=None, help="also write the trial counts here (JSON)")
     a = ap.parse_args()
     START_TRIAL = a.start
     c = run(a.seed, a.minutes, None, a.families, a.only)
     print("fuzz_parity: seed %d, %d trials OK in %.1f min %s" % (a.seed, sum(c.values()), a.minutes, c), flush=True)
+    if a.out:
+        import json
+        with open(a.out, "w") as fh:
+            json.dump({"seed": a.seed, "minutes": a.minutes, "families": a.families, "trials": c}, fh)

@@ -7,6 +7,7 @@
 #include "x3_decode_blocks_kernel.h"
 #include "x3_index_kernels.h"
 #include "x3_decode_mc_kernel.h"
+#include "x3_decode_window_kernel.h"
 
 // ------------------------------------------------------------------------------------------------
 // decode
@@ -1001,5 +1002,100 @@ extern "C" int x3_place_buffers(x3_ctx* c, const int16_t* d_wav, uint64_t n, con
       ms_per_step[(size_t)i * n_backs + j] = std::chrono::duration<double, std::milli>(t1 - t0).count() / steps;
     }
   }
+  return X3_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// random access: sample offsets and windows (x3_decode_window_kernel.h)
+// ------------------------------------------------------------------------------------------------
+extern "C" int x3_sample_offsets_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
+                                     uint64_t n_frames, uint64_t* d_sample_offsets) {
+  if (!c || !d_x3 || !d_frame_offsets || !d_sample_offsets) return X3_ERR_BAD_ARG;
+  if ((reinterpret_cast<uintptr_t>(d_x3) & 3u) || (reinterpret_cast<uintptr_t>(d_frame_offsets) & 7u) ||
+      (reinterpret_cast<uintptr_t>(d_sample_offsets) & 7u))
+    return X3_ERR_BAD_ARG;
+  if (n_frames == 0 || n_frames > 0x7FFFFFFFull) return X3_ERR_BAD_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  hipLaunchKernelGGL(x3_window_sample_offsets_kernel, dim3(1), dim3(1024), 0, c->stream, d_x3, x3_len, d_frame_offsets,
+                     n_frames, d_sample_offsets);
+  HIPCHK(c, hipGetLastError());
+  return X3_OK;
+}
+
+extern "C" int x3_decode_windows_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
+                                     const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
+                                     const uint64_t* d_seg_index, uint32_t seg_blocks, const uint64_t* d_starts,
+                                     uint64_t n_windows, uint32_t window_len, void* d_out, int out_format, int32_t* d_status) {
+  if (!c || !d_x3 || !d_frame_offsets || !d_sample_offsets || !p || !d_starts || !d_out || !d_status) return X3_ERR_BAD_ARG;
+  if (window_len == 0 || n_windows == 0 || n_windows > (1ull << 40)) return X3_ERR_BAD_ARG;
+  if (out_format != X3_WINDOW_I16 && out_format != X3_WINDOW_F32) return X3_ERR_BAD_ARG;
+  const uint64_t esz = out_format == X3_WINDOW_F32 ? 4u : 2u;
+  if (reinterpret_cast<uintptr_t>(d_out) % esz) return X3_ERR_BAD_ARG;
+  if ((reinterpret_cast<uintptr_t>(d_x3) & 3u) || (reinterpret_cast<uintptr_t>(d_frame_offsets) & 7u) ||
+      (reinterpret_cast<uintptr_t>(d_sample_offsets) & 7u) || (reinterpret_cast<uintptr_t>(d_starts) & 7u) ||
+      (reinterpret_cast<uintptr_t>(d_status) & 3u))
+    return X3_ERR_BAD_ARG;
+  if (d_seg_index && (seg_blocks == 0 || (seg_blocks & 3u) || seg_blocks > 3200u || (reinterpret_cast<uintptr_t>(d_seg_index) & 7u)))
+    return X3_ERR_BAD_ARG;
+  if (n_frames == 0 || n_frames > 0x7FFFFFFFull) return X3_ERR_BAD_ARG;
+  X3DevParams dp;
+  const uint64_t spf = spf_of(p);
+  int rc = derive(p, spf > 0xFFFFFFFFull ? 0 : spf, &dp);
+  if (rc) return rc;
+  if (dp.block_len == 0 || dp.blocks_per_frame == 0) return X3_ERR_BAD_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  // the stretches of a frame as the index tells them apart (x3_seg_index_entries); 1 = whole frames
+  const uint64_t nidx = d_seg_index ? ((uint64_t)dp.blocks_per_frame + seg_blocks - 1) / seg_blocks : 1;
+  const uint32_t nseg = nidx >= 2 ? (uint32_t)nidx : 1u;
+  const uint2* idx = nseg >= 2 ? reinterpret_cast<const uint2*>(d_seg_index) : nullptr;
+  // workspace: plans, the two scans, per-frame verdicts, a block of replay scratch per window, the summary
+  const uint64_t n = n_windows;
+  const uint32_t scratch_per = (dp.block_len + 7u) & ~7u;
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t o_plan = 0, o_cov = up(o_plan + n * sizeof(X3WinPlan)), o_item = up(o_cov + (n + 1) * 8),
+               o_fst = up(o_item + (n + 1) * 8), o_scr = up(o_fst + n_frames * 4), o_sum = up(o_scr + n * scratch_per * 2),
+               total = o_sum + sizeof(X3WinSummary);
+  if ((rc = ensure(c, c->win_ws, total))) return rc;
+  char* const ws = (char*)c->win_ws.p;
+  X3WinPlan* plan = (X3WinPlan*)(ws + o_plan);
+  unsigned long long* cov_off = (unsigned long long*)(ws + o_cov);
+  unsigned long long* item_off = (unsigned long long*)(ws + o_item);
+  int32_t* fst = (int32_t*)(ws + o_fst);
+  int16_t* scratch = (int16_t*)(ws + o_scr);
+  X3WinSummary* sum = (X3WinSummary*)(ws + o_sum);
+  // grids: the plan covers the windows; the grid-stride kernels take as many groups as the work of full-length frames needs,
+  // at most X3W_GRID_LIMIT (their counts are on the device)
+  const uint64_t frames_per = (uint64_t)window_len / (spf ? spf : 1) + 2;
+  auto groups = [&](uint64_t units, uint64_t per_group) {
+    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((units + per_group - 1) / per_group, X3W_GRID_LIMIT));
+  };
+  hipLaunchKernelGGL(x3_window_plan_kernel, dim3(groups(n, 256)), dim3(256), 0, c->stream, d_sample_offsets, n_frames,
+                     d_starts, n, window_len, plan, sum);
+  hipLaunchKernelGGL(x3_window_scan_kernel, dim3(1), dim3(1024), 0, c->stream, plan, n, idx, seg_blocks, nseg, cov_off, item_off);
+  hipLaunchKernelGGL(x3_window_check_kernel, dim3(groups(n * frames_per, 4)), dim3(256), 0, c->stream, d_x3, x3_len,
+                     d_frame_offsets, d_sample_offsets, plan, n, cov_off, fst);
+  hipLaunchKernelGGL(x3_window_decode_kernel, dim3(groups(n * frames_per * nseg, 256)), dim3(256), 0, c->stream, d_x3, x3_len,
+                     d_frame_offsets, d_sample_offsets, d_starts, plan, n, window_len, item_off, dp, idx, seg_blocks, nseg,
+                     d_out, out_format, fst);
+  hipLaunchKernelGGL(x3_window_fixup_kernel, dim3(groups(n, 4)), dim3(256), 0, c->stream, d_x3, d_frame_offsets,
+                     d_sample_offsets, d_starts, plan, n, window_len, dp, fst, d_out, out_format, d_status, scratch,
+                     scratch_per, sum);
+  HIPCHK(c, hipGetLastError());
+  c->windows_pending = true;
+  c->win_windows = n;
+  c->win_sum_off = o_sum;
+  return X3_OK;
+}
+
+extern "C" int x3_decode_windows_result(x3_ctx* c, uint64_t* n_bad, uint64_t* first_bad, int* first_bad_status) {
+  if (!c || !c->windows_pending) return X3_ERR_BAD_ARG;
+  X3WinSummary h{0, 0};
+  HIPCHK(c, hipMemcpyAsync(&h, (char*)c->win_ws.p + c->win_sum_off, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->windows_pending = false;
+  const bool any = h.n_bad != 0;
+  if (n_bad) *n_bad = h.n_bad;
+  if (first_bad) *first_bad = any ? (h.first >> 8) : c->win_windows;
+  if (first_bad_status) *first_bad_status = any ? (int)(h.first & 0xFFu) : 0;
   return X3_OK;
 }

@@ -1,0 +1,497 @@
+// x3_decode_window_kernel.h -- random access: batches of sample windows from a device-resident stream (x3_decode_windows_dev).
+//
+// A window is the samples at positions [start, start + L) of the stream, position = sample_offsets[f] + i for sample i of
+// frame f.  The work of a call follows the windows, not the stream: per window, the frames that cover it, and per frame
+// its stretches of the segment index.  Five launches, nothing comes back to the host in between (every count lives in the
+// workspace and the later kernels walk it grid-stride):
+//
+//  x3_window_plan_kernel    -- a thread per window: the start is checked against the total (sample_offsets[F]), the
+//      covering frames [fa, fb] are found by binary search.  A window off the end is X3_ERR_BAD_ARG and covers nothing.
+//  x3_window_scan_kernel    -- one workgroup: exclusive scans of the covering frames and of the work items per window.
+//  x3_window_check_kernel   -- a WAVE per (window, covering frame): header (x3_frame_header_check_words), payload CRC as a
+//      segmented reduction over the wave, `samples` against sample_offsets[f + 1] - sample_offsets[f].  The verdict goes
+//      to the frame's word of a per-frame array (every window that covers the frame writes the same word).
+//  x3_window_decode_kernel  -- a LANE per (window, covering frame, stretch).  A stretch starts at block 0 or at a usable
+//      index entry and runs to the next usable entry, where it compares its end -- bit position and last sample -- with
+//      that entry (x3_decode_split_kernel.h, "STRETCHES"): by induction from block 0 the frame then decodes as the serial
+//      walk does.  Every stretch of every covering frame runs, also those outside the window: they are the proof chain of
+//      the stretches inside it, and a frame's verdict (decode errors behind the window included) is the whole frame's.
+//      Only samples inside the window are stored.  Without an index a frame is one stretch: one lane, serially.
+//  x3_window_fixup_kernel   -- a wave per window, in frame order: a frame that a stretch has flagged (contradicted entry,
+//      decode error, zero run of 32 bits or more, a read behind the payload) goes through the reference's reader
+//      (x3_replay_block, x3_decode_replay.h), which rewrites its in-window samples.  At the first frame that fails the
+//      window's status is set and the rest of the row is zeroed.
+//
+// Nothing here trusts the caller's offsets, starts or index: every stream read is bounds-checked against x3_len (a
+// partial last dword is read byte by byte), every store is at a row position in [0, L).
+#pragma once
+#include "x3_device.h"
+#include "x3_decode_kernel.h"
+#include "x3_decode_replay.h"
+#include "x3_decode_split_kernel.h"   // X3S_SEG_MAGIC, X3S_SEG_VALID: the segment index
+
+// (X3_WINDOW_I16 / X3_WINDOW_F32: include/x3hip.h)
+#define X3W_FLAG 0x10000      // per-frame word: a stretch has flagged the frame for the reference's reader
+#define X3W_GRID_LIMIT 4096u  // workgroups of the grid-stride kernels
+
+struct X3WinPlan {
+  uint64_t fa;     // first covering frame
+  uint32_t ncov;   // covering frames (0: the window is off the end)
+  int32_t status;  // X3D_OK or X3D_BAD_ARG from the plan
+};
+
+// the windows' summary: n_bad and min(w << 8 | status) over the bad windows
+struct X3WinSummary {
+  unsigned long long n_bad;
+  unsigned long long first;
+};
+
+// stream dword j (bytes 4j .. 4j+3) as a big-endian value, bytes at or beyond len read as zero
+__device__ __forceinline__ uint32_t x3w_be_dword(const uint8_t* __restrict__ x3, uint64_t len, uint64_t j) {
+  const uint64_t b = j << 2;
+  if (b + 4u <= len) return x3_bswap32(reinterpret_cast<const uint32_t*>(x3)[j]);
+  uint32_t v = 0;
+  for (uint32_t k = 0; k < 4u; ++k)
+    if (b + k < len) v |= (uint32_t)x3[b + k] << (24u - 8u * k);
+  return v;
+}
+
+// 4 stream bytes at byte offset o, big-endian (zero beyond len)
+__device__ __forceinline__ uint32_t x3w_be32_at(const uint8_t* __restrict__ x3, uint64_t len, uint64_t o) {
+  const uint32_t sh = (uint32_t)(o & 3u) * 8u;
+  const uint32_t a = x3w_be_dword(x3, len, o >> 2);
+  if (sh == 0) return a;
+  return (a << sh) | (x3w_be_dword(x3, len, (o >> 2) + 1u) >> (32u - sh));
+}
+
+// MSB-first bit reader over the stream at an absolute bit position: a 64-bit window with at least 32 valid bits after every
+// refill, fed from four stream dwords loaded together.  On gfx9 a wave's stores count in the same vmcnt as its loads, so a
+// refill waits for every sample stored before it: one wait per 128 bits instead of per 32 (measured: the kernel of a single
+// window: 0.82 ms with a refill per dword, profiles/windows/).  Reads behind the payload are not refused
+// here (the bits are the stream's, or zero behind len); the caller compares the position with the payload's end, as the fast
+// decoders do (x3_decode_replay.h).
+struct X3WinBits {
+  const uint8_t* x3;
+  uint64_t len;
+  uint64_t win;   // bits [pos, pos + nv) in the top nv bits
+  uint64_t pos;   // absolute bit position of the next bit
+  uint64_t nxt;   // next dword to load
+  uint32_t nv;
+  uint32_t q0, q1, q2, q3, nq;   // loaded dwords not yet in the window (big-endian values), nq of them
+  __device__ __forceinline__ void open(const uint8_t* s, uint64_t n, uint64_t bitpos) {
+    x3 = s;
+    len = n;
+    pos = bitpos;
+    const uint64_t j = bitpos >> 5;
+    const uint32_t sh = (uint32_t)(bitpos & 31u);
+    win = (((uint64_t)x3w_be_dword(s, n, j) << 32) | x3w_be_dword(s, n, j + 1u)) << sh;
+    nv = 64u - sh;
+    nxt = j + 2u;
+    nq = 0;
+  }
+  __device__ __forceinline__ void load4() {
+    if ((nxt + 4u) * 4u <= len) {
+      const uint32_t* w = reinterpret_cast<const uint32_t*>(x3) + nxt;
+      q0 = x3_bswap32(w[0]); q1 = x3_bswap32(w[1]); q2 = x3_bswap32(w[2]); q3 = x3_bswap32(w[3]);
+    } else {
+      q0 = x3w_be_dword(x3, len, nxt); q1 = x3w_be_dword(x3, len, nxt + 1u);
+      q2 = x3w_be_dword(x3, len, nxt + 2u); q3 = x3w_be_dword(x3, len, nxt + 3u);
+    }
+    nxt += 4u;
+    nq = 4u;
+  }
+  __device__ __forceinline__ void fill() {
+    if (nv < 32u) {
+      if (nq == 0u) load4();
+      win |= (uint64_t)q0 << (32u - nv);
+      nv += 32u;
+      q0 = q1; q1 = q2; q2 = q3;
+      --nq;
+    }
+  }
+  __device__ __forceinline__ uint32_t bits(uint32_t n) {  // 1 <= n <= 16
+    fill();
+    const uint32_t r = (uint32_t)(win >> (64u - n));
+    win <<= n;
+    nv -= n;
+    pos += n;
+    return r;
+  }
+  // the zero run in front of the next one bit; 32 or more -> `run32` (the reference's reader differs there)
+  __device__ __forceinline__ uint32_t zeros(bool& run32) {
+    fill();
+    const uint32_t top = (uint32_t)(win >> 32);
+    if (top == 0u) {
+      run32 = true;
+      return 0u;
+    }
+    const uint32_t z = (uint32_t)__clz(top);
+    win <<= z;
+    nv -= z;
+    pos += z;
+    return z;
+  }
+};
+
+// decoder::decode_block over X3WinBits: x3_replay_block's arithmetic.  Returns false where the reference's reader may
+// disagree or the block is an error -- the frame then goes to x3_replay_frame's loop.  Sample i of the block is handed
+// to put(i, value).
+template <class Put>
+__device__ __forceinline__ bool x3w_block(X3WinBits& br, uint32_t n, const X3DevParams& p, uint32_t& last, Put put) {
+  const uint32_t ftype = br.bits(2u);
+  bool run32 = false;
+  if (ftype == 0u) {
+    const uint32_t E = br.bits(4u) + 1u;
+    if (E <= 5u || n == 0u) return false;
+    if (E == 16u) {
+      for (uint32_t i = 0; i < n; ++i) {
+        last = br.bits(16u) & 0xFFFFu;
+        put(i, last);
+      }
+    } else {
+      const uint32_t half = 1u << (E - 1u);
+      for (uint32_t i = 0; i < n; ++i) {
+        uint32_t v = br.bits(E) & 0xFFFFu;
+        if (v > half) v -= half << 1;
+        last = (last + v) & 0xFFFFu;
+        put(i, last);
+      }
+    }
+  } else if (ftype == 1u) {
+    const uint32_t bound = p.inv_len[0];
+    for (uint32_t i = 0; i < n; ++i) {
+      const uint32_t ix = br.zeros(run32);
+      if (run32) return false;
+      (void)br.bits(1u);
+      if (ix >= bound) return false;
+      const uint32_t d = (ix & 1u) ? 0u - ((ix + 1u) >> 1) : (ix >> 1);
+      last = (last + d) & 0xFFFFu;
+      put(i, last);
+    }
+  } else {
+    const uint32_t nb = ftype == 2u ? 2u : 4u;
+    const int32_t level = 1 << p.k[ftype - 1u];
+    const uint32_t bound = p.inv_len[ftype - 1u];
+    for (uint32_t i = 0; i < n; ++i) {
+      const int32_t nz = (int32_t)br.zeros(run32);
+      if (run32) return false;
+      const int32_t r = (int32_t)(int16_t)br.bits(nb);
+      const int32_t ix = (int32_t)(int16_t)(r + level * (nz - 1));
+      if (ix < 0 || (uint32_t)ix >= bound) return false;
+      const uint32_t u = (uint32_t)ix;
+      const uint32_t d = (u & 1u) ? 0u - ((u + 1u) >> 1) : (u >> 1);
+      last = (last + d) & 0xFFFFu;
+      put(i, last);
+    }
+  }
+  return true;
+}
+
+__device__ __forceinline__ void x3w_store(void* __restrict__ out, int fmt, uint64_t at, uint32_t v) {
+  if (fmt == X3_WINDOW_F32) reinterpret_cast<float*>(out)[at] = (float)(int16_t)(uint16_t)v * (1.0f / 32768.0f);
+  else reinterpret_cast<int16_t*>(out)[at] = (int16_t)(uint16_t)v;
+}
+
+// index header: {X3S_SEG_MAGIC, blocks per entry}; anything else (or no index) = decode frames whole
+__device__ __forceinline__ bool x3w_index_ok(const uint2* __restrict__ idx, uint32_t sb) {
+  if (!idx || sb == 0u) return false;
+  const uint2 h = idx[0];
+  return h.x == X3S_SEG_MAGIC && h.y == sb;
+}
+
+// largest f in [lo, hi) with so[f] <= x, given so[lo] <= x < so[hi]
+__device__ __forceinline__ uint64_t x3w_search(const uint64_t* __restrict__ so, uint64_t lo, uint64_t hi, uint64_t x) {
+  while (hi - lo > 1u) {
+    const uint64_t mid = lo + ((hi - lo) >> 1);
+    if (so[mid] <= x) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// largest w with off[w] <= i (off[0] = 0, non-decreasing, n + 1 entries)
+__device__ __forceinline__ uint64_t x3w_owner(const unsigned long long* __restrict__ off, uint64_t n, uint64_t i) {
+  uint64_t lo = 0, hi = n;
+  while (hi - lo > 1u) {
+    const uint64_t mid = lo + ((hi - lo) >> 1);
+    if (off[mid] <= i) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// ---- sample offsets: so[f] = exclusive prefix of the headers' `samples` (0 for a header that is not inside the stream),
+// so[F] = the total.  One workgroup of 1024: a contiguous run of frames per thread, a workgroup scan of the runs' sums.
+__device__ __forceinline__ unsigned long long x3w_block_excl_scan(unsigned long long v, unsigned long long* s, unsigned long long* total) {
+  const uint32_t t = threadIdx.x, n = blockDim.x;
+  s[t] = v;
+  __syncthreads();
+  for (uint32_t d = 1; d < n; d <<= 1) {
+    const unsigned long long a = t >= d ? s[t - d] : 0ull;
+    __syncthreads();
+    s[t] += a;
+    __syncthreads();
+  }
+  const unsigned long long incl = s[t];
+  *total = s[n - 1];
+  __syncthreads();
+  return incl - v;
+}
+
+__device__ __forceinline__ uint32_t x3w_header_samples(const uint8_t* __restrict__ x3, uint64_t len, uint64_t off) {
+  if (len < 20u || off > len - 20u) return 0u;
+  return ((uint32_t)x3[off + 4u] << 8) | x3[off + 5u];
+}
+
+__global__ void __launch_bounds__(1024)
+x3_window_sample_offsets_kernel(const uint8_t* __restrict__ x3, uint64_t len, const uint64_t* __restrict__ frame_off,
+                                uint64_t F, uint64_t* __restrict__ so) {
+  __shared__ unsigned long long s[1024];
+  const uint64_t per = (F + blockDim.x - 1) / blockDim.x;
+  const uint64_t a = min((uint64_t)threadIdx.x * per, F), b = min(a + per, F);
+  unsigned long long sum = 0;
+  for (uint64_t f = a; f < b; ++f) sum += x3w_header_samples(x3, len, frame_off[f]);
+  unsigned long long total;
+  unsigned long long run = x3w_block_excl_scan(sum, s, &total);
+  for (uint64_t f = a; f < b; ++f) {
+    so[f] = run;
+    run += x3w_header_samples(x3, len, frame_off[f]);
+  }
+  if (threadIdx.x == 0) so[F] = total;
+}
+
+// ---- plan: a thread per window
+__global__ void __launch_bounds__(256)
+x3_window_plan_kernel(const uint64_t* __restrict__ so, uint64_t F, const uint64_t* __restrict__ starts, uint64_t n_windows,
+                      uint32_t L, X3WinPlan* __restrict__ plan, X3WinSummary* __restrict__ sum) {
+  const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (w == 0) {
+    sum->n_bad = 0;
+    sum->first = ~0ull;
+  }
+  if (w >= n_windows) return;
+  const uint64_t start = starts[w], total = so[F];
+  X3WinPlan pl{0, 0, X3D_BAD_ARG};
+  // (so[0] <= start and so[F] > start + L - 1 are the search's invariants; offsets that break them are not this stream's)
+  if (L <= total && start <= total - L && so[0] <= start) {
+    const uint64_t e = start + (L - 1u);
+    const uint64_t fa = x3w_search(so, 0, F, start);
+    const uint64_t fb = x3w_search(so, fa, F, e);
+    // more covering frames than samples: a frame of 0 samples or offsets out of order, no stream's frames
+    if (fb - fa < (uint64_t)L) pl = X3WinPlan{fa, (uint32_t)(fb - fa + 1u), X3D_OK};
+  }
+  plan[w] = pl;
+}
+
+// ---- exclusive scans of the covering frames (cov) and the work items (cov * stretches) per window; n + 1 entries each
+__global__ void __launch_bounds__(1024)
+x3_window_scan_kernel(const X3WinPlan* __restrict__ plan, uint64_t n, const uint2* __restrict__ idx, uint32_t sb, uint32_t nseg,
+                      unsigned long long* __restrict__ cov_off, unsigned long long* __restrict__ item_off) {
+  __shared__ unsigned long long s[1024];
+  const uint32_t ns = x3w_index_ok(idx, sb) ? nseg : 1u;
+  const uint64_t per = (n + blockDim.x - 1) / blockDim.x;
+  const uint64_t a = min((uint64_t)threadIdx.x * per, n), b = min(a + per, n);
+  unsigned long long c = 0;
+  for (uint64_t w = a; w < b; ++w) c += plan[w].ncov;
+  unsigned long long total;
+  unsigned long long run = x3w_block_excl_scan(c, s, &total);
+  for (uint64_t w = a; w < b; ++w) {
+    cov_off[w] = run;
+    item_off[w] = run * ns;
+    run += plan[w].ncov;
+  }
+  if (threadIdx.x == 0) {
+    cov_off[n] = total;
+    item_off[n] = total * ns;
+  }
+}
+
+// ---- check: a wave per (window, covering frame)
+__global__ void __launch_bounds__(256)
+x3_window_check_kernel(const uint8_t* __restrict__ x3, uint64_t len, const uint64_t* __restrict__ frame_off,
+                       const uint64_t* __restrict__ so, const X3WinPlan* __restrict__ plan, uint64_t n_windows,
+                       const unsigned long long* __restrict__ cov_off, int32_t* __restrict__ fst) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t n_items = cov_off[n_windows];
+  const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+  for (uint64_t i = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); i < n_items; i += waves) {
+    const uint64_t w = x3w_owner(cov_off, n_windows, i);
+    const uint64_t f = plan[w].fa + (i - cov_off[w]);
+    const uint64_t off = frame_off[f];
+    uint32_t plen = 0, samples = 0, pcrc = 0;
+    int32_t st;
+    if (len < 20u || off > len - 20u) {
+      st = X3D_BAD_ARG;   // (the caller's offset is not inside this stream)
+    } else {
+      const uint32_t h0 = x3w_be32_at(x3, len, off), h1 = x3w_be32_at(x3, len, off + 4u);
+      const uint32_t h2 = x3w_be32_at(x3, len, off + 8u), h3 = x3w_be32_at(x3, len, off + 12u);
+      const uint32_t h4 = x3w_be32_at(x3, len, off + 16u);
+      uint32_t hc = 0xFFFFu;
+      hc = x3_crc_be32(hc, h0);
+      hc = x3_crc_be32(hc, h1);
+      hc = x3_crc_be32(hc, h2);
+      hc = x3_crc_be32(hc, h3);
+      st = x3_frame_header_check_words(h0, h1, h4, hc, len, off, plen, samples, pcrc);
+      if (st == X3D_STREAM_ENDS_IN_FRAME) st = X3D_BAD_ARG;
+    }
+    if (st == X3D_OK) {
+      // payload CRC: lane t CRCs a contiguous chunk with init 0, the chunks are joined by x^(8 * bytes behind them)
+      const uint64_t p0 = off + 20u;
+      const uint32_t chunk = (plen + 63u) >> 6;
+      const uint32_t a = min(lane * chunk, plen), b = min(a + chunk, plen);
+      uint32_t c = 0;
+      for (uint32_t k = a; k < b; ++k) c = x3_crc_byte(c, x3[p0 + k]);
+      // x^(8 * (plen - b)) by squaring; lane 0 also carries the init value 0xFFFF times x^(8 * plen)
+      auto xpow8 = [](uint32_t nbytes) -> uint32_t {
+        uint32_t r = 1u, base = 0x100u;
+        while (nbytes) {
+          if (nbytes & 1u) r = x3_gf_mul(r, base);
+          base = x3_gf_mul(base, base);
+          nbytes >>= 1;
+        }
+        return r;
+      };
+      uint32_t part = x3_gf_mul(c, xpow8(plen - b));
+      if (lane == 0) part ^= x3_gf_mul(0xFFFFu, xpow8(plen));
+#pragma unroll
+      for (int o = 32; o >= 1; o >>= 1) part ^= (uint32_t)__shfl_xor((int)part, o, X3_WAVE);
+      if ((part & 0xFFFFu) != pcrc) st = X3D_FRAME_HEADER_INVALID_PAYLOAD_CRC;
+    }
+    // what x3_decode_dev's decoders refuse behind the check, and the caller's offsets against the header
+    if (st == X3D_OK && (samples == 0u || plen < 2u)) st = X3D_BAD_ARG;
+    if (st == X3D_OK && (so[f + 1u] < so[f] || so[f + 1u] - so[f] != samples)) st = X3D_BAD_ARG;
+    if (lane == 0) fst[f] = st;
+  }
+}
+
+// ---- decode: a lane per (window, covering frame, stretch)
+__global__ void __launch_bounds__(256)
+x3_window_decode_kernel(const uint8_t* __restrict__ x3, uint64_t len, const uint64_t* __restrict__ frame_off,
+                        const uint64_t* __restrict__ so, const uint64_t* __restrict__ starts, const X3WinPlan* __restrict__ plan,
+                        uint64_t n_windows, uint32_t L, const unsigned long long* __restrict__ item_off, X3DevParams p,
+                        const uint2* __restrict__ idx, uint32_t sb, uint32_t nseg, void* __restrict__ out, int fmt,
+                        int32_t* __restrict__ fst) {
+  const bool segd = x3w_index_ok(idx, sb);
+  const uint32_t ns = segd ? nseg : 1u;
+  const uint32_t pitch = nseg - 1u;
+  const uint64_t n_items = item_off[n_windows];
+  const uint64_t lanes = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_items; i += lanes) {
+    const uint64_t w = x3w_owner(item_off, n_windows, i);
+    const uint64_t k = i - item_off[w];
+    const uint64_t f = plan[w].fa + k / ns;
+    const uint32_t j = (uint32_t)(k % ns);
+    if (fst[f] != X3D_OK) continue;   // (checked: header, CRC, sample count; a frame that failed is not decoded)
+    const uint64_t off = frame_off[f], p0 = off + 20u;
+    const uint32_t h1 = x3w_be32_at(x3, len, off + 4u);
+    const uint32_t samples = h1 >> 16, plen = h1 & 0xFFFFu;
+    const uint32_t nbf = (samples - 1u + p.block_len - 1u) / p.block_len;   // blocks of the frame
+    const uint2* const e = segd ? idx + 1 + f * (uint64_t)pitch : nullptr;
+    auto usable = [&](uint32_t q) -> bool {   // entry q (1 .. nseg-1) is one to start from / end at
+      if (sb * q >= nbf) return false;
+      const uint2 h = e[q - 1u];
+      return (h.y & X3S_SEG_VALID) && h.x >= 16u && h.x <= 8u * plen;
+    };
+    if (j && !usable(j)) continue;   // (the stretch in front runs through these blocks)
+    uint32_t q = j + 1u;             // the next usable entry, nseg if none
+    if (segd)
+      while (q < nseg && !usable(q)) ++q;
+    else
+      q = 1u;
+    const uint32_t b0 = sb * j;
+    const uint32_t b1 = (segd && q < nseg) ? sb * q : nbf;
+    const uint64_t rbase = w * (uint64_t)L, start = starts[w], fpos = so[f];
+    auto put_at = [&](uint32_t s, uint32_t v) {   // sample s of the frame
+      const uint64_t g = fpos + s;
+      if (g >= start && g - start < (uint64_t)L) x3w_store(out, fmt, rbase + (g - start), v);
+    };
+    uint32_t last;
+    X3WinBits br;
+    if (j == 0u) {
+      last = x3w_be32_at(x3, len, p0) >> 16;
+      put_at(0u, last);
+      br.open(x3, len, p0 * 8u + 16u);
+    } else {
+      const uint2 h = e[j - 1u];
+      last = h.y & 0xFFFFu;
+      br.open(x3, len, p0 * 8u + h.x);
+    }
+    const uint64_t end_bit = (p0 + plen) * 8u;
+    bool ok = true;
+    for (uint32_t b = b0; b < b1 && ok; ++b) {
+      const uint32_t s0 = 1u + b * p.block_len;
+      const uint32_t n = min(p.block_len, samples - s0);
+      ok = x3w_block(br, n, p, last, [&](uint32_t t, uint32_t v) { put_at(s0 + t, v); });
+      ok = ok && br.pos <= end_bit;
+    }
+    if (ok && segd && q < nseg) {
+      const uint2 h = e[q - 1u];
+      ok = br.pos - p0 * 8u == h.x && last == (h.y & 0xFFFFu);
+    }
+    if (!ok) atomicOr(&fst[f], X3W_FLAG);
+  }
+}
+
+// ---- fix-up: a wave per window, frames in order; scratch: a block's samples per window (x3_replay_block's output)
+__global__ void __launch_bounds__(256)
+x3_window_fixup_kernel(const uint8_t* __restrict__ x3, const uint64_t* __restrict__ frame_off, const uint64_t* __restrict__ so,
+                       const uint64_t* __restrict__ starts, const X3WinPlan* __restrict__ plan, uint64_t n_windows, uint32_t L,
+                       X3DevParams p, const int32_t* __restrict__ fst, void* __restrict__ out, int fmt,
+                       int32_t* __restrict__ status, int16_t* __restrict__ scratch, uint32_t scratch_per,
+                       X3WinSummary* __restrict__ sum) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+  for (uint64_t w = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); w < n_windows; w += waves) {
+    const X3WinPlan pl = plan[w];
+    const uint64_t start = starts[w], rbase = w * (uint64_t)L;
+    int32_t st = pl.status;
+    uint64_t zero_from = 0;   // (st != 0) the row from here on is zero
+    if (lane == 0 && st == X3D_OK) {
+      int16_t* const blk = scratch + w * (uint64_t)scratch_per;
+      for (uint64_t f = pl.fa; f < pl.fa + pl.ncov; ++f) {
+        int32_t fs = fst[f];
+        if (fs == X3W_FLAG) {
+          // decoder::decode_frame through the reference's reader (x3_replay_frame's loop), block by block into the scratch
+          const uint8_t* const payload = x3 + frame_off[f] + 20u;
+          const uint32_t samples = ((uint32_t)payload[-16] << 8) | payload[-15];
+          const uint32_t plen = ((uint32_t)payload[-14] << 8) | payload[-13];
+          const uint64_t fpos = so[f];
+          auto put_at = [&](uint32_t s, uint32_t v) {
+            const uint64_t g = fpos + s;
+            if (g >= start && g - start < (uint64_t)L) x3w_store(out, fmt, rbase + (g - start), v);
+          };
+          uint32_t last = ((uint32_t)payload[0] << 8) | payload[1];
+          put_at(0u, last);
+          X3RefReader br;
+          br.open(payload + 2, plen - 2u);
+          uint32_t at = 1u, remaining = samples - 1u;
+          fs = X3D_OK;
+          while (remaining && fs == X3D_OK) {
+            const uint32_t n = remaining < p.block_len ? remaining : p.block_len;
+            fs = x3_replay_block(br, n, p, last, blk);
+            if (fs == X3D_OK)
+              for (uint32_t t = 0; t < n; ++t) put_at(at + t, (uint16_t)blk[t]);
+            remaining -= n;
+            at += n;
+          }
+        }
+        if (fs != X3D_OK) {
+          st = fs;
+          zero_from = so[f] > start ? min(so[f] - start, (uint64_t)L) : 0u;
+          break;
+        }
+      }
+    }
+    st = __shfl(st, 0, X3_WAVE);
+    zero_from = (uint64_t)__shfl((long long)zero_from, 0, X3_WAVE);
+    if (st != X3D_OK)
+      for (uint64_t t = zero_from + lane; t < L; t += 64u) x3w_store(out, fmt, rbase + t, 0u);
+    if (lane == 0) {
+      status[w] = st;
+      if (st != X3D_OK) {
+        atomicAdd(&sum->n_bad, 1ull);
+        atomicMin(&sum->first, (unsigned long long)(w << 8) | (uint32_t)st);
+      }
+    }
+  }
+}

@@ -147,6 +147,7 @@ struct x3_ctx {
   DevBuf in_more[2], out_more[2];  // x3_decode_stream on a long host buffer: rings of three buffers on either side of the decoder
   DevBuf idx_cand, idx_keys, idx_vals, idx_J, idx_S, idx_L, idx_sum;  // x3_index_dev scratch
   DevBuf idx_wg, idx_sorted, idx_scan;  // ... of its fast path: candidates per scanning workgroup, in order, the scans
+  DevBuf win_ws;   // x3_decode_windows_dev: plans, scans, per-frame verdicts, replay scratch, summary (x3_decode_window_kernel.h)
   unsigned long long index_fast = 0, index_general = 0;  // walks that the fast path / the general path have served (options)
   int n_cus = 0;
   bool force_single_wave_decode = false;
@@ -155,6 +156,9 @@ struct x3_ctx {
   uint64_t stream_wg_key = 0; // ... of which instantiation with how much LDS (block length, table form, bytes)
   // bookkeeping of the last async calls
   bool encode_pending = false, decode_pending = false;
+  bool windows_pending = false;    // x3_decode_windows_dev: its own pending state (x3_decode_result is not touched)
+  uint64_t win_windows = 0;        // ... its window count and where its summary lies in win_ws
+  size_t win_sum_off = 0;
   bool force_two_pass = false;
   // Contexts that encode concurrently on ONE GPU (the file pipeline's workers) share this gate: the single-pass encoders
   // are persistent grids whose workgroups wait for each other, so only one of them may be in flight on a device.  A

@@ -687,6 +687,37 @@ inline X3Error decode(Context& ctx, const EncodedStream& s, const Parameters& pa
   return static_cast<X3Error>(st);
 }
 
+// Random access (x3_decode_windows_dev): n_windows windows of window_len samples, window w = positions [d_starts[w], d_starts[w] +
+// window_len) of the stream, as rows of d_out (X3_WINDOW_I16 / X3_WINDOW_F32); d_status[w] = 0 or the first failing covering
+// frame's status.  The stream's sample offsets are made once (sample_offsets); the segment index, where the stream has one,
+// is the hint the stretches start from.  Waits for the call: res = windows with status != 0, the first, its status.
+struct WindowsResult {
+  uint64_t n_bad = 0, first_bad = 0;
+  int first_bad_status = 0;
+};
+inline X3Error sample_offsets(Context& ctx, const EncodedStream& s, Buffer* d_sample_offsets) {
+  if (!d_sample_offsets || !s.bytes.ok() || !s.frame_offsets.ok()) return X3Error::BadArg;
+  *d_sample_offsets = Buffer(ctx, 8 * (s.n_frames + 1));
+  if (!d_sample_offsets->ok()) return X3Error::Hip;
+  return static_cast<X3Error>(x3_sample_offsets_dev(ctx.raw(), s.bytes.as<uint8_t>(), s.len, s.frame_offsets.as<uint64_t>(),
+                                                    s.n_frames, d_sample_offsets->as<uint64_t>()));
+}
+inline X3Error decode_windows(Context& ctx, const EncodedStream& s, const Parameters& params, const Buffer& d_sample_offsets,
+                              const uint64_t* d_starts, size_t n_windows, uint32_t window_len, void* d_out, int out_format,
+                              int32_t* d_status, WindowsResult* res) {
+  if (!s.bytes.ok() || !s.frame_offsets.ok() || !d_sample_offsets.ok()) return X3Error::BadArg;
+  const x3_params c = params.c_params();
+  int rc = x3_decode_windows_dev(ctx.raw(), s.bytes.as<uint8_t>(), s.len, s.frame_offsets.as<uint64_t>(),
+                                 d_sample_offsets.as<uint64_t>(), s.n_frames, &c,
+                                 s.seg_blocks ? s.seg_index.as<uint64_t>() : nullptr, s.seg_blocks, d_starts, n_windows,
+                                 window_len, d_out, out_format, d_status);
+  if (rc != X3_OK) return static_cast<X3Error>(rc);
+  WindowsResult r;
+  rc = x3_decode_windows_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status);
+  if (res) *res = r;
+  return static_cast<X3Error>(rc);
+}
+
 // Placement (x3_place_buffers; profiles/r6/decoder_modes.txt): the round trip timed on every pair of candidate buffers --
 // ms[i * backs.size() + j] for (streams[i], backs[j]).  A pipeline that keeps its buffers calls this once and keeps the
 // pair that runs best; what it does not keep it frees.

@@ -121,6 +121,13 @@ pub mod ffi {
                                  batch: *const x3_batch, d_wav_offsets: *const u64, p: *const x3_params, d_wav: *mut i16,
                                  wav_cap: u64, d_status: *mut i32, d_seg_index: *mut u64, seg_blocks: u32, record: c_int) -> c_int;
         pub fn x3_decode_result(ctx: *mut x3_ctx, first_bad: *mut u64, first_bad_status: *mut c_int, samples_before: *mut u64) -> c_int;
+        pub fn x3_sample_offsets_dev(ctx: *mut x3_ctx, d_x3: *const u8, x3_len: u64, d_frame_offsets: *const u64, n_frames: u64,
+                                     d_sample_offsets: *mut u64) -> c_int;
+        pub fn x3_decode_windows_dev(ctx: *mut x3_ctx, d_x3: *const u8, x3_len: u64, d_frame_offsets: *const u64,
+                                     d_sample_offsets: *const u64, n_frames: u64, p: *const x3_params, d_seg_index: *const u64,
+                                     seg_blocks: u32, d_starts: *const u64, n_windows: u64, window_len: u32, d_out: *mut c_void,
+                                     out_format: c_int, d_status: *mut i32) -> c_int;
+        pub fn x3_decode_windows_result(ctx: *mut x3_ctx, n_bad: *mut u64, first_bad: *mut u64, first_bad_status: *mut c_int) -> c_int;
         pub fn x3_place_buffers(ctx: *mut x3_ctx, d_wav: *const i16, n: u64, p: *const x3_params, d_streams: *const *mut u8,
                                 n_streams: u32, cap: u64, d_frame_offsets: *mut u64, d_backs: *const *mut i16, n_backs: u32,
                                 warm: u32, steps: u32, ms_per_step: *mut f64) -> c_int;
@@ -1133,6 +1140,45 @@ pub mod device {
         error::check(unsafe { ffi::x3_decode_result(gpu.raw(), &mut first_bad, &mut st, &mut before) })?;
         error::check(st)?;
         Ok(before as usize)
+    }
+
+    /// output formats of `decode_windows`: int16 samples, or float32 = s / 32768 (exact)
+    pub const WINDOW_I16: i32 = 0;
+    pub const WINDOW_F32: i32 = 1;
+
+    /// the stream's sample offsets (`x3_sample_offsets_dev`): `n_frames + 1` words, frame f's first sample and the total last
+    pub fn sample_offsets<'g>(gpu: &'g Gpu, s: &EncodedStream<'g>) -> error::Result<Buffer<'g>> {
+        let so = Buffer::new(gpu, 8 * (s.n_frames + 1))?;
+        error::check(unsafe {
+            ffi::x3_sample_offsets_dev(gpu.raw(), s.bytes.as_ptr::<u8>(), s.len as u64, s.frame_offsets.as_ptr::<u64>(), s.n_frames as u64,
+                                       so.as_ptr::<u64>())
+        })?;
+        Ok(so)
+    }
+
+    /// Random access (`x3_decode_windows_dev`; not in the reference crate, whose reader goes frame after frame): `n_windows`
+    /// windows of `window_len` samples, window w = positions `[starts[w], starts[w] + window_len)` (`d_starts`: device u64s) as
+    /// rows of `d_out` (`WINDOW_I16` / `WINDOW_F32`), `d_status[w]` = 0 or the first failing covering frame's status.  By the
+    /// segment index when the stream has one.  Waits: -> (windows with status != 0, the first of them, its status)
+    #[allow(clippy::too_many_arguments)]
+    pub fn decode_windows<'g>(gpu: &'g Gpu, s: &EncodedStream<'g>, params: &x3::Parameters, sample_offsets: &Buffer<'g>,
+                              d_starts: &Buffer<'g>, n_windows: usize, window_len: u32, d_out: &mut Buffer<'g>, out_format: i32,
+                              d_status: &mut Buffer<'g>) -> error::Result<(u64, u64, i32)> {
+        let esz = if out_format == WINDOW_F32 { 4 } else { 2 };
+        if d_starts.len() < 8 * n_windows || d_out.len() < esz * n_windows * window_len as usize || d_status.len() < 4 * n_windows {
+            return Err(X3Error::BadArg);
+        }
+        let p = params.c()?;
+        let idx = match &s.seg_index { Some(i) => i.as_ptr::<u64>() as *const u64, None => core::ptr::null() };
+        error::check(unsafe {
+            ffi::x3_decode_windows_dev(gpu.raw(), s.bytes.as_ptr::<u8>(), s.len as u64, s.frame_offsets.as_ptr::<u64>(),
+                                       sample_offsets.as_ptr::<u64>(), s.n_frames as u64, &p, idx, s.seg_blocks,
+                                       d_starts.as_ptr::<u64>(), n_windows as u64, window_len, d_out.as_ptr::<c_void>(), out_format,
+                                       d_status.as_ptr::<i32>())
+        })?;
+        let (mut n_bad, mut first_bad, mut st) = (0u64, 0u64, 0);
+        error::check(unsafe { ffi::x3_decode_windows_result(gpu.raw(), &mut n_bad, &mut first_bad, &mut st) })?;
+        Ok((n_bad, first_bad, st))
     }
 
     /// Placement (`x3_place_buffers`; profiles/r6/decoder_modes.txt): the round trip timed on every pair of candidate buffers --

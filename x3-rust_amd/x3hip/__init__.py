@@ -56,7 +56,10 @@ SYMBOLS = [
     "x3_mgpu_create", "x3_mgpu_destroy", "x3_mgpu_devices", "x3_mgpu_ctx", "x3_mgpu_shard", "x3_mgpu_last_error",
     "x3_mgpu_encode", "x3_mgpu_decode_stream",
     "x3_encode_mc", "x3_decode_stream_mc",
+    "x3_sample_offsets_dev", "x3_decode_windows_dev", "x3_decode_windows_result",
 ]
+
+WINDOW_I16, WINDOW_F32 = 0, 1   # x3_decode_windows_dev output formats
 
 
 class RiceCode(C.Structure):
@@ -189,6 +192,9 @@ def lib():
     L.x3_decode_dev_seg.argtypes = [vp, vp, u64, vp, u64, C.POINTER(Batch), vp, PP, vp, u64, vp, vp, u32, i32]
     L.x3_index_dev.argtypes = [vp, vp, u64, u64, vp, vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(i32)]
     L.x3_decode_stream_dev.argtypes = [vp, vp, u64, PP, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+    L.x3_sample_offsets_dev.argtypes = [vp, vp, u64, vp, u64, vp]
+    L.x3_decode_windows_dev.argtypes = [vp, vp, u64, vp, vp, u64, PP, vp, u32, vp, u64, u32, vp, i32, vp]
+    L.x3_decode_windows_result.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(i32)]
     L.x3_synth.argtypes = [i32, u64, u64, u64, vp]
     L.x3_synth_dev.argtypes = [vp, i32, u64, u64, u64, vp]
     L.x3_dev_alloc.argtypes = [vp, u64, C.POINTER(vp)]
@@ -777,6 +783,23 @@ class Context:
                                         C.byref(fok), C.byref(ferr))
         return rc, n.value, fok.value, ferr.value
 
+    def sample_offsets_dev(self, d_x3, x3_len, d_frame_offsets, n_frames, d_sample_offsets):
+        """x3_sample_offsets_dev: d_sample_offsets[0..n_frames] = exclusive prefix of the headers' sample counts"""
+        return lib().x3_sample_offsets_dev(self._h, d_x3, x3_len, d_frame_offsets, n_frames, d_sample_offsets)
+
+    def decode_windows_dev(self, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, params, d_starts, n_windows,
+                           window_len, d_out, out_format, d_status, d_seg_index=None, seg_blocks=0):
+        """x3_decode_windows_dev: n_windows rows of window_len samples (random access; asynchronous)"""
+        return lib().x3_decode_windows_dev(self._h, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames,
+                                           C.byref(params), d_seg_index, seg_blocks, d_starts, n_windows, window_len, d_out,
+                                           out_format, d_status)
+
+    def decode_windows_result(self):
+        """-> (rc, n_bad, first_bad, first_bad_status) of the last decode_windows_dev"""
+        nb, fb, st = C.c_uint64(0), C.c_uint64(0), C.c_int(0)
+        rc = lib().x3_decode_windows_result(self._h, C.byref(nb), C.byref(fb), C.byref(st))
+        return rc, nb.value, fb.value, st.value
+
     def synth_dev(self, kind, seed, start, n, d_out):
         rc = lib().x3_synth_dev(self._h, kind, seed, start, n, d_out)
         if rc:
@@ -837,3 +860,98 @@ class Context:
         if rc:
             raise X3Error(rc, "x3_dev_download: " + self.last_error())
         return out
+
+
+class WindowSource:
+    """Random access to one mono stream in HBM: windows of samples [start, start + length) as rows of a batch.
+
+    `stream`: host bytes (uploaded once) or (d_x3, x3_len) of a device stream.  Without `frame_offsets` (a device pointer to
+    n_frames + 1 byte offsets, with `n_frames`) the frames are found by x3_index_dev.  The sample offsets come from
+    x3_sample_offsets_dev.  Without `seg_index` one is recorded once by a decode with x3_decode_dev_seg(record=1); it is
+    only ever a hint (seg_blocks=0: no index, frames decode whole)."""
+
+    def __init__(self, ctx, stream, params=None, seg_blocks=32, frame_offsets=None, n_frames=None, seg_index=None):
+        self.ctx, self.params, self.seg_blocks = ctx, params or Params.default(), seg_blocks
+        self._own = []
+        if isinstance(stream, tuple):
+            self.d_x3, self.x3_len = stream
+        else:
+            b = np.ascontiguousarray(stream, dtype=np.uint8)
+            self.x3_len = b.size
+            self.d_x3 = self._alloc(max(b.size, 4))
+            ctx.upload(self.d_x3, b)
+        if frame_offsets is None:
+            cap = self.x3_len // 20 + 2
+            self.d_frame_offsets = self._alloc(8 * (cap + 1))
+            d_wo = self._alloc(8 * cap)
+            rc, nf, _, _ = ctx.index_dev(self.d_x3, self.x3_len, cap, self.d_frame_offsets, d_wo)
+            if rc:
+                raise X3Error(rc, "x3_index_dev: " + ctx.last_error())
+            self.n_frames = nf
+        else:
+            self.d_frame_offsets, self.n_frames = frame_offsets, n_frames
+        if not self.n_frames:
+            raise X3Error(ERR_BAD_ARG, "WindowSource: the stream holds no frame")
+        self.d_sample_offsets = self._alloc(8 * (self.n_frames + 1))
+        rc = ctx.sample_offsets_dev(self.d_x3, self.x3_len, self.d_frame_offsets, self.n_frames, self.d_sample_offsets)
+        if rc:
+            raise X3Error(rc, "x3_sample_offsets_dev: " + ctx.last_error())
+        self.total = int(ctx.download(self.d_sample_offsets + 8 * self.n_frames, 8, np.uint64)[0])
+        self.d_seg_index = seg_index
+        if seg_blocks and seg_index is None and lib().x3_seg_index_entries(self.n_frames, C.byref(self.params), seg_blocks):
+            ne = lib().x3_seg_index_entries(self.n_frames, C.byref(self.params), seg_blocks)
+            self.d_seg_index = self._alloc(8 * ne)
+            ctx.upload(self.d_seg_index, np.zeros(ne, dtype=np.uint64))
+            d_back = self._alloc(2 * max(self.total, 1))
+            # (the three-wave decoder records the index; it takes caller offsets that are multiples of four samples)
+            so = ctx.download(self.d_sample_offsets, 8 * self.n_frames, np.uint64)   # (where frames begin; not the total)
+            x4 = ctx.get_option("wav_offsets_x4")
+            ctx.set_option("wav_offsets_x4", 1 if not np.any(so & np.uint64(3)) else x4)
+            try:
+                rc = ctx.decode_dev_seg(self.d_x3, self.x3_len, self.d_frame_offsets, self.n_frames, self.params, d_back,
+                                        self.total, self.d_seg_index, seg_blocks, record=True,
+                                        d_wav_offsets=self.d_sample_offsets)
+                if rc == 0:
+                    ctx.decode_result()
+            finally:
+                ctx.set_option("wav_offsets_x4", x4)
+                ctx.free(d_back)
+                self._own.remove(d_back)
+        if self.d_seg_index is None:
+            self.seg_blocks = 0
+
+    def _alloc(self, n):
+        p = self.ctx.alloc(n)
+        self._own.append(p)
+        return p
+
+    def decode_into(self, d_starts, n, length, d_out, fmt, d_status):
+        """enqueue n windows (device pointers: d_starts n x u64, d_out n x length, d_status n x i32); -> rc"""
+        return self.ctx.decode_windows_dev(self.d_x3, self.x3_len, self.d_frame_offsets, self.d_sample_offsets, self.n_frames,
+                                           self.params, d_starts, n, length, d_out, fmt, d_status, self.d_seg_index,
+                                           self.seg_blocks)
+
+    def decode(self, starts, length, fmt=WINDOW_I16):
+        """-> (rows np.int16 / np.float32 [n, length], statuses np.int32 [n])"""
+        starts = np.ascontiguousarray(starts, dtype=np.uint64)
+        n = starts.size
+        esz = 4 if fmt == WINDOW_F32 else 2
+        d_starts, d_out, d_st = self.ctx.alloc(8 * n), self.ctx.alloc(esz * n * length), self.ctx.alloc(4 * n)
+        try:
+            self.ctx.upload(d_starts, starts)
+            rc = self.decode_into(d_starts, n, length, d_out, fmt, d_st)
+            if rc:
+                raise X3Error(rc, "x3_decode_windows_dev: " + self.ctx.last_error())
+            rc = self.ctx.decode_windows_result()[0]
+            if rc:
+                raise X3Error(rc, "x3_decode_windows_result: " + self.ctx.last_error())
+            rows = self.ctx.download(d_out, esz * n * length, np.float32 if fmt == WINDOW_F32 else np.int16)
+            return rows.reshape(n, length), self.ctx.download(d_st, 4 * n, np.int32)
+        finally:
+            for p in (d_starts, d_out, d_st):
+                self.ctx.free(p)
+
+    def close(self):
+        for p in self._own:
+            self.ctx.free(p)
+        self._own = []
