@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from x3_cases import frame_offsets, refresh_crcs
 
 pytestmark = pytest.mark.gpu
 
@@ -33,23 +34,6 @@ def ctx(x3):
     c.set_option("decode_blocks", 1)
     yield c
     c.close()
-
-
-def frame_offsets(stream):
-    offs, pos = [], 0
-    while pos + 20 <= len(stream):
-        offs.append(pos)
-        pos += 20 + (int(stream[pos + 6]) << 8 | int(stream[pos + 7]))
-    return offs
-
-
-def refresh_crcs(x3, s, off):
-    """payload and header CRC of the frame at `off`, after its payload was tampered with"""
-    plen = int(s[off + 6]) << 8 | int(s[off + 7])
-    pc = O.crc16(s[off + 20:off + 20 + plen])
-    s[off + 18], s[off + 19] = pc >> 8, pc & 0xFF
-    hc = O.crc16(s[off:off + 16])
-    s[off + 16], s[off + 17] = hc >> 8, hc & 0xFF
 
 
 def test_round_trips_and_kernel_in_use(ctx, x3):
@@ -87,7 +71,7 @@ def test_three_decoder_kernels_agree_on_damaged_streams(ctx, x3):
         else:   # the header asks for more samples than the payload holds: reads behind the payload
             ns = min(65535, (int(s[offs[fi] + 4]) << 8 | int(s[offs[fi] + 5])) + int(rng.integers(1, 400)))
             s[offs[fi] + 4], s[offs[fi] + 5] = ns >> 8, ns & 0xFF
-        refresh_crcs(x3, s, offs[fi])
+        refresh_crcs(s, offs[fi])
         cases.append(s)
     cap = wav.size + 70000
     on_blocks = 0
@@ -258,7 +242,7 @@ def test_block_lengths_10_and_40_take_the_blocks_kernel(x3, bl, bpf):
                         s2[pos] ^= 1 << int(rng.integers(0, 8))
                     else:
                         s2[pos:pos + 4] = rng.integers(0, 256, size=4, dtype=np.uint8)
-                    refresh_crcs(x3, s2, offs[fi])
+                    refresh_crcs(s2, offs[fi])
                     cases.append(s2)
             for s2 in cases:
                 o = O.decode_stream(s2, po, wav_cap=n + 100)

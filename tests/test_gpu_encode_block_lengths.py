@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from x3_cases import patchwork
 
 pytestmark = pytest.mark.gpu
 
@@ -25,28 +26,6 @@ def ctx(x3):
     c = x3.Context(0)
     yield c
     c.close()
-
-
-def patchwork(seed, n):
-    """runs of 3..70 samples whose differences stay inside one of the encoder's classes: silence, each Rice code's range and
-    its edges, BFP widths, literals, saturating jumps -- so that blocks of every type and lanes of every mix sit side by side"""
-    rng = np.random.default_rng(seed)
-    out = np.zeros(n, dtype=np.int64)
-    pos, level = 0, 0
-    amps = (0, 1, 2, 3, 4, 7, 8, 9, 19, 20, 21, 31, 32, 100, 1000, 8191, 8192, 16383, 16384, 30000, 65535)
-    while pos < n:
-        ln = int(rng.integers(3, 71))
-        a = amps[int(rng.integers(0, len(amps)))]
-        d = rng.integers(-a, a + 1, size=ln)
-        if a and rng.integers(0, 4) == 0:
-            d[int(rng.integers(0, ln))] = a if rng.integers(0, 2) else -a   # the class's edge itself
-        seg = level + np.cumsum(d)
-        seg = np.clip(seg, -32768, 32767)
-        m = min(ln, n - pos)
-        out[pos:pos + m] = seg[:m]
-        level = int(seg[m - 1])
-        pos += m
-    return out.astype(np.int16)
 
 
 GEOMS = [(10, 1000), (10, 1024), (10, 500), (10, 2), (10, 6), (10, 64), (40, 250), (40, 256), (40, 37), (40, 1), (40, 3), (40, 500)]

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from x3_cases import frame_offsets, refresh_crcs
 
 pytestmark = pytest.mark.gpu
 
@@ -402,26 +403,6 @@ def test_encode_host_buffers_in_chunks(ctx, x3):
 
 # ------------------------------------------------------------------ decode parity incl. corrupt streams
 
-def refresh_crcs(x3, stream, off):
-    """recompute payload CRC + header CRC of the frame at `off` after tampering"""
-    rc, h = x3.read_frame_header(stream[off:off + 20])
-    plen = int(stream[off + 6]) << 8 | int(stream[off + 7])
-    pcrc = O.crc16(stream[off + 20: off + 20 + plen])
-    stream[off + 18] = pcrc >> 8
-    stream[off + 19] = pcrc & 0xFF
-    hcrc = O.crc16(stream[off: off + 16])
-    stream[off + 16] = hcrc >> 8
-    stream[off + 17] = hcrc & 0xFF
-
-
-def frame_offsets(stream):
-    offs, pos = [], 0
-    while pos + 20 < stream.size:
-        offs.append(pos)
-        pos += 20 + (int(stream[pos + 6]) << 8 | int(stream[pos + 7]))
-    return offs
-
-
 def test_decode_roundtrip_kinds(ctx, x3):
     for kind in range(5):
         wav = x3.synth(kind, 77, 0, 54321)
@@ -461,7 +442,7 @@ def test_decode_corrupt_payload_with_valid_crc(ctx, x3):
             s[pos:pos + 8] = 0          # long zero run -> OutOfBoundsInverse or BFP with E <= 5
         else:
             s[pos:pos + 6] = rng.integers(0, 256, size=6, dtype=np.uint8)
-        refresh_crcs(x3, s, offs[fi])
+        refresh_crcs(s, offs[fi])
         r = check_decode(ctx, x3, s, wav_cap=wav.size + 70000)
         seen.add((r[0], r[3]))
     assert (0, 1) in seen  # at least one counted frame error was exercised
@@ -476,13 +457,13 @@ def test_decode_header_errors(ctx, x3):
     s = stream.copy(); s[o2 + 5] ^= 1
     assert check_decode(ctx, x3, s, wav_cap=wav.size)[0] == x3.ERR_FRAME_HEADER_INVALID_HEADER_CRC
     # key (with a valid header CRC)
-    s = stream.copy(); s[o2] = 0x79; refresh_crcs(x3, s, o2)
+    s = stream.copy(); s[o2] = 0x79; refresh_crcs(s, o2)
     assert check_decode(ctx, x3, s, wav_cap=wav.size)[0] == x3.ERR_FRAME_HEADER_INVALID_KEY
     # channels > 1
-    s = stream.copy(); s[o2 + 3] = 2; refresh_crcs(x3, s, o2)
+    s = stream.copy(); s[o2 + 3] = 2; refresh_crcs(s, o2)
     assert check_decode(ctx, x3, s, wav_cap=wav.size)[0] == x3.ERR_MORE_THAN_ONE_CHANNEL
     # payload_len >= Frame::MAX_LENGTH
-    s = stream.copy(); s[o2 + 6] = 0x7F; s[o2 + 7] = 0xE0; refresh_crcs(x3, s, o2)
+    s = stream.copy(); s[o2 + 6] = 0x7F; s[o2 + 7] = 0xE0; refresh_crcs(s, o2)
     assert check_decode(ctx, x3, s, wav_cap=wav.size)[0] == x3.ERR_FRAME_LENGTH
     # payload_len beyond the data: quiet end
     s = stream.copy(); s[o2 + 6] = 0x70; hc = O.crc16(s[o2:o2 + 16]); s[o2 + 16] = hc >> 8; s[o2 + 17] = hc & 0xFF
@@ -494,7 +475,7 @@ def test_decode_header_errors(ctx, x3):
     # trailing garbage shorter than a header is ignored
     check_decode(ctx, x3, np.concatenate([stream, np.zeros(20, dtype=np.uint8)]), wav_cap=wav.size)
     # samples field larger than what the payload encodes: reads zeros past the end
-    s = stream.copy(); s[offs[-1] + 4] = 0x27; s[offs[-1] + 5] = 0x10; refresh_crcs(x3, s, offs[-1])
+    s = stream.copy(); s[offs[-1] + 4] = 0x27; s[offs[-1] + 5] = 0x10; refresh_crcs(s, offs[-1])
     check_decode(ctx, x3, s, wav_cap=wav.size + 20000)
 
 
@@ -877,7 +858,7 @@ def test_decoder_kernels_agree(ctx, x3):
             s[pos:pos + 8] = 0
         else:
             s[pos:pos + 6] = rng.integers(0, 256, size=6, dtype=np.uint8)
-        refresh_crcs(x3, s, offs[fi])
+        refresh_crcs(s, offs[fi])
         cases.append(s)
     for s in cases:
         a = ctx.decode_stream(s, x3.Params.default(), wav_cap=wav.size + 70000)
@@ -963,7 +944,7 @@ def test_decode_stream_dev_matches_host_api(ctx, x3):
             s[pos:pos + 8] = 0
         else:
             s[pos:pos + 6] = rng.integers(0, 256, size=6, dtype=np.uint8)
-        refresh_crcs(x3, s, offs[fi])
+        refresh_crcs(s, offs[fi])
         cases.append(s)
     p = x3.Params.default()
     for cap, no_fast in ((wav.size + 70000, 0), (55555, 0), (wav.size + 70000, 1)):
