@@ -1,5 +1,5 @@
 #!/bin/bash
-# more of modes_experiments.sh: what the check kernel beside the decoder does to it, by how the check kernel is run
+# what selects the decode phase's pace (profiles/r6/decoder_modes.txt): what the check kernel beside the decoder does to it, by how the check kernel is run
 out=${1:-gpurun_out/r6/modes_experiments2.txt}
 run() { echo -n "$LABEL $*: "; python3 tools/kbench.py --steps 20 "$@" 2>&1 | tail -1 | sed -e 's/sizes=.*check=/check=/' -e 's/dense=.*rep 0//'; }
 {

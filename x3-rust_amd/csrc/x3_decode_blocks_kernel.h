@@ -45,10 +45,7 @@
 // walks on from its own first bit) -- so that what a lane holds, what a piece is and what the staging takes do not depend on
 // the block length: instantiations <20, 1> (the default geometry), <20, 2> (block_len 40), <10, 1> (block_len 10).
 #define X3B_NB 32u                       // units per batch and frame
-#ifndef X3B_D
-#define X3B_D 3u
-#endif
-// (decoder waves)                         // decoder waves
+#define X3B_D 3u                         // decoder waves
 #define X3B_WAVES (1u + X3B_D)
 #define X3B_SPAN_MAX (X3B_NB * 326u)     // bits 32 valid units can take (a literal block of 20: 6 + 20 * 16)
 #define X3B_IN_PITCH 1392u               // input staging per frame piece: 86 chunks of 16 bytes + 16
@@ -58,19 +55,7 @@
 #define X3B_DESC_PITCH 34u               // uint16 per frame and batch buffer: 32 + 2 (17 dwords: rows spread over the banks)
 #define X3B_PERIOD 2u                    // the walker's ring is topped up every second block
 #define X3B_AHEAD 3u
-#ifndef X3B_WALKER_PRIO
 #define X3B_WALKER_PRIO 3
-#endif
-
-// TIMING experiments (results are wrong; -DX3_EXPERIMENT builds only): 1 = the decoders do nothing, 2 = the walker skips its
-// codeword walk, 4 = no global stores from the decoders, 8 = no staging copy, 16 = the decoders skip their pair loops,
-// 32 = the walker skips its ring service
-#ifndef X3B_KO
-#define X3B_KO 0
-#endif
-#if X3B_KO && !defined(X3_EXPERIMENT)
-#error "X3B_KO builds give wrong results: experiment builds only (-DX3_EXPERIMENT)"
-#endif
 
 #define X3B_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
@@ -403,7 +388,7 @@ x3_decode_blocks_kernel(const uint8_t* __restrict__ x3, uint64_t x3_len, const u
         dq[b] = (uint16_t)(rel_c - ((qb << 3) + s));
         X3_STAMP(0);
         // (every 40 samples walked, whatever a unit is: units of 10 are served every fourth)
-        if (!(X3B_KO & 32) && (it % (X3B_PERIOD * (20u / UNIT))) == 0u) service(ring_index());
+        if ((it % (X3B_PERIOD * (20u / UNIT))) == 0u) service(ring_index());
         X3_STAMP(1);
         const uint32_t live = cnt ? 0xFFFFFFFFu : 0u;
         if (UPB == 1u || (b % UPB) == 0u) {   // (batches are whole blocks in every lane: the header's turn is the wave's)
@@ -416,8 +401,7 @@ x3_decode_blocks_kernel(const uint8_t* __restrict__ x3, uint64_t x3_len, const u
         const uint32_t zmask = zmask0 & live;
         const uint32_t nwidth = (0u - width) & live;
         X3_STAMP(2);
-        if (X3B_KO & 2) {
-        } else if (!shorts || __all(cnt == UNIT || cnt == 0u)) {
+        if (!shorts || __all(cnt == UNIT || cnt == 0u)) {
           uint32_t t_, z_, n1_, wnb_;
           if (UNIT == 20u) {
             asm volatile(
@@ -540,7 +524,7 @@ x3_decode_blocks_kernel(const uint8_t* __restrict__ x3, uint64_t x3_len, const u
         const uint2 b = recB[buf][fl];
         const uint32_t nchunk = b.x >> 24;
         uint4 q = make_uint4(0u, 0u, 0u, 0u);
-        if (j < nchunk && !(b.y & (1u << 21)) && !(X3B_KO & 8)) q = x3b_global_load16(recA[buf][fl].ga + 16u * j);
+        if (j < nchunk && !(b.y & (1u << 21))) q = x3b_global_load16(recA[buf][fl].ga + 16u * j);
         return q;
       };
       // iterations go to whichever decoder wave is free (the waves of a group sit on different SIMDs, whose other
@@ -550,7 +534,7 @@ x3_decode_blocks_kernel(const uint8_t* __restrict__ x3, uint64_t x3_len, const u
         if (lane == 0u) t = atomicAdd(&s_tick[buf], 1u);
         return (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
       };
-      uint32_t i = (X3B_KO & 1) ? niter : ticket();
+      uint32_t i = ticket();
       uint4 q0 = make_uint4(0u, 0u, 0u, 0u);
       if (i < niter) q0 = fetch0(i);
       const uint32_t desc_lane = x3_lds_addr(&desc[buf][0]) + 2u * (h * X3B_DESC_PITCH + j);
@@ -582,7 +566,7 @@ x3_decode_blocks_kernel(const uint8_t* __restrict__ x3, uint64_t x3_len, const u
             }
           }
         }
-        if (__any(nchunk > 32u && !clamped) && !(X3B_KO & 8)) {   // long pieces (BFP / literal blocks): the rest at once
+        if (__any(nchunk > 32u && !clamped)) {   // long pieces (BFP / literal blocks): the rest at once
 #pragma unroll
           for (uint32_t r = 1; r < 3u; ++r) {
             const uint32_t c = j + 32u * r;
@@ -647,10 +631,7 @@ x3_decode_blocks_kernel(const uint8_t* __restrict__ x3, uint64_t x3_len, const u
         X3_STAMP(1);
         uint32_t maxii2 = 0, prevP = 0;
         uint32_t W[PAIRS];
-        if (X3B_KO & 16) {
-#pragma unroll
-          for (uint32_t r = 0; r < PAIRS; ++r) W[r] = w0 + r;
-        } else if (full && !any_lit) {
+        if (full && !any_lit) {
           const uint32_t zsh2 = zmask & 0x00010001u;
           uint32_t wnb_, pb_, t_, t2_, z1_, z2_, n1_, n2_, v1_, v2_;
           asm volatile(
@@ -770,21 +751,19 @@ x3_decode_blocks_kernel(const uint8_t* __restrict__ x3, uint64_t x3_len, const u
           // the usual piece: ten whole lines, in both halves
           const x3_u32x4 v0 = x3_lds_read_b128(out_base + 16u * j);
           const x3_u32x4 v1 = x3_lds_read_b128(out_base + 16u * j + 512u);
-          if (!(X3B_KO & 4)) {
-            x3b_global_store16_nt(GL + 16u * j, v0);
-            x3b_global_store16_nt(GL + 16u * j + 512u, v1);
-          }
+          x3b_global_store16_nt(GL + 16u * j, v0);
+          x3b_global_store16_nt(GL + 16u * j + 512u, v1);
           if (j < 16u) {
             const x3_u32x4 v2 = x3_lds_read_b128(out_base + 16u * j + 1024u);
-            if (!(X3B_KO & 4)) x3b_global_store16_nt(GL + 16u * j + 1024u, v2);
+            x3b_global_store16_nt(GL + 16u * j + 1024u, v2);
           }
         } else if (UNIT == 10u && __all((rb.y & 0xFFFFFu) == (640u << 8))) {
           // ... five whole lines
           const x3_u32x4 v0 = x3_lds_read_b128(out_base + 16u * j);
-          if (!(X3B_KO & 4)) x3b_global_store16_nt(GL + 16u * j, v0);
+          x3b_global_store16_nt(GL + 16u * j, v0);
           if (j < 8u) {
             const x3_u32x4 v1 = x3_lds_read_b128(out_base + 16u * j + 512u);
-            if (!(X3B_KO & 4)) x3b_global_store16_nt(GL + 16u * j + 512u, v1);
+            x3b_global_store16_nt(GL + 16u * j + 512u, v1);
           }
         } else {
 #pragma unroll
@@ -792,7 +771,7 @@ x3_decode_blocks_kernel(const uint8_t* __restrict__ x3, uint64_t x3_len, const u
             const uint32_t lo = 16u * (j + 32u * r);
             if (lo < EB && lo + 16u > PH) {
               if (lo >= PH && lo + 16u <= EB) {
-                if (!(X3B_KO & 4)) x3b_global_store16_nt(GL + lo, x3_lds_read_b128(out_base + lo));
+                x3b_global_store16_nt(GL + lo, x3_lds_read_b128(out_base + lo));
               } else {
                 // the two ends of a row: sample by sample
                 const uint32_t from = lo > PH ? lo : PH, to = lo + 16u < EB ? lo + 16u : EB;

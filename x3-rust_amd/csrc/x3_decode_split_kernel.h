@@ -50,144 +50,33 @@
 #define X3S_BL 20u             // block length served by this kernel
 #define X3S_PAIRS 10u
 #define X3S_RING_DW 64u        // staging ring per row: 64 dwords = two 128-byte lines of the destination
-#ifndef X3S_PERIOD
-#define X3S_PERIOD 2u         // the ring is topped up every X3S_PERIOD blocks (1 or 2)
-#endif
-#ifndef X3S_AHEAD
-#define X3S_AHEAD 3u          // 16-byte chunks per lane requested one service ahead (of up to 6 per service)
-#endif
-#ifndef X3S_VALUER_FOLD
-#define X3S_VALUER_FOLD 0
-#endif
-// Round 5: the THIN parser.  The parser is the group's critical wave -- its pair loop runs at the speed of a lone wave
-// (152 clocks per pair of codewords against 139 alone on a SIMD: profiles/r4/stamps_decode_split_base.txt,
-// ubench_pair_cost.txt) -- so what it does not have to do itself is taken off it: it walks the codeword LENGTHS only (peek,
-// two v_ffbh / v_mad / the shift between them, the window update: 14 vector instructions per pair instead of 19) and hands
-// over the 32-bit PEEK of every pair; the valuer, which idles 29 % of the time at the barrier and whose pairs do not depend
-// on each other, repeats the five-instruction walk on the peek and extracts the two fields from it (+10 per pair there).
-// Measured (profiles/r5/decoder_thin_parser.txt): 0.649 -> 0.684 ms.  The ten instructions a pair gains in the valuer make
-// IT the critical wave.  Kept as a build option.
-#ifndef X3S_THIN
-#define X3S_THIN 0
-#endif
-// Round 5: the input ring TRANSPOSED -- word slot s of lane l at dword s * 64 + l instead of l * 32 + s.  With a row of 128
-// bytes per lane the 64 lanes' rows start on two banks only (lane * 32 dwords: bank 0 or 32), and lanes that are at the same
-// slot of their rows -- they read at similar rates -- pile onto one bank pair: 42 % of the decoder's LDS cycles were bank
-// conflicts (profiles/r5/pmc_instruction_mix.txt).  Transposed, lane l only ever touches bank l: the parser's read of the next
-// window word and the parks are conflict-free whatever the lanes' positions.  Same instruction count (the byte counter
-// steps by 256 instead of 4; a park is four dword rows = two ds_write2st64_b32 instead of one ds_write_b128).
-#ifndef X3S_RING_T
-#define X3S_RING_T 0
-#endif
-#if X3S_RING_T
-#define X3S_QSH 8            // log2 of the byte distance of two ring words of a lane
-#define X3S_QMASK 0x1F00u    // (slot & 31) << 8
-#else
-#define X3S_QSH 2
-#define X3S_QMASK 124u
-#endif
-#if X3S_RING_T && X3S_SWP
-#error "the software-pipelined pair loop (X3S_SWP) is written for the untransposed ring"
-#endif
-#ifndef X3S_PAIR_ASM2
-#define X3S_PAIR_ASM2 1      // the parser's pair block also holds the shift's sign and the ring address (one s_nop per pair less)
-#endif
-#ifndef X3S_VALUER_ASM
-#define X3S_VALUER_ASM 0     // 1: the valuer's pair arithmetic as one asm block per pair (no s_nop padding between its instructions; measured: +-0)
-#endif
-// TIMING experiments on top of X3S_THIN (results are wrong): the valuer converts only the first X3S_THIN_K of a block's ten
-// pairs from peeks to indices (as if another wave had converted the others in place); X3S_THIN_F: the flusher executes
-// the conversion's instructions and LDS traffic for the other 10 - K on dummy data
-#ifndef X3S_THIN_K
-#define X3S_THIN_K 10
-#endif
-#ifndef X3S_THIN_F
-#define X3S_THIN_F 0
-#endif
-// Round 5: the parser's pair loop SOFTWARE-PIPELINED, one asm block per block of ten pairs.  A lone wave issues an
-// instruction every ~4.3 clocks when it does not depend on the one before and every ~8.5 when it does
-// (tools/ubench/issue_cost.hip), and in the loop as the compiler laid it out (peek, ffbh, mad, shift, ffbh, mad, add3,
-// sign, address, read, bfi, bfi: a dependent instruction behind nearly every one) a pair took 139 clocks for its 19 + 1
-// instructions.  Here every instruction of the dependent chain is followed by one that does not depend on it: the
-// PREVIOUS pair's index packing and its store to the block buffer, this pair's field extraction, the ring address and
-// read.  The window has a third word w2 that is brought up to date half a pair late, so that the ring read has a pair and
-// a half to arrive (tools/ubench/pair_cost.hip: 139 -> ~100 clocks per pair for one wave on its SIMD).  Nothing that the
-// asm block reads asynchronously is left pending in a register the compiler knows: the block ends with the window settled.
-#ifndef X3S_SWP
-#define X3S_SWP 0
-#endif
-#if X3S_SWP && X3S_THIN
-#error "X3S_THIN is an option of the compiler-scheduled pair loop (X3S_SWP=0)"
-#endif
-// pair i of a block: chain instruction, filler, chain instruction, filler ...; CNT = LDS operations that may still be in
-// flight when the read of pair i-1 is needed (those issued behind it); STORE = the store of pair i-1's packed indices
-#define X3S_SWP_PAIR(WNC, WNP, CNT, STORE)                           \
-  "v_alignbit_b32 %[tt], %[w0], %[w1], %[s]\n\t"                     \
-  "v_lshl_add_u32 %[xa], %[z1], %[lsh], %[pv1]\n\t"                  \
-  "v_ffbh_u32 %[z1], %[tt]\n\t"                                      \
-  "v_lshl_add_u32 %[xb], %[z2], %[lsh], %[pv2]\n\t"                  \
-  "v_mad_i32_i24 %[nn1], %[z1], %[zmask], %[nwidth]\n\t"             \
-  "v_lshl_add_u32 %[qb], %[mp], 2, %[qb]\n\t"                        \
-  "v_alignbit_b32 %[t2], %[tt], 0, %[nn1]\n\t"                       \
-  "v_and_or_b32 %[ad], %[qb], %[c124], %[rowb]\n\t"                  \
-  "v_ffbh_u32 %[z2], %[t2]\n\t"                                      \
-  "ds_read_b32 %[" WNC "], %[ad]\n\t"                                \
-  "v_mad_i32_i24 %[nn2], %[z2], %[zmask], %[nwidth]\n\t"             \
-  "v_perm_b32 %[xa], %[xb], %[xa], %[sel]\n\t"                       \
-  "s_waitcnt lgkmcnt(" CNT ")\n\t"                                   \
-  "v_bfi_b32 %[w2], %[mp], %[" WNP "], %[w2]\n\t"                    \
-  "v_add3_u32 %[s2], %[s], %[nn1], %[nn2]\n\t"                       \
-  STORE                                                              \
-  "v_bfe_u32 %[pv1], %[tt], %[nn1], %[fw]\n\t"                       \
-  "v_ashrrev_i32 %[mp], 31, %[s2]\n\t"                               \
-  "v_bfe_u32 %[pv2], %[t2], %[nn2], %[fw]\n\t"                       \
-  "v_bfi_b32 %[w0], %[mp], %[w1], %[w0]\n\t"                         \
-  "v_and_b32 %[s], 31, %[s2]\n\t"                                    \
-  "v_bfi_b32 %[w1], %[mp], %[w2], %[w1]\n\t"
-#define X3S_SWP_STORE(OFF) "ds_write_b32 %[buf], %[xa] offset:" #OFF "\n\t"
-// timing experiments only (results are wrong): knock out one role's work to see what the others cost each other.
-// 1: the valuer's pair arithmetic and staging; 2: the flusher's loads and stores; 4: the parser's codeword walk;
-// 8: the flusher's global stores only (its LDS reads stay); 16: the parser's ring service (no loads, no parks);
-// 32: the service's loads only are skipped (parks of stale registers stay)
-#ifndef X3S_KO
-#define X3S_KO 0
-#endif
+#define X3S_PERIOD 2u          // the ring is topped up every X3S_PERIOD blocks
+#define X3S_AHEAD 3u           // 16-byte chunks per lane requested one service ahead (of up to 6 per service)
+// Tried on this kernel in round 5 and dropped (DESIGN_HISTORY.md, round 5's list of what was tried, and its item 1):
+//   * a THIN parser that walks the codeword lengths only and leaves the fields to the valuer: 0.649 -> 0.684 ms, the valuer
+//     becomes the critical wave (profiles/r5/decoder_thin_parser_and_balance.txt);
+//   * the parser's pair loop software-pipelined as one asm block per block of ten pairs: 139 -> 110 clocks per pair for a
+//     lone wave in a bare loop, +-0 in the kernel -- a wave's stalls are issue slots for the other waves of its SIMD
+//     (profiles/r5/decoder_software_pipelined_parser.txt);
+//   * the input ring transposed (slot s of lane l at dword s * 64 + l): it removes the ring's LDS bank conflicts (42 % of the
+//     decoder's LDS cycles, profiles/r5/pmc_instruction_mix.txt) and is no faster (profiles/r5/decoder_ring_transposed.txt);
+//   * the valuer's pair arithmetic as one asm block: +-0 (profiles/r5/decoder_valuer_asm_block.txt).
 // (Round 4 also swept the cache policies of the flusher's stores and the parser's requests as buffer instructions --
 // plain / nt / sc1 / sc0 sc1 / sc1 nt: nothing beats nontemporal stores and plain loads, plain or sc1 stores cost 7 %
 // and slow the ENCODER down by 8 % through what they leave in L2, nt loads cost 56 %: profiles/r4/decoder_cache_policies.txt.)
-//  the switches above that give WRONG RESULTS are one -D away from the shipped library: they only
-// compile in experiment builds
-#if (X3S_KO || X3S_THIN_K != 10 || X3S_THIN_F || defined(X3S_HALF_LINES_WRONG)) && !defined(X3_EXPERIMENT)
-#error "X3S_KO / X3S_THIN_K / X3S_THIN_F builds give wrong results: experiment builds only (-DX3_EXPERIMENT)"
-#endif
 #define X3S_XROWS 11u          // transfer rows per block buffer: 10 pair dwords + the header word
 #define X3S_WAVES 3u            // parser, valuer, flusher
 // Code placement (round 5).  The kernel's time depends on where its hot loops fall against the instruction fetch windows:
 // the same instructions shifted by four bytes decode at 0.76 instead of 0.69 ms (MI355X_MICROARCH.md, "Code-placement
 // sensitivity"; profiles/r5/decoder_code_placement.txt) -- and any edit in front of a loop shifts it.  Each role's block
-// loop therefore starts at a fixed phase: aligned to 64 bytes plus X3S_PAD_x four-byte s_nops (executed once), chosen by
-// measurement.  -1: no alignment (the loop falls where the code in front of it puts it).
-#ifndef X3S_PAD_P
-#define X3S_PAD_P 0
-#endif
-#ifndef X3S_PAD_V
-#define X3S_PAD_V 0
-#endif
-#ifndef X3S_PAD_F
-#define X3S_PAD_F 0
-#endif
-#define X3S_STR2(x) #x
-#define X3S_STR(x) X3S_STR2(x)
-#define X3S_PLACE(n) do { if ((n) >= 0) asm volatile(".p2align 6\n\t.rept " X3S_STR(n) "\n\ts_nop 0\n\t.endr" ::: "memory"); } while (0)
+// loop therefore starts at a fixed phase: aligned to 64 bytes plus `nops` four-byte s_nops (executed once), chosen by
+// measurement.
+#define X3S_PLACE(nops) asm volatile(".p2align 6\n\t.rept " #nops "\n\ts_nop 0\n\t.endr" ::: "memory")
 
 // halfword index of sample j (0..19) of a block in its transfer buffer: pair j/2 is dword (j/2 & 1) of the
 // 8-byte slot of this lane in row j/4
 __device__ __forceinline__ uint32_t x3s_half_index(uint32_t j, uint32_t lane) {
-#if X3S_SWP
-  return 2u * ((j >> 1) * 64u + lane) + (j & 1u);   // (software-pipelined parser: pair j/2 is dword `lane` of row j/2)
-#else
   return 2u * (((j >> 2) * 64u + lane) * 2u + ((j >> 1) & 1u)) + (j & 1u);
-#endif
 }
 
 // Pacing.  The SQ issues oldest-first, so the groups dispatched first run ahead of the ones dispatched last (group
@@ -198,59 +87,27 @@ __device__ __forceinline__ uint32_t x3s_half_index(uint32_t j, uint32_t lane) {
 // atomicMax, tagged with the launch's epoch, and the next launch sets its target by that and by what the last one aimed
 // at (below).  A target that does not fit (first launch of a context, other data) pins all waves at one priority: the
 // unpaced kernel, nothing worse.
-#ifndef X3S_PACE_OFF
-#define X3S_PACE_OFF 0
-#endif
 #define X3S_PACE_BAND 6            // blocks ahead / behind that move a wave one priority level
 // (Round 5: the pace is counted in SHADER clocks -- s_memtime -- not in 10 ns wall ticks: a box that is still ramping its
 // clock, or a launch that runs at 2.0 GHz instead of 2.4, does the same work per clock, and a target in wall time read that
 // as "behind" -- all waves at one priority, the controller backing off for launches on end: VERDICT r4, item 2)
 #define X3S_PACE_DEFAULT 48000u    // shader clocks per 16 blocks when there is no launch to go by (1.25 us per block at 2.4 GHz)
 #define X3S_PACE_EPOCH_SHIFT 20u   // pace word: epoch << 20 | shader clocks per 16 blocks
-// Priorities by ROLE (round 4).  The SIMD arbitrates by priority, then age (MI355X_MICROARCH.md, "Two waves per SIMD"):
-// with all three waves of a group paced over the same four levels the critical wave -- the parser, whose dependent
-// chain sets the group's time per block -- was never preferred over the valuer or flusher of another group on its SIMD.
-// X3S_PRIO_MODE: 0 = round 3 (every role 0..3 by pace); 1 = parser {2,3}, valuer / flusher {0,1}; 2 = parser 3,
-// the others 0..2 by pace; 3 = parser {1,2,3}, others {0,1}; 4 = parser 0..3, others one level below;
-// 5 = no pacing: parser 3, valuer 1, flusher 0; 6 = parser {2,3}, valuer {1,2}, flusher {0,1}; 7 = round 3 with the
-// groups beyond 1 024 (four per CU) one level up
-#ifndef X3S_PRIO_MODE
-#define X3S_PRIO_MODE 0
-#endif
-#define X3S_ROLE_PARSER 0
-#define X3S_ROLE_VALUER 1
-#define X3S_ROLE_FLUSHER 2
-template <int ROLE>
+// (Round 4 also paced the three roles over different priority levels -- the parser, whose dependent chain sets the group's
+// time per block, above the valuer and flusher of other groups on its SIMD -- in seven ways: none was faster than every role
+// over the same four levels, profiles/r4/decoder_role_priorities.txt, decoder_valuer_fold_and_late_groups.txt.)
 __device__ __forceinline__ void x3s_set_priority(int32_t d) {
   constexpr int B2 = 2 * X3S_PACE_BAND;
-#define X3S_P4(a, b, c, e) { if (d > B2) __builtin_amdgcn_s_setprio(a); else if (d > 0) __builtin_amdgcn_s_setprio(b); else if (d > -B2) __builtin_amdgcn_s_setprio(c); else __builtin_amdgcn_s_setprio(e); }
-#define X3S_P2(a, b) { if (d > 0) __builtin_amdgcn_s_setprio(a); else __builtin_amdgcn_s_setprio(b); }
-#if X3S_PRIO_MODE == 0
-  X3S_P4(0, 1, 2, 3)
-#elif X3S_PRIO_MODE == 1
-  if (ROLE == X3S_ROLE_PARSER) X3S_P2(2, 3) else X3S_P2(0, 1)
-#elif X3S_PRIO_MODE == 2
-  if (ROLE == X3S_ROLE_PARSER) __builtin_amdgcn_s_setprio(3); else X3S_P4(0, 1, 2, 2)
-#elif X3S_PRIO_MODE == 3
-  if (ROLE == X3S_ROLE_PARSER) X3S_P4(1, 2, 2, 3) else X3S_P2(0, 1)
-#elif X3S_PRIO_MODE == 4
-  if (ROLE == X3S_ROLE_PARSER) X3S_P4(0, 1, 2, 3) else X3S_P4(0, 0, 1, 2)
-#elif X3S_PRIO_MODE == 5
-  __builtin_amdgcn_s_setprio(ROLE == X3S_ROLE_PARSER ? 3 : (ROLE == X3S_ROLE_VALUER ? 1 : 0));
-#elif X3S_PRIO_MODE == 6
-  if (ROLE == X3S_ROLE_PARSER) X3S_P2(2, 3) else if (ROLE == X3S_ROLE_VALUER) X3S_P2(1, 2) else X3S_P2(0, 1)
-#elif X3S_PRIO_MODE == 7
-  // the groups beyond four per CU (the fifth group of 56 CUs in config 3) one level up
-  if (blockIdx.x >= 1024u) X3S_P4(1, 2, 3, 3) else X3S_P4(0, 1, 2, 3)
-#endif
-#undef X3S_P4
-#undef X3S_P2
+  if (d > B2) __builtin_amdgcn_s_setprio(0);
+  else if (d > 0) __builtin_amdgcn_s_setprio(1);
+  else if (d > -B2) __builtin_amdgcn_s_setprio(2);
+  else __builtin_amdgcn_s_setprio(3);
 }
-#define X3S_PACE_STEP(b, ROLE)                                                                 \
+#define X3S_PACE_STEP(b)                                                                       \
   if (paced && ((b) & 7u) == 0u) {                                                             \
     const unsigned long long el = (unsigned long long)(clock64() - pace_t0); /* shader clocks */ \
     const int32_t d = (int32_t)(b) - (int32_t)((el * pace_inv) >> 24);                           \
-    x3s_set_priority<ROLE>(d);                                                                 \
+    x3s_set_priority(d);                                                                       \
   }
 
 // ---- Round 5: STRETCHES.  A frame is one serial bit stream, so a stream of few frames cannot be decoded faster than
@@ -287,9 +144,7 @@ struct X3SegArgs {
 // may use 128 registers per lane.  Left to aim at eight waves per SIMD it squeezes the kernel into 70 and, depending on the
 // code around them, COPIES part of a ring request's destination registers right behind the request -- a wait for a load
 // that has just been issued, in every service: 0.69 -> 0.75 ms (profiles/r5/decoder_service_schedule.txt).)
-#ifndef X3S_WAVES_PER_EU
 #define X3S_WAVES_PER_EU 4
-#endif
 __global__ void __launch_bounds__(64 * X3S_WAVES) __attribute__((amdgpu_waves_per_eu(1, X3S_WAVES_PER_EU)))
 x3_decode_split_kernel(const uint8_t* __restrict__ x3, uint64_t x3_len, const uint64_t* __restrict__ frame_off,
                        uint64_t n_frames_arg, X3Geom g, const uint64_t* __restrict__ wav_off, X3DevParams p,
@@ -304,11 +159,7 @@ x3_decode_split_kernel(const uint8_t* __restrict__ x3, uint64_t x3_len, const ui
   // slot ~j & 31 (descending): the address of a word is then ONE v_and_or_b32 on a byte counter that a shift of
   // the window decrements with one v_lshl_add_u32.  (Lanes are at different places in their rows, so the aligned
   // rows do not line the reads up on one bank.)
-#if X3S_RING_T
-  __shared__ __attribute__((aligned(8192))) uint32_t ring[64 * X3_DEC_RING_DW];   // [slot][lane]; 8 KB aligned: slot bits 8..12 of the address are the ring's own
-#else
   __shared__ __attribute__((aligned(128))) uint32_t ring[64 * X3_DEC_RING_DW];
-#endif
   __shared__ __attribute__((aligned(256))) uint32_t outs[64 * X3S_RING_DW];
   __shared__ __attribute__((aligned(16))) uint32_t xfer[2 * X3S_XROWS * 64];
   __shared__ uint32_t s_over[64];  // parser -> valuer: the frame was read beyond its payload (x3_decode_replay.h)
@@ -332,7 +183,7 @@ x3_decode_split_kernel(const uint8_t* __restrict__ x3, uint64_t x3_len, const ui
   }
   const uint64_t f = (uint64_t)(seg_grid ? blockIdx.x / sg.nseg : blockIdx.x) * 64 + lane;
   if (sg.out && blockIdx.x == 0 && threadIdx.x == 0) sg.out[0] = make_uint2(X3S_SEG_MAGIC, sg.sb);
-  const bool paced = !X3S_PACE_OFF && !segd;   // (stretches: many short groups, dispatched as CUs fall free -- nothing to pace)
+  const bool paced = !segd;   // (stretches: many short groups, dispatched as CUs fall free -- nothing to pace)
   const unsigned long long wall_t0 = wall_clock64();
   const unsigned long long clk_t0 = clock64();   // (shader clock: the pace's clock, and the launch log's clock measurement, below)
   const unsigned long long pace_t0 = clk_t0;
@@ -471,14 +322,8 @@ x3_decode_split_kernel(const uint8_t* __restrict__ x3, uint64_t x3_len, const ui
   uint32_t remaining = samples ? samples - 1u : 0u;
 
   // ---- the input ring of this lane's frame (the parser fills and reads it)
-#if X3S_RING_T
-  const uint32_t row_base = x3_lds_addr(ring) + 4u * lane;   // LDS byte address of this lane's column (bits 8..12 zero)
-#define X3S_RING_WORD(j) ring[((~(j)) & 31u) * 64u + lane]
-#else
   uint32_t* const row = ring + lane * X3_DEC_RING_DW;
   const uint32_t row_base = (uint32_t)(uintptr_t)row;  // LDS byte address of the row (low 7 bits zero)
-#define X3S_RING_WORD(j) row[~(j) & 31u]
-#endif
   // words are parked BIG-ENDIAN
   const uint32_t adj = (uint32_t)(reinterpret_cast<uintptr_t>(x3) & 15u);
   // offsets are relative to this lane's first 16-byte chunk (a frame is < 64 KB): a 64-bit pointer per lane,
@@ -511,30 +356,18 @@ x3_decode_split_kernel(const uint8_t* __restrict__ x3, uint64_t x3_len, const ui
     const uint32_t w[4] = {c.x, c.y, c.z, c.w};
     // words wr_abs .. wr_abs+3 -> slots ~wr_abs & 31 downwards = the aligned 16-byte block at slot ~(wr_abs+3) & 31:
     // byte offset (-4 * wr_abs - 16) & 112 of the 128-byte aligned row
-#if X3S_RING_T
-    // ... transposed: slots g .. g + 3, g = ~(wr_abs + 3) & 31 (a multiple of four), 256 bytes apart in this lane's column
-    uint32_t* const q = ring + ((~(wr_abs + 3u)) & 31u) * 64u + lane;
-    q[0] = x3_bswap32(w[3]);
-    q[64] = x3_bswap32(w[2]);
-    q[128] = x3_bswap32(w[1]);
-    q[192] = x3_bswap32(w[0]);
-#else
     x3_lds_write_b128(x3_and_or(0u - 4u * wr_abs - 16u, 112u, row_base), x3_bswap32(w[3]), x3_bswap32(w[2]),
                       x3_bswap32(w[1]), x3_bswap32(w[0]));
-#endif
     wr_abs += 4;
   };
-  // Round 5 (-DX3S_DENSE_AHEAD=0: off): a group that holds a DENSE frame -- a payload beyond what the encoder's image takes,
+  // Round 5: a group that holds a DENSE frame -- a payload beyond what the encoder's image takes,
   // literal and wide BFP blocks: a ship passing the hydrophone -- needs all SVC_MAX chunks in that lane at every service,
   // and asked for the ones beyond SVC_AHEAD only then, with the whole group waiting for memory (1 % loud frames: every
   // second group holds one, 0.82 ms against 0.68).  Such groups request all of them a service ahead.
   // (ONE lambda, ONE array: the register allocator is touchy about the requests' destination registers -- with the two
   // cases in lambdas of their own behind a dispatching one it copied part of a destination right behind the request and
-  // waited for it there, 0.69 -> 0.75 ms with the feature compiled out; tools/check_decoder_isa.py looks for that.)
-#ifndef X3S_DENSE_AHEAD
-#define X3S_DENSE_AHEAD 1
-#endif
-  const bool dense_grp = X3S_DENSE_AHEAD && __any(active && plen > 9728u);   // (9 728: X3_DENSE_PAYLOAD_BYTES, the encoder's image)
+  // waited for it there, 0.69 -> 0.75 ms; tools/check_decoder_isa.py looks for that.)
+  const bool dense_grp = __any(active && plen > 9728u);   // (9 728: X3_DENSE_PAYLOAD_BYTES, the encoder's image)
   uint4 ld[SVC_MAX];
   uint32_t v_req = 0;
   auto fill_ring = [&]() {  // the first 128 bytes, and the requests of the first service
@@ -576,13 +409,11 @@ x3_decode_split_kernel(const uint8_t* __restrict__ x3, uint64_t x3_len, const ui
     }
     v_next += 16u * (fit > SVC_MAX ? SVC_MAX : fit);
     v_req = v_next;
-    if (!(X3S_KO & 32)) {
 #pragma unroll
-      for (int k = 0; k < (int)SVC_AHEAD; ++k) ld[k] = request(v_req + 16u * k);
-      if (dense_grp) {
+    for (int k = 0; k < (int)SVC_AHEAD; ++k) ld[k] = request(v_req + 16u * k);
+    if (dense_grp) {
 #pragma unroll
-        for (int k = (int)SVC_AHEAD; k < (int)SVC_MAX; ++k) ld[k] = request(v_req + 16u * k);
-      }
+      for (int k = (int)SVC_AHEAD; k < (int)SVC_MAX; ++k) ld[k] = request(v_req + 16u * k);
     }
   };
 
@@ -640,11 +471,10 @@ x3_decode_split_kernel(const uint8_t* __restrict__ x3, uint64_t x3_len, const ui
     const x3_u32x4 v1 = x3_lds_read_b128(c_src1 ^ flip);
     // a frame that failed is not written any further (the valuer says which)
     const bool ok0 = s_dead[4u * (lane >> 3) + c] == 0u, ok1 = s_dead[4u * ((lane >> 3) + 8u) + c] == 0u;
-    if (!(X3S_KO & 8) && pc >= p_lo && pc < p_hi) {
+    if (pc >= p_lo && pc < p_hi) {
       if (ok0) x3_store_stream16(line0 + (c_dst0 + 128u * n), v0);
       if (ok1) x3_store_stream16(line0 + (c_dst1 + 128u * n), v1);
     }
-    if (X3S_KO & 8) asm volatile("" :: "v"(v0.x), "v"(v1.x), "v"(v0.w), "v"(v1.w));
     X3_WAVE_LDS_ORDER();
   };
   // the same for one of EIGHT classes: one line of each of its eight rows
@@ -655,8 +485,9 @@ x3_decode_split_kernel(const uint8_t* __restrict__ x3, uint64_t x3_len, const ui
     if (pc >= p_lo && pc < p_hi && ok) x3_store_stream16(line0 + (c_dst + 128u * n), v);
     X3_WAVE_LDS_ORDER();
   };
-  // every class whose rows have completed a line: k_done = dwords of each row that are staged
-#ifndef X3S_HALF_LINES
+  // every class whose rows have completed a line: k_done = dwords of each row that are staged.  (Flushing 64-byte half
+  // lines as soon as each is complete was bit-exact and decoded in 0.94-1.00 ms against 0.67-0.70: whole lines are not
+  // negotiable)
 #define X3S_FLUSH_CLASS(c)                                                                                       \
   {                                                                                                              \
     const uint32_t ld = (ph[c] + k_done) >> 5;                                                                   \
@@ -683,28 +514,6 @@ x3_decode_split_kernel(const uint8_t* __restrict__ x3, uint64_t x3_len, const ui
     const uint32_t tail = ((ph[c] + (R0 >> 1)) & 31u) >> 2;                                                      \
     if (tail) flush_row(c, f_src[c & 3][c >> 2], f_dst[c & 3][c >> 2], nfl[c], nfl[c] ? 0u : ph[c] >> 2, tail);   \
   }
-#else
-  // EXPERIMENT (-DX3S_HALF_LINES; never shipped): the same flush in aligned 64-byte HALF lines, each as soon as it is
-  // complete -- what a group with 128-byte staging rows would do.  nfl counts half lines here.  Bit-exact
-  // (tools/scratch/half_check.py) and 0.94-1.00 ms against 0.67-0.70 on the same box: whole lines are not negotiable
-  // (DESIGN.md section 8).
-#define X3S_FLUSH_CLASS(c)                                                                                       \
-  {                                                                                                              \
-    const uint32_t hd = (ph[c] + k_done) >> 4;                                                                   \
-    if (hd > nfl[c]) {                                                                                           \
-      const uint32_t lo_ = 4u * (nfl[c] & 1u), first_ = ph[c] >> 2;                                              \
-      flush_class(c, f_src[c][0], f_src[c][1], f_dst[c][0], f_dst[c][1], nfl[c] >> 1,                            \
-                  (nfl[c] >> 1) == 0u && first_ > lo_ ? first_ : lo_, lo_ + 4u);                                 \
-      nfl[c] += 1u;                                                                                              \
-    }                                                                                                            \
-  }
-#define X3S_FLUSH_TAILS()                                                                                        \
-  _Pragma("unroll") for (uint32_t c = 0; c < 4; ++c) {                                                           \
-    const uint32_t tail = ((ph[c] + (R0 >> 1)) & 31u) >> 2; /* pieces of the last, partial line */               \
-    const uint32_t tline = (ph[c] + (R0 >> 1)) >> 5;        /* that line's number */                             \
-    if (tail) flush_class(c, f_src[c][0], f_src[c][1], f_dst[c][0], f_dst[c][1], tline, tline ? 0u : ph[c] >> 2, tail); \
-  }
-#endif
 
 
   if (flusher) {
@@ -765,41 +574,22 @@ x3_decode_split_kernel(const uint8_t* __restrict__ x3, uint64_t x3_len, const ui
       }
       X3_WAVE_LDS_ORDER();
     };
-    X3S_PLACE(X3S_PAD_F);
+    X3S_PLACE(0);
     for (uint32_t b = 0; b < nblk_max; ++b) {
-      X3S_PACE_STEP(b, X3S_ROLE_FLUSHER)
+      X3S_PACE_STEP(b)
       X3_STAMP(0);
       X3S_BARRIER();
       X3_STAMP(4);
-      if (!(X3S_KO & 2) && regular && b) {
+      if (regular && b) {
         const uint32_t k_done = have >> 1;
-#ifndef X3S_HALF_LINES
         if (cls8) {
           X3S_FLUSH_CLASS8(0) X3S_FLUSH_CLASS8(1) X3S_FLUSH_CLASS8(2) X3S_FLUSH_CLASS8(3)
           X3S_FLUSH_CLASS8(4) X3S_FLUSH_CLASS8(5) X3S_FLUSH_CLASS8(6) X3S_FLUSH_CLASS8(7)
-        } else
-#endif
-        {
+        } else {
           X3S_FLUSH_CLASS(0) X3S_FLUSH_CLASS(1) X3S_FLUSH_CLASS(2) X3S_FLUSH_CLASS(3)
         }
       }
       if (!regular && b) flush_rows();
-#if X3S_THIN && X3S_THIN_F
-      {   // TIMING ONLY: what converting 10 - K pairs of the block in place would cost this wave
-        const uint32_t* const tb = xfer + ((b + 1u) & 1u) * (X3S_XROWS * 64u);
-        uint32_t dz = lane, dn = 0u - 2u, dfw = 1u, dl = 1u, acc = 0;
-#pragma unroll
-        for (uint32_t q = X3S_THIN_K; q < 10u; ++q) {
-          const uint32_t t = tb[(q >> 1) * 128u + 2u * lane + (q & 1u)];
-          uint32_t z1, z2, v1, v2, t2, nn1, nn2;
-          asm volatile("v_ffbh_u32 %0, %7\n\tv_mad_i32_i24 %4, %0, %8, %9\n\tv_alignbit_b32 %6, %7, 0, %4\n\tv_bfe_u32 %1, %7, %4, %10\n\t"
-              "v_ffbh_u32 %2, %6\n\tv_mad_i32_i24 %5, %2, %8, %9\n\tv_bfe_u32 %3, %6, %5, %10"
-              : "=&v"(z1), "=&v"(v1), "=&v"(z2), "=&v"(v2), "=&v"(nn1), "=&v"(nn2), "=&v"(t2) : "v"(t), "v"(dz), "v"(dn), "v"(dfw));
-          acc = x3_pack_lo16((z1 << dl) + v1, (z2 << dl) + v2);
-          s_prm[(q & 3u) * 64u + lane] = acc;     // (a write of the same size, somewhere harmless)
-        }
-      }
-#endif
       const uint32_t cnt = rem < X3S_BL ? rem : X3S_BL;
       rem -= cnt;
       have = 1u + X3S_BL * b + cnt - ((cnt && rem == 0u) ? 0u : 1u);  // staged once the valuer is through block b
@@ -817,14 +607,11 @@ x3_decode_split_kernel(const uint8_t* __restrict__ x3, uint64_t x3_len, const ui
     }
     if (regular) {
       const uint32_t k_done = have >> 1;
-#ifndef X3S_HALF_LINES
       if (cls8) {
         X3S_FLUSH_CLASS8(0) X3S_FLUSH_CLASS8(1) X3S_FLUSH_CLASS8(2) X3S_FLUSH_CLASS8(3)
         X3S_FLUSH_CLASS8(4) X3S_FLUSH_CLASS8(5) X3S_FLUSH_CLASS8(6) X3S_FLUSH_CLASS8(7)
         X3S_FLUSH_TAILS8()
-      } else
-#endif
-      {
+      } else {
         X3S_FLUSH_CLASS(0) X3S_FLUSH_CLASS(1) X3S_FLUSH_CLASS(2) X3S_FLUSH_CLASS(3)
         X3S_FLUSH_TAILS()
       }
@@ -841,50 +628,34 @@ x3_decode_split_kernel(const uint8_t* __restrict__ x3, uint64_t x3_len, const ui
     const uint32_t a0 = 8u * (skip & 3u) + ebits;               // bits of the first word in front of the header
     const uint32_t widx0 = (skip >> 2) - (a0 == 0 ? 1u : 0u);  // a0 == 0: start with a fully consumed w0
     uint32_t s = (32u - a0) & 31u;
-    uint32_t w0 = X3S_RING_WORD(widx0), w1 = X3S_RING_WORD(widx0 + 1u);
-#if X3S_SWP
-    // (software-pipelined pair loop: a window of three words, wn is the word behind w2)
-    uint32_t w2 = X3S_RING_WORD(widx0 + 2u);
-    uint32_t wn = X3S_RING_WORD(widx0 + 3u);
-    uint32_t qb = 4u * ~(widx0 + 3u);
-#else
-    uint32_t wn = X3S_RING_WORD(widx0 + 2u);
-    // qb = (4 or 256) * ~(widx + 2): the byte offset of wn's slot before masking; widx itself is only needed by service()
-    uint32_t qb = (1u << X3S_QSH) * ~(widx0 + 2u);
-#endif
+    uint32_t w0 = row[~(widx0) & 31u], w1 = row[~(widx0 + 1u) & 31u];
+    uint32_t wn = row[~(widx0 + 2u) & 31u];
+    // qb = 4 * ~(widx + 2): the byte offset of wn's slot before masking; widx itself is only needed by service()
+    uint32_t qb = 4u * ~(widx0 + 2u);
     // consume -nn (<= 32) bits, given as the NEGATIVE count (that is what the codeword walk below has at hand);
     // the word shift is v_bfi with a VGPR mask (see x3_decode_fast_kernel)
     auto consume_to = [&](int32_t s2) {  // s2 = s - bits consumed (>= -32)
       const uint32_t m = (uint32_t)(s2 >> 31);
       s = (uint32_t)s2 & 31u;
       w0 = x3_bfi(m, w1, w0);
-#if X3S_SWP
-      w1 = x3_bfi(m, w2, w1);
-      w2 = x3_bfi(m, wn, w2);
-#else
       w1 = x3_bfi(m, wn, w1);
-#endif
       uint32_t addr;
-      asm("v_lshl_add_u32 %0, %2, " X3S_STR(X3S_QSH) ", %0\n\t"   // widx += 1 on a shift: qb -= 4 (256: transposed ring)
+      asm("v_lshl_add_u32 %0, %2, 2, %0\n\t"   // widx += 1 on a shift: qb -= 4
           "v_and_or_b32 %1, %0, %3, %4"
-          : "+v"(qb), "=v"(addr) : "v"(m), "v"(X3S_QMASK), "v"(row_base));
+          : "+v"(qb), "=v"(addr) : "v"(m), "v"(124u), "v"(row_base));
       wn = x3_lds_read_b32(addr);
       // keep the read HERE: left to itself the scheduler sinks it to just in front of the next shift, where its
       // whole LDS latency is waited for
       __builtin_amdgcn_sched_barrier(0);
     };
     auto consume_neg = [&](uint32_t nn) { consume_to((int32_t)(s + nn)); };
-#if X3S_SWP
-    auto ring_index = [&]() -> uint32_t { return ~((uint32_t)((int32_t)qb >> 2)) - 3u; };  // of w0
-#else
-    auto ring_index = [&]() -> uint32_t { return ~((uint32_t)((int32_t)qb >> X3S_QSH)) - 2u; };  // of w0
-#endif
+    auto ring_index = [&]() -> uint32_t { return ~((uint32_t)((int32_t)qb >> 2)) - 2u; };  // of w0
 
     const uint32_t k_tab = (p.k[1] << 16) | (p.k[2] << 24);  // log2(level) by ftype
     uint32_t over = 0;
-    X3S_PLACE(X3S_PAD_P);
+    X3S_PLACE(0);
     for (uint32_t b = 0; b < nblk_max; ++b) {
-      X3S_PACE_STEP(b, X3S_ROLE_PARSER)
+      X3S_PACE_STEP(b)
       const uint32_t cnt = remaining < X3S_BL ? remaining : X3S_BL;
       remaining -= cnt;
       X3_STAMP(0);
@@ -894,7 +665,7 @@ x3_decode_split_kernel(const uint8_t* __restrict__ x3, uint64_t x3_len, const ui
       // or behind the index: ADVICE r5)
       if (sg.out && b && (b % sg.sb) == 0u && cnt && b / sg.sb <= sg.pitch)
         sg.out[1 + f * (uint64_t)sg.pitch + (b / sg.sb - 1u)].x = (uint32_t)((int32_t)(32u * ring_index() + 32u - s) + v_rel);
-      if (!(X3S_KO & 16) && (b % X3S_PERIOD) == 0) service(ring_index());
+      if ((b % X3S_PERIOD) == 0) service(ring_index());
       X3_STAMP(1);
       // block header: 2 bits ftype; ftype 0 -> 4 more bits E-1 (decoder.rs:138-144, 209-216)
       const uint32_t hdr = __builtin_amdgcn_alignbit(w0, w1, s) >> 26;
@@ -915,46 +686,7 @@ x3_decode_split_kernel(const uint8_t* __restrict__ x3, uint64_t x3_len, const ui
       uint32_t* const buf = xfer + (b & 1u) * (X3S_XROWS * 64u);
       buf[X3S_PAIRS * 64u + lane] = hdr;
       X3_STAMP(2);
-      if ((X3S_KO & 4)) {
-      } else if (__all(cnt == X3S_BL || cnt == 0u)) {
-#if X3S_SWP
-        {
-          // ten pairs, software-pipelined (see X3S_SWP_PAIR).  Even pairs read the ring into wnb and use wn, odd pairs the
-          // other way round; pair i packs and stores the indices of pair i - 1 (row i - 1 of the block buffer: one dword per
-          // lane), the tail does so for pair 9 and settles the window: w2 up to date, the last read (into wn) arrived.
-          uint32_t tt, t2, nn1, nn2, ad, xa, xb, z1, z2, pv1, pv2, wnb, mp;
-          int32_t s2;
-          const uint32_t bufa = x3_lds_addr(buf) + 4u * lane;
-          asm volatile(
-              "v_mov_b32 %[mp], 0\n\t"
-              X3S_SWP_PAIR("wnb", "wn", "1", "")
-              X3S_SWP_PAIR("wn", "wnb", "1", X3S_SWP_STORE(0))
-              X3S_SWP_PAIR("wnb", "wn", "2", X3S_SWP_STORE(256))
-              X3S_SWP_PAIR("wn", "wnb", "2", X3S_SWP_STORE(512))
-              X3S_SWP_PAIR("wnb", "wn", "2", X3S_SWP_STORE(768))
-              X3S_SWP_PAIR("wn", "wnb", "2", X3S_SWP_STORE(1024))
-              X3S_SWP_PAIR("wnb", "wn", "2", X3S_SWP_STORE(1280))
-              X3S_SWP_PAIR("wn", "wnb", "2", X3S_SWP_STORE(1536))
-              X3S_SWP_PAIR("wnb", "wn", "2", X3S_SWP_STORE(1792))
-              X3S_SWP_PAIR("wn", "wnb", "2", X3S_SWP_STORE(2048))
-              "v_lshl_add_u32 %[xa], %[z1], %[lsh], %[pv1]\n\t"
-              "v_lshl_add_u32 %[xb], %[z2], %[lsh], %[pv2]\n\t"
-              "v_lshl_add_u32 %[qb], %[mp], 2, %[qb]\n\t"
-              "v_perm_b32 %[xa], %[xb], %[xa], %[sel]\n\t"
-              "ds_write_b32 %[buf], %[xa] offset:2304\n\t"
-              "s_waitcnt lgkmcnt(2)\n\t"
-              "v_bfi_b32 %[w2], %[mp], %[wn], %[w2]\n\t"
-              : [tt] "=&v"(tt), [t2] "=&v"(t2), [nn1] "=&v"(nn1), [nn2] "=&v"(nn2), [ad] "=&v"(ad), [xa] "=&v"(xa),
-                [xb] "=&v"(xb), [z1] "=&v"(z1), [z2] "=&v"(z2), [pv1] "=&v"(pv1), [pv2] "=&v"(pv2), [wnb] "=&v"(wnb),
-                [mp] "=&v"(mp), [s2] "=&v"(s2), [w0] "+v"(w0), [w1] "+v"(w1), [w2] "+v"(w2), [wn] "+v"(wn), [s] "+v"(s),
-                [qb] "+v"(qb)
-              : [zmask] "v"(zmask), [nwidth] "v"(nwidth), [fw] "v"(fw), [lsh] "v"(lsh), [rowb] "v"(row_base), [buf] "v"(bufa),
-                [c124] "s"(124u), [sel] "s"(0x05040100u)
-              : "memory");
-          // the word behind the settled window, as consume_to leaves it (the compiler tracks this read)
-          wn = x3_lds_read_b32(x3_and_or(qb, 124u, row_base));
-        }
-#else
+      if (__all(cnt == X3S_BL || cnt == 0u)) {
         // two samples per 32-bit peek and per window update (two valid codewords are <= 32 bits)
         uint2* const b2 = reinterpret_cast<uint2*>(buf) + lane;
 #pragma unroll
@@ -969,21 +701,6 @@ x3_decode_split_kernel(const uint8_t* __restrict__ x3, uint64_t x3_len, const ui
             // shift count (the hardware uses its low five bits): 4 instructions per codeword.  One asm block, so that the
             // compiler neither pads the dependent chain with s_nop nor reorders it.
             const uint32_t t = __builtin_amdgcn_alignbit(w0, w1, s);
-#if X3S_THIN
-            // the lengths only: the valuer takes z and the fields from the peek (x3s_fields)
-            uint32_t z1, z2, t2, nn1, nn2;
-            int32_t s2;
-            asm("v_ffbh_u32 %0, %6\n\t"
-                "v_mad_i32_i24 %2, %0, %7, %8\n\t"
-                "v_alignbit_b32 %4, %6, 0, %2\n\t"
-                "v_ffbh_u32 %1, %4\n\t"
-                "v_mad_i32_i24 %3, %1, %7, %8\n\t"
-                "v_add3_u32 %5, %9, %2, %3"
-                : "=&v"(z1), "=&v"(z2), "=&v"(nn1), "=&v"(nn2), "=&v"(t2), "=&v"(s2)
-                : "v"(t), "v"(zmask), "v"(nwidth), "v"(s));
-            consume_to(s2);
-            X[e] = t;
-#elif X3S_PAIR_ASM2 && !X3S_SWP
             // (round 5) ... and the sign of the bit counter, the ring byte counter and the address of the next ring word
             // in the same block: a compiler-made instruction that reads what an asm block wrote gets an `s_nop 0` in
             // front (the dst_sel forwarding hazard, assumed for any asm) -- one per pair on the parser's path
@@ -998,11 +715,11 @@ x3_decode_split_kernel(const uint8_t* __restrict__ x3, uint64_t x3_len, const ui
                 "v_bfe_u32 %[v2], %[t2], %[nn2], %[fw]\n\t"
                 "v_add3_u32 %[s2], %[s], %[nn1], %[nn2]\n\t"
                 "v_ashrrev_i32 %[m], 31, %[s2]\n\t"
-                "v_lshl_add_u32 %[qb], %[m], " X3S_STR(X3S_QSH) ", %[qb]\n\t"
+                "v_lshl_add_u32 %[qb], %[m], 2, %[qb]\n\t"
                 "v_and_or_b32 %[addr], %[qb], %[c124], %[rowb]"
                 : [z1] "=&v"(z1), [v1] "=&v"(v1), [z2] "=&v"(z2), [v2] "=&v"(v2), [nn1] "=&v"(nn1), [nn2] "=&v"(nn2),
                   [t2] "=&v"(t2), [s2] "=&v"(s2), [m] "=&v"(m), [addr] "=&v"(addr), [qb] "+v"(qb)
-                : [t] "v"(t), [zmask] "v"(zmask), [nwidth] "v"(nwidth), [s] "v"(s), [fw] "v"(fw), [c124] "v"(X3S_QMASK), [rowb] "v"(row_base));
+                : [t] "v"(t), [zmask] "v"(zmask), [nwidth] "v"(nwidth), [s] "v"(s), [fw] "v"(fw), [c124] "v"(124u), [rowb] "v"(row_base));
             {
               const uint32_t wn_new = x3_lds_read_b32(addr);
               __builtin_amdgcn_sched_barrier(0);   // (the read stays here: see consume_to)
@@ -1012,26 +729,9 @@ x3_decode_split_kernel(const uint8_t* __restrict__ x3, uint64_t x3_len, const ui
               wn = wn_new;
             }
             X[e] = x3_pack_lo16((z1 << lsh) + v1, (z2 << lsh) + v2);
-#else
-            uint32_t z1, z2, v1, v2, t2, nn1, nn2;
-            int32_t s2;
-            asm("v_ffbh_u32 %0, %8\n\t"
-                "v_mad_i32_i24 %4, %0, %9, %10\n\t"
-                "v_alignbit_b32 %6, %8, 0, %4\n\t"
-                "v_bfe_u32 %1, %8, %4, %12\n\t"
-                "v_ffbh_u32 %2, %6\n\t"
-                "v_mad_i32_i24 %5, %2, %9, %10\n\t"
-                "v_bfe_u32 %3, %6, %5, %12\n\t"
-                "v_add3_u32 %7, %11, %4, %5"
-                : "=&v"(z1), "=&v"(v1), "=&v"(z2), "=&v"(v2), "=&v"(nn1), "=&v"(nn2), "=&v"(t2), "=&v"(s2)
-                : "v"(t), "v"(zmask), "v"(nwidth), "v"(s), "v"(fw));
-            consume_to(s2);
-            X[e] = x3_pack_lo16((z1 << lsh) + v1, (z2 << lsh) + v2);
-#endif
           }
           b2[(j >> 1) * 64u] = make_uint2(X[0], X[1]);
         }
-#endif
       } else {
         // a block that is short in some lane (the last block of a frame): one sample at a time
         uint16_t* const h = reinterpret_cast<uint16_t*>(buf);
@@ -1089,27 +789,10 @@ x3_decode_split_kernel(const uint8_t* __restrict__ x3, uint64_t x3_len, const ui
     X3S_BARRIER();  // (s_dead is cleared)
 
     const uint32_t bound_tab = (p.inv_len[0] << 8) | (p.inv_len[1] << 16) | (p.inv_len[2] << 24);  // by ftype (< 256)
-#if X3S_THIN
-    const uint32_t k_tab_v = (p.k[1] << 16) | (p.k[2] << 24);  // log2(level) by ftype (the parser's k_tab)
-    // a pair's peek -> its two indices (z << k) + r / fields, packed: exactly what the parser computed until round 4
-    auto x3s_fields = [&](uint32_t t, uint32_t zmask_, uint32_t nwidth_, uint32_t fw_, uint32_t lsh_) __attribute__((always_inline)) -> uint32_t {
-      uint32_t z1, z2, v1, v2, t2, nn1, nn2;
-      asm("v_ffbh_u32 %0, %7\n\t"
-          "v_mad_i32_i24 %4, %0, %8, %9\n\t"
-          "v_alignbit_b32 %6, %7, 0, %4\n\t"
-          "v_bfe_u32 %1, %7, %4, %10\n\t"
-          "v_ffbh_u32 %2, %6\n\t"
-          "v_mad_i32_i24 %5, %2, %8, %9\n\t"
-          "v_bfe_u32 %3, %6, %5, %10"
-          : "=&v"(z1), "=&v"(v1), "=&v"(z2), "=&v"(v2), "=&v"(nn1), "=&v"(nn2), "=&v"(t2)
-          : "v"(t), "v"(zmask_), "v"(nwidth_), "v"(fw_));
-      return x3_pack_lo16((z1 << lsh_) + v1, (z2 << lsh_) + v2);
-    };
-#endif
     uint32_t posb = pos0;  // ring byte of the block's first pair, unmasked
-    X3S_PLACE(X3S_PAD_V);
+    X3S_PLACE(0);
     for (uint32_t b = 0; b < nblk_max; ++b, posb += 2u * X3S_BL) {
-      X3S_PACE_STEP(b, X3S_ROLE_VALUER)
+      X3S_PACE_STEP(b)
       X3_STAMP(0);
       X3S_BARRIER();
       X3_STAMP(4);
@@ -1132,114 +815,25 @@ x3_decode_split_kernel(const uint8_t* __restrict__ x3, uint64_t x3_len, const ui
         st = X3D_FRAME_DECODE_INVALID_BPF;
         alive = false;
       }
-#if X3S_THIN
-      // the codeword geometry of this lane's block, as the parser derives it (thin parser: the walk is repeated here)
-      const uint32_t t_width = x3_bfi(zmask, (1u << ftype) >> 1, E);                 // Rice 1,2,4; BFP E
-      const uint32_t t_kk = (k_tab_v >> (8u * ftype)) & 0xFFu;                       // 0, 0, k1, k2
-      const uint32_t t_fw = x3_bfi(zmask, t_kk, t_width);
-      const uint32_t t_lsh = x3_bfi(zmask, t_kk, 31u);
-      const uint32_t t_nwidth = 0u - t_width;
-#endif
       const uint32_t tm12 = ((neg_thresh - 1u) & 0xFFFFu) * 0x10001u;  // thresh - 1 in each half
       const uint32_t neg22 = (neg2 & 0xFFFFu) * 0x10001u;              // 2 * thresh = 2^E (0 for a literal block)
       uint32_t maxii2 = 0;
       X3_STAMP(2);
 
-      if ((X3S_KO & 1)) {
-      } else if (__all(cnt == X3S_BL || cnt == 0u)) {
+      if (__all(cnt == X3S_BL || cnt == 0u)) {
         // the whole block's indices at once (five 8-byte reads in flight), then ten pairs from registers
         uint2 XX[5];
-#if X3S_SWP
-#pragma unroll
-        for (uint32_t r = 0; r < 5u; ++r) XX[r] = make_uint2(buf[(2u * r) * 64u + lane], buf[(2u * r + 1u) * 64u + lane]);
-#else
         const uint2* const b2 = reinterpret_cast<const uint2*>(buf) + lane;
 #pragma unroll
         for (uint32_t r = 0; r < 5u; ++r) XX[r] = b2[r * 64u];
-#endif
-#if X3S_VALUER_FOLD
-        // Round 4: the Rice / BFP choice is in the CONSTANTS, not in a select behind both computations.  A Rice lane's
-        // thresh is 0 (B = X - ((X + 0xFFFF) & 0) = X: the BFP step is the identity there); a BFP lane shifts by 0 and
-        // takes no sign bit (zsh2 = 0: the zigzag step is the identity there).  One instruction per pair less than
-        // R, B and v_bfi -- and the literal select (0.1 % of config 3's blocks) only runs in blocks in which some lane
-        // of the wave HAS a literal block (6 % of them).
-        const uint32_t zsh2 = zmask & 0x00010001u;   // per half: shift and sign-bit mask of the zigzag step
-        auto pairs = [&](auto lit_tag) __attribute__((always_inline)) {
-          constexpr bool LIT = decltype(lit_tag)::value;
-#pragma unroll
-          for (uint32_t r = 0; r < 5u; ++r) {
-            uint32_t W[2];
-#pragma unroll
-            for (uint32_t e = 0; e < 2; ++e) {
-#if X3S_THIN
-              const uint32_t X = (2u * r + e < X3S_THIN_K) ? x3s_fields(e ? XX[r].y : XX[r].x, zmask, t_nwidth, t_fw, t_lsh) : (e ? XX[r].y : XX[r].x);
-#else
-              const uint32_t X = e ? XX[r].y : XX[r].x;
-#endif
-              maxii2 = x3_pk_max_u16(maxii2, X);   // (Rice: X = i, the index into the inverse table, decoder.rs:186)
-              // BFP: unsigned_to_i16 (decoder.rs:198-207): v - (v > thresh ? 2*thresh : 0), strict compare.
-              // v < 2^E and thresh = 2^(E-1), so bit E of v + thresh - 1 says v > thresh.
-              const uint32_t B = x3_pk_sub_u16(X, x3_pk_add_u16(X, tm12) & neg22);
-              // Rice: the inverse table is a zigzag (x3.rs:200-204)
-              const uint32_t D = x3_pk_lshr_b16(B, zsh2) ^ x3_pk_sub_u16(0u, B & zsh2);   // (d1, d2)
-              // (last + d1, last + d1 + d2), last = the high half of the previous pair: both halves of D plus last,
-              // then d1 once more onto the high half
-              uint32_t P = x3_pk_mad_u16_alo(D, 0x00010000u, x3_pk_add_u16_bhi(D, prevP));
-              if (LIT) P = x3_bfi(litmask, X, P);                          // literal: field = sample
-              W[e] = __builtin_amdgcn_alignbit(P, prevP, 16);                // (pending sample, la)
-              prevP = P;
-            }
-            // samples 20 b + 4 r .. + 3: eight bytes of the ring (positions are multiples of 8: no wrap inside)
-            x3_lds_write_b64(x3_and_or(posb + 8u * r, 248u, orow_b), W[0], W[1]);
-          }
-        };
-        if (__any(litmask != 0u)) pairs(std::true_type{}); else pairs(std::false_type{});
-#elif X3S_VALUER_ASM && !X3S_THIN
-        // Round 5: the thirteen instructions of a pair as ONE asm block.  As single-instruction helpers the compiler puts
-        // an `s_nop 0` behind most of them (it cannot see into an asm and assumes that one which feeds the next may have
-        // written half a register: the dst_sel forwarding hazard of gfx94x -- packed instructions write whole registers);
-        // forty issue slots per block in this wave, a quarter more than its arithmetic.  Same arithmetic, same order.
-        {
-          const uint32_t c10001 = 0x00010001u, c10000 = 0x00010000u;
-#pragma unroll
-          for (uint32_t r = 0; r < 5u; ++r) {
-            uint32_t W[2];
-#pragma unroll
-            for (uint32_t e = 0; e < 2; ++e) {
-              const uint32_t X = e ? XX[r].y : XX[r].x;
-              uint32_t t0, t1, t2, P;
-              asm("v_pk_max_u16 %[mx], %[mx], %[X]\n\t"
-                  "v_and_b32 %[t0], %[c10001], %[X]\n\t"
-                  "v_pk_lshrrev_b16 %[t1], 1, %[X] op_sel_hi:[0,1]\n\t"
-                  "v_pk_sub_u16 %[t0], 0, %[t0]\n\t"
-                  "v_pk_add_u16 %[t2], %[X], %[tm12]\n\t"
-                  "v_xor_b32 %[t1], %[t0], %[t1]\n\t"
-                  "v_and_b32 %[t2], %[t2], %[neg22]\n\t"
-                  "v_pk_sub_u16 %[t2], %[X], %[t2]\n\t"
-                  "v_bfi_b32 %[t1], %[zmask], %[t1], %[t2]\n\t"
-                  "v_pk_add_u16 %[t2], %[t1], %[prev] op_sel:[0,1] op_sel_hi:[1,1]\n\t"
-                  "v_pk_mad_u16 %[t1], %[t1], %[c10000], %[t2] op_sel:[0,0,0] op_sel_hi:[0,1,1]\n\t"
-                  "v_bfi_b32 %[P], %[litmask], %[X], %[t1]\n\t"
-                  "v_alignbit_b32 %[W], %[P], %[prev], 16"
-                  : [mx] "+v"(maxii2), [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [P] "=&v"(P), [W] "=&v"(W[e])
-                  : [X] "v"(X), [tm12] "v"(tm12), [neg22] "v"(neg22), [zmask] "v"(zmask), [litmask] "v"(litmask), [prev] "v"(prevP),
-                    [c10001] "s"(c10001), [c10000] "v"(c10000));
-              prevP = P;
-            }
-            x3_lds_write_b64(x3_and_or(posb + 8u * r, 248u, orow_b), W[0], W[1]);
-          }
-        }
-#else
+        // (Round 4 folded the Rice / BFP choice into the constants -- two of these thirteen instructions per pair less --
+        // and was no faster: profiles/r4/decoder_valuer_fold_and_late_groups.txt)
 #pragma unroll
         for (uint32_t r = 0; r < 5u; ++r) {
           uint32_t W[2];
 #pragma unroll
           for (uint32_t e = 0; e < 2; ++e) {
-#if X3S_THIN
-            const uint32_t X = (2u * r + e < X3S_THIN_K) ? x3s_fields(e ? XX[r].y : XX[r].x, zmask, t_nwidth, t_fw, t_lsh) : (e ? XX[r].y : XX[r].x);
-#else
             const uint32_t X = e ? XX[r].y : XX[r].x;
-#endif
             // Rice: X = i, the index into the inverse table (decoder.rs:186), which is a zigzag (x3.rs:200-204)
             maxii2 = x3_pk_max_u16(maxii2, X);
             const uint32_t R = x3_pk_lshr_b16_1(X) ^ x3_pk_sub_u16(0u, X & 0x00010001u);
@@ -1257,7 +851,6 @@ x3_decode_split_kernel(const uint8_t* __restrict__ x3, uint64_t x3_len, const ui
           // samples 20 b + 4 r .. + 3: eight bytes of the ring (positions are multiples of 8: no wrap inside)
           x3_lds_write_b64(x3_and_or(posb + 8u * r, 248u, orow_b), W[0], W[1]);
         }
-#endif
       } else {
         // short block somewhere in the group: one sample at a time, staged as halfwords
         const uint16_t* const h = reinterpret_cast<const uint16_t*>(buf);

@@ -7,16 +7,14 @@
 // ------------------------------------------------------------------------------------------------
 // encode
 // ------------------------------------------------------------------------------------------------
-// x3_encode_stream2_kernel has no "diff outside the reference's Rice table" test (the reference panics there:
-// X3_ERR_BAD_ARG from the two-pass kernels): true when no block can need it.  A block with max|d| = m <= thr[2] is
-// coded with code[ft(m)], ft = [m > thr0] + [m > thr1] (encoder.rs:241-247); it is inside that code's table when
-// m <= min(offset, len - offset - 1).
-#ifndef X3_ENC_FRAME_ALIGN
 // samples between frame starts that the single-pass encoders take: 4 = frames on 8-byte boundaries of a buffer that is
 // itself dword aligned.  (Their sample loads are range-checked 16-byte BUFFER loads, which need dword alignment only; until round 4 this was 8 -- frames of an odd
 // number of blocks went to the two-pass kernels, 3.6 ms against 0.45 for 501 blocks a frame.)
 #define X3_ENC_FRAME_ALIGN 4u
-#endif
+// x3_encode_stream2_kernel has no "diff outside the reference's Rice table" test (the reference panics there:
+// X3_ERR_BAD_ARG from the two-pass kernels): true when no block can need it.  A block with max|d| = m <= thr[2] is
+// coded with code[ft(m)], ft = [m > thr0] + [m > thr1] (encoder.rs:241-247); it is inside that code's table when
+// m <= min(offset, len - offset - 1).
 static bool stream_safe_thresholds(const x3_params* p) {
   uint32_t mmax[3] = {0, 0, 0};
   bool used[3] = {false, false, false};

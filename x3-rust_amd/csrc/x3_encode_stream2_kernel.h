@@ -36,15 +36,8 @@
 
 #include "x3_encode_common.h"
 
-#ifndef X3E_PACE_CLIMB
-#define X3E_PACE_CLIMB 1
-#endif
-#ifndef X3E_PACE_DIV
 #define X3E_PACE_DIV 16u  // the target is the slowest workgroup's pace of the launch before less 1/DIV
-#endif
-#ifndef X3E_BAND
 #define X3E_BAND 16  // sixteenths of a frame ahead / behind that move a workgroup one priority level
-#endif
 #define X3_STREAM2_THREADS 512u
 #define X3_STREAM2_MAX_GRID 1024u  // two size words per thread cover 1023 predecessors
 #define X3_STREAM2_DESC_PAD 1088u  // words in front of desc[0]: the windows of the first frames reach below frame 0
@@ -77,9 +70,7 @@ typedef uint32_t x3_v2u32 __attribute__((ext_vector_type(2)));
 // Waves per SIMD the register budget is cut for: 6 = 80 VGPRs (79 used) = three workgroups per CU, which is also what
 // two worst-case frame images per workgroup leave room for in LDS.  Four per CU were tried with 12 KB images (enough for
 // config 3) and a 64-VGPR build: 9 registers spill, 0.72 ms with three workgroups, 0.67 ms with four -- against 0.615.
-#ifndef X3E_WAVES_PER_SIMD
 #define X3E_WAVES_PER_SIMD 6
-#endif
 // A payload of more than this many bytes does not fit the wave encoder's LDS image (x3_encode_wave_kernel.h: 38 rows of
 // 256 bytes).  The control block's word X3_CTL_DENSE_COUNT counts a call's frames beyond it: the wave encoder leaves
 // them to this kernel's LIST form, and the host reads the count as a hint for the next call (x3_encode.hip).
@@ -350,12 +341,10 @@ x3_encode_stream2_kernel(const int16_t* __restrict__ wav, X3Geom g, X3DevParams 
       if (pace_target >= 64u) pace_inv = (16u << 16) / pace_target;
     } else {
       uint32_t t = P - P / X3E_PACE_DIV;
-#if X3E_PACE_CLIMB
       if (T >= 64u) {
         const uint32_t r = (P << 8) / T;  // 256 = met exactly
         t = r < 261u ? T - T / 24u : (r < 266u ? T - T / 64u : (r <= 279u ? T : P - P / X3E_PACE_DIV));  // (met by a wide margin: 4 % faster)
       }
-#endif
       pace_target = t;
       pace_inv = (16u << 16) / t;
     }

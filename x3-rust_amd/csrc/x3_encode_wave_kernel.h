@@ -41,40 +41,15 @@
 #pragma once
 #include "x3_encode_stream2_kernel.h"
 
-#ifndef X3W_CLAIM
-#define X3W_CLAIM 1
-#endif
-#ifndef X3W_PRIO
-#define X3W_PRIO 1  // 1: priorities from the arrival rank in the workgroup's generation; >= 2: this priority until the size is out; 0: none
-#endif
-#ifndef X3W_BARRIER
-#define X3W_BARRIER 0
-#endif
 // Polls are far apart: a waiting wave that looks again every 128 clocks takes issue slots and LDS / L2 bandwidth from the
 // waves it is waiting for.  s_sleep 24 (1 500 clocks) between looks at the workgroup's LDS words and 127 (8 000 clocks)
 // between trips to the size words: 0.4225 ms on every box seen, against 0.427-0.439 with 2 and 8
 // (sweeps of five pairs of values x four to six processes on three boxes, round 3).
-#ifndef X3W_SLEEP_LDS
 #define X3W_SLEEP_LDS 24
-#endif
-#ifndef X3W_SLEEP_DESC
 #define X3W_SLEEP_DESC 127
-#endif
 // bounded waits of about 25 ms with those sleeps
 #define X3W_SPINS_LDS (X3_SPIN_LIMIT << 2)
 #define X3W_SPINS_DESC (X3_SPIN_LIMIT >> 1)
-#ifndef X3W_SKIP_EMPTY_HALF
-#define X3W_SKIP_EMPTY_HALF 1
-#endif
-#ifndef X3W_NOWAIT
-#define X3W_NOWAIT 0
-#endif
-#if X3W_NOWAIT && !defined(X3_EXPERIMENT)
-#error "X3W_NOWAIT builds give wrong results (frames land at wrong offsets): experiment builds only (-DX3_EXPERIMENT)"
-#endif
-#ifndef X3W_COPY_UNROLL
-#define X3W_COPY_UNROLL 2
-#endif
 #define X3W_WAVES 16u
 #define X3W_THREADS (64u * X3W_WAVES)
 // (X3W_TAB_BYTES: x3_tables.h)
@@ -573,12 +548,8 @@ __global__ void __launch_bounds__(X3W_THREADS) x3_encode_wave_kernel(X3WaveArgs 
     const uint32_t gtag = ((prev_gen + 1u) & 0xFFFu) << X3_DESC_BYTES_BITS;
     const uint32_t L = prev_L, frame_bytes = 20u + prev_L, rtot = (prev_L + 255u) >> 8;
     uint32_t intra = 0;
-#if X3W_NOWAIT
-    // timing experiment only (the stream is NOT valid): every frame at a fixed stride, nobody waits for anybody
-    gen_base = prev_f * 10240ull;
-#endif
     X3W_TL(prev_gen, 1);
-    if (!X3W_NOWAIT) {
+    {
       // the wave's predecessors in that generation (LDS)
       uint32_t spins = 0;
       for (;;) {
@@ -601,8 +572,8 @@ __global__ void __launch_bounds__(X3W_THREADS) x3_encode_wave_kernel(X3WaveArgs 
     }
     // The generation's base is the same for the sixteen waves: whoever has summed it leaves it in LDS, the others
     // take it from there (about one wave in two pays the trip to the descriptors: they arrive in clusters).
-    bool have_base = X3W_NOWAIT != 0;
-    if (!lost && !X3W_NOWAIT) {
+    bool have_base = false;
+    if (!lost) {
       const uint32_t t = __hip_atomic_load(&book[160u + par], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
       if (t == gtag) {
         const uint32_t lo = __hip_atomic_load(&book[168u + par], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -611,7 +582,6 @@ __global__ void __launch_bounds__(X3W_THREADS) x3_encode_wave_kernel(X3WaveArgs 
         have_base = true;
       }
     }
-#if X3W_CLAIM
     // one wave per generation makes the trip; the others wait for its result in LDS (the descriptors are polled by
     // 256 waves instead of 4 096)
     if (!lost && !have_base) {
@@ -638,7 +608,6 @@ __global__ void __launch_bounds__(X3W_THREADS) x3_encode_wave_kernel(X3WaveArgs 
         X3W_DBG(dbg_cnt[3] += clock64() - tw0;)
       }
     }
-#endif
     if (!lost && !have_base) {
       const uint32_t need = prev_gen == 0 ? b : a.nwg;  // totals in front of generation prev_wgi that count
       const bool in0 = lane < need, in1 = lane + 64u < need, in2 = lane + 128u < need, in3 = lane + 192u < need;
@@ -733,11 +702,7 @@ __global__ void __launch_bounds__(X3W_THREADS) x3_encode_wave_kernel(X3WaveArgs 
         uint8_t* const abase = pdst + head;                     // 16-byte aligned
         // memory order of a stored dword = stream order: bytes (31..24), (23..16), (15..8), (7..0) of the image's value
         if (head & 2u) {
-#if X3W_COPY_UNROLL == 2
 #pragma unroll 2
-#elif X3W_COPY_UNROLL == 3
-#pragma unroll 3
-#endif
           for (uint32_t u = lane; u < nfull; u += 64u) {
             const uint32_t ia = img_addr + ((head + 16u * u) & ~3u);  // the unit starts in the low half of this dword
             const uint32_t v0 = x3_lds_read_b32(ia), v1 = x3_lds_read_b32(ia + 4u), v2 = x3_lds_read_b32(ia + 8u),
@@ -747,11 +712,7 @@ __global__ void __launch_bounds__(X3W_THREADS) x3_encode_wave_kernel(X3WaveArgs 
             *reinterpret_cast<x3_u32x4*>(abase + 16u * u) = vv;
           }
         } else {
-#if X3W_COPY_UNROLL == 2
 #pragma unroll 2
-#elif X3W_COPY_UNROLL == 3
-#pragma unroll 3
-#endif
           for (uint32_t u = lane; u < nfull; u += 64u) {
             const uint32_t ia = img_addr + head + 16u * u;
             const uint32_t v0 = x3_lds_read_b32(ia), v1 = x3_lds_read_b32(ia + 4u), v2 = x3_lds_read_b32(ia + 8u),
@@ -803,19 +764,16 @@ __global__ void __launch_bounds__(X3W_THREADS) x3_encode_wave_kernel(X3WaveArgs 
       // (opaque per frame: nothing derived from the lane index is kept in registers across the loop -- hipcc otherwise
       // hoists a dozen lane masks and offsets out of it and spills them)
       asm volatile("" : "+v"(lane));
-#if X3W_PRIO == 1
       // Feedback priorities.  The SQ issues oldest-first, so left alone the first wave of every SIMD runs a generation
       // ahead and then sits at its offset wait for the sizes of the waves it has starved, and the SIMD runs on the
       // waves that are left.  A wave's arrival rank among the sixteen of its workgroup generation says where it
-      // stands: the first arrivers yield, the last ones are served first.
+      // stands: the first arrivers yield, the last ones are served first.  (Lining the waves up instead -- one s_barrier
+      // behind the analyses -- made the launch 6 % slower: the stagger keeps the SIMDs and the LDS pipe mixed; DESIGN_HISTORY.md,
+      // round 3's section 4, "Encoder, third generation".)
       if (rank >= 12u) __builtin_amdgcn_s_setprio(3);
       else if (rank >= 8u) __builtin_amdgcn_s_setprio(2);
       else if (rank >= 4u) __builtin_amdgcn_s_setprio(1);
       else __builtin_amdgcn_s_setprio(0);
-#elif X3W_PRIO >= 2
-      // a wave that still owes its frame's size goes first: everybody's offsets wait for it
-      __builtin_amdgcn_s_setprio(X3W_PRIO);
-#endif
       const uint32_t tail = (n - 1u) % 20u;
       const bool plain = tail == 0u || tail == 19u;  // every block has 20 samples, or 19 in the frame's last block
 #ifdef X3_DBG_STAMPS
@@ -897,7 +855,7 @@ __global__ void __launch_bounds__(X3W_THREADS) x3_encode_wave_kernel(X3WaveArgs 
         mB = m2 | (m3 << 16);
         mC = 0;
         mD = 0;
-        if (X3W_SKIP_EMPTY_HALF && n <= X3W_PART + 1u) {
+        if (n <= X3W_PART + 1u) {
           // (a frame of at most 5 121 samples has nothing in its second half: no analysis, no emission, no loads for it --
           // 256 blocks a frame 0.58 -> 0.48 ms, 100 blocks 1.34 -> 1.06; config 3 the same)
         } else {
@@ -941,10 +899,6 @@ __global__ void __launch_bounds__(X3W_THREADS) x3_encode_wave_kernel(X3WaveArgs 
         }
       }
       X3_STAMP(1);
-#if X3W_BARRIER
-      // experiment: the sixteen waves of the workgroup meet behind their analyses (waves that have ended do not count)
-      __builtin_amdgcn_s_barrier();
-#endif
 
       // ---- C: bit offsets (the BitPacker's running position as two wave scans)
       uint32_t excl0, excl1, tot0, tot1;  // (only the exclusive sums stay: whether a lane has blocks is in its metas)
@@ -996,9 +950,6 @@ __global__ void __launch_bounds__(X3W_THREADS) x3_encode_wave_kernel(X3WaveArgs 
       }
       rank = (uint32_t)__builtin_amdgcn_readfirstlane((int)arrived);
       X3W_TL(gen, 0);
-#if X3W_PRIO >= 2
-      __builtin_amdgcn_s_setprio(0);
-#endif
       // the geometry of this wave's next frame
       bool have_next;
       uint32_t n_next = 0;
@@ -1018,12 +969,10 @@ __global__ void __launch_bounds__(X3W_THREADS) x3_encode_wave_kernel(X3WaveArgs 
       X3_STAMP(2);
 
       // ---- the frame in waiting leaves its image now (its size went out a whole iteration ago)
-#ifndef X3W_SKEW2_TIMING
       if (have_prev) {
         finish_prev();
         if (lost) break;
       }
-#endif
 
       // ---- D: emission, half 0 then half 1; the next frame's halves are requested as their registers fall free.
       // Lane 0 starts with the frame's first sample.  (The block sizes are worked out again rather than kept from the
@@ -1093,7 +1042,7 @@ __global__ void __launch_bounds__(X3W_THREADS) x3_encode_wave_kernel(X3WaveArgs 
         if ((mA | mB) || lane == 0) e.finish();
       }
       if (have_next) load_half(X0, src_next, n_next, 0);
-      if (!ovf && !(X3W_SKIP_EMPTY_HALF && n <= X3W_PART + 1u)) {
+      if (!ovf && n > X3W_PART + 1u) {
         X3WEmit e;
         e.start(16u + tot0 + excl1, img_addr);
         if constexpr (BL == 10u) {
@@ -1206,17 +1155,9 @@ __global__ void __launch_bounds__(X3W_THREADS) x3_encode_wave_kernel(X3WaveArgs 
       }
       // the next frame's second half: behind the CRC pass (whose look-ups want the registers), in front of the
       // analysis of its first half
-      if (have_next && !(X3W_SKIP_EMPTY_HALF && n_next <= X3W_PART + 1u)) load_half(X1, src_next, n_next, 1);
+      if (have_next && n_next > X3W_PART + 1u) load_half(X1, src_next, n_next, 1);
       X3_STAMP(4);
 
-#ifdef X3W_SKEW2_TIMING
-      // timing experiment only (the stream is NOT valid): the frame before leaves its image BEHIND this frame's emission
-      // and CRC pass, as it could if a wave had room for two images
-      if (have_prev) {
-        finish_prev();
-        if (lost) break;
-      }
-#endif
       // ---- this frame waits in its image; the wave goes on to its next one
       have_prev = true;
       prev_ovf = ovf;

@@ -27,9 +27,6 @@
 #define X3I_IO 4u       // header fine, payload inside the bytes the reader believes in but past the real end: Io
 #define X3I_NONE 0xFFFFFFFFu
 #define X3I_READ_BUFFER 24576u
-#ifndef X3I_DEFER_CHECK
-#define X3I_DEFER_CHECK 1
-#endif
 #define X3I_WG_RAW 384u     // places with the key that a workgroup of x3_index_candidates_kernel lists before it checks them
 #define X3I_WG_CANDS 256u   // candidates a workgroup of x3_index_candidates_kernel collects before it touches the global counter
 
@@ -121,7 +118,7 @@ x3_index_candidates_kernel(const uint32_t* __restrict__ xw, uint64_t len, uint64
   // nothing requested ahead and half the instructions per trip: 113 us; without the fifth dword: 103.  A bare read of the
   // same bytes, one span per workgroup, takes 58 us (tools/ubench/read_rate.hip: 6.3 TB/s): it is not the loads.  It was
   // the candidates: each header read in the loop held its wave for a memory round trip -- checked behind the loop, all at
-  // once (X3I_DEFER_CHECK): 74 us.)
+  // once (s_raw, below): 74 us.)
   auto fetch = [&](uint64_t t, uint32_t (&w)[5]) {
     if (t >= t_end) {
 #pragma unroll
@@ -180,10 +177,10 @@ x3_index_candidates_kernel(const uint32_t* __restrict__ xw, uint64_t len, uint64
       if (hw != 0x3378u) continue;  // bytes 0x78 0x33
       const uint64_t off = 16 * t + b;
       if (off + 20 > len) continue;
-      // the key is there: the header is read and checked BEHIND the loop, all of the workgroup's at once (X3I_DEFER_CHECK;
-      // in the loop every one of them held its wave for a memory round trip)
+      // the key is there: the header is read and checked BEHIND the loop, all of the workgroup's at once (in the
+      // loop every one of them held its wave for a memory round trip)
       const uint32_t ri = atomicAdd(&s_nraw, 1u);
-      if (X3I_DEFER_CHECK && ri < X3I_WG_RAW) {
+      if (ri < X3I_WG_RAW) {
         s_raw[ri] = off;
         continue;
       }
@@ -193,8 +190,7 @@ x3_index_candidates_kernel(const uint32_t* __restrict__ xw, uint64_t len, uint64
   __syncthreads();
   {
     const uint32_t nraw = s_nraw < X3I_WG_RAW ? s_nraw : X3I_WG_RAW;
-    if (X3I_DEFER_CHECK)
-      for (uint32_t i = threadIdx.x; i < nraw; i += blockDim.x) consider(s_raw[i]);
+    for (uint32_t i = threadIdx.x; i < nraw; i += blockDim.x) consider(s_raw[i]);
   }
   __syncthreads();
   const uint32_t mine = s_n < X3I_WG_CANDS ? s_n : X3I_WG_CANDS;
