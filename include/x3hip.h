@@ -133,6 +133,9 @@ const char* x3_last_error(const x3_ctx* ctx);
  *                                           piece.  A call that goes in chunks starts two helper threads for its duration
  *                                           (pageable copies hold their caller); the results are the same either way.
  *   "file_chunk_frames" (X3HIP_FILE_CHUNK_FRAMES), "file_workers" (X3HIP_FILE_WORKERS)   x3_wav_to_x3a / x3_x3a_to_wav
+ *   "file_tune" (X3HIP_FILE_TUNE)          1: x3_wav_to_x3a makes one tuning pass over the WAV's samples first and writes the
+ *                                          archive with the parameters x3_tune chooses (section "parameter tuning"); 0
+ *                                          (default): the reference's defaults, byte for byte
  *   "reader_window_frames" (X3HIP_READER_WINDOW_FRAMES)   frames x3_reader decodes ahead per launch set
  *   "check_main" (X3HIP_CHECK_MAIN)        1: the check pass on the context's stream, the decoder on the side stream (experiment)
  *   "check_wgs", "check_prio", "check_first"   grid, queue priority and launch order of the check pass (experiments)
@@ -636,6 +639,60 @@ int x3_mgpu_encode(x3_mgpu* m, const int16_t* wav, uint64_t n, uint32_t n_channe
                    uint64_t out_cap, uint64_t start_pos, uint64_t* out_pos, uint64_t stats[6]);
 int x3_mgpu_decode_stream(x3_mgpu* m, const uint8_t* x3, uint64_t len, const x3_params* p, int16_t* wav,
                           uint64_t wav_cap, uint64_t* n_out, uint64_t* frames_ok, uint64_t* frame_errors);
+
+/* ------------------------------------------------------------------ parameter tuning (NOT in the reference) */
+
+/* The reference's wav_to_x3a always writes the default parameters (src/encodefile.rs:57), but the archive XML records
+ * <BLKLEN> and <T> (:102-111) and parse_xml reads them back (src/decodefile.rs:232-303).  These entry points find, for
+ * one input, the parameter set that encodes it in the fewest bytes -- exactly: a candidate's size is the number of
+ * bytes x3_encode_dev writes for it from start_pos 0 -- in one read of the samples on the GPU (csrc/x3_tune_kernel.h).
+ *
+ * CANDIDATES (2 184): the sets the reference decoder reads back exactly, its encoder takes without a panic and the
+ * single-pass encoders take: codes (0, 1, 3); block length 10, 20 or 40 (g = 0, 1, 2); t0 in 0..6, t1 in t0..10,
+ * t2 in 15..27 (stream-safe for codes (0, 1, 3), t2 >= 15 so that no BFP block is 5 bits wide or less, t0 <= t1 as
+ * the decoder never reads thresholds) -- 728 triples per block length.  Candidate index = g * 728 + the rank of
+ * (t0, t1, t2) in lexicographic order; the default set (20; 3, 8, 20) is index 1188.  All candidates share the frame
+ * length spf (samples per frame; blocks_per_frame = spf / block_len): a multiple of 40 in 40 ..= 10 240.
+ * CHOICE: the smallest total; among equal totals the default set if it is one of them, else the lowest index. */
+
+/* Candidate `index` (< X3_TUNE_CANDIDATES) at frame length spf as x3_params.  Host arithmetic.  BAD_ARG for a bad
+ * index or spf, or p = NULL. */
+int x3_tune_candidate(uint32_t index, uint32_t spf, x3_params* p);
+#define X3_TUNE_CANDIDATES 2184
+#define X3_TUNE_DEFAULT_INDEX 1188
+#define X3_TUNE_DEFAULT_SPF 10000
+
+/* An accumulating tuner: per-candidate 64-bit byte totals (and largest frame payloads) on the context's device.
+ * x3_tuner_create(ctx, spf, &t): an empty tuner at frame length spf (BAD_ARG as x3_tune_candidate).
+ * x3_tuner_add_dev(t, d_wav, batch): adds the encoded sizes of a device-resident batch (x3_encode_dev's layout:
+ *   batch->n_clips clips of batch->n_per_clip samples, clip c at d_wav + c * clip_stride samples).  Enqueued on the
+ *   context's stream, no sync.  Every clip is cut into frames from its own start, so the totals of several calls equal
+ *   those of one encode of the whole input only when every chunk but the last is whole frames (a multiple of spf
+ *   samples): that is the caller's to keep, it cannot be checked.  BAD_ARG, with nothing enqueued and the totals as they
+ *   were, for t, d_wav or batch NULL, d_wav not 2-byte aligned, 0 samples or 0 clips, or (n_clips > 1) a clip_stride
+ *   smaller than n_per_clip.  d_wav must stay unchanged until the next x3_tuner_result.
+ * x3_tuner_result(t, best, best_bytes, sizes): syncs; *best = the chosen candidate (the rule above), *best_bytes its
+ *   total, sizes[0 .. 2184) every candidate's total (each may be NULL).  A tuner that has been given nothing reports
+ *   totals of 0 and the default set.
+ * x3_tuner_max_payloads(t, payloads): syncs; payloads[0 .. 2184) = each candidate's largest frame payload in bytes.
+ * x3_tuner_reset empties the totals; x3_tuner_destroy waits for the context's stream and frees the tuner. */
+typedef struct x3_tuner x3_tuner;
+int x3_tuner_create(x3_ctx* ctx, uint32_t spf, x3_tuner** t);
+int x3_tuner_add_dev(x3_tuner* t, const int16_t* d_wav, const x3_batch* batch);
+int x3_tuner_result(x3_tuner* t, x3_params* best, uint64_t* best_bytes, uint64_t* sizes);
+int x3_tuner_max_payloads(x3_tuner* t, uint32_t* payloads);
+int x3_tuner_reset(x3_tuner* t);
+void x3_tuner_destroy(x3_tuner* t);
+
+/* The same for wav[0..n) in host memory (n >= 1), taken through the device in chunks of whole frames.  Syncs. */
+int x3_tune(x3_ctx* ctx, const int16_t* wav, uint64_t n, uint32_t spf, x3_params* best, uint64_t* best_bytes,
+            uint64_t* sizes);
+
+/* x3_x3a_encode with the parameters x3_tune chooses at spf = X3_TUNE_DEFAULT_SPF: the archive header records the chosen
+ * BLKLEN and T, the stream follows.  *chosen (may be NULL) receives them (the defaults for n = 0).  The reference's
+ * x3a_to_wav reads such an archive back unchanged. */
+int x3_x3a_encode_tuned(x3_ctx* ctx, const int16_t* wav, uint64_t n, uint32_t sample_rate, uint8_t* out,
+                        uint64_t out_cap, uint64_t* out_len, uint64_t stats[6], x3_params* chosen);
 
 /* ------------------------------------------------------------------ synthetic inputs (bench/tests) */
 

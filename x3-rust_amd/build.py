@@ -13,7 +13,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 # the translation units of the library (x3_internal.h says what each one holds)
-UNITS = ["x3_ctx.hip", "x3_encode.hip", "x3_decode.hip", "x3_files.hip", "x3_mgpu.hip"]
+UNITS = ["x3_ctx.hip", "x3_encode.hip", "x3_decode.hip", "x3_files.hip", "x3_mgpu.hip", "x3_tune.hip"]
 DEPS = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", "x3hip.h")]
 LIB = os.path.join(HERE, "lib", "libx3hip.so")
 OBJ = os.path.join(HERE, "lib", "obj")

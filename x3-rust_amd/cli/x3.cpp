@@ -27,13 +27,15 @@ static AudioFile filetype(const std::string& name) {  // get_filetype (bin/x3.rs
 static int usage(const char* why) {
   std::fprintf(stderr, "error: %s\n\nUSAGE:\n    x3 --input <FILE> --output <FILE>\n\n"
                "    -i, --input <FILE>     The input file, a .wav or .x3a file\n"
-               "    -o, --output <FILE>    The output file, a .wav or .x3a file\n", why);
+               "    -o, --output <FILE>    The output file, a .wav or .x3a file\n"
+               "        --tune             (.wav -> .x3a) choose block length and thresholds by exact encoded size\n", why);
   return 2;  // clap's exit status for a usage error
 }
 
 int main(int argc, char** argv) {
   std::string in_file, out_file;
   int device = 0;
+  bool tune = false;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
     auto value = [&](std::string* dst) -> bool {
@@ -49,6 +51,8 @@ int main(int argc, char** argv) {
       std::string d;
       if (!value(&d)) return usage("--device needs a value");
       device = std::atoi(d.c_str());
+    } else if (a == "--tune") {  // not in the reference: tuned parameters (include/x3hip.h, "parameter tuning")
+      tune = true;
     } else if (a == "-V" || a == "--version") {
       std::printf("x3 0.3.0 (libx3hip, MI355X)\n");
       return 0;
@@ -56,6 +60,7 @@ int main(int argc, char** argv) {
       return usage(("unexpected argument '" + a + "'").c_str());
     }
   }
+  if (tune && !in_file.empty() && filetype(in_file) != AudioFile::Wav) return usage("--tune applies to a .wav input");
   if (in_file.empty() || out_file.empty()) return usage("the following required arguments were not provided: --input <FILE> --output <FILE>");
   const AudioFile in_type = filetype(in_file), out_type = filetype(out_file);
   for (const std::string* f : {&in_file, &out_file})
@@ -76,7 +81,23 @@ int main(int argc, char** argv) {
   x3::Context ctx(device);
   x3::X3Error e;
   if (in_type == AudioFile::Wav) {
+    if (tune) x3_ctx_set_option(ctx.raw(), "file_tune", 1);
     e = x3::encodefile::wav_to_x3a(ctx, in_file.c_str(), out_file.c_str());
+    if (tune && e == x3::X3Error::Ok) {
+      uint8_t head[1024];
+      size_t got = 0;
+      if (FILE* f = std::fopen(out_file.c_str(), "rb")) {
+        got = std::fread(head, 1, sizeof head, f);
+        std::fclose(f);
+      }
+      x3_params p;
+      uint32_t rate = 0;
+      uint8_t ch = 0;
+      uint64_t hsize = 0;
+      if (x3_archive_header_read(head, got, &rate, &p, &ch, &hsize) == X3_OK)
+        std::printf("Tuned parameters: block length %u, thresholds (%u, %u, %u)\n", p.block_len, p.thresholds[0],
+                    p.thresholds[1], p.thresholds[2]);
+    }
   } else {
     uint64_t samples = 0, frame_errors = 0;
     e = x3::decodefile::x3a_to_wav(ctx, in_file.c_str(), out_file.c_str(), &samples, &frame_errors);

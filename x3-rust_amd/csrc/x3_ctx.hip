@@ -57,6 +57,7 @@ static void opts_from_env(X3Opts* o) {
   o->verbose = std::getenv("X3HIP_VERBOSE") ? 1 : 0;
   o->file_chunk_frames = std::max(1ll, geti("X3HIP_FILE_CHUNK_FRAMES", o->file_chunk_frames));
   o->file_workers = (int)std::max(1ll, std::min(16ll, geti("X3HIP_FILE_WORKERS", o->file_workers)));
+  o->file_tune = geti("X3HIP_FILE_TUNE", o->file_tune) ? 1 : 0;
   o->reader_window_frames = std::max(1ll, geti("X3HIP_READER_WINDOW_FRAMES", o->reader_window_frames));
   o->check_main = (int)geti("X3HIP_CHECK_MAIN", o->check_main);
   o->check_prio = (int)geti("X3HIP_CHECK_PRIO", o->check_prio);
@@ -422,6 +423,7 @@ extern "C" int x3_ctx_set_option(x3_ctx* c, const char* name, long long value) {
   else if (n == "verbose") c->opt.verbose = value != 0;
   else if (n == "file_chunk_frames") c->opt.file_chunk_frames = std::max(1ll, value);
   else if (n == "file_workers") c->opt.file_workers = (int)std::max(1ll, std::min(16ll, value));
+  else if (n == "file_tune") c->opt.file_tune = value ? 1 : 0;
   else if (n == "reader_window_frames") c->opt.reader_window_frames = std::max(1ll, value);
   else if (n == "kernel_timing_mask") c->timing_mask = (uint32_t)value;   // bit k: kernel id k carries events while timing is enabled (default: all)
   else if (n == "check_main") c->opt.check_main = value != 0;
@@ -455,6 +457,7 @@ extern "C" int x3_ctx_get_option(const x3_ctx* c, const char* name, long long* v
   else if (n == "verbose") *value = c->opt.verbose;
   else if (n == "file_chunk_frames") *value = c->opt.file_chunk_frames;
   else if (n == "file_workers") *value = c->opt.file_workers;
+  else if (n == "file_tune") *value = c->opt.file_tune;
   else if (n == "reader_window_frames") *value = c->opt.reader_window_frames;
   else if (n == "check_main") *value = c->opt.check_main;
   else if (n == "decode_pace" || n == "encode_pace") {  // (read-only, syncs) the pace words: the decoder's in shader clocks per 16 blocks, the encoder's in 10 ns ticks per frame

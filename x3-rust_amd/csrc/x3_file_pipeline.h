@@ -202,6 +202,10 @@ extern "C" int x3_wav_to_x3a(x3_ctx* c, const char* wav_path, const char* x3a_pa
 
   x3_params p;
   x3_params_default(&p);  // encodefile.rs:57
+  if (c->opt.file_tune && n > 0) {   // option "file_tune"
+    if (!tune_fd) return X3_ERR_BAD_ARG;
+    if ((rc = tune_fd(c, in.fd, wi.data_off, n, &p))) return rc;
+  }
   uint8_t hdr[512];
   uint64_t hlen = 0;
   if ((rc = x3_archive_header_write(wi.sample_rate, &p, hdr, sizeof hdr, &hlen))) return rc;

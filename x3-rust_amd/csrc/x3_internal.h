@@ -9,6 +9,7 @@
 //                   the BitReader / BitPacker / decode_block handles (x3_bits.h)
 //   x3_files.hip    .x3a archive header, wav <-> x3a in memory and on files, the incremental reader
 //   x3_mgpu.hip     x3_shard_* / x3_mgpu_* (librccl through dlopen)
+//   x3_tune.hip     parameter tuning: the tuning kernel (x3_tune_kernel.h), x3_tune* / x3_tuner_*, x3_x3a_encode_tuned
 //
 // Kernels live in headers; every NON-template kernel header is included by exactly one unit.
 #pragma once
@@ -66,6 +67,7 @@ struct X3Opts {
   int verbose = 0;            // X3HIP_VERBOSE
   long long file_chunk_frames = 800;  // X3HIP_FILE_CHUNK_FRAMES: 16 MB of samples per chunk (tools/file_bench.py)
   int file_workers = 4;       // X3HIP_FILE_WORKERS
+  int file_tune = 0;          // X3HIP_FILE_TUNE: x3_wav_to_x3a tunes the parameters first (one pass over the file, x3_tune)
   int check_main = 0;         // X3HIP_CHECK_MAIN: the check pass on the caller's stream and the decoder on the side stream
   long long reader_window_frames = 4096;  // X3HIP_READER_WINDOW_FRAMES: frames x3_reader decodes ahead per launch set
   int check_prio = 1;         // X3HIP_CHECK_PRIO: queue priority of the side stream the check kernel runs on (-1 low, 0 same, 1 high)
@@ -319,6 +321,9 @@ struct EncPlan {
 
 // ---- x3_ctx.hip
 X3_INTERNAL int ensure(x3_ctx* c, DevBuf& b, size_t bytes);
+// x3_wav_to_x3a with option "file_tune": the tuned parameters of samples [0, n) at byte data_off of a file (x3_tune.hip;
+// weak, so that the other units also link without that one, as the sanitizer build of the host code does)
+X3_INTERNAL int tune_fd(x3_ctx* c, int fd, uint64_t data_off, uint64_t n, x3_params* best) __attribute__((weak));
 // an encode call takes the control block the call before did not use (x3_ctx::d_ctl_base), cleared -- by the last kernel of
 // the call before where that was a wave-encoder call, by a memset otherwise (and always while a graph is recorded: every
 // replay runs the same nodes); x3_encode.hip

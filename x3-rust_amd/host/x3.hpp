@@ -731,7 +731,54 @@ inline X3Error place_buffers(Context& ctx, const int16_t* d_wav, size_t n, const
                                                d_frame_offsets, backs.data(), static_cast<uint32_t>(backs.size()), warm, steps,
                                                ms->data()));
 }
+
+// Parameter tuning (NOT in the crate; include/x3hip.h, "parameter tuning"): per-candidate exact encoded sizes of
+// device-resident batches, accumulated.  Choice: the smallest total; among equal totals the default set, else the lowest
+// index.
+class Tuner {
+ public:
+  Tuner(Context& ctx, uint32_t spf = X3_TUNE_DEFAULT_SPF) { rc_ = static_cast<X3Error>(x3_tuner_create(ctx.raw(), spf, &t_)); }
+  Tuner(const Tuner&) = delete;
+  Tuner& operator=(const Tuner&) = delete;
+  ~Tuner() { x3_tuner_destroy(t_); }
+  X3Error status() const { return rc_; }
+  // every chunk but the last must be whole frames for the totals to be those of one encode of the whole input
+  X3Error add(const int16_t* d_wav, size_t n_per_clip, size_t n_clips = 1, size_t clip_stride = 0) {
+    const x3_batch b{n_per_clip, clip_stride ? clip_stride : n_per_clip, n_clips};
+    return static_cast<X3Error>(x3_tuner_add_dev(t_, d_wav, &b));
+  }
+  // syncs; sizes (may be null) receives every candidate's total
+  X3Error result(Parameters* best, uint64_t* best_bytes, std::vector<uint64_t>* sizes = nullptr) {
+    x3_params c;
+    if (sizes) sizes->assign(X3_TUNE_CANDIDATES, 0);
+    const int rc = x3_tuner_result(t_, &c, best_bytes, sizes ? sizes->data() : nullptr);
+    if (rc == X3_OK && best) *best = Parameters::from_c(c);
+    return static_cast<X3Error>(rc);
+  }
+  X3Error reset() { return static_cast<X3Error>(x3_tuner_reset(t_)); }
+
+ private:
+  x3_tuner* t_ = nullptr;
+  X3Error rc_ = X3Error::Ok;
+};
 }  // namespace device
+
+// x3_tune on host samples: the chosen parameters, their total and (sizes != null) every candidate's total
+inline X3Error tune(Context& ctx, const int16_t* wav, size_t n, Parameters* best, uint64_t* best_bytes = nullptr,
+                    std::vector<uint64_t>* sizes = nullptr, uint32_t spf = X3_TUNE_DEFAULT_SPF) {
+  x3_params c;
+  if (sizes) sizes->assign(X3_TUNE_CANDIDATES, 0);
+  const int rc = x3_tune(ctx.raw(), wav, n, spf, &c, best_bytes, sizes ? sizes->data() : nullptr);
+  if (rc == X3_OK && best) *best = Parameters::from_c(c);
+  return static_cast<X3Error>(rc);
+}
+// candidate `index` of the grid at frame length spf
+inline X3Error tune_candidate(uint32_t index, Parameters* out, uint32_t spf = X3_TUNE_DEFAULT_SPF) {
+  x3_params c;
+  const int rc = x3_tune_candidate(index, spf, &c);
+  if (rc == X3_OK && out) *out = Parameters::from_c(c);
+  return static_cast<X3Error>(rc);
+}
 
 // Multi-channel extension (x3_mc.h; NOT in the crate, whose encode() returns MoreThanOneChannel for more than one channel
 // and whose reader refuses such frames -- as encoder::encode and decoder::decode_stream above do): the layout the frame

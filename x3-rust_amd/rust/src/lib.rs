@@ -54,7 +54,7 @@ pub mod ffi {
     macro_rules! opaque {
         ($($n:ident),*) => { $(#[repr(C)] pub struct $n { _private: [u8; 0] })* };
     }
-    opaque!(x3_ctx, x3_bitreader, x3_bitpacker, x3_reader);
+    opaque!(x3_ctx, x3_bitreader, x3_bitpacker, x3_reader, x3_tuner);
 
     extern "C" {
         pub fn x3_strerror(status: c_int) -> *const c_char;
@@ -132,6 +132,18 @@ pub mod ffi {
                                 n_streams: u32, cap: u64, d_frame_offsets: *mut u64, d_backs: *const *mut i16, n_backs: u32,
                                 warm: u32, steps: u32, ms_per_step: *mut f64) -> c_int;
         pub fn x3_wav_to_x3a(ctx: *mut x3_ctx, wav_path: *const c_char, x3a_path: *const c_char, stats: *mut u64) -> c_int;
+        // parameter tuning (not in the reference)
+        pub fn x3_tune_candidate(index: u32, spf: u32, p: *mut x3_params) -> c_int;
+        pub fn x3_tuner_create(ctx: *mut x3_ctx, spf: u32, t: *mut *mut x3_tuner) -> c_int;
+        pub fn x3_tuner_add_dev(t: *mut x3_tuner, d_wav: *const i16, batch: *const x3_batch) -> c_int;
+        pub fn x3_tuner_result(t: *mut x3_tuner, best: *mut x3_params, best_bytes: *mut u64, sizes: *mut u64) -> c_int;
+        pub fn x3_tuner_max_payloads(t: *mut x3_tuner, payloads: *mut u32) -> c_int;
+        pub fn x3_tuner_reset(t: *mut x3_tuner) -> c_int;
+        pub fn x3_tuner_destroy(t: *mut x3_tuner);
+        pub fn x3_tune(ctx: *mut x3_ctx, wav: *const i16, n: u64, spf: u32, best: *mut x3_params, best_bytes: *mut u64,
+                       sizes: *mut u64) -> c_int;
+        pub fn x3_x3a_encode_tuned(ctx: *mut x3_ctx, wav: *const i16, n: u64, sample_rate: u32, out: *mut u8, out_cap: u64,
+                                   out_len: *mut u64, stats: *mut u64, chosen: *mut x3_params) -> c_int;
         pub fn x3_x3a_to_wav(ctx: *mut x3_ctx, x3a_path: *const c_char, wav_path: *const c_char, n_samples: *mut u64,
                              frame_errors: *mut u64) -> c_int;
         pub fn x3_reader_open(ctx: *mut x3_ctx, x3a_path: *const c_char, reader: *mut *mut x3_reader) -> c_int;
@@ -1219,6 +1231,58 @@ pub mod encodefile {
         println!("\nStatistics:\n  Rice-0: {:.4}%\n  Rice-1: {:.4}%\n  Rice-2: {:.4}%\n  Rice-3: {:.4}%\n  BFP: {:.4}%\n  Pass-through {:.4}%\n",
                  pc(0), pc(1), pc(2), pc(3), pc(4), pc(5));
         Ok(())
+    }
+}
+
+pub mod tune {
+    //! Parameter tuning (not in the reference; include/x3hip.h, "parameter tuning"): the exact encoded size of an input
+    //! under each of the 2 184 safe parameter sets, in one pass on the GPU, and the .x3a encode that uses the smallest.
+    use crate::error::{self, X3Error};
+    use crate::x3::Parameters;
+    use crate::{ffi, gpu};
+
+    pub const CANDIDATES: usize = 2184;
+    pub const DEFAULT_INDEX: usize = 1188;
+    pub const DEFAULT_SPF: u32 = 10000;
+
+    fn zero_params() -> ffi::x3_params {
+        ffi::x3_params { block_len: 0, blocks_per_frame: 0, codes: [0; 3], thresholds: [0; 3] }
+    }
+
+    /// candidate `index` of the grid at frame length `spf`
+    pub fn candidate(index: u32, spf: u32) -> Result<Parameters, X3Error> {
+        let mut p = zero_params();
+        error::check(unsafe { ffi::x3_tune_candidate(index, spf, &mut p) })?;
+        Ok(Parameters::from_c(&p))
+    }
+
+    /// the chosen set (smallest total; ties: the default set, else the lowest index), its total and every candidate's total
+    pub fn tune(wav: &[i16], spf: u32) -> Result<(Parameters, u64, Vec<u64>), X3Error> {
+        let mut p = zero_params();
+        let mut best = 0u64;
+        let mut sizes = vec![0u64; CANDIDATES];
+        gpu::with_default(|g| {
+            error::check(unsafe {
+                ffi::x3_tune(g.raw(), wav.as_ptr(), wav.len() as u64, spf, &mut p, &mut best, sizes.as_mut_ptr())
+            })
+        })?;
+        Ok((Parameters::from_c(&p), best, sizes))
+    }
+
+    /// `wav_to_x3a` in memory with the tuned parameters: the archive bytes and the parameters its header records
+    pub fn x3a_encode_tuned(wav: &[i16], sample_rate: u32) -> Result<(Vec<u8>, Parameters), X3Error> {
+        let mut out = vec![0u8; 1024 + 20 * (wav.len() / 40 + 1) + 2 * wav.len() + 64];
+        let mut len = 0u64;
+        let mut stats = [0u64; 6];
+        let mut p = zero_params();
+        gpu::with_default(|g| {
+            error::check(unsafe {
+                ffi::x3_x3a_encode_tuned(g.raw(), wav.as_ptr(), wav.len() as u64, sample_rate, out.as_mut_ptr(),
+                                         out.len() as u64, &mut len, stats.as_mut_ptr(), &mut p)
+            })
+        })?;
+        out.truncate(len as usize);
+        Ok((out, Parameters::from_c(&p)))
     }
 }
 

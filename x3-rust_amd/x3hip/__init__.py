@@ -57,7 +57,11 @@ SYMBOLS = [
     "x3_mgpu_encode", "x3_mgpu_decode_stream",
     "x3_encode_mc", "x3_decode_stream_mc",
     "x3_sample_offsets_dev", "x3_decode_windows_dev", "x3_decode_windows_result",
+    "x3_tune_candidate", "x3_tuner_create", "x3_tuner_add_dev", "x3_tuner_result", "x3_tuner_max_payloads",
+    "x3_tuner_reset", "x3_tuner_destroy", "x3_tune", "x3_x3a_encode_tuned",
 ]
+
+TUNE_CANDIDATES, TUNE_DEFAULT_INDEX, TUNE_DEFAULT_SPF = 2184, 1188, 10000   # include/x3hip.h, "parameter tuning"
 
 WINDOW_I16, WINDOW_F32 = 0, 1   # x3_decode_windows_dev output formats
 
@@ -261,6 +265,16 @@ def lib():
     L.x3_mgpu_last_error.argtypes = [vp]
     L.x3_mgpu_encode.argtypes = [vp, vp, u64, u32, PP, vp, u64, u64, C.POINTER(u64), vp]
     L.x3_mgpu_decode_stream.argtypes = [vp, vp, u64, PP, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+    L.x3_tune_candidate.argtypes = [u32, u32, PP]
+    L.x3_tuner_create.argtypes = [vp, u32, C.POINTER(vp)]
+    L.x3_tuner_add_dev.argtypes = [vp, vp, C.POINTER(Batch)]
+    L.x3_tuner_result.argtypes = [vp, PP, C.POINTER(u64), vp]
+    L.x3_tuner_max_payloads.argtypes = [vp, vp]
+    L.x3_tuner_reset.argtypes = [vp]
+    L.x3_tuner_destroy.restype = None
+    L.x3_tuner_destroy.argtypes = [vp]
+    L.x3_tune.argtypes = [vp, vp, u64, u32, PP, C.POINTER(u64), vp]
+    L.x3_x3a_encode_tuned.argtypes = [vp, vp, u64, u32, vp, u64, C.POINTER(u64), vp, PP]
     _lib = L
     return L
 
@@ -456,6 +470,59 @@ class X3Error(RuntimeError):
     def __init__(self, rc, what=""):
         self.rc = rc
         super().__init__("%s: %s (%d)" % (what, strerror(rc), rc))
+
+
+def tune_candidate(index, spf=TUNE_DEFAULT_SPF):
+    """candidate `index` of the tuning grid at frame length spf -> (rc, Params)"""
+    p = Params()
+    rc = lib().x3_tune_candidate(index, spf, C.byref(p))
+    return rc, p
+
+
+class Tuner:
+    """x3_tuner: per-candidate encoded sizes accumulated over device-resident batches (include/x3hip.h)"""
+
+    def __init__(self, ctx, spf=TUNE_DEFAULT_SPF):
+        self._ctx = ctx
+        self._h = C.c_void_p()
+        rc = lib().x3_tuner_create(ctx._h, spf, C.byref(self._h))
+        if rc:
+            raise X3Error(rc, "x3_tuner_create")
+        self.spf = spf
+
+    def add_dev(self, d_wav, n_per_clip, clip_stride=None, n_clips=1):
+        """enqueue one batch (x3_encode_dev's layout) -> status"""
+        b = Batch(n_per_clip, n_per_clip if clip_stride is None else clip_stride, n_clips)
+        return lib().x3_tuner_add_dev(self._h, C.c_void_p(d_wav), C.byref(b))
+
+    def result(self):
+        """-> (rc, best Params, best_bytes, sizes[2184] uint64)"""
+        p = Params()
+        bb = C.c_uint64(0)
+        sizes = np.zeros(TUNE_CANDIDATES, dtype=np.uint64)
+        rc = lib().x3_tuner_result(self._h, C.byref(p), C.byref(bb), sizes.ctypes.data)
+        return rc, p, bb.value, sizes
+
+    def max_payloads(self):
+        out = np.zeros(TUNE_CANDIDATES, dtype=np.uint32)
+        rc = lib().x3_tuner_max_payloads(self._h, out.ctypes.data)
+        if rc:
+            raise X3Error(rc, "x3_tuner_max_payloads")
+        return out
+
+    def reset(self):
+        return lib().x3_tuner_reset(self._h)
+
+    def close(self):
+        if self._h:
+            lib().x3_tuner_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 SYNTH_ZEROS, SYNTH_WHITE, SYNTH_HYDROPHONE, SYNTH_SINE, SYNTH_WALK = range(5)
@@ -664,6 +731,31 @@ class Context:
         rc = lib().x3_x3a_encode(self._h, wav.ctypes.data, wav.size, sample_rate, out.ctypes.data, cap, C.byref(n),
                                  stats.ctypes.data)
         return rc, out[: min(n.value, cap)].copy(), stats
+
+    def tune(self, wav, spf=TUNE_DEFAULT_SPF):
+        """x3_tune on host samples -> (Params, best_bytes, sizes[2184] uint64); raises X3Error on failure"""
+        wav = np.ascontiguousarray(wav, dtype=np.int16)
+        p = Params()
+        bb = C.c_uint64(0)
+        sizes = np.zeros(TUNE_CANDIDATES, dtype=np.uint64)
+        rc = lib().x3_tune(self._h, wav.ctypes.data if wav.size else None, wav.size, spf, C.byref(p), C.byref(bb),
+                           sizes.ctypes.data)
+        if rc:
+            raise X3Error(rc, "x3_tune")
+        return p, bb.value, sizes
+
+    def x3a_encode_tuned(self, wav, sample_rate, cap=None):
+        """x3a_encode with the parameters x3_tune chooses -> (rc, .x3a bytes, stats, chosen Params)"""
+        wav = np.ascontiguousarray(wav, dtype=np.int16)
+        if cap is None:
+            cap = 1024 + lib().x3_encode_bound(wav.size, C.byref(Params.make(block_len=10, blocks_per_frame=1000)))
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        n = C.c_uint64(0)
+        stats = np.zeros(6, dtype=np.uint64)
+        p = Params()
+        rc = lib().x3_x3a_encode_tuned(self._h, wav.ctypes.data, wav.size, sample_rate, out.ctypes.data, cap, C.byref(n),
+                                       stats.ctypes.data, C.byref(p))
+        return rc, out[: min(n.value, cap)].copy(), stats, p
 
     def x3a_decode(self, x3a, wav_cap=None):
         """x3a_to_wav in memory -> (rc, samples, sample_rate, frames_ok, frame_errors)"""
