@@ -145,6 +145,12 @@ const char* x3_last_error(const x3_ctx* ctx);
  * "decode_pace": what the slowest workgroup of the last encoder / decoder launch achieved, in 10 ns ticks per frame /
  * in shader clocks per 16 blocks -- the next launch paces its waves' priorities by it (x3_encode_stream2_kernel.h,
  * x3_decode_split_kernel.h); reading them synchronizes.
+ * Read-only "last_decode_replays": frames the fast decoders handed to the reference's own reader (a decode error, a zero
+ * run of 32 bits or more, or a read behind the payload's last byte: x3_decode_replay.h) -- of the launch the last
+ * x3_decode_result read, or of the last x3_decode_stream (summed over its chunks), x3_decode_stream_dev or
+ * x3_decode_stream_mc as a whole (there: the frames its per-thread kernel decoded, all of them with "mc_decode_threads" = 1).
+ * A stream an encoder wrote has none.  Read-only "last_window_replays": the (window, covering frame) pairs the last
+ * x3_decode_windows_dev re-decoded that way, read after x3_decode_windows_result.
  * Unknown name: X3_ERR_BAD_ARG. */
 int x3_ctx_set_option(x3_ctx* ctx, const char* name, long long value);
 int x3_ctx_get_option(const x3_ctx* ctx, const char* name, long long* value);

@@ -721,6 +721,89 @@ int x3o_decode_frame_mc(const uint8_t* x3_bytes, size_t len, int16_t* const* wav
   return X3O_OK;
 }
 
+/* ---- the plain-frame predicate (the contract of the GPU decoders' replay, x3-rust_amd/csrc/x3_decode_replay.h:1-20).
+ * Not the reference's reader: a plain MSB-first bit string that reads as zero beyond the payload's last byte, zero runs
+ * counted exactly.  A frame is PLAIN when, read this way, every block decodes without an error (inverse-table bound, BFP
+ * width E <= 5), no codeword's zero run is 32 bits or longer, and no bit read lies behind the last byte.  On such a frame
+ * the reference's reader gives the same samples (tests/test_oracle_plain.py pins that), and the GPU's fast decoders must
+ * decode it themselves; every other frame they hand to the reference's reader. */
+typedef struct { const uint8_t* a; uint64_t nbits, pos; } plain_reader;
+
+static inline uint32_t plain_bit(const plain_reader* r, uint64_t at) {
+  return at < r->nbits ? (r->a[at >> 3] >> (7 - (at & 7))) & 1u : 0u;
+}
+static inline uint32_t plain_bits(plain_reader* r, uint32_t n) {
+  uint32_t v = 0;
+  for (uint32_t i = 0; i < n; i++) v = (v << 1) | plain_bit(r, r->pos + i);
+  r->pos += n;
+  return v;
+}
+/* the zero run at the read position; 32 or more: stop counting (the frame is not plain) */
+static inline uint32_t plain_zeros(plain_reader* r) {
+  uint32_t z = 0;
+  while (z < 32 && plain_bit(r, r->pos + z) == 0) z++;
+  r->pos += z;
+  return z;
+}
+
+/* one block of n >= 1 samples; 1: plain so far */
+static int plain_block(plain_reader* r, uint32_t n, const x3o_params* p, int16_t* last, int16_t* out) {
+  const uint32_t ftype = plain_bits(r, 2);
+  uint16_t lw = (uint16_t)*last;
+  if (ftype == 0) {
+    const uint32_t E = plain_bits(r, 4) + 1;
+    if (E <= 5) return 0;
+    for (uint32_t i = 0; i < n; i++) {
+      const uint32_t v = plain_bits(r, E);
+      if (E == 16) lw = (uint16_t)v;
+      else lw = (uint16_t)(lw + (uint16_t)(v > (1u << (E - 1)) ? (int32_t)v - (1 << E) : (int32_t)v));
+      out[i] = (int16_t)lw;
+    }
+  } else {
+    const x3o_rice_code* code = &X3O_RICE[p->codes[ftype - 1]];
+    for (uint32_t i = 0; i < n; i++) {
+      const uint32_t z = plain_zeros(r);
+      if (z >= 32) return 0;
+      int64_t ix;
+      if (ftype == 1) {
+        ix = z;
+        r->pos += 1;                                   /* the terminating one */
+      } else {
+        /* decoder.rs:180-186: 2 or 4 bits, the terminating one included, whatever the code's sub-bit count */
+        const uint32_t rr = plain_bits(r, ftype == 2 ? 2 : 4);
+        ix = (int64_t)rr + ((int64_t)1 << code->nsubs) * ((int64_t)z - 1);
+      }
+      if (ix < 0 || ix >= (int64_t)code->inv_len) return 0;
+      lw = (uint16_t)(lw + (uint16_t)X3O_INV_RICE[ix]);
+      out[i] = (int16_t)lw;
+    }
+  }
+  *last = (int16_t)lw;
+  return 1;
+}
+
+int x3o_frame_plain(const uint8_t* payload, size_t plen, size_t samples, uint32_t n_ch, const x3o_params* p,
+                    int16_t* wav_out) {
+  x3o_init();
+  if (n_ch == 0 || n_ch > 255 || plen < 2u * n_ch || samples == 0 || p->block_len == 0 || p->codes[0] > 3 ||
+      p->codes[1] > 3 || p->codes[2] > 3)
+    return -1;
+  int16_t last[255];
+  for (uint32_t c = 0; c < n_ch; c++) {
+    last[c] = (int16_t)rd_be16(payload + 2 * c);
+    wav_out[c * samples] = last[c];
+  }
+  plain_reader r = {payload + 2 * n_ch, 8 * (uint64_t)(plen - 2u * n_ch), 0};
+  for (size_t at = 1; at < samples;) {
+    const uint32_t n = (uint32_t)(samples - at < p->block_len ? samples - at : p->block_len);
+    for (uint32_t c = 0; c < n_ch; c++)
+      if (!plain_block(&r, n, p, &last[c], wav_out + c * samples + at)) return 0;
+    if (r.pos > r.nbits) return 0;
+    at += n;
+  }
+  return 1;
+}
+
 /* the frame walk of decode_stream_phantom for frames of n_ch channels: the header's <Num Channels> must say n_ch */
 int x3o_decode_stream_mc(const uint8_t* x3, uint64_t len, uint32_t n_ch, const x3o_params* p, int16_t* const* wavs,
                          uint64_t wav_cap, uint64_t* n_out, uint64_t* frames_ok, uint64_t* frame_errors) {

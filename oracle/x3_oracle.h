@@ -171,6 +171,12 @@ int x3o_decode_frame_mc(const uint8_t* x3_bytes, size_t len, int16_t* const* wav
 int x3o_decode_stream_mc(const uint8_t* x3, uint64_t len, uint32_t n_ch, const x3o_params* p, int16_t* const* wavs,
                          uint64_t wav_cap, uint64_t* n_out, uint64_t* frames_ok, uint64_t* frame_errors);
 
+/* 1 when the frame is PLAIN -- read as an MSB-first bit string that is zero beyond its last byte, every block decodes
+ * without error, no codeword has a zero run of 32 bits or more and no bit read lies behind the last byte -- 0 when not,
+ * -1 on arguments decode_frame refuses (and block_len 0).  The samples decoded go to wav_out[c * samples + i] (valid when 1).
+ * Frames that are not plain are the ones the GPU's fast decoders hand to the reference's reader. */
+int x3o_frame_plain(const uint8_t* payload, size_t plen, size_t samples, uint32_t n_ch, const x3o_params* p,
+                    int16_t* wav_out);
 
 /* ---- encodefile.rs / decodefile.rs: the .x3a archive around the frame stream (no file I/O).
  * Unpinned by any reference test (its file tests are commented out): follows the source.

@@ -100,6 +100,7 @@ def lib(native=False):
                                    C.POINTER(Params)]
     L.x3o_decode_frame.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(Params), C.c_size_t,
                                    C.POINTER(C.c_size_t)]
+    L.x3o_frame_plain.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32, C.POINTER(Params), C.c_void_p]
     L.x3o_decode_stream.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(Params), C.c_void_p, C.c_uint64,
                                     C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.x3o_archive_header_write.argtypes = [C.c_uint32, C.POINTER(Params), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
@@ -211,6 +212,16 @@ def decode_frame(payload, samples, params=None, wav_cap=None):
     rc = lib().x3o_decode_frame(payload.ctypes.data, payload.size, wav.ctypes.data, wav_cap, C.byref(params), samples,
                                 C.byref(n))
     return rc, wav[: n.value].copy()
+
+
+def frame_plain(payload, samples, params=None, n_ch=1):
+    """x3o_frame_plain: (1 plain / 0 not / -1 refused, samples decoded -- n_ch rows of `samples`, valid when plain).  A frame
+    that is not plain is one the GPU's fast decoders hand to the reference's reader (x3_decode_replay.h)."""
+    params = params or Params.default()
+    payload = np.ascontiguousarray(payload, dtype=np.uint8)
+    wav = np.zeros((n_ch, max(samples, 1)), dtype=np.int16)
+    rc = lib().x3o_frame_plain(payload.ctypes.data, payload.size, samples, n_ch, C.byref(params), wav.ctypes.data)
+    return rc, (wav[0] if n_ch == 1 else wav)
 
 
 def archive_header_write(sample_rate, params=None, cap=1024):

@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
-from x3_cases import frame_offsets, refresh_crcs
+from x3_cases import frame_offsets, not_plain, refresh_crcs, walked_frames
 
 pytestmark = pytest.mark.gpu
 
@@ -246,11 +246,16 @@ def test_block_lengths_10_and_40_take_the_blocks_kernel(x3, bl, bpf):
                     cases.append(s2)
             for s2 in cases:
                 o = O.decode_stream(s2, po, wav_cap=n + 100)
+                # the frames handed to the reference's reader: exactly those that are not plain (none of an intact stream)
+                replays = not_plain(walked_frames(s2, n + 100), po)
+                assert s2 is not stream or replays == 0
                 r = c.decode_stream(s2, p, wav_cap=n + 100)
                 used = c.get_option("decode_kernel_in_use")
+                assert c.get_option("last_decode_replays") == replays, (bl, bpf, nfr, tail, replays)
                 c.set_option("decode_blocks_off", 1)
                 r1 = c.decode_stream(s2, p, wav_cap=n + 100)
                 assert c.get_option("decode_kernel_in_use") != 3
+                assert c.get_option("last_decode_replays") == replays, (bl, bpf, nfr, tail, replays)
                 c.set_option("decode_blocks_off", 0)
                 for a in (r, r1):
                     assert (a[0], a[2], a[3]) == (o[0], o[2], o[3]) and np.array_equal(a[1], o[1]), (bl, bpf, nfr, tail)

@@ -9,16 +9,18 @@ through both flagship decoders.  The reference's decoder hard-wires the sub-code
 valid headers and CRCs around bit patterns the default encoder never writes, with an exact answer from the oracle.
 Encoders: bytes, statistics, status and the generation in use.  Decoders: status, frame counts, first failing frame,
 samples and the 0x5A guard behind each row, and the kernel in use (a coverage table that must be filled).
-(What no output can show: a fast kernel whose index bound is too LOW -- every index it refuses sends the frame to the
-reference's reader, x3_decode_replay.h, which decides exactly.  A bound too high, or a parse that hard-wires part of the
-default code set, gives other statuses or samples, and that is what fails here.)"""
+No output can show a fast kernel whose index bound is too LOW: every index it refuses sends the frame to the reference's
+reader (x3_decode_replay.h), which decides exactly.  So every decode here also counts those replays (option
+last_decode_replays) against the oracle's plain-frame predicate (oracle_lib.frame_plain): a kernel must hand over exactly
+the frames that are not plain -- the edge codewords test each index bound from the fast side too.  A bound too high, or a
+parse that hard-wires part of the default code set, gives other statuses or samples."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 import oracle_lib as O
-from x3_cases import AMPS, compare, crafted_frames, damage, frame_offsets, oparams, patchwork
+from x3_cases import AMPS, compare, crafted_frames, damage, frame_offsets, not_plain, oparams, patchwork, walked_frames
 
 pytestmark = pytest.mark.gpu
 
@@ -248,11 +250,15 @@ def test_encoders(ctx, x3, codes, thr):
 
 # ------------------------------------------------------------------ decoders
 
-def _walks(ctx, stream, p, cap, o):
-    """x3_decode_stream with the walk on the host, on the GPU, and in chunks of three frames"""
+def _walks(ctx, stream, p, cap, o, replays=None):
+    """x3_decode_stream with the walk on the host, on the GPU, and in chunks of three frames; `replays`: the frames all of
+    them hand to the reference's reader (the chunked walk stops after the chunk of the first failing frame: there only when
+    that is none)"""
     for host_walk, chunk in ((1, -1), (0, -1), (-1, 3)):
         with _opts(ctx, {"host_walk": host_walk, "host_chunk_frames": chunk}):
             same(ctx.decode_stream(stream, p, wav_cap=cap), o, ("walk", host_walk, chunk))
+            if replays is not None and (chunk < 0 or replays == 0):
+                assert ctx.get_option("last_decode_replays") == replays, ("walk", host_walk, chunk)
 
 
 def _per_frame(ctx, x3, stream, p, x4):
@@ -275,12 +281,14 @@ def _per_frame(ctx, x3, stream, p, x4):
             assert ctx.decode_dev(d_x3, stream.size, d_off, F, p, d_wav, total, d_wav_offsets=d_wo, d_status=d_st) == 0
         rc, first_bad, st0, before = ctx.decode_result()
         assert rc == 0
+        replays = ctx.get_option("last_decode_replays")
         status = ctx.download(d_st, 4 * F, np.int32)
         wav = ctx.download(d_wav, 2 * total, np.int16)
     finally:
         for d in (d_x3, d_off, d_wo, d_wav, d_st):
             ctx.free(d)
     op = oparams(p)
+    assert replays == not_plain(walked_frames(stream, total), op), (x4, replays)
     exp_first = F
     for f, o in enumerate(offs):
         plen = int(stream[o + 6]) << 8 | int(stream[o + 7])
@@ -315,6 +323,10 @@ def test_decoders(ctx, x3, codes, thr):
         if codes == (0, 1, 3) and thr[2] >= 16:
             assert want[0][0] == 0 and np.array_equal(want[0][1], wav)
         frames = crafted_frames(x3, rng, p, 1000) + edge_frames(bl)
+        # the frames each case's decode launch hands to the reference's reader (none on a stream of the default codes)
+        replays = [not_plain(walked_frames(s, cap), po) for s in cases]
+        if codes == (0, 1, 3) and thr[2] >= 16:
+            assert replays[0] == 0
         for name, kv in DECODERS:
             with _opts(ctx, kv):
                 eff = [ctx.get_option(k) for k in OPTS]
@@ -324,6 +336,7 @@ def test_decoders(ctx, x3, codes, thr):
                     if i == 0:
                         poison(ctx, x3, exp)
                     same(ctx.decode_stream(s, p, wav_cap=cap), want[i], (bl, name, i))
+                    assert ctx.get_option("last_decode_replays") == replays[i], (bl, name, i, replays[i])
                     if i == 0:
                         used = ctx.get_option("decode_kernel_in_use")
                         assert used == exp, (bl, name, used, exp)
@@ -336,7 +349,7 @@ def test_decoders(ctx, x3, codes, thr):
                     cell.add(used)
                 for x4 in (1, 0):
                     _per_frame(ctx, x3, stream, p, x4)
-        _walks(ctx, stream, p, cap, want[0])
+        _walks(ctx, stream, p, cap, want[0], replays[0])
         _walks(ctx, cases[1], p, cap, want[1])
         # a device-resident stream in one trip (block length 20) or two
         d_wav = ctx.alloc(2 * cap)
@@ -346,6 +359,7 @@ def test_decoders(ctx, x3, codes, thr):
                 ctx.upload(d, np.concatenate([s, np.zeros(64, dtype=np.uint8)]))
                 b = ctx.decode_stream_dev(d, s.size, p, d_wav, cap)
                 ctx.free(d)
+                assert ctx.get_option("last_decode_replays") == replays[i], (bl, i, replays[i])
                 o = want[i]
                 assert b == (o[0], o[1].size, o[2], o[3]), (bl, i, b, o[0], o[1].size, o[2:])
                 assert np.array_equal(ctx.download(d_wav, 2 * b[1], np.int16), o[1]), (bl, i)

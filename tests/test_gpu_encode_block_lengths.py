@@ -57,6 +57,7 @@ def test_streams_and_statistics_equal_the_oracles(ctx, x3, bl, bpf):
                 r, o = ctx.decode_stream(s, p, wav_cap=n + 8), O.decode_stream(s, po, wav_cap=n + 8)
                 assert (r[0], r[2], r[3]) == (o[0], o[2], o[3]) and np.array_equal(r[1], o[1])
                 assert o[0] != 0 or np.array_equal(r[1], wav)
+                assert ctx.get_option("last_decode_replays") == 0   # (dense blocks of 10 and 40: the fast kernels' own)
 
 
 @pytest.mark.parametrize("bl,bpf", [(10, 1000), (40, 250), (10, 36), (40, 9)])

@@ -72,8 +72,18 @@ def test_channels_match_the_oracle(ctx, n_ch, n, bpf):
     rc_d, back, fok, ferr = ctx.decode_stream_mc(x_g, n_ch, p, wav_cap=n + 64)
     rc_do, back_o, fok_o, ferr_o = O.decode_stream_mc(x_o, n_ch, po, wav_cap=n + 64)
     assert (rc_d, fok, ferr) == (rc_do, fok_o, ferr_o) == (0, (n + 20 * bpf - 1) // (20 * bpf), 0)
+    assert ctx.get_option("last_decode_replays") == 0   # (the lane kernel decoded every frame itself)
     for k in range(n_ch):
         assert np.array_equal(back[k], wavs[k]) and np.array_equal(back_o[k], wavs[k]), k
+    # one thread per frame over the reference's reader: every frame goes through it, and the counter says so
+    ctx.set_option("mc_decode_threads", 1)
+    try:
+        rc_t, back_t, fok_t, _ = ctx.decode_stream_mc(x_g, n_ch, p, wav_cap=n + 64)
+    finally:
+        ctx.set_option("mc_decode_threads", 0)
+    assert rc_t == 0 and fok_t == fok and ctx.get_option("last_decode_replays") == fok
+    for k in range(n_ch):
+        assert np.array_equal(back_t[k], wavs[k]), k
 
 
 def test_a_frame_no_reader_takes_is_frame_length(ctx):

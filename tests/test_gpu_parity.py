@@ -699,6 +699,7 @@ def test_full_size_config3_roundtrip(ctx, x3):
     assert ctx.decode_dev(out.data_ptr(), pos, off.data_ptr(), F, p, back.data_ptr(), n, n_per_clip=n) == 0
     rc, first_bad, st, before = ctx.decode_result()
     assert (rc, first_bad, st, before) == (0, F, 0, n)
+    assert ctx.get_option("last_decode_replays") == 0   # (every frame decoded by the fast kernel itself)
     lap("decode")
     assert torch.equal(back, wav)
     offs = off.cpu().numpy()
@@ -792,6 +793,7 @@ def test_full_size_config5_batch(ctx, x3):
     assert ctx.decode_dev(out.data_ptr(), pos, off.data_ptr(), F, p, back.data_ptr(), n, n_per_clip=n_per,
                           n_clips=n_clips) == 0
     assert ctx.decode_result() == (0, F, 0, n)
+    assert ctx.get_option("last_decode_replays") == 0
     assert torch.equal(back, wav)
     del back
     # header chain: every frame's header says what the index says

@@ -56,6 +56,7 @@ def test_segmented_decode_equals_the_serial_decode_and_the_oracle(ctx, x3, sb, k
     ctx.upload(d_back, np.zeros(n, dtype=np.int16))
     assert ctx.decode_dev_seg(d_out, pos, d_off, F, p, d_back, n, d_seg, sb, record=True, n_per_clip=n) == 0
     assert ctx.decode_result() == (0, F, 0, n)
+    assert ctx.get_option("last_decode_replays") == 0
     assert np.array_equal(ctx.download(d_back, 2 * n, np.int16), wav)
     seg = ctx.download(d_seg, 8 * ne, np.uint64)
     assert int(seg[0]) == (sb << 32) | 0x58335347
@@ -78,6 +79,7 @@ def test_segmented_decode_equals_the_serial_decode_and_the_oracle(ctx, x3, sb, k
         ctx.upload(d_back, np.zeros(n, dtype=np.int16))
         assert ctx.decode_dev_seg(d_out, pos, d_off, F, p, d_back, n, d_seg, sb, record=False, n_per_clip=n) == 0
         assert ctx.decode_result() == (0, F, 0, n)
+        assert ctx.get_option("last_decode_replays") == 0, want   # (an intact index: every stretch's proof holds)
         assert np.array_equal(ctx.download(d_back, 2 * n, np.int16), wav), want
         used = ctx.get_option("last_seg_stretches")
         assert 2 <= used <= nseg and (want == 0 or used <= max(want, 2)), (want, used)
@@ -88,7 +90,9 @@ def test_segmented_decode_equals_the_serial_decode_and_the_oracle(ctx, x3, sb, k
 
 def test_a_broken_index_costs_time_not_correctness(ctx, x3):
     """entries zeroed, shifted by a bit, pointing behind the payload, carrying the wrong sample, swapped between frames,
-    random: the frames they belong to go through the reference's reader and the samples are the oracle's"""
+    random: the frames they belong to -- exactly those, with every entry in use (a stretch per entry) -- go through the
+    reference's reader and the samples are the oracle's.  A header that is missing or of another granularity: whole frames
+    per lane, nothing replayed"""
     p = x3.Params.default()
     n, sb = 400_000, 64
     wav = x3.synth(2, 4242, 0, n)
@@ -112,12 +116,19 @@ def test_a_broken_index_costs_time_not_correctness(ctx, x3):
     a = good.copy(); a[::3] = rng.integers(0, 1 << 49, a[::3].size, dtype=np.uint64); cases.append(("random thirds", a))
     a = rng.integers(0, 1 << 63, good.size, dtype=np.uint64); a[0] = good[0]; cases.append(("all random", a))
     a = good.copy(); a[-1] = 0; cases.append(("last entry missing", a))
-    for name, idx in cases:
-        ctx.upload(d_seg, idx)
-        ctx.upload(d_back, np.zeros(n, dtype=np.int16))
-        assert ctx.decode_dev_seg(d_out, pos, d_off, F, p, d_back, n, d_seg, sb, n_per_clip=n) == 0, name
-        assert ctx.decode_result() == (0, F, 0, n), name
-        assert np.array_equal(ctx.download(d_back, 2 * n, np.int16), wav), name
+    nseg = (500 + sb - 1) // sb
+    ctx.set_option("seg_stretches", nseg)
+    try:
+        for name, idx in cases:
+            ctx.upload(d_seg, idx)
+            ctx.upload(d_back, np.zeros(n, dtype=np.int16))
+            assert ctx.decode_dev_seg(d_out, pos, d_off, F, p, d_back, n, d_seg, sb, n_per_clip=n) == 0, name
+            assert ctx.decode_result() == (0, F, 0, n), name
+            assert np.array_equal(ctx.download(d_back, 2 * n, np.int16), wav), name
+            altered = int((idx[1:].reshape(F, nseg - 1) != good[1:].reshape(F, nseg - 1)).any(axis=1).sum())
+            assert ctx.get_option("last_decode_replays") == (altered if idx[0] == good[0] else 0), (name, altered)
+    finally:
+        ctx.set_option("seg_stretches", 0)
 
 
 def test_segmented_decode_of_corrupt_streams_matches_the_oracle(ctx, x3):

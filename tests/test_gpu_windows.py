@@ -98,6 +98,7 @@ class Dev:
                                              d_st, n, L, d_out, fmt, d_status, idx, self.sb if idx else 0)
             assert rc == 0, self.ctx.last_error()
             res = self.ctx.decode_windows_result()
+            self.replays = self.ctx.get_option("last_window_replays")
             rows = self.ctx.download(d_out, esz * n * L, np.uint32 if fmt else np.int16).reshape(n, L)
             st = self.ctx.download(d_status, 4 * n, np.int32)
         finally:
@@ -119,10 +120,14 @@ def _starts(total, L, rng, spf=10_000):
     return sorted(s)
 
 
-def _check_exact(dev, wav, L, starts, seg=True, d_seg=None):
+def _check_exact(dev, wav, L, starts, seg=True, d_seg=None, replays=0):
+    """windows of an intact stream are its samples; `replays`: (window, frame) pairs re-decoded by the reference's reader
+    (none: every stretch's proof holds; None: not asserted)"""
     for fmt in (0, 1):
         rows, st = dev.windows(starts, L, fmt, seg=seg, d_seg=d_seg)
         assert not st.any(), (L, st)
+        if replays is not None:
+            assert dev.replays == replays, (L, fmt, dev.replays)
         for r, s in zip(rows, starts):
             want = wav[s:s + L]
             if fmt:
@@ -243,7 +248,7 @@ def test_a_broken_index_costs_time_not_correctness(ctx, x3):
     for name, idx in cases:
         ctx.upload(d_bad, idx)
         for L in (640, 25_000):
-            _check_exact(dev, wav, L, _starts(n, L, rng), d_seg=d_bad)
+            _check_exact(dev, wav, L, _starts(n, L, rng), d_seg=d_bad, replays=None)
     dev.close()
 
 

@@ -147,6 +147,7 @@ def run_batch(x3, ctx, params, frames, mode):
     assert rc == 0, ctx.last_error()
     rc, first_bad, st0, before = ctx.decode_result()
     assert rc == 0
+    run_batch.replays = ctx.get_option("last_decode_replays")
     status = ctx.download(d_st, 4 * F, np.int32)
     wav = ctx.download(d_wav, 2 * STRIDE * F, np.int16).reshape(F, STRIDE)
     for d in (d_x3, d_off, d_wav, d_st) + ((d_wo,) if d_wo else ()):
@@ -154,11 +155,41 @@ def run_batch(x3, ctx, params, frames, mode):
     return status, wav, first_bad
 
 
+def not_plain(frames, op):
+    """how many of the (payload, samples) frames are not plain (oracle_lib.frame_plain): the frames a decode launch hands to
+    the reference's reader (x3_decode_replay.h), option last_decode_replays.  Frames decode_frame refuses do not count."""
+    return sum(O.frame_plain(pay, n, op)[0] == 0 for pay, n in frames)
+
+
+def walked_frames(stream, cap):
+    """the frames x3_decode_stream / x3_decode_stream_dev hand to the decoder in one launch: the reference's walk of the
+    headers (decodefile.rs:105-121) -- up to a bad header, a cut or overlong payload, or a frame that is a panic there --
+    less those whose payload CRC fails (the check pass decides them).  -> [(payload, samples)]"""
+    out, pos, nsamp = [], 0, 0
+    while len(stream) - pos > 20:
+        h = stream[pos:pos + 20]
+        if O.crc16(h[:16]) != (int(h[16]) << 8 | int(h[17])) or (int(h[0]) << 8 | int(h[1])) != 30771 or h[3] > 1:
+            break
+        n, plen = int(h[4]) << 8 | int(h[5]), int(h[6]) << 8 | int(h[7])
+        if plen >= 0x7FE0 or plen > 24576 or len(stream) - pos - 20 < plen:   # (X3_READ_BUFFER_SIZE)
+            break
+        pay = stream[pos + 20:pos + 20 + plen]
+        if n == 0 or plen < 2 or nsamp + n > cap:
+            break
+        if O.crc16(pay) == (int(h[18]) << 8 | int(h[19])):
+            out.append((pay, n))
+        nsamp += n
+        pos += 20 + plen
+    return out
+
+
 def compare(x3, ctx, params, frames, mode):
     """crafted frames through run_batch against the oracle's decode_frame: status and samples of every frame, the 0x5A guard
-    behind every good row, the first failing frame; -> {oracle status: frames}"""
+    behind every good row, the first failing frame, and the frames the decoder handed to the reference's reader: exactly
+    those that are not plain; -> {oracle status: frames}"""
     status, wav, first_bad = run_batch(x3, ctx, params, frames, mode)
     op = oparams(params)
+    assert run_batch.replays == not_plain(frames, op), (mode, run_batch.replays, not_plain(frames, op))
     seen = {}
     exp_first_bad = len(frames)
     for i, (pay, n) in enumerate(frames):

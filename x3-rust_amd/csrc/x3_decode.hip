@@ -217,7 +217,7 @@ int decode_dev_impl(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint6
     init.first_bad = F;
     init.samples_before = 0;
     init.first_bad_status = 0;
-    init.pad = 0;
+    init.replays = 0;
     *c->h_summary_init = init;
     HIPCHK(c, hipMemcpyAsync(c->d_summary, c->h_summary_init, sizeof init, hipMemcpyHostToDevice, c->stream));
   }
@@ -268,6 +268,8 @@ extern "C" int x3_decode_result(x3_ctx* c, uint64_t* first_bad, int* first_bad_s
   HIPCHK(c, hipMemcpyAsync(c->h_summary, c->d_summary, sizeof(X3DecodeSummary), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->decode_pending = false;
+  c->last_decode_replays = c->h_summary->replays;
+  c->decode_replays += c->h_summary->replays;
   if (c->h_summary->first_bad < c->dec_frames) {
     // rare: a frame is bad -- its status and the samples of the good frames before it
     hipLaunchKernelGGL(x3_decode_prefix_kernel, dim3(1), dim3(1024), 0, c->stream, (const int32_t*)c->dec_status_ptr,
@@ -458,7 +460,10 @@ extern "C" int x3_decode_stream_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t len
   if (frames_ok) *frames_ok = 0;
   if (frame_errors) *frame_errors = 0;
   HIPCHK(c, hipSetDevice(c->device));
-  return decode_stream_dev_impl(c, d_x3, len, 0, p, d_wav, wav_cap, nullptr, n_out, frames_ok, frame_errors);
+  const unsigned long long replays0 = c->decode_replays;
+  const int rc = decode_stream_dev_impl(c, d_x3, len, 0, p, d_wav, wav_cap, nullptr, n_out, frames_ok, frame_errors);
+  c->last_decode_replays = c->decode_replays - replays0;   // (one launch, or the second of two trips)
+  return rc;
 }
 
 // the walk on the GPU (x3_index_kernels.h), then one decode launch; `phantom` as in walk_host.  own_out: decode
@@ -514,7 +519,10 @@ int decode_stream_dev_impl(x3_ctx* c, const uint8_t* d_x3, uint64_t len, uint64_
             if (first_bad < F1) {   // rare: a frame is bad -- its status and the samples of the good frames before it
               c->dec_frames = F1;
               c->decode_pending = true;
-              if ((rc = x3_decode_result(c, &first_bad, &bad_status, &before))) return rc;
+              if ((rc = x3_decode_result(c, &first_bad, &bad_status, &before))) return rc;   // (counts the replays)
+            } else {
+              c->last_decode_replays = c->h_summary->replays;
+              c->decode_replays += c->h_summary->replays;
             }
             if (n_out) *n_out = before;
             if (frames_ok) *frames_ok = first_bad;
@@ -575,7 +583,11 @@ int decode_stream_dev_impl(x3_ctx* c, const uint8_t* d_x3, uint64_t len, uint64_
 
 extern "C" int x3_decode_stream(x3_ctx* c, const uint8_t* x3, uint64_t len, const x3_params* p, int16_t* wav,
                                 uint64_t wav_cap, uint64_t* n_out, uint64_t* frames_ok, uint64_t* frame_errors) {
-  return decode_stream_impl(c, x3, len, 0, p, wav, wav_cap, n_out, frames_ok, frame_errors);
+  if (!c) return X3_ERR_BAD_ARG;
+  const unsigned long long replays0 = c->decode_replays;
+  const int rc = decode_stream_impl(c, x3, len, 0, p, wav, wav_cap, n_out, frames_ok, frame_errors);
+  c->last_decode_replays = c->decode_replays - replays0;   // (summed over the host chunks)
+  return rc;
 }
 
 void walk_host(const uint8_t* buf, uint64_t buf_len, uint64_t real_total, uint64_t believed_total,
@@ -1089,10 +1101,11 @@ extern "C" int x3_decode_windows_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3
 
 extern "C" int x3_decode_windows_result(x3_ctx* c, uint64_t* n_bad, uint64_t* first_bad, int* first_bad_status) {
   if (!c || !c->windows_pending) return X3_ERR_BAD_ARG;
-  X3WinSummary h{0, 0};
+  X3WinSummary h{0, 0, 0};
   HIPCHK(c, hipMemcpyAsync(&h, (char*)c->win_ws.p + c->win_sum_off, sizeof(h), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->windows_pending = false;
+  c->last_window_replays = h.replays;
   const bool any = h.n_bad != 0;
   if (n_bad) *n_bad = h.n_bad;
   if (first_bad) *first_bad = any ? (h.first >> 8) : c->win_windows;

@@ -123,7 +123,7 @@ x3_frame_check_kernel(const uint32_t* __restrict__ xw, uint64_t x3_len, const ui
   // early instead of being stretched to the decoder's whole duration
   __builtin_amdgcn_s_setprio(X3_CHECK_SETPRIO);
   // the summary x3_decode_merge_kernel reduces into starts as {first_bad = n_frames, samples_before = 0,
-  // status 0} (X3DecodeSummary, 24 bytes); this kernel is joined in front of the merge, so it can set that up
+  // status 0, replays 0} (X3DecodeSummary, 24 bytes); this kernel is joined in front of the merge, so it can set that up
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     summary[0] = n_frames;
     summary[1] = 0;
@@ -1114,7 +1114,7 @@ x3_decode_fast_kernel(const uint8_t* __restrict__ x3, uint64_t x3_len, const uin
 // decoder's.  A frame the decoder deferred (X3D_REPLAY: decode error, zero run >= 32 bits or a read behind
 // the payload's end -- see x3_decode_replay.h) is decoded again here, by this thread alone, through the
 // reference's own reader semantics.  Also finds the first bad frame and the total sample count.
-// summary must be pre-set to {n_frames, 0, 0}.
+// summary must be pre-set to {n_frames, 0, 0, 0}.
 __global__ void __launch_bounds__(256)
 x3_decode_merge_kernel(const int32_t* __restrict__ cstatus, int32_t* __restrict__ status,
                        const X3FrameMeta* __restrict__ meta, uint64_t n_frames_arg, X3DecodeSummary* __restrict__ out,
@@ -1152,6 +1152,7 @@ x3_decode_merge_kernel(const int32_t* __restrict__ cstatus, int32_t* __restrict_
       }
       st = x3_replay_frame(x3 + frame_off[f] + 20, m.payload_len, m.samples, p, wav + wo);
       status[f] = st;
+      atomicAdd(&out->replays, 1u);   // (option "last_decode_replays"; conforming streams never get here)
     }
     if (st != 0) atomicMin(&out->first_bad, (unsigned long long)f);
     else ns += meta[f].samples;

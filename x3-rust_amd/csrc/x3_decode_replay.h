@@ -17,7 +17,8 @@
 // of 32 bits or more, or a read position behind the payload's last byte (status X3D_REPLAY), and
 // x3_decode_merge_kernel runs such a frame again through x3_replay_frame below: a scalar restatement of
 // decoder::decode_frame (src/decoder.rs:36-58) over the reference's own reader.  Conforming streams never
-// get here.
+// get here.  The merge kernel counts such frames (option "last_decode_replays"); the oracle's x3o_frame_plain states the
+// three conditions independently, and the tests hold every fast decoder to exactly the frames it rejects.
 #pragma once
 #include "x3_device.h"
 
@@ -195,18 +196,19 @@ __global__ void x3_replay_one_kernel(const uint8_t* __restrict__ payload, uint32
 // One thread per frame over the reference's own reader: the first sample of every channel,
 // then for every block index the block of channel 0 .. n_ch-1, each against its own channel's last sample.  Channel c
 // goes to wav + c * ch_stride.  status[f]: X3D_OK or the block decoder's error; frames the check kernel has refused
-// (cstatus[f] != 0) are skipped.
+// (cstatus[f] != 0) are skipped.  *replays counts the frames decoded here (option "last_decode_replays").
 // (X3_MAX_CHANNELS: x3_tables.h)
 __global__ void __launch_bounds__(64)
 x3_decode_mc_kernel(const uint8_t* __restrict__ x3, const uint64_t* __restrict__ frame_off, const uint64_t* __restrict__ wav_off,
                     uint64_t n_frames, X3DevParams p, uint32_t n_ch, int16_t* __restrict__ wav, uint64_t ch_stride,
                     uint64_t wav_cap, const int32_t* __restrict__ cstatus, int32_t* __restrict__ status,
-                    uint32_t replay_only) {
+                    uint32_t replay_only, unsigned int* __restrict__ replays) {
   const uint64_t f = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (f >= n_frames) return;
   // replay_only (round 4): the frames x3_decode_mc_lanes_kernel has flagged (x3_decode_mc_kernel.h), nothing else
   if (replay_only && status[f] != X3D_REPLAY) return;
   if (cstatus[f] != X3D_OK) { status[f] = X3D_OK; return; }
+  atomicAdd(replays, 1u);
   const uint8_t* __restrict__ h = x3 + frame_off[f];
   const uint32_t samples = ((uint32_t)h[4] << 8) | h[5], plen = ((uint32_t)h[6] << 8) | h[7];
   const uint8_t* __restrict__ payload = h + 20;

@@ -40,10 +40,12 @@ struct X3WinPlan {
   int32_t status;  // X3D_OK or X3D_BAD_ARG from the plan
 };
 
-// the windows' summary: n_bad and min(w << 8 | status) over the bad windows
+// the windows' summary: n_bad and min(w << 8 | status) over the bad windows; replays: the (window, covering frame) pairs
+// x3_window_fixup_kernel re-decoded through the reference's reader (option "last_window_replays")
 struct X3WinSummary {
   unsigned long long n_bad;
   unsigned long long first;
+  unsigned long long replays;
 };
 
 // stream dword j (bytes 4j .. 4j+3) as a big-endian value, bytes at or beyond len read as zero
@@ -268,6 +270,7 @@ x3_window_plan_kernel(const uint64_t* __restrict__ so, uint64_t F, const uint64_
   if (w == 0) {
     sum->n_bad = 0;
     sum->first = ~0ull;
+    sum->replays = 0;
   }
   if (w >= n_windows) return;
   const uint64_t start = starts[w], total = so[F];
@@ -446,6 +449,7 @@ x3_window_fixup_kernel(const uint8_t* __restrict__ x3, const uint64_t* __restric
     const uint64_t start = starts[w], rbase = w * (uint64_t)L;
     int32_t st = pl.status;
     uint64_t zero_from = 0;   // (st != 0) the row from here on is zero
+    uint32_t replayed = 0;
     if (lane == 0 && st == X3D_OK) {
       int16_t* const blk = scratch + w * (uint64_t)scratch_per;
       for (uint64_t f = pl.fa; f < pl.fa + pl.ncov; ++f) {
@@ -466,6 +470,7 @@ x3_window_fixup_kernel(const uint8_t* __restrict__ x3, const uint64_t* __restric
           br.open(payload + 2, plen - 2u);
           uint32_t at = 1u, remaining = samples - 1u;
           fs = X3D_OK;
+          ++replayed;
           while (remaining && fs == X3D_OK) {
             const uint32_t n = remaining < p.block_len ? remaining : p.block_len;
             fs = x3_replay_block(br, n, p, last, blk);
@@ -487,6 +492,7 @@ x3_window_fixup_kernel(const uint8_t* __restrict__ x3, const uint64_t* __restric
     if (st != X3D_OK)
       for (uint64_t t = zero_from + lane; t < L; t += 64u) x3w_store(out, fmt, rbase + t, 0u);
     if (lane == 0) {
+      if (replayed) atomicAdd(&sum->replays, (unsigned long long)replayed);
       status[w] = st;
       if (st != X3D_OK) {
         atomicAdd(&sum->n_bad, 1ull);

@@ -176,6 +176,11 @@ struct x3_ctx {
   int last_enc_gen = 0;       // which kernel generation served the pending / last encode (3 wave + dense pass, 2, 1; 0 two-pass)
   unsigned long long encode_dense_frames = 0;   // frames handed to the dense pass so far (read-only option)
   unsigned long long last_dense_frames = 0;     // of the last call (either generation counts them)
+  // frames the decoders re-decoded through the reference's reader (x3_decode_replay.h): of the last x3_decode_result, or of
+  // the last x3_decode_stream / x3_decode_stream_dev / x3_decode_stream_mc as a whole (read-only option "last_decode_replays");
+  // decode_replays sums every summary read so far, the stream entry points take their difference
+  unsigned long long last_decode_replays = 0, decode_replays = 0;
+  unsigned long long last_window_replays = 0;   // (window, covering frame) pairs x3_window_fixup_kernel re-decoded
   struct LastEnc {
     const int16_t* d_wav; x3_batch b; x3_params p; uint64_t spf; uint8_t* d_out; uint64_t out_cap, start_pos; uint64_t* d_off;
     const uint64_t* src_off; const uint32_t* src_n; bool src_even;   // x3_encode_frames_dev's frame table (device), or nullptr

@@ -175,13 +175,16 @@ extern "C" int x3_decode_stream_mc(x3_ctx* c, const uint8_t* x3, uint64_t len, u
     hipLaunchKernelGGL(x3_decode_mc_kernel, dim3((unsigned)((F + 63) / 64)), dim3(64), 0, c->stream, (const uint8_t*)c->in.p,
                        (const uint64_t*)c->frame_off.p, (const uint64_t*)c->wav_off.p, F, dp, n_ch, (int16_t*)c->out.p, ch_stride,
                        std::min<uint64_t>(wav_cap, w.nsamp + 65535), (const int32_t*)c->dec_cstatus.p, (int32_t*)c->dec_status.p,
-                       lanes ? 1u : 0u);
+                       lanes ? 1u : 0u, &c->d_summary->replays);   // (the check kernel has zeroed the summary)
   }
   HIPCHK(c, hipGetLastError());
   std::vector<int32_t> cst(F), dst(F);
   HIPCHK(c, hipMemcpyAsync(cst.data(), c->dec_cstatus.p, F * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(dst.data(), c->dec_status.p, F * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->h_summary, c->d_summary, sizeof(X3DecodeSummary), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->last_decode_replays = c->h_summary->replays;
+  c->decode_replays += c->h_summary->replays;
   // the first frame that fails ends the walk: header / payload CRC errors come first (decodefile.rs:96-100)
   uint64_t first_bad = F, before = w.nsamp;
   int bad_status = 0;

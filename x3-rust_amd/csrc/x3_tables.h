@@ -36,7 +36,7 @@ struct X3DecodeSummary {
   unsigned long long first_bad;
   unsigned long long samples_before;  // valid when first_bad == n_frames (else see x3_decode_prefix_kernel)
   int first_bad_status;
-  int pad;
+  unsigned int replays;   // frames x3_decode_merge_kernel (or x3_decode_mc_kernel) re-decoded through x3_replay_frame
 };
 struct X3IndexSummary {
   unsigned long long n_frames;
