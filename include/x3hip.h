@@ -151,6 +151,12 @@ const char* x3_last_error(const x3_ctx* ctx);
  * x3_decode_stream_mc as a whole (there: the frames its per-thread kernel decoded, all of them with "mc_decode_threads" = 1).
  * A stream an encoder wrote has none.  Read-only "last_window_replays": the (window, covering frame) pairs the last
  * x3_decode_windows_dev re-decoded that way, read after x3_decode_windows_result.
+ * The GPU frame walk (x3_index_dev, x3_decode_stream_dev, x3_decode_stream of 4-16 MiB): "index_no_fast" = 1 skips its
+ * fast path (one clean chain of frames) and takes the general one (candidates, hash table, pointer doubling) every time.
+ * Read-only counters: "index_fast_walks" / "index_general_walks" (walks each path has served), "stream_one_trip"
+ * (x3_decode_stream_dev calls served with one trip to the host), "last_index_candidates" (valid headers at any byte offset
+ * that the last general walk found; 0 before the first) and "index_rescans" (general walks that found more candidates than
+ * their first buffer held and scanned the stream a second time).
  * Unknown name: X3_ERR_BAD_ARG. */
 int x3_ctx_set_option(x3_ctx* ctx, const char* name, long long value);
 int x3_ctx_get_option(const x3_ctx* ctx, const char* name, long long* value);

@@ -481,6 +481,8 @@ extern "C" int x3_ctx_get_option(const x3_ctx* c, const char* name, long long* v
   else if (n == "wav_offsets_x4") *value = c->opt.wav_offsets_x4;
   else if (n == "index_fast_walks") *value = (long long)c->index_fast;        // read-only counters
   else if (n == "index_general_walks") *value = (long long)c->index_general;
+  else if (n == "last_index_candidates") *value = (long long)c->index_last_cands;
+  else if (n == "index_rescans") *value = (long long)c->index_rescans;
   else if (n == "check_prio") *value = c->opt.check_prio;
   else if (n == "encode_fallbacks") *value = (long long)c->encode_fallbacks;  // read-only counter
   else if (n == "encode_needed_pos") *value = (long long)c->needed_pos;       // read-only: where the last host-buffer encode that ran out of room would have ended

@@ -374,12 +374,14 @@ static int index_dev_impl(x3_ctx* c, const uint8_t* d_x3, uint64_t len, uint64_t
     HIPCHK(c, hipStreamSynchronize(c->stream));
     std::memcpy(&n_cand, c->h_crc, sizeof n_cand);
     if (n_cand > cap) {  // rare: denser than one frame per 256 bytes
+      ++c->index_rescans;
       if ((rc = ensure(c, c->idx_cand, (size_t)n_cand * sizeof(X3Cand)))) return rc;
       HIPCHK(c, hipMemsetAsync(d_count, 0, sizeof(unsigned int), c->stream));
       hipLaunchKernelGGL(x3_index_candidates_kernel<false>, dim3(grid), dim3(256), 0, c->stream, xw, len, len + phantom, bl0,
                          (X3Cand*)c->idx_cand.p, n_cand, d_count, (unsigned long long*)nullptr, (uint32_t*)nullptr);
     }
   }
+  c->index_last_cands = n_cand;
   if (n_cand) {
     uint32_t tsize = 1024;
     while (tsize < 2u * n_cand && tsize < 0x80000000u) tsize <<= 1;
@@ -486,8 +488,10 @@ int decode_stream_dev_impl(x3_ctx* c, const uint8_t* d_x3, uint64_t len, uint64_
   // again the old way (the walk, a trip, the decode, a trip): the speculative decode wrote nothing that is not rewritten.
   {
     X3DevParams dq;
-    // (frames of fewer than ~1 000 samples are more than one per KiB of stream: the bound below cannot hold, and every call
-    // would pay the speculative launches and a sync before it takes the two trips anyway -- ADVICE r5)
+    // (parameters of fewer than 2 048 samples a frame do not try: frames that short often come more than one per KiB of
+    // stream, the bound below then fails, and every call would pay the speculative launches and a sync before it takes the
+    // two trips anyway -- ADVICE r5.  The gate is the parameters', the bound the stream's: quiet or zero content at 2 048
+    // samples or more can still give frames of ~300 bytes, and such a stream tries, misses the bound and takes two trips.)
     const bool try_one = !own_out && !c->opt.index_no_fast && !c->opt.two_trips && p->block_len == X3S_BL && !c->opt.decode_single &&
                          spf_of(p) >= 2048 &&
                          !c->force_single_wave_decode && derive(p, spf_of(p) > 0xFFFFFFFFull ? 0 : spf_of(p), &dq) == X3_OK &&

@@ -151,6 +151,7 @@ struct x3_ctx {
   DevBuf idx_wg, idx_sorted, idx_scan;  // ... of its fast path: candidates per scanning workgroup, in order, the scans
   DevBuf win_ws;   // x3_decode_windows_dev: plans, scans, per-frame verdicts, replay scratch, summary (x3_decode_window_kernel.h)
   unsigned long long index_fast = 0, index_general = 0;  // walks that the fast path / the general path have served (options)
+  unsigned long long index_last_cands = 0, index_rescans = 0;  // candidates of the last general walk; its second scans (options)
   int n_cus = 0;
   bool force_single_wave_decode = false;
   uint32_t desc_epoch = 0;    // tag of the current launch's frame-size descriptors (single-pass encoders)
