@@ -2,7 +2,7 @@
 defaults (codes (0, 1, 3), thresholds (3, 8, 20)), at block lengths 10, 20, 40 and 13.
 
 x3_params_validate accepts any code per block type and thresholds up to the code's table offset, and the kernels take
-such parameters.  The decoder's kernel choice depends on the codes (x3_decode.hip): the branch-free kernels need codes[0]
+such parameters.  The decoder's kernel choice depends on the codes (x3_decode.hip, decode_route): the branch-free kernels need codes[0]
 in {0, 1}; the three-wave and block-per-lane kernels also need codes[1] == 1 and codes[2] == 3 -- so (1, 1, 3) goes
 through both flagship decoders.  The reference's decoder hard-wires the sub-code widths of block types 2 and 3
 (decoder.rs:180): a stream written with another code set decodes to errors or to other samples.  That is the point here:
@@ -72,7 +72,7 @@ def ctx(x3):
 
 
 def stream_safe(codes, thr):
-    """x3_encode.hip's stream_safe_thresholds: no block can need a difference outside its code's table"""
+    """x3_encode.hip's stream_safe_thresholds (encode_route): no block can need a difference outside its code's table"""
     mmax, used = [0, 0, 0], [False] * 3
     for m in range(min(thr[2], 70000) + 1):
         ft = (m > thr[0]) + (m > thr[1])

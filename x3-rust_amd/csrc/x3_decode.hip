@@ -12,6 +12,38 @@
 // ------------------------------------------------------------------------------------------------
 // decode
 // ------------------------------------------------------------------------------------------------
+// The decoder of a call (the inputs: x3_internal.h).
+DecodeRoute decode_route(const X3DevParams& dp, const X3Geom& g, const int16_t* d_wav, bool offsets, bool x4, int seg_mode,
+                         const X3Opts& o) {
+  // the branch-free kernels need every valid Rice codeword (zeros + terminator + sub-code) to fit 32 bits
+  bool fast = true;
+  const uint32_t widths[3] = {1, 2, 4};
+  for (int k = 0; k < 3; ++k) {
+    const uint32_t level = k == 0 ? 1u : (1u << dp.k[k]);
+    fast = fast && (dp.inv_len[k] / level + 1 + widths[k] <= 32);
+  }
+  if (!fast) return {X3_DEC_SINGLE, 0, 0, false};
+  // The three-wave kernel's parser hands over i = (z << k) + r with r the k bits behind the terminating one, which equals
+  // the reference's r' + level * (n - 1) (decoder.rs:186, r' = the hard-wired 2 / 4 bits INCLUDING the one) only when the
+  // code of ftype 2 has one sub-bit and that of ftype 3 three -- the default codes; the block-per-lane kernel likewise.  The
+  // single-wave kernels follow the reference's formula literally and take every other code set.  Both multi-wave kernels
+  // need rows on 8-byte boundaries (x3_decode_split_kernel.h flush_rows): a frame's samples begin where the layout says --
+  // multiples of spf samples or of the clip stride, or the caller's offsets, which only the caller can vouch for (x4).
+  const bool rows8 = (reinterpret_cast<uintptr_t>(d_wav) & 7u) == 0 &&
+                     (offsets ? x4 : (dp.spf % 4u) == 0 && (g.fpc >= g.n_frames || (g.clip_stride % 4u) == 0));
+  if (dp.k[1] != 1u || dp.k[2] != 3u || !rows8 || o.decode_single) return {X3_DEC_SINGLE_FAST, 0, 0, false};
+  // Block length 20: the three-wave kernel, which also decodes by the segment index and records it.  Option "decode_blocks"
+  // moves the calls without an index to the block-per-lane kernel (x3_decode_blocks_kernel.h): bit-exact, but it walks
+  // every frame twice and is slower on config 3 (profiles/r6/decoder_blocks_kernel.txt).  Block lengths 10 and 40: the
+  // block-per-lane kernel is the default -- the three-wave kernel is written for blocks of 20, and the single-wave kernels
+  // are one serial chain per frame with nothing beside it (1.8 / 1.1 ms at config 3's size).
+  if (dp.block_len == X3S_BL)
+    return o.decode_blocks && !seg_mode ? DecodeRoute{X3_DEC_BLOCKS, 20u, 1u, true} : DecodeRoute{X3_DEC_SPLIT, 0, 0, true};
+  if (dp.block_len == 40u && !o.decode_blocks_off) return {X3_DEC_BLOCKS, 20u, 2u, false};
+  if (dp.block_len == 10u && !o.decode_blocks_off) return {X3_DEC_BLOCKS, 10u, 1u, false};
+  return {X3_DEC_SINGLE_FAST, 0, 0, false};
+}
+
 // wav_off_aligned: the caller knows that every d_wav_offsets[f] is a multiple of FOUR samples (the three-wave decoder
 // moves rows in 8- or 16-byte pieces); without that knowledge caller-supplied offsets go to the single-wave kernels
 int decode_dev_impl(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
@@ -35,6 +67,9 @@ int decode_dev_impl(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint6
     g.clip_stride = batch->clip_stride;
     g.fpc = (uint32_t)fpc;
   }
+  const bool by_seg = seg && seg->mode && seg->d_index && seg->seg_blocks;
+  const DecodeRoute rt = decode_route(dp, g, d_wav, d_wav_offsets != nullptr, wav_off_aligned, by_seg ? seg->mode : 0, c->opt);
+  if (d_nf && !rt.device_count) return X3_ERR_BAD_ARG;
   c->last_seg_stretches = 0;
   if ((rc = ensure(c, c->dec_meta, F * sizeof(X3FrameMeta)))) return rc;
   if (!d_status) {
@@ -77,48 +112,19 @@ int decode_dev_impl(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint6
   };
   if (c->opt.check_first && (rc = launch_check())) return rc;
   {
-    // the branch-free kernel needs every valid Rice codeword (zeros + terminator + sub-code) to fit 32 bits
-    bool fast = true;
-    const uint32_t widths[3] = {1, 2, 4};
-    for (int k = 0; k < 3; ++k) {
-      const uint32_t level = k == 0 ? 1u : (1u << dp.k[k]);
-      fast = fast && (dp.inv_len[k] / level + 1 + widths[k] <= 32);
-    }
-    // two waves per group of 64 frames (parser + valuer) when the geometry is the plain one.  Its parser hands
-    // over i = (z << k) + r with r the k bits behind the terminating one, which equals the reference's
-    // r' + level * (n - 1) (decoder.rs:186, r' = the hard-wired 2 / 4 bits INCLUDING the one) only when the
-    // code of ftype 2 has one sub-bit and that of ftype 3 three -- the default codes; the single-wave kernels
-    // follow the reference's formula literally and take every other code set.
-    const bool split = fast && dp.block_len == X3S_BL && dp.k[1] == 1u && dp.k[2] == 3u &&
-                       (!d_wav_offsets || wav_off_aligned) && !c->force_single_wave_decode &&
-                       !c->opt.decode_single && (reinterpret_cast<uintptr_t>(d_wav) & 7u) == 0 &&
-                       (d_wav_offsets || ((dp.spf % 4u) == 0 && (g.fpc * (uint64_t)1 >= g.n_frames || (g.clip_stride % 4u) == 0)));
-    // (rows on 16-byte boundaries: whole lines in 16-byte pieces; on 8-byte boundaries -- an output pointer, a clip stride
-    // or a frame length of 4 (mod 8) samples --: the same lines in 8-byte pieces, x3_decode_split_kernel.h flush_rows)
     // (X3HIP_DECODE_DYN_LDS: extra LDS per decoder group = fewer groups per CU; an occupancy experiment)
     const size_t dyn_lds = (size_t)c->opt.dyn_lds;
-    // Round 6: a BLOCK per lane (x3_decode_blocks_kernel.h).  Block length 20: option "decode_blocks" -- wherever the three-wave
-    // kernel would run frame by frame (that one keeps the segment index, decoding by it and recording it, and stays the default:
-    // the block-per-lane kernel walks every frame twice and is slower on config 3, profiles/r6/decoder_blocks_kernel.txt).
-    // Block lengths 10 and 40 (the default codes, rows on 8-byte boundaries): the block-per-lane kernel IS the default -- the
-    // three-wave kernel is written for blocks of 20, and the single-wave kernels such streams took until round 6 are one serial
-    // chain per frame with nothing beside it (1.8 / 1.1 ms at config 3's size).
-    const bool by_seg = seg && seg->mode && seg->d_index && seg->seg_blocks;
-    const bool blocks_geom = fast && dp.k[1] == 1u && dp.k[2] == 3u && (!d_wav_offsets || wav_off_aligned) &&
-                             !c->force_single_wave_decode && !c->opt.decode_single;
-    // (rows: a frame's samples begin where the layout says -- multiples of spf samples, of the clip stride, or the caller's
-    // offsets -- so the row alignment follows from the pointer's and theirs)
-    auto rows_on = [&](uint64_t bytes) {
-      const uint64_t samples_unit = bytes / 2;
-      if (reinterpret_cast<uintptr_t>(d_wav) % bytes) return false;
-      if (d_wav_offsets) return bytes <= 8;            // (the caller vouches for multiples of four samples, no more)
-      return (dp.spf % samples_unit) == 0 && (g.fpc * (uint64_t)1 >= g.n_frames || (g.clip_stride % samples_unit) == 0);
-    };
-    const bool blocks40 = blocks_geom && dp.block_len == 40u && rows_on(8) && !c->opt.decode_blocks_off;
-    const bool blocks10 = blocks_geom && dp.block_len == 10u && rows_on(8) && !c->opt.decode_blocks_off;
-    if (d_nf && !split) return X3_ERR_BAD_ARG;   // (only the block_len 20 decoders take the frame count from device memory)
-    TimerScope ts(c, 1, dec_stream, split || blocks40 || blocks10);   // (events on the dispatch packet of the kernels launched with X3_LAUNCH_TIMED; the rarer single-wave kernels below: bracketed)
-    if ((split && !by_seg && c->opt.decode_blocks) || blocks40 || blocks10) {
+    const bool paced = rt.kernel == X3_DEC_SPLIT || rt.kernel == X3_DEC_BLOCKS;   // (the kernels with a pace word)
+    c->last_decode_kernel = rt.kernel;
+    TimerScope ts(c, 1, dec_stream, paced);   // (events on the dispatch packet of the kernels launched with X3_LAUNCH_TIMED; the rarer single-wave kernels below: bracketed)
+    // the pace word's 12-bit epoch: launches 1, 2, ... 4095, then the word starts over
+    if (paced && (c->dec_epoch & 0xFFFu) == 0u) {
+      HIPCHK(c, hipMemsetAsync(c->d_pace, 0, 16, dec_stream));  // (achieved and aimed-at, one word per launch parity)
+      HIPCHK(c, hipMemsetAsync(c->d_pace + 8, 0, 8, dec_stream));   // (the launch shapes)
+      HIPCHK(c, hipMemsetAsync(c->d_pace + X3_LOG_BASE, 0, X3_LOG_ENTRIES * X3_LOG_WORDS * sizeof(uint32_t), dec_stream));  // (its atomicMax entries carry the epoch too)
+      ++c->dec_epoch;
+    }
+    if (rt.kernel == X3_DEC_BLOCKS) {
       // as many groups as give every CU the same number (five are resident per CU: the walkers of ALL groups must run
       // side by side, a frame's walk is the kernel's critical path): config 3 is 1 280 groups of 54 frames
       const uint64_t slots = (uint64_t)c->n_cus * 5;
@@ -128,37 +134,22 @@ int decode_dev_impl(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint6
         fpg = (F + rounds * slots - 1) / (rounds * slots);
       }
       const uint64_t groups = (F + fpg - 1) / fpg;
-      if ((c->dec_epoch & 0xFFFu) == 0u) {
-        HIPCHK(c, hipMemsetAsync(c->d_pace, 0, 16, dec_stream));
-        HIPCHK(c, hipMemsetAsync(c->d_pace + 8, 0, 8, dec_stream));
-        HIPCHK(c, hipMemsetAsync(c->d_pace + X3_LOG_BASE, 0, X3_LOG_ENTRIES * X3_LOG_WORDS * sizeof(uint32_t), dec_stream));
-        ++c->dec_epoch;
-      }
-      c->last_decode_kernel = 3;
 #define X3B_LAUNCH(UNIT, UPB)                                                                                             \
       X3_LAUNCH_TIMED(ts, (x3_decode_blocks_kernel<UNIT, UPB>), dim3((unsigned)groups), dim3(64 * X3B_WAVES), dyn_lds, dec_stream, \
                       d_x3, x3_len, d_frame_offsets, F, (uint32_t)fpg, g, d_wav_offsets, dp, d_wav, wav_cap, d_status,     \
                       (X3FrameMeta*)c->dec_meta.p, c->d_pace, c->dec_epoch & 0xFFFu, d_nf)
-      if (blocks40) X3B_LAUNCH(20u, 2u);
-      else if (blocks10) X3B_LAUNCH(10u, 1u);
+      if (rt.upb == 2u) X3B_LAUNCH(20u, 2u);
+      else if (rt.unit == 10u) X3B_LAUNCH(10u, 1u);
       else X3B_LAUNCH(20u, 1u);
 #undef X3B_LAUNCH
       ++c->dec_epoch;
     }
-    else if (split) {
-      c->last_decode_kernel = 2;
-      // the pace word's 12-bit epoch: launches 1, 2, ... 4095, then the word starts over
-      if ((c->dec_epoch & 0xFFFu) == 0u) {
-        HIPCHK(c, hipMemsetAsync(c->d_pace, 0, 16, dec_stream));  // (achieved and aimed-at, one word per launch parity)
-        HIPCHK(c, hipMemsetAsync(c->d_pace + 8, 0, 8, dec_stream));   // (the launch shapes)
-        HIPCHK(c, hipMemsetAsync(c->d_pace + X3_LOG_BASE, 0, X3_LOG_ENTRIES * X3_LOG_WORDS * sizeof(uint32_t), dec_stream));  // (its atomicMax entries carry the epoch too)
-        ++c->dec_epoch;
-      }
+    else if (rt.kernel == X3_DEC_SPLIT) {
       // The segment index (x3_decode_split_kernel.h, "STRETCHES"): decode by it -- a lane per stretch of `seg_blocks` blocks,
       // nseg times the groups -- or record it while decoding frame by frame.  Frames of at most one stretch need none.
       X3SegArgs sg{nullptr, nullptr, 0u, 1u, 0u, 1u};
       uint64_t groups = (F + 63) / 64;
-      if (seg && seg->mode && seg->d_index && seg->seg_blocks) {
+      if (by_seg) {
         // (the index's pitch follows the PARAMETERS -- blocks of a full frame -- not the call: x3_seg_index_entries, the
         // encoder and this launch must agree on it whatever the clips' lengths are)
         const uint64_t bpf = (dp.spf + X3S_BL - 1) / X3S_BL;
@@ -196,13 +187,11 @@ int decode_dev_impl(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint6
                          c->d_pace, c->dec_epoch & 0xFFFu, sg, d_nf);
       ++c->dec_epoch;
     }
-    else if (fast) {
-      c->last_decode_kernel = 1;
+    else if (rt.kernel == X3_DEC_SINGLE_FAST) {
       hipLaunchKernelGGL(x3_decode_fast_kernel, dim3((unsigned)((F + 63) / 64)), dim3(64), 0, dec_stream, d_x3, x3_len,
                          d_frame_offsets, F, g, d_wav_offsets, dp, d_wav, wav_cap, d_status,
                          (X3FrameMeta*)c->dec_meta.p);
     } else {
-      c->last_decode_kernel = 0;
       hipLaunchKernelGGL((x3_decode_lanes_kernel<false, 64>), dim3((unsigned)((F + 63) / 64)), dim3(64), 0, dec_stream,
                          d_x3, x3_len, d_frame_offsets, F, g, d_wav_offsets, dp, d_wav, wav_cap, d_status,
                          (X3FrameMeta*)c->dec_meta.p);
@@ -487,17 +476,17 @@ int decode_stream_dev_impl(x3_ctx* c, const uint8_t* d_x3, uint64_t len, uint64_
   // summary then objects to -- not a clean chain, more frames than the bound, sample offsets off the 8-byte grid -- is done
   // again the old way (the walk, a trip, the decode, a trip): the speculative decode wrote nothing that is not rewritten.
   {
-    X3DevParams dq;
+    const uint64_t bound = std::min<uint64_t>(cap_frames, len / 1024 + 64);
     // (parameters of fewer than 2 048 samples a frame do not try: frames that short often come more than one per KiB of
     // stream, the bound below then fails, and every call would pay the speculative launches and a sync before it takes the
     // two trips anyway -- ADVICE r5.  The gate is the parameters', the bound the stream's: quiet or zero content at 2 048
     // samples or more can still give frames of ~300 bytes, and such a stream tries, misses the bound and takes two trips.)
-    const bool try_one = !own_out && !c->opt.index_no_fast && !c->opt.two_trips && p->block_len == X3S_BL && !c->opt.decode_single &&
-                         spf_of(p) >= 2048 &&
-                         !c->force_single_wave_decode && derive(p, spf_of(p) > 0xFFFFFFFFull ? 0 : spf_of(p), &dq) == X3_OK &&
-                         dq.k[1] == 1u && dq.k[2] == 3u && (reinterpret_cast<uintptr_t>(d_wav) & 7u) == 0 &&
-                         (reinterpret_cast<uintptr_t>(d_x3) & 3u) == 0 && len >= 22;
-    const uint64_t bound = std::min<uint64_t>(cap_frames, len / 1024 + 64);
+    // The decoder must take the frame count from the device: decode_route of the speculative call below.
+    X3DevParams dq;
+    const bool try_one = !own_out && !c->opt.index_no_fast && !c->opt.two_trips && spf_of(p) >= 2048 && len >= 22 &&
+                         (reinterpret_cast<uintptr_t>(d_x3) & 3u) == 0 &&
+                         derive(p, spf_of(p) > 0xFFFFFFFFull ? 0 : spf_of(p), &dq) == X3_OK &&
+                         decode_route(dq, X3Geom{0, 0, 1, bound}, d_wav, true, true, 0, c->opt).device_count;
     if (try_one) {
       if ((rc = ensure(c, c->frame_off, (bound + 1) * sizeof(uint64_t)))) return rc;
       if ((rc = ensure(c, c->wav_off, bound * sizeof(uint64_t)))) return rc;

@@ -76,6 +76,51 @@ int ctl_begin(x3_ctx* c) {
   return X3_OK;
 }
 
+// The encoder of a call (x3_internal.h).  smem2: the LDS of a second-generation workgroup.
+EncodeRoute encode_route(const x3_params* p, uint64_t spf, const x3_batch* b, const X3FrameTable* tab, const int16_t* d_wav,
+                         size_t smem2, const X3Opts& o, bool prefer_gen2, bool force_two_pass) {
+  if (force_two_pass || o.two_pass) return {X3_ENC_TWO_PASS, 0};
+  // the single-pass kernels: block lengths 10, 20 and 40 (a lane of the second generation holds 20 samples -- half a block,
+  // one, or two -- so the bound on a frame is the same 512 lanes), frames on dword boundaries (buffer loads), and
+  // thresholds under which no block needs a difference outside its code's table
+  const uint32_t bl = p->block_len;
+  if ((bl != 20 && bl != 10 && bl != 40) || (std::min<uint64_t>(spf, b->n_per_clip) + 18) / 20 > 512 ||
+      (spf % X3_ENC_FRAME_ALIGN) != 0 || (b->n_clips != 1 && (b->clip_stride % X3_ENC_FRAME_ALIGN) != 0) ||
+      (reinterpret_cast<uintptr_t>(d_wav) & 3u) != 0 || (tab && !tab->even) || !stream_safe_thresholds(p) || smem2 > 160 * 1024)
+    return {X3_ENC_LOOKBACK, 0};
+  // the wave encoder, unless an option asks for the second generation or the last call's content was mostly dense
+  // (x3_ctx::prefer_gen2)
+  if (o.enc_gen == 3 && o.stream_wgs == 0 && !prefer_gen2) return {X3_ENC_WAVE, bl};
+  return {X3_ENC_GEN2, bl};
+}
+
+// the <TAB, BL> instance of an encoder kernel: pick(std::integral_constant TAB, std::integral_constant BL)
+template <class Pick>
+static auto enc_instance(bool tab, uint32_t bl, Pick pick) {
+  using T = std::true_type;
+  using F = std::false_type;
+  using B10 = std::integral_constant<uint32_t, 10u>;
+  using B20 = std::integral_constant<uint32_t, 20u>;
+  using B40 = std::integral_constant<uint32_t, 40u>;
+  if (tab) return bl == 10 ? pick(T{}, B10{}) : bl != 40 ? pick(T{}, B20{}) : pick(T{}, B40{});
+  return bl == 10 ? pick(F{}, B10{}) : bl != 40 ? pick(F{}, B20{}) : pick(F{}, B40{});
+}
+
+// Frame-size descriptors carry a 12-bit epoch that makes the last launch's words read "not ready" without clearing the
+// array: it is cleared when it is (re)allocated, when the epoch wraps, and while a graph is recorded (by a node of the
+// graph, on every replay).  pace: the encoder's pace words carry the same epoch.
+static int desc_begin(x3_ctx* c, DevBuf& d, size_t bytes, uint32_t& epoch, bool pace) {
+  const bool fresh = d.cap < bytes;
+  int rc;
+  if ((rc = ensure(c, d, bytes))) return rc;
+  if (fresh || c->capturing || ++epoch > 0xFFFu) {
+    HIPCHK(c, hipMemsetAsync(d.p, 0, d.cap, c->stream));
+    if (pace) HIPCHK(c, hipMemsetAsync(c->d_pace + 4, 0, 16, c->stream));
+    epoch = 1;
+  }
+  return X3_OK;
+}
+
 int encode_dev_impl(x3_ctx* c, const int16_t* d_wav, const x3_batch* b, const x3_params* p, uint64_t spf,
                            uint8_t* d_out, uint64_t out_cap, uint64_t start_pos, uint64_t* d_frame_offsets,
                            const X3FrameTable* tab) {
@@ -106,137 +151,102 @@ int encode_dev_impl(x3_ctx* c, const int16_t* d_wav, const x3_batch* b, const x3
     seg_header_open = false;
     return X3_OK;
   };
-  // ---- single-pass path: default block length, frames on dword boundaries (buffer loads)
-  // (block lengths 10 and 40, round 6: the second-generation kernel's lanes hold 20 samples whatever a block is -- half a
-  // block, one, or two -- so the bound on a frame is the same 512 lanes; the wave encoder stays with the default length)
-  const bool stream_path = (p->block_len == 20 || p->block_len == 10 || p->block_len == 40) &&
-                           (std::min<uint64_t>(spf, b->n_per_clip) + 18) / 20 <= 512 &&
-                           (spf % X3_ENC_FRAME_ALIGN) == 0 &&
-                           (b->n_clips == 1 || (b->clip_stride % X3_ENC_FRAME_ALIGN) == 0) &&
-                           (reinterpret_cast<uintptr_t>(d_wav) & 3u) == 0 && !c->force_two_pass && !c->opt.two_pass &&
-                           (!tab || tab->even);
   c->last_enc = {d_wav, *b, *p, spf, d_out, out_cap, start_pos, d_frame_offsets, tab ? tab->src_off : nullptr,
                  tab ? tab->src_n : nullptr, tab ? tab->even : false, seg};
   // part + two worst-case frame images + CRC tables + the multipliers of one chunk size (x3_encode_stream2_kernel.h)
   const size_t smem2 = X3_ENC_SMEM_HDR + 2 * (size_t)pl.img_dwords * 4 + 2048 + X3_K2_DWORDS * 4;
-  c->last_enc_gen = 0;
-  if (stream_path && c->opt.enc_gen == 3 && c->opt.stream_wgs == 0 &&
-      stream_safe_thresholds(p) && smem2 <= 160 * 1024) {
-    if (c->prefer_gen2) {
-      // the last call's content was mostly dense: the second generation, until it counts few dense frames again
-    } else {
-      // third generation (x3_encode_wave_kernel.h): one wave per frame, sixteen waves per CU, one workgroup per CU
-      static_assert(X3W_SMEM <= 160 * 1024, "LDS");
-      typedef decltype(&x3_encode_wave_kernel<false, 20u>) gen3_fn;
-      // (a block of 40 is two of a lane's runs of 20, a run is two blocks of 10: x3w_analyse40, x3w_analyse10)
-      const uint32_t bl = p->block_len;
-      const gen3_fn wave_fn = pl.g.src_off ? (bl == 40 ? &x3_encode_wave_kernel<true, 40u> : bl == 10 ? &x3_encode_wave_kernel<true, 10u>
-                                                                                                       : &x3_encode_wave_kernel<true, 20u>)
-                                           : (bl == 40 ? &x3_encode_wave_kernel<false, 40u> : bl == 10 ? &x3_encode_wave_kernel<false, 10u>
-                                                                                                       : &x3_encode_wave_kernel<false, 20u>);
-      HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(wave_fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)X3W_SMEM));
-      uint64_t nwg_max = std::min<uint64_t>((uint64_t)c->n_cus, X3W_MAX_NWG);
-      if (c->opt.wave_nwg > 0) nwg_max = std::min<uint64_t>(nwg_max, (uint64_t)c->opt.wave_nwg);
-      X3WaveArgs wa;
-      wa.m = (uint32_t)std::min<uint64_t>(X3W_WAVES, (F + nwg_max - 1) / nwg_max);
-      if (c->opt.wave_m > 0) wa.m = (uint32_t)c->opt.wave_m;
-      const uint64_t n_wggen = (F + wa.m - 1) / wa.m;
-      wa.nwg = (uint32_t)std::min<uint64_t>(nwg_max, n_wggen);
-      wa.n_wggen = (uint32_t)n_wggen;
-      const uint64_t step = (uint64_t)wa.nwg * wa.m;
-      wa.step_clip = (uint32_t)(step / pl.g.fpc);
-      wa.step_idx = (uint32_t)(step % pl.g.fpc);
-      const size_t desc_bytes = (n_wggen + X3W_DESC_PAD) * sizeof(uint32_t);
-      const bool fresh = c->desc.cap < desc_bytes;
-      if ((rc = ensure(c, c->desc, desc_bytes))) return rc;
-      if (fresh || c->capturing || ++c->desc_epoch > 0xFFFu) {   // (recorded into a graph: cleared by a node of it, every replay)
-        HIPCHK(c, hipMemsetAsync(c->desc.p, 0, c->desc.cap, c->stream));
-        HIPCHK(c, hipMemsetAsync(c->d_pace + 4, 0, 16, c->stream));
-        c->desc_epoch = 1;
+  const EncodeRoute rt = encode_route(p, spf, b, tab, d_wav, smem2, c->opt, c->prefer_gen2, c->force_two_pass);
+  auto launched = [&](int gen) {
+    c->last_enc_gen = gen;
+    c->encode_pending = true;
+    c->enc_start_pos = start_pos;
+    return X3_OK;
+  };
+  c->last_enc_gen = X3_ENC_TWO_PASS;
+  if (rt.gen == X3_ENC_WAVE) {
+    // third generation (x3_encode_wave_kernel.h): one wave per frame, sixteen waves per CU, one workgroup per CU
+    static_assert(X3W_SMEM <= 160 * 1024, "LDS");
+    // (a block of 40 is two of a lane's runs of 20, a run is two blocks of 10: x3w_analyse40, x3w_analyse10)
+    const auto wave_fn = enc_instance(pl.g.src_off != nullptr, rt.bl, [](auto t, auto l) { return &x3_encode_wave_kernel<decltype(t)::value, decltype(l)::value>; });
+    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(wave_fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)X3W_SMEM));
+    uint64_t nwg_max = std::min<uint64_t>((uint64_t)c->n_cus, X3W_MAX_NWG);
+    if (c->opt.wave_nwg > 0) nwg_max = std::min<uint64_t>(nwg_max, (uint64_t)c->opt.wave_nwg);
+    X3WaveArgs wa;
+    wa.m = (uint32_t)std::min<uint64_t>(X3W_WAVES, (F + nwg_max - 1) / nwg_max);
+    if (c->opt.wave_m > 0) wa.m = (uint32_t)c->opt.wave_m;
+    const uint64_t n_wggen = (F + wa.m - 1) / wa.m;
+    wa.nwg = (uint32_t)std::min<uint64_t>(nwg_max, n_wggen);
+    wa.n_wggen = (uint32_t)n_wggen;
+    const uint64_t step = (uint64_t)wa.nwg * wa.m;
+    wa.step_clip = (uint32_t)(step / pl.g.fpc);
+    wa.step_idx = (uint32_t)(step % pl.g.fpc);
+    if ((rc = desc_begin(c, c->desc, (n_wggen + X3W_DESC_PAD) * sizeof(uint32_t), c->desc_epoch, true))) return rc;
+    wa.wav = d_wav;
+    wa.out = d_out;
+    wa.frame_off = d_off;
+    wa.desc = (uint32_t*)c->desc.p + X3W_DESC_PAD;
+    wa.ctl = reinterpret_cast<unsigned char*>(c->d_status);
+    wa.tabs = c->d_wtab;
+    wa.log = c->d_pace + X3_LOG_ENC_BASE;
+    wa.log_epoch = ++c->enc_log_epoch & 0xFFFu;
+    if ((rc = ensure(c, c->dense_list, F * sizeof(uint32_t)))) return rc;
+    wa.dense_list = (uint32_t*)c->dense_list.p;
+    wa.out_cap = out_cap;
+    wa.start_pos = start_pos;
+    wa.n_per_clip = pl.g.n_per_clip;
+    wa.clip_stride = pl.g.clip_stride;
+    wa.n_frames = F;
+    wa.src_off = pl.g.src_off;
+    wa.src_n = pl.g.src_n;
+    wa.fpc = pl.g.fpc;
+    wa.spf = pl.dp.spf;
+    wa.epoch = c->desc_epoch;
+    wa.thr0 = pl.dp.thr[0];
+    wa.thr1 = pl.dp.thr[1];
+    wa.thr2 = pl.dp.thr[2];
+    wa.kpack = pl.dp.k[0] | (pl.dp.k[1] << 8) | (pl.dp.k[2] << 16);
+    wa.drop_wgi = c->opt.wave_drop >= 0 ? (uint32_t)c->opt.wave_drop : 0xFFFFFFFFu;
+    wa.seg = nullptr;
+    wa.seg_log2 = 0;
+    wa.seg_pitch = 0;
+    if (seg.d_index && rt.bl == 20 && seg.seg_blocks >= 4 && (seg.seg_blocks & (seg.seg_blocks - 1)) == 0) {
+      const uint64_t bpf = (spf + 19) / 20;   // blocks of a full frame (<= 512 here): the pitch follows the parameters, not the call
+      const uint64_t nidx = (bpf + seg.seg_blocks - 1) / seg.seg_blocks;
+      if (nidx >= 2 && !tab) {
+        wa.seg = reinterpret_cast<uint2*>(seg.d_index);
+        wa.seg_log2 = (uint32_t)__builtin_ctz(seg.seg_blocks);
+        wa.seg_pitch = (uint32_t)(nidx - 1);
       }
-      wa.wav = d_wav;
-      wa.out = d_out;
-      wa.frame_off = d_off;
-      wa.desc = (uint32_t*)c->desc.p + X3W_DESC_PAD;
-      wa.ctl = reinterpret_cast<unsigned char*>(c->d_status);
-      wa.tabs = c->d_wtab;
-      wa.log = c->d_pace + X3_LOG_ENC_BASE;
-      wa.log_epoch = ++c->enc_log_epoch & 0xFFFu;
-      if ((rc = ensure(c, c->dense_list, F * sizeof(uint32_t)))) return rc;
-      wa.dense_list = (uint32_t*)c->dense_list.p;
-      wa.out_cap = out_cap;
-      wa.start_pos = start_pos;
-      wa.n_per_clip = pl.g.n_per_clip;
-      wa.clip_stride = pl.g.clip_stride;
-      wa.n_frames = F;
-      wa.src_off = pl.g.src_off;
-      wa.src_n = pl.g.src_n;
-      wa.fpc = pl.g.fpc;
-      wa.spf = pl.dp.spf;
-      wa.epoch = c->desc_epoch;
-      wa.thr0 = pl.dp.thr[0];
-      wa.thr1 = pl.dp.thr[1];
-      wa.thr2 = pl.dp.thr[2];
-      wa.kpack = pl.dp.k[0] | (pl.dp.k[1] << 8) | (pl.dp.k[2] << 16);
-      wa.drop_wgi = c->opt.wave_drop >= 0 ? (uint32_t)c->opt.wave_drop : 0xFFFFFFFFu;
-      wa.seg = nullptr;
-      wa.seg_log2 = 0;
-      wa.seg_pitch = 0;
-      if (seg.d_index && bl == 20 && seg.seg_blocks >= 4 && (seg.seg_blocks & (seg.seg_blocks - 1)) == 0) {
-        const uint64_t bpf = (spf + 19) / 20;   // blocks of a full frame (<= 512 here): the pitch follows the parameters, not the call
-        const uint64_t nidx = (bpf + seg.seg_blocks - 1) / seg.seg_blocks;
-        if (nidx >= 2 && !tab) {
-          wa.seg = reinterpret_cast<uint2*>(seg.d_index);
-          wa.seg_log2 = (uint32_t)__builtin_ctz(seg.seg_blocks);
-          wa.seg_pitch = (uint32_t)(nidx - 1);
-        }
-      }
-      if (!wa.seg && (rc = seg_header_none())) return rc;
-      {
-        TimerScope ts(c, 0, nullptr, true);
-        X3_LAUNCH_TIMED(ts, wave_fn, dim3(wa.nwg), dim3(X3W_THREADS), X3W_SMEM, c->stream, wa);
-      }
-      {
-        // The dense pass, always: the frames the wave kernel listed (none, in most recordings: the workgroups read a zero
-        // count and leave, ~2 us of queue) written at the offsets it assigned.  In the stream, not in x3_encode_result:
-        // whatever the caller enqueues behind this call -- x3_decode_dev, a copy -- finds the whole stream.
-        typedef decltype(&x3_encode_stream2_kernel<true, false, 20u>) dense_fn_t;
-        const dense_fn_t dense_fn =
-            pl.g.src_off ? (bl == 40 ? &x3_encode_stream2_kernel<true, true, 40u> : bl == 10 ? &x3_encode_stream2_kernel<true, true, 10u>
-                                                                                             : &x3_encode_stream2_kernel<true, true, 20u>)
-                         : (bl == 40 ? &x3_encode_stream2_kernel<true, false, 40u> : bl == 10 ? &x3_encode_stream2_kernel<true, false, 10u>
-                                                                                              : &x3_encode_stream2_kernel<true, false, 20u>);
-        if (smem2 > 64 * 1024)
-          HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(dense_fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem2));
-        const uint64_t per_cu = std::max<uint64_t>(1, (160 * 1024) / (smem2 + 256));
-        const uint64_t grid = std::min<uint64_t>(F, (uint64_t)c->n_cus * std::min<uint64_t>(per_cu, 3));
-        TimerScope ts(c, 5, nullptr, true);
-        X3_LAUNCH_TIMED(ts, dense_fn, dim3((unsigned)grid), dim3(X3_STREAM2_THREADS), smem2,
-                        c->stream, d_wav, pl.g, pl.dp, d_off, d_out, out_cap, start_pos, (uint32_t*)nullptr, 0u,
-                        reinterpret_cast<unsigned char*>(c->d_status), (const uint32_t*)c->d_xk2,
-                        (const uint16_t*)c->d_crctab, pl.img_dwords, (uint32_t*)nullptr, (const uint32_t*)c->dense_list.p,
-                        reinterpret_cast<uint32_t*>(c->d_ctl_base + 32 * (c->ctl_half ^ 1)));
-      }
-      HIPCHK(c, hipGetLastError());
-      c->ctl_clean[c->ctl_half ^ 1] = !c->capturing;   // (the dense pass clears the next call's control block -- when it runs)
-      c->last_enc_gen = 3;
-      c->encode_pending = true;
-      c->enc_start_pos = start_pos;
-      return X3_OK;
     }
+    if (!wa.seg && (rc = seg_header_none())) return rc;
+    {
+      TimerScope ts(c, 0, nullptr, true);
+      X3_LAUNCH_TIMED(ts, wave_fn, dim3(wa.nwg), dim3(X3W_THREADS), X3W_SMEM, c->stream, wa);
+    }
+    {
+      // The dense pass, always: the frames the wave kernel listed (none, in most recordings: the workgroups read a zero
+      // count and leave, ~2 us of queue) written at the offsets it assigned.  In the stream, not in x3_encode_result:
+      // whatever the caller enqueues behind this call -- x3_decode_dev, a copy -- finds the whole stream.
+      const auto dense_fn = enc_instance(pl.g.src_off != nullptr, rt.bl, [](auto t, auto l) { return &x3_encode_stream2_kernel<true, decltype(t)::value, decltype(l)::value>; });
+      if (smem2 > 64 * 1024)
+        HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(dense_fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem2));
+      const uint64_t per_cu = std::max<uint64_t>(1, (160 * 1024) / (smem2 + 256));
+      const uint64_t grid = std::min<uint64_t>(F, (uint64_t)c->n_cus * std::min<uint64_t>(per_cu, 3));
+      TimerScope ts(c, 5, nullptr, true);
+      X3_LAUNCH_TIMED(ts, dense_fn, dim3((unsigned)grid), dim3(X3_STREAM2_THREADS), smem2,
+                      c->stream, d_wav, pl.g, pl.dp, d_off, d_out, out_cap, start_pos, (uint32_t*)nullptr, 0u,
+                      reinterpret_cast<unsigned char*>(c->d_status), (const uint32_t*)c->d_xk2,
+                      (const uint16_t*)c->d_crctab, pl.img_dwords, (uint32_t*)nullptr, (const uint32_t*)c->dense_list.p,
+                      reinterpret_cast<uint32_t*>(c->d_ctl_base + 32 * (c->ctl_half ^ 1)));
+    }
+    HIPCHK(c, hipGetLastError());
+    c->ctl_clean[c->ctl_half ^ 1] = !c->capturing;   // (the dense pass clears the next call's control block -- when it runs)
+    return launched(X3_ENC_WAVE);
   }
   if ((rc = seg_header_none())) return rc;
-  if (stream_path && stream_safe_thresholds(p)) {
+  if (rt.gen == X3_ENC_GEN2) {
     // second generation (x3_encode_stream2_kernel.h): eight waves, no sample tile in LDS
-    // the instantiation of this call: block length x (frames from a table?)
-    typedef decltype(&x3_encode_stream2_kernel<false, false, 20u>) gen2_fn;
-    const gen2_fn fn_plain = p->block_len == 10 ? &x3_encode_stream2_kernel<false, false, 10u>
-                           : p->block_len == 40 ? &x3_encode_stream2_kernel<false, false, 40u>
-                                                : &x3_encode_stream2_kernel<false, false, 20u>;
-    const gen2_fn fn_tab = p->block_len == 10 ? &x3_encode_stream2_kernel<false, true, 10u>
-                         : p->block_len == 40 ? &x3_encode_stream2_kernel<false, true, 40u>
-                                              : &x3_encode_stream2_kernel<false, true, 20u>;
-    const gen2_fn fn = pl.g.src_off ? fn_tab : fn_plain;
+    const auto fn = enc_instance(pl.g.src_off != nullptr, rt.bl, [](auto t, auto l) { return &x3_encode_stream2_kernel<false, decltype(t)::value, decltype(l)::value>; });
     const uint64_t wg_key = (uint64_t)smem2 | ((uint64_t)p->block_len << 32) | (pl.g.src_off ? 1ull << 40 : 0ull);
     if (c->stream_wg_per_cu < 0 || c->stream_wg_key != wg_key) {
       c->stream_wg_key = wg_key;
@@ -261,19 +271,11 @@ int encode_dev_impl(x3_ctx* c, const int16_t* d_wav, const x3_batch* b, const x3
         std::fprintf(stderr, "x3hip: stream encoder v2 (block length %u) %d VGPRs, %zu B LDS, occupancy API %d, by_regs %d, by_lds %d -> %d workgroups/CU\n",
                      p->block_len, fa.numRegs, smem2, nb, by_regs, by_lds, c->stream_wg_per_cu);
     }
-    if (c->stream_wg_per_cu >= 1 && smem2 <= 160 * 1024) {
-      // frame-size descriptors {epoch:12 | bytes:20}: the epoch makes last launch's words "not ready"
-      // without clearing the array (cleared when it is (re)allocated and when the epoch wraps)
+    // (no workgroup of it resident per CU: the call falls through to look-back below)
+    if (c->stream_wg_per_cu >= 1) {
       const uint64_t grid = std::min<uint64_t>(std::min<uint64_t>(F, X3_STREAM2_MAX_GRID), (uint64_t)c->n_cus * c->stream_wg_per_cu);
       const size_t desc_pad = 1024 + 64;  // words in front of desc[0]: the windows of the first frames reach below frame 0
-      const size_t desc_bytes = (F + desc_pad) * sizeof(uint32_t);
-      const bool fresh = c->desc.cap < desc_bytes;
-      if ((rc = ensure(c, c->desc, desc_bytes))) return rc;
-      if (fresh || c->capturing || ++c->desc_epoch > 0xFFFu) {   // (recorded into a graph: cleared by a node of it, every replay)
-        HIPCHK(c, hipMemsetAsync(c->desc.p, 0, c->desc.cap, c->stream));
-        HIPCHK(c, hipMemsetAsync(c->d_pace + 4, 0, 16, c->stream));  // (the encoder's pace words carry the same epoch)
-        c->desc_epoch = 1;
-      }
+      if ((rc = desc_begin(c, c->desc, (F + desc_pad) * sizeof(uint32_t), c->desc_epoch, true))) return rc;
       {
         TimerScope ts(c, 0);
         hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(X3_STREAM2_THREADS), smem2,
@@ -283,10 +285,7 @@ int encode_dev_impl(x3_ctx* c, const int16_t* d_wav, const x3_batch* b, const x3
                            (uint32_t*)nullptr);
       }
       HIPCHK(c, hipGetLastError());
-      c->last_enc_gen = 2;
-      c->encode_pending = true;
-      c->enc_start_pos = start_pos;
-      return X3_OK;
+      return launched(X3_ENC_GEN2);
     }
   }
   if (pl.smem > 64 * 1024) {
@@ -297,16 +296,10 @@ int encode_dev_impl(x3_ctx* c, const int16_t* d_wav, const x3_batch* b, const x3
   }
   // ---- any geometry in ONE pass (round 4): sizes by decoupled look-back (x3_encode_kernel.h, LOOKBACK).  The two passes
   // below stay as what a launch falls back to whose look-back gave up (x3_encode_result), and for option two_pass.
-  if (!c->force_two_pass && !c->opt.two_pass) {
+  if (rt.gen != X3_ENC_TWO_PASS) {
     HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&x3_encode_frames_kernel<false, true>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max<size_t>(pl.smem, 64 * 1024)));
-    const size_t lb_bytes = F * sizeof(unsigned long long);
-    const bool fresh = c->lb_desc.cap < lb_bytes;
-    if ((rc = ensure(c, c->lb_desc, lb_bytes))) return rc;
-    if (fresh || c->capturing || ++c->lb_epoch > 0xFFFu) {
-      HIPCHK(c, hipMemsetAsync(c->lb_desc.p, 0, c->lb_desc.cap, c->stream));
-      c->lb_epoch = 1;
-    }
+    if ((rc = desc_begin(c, c->lb_desc, F * sizeof(unsigned long long), c->lb_epoch, false))) return rc;
     {
       TimerScope ts(c, 0);
       hipLaunchKernelGGL((x3_encode_frames_kernel<false, true>), dim3((unsigned)F), dim3(pl.nthr), pl.smem, c->stream, d_wav,
@@ -315,10 +308,7 @@ int encode_dev_impl(x3_ctx* c, const int16_t* d_wav, const x3_batch* b, const x3
                          c->lb_epoch, out_cap, c->d_end_pos, c->opt.lb_drop >= 0 ? (uint32_t)c->opt.lb_drop : 0xFFFFFFFFu);
     }
     HIPCHK(c, hipGetLastError());
-    c->last_enc_gen = 1;
-    c->encode_pending = true;
-    c->enc_start_pos = start_pos;
-    return X3_OK;
+    return launched(X3_ENC_LOOKBACK);
   }
   {
     TimerScope ts(c, 2);
@@ -339,9 +329,7 @@ int encode_dev_impl(x3_ctx* c, const int16_t* d_wav, const x3_batch* b, const x3
                        c->d_status, (const uint16_t*)c->d_xpow, pl.lds_in_bytes, pl.img_dwords, 1u, (uint64_t)0);
   }
   HIPCHK(c, hipGetLastError());
-  c->encode_pending = true;
-  c->enc_start_pos = start_pos;
-  return X3_OK;
+  return launched(X3_ENC_TWO_PASS);
 }
 
 extern "C" int x3_encode_dev(x3_ctx* c, const int16_t* d_wav, const x3_batch* batch, const x3_params* p,

@@ -153,7 +153,6 @@ struct x3_ctx {
   unsigned long long index_fast = 0, index_general = 0;  // walks that the fast path / the general path have served (options)
   unsigned long long index_last_cands = 0, index_rescans = 0;  // candidates of the last general walk; its second scans (options)
   int n_cus = 0;
-  bool force_single_wave_decode = false;
   uint32_t desc_epoch = 0;    // tag of the current launch's frame-size descriptors (single-pass encoders)
   int stream_wg_per_cu = -1;  // co-resident workgroups per CU of x3_encode_stream2_kernel (-1 = not queried)
   uint64_t stream_wg_key = 0; // ... of which instantiation with how much LDS (block length, table form, bytes)
@@ -351,10 +350,23 @@ struct X3FrameTable { const uint64_t* src_off; const uint32_t* src_n; bool even;
 X3_INTERNAL int encode_dev_impl(x3_ctx* c, const int16_t* d_wav, const x3_batch* b, const x3_params* p, uint64_t spf,
                                 uint8_t* d_out, uint64_t out_cap, uint64_t start_pos, uint64_t* d_frame_offsets,
                                 const struct X3FrameTable* tab = nullptr);
+// Which encoder a call takes (option "enc_gen_in_use"), and the block length of its <TAB, BL> instance (generations 2 and 3).
+// Generation 2 falls through to look-back at launch when the occupancy query finds no resident workgroup per CU.
+enum { X3_ENC_TWO_PASS = 0, X3_ENC_LOOKBACK = 1, X3_ENC_GEN2 = 2, X3_ENC_WAVE = 3 };
+struct EncodeRoute { int gen; uint32_t bl; };
+X3_INTERNAL EncodeRoute encode_route(const x3_params* p, uint64_t spf, const x3_batch* b, const struct X3FrameTable* tab,
+                                     const int16_t* d_wav, size_t smem2, const X3Opts& o, bool prefer_gen2, bool force_two_pass);
 X3_INTERNAL int encode_host(x3_ctx* c, const int16_t* const* wavs, uint64_t n_per_clip, uint64_t n_clips,
                             const x3_params* p, uint64_t spf, uint8_t* out, uint64_t out_cap, uint64_t start_pos,
                             uint64_t* out_pos, uint64_t* clip_offsets, uint64_t stats[6]);
 // ---- x3_decode.hip
+// Which decoder a call takes (option "decode_kernel_in_use"): for the block-per-lane kernel also its <UNIT, UPB> instance;
+// `device_count`: the route takes the frame count from device memory.  offsets: the caller gives sample offsets, x4: ... and
+// promises multiples of four samples; seg_mode: the segment index is decoded by (1) or recorded (2).
+enum { X3_DEC_SINGLE = 0, X3_DEC_SINGLE_FAST = 1, X3_DEC_SPLIT = 2, X3_DEC_BLOCKS = 3 };
+struct DecodeRoute { int kernel; uint32_t unit, upb; bool device_count; };
+X3_INTERNAL DecodeRoute decode_route(const X3DevParams& dp, const X3Geom& g, const int16_t* d_wav, bool offsets, bool x4,
+                                     int seg_mode, const X3Opts& o);
 X3_INTERNAL int decode_dev_impl(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
                                 uint64_t F, const x3_batch* batch, const uint64_t* d_wav_offsets, const x3_params* p,
                                 int16_t* d_wav, uint64_t wav_cap, int32_t* d_status, bool wav_off_aligned = false,
