@@ -157,6 +157,8 @@ const char* x3_last_error(const x3_ctx* ctx);
  * (x3_decode_stream_dev calls served with one trip to the host), "last_index_candidates" (valid headers at any byte offset
  * that the last general walk found; 0 before the first) and "index_rescans" (general walks that found more candidates than
  * their first buffer held and scanned the stream a second time).
+ * x3_decode_streams_dev: read-only "streams_general_walks" (entries so far that the segmented fast walk left to the
+ * general walk) and "last_streams_general_walks" (of the last x3_decode_streams_result).
  * Unknown name: X3_ERR_BAD_ARG. */
 int x3_ctx_set_option(x3_ctx* ctx, const char* name, long long value);
 int x3_ctx_get_option(const x3_ctx* ctx, const char* name, long long* value);
@@ -576,6 +578,43 @@ int x3_decode_windows_result(x3_ctx* ctx, uint64_t* n_bad, uint64_t* first_bad, 
 /* out_format of x3_decode_windows_dev */
 #define X3_WINDOW_I16 0     /* int16 samples */
 #define X3_WINDOW_F32 1     /* float32 samples, s / 32768.0f (exact) */
+
+/* ---- BATCHES OF STREAMS (no counterpart in the reference: decodefile.rs reads one file).  Entry s of a call is the bytes
+ * [offsets[s], offsets[s] + lengths[s]) of d_x3 -- any byte offset; entries may overlap or repeat, and a batch that
+ * x3_encode_frames_dev wrote back to back is taken as it is.  All entries share one x3_params.  Each entry's results are
+ * exactly those of ONE call on that entry alone, with wav_cap = row_len:
+ *   flags 0:                         x3_decode_stream_dev(entry, p, row_len)
+ *   X3_STREAMS_ARCHIVE_FRAMES:       the frame walk of x3_x3a_decode on the archive whose frame part the entry is (the
+ *                                    reader believes in 8 bytes more than there are: decodefile.rs:62-66)
+ * -- status, n_out, frames_ok and frame_errors for every kind of damage, multi-channel frames included.  Row s of d_out
+ * (n_streams x row_len samples, out_format X3_WINDOW_I16 / X3_WINDOW_F32) holds that call's samples in [0, n_out) and
+ * zeros in [n_out, row_len); d_results[s] its x3_stream_result.  Nothing outside d_out's n_streams x row_len samples or
+ * d_results is written, nothing outside the entries (and the dwords that hold their bytes) is read.
+ *   How: every entry's frames are found on the GPU in one launch set, all entries at once (a segmented form of the frame
+ * walk's fast path: DESIGN.md section 12), then decoded by x3_decode_dev's kernels with the frame count read from device
+ * memory -- no host trip.  Where the decoder the parameters route to cannot take its count from there (single-wave
+ * decoders: codes other than the defaults, row_len not a multiple of 4), the call waits once for the count.  An entry the
+ * fast walk cannot vouch for (not one clean chain of frames from its first byte: junk, damage, a truncated last frame, a
+ * frame that does not fit its row) is walked again by x3_decode_stream_dev's own path inside x3_decode_streams_result and
+ * decoded into its row there; read-only options "streams_general_walks" / "last_streams_general_walks" count such entries.
+ *   Asynchronous on the context's stream; d_out and d_results are final once x3_decode_streams_result has returned (d_x3
+ * must stay untouched until then).  Replaces the pending state of an earlier x3_decode_dev, as x3_decode_stream_dev does.
+ * offsets / lengths are HOST arrays, checked and copied here.  X3_ERR_BAD_ARG with nothing enqueued for n_streams == 0,
+ * row_len == 0, an unknown out_format or flag, d_x3 not on a 4-byte boundary, d_out not on its sample size's boundary,
+ * d_results not on an 8-byte one, an entry outside [0, x3_len), and parameters x3_params_validate refuses. */
+#define X3_STREAMS_ARCHIVE_FRAMES 1u   /* entries are the frame part of .x3a archives: walked as X3aReader walks them */
+typedef struct x3_stream_result {
+  uint64_t n_out;        /* samples of the entry (x3_decode_stream_dev's *n_out) */
+  uint64_t frames_ok;    /* its *frames_ok */
+  int32_t status;        /* its return value */
+  uint32_t frame_errors; /* its *frame_errors */
+} x3_stream_result;
+int x3_decode_streams_dev(x3_ctx* ctx, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* offsets,
+                          const uint64_t* lengths, uint64_t n_streams, uint32_t flags, const x3_params* p, void* d_out,
+                          uint64_t row_len, int out_format, x3_stream_result* d_results);
+/* Waits for the last x3_decode_streams_dev, walks the entries the fast walk left alone: entries with status != 0, the
+ * first of them (n_streams if none) and its status. */
+int x3_decode_streams_result(x3_ctx* ctx, uint64_t* n_bad, uint64_t* first_bad, int* first_bad_status);
 
 /* ------------------------------------------------------------------ multi-GPU (no reference analogue) */
 

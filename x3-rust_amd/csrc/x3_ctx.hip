@@ -275,7 +275,8 @@ extern "C" void x3_ctx_destroy(x3_ctx* c) {
   if (c->fcache) x3_reader_close(c->fcache);
   for (DevBuf* b : {&c->in, &c->out, &c->in_more[0], &c->in_more[1], &c->out_more[0], &c->out_more[1], &c->frame_bytes, &c->frame_off, &c->dec_status, &c->dec_cstatus, &c->dec_meta, &c->wav_off,
                     &c->seg_crc, &c->desc, &c->idx_cand, &c->idx_keys, &c->idx_vals, &c->idx_J, &c->idx_S,
-                    &c->idx_L, &c->idx_sum, &c->idx_wg, &c->idx_sorted, &c->idx_scan, &c->dense_list, &c->lb_desc, &c->src_tab, &c->win_ws})
+                    &c->idx_L, &c->idx_sum, &c->idx_wg, &c->idx_sorted, &c->idx_scan, &c->dense_list, &c->lb_desc, &c->src_tab, &c->win_ws, &c->st_tab, &c->st_cand, &c->st_scan, &c->st_frames, &c->st_ent, &c->st_ws,
+                    &c->st_one, &c->st_row})
     if (b->p) (void)x3_dfree(b->p);
   for (auto& t : c->timers) {
     for (auto& e : t.used) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -481,6 +482,8 @@ extern "C" int x3_ctx_get_option(const x3_ctx* c, const char* name, long long* v
   else if (n == "wav_offsets_x4") *value = c->opt.wav_offsets_x4;
   else if (n == "index_fast_walks") *value = (long long)c->index_fast;        // read-only counters
   else if (n == "index_general_walks") *value = (long long)c->index_general;
+  else if (n == "streams_general_walks") *value = (long long)c->streams_general;   // read-only counters (x3_decode_streams_dev)
+  else if (n == "last_streams_general_walks") *value = (long long)c->last_streams_general;
   else if (n == "last_index_candidates") *value = (long long)c->index_last_cands;
   else if (n == "index_rescans") *value = (long long)c->index_rescans;
   else if (n == "check_prio") *value = c->opt.check_prio;

@@ -1105,3 +1105,288 @@ extern "C" int x3_decode_windows_result(x3_ctx* c, uint64_t* n_bad, uint64_t* fi
   if (first_bad_status) *first_bad_status = any ? (int)(h.first & 0xFFu) : 0;
   return X3_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// BATCHES OF STREAMS (include/x3hip.h; x3_streams_kernel.h)
+// ------------------------------------------------------------------------------------------------
+#include "x3_streams_kernel.h"
+
+// where the pieces of a call lie in its buffers
+struct StreamsLayout {
+  uint64_t* eoff; uint64_t* elen; uint32_t* span_first;                        // st_tab
+  X3IndexSummary* isum; X3StreamsSum* sum;                                     // st_scan: summaries, then the scans
+  unsigned int* cnt; uint32_t* base; unsigned long long* samp; unsigned long long* sbase;
+  unsigned long long* frame_off; unsigned long long* wav_off; int32_t* status; uint32_t* fent;   // st_frames (cap words)
+  unsigned long long* ent_bad; unsigned long long* ent_end; unsigned long long* ent_nsamp; unsigned long long* nout;
+  uint32_t* ent_flags; uint32_t* dirty;                                         // st_ent
+};
+
+static StreamsLayout streams_layout(x3_ctx* c, uint64_t n, uint64_t G) {
+  StreamsLayout l;
+  const uint64_t cap = G * X3I_WG_CANDS;
+  l.eoff = (uint64_t*)c->st_tab.p;
+  l.elen = l.eoff + n;
+  l.span_first = (uint32_t*)(l.elen + n);
+  l.isum = (X3IndexSummary*)c->st_scan.p;
+  l.sum = (X3StreamsSum*)((char*)c->st_scan.p + 128);
+  l.cnt = (unsigned int*)((char*)c->st_scan.p + 256);
+  l.base = (uint32_t*)(l.cnt + G);
+  l.samp = (unsigned long long*)(l.base + G);
+  l.sbase = l.samp + G;
+  l.frame_off = (unsigned long long*)c->st_frames.p;
+  l.wav_off = l.frame_off + cap;
+  l.status = (int32_t*)(l.wav_off + cap);
+  l.fent = (uint32_t*)(l.status + cap);
+  l.ent_bad = (unsigned long long*)c->st_ent.p;
+  l.ent_end = l.ent_bad + n;
+  l.ent_nsamp = l.ent_end + n;
+  l.nout = l.ent_nsamp + n;
+  l.ent_flags = (uint32_t*)(l.nout + n);
+  l.dirty = l.ent_flags + n;
+  return l;
+}
+
+// decode launch over frames [0, F) of the table (d_nf: the count on the device, or nullptr when F is the count), then the
+// per-entry verdicts and the rows
+static int streams_finish(x3_ctx* c, uint64_t F, bool device_count) {
+  auto& s = c->streams;
+  const StreamsLayout l = streams_layout(c, s.n, s.G);
+  const uint64_t total_samples = s.n * s.row_len;
+  int16_t* d_wav = s.fmt == X3_WINDOW_F32 ? (int16_t*)c->st_ws.p : (int16_t*)s.d_out;
+  const unsigned long long* d_nf = &l.isum->n_chain;
+  int rc;
+  if (F) {
+    x3_params pp = s.p;
+    if ((rc = decode_dev_impl(c, s.d_x3, s.x3_len, (const uint64_t*)l.frame_off, F, nullptr, (const uint64_t*)l.wav_off, &pp,
+                              d_wav, total_samples, l.status, s.row_len % 4u == 0, false, nullptr,
+                              device_count ? d_nf : nullptr)))
+      return rc;
+    c->decode_pending = false;   // (the merge kernel's summary is not this call's result)
+    hipLaunchKernelGGL(x3_streams_firstbad_kernel, dim3((unsigned)std::min<uint64_t>((F + 255) / 256, 4096)), dim3(256), 0,
+                       c->stream, (const int32_t*)l.status, (const uint32_t*)l.fent, F, d_nf, l.ent_bad);
+  }
+  hipLaunchKernelGGL(x3_streams_resolve_kernel, dim3((unsigned)((s.n + 255) / 256)), dim3(256), 0, c->stream,
+                     reinterpret_cast<const uint32_t*>(s.d_x3), s.x3_len, (const uint64_t*)l.eoff, (const uint64_t*)l.elen,
+                     (const uint32_t*)l.span_first, (uint32_t)s.n, s.phantom, (const uint32_t*)l.base, (uint32_t)s.G, d_nf, F,
+                     (const int32_t*)l.status, (const unsigned long long*)l.wav_off, (const uint32_t*)l.ent_flags,
+                     (const unsigned long long*)l.ent_bad, (const unsigned long long*)l.ent_end,
+                     (const unsigned long long*)l.ent_nsamp, s.row_len, s.d_results, l.nout, l.dirty, l.sum);
+  const dim3 rg((unsigned)std::min<uint64_t>((s.row_len + 255) / 256, s.fmt == X3_WINDOW_F32 ? 64 : 8),
+                (unsigned)std::min<uint64_t>(s.n, 65535));
+  if (s.fmt == X3_WINDOW_F32)
+    hipLaunchKernelGGL(x3_streams_rows_kernel<true>, rg, dim3(256), 0, c->stream, (const int16_t*)c->st_ws.p, s.d_out, s.n,
+                       s.row_len, (const unsigned long long*)l.nout, 0ull, (const X3StreamsSum*)l.sum);
+  else
+    hipLaunchKernelGGL(x3_streams_rows_kernel<false>, rg, dim3(256), 0, c->stream, (const int16_t*)nullptr, s.d_out, s.n,
+                       s.row_len, (const unsigned long long*)l.nout, 0ull, (const X3StreamsSum*)l.sum);
+  HIPCHK(c, hipGetLastError());
+  return X3_OK;
+}
+
+extern "C" int x3_decode_streams_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* offsets,
+                                     const uint64_t* lengths, uint64_t n, uint32_t flags, const x3_params* p, void* d_out,
+                                     uint64_t row_len, int out_format, x3_stream_result* d_results) {
+  if (!c || !offsets || !lengths || !p || !d_out || !d_results || (!d_x3 && x3_len)) return X3_ERR_BAD_ARG;
+  if (n == 0 || row_len == 0 || n > 0xFFFFFFF0ull || (flags & ~X3_STREAMS_ARCHIVE_FRAMES)) return X3_ERR_BAD_ARG;
+  if (out_format != X3_WINDOW_I16 && out_format != X3_WINDOW_F32) return X3_ERR_BAD_ARG;
+  const uint64_t ss = out_format == X3_WINDOW_F32 ? 4 : 2;
+  if ((reinterpret_cast<uintptr_t>(d_x3) & 3u) || (reinterpret_cast<uintptr_t>(d_out) & (ss - 1)) ||
+      (reinterpret_cast<uintptr_t>(d_results) & 7u))
+    return X3_ERR_BAD_ARG;
+  if (row_len > (~0ull / 4) / n) return X3_ERR_BAD_ARG;
+  if (x3_params_validate(p) != X3_OK) return X3_ERR_BAD_ARG;
+  uint64_t G = 0, bytes = 0;
+  for (uint64_t e = 0; e < n; ++e) {
+    if (offsets[e] > x3_len || lengths[e] > x3_len - offsets[e]) return X3_ERR_BAD_ARG;
+    G += (lengths[e] + X3T_SPAN_BYTES - 1) / X3T_SPAN_BYTES;
+    bytes += lengths[e];
+  }
+  if (G > 0x7FFFFFFFull / X3I_WG_CANDS) return X3_ERR_BAD_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  auto& s = c->streams;
+  s.pending = false;
+  s.d_x3 = d_x3;
+  s.x3_len = x3_len;
+  s.n = n;
+  s.row_len = row_len;
+  s.phantom = (flags & X3_STREAMS_ARCHIVE_FRAMES) ? 8 : 0;
+  s.fmt = out_format;
+  s.p = *p;
+  s.d_out = d_out;
+  s.d_results = d_results;
+  s.G = G;
+  s.off.assign(offsets, offsets + n);
+  s.len.assign(lengths, lengths + n);
+  s.span_first.resize(n + 1);
+  s.span_first[0] = 0;
+  for (uint64_t e = 0; e < n; ++e) s.span_first[e + 1] = s.span_first[e] + (uint32_t)((lengths[e] + X3T_SPAN_BYTES - 1) / X3T_SPAN_BYTES);
+  c->decode_pending = false;
+  // Block length 0 (frames of one sample, decided by block types alone) and option "index_no_fast": every entry takes the
+  // general walk at result time.
+  s.all_general = p->block_len == 0 || c->opt.index_no_fast != 0;
+  int rc;
+  if ((rc = ensure(c, c->st_tab, 16 * n + 4 * (n + 1) + 16))) return rc;
+  if ((rc = ensure(c, c->st_scan, 256 + 24 * G + 64))) return rc;
+  if ((rc = ensure(c, c->st_ent, 40 * n + 64))) return rc;
+  const uint64_t cap = std::max<uint64_t>(G * X3I_WG_CANDS, 1);
+  if ((rc = ensure(c, c->st_frames, 24 * cap + 64))) return rc;
+  if ((rc = ensure(c, c->st_cand, cap * sizeof(X3Cand) + 64))) return rc;
+  if (out_format == X3_WINDOW_F32 && (rc = ensure(c, c->st_ws, 2 * n * row_len + 64))) return rc;
+  const StreamsLayout l = streams_layout(c, n, G);
+  if (s.all_general) {
+    s.F = 0;
+    s.pending = true;
+    return X3_OK;
+  }
+  // the entry table through the context's pinned block (x3_encode_frames_dev's way)
+  const size_t tab_bytes = 16 * n + 4 * (n + 1);
+  if (c->ev_src_tab) HIPCHK(c, hipEventSynchronize(c->ev_src_tab));
+  else HIPCHK(c, hipEventCreateWithFlags(&c->ev_src_tab, hipEventDisableTiming));
+  if (c->h_src_tab_cap < tab_bytes) {
+    if (c->h_src_tab) (void)hipHostFree(c->h_src_tab);
+    c->h_src_tab = nullptr;
+    c->h_src_tab_cap = 0;
+    HIPCHK(c, hipHostMalloc(&c->h_src_tab, tab_bytes + tab_bytes / 4 + 64));
+    c->h_src_tab_cap = tab_bytes + tab_bytes / 4 + 64;
+  }
+  std::memcpy(c->h_src_tab, offsets, 8 * n);
+  std::memcpy((char*)c->h_src_tab + 8 * n, lengths, 8 * n);
+  std::memcpy((char*)c->h_src_tab + 16 * n, s.span_first.data(), 4 * (n + 1));
+  HIPCHK(c, hipMemcpyAsync(c->st_tab.p, c->h_src_tab, tab_bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipEventRecord(c->ev_src_tab, c->stream));
+  // clean per-call state: the summaries (bad_first = all ones), the entries' flags and first failing frames
+  HIPCHK(c, hipMemsetAsync(c->st_scan.p, 0, 256, c->stream));
+  HIPCHK(c, hipMemsetAsync(&l.sum->bad_first, 0xFF, 8, c->stream));
+  HIPCHK(c, hipMemsetAsync(l.ent_bad, 0xFF, 8 * n, c->stream));
+  HIPCHK(c, hipMemsetAsync(l.ent_flags, 0, 4 * n, c->stream));
+  const uint32_t x4 = row_len % 4u == 0 ? 1u : 0u;
+  if (G) {
+    hipLaunchKernelGGL(x3_streams_candidates_kernel, dim3((unsigned)G), dim3(256), 0, c->stream,
+                       reinterpret_cast<const uint32_t*>(d_x3), x3_len, (const uint64_t*)l.eoff, (const uint64_t*)l.elen,
+                       (const uint32_t*)l.span_first, (uint32_t)n, s.phantom, (X3Cand*)c->st_cand.p, l.cnt, l.samp,
+                       l.ent_flags);
+    hipLaunchKernelGGL(x3_index_chain_kernel, dim3(1), dim3(1024), 0, c->stream, (const unsigned int*)l.cnt,
+                       (const unsigned long long*)l.samp, (uint32_t)G, l.base, l.sbase, l.isum);
+    hipLaunchKernelGGL(x3_streams_link_kernel, dim3((unsigned)G), dim3(64), 0, c->stream, (const X3Cand*)c->st_cand.p,
+                       (const unsigned int*)l.cnt, (const uint32_t*)l.base, (const unsigned long long*)l.sbase, (uint32_t)G,
+                       (const uint64_t*)l.eoff, (const uint32_t*)l.span_first, (uint32_t)n, x3_len, row_len, x4, l.frame_off,
+                       l.wav_off, l.fent, l.ent_flags, l.ent_end, l.ent_nsamp);
+    HIPCHK(c, hipGetLastError());
+  }
+  // The decode launch covers a bound on the frame count (a frame per KiB of entry, as x3_decode_stream_dev's one-trip
+  // path bounds it) and reads the real count from the device; a batch with more is launched again, with the count, by
+  // x3_decode_streams_result.  A decoder that cannot read the count from the device: one wait for it, here.
+  X3DevParams dq;
+  const uint64_t bound = std::min<uint64_t>(cap, bytes / 1024 + n + 64);
+  const bool dev_count = G && derive(p, spf_of(p) > 0xFFFFFFFFull ? 0 : spf_of(p), &dq) == X3_OK &&
+                         decode_route(dq, X3Geom{0, 0, 1, bound}, out_format == X3_WINDOW_F32 ? (const int16_t*)c->st_ws.p
+                                                                                                : (const int16_t*)d_out,
+                                      true, x4 != 0, 0, c->opt).device_count;
+  uint64_t F = bound;
+  if (!dev_count) {
+    unsigned long long total = 0;
+    if (G) {
+      HIPCHK(c, hipMemcpyAsync(c->h_summary_init, l.isum, sizeof(X3IndexSummary), hipMemcpyDeviceToHost, c->stream));  // (pinned)
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      std::memcpy(&total, &reinterpret_cast<const X3IndexSummary*>(c->h_summary_init)->n_chain, sizeof total);
+    }
+    F = total;
+  }
+  if ((rc = streams_finish(c, F, dev_count))) return rc;
+  s.F = F;
+  s.pending = true;
+  return X3_OK;
+}
+
+// one entry by x3_decode_stream_dev's own path (an aligned copy of its bytes), into its row: the general walk
+static int streams_general(x3_ctx* c, uint64_t e, x3_stream_result* r) {
+  auto& s = c->streams;
+  const uint64_t len = s.len[e];
+  int rc;
+  if ((rc = ensure(c, c->st_one, len + 64))) return rc;
+  if (len) HIPCHK(c, hipMemcpyAsync(c->st_one.p, s.d_x3 + s.off[e], len, hipMemcpyDeviceToDevice, c->stream));
+  int16_t* row;
+  if (s.fmt == X3_WINDOW_F32) {
+    if ((rc = ensure(c, c->st_row, 2 * s.row_len + 64))) return rc;
+    row = (int16_t*)c->st_row.p;
+  } else {
+    row = (int16_t*)s.d_out + e * s.row_len;
+  }
+  uint64_t n_out = 0, fok = 0, ferr = 0;
+  rc = decode_stream_dev_impl(c, (const uint8_t*)c->st_one.p, len, s.phantom, &s.p, row, s.row_len, nullptr, &n_out, &fok, &ferr);
+  if (rc == X3_ERR_HIP) return rc;
+  if (n_out > s.row_len) n_out = s.row_len;   // (cannot happen: wav_cap)
+  r->n_out = n_out;
+  r->frames_ok = fok;
+  r->status = rc;
+  r->frame_errors = (uint32_t)ferr;
+  const dim3 rg((unsigned)std::min<uint64_t>((s.row_len + 255) / 256, 1024), 1u);
+  if (s.fmt == X3_WINDOW_F32)
+    hipLaunchKernelGGL(x3_streams_rows_kernel<true>, rg, dim3(256), 0, c->stream, (const int16_t*)row,
+                       (void*)((float*)s.d_out + e * s.row_len), (uint64_t)1, s.row_len, (const unsigned long long*)nullptr,
+                       (unsigned long long)n_out, (const X3StreamsSum*)nullptr);
+  else if (n_out < s.row_len)
+    HIPCHK(c, hipMemsetAsync(row + n_out, 0, 2 * (s.row_len - n_out), c->stream));
+  HIPCHK(c, hipGetLastError());
+  return X3_OK;
+}
+
+extern "C" int x3_decode_streams_result(x3_ctx* c, uint64_t* n_bad, uint64_t* first_bad, int* first_bad_status) {
+  if (!c || !c->streams.pending) return X3_ERR_BAD_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  auto& s = c->streams;
+  s.pending = false;
+  std::vector<uint32_t> general;
+  uint64_t nb = 0, fb = s.n;
+  int fst = 0;
+  if (s.all_general) {
+    general.resize(s.n);
+    for (uint64_t e = 0; e < s.n; ++e) general[e] = (uint32_t)e;
+  } else {
+    const StreamsLayout l = streams_layout(c, s.n, s.G);
+    X3StreamsSum sum;
+    unsigned long long total = 0;
+    HIPCHK(c, hipMemcpyAsync(c->h_summary_init, l.isum, 128 + sizeof sum, hipMemcpyDeviceToHost, c->stream));  // (pinned; both summaries)
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::memcpy(&sum, (const char*)c->h_summary_init + 128, sizeof sum);
+    std::memcpy(&total, &reinterpret_cast<const X3IndexSummary*>(c->h_summary_init)->n_chain, sizeof total);
+    if (sum.over) {   // more frames than the launch covered: again, with the count
+      HIPCHK(c, hipMemsetAsync(&l.sum->over, 0, 4, c->stream));
+      int rc = streams_finish(c, total, false);
+      if (rc) return rc;
+      s.F = total;
+      HIPCHK(c, hipMemcpyAsync(c->h_summary_init, l.isum, 128 + sizeof sum, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      std::memcpy(&sum, (const char*)c->h_summary_init + 128, sizeof sum);
+    }
+    nb = sum.n_bad;
+    if (sum.n_bad) {
+      fb = sum.bad_first >> 8;
+      fst = (int)(sum.bad_first & 0xFFull);
+    }
+    if (sum.n_dirty) {
+      general.resize(sum.n_dirty);
+      HIPCHK(c, hipMemcpyAsync(general.data(), l.dirty, 4ull * sum.n_dirty, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+  }
+  if (!general.empty()) {
+    std::vector<x3_stream_result> res(general.size());
+    for (size_t i = 0; i < general.size(); ++i) {
+      int rc = streams_general(c, general[i], &res[i]);
+      if (rc) return rc;
+      if (res[i].status != 0) {
+        ++nb;
+        if (general[i] < fb) { fb = general[i]; fst = res[i].status; }
+      }
+      HIPCHK(c, hipMemcpyAsync(s.d_results + general[i], &res[i], sizeof res[i], hipMemcpyHostToDevice, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // (res is read by the copies)
+  }
+  c->last_streams_general = general.size();
+  c->streams_general += general.size();
+  if (n_bad) *n_bad = nb;
+  if (first_bad) *first_bad = fb;
+  if (first_bad_status) *first_bad_status = fst;
+  return X3_OK;
+}

@@ -150,6 +150,21 @@ struct x3_ctx {
   DevBuf idx_cand, idx_keys, idx_vals, idx_J, idx_S, idx_L, idx_sum;  // x3_index_dev scratch
   DevBuf idx_wg, idx_sorted, idx_scan;  // ... of its fast path: candidates per scanning workgroup, in order, the scans
   DevBuf win_ws;   // x3_decode_windows_dev: plans, scans, per-frame verdicts, replay scratch, summary (x3_decode_window_kernel.h)
+  // x3_decode_streams_dev (x3_streams_kernel.h): the entry table, the spans' candidates and scans, the frame table, the
+  // per-entry words, the int16 rows of a float32 call, an entry the general walk takes (aligned copy, int16 row)
+  DevBuf st_tab, st_cand, st_scan, st_frames, st_ent, st_ws, st_one, st_row;
+  struct StreamsCall {
+    bool pending = false, all_general = false;
+    const uint8_t* d_x3 = nullptr;
+    uint64_t x3_len = 0, n = 0, row_len = 0, phantom = 0, F = 0, G = 0;
+    int fmt = 0;
+    x3_params p{};
+    void* d_out = nullptr;
+    x3_stream_result* d_results = nullptr;
+    std::vector<uint64_t> off, len;   // the entries (host copies); the device table follows them in st_tab
+    std::vector<uint32_t> span_first;
+  } streams;
+  unsigned long long streams_general = 0, last_streams_general = 0;   // entries the general walk took (options)
   unsigned long long index_fast = 0, index_general = 0;  // walks that the fast path / the general path have served (options)
   unsigned long long index_last_cands = 0, index_rescans = 0;  // candidates of the last general walk; its second scans (options)
   int n_cus = 0;

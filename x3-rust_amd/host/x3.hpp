@@ -718,6 +718,24 @@ inline X3Error decode_windows(Context& ctx, const EncodedStream& s, const Parame
   return static_cast<X3Error>(rc);
 }
 
+// A batch of independent streams (x3_decode_streams_dev): entry s = bytes [offsets[s], offsets[s] + lengths[s]) of d_x3 (flags:
+// X3_STREAMS_ARCHIVE_FRAMES for the frame parts of .x3a archives), decoded into row s of d_out (offsets.size() rows of row_len
+// samples, X3_WINDOW_I16 / X3_WINDOW_F32, zeros behind each entry's samples); d_results[s] = x3_decode_stream_dev's results on
+// that entry alone.  Waits for the call: res = entries with status != 0, the first, its status.
+inline X3Error decode_streams(Context& ctx, const uint8_t* d_x3, uint64_t x3_len, const std::vector<uint64_t>& offsets,
+                              const std::vector<uint64_t>& lengths, uint32_t flags, const Parameters& params, void* d_out,
+                              uint64_t row_len, int out_format, x3_stream_result* d_results, WindowsResult* res) {
+  if (offsets.size() != lengths.size()) return X3Error::BadArg;
+  const x3_params c = params.c_params();
+  int rc = x3_decode_streams_dev(ctx.raw(), d_x3, x3_len, offsets.data(), lengths.data(), offsets.size(), flags, &c, d_out,
+                                 row_len, out_format, d_results);
+  if (rc != X3_OK) return static_cast<X3Error>(rc);
+  WindowsResult r;
+  rc = x3_decode_streams_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status);
+  if (res) *res = r;
+  return static_cast<X3Error>(rc);
+}
+
 // Placement (x3_place_buffers; profiles/r6/decoder_modes.txt): the round trip timed on every pair of candidate buffers --
 // ms[i * backs.size() + j] for (streams[i], backs[j]).  A pipeline that keeps its buffers calls this once and keeps the
 // pair that runs best; what it does not keep it frees.

@@ -40,6 +40,15 @@ pub mod ffi {
         pub payload_len: u32,
         pub payload_crc: u16,
     }
+    /// `x3_stream_result`: one entry of `x3_decode_streams_dev`
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct x3_stream_result {
+        pub n_out: u64,
+        pub frames_ok: u64,
+        pub status: i32,
+        pub frame_errors: u32,
+    }
     #[repr(C)]
     #[derive(Clone, Copy, Debug)]
     pub struct x3_rice_code {
@@ -128,6 +137,10 @@ pub mod ffi {
                                      seg_blocks: u32, d_starts: *const u64, n_windows: u64, window_len: u32, d_out: *mut c_void,
                                      out_format: c_int, d_status: *mut i32) -> c_int;
         pub fn x3_decode_windows_result(ctx: *mut x3_ctx, n_bad: *mut u64, first_bad: *mut u64, first_bad_status: *mut c_int) -> c_int;
+        pub fn x3_decode_streams_dev(ctx: *mut x3_ctx, d_x3: *const u8, x3_len: u64, offsets: *const u64, lengths: *const u64,
+                                     n_streams: u64, flags: u32, p: *const x3_params, d_out: *mut c_void, row_len: u64,
+                                     out_format: c_int, d_results: *mut x3_stream_result) -> c_int;
+        pub fn x3_decode_streams_result(ctx: *mut x3_ctx, n_bad: *mut u64, first_bad: *mut u64, first_bad_status: *mut c_int) -> c_int;
         pub fn x3_place_buffers(ctx: *mut x3_ctx, d_wav: *const i16, n: u64, p: *const x3_params, d_streams: *const *mut u8,
                                 n_streams: u32, cap: u64, d_frame_offsets: *mut u64, d_backs: *const *mut i16, n_backs: u32,
                                 warm: u32, steps: u32, ms_per_step: *mut f64) -> c_int;
@@ -1190,6 +1203,34 @@ pub mod device {
         })?;
         let (mut n_bad, mut first_bad, mut st) = (0u64, 0u64, 0);
         error::check(unsafe { ffi::x3_decode_windows_result(gpu.raw(), &mut n_bad, &mut first_bad, &mut st) })?;
+        Ok((n_bad, first_bad, st))
+    }
+
+    /// `decode_streams` flag: the entries are the frame part of .x3a archives (walked with the reader's 8 phantom bytes)
+    pub const STREAMS_ARCHIVE_FRAMES: u32 = 1;
+
+    /// A batch of independent streams (`x3_decode_streams_dev`; not in the reference crate, which reads one file): entry s =
+    /// bytes `[offsets[s], offsets[s] + lengths[s])` of `d_x3`, decoded into row s of `d_out` (`offsets.len()` rows of
+    /// `row_len` samples, `WINDOW_I16` / `WINDOW_F32`, zeros behind each entry's samples) with `x3_decode_stream_dev`'s results
+    /// per entry in `d_results` (`x3_stream_result` each).  Waits: -> (entries with status != 0, the first of them, its status)
+    #[allow(clippy::too_many_arguments)]
+    pub fn decode_streams<'g>(gpu: &'g Gpu, d_x3: &Buffer<'g>, x3_len: usize, offsets: &[u64], lengths: &[u64], flags: u32,
+                              params: &x3::Parameters, d_out: &mut Buffer<'g>, row_len: usize, out_format: i32,
+                              d_results: &mut Buffer<'g>) -> error::Result<(u64, u64, i32)> {
+        let n = offsets.len();
+        let esz = if out_format == WINDOW_F32 { 4 } else { 2 };
+        if lengths.len() != n || x3_len > d_x3.len() || d_out.len() < esz * n * row_len
+            || d_results.len() < core::mem::size_of::<ffi::x3_stream_result>() * n {
+            return Err(X3Error::BadArg);
+        }
+        let p = params.c()?;
+        error::check(unsafe {
+            ffi::x3_decode_streams_dev(gpu.raw(), d_x3.as_ptr::<u8>(), x3_len as u64, offsets.as_ptr(), lengths.as_ptr(), n as u64,
+                                       flags, &p, d_out.as_ptr::<c_void>(), row_len as u64, out_format,
+                                       d_results.as_ptr::<ffi::x3_stream_result>())
+        })?;
+        let (mut n_bad, mut first_bad, mut st) = (0u64, 0u64, 0);
+        error::check(unsafe { ffi::x3_decode_streams_result(gpu.raw(), &mut n_bad, &mut first_bad, &mut st) })?;
         Ok((n_bad, first_bad, st))
     }
 

@@ -57,6 +57,7 @@ SYMBOLS = [
     "x3_mgpu_encode", "x3_mgpu_decode_stream",
     "x3_encode_mc", "x3_decode_stream_mc",
     "x3_sample_offsets_dev", "x3_decode_windows_dev", "x3_decode_windows_result",
+    "x3_decode_streams_dev", "x3_decode_streams_result",
     "x3_tune_candidate", "x3_tuner_create", "x3_tuner_add_dev", "x3_tuner_result", "x3_tuner_max_payloads",
     "x3_tuner_reset", "x3_tuner_destroy", "x3_tune", "x3_x3a_encode_tuned",
 ]
@@ -64,6 +65,15 @@ SYMBOLS = [
 TUNE_CANDIDATES, TUNE_DEFAULT_INDEX, TUNE_DEFAULT_SPF = 2184, 1188, 10000   # include/x3hip.h, "parameter tuning"
 
 WINDOW_I16, WINDOW_F32 = 0, 1   # x3_decode_windows_dev output formats
+STREAMS_ARCHIVE_FRAMES = 1       # x3_decode_streams_dev: entries are the frame part of .x3a archives
+
+
+class StreamResult(C.Structure):
+    """x3_stream_result: one entry of x3_decode_streams_dev"""
+    _fields_ = [("n_out", C.c_uint64), ("frames_ok", C.c_uint64), ("status", C.c_int32), ("frame_errors", C.c_uint32)]
+
+
+STREAM_RESULT_DTYPE = np.dtype([("n_out", "<u8"), ("frames_ok", "<u8"), ("status", "<i4"), ("frame_errors", "<u4")])
 
 
 class RiceCode(C.Structure):
@@ -199,6 +209,8 @@ def lib():
     L.x3_sample_offsets_dev.argtypes = [vp, vp, u64, vp, u64, vp]
     L.x3_decode_windows_dev.argtypes = [vp, vp, u64, vp, vp, u64, PP, vp, u32, vp, u64, u32, vp, i32, vp]
     L.x3_decode_windows_result.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(i32)]
+    L.x3_decode_streams_dev.argtypes = [vp, vp, u64, vp, vp, u64, u32, PP, vp, u64, i32, vp]
+    L.x3_decode_streams_result.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(i32)]
     L.x3_synth.argtypes = [i32, u64, u64, u64, vp]
     L.x3_synth_dev.argtypes = [vp, i32, u64, u64, u64, vp]
     L.x3_dev_alloc.argtypes = [vp, u64, C.POINTER(vp)]
@@ -892,6 +904,22 @@ class Context:
         rc = lib().x3_decode_windows_result(self._h, C.byref(nb), C.byref(fb), C.byref(st))
         return rc, nb.value, fb.value, st.value
 
+    def decode_streams_dev(self, d_x3, x3_len, offsets, lengths, params, d_out, row_len, out_format, d_results, flags=0):
+        """x3_decode_streams_dev: entry s = bytes [offsets[s], offsets[s] + lengths[s]) of d_x3 -> row s of d_out
+        (len(offsets) x row_len samples) and d_results[s] (asynchronous; offsets / lengths: host sequences)"""
+        offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+        lens = np.ascontiguousarray(lengths, dtype=np.uint64)
+        if offs.size != lens.size:
+            raise ValueError("offsets and lengths differ in length")
+        return lib().x3_decode_streams_dev(self._h, d_x3, x3_len, offs.ctypes.data, lens.ctypes.data, offs.size, flags,
+                                           C.byref(params), d_out, row_len, out_format, d_results)
+
+    def decode_streams_result(self):
+        """-> (rc, n_bad, first_bad, first_bad_status) of the last decode_streams_dev"""
+        nb, fb, st = C.c_uint64(0), C.c_uint64(0), C.c_int(0)
+        rc = lib().x3_decode_streams_result(self._h, C.byref(nb), C.byref(fb), C.byref(st))
+        return rc, nb.value, fb.value, st.value
+
     def synth_dev(self, kind, seed, start, n, d_out):
         rc = lib().x3_synth_dev(self._h, kind, seed, start, n, d_out)
         if rc:
@@ -1047,3 +1075,79 @@ class WindowSource:
         for p in self._own:
             self.ctx.free(p)
         self._own = []
+
+
+def _frames_samples(data, start):
+    """samples the frame headers of data[start:] announce, walked header to header (no CRC checks: a size hint)"""
+    n, pos, end = 0, start, len(data)
+    while pos + 20 <= end and data[pos] == 0x78 and data[pos + 1] == 0x33:
+        n += (data[pos + 4] << 8) | data[pos + 5]
+        pos += 20 + ((data[pos + 6] << 8) | data[pos + 7])
+    return n
+
+
+def decode_archives(ctx, archives, row_len=None, fmt=WINDOW_I16):
+    """Decode many .x3a archives (bytes-like objects or paths) into padded rows with x3_decode_streams_dev.
+
+    Each archive's header is read on the host (x3_archive_header_read); archives are grouped by parameter set and every
+    group is one device call over one buffer of frame parts.  row_len=None: the longest archive's sample count by its frame
+    headers, rounded up to a multiple of 4.  Returns (rows [n, row_len] int16 / float32, results (STREAM_RESULT_DTYPE,
+    per archive: x3_x3a_decode's n_out, frames_ok, status, frame_errors with wav_cap = row_len), sample rates) in the input
+    order.  An archive whose header does not parse gets that status, no samples, and is not sent to the device."""
+    datas = []
+    for a in archives:
+        if isinstance(a, (str, os.PathLike)):
+            with open(a, "rb") as f:
+                datas.append(f.read())
+        else:
+            datas.append(bytes(a))
+    n = len(datas)
+    if n == 0:
+        raise ValueError("no archives")
+    rates = np.zeros(n, dtype=np.uint32)
+    results = np.zeros(n, dtype=STREAM_RESULT_DTYPE)
+    groups, starts = {}, [0] * n
+    for i, d in enumerate(datas):
+        rc, rate, p, _ch, hsize = archive_header_read(np.frombuffer(d, dtype=np.uint8))
+        if rc:
+            results[i]["status"] = rc
+            continue
+        rates[i] = rate
+        starts[i] = 8 + hsize
+        key = bytes(p)
+        groups.setdefault(key, (p, []))[1].append(i)
+    if row_len is None:
+        row_len = max([_frames_samples(datas[i], starts[i]) for _, idx in groups.values() for i in idx] + [1])
+        row_len = (row_len + 3) // 4 * 4
+    esz = 4 if fmt == WINDOW_F32 else 2
+    rows = np.zeros((n, row_len), dtype=np.float32 if fmt == WINDOW_F32 else np.int16)
+    for p, idx in groups.values():
+        offs, lens, blob, pos = [], [], [], 0
+        for i in idx:
+            part = datas[i][starts[i]:]
+            offs.append(pos)
+            lens.append(len(part))
+            blob.append(part)
+            pos += len(part)
+            if pos & 1:
+                blob.append(b"\0")
+                pos += 1
+        buf = np.frombuffer(b"".join(blob) + b"\0" * 16, dtype=np.uint8)
+        m = len(idx)
+        d_x3 = ctx.alloc(buf.size)
+        d_out = ctx.alloc(esz * m * row_len)
+        d_res = ctx.alloc(STREAM_RESULT_DTYPE.itemsize * m)
+        try:
+            ctx.upload(d_x3, buf)
+            rc = ctx.decode_streams_dev(d_x3, pos, offs, lens, p, d_out, row_len, fmt, d_res, flags=STREAMS_ARCHIVE_FRAMES)
+            if rc:
+                raise X3Error(rc, "x3_decode_streams_dev: " + ctx.last_error())
+            rc = ctx.decode_streams_result()[0]
+            if rc:
+                raise X3Error(rc, "x3_decode_streams_result: " + ctx.last_error())
+            rows[idx] = ctx.download(d_out, esz * m * row_len, rows.dtype).reshape(m, row_len)
+            results[idx] = ctx.download(d_res, STREAM_RESULT_DTYPE.itemsize * m, STREAM_RESULT_DTYPE)
+        finally:
+            for ptr in (d_x3, d_out, d_res):
+                ctx.free(ptr)
+    return rows, results, rates
