@@ -276,6 +276,24 @@ extern "C" int x3_decode_result(x3_ctx* c, uint64_t* first_bad, int* first_bad_s
 // ------------------------------------------------------------------------------------------------
 // GPU-side frame index of a device-resident stream (x3_index_kernels.h)
 // ------------------------------------------------------------------------------------------------
+// the scanning grid of a stream of len bytes: a workgroup per 4 KiB, at most 16 per CU (0: an empty stream)
+static unsigned index_grid(const x3_ctx* c, uint64_t len) {
+  const uint64_t chunks = (len + 15) >> 4;
+  return (unsigned)std::min<uint64_t>((chunks + 255) / 256, (uint64_t)c->n_cus * 16);
+}
+
+// the walk's summary back to the host (one wait); a chain longer than max_frames is BAD_ARG
+static int index_summary(x3_ctx* c, const X3IndexSummary* d_sum, X3IndexSummary* result) {
+  HIPCHK(c, hipMemcpyAsync(c->h_summary_init, d_sum, sizeof *result, hipMemcpyDeviceToHost, c->stream));  // (pinned)
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  std::memcpy(result, c->h_summary_init, sizeof *result);
+  if (result->pad) {
+    c->last_error = "x3_index_dev: more frames in the stream than max_frames";
+    return X3_ERR_BAD_ARG;
+  }
+  return X3_OK;
+}
+
 // The fast path's five launches (x3_index_kernels.h), nothing waited for: the summary -- frame and sample count, how the
 // walk ends, pad2 = "not one clean chain: take the general walk" -- stays in *d_sum_out on the device.
 static int index_fast_launch(x3_ctx* c, const uint8_t* d_x3, uint64_t len, uint64_t phantom, uint32_t bl0, uint64_t wav_cap,
@@ -286,8 +304,7 @@ static int index_fast_launch(x3_ctx* c, const uint8_t* d_x3, uint64_t len, uint6
   if ((rc = ensure(c, c->idx_sum, 256))) return rc;
   unsigned int* d_count = reinterpret_cast<unsigned int*>((char*)c->idx_sum.p + 128);
   X3IndexSummary* d_sum = reinterpret_cast<X3IndexSummary*>(c->idx_sum.p);
-  const uint64_t chunks = (len + 15) >> 4;
-  const unsigned grid = (unsigned)std::min<uint64_t>((chunks + 255) / 256, (uint64_t)c->n_cus * 16);
+  const unsigned grid = index_grid(c, len);
   *d_sum_out = d_sum;
   if (!grid) return X3_ERR_BAD_ARG;
   {
@@ -325,8 +342,7 @@ static int index_dev_impl(x3_ctx* c, const uint8_t* d_x3, uint64_t len, uint64_t
   if ((rc = ensure(c, c->idx_sum, 256))) return rc;
   unsigned int* d_count = reinterpret_cast<unsigned int*>((char*)c->idx_sum.p + 128);
   X3IndexSummary* d_sum = reinterpret_cast<X3IndexSummary*>(c->idx_sum.p);
-  const uint64_t chunks = (len + 15) >> 4;
-  const unsigned grid = (unsigned)std::min<uint64_t>((chunks + 255) / 256, (uint64_t)c->n_cus * 16);
+  const unsigned grid = index_grid(c, len);
   // ---- the fast path (round 4): a stream that is ONE CLEAN CHAIN -- what an encoder writes -- needs no hash table and
   // no pointer doubling.  The scanning workgroups keep their candidates in stream order, two scans number them, and one
   // kernel checks all at once that the first frame sits at offset 0 and that every frame ends where the next begins
@@ -336,13 +352,7 @@ static int index_dev_impl(x3_ctx* c, const uint8_t* d_x3, uint64_t len, uint64_t
   if (grid && !c->opt.index_no_fast) {
     X3IndexSummary* ds = nullptr;
     if ((rc = index_fast_launch(c, d_x3, len, phantom, bl0, wav_cap, max_frames, d_frame_offsets, d_wav_offsets, &ds))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->h_summary_init, d_sum, sizeof *result, hipMemcpyDeviceToHost, c->stream));  // (pinned)
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    std::memcpy(result, c->h_summary_init, sizeof *result);
-    if (result->pad) {
-      c->last_error = "x3_index_dev: more frames in the stream than max_frames";
-      return X3_ERR_BAD_ARG;
-    }
+    if ((rc = index_summary(c, d_sum, result))) return rc;
     if (!result->pad2) {
       ++c->index_fast;
       return X3_OK;
@@ -419,14 +429,7 @@ static int index_dev_impl(x3_ctx* c, const uint8_t* d_x3, uint64_t len, uint64_t
                        (const X3Cand*)nullptr, (const unsigned long long*)nullptr, d_sum);
   }
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(c->h_summary_init, d_sum, sizeof *result, hipMemcpyDeviceToHost, c->stream));  // (pinned)
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  std::memcpy(result, c->h_summary_init, sizeof *result);
-  if (result->pad) {
-    c->last_error = "x3_index_dev: more frames in the stream than max_frames";
-    return X3_ERR_BAD_ARG;
-  }
-  return X3_OK;
+  return index_summary(c, d_sum, result);
 }
 
 extern "C" int x3_index_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t len, uint64_t max_frames,
@@ -1268,7 +1271,7 @@ extern "C" int x3_decode_streams_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3
     hipLaunchKernelGGL(x3_index_chain_kernel, dim3(1), dim3(1024), 0, c->stream, (const unsigned int*)l.cnt,
                        (const unsigned long long*)l.samp, (uint32_t)G, l.base, l.sbase, l.isum);
     hipLaunchKernelGGL(x3_streams_link_kernel, dim3((unsigned)G), dim3(64), 0, c->stream, (const X3Cand*)c->st_cand.p,
-                       (const unsigned int*)l.cnt, (const uint32_t*)l.base, (const unsigned long long*)l.sbase, (uint32_t)G,
+                       (const unsigned int*)l.cnt, (const uint32_t*)l.base, (const unsigned long long*)l.sbase,
                        (const uint64_t*)l.eoff, (const uint32_t*)l.span_first, (uint32_t)n, x3_len, row_len, x4, l.frame_off,
                        l.wav_off, l.fent, l.ent_flags, l.ent_end, l.ent_nsamp);
     HIPCHK(c, hipGetLastError());

@@ -69,6 +69,154 @@ __device__ __forceinline__ uint32_t x3i_kind(uint64_t len, uint64_t believed, ui
   return X3I_CONT;
 }
 
+// how the walk ends when it arrives at `pos` of the stream of `len` bytes at `base` of the buffer and finds no frame to push
+__device__ __forceinline__ int32_t x3i_walk_end(const uint32_t* __restrict__ xw, uint64_t n_dw, uint64_t base, uint64_t len,
+                                                uint64_t believed, uint64_t pos, uint32_t bl0) {
+  if (believed - pos <= 20) return X3D_OK;
+  if (len - pos < 20) return X3D_IO;  // read_exact of a header the reader believes in
+  uint32_t plen, samples;
+  const int32_t st = x3i_read_header(xw, n_dw, base + pos, plen, samples);
+  if (st != X3D_OK) return st;
+  const uint32_t kind = x3i_kind(len, believed, pos, plen, samples, bl0);
+  if (kind == X3I_QUIET) return X3D_OK;
+  if (kind == X3I_IO) return X3D_IO;
+  if (kind == X3I_PLEN) return X3D_FRAME_HEADER_INVALID_PAYLOAD_LEN;
+  return X3D_BAD_ARG;  // unreachable: such a header is a candidate and would be part of the chain
+}
+
+// ---- the scan of x3_index_candidates_kernel and x3_streams_candidates_kernel: each keeps its own loop over its chunks.
+// A workgroup's LDS: its candidates (c, n) and the places with the key it has yet to check (raw, nraw).
+struct X3ScanLds {
+  X3Cand c[X3I_WG_CANDS];
+  unsigned long long raw[X3I_WG_RAW];
+  uint32_t n, nraw;
+};
+
+// the key at byte `off` of the stream of L bytes at `a`: a valid header goes into the list with its offset relative to `a`
+// and its kind.  false: the list is full, cd is the candidate that did not fit.
+__device__ __forceinline__ bool x3i_consider(X3ScanLds& s, const uint32_t* __restrict__ xw, uint64_t n_dw, uint64_t off,
+                                             uint64_t a, uint64_t L, uint64_t believed, uint32_t bl0, X3Cand& cd) {
+  uint32_t plen, samples;
+  if (x3i_read_header(xw, n_dw, off, plen, samples) != X3D_OK) return true;
+  // (collected per workgroup: 70 000 atomics on ONE global counter serialise in L2, ~10 ns each -- that was
+  // 0.75 of this kernel's 0.81 ms on config 3)
+  cd.off = off - a;
+  cd.plen_kind = plen | (x3i_kind(L, believed, off - a, plen, samples, bl0) << 16);
+  cd.samples = samples;
+  const uint32_t li = atomicAdd(&s.n, 1u);
+  if (li >= X3I_WG_CANDS) return false;
+  s.c[li] = cd;
+  return true;
+}
+
+// 16-byte chunk t of the buffer and the dword behind it (dwords from n_dw on read as zero)
+__device__ __forceinline__ void x3i_load_chunk(const uint32_t* __restrict__ xw, uint64_t n_dw, uint64_t t, uint32_t (&w)[5]) {
+  if (4 * t + 4 < n_dw) {  // (all but the buffer's last chunk)
+    const uint4 v = reinterpret_cast<const uint4*>(xw)[t];
+    w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+    w[4] = xw[4 * t + 4];  // (taking it from the next lane's chunk by ds_bpermute instead: 125 against 115 us; by DPP wave_shl:1, round 4: the whole call 0.89-0.91 against 0.86-0.88 ms)
+  } else {
+#pragma unroll
+    for (int d = 0; d < 5; ++d) w[d] = 4 * t + d < n_dw ? xw[4 * t + d] : 0u;
+  }
+}
+
+// 16-byte chunk t (w: its four dwords and the next): each offset with the key whose header starts at or behind `lo` and
+// ends by `end` goes into s.raw, or to consider(off) once that list is full
+template <class Consider>
+__device__ __forceinline__ void x3i_scan_chunk(const uint32_t (&w)[5], uint64_t t, uint64_t lo, uint64_t end, X3ScanLds& s,
+                                               Consider&& consider) {
+  // filter: is the key 0x78 0x33 at ANY of the sixteen byte offsets?  Halfword-zero test (x - 0x0001..) & ~x & 0x8000..
+  // on the dwords XOR the key, for the even offsets as they are and for the odd ones shifted by a byte.  One chunk
+  // in 4 000 passes (random bytes), so the exact per-offset work below is rare.
+  uint32_t hit = 0;
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    const uint32_t e = w[d] ^ 0x33783378u;
+    const uint32_t o = __builtin_amdgcn_alignbit(w[d + 1], w[d], 8) ^ 0x33783378u;
+    hit |= ((e - 0x00010001u) & ~e) | ((o - 0x00010001u) & ~o);
+  }
+  if ((hit & 0x80008000u) == 0) return;
+#pragma unroll
+  for (int b = 0; b < 16; ++b) {
+    // bytes b, b+1 of the chunk in memory order
+    const uint32_t lw = w[b >> 2] >> (8 * (b & 3));
+    const uint32_t hw = ((b & 3) == 3 ? (lw & 0xFFu) | ((w[(b >> 2) + 1] & 0xFFu) << 8) : lw) & 0xFFFFu;
+    if (hw != 0x3378u) continue;  // bytes 0x78 0x33
+    const uint64_t off = 16 * t + b;
+    if (off < lo || off + 20 > end) continue;
+    // the key is there: the header is read and checked BEHIND the loop, all of the workgroup's at once (in the
+    // loop every one of them held its wave for a memory round trip)
+    const uint32_t ri = atomicAdd(&s.nraw, 1u);
+    if (ri < X3I_WG_RAW) {
+      s.raw[ri] = off;
+      continue;
+    }
+    consider(off);
+  }
+}
+
+// behind the loop: the places in s.raw, all at once
+template <class Consider>
+__device__ __forceinline__ void x3i_check_raw(X3ScanLds& s, Consider&& consider) {
+  __syncthreads();
+  const uint32_t nraw = s.nraw < X3I_WG_RAW ? s.nraw : X3I_WG_RAW;
+  for (uint32_t i = threadIdx.x; i < nraw; i += blockDim.x) consider(s.raw[i]);
+  __syncthreads();
+}
+
+// ordered span b: its candidates by offset at cand[b * X3I_WG_CANDS ...], their number and samples in count[b], samp[b];
+// more than the list holds: `mark` in *overflow (a plain store: every writer stores the same mark)
+__device__ __forceinline__ void x3i_store_span(const X3ScanLds& s, uint32_t b, X3Cand* __restrict__ cand, unsigned int* __restrict__ count,
+                                               unsigned long long* __restrict__ samp, uint32_t* __restrict__ overflow, uint32_t mark) {
+  const uint32_t mine = s.n < X3I_WG_CANDS ? s.n : X3I_WG_CANDS;
+  if (threadIdx.x == 0) {
+    if (s.n > X3I_WG_CANDS) *overflow = mark;
+    count[b] = mine;
+  }
+  // rank sort by offset (a dozen candidates per workgroup on config 3; 256 at most), samples summed on the way
+  X3Cand* const dst = cand + (size_t)b * X3I_WG_CANDS;
+  unsigned long long tot = 0;
+  for (uint32_t i = threadIdx.x; i < mine; i += blockDim.x) {
+    const X3Cand me = s.c[i];
+    uint32_t rank = 0;
+    for (uint32_t j = 0; j < mine; ++j) rank += s.c[j].off < me.off ? 1u : 0u;
+    dst[rank] = me;
+  }
+  if (threadIdx.x == 0) {
+    for (uint32_t j = 0; j < mine; ++j) tot += s.c[j].samples;
+    samp[b] = tot;
+  }
+}
+
+// candidate i of the n of ordered span b, in the chain of a stream whose spans end before b_end and whose first candidate
+// and sample base are k0, s0: its number k over all spans, sample offset acc in the stream, end, the next candidate's
+// offset (~0: none, it is the stream's last), and ok: a frame the walk steps over, the first at 0, ending at the next
+struct X3Link { X3Cand cd; unsigned long long k, acc, end, next; bool ok; };
+__device__ __forceinline__ X3Link x3i_link(const X3Cand* __restrict__ cand_wg, const unsigned int* __restrict__ count,
+                                           const uint32_t* __restrict__ base, const unsigned long long* __restrict__ sbase,
+                                           uint32_t b, uint32_t n, uint32_t i, uint32_t b_end, unsigned long long k0, unsigned long long s0) {
+  const X3Cand* const mine = cand_wg + (size_t)b * X3I_WG_CANDS;
+  X3Link l;
+  l.cd = mine[i];
+  l.k = (unsigned long long)base[b] + i;
+  l.acc = sbase[b] - s0;
+  for (uint32_t j = 0; j < i; ++j) l.acc += mine[j].samples;
+  l.end = l.cd.off + 20ull + (l.cd.plen_kind & 0xFFFFu);
+  l.ok = (l.cd.plen_kind >> 16) == X3I_CONT;
+  if (l.k == k0) l.ok = l.ok && l.cd.off == 0ull;
+  // the next candidate of the stream: the next one of this span, or the first one of the next span that has any
+  l.next = ~0ull;
+  if (i + 1u < n) {
+    l.next = mine[i + 1u].off;
+  } else {
+    for (uint32_t b2 = b + 1u; b2 < b_end; ++b2)
+      if (count[b2]) { l.next = cand_wg[(size_t)b2 * X3I_WG_CANDS].off; break; }
+  }
+  if (l.next != ~0ull) l.ok = l.ok && l.end == l.next;
+  return l;
+}
+
 // 0. the summary and the candidate counter start clean (one launch instead of two small copies)
 __global__ void x3_index_init_kernel(X3IndexSummary* __restrict__ sum, unsigned int* __restrict__ count) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -101,10 +249,9 @@ __global__ void __launch_bounds__(256)
 x3_index_candidates_kernel(const uint32_t* __restrict__ xw, uint64_t len, uint64_t believed, uint32_t bl0,
                            X3Cand* __restrict__ cand, uint32_t cap, unsigned int* __restrict__ count,
                            unsigned long long* __restrict__ samp, uint32_t* __restrict__ not_simple) {
-  __shared__ X3Cand s_c[X3I_WG_CANDS];
-  __shared__ uint32_t s_n, s_base, s_nraw;
-  __shared__ unsigned long long s_raw[X3I_WG_RAW];
-  if (threadIdx.x == 0) { s_n = 0; s_nraw = 0; }
+  __shared__ X3ScanLds s;
+  __shared__ uint32_t s_base;
+  if (threadIdx.x == 0) { s.n = 0; s.nraw = 0; }
   __syncthreads();
   const uint64_t n_dw = (len + 3) >> 2;
   const uint64_t chunks = (len + 15) >> 4;
@@ -118,36 +265,22 @@ x3_index_candidates_kernel(const uint32_t* __restrict__ xw, uint64_t len, uint64
   // nothing requested ahead and half the instructions per trip: 113 us; without the fifth dword: 103.  A bare read of the
   // same bytes, one span per workgroup, takes 58 us (tools/ubench/read_rate.hip: 6.3 TB/s): it is not the loads.  It was
   // the candidates: each header read in the loop held its wave for a memory round trip -- checked behind the loop, all at
-  // once (s_raw, below): 74 us.)
+  // once (s.raw, x3i_scan_chunk): 74 us.)
   auto fetch = [&](uint64_t t, uint32_t (&w)[5]) {
-    if (t >= t_end) {
-#pragma unroll
-      for (int d = 0; d < 5; ++d) w[d] = 0u;
-    } else if (4 * t + 4 < n_dw) {  // (all but the stream's last chunk)
-      const uint4 v = reinterpret_cast<const uint4*>(xw)[t];
-      w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-      w[4] = xw[4 * t + 4];  // (taking it from the next lane's chunk by ds_bpermute instead: 125 against 115 us; by DPP wave_shl:1, round 4: the whole call 0.89-0.91 against 0.86-0.88 ms)
+    if (t < t_end) {
+      x3i_load_chunk(xw, n_dw, t, w);
     } else {
 #pragma unroll
-      for (int d = 0; d < 5; ++d) w[d] = 4 * t + d < n_dw ? xw[4 * t + d] : 0u;
+      for (int d = 0; d < 5; ++d) w[d] = 0u;
     }
   };
   auto consider = [&](uint64_t off) {
-      uint32_t plen, samples;
-      if (x3i_read_header(xw, n_dw, off, plen, samples) != X3D_OK) return;
-      // (collected per workgroup: 70 000 atomics on ONE global counter serialise in L2, ~10 ns each -- that was
-      // 0.75 of this kernel's 0.81 ms on config 3)
-      X3Cand cd;
-      cd.off = off;
-      cd.plen_kind = plen | (x3i_kind(len, believed, off, plen, samples, bl0) << 16);
-      cd.samples = samples;
-      const uint32_t li = atomicAdd(&s_n, 1u);
-      if (li < X3I_WG_CANDS) {
-        s_c[li] = cd;
-      } else if (!ORDERED) {  // (a span with more candidates than the workgroup's buffer holds: straight to the global counter)
-        const unsigned int slot = atomicAdd(count, 1u);
-        if (cand && slot < cap) cand[slot] = cd;
-      }
+    X3Cand cd;
+    if (!x3i_consider(s, xw, n_dw, off, 0ull, len, believed, bl0, cd) && !ORDERED) {
+      // (a span with more candidates than the workgroup's list holds: straight to the global counter)
+      const unsigned int slot = atomicAdd(count, 1u);
+      if (cand && slot < cap) cand[slot] = cd;
+    }
   };
   const uint64_t t_first = (uint64_t)blockIdx.x * per_wg + threadIdx.x;
   uint32_t wa[5], wb[5];
@@ -158,66 +291,18 @@ x3_index_candidates_kernel(const uint32_t* __restrict__ xw, uint64_t len, uint64
 #pragma unroll
     for (int d = 0; d < 5; ++d) { w[d] = wa[d]; wa[d] = wb[d]; }
     fetch(t + 2 * (uint64_t)blockDim.x, wb);
-    // filter: is the key 0x78 0x33 at ANY of the sixteen byte offsets?  Halfword-zero test (x - 0x0001..) & ~x & 0x8000..
-    // on the dwords XOR the key, for the even offsets as they are and for the odd ones shifted by a byte.  One chunk
-    // in 4 000 passes (random bytes), so the exact per-offset work below is rare.
-    uint32_t hit = 0;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-      const uint32_t e = w[d] ^ 0x33783378u;
-      const uint32_t o = __builtin_amdgcn_alignbit(w[d + 1], w[d], 8) ^ 0x33783378u;
-      hit |= ((e - 0x00010001u) & ~e) | ((o - 0x00010001u) & ~o);
-    }
-    if ((hit & 0x80008000u) == 0) continue;
-#pragma unroll
-    for (int b = 0; b < 16; ++b) {
-      // bytes b, b+1 of the chunk in memory order
-      const uint32_t lo = w[b >> 2] >> (8 * (b & 3));
-      const uint32_t hw = ((b & 3) == 3 ? (lo & 0xFFu) | ((w[(b >> 2) + 1] & 0xFFu) << 8) : lo) & 0xFFFFu;
-      if (hw != 0x3378u) continue;  // bytes 0x78 0x33
-      const uint64_t off = 16 * t + b;
-      if (off + 20 > len) continue;
-      // the key is there: the header is read and checked BEHIND the loop, all of the workgroup's at once (in the
-      // loop every one of them held its wave for a memory round trip)
-      const uint32_t ri = atomicAdd(&s_nraw, 1u);
-      if (ri < X3I_WG_RAW) {
-        s_raw[ri] = off;
-        continue;
-      }
-      consider(off);
-    }
+    x3i_scan_chunk(w, t, 0ull, len, s, consider);
   }
-  __syncthreads();
-  {
-    const uint32_t nraw = s_nraw < X3I_WG_RAW ? s_nraw : X3I_WG_RAW;
-    for (uint32_t i = threadIdx.x; i < nraw; i += blockDim.x) consider(s_raw[i]);
-  }
-  __syncthreads();
-  const uint32_t mine = s_n < X3I_WG_CANDS ? s_n : X3I_WG_CANDS;
+  x3i_check_raw(s, consider);
   if (ORDERED) {
-    if (threadIdx.x == 0) {
-      if (s_n > X3I_WG_CANDS) *not_simple = 1u;
-      count[blockIdx.x] = mine;
-    }
-    // rank sort by offset (a dozen candidates per workgroup on config 3; 256 at most), samples summed on the way
-    X3Cand* const dst = cand + (size_t)blockIdx.x * X3I_WG_CANDS;
-    unsigned long long tot = 0;
-    for (uint32_t i = threadIdx.x; i < mine; i += blockDim.x) {
-      const X3Cand me = s_c[i];
-      uint32_t rank = 0;
-      for (uint32_t j = 0; j < mine; ++j) rank += s_c[j].off < me.off ? 1u : 0u;
-      dst[rank] = me;
-    }
-    if (threadIdx.x == 0) {
-      for (uint32_t j = 0; j < mine; ++j) tot += s_c[j].samples;
-      samp[blockIdx.x] = tot;
-    }
+    x3i_store_span(s, blockIdx.x, cand, count, samp, not_simple, 1u);
     return;
   }
+  const uint32_t mine = s.n < X3I_WG_CANDS ? s.n : X3I_WG_CANDS;
   if (threadIdx.x == 0) s_base = mine ? atomicAdd(count, mine) : 0u;
   __syncthreads();
   for (uint32_t i = threadIdx.x; i < mine; i += blockDim.x)
-    if (cand && s_base + i < cap) cand[s_base + i] = s_c[i];
+    if (cand && s_base + i < cap) cand[s_base + i] = s.c[i];
 }
 
 __device__ __forceinline__ uint32_t x3i_hash(unsigned long long off, uint32_t mask) {
@@ -367,22 +452,10 @@ __global__ void x3_index_finalize_kernel(const uint32_t* __restrict__ xw, uint64
   const unsigned long long n_chain = sum->n_chain;
   if (sum->pad) return;  // more frames than the caller's arrays hold: the host reports it
   const uint64_t n_dw = (len + 3) >> 2;
-  auto ending_at = [&](uint64_t pos) -> int {  // the walk arrives at `pos` and finds no frame to push
-    if (believed - pos <= 20) return X3D_OK;
-    if (len - pos < 20) return X3D_IO;  // read_exact of a header the reader believes in
-    uint32_t plen, samples;
-    const int32_t st = x3i_read_header(xw, n_dw, pos, plen, samples);
-    if (st != X3D_OK) return st;
-    const uint32_t kind = x3i_kind(len, believed, pos, plen, samples, bl0);
-    if (kind == X3I_QUIET) return X3D_OK;
-    if (kind == X3I_IO) return X3D_IO;
-    if (kind == X3I_PLEN) return X3D_FRAME_HEADER_INVALID_PAYLOAD_LEN;
-    return X3D_BAD_ARG;  // unreachable: such a header is a candidate and would be part of the chain
-  };
   if (start == X3I_NONE) {
     sum->n_frames = 0;
     sum->n_samples = 0;
-    sum->terminal = ending_at(0);
+    sum->terminal = x3i_walk_end(xw, n_dw, 0ull, len, believed, 0ull, bl0);
     return;
   }
   if (sum->first_over < n_chain) {  // the first frame that does not fit the output: pushed, BAD_ARG
@@ -398,7 +471,7 @@ __global__ void x3_index_finalize_kernel(const uint32_t* __restrict__ xw, uint64
     sum->terminal = X3D_BAD_ARG;
   } else {
     sum->n_samples = wav_off[n_chain - 1] + last.samples;
-    sum->terminal = ending_at(last.off + 20ull + (last.plen_kind & 0xFFFFu));
+    sum->terminal = x3i_walk_end(xw, n_dw, 0ull, len, believed, last.off + 20ull + (last.plen_kind & 0xFFFFu), bl0);
   }
 }
 
@@ -463,30 +536,15 @@ x3_index_link_kernel(const X3Cand* __restrict__ cand_wg, const unsigned int* __r
     if (b == 0 && threadIdx.x == 0) sum->pad2 = 1;
     return;
   }
-  const X3Cand* const mine = cand_wg + (size_t)b * X3I_WG_CANDS;
   for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
-    const X3Cand cd = mine[i];
-    const unsigned long long k = (unsigned long long)base[b] + i;
-    unsigned long long acc = sbase[b];
-    for (uint32_t j = 0; j < i; ++j) acc += mine[j].samples;
-    bool ok = (cd.plen_kind >> 16) == X3I_CONT;
-    if (k == 0ull) ok = ok && cd.off == 0ull;
-    // the next candidate of the stream: the next one of this span, or the first one of the next span that has any
-    unsigned long long next_off = ~0ull;
-    if (i + 1u < n) {
-      next_off = mine[i + 1u].off;
-    } else {
-      for (uint32_t b2 = b + 1u; b2 < G; ++b2)
-        if (count[b2]) { next_off = cand_wg[(size_t)b2 * X3I_WG_CANDS].off; break; }
-    }
-    if (next_off != ~0ull) ok = ok && cd.off + 20ull + (cd.plen_kind & 0xFFFFu) == next_off;
-    else sum->last_node = (uint32_t)k;          // the stream's last candidate
-    if (!ok) sum->pad2 = 1;
-    sorted[k] = cd;
-    frame_off[k] = cd.off;
-    wav_off[k] = acc;
-    if ((acc & 3ull) && sum->unaligned == 0) sum->unaligned = 1;
-    if (acc + cd.samples > wav_cap) atomicMin(&sum->first_over, k);
-    if (k == 0ull) sum->start = 0u;
+    const X3Link l = x3i_link(cand_wg, count, base, sbase, b, n, i, G, 0ull, 0ull);
+    if (l.next == ~0ull) sum->last_node = (uint32_t)l.k;   // the stream's last candidate
+    if (!l.ok) sum->pad2 = 1;
+    sorted[l.k] = l.cd;
+    frame_off[l.k] = l.cd.off;
+    wav_off[l.k] = l.acc;
+    if ((l.acc & 3ull) && sum->unaligned == 0) sum->unaligned = 1;
+    if (l.acc + l.cd.samples > wav_cap) atomicMin(&sum->first_over, l.k);
+    if (l.k == 0ull) sum->start = 0u;
   }
 }

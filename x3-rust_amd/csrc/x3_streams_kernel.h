@@ -1,18 +1,16 @@
 // x3_streams_kernel.h -- the frame walk of MANY independent streams in one launch set (x3_decode_streams_dev,
 // include/x3hip.h "BATCHES OF STREAMS").
 //
-// The fast path of x3_index_kernels.h made segmented.  Every entry (a stream at any byte offset of one device buffer) is
-// cut into spans of X3T_SPAN_BYTES; a span belongs to exactly one entry, so its workgroup tests only that entry's byte
-// offsets and states its candidates RELATIVE to the entry's start, with the walk's length rules taken against the entry's
-// own length and phantom bytes.  One exclusive scan of the spans' counts and sample sums (x3_index_chain_kernel) numbers
-// every candidate of the batch; an entry's spans are consecutive, so its first candidate and its sample base are the
-// scans' values at its first span, and a difference gives everything relative to the entry.  The link kernel then checks,
-// per entry, that the candidates are one clean chain from offset 0, and writes the decoder's frame table: byte offsets
-// into the buffer and sample offsets entry * row_len + position.  A candidate the decoder must not see -- not a frame the
-// walk steps over, a frame that does not fit its row, a row offset off the four-sample grid the multi-wave decoders need
-// -- gets the offset x3_len: every decoder and the check pass give such a frame a status without reading or writing
-// anything.  Its entry is then not clean, and so is every entry whose chain breaks: the host walks those again with the
-// general walk when the result is asked for.
+// The fast path of x3_index_kernels.h over entries (streams at any byte offset of one device buffer): these kernels call its
+// helpers for every walk rule (x3i_load_chunk, x3i_scan_chunk, x3i_consider, x3i_store_span, x3i_link, x3i_walk_end) and
+// keep what is per entry.  Each entry is cut into spans of X3T_SPAN_BYTES, a workgroup's each, whose candidates carry
+// offsets RELATIVE to the entry and the walk's kind against the entry's own length and phantom bytes.  One exclusive scan
+// over all spans (x3_index_chain_kernel) numbers every candidate; an entry's spans are consecutive, so its first candidate
+// and sample base are the scans at its first span.  The link kernel checks each entry's chain and writes the decoder's frame
+// table (buffer offsets, sample offsets entry * row_len + position).  A candidate the decoder must not see -- not a frame
+// the walk steps over, past its row, off the four-sample grid of the multi-wave decoders -- gets the offset x3_len, which
+// every decoder and the check pass give a status without reading or writing; its entry, like one whose chain breaks, is
+// left to the general walk at result time.
 #pragma once
 #include "x3_index_kernels.h"
 
@@ -38,88 +36,34 @@ __device__ __forceinline__ uint32_t x3t_entry_of(const uint32_t* __restrict__ sp
   return lo;
 }
 
-// 1. candidates of one span (x3_index_candidates_kernel<true>, segmented): count[b], samp[b] and the span's candidates in
-// offset order at cand[b * X3I_WG_CANDS ...], offsets relative to the entry
+// 1. candidates of one span (x3_index_candidates_kernel<true>'s scan, over the span's chunks): count[b], samp[b] and the
+// span's candidates in offset order at cand[b * X3I_WG_CANDS ...], offsets relative to the entry
 __global__ void __launch_bounds__(256)
 x3_streams_candidates_kernel(const uint32_t* __restrict__ xw, uint64_t x3_len, const uint64_t* __restrict__ eoff,
                              const uint64_t* __restrict__ elen, const uint32_t* __restrict__ span_first, uint32_t n,
                              uint64_t phantom, X3Cand* __restrict__ cand, unsigned int* __restrict__ count,
                              unsigned long long* __restrict__ samp, uint32_t* __restrict__ ent_flags) {
-  __shared__ X3Cand s_c[X3I_WG_CANDS];
-  __shared__ uint32_t s_n, s_nraw;
-  __shared__ unsigned long long s_raw[X3I_WG_RAW];
-  if (threadIdx.x == 0) { s_n = 0; s_nraw = 0; }
+  __shared__ X3ScanLds s;
+  if (threadIdx.x == 0) { s.n = 0; s.nraw = 0; }
   __syncthreads();
   const uint32_t b = blockIdx.x;
   const uint32_t e = x3t_entry_of(span_first, n, b);
   const uint64_t a = eoff[e], L = elen[e];
   const uint64_t lo = a + (uint64_t)(b - span_first[e]) * X3T_SPAN_BYTES;
   const uint64_t hi = lo + X3T_SPAN_BYTES < a + L ? lo + X3T_SPAN_BYTES : a + L;   // header offsets [lo, hi) of this span
+  const uint64_t end = hi + 19 < a + L ? hi + 19 : a + L;                          // ... whose 20 bytes lie in the entry
   const uint64_t n_dw = (x3_len + 3) >> 2;
   auto consider = [&](uint64_t off) {
-    uint32_t plen, samples;
-    if (x3i_read_header(xw, n_dw, off, plen, samples) != X3D_OK) return;
     X3Cand cd;
-    cd.off = off - a;
-    cd.plen_kind = plen | (x3i_kind(L, L + phantom, off - a, plen, samples, 0u) << 16);
-    cd.samples = samples;
-    const uint32_t li = atomicAdd(&s_n, 1u);
-    if (li < X3I_WG_CANDS) s_c[li] = cd;
+    x3i_consider(s, xw, n_dw, off, a, L, L + phantom, 0u, cd);
   };
   for (uint64_t t = (lo >> 4) + threadIdx.x; 16 * t < hi; t += blockDim.x) {
     uint32_t w[5];
-    if (4 * t + 4 < n_dw) {
-      const uint4 v = reinterpret_cast<const uint4*>(xw)[t];
-      w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-      w[4] = xw[4 * t + 4];
-    } else {
-#pragma unroll
-      for (int d = 0; d < 5; ++d) w[d] = 4 * t + d < n_dw ? xw[4 * t + d] : 0u;
-    }
-    // the key 0x78 0x33 at any of the sixteen byte offsets? (x3_index_candidates_kernel's filter)
-    uint32_t hit = 0;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-      const uint32_t ev = w[d] ^ 0x33783378u;
-      const uint32_t o = __builtin_amdgcn_alignbit(w[d + 1], w[d], 8) ^ 0x33783378u;
-      hit |= ((ev - 0x00010001u) & ~ev) | ((o - 0x00010001u) & ~o);
-    }
-    if ((hit & 0x80008000u) == 0) continue;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-      const uint32_t lw = w[k >> 2] >> (8 * (k & 3));
-      const uint32_t hw = ((k & 3) == 3 ? (lw & 0xFFu) | ((w[(k >> 2) + 1] & 0xFFu) << 8) : lw) & 0xFFFFu;
-      if (hw != 0x3378u) continue;
-      const uint64_t off = 16 * t + k;
-      if (off < lo || off >= hi || off + 20 > a + L) continue;   // (the entry's bytes only)
-      const uint32_t ri = atomicAdd(&s_nraw, 1u);
-      if (ri < X3I_WG_RAW) { s_raw[ri] = off; continue; }
-      consider(off);
-    }
+    x3i_load_chunk(xw, n_dw, t, w);
+    x3i_scan_chunk(w, t, lo, end, s, consider);
   }
-  __syncthreads();
-  {
-    const uint32_t nraw = s_nraw < X3I_WG_RAW ? s_nraw : X3I_WG_RAW;
-    for (uint32_t i = threadIdx.x; i < nraw; i += blockDim.x) consider(s_raw[i]);
-  }
-  __syncthreads();
-  const uint32_t mine = s_n < X3I_WG_CANDS ? s_n : X3I_WG_CANDS;
-  if (threadIdx.x == 0) {
-    if (s_n > X3I_WG_CANDS) atomicOr(&ent_flags[e], X3T_DIRTY);
-    count[b] = mine;
-  }
-  X3Cand* const dst = cand + (size_t)b * X3I_WG_CANDS;
-  for (uint32_t i = threadIdx.x; i < mine; i += blockDim.x) {
-    const X3Cand me = s_c[i];
-    uint32_t rank = 0;
-    for (uint32_t j = 0; j < mine; ++j) rank += s_c[j].off < me.off ? 1u : 0u;
-    dst[rank] = me;
-  }
-  if (threadIdx.x == 0) {
-    unsigned long long tot = 0;
-    for (uint32_t j = 0; j < mine; ++j) tot += s_c[j].samples;
-    samp[b] = tot;
-  }
+  x3i_check_raw(s, consider);
+  x3i_store_span(s, b, cand, count, samp, &ent_flags[e], X3T_DIRTY);
 }
 
 // 2. (x3_index_chain_kernel: exclusive scans of count and samp over all spans)
@@ -129,7 +73,7 @@ x3_streams_candidates_kernel(const uint32_t* __restrict__ xw, uint64_t x3_len, c
 // the entry's sample count behind it.  x4: the decode launch needs row offsets that are multiples of four samples.
 __global__ void __launch_bounds__(64)
 x3_streams_link_kernel(const X3Cand* __restrict__ cand_wg, const unsigned int* __restrict__ count,
-                       const uint32_t* __restrict__ base, const unsigned long long* __restrict__ sbase, uint32_t G,
+                       const uint32_t* __restrict__ base, const unsigned long long* __restrict__ sbase,
                        const uint64_t* __restrict__ eoff, const uint32_t* __restrict__ span_first, uint32_t n,
                        uint64_t x3_len, uint64_t row_len, uint32_t x4, unsigned long long* __restrict__ frame_off,
                        unsigned long long* __restrict__ wav_off, uint32_t* __restrict__ fent,
@@ -140,36 +84,21 @@ x3_streams_link_kernel(const X3Cand* __restrict__ cand_wg, const unsigned int* _
   if (cnt == 0) return;
   const uint32_t e = x3t_entry_of(span_first, n, b);
   const uint32_t fs = span_first[e], fe = span_first[e + 1];
-  const unsigned long long k0 = base[fs];
-  const X3Cand* const mine = cand_wg + (size_t)b * X3I_WG_CANDS;
+  const unsigned long long k0 = base[fs], s0 = sbase[fs];   // the entry's first candidate and sample base
   bool dirty = false;
   for (uint32_t i = threadIdx.x; i < cnt; i += blockDim.x) {
-    const X3Cand cd = mine[i];
-    const unsigned long long k = (unsigned long long)base[b] + i;
-    unsigned long long acc = sbase[b] - sbase[fs];
-    for (uint32_t j = 0; j < i; ++j) acc += mine[j].samples;
-    const unsigned long long end = cd.off + 20ull + (cd.plen_kind & 0xFFFFu);
-    bool ok = (cd.plen_kind >> 16) == X3I_CONT;
-    if (k == k0) ok = ok && cd.off == 0ull;
-    unsigned long long next_off = ~0ull;
-    if (i + 1u < cnt) {
-      next_off = mine[i + 1u].off;
-    } else {
-      for (uint32_t b2 = b + 1u; b2 < fe && b2 < G; ++b2)
-        if (count[b2]) { next_off = cand_wg[(size_t)b2 * X3I_WG_CANDS].off; break; }
-    }
-    if (next_off != ~0ull) {
-      ok = ok && end == next_off;
-    } else {
-      ent_end[e] = end;
-      ent_nsamp[e] = acc + cd.samples;
+    const X3Link l = x3i_link(cand_wg, count, base, sbase, b, cnt, i, fe, k0, s0);
+    if (l.next == ~0ull) {   // the entry's last candidate
+      ent_end[e] = l.end;
+      ent_nsamp[e] = l.acc + l.cd.samples;
     }
     // what the decoder may see: a frame the walk steps over, inside its row, on the grid the launch needs
-    const bool live = (cd.plen_kind >> 16) == X3I_CONT && acc + cd.samples <= row_len && (!x4 || (acc & 3ull) == 0ull);
-    dirty = dirty || !ok || !live;
-    frame_off[k] = live ? eoff[e] + cd.off : x3_len;
-    wav_off[k] = live ? (unsigned long long)e * row_len + acc : 0ull;
-    fent[k] = e;
+    const bool live = (l.cd.plen_kind >> 16) == X3I_CONT && l.acc + l.cd.samples <= row_len &&
+                      (!x4 || (l.acc & 3ull) == 0ull);
+    dirty = dirty || !l.ok || !live;
+    frame_off[l.k] = live ? eoff[e] + l.cd.off : x3_len;
+    wav_off[l.k] = live ? (unsigned long long)e * row_len + l.acc : 0ull;
+    fent[l.k] = e;
   }
   if (dirty) atomicOr(&ent_flags[e], X3T_DIRTY);
 }
@@ -224,25 +153,11 @@ x3_streams_resolve_kernel(const uint32_t* __restrict__ xw, uint64_t x3_len, cons
       r.status = st;
     }
   } else {
-    // every frame good: how the walk ends behind the last one (x3_index_finalize_kernel's ending_at, per entry)
-    const uint64_t L = elen[e], believed = L + phantom, pos = m ? ent_end[e] : 0ull;
-    int st = X3D_OK;
-    if (believed - pos <= 20) {
-      st = X3D_OK;
-    } else if (L - pos < 20) {
-      st = X3D_IO;
-    } else {
-      uint32_t plen, samples;
-      st = x3i_read_header(xw, (x3_len + 3) >> 2, eoff[e] + pos, plen, samples);
-      if (st == X3D_OK) {   // (a valid header would be a candidate of the chain; the kinds that end the walk)
-        const uint32_t kind = x3i_kind(L, believed, pos, plen, samples, 0u);
-        st = kind == X3I_QUIET ? X3D_OK : kind == X3I_IO ? X3D_IO
-             : kind == X3I_PLEN ? X3D_FRAME_HEADER_INVALID_PAYLOAD_LEN : X3D_BAD_ARG;
-      }
-    }
+    // every frame good: how the walk ends behind the last one
+    const uint64_t L = elen[e];
     r.frames_ok = m;
     r.n_out = m ? ent_nsamp[e] : 0ull;
-    r.status = st;
+    r.status = x3i_walk_end(xw, (x3_len + 3) >> 2, eoff[e], L, L + phantom, m ? ent_end[e] : 0ull, 0u);
   }
   results[e] = r;
   nout[e] = r.n_out;
