@@ -159,6 +159,8 @@ const char* x3_last_error(const x3_ctx* ctx);
  * their first buffer held and scanned the stream a second time).
  * x3_decode_streams_dev: read-only "streams_general_walks" (entries so far that the segmented fast walk left to the
  * general walk) and "last_streams_general_walks" (of the last x3_decode_streams_result).
+ * x3_corpus_build: read-only "last_corpus_record_slices" (slices of frames the last build recorded its segment index in;
+ * 0 without an index).
  * Unknown name: X3_ERR_BAD_ARG. */
 int x3_ctx_set_option(x3_ctx* ctx, const char* name, long long value);
 int x3_ctx_get_option(const x3_ctx* ctx, const char* name, long long* value);
@@ -615,6 +617,52 @@ int x3_decode_streams_dev(x3_ctx* ctx, const uint8_t* d_x3, uint64_t x3_len, con
 /* Waits for the last x3_decode_streams_dev, walks the entries the fast walk left alone: entries with status != 0, the
  * first of them (n_streams if none) and its status. */
 int x3_decode_streams_result(x3_ctx* ctx, uint64_t* n_bad, uint64_t* first_bad, int* first_bad_status);
+
+/* ---- CORPUS: windows of many streams (no counterpart in the reference).  An index built once over the entries of one
+ * device buffer (as in x3_decode_streams_dev: any byte offset, overlaps and repeats, one x3_params), after which a window is
+ * addressed as (entry, start).  Take entry e alone, its bytes in a buffer of their own: its frames are those x3_index_dev
+ * finds (X3_STREAMS_ARCHIVE_FRAMES: those of x3_x3a_decode's walk, which believes in 8 bytes more), its sample offsets
+ * those of x3_sample_offsets_dev.  Window (e, s) of x3_corpus_windows_dev is then exactly what x3_decode_windows_dev with
+ * start s returns on that entry: the same row, the same status, zeros behind the first failing covering frame.  The
+ * segment index is a hint: it changes time, never results.  One exception, for bytes changed after
+ * the build: a frame is bounded by d_x3's x3_len, not by its entry's end, so a header rewritten with a valid header CRC
+ * and a payload that now runs past its entry gives the status of that payload's check where the entry alone gives
+ * X3_ERR_BAD_ARG (every read still stays inside [d_x3, d_x3 + x3_len)). */
+typedef struct x3_corpus x3_corpus;
+typedef struct x3_corpus_entry {
+  uint64_t n_samples;    /* positions of the entry: x3_sample_offsets_dev's total over its frames */
+  uint64_t first_frame;  /* its frames are [first_frame, first_frame + n_frames) of the corpus's frame table */
+  uint64_t n_frames;
+  int32_t walk_status;   /* how its walk ended behind those frames (x3_index_dev's *terminal) */
+  uint32_t general_walk; /* 1: the fast walk could not vouch for it; the general walk found its frames */
+} x3_corpus_entry;
+/* Synchronous.  offsets / lengths: HOST arrays into d_x3.  flags: 0 or X3_STREAMS_ARCHIVE_FRAMES.  seg_blocks: 0 = no
+ * segment index, else as x3_decode_dev_seg accepts it; it is recorded by one decode of the corpus where the parameters
+ * route to a decoder that records (block length 20, the default codes), and kept nowhere else (seg_blocks_in_use 0).
+ * d_x3 is referenced, not copied: it must outlive the corpus.  The build ends the pending state of an earlier
+ * x3_decode_dev, as x3_decode_stream_dev does.  X3_ERR_BAD_ARG, with nothing left allocated, for n_entries == 0 or above
+ * 0xFFFFFFF0, an entry outside [0, x3_len), an unknown flag, d_x3 not on a 4-byte boundary, parameters that
+ * x3_params_validate or x3_decode_windows_dev refuses, a seg_blocks that x3_decode_dev_seg refuses, and more than
+ * 0x7FFFFFFF frames in all. */
+int x3_corpus_build(x3_ctx* ctx, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* offsets, const uint64_t* lengths,
+                    uint64_t n_entries, uint32_t flags, const x3_params* p, uint32_t seg_blocks, x3_corpus** corpus);
+int x3_corpus_info(const x3_corpus* corpus, uint64_t* n_entries, uint64_t* n_frames, uint64_t* total_samples,
+                   uint32_t* seg_blocks_in_use);
+/* the entry table (host array of n_entries) */
+int x3_corpus_entries(const x3_corpus* corpus, x3_corpus_entry* out);
+/* The segment index the build recorded (device memory the corpus owns; layout as x3_decode_dev_seg's, over the corpus's frame
+ * table): *d_seg_index and *n_words, or NULL and 0 without one. */
+int x3_corpus_seg_index(const x3_corpus* corpus, const uint64_t** d_seg_index, uint64_t* n_words);
+/* Window w = samples [d_starts[w], d_starts[w] + window_len) of entry d_entries[w] (device arrays: uint32 / uint64).  Rows,
+ * formats, d_status and x3_decode_windows_result as for x3_decode_windows_dev; a window whose entry is not in the corpus,
+ * or that runs past its entry's n_samples (it never runs into the next entry), is X3_ERR_BAD_ARG and zeros.  Asynchronous,
+ * one launch set, no host trip; leaves a pending x3_decode_dev alone.  Nothing is trusted -- tables, entries, starts, bytes
+ * changed after the build: they can give a status or a slower path, never a read outside [d_x3, d_x3 + x3_len) or a
+ * write outside d_out / d_status.  X3_ERR_BAD_ARG with nothing enqueued for the arguments x3_decode_windows_dev refuses,
+ * d_entries not on a 4-byte boundary, and a context on another device than the build's. */
+int x3_corpus_windows_dev(x3_ctx* ctx, const x3_corpus* corpus, const uint32_t* d_entries, const uint64_t* d_starts,
+                          uint64_t n_windows, uint32_t window_len, void* d_out, int out_format, int32_t* d_status);
+void x3_corpus_destroy(x3_corpus* corpus);
 
 /* ------------------------------------------------------------------ multi-GPU (no reference analogue) */
 

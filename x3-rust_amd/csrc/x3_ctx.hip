@@ -454,6 +454,7 @@ extern "C" int x3_ctx_get_option(const x3_ctx* c, const char* name, long long* v
   else if (n == "last_dense_frames") *value = (long long)c->last_dense_frames;      // read-only: of the last call (after x3_encode_result)
   else if (n == "last_decode_replays") *value = (long long)c->last_decode_replays;   // read-only: frames of the last decode the reference's reader re-decoded
   else if (n == "last_window_replays") *value = (long long)c->last_window_replays;   // read-only: (window, frame) pairs of the last x3_decode_windows_dev re-decoded
+  else if (n == "last_corpus_record_slices") *value = (long long)c->last_corpus_slices;   // read-only: slices the last x3_corpus_build recorded its index in
   else if (n == "enc_gen_in_use") *value = c->last_enc_gen;                          // read-only: 3 = wave encoder, 2 = second generation, 1 = the general kernel in one pass (look-back), 0 = two passes
   else if (n == "host_walk") *value = c->opt.host_walk;
   else if (n == "host_chunk_frames") *value = c->opt.host_chunk_frames;

@@ -1030,39 +1030,36 @@ extern "C" int x3_sample_offsets_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3
   return X3_OK;
 }
 
-extern "C" int x3_decode_windows_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
-                                     const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
-                                     const uint64_t* d_seg_index, uint32_t seg_blocks, const uint64_t* d_starts,
-                                     uint64_t n_windows, uint32_t window_len, void* d_out, int out_format, int32_t* d_status) {
-  if (!c || !d_x3 || !d_frame_offsets || !d_sample_offsets || !p || !d_starts || !d_out || !d_status) return X3_ERR_BAD_ARG;
-  if (window_len == 0 || n_windows == 0 || n_windows > (1ull << 40)) return X3_ERR_BAD_ARG;
-  if (out_format != X3_WINDOW_I16 && out_format != X3_WINDOW_F32) return X3_ERR_BAD_ARG;
+// the argument checks x3_decode_windows_dev and x3_corpus_windows_dev share
+static bool windows_args_ok(uint64_t n_windows, uint32_t window_len, const void* d_out, int out_format, const uint64_t* d_starts,
+                            const int32_t* d_status) {
+  if (!d_starts || !d_out || !d_status) return false;
+  if (window_len == 0 || n_windows == 0 || n_windows > (1ull << 40)) return false;
+  if (out_format != X3_WINDOW_I16 && out_format != X3_WINDOW_F32) return false;
   const uint64_t esz = out_format == X3_WINDOW_F32 ? 4u : 2u;
-  if (reinterpret_cast<uintptr_t>(d_out) % esz) return X3_ERR_BAD_ARG;
-  if ((reinterpret_cast<uintptr_t>(d_x3) & 3u) || (reinterpret_cast<uintptr_t>(d_frame_offsets) & 7u) ||
-      (reinterpret_cast<uintptr_t>(d_sample_offsets) & 7u) || (reinterpret_cast<uintptr_t>(d_starts) & 7u) ||
-      (reinterpret_cast<uintptr_t>(d_status) & 3u))
-    return X3_ERR_BAD_ARG;
-  if (d_seg_index && (seg_blocks == 0 || (seg_blocks & 3u) || seg_blocks > 3200u || (reinterpret_cast<uintptr_t>(d_seg_index) & 7u)))
-    return X3_ERR_BAD_ARG;
-  if (n_frames == 0 || n_frames > 0x7FFFFFFFull) return X3_ERR_BAD_ARG;
-  X3DevParams dp;
-  const uint64_t spf = spf_of(p);
-  int rc = derive(p, spf > 0xFFFFFFFFull ? 0 : spf, &dp);
-  if (rc) return rc;
-  if (dp.block_len == 0 || dp.blocks_per_frame == 0) return X3_ERR_BAD_ARG;
-  HIPCHK(c, hipSetDevice(c->device));
+  if (reinterpret_cast<uintptr_t>(d_out) % esz) return false;
+  return (reinterpret_cast<uintptr_t>(d_starts) & 7u) == 0 && (reinterpret_cast<uintptr_t>(d_status) & 3u) == 0;
+}
+
+// The launch set of a windows call (x3_decode_window_kernel.h) behind its plan step: plan(grid, plan, gstart, sum) enqueues
+// the plan kernel and returns the starts the decode and fix-up kernels read (the caller's, or the plan's gstart).
+template <class Plan>
+static int windows_launch(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
+                          const uint64_t* d_sample_offsets, uint64_t n_frames, const X3DevParams& dp, uint64_t spf,
+                          const uint64_t* d_seg_index, uint32_t seg_blocks, uint64_t n_windows, uint32_t window_len,
+                          void* d_out, int out_format, int32_t* d_status, Plan plan_step) {
   // the stretches of a frame as the index tells them apart (x3_seg_index_entries); 1 = whole frames
   const uint64_t nidx = d_seg_index ? ((uint64_t)dp.blocks_per_frame + seg_blocks - 1) / seg_blocks : 1;
   const uint32_t nseg = nidx >= 2 ? (uint32_t)nidx : 1u;
   const uint2* idx = nseg >= 2 ? reinterpret_cast<const uint2*>(d_seg_index) : nullptr;
-  // workspace: plans, the two scans, per-frame verdicts, a block of replay scratch per window, the summary
+  // workspace: plans, the two scans, per-frame verdicts, a block of replay scratch per window, the summary, the plan's starts
   const uint64_t n = n_windows;
   const uint32_t scratch_per = (dp.block_len + 7u) & ~7u;
   auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
   const size_t o_plan = 0, o_cov = up(o_plan + n * sizeof(X3WinPlan)), o_item = up(o_cov + (n + 1) * 8),
                o_fst = up(o_item + (n + 1) * 8), o_scr = up(o_fst + n_frames * 4), o_sum = up(o_scr + n * scratch_per * 2),
-               total = o_sum + sizeof(X3WinSummary);
+               o_gs = up(o_sum + sizeof(X3WinSummary)), total = o_gs + n * 8;
+  int rc;
   if ((rc = ensure(c, c->win_ws, total))) return rc;
   char* const ws = (char*)c->win_ws.p;
   X3WinPlan* plan = (X3WinPlan*)(ws + o_plan);
@@ -1077,8 +1074,7 @@ extern "C" int x3_decode_windows_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3
   auto groups = [&](uint64_t units, uint64_t per_group) {
     return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((units + per_group - 1) / per_group, X3W_GRID_LIMIT));
   };
-  hipLaunchKernelGGL(x3_window_plan_kernel, dim3(groups(n, 256)), dim3(256), 0, c->stream, d_sample_offsets, n_frames,
-                     d_starts, n, window_len, plan, sum);
+  const uint64_t* d_starts = plan_step(dim3(groups(n, 256)), plan, (uint64_t*)(ws + o_gs), sum);
   hipLaunchKernelGGL(x3_window_scan_kernel, dim3(1), dim3(1024), 0, c->stream, plan, n, idx, seg_blocks, nseg, cov_off, item_off);
   hipLaunchKernelGGL(x3_window_check_kernel, dim3(groups(n * frames_per, 4)), dim3(256), 0, c->stream, d_x3, x3_len,
                      d_frame_offsets, d_sample_offsets, plan, n, cov_off, fst);
@@ -1093,6 +1089,33 @@ extern "C" int x3_decode_windows_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3
   c->win_windows = n;
   c->win_sum_off = o_sum;
   return X3_OK;
+}
+
+extern "C" int x3_decode_windows_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
+                                     const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
+                                     const uint64_t* d_seg_index, uint32_t seg_blocks, const uint64_t* d_starts,
+                                     uint64_t n_windows, uint32_t window_len, void* d_out, int out_format, int32_t* d_status) {
+  if (!c || !d_x3 || !d_frame_offsets || !d_sample_offsets || !p) return X3_ERR_BAD_ARG;
+  if (!windows_args_ok(n_windows, window_len, d_out, out_format, d_starts, d_status)) return X3_ERR_BAD_ARG;
+  if ((reinterpret_cast<uintptr_t>(d_x3) & 3u) || (reinterpret_cast<uintptr_t>(d_frame_offsets) & 7u) ||
+      (reinterpret_cast<uintptr_t>(d_sample_offsets) & 7u))
+    return X3_ERR_BAD_ARG;
+  if (d_seg_index && (seg_blocks == 0 || (seg_blocks & 3u) || seg_blocks > 3200u || (reinterpret_cast<uintptr_t>(d_seg_index) & 7u)))
+    return X3_ERR_BAD_ARG;
+  if (n_frames == 0 || n_frames > 0x7FFFFFFFull) return X3_ERR_BAD_ARG;
+  X3DevParams dp;
+  const uint64_t spf = spf_of(p);
+  int rc = derive(p, spf > 0xFFFFFFFFull ? 0 : spf, &dp);
+  if (rc) return rc;
+  if (dp.block_len == 0 || dp.blocks_per_frame == 0) return X3_ERR_BAD_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  return windows_launch(c, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, dp, spf, d_seg_index, seg_blocks, n_windows,
+                        window_len, d_out, out_format, d_status,
+                        [&](dim3 grid, X3WinPlan* plan, uint64_t*, X3WinSummary* sum) -> const uint64_t* {
+                          hipLaunchKernelGGL(x3_window_plan_kernel, grid, dim3(256), 0, c->stream, d_sample_offsets, n_frames,
+                                             d_starts, n_windows, window_len, plan, sum);
+                          return d_starts;
+                        });
 }
 
 extern "C" int x3_decode_windows_result(x3_ctx* c, uint64_t* n_bad, uint64_t* first_bad, int* first_bad_status) {
@@ -1392,4 +1415,308 @@ extern "C" int x3_decode_streams_result(x3_ctx* c, uint64_t* n_bad, uint64_t* fi
   if (first_bad) *first_bad = fb;
   if (first_bad_status) *first_bad_status = fst;
   return X3_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// CORPUS: windows of many streams (include/x3hip.h)
+// ------------------------------------------------------------------------------------------------
+struct x3_corpus {
+  int device = 0;
+  const uint8_t* d_x3 = nullptr;
+  uint64_t x3_len = 0, n = 0, F = 0, total = 0;
+  x3_params p{};
+  uint32_t seg_blocks = 0;             // in use (0: no index)
+  uint64_t* d_frame_off = nullptr;     // F words (at least one): the frames' byte offsets in d_x3, entries in order
+  uint64_t* d_so = nullptr;            // F + 1 words: x3_window_sample_offsets_kernel over that table
+  x3_corpus_entry* d_ent = nullptr;    // n entries
+  uint64_t* d_index = nullptr;         // the segment index (1 + F * (nseg - 1) words), or nullptr
+  std::vector<x3_corpus_entry> ent;    // the entry table's host copy
+};
+
+extern "C" void x3_corpus_destroy(x3_corpus* k) {
+  if (!k) return;
+  int dev = -1;
+  (void)hipGetDevice(&dev);
+  (void)hipSetDevice(k->device);
+  for (void* q : {(void*)k->d_frame_off, (void*)k->d_so, (void*)k->d_ent, (void*)k->d_index})
+    if (q) (void)hipFree(q);
+  if (dev >= 0) (void)hipSetDevice(dev);
+  delete k;
+}
+
+// The build's device scratch, freed on every way out.
+struct CorpusScratch {
+  std::vector<void*> bufs;
+  ~CorpusScratch() { for (void* q : bufs) (void)hipFree(q); }
+  template <class T> int get(x3_ctx* c, T** out, uint64_t count) {
+    void* q = nullptr;
+    HIPCHK(c, hipMalloc(&q, std::max<uint64_t>(count * sizeof(T), 64)));
+    bufs.push_back(q);
+    *out = (T*)q;
+    return X3_OK;
+  }
+};
+
+// The entries the segmented walk left alone, by x3_index_dev's own path (its phantom bytes with the archive flag) on an
+// aligned copy of each: frames (buffer offsets), count and how the walk ends.
+static int corpus_general_walk(x3_ctx* c, const uint8_t* d_x3, uint64_t off, uint64_t len, uint64_t phantom,
+                               std::vector<uint64_t>* frames, int* terminal) {
+  int rc;
+  if ((rc = ensure(c, c->st_one, len + 64))) return rc;
+  if (len) HIPCHK(c, hipMemcpyAsync(c->st_one.p, d_x3 + off, len, hipMemcpyDeviceToDevice, c->stream));
+  const uint64_t max_frames = len / 22 + 1;
+  uint64_t cap = std::min<uint64_t>(max_frames, 1u << 20);
+  X3IndexSummary r;
+  for (;;) {
+    if ((rc = ensure(c, c->frame_off, (cap + 1) * sizeof(uint64_t)))) return rc;
+    if ((rc = ensure(c, c->wav_off, cap * sizeof(uint64_t)))) return rc;
+    rc = index_dev_impl(c, (const uint8_t*)c->st_one.p, len, phantom, 0u, ~0ull, cap, (uint64_t*)c->frame_off.p,
+                        (uint64_t*)c->wav_off.p, &r);
+    if (rc == X3_ERR_BAD_ARG && cap < max_frames) { cap = max_frames; continue; }
+    break;
+  }
+  if (rc) return rc;
+  frames->resize(r.n_frames);
+  if (r.n_frames) {
+    HIPCHK(c, hipMemcpy(frames->data(), c->frame_off.p, 8 * r.n_frames, hipMemcpyDeviceToHost));
+    for (auto& f : *frames) f += off;
+  }
+  *terminal = r.terminal;
+  return X3_OK;
+}
+
+// the recording decode: slices of frames into a scratch layout of its own (a frame's samples at a multiple of four), each
+// slice's index slots copied into place -- what one recording call over the whole table leaves
+#define X3K_RECORD_SCRATCH (256ull << 20)   // bytes of samples one slice decodes into
+static int corpus_record(x3_ctx* c, x3_corpus* k, const X3DevParams& dp, uint32_t seg_blocks, CorpusScratch& tmp) {
+  const uint64_t F = k->F;
+  const uint64_t nidx = ((uint64_t)dp.blocks_per_frame + seg_blocks - 1) / seg_blocks;
+  const uint64_t pitch = ((uint64_t)dp.spf + 3) & ~3ull;
+  const uint64_t S = std::min<uint64_t>(F, std::max<uint64_t>(X3K_RECORD_SCRATCH / 2 / pitch, 1));
+  int rc;
+  int16_t* wav;
+  uint64_t *woff, *sidx;
+  if ((rc = tmp.get(c, &wav, S * pitch))) return rc;
+  if ((rc = tmp.get(c, &woff, S))) return rc;
+  if ((rc = tmp.get(c, &sidx, 1 + S * (nidx - 1)))) return rc;
+  std::vector<uint64_t> h(S);
+  for (uint64_t i = 0; i < S; ++i) h[i] = i * pitch;
+  HIPCHK(c, hipMemcpy(woff, h.data(), 8 * S, hipMemcpyHostToDevice));
+  if ((rc = ensure(c, c->dec_status, S * sizeof(int32_t)))) return rc;
+  const X3SegSpec seg{sidx, seg_blocks, 2};
+  c->last_corpus_slices = 0;
+  for (uint64_t f0 = 0; f0 < F; f0 += S) {
+    ++c->last_corpus_slices;
+    const uint64_t m = std::min<uint64_t>(S, F - f0);
+    x3_params pp = k->p;
+    if ((rc = decode_dev_impl(c, k->d_x3, k->x3_len, k->d_frame_off + f0, m, nullptr, woff, &pp, wav, m * pitch,
+                              (int32_t*)c->dec_status.p, true, false, &seg)))
+      return rc;
+    if (f0 == 0) HIPCHK(c, hipMemcpyAsync(k->d_index, sidx, 8, hipMemcpyDeviceToDevice, c->stream));   // (the header word)
+    HIPCHK(c, hipMemcpyAsync(k->d_index + 1 + f0 * (nidx - 1), sidx + 1, 8 * m * (nidx - 1), hipMemcpyDeviceToDevice, c->stream));
+  }
+  c->decode_pending = false;   // (the recording's summary is no call's result)
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return X3_OK;
+}
+
+static int corpus_build_impl(x3_ctx* c, x3_corpus* k, const uint64_t* offsets, const uint64_t* lengths, uint64_t phantom,
+                             uint32_t seg_blocks) {
+  const uint64_t n = k->n;
+  int rc;
+  X3DevParams dp;
+  if ((rc = derive(&k->p, spf_of(&k->p), &dp))) return rc;
+  CorpusScratch tmp;
+  std::vector<uint32_t> span_first(n + 1, 0);
+  for (uint64_t e = 0; e < n; ++e) span_first[e + 1] = span_first[e] + (uint32_t)((lengths[e] + X3T_SPAN_BYTES - 1) / X3T_SPAN_BYTES);
+  const uint64_t G = span_first[n];
+  // ---- 1. every entry's frames: the segmented fast walk (x3_streams_kernel.h), all entries at once
+  std::vector<unsigned long long> m(n, ~0ull);
+  std::vector<int32_t> st(n, 0);
+  const bool fast = G && !c->opt.index_no_fast;
+  uint64_t *eoff = nullptr, *elen = nullptr;
+  uint32_t *sf = nullptr, *cnt = nullptr, *base = nullptr, *fent = nullptr, *ent_flags = nullptr;
+  unsigned long long *samp = nullptr, *sbase = nullptr, *frame_off = nullptr, *wav_off = nullptr, *ent_end = nullptr,
+                     *ent_nsamp = nullptr, *ent_k0 = nullptr, *ent_m = nullptr;
+  int32_t* ent_st = nullptr;
+  X3IndexSummary* isum = nullptr;
+  X3Cand* cand = nullptr;
+  const uint64_t cap = std::max<uint64_t>(G * X3I_WG_CANDS, 1);
+  if ((rc = tmp.get(c, &eoff, n)) || (rc = tmp.get(c, &elen, n)) || (rc = tmp.get(c, &sf, n + 1)) ||
+      (rc = tmp.get(c, &isum, 1)) || (rc = tmp.get(c, &cnt, G)) || (rc = tmp.get(c, &base, G)) || (rc = tmp.get(c, &samp, G)) ||
+      (rc = tmp.get(c, &sbase, G)) || (rc = tmp.get(c, &ent_flags, n)) || (rc = tmp.get(c, &ent_end, n)) ||
+      (rc = tmp.get(c, &ent_nsamp, n)) || (rc = tmp.get(c, &ent_k0, n)) || (rc = tmp.get(c, &ent_m, n)) ||
+      (rc = tmp.get(c, &ent_st, n)))
+    return rc;
+  if (fast) {
+    if ((rc = tmp.get(c, &cand, cap)) || (rc = tmp.get(c, &frame_off, cap)) || (rc = tmp.get(c, &wav_off, cap)) ||
+        (rc = tmp.get(c, &fent, cap)))
+      return rc;
+    HIPCHK(c, hipMemcpyAsync(eoff, offsets, 8 * n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(elen, lengths, 8 * n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(sf, span_first.data(), 4 * (n + 1), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(isum, 0, sizeof(X3IndexSummary), c->stream));
+    HIPCHK(c, hipMemsetAsync(ent_flags, 0, 4 * n, c->stream));
+    const uint32_t* xw = reinterpret_cast<const uint32_t*>(k->d_x3);
+    hipLaunchKernelGGL(x3_streams_candidates_kernel, dim3((unsigned)G), dim3(256), 0, c->stream, xw, k->x3_len,
+                       (const uint64_t*)eoff, (const uint64_t*)elen, (const uint32_t*)sf, (uint32_t)n, phantom, cand, cnt, samp,
+                       ent_flags);
+    hipLaunchKernelGGL(x3_index_chain_kernel, dim3(1), dim3(1024), 0, c->stream, (const unsigned int*)cnt,
+                       (const unsigned long long*)samp, (uint32_t)G, base, sbase, isum);
+    // (the index form of the link step: row_len ~0 and no four-sample grid, so every frame the walk steps over is live)
+    hipLaunchKernelGGL(x3_streams_link_kernel, dim3((unsigned)G), dim3(64), 0, c->stream, (const X3Cand*)cand,
+                       (const unsigned int*)cnt, (const uint32_t*)base, (const unsigned long long*)sbase, (const uint64_t*)eoff,
+                       (const uint32_t*)sf, (uint32_t)n, k->x3_len, ~0ull, 0u, frame_off, wav_off, fent, ent_flags, ent_end,
+                       ent_nsamp);
+    hipLaunchKernelGGL(x3_corpus_walk_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, xw, k->x3_len,
+                       (const uint64_t*)eoff, (const uint64_t*)elen, (const uint32_t*)sf, (uint32_t)n, phantom,
+                       (const uint32_t*)base, (uint32_t)G, (const unsigned long long*)&isum->n_chain, (const uint32_t*)ent_flags,
+                       (const unsigned long long*)ent_end, ent_k0, ent_m, ent_st);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(m.data(), ent_m, 8 * n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(st.data(), ent_st, 4 * n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  // ---- the entries the fast walk could not vouch for (and, without it, every entry): the general walk, one by one
+  k->ent.assign(n, x3_corpus_entry{0, 0, 0, 0, 0});
+  std::vector<std::pair<uint64_t, std::vector<uint64_t>>> general;
+  uint64_t F = 0;
+  for (uint64_t e = 0; e < n; ++e) {
+    x3_corpus_entry& en = k->ent[e];
+    if (m[e] == ~0ull) {
+      std::vector<uint64_t> fr;
+      int term = 0;
+      if ((rc = corpus_general_walk(c, k->d_x3, offsets[e], lengths[e], phantom, &fr, &term))) return rc;
+      en.n_frames = fr.size();
+      en.walk_status = term;
+      en.general_walk = 1;
+      general.emplace_back(e, std::move(fr));
+    } else {
+      en.n_frames = m[e];
+      en.walk_status = st[e];
+    }
+    en.first_frame = F;
+    F += en.n_frames;
+  }
+  if (F > 0x7FFFFFFFull) {
+    c->last_error = "x3_corpus_build: more than 0x7FFFFFFF frames";
+    return X3_ERR_BAD_ARG;
+  }
+  k->F = F;
+  // ---- 2. one frame table, its sample offsets, the entries' sample counts
+  HIPCHK(c, hipMalloc(&k->d_frame_off, 8 * std::max<uint64_t>(F, 1)));
+  HIPCHK(c, hipMalloc(&k->d_so, 8 * (F + 1)));
+  HIPCHK(c, hipMalloc(&k->d_ent, sizeof(x3_corpus_entry) * n));
+  HIPCHK(c, hipMemcpyAsync(k->d_ent, k->ent.data(), sizeof(x3_corpus_entry) * n, hipMemcpyHostToDevice, c->stream));
+  if (fast && F)
+    hipLaunchKernelGGL(x3_corpus_compact_kernel, dim3((unsigned)std::min<uint64_t>((cap + 255) / 256, 4096)), dim3(256), 0,
+                       c->stream, (const unsigned long long*)frame_off, (const uint32_t*)fent, cap,
+                       (const unsigned long long*)&isum->n_chain, (const unsigned long long*)ent_k0,
+                       (const x3_corpus_entry*)k->d_ent, F, k->d_frame_off);
+  for (const auto& g : general)
+    if (!g.second.empty())
+      HIPCHK(c, hipMemcpyAsync(k->d_frame_off + k->ent[g.first].first_frame, g.second.data(), 8 * g.second.size(),
+                               hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(x3_window_sample_offsets_kernel, dim3(1), dim3(1024), 0, c->stream, k->d_x3, k->x3_len,
+                     (const uint64_t*)k->d_frame_off, F, k->d_so);
+  hipLaunchKernelGGL(x3_corpus_samples_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
+                     (const uint64_t*)k->d_so, F, k->d_ent, n);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(k->ent.data(), k->d_ent, sizeof(x3_corpus_entry) * n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&k->total, k->d_so + F, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  // ---- 3. the segment index, where the parameters route to the decoder that records it
+  if (seg_blocks && F) {
+    const uint64_t nidx = ((uint64_t)dp.blocks_per_frame + seg_blocks - 1) / seg_blocks;
+    const bool records = nidx >= 2 &&
+                         decode_route(dp, X3Geom{0, 0, 1, F}, (const int16_t*)nullptr, true, true, 2, c->opt).kernel == X3_DEC_SPLIT;
+    if (records) {
+      HIPCHK(c, hipMalloc(&k->d_index, 8 * (1 + F * (nidx - 1))));
+      if ((rc = corpus_record(c, k, dp, seg_blocks, tmp))) return rc;
+      k->seg_blocks = seg_blocks;
+    }
+  }
+  return X3_OK;
+}
+
+extern "C" int x3_corpus_build(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* offsets, const uint64_t* lengths,
+                               uint64_t n, uint32_t flags, const x3_params* p, uint32_t seg_blocks, x3_corpus** out) {
+  if (out) *out = nullptr;
+  if (!c || !offsets || !lengths || !p || !out || (!d_x3 && x3_len)) return X3_ERR_BAD_ARG;
+  if (n == 0 || n > 0xFFFFFFF0ull || (flags & ~X3_STREAMS_ARCHIVE_FRAMES)) return X3_ERR_BAD_ARG;
+  if (reinterpret_cast<uintptr_t>(d_x3) & 3u) return X3_ERR_BAD_ARG;
+  if (x3_params_validate(p) != X3_OK) return X3_ERR_BAD_ARG;
+  if (p->block_len == 0 || p->blocks_per_frame == 0 || spf_of(p) > 0xFFFFFFFFull) return X3_ERR_BAD_ARG;   // (windows refuse them)
+  if (seg_blocks && ((seg_blocks & 3u) || seg_blocks > 3200u)) return X3_ERR_BAD_ARG;
+  uint64_t G = 0;
+  for (uint64_t e = 0; e < n; ++e) {
+    if (offsets[e] > x3_len || lengths[e] > x3_len - offsets[e]) return X3_ERR_BAD_ARG;
+    G += (lengths[e] + X3T_SPAN_BYTES - 1) / X3T_SPAN_BYTES;
+  }
+  if (G > 0x7FFFFFFFull / X3I_WG_CANDS) return X3_ERR_BAD_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  x3_corpus* k = new x3_corpus;
+  k->device = c->device;
+  k->d_x3 = d_x3;
+  k->x3_len = x3_len;
+  k->n = n;
+  k->p = *p;
+  c->decode_pending = false;
+  c->last_corpus_slices = 0;
+  const int rc = corpus_build_impl(c, k, offsets, lengths, (flags & X3_STREAMS_ARCHIVE_FRAMES) ? 8 : 0, seg_blocks);
+  if (rc) {
+    (void)hipStreamSynchronize(c->stream);   // (nothing of the build may still run when its buffers go)
+    x3_corpus_destroy(k);
+    return rc;
+  }
+  *out = k;
+  return X3_OK;
+}
+
+extern "C" int x3_corpus_info(const x3_corpus* k, uint64_t* n_entries, uint64_t* n_frames, uint64_t* total_samples,
+                              uint32_t* seg_blocks_in_use) {
+  if (!k) return X3_ERR_BAD_ARG;
+  if (n_entries) *n_entries = k->n;
+  if (n_frames) *n_frames = k->F;
+  if (total_samples) *total_samples = k->total;
+  if (seg_blocks_in_use) *seg_blocks_in_use = k->seg_blocks;
+  return X3_OK;
+}
+
+extern "C" int x3_corpus_entries(const x3_corpus* k, x3_corpus_entry* out) {
+  if (!k || !out) return X3_ERR_BAD_ARG;
+  std::memcpy(out, k->ent.data(), sizeof(x3_corpus_entry) * k->n);
+  return X3_OK;
+}
+
+extern "C" int x3_corpus_seg_index(const x3_corpus* k, const uint64_t** d_seg_index, uint64_t* n_words) {
+  if (!k || !d_seg_index || !n_words) return X3_ERR_BAD_ARG;
+  *d_seg_index = k->d_index;
+  *n_words = k->d_index ? x3_seg_index_entries(k->F, &k->p, k->seg_blocks) : 0;
+  return X3_OK;
+}
+
+extern "C" int x3_corpus_windows_dev(x3_ctx* c, const x3_corpus* k, const uint32_t* d_entries, const uint64_t* d_starts,
+                                     uint64_t n_windows, uint32_t window_len, void* d_out, int out_format, int32_t* d_status) {
+  if (!c || !k || !d_entries || (reinterpret_cast<uintptr_t>(d_entries) & 3u)) return X3_ERR_BAD_ARG;
+  if (!windows_args_ok(n_windows, window_len, d_out, out_format, d_starts, d_status)) return X3_ERR_BAD_ARG;
+  if (c->device != k->device) {
+    c->last_error = "x3_corpus_windows_dev: the corpus was built on another device";
+    return X3_ERR_BAD_ARG;
+  }
+  X3DevParams dp;
+  const uint64_t spf = spf_of(&k->p);
+  int rc = derive(&k->p, spf, &dp);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  const uint64_t n_ent = k->n, F = k->F;
+  const x3_corpus_entry* ent = k->d_ent;
+  const uint64_t* so = k->d_so;
+  return windows_launch(c, k->d_x3, k->x3_len, k->d_frame_off, k->d_so, F, dp, spf, k->d_index, k->seg_blocks, n_windows,
+                        window_len, d_out, out_format, d_status,
+                        [&](dim3 grid, X3WinPlan* plan, uint64_t* gstart, X3WinSummary* sum) -> const uint64_t* {
+                          hipLaunchKernelGGL(x3_corpus_plan_kernel, grid, dim3(256), 0, c->stream, ent, n_ent, so, F, d_entries,
+                                             d_starts, n_windows, window_len, plan, gstart, sum);
+                          return gstart;
+                        });
 }

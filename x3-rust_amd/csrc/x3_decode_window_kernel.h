@@ -262,28 +262,30 @@ x3_window_sample_offsets_kernel(const uint8_t* __restrict__ x3, uint64_t len, co
   if (threadIdx.x == 0) so[F] = total;
 }
 
-// ---- plan: a thread per window
+// ---- plan: a thread per window, grid-stride (the grid is capped at X3W_GRID_LIMIT groups; every window gets its plan)
 __global__ void __launch_bounds__(256)
 x3_window_plan_kernel(const uint64_t* __restrict__ so, uint64_t F, const uint64_t* __restrict__ starts, uint64_t n_windows,
                       uint32_t L, X3WinPlan* __restrict__ plan, X3WinSummary* __restrict__ sum) {
-  const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (w == 0) {
+  const uint64_t w0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (w0 == 0) {
     sum->n_bad = 0;
     sum->first = ~0ull;
     sum->replays = 0;
   }
-  if (w >= n_windows) return;
-  const uint64_t start = starts[w], total = so[F];
-  X3WinPlan pl{0, 0, X3D_BAD_ARG};
-  // (so[0] <= start and so[F] > start + L - 1 are the search's invariants; offsets that break them are not this stream's)
-  if (L <= total && start <= total - L && so[0] <= start) {
-    const uint64_t e = start + (L - 1u);
-    const uint64_t fa = x3w_search(so, 0, F, start);
-    const uint64_t fb = x3w_search(so, fa, F, e);
-    // more covering frames than samples: a frame of 0 samples or offsets out of order, no stream's frames
-    if (fb - fa < (uint64_t)L) pl = X3WinPlan{fa, (uint32_t)(fb - fa + 1u), X3D_OK};
+  const uint64_t total = so[F];
+  for (uint64_t w = w0; w < n_windows; w += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t start = starts[w];
+    X3WinPlan pl{0, 0, X3D_BAD_ARG};
+    // (so[0] <= start and so[F] > start + L - 1 are the search's invariants; offsets that break them are not this stream's)
+    if (L <= total && start <= total - L && so[0] <= start) {
+      const uint64_t e = start + (L - 1u);
+      const uint64_t fa = x3w_search(so, 0, F, start);
+      const uint64_t fb = x3w_search(so, fa, F, e);
+      // more covering frames than samples: a frame of 0 samples or offsets out of order, no stream's frames
+      if (fb - fa < (uint64_t)L) pl = X3WinPlan{fa, (uint32_t)(fb - fa + 1u), X3D_OK};
+    }
+    plan[w] = pl;
   }
-  plan[w] = pl;
 }
 
 // ---- exclusive scans of the covering frames (cov) and the work items (cov * stretches) per window; n + 1 entries each
@@ -499,5 +501,53 @@ x3_window_fixup_kernel(const uint8_t* __restrict__ x3, const uint64_t* __restric
         atomicMin(&sum->first, (unsigned long long)(w << 8) | (uint32_t)st);
       }
     }
+  }
+}
+
+// ---- CORPUS (x3_corpus_windows_dev)
+// an entry's positions: so[first_frame + n_frames] - so[first_frame] (the build, one thread per entry)
+__global__ void __launch_bounds__(256)
+x3_corpus_samples_kernel(const uint64_t* __restrict__ so, uint64_t F, x3_corpus_entry* __restrict__ ent, uint64_t n) {
+  const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n) return;
+  const uint64_t a = ent[e].first_frame, b = a + ent[e].n_frames;
+  ent[e].n_samples = b <= F && so[b] >= so[a] ? so[b] - so[a] : 0ull;
+}
+
+// plan: a thread per window (entry, start), grid-stride as x3_window_plan_kernel.  The entry's positions are consecutive in
+// the corpus's sample offsets, so its start s is the global position so[first_frame] + s; the covering frames are searched
+// inside the entry's frames as x3_window_plan_kernel searches a stream's.  gstart[w]: the position the later kernels read
+// where they read d_starts.
+__global__ void __launch_bounds__(256)
+x3_corpus_plan_kernel(const x3_corpus_entry* __restrict__ ent, uint64_t n_ent, const uint64_t* __restrict__ so, uint64_t F,
+                      const uint32_t* __restrict__ entries, const uint64_t* __restrict__ starts, uint64_t n_windows, uint32_t L,
+                      X3WinPlan* __restrict__ plan, uint64_t* __restrict__ gstart, X3WinSummary* __restrict__ sum) {
+  const uint64_t w0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (w0 == 0) {
+    sum->n_bad = 0;
+    sum->first = ~0ull;
+    sum->replays = 0;
+  }
+  for (uint64_t w = w0; w < n_windows; w += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t e = entries[w];
+    const uint64_t start = starts[w];
+    X3WinPlan pl{0, 0, X3D_BAD_ARG};
+    uint64_t g = 0;
+    if (e < n_ent) {
+      const x3_corpus_entry en = ent[e];
+      const uint64_t fa0 = en.first_frame, fb0 = en.first_frame + en.n_frames;
+      // (the table's words are checked, not trusted: the entry's frames inside the table, its positions inside so's range)
+      if (en.n_frames && fa0 < F && en.n_frames <= F - fa0 && L <= en.n_samples && start <= en.n_samples - L) {
+        const uint64_t base = so[fa0], total = so[fb0];
+        if (total >= base && total - base == en.n_samples) {
+          g = base + start;
+          const uint64_t fa = x3w_search(so, fa0, fb0, g);
+          const uint64_t fb = x3w_search(so, fa, fb0, g + (L - 1u));
+          if (fb - fa < (uint64_t)L) pl = X3WinPlan{fa, (uint32_t)(fb - fa + 1u), X3D_OK};
+        }
+      }
+    }
+    plan[w] = pl;
+    gstart[w] = g;
   }
 }

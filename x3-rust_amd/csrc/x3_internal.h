@@ -196,6 +196,7 @@ struct x3_ctx {
   // decode_replays sums every summary read so far, the stream entry points take their difference
   unsigned long long last_decode_replays = 0, decode_replays = 0;
   unsigned long long last_window_replays = 0;   // (window, covering frame) pairs x3_window_fixup_kernel re-decoded
+  unsigned long long last_corpus_slices = 0;    // x3_corpus_build: slices of frames its recording decode took (option)
   struct LastEnc {
     const int16_t* d_wav; x3_batch b; x3_params p; uint64_t spf; uint8_t* d_out; uint64_t out_cap, start_pos; uint64_t* d_off;
     const uint64_t* src_off; const uint32_t* src_n; bool src_even;   // x3_encode_frames_dev's frame table (device), or nullptr

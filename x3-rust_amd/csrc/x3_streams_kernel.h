@@ -189,3 +189,47 @@ x3_streams_rows_kernel(const int16_t* __restrict__ ws, void* __restrict__ out, u
     }
   }
 }
+
+// ---- CORPUS (x3_corpus_build): the same walk as an index.  Its link step is x3_streams_link_kernel
+// with row_len = ~0 and x4 = 0: every frame the walk steps over is live, at its buffer offset, whatever its position.
+
+// C1. one thread per entry: a clean entry's candidates [k0, k0 + m) are its frames, its walk ends as x3i_walk_end says
+// behind them; m = ~0 marks an entry left to the general walk
+__global__ void __launch_bounds__(256)
+x3_corpus_walk_kernel(const uint32_t* __restrict__ xw, uint64_t x3_len, const uint64_t* __restrict__ eoff,
+                      const uint64_t* __restrict__ elen, const uint32_t* __restrict__ span_first, uint32_t n, uint64_t phantom,
+                      const uint32_t* __restrict__ base, uint32_t G, const unsigned long long* __restrict__ d_total,
+                      const uint32_t* __restrict__ ent_flags, const unsigned long long* __restrict__ ent_end,
+                      unsigned long long* __restrict__ ent_k0, unsigned long long* __restrict__ ent_m,
+                      int32_t* __restrict__ ent_st) {
+  const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n) return;
+  if (ent_flags[e] & X3T_DIRTY) {
+    ent_k0[e] = 0ull;
+    ent_m[e] = ~0ull;
+    ent_st[e] = 0;
+    return;
+  }
+  const unsigned long long total = *d_total;
+  const uint32_t fs = span_first[e], fe = span_first[e + 1];
+  const unsigned long long k0 = fs < G ? base[fs] : total, k1 = fe < G ? base[fe] : total;
+  const uint64_t L = elen[e];
+  ent_k0[e] = k0;
+  ent_m[e] = k1 - k0;
+  ent_st[e] = x3i_walk_end(xw, (x3_len + 3) >> 2, eoff[e], L, L + phantom, k1 > k0 ? ent_end[e] : 0ull, 0u);
+}
+
+// C2. one thread per candidate: a clean entry's frame goes to its place in the corpus's frame table (entries in order);
+// the general walk's entries are filled from the host
+__global__ void __launch_bounds__(256)
+x3_corpus_compact_kernel(const unsigned long long* __restrict__ frame_off, const uint32_t* __restrict__ fent, uint64_t cap,
+                         const unsigned long long* __restrict__ d_total, const unsigned long long* __restrict__ ent_k0,
+                         const x3_corpus_entry* __restrict__ ent, uint64_t F, uint64_t* __restrict__ out) {
+  const unsigned long long total = *d_total < cap ? *d_total : cap;
+  for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < total; k += (uint64_t)gridDim.x * blockDim.x) {
+    const x3_corpus_entry& en = ent[fent[k]];
+    if (en.general_walk) continue;
+    const uint64_t i = k - ent_k0[fent[k]];
+    if (i < en.n_frames && en.first_frame + i < F) out[en.first_frame + i] = frame_off[k];
+  }
+}

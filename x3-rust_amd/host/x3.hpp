@@ -736,6 +736,71 @@ inline X3Error decode_streams(Context& ctx, const uint8_t* d_x3, uint64_t x3_len
   return static_cast<X3Error>(rc);
 }
 
+// Windows of many streams (x3_corpus_build / x3_corpus_windows_dev): an index built once over the entries of d_x3 (as in
+// decode_streams; d_x3 must outlive the corpus), after which window w is samples [d_starts[w], d_starts[w] + window_len) of
+// entry d_entries[w].  RAII: the index is freed with the object.
+class Corpus {
+ public:
+  Corpus() = default;
+  Corpus(const Corpus&) = delete;
+  Corpus& operator=(const Corpus&) = delete;
+  Corpus(Corpus&& o) noexcept : raw_(o.raw_) { o.raw_ = nullptr; }
+  Corpus& operator=(Corpus&& o) noexcept {
+    if (this != &o) {
+      reset();
+      raw_ = o.raw_;
+      o.raw_ = nullptr;
+    }
+    return *this;
+  }
+  ~Corpus() { reset(); }
+  // Synchronous.  seg_blocks: 0 = no segment index (it is only ever a hint).
+  X3Error build(Context& ctx, const uint8_t* d_x3, uint64_t x3_len, const std::vector<uint64_t>& offsets,
+                const std::vector<uint64_t>& lengths, uint32_t flags, const Parameters& params, uint32_t seg_blocks = 32) {
+    if (offsets.size() != lengths.size()) return X3Error::BadArg;
+    reset();
+    const x3_params c = params.c_params();
+    return static_cast<X3Error>(x3_corpus_build(ctx.raw(), d_x3, x3_len, offsets.data(), lengths.data(), offsets.size(), flags,
+                                                &c, seg_blocks, &raw_));
+  }
+  bool ok() const { return raw_ != nullptr; }
+  uint64_t n_entries() const { uint64_t v = 0; x3_corpus_info(raw_, &v, nullptr, nullptr, nullptr); return v; }
+  uint64_t n_frames() const { uint64_t v = 0; x3_corpus_info(raw_, nullptr, &v, nullptr, nullptr); return v; }
+  uint64_t total_samples() const { uint64_t v = 0; x3_corpus_info(raw_, nullptr, nullptr, &v, nullptr); return v; }
+  uint32_t seg_blocks_in_use() const { uint32_t v = 0; x3_corpus_info(raw_, nullptr, nullptr, nullptr, &v); return v; }
+  std::vector<x3_corpus_entry> entries() const {
+    std::vector<x3_corpus_entry> v(raw_ ? n_entries() : 0);
+    if (raw_) x3_corpus_entries(raw_, v.data());
+    return v;
+  }
+  // Waits for the call: res = windows with status != 0, the first, its status.
+  X3Error windows(Context& ctx, const uint32_t* d_entries, const uint64_t* d_starts, uint64_t n_windows, uint32_t window_len,
+                  void* d_out, int out_format, int32_t* d_status, WindowsResult* res) const {
+    int rc = x3_corpus_windows_dev(ctx.raw(), raw_, d_entries, d_starts, n_windows, window_len, d_out, out_format, d_status);
+    if (rc != X3_OK) return static_cast<X3Error>(rc);
+    WindowsResult r;
+    rc = x3_decode_windows_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status);
+    if (res) *res = r;
+    return static_cast<X3Error>(rc);
+  }
+  // the recorded segment index (device memory the corpus owns), nullptr and 0 words without one
+  const uint64_t* seg_index(uint64_t* n_words) const {
+    const uint64_t* d = nullptr;
+    uint64_t n = 0;
+    if (raw_) x3_corpus_seg_index(raw_, &d, &n);
+    if (n_words) *n_words = n;
+    return d;
+  }
+  const x3_corpus* raw() const { return raw_; }
+
+ private:
+  void reset() {
+    if (raw_) x3_corpus_destroy(raw_);
+    raw_ = nullptr;
+  }
+  x3_corpus* raw_ = nullptr;
+};
+
 // Placement (x3_place_buffers; profiles/r6/decoder_modes.txt): the round trip timed on every pair of candidate buffers --
 // ms[i * backs.size() + j] for (streams[i], backs[j]).  A pipeline that keeps its buffers calls this once and keeps the
 // pair that runs best; what it does not keep it frees.

@@ -49,6 +49,16 @@ pub mod ffi {
         pub status: i32,
         pub frame_errors: u32,
     }
+    /// `x3_corpus_entry`: one entry of a corpus (`x3_corpus_entries`)
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct x3_corpus_entry {
+        pub n_samples: u64,
+        pub first_frame: u64,
+        pub n_frames: u64,
+        pub walk_status: i32,
+        pub general_walk: u32,
+    }
     #[repr(C)]
     #[derive(Clone, Copy, Debug)]
     pub struct x3_rice_code {
@@ -63,7 +73,7 @@ pub mod ffi {
     macro_rules! opaque {
         ($($n:ident),*) => { $(#[repr(C)] pub struct $n { _private: [u8; 0] })* };
     }
-    opaque!(x3_ctx, x3_bitreader, x3_bitpacker, x3_reader, x3_tuner);
+    opaque!(x3_ctx, x3_bitreader, x3_bitpacker, x3_reader, x3_tuner, x3_corpus);
 
     extern "C" {
         pub fn x3_strerror(status: c_int) -> *const c_char;
@@ -141,6 +151,15 @@ pub mod ffi {
                                      n_streams: u64, flags: u32, p: *const x3_params, d_out: *mut c_void, row_len: u64,
                                      out_format: c_int, d_results: *mut x3_stream_result) -> c_int;
         pub fn x3_decode_streams_result(ctx: *mut x3_ctx, n_bad: *mut u64, first_bad: *mut u64, first_bad_status: *mut c_int) -> c_int;
+        pub fn x3_corpus_build(ctx: *mut x3_ctx, d_x3: *const u8, x3_len: u64, offsets: *const u64, lengths: *const u64,
+                               n_entries: u64, flags: u32, p: *const x3_params, seg_blocks: u32, corpus: *mut *mut x3_corpus) -> c_int;
+        pub fn x3_corpus_info(corpus: *const x3_corpus, n_entries: *mut u64, n_frames: *mut u64, total_samples: *mut u64,
+                              seg_blocks_in_use: *mut u32) -> c_int;
+        pub fn x3_corpus_entries(corpus: *const x3_corpus, out: *mut x3_corpus_entry) -> c_int;
+        pub fn x3_corpus_seg_index(corpus: *const x3_corpus, d_seg_index: *mut *const u64, n_words: *mut u64) -> c_int;
+        pub fn x3_corpus_windows_dev(ctx: *mut x3_ctx, corpus: *const x3_corpus, d_entries: *const u32, d_starts: *const u64,
+                                     n_windows: u64, window_len: u32, d_out: *mut c_void, out_format: c_int, d_status: *mut i32) -> c_int;
+        pub fn x3_corpus_destroy(corpus: *mut x3_corpus);
         pub fn x3_place_buffers(ctx: *mut x3_ctx, d_wav: *const i16, n: u64, p: *const x3_params, d_streams: *const *mut u8,
                                 n_streams: u32, cap: u64, d_frame_offsets: *mut u64, d_backs: *const *mut i16, n_backs: u32,
                                 warm: u32, steps: u32, ms_per_step: *mut f64) -> c_int;
@@ -1232,6 +1251,78 @@ pub mod device {
         let (mut n_bad, mut first_bad, mut st) = (0u64, 0u64, 0);
         error::check(unsafe { ffi::x3_decode_streams_result(gpu.raw(), &mut n_bad, &mut first_bad, &mut st) })?;
         Ok((n_bad, first_bad, st))
+    }
+
+    /// Windows of many streams (`x3_corpus_build`; not in the reference crate): an index built once over the entries of
+    /// `d_x3` (as in `decode_streams`), after which window w is samples `[d_starts[w], d_starts[w] + window_len)` of entry
+    /// `d_entries[w]`.  The corpus borrows `d_x3`; dropping it frees the index.
+    pub struct Corpus<'g> {
+        gpu: &'g Gpu,
+        raw: *mut ffi::x3_corpus,
+        _bytes: core::marker::PhantomData<&'g Buffer<'g>>,
+    }
+
+    impl<'g> Corpus<'g> {
+        /// Synchronous.  `seg_blocks`: 0 = no segment index (32 is the usual choice); it is only ever a hint.
+        #[allow(clippy::too_many_arguments)]
+        pub fn build(gpu: &'g Gpu, d_x3: &'g Buffer<'g>, x3_len: usize, offsets: &[u64], lengths: &[u64], flags: u32,
+                     params: &x3::Parameters, seg_blocks: u32) -> error::Result<Corpus<'g>> {
+            if lengths.len() != offsets.len() || x3_len > d_x3.len() {
+                return Err(X3Error::BadArg);
+            }
+            let p = params.c()?;
+            let mut raw: *mut ffi::x3_corpus = core::ptr::null_mut();
+            error::check(unsafe {
+                ffi::x3_corpus_build(gpu.raw(), d_x3.as_ptr::<u8>(), x3_len as u64, offsets.as_ptr(), lengths.as_ptr(),
+                                     offsets.len() as u64, flags, &p, seg_blocks, &mut raw)
+            })?;
+            Ok(Corpus { gpu, raw, _bytes: core::marker::PhantomData })
+        }
+
+        /// -> (entries, frames, samples in all, segment index blocks in use)
+        pub fn info(&self) -> (u64, u64, u64, u32) {
+            let (mut n, mut f, mut t, mut sb) = (0u64, 0u64, 0u64, 0u32);
+            unsafe { ffi::x3_corpus_info(self.raw, &mut n, &mut f, &mut t, &mut sb) };
+            (n, f, t, sb)
+        }
+
+        pub fn entries(&self) -> Vec<ffi::x3_corpus_entry> {
+            let mut v = vec![ffi::x3_corpus_entry::default(); self.info().0 as usize];
+            unsafe { ffi::x3_corpus_entries(self.raw, v.as_mut_ptr()) };
+            v
+        }
+
+        /// The recorded segment index: (device pointer the corpus owns, words), or (null, 0) without one
+        pub fn seg_index(&self) -> (*const u64, u64) {
+            let (mut d, mut n): (*const u64, u64) = (core::ptr::null(), 0);
+            unsafe { ffi::x3_corpus_seg_index(self.raw, &mut d, &mut n) };
+            (d, n)
+        }
+
+        /// `n` windows of `window_len` samples (`d_entries`: n x u32, `d_starts`: n x u64, `d_out`: n x window_len samples of
+        /// `out_format`, `d_status`: n x i32).  Waits: -> (windows with status != 0, the first of them, its status)
+        #[allow(clippy::too_many_arguments)]
+        pub fn windows(&self, d_entries: &Buffer<'g>, d_starts: &Buffer<'g>, n: usize, window_len: u32, d_out: &mut Buffer<'g>,
+                       out_format: i32, d_status: &mut Buffer<'g>) -> error::Result<(u64, u64, i32)> {
+            let esz = if out_format == WINDOW_F32 { 4 } else { 2 };
+            if d_entries.len() < 4 * n || d_starts.len() < 8 * n || d_out.len() < esz * n * window_len as usize
+                || d_status.len() < 4 * n {
+                return Err(X3Error::BadArg);
+            }
+            error::check(unsafe {
+                ffi::x3_corpus_windows_dev(self.gpu.raw(), self.raw, d_entries.as_ptr::<u32>(), d_starts.as_ptr::<u64>(),
+                                           n as u64, window_len, d_out.as_ptr::<c_void>(), out_format, d_status.as_ptr::<i32>())
+            })?;
+            let (mut n_bad, mut first_bad, mut st) = (0u64, 0u64, 0);
+            error::check(unsafe { ffi::x3_decode_windows_result(self.gpu.raw(), &mut n_bad, &mut first_bad, &mut st) })?;
+            Ok((n_bad, first_bad, st))
+        }
+    }
+
+    impl Drop for Corpus<'_> {
+        fn drop(&mut self) {
+            unsafe { ffi::x3_corpus_destroy(self.raw) };
+        }
     }
 
     /// Placement (`x3_place_buffers`; profiles/r6/decoder_modes.txt): the round trip timed on every pair of candidate buffers --

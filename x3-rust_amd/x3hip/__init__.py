@@ -58,6 +58,8 @@ SYMBOLS = [
     "x3_encode_mc", "x3_decode_stream_mc",
     "x3_sample_offsets_dev", "x3_decode_windows_dev", "x3_decode_windows_result",
     "x3_decode_streams_dev", "x3_decode_streams_result",
+    "x3_corpus_build", "x3_corpus_info", "x3_corpus_entries", "x3_corpus_seg_index", "x3_corpus_windows_dev",
+    "x3_corpus_destroy",
     "x3_tune_candidate", "x3_tuner_create", "x3_tuner_add_dev", "x3_tuner_result", "x3_tuner_max_payloads",
     "x3_tuner_reset", "x3_tuner_destroy", "x3_tune", "x3_x3a_encode_tuned",
 ]
@@ -74,6 +76,9 @@ class StreamResult(C.Structure):
 
 
 STREAM_RESULT_DTYPE = np.dtype([("n_out", "<u8"), ("frames_ok", "<u8"), ("status", "<i4"), ("frame_errors", "<u4")])
+# x3_corpus_entry: one entry of a Corpus
+CORPUS_ENTRY_DTYPE = np.dtype([("n_samples", "<u8"), ("first_frame", "<u8"), ("n_frames", "<u8"), ("walk_status", "<i4"),
+                               ("general_walk", "<u4")])
 
 
 class RiceCode(C.Structure):
@@ -211,6 +216,13 @@ def lib():
     L.x3_decode_windows_result.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(i32)]
     L.x3_decode_streams_dev.argtypes = [vp, vp, u64, vp, vp, u64, u32, PP, vp, u64, i32, vp]
     L.x3_decode_streams_result.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(i32)]
+    L.x3_corpus_build.argtypes = [vp, vp, u64, vp, vp, u64, u32, PP, u32, C.POINTER(vp)]
+    L.x3_corpus_info.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]
+    L.x3_corpus_entries.argtypes = [vp, vp]
+    L.x3_corpus_seg_index.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
+    L.x3_corpus_windows_dev.argtypes = [vp, vp, vp, vp, u64, u32, vp, i32, vp]
+    L.x3_corpus_destroy.argtypes = [vp]
+    L.x3_corpus_destroy.restype = None
     L.x3_synth.argtypes = [i32, u64, u64, u64, vp]
     L.x3_synth_dev.argtypes = [vp, i32, u64, u64, u64, vp]
     L.x3_dev_alloc.argtypes = [vp, u64, C.POINTER(vp)]
@@ -1086,14 +1098,9 @@ def _frames_samples(data, start):
     return n
 
 
-def decode_archives(ctx, archives, row_len=None, fmt=WINDOW_I16):
-    """Decode many .x3a archives (bytes-like objects or paths) into padded rows with x3_decode_streams_dev.
-
-    Each archive's header is read on the host (x3_archive_header_read); archives are grouped by parameter set and every
-    group is one device call over one buffer of frame parts.  row_len=None: the longest archive's sample count by its frame
-    headers, rounded up to a multiple of 4.  Returns (rows [n, row_len] int16 / float32, results (STREAM_RESULT_DTYPE,
-    per archive: x3_x3a_decode's n_out, frames_ok, status, frame_errors with wav_cap = row_len), sample rates) in the input
-    order.  An archive whose header does not parse gets that status, no samples, and is not sent to the device."""
+def _read_archives(archives):
+    """-> (datas, frame-part starts, sample rates, header statuses, {parameter-set key: (params, [indices])}) of .x3a
+    archives (bytes-like objects or paths); an archive whose header does not parse has its status and no group"""
     datas = []
     for a in archives:
         if isinstance(a, (str, os.PathLike)):
@@ -1105,34 +1112,55 @@ def decode_archives(ctx, archives, row_len=None, fmt=WINDOW_I16):
     if n == 0:
         raise ValueError("no archives")
     rates = np.zeros(n, dtype=np.uint32)
-    results = np.zeros(n, dtype=STREAM_RESULT_DTYPE)
+    statuses = np.zeros(n, dtype=np.int32)
     groups, starts = {}, [0] * n
     for i, d in enumerate(datas):
         rc, rate, p, _ch, hsize = archive_header_read(np.frombuffer(d, dtype=np.uint8))
         if rc:
-            results[i]["status"] = rc
+            statuses[i] = rc
             continue
         rates[i] = rate
         starts[i] = 8 + hsize
         key = bytes(p)
         groups.setdefault(key, (p, []))[1].append(i)
+    return datas, starts, rates, statuses, groups
+
+
+def _frame_parts(datas, starts, idx):
+    """one buffer of the archives' frame parts (idx), each at an even offset -> (buf with 16 bytes of slack, its length
+    without them, offsets, lengths)"""
+    offs, lens, blob, pos = [], [], [], 0
+    for i in idx:
+        part = datas[i][starts[i]:]
+        offs.append(pos)
+        lens.append(len(part))
+        blob.append(part)
+        pos += len(part)
+        if pos & 1:
+            blob.append(b"\0")
+            pos += 1
+    return np.frombuffer(b"".join(blob) + b"\0" * 16, dtype=np.uint8), pos, offs, lens
+
+
+def decode_archives(ctx, archives, row_len=None, fmt=WINDOW_I16):
+    """Decode many .x3a archives (bytes-like objects or paths) into padded rows with x3_decode_streams_dev.
+
+    Each archive's header is read on the host (x3_archive_header_read); archives are grouped by parameter set and every
+    group is one device call over one buffer of frame parts.  row_len=None: the longest archive's sample count by its frame
+    headers, rounded up to a multiple of 4.  Returns (rows [n, row_len] int16 / float32, results (STREAM_RESULT_DTYPE,
+    per archive: x3_x3a_decode's n_out, frames_ok, status, frame_errors with wav_cap = row_len), sample rates) in the input
+    order.  An archive whose header does not parse gets that status, no samples, and is not sent to the device."""
+    datas, starts, rates, statuses, groups = _read_archives(archives)
+    n = len(datas)
+    results = np.zeros(n, dtype=STREAM_RESULT_DTYPE)
+    results["status"] = statuses
     if row_len is None:
         row_len = max([_frames_samples(datas[i], starts[i]) for _, idx in groups.values() for i in idx] + [1])
         row_len = (row_len + 3) // 4 * 4
     esz = 4 if fmt == WINDOW_F32 else 2
     rows = np.zeros((n, row_len), dtype=np.float32 if fmt == WINDOW_F32 else np.int16)
     for p, idx in groups.values():
-        offs, lens, blob, pos = [], [], [], 0
-        for i in idx:
-            part = datas[i][starts[i]:]
-            offs.append(pos)
-            lens.append(len(part))
-            blob.append(part)
-            pos += len(part)
-            if pos & 1:
-                blob.append(b"\0")
-                pos += 1
-        buf = np.frombuffer(b"".join(blob) + b"\0" * 16, dtype=np.uint8)
+        buf, pos, offs, lens = _frame_parts(datas, starts, idx)
         m = len(idx)
         d_x3 = ctx.alloc(buf.size)
         d_out = ctx.alloc(esz * m * row_len)
@@ -1151,3 +1179,117 @@ def decode_archives(ctx, archives, row_len=None, fmt=WINDOW_I16):
             for ptr in (d_x3, d_out, d_res):
                 ctx.free(ptr)
     return rows, results, rates
+
+
+class Corpus:
+    """Windows of many streams in HBM (x3_corpus_build / x3_corpus_windows_dev): an index built once over the entries of
+    one device buffer, windows addressed as (entry, start).
+
+    `stream`: host bytes (uploaded once, owned) or (d_x3, x3_len) of a device buffer the caller keeps alive.  `offsets` /
+    `lengths`: the entries, as in Context.decode_streams_dev.  flags: 0 or STREAMS_ARCHIVE_FRAMES.  seg_blocks: the
+    segment index (0: none; it is only ever a hint).  `.entries`: the entry table (CORPUS_ENTRY_DTYPE)."""
+
+    def __init__(self, ctx, stream, offsets, lengths, params=None, flags=0, seg_blocks=32):
+        self.ctx, self.params, self._h, self._own = ctx, params or Params.default(), None, []
+        offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+        lens = np.ascontiguousarray(lengths, dtype=np.uint64)
+        if offs.ndim != 1 or offs.size != lens.size:
+            raise ValueError("offsets and lengths must be 1-D and of one length")
+        if offs.size == 0 or offs.size > 0xFFFFFFF0:
+            raise ValueError("a corpus holds 1 .. 0xFFFFFFF0 entries")
+        if flags & ~STREAMS_ARCHIVE_FRAMES:
+            raise ValueError("unknown flag")
+        if seg_blocks < 0 or seg_blocks % 4 or seg_blocks > 3200:
+            raise ValueError("seg_blocks: 0, or a multiple of 4 up to 3200")
+        if isinstance(stream, tuple):
+            self.d_x3, self.x3_len = stream
+        else:
+            b = np.ascontiguousarray(stream, dtype=np.uint8)
+            self.x3_len = b.size
+        if np.any(offs > self.x3_len) or np.any(lens > np.uint64(self.x3_len) - np.minimum(offs, self.x3_len)):
+            raise ValueError("an entry lies outside the buffer")
+        if not isinstance(stream, tuple):
+            self.d_x3 = ctx.alloc(max(b.size, 4))
+            self._own.append(self.d_x3)
+            ctx.upload(self.d_x3, b)
+        h = C.c_void_p(0)
+        rc = lib().x3_corpus_build(ctx._h, self.d_x3, self.x3_len, offs.ctypes.data, lens.ctypes.data, offs.size, flags,
+                                   C.byref(self.params), seg_blocks, C.byref(h))
+        if rc:
+            self.close()
+            raise X3Error(rc, "x3_corpus_build: " + ctx.last_error())
+        self._h = h
+        ne, nf, tot, sb = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
+        lib().x3_corpus_info(h, C.byref(ne), C.byref(nf), C.byref(tot), C.byref(sb))
+        self.n_entries, self.n_frames, self.total_samples, self.seg_blocks = ne.value, nf.value, tot.value, sb.value
+        self.entries = np.zeros(self.n_entries, dtype=CORPUS_ENTRY_DTYPE)
+        lib().x3_corpus_entries(h, self.entries.ctypes.data)
+        d_idx, nw = C.c_void_p(0), C.c_uint64(0)
+        lib().x3_corpus_seg_index(h, C.byref(d_idx), C.byref(nw))
+        self.d_seg_index, self.seg_index_words = d_idx.value, nw.value   # (device memory the corpus owns; None, 0: no index)
+
+    @classmethod
+    def from_archives(cls, ctx, archives, seg_blocks=32):
+        """A corpus of the frame parts of .x3a archives (bytes-like objects or paths), one entry per archive in the input
+        order, buffer built as decode_archives builds it.  ValueError for archives of more than one parameter set or with
+        a header that does not parse.  `.rates`: the archives' sample rates."""
+        datas, starts, rates, statuses, groups = _read_archives(archives)
+        if np.any(statuses):
+            raise ValueError("archive %d: its header does not parse (status %d)" % (int(np.argmax(statuses != 0)),
+                                                                                 int(statuses[statuses != 0][0])))
+        if len(groups) != 1:
+            raise ValueError("the archives have %d parameter sets; a corpus takes one" % len(groups))
+        p, idx = next(iter(groups.values()))
+        buf, pos, offs, lens = _frame_parts(datas, starts, idx)
+        d_x3 = ctx.alloc(buf.size)
+        try:
+            ctx.upload(d_x3, buf)
+            self = cls(ctx, (d_x3, pos), offs, lens, params=p, flags=STREAMS_ARCHIVE_FRAMES, seg_blocks=seg_blocks)
+        except BaseException:
+            ctx.free(d_x3)
+            raise
+        self._own.append(d_x3)
+        self.rates = rates
+        return self
+
+    def decode_into(self, d_entries, d_starts, n, length, d_out, fmt, d_status):
+        """enqueue n windows (device pointers: d_entries n x u32, d_starts n x u64, d_out n x length, d_status n x i32) ->
+        rc; x3_decode_windows_result waits"""
+        if self._h is None:
+            raise ValueError("the corpus is closed")
+        return lib().x3_corpus_windows_dev(self.ctx._h, self._h, d_entries, d_starts, n, length, d_out, fmt, d_status)
+
+    def decode(self, entries, starts, length, fmt=WINDOW_I16):
+        """-> (rows np.int16 / np.float32 [n, length], statuses np.int32 [n])"""
+        entries = np.ascontiguousarray(entries, dtype=np.uint32)
+        starts = np.ascontiguousarray(starts, dtype=np.uint64)
+        if entries.shape != starts.shape or entries.ndim != 1 or entries.size == 0:
+            raise ValueError("entries and starts: 1-D, non-empty, of one length")
+        if length <= 0 or length > 0xFFFFFFFF:
+            raise ValueError("length: 1 .. 2^32 - 1")
+        n = starts.size
+        esz = 4 if fmt == WINDOW_F32 else 2
+        d_ent, d_starts, d_out, d_st = (self.ctx.alloc(4 * n), self.ctx.alloc(8 * n), self.ctx.alloc(esz * n * length),
+                                        self.ctx.alloc(4 * n))
+        try:
+            self.ctx.upload(d_ent, entries)
+            self.ctx.upload(d_starts, starts)
+            rc = self.decode_into(d_ent, d_starts, n, length, d_out, fmt, d_st)
+            if rc:
+                raise X3Error(rc, "x3_corpus_windows_dev: " + self.ctx.last_error())
+            rc = self.ctx.decode_windows_result()[0]
+            if rc:
+                raise X3Error(rc, "x3_decode_windows_result: " + self.ctx.last_error())
+            rows = self.ctx.download(d_out, esz * n * length, np.float32 if fmt == WINDOW_F32 else np.int16)
+            return rows.reshape(n, length), self.ctx.download(d_st, 4 * n, np.int32)
+        finally:
+            for ptr in (d_ent, d_starts, d_out, d_st):
+                self.ctx.free(ptr)
+
+    def close(self):
+        if self._h is not None:
+            lib().x3_corpus_destroy(self._h)
+            self._h = None
+        for ptr in self._own:
+            self.ctx.free(ptr)
+        self._own = []
