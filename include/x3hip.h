@@ -161,6 +161,8 @@ const char* x3_last_error(const x3_ctx* ctx);
  * general walk) and "last_streams_general_walks" (of the last x3_decode_streams_result).
  * x3_corpus_build: read-only "last_corpus_record_slices" (slices of frames the last build recorded its segment index in;
  * 0 without an index).
+ * x3_seg_index_build_dev: read-only "last_seg_index_irregular" (frames of the last build -- x3_corpus_build's with
+ * X3_CORPUS_INDEX_WALK included -- whose walk stopped early: they have no valid entry from there on; reading it synchronizes).
  * Unknown name: X3_ERR_BAD_ARG. */
 int x3_ctx_set_option(x3_ctx* ctx, const char* name, long long value);
 int x3_ctx_get_option(const x3_ctx* ctx, const char* name, long long* value);
@@ -488,6 +490,28 @@ int x3_decode_dev_seg(x3_ctx* ctx, const uint8_t* d_x3, uint64_t x3_len, const u
                       uint64_t n_frames, const x3_batch* batch, const uint64_t* d_wav_offsets,
                       const x3_params* p, int16_t* d_wav, uint64_t wav_cap, int32_t* d_status,
                       uint64_t* d_seg_index, uint32_t seg_blocks, int record);
+/* The segment index of a stream somebody else wrote, WITHOUT decoding it: a kernel that walks every frame's codewords and
+ * adds up their values but stores no sample (csrc/x3_seg_index_kernel.h) -- a frame per lane, one
+ * 8-byte entry per seg_blocks blocks.  For ANY x3_params that x3_decode_windows_dev accepts: block lengths other than 20,
+ * any blocks_per_frame, any code set and thresholds, frames shorter than the parameters' frame (entries at or behind a
+ * frame's last block stay invalid), frames anywhere in d_x3.  d_frame_offsets: n_frames byte offsets into d_x3, as the
+ * device decode calls take.  d_seg_index: x3_seg_index_entries() words, 8-byte aligned; EVERY word is written (the header
+ * word, invalid entries as zero), so the buffer need not be cleared.  seg_blocks as x3_decode_dev_seg accepts it (a
+ * multiple of 4, <= 3 200); where it leaves a frame one stretch (x3_seg_index_entries() == 0) nothing is written.
+ *   Asynchronous on the context's stream: one launch, no host trip, no workspace, nothing allocated; the pending state of
+ * x3_decode_dev and of the window calls is left alone.  Offsets, headers and bytes are untrusted: nothing outside
+ * [d_x3, d_x3 + x3_len) (and the 16-byte chunks that hold its bytes) is read, nothing outside d_seg_index's words is
+ * written.  A frame that is irregular in a way the fast decoders flag (decode error, BFP width <= 5, a zero run of 32 bits
+ * or more, a block that ends behind the payload) has no valid entry from that point on and is counted in the read-only
+ * option "last_seg_index_irregular"; it gets no status here -- the consumers' check and fix-up passes give it one.  CRCs
+ * are not verified.  X3_ERR_BAD_ARG (nothing enqueued) for a NULL or misaligned pointer, n_frames == 0 or above
+ * 0x7FFFFFFF, a seg_blocks that x3_decode_dev_seg refuses and parameters that x3_decode_windows_dev refuses.
+ *   The walk-built index is for the WINDOW paths (x3_decode_windows_dev, x3_corpus_windows_dev), which decode any block
+ * length by it.  Out of scope: x3_decode_dev_seg still decodes frame by frame off block length 20 and the default codes
+ * whatever index it is given (the block-per-lane decoder has no stretch mode), and x3_encode_dev_seg still fills none
+ * there. */
+int x3_seg_index_build_dev(x3_ctx* ctx, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
+                           uint64_t n_frames, const x3_params* p, uint64_t* d_seg_index, uint32_t seg_blocks);
 /* ---- Placement (round 6).  Where the x3 stream and where the decoded samples lie in HBM decides the decode phase's pace by
  * up to 10 % -- per PAIR of buffers, reproducibly within a process, and by nothing their addresses show
  * (profiles/r6/decoder_modes.txt).  A pipeline that keeps its buffers allocates a few candidates once and keeps the pair that
@@ -605,6 +629,7 @@ int x3_decode_windows_result(x3_ctx* ctx, uint64_t* n_bad, uint64_t* first_bad, 
  * row_len == 0, an unknown out_format or flag, d_x3 not on a 4-byte boundary, d_out not on its sample size's boundary,
  * d_results not on an 8-byte one, an entry outside [0, x3_len), and parameters x3_params_validate refuses. */
 #define X3_STREAMS_ARCHIVE_FRAMES 1u   /* entries are the frame part of .x3a archives: walked as X3aReader walks them */
+#define X3_CORPUS_INDEX_WALK 0x100u    /* x3_corpus_build only (below): the segment index by x3_seg_index_build_dev */
 typedef struct x3_stream_result {
   uint64_t n_out;        /* samples of the entry (x3_decode_stream_dev's *n_out) */
   uint64_t frames_ok;    /* its *frames_ok */
@@ -636,9 +661,12 @@ typedef struct x3_corpus_entry {
   int32_t walk_status;   /* how its walk ended behind those frames (x3_index_dev's *terminal) */
   uint32_t general_walk; /* 1: the fast walk could not vouch for it; the general walk found its frames */
 } x3_corpus_entry;
-/* Synchronous.  offsets / lengths: HOST arrays into d_x3.  flags: 0 or X3_STREAMS_ARCHIVE_FRAMES.  seg_blocks: 0 = no
- * segment index, else as x3_decode_dev_seg accepts it; it is recorded by one decode of the corpus where the parameters
- * route to a decoder that records (block length 20, the default codes), and kept nowhere else (seg_blocks_in_use 0).
+/* Synchronous.  offsets / lengths: HOST arrays into d_x3.  flags: 0, X3_STREAMS_ARCHIVE_FRAMES, X3_CORPUS_INDEX_WALK or
+ * both.  seg_blocks: 0 = no segment index, else as x3_decode_dev_seg accepts it.  Without X3_CORPUS_INDEX_WALK it is
+ * recorded by one decode of the corpus where the parameters route to a decoder that records (block length 20, the default
+ * codes), and kept nowhere else (seg_blocks_in_use 0).  With the flag it is built by ONE x3_seg_index_build_dev over the
+ * corpus's frame table, for every parameter set (seg_blocks_in_use = seg_blocks unless frames are one stretch; no scratch
+ * rows, "last_corpus_record_slices" 0).
  * d_x3 is referenced, not copied: it must outlive the corpus.  The build ends the pending state of an earlier
  * x3_decode_dev, as x3_decode_stream_dev does.  X3_ERR_BAD_ARG, with nothing left allocated, for n_entries == 0 or above
  * 0xFFFFFFF0, an entry outside [0, x3_len), an unknown flag, d_x3 not on a 4-byte boundary, parameters that

@@ -11,7 +11,9 @@ Families: (e) the single-pass encoders on block_len 20 with mixed content, many 
           chunked pipeline (not in the default family set: file I/O); (s) the segment index: the encoder's against the one a
           decode records, decode by it with the stream and the index intact or damaged; (c) random access: batches of
           windows (x3_decode_windows_dev) of random streams, geometries and lengths, with damaged frames, damaged indexes
-          and wild starts, against the oracle's frame verdicts (not in the default family set)."""
+          and wild starts, against the oracle's frame verdicts (not in the default family set); (x) the same with the
+          index built by x3_seg_index_build_dev on the stream as it is -- any block length and code set, damage included
+          (not in the default family set)."""
 import argparse, ctypes as C, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "x3-rust_amd"))
@@ -679,8 +681,10 @@ def _frame_verdicts(stream, offs, p):
     return out
 
 
-def fam_c(rng, tag):
-    """random access: windows of a random stream against the oracle's verdict of every frame that covers them"""
+def _fam_windows(rng, tag, index):
+    """random access: windows of a random stream against the oracle's verdict of every frame that covers them; the segment
+    index recorded by a decode (index = "decode") or built by x3_seg_index_build_dev on the stream as it is, damage
+    included (index = "walk": there always with an index)"""
     r = rng.random()
     if r < 0.6:
         p = x3hip.Params.default()
@@ -727,7 +731,9 @@ def fam_c(rng, tag):
         d_off = ctx.alloc(8 * (len(offs) + 1)); d.append(d_off)
         ctx.upload(d_off, np.array(offs + [stream.size], dtype=np.uint64))
         sb = int(rng.choice([0, 4, 32, 64]))
-        src = x3hip.WindowSource(ctx, bad, p, seg_blocks=sb, frame_offsets=d_off, n_frames=len(offs))
+        if index == "walk" and sb == 0:
+            sb = 8
+        src = x3hip.WindowSource(ctx, bad, p, seg_blocks=sb, frame_offsets=d_off, n_frames=len(offs), index=index)
         d.extend(src._own); src._own = []
         assert src.total == n, (tag, "total", src.total, n)
         if src.d_seg_index is not None and rng.random() < 0.3:   # a damaged index: a hint, never trusted
@@ -772,7 +778,17 @@ def fam_c(rng, tag):
             ctx.free(q)
 
 
+def fam_c(rng, tag):
+    _fam_windows(rng, tag, "decode")
+
+
+def fam_x(rng, tag):
+    """(c) by a walk-built index: content x geometry x damage, any block length and code set"""
+    _fam_windows(rng, tag, "walk")
+
+
 fams["c"] = fam_c
+fams["x"] = fam_x
 
 
 def run(seed=1, minutes=None, trials=None, families="egdbaf", only=-1, context=None):

@@ -126,6 +126,8 @@ static int ctx_init(x3_ctx* c, int device, hipStream_t stream, bool own) {
   HIPCHK(c, x3_dmalloc(&c->d_pace, X3_PACE_WORDS * sizeof(uint32_t)));
   HIPCHK(c, hipMemset(c->d_pace, 0, X3_PACE_WORDS * sizeof(uint32_t)));
   HIPCHK(c, x3_dmalloc(&c->d_crc, 16));
+  HIPCHK(c, x3_dmalloc(&c->d_seg_irregular, 16));
+  HIPCHK(c, hipMemset(c->d_seg_irregular, 0, 16));
   HIPCHK(c, hipHostMalloc(&c->h_status, 128));
   c->h_stats = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(c->h_status) + 32);
   HIPCHK(c, hipHostMalloc(&c->h_summary, sizeof(X3DecodeSummary)));
@@ -293,6 +295,7 @@ extern "C" void x3_ctx_destroy(x3_ctx* c) {
   (void)x3_dfree(c->d_summary);
   (void)x3_dfree(c->d_pace);
   (void)x3_dfree(c->d_crc);
+  (void)x3_dfree(c->d_seg_irregular);
   (void)hipHostFree(c->h_status);
   if (c->h_walk) (void)hipHostFree(c->h_walk);
   (void)hipHostFree(c->h_summary);
@@ -471,6 +474,13 @@ extern "C" int x3_ctx_get_option(const x3_ctx* c, const char* name, long long* v
       return X3_ERR_HIP;
     // (the decoder keeps one word per launch parity: the newer one carries the larger epoch tag)
     *value = (long long)((n == "encode_pace" ? w[4] : std::max(w[0], w[1])) & 0xFFFFFu);
+  }
+  else if (n == "last_seg_index_irregular") {  // (read-only, syncs) frames of the last x3_seg_index_build_dev whose walk stopped early
+    unsigned long long w = 0;
+    if (hipSetDevice(c->device) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess ||
+        hipMemcpy(&w, c->d_seg_irregular, sizeof w, hipMemcpyDeviceToHost) != hipSuccess)
+      return X3_ERR_HIP;
+    *value = (long long)w;
   }
   else if (n == "check_first") *value = c->opt.check_first;
   else if (n == "check_wgs") *value = c->opt.check_wgs;

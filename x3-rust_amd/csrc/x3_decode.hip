@@ -8,6 +8,7 @@
 #include "x3_index_kernels.h"
 #include "x3_decode_mc_kernel.h"
 #include "x3_decode_window_kernel.h"
+#include "x3_seg_index_kernel.h"
 
 // ------------------------------------------------------------------------------------------------
 // decode
@@ -1133,6 +1134,38 @@ extern "C" int x3_decode_windows_result(x3_ctx* c, uint64_t* n_bad, uint64_t* fi
 }
 
 // ------------------------------------------------------------------------------------------------
+// the segment index by a walk (x3_seg_index_kernel.h)
+// ------------------------------------------------------------------------------------------------
+// One launch behind a 8-byte memset of the counter; nothing is allocated, nothing waits, no pending state is touched.
+static int seg_index_launch(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets, uint64_t F,
+                            const X3DevParams& dp, uint64_t* d_seg_index, uint32_t seg_blocks) {
+  const uint64_t nidx = ((uint64_t)dp.blocks_per_frame + seg_blocks - 1) / seg_blocks;
+  HIPCHK(c, hipMemsetAsync(c->d_seg_irregular, 0, sizeof(unsigned long long), c->stream));
+  if (nidx < 2) return X3_OK;   // (x3_seg_index_entries() == 0: frames of one stretch have no index)
+  const uint64_t groups = std::min<uint64_t>((F + 63) / 64, (uint64_t)c->n_cus * X3X_WAVES_PER_CU);
+  hipLaunchKernelGGL(x3_seg_index_kernel, dim3((unsigned)groups), dim3(64), 0, c->stream, d_x3, x3_len, d_frame_offsets, F, dp,
+                     reinterpret_cast<uint2*>(d_seg_index), seg_blocks, (uint32_t)nidx, c->d_seg_irregular);
+  HIPCHK(c, hipGetLastError());
+  return X3_OK;
+}
+
+extern "C" int x3_seg_index_build_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
+                                      uint64_t n_frames, const x3_params* p, uint64_t* d_seg_index, uint32_t seg_blocks) {
+  if (!c || !d_x3 || !d_frame_offsets || !p || !d_seg_index) return X3_ERR_BAD_ARG;
+  if ((reinterpret_cast<uintptr_t>(d_x3) & 3u) || (reinterpret_cast<uintptr_t>(d_frame_offsets) & 7u)) return X3_ERR_BAD_ARG;
+  if (seg_blocks == 0 || (seg_blocks & 3u) || seg_blocks > 3200u || (reinterpret_cast<uintptr_t>(d_seg_index) & 7u))
+    return X3_ERR_BAD_ARG;
+  if (n_frames == 0 || n_frames > 0x7FFFFFFFull) return X3_ERR_BAD_ARG;
+  X3DevParams dp;
+  const uint64_t spf = spf_of(p);
+  int rc = derive(p, spf > 0xFFFFFFFFull ? 0 : spf, &dp);
+  if (rc) return rc;
+  if (dp.block_len == 0 || dp.blocks_per_frame == 0) return X3_ERR_BAD_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  return seg_index_launch(c, d_x3, x3_len, d_frame_offsets, n_frames, dp, d_seg_index, seg_blocks);
+}
+
+// ------------------------------------------------------------------------------------------------
 // BATCHES OF STREAMS (include/x3hip.h; x3_streams_kernel.h)
 // ------------------------------------------------------------------------------------------------
 #include "x3_streams_kernel.h"
@@ -1521,7 +1554,7 @@ static int corpus_record(x3_ctx* c, x3_corpus* k, const X3DevParams& dp, uint32_
 }
 
 static int corpus_build_impl(x3_ctx* c, x3_corpus* k, const uint64_t* offsets, const uint64_t* lengths, uint64_t phantom,
-                             uint32_t seg_blocks) {
+                             uint32_t seg_blocks, bool index_walk) {
   const uint64_t n = k->n;
   int rc;
   X3DevParams dp;
@@ -1625,8 +1658,17 @@ static int corpus_build_impl(x3_ctx* c, x3_corpus* k, const uint64_t* offsets, c
   HIPCHK(c, hipMemcpyAsync(k->ent.data(), k->d_ent, sizeof(x3_corpus_entry) * n, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(&k->total, k->d_so + F, 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  // ---- 3. the segment index, where the parameters route to the decoder that records it
-  if (seg_blocks && F) {
+  // ---- 3. the segment index: by one walk over the whole frame table for any parameters (X3_CORPUS_INDEX_WALK), or by
+  // the recording decode where the parameters route to the decoder that records it
+  if (seg_blocks && F && index_walk) {
+    const uint64_t nidx = ((uint64_t)dp.blocks_per_frame + seg_blocks - 1) / seg_blocks;
+    if (nidx >= 2) {
+      HIPCHK(c, hipMalloc(&k->d_index, 8 * (1 + F * (nidx - 1))));
+      if ((rc = seg_index_launch(c, k->d_x3, k->x3_len, k->d_frame_off, F, dp, k->d_index, seg_blocks))) return rc;
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      k->seg_blocks = seg_blocks;
+    }
+  } else if (seg_blocks && F) {
     const uint64_t nidx = ((uint64_t)dp.blocks_per_frame + seg_blocks - 1) / seg_blocks;
     const bool records = nidx >= 2 &&
                          decode_route(dp, X3Geom{0, 0, 1, F}, (const int16_t*)nullptr, true, true, 2, c->opt).kernel == X3_DEC_SPLIT;
@@ -1643,7 +1685,7 @@ extern "C" int x3_corpus_build(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, 
                                uint64_t n, uint32_t flags, const x3_params* p, uint32_t seg_blocks, x3_corpus** out) {
   if (out) *out = nullptr;
   if (!c || !offsets || !lengths || !p || !out || (!d_x3 && x3_len)) return X3_ERR_BAD_ARG;
-  if (n == 0 || n > 0xFFFFFFF0ull || (flags & ~X3_STREAMS_ARCHIVE_FRAMES)) return X3_ERR_BAD_ARG;
+  if (n == 0 || n > 0xFFFFFFF0ull || (flags & ~(X3_STREAMS_ARCHIVE_FRAMES | X3_CORPUS_INDEX_WALK))) return X3_ERR_BAD_ARG;
   if (reinterpret_cast<uintptr_t>(d_x3) & 3u) return X3_ERR_BAD_ARG;
   if (x3_params_validate(p) != X3_OK) return X3_ERR_BAD_ARG;
   if (p->block_len == 0 || p->blocks_per_frame == 0 || spf_of(p) > 0xFFFFFFFFull) return X3_ERR_BAD_ARG;   // (windows refuse them)
@@ -1663,7 +1705,8 @@ extern "C" int x3_corpus_build(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, 
   k->p = *p;
   c->decode_pending = false;
   c->last_corpus_slices = 0;
-  const int rc = corpus_build_impl(c, k, offsets, lengths, (flags & X3_STREAMS_ARCHIVE_FRAMES) ? 8 : 0, seg_blocks);
+  const int rc = corpus_build_impl(c, k, offsets, lengths, (flags & X3_STREAMS_ARCHIVE_FRAMES) ? 8 : 0, seg_blocks,
+                                   (flags & X3_CORPUS_INDEX_WALK) != 0);
   if (rc) {
     (void)hipStreamSynchronize(c->stream);   // (nothing of the build may still run when its buffers go)
     x3_corpus_destroy(k);

@@ -135,6 +135,7 @@ struct x3_ctx {
   uint32_t dec_epoch = 1;
   uint32_t enc_log_epoch = 0;          // launches of the wave encoder (its launch-log entries are indexed by it)
   uint16_t* d_crc = nullptr;
+  unsigned long long* d_seg_irregular = nullptr;   // x3_seg_index_kernel's counter: frames whose walk stopped early (option)
   // pinned mirrors
   int* h_status = nullptr;
   unsigned long long* h_stats = nullptr;  // 6 stats + end_pos

@@ -687,6 +687,32 @@ inline X3Error decode(Context& ctx, const EncodedStream& s, const Parameters& pa
   return static_cast<X3Error>(st);
 }
 
+// The segment index of a stream somebody else wrote (x3_seg_index_build_dev): a walk that stores no sample, for any block
+// length, frame length and code set.  d_frame_offsets: n_frames byte offsets into d_x3.  *out stays empty where seg_blocks
+// leaves a frame one stretch.  Asynchronous; the index is only ever a hint and serves the window paths.
+inline X3Error build_seg_index(Context& ctx, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
+                               uint64_t n_frames, const Parameters& params, uint32_t seg_blocks, Buffer* out) {
+  if (!out) return X3Error::BadArg;
+  const x3_params c = params.c_params();
+  const uint64_t n_idx = seg_blocks ? x3_seg_index_entries(n_frames, &c, seg_blocks) : 0;
+  *out = Buffer();
+  if (!n_idx) return X3Error::Ok;
+  Buffer idx(ctx, 8 * n_idx);
+  if (!idx.ok()) return X3Error::Hip;
+  const int rc = x3_seg_index_build_dev(ctx.raw(), d_x3, x3_len, d_frame_offsets, n_frames, &c, idx.as<uint64_t>(), seg_blocks);
+  if (rc == X3_OK) *out = std::move(idx);
+  return static_cast<X3Error>(rc);
+}
+// ... for a stream that has none (another encoder's, a block length the encoder does not index): decode_windows then
+// decodes by it
+inline X3Error index_by_walk(Context& ctx, EncodedStream* s, const Parameters& params, uint32_t seg_blocks) {
+  if (!s || !s->bytes.ok() || !s->frame_offsets.ok()) return X3Error::BadArg;
+  const X3Error rc = build_seg_index(ctx, s->bytes.as<uint8_t>(), s->len, s->frame_offsets.as<uint64_t>(), s->n_frames, params,
+                                     seg_blocks, &s->seg_index);
+  s->seg_blocks = rc == X3Error::Ok && s->seg_index.ok() ? seg_blocks : 0;
+  return rc;
+}
+
 // Random access (x3_decode_windows_dev): n_windows windows of window_len samples, window w = positions [d_starts[w], d_starts[w] +
 // window_len) of the stream, as rows of d_out (X3_WINDOW_I16 / X3_WINDOW_F32); d_status[w] = 0 or the first failing covering
 // frame's status.  The stream's sample offsets are made once (sample_offsets); the segment index, where the stream has one,
@@ -754,12 +780,16 @@ class Corpus {
     return *this;
   }
   ~Corpus() { reset(); }
-  // Synchronous.  seg_blocks: 0 = no segment index (it is only ever a hint).
+  // Synchronous.  seg_blocks: 0 = no segment index (it is only ever a hint).  index_walk: the index by
+  // x3_seg_index_build_dev (X3_CORPUS_INDEX_WALK) -- for every parameter set, where the default records one at block length
+  // 20 and the default codes only.
   X3Error build(Context& ctx, const uint8_t* d_x3, uint64_t x3_len, const std::vector<uint64_t>& offsets,
-                const std::vector<uint64_t>& lengths, uint32_t flags, const Parameters& params, uint32_t seg_blocks = 32) {
+                const std::vector<uint64_t>& lengths, uint32_t flags, const Parameters& params, uint32_t seg_blocks = 32,
+                bool index_walk = false) {
     if (offsets.size() != lengths.size()) return X3Error::BadArg;
     reset();
     const x3_params c = params.c_params();
+    if (index_walk) flags |= X3_CORPUS_INDEX_WALK;
     return static_cast<X3Error>(x3_corpus_build(ctx.raw(), d_x3, x3_len, offsets.data(), lengths.data(), offsets.size(), flags,
                                                 &c, seg_blocks, &raw_));
   }

@@ -140,6 +140,8 @@ pub mod ffi {
                                  batch: *const x3_batch, d_wav_offsets: *const u64, p: *const x3_params, d_wav: *mut i16,
                                  wav_cap: u64, d_status: *mut i32, d_seg_index: *mut u64, seg_blocks: u32, record: c_int) -> c_int;
         pub fn x3_decode_result(ctx: *mut x3_ctx, first_bad: *mut u64, first_bad_status: *mut c_int, samples_before: *mut u64) -> c_int;
+        pub fn x3_seg_index_build_dev(ctx: *mut x3_ctx, d_x3: *const u8, x3_len: u64, d_frame_offsets: *const u64, n_frames: u64,
+                                      p: *const x3_params, d_seg_index: *mut u64, seg_blocks: u32) -> c_int;
         pub fn x3_sample_offsets_dev(ctx: *mut x3_ctx, d_x3: *const u8, x3_len: u64, d_frame_offsets: *const u64, n_frames: u64,
                                      d_sample_offsets: *mut u64) -> c_int;
         pub fn x3_decode_windows_dev(ctx: *mut x3_ctx, d_x3: *const u8, x3_len: u64, d_frame_offsets: *const u64,
@@ -1186,6 +1188,36 @@ pub mod device {
         Ok(before as usize)
     }
 
+    /// The segment index of a stream somebody else wrote (`x3_seg_index_build_dev`; not in the reference crate): a walk
+    /// that stores no sample, for any block length, frame length and code set.  `d_frame_offsets`: `n_frames` byte offsets
+    /// into `d_x3`.  -> the index (`None` where `seg_blocks` leaves a frame one stretch); asynchronous, it is only ever a
+    /// hint and is for the window paths (`decode_windows`, `Corpus`).
+    pub fn build_seg_index<'g>(gpu: &'g Gpu, d_x3: &Buffer<'g>, x3_len: usize, d_frame_offsets: &Buffer<'g>, n_frames: usize,
+                               params: &x3::Parameters, seg_blocks: u32) -> error::Result<Option<Buffer<'g>>> {
+        if x3_len > d_x3.len() || d_frame_offsets.len() < 8 * n_frames {
+            return Err(X3Error::BadArg);
+        }
+        let p = params.c()?;
+        let n_idx = if seg_blocks != 0 { unsafe { ffi::x3_seg_index_entries(n_frames as u64, &p, seg_blocks) } as usize } else { 0 };
+        if n_idx == 0 {
+            return Ok(None);
+        }
+        let idx = Buffer::new(gpu, 8 * n_idx)?;
+        error::check(unsafe {
+            ffi::x3_seg_index_build_dev(gpu.raw(), d_x3.as_ptr::<u8>(), x3_len as u64, d_frame_offsets.as_ptr::<u64>(),
+                                        n_frames as u64, &p, idx.as_ptr::<u64>(), seg_blocks)
+        })?;
+        Ok(Some(idx))
+    }
+
+    /// Give a stream that has no segment index (another encoder's, a block length the encoder does not index) one by a walk;
+    /// `decode_windows` then decodes by it.
+    pub fn index_by_walk<'g>(gpu: &'g Gpu, s: &mut EncodedStream<'g>, params: &x3::Parameters, seg_blocks: u32) -> error::Result<()> {
+        s.seg_index = build_seg_index(gpu, &s.bytes, s.len, &s.frame_offsets, s.n_frames, params, seg_blocks)?;
+        s.seg_blocks = if s.seg_index.is_some() { seg_blocks } else { 0 };
+        Ok(())
+    }
+
     /// output formats of `decode_windows`: int16 samples, or float32 = s / 32768 (exact)
     pub const WINDOW_I16: i32 = 0;
     pub const WINDOW_F32: i32 = 1;
@@ -1227,6 +1259,9 @@ pub mod device {
 
     /// `decode_streams` flag: the entries are the frame part of .x3a archives (walked with the reader's 8 phantom bytes)
     pub const STREAMS_ARCHIVE_FRAMES: u32 = 1;
+    /// `Corpus::build` flag: the segment index by `x3_seg_index_build_dev` -- for every parameter set, not only where a
+    /// decoder records one (block length 20, the default codes); `decode_streams` refuses it
+    pub const CORPUS_INDEX_WALK: u32 = 0x100;
 
     /// A batch of independent streams (`x3_decode_streams_dev`; not in the reference crate, which reads one file): entry s =
     /// bytes `[offsets[s], offsets[s] + lengths[s])` of `d_x3`, decoded into row s of `d_out` (`offsets.len()` rows of
@@ -1263,7 +1298,8 @@ pub mod device {
     }
 
     impl<'g> Corpus<'g> {
-        /// Synchronous.  `seg_blocks`: 0 = no segment index (32 is the usual choice); it is only ever a hint.
+        /// Synchronous.  `seg_blocks`: 0 = no segment index (32 is the usual choice); it is only ever a hint.  `flags`: 0,
+        /// `STREAMS_ARCHIVE_FRAMES`, `CORPUS_INDEX_WALK` or both.
         #[allow(clippy::too_many_arguments)]
         pub fn build(gpu: &'g Gpu, d_x3: &'g Buffer<'g>, x3_len: usize, offsets: &[u64], lengths: &[u64], flags: u32,
                      params: &x3::Parameters, seg_blocks: u32) -> error::Result<Corpus<'g>> {

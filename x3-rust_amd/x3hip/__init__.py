@@ -47,7 +47,7 @@ SYMBOLS = [
     "x3_reader_open", "x3_reader_open_mem", "x3_reader_spec", "x3_reader_next_frame", "x3_reader_frame_errors",
     "x3_reader_position", "x3_reader_close",
     "x3_encode_dev", "x3_encode_frames_dev", "x3_encode_result", "x3_decode_dev", "x3_decode_result", "x3_index_dev", "x3_decode_stream_dev",
-    "x3_seg_index_entries", "x3_decode_dev_seg", "x3_encode_dev_seg", "x3_place_buffers",
+    "x3_seg_index_entries", "x3_decode_dev_seg", "x3_encode_dev_seg", "x3_seg_index_build_dev", "x3_place_buffers",
     "x3_graph_begin", "x3_graph_end", "x3_graph_launch", "x3_graph_destroy",
     "x3_synth", "x3_synth_dev", "x3_dev_alloc", "x3_dev_free", "x3_dev_upload", "x3_dev_download",
     "x3_shard_unique_id", "x3_shard_create", "x3_shard_destroy", "x3_shard_rank", "x3_shard_world",
@@ -68,6 +68,7 @@ TUNE_CANDIDATES, TUNE_DEFAULT_INDEX, TUNE_DEFAULT_SPF = 2184, 1188, 10000   # in
 
 WINDOW_I16, WINDOW_F32 = 0, 1   # x3_decode_windows_dev output formats
 STREAMS_ARCHIVE_FRAMES = 1       # x3_decode_streams_dev: entries are the frame part of .x3a archives
+CORPUS_INDEX_WALK = 0x100        # x3_corpus_build: the segment index by x3_seg_index_build_dev (any parameters)
 
 
 class StreamResult(C.Structure):
@@ -208,6 +209,7 @@ def lib():
     L.x3_graph_destroy.restype = None
     L.x3_seg_index_entries.argtypes = [u64, PP, u32]
     L.x3_seg_index_entries.restype = u64
+    L.x3_seg_index_build_dev.argtypes = [vp, vp, u64, vp, u64, PP, vp, u32]
     L.x3_decode_dev_seg.argtypes = [vp, vp, u64, vp, u64, C.POINTER(Batch), vp, PP, vp, u64, vp, vp, u32, i32]
     L.x3_index_dev.argtypes = [vp, vp, u64, u64, vp, vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(i32)]
     L.x3_decode_stream_dev.argtypes = [vp, vp, u64, PP, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
@@ -859,6 +861,12 @@ class Context:
         return lib().x3_decode_dev_seg(self._h, d_x3, x3_len, d_frame_offsets, n_frames, b, d_wav_offsets,
                                        C.byref(params), d_wav, wav_cap, d_status, d_seg_index, seg_blocks, 1 if record else 0)
 
+    def seg_index_build_dev(self, d_x3, x3_len, d_frame_offsets, n_frames, params, d_seg_index, seg_blocks):
+        """x3_seg_index_build_dev: the segment index of any stream by a walk that stores no sample (asynchronous; every
+        word of d_seg_index is written).  get_option("last_seg_index_irregular"): frames whose walk stopped early"""
+        return lib().x3_seg_index_build_dev(self._h, d_x3, x3_len, d_frame_offsets, n_frames, C.byref(params), d_seg_index,
+                                            seg_blocks)
+
     # ---- HIP graphs (x3_graph_*): record the device calls made between graph_begin() and graph_end(), replay them
     def graph_begin(self):
         rc = lib().x3_graph_begin(self._h)
@@ -999,10 +1007,15 @@ class WindowSource:
 
     `stream`: host bytes (uploaded once) or (d_x3, x3_len) of a device stream.  Without `frame_offsets` (a device pointer to
     n_frames + 1 byte offsets, with `n_frames`) the frames are found by x3_index_dev.  The sample offsets come from
-    x3_sample_offsets_dev.  Without `seg_index` one is recorded once by a decode with x3_decode_dev_seg(record=1); it is
+    x3_sample_offsets_dev.  Without `seg_index` one is made once: index="decode" records it by a decode with
+    x3_decode_dev_seg(record=1) (block length 20 and the default codes only; it decodes the whole stream into a buffer
+    that is thrown away), index="walk" builds it with x3_seg_index_build_dev (any parameters, no sample buffer).  It is
     only ever a hint (seg_blocks=0: no index, frames decode whole)."""
 
-    def __init__(self, ctx, stream, params=None, seg_blocks=32, frame_offsets=None, n_frames=None, seg_index=None):
+    def __init__(self, ctx, stream, params=None, seg_blocks=32, frame_offsets=None, n_frames=None, seg_index=None,
+                 index="decode"):
+        if index not in ("decode", "walk"):
+            raise ValueError('index: "decode" or "walk"')
         self.ctx, self.params, self.seg_blocks = ctx, params or Params.default(), seg_blocks
         self._own = []
         if isinstance(stream, tuple):
@@ -1033,6 +1046,12 @@ class WindowSource:
         if seg_blocks and seg_index is None and lib().x3_seg_index_entries(self.n_frames, C.byref(self.params), seg_blocks):
             ne = lib().x3_seg_index_entries(self.n_frames, C.byref(self.params), seg_blocks)
             self.d_seg_index = self._alloc(8 * ne)
+            if index == "walk":
+                rc = ctx.seg_index_build_dev(self.d_x3, self.x3_len, self.d_frame_offsets, self.n_frames, self.params,
+                                             self.d_seg_index, seg_blocks)
+                if rc:
+                    raise X3Error(rc, "x3_seg_index_build_dev: " + ctx.last_error())
+                return
             ctx.upload(self.d_seg_index, np.zeros(ne, dtype=np.uint64))
             d_back = self._alloc(2 * max(self.total, 1))
             # (the three-wave decoder records the index; it takes caller offsets that are multiples of four samples)
@@ -1187,17 +1206,21 @@ class Corpus:
 
     `stream`: host bytes (uploaded once, owned) or (d_x3, x3_len) of a device buffer the caller keeps alive.  `offsets` /
     `lengths`: the entries, as in Context.decode_streams_dev.  flags: 0 or STREAMS_ARCHIVE_FRAMES.  seg_blocks: the
-    segment index (0: none; it is only ever a hint).  `.entries`: the entry table (CORPUS_ENTRY_DTYPE)."""
+    segment index (0: none; it is only ever a hint).  index: "decode" = recorded by a decode of the corpus (block length
+    20 and the default codes; none elsewhere), "walk" = built by x3_seg_index_build_dev for any parameters
+    (CORPUS_INDEX_WALK).  `.entries`: the entry table (CORPUS_ENTRY_DTYPE)."""
 
-    def __init__(self, ctx, stream, offsets, lengths, params=None, flags=0, seg_blocks=32):
+    def __init__(self, ctx, stream, offsets, lengths, params=None, flags=0, seg_blocks=32, index="decode"):
         self.ctx, self.params, self._h, self._own = ctx, params or Params.default(), None, []
+        if index not in ("decode", "walk"):
+            raise ValueError('index: "decode" or "walk"')
         offs = np.ascontiguousarray(offsets, dtype=np.uint64)
         lens = np.ascontiguousarray(lengths, dtype=np.uint64)
         if offs.ndim != 1 or offs.size != lens.size:
             raise ValueError("offsets and lengths must be 1-D and of one length")
         if offs.size == 0 or offs.size > 0xFFFFFFF0:
             raise ValueError("a corpus holds 1 .. 0xFFFFFFF0 entries")
-        if flags & ~STREAMS_ARCHIVE_FRAMES:
+        if flags & ~(STREAMS_ARCHIVE_FRAMES | CORPUS_INDEX_WALK):
             raise ValueError("unknown flag")
         if seg_blocks < 0 or seg_blocks % 4 or seg_blocks > 3200:
             raise ValueError("seg_blocks: 0, or a multiple of 4 up to 3200")
@@ -1213,6 +1236,8 @@ class Corpus:
             self._own.append(self.d_x3)
             ctx.upload(self.d_x3, b)
         h = C.c_void_p(0)
+        if index == "walk":
+            flags |= CORPUS_INDEX_WALK
         rc = lib().x3_corpus_build(ctx._h, self.d_x3, self.x3_len, offs.ctypes.data, lens.ctypes.data, offs.size, flags,
                                    C.byref(self.params), seg_blocks, C.byref(h))
         if rc:
@@ -1229,7 +1254,7 @@ class Corpus:
         self.d_seg_index, self.seg_index_words = d_idx.value, nw.value   # (device memory the corpus owns; None, 0: no index)
 
     @classmethod
-    def from_archives(cls, ctx, archives, seg_blocks=32):
+    def from_archives(cls, ctx, archives, seg_blocks=32, index="decode"):
         """A corpus of the frame parts of .x3a archives (bytes-like objects or paths), one entry per archive in the input
         order, buffer built as decode_archives builds it.  ValueError for archives of more than one parameter set or with
         a header that does not parse.  `.rates`: the archives' sample rates."""
@@ -1244,7 +1269,8 @@ class Corpus:
         d_x3 = ctx.alloc(buf.size)
         try:
             ctx.upload(d_x3, buf)
-            self = cls(ctx, (d_x3, pos), offs, lens, params=p, flags=STREAMS_ARCHIVE_FRAMES, seg_blocks=seg_blocks)
+            self = cls(ctx, (d_x3, pos), offs, lens, params=p, flags=STREAMS_ARCHIVE_FRAMES, seg_blocks=seg_blocks,
+                       index=index)
         except BaseException:
             ctx.free(d_x3)
             raise
