@@ -442,7 +442,10 @@ int x3_encode_dev(x3_ctx* ctx, const int16_t* d_wav, const x3_batch* batch, cons
  * DIFFERENT lengths is such a list (each clip cut into frames as encoder::encode cuts it, encoder.rs:61-73: full frames and
  * a last short one), one launch set for all of them instead of one per clip; d_frame_offsets[F + 1] then gives every clip's
  * byte range.  src_offsets / src_samples are HOST arrays (checked and copied here); offsets that are all even take the
- * single-pass encoders.  Asynchronous like x3_encode_dev; results via x3_encode_result(). */
+ * single-pass encoders.  Asynchronous like x3_encode_dev; results via x3_encode_result().  One exception to "does not
+ * synchronise": the table travels through ONE pinned block per context, so a call waits on the host until the table copy
+ * of the context's previous x3_encode_frames_dev / x3_decode_streams_dev has run -- it waits out whatever stands in front
+ * of that copy in the stream, nothing behind it. */
 int x3_encode_frames_dev(x3_ctx* ctx, const int16_t* d_wav, const uint64_t* src_offsets, const uint32_t* src_samples,
                          uint64_t n_frames, const x3_params* p, uint8_t* d_out, uint64_t out_cap, uint64_t start_pos,
                          uint64_t* d_frame_offsets);
@@ -625,9 +628,11 @@ int x3_decode_windows_result(x3_ctx* ctx, uint64_t* n_bad, uint64_t* first_bad, 
  * decoded into its row there; read-only options "streams_general_walks" / "last_streams_general_walks" count such entries.
  *   Asynchronous on the context's stream; d_out and d_results are final once x3_decode_streams_result has returned (d_x3
  * must stay untouched until then).  Replaces the pending state of an earlier x3_decode_dev, as x3_decode_stream_dev does.
- * offsets / lengths are HOST arrays, checked and copied here.  X3_ERR_BAD_ARG with nothing enqueued for n_streams == 0,
- * row_len == 0, an unknown out_format or flag, d_x3 not on a 4-byte boundary, d_out not on its sample size's boundary,
- * d_results not on an 8-byte one, an entry outside [0, x3_len), and parameters x3_params_validate refuses. */
+ * offsets / lengths are HOST arrays, checked and copied here (through the context's one pinned block: a call waits on the
+ * host for the table copy of the previous x3_decode_streams_dev / x3_encode_frames_dev, as described there).
+ * X3_ERR_BAD_ARG with nothing enqueued for n_streams == 0, row_len == 0, an unknown out_format or flag, d_x3 not on a
+ * 4-byte boundary, d_out not on its sample size's boundary, d_results not on an 8-byte one, an entry outside [0, x3_len),
+ * and parameters x3_params_validate refuses. */
 #define X3_STREAMS_ARCHIVE_FRAMES 1u   /* entries are the frame part of .x3a archives: walked as X3aReader walks them */
 #define X3_CORPUS_INDEX_WALK 0x100u    /* x3_corpus_build only (below): the segment index by x3_seg_index_build_dev */
 typedef struct x3_stream_result {
