@@ -145,7 +145,7 @@ extern "C" int x3_decode_block(x3_bitreader* b, int16_t* wav, uint32_t n, int16_
   if (!b || !wav || !last_wav || !p || n > 60) return X3_ERR_BAD_ARG;
   x3_ctx* c = b->c;
   X3DevParams dp;
-  int rc = derive(p, spf_of(p) > 0xFFFFFFFFull ? 0 : spf_of(p), &dp);
+  int rc = derive_params(p, &dp);
   if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   b->h_out[1] = (uint32_t)(uint16_t)*last_wav;

@@ -13,6 +13,25 @@
 // ------------------------------------------------------------------------------------------------
 // decode
 // ------------------------------------------------------------------------------------------------
+// The kernels' view of the caller's parameters.  (Samples per frame beyond 32 bits: 0 -- the entry points that need a
+// frame length refuse that, the others never use it.)
+static int derive_params(const x3_params* p, X3DevParams* d) {
+  const uint64_t spf = spf_of(p);
+  return derive(p, spf > 0xFFFFFFFFull ? 0 : spf, d);
+}
+
+// The SEGMENT INDEX (include/x3hip.h): the stretches of `seg_blocks` blocks that the index tells apart in a frame.  Its
+// pitch follows the PARAMETERS -- the blocks of a full frame -- not the call: x3_seg_index_entries, the encoder and every
+// launch that reads or writes an index go by this whatever the clips' lengths are.
+static uint64_t seg_stretches(uint64_t blocks_per_frame, uint32_t seg_blocks) {
+  return (blocks_per_frame + seg_blocks - 1) / seg_blocks;
+}
+
+// ... and what the entry points take for one: stretches of whole groups of four blocks, an 8-byte aligned table
+static bool seg_index_args_ok(const uint64_t* d_seg_index, uint32_t seg_blocks) {
+  return seg_blocks != 0 && (seg_blocks & 3u) == 0 && seg_blocks <= 3200u && (reinterpret_cast<uintptr_t>(d_seg_index) & 7u) == 0;
+}
+
 // The decoder of a call (the inputs: x3_internal.h).
 DecodeRoute decode_route(const X3DevParams& dp, const X3Geom& g, const int16_t* d_wav, bool offsets, bool x4, int seg_mode,
                          const X3Opts& o) {
@@ -57,7 +76,7 @@ int decode_dev_impl(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint6
   if (F == 0 || F > 0x7FFFFFFFull) return X3_ERR_BAD_ARG;
   const uint64_t spf = spf_of(p);
   X3DevParams dp;
-  int rc = derive(p, spf > 0xFFFFFFFFull ? 0 : spf, &dp);
+  int rc = derive_params(p, &dp);
   if (rc) return rc;
   X3Geom g{0, 0, 1, F};
   if (!d_wav_offsets) {
@@ -151,10 +170,7 @@ int decode_dev_impl(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint6
       X3SegArgs sg{nullptr, nullptr, 0u, 1u, 0u, 1u};
       uint64_t groups = (F + 63) / 64;
       if (by_seg) {
-        // (the index's pitch follows the PARAMETERS -- blocks of a full frame -- not the call: x3_seg_index_entries, the
-        // encoder and this launch must agree on it whatever the clips' lengths are)
-        const uint64_t bpf = (dp.spf + X3S_BL - 1) / X3S_BL;
-        const uint64_t nidx = (bpf + seg->seg_blocks - 1) / seg->seg_blocks;   // stretches the index can tell apart
+        const uint64_t nidx = seg_stretches((dp.spf + X3S_BL - 1) / X3S_BL, seg->seg_blocks);
         if (nidx >= 2) {
           sg.pitch = (uint32_t)(nidx - 1);
           if (seg->mode == 1) {
@@ -193,7 +209,7 @@ int decode_dev_impl(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint6
                          d_frame_offsets, F, g, d_wav_offsets, dp, d_wav, wav_cap, d_status,
                          (X3FrameMeta*)c->dec_meta.p);
     } else {
-      hipLaunchKernelGGL((x3_decode_lanes_kernel<false, 64>), dim3((unsigned)((F + 63) / 64)), dim3(64), 0, dec_stream,
+      hipLaunchKernelGGL(x3_decode_lanes_kernel, dim3((unsigned)((F + 63) / 64)), dim3(64), 0, dec_stream,
                          d_x3, x3_len, d_frame_offsets, F, g, d_wav_offsets, dp, d_wav, wav_cap, d_status,
                          (X3FrameMeta*)c->dec_meta.p);
     }
@@ -236,7 +252,7 @@ extern "C" int x3_decode_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, co
 // leaves it in d_seg_index for the next decode of the same stream
 extern "C" uint64_t x3_seg_index_entries(uint64_t n_frames, const x3_params* p, uint32_t seg_blocks) {
   if (!p || seg_blocks == 0 || p->blocks_per_frame == 0) return 0;
-  const uint64_t nseg = ((uint64_t)p->blocks_per_frame + seg_blocks - 1) / seg_blocks;
+  const uint64_t nseg = seg_stretches(p->blocks_per_frame, seg_blocks);
   return nseg >= 2 ? 1 + n_frames * (nseg - 1) : 0;   // (a header word, then nseg - 1 entries per frame)
 }
 
@@ -245,8 +261,7 @@ extern "C" int x3_decode_dev_seg(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len
                                  const x3_params* p, int16_t* d_wav, uint64_t wav_cap, int32_t* d_status,
                                  uint64_t* d_seg_index, uint32_t seg_blocks, int record) {
   if (!c || !d_x3 || !d_frame_offsets || !p || !d_wav) return X3_ERR_BAD_ARG;
-  if (d_seg_index && (seg_blocks == 0 || (seg_blocks & 3u) || seg_blocks > 3200u || (reinterpret_cast<uintptr_t>(d_seg_index) & 7u)))
-    return X3_ERR_BAD_ARG;
+  if (d_seg_index && !seg_index_args_ok(d_seg_index, seg_blocks)) return X3_ERR_BAD_ARG;
   HIPCHK(c, hipSetDevice(c->device));
   const X3SegSpec seg{d_seg_index, seg_blocks, d_seg_index ? (record ? 2 : 1) : 0};
   return decode_dev_impl(c, d_x3, x3_len, d_frame_offsets, n_frames, batch, d_wav_offsets, p, d_wav, wav_cap, d_status,
@@ -489,7 +504,7 @@ int decode_stream_dev_impl(x3_ctx* c, const uint8_t* d_x3, uint64_t len, uint64_
     X3DevParams dq;
     const bool try_one = !own_out && !c->opt.index_no_fast && !c->opt.two_trips && spf_of(p) >= 2048 && len >= 22 &&
                          (reinterpret_cast<uintptr_t>(d_x3) & 3u) == 0 &&
-                         derive(p, spf_of(p) > 0xFFFFFFFFull ? 0 : spf_of(p), &dq) == X3_OK &&
+                         derive_params(p, &dq) == X3_OK &&
                          decode_route(dq, X3Geom{0, 0, 1, bound}, d_wav, true, true, 0, c->opt).device_count;
     if (try_one) {
       if ((rc = ensure(c, c->frame_off, (bound + 1) * sizeof(uint64_t)))) return rc;
@@ -523,14 +538,7 @@ int decode_stream_dev_impl(x3_ctx* c, const uint8_t* d_x3, uint64_t len, uint64_
             }
             if (n_out) *n_out = before;
             if (frames_ok) *frames_ok = first_bad;
-            if (first_bad < F1) {
-              if (bad_status == X3_ERR_OUT_OF_BOUNDS_INVERSE || bad_status == X3_ERR_FRAME_DECODE_INVALID_BPF) {
-                if (frame_errors) *frame_errors = 1;
-                return X3_OK;
-              }
-              return bad_status;
-            }
-            return r.terminal;
+            return walk_result(F1, first_bad, bad_status, r.terminal, frame_errors);
           }
         } else if (rc != X3_ERR_BAD_ARG) {
           return rc;
@@ -567,14 +575,7 @@ int decode_stream_dev_impl(x3_ctx* c, const uint8_t* d_x3, uint64_t len, uint64_
   if ((rc = x3_decode_result(c, &first_bad, &bad_status, &before))) return rc;
   if (n_out) *n_out = before;
   if (frames_ok) *frames_ok = first_bad;
-  if (first_bad < F) {
-    if (bad_status == X3_ERR_OUT_OF_BOUNDS_INVERSE || bad_status == X3_ERR_FRAME_DECODE_INVALID_BPF) {
-      if (frame_errors) *frame_errors = 1;  // counted, the walk ends quietly (decodefile.rs:129-135)
-      return X3_OK;
-    }
-    return bad_status;
-  }
-  return terminal;
+  return walk_result(F, first_bad, bad_status, terminal, frame_errors);
 }
 
 
@@ -1050,7 +1051,7 @@ static int windows_launch(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const
                           const uint64_t* d_seg_index, uint32_t seg_blocks, uint64_t n_windows, uint32_t window_len,
                           void* d_out, int out_format, int32_t* d_status, Plan plan_step) {
   // the stretches of a frame as the index tells them apart (x3_seg_index_entries); 1 = whole frames
-  const uint64_t nidx = d_seg_index ? ((uint64_t)dp.blocks_per_frame + seg_blocks - 1) / seg_blocks : 1;
+  const uint64_t nidx = d_seg_index ? seg_stretches(dp.blocks_per_frame, seg_blocks) : 1;
   const uint32_t nseg = nidx >= 2 ? (uint32_t)nidx : 1u;
   const uint2* idx = nseg >= 2 ? reinterpret_cast<const uint2*>(d_seg_index) : nullptr;
   // workspace: plans, the two scans, per-frame verdicts, a block of replay scratch per window, the summary, the plan's starts
@@ -1101,12 +1102,11 @@ extern "C" int x3_decode_windows_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3
   if ((reinterpret_cast<uintptr_t>(d_x3) & 3u) || (reinterpret_cast<uintptr_t>(d_frame_offsets) & 7u) ||
       (reinterpret_cast<uintptr_t>(d_sample_offsets) & 7u))
     return X3_ERR_BAD_ARG;
-  if (d_seg_index && (seg_blocks == 0 || (seg_blocks & 3u) || seg_blocks > 3200u || (reinterpret_cast<uintptr_t>(d_seg_index) & 7u)))
-    return X3_ERR_BAD_ARG;
+  if (d_seg_index && !seg_index_args_ok(d_seg_index, seg_blocks)) return X3_ERR_BAD_ARG;
   if (n_frames == 0 || n_frames > 0x7FFFFFFFull) return X3_ERR_BAD_ARG;
   X3DevParams dp;
   const uint64_t spf = spf_of(p);
-  int rc = derive(p, spf > 0xFFFFFFFFull ? 0 : spf, &dp);
+  int rc = derive_params(p, &dp);
   if (rc) return rc;
   if (dp.block_len == 0 || dp.blocks_per_frame == 0) return X3_ERR_BAD_ARG;
   HIPCHK(c, hipSetDevice(c->device));
@@ -1139,7 +1139,7 @@ extern "C" int x3_decode_windows_result(x3_ctx* c, uint64_t* n_bad, uint64_t* fi
 // One launch behind a 8-byte memset of the counter; nothing is allocated, nothing waits, no pending state is touched.
 static int seg_index_launch(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets, uint64_t F,
                             const X3DevParams& dp, uint64_t* d_seg_index, uint32_t seg_blocks) {
-  const uint64_t nidx = ((uint64_t)dp.blocks_per_frame + seg_blocks - 1) / seg_blocks;
+  const uint64_t nidx = seg_stretches(dp.blocks_per_frame, seg_blocks);
   HIPCHK(c, hipMemsetAsync(c->d_seg_irregular, 0, sizeof(unsigned long long), c->stream));
   if (nidx < 2) return X3_OK;   // (x3_seg_index_entries() == 0: frames of one stretch have no index)
   const uint64_t groups = std::min<uint64_t>((F + 63) / 64, (uint64_t)c->n_cus * X3X_WAVES_PER_CU);
@@ -1153,12 +1153,10 @@ extern "C" int x3_seg_index_build_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x
                                       uint64_t n_frames, const x3_params* p, uint64_t* d_seg_index, uint32_t seg_blocks) {
   if (!c || !d_x3 || !d_frame_offsets || !p || !d_seg_index) return X3_ERR_BAD_ARG;
   if ((reinterpret_cast<uintptr_t>(d_x3) & 3u) || (reinterpret_cast<uintptr_t>(d_frame_offsets) & 7u)) return X3_ERR_BAD_ARG;
-  if (seg_blocks == 0 || (seg_blocks & 3u) || seg_blocks > 3200u || (reinterpret_cast<uintptr_t>(d_seg_index) & 7u))
-    return X3_ERR_BAD_ARG;
+  if (!seg_index_args_ok(d_seg_index, seg_blocks)) return X3_ERR_BAD_ARG;
   if (n_frames == 0 || n_frames > 0x7FFFFFFFull) return X3_ERR_BAD_ARG;
   X3DevParams dp;
-  const uint64_t spf = spf_of(p);
-  int rc = derive(p, spf > 0xFFFFFFFFull ? 0 : spf, &dp);
+  int rc = derive_params(p, &dp);
   if (rc) return rc;
   if (dp.block_len == 0 || dp.blocks_per_frame == 0) return X3_ERR_BAD_ARG;
   HIPCHK(c, hipSetDevice(c->device));
@@ -1337,7 +1335,7 @@ extern "C" int x3_decode_streams_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3
   // x3_decode_streams_result.  A decoder that cannot read the count from the device: one wait for it, here.
   X3DevParams dq;
   const uint64_t bound = std::min<uint64_t>(cap, bytes / 1024 + n + 64);
-  const bool dev_count = G && derive(p, spf_of(p) > 0xFFFFFFFFull ? 0 : spf_of(p), &dq) == X3_OK &&
+  const bool dev_count = G && derive_params(p, &dq) == X3_OK &&
                          decode_route(dq, X3Geom{0, 0, 1, bound}, out_format == X3_WINDOW_F32 ? (const int16_t*)c->st_ws.p
                                                                                                 : (const int16_t*)d_out,
                                       true, x4 != 0, 0, c->opt).device_count;
@@ -1523,7 +1521,7 @@ static int corpus_general_walk(x3_ctx* c, const uint8_t* d_x3, uint64_t off, uin
 #define X3K_RECORD_SCRATCH (256ull << 20)   // bytes of samples one slice decodes into
 static int corpus_record(x3_ctx* c, x3_corpus* k, const X3DevParams& dp, uint32_t seg_blocks, CorpusScratch& tmp) {
   const uint64_t F = k->F;
-  const uint64_t nidx = ((uint64_t)dp.blocks_per_frame + seg_blocks - 1) / seg_blocks;
+  const uint64_t nidx = seg_stretches(dp.blocks_per_frame, seg_blocks);
   const uint64_t pitch = ((uint64_t)dp.spf + 3) & ~3ull;
   const uint64_t S = std::min<uint64_t>(F, std::max<uint64_t>(X3K_RECORD_SCRATCH / 2 / pitch, 1));
   int rc;
@@ -1558,7 +1556,7 @@ static int corpus_build_impl(x3_ctx* c, x3_corpus* k, const uint64_t* offsets, c
   const uint64_t n = k->n;
   int rc;
   X3DevParams dp;
-  if ((rc = derive(&k->p, spf_of(&k->p), &dp))) return rc;
+  if ((rc = derive_params(&k->p, &dp))) return rc;
   CorpusScratch tmp;
   std::vector<uint32_t> span_first(n + 1, 0);
   for (uint64_t e = 0; e < n; ++e) span_first[e + 1] = span_first[e] + (uint32_t)((lengths[e] + X3T_SPAN_BYTES - 1) / X3T_SPAN_BYTES);
@@ -1661,7 +1659,7 @@ static int corpus_build_impl(x3_ctx* c, x3_corpus* k, const uint64_t* offsets, c
   // ---- 3. the segment index: by one walk over the whole frame table for any parameters (X3_CORPUS_INDEX_WALK), or by
   // the recording decode where the parameters route to the decoder that records it
   if (seg_blocks && F && index_walk) {
-    const uint64_t nidx = ((uint64_t)dp.blocks_per_frame + seg_blocks - 1) / seg_blocks;
+    const uint64_t nidx = seg_stretches(dp.blocks_per_frame, seg_blocks);
     if (nidx >= 2) {
       HIPCHK(c, hipMalloc(&k->d_index, 8 * (1 + F * (nidx - 1))));
       if ((rc = seg_index_launch(c, k->d_x3, k->x3_len, k->d_frame_off, F, dp, k->d_index, seg_blocks))) return rc;
@@ -1669,7 +1667,7 @@ static int corpus_build_impl(x3_ctx* c, x3_corpus* k, const uint64_t* offsets, c
       k->seg_blocks = seg_blocks;
     }
   } else if (seg_blocks && F) {
-    const uint64_t nidx = ((uint64_t)dp.blocks_per_frame + seg_blocks - 1) / seg_blocks;
+    const uint64_t nidx = seg_stretches(dp.blocks_per_frame, seg_blocks);
     const bool records = nidx >= 2 &&
                          decode_route(dp, X3Geom{0, 0, 1, F}, (const int16_t*)nullptr, true, true, 2, c->opt).kernel == X3_DEC_SPLIT;
     if (records) {
@@ -1689,7 +1687,7 @@ extern "C" int x3_corpus_build(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, 
   if (reinterpret_cast<uintptr_t>(d_x3) & 3u) return X3_ERR_BAD_ARG;
   if (x3_params_validate(p) != X3_OK) return X3_ERR_BAD_ARG;
   if (p->block_len == 0 || p->blocks_per_frame == 0 || spf_of(p) > 0xFFFFFFFFull) return X3_ERR_BAD_ARG;   // (windows refuse them)
-  if (seg_blocks && ((seg_blocks & 3u) || seg_blocks > 3200u)) return X3_ERR_BAD_ARG;
+  if (seg_blocks && !seg_index_args_ok(nullptr, seg_blocks)) return X3_ERR_BAD_ARG;   // (0: no index; the table is the corpus's own)
   uint64_t G = 0;
   for (uint64_t e = 0; e < n; ++e) {
     if (offsets[e] > x3_len || lengths[e] > x3_len - offsets[e]) return X3_ERR_BAD_ARG;
@@ -1749,7 +1747,7 @@ extern "C" int x3_corpus_windows_dev(x3_ctx* c, const x3_corpus* k, const uint32
   }
   X3DevParams dp;
   const uint64_t spf = spf_of(&k->p);
-  int rc = derive(&k->p, spf, &dp);
+  int rc = derive_params(&k->p, &dp);
   if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   const uint64_t n_ent = k->n, F = k->F;

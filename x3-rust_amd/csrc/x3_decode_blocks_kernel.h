@@ -208,37 +208,16 @@ x3_decode_blocks_kernel(const uint8_t* __restrict__ x3, uint64_t x3_len, const u
     // ================================================================================ the walker
     __builtin_amdgcn_s_setprio(X3B_WALKER_PRIO);
     const uint64_t f = f0 + lane;
-    bool active = lane < nfr;
-    int32_t st = X3D_OK;
-    uint32_t samples = 0, plen = 2;
-    uint64_t p0 = 0, wo = 0;
-    if (active) {
-      uint32_t pcrc_unused;
-      st = x3_frame_header_check(reinterpret_cast<const uint32_t*>(x3 - (reinterpret_cast<uintptr_t>(x3) & 3u)),
-                                 (x3_len + (reinterpret_cast<uintptr_t>(x3) & 3u) + 3) >> 2,
-                                 x3_len + (reinterpret_cast<uintptr_t>(x3) & 3u),
-                                 frame_off[f] + (reinterpret_cast<uintptr_t>(x3) & 3u), plen, samples, pcrc_unused);
-      meta[f].payload_len = plen;
-      meta[f].samples = samples;
-      p0 = frame_off[f] + 20;
-      if (st != X3D_OK) {
-        active = false;
-      } else if (samples == 0 || plen < 2) {
-        st = X3D_BAD_ARG;
-        active = false;
-      } else {
-        if (wav_off) {
-          wo = wav_off[f];
-        } else {
-          const uint64_t clip = f / g.fpc;
-          wo = clip * g.clip_stride + (f - clip * g.fpc) * (uint64_t)p.spf;
-        }
-        if (wo + samples > wav_cap) {
-          st = X3D_BAD_ARG;
-          active = false;
-        }
-      }
+    // ---- per-lane frame setup (x3_frame_setup: x3_decode_frame.h)
+    const X3FrameSetup fs = x3_frame_setup(x3, x3_len, frame_off, f, lane < nfr, g, wav_off, p, wav_cap);
+    if (lane < nfr) {
+      meta[f].payload_len = fs.plen;
+      meta[f].samples = fs.samples;
     }
+    const bool active = fs.active;
+    int32_t st = fs.st;
+    uint32_t samples = fs.samples, plen = fs.plen;
+    uint64_t p0 = fs.p0, wo = fs.wo;
     if (!active) { p0 = 0; plen = 2; wo = 0; samples = 0; }
     const uint32_t nblk = samples ? (samples - 1u + UNIT - 1u) / UNIT : 0u;   // UNITS of the frame
     const uint64_t rowb = (uint64_t)(uintptr_t)(wav + wo);
@@ -261,25 +240,13 @@ x3_decode_blocks_kernel(const uint8_t* __restrict__ x3, uint64_t x3_len, const u
     uint32_t* const row = ring + lane * X3_DEC_RING_DW;
     const uint32_t row_base = x3_lds_addr(row);
 #define X3B_RING_WORD(j) row[~(j) & 31u]
-    const uint32_t adj = (uint32_t)(reinterpret_cast<uintptr_t>(x3) & 15u);
-    const uint64_t abs_bits = (uint64_t)adj + p0 + 2u;              // the byte behind the first sample
-    const uint64_t abs_last = (uint64_t)adj + p0 + plen - 1u;       // the payload's last byte
-    const uint64_t abs_base = (abs_bits < abs_last ? abs_bits : abs_last) & ~15ull;
-    const uint8_t* __restrict__ const x3b = (x3 - adj) + abs_base;
-    const uint32_t v_bits = (uint32_t)(abs_bits - abs_base);        // first block header (0..16), in bytes from the ring's first chunk
+    // Its origin is the chunk of the byte behind the first sample (x3_ring_origin: x3_decode_frame.h), and it takes the
+    // STREAM as it comes, to its last chunk, as the decoders below do (x3_ring_last_stream_chunk).
+    const X3RingOrigin ro = x3_ring_origin(x3, p0, plen, 2u);
+    const uint8_t* __restrict__ const x3b = ro.x3b;
+    const uint32_t v_bits = ro.v_bits;                              // first block header (0..16), in bytes from the ring's first chunk
     const int32_t v_rel = 16 - 8 * (int32_t)v_bits;                 // payload bit = ring bit + v_rel
-    // The ring takes the STREAM as it comes -- behind the payload the next frame's bytes, up to the stream's last 16-byte
-    // chunk, which repeats from there on -- and the decoders stage the very same bytes (below): a codeword is then parsed
-    // alike by walker and decoders wherever it stands.  (Until the soak of round 6 the walker stopped at the PAYLOAD's last
-    // chunk, as the lane-per-frame kernels do; there parser and valuer share one view.  Here a codeword whose zero run
-    // began in the payload's last bits was parsed on different bits by the two sides, and the frame was not flagged:
-    // tools/r6/repro_overread.py.)  What is read behind the payload still sends the frame to the reference's reader.
-    uint32_t v_last;
-    {
-      const uint64_t lastc_abs = ((uint64_t)adj + x3_len - 1u) & ~15ull;          // (in the coordinates of abs_base)
-      const uint64_t rel = lastc_abs > abs_base ? lastc_abs - abs_base : 0u;
-      v_last = rel > 0xFFFFFFF0ull ? 0xFFFFFFF0u : (uint32_t)rel;
-    }
+    const uint32_t v_last = x3_ring_last_stream_chunk(x3, x3_len, ro.abs_base);
     uint32_t v_next = 0, wr_abs = 0;
     constexpr uint32_t SVC_MAX = 3u * X3B_PERIOD;
     constexpr uint32_t SVC_AHEAD = X3B_AHEAD;

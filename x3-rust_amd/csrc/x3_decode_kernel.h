@@ -29,65 +29,10 @@
 
 #include "x3_device.h"
 #include "x3_decode_replay.h"
-
-#define X3D_STREAM_ENDS_IN_FRAME (-1)  // quiet stop of the walk (decodefile.rs:107-116)
-
-struct X3FrameMeta {
-  uint32_t payload_len;
-  uint32_t samples;
-};
-
-// 4 stream bytes at byte offset `o` of the 4-byte-aligned buffer xw, as a big-endian value;
-// dwords at or beyond n_dw read as zero
-__device__ __forceinline__ uint32_t x3_be32_at(const uint32_t* __restrict__ xw, uint64_t n_dw, uint64_t o) {
-  const uint64_t j = o >> 2;
-  const uint32_t sh = (uint32_t)(o & 3u) * 8u;
-  const uint32_t a = j < n_dw ? x3_bswap32(xw[j]) : 0u;
-  if (sh == 0) return a;
-  const uint32_t b = (j + 1) < n_dw ? x3_bswap32(xw[j + 1]) : 0u;
-  return (a << sh) | (b >> (32u - sh));
-}
+#include "x3_decode_frame.h"   // X3FrameMeta, the header check, the per-frame setup the decoders share
 
 // x^(-8t) mod P for t = 1..3 lives behind the x^n table
 // (X3_XINV8_INDEX: x3_device.h)
-
-// decoder::read_frame_header (decoder.rs:69-118) + the walk's length checks (decodefile.rs:107-121) for
-// the frame at byte offset `off`; same check order as the reference.
-// ... on the five big-endian words of the header
-// hc = CRC-16 of the first 16 header bytes, computed by the caller (table-free or from LDS tables)
-__device__ __forceinline__ int32_t x3_frame_header_check_words(uint32_t h0, uint32_t h1, uint32_t h4, uint32_t hc,
-                                                               uint64_t x3_len, uint64_t off, uint32_t& plen,
-                                                               uint32_t& samples, uint32_t& pcrc, uint32_t n_ch = 1u) {
-  samples = h1 >> 16;
-  plen = h1 & 0xFFFFu;
-  pcrc = h4 & 0xFFFFu;
-  if ((h4 >> 16) != hc) return X3D_FRAME_HEADER_INVALID_HEADER_CRC;
-  if ((h0 >> 16) != 0x7833u) return X3D_FRAME_HEADER_INVALID_KEY;
-  // (n_ch > 1: the multi-channel extension -- the frame must say exactly n_ch; else the reference's test)
-  if (n_ch == 1u ? (h0 & 0xFFu) > 1u : (h0 & 0xFFu) != n_ch) return X3D_MORE_THAN_ONE_CHANNEL;
-  if (plen >= 0x7fe0u) return X3D_FRAME_LENGTH;
-  if (off + 20 + plen > x3_len) return X3D_STREAM_ENDS_IN_FRAME;   // decodefile.rs:114-116
-  if (plen > 24576u) return X3D_FRAME_HEADER_INVALID_PAYLOAD_LEN;  // decodefile.rs:118-121
-  return X3D_OK;
-}
-
-__device__ __forceinline__ int32_t x3_frame_header_check(const uint32_t* __restrict__ xw, uint64_t n_dw,
-                                                         uint64_t x3_len, uint64_t off, uint32_t& plen,
-                                                         uint32_t& samples, uint32_t& pcrc) {
-  plen = 0;
-  samples = 0;
-  pcrc = 0;
-  if (off + 20 > x3_len) return X3D_STREAM_ENDS_IN_FRAME;
-  const uint32_t h0 = x3_be32_at(xw, n_dw, off), h1 = x3_be32_at(xw, n_dw, off + 4);
-  const uint32_t h2 = x3_be32_at(xw, n_dw, off + 8), h3 = x3_be32_at(xw, n_dw, off + 12);
-  const uint32_t h4 = x3_be32_at(xw, n_dw, off + 16);
-  uint32_t hc = 0xFFFFu;
-  hc = x3_crc_be32(hc, h0);
-  hc = x3_crc_be32(hc, h1);
-  hc = x3_crc_be32(hc, h2);
-  hc = x3_crc_be32(hc, h3);
-  return x3_frame_header_check_words(h0, h1, h4, hc, x3_len, off, plen, samples, pcrc);
-}
 
 // Payload-CRC tables in LDS: T[0..3][v] = crc0 of byte v followed by 0..3 zero bytes (slicing by 4),
 // T[4][v] = (v << 8) * x^2048, T[5][v] = v * x^2048 (a 16-bit state times x^(32*64) is T[4][hi] ^ T[5][lo]).
@@ -362,79 +307,44 @@ __device__ __forceinline__ uint32_t x3_wave_max_u32(uint32_t v) {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");    \
   } while (0)
 
-// FAST: every valid Rice codeword (zero run + terminator + sub-code) is at most 33 bits, so one
-// window refill per sample suffices and a zero run of >= 32 bits is an error outright.  True for
-// the default parameters; the host picks the general instantiation otherwise.
-// LANES: frames decoded per wave (the first LANES lanes decode, all 64 lanes flush).  The decode
-// loop is one long dependent instruction chain per wave, so with few frames (config 3: 69 120)
-// it is better to spread them over MORE waves than to fill every lane: 16 frames per wave gives
-// ~4 resident waves per SIMD whose chains interleave ("Decode occupancy").
-template <bool FAST, int LANES>
+// The general kernel: any parameter set (a Rice codeword may be longer than 32 bits: a second window refill per
+// sample, and zero runs of >= 32 bits are counted on).
 __global__ void __launch_bounds__(64)
 x3_decode_lanes_kernel(const uint8_t* __restrict__ x3, uint64_t x3_len, const uint64_t* __restrict__ frame_off,
                        uint64_t n_frames, X3Geom g, const uint64_t* __restrict__ wav_off, X3DevParams p,
                        int16_t* __restrict__ wav, uint64_t wav_cap, int32_t* __restrict__ status,
                        X3FrameMeta* __restrict__ meta) {
-  __shared__ __attribute__((aligned(16))) uint32_t ring[LANES * X3_DEC_RING_STRIDE];
-  __shared__ __attribute__((aligned(16))) uint32_t outs[LANES * X3_DEC_OUT_STRIDE];
-  __shared__ unsigned long long s_wo[LANES];  // sample offset of each lane's frame in wav
-  __shared__ uint32_t s_ns[LANES];            // samples of each lane's frame (0 = not flushed cooperatively)
+  __shared__ __attribute__((aligned(16))) uint32_t ring[64 * X3_DEC_RING_STRIDE];
+  __shared__ __attribute__((aligned(16))) uint32_t outs[64 * X3_DEC_OUT_STRIDE];
+  __shared__ unsigned long long s_wo[64];  // sample offset of each lane's frame in wav
+  __shared__ uint32_t s_ns[64];            // samples of each lane's frame (0 = not flushed cooperatively)
 
   const uint32_t lane = threadIdx.x;
-  const bool decoder = lane < (uint32_t)LANES;
-  const uint32_t dl = decoder ? lane : 0u;  // row used by this lane (idle lanes alias row 0, never write)
-  const uint64_t f = (uint64_t)blockIdx.x * LANES + lane;
+  const uint64_t f = (uint64_t)blockIdx.x * 64 + lane;
 #ifdef X3_DBG_STAMPS
   unsigned long long dbg_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   unsigned long long dbg_t = clock64();
 #endif
-  uint32_t* const row = ring + dl * X3_DEC_RING_STRIDE;
-  uint32_t* const orow = outs + dl * X3_DEC_OUT_STRIDE;
+  uint32_t* const row = ring + lane * X3_DEC_RING_STRIDE;
+  uint32_t* const orow = outs + lane * X3_DEC_OUT_STRIDE;
 
-  // ---- per-lane frame setup
-  bool active = decoder && f < n_frames;
-  int32_t st = X3D_OK;
-  uint32_t samples = 0, plen = 2;
-  uint64_t p0 = 0, wo = 0;
-  if (active) {
-    // header validation is repeated here (cheap, once per frame) so that this kernel does not depend
-    // on x3_frame_check_kernel: the payload-CRC pass runs CONCURRENTLY on a second stream and the
-    // two status arrays are merged afterwards (x3_decode_merge_kernel)
-    uint32_t pcrc_unused;
-    st = x3_frame_header_check(reinterpret_cast<const uint32_t*>(x3 - (reinterpret_cast<uintptr_t>(x3) & 3u)),
-                               (x3_len + (reinterpret_cast<uintptr_t>(x3) & 3u) + 3) >> 2,
-                               x3_len + (reinterpret_cast<uintptr_t>(x3) & 3u),
-                               frame_off[f] + (reinterpret_cast<uintptr_t>(x3) & 3u), plen, samples, pcrc_unused);
-    meta[f].payload_len = plen;
-    meta[f].samples = samples;
-    p0 = frame_off[f] + 20;
-    if (st != X3D_OK) {
-      active = false;
-    } else if (samples == 0 || plen < 2) {
-      st = X3D_BAD_ARG;  // the reference panics (decoder.rs:42,47)
-      active = false;
-    } else {
-      if (wav_off) {
-        wo = wav_off[f];
-      } else {
-        const uint64_t clip = f / g.fpc;
-        const uint64_t idx = f - clip * g.fpc;
-        wo = clip * g.clip_stride + idx * (uint64_t)p.spf;
-      }
-      if (wo + samples > wav_cap) {
-        st = X3D_BAD_ARG;  // slice index panic
-        active = false;
-      }
-    }
+  // ---- per-lane frame setup (x3_frame_setup: x3_decode_frame.h)
+  const X3FrameSetup fs = x3_frame_setup(x3, x3_len, frame_off, f, f < n_frames, g, wav_off, p, wav_cap);
+  if (f < n_frames) {
+    meta[f].payload_len = fs.plen;
+    meta[f].samples = fs.samples;
   }
+  const bool active = fs.active;
+  int32_t st = fs.st;
+  const uint32_t samples = fs.samples;
+  uint32_t plen = fs.plen;
+  uint64_t p0 = fs.p0, wo = fs.wo;
   if (!active) { p0 = 0; plen = 2; wo = 0; }  // harmless addresses for idle lanes
   int16_t* __restrict__ const o = wav + wo;
   // frames whose output is 16-byte aligned are flushed cooperatively, the others store directly
   const bool coop = active && ((reinterpret_cast<uintptr_t>(o) & 15u) == 0);
-  if (decoder) {
-    s_wo[lane] = wo;
-    s_ns[lane] = coop ? samples : 0u;
-  }
+  s_wo[lane] = wo;
+  s_ns[lane] = coop ? samples : 0u;
 
   // ---- input ring.  Offsets are "virtual": v = byte offset from x3b, the 16-byte-aligned address
   // at or below x3, so that 16-byte chunks are aligned in memory whatever x3's own alignment is.
@@ -464,7 +374,7 @@ x3_decode_lanes_kernel(const uint8_t* __restrict__ x3, uint64_t x3_len, const ui
       }
       c = make_uint4(w[0], w[1], w[2], w[3]);
     }
-    if (decoder) *reinterpret_cast<uint4*>(row + (wr_abs & (X3_DEC_RING_DW - 1u))) = c;
+    *reinterpret_cast<uint4*>(row + (wr_abs & (X3_DEC_RING_DW - 1u))) = c;
     wr_abs += 4;
   };
 
@@ -538,7 +448,7 @@ x3_decode_lanes_kernel(const uint8_t* __restrict__ x3, uint64_t x3_len, const ui
     }
     X3_WAVE_LDS_ORDER();
     const uint32_t pieces = (upto - wbase + 7u) >> 3;  // 16-byte pieces per frame in this window
-    const uint32_t total = pieces * (uint32_t)LANES;
+    const uint32_t total = pieces * 64u;
     for (uint32_t t = lane; t < total; t += 64u) {
       const uint32_t r = t / pieces, q = t - r * pieces;
       const uint32_t ns = s_ns[r];
@@ -609,22 +519,20 @@ x3_decode_lanes_kernel(const uint8_t* __restrict__ x3, uint64_t x3_len, const ui
         uint32_t top = (uint32_t)(win >> 32);
         uint32_t z = (uint32_t)__clz(top) & zmask;  // __clz(0) = 32
         uint32_t zextra = 0;
-        if (!FAST) {
-          if (zmask && top == 0) {  // zero run of >= 32 bits: keep counting (general parameters only)
-            deferred = true;        // ... and let the reference's reader have the last word (x3_decode_replay.h)
-            do {
-              win <<= 32;
-              have -= 32;
-              zextra += 32;
-              refill();
-              top = (uint32_t)(win >> 32);
-            } while (top == 0 && zextra < 128);
-            z = top ? (uint32_t)__clz(top) : 0u;
-          }
+        if (zmask && top == 0) {  // zero run of >= 32 bits: keep counting (general parameters only)
+          deferred = true;        // ... and let the reference's reader have the last word (x3_decode_replay.h)
+          do {
+            win <<= 32;
+            have -= 32;
+            zextra += 32;
+            refill();
+            top = (uint32_t)(win >> 32);
+          } while (top == 0 && zextra < 128);
+          z = top ? (uint32_t)__clz(top) : 0u;
         }
         win <<= z;
         have -= z;
-        if (!FAST) refill();
+        refill();
         const uint32_t v = (uint32_t)(win >> 32) >> rsh;
         win <<= width;
         have -= width;
@@ -670,7 +578,7 @@ x3_decode_lanes_kernel(const uint8_t* __restrict__ x3, uint64_t x3_len, const ui
     if (st == X3D_OUT_OF_BOUNDS_INVERSE || st == X3D_FRAME_DECODE_INVALID_BPF || deferred || taken > held)
       st = X3D_REPLAY;
   }
-  if (decoder && f < n_frames) status[f] = st;
+  if (f < n_frames) status[f] = st;
 #ifdef X3_DBG_STAMPS
   X3_STAMP(6);
   if (lane == 0 && blockIdx.x < 4096)
@@ -714,61 +622,29 @@ x3_decode_fast_kernel(const uint8_t* __restrict__ x3, uint64_t x3_len, const uin
   uint32_t* const row = ring + lane * X3_DEC_RING_STRIDE;
   uint32_t* const orow = outs + lane * X3_DEC_OUT_STRIDE;
 
-  // ---- per-lane frame setup (same checks as the general kernel)
-  bool active = f < n_frames;
-  int32_t st = X3D_OK;
-  uint32_t samples = 0, plen = 2;
-  uint64_t p0 = 0, wo = 0;
-  if (active) {
-    // header validation is repeated here (cheap, once per frame) so that this kernel does not depend
-    // on x3_frame_check_kernel: the payload-CRC pass runs CONCURRENTLY on a second stream and the
-    // two status arrays are merged afterwards (x3_decode_merge_kernel)
-    uint32_t pcrc_unused;
-    st = x3_frame_header_check(reinterpret_cast<const uint32_t*>(x3 - (reinterpret_cast<uintptr_t>(x3) & 3u)),
-                               (x3_len + (reinterpret_cast<uintptr_t>(x3) & 3u) + 3) >> 2,
-                               x3_len + (reinterpret_cast<uintptr_t>(x3) & 3u),
-                               frame_off[f] + (reinterpret_cast<uintptr_t>(x3) & 3u), plen, samples, pcrc_unused);
-    meta[f].payload_len = plen;
-    meta[f].samples = samples;
-    p0 = frame_off[f] + 20;
-    if (st != X3D_OK) {
-      active = false;
-    } else if (samples == 0 || plen < 2) {
-      st = X3D_BAD_ARG;
-      active = false;
-    } else {
-      if (wav_off) {
-        wo = wav_off[f];
-      } else {
-        const uint64_t clip = f / g.fpc;
-        const uint64_t idx = f - clip * g.fpc;
-        wo = clip * g.clip_stride + idx * (uint64_t)p.spf;
-      }
-      if (wo + samples > wav_cap) {
-        st = X3D_BAD_ARG;
-        active = false;
-      }
-    }
+  // ---- per-lane frame setup (x3_frame_setup: x3_decode_frame.h)
+  const X3FrameSetup fs = x3_frame_setup(x3, x3_len, frame_off, f, f < n_frames, g, wav_off, p, wav_cap);
+  if (f < n_frames) {
+    meta[f].payload_len = fs.plen;
+    meta[f].samples = fs.samples;
   }
-  if (!active) { p0 = 0; plen = 2; wo = 0; }
+  const bool active = fs.active;
+  int32_t st = fs.st;
+  const uint32_t samples = fs.samples;
+  uint32_t plen = fs.plen;
+  uint64_t p0 = fs.p0, wo = fs.wo;
+  if (!active) { p0 = 0; plen = 2; wo = 0; }  // harmless addresses for idle lanes
   int16_t* __restrict__ const o = wav + wo;
   const bool coop = active && ((reinterpret_cast<uintptr_t>(o) & 15u) == 0);
   s_wo[lane] = wo;
   s_ns[lane] = coop ? samples : 0u;
 
-  // ---- input ring; words are parked BIG-ENDIAN
-  const uint32_t adj = (uint32_t)(reinterpret_cast<uintptr_t>(x3) & 15u);
-  // offsets are relative to this lane's first 16-byte chunk (a frame is < 64 KB): a 64-bit pointer per lane,
-  // 32-bit arithmetic on everything else, streams of any length
-  const uint64_t abs_bits = (uint64_t)adj + p0 + 2u;
-  // (the first chunk: the one with the first block header, or -- a payload of two bytes that ends on a 16-byte boundary --
-  // the one with the payload's last byte: the chunk behind it may be the first one behind the stream; x3_decode_split_kernel.h)
-  const uint64_t abs_last = (uint64_t)adj + p0 + plen - 1u;
-  const uint64_t abs_base = (abs_bits < abs_last ? abs_bits : abs_last) & ~15ull;
-  const uint8_t* __restrict__ const x3b = (x3 - adj) + abs_base;
-  const uint32_t v_bits = (uint32_t)(abs_bits - abs_base);   // first block header (0..16)
+  // ---- input ring (x3_ring_origin: x3_decode_frame.h); words are parked BIG-ENDIAN
+  const X3RingOrigin ro = x3_ring_origin(x3, p0, plen, 2u);   // (the bit stream starts behind the raw first sample)
+  const uint8_t* __restrict__ const x3b = ro.x3b;
+  const uint32_t v_bits = ro.v_bits;                       // first block header (0..16)
   const uint32_t v_end = v_bits - 2u + plen;               // end of the payload
-  const uint32_t v_last = (v_end - 1u) & ~15u;             // last 16-byte chunk that holds payload
+  const uint32_t v_last = x3_ring_last_payload_chunk(v_end);
   uint32_t v_next = 0;
   uint32_t wr_abs = 0;
 
@@ -1141,16 +1017,9 @@ x3_decode_merge_kernel(const int32_t* __restrict__ cstatus, int32_t* __restrict_
       st = x3_replay_frame(x3 + frame_off[f] + 20, m.payload_len, m.samples, q, &first_sample);
       status[f] = st;
     } else if (st == X3D_REPLAY) {
-      // (the decoder has validated the header, the sample count and the output range of this frame)
+      // (the decoder has validated the header, the sample count and the output range of this frame: the same row)
       const X3FrameMeta m = meta[f];
-      uint64_t wo;
-      if (wav_off) {
-        wo = wav_off[f];
-      } else {
-        const uint64_t clip = f / g.fpc;
-        wo = clip * g.clip_stride + (f - clip * g.fpc) * (uint64_t)p.spf;
-      }
-      st = x3_replay_frame(x3 + frame_off[f] + 20, m.payload_len, m.samples, p, wav + wo);
+      st = x3_replay_frame(x3 + frame_off[f] + 20, m.payload_len, m.samples, p, wav + x3_frame_wav_offset(f, g, p, wav_off));
       status[f] = st;
       atomicAdd(&out->replays, 1u);   // (option "last_decode_replays"; conforming streams never get here)
     }

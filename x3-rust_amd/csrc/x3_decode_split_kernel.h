@@ -243,41 +243,17 @@ x3_decode_split_kernel(const uint8_t* __restrict__ x3, uint64_t x3_len, const ui
   const unsigned long long dbg_start = wall_clock64();
 #endif
 
-  // ---- per-lane frame setup, done by both waves (same checks as the fast kernel)
-  bool active = f < n_frames;
-  int32_t st = X3D_OK;
-  uint32_t samples = 0, plen = 2;
-  uint64_t p0 = 0, wo = 0;
-  if (active) {
-    uint32_t pcrc_unused;
-    st = x3_frame_header_check(reinterpret_cast<const uint32_t*>(x3 - (reinterpret_cast<uintptr_t>(x3) & 3u)),
-                               (x3_len + (reinterpret_cast<uintptr_t>(x3) & 3u) + 3) >> 2,
-                               x3_len + (reinterpret_cast<uintptr_t>(x3) & 3u),
-                               frame_off[f] + (reinterpret_cast<uintptr_t>(x3) & 3u), plen, samples, pcrc_unused);
-    if ((threadIdx.x >> 6) == 1u) {
-      meta[f].payload_len = plen;
-      meta[f].samples = samples;
-    }
-    p0 = frame_off[f] + 20;
-    if (st != X3D_OK) {
-      active = false;
-    } else if (samples == 0 || plen < 2) {
-      st = X3D_BAD_ARG;
-      active = false;
-    } else {
-      if (wav_off) {  // (the caller vouches for multiples of four samples: output rows on 8-byte boundaries at least)
-        wo = wav_off[f];
-      } else {
-        const uint64_t clip = f / g.fpc;
-        const uint64_t idx = f - clip * g.fpc;
-        wo = clip * g.clip_stride + idx * (uint64_t)p.spf;
-      }
-      if (wo + samples > wav_cap) {
-        st = X3D_BAD_ARG;
-        active = false;
-      }
-    }
+  // ---- per-lane frame setup, done by all waves (x3_frame_setup: x3_decode_frame.h; with caller-supplied offsets the
+  // caller vouches for multiples of four samples: output rows on 8-byte boundaries at least)
+  const X3FrameSetup fs = x3_frame_setup(x3, x3_len, frame_off, f, f < n_frames, g, wav_off, p, wav_cap);
+  if (f < n_frames && (threadIdx.x >> 6) == 1u) {
+    meta[f].payload_len = fs.plen;
+    meta[f].samples = fs.samples;
   }
+  bool active = fs.active;
+  int32_t st = fs.st;
+  uint32_t samples = fs.samples, plen = fs.plen;
+  uint64_t p0 = fs.p0, wo = fs.wo;
   // ---- the stretch of the frame that this lane decodes (all of it without an index)
   uint32_t hb = 16u;                    // bit offset of its first block header from the start of the payload
   uint32_t pred = 0;                    // (seg_j > 0) the sample in front of it
@@ -324,23 +300,15 @@ x3_decode_split_kernel(const uint8_t* __restrict__ x3, uint64_t x3_len, const ui
   // ---- the input ring of this lane's frame (the parser fills and reads it)
   uint32_t* const row = ring + lane * X3_DEC_RING_DW;
   const uint32_t row_base = (uint32_t)(uintptr_t)row;  // LDS byte address of the row (low 7 bits zero)
-  // words are parked BIG-ENDIAN
-  const uint32_t adj = (uint32_t)(reinterpret_cast<uintptr_t>(x3) & 15u);
-  // offsets are relative to this lane's first 16-byte chunk (a frame is < 64 KB): a 64-bit pointer per lane,
-  // 32-bit arithmetic on everything else, streams of any length
-  const uint64_t abs_bits = (uint64_t)adj + p0 + (hb >> 3);   // (a byte position; hb = 16 without an index: behind the first sample)
+  // words are parked BIG-ENDIAN.  Its origin (x3_ring_origin: x3_decode_frame.h) is the chunk of the byte of the first
+  // block header (hb = 16 without an index: behind the first sample) ...
+  const X3RingOrigin ro = x3_ring_origin(x3, p0, plen, hb >> 3);
   const uint32_t ebits = hb & 7u;                             // ... and the bits of that byte in front of the header
-  // The first chunk is the one that holds that byte -- or the payload's LAST byte, where the bit stream starts at the very
-  // end of the payload (a frame of one sample; an index entry that points there) on a 16-byte boundary: the chunk behind
-  // the payload may be the first one behind the stream (found by the guard pages of x3_fence.h: until round 5 such a lane
-  // read its eight chunks from there, 128 bytes that nobody used and that nobody may have mapped).  hb >> 3 <= plen, plen >= 2.
-  const uint64_t abs_last = (uint64_t)adj + p0 + plen - 1u;
-  const uint64_t abs_base = (abs_bits < abs_last ? abs_bits : abs_last) & ~15ull;
-  const uint8_t* __restrict__ const x3b = (x3 - adj) + abs_base;
-  const uint32_t v_bits = (uint32_t)(abs_bits - abs_base);   // first block header (0..16)
+  const uint8_t* __restrict__ const x3b = ro.x3b;
+  const uint32_t v_bits = ro.v_bits;                         // first block header (0..16)
   const uint32_t v_end = v_bits - (hb >> 3) + plen;          // end of the payload
   const int32_t v_rel = 8 * (int32_t)(hb >> 3) - 8 * (int32_t)v_bits;   // payload bit = ring bit + v_rel
-  const uint32_t v_last = (v_end - 1u) & ~15u;               // last 16-byte chunk that holds payload
+  const uint32_t v_last = x3_ring_last_payload_chunk(v_end);
   uint32_t v_next = 0;
   uint32_t wr_abs = 0;
   constexpr uint32_t SVC_MAX = 3u * X3S_PERIOD;  // chunks a service can park per lane

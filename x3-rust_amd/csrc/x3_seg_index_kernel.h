@@ -44,7 +44,6 @@ x3_seg_index_kernel(const uint8_t* __restrict__ x3, uint64_t len, const uint64_t
   const uint32_t lane = threadIdx.x;
   const uint32_t pitch = nseg - 1u;
   if (blockIdx.x == 0 && lane == 0) idx[0] = make_uint2(X3S_SEG_MAGIC, sb);
-  const uint32_t adj = (uint32_t)(reinterpret_cast<uintptr_t>(x3) & 15u);
   const uint64_t n_groups = (F + 63u) >> 6;
   for (uint64_t grp = blockIdx.x; grp < n_groups; grp += gridDim.x) {
     const uint64_t f = grp * 64u + lane;
@@ -127,14 +126,10 @@ x3_seg_index_kernel(const uint8_t* __restrict__ x3, uint64_t len, const uint64_t
       pos += n;
     };
     if (target) {
-      const uint64_t abs_bits = (uint64_t)adj + p0 + 2u;          // the byte behind the first sample
-      const uint64_t abs_last = (uint64_t)adj + p0 + plen - 1u;   // the payload's last byte
-      const uint64_t abs_base = (abs_bits < abs_last ? abs_bits : abs_last) & ~15ull;
-      x3b = (x3 - adj) + abs_base;
-      const uint64_t lastc = ((uint64_t)adj + len - 1u) & ~15ull;   // (>= abs_base: the payload lies inside the stream)
-      const uint64_t rel = lastc - abs_base;
-      v_last = rel > 0xFFFFFFF0ull ? 0xFFFFFFF0u : (uint32_t)rel;
-      d8 = 8u * (uint32_t)(abs_bits - abs_base);   // position of the first block header (payload bit 16)
+      const X3RingOrigin ro = x3_ring_origin(x3, p0, plen, 2u);   // (x3_decode_frame.h; the byte behind the first sample)
+      x3b = ro.x3b;
+      v_last = x3_ring_last_stream_chunk(x3, len, ro.abs_base);
+      d8 = 8u * ro.v_bits;                         // position of the first block header (payload bit 16)
       end_pos = d8 + 8u * plen - 16u;              // position of the payload's end
       last = x3w_be32_at(x3, len, p0) >> 16;
 #pragma unroll
