@@ -1,0 +1,23 @@
+"""The segmented walk's entry table and workspace layout, on the CPU: tests/host_cpp/test_segwalk_layout.cpp calls the
+library's seg_entries, segwalk_carve and streams_carve (x3_internal.h) over entry tables of 1 to 1 000 entries -- lengths
+around the span size, empty tables, overlapping and repeated offsets, the bound on the span count -- and checks the span
+counts, the refusals and the carved pieces (disjoint, aligned, long enough, inside the returned size, the entry table in one
+piece as its upload needs it).  Built by tests/test_routes.py's build_driver: the library's translation units compiled, the
+driver host code only, no context."""
+import os
+import subprocess
+
+import pytest
+
+import test_routes as R
+
+DRIVER = os.path.join(R.ROOT, "tests", "host_cpp", "test_segwalk_layout.cpp")
+
+
+@pytest.mark.skipif(not os.path.exists(R.HIPCC), reason="hipcc not found")
+def test_entry_table_and_workspace_layout():
+    exe = R.build_driver(DRIVER, "test_segwalk_layout")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and r.stdout.startswith("ok tables="), (r.stdout[-4000:], r.stderr[-2000:])
+    counts = dict(kv.split("=") for kv in r.stdout.split()[1:])
+    assert int(counts["tables"]) >= 240 and int(counts["carves"]) >= 240, counts

@@ -242,6 +242,24 @@ static int ctx_init(x3_ctx* c, int device, hipStream_t stream, bool own) {
   return X3_OK;
 }
 
+int src_tab_upload(x3_ctx* c, void* d_dst, std::initializer_list<std::pair<const void*, size_t>> parts) {
+  size_t tab_bytes = 0, at = 0;
+  for (const auto& q : parts) tab_bytes += q.second;
+  if (c->ev_src_tab) HIPCHK(c, hipEventSynchronize(c->ev_src_tab));   // (the last call's copy out of the pinned block)
+  else HIPCHK(c, hipEventCreateWithFlags(&c->ev_src_tab, hipEventDisableTiming));
+  if (c->h_src_tab_cap < tab_bytes) {
+    if (c->h_src_tab) (void)hipHostFree(c->h_src_tab);
+    c->h_src_tab = nullptr;
+    c->h_src_tab_cap = 0;
+    HIPCHK(c, hipHostMalloc(&c->h_src_tab, tab_bytes + tab_bytes / 4 + 64));
+    c->h_src_tab_cap = tab_bytes + tab_bytes / 4 + 64;
+  }
+  for (const auto& q : parts) { std::memcpy((char*)c->h_src_tab + at, q.first, q.second); at += q.second; }
+  HIPCHK(c, hipMemcpyAsync(d_dst, c->h_src_tab, tab_bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipEventRecord(c->ev_src_tab, c->stream));
+  return X3_OK;
+}
+
 extern "C" int x3_ctx_create(int device, x3_ctx** ctx) {
   if (!ctx) return X3_ERR_BAD_ARG;
   *ctx = nullptr;
@@ -277,7 +295,7 @@ extern "C" void x3_ctx_destroy(x3_ctx* c) {
   if (c->fcache) x3_reader_close(c->fcache);
   for (DevBuf* b : {&c->in, &c->out, &c->in_more[0], &c->in_more[1], &c->out_more[0], &c->out_more[1], &c->frame_bytes, &c->frame_off, &c->dec_status, &c->dec_cstatus, &c->dec_meta, &c->wav_off,
                     &c->seg_crc, &c->desc, &c->idx_cand, &c->idx_keys, &c->idx_vals, &c->idx_J, &c->idx_S,
-                    &c->idx_L, &c->idx_sum, &c->idx_wg, &c->idx_sorted, &c->idx_scan, &c->dense_list, &c->lb_desc, &c->src_tab, &c->win_ws, &c->st_tab, &c->st_cand, &c->st_scan, &c->st_frames, &c->st_ent, &c->st_ws,
+                    &c->idx_L, &c->idx_sum, &c->idx_wg, &c->idx_sorted, &c->idx_scan, &c->dense_list, &c->lb_desc, &c->src_tab, &c->win_ws, &c->st_walk, &c->st_ws,
                     &c->st_one, &c->st_row})
     if (b->p) (void)x3_dfree(b->p);
   for (auto& t : c->timers) {

@@ -27,7 +27,26 @@ static uint64_t seg_stretches(uint64_t blocks_per_frame, uint32_t seg_blocks) {
   return (blocks_per_frame + seg_blocks - 1) / seg_blocks;
 }
 
-// ... and what the entry points take for one: stretches of whole groups of four blocks, an 8-byte aligned table
+// The parameters as the decoders take them: block length 0 travels as 1 (frames that need it are BAD_ARG frames of the walk)
+static x3_params decoder_params(const x3_params* p) {
+  x3_params pp = *p;
+  if (pp.block_len == 0) pp.block_len = 1;
+  return pp;
+}
+
+// ... for the entry points that address blocks inside a frame (windows, the segment index): both lengths are needed
+static int derive_block_params(const x3_params* p, X3DevParams* d) {
+  const int rc = derive_params(p, d);
+  return rc ? rc : d->block_len == 0 || d->blocks_per_frame == 0 ? X3_ERR_BAD_ARG : X3_OK;
+}
+
+// what the entry points take for a frame table: the stream on a 4-byte boundary, offsets on an 8-byte one, a count in 31 bits
+static bool frame_table_args_ok(const uint8_t* d_x3, const uint64_t* d_frame_offsets, uint64_t n_frames) {
+  return (reinterpret_cast<uintptr_t>(d_x3) & 3u) == 0 && (reinterpret_cast<uintptr_t>(d_frame_offsets) & 7u) == 0 &&
+         n_frames != 0 && n_frames <= 0x7FFFFFFFull;
+}
+
+// ... and for a segment index: stretches of whole groups of four blocks, an 8-byte aligned table
 static bool seg_index_args_ok(const uint64_t* d_seg_index, uint32_t seg_blocks) {
   return seg_blocks != 0 && (seg_blocks & 3u) == 0 && seg_blocks <= 3200u && (reinterpret_cast<uintptr_t>(d_seg_index) & 7u) == 0;
 }
@@ -310,42 +329,42 @@ static int index_summary(x3_ctx* c, const X3IndexSummary* d_sum, X3IndexSummary*
   return X3_OK;
 }
 
+// what a walk of a stream of len bytes starts from: summary and candidate counter on the device (idx_sum), its grid
+struct IndexWords { X3IndexSummary* d_sum; unsigned int* d_count; unsigned grid; };
+static int index_words(x3_ctx* c, uint64_t len, IndexWords* w) {
+  const int rc = ensure(c, c->idx_sum, 256);
+  if (rc == X3_OK) *w = {(X3IndexSummary*)c->idx_sum.p, (unsigned int*)((char*)c->idx_sum.p + 128), index_grid(c, len)};
+  return rc;
+}
+
 // The fast path's five launches (x3_index_kernels.h), nothing waited for: the summary -- frame and sample count, how the
-// walk ends, pad2 = "not one clean chain: take the general walk" -- stays in *d_sum_out on the device.
+// walk ends, pad2 = "not one clean chain: take the general walk" -- stays in *w.d_sum on the device.
 static int index_fast_launch(x3_ctx* c, const uint8_t* d_x3, uint64_t len, uint64_t phantom, uint32_t bl0, uint64_t wav_cap,
-                             uint64_t max_frames, uint64_t* d_frame_offsets, uint64_t* d_wav_offsets,
-                             X3IndexSummary** d_sum_out) {
+                             uint64_t max_frames, uint64_t* d_frame_offsets, uint64_t* d_wav_offsets, const IndexWords& w) {
   const uint32_t* xw = reinterpret_cast<const uint32_t*>(d_x3);
   int rc;
-  if ((rc = ensure(c, c->idx_sum, 256))) return rc;
-  unsigned int* d_count = reinterpret_cast<unsigned int*>((char*)c->idx_sum.p + 128);
-  X3IndexSummary* d_sum = reinterpret_cast<X3IndexSummary*>(c->idx_sum.p);
-  const unsigned grid = index_grid(c, len);
-  *d_sum_out = d_sum;
-  if (!grid) return X3_ERR_BAD_ARG;
-  {
-    const size_t G = grid;
-    if ((rc = ensure(c, c->idx_wg, G * X3I_WG_CANDS * sizeof(X3Cand)))) return rc;
-    if ((rc = ensure(c, c->idx_sorted, G * X3I_WG_CANDS * sizeof(X3Cand)))) return rc;
-    if ((rc = ensure(c, c->idx_scan, G * 32))) return rc;   // count u32 | base u32 | samp u64 | sbase u64 per span
-    unsigned int* cnt = reinterpret_cast<unsigned int*>(c->idx_scan.p);
-    uint32_t* base = reinterpret_cast<uint32_t*>(cnt + G);
-    unsigned long long* samp = reinterpret_cast<unsigned long long*>(base + G);
-    unsigned long long* sbase = samp + G;
-    hipLaunchKernelGGL(x3_index_init_kernel, dim3(1), dim3(64), 0, c->stream, d_sum, d_count);
-    hipLaunchKernelGGL(x3_index_candidates_kernel<true>, dim3(grid), dim3(256), 0, c->stream, xw, len, len + phantom, bl0,
-                       (X3Cand*)c->idx_wg.p, 0u, cnt, samp, &d_sum->pad2);
-    hipLaunchKernelGGL(x3_index_chain_kernel, dim3(1), dim3(1024), 0, c->stream, (const unsigned int*)cnt,
-                       (const unsigned long long*)samp, (uint32_t)G, base, sbase, d_sum);
-    hipLaunchKernelGGL(x3_index_link_kernel, dim3(grid), dim3(64), 0, c->stream, (const X3Cand*)c->idx_wg.p,
-                       (const unsigned int*)cnt, (uint32_t)G, (const uint32_t*)base, (const unsigned long long*)sbase,
-                       (X3Cand*)c->idx_sorted.p, (uint32_t)std::min<uint64_t>(G * X3I_WG_CANDS, 0xFFFFFFFFull),
-                       (unsigned long long)max_frames, (unsigned long long)wav_cap, (unsigned long long*)d_frame_offsets,
-                       (unsigned long long*)d_wav_offsets, d_sum);
-    hipLaunchKernelGGL(x3_index_finalize_kernel, dim3(1), dim3(64), 0, c->stream, xw, len, len + phantom, bl0,
-                       (const X3Cand*)c->idx_sorted.p, (const unsigned long long*)d_wav_offsets, d_sum);
-    HIPCHK(c, hipGetLastError());
-  }
+  if (!w.grid) return X3_ERR_BAD_ARG;
+  const size_t G = w.grid;
+  if ((rc = ensure(c, c->idx_wg, G * X3I_WG_CANDS * sizeof(X3Cand)))) return rc;
+  if ((rc = ensure(c, c->idx_sorted, G * X3I_WG_CANDS * sizeof(X3Cand)))) return rc;
+  if ((rc = ensure(c, c->idx_scan, G * 32))) return rc;   // count u32 | base u32 | samp u64 | sbase u64 per span
+  unsigned int* cnt = reinterpret_cast<unsigned int*>(c->idx_scan.p);
+  uint32_t* base = reinterpret_cast<uint32_t*>(cnt + G);
+  unsigned long long* samp = reinterpret_cast<unsigned long long*>(base + G);
+  unsigned long long* sbase = samp + G;
+  hipLaunchKernelGGL(x3_index_init_kernel, dim3(1), dim3(64), 0, c->stream, w.d_sum, w.d_count);
+  hipLaunchKernelGGL(x3_index_candidates_kernel<true>, dim3(w.grid), dim3(256), 0, c->stream, xw, len, len + phantom, bl0,
+                     (X3Cand*)c->idx_wg.p, 0u, cnt, samp, &w.d_sum->pad2);
+  hipLaunchKernelGGL(x3_index_chain_kernel, dim3(1), dim3(1024), 0, c->stream, (const unsigned int*)cnt,
+                     (const unsigned long long*)samp, (uint32_t)G, base, sbase, w.d_sum);
+  hipLaunchKernelGGL(x3_index_link_kernel, dim3(w.grid), dim3(64), 0, c->stream, (const X3Cand*)c->idx_wg.p,
+                     (const unsigned int*)cnt, (uint32_t)G, (const uint32_t*)base, (const unsigned long long*)sbase,
+                     (X3Cand*)c->idx_sorted.p, (uint32_t)std::min<uint64_t>(G * X3I_WG_CANDS, 0xFFFFFFFFull),
+                     (unsigned long long)max_frames, (unsigned long long)wav_cap, (unsigned long long*)d_frame_offsets,
+                     (unsigned long long*)d_wav_offsets, w.d_sum);
+  hipLaunchKernelGGL(x3_index_finalize_kernel, dim3(1), dim3(64), 0, c->stream, xw, len, len + phantom, bl0,
+                     (const X3Cand*)c->idx_sorted.p, (const unsigned long long*)d_wav_offsets, w.d_sum);
+  HIPCHK(c, hipGetLastError());
   return X3_OK;
 }
 
@@ -355,45 +374,42 @@ static int index_dev_impl(x3_ctx* c, const uint8_t* d_x3, uint64_t len, uint64_t
   if (reinterpret_cast<uintptr_t>(d_x3) & 3u) return X3_ERR_BAD_ARG;
   const uint32_t* xw = reinterpret_cast<const uint32_t*>(d_x3);
   int rc;
-  if ((rc = ensure(c, c->idx_sum, 256))) return rc;
-  unsigned int* d_count = reinterpret_cast<unsigned int*>((char*)c->idx_sum.p + 128);
-  X3IndexSummary* d_sum = reinterpret_cast<X3IndexSummary*>(c->idx_sum.p);
-  const unsigned grid = index_grid(c, len);
+  IndexWords w;
+  if ((rc = index_words(c, len, &w))) return rc;
   // ---- the fast path (round 4): a stream that is ONE CLEAN CHAIN -- what an encoder writes -- needs no hash table and
   // no pointer doubling.  The scanning workgroups keep their candidates in stream order, two scans number them, and one
   // kernel checks all at once that the first frame sits at offset 0 and that every frame ends where the next begins
   // (x3_index_kernels.h).  Five launches and one trip to the host where the general walk below takes thirteen and two;
   // anything else -- a false candidate inside a payload, damage, a frame the walk does not step over -- sets pad2, and
   // the general walk takes the stream as before.
-  if (grid && !c->opt.index_no_fast) {
-    X3IndexSummary* ds = nullptr;
-    if ((rc = index_fast_launch(c, d_x3, len, phantom, bl0, wav_cap, max_frames, d_frame_offsets, d_wav_offsets, &ds))) return rc;
-    if ((rc = index_summary(c, d_sum, result))) return rc;
+  if (w.grid && !c->opt.index_no_fast) {
+    if ((rc = index_fast_launch(c, d_x3, len, phantom, bl0, wav_cap, max_frames, d_frame_offsets, d_wav_offsets, w))) return rc;
+    if ((rc = index_summary(c, w.d_sum, result))) return rc;
     if (!result->pad2) {
       ++c->index_fast;
       return X3_OK;
     }
   }
   ++c->index_general;
-  hipLaunchKernelGGL(x3_index_init_kernel, dim3(1), dim3(64), 0, c->stream, d_sum, d_count);
+  hipLaunchKernelGGL(x3_index_init_kernel, dim3(1), dim3(64), 0, c->stream, w.d_sum, w.d_count);
   // ONE pass over the stream: the candidates go into a buffer sized for a frame every 256 bytes (the context keeps
   // it; typical streams hold one every few kilobytes); only a stream with more than that is scanned a second time.
   unsigned int n_cand = 0;
-  if (grid) {
+  if (w.grid) {
     const uint64_t guess = std::max<uint64_t>(4096, len / 256 + 1024);
     if ((rc = ensure(c, c->idx_cand, (size_t)std::min<uint64_t>(guess, 0x7FFFFFFFull) * sizeof(X3Cand)))) return rc;
     const uint32_t cap = (uint32_t)std::min<uint64_t>(c->idx_cand.cap / sizeof(X3Cand), 0x7FFFFFFFull);
-    hipLaunchKernelGGL(x3_index_candidates_kernel<false>, dim3(grid), dim3(256), 0, c->stream, xw, len, len + phantom, bl0,
-                       (X3Cand*)c->idx_cand.p, cap, d_count, (unsigned long long*)nullptr, (uint32_t*)nullptr);
-    HIPCHK(c, hipMemcpyAsync(c->h_crc, d_count, sizeof n_cand, hipMemcpyDeviceToHost, c->stream));  // (pinned)
+    hipLaunchKernelGGL(x3_index_candidates_kernel<false>, dim3(w.grid), dim3(256), 0, c->stream, xw, len, len + phantom, bl0,
+                       (X3Cand*)c->idx_cand.p, cap, w.d_count, (unsigned long long*)nullptr, (uint32_t*)nullptr);
+    HIPCHK(c, hipMemcpyAsync(c->h_crc, w.d_count, sizeof n_cand, hipMemcpyDeviceToHost, c->stream));  // (pinned)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     std::memcpy(&n_cand, c->h_crc, sizeof n_cand);
     if (n_cand > cap) {  // rare: denser than one frame per 256 bytes
       ++c->index_rescans;
       if ((rc = ensure(c, c->idx_cand, (size_t)n_cand * sizeof(X3Cand)))) return rc;
-      HIPCHK(c, hipMemsetAsync(d_count, 0, sizeof(unsigned int), c->stream));
-      hipLaunchKernelGGL(x3_index_candidates_kernel<false>, dim3(grid), dim3(256), 0, c->stream, xw, len, len + phantom, bl0,
-                         (X3Cand*)c->idx_cand.p, n_cand, d_count, (unsigned long long*)nullptr, (uint32_t*)nullptr);
+      HIPCHK(c, hipMemsetAsync(w.d_count, 0, sizeof(unsigned int), c->stream));
+      hipLaunchKernelGGL(x3_index_candidates_kernel<false>, dim3(w.grid), dim3(256), 0, c->stream, xw, len, len + phantom, bl0,
+                         (X3Cand*)c->idx_cand.p, n_cand, w.d_count, (unsigned long long*)nullptr, (uint32_t*)nullptr);
     }
   }
   c->index_last_cands = n_cand;
@@ -436,16 +452,16 @@ static int index_dev_impl(x3_ctx* c, const uint8_t* d_x3, uint64_t len, uint64_t
     hipLaunchKernelGGL(x3_index_emit_kernel, dim3(cg), dim3(256), 0, c->stream, (const X3Cand*)cand, n_cand, levels,
                        (const uint32_t*)J, (const unsigned long long*)S, (unsigned long long)max_frames,
                        (unsigned long long)wav_cap, (unsigned long long*)d_frame_offsets,
-                       (unsigned long long*)d_wav_offsets, d_sum, (const unsigned long long*)keys, (const uint32_t*)vals,
+                       (unsigned long long*)d_wav_offsets, w.d_sum, (const unsigned long long*)keys, (const uint32_t*)vals,
                        tsize - 1, (const uint32_t*)(L + (size_t)(levels - 1) * n_cand));
     hipLaunchKernelGGL(x3_index_finalize_kernel, dim3(1), dim3(64), 0, c->stream, xw, len, len + phantom, bl0,
-                       (const X3Cand*)cand, (const unsigned long long*)d_wav_offsets, d_sum);
+                       (const X3Cand*)cand, (const unsigned long long*)d_wav_offsets, w.d_sum);
   } else {
     hipLaunchKernelGGL(x3_index_finalize_kernel, dim3(1), dim3(64), 0, c->stream, xw, len, len + phantom, bl0,
-                       (const X3Cand*)nullptr, (const unsigned long long*)nullptr, d_sum);
+                       (const X3Cand*)nullptr, (const unsigned long long*)nullptr, w.d_sum);
   }
   HIPCHK(c, hipGetLastError());
-  return index_summary(c, d_sum, result);
+  return index_summary(c, w.d_sum, result);
 }
 
 extern "C" int x3_index_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t len, uint64_t max_frames,
@@ -462,6 +478,21 @@ extern "C" int x3_index_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t len, uint64
   return X3_OK;
 }
 
+// The walk of a whole stream into c->frame_off / c->wav_off, whose sizes are not known before the candidate count: a cap of
+// 2^20 frames first, and a stream with more once again with its upper bound (every frame is at least 22 bytes).
+static int index_all_frames(x3_ctx* c, const uint8_t* d_x3, uint64_t len, uint64_t phantom, uint32_t bl0, uint64_t wav_cap,
+                            X3IndexSummary* r) {
+  const uint64_t max_frames = len / 22 + 1;
+  uint64_t cap_frames = std::min<uint64_t>(max_frames, 1u << 20);
+  for (;;) {
+    int rc;
+    if ((rc = ensure(c, c->frame_off, (cap_frames + 1) * sizeof(uint64_t)))) return rc;
+    if ((rc = ensure(c, c->wav_off, cap_frames * sizeof(uint64_t)))) return rc;
+    rc = index_dev_impl(c, d_x3, len, phantom, bl0, wav_cap, cap_frames, (uint64_t*)c->frame_off.p, (uint64_t*)c->wav_off.p, r);
+    if (rc != X3_ERR_BAD_ARG || cap_frames == max_frames) return rc;
+    cap_frames = max_frames;
+  }
+}
 
 extern "C" int x3_decode_stream_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t len, const x3_params* p, int16_t* d_wav,
                                     uint64_t wav_cap, uint64_t* n_out, uint64_t* frames_ok, uint64_t* frame_errors) {
@@ -481,13 +512,8 @@ extern "C" int x3_decode_stream_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t len
 int decode_stream_dev_impl(x3_ctx* c, const uint8_t* d_x3, uint64_t len, uint64_t phantom, const x3_params* p,
                                   int16_t* d_wav, uint64_t wav_cap, DevBuf* own_out, uint64_t* n_out,
                                   uint64_t* frames_ok, uint64_t* frame_errors) {
-  // every frame is at least 22 bytes; index into internal buffers sized for the real count
-  const uint64_t max_frames = len / 22 + 1;
   int rc;
   X3IndexSummary r;
-  // sizes are not known before the candidate count: index_dev_impl sizes its own scratch, the two output arrays
-  // are sized here from an upper bound that is refined by a first call when it is large
-  uint64_t cap_frames = std::min<uint64_t>(max_frames, 1u << 20);
   // ---- ONE trip to the host (round 5).  A stream that is one clean chain of frames -- what an encoder
   // writes -- is walked by five launches that leave the frame count on the device; the decoder, the check pass and the merge
   // are enqueued right behind them with a grid for an upper bound of the count (a frame per KiB of stream) and read the
@@ -495,7 +521,7 @@ int decode_stream_dev_impl(x3_ctx* c, const uint8_t* d_x3, uint64_t len, uint64_
   // summary then objects to -- not a clean chain, more frames than the bound, sample offsets off the 8-byte grid -- is done
   // again the old way (the walk, a trip, the decode, a trip): the speculative decode wrote nothing that is not rewritten.
   {
-    const uint64_t bound = std::min<uint64_t>(cap_frames, len / 1024 + 64);
+    const uint64_t bound = std::min<uint64_t>(std::min<uint64_t>(len / 22 + 1, 1u << 20), len / 1024 + 64);
     // (parameters of fewer than 2 048 samples a frame do not try: frames that short often come more than one per KiB of
     // stream, the bound below then fails, and every call would pay the speculative launches and a sync before it takes the
     // two trips anyway -- ADVICE r5.  The gate is the parameters', the bound the stream's: quiet or zero content at 2 048
@@ -509,59 +535,47 @@ int decode_stream_dev_impl(x3_ctx* c, const uint8_t* d_x3, uint64_t len, uint64_
     if (try_one) {
       if ((rc = ensure(c, c->frame_off, (bound + 1) * sizeof(uint64_t)))) return rc;
       if ((rc = ensure(c, c->wav_off, bound * sizeof(uint64_t)))) return rc;
-      X3IndexSummary* ds = nullptr;
-      rc = index_fast_launch(c, d_x3, len, phantom, 0u, wav_cap, bound, (uint64_t*)c->frame_off.p, (uint64_t*)c->wav_off.p, &ds);
+      IndexWords iw;
+      if ((rc = index_words(c, len, &iw))) return rc;
+      rc = index_fast_launch(c, d_x3, len, phantom, 0u, wav_cap, bound, (uint64_t*)c->frame_off.p, (uint64_t*)c->wav_off.p, iw);
+      if (rc == X3_OK)
+        rc = decode_dev_impl(c, d_x3, len, (const uint64_t*)c->frame_off.p, bound, nullptr, (const uint64_t*)c->wav_off.p, p,
+                             d_wav, wav_cap, nullptr, true, false, nullptr, &iw.d_sum->n_frames);
       if (rc == X3_OK) {
-        x3_params pq = *p;
-        rc = decode_dev_impl(c, d_x3, len, (const uint64_t*)c->frame_off.p, bound, nullptr, (const uint64_t*)c->wav_off.p, &pq,
-                             d_wav, wav_cap, nullptr, true, false, nullptr, &ds->n_frames);
-        if (rc == X3_OK) {
-          HIPCHK(c, hipMemcpyAsync(c->h_summary_init, ds, sizeof(X3IndexSummary), hipMemcpyDeviceToHost, c->stream));  // (pinned)
-          HIPCHK(c, hipMemcpyAsync(c->h_summary, c->d_summary, sizeof(X3DecodeSummary), hipMemcpyDeviceToHost, c->stream));
-          HIPCHK(c, hipStreamSynchronize(c->stream));
-          std::memcpy(&r, c->h_summary_init, sizeof r);
-          c->decode_pending = false;
-          if (!r.pad && !r.pad2 && !r.unaligned && r.n_frames <= bound) {
-            ++c->index_fast;
-            ++c->stream_one_trip;
-            const uint64_t F1 = r.n_frames;
-            if (F1 == 0) return r.terminal;
-            uint64_t first_bad = c->h_summary->first_bad, before = c->h_summary->samples_before;
-            int bad_status = c->h_summary->first_bad_status;
-            if (first_bad < F1) {   // rare: a frame is bad -- its status and the samples of the good frames before it
-              c->dec_frames = F1;
-              c->decode_pending = true;
-              if ((rc = x3_decode_result(c, &first_bad, &bad_status, &before))) return rc;   // (counts the replays)
-            } else {
-              c->last_decode_replays = c->h_summary->replays;
-              c->decode_replays += c->h_summary->replays;
-            }
-            if (n_out) *n_out = before;
-            if (frames_ok) *frames_ok = first_bad;
-            return walk_result(F1, first_bad, bad_status, r.terminal, frame_errors);
+        HIPCHK(c, hipMemcpyAsync(c->h_summary_init, iw.d_sum, sizeof(X3IndexSummary), hipMemcpyDeviceToHost, c->stream));  // (pinned)
+        HIPCHK(c, hipMemcpyAsync(c->h_summary, c->d_summary, sizeof(X3DecodeSummary), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        std::memcpy(&r, c->h_summary_init, sizeof r);
+        c->decode_pending = false;
+        if (!r.pad && !r.pad2 && !r.unaligned && r.n_frames <= bound) {
+          ++c->index_fast;
+          ++c->stream_one_trip;
+          const uint64_t F1 = r.n_frames;
+          if (F1 == 0) return r.terminal;
+          uint64_t first_bad = c->h_summary->first_bad, before = c->h_summary->samples_before;
+          int bad_status = c->h_summary->first_bad_status;
+          if (first_bad < F1) {   // rare: a frame is bad -- its status and the samples of the good frames before it
+            c->dec_frames = F1;
+            c->decode_pending = true;
+            if ((rc = x3_decode_result(c, &first_bad, &bad_status, &before))) return rc;   // (counts the replays)
+          } else {
+            c->last_decode_replays = c->h_summary->replays;
+            c->decode_replays += c->h_summary->replays;
           }
-        } else if (rc != X3_ERR_BAD_ARG) {
-          return rc;
+          if (n_out) *n_out = before;
+          if (frames_ok) *frames_ok = first_bad;
+          return walk_result(F1, first_bad, bad_status, r.terminal, frame_errors);
         }
       } else if (rc != X3_ERR_BAD_ARG) {
         return rc;
       }
     }
   }
-  for (;;) {
-    if ((rc = ensure(c, c->frame_off, (cap_frames + 1) * sizeof(uint64_t)))) return rc;
-    if ((rc = ensure(c, c->wav_off, cap_frames * sizeof(uint64_t)))) return rc;
-    rc = index_dev_impl(c, d_x3, len, phantom, p->block_len == 0 ? 1u : 0u, wav_cap, cap_frames, (uint64_t*)c->frame_off.p,
-                        (uint64_t*)c->wav_off.p, &r);
-    if (rc == X3_ERR_BAD_ARG && cap_frames < max_frames) { cap_frames = max_frames; continue; }
-    break;
-  }
-  if (rc) return rc;
+  if ((rc = index_all_frames(c, d_x3, len, phantom, p->block_len == 0 ? 1u : 0u, wav_cap, &r))) return rc;
   const uint64_t F = r.n_frames;
   const int terminal = r.terminal;
   if (F == 0) return terminal;
-  x3_params pp = *p;
-  if (pp.block_len == 0) pp.block_len = 1;  // frames that need block_len are BAD_ARG frames of the index
+  const x3_params pp = decoder_params(p);
   if (own_out) {
     if ((rc = ensure(c, *own_out, (r.n_samples + 65536) * sizeof(int16_t)))) return rc;
     d_wav = (int16_t*)own_out->p;
@@ -659,8 +673,7 @@ int decode_frames_host(x3_ctx* c, const uint8_t* x3, uint64_t len, const HostWal
   std::memcpy((uint64_t*)c->h_walk + F, w.woffs.data(), F * sizeof(uint64_t));
   HIPCHK(c, hipMemcpyAsync(c->frame_off.p, c->h_walk, F * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->wav_off.p, (uint64_t*)c->h_walk + F, F * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-  x3_params pp = *p;
-  if (pp.block_len == 0) pp.block_len = 1;  // frames that need block_len were routed to BAD_ARG by the walk
+  const x3_params pp = decoder_params(p);
   const uint64_t dev_wav_cap = std::min<uint64_t>(wav_cap, w.nsamp + 65535);
   bool aligned = true;
   for (uint64_t v : w.woffs) aligned = aligned && (v & 3ull) == 0;   // (rows on the 8-byte grid)
@@ -903,8 +916,7 @@ static int decode_frame_impl(x3_ctx* c, const uint8_t* payload, uint64_t len, in
     // decode_frame itself has no such limits: the reference's reader, one thread (x3_decode_replay.h)
     if (samples > 0xFFFFFFFFull || len > 0xFFFFFFFFull) return X3_ERR_BAD_ARG;
     X3DevParams dpr;
-    x3_params pr = *p;
-    if (pr.block_len == 0) pr.block_len = 1;
+    const x3_params pr = decoder_params(p);
     if ((rc = derive(&pr, 0, &dpr))) return rc;
     if (bl0) dpr.block_len = 0;
     if ((rc = ensure(c, c->in, len + 16))) return rc;
@@ -945,8 +957,7 @@ static int decode_frame_impl(x3_ctx* c, const uint8_t* payload, uint64_t len, in
   HIPCHK(c, hipMemcpyAsync(c->in.p, hdr, 20, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->frame_off.p, &zero, sizeof zero, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->wav_off.p, &zero, sizeof zero, hipMemcpyHostToDevice, c->stream));
-  x3_params pp = *p;
-  if (pp.block_len == 0) pp.block_len = 1;
+  const x3_params pp = decoder_params(p);
   if ((rc = decode_dev_impl(c, (const uint8_t*)c->in.p, 20 + len, (const uint64_t*)c->frame_off.p, 1, nullptr,
                             (const uint64_t*)c->wav_off.p, &pp, (int16_t*)c->out.p, samples, nullptr)))
     return rc;
@@ -1021,10 +1032,8 @@ extern "C" int x3_place_buffers(x3_ctx* c, const int16_t* d_wav, uint64_t n, con
 extern "C" int x3_sample_offsets_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
                                      uint64_t n_frames, uint64_t* d_sample_offsets) {
   if (!c || !d_x3 || !d_frame_offsets || !d_sample_offsets) return X3_ERR_BAD_ARG;
-  if ((reinterpret_cast<uintptr_t>(d_x3) & 3u) || (reinterpret_cast<uintptr_t>(d_frame_offsets) & 7u) ||
-      (reinterpret_cast<uintptr_t>(d_sample_offsets) & 7u))
+  if (!frame_table_args_ok(d_x3, d_frame_offsets, n_frames) || (reinterpret_cast<uintptr_t>(d_sample_offsets) & 7u))
     return X3_ERR_BAD_ARG;
-  if (n_frames == 0 || n_frames > 0x7FFFFFFFull) return X3_ERR_BAD_ARG;
   HIPCHK(c, hipSetDevice(c->device));
   hipLaunchKernelGGL(x3_window_sample_offsets_kernel, dim3(1), dim3(1024), 0, c->stream, d_x3, x3_len, d_frame_offsets,
                      n_frames, d_sample_offsets);
@@ -1099,16 +1108,13 @@ extern "C" int x3_decode_windows_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3
                                      uint64_t n_windows, uint32_t window_len, void* d_out, int out_format, int32_t* d_status) {
   if (!c || !d_x3 || !d_frame_offsets || !d_sample_offsets || !p) return X3_ERR_BAD_ARG;
   if (!windows_args_ok(n_windows, window_len, d_out, out_format, d_starts, d_status)) return X3_ERR_BAD_ARG;
-  if ((reinterpret_cast<uintptr_t>(d_x3) & 3u) || (reinterpret_cast<uintptr_t>(d_frame_offsets) & 7u) ||
-      (reinterpret_cast<uintptr_t>(d_sample_offsets) & 7u))
+  if (!frame_table_args_ok(d_x3, d_frame_offsets, n_frames) || (reinterpret_cast<uintptr_t>(d_sample_offsets) & 7u))
     return X3_ERR_BAD_ARG;
   if (d_seg_index && !seg_index_args_ok(d_seg_index, seg_blocks)) return X3_ERR_BAD_ARG;
-  if (n_frames == 0 || n_frames > 0x7FFFFFFFull) return X3_ERR_BAD_ARG;
   X3DevParams dp;
   const uint64_t spf = spf_of(p);
-  int rc = derive_params(p, &dp);
+  int rc = derive_block_params(p, &dp);
   if (rc) return rc;
-  if (dp.block_len == 0 || dp.blocks_per_frame == 0) return X3_ERR_BAD_ARG;
   HIPCHK(c, hipSetDevice(c->device));
   return windows_launch(c, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, dp, spf, d_seg_index, seg_blocks, n_windows,
                         window_len, d_out, out_format, d_status,
@@ -1152,13 +1158,10 @@ static int seg_index_launch(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, con
 extern "C" int x3_seg_index_build_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
                                       uint64_t n_frames, const x3_params* p, uint64_t* d_seg_index, uint32_t seg_blocks) {
   if (!c || !d_x3 || !d_frame_offsets || !p || !d_seg_index) return X3_ERR_BAD_ARG;
-  if ((reinterpret_cast<uintptr_t>(d_x3) & 3u) || (reinterpret_cast<uintptr_t>(d_frame_offsets) & 7u)) return X3_ERR_BAD_ARG;
-  if (!seg_index_args_ok(d_seg_index, seg_blocks)) return X3_ERR_BAD_ARG;
-  if (n_frames == 0 || n_frames > 0x7FFFFFFFull) return X3_ERR_BAD_ARG;
+  if (!frame_table_args_ok(d_x3, d_frame_offsets, n_frames) || !seg_index_args_ok(d_seg_index, seg_blocks)) return X3_ERR_BAD_ARG;
   X3DevParams dp;
-  int rc = derive_params(p, &dp);
+  int rc = derive_block_params(p, &dp);
   if (rc) return rc;
-  if (dp.block_len == 0 || dp.blocks_per_frame == 0) return X3_ERR_BAD_ARG;
   HIPCHK(c, hipSetDevice(c->device));
   return seg_index_launch(c, d_x3, x3_len, d_frame_offsets, n_frames, dp, d_seg_index, seg_blocks);
 }
@@ -1168,74 +1171,144 @@ extern "C" int x3_seg_index_build_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x
 // ------------------------------------------------------------------------------------------------
 #include "x3_streams_kernel.h"
 
-// where the pieces of a call lie in its buffers
-struct StreamsLayout {
-  uint64_t* eoff; uint64_t* elen; uint32_t* span_first;                        // st_tab
-  X3IndexSummary* isum; X3StreamsSum* sum;                                     // st_scan: summaries, then the scans
-  unsigned int* cnt; uint32_t* base; unsigned long long* samp; unsigned long long* sbase;
-  unsigned long long* frame_off; unsigned long long* wav_off; int32_t* status; uint32_t* fent;   // st_frames (cap words)
-  unsigned long long* ent_bad; unsigned long long* ent_end; unsigned long long* ent_nsamp; unsigned long long* nout;
-  uint32_t* ent_flags; uint32_t* dirty;                                         // st_ent
+// ---- THE SEGMENTED WALK: every entry's frames by one launch set, for the batch decode and for the corpus build alike
+static uint64_t seg_cands(uint64_t G) { return std::max<uint64_t>(G * X3I_WG_CANDS, 1); }   // candidate slots of G spans
+
+int seg_entries(const uint64_t* offsets, const uint64_t* lengths, uint64_t n, uint64_t x3_len, std::vector<uint32_t>* span_first,
+                uint64_t* G, uint64_t* bytes) {
+  auto spans = [](uint64_t len) { return (len + X3T_SPAN_BYTES - 1) / X3T_SPAN_BYTES; };
+  *G = *bytes = 0;
+  for (uint64_t e = 0; e < n; ++e) {
+    if (offsets[e] > x3_len || lengths[e] > x3_len - offsets[e]) return X3_ERR_BAD_ARG;
+    *G += spans(lengths[e]);
+    *bytes += lengths[e];
+    if (*G > 0x7FFFFFFFull / X3I_WG_CANDS) return X3_ERR_BAD_ARG;   // (refused here: neither sum can wrap)
+  }
+  span_first->assign(n + 1, 0);
+  for (uint64_t e = 0; e < n; ++e) (*span_first)[e + 1] = (*span_first)[e] + (uint32_t)spans(lengths[e]);
+  return X3_OK;
+}
+
+// the pieces of one block, each a multiple of 256 bytes behind its base
+struct SegCarver {
+  char* base; size_t at;
+  template <class T> T* take(uint64_t count, size_t round = 256) {   // (round 1: the next piece follows directly)
+    T* const piece = reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(base) + at);
+    at = (at + count * sizeof(T) + round - 1) & ~(round - 1);
+    return piece;
+  }
 };
 
-static StreamsLayout streams_layout(x3_ctx* c, uint64_t n, uint64_t G) {
-  StreamsLayout l;
-  const uint64_t cap = G * X3I_WG_CANDS;
-  l.eoff = (uint64_t*)c->st_tab.p;
-  l.elen = l.eoff + n;
-  l.span_first = (uint32_t*)(l.elen + n);
-  l.isum = (X3IndexSummary*)c->st_scan.p;
-  l.sum = (X3StreamsSum*)((char*)c->st_scan.p + 128);
-  l.cnt = (unsigned int*)((char*)c->st_scan.p + 256);
-  l.base = (uint32_t*)(l.cnt + G);
-  l.samp = (unsigned long long*)(l.base + G);
-  l.sbase = l.samp + G;
-  l.frame_off = (unsigned long long*)c->st_frames.p;
-  l.wav_off = l.frame_off + cap;
-  l.status = (int32_t*)(l.wav_off + cap);
-  l.fent = (uint32_t*)(l.status + cap);
-  l.ent_bad = (unsigned long long*)c->st_ent.p;
-  l.ent_end = l.ent_bad + n;
-  l.ent_nsamp = l.ent_end + n;
-  l.nout = l.ent_nsamp + n;
-  l.ent_flags = (uint32_t*)(l.nout + n);
-  l.dirty = l.ent_flags + n;
-  return l;
+size_t segwalk_carve(char* base, uint64_t n, uint64_t G, SegWalkWs* w) {
+  const uint64_t cap = seg_cands(G);
+  SegCarver k{base, 0};
+  w->eoff = k.take<uint64_t>(n, 1);   // eoff | elen | span_first back to back: segwalk_launch uploads them in one copy
+  w->elen = k.take<uint64_t>(n, 1);
+  w->span_first = k.take<uint32_t>(n + 1);
+  w->isum = k.take<X3IndexSummary>(1);
+  w->cnt = k.take<unsigned int>(G);
+  w->base = k.take<uint32_t>(G);
+  w->samp = k.take<unsigned long long>(G);
+  w->sbase = k.take<unsigned long long>(G);
+  w->cand = k.take<X3Cand>(cap);
+  w->frame_off = k.take<unsigned long long>(cap);
+  w->wav_off = k.take<unsigned long long>(cap);
+  w->fent = k.take<uint32_t>(cap);
+  w->ent_flags = k.take<uint32_t>(n);
+  w->ent_end = k.take<unsigned long long>(n);
+  w->ent_nsamp = k.take<unsigned long long>(n);
+  return k.at;
+}
+
+// Enqueues the walk over a validated entry table: the table to the device (src_tab_upload), a clean summary and clean entry
+// flags, then the candidates, the scans and the links; no kernel for a table without bytes.  row_len and x4 are those of the
+// decode launch the frame table is for.  The INDEX form is row_len ~0 and no four-sample grid: every frame the walk steps
+// over is live.
+static int segwalk_launch(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* offsets, const uint64_t* lengths,
+                          const std::vector<uint32_t>& span_first, uint64_t phantom, uint64_t row_len, uint32_t x4,
+                          const SegWalkWs& w) {
+  const uint64_t n = span_first.size() - 1, G = span_first[n];
+  int rc;
+  if ((rc = src_tab_upload(c, w.eoff, {{offsets, 8 * n}, {lengths, 8 * n}, {span_first.data(), 4 * (n + 1)}}))) return rc;
+  HIPCHK(c, hipMemsetAsync(w.isum, 0, sizeof(X3IndexSummary), c->stream));
+  HIPCHK(c, hipMemsetAsync(w.ent_flags, 0, 4 * n, c->stream));
+  if (G) {
+    hipLaunchKernelGGL(x3_streams_candidates_kernel, dim3((unsigned)G), dim3(256), 0, c->stream,
+                       reinterpret_cast<const uint32_t*>(d_x3), x3_len, w.eoff, w.elen, w.span_first, (uint32_t)n, phantom,
+                       w.cand, w.cnt, w.samp, w.ent_flags);
+    hipLaunchKernelGGL(x3_index_chain_kernel, dim3(1), dim3(1024), 0, c->stream, w.cnt, w.samp, (uint32_t)G, w.base, w.sbase,
+                       w.isum);
+    hipLaunchKernelGGL(x3_streams_link_kernel, dim3((unsigned)G), dim3(64), 0, c->stream, w.cand, w.cnt, w.base, w.sbase, w.eoff,
+                       w.span_first, (uint32_t)n, x3_len, row_len, x4, w.frame_off, w.wav_off, w.fent, w.ent_flags, w.ent_end,
+                       w.ent_nsamp);
+  }
+  HIPCHK(c, hipGetLastError());
+  return X3_OK;
+}
+
+// an entry of a batch on a 4-byte boundary of its own (st_one), for the walks that take one stream
+static int entry_copy(x3_ctx* c, const uint8_t* d_x3, uint64_t off, uint64_t len) {
+  const int rc = ensure(c, c->st_one, len + 64);
+  if (rc == X3_OK && len) HIPCHK(c, hipMemcpyAsync(c->st_one.p, d_x3 + off, len, hipMemcpyDeviceToDevice, c->stream));
+  return rc;
+}
+
+// ---- the batch decode.  A call's block (st_walk): the walk's workspace, then the call's own words (StreamsWs)
+size_t streams_carve(char* base, uint64_t n, uint64_t G, StreamsWs* s) {
+  SegCarver k{base, segwalk_carve(base, n, G, s)};
+  s->sum = k.take<X3StreamsSum>(1);
+  s->status = k.take<int32_t>(seg_cands(G));
+  s->ent_bad = k.take<unsigned long long>(n);
+  s->nout = k.take<unsigned long long>(n);
+  s->dirty = k.take<uint32_t>(n);
+  return k.at;
+}
+
+// x3_streams_rows_kernel for either format: float32 rows from the int16 rows at ws, or int16 rows zeroed in place from
+// their sample counts on (ws is not read)
+static void streams_rows_launch(x3_ctx* c, dim3 grid, int fmt, const int16_t* ws, void* out, uint64_t n, uint64_t row_len,
+                                const unsigned long long* nout, unsigned long long no_value, const X3StreamsSum* sum) {
+  auto* const rows = fmt == X3_WINDOW_F32 ? x3_streams_rows_kernel<true> : x3_streams_rows_kernel<false>;
+  hipLaunchKernelGGL(rows, grid, dim3(256), 0, c->stream, ws, out, n, row_len, nout, no_value, sum);
+}
+
+// the walk's candidate count and, with `sum`, the call's summary: one wait (through the pinned block, 128 bytes apart)
+static int streams_fetch(x3_ctx* c, const StreamsWs& l, unsigned long long* total, X3StreamsSum* sum) {
+  char* const h = (char*)c->h_summary_init;
+  HIPCHK(c, hipMemcpyAsync(h, l.isum, sizeof(X3IndexSummary), hipMemcpyDeviceToHost, c->stream));
+  if (sum) HIPCHK(c, hipMemcpyAsync(h + 128, l.sum, sizeof *sum, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  *total = reinterpret_cast<const X3IndexSummary*>(h)->n_chain;
+  if (sum) std::memcpy(sum, h + 128, sizeof *sum);
+  return X3_OK;
 }
 
 // decode launch over frames [0, F) of the table (d_nf: the count on the device, or nullptr when F is the count), then the
 // per-entry verdicts and the rows
 static int streams_finish(x3_ctx* c, uint64_t F, bool device_count) {
   auto& s = c->streams;
-  const StreamsLayout l = streams_layout(c, s.n, s.G);
+  StreamsWs l;
+  streams_carve((char*)c->st_walk.p, s.n, s.G, &l);
   const uint64_t total_samples = s.n * s.row_len;
   int16_t* d_wav = s.fmt == X3_WINDOW_F32 ? (int16_t*)c->st_ws.p : (int16_t*)s.d_out;
   const unsigned long long* d_nf = &l.isum->n_chain;
   int rc;
   if (F) {
-    x3_params pp = s.p;
-    if ((rc = decode_dev_impl(c, s.d_x3, s.x3_len, (const uint64_t*)l.frame_off, F, nullptr, (const uint64_t*)l.wav_off, &pp,
+    if ((rc = decode_dev_impl(c, s.d_x3, s.x3_len, (const uint64_t*)l.frame_off, F, nullptr, (const uint64_t*)l.wav_off, &s.p,
                               d_wav, total_samples, l.status, s.row_len % 4u == 0, false, nullptr,
                               device_count ? d_nf : nullptr)))
       return rc;
     c->decode_pending = false;   // (the merge kernel's summary is not this call's result)
     hipLaunchKernelGGL(x3_streams_firstbad_kernel, dim3((unsigned)std::min<uint64_t>((F + 255) / 256, 4096)), dim3(256), 0,
-                       c->stream, (const int32_t*)l.status, (const uint32_t*)l.fent, F, d_nf, l.ent_bad);
+                       c->stream, l.status, l.fent, F, d_nf, l.ent_bad);
   }
   hipLaunchKernelGGL(x3_streams_resolve_kernel, dim3((unsigned)((s.n + 255) / 256)), dim3(256), 0, c->stream,
-                     reinterpret_cast<const uint32_t*>(s.d_x3), s.x3_len, (const uint64_t*)l.eoff, (const uint64_t*)l.elen,
-                     (const uint32_t*)l.span_first, (uint32_t)s.n, s.phantom, (const uint32_t*)l.base, (uint32_t)s.G, d_nf, F,
-                     (const int32_t*)l.status, (const unsigned long long*)l.wav_off, (const uint32_t*)l.ent_flags,
-                     (const unsigned long long*)l.ent_bad, (const unsigned long long*)l.ent_end,
-                     (const unsigned long long*)l.ent_nsamp, s.row_len, s.d_results, l.nout, l.dirty, l.sum);
+                     reinterpret_cast<const uint32_t*>(s.d_x3), s.x3_len, l.eoff, l.elen, l.span_first, (uint32_t)s.n, s.phantom,
+                     l.base, (uint32_t)s.G, d_nf, F, l.status, l.wav_off, l.ent_flags, l.ent_bad, l.ent_end, l.ent_nsamp,
+                     s.row_len, s.d_results, l.nout, l.dirty, l.sum);
   const dim3 rg((unsigned)std::min<uint64_t>((s.row_len + 255) / 256, s.fmt == X3_WINDOW_F32 ? 64 : 8),
                 (unsigned)std::min<uint64_t>(s.n, 65535));
-  if (s.fmt == X3_WINDOW_F32)
-    hipLaunchKernelGGL(x3_streams_rows_kernel<true>, rg, dim3(256), 0, c->stream, (const int16_t*)c->st_ws.p, s.d_out, s.n,
-                       s.row_len, (const unsigned long long*)l.nout, 0ull, (const X3StreamsSum*)l.sum);
-  else
-    hipLaunchKernelGGL(x3_streams_rows_kernel<false>, rg, dim3(256), 0, c->stream, (const int16_t*)nullptr, s.d_out, s.n,
-                       s.row_len, (const unsigned long long*)l.nout, 0ull, (const X3StreamsSum*)l.sum);
+  streams_rows_launch(c, rg, s.fmt, (const int16_t*)c->st_ws.p, s.d_out, s.n, s.row_len, l.nout, 0ull, l.sum);
   HIPCHK(c, hipGetLastError());
   return X3_OK;
 }
@@ -1252,13 +1325,9 @@ extern "C" int x3_decode_streams_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3
     return X3_ERR_BAD_ARG;
   if (row_len > (~0ull / 4) / n) return X3_ERR_BAD_ARG;
   if (x3_params_validate(p) != X3_OK) return X3_ERR_BAD_ARG;
+  std::vector<uint32_t> span_first;
   uint64_t G = 0, bytes = 0;
-  for (uint64_t e = 0; e < n; ++e) {
-    if (offsets[e] > x3_len || lengths[e] > x3_len - offsets[e]) return X3_ERR_BAD_ARG;
-    G += (lengths[e] + X3T_SPAN_BYTES - 1) / X3T_SPAN_BYTES;
-    bytes += lengths[e];
-  }
-  if (G > 0x7FFFFFFFull / X3I_WG_CANDS) return X3_ERR_BAD_ARG;
+  if (seg_entries(offsets, lengths, n, x3_len, &span_first, &G, &bytes)) return X3_ERR_BAD_ARG;
   HIPCHK(c, hipSetDevice(c->device));
   auto& s = c->streams;
   s.pending = false;
@@ -1274,83 +1343,38 @@ extern "C" int x3_decode_streams_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3
   s.G = G;
   s.off.assign(offsets, offsets + n);
   s.len.assign(lengths, lengths + n);
-  s.span_first.resize(n + 1);
-  s.span_first[0] = 0;
-  for (uint64_t e = 0; e < n; ++e) s.span_first[e + 1] = s.span_first[e] + (uint32_t)((lengths[e] + X3T_SPAN_BYTES - 1) / X3T_SPAN_BYTES);
   c->decode_pending = false;
   // Block length 0 (frames of one sample, decided by block types alone) and option "index_no_fast": every entry takes the
   // general walk at result time.
   s.all_general = p->block_len == 0 || c->opt.index_no_fast != 0;
   int rc;
-  if ((rc = ensure(c, c->st_tab, 16 * n + 4 * (n + 1) + 16))) return rc;
-  if ((rc = ensure(c, c->st_scan, 256 + 24 * G + 64))) return rc;
-  if ((rc = ensure(c, c->st_ent, 40 * n + 64))) return rc;
-  const uint64_t cap = std::max<uint64_t>(G * X3I_WG_CANDS, 1);
-  if ((rc = ensure(c, c->st_frames, 24 * cap + 64))) return rc;
-  if ((rc = ensure(c, c->st_cand, cap * sizeof(X3Cand) + 64))) return rc;
+  StreamsWs l;
+  if ((rc = ensure(c, c->st_walk, streams_carve(nullptr, n, G, &l)))) return rc;
   if (out_format == X3_WINDOW_F32 && (rc = ensure(c, c->st_ws, 2 * n * row_len + 64))) return rc;
-  const StreamsLayout l = streams_layout(c, n, G);
   if (s.all_general) {
-    s.F = 0;
     s.pending = true;
     return X3_OK;
   }
-  // the entry table through the context's pinned block (x3_encode_frames_dev's way)
-  const size_t tab_bytes = 16 * n + 4 * (n + 1);
-  if (c->ev_src_tab) HIPCHK(c, hipEventSynchronize(c->ev_src_tab));
-  else HIPCHK(c, hipEventCreateWithFlags(&c->ev_src_tab, hipEventDisableTiming));
-  if (c->h_src_tab_cap < tab_bytes) {
-    if (c->h_src_tab) (void)hipHostFree(c->h_src_tab);
-    c->h_src_tab = nullptr;
-    c->h_src_tab_cap = 0;
-    HIPCHK(c, hipHostMalloc(&c->h_src_tab, tab_bytes + tab_bytes / 4 + 64));
-    c->h_src_tab_cap = tab_bytes + tab_bytes / 4 + 64;
-  }
-  std::memcpy(c->h_src_tab, offsets, 8 * n);
-  std::memcpy((char*)c->h_src_tab + 8 * n, lengths, 8 * n);
-  std::memcpy((char*)c->h_src_tab + 16 * n, s.span_first.data(), 4 * (n + 1));
-  HIPCHK(c, hipMemcpyAsync(c->st_tab.p, c->h_src_tab, tab_bytes, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipEventRecord(c->ev_src_tab, c->stream));
-  // clean per-call state: the summaries (bad_first = all ones), the entries' flags and first failing frames
-  HIPCHK(c, hipMemsetAsync(c->st_scan.p, 0, 256, c->stream));
+  streams_carve((char*)c->st_walk.p, n, G, &l);
+  const uint32_t x4 = row_len % 4u == 0 ? 1u : 0u;
+  if ((rc = segwalk_launch(c, d_x3, x3_len, offsets, lengths, span_first, s.phantom, row_len, x4, l))) return rc;
+  // the call's own clean state: its summary (bad_first = all ones) and the entries' first failing frames
+  HIPCHK(c, hipMemsetAsync(l.sum, 0, sizeof(X3StreamsSum), c->stream));
   HIPCHK(c, hipMemsetAsync(&l.sum->bad_first, 0xFF, 8, c->stream));
   HIPCHK(c, hipMemsetAsync(l.ent_bad, 0xFF, 8 * n, c->stream));
-  HIPCHK(c, hipMemsetAsync(l.ent_flags, 0, 4 * n, c->stream));
-  const uint32_t x4 = row_len % 4u == 0 ? 1u : 0u;
-  if (G) {
-    hipLaunchKernelGGL(x3_streams_candidates_kernel, dim3((unsigned)G), dim3(256), 0, c->stream,
-                       reinterpret_cast<const uint32_t*>(d_x3), x3_len, (const uint64_t*)l.eoff, (const uint64_t*)l.elen,
-                       (const uint32_t*)l.span_first, (uint32_t)n, s.phantom, (X3Cand*)c->st_cand.p, l.cnt, l.samp,
-                       l.ent_flags);
-    hipLaunchKernelGGL(x3_index_chain_kernel, dim3(1), dim3(1024), 0, c->stream, (const unsigned int*)l.cnt,
-                       (const unsigned long long*)l.samp, (uint32_t)G, l.base, l.sbase, l.isum);
-    hipLaunchKernelGGL(x3_streams_link_kernel, dim3((unsigned)G), dim3(64), 0, c->stream, (const X3Cand*)c->st_cand.p,
-                       (const unsigned int*)l.cnt, (const uint32_t*)l.base, (const unsigned long long*)l.sbase,
-                       (const uint64_t*)l.eoff, (const uint32_t*)l.span_first, (uint32_t)n, x3_len, row_len, x4, l.frame_off,
-                       l.wav_off, l.fent, l.ent_flags, l.ent_end, l.ent_nsamp);
-    HIPCHK(c, hipGetLastError());
-  }
   // The decode launch covers a bound on the frame count (a frame per KiB of entry, as x3_decode_stream_dev's one-trip
   // path bounds it) and reads the real count from the device; a batch with more is launched again, with the count, by
   // x3_decode_streams_result.  A decoder that cannot read the count from the device: one wait for it, here.
   X3DevParams dq;
-  const uint64_t bound = std::min<uint64_t>(cap, bytes / 1024 + n + 64);
+  const uint64_t bound = std::min<uint64_t>(seg_cands(G), bytes / 1024 + n + 64);
   const bool dev_count = G && derive_params(p, &dq) == X3_OK &&
                          decode_route(dq, X3Geom{0, 0, 1, bound}, out_format == X3_WINDOW_F32 ? (const int16_t*)c->st_ws.p
                                                                                                 : (const int16_t*)d_out,
                                       true, x4 != 0, 0, c->opt).device_count;
-  uint64_t F = bound;
-  if (!dev_count) {
-    unsigned long long total = 0;
-    if (G) {
-      HIPCHK(c, hipMemcpyAsync(c->h_summary_init, l.isum, sizeof(X3IndexSummary), hipMemcpyDeviceToHost, c->stream));  // (pinned)
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      std::memcpy(&total, &reinterpret_cast<const X3IndexSummary*>(c->h_summary_init)->n_chain, sizeof total);
-    }
-    F = total;
-  }
+  unsigned long long F = bound;
+  if (!G) F = 0;
+  else if (!dev_count && (rc = streams_fetch(c, l, &F, nullptr))) return rc;
   if ((rc = streams_finish(c, F, dev_count))) return rc;
-  s.F = F;
   s.pending = true;
   return X3_OK;
 }
@@ -1360,8 +1384,7 @@ static int streams_general(x3_ctx* c, uint64_t e, x3_stream_result* r) {
   auto& s = c->streams;
   const uint64_t len = s.len[e];
   int rc;
-  if ((rc = ensure(c, c->st_one, len + 64))) return rc;
-  if (len) HIPCHK(c, hipMemcpyAsync(c->st_one.p, s.d_x3 + s.off[e], len, hipMemcpyDeviceToDevice, c->stream));
+  if ((rc = entry_copy(c, s.d_x3, s.off[e], len))) return rc;
   int16_t* row;
   if (s.fmt == X3_WINDOW_F32) {
     if ((rc = ensure(c, c->st_row, 2 * s.row_len + 64))) return rc;
@@ -1377,11 +1400,9 @@ static int streams_general(x3_ctx* c, uint64_t e, x3_stream_result* r) {
   r->frames_ok = fok;
   r->status = rc;
   r->frame_errors = (uint32_t)ferr;
-  const dim3 rg((unsigned)std::min<uint64_t>((s.row_len + 255) / 256, 1024), 1u);
   if (s.fmt == X3_WINDOW_F32)
-    hipLaunchKernelGGL(x3_streams_rows_kernel<true>, rg, dim3(256), 0, c->stream, (const int16_t*)row,
-                       (void*)((float*)s.d_out + e * s.row_len), (uint64_t)1, s.row_len, (const unsigned long long*)nullptr,
-                       (unsigned long long)n_out, (const X3StreamsSum*)nullptr);
+    streams_rows_launch(c, dim3((unsigned)std::min<uint64_t>((s.row_len + 255) / 256, 1024), 1u), s.fmt, row,
+                        (float*)s.d_out + e * s.row_len, 1, s.row_len, nullptr, n_out, nullptr);
   else if (n_out < s.row_len)
     HIPCHK(c, hipMemsetAsync(row + n_out, 0, 2 * (s.row_len - n_out), c->stream));
   HIPCHK(c, hipGetLastError());
@@ -1400,21 +1421,16 @@ extern "C" int x3_decode_streams_result(x3_ctx* c, uint64_t* n_bad, uint64_t* fi
     general.resize(s.n);
     for (uint64_t e = 0; e < s.n; ++e) general[e] = (uint32_t)e;
   } else {
-    const StreamsLayout l = streams_layout(c, s.n, s.G);
+    StreamsWs l;
+    streams_carve((char*)c->st_walk.p, s.n, s.G, &l);
     X3StreamsSum sum;
     unsigned long long total = 0;
-    HIPCHK(c, hipMemcpyAsync(c->h_summary_init, l.isum, 128 + sizeof sum, hipMemcpyDeviceToHost, c->stream));  // (pinned; both summaries)
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    std::memcpy(&sum, (const char*)c->h_summary_init + 128, sizeof sum);
-    std::memcpy(&total, &reinterpret_cast<const X3IndexSummary*>(c->h_summary_init)->n_chain, sizeof total);
+    int rc;
+    if ((rc = streams_fetch(c, l, &total, &sum))) return rc;
     if (sum.over) {   // more frames than the launch covered: again, with the count
       HIPCHK(c, hipMemsetAsync(&l.sum->over, 0, 4, c->stream));
-      int rc = streams_finish(c, total, false);
-      if (rc) return rc;
-      s.F = total;
-      HIPCHK(c, hipMemcpyAsync(c->h_summary_init, l.isum, 128 + sizeof sum, hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      std::memcpy(&sum, (const char*)c->h_summary_init + 128, sizeof sum);
+      if ((rc = streams_finish(c, total, false))) return rc;
+      if ((rc = streams_fetch(c, l, &total, &sum))) return rc;
     }
     nb = sum.n_bad;
     if (sum.n_bad) {
@@ -1475,15 +1491,13 @@ extern "C" void x3_corpus_destroy(x3_corpus* k) {
   delete k;
 }
 
-// The build's device scratch, freed on every way out.
-struct CorpusScratch {
-  std::vector<void*> bufs;
-  ~CorpusScratch() { for (void* q : bufs) (void)hipFree(q); }
-  template <class T> int get(x3_ctx* c, T** out, uint64_t count) {
-    void* q = nullptr;
-    HIPCHK(c, hipMalloc(&q, std::max<uint64_t>(count * sizeof(T), 64)));
-    bufs.push_back(q);
-    *out = (T*)q;
+// A device block of the build's own, freed on every way out (not st_walk: a build may run between a streams call and its result)
+struct CorpusBlock {
+  void* p = nullptr;
+  ~CorpusBlock() { if (p) (void)hipFree(p); }
+  template <class Carve> int alloc(x3_ctx* c, Carve carve) {   // carve(base): the pieces, and the bytes they take
+    HIPCHK(c, hipMalloc(&p, carve(nullptr)));
+    carve((char*)p);
     return X3_OK;
   }
 };
@@ -1493,20 +1507,9 @@ struct CorpusScratch {
 static int corpus_general_walk(x3_ctx* c, const uint8_t* d_x3, uint64_t off, uint64_t len, uint64_t phantom,
                                std::vector<uint64_t>* frames, int* terminal) {
   int rc;
-  if ((rc = ensure(c, c->st_one, len + 64))) return rc;
-  if (len) HIPCHK(c, hipMemcpyAsync(c->st_one.p, d_x3 + off, len, hipMemcpyDeviceToDevice, c->stream));
-  const uint64_t max_frames = len / 22 + 1;
-  uint64_t cap = std::min<uint64_t>(max_frames, 1u << 20);
+  if ((rc = entry_copy(c, d_x3, off, len))) return rc;
   X3IndexSummary r;
-  for (;;) {
-    if ((rc = ensure(c, c->frame_off, (cap + 1) * sizeof(uint64_t)))) return rc;
-    if ((rc = ensure(c, c->wav_off, cap * sizeof(uint64_t)))) return rc;
-    rc = index_dev_impl(c, (const uint8_t*)c->st_one.p, len, phantom, 0u, ~0ull, cap, (uint64_t*)c->frame_off.p,
-                        (uint64_t*)c->wav_off.p, &r);
-    if (rc == X3_ERR_BAD_ARG && cap < max_frames) { cap = max_frames; continue; }
-    break;
-  }
-  if (rc) return rc;
+  if ((rc = index_all_frames(c, (const uint8_t*)c->st_one.p, len, phantom, 0u, ~0ull, &r))) return rc;
   frames->resize(r.n_frames);
   if (r.n_frames) {
     HIPCHK(c, hipMemcpy(frames->data(), c->frame_off.p, 8 * r.n_frames, hipMemcpyDeviceToHost));
@@ -1519,7 +1522,7 @@ static int corpus_general_walk(x3_ctx* c, const uint8_t* d_x3, uint64_t off, uin
 // the recording decode: slices of frames into a scratch layout of its own (a frame's samples at a multiple of four), each
 // slice's index slots copied into place -- what one recording call over the whole table leaves
 #define X3K_RECORD_SCRATCH (256ull << 20)   // bytes of samples one slice decodes into
-static int corpus_record(x3_ctx* c, x3_corpus* k, const X3DevParams& dp, uint32_t seg_blocks, CorpusScratch& tmp) {
+static int corpus_record(x3_ctx* c, x3_corpus* k, const X3DevParams& dp, uint32_t seg_blocks, CorpusBlock& blk) {
   const uint64_t F = k->F;
   const uint64_t nidx = seg_stretches(dp.blocks_per_frame, seg_blocks);
   const uint64_t pitch = ((uint64_t)dp.spf + 3) & ~3ull;
@@ -1527,9 +1530,12 @@ static int corpus_record(x3_ctx* c, x3_corpus* k, const X3DevParams& dp, uint32_
   int rc;
   int16_t* wav;
   uint64_t *woff, *sidx;
-  if ((rc = tmp.get(c, &wav, S * pitch))) return rc;
-  if ((rc = tmp.get(c, &woff, S))) return rc;
-  if ((rc = tmp.get(c, &sidx, 1 + S * (nidx - 1)))) return rc;
+  auto carve = [&](char* base) {
+    SegCarver q{base, 0};
+    wav = q.take<int16_t>(S * pitch), woff = q.take<uint64_t>(S), sidx = q.take<uint64_t>(1 + S * (nidx - 1));
+    return q.at;
+  };
+  if ((rc = blk.alloc(c, carve))) return rc;
   std::vector<uint64_t> h(S);
   for (uint64_t i = 0; i < S; ++i) h[i] = i * pitch;
   HIPCHK(c, hipMemcpy(woff, h.data(), 8 * S, hipMemcpyHostToDevice));
@@ -1539,8 +1545,7 @@ static int corpus_record(x3_ctx* c, x3_corpus* k, const X3DevParams& dp, uint32_
   for (uint64_t f0 = 0; f0 < F; f0 += S) {
     ++c->last_corpus_slices;
     const uint64_t m = std::min<uint64_t>(S, F - f0);
-    x3_params pp = k->p;
-    if ((rc = decode_dev_impl(c, k->d_x3, k->x3_len, k->d_frame_off + f0, m, nullptr, woff, &pp, wav, m * pitch,
+    if ((rc = decode_dev_impl(c, k->d_x3, k->x3_len, k->d_frame_off + f0, m, nullptr, woff, &k->p, wav, m * pitch,
                               (int32_t*)c->dec_status.p, true, false, &seg)))
       return rc;
     if (f0 == 0) HIPCHK(c, hipMemcpyAsync(k->d_index, sidx, 8, hipMemcpyDeviceToDevice, c->stream));   // (the header word)
@@ -1551,58 +1556,31 @@ static int corpus_record(x3_ctx* c, x3_corpus* k, const X3DevParams& dp, uint32_
   return X3_OK;
 }
 
-static int corpus_build_impl(x3_ctx* c, x3_corpus* k, const uint64_t* offsets, const uint64_t* lengths, uint64_t phantom,
-                             uint32_t seg_blocks, bool index_walk) {
-  const uint64_t n = k->n;
+static int corpus_build_impl(x3_ctx* c, x3_corpus* k, const uint64_t* offsets, const uint64_t* lengths,
+                             const std::vector<uint32_t>& span_first, uint64_t phantom, uint32_t seg_blocks, bool index_walk) {
+  const uint64_t n = k->n, G = span_first[n], cap = seg_cands(G);
   int rc;
   X3DevParams dp;
   if ((rc = derive_params(&k->p, &dp))) return rc;
-  CorpusScratch tmp;
-  std::vector<uint32_t> span_first(n + 1, 0);
-  for (uint64_t e = 0; e < n; ++e) span_first[e + 1] = span_first[e] + (uint32_t)((lengths[e] + X3T_SPAN_BYTES - 1) / X3T_SPAN_BYTES);
-  const uint64_t G = span_first[n];
   // ---- 1. every entry's frames: the segmented fast walk (x3_streams_kernel.h), all entries at once
   std::vector<unsigned long long> m(n, ~0ull);
   std::vector<int32_t> st(n, 0);
   const bool fast = G && !c->opt.index_no_fast;
-  uint64_t *eoff = nullptr, *elen = nullptr;
-  uint32_t *sf = nullptr, *cnt = nullptr, *base = nullptr, *fent = nullptr, *ent_flags = nullptr;
-  unsigned long long *samp = nullptr, *sbase = nullptr, *frame_off = nullptr, *wav_off = nullptr, *ent_end = nullptr,
-                     *ent_nsamp = nullptr, *ent_k0 = nullptr, *ent_m = nullptr;
-  int32_t* ent_st = nullptr;
-  X3IndexSummary* isum = nullptr;
-  X3Cand* cand = nullptr;
-  const uint64_t cap = std::max<uint64_t>(G * X3I_WG_CANDS, 1);
-  if ((rc = tmp.get(c, &eoff, n)) || (rc = tmp.get(c, &elen, n)) || (rc = tmp.get(c, &sf, n + 1)) ||
-      (rc = tmp.get(c, &isum, 1)) || (rc = tmp.get(c, &cnt, G)) || (rc = tmp.get(c, &base, G)) || (rc = tmp.get(c, &samp, G)) ||
-      (rc = tmp.get(c, &sbase, G)) || (rc = tmp.get(c, &ent_flags, n)) || (rc = tmp.get(c, &ent_end, n)) ||
-      (rc = tmp.get(c, &ent_nsamp, n)) || (rc = tmp.get(c, &ent_k0, n)) || (rc = tmp.get(c, &ent_m, n)) ||
-      (rc = tmp.get(c, &ent_st, n)))
-    return rc;
+  CorpusBlock walk_blk, record_blk;
+  SegWalkWs w{};
+  unsigned long long *ent_k0 = nullptr, *ent_m = nullptr;   // per entry: its first candidate, its frame count,
+  int32_t* ent_st = nullptr;                                // how its walk ends
   if (fast) {
-    if ((rc = tmp.get(c, &cand, cap)) || (rc = tmp.get(c, &frame_off, cap)) || (rc = tmp.get(c, &wav_off, cap)) ||
-        (rc = tmp.get(c, &fent, cap)))
-      return rc;
-    HIPCHK(c, hipMemcpyAsync(eoff, offsets, 8 * n, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(elen, lengths, 8 * n, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(sf, span_first.data(), 4 * (n + 1), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(isum, 0, sizeof(X3IndexSummary), c->stream));
-    HIPCHK(c, hipMemsetAsync(ent_flags, 0, 4 * n, c->stream));
-    const uint32_t* xw = reinterpret_cast<const uint32_t*>(k->d_x3);
-    hipLaunchKernelGGL(x3_streams_candidates_kernel, dim3((unsigned)G), dim3(256), 0, c->stream, xw, k->x3_len,
-                       (const uint64_t*)eoff, (const uint64_t*)elen, (const uint32_t*)sf, (uint32_t)n, phantom, cand, cnt, samp,
-                       ent_flags);
-    hipLaunchKernelGGL(x3_index_chain_kernel, dim3(1), dim3(1024), 0, c->stream, (const unsigned int*)cnt,
-                       (const unsigned long long*)samp, (uint32_t)G, base, sbase, isum);
-    // (the index form of the link step: row_len ~0 and no four-sample grid, so every frame the walk steps over is live)
-    hipLaunchKernelGGL(x3_streams_link_kernel, dim3((unsigned)G), dim3(64), 0, c->stream, (const X3Cand*)cand,
-                       (const unsigned int*)cnt, (const uint32_t*)base, (const unsigned long long*)sbase, (const uint64_t*)eoff,
-                       (const uint32_t*)sf, (uint32_t)n, k->x3_len, ~0ull, 0u, frame_off, wav_off, fent, ent_flags, ent_end,
-                       ent_nsamp);
-    hipLaunchKernelGGL(x3_corpus_walk_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, xw, k->x3_len,
-                       (const uint64_t*)eoff, (const uint64_t*)elen, (const uint32_t*)sf, (uint32_t)n, phantom,
-                       (const uint32_t*)base, (uint32_t)G, (const unsigned long long*)&isum->n_chain, (const uint32_t*)ent_flags,
-                       (const unsigned long long*)ent_end, ent_k0, ent_m, ent_st);
+    auto carve = [&](char* base) {   // the walk's workspace, then the build's own words
+      SegCarver q{base, segwalk_carve(base, n, G, &w)};
+      ent_k0 = q.take<unsigned long long>(n), ent_m = q.take<unsigned long long>(n), ent_st = q.take<int32_t>(n);
+      return q.at;
+    };
+    if ((rc = walk_blk.alloc(c, carve))) return rc;
+    if ((rc = segwalk_launch(c, k->d_x3, k->x3_len, offsets, lengths, span_first, phantom, ~0ull, 0u, w))) return rc;
+    hipLaunchKernelGGL(x3_corpus_walk_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
+                       reinterpret_cast<const uint32_t*>(k->d_x3), k->x3_len, w.eoff, w.elen, w.span_first, (uint32_t)n, phantom,
+                       w.base, (uint32_t)G, &w.isum->n_chain, w.ent_flags, w.ent_end, ent_k0, ent_m, ent_st);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(m.data(), ent_m, 8 * n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(st.data(), ent_st, 4 * n, hipMemcpyDeviceToHost, c->stream));
@@ -1641,9 +1619,7 @@ static int corpus_build_impl(x3_ctx* c, x3_corpus* k, const uint64_t* offsets, c
   HIPCHK(c, hipMemcpyAsync(k->d_ent, k->ent.data(), sizeof(x3_corpus_entry) * n, hipMemcpyHostToDevice, c->stream));
   if (fast && F)
     hipLaunchKernelGGL(x3_corpus_compact_kernel, dim3((unsigned)std::min<uint64_t>((cap + 255) / 256, 4096)), dim3(256), 0,
-                       c->stream, (const unsigned long long*)frame_off, (const uint32_t*)fent, cap,
-                       (const unsigned long long*)&isum->n_chain, (const unsigned long long*)ent_k0,
-                       (const x3_corpus_entry*)k->d_ent, F, k->d_frame_off);
+                       c->stream, w.frame_off, w.fent, cap, &w.isum->n_chain, ent_k0, k->d_ent, F, k->d_frame_off);
   for (const auto& g : general)
     if (!g.second.empty())
       HIPCHK(c, hipMemcpyAsync(k->d_frame_off + k->ent[g.first].first_frame, g.second.data(), 8 * g.second.size(),
@@ -1658,23 +1634,16 @@ static int corpus_build_impl(x3_ctx* c, x3_corpus* k, const uint64_t* offsets, c
   HIPCHK(c, hipStreamSynchronize(c->stream));
   // ---- 3. the segment index: by one walk over the whole frame table for any parameters (X3_CORPUS_INDEX_WALK), or by
   // the recording decode where the parameters route to the decoder that records it
-  if (seg_blocks && F && index_walk) {
-    const uint64_t nidx = seg_stretches(dp.blocks_per_frame, seg_blocks);
-    if (nidx >= 2) {
-      HIPCHK(c, hipMalloc(&k->d_index, 8 * (1 + F * (nidx - 1))));
+  const uint64_t nidx = seg_blocks && F ? seg_stretches(dp.blocks_per_frame, seg_blocks) : 0;
+  if (nidx >= 2 && (index_walk || decode_route(dp, X3Geom{0, 0, 1, F}, (const int16_t*)nullptr, true, true, 2, c->opt).kernel == X3_DEC_SPLIT)) {
+    HIPCHK(c, hipMalloc(&k->d_index, 8 * (1 + F * (nidx - 1))));
+    if (index_walk) {
       if ((rc = seg_index_launch(c, k->d_x3, k->x3_len, k->d_frame_off, F, dp, k->d_index, seg_blocks))) return rc;
       HIPCHK(c, hipStreamSynchronize(c->stream));
-      k->seg_blocks = seg_blocks;
+    } else if ((rc = corpus_record(c, k, dp, seg_blocks, record_blk))) {
+      return rc;
     }
-  } else if (seg_blocks && F) {
-    const uint64_t nidx = seg_stretches(dp.blocks_per_frame, seg_blocks);
-    const bool records = nidx >= 2 &&
-                         decode_route(dp, X3Geom{0, 0, 1, F}, (const int16_t*)nullptr, true, true, 2, c->opt).kernel == X3_DEC_SPLIT;
-    if (records) {
-      HIPCHK(c, hipMalloc(&k->d_index, 8 * (1 + F * (nidx - 1))));
-      if ((rc = corpus_record(c, k, dp, seg_blocks, tmp))) return rc;
-      k->seg_blocks = seg_blocks;
-    }
+    k->seg_blocks = seg_blocks;
   }
   return X3_OK;
 }
@@ -1688,12 +1657,9 @@ extern "C" int x3_corpus_build(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, 
   if (x3_params_validate(p) != X3_OK) return X3_ERR_BAD_ARG;
   if (p->block_len == 0 || p->blocks_per_frame == 0 || spf_of(p) > 0xFFFFFFFFull) return X3_ERR_BAD_ARG;   // (windows refuse them)
   if (seg_blocks && !seg_index_args_ok(nullptr, seg_blocks)) return X3_ERR_BAD_ARG;   // (0: no index; the table is the corpus's own)
-  uint64_t G = 0;
-  for (uint64_t e = 0; e < n; ++e) {
-    if (offsets[e] > x3_len || lengths[e] > x3_len - offsets[e]) return X3_ERR_BAD_ARG;
-    G += (lengths[e] + X3T_SPAN_BYTES - 1) / X3T_SPAN_BYTES;
-  }
-  if (G > 0x7FFFFFFFull / X3I_WG_CANDS) return X3_ERR_BAD_ARG;
+  std::vector<uint32_t> span_first;
+  uint64_t G = 0, bytes = 0;
+  if (seg_entries(offsets, lengths, n, x3_len, &span_first, &G, &bytes)) return X3_ERR_BAD_ARG;
   HIPCHK(c, hipSetDevice(c->device));
   x3_corpus* k = new x3_corpus;
   k->device = c->device;
@@ -1703,7 +1669,7 @@ extern "C" int x3_corpus_build(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, 
   k->p = *p;
   c->decode_pending = false;
   c->last_corpus_slices = 0;
-  const int rc = corpus_build_impl(c, k, offsets, lengths, (flags & X3_STREAMS_ARCHIVE_FRAMES) ? 8 : 0, seg_blocks,
+  const int rc = corpus_build_impl(c, k, offsets, lengths, span_first, (flags & X3_STREAMS_ARCHIVE_FRAMES) ? 8 : 0, seg_blocks,
                                    (flags & X3_CORPUS_INDEX_WALK) != 0);
   if (rc) {
     (void)hipStreamSynchronize(c->stream);   // (nothing of the build may still run when its buffers go)

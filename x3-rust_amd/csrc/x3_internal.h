@@ -24,8 +24,10 @@
 #include <system_error>
 #include <condition_variable>
 #include <deque>
+#include <initializer_list>
 #include <mutex>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/x3hip.h"
@@ -151,19 +153,18 @@ struct x3_ctx {
   DevBuf idx_cand, idx_keys, idx_vals, idx_J, idx_S, idx_L, idx_sum;  // x3_index_dev scratch
   DevBuf idx_wg, idx_sorted, idx_scan;  // ... of its fast path: candidates per scanning workgroup, in order, the scans
   DevBuf win_ws;   // x3_decode_windows_dev: plans, scans, per-frame verdicts, replay scratch, summary (x3_decode_window_kernel.h)
-  // x3_decode_streams_dev (x3_streams_kernel.h): the entry table, the spans' candidates and scans, the frame table, the
-  // per-entry words, the int16 rows of a float32 call, an entry the general walk takes (aligned copy, int16 row)
-  DevBuf st_tab, st_cand, st_scan, st_frames, st_ent, st_ws, st_one, st_row;
+  // x3_decode_streams_dev (x3_streams_kernel.h): the call's block (the segmented walk's workspace and the call's own words:
+  // streams_carve, x3_decode.hip), the int16 rows of a float32 call, an entry the general walk takes (aligned copy, int16 row)
+  DevBuf st_walk, st_ws, st_one, st_row;
   struct StreamsCall {
     bool pending = false, all_general = false;
     const uint8_t* d_x3 = nullptr;
-    uint64_t x3_len = 0, n = 0, row_len = 0, phantom = 0, F = 0, G = 0;
+    uint64_t x3_len = 0, n = 0, row_len = 0, phantom = 0, G = 0;
     int fmt = 0;
     x3_params p{};
     void* d_out = nullptr;
     x3_stream_result* d_results = nullptr;
-    std::vector<uint64_t> off, len;   // the entries (host copies); the device table follows them in st_tab
-    std::vector<uint32_t> span_first;
+    std::vector<uint64_t> off, len;   // the entries (host copies)
   } streams;
   unsigned long long streams_general = 0, last_streams_general = 0;   // entries the general walk took (options)
   unsigned long long index_fast = 0, index_general = 0;  // walks that the fast path / the general path have served (options)
@@ -343,6 +344,8 @@ struct EncPlan {
 
 // ---- x3_ctx.hip
 X3_INTERNAL int ensure(x3_ctx* c, DevBuf& b, size_t bytes);
+// host arrays of a call to d_dst, one behind the other, through the context's pinned block (x3_ctx::h_src_tab: read HERE)
+X3_INTERNAL int src_tab_upload(x3_ctx* c, void* d_dst, std::initializer_list<std::pair<const void*, size_t>> parts);
 // x3_wav_to_x3a with option "file_tune": the tuned parameters of samples [0, n) at byte data_off of a file (x3_tune.hip;
 // weak, so that the other units also link without that one, as the sanitizer build of the host code does)
 X3_INTERNAL int tune_fd(x3_ctx* c, int fd, uint64_t data_off, uint64_t n, x3_params* best) __attribute__((weak));
@@ -402,6 +405,30 @@ X3_INTERNAL int decode_frames_host(x3_ctx* c, const uint8_t* x3, uint64_t len, c
                                    bool download = true,  // !download: the samples stay in c->out (x3_mgpu_decode_stream)
                                    const uint8_t* d_x3 = nullptr);  // the frames' bytes are on the device already
 X3_INTERNAL int walk_result(uint64_t F, uint64_t first_bad, int bad_status, int terminal, uint64_t* frame_errors);
+// The SEGMENTED WALK of x3_decode_streams_dev and x3_corpus_build (x3_streams_kernel.h).  Its entry
+// table: X3_ERR_BAD_ARG for an entry outside [0, x3_len] or more than 0x7FFFFFFF / X3I_WG_CANDS spans; otherwise
+// span_first[e] = the spans (X3T_SPAN_BYTES each) in front of entry e <= n, *G = span_first[n], *bytes = the lengths' sum.
+X3_INTERNAL int seg_entries(const uint64_t* offsets, const uint64_t* lengths, uint64_t n, uint64_t x3_len,
+                            std::vector<uint32_t>* span_first, uint64_t* G, uint64_t* bytes);
+// Its workspace: per entry (n), per span (G) and per candidate (max(G * X3I_WG_CANDS, 1)) arrays, as the kernels index them.
+struct X3Cand;
+struct SegWalkWs {
+  uint64_t* eoff; uint64_t* elen; uint32_t* span_first;   // the entry table: n, n and n + 1 words in ONE piece (one upload)
+  unsigned int* cnt; uint32_t* base; unsigned long long* samp; unsigned long long* sbase;   // per span: counts, their scans
+  X3IndexSummary* isum; X3Cand* cand;   // the scans' summary (n_chain: the candidates of all entries); per candidate, by span
+  unsigned long long* frame_off; unsigned long long* wav_off; uint32_t* fent;   // per candidate, numbered: the frame table
+  uint32_t* ent_flags; unsigned long long* ent_end; unsigned long long* ent_nsamp;   // per entry
+};
+// ... carved out of one block at `base` (nullptr: the size alone): the bytes it takes.  Every piece, and the end, where a
+// caller's own pieces follow, lies a multiple of 256 bytes behind base (device allocations: 16-byte aligned at least).
+X3_INTERNAL size_t segwalk_carve(char* base, uint64_t n, uint64_t G, SegWalkWs* w);
+// ... and x3_decode_streams_dev's block: the walk's workspace, then the call's own words
+struct X3StreamsSum;
+struct StreamsWs : SegWalkWs {
+  X3StreamsSum* sum; int32_t* status;                                       // the summary; per candidate: the decoder's
+  unsigned long long* ent_bad; unsigned long long* nout; uint32_t* dirty;   // per entry
+};
+X3_INTERNAL size_t streams_carve(char* base, uint64_t n, uint64_t G, StreamsWs* s);
 // ---- x3_files.hip (x3_reader.h)
 // the RIFF/WAVE header parser of x3_wav_to_x3a on an open file, for the sanitised host tests (tests/host_cpp/fuzz_host_parsers.cpp)
 X3_INTERNAL int x3_wav_parse_fd_for_tests(int fd, uint64_t file_len, uint32_t* sample_rate, uint16_t* channels, uint16_t* bits,
