@@ -159,6 +159,9 @@ const char* x3_last_error(const x3_ctx* ctx);
  * their first buffer held and scanned the stream a second time).
  * x3_decode_streams_dev: read-only "streams_general_walks" (entries so far that the segmented fast walk left to the
  * general walk) and "last_streams_general_walks" (of the last x3_decode_streams_result).
+ * x3_levels_dev / x3_corpus_levels_dev: read-only "last_levels_replays" (frames of the last call that were decoded through
+ * the reference's reader instead of by stretches: flagged ones, and frames whose offsets are out of order; read after
+ * x3_levels_result).
  * x3_corpus_build: read-only "last_corpus_record_slices" (slices of frames the last build recorded its segment index in;
  * 0 without an index).
  * x3_seg_index_build_dev: read-only "last_seg_index_irregular" (frames of the last build -- x3_corpus_build's with
@@ -608,6 +611,43 @@ int x3_decode_windows_result(x3_ctx* ctx, uint64_t* n_bad, uint64_t* first_bad, 
 #define X3_WINDOW_I16 0     /* int16 samples */
 #define X3_WINDOW_F32 1     /* float32 samples, s / 32768.0f (exact) */
 
+/* ---- LEVELS (no counterpart in the reference): min, max, count, sum and sum of squares of the samples per BIN of sample
+ * positions, computed from the stream in device memory without a sample buffer -- overviews, peak / RMS per clip, "where is
+ * anything loud".  All five are integers: the records are exact and do not depend on any order of execution.
+ *   Positions are the window calls': sample i of frame f is at d_sample_offsets[f] + i.  Bin b covers positions
+ * [b * bin_len, (b + 1) * bin_len); bin_len == 0 means one bin for everything.
+ *   A frame's STATUS (d_frame_status[f], when given) is the status x3_decode_windows_dev gives a window that is exactly that
+ * frame: its header check, its payload CRC, its header's sample count against the offsets (a mismatch, or an offset or
+ * payload past x3_len: X3_ERR_BAD_ARG), then decoder::decode_frame.  A frame with status 0 adds EVERY one of its samples to
+ * the bins they fall in; a frame with any other status adds NOTHING, also when its first blocks decode cleanly.  Positions
+ * at or beyond n_bins * bin_len are not counted.  EVERY one of the n_bins records is written (the caller need not clear
+ * them; a bin that no sample falls in holds the identities); nothing outside d_levels[0 .. n_bins) and
+ * d_frame_status[0 .. n_frames) is written, nothing outside [d_x3, d_x3 + x3_len) is read: offsets, sample offsets, index
+ * and bytes are untrusted exactly as in x3_decode_windows_dev.  The segment index is a hint that changes time, never
+ * results; without one (NULL, or a header word that says "none") a frame is one stretch.  n counts modulo 2^32.
+ *   How: the window path's check and stretches, with a consumer that keeps a bin in registers.
+ * Stretches add to rows of the frame's own in a workspace of (n_bins + n_frames) records; only a frame whose every stretch
+ * has been proven is added to d_levels, a flagged one goes through the reference's reader first.
+ *   Asynchronous on the context's stream: one launch set, no host trip, nothing allocated after the first call of a size
+ * (the workspace grows like the windows').  The pending states of x3_decode_dev and of the window calls are left alone.
+ * X3_ERR_BAD_ARG with nothing enqueued for n_bins == 0 or above 0x7FFFFFFF, n_frames == 0 or above 0x7FFFFFFF, NULL or
+ * misaligned pointers (d_levels: 8 bytes; d_frame_status may be NULL), a seg_blocks that x3_decode_dev_seg refuses,
+ * parameters that x3_decode_windows_dev refuses, and a context that is recording a graph. */
+typedef struct x3_level {      /* 32 bytes, 8-byte aligned */
+  uint64_t sum_sq;             /* sum of s*s */
+  int64_t  sum;                /* sum of s   */
+  int32_t  min, max;           /* n == 0: 32767 / -32768 (the identities) */
+  uint32_t n;                  /* samples counted into this bin */
+  uint32_t reserved;           /* 0 */
+} x3_level;
+int x3_levels_dev(x3_ctx* ctx, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
+                  const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
+                  const uint64_t* d_seg_index, uint32_t seg_blocks, uint64_t bin_len,
+                  x3_level* d_levels, uint64_t n_bins, int32_t* d_frame_status);
+/* Waits for the last x3_levels_dev / x3_corpus_levels_dev: frames with status != 0, the first of them (the frame count if
+ * none) and its status. */
+int x3_levels_result(x3_ctx* ctx, uint64_t* n_bad_frames, uint64_t* first_bad, int* first_bad_status);
+
 /* ---- BATCHES OF STREAMS (no counterpart in the reference: decodefile.rs reads one file).  Entry s of a call is the bytes
  * [offsets[s], offsets[s] + lengths[s]) of d_x3 -- any byte offset; entries may overlap or repeat, and a batch that
  * x3_encode_frames_dev wrote back to back is taken as it is.  All entries share one x3_params.  Each entry's results are
@@ -695,6 +735,16 @@ int x3_corpus_seg_index(const x3_corpus* corpus, const uint64_t** d_seg_index, u
  * d_entries not on a 4-byte boundary, and a context on another device than the build's. */
 int x3_corpus_windows_dev(x3_ctx* ctx, const x3_corpus* corpus, const uint32_t* d_entries, const uint64_t* d_starts,
                           uint64_t n_windows, uint32_t window_len, void* d_out, int out_format, int32_t* d_status);
+/* LEVELS of every entry of a corpus.  Entry e has max(1, ceil(n_samples[e] / bin_len)) rows (one with bin_len == 0), the
+ * rows lie entry after entry; x3_corpus_levels_rows writes that prefix (HOST array of n_entries + 1 words, from the entry
+ * table).  Positions are relative to the entry, and entry e's rows are exactly what x3_levels_dev gives on that entry alone
+ * with its own frame table, n_bins = its rows.  d_frame_status: one int32 per frame of the corpus's frame table, or NULL.
+ * The corpus's own segment index is used when it has one.  Contract and refusals as for x3_levels_dev (n_rows for n_bins);
+ * also X3_ERR_BAD_ARG with nothing enqueued when n_rows is not the prefix's last word, and for a context on another device
+ * than the build's.  x3_levels_result as there. */
+int x3_corpus_levels_rows(const x3_corpus* corpus, uint64_t bin_len, uint64_t* row_first);
+int x3_corpus_levels_dev(x3_ctx* ctx, const x3_corpus* corpus, uint64_t bin_len, x3_level* d_levels, uint64_t n_rows,
+                         int32_t* d_frame_status);
 void x3_corpus_destroy(x3_corpus* corpus);
 
 /* ------------------------------------------------------------------ multi-GPU (no reference analogue) */

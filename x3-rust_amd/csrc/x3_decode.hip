@@ -9,6 +9,7 @@
 #include "x3_decode_mc_kernel.h"
 #include "x3_decode_window_kernel.h"
 #include "x3_seg_index_kernel.h"
+#include "x3_levels_kernel.h"
 
 // ------------------------------------------------------------------------------------------------
 // decode
@@ -1140,6 +1141,103 @@ extern "C" int x3_decode_windows_result(x3_ctx* c, uint64_t* n_bad, uint64_t* fi
 }
 
 // ------------------------------------------------------------------------------------------------
+// levels: per-bin min, max, count, sum and sum of squares without a sample buffer (x3_levels_kernel.h)
+// ------------------------------------------------------------------------------------------------
+// the argument checks x3_levels_dev and x3_corpus_levels_dev share
+static bool levels_args_ok(const x3_ctx* c, const x3_level* d_levels, uint64_t n_rows, const int32_t* d_frame_status) {
+  if (!d_levels || n_rows == 0 || n_rows > 0x7FFFFFFFull || c->capturing) return false;
+  return (reinterpret_cast<uintptr_t>(d_levels) & 7u) == 0 && (reinterpret_cast<uintptr_t>(d_frame_status) & 3u) == 0;
+}
+
+// The launch set of a levels call behind its prep step: prep(grid, row_first, fst, frames, cnt) enqueues the kernels that
+// give every frame its position, its records and its row count.  n_ent: entries of a corpus call (their row prefix lives
+// in the workspace), 0 for a stream.
+template <class Prep>
+static int levels_launch(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
+                         const uint64_t* d_sample_offsets, uint64_t F, const X3DevParams& dp, const uint64_t* d_seg_index,
+                         uint32_t seg_blocks, uint64_t bin_len, x3_level* d_levels, uint64_t n_rows, int32_t* d_frame_status,
+                         uint64_t n_ent, Prep prep) {
+  const uint64_t nidx = d_seg_index ? seg_stretches(dp.blocks_per_frame, seg_blocks) : 1;
+  const uint32_t nseg = nidx >= 2 ? (uint32_t)nidx : 1u;
+  const uint2* idx = nseg >= 2 ? reinterpret_cast<const uint2*>(d_seg_index) : nullptr;
+  // the fix-up's waves: one block of replay scratch each, 32 MiB of it at most
+  const uint32_t scratch_per = (std::min<uint32_t>(dp.block_len, 0x10000u) + 7u) & ~7u;
+  const uint64_t fix_waves = std::max<uint64_t>(1, std::min<uint64_t>({(F + 3) / 4 * 4, 4096, (32ull << 20) / (2ull * scratch_per) / 4 * 4}));
+  // workspace: per-frame verdicts, plans, row counts and their scan; the partial rows; replay scratch; summary; row prefix
+  const uint64_t cap = n_rows + F;
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t o_fst = 0, o_fr = up(o_fst + F * 4), o_cnt = up(o_fr + F * sizeof(X3LevFrame)), o_row = up(o_cnt + F * 4),
+               o_rows = up(o_row + (F + 1) * 8), o_scr = up(o_rows + cap * sizeof(x3_level)),
+               o_sum = up(o_scr + std::max<uint64_t>(fix_waves, 4) * scratch_per * 2), o_rf = up(o_sum + sizeof(X3LevSummary)),
+               total = o_rf + (n_ent + 1) * 8;
+  int rc;
+  if ((rc = ensure(c, c->lev_ws, total))) return rc;
+  char* const ws = (char*)c->lev_ws.p;
+  int32_t* fst = (int32_t*)(ws + o_fst);
+  X3LevFrame* frames = (X3LevFrame*)(ws + o_fr);
+  uint32_t* cnt = (uint32_t*)(ws + o_cnt);
+  unsigned long long* row = (unsigned long long*)(ws + o_row);
+  x3_level* rows = (x3_level*)(ws + o_rows);
+  int16_t* scratch = (int16_t*)(ws + o_scr);
+  X3LevSummary* sum = (X3LevSummary*)(ws + o_sum);
+  auto groups = [&](uint64_t units, uint64_t per_group) {
+    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((units + per_group - 1) / per_group, X3W_GRID_LIMIT));
+  };
+  hipLaunchKernelGGL(x3_levels_init_kernel, dim3(groups(n_rows + cap, 256)), dim3(256), 0, c->stream, d_levels, n_rows, rows, cap, sum);
+  hipLaunchKernelGGL(x3_levels_check_kernel, dim3(groups(F, 4)), dim3(256), 0, c->stream, d_x3, x3_len, d_frame_offsets,
+                     d_sample_offsets, F, fst);
+  prep(dim3(groups(F, 256)), (unsigned long long*)(ws + o_rf), (const int32_t*)fst, frames, cnt);
+  hipLaunchKernelGGL(x3_levels_scan_kernel, dim3(1), dim3(1024), 0, c->stream, (const uint32_t*)cnt, F, cap, row, fst);
+  hipLaunchKernelGGL(x3_levels_accum_kernel, dim3(groups(F * nseg, 256)), dim3(256), 0, c->stream, d_x3, x3_len, d_frame_offsets,
+                     F, dp, idx, seg_blocks, nseg, bin_len, (const X3LevFrame*)frames, (const unsigned long long*)row, rows, fst);
+  hipLaunchKernelGGL(x3_levels_fixup_kernel, dim3((unsigned)((fix_waves + 3) / 4)), dim3(256), 0, c->stream, d_x3, d_frame_offsets,
+                     F, dp, bin_len, (const X3LevFrame*)frames, fst, d_levels, d_frame_status, scratch, scratch_per, sum);
+  hipLaunchKernelGGL(x3_levels_merge_kernel, dim3(groups(cap, 256)), dim3(256), 0, c->stream, (const X3LevFrame*)frames,
+                     (const unsigned long long*)row, F, cap, (const x3_level*)rows, (const int32_t*)fst, d_levels);
+  HIPCHK(c, hipGetLastError());
+  c->levels_pending = true;
+  c->lev_frames = F;
+  c->lev_sum_off = o_sum;
+  return X3_OK;
+}
+
+extern "C" int x3_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
+                             const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
+                             const uint64_t* d_seg_index, uint32_t seg_blocks, uint64_t bin_len, x3_level* d_levels,
+                             uint64_t n_bins, int32_t* d_frame_status) {
+  if (!c || !d_x3 || !d_frame_offsets || !d_sample_offsets || !p) return X3_ERR_BAD_ARG;
+  if (!levels_args_ok(c, d_levels, n_bins, d_frame_status)) return X3_ERR_BAD_ARG;
+  if (!frame_table_args_ok(d_x3, d_frame_offsets, n_frames) || (reinterpret_cast<uintptr_t>(d_sample_offsets) & 7u))
+    return X3_ERR_BAD_ARG;
+  if (d_seg_index && !seg_index_args_ok(d_seg_index, seg_blocks)) return X3_ERR_BAD_ARG;
+  X3DevParams dp;
+  int rc = derive_block_params(p, &dp);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  return levels_launch(c, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, dp, d_seg_index, seg_blocks, bin_len,
+                       d_levels, n_bins, d_frame_status, 0,
+                       [&](dim3 grid, unsigned long long*, const int32_t* fst, X3LevFrame* frames, uint32_t* cnt) {
+                         hipLaunchKernelGGL(x3_levels_prep_kernel, grid, dim3(256), 0, c->stream, d_sample_offsets, n_frames,
+                                            bin_len, n_bins, fst, frames, cnt);
+                       });
+}
+
+extern "C" int x3_levels_result(x3_ctx* c, uint64_t* n_bad_frames, uint64_t* first_bad, int* first_bad_status) {
+  if (!c || !c->levels_pending) return X3_ERR_BAD_ARG;
+  X3LevSummary h{0, 0, 0};
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(&h, (char*)c->lev_ws.p + c->lev_sum_off, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->levels_pending = false;
+  c->last_levels_replays = h.replays;
+  const bool any = h.n_bad != 0;
+  if (n_bad_frames) *n_bad_frames = h.n_bad;
+  if (first_bad) *first_bad = any ? (h.first >> 8) : c->lev_frames;
+  if (first_bad_status) *first_bad_status = any ? (int)(h.first & 0xFFu) : 0;
+  return X3_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // the segment index by a walk (x3_seg_index_kernel.h)
 // ------------------------------------------------------------------------------------------------
 // One launch behind a 8-byte memset of the counter; nothing is allocated, nothing waits, no pending state is touched.
@@ -1726,4 +1824,45 @@ extern "C" int x3_corpus_windows_dev(x3_ctx* c, const x3_corpus* k, const uint32
                                              d_starts, n_windows, window_len, plan, gstart, sum);
                           return gstart;
                         });
+}
+
+// the rows of entry e (max(1, ceil(n_samples / bin_len)), one with bin_len 0) in front of each other: n_entries + 1 words
+extern "C" int x3_corpus_levels_rows(const x3_corpus* k, uint64_t bin_len, uint64_t* row_first) {
+  if (!k || !row_first) return X3_ERR_BAD_ARG;
+  uint64_t run = 0;
+  for (uint64_t e = 0; e < k->n; ++e) {
+    row_first[e] = run;
+    const uint64_t ns = k->ent[e].n_samples;
+    run += bin_len == 0 || ns == 0 ? 1 : ns / bin_len + (ns % bin_len ? 1 : 0);
+  }
+  row_first[k->n] = run;
+  return X3_OK;
+}
+
+extern "C" int x3_corpus_levels_dev(x3_ctx* c, const x3_corpus* k, uint64_t bin_len, x3_level* d_levels, uint64_t n_rows,
+                                    int32_t* d_frame_status) {
+  if (!c || !k || !levels_args_ok(c, d_levels, n_rows, d_frame_status)) return X3_ERR_BAD_ARG;
+  if (c->device != k->device) {
+    c->last_error = "x3_corpus_levels_dev: the corpus was built on another device";
+    return X3_ERR_BAD_ARG;
+  }
+  uint64_t want = 0;
+  for (const x3_corpus_entry& en : k->ent)
+    want += bin_len == 0 || en.n_samples == 0 ? 1 : en.n_samples / bin_len + (en.n_samples % bin_len ? 1 : 0);
+  if (n_rows != want) return X3_ERR_BAD_ARG;
+  X3DevParams dp;
+  int rc = derive_params(&k->p, &dp);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  const uint64_t n_ent = k->n, F = k->F;
+  const x3_corpus_entry* ent = k->d_ent;
+  const uint64_t* so = k->d_so;
+  return levels_launch(c, k->d_x3, k->x3_len, k->d_frame_off, k->d_so, F, dp, k->d_index, k->seg_blocks, bin_len, d_levels,
+                       n_rows, d_frame_status, n_ent,
+                       [&](dim3 grid, unsigned long long* row_first, const int32_t* fst, X3LevFrame* frames, uint32_t* cnt) {
+                         hipLaunchKernelGGL(x3_corpus_levels_rows_kernel, dim3(1), dim3(1024), 0, c->stream, ent, n_ent, bin_len,
+                                            row_first);
+                         hipLaunchKernelGGL(x3_corpus_levels_prep_kernel, grid, dim3(256), 0, c->stream, ent, n_ent,
+                                            (const unsigned long long*)row_first, so, F, bin_len, n_rows, fst, frames, cnt);
+                       });
 }

@@ -312,6 +312,55 @@ x3_window_scan_kernel(const X3WinPlan* __restrict__ plan, uint64_t n, const uint
 }
 
 // ---- check: a wave per (window, covering frame)
+// The verdict of frame f by one wave (every lane returns it): header, payload CRC, what x3_decode_dev's decoders refuse behind
+// the check, and the header's `samples` against the caller's sample offsets.
+__device__ __forceinline__ int32_t x3w_check_frame(const uint8_t* __restrict__ x3, uint64_t len, uint64_t off,
+                                                   const uint64_t* __restrict__ so, uint64_t f, uint32_t lane) {
+  uint32_t plen = 0, samples = 0, pcrc = 0;
+  int32_t st;
+  if (len < 20u || off > len - 20u) {
+    st = X3D_BAD_ARG;   // (the caller's offset is not inside this stream)
+  } else {
+    const uint32_t h0 = x3w_be32_at(x3, len, off), h1 = x3w_be32_at(x3, len, off + 4u);
+    const uint32_t h2 = x3w_be32_at(x3, len, off + 8u), h3 = x3w_be32_at(x3, len, off + 12u);
+    const uint32_t h4 = x3w_be32_at(x3, len, off + 16u);
+    uint32_t hc = 0xFFFFu;
+    hc = x3_crc_be32(hc, h0);
+    hc = x3_crc_be32(hc, h1);
+    hc = x3_crc_be32(hc, h2);
+    hc = x3_crc_be32(hc, h3);
+    st = x3_frame_header_check_words(h0, h1, h4, hc, len, off, plen, samples, pcrc);
+    if (st == X3D_STREAM_ENDS_IN_FRAME) st = X3D_BAD_ARG;
+  }
+  if (st == X3D_OK) {
+    // payload CRC: lane t CRCs a contiguous chunk with init 0, the chunks are joined by x^(8 * bytes behind them)
+    const uint64_t p0 = off + 20u;
+    const uint32_t chunk = (plen + 63u) >> 6;
+    const uint32_t a = min(lane * chunk, plen), b = min(a + chunk, plen);
+    uint32_t c = 0;
+    for (uint32_t k = a; k < b; ++k) c = x3_crc_byte(c, x3[p0 + k]);
+    // x^(8 * (plen - b)) by squaring; lane 0 also carries the init value 0xFFFF times x^(8 * plen)
+    auto xpow8 = [](uint32_t nbytes) -> uint32_t {
+      uint32_t r = 1u, base = 0x100u;
+      while (nbytes) {
+        if (nbytes & 1u) r = x3_gf_mul(r, base);
+        base = x3_gf_mul(base, base);
+        nbytes >>= 1;
+      }
+      return r;
+    };
+    uint32_t part = x3_gf_mul(c, xpow8(plen - b));
+    if (lane == 0) part ^= x3_gf_mul(0xFFFFu, xpow8(plen));
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) part ^= (uint32_t)__shfl_xor((int)part, o, X3_WAVE);
+    if ((part & 0xFFFFu) != pcrc) st = X3D_FRAME_HEADER_INVALID_PAYLOAD_CRC;
+  }
+  // what x3_decode_dev's decoders refuse behind the check, and the caller's offsets against the header
+  if (st == X3D_OK && (samples == 0u || plen < 2u)) st = X3D_BAD_ARG;
+  if (st == X3D_OK && (so[f + 1u] < so[f] || so[f + 1u] - so[f] != samples)) st = X3D_BAD_ARG;
+  return st;
+}
+
 __global__ void __launch_bounds__(256)
 x3_window_check_kernel(const uint8_t* __restrict__ x3, uint64_t len, const uint64_t* __restrict__ frame_off,
                        const uint64_t* __restrict__ so, const X3WinPlan* __restrict__ plan, uint64_t n_windows,
@@ -322,54 +371,64 @@ x3_window_check_kernel(const uint8_t* __restrict__ x3, uint64_t len, const uint6
   for (uint64_t i = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); i < n_items; i += waves) {
     const uint64_t w = x3w_owner(cov_off, n_windows, i);
     const uint64_t f = plan[w].fa + (i - cov_off[w]);
-    const uint64_t off = frame_off[f];
-    uint32_t plen = 0, samples = 0, pcrc = 0;
-    int32_t st;
-    if (len < 20u || off > len - 20u) {
-      st = X3D_BAD_ARG;   // (the caller's offset is not inside this stream)
-    } else {
-      const uint32_t h0 = x3w_be32_at(x3, len, off), h1 = x3w_be32_at(x3, len, off + 4u);
-      const uint32_t h2 = x3w_be32_at(x3, len, off + 8u), h3 = x3w_be32_at(x3, len, off + 12u);
-      const uint32_t h4 = x3w_be32_at(x3, len, off + 16u);
-      uint32_t hc = 0xFFFFu;
-      hc = x3_crc_be32(hc, h0);
-      hc = x3_crc_be32(hc, h1);
-      hc = x3_crc_be32(hc, h2);
-      hc = x3_crc_be32(hc, h3);
-      st = x3_frame_header_check_words(h0, h1, h4, hc, len, off, plen, samples, pcrc);
-      if (st == X3D_STREAM_ENDS_IN_FRAME) st = X3D_BAD_ARG;
-    }
-    if (st == X3D_OK) {
-      // payload CRC: lane t CRCs a contiguous chunk with init 0, the chunks are joined by x^(8 * bytes behind them)
-      const uint64_t p0 = off + 20u;
-      const uint32_t chunk = (plen + 63u) >> 6;
-      const uint32_t a = min(lane * chunk, plen), b = min(a + chunk, plen);
-      uint32_t c = 0;
-      for (uint32_t k = a; k < b; ++k) c = x3_crc_byte(c, x3[p0 + k]);
-      // x^(8 * (plen - b)) by squaring; lane 0 also carries the init value 0xFFFF times x^(8 * plen)
-      auto xpow8 = [](uint32_t nbytes) -> uint32_t {
-        uint32_t r = 1u, base = 0x100u;
-        while (nbytes) {
-          if (nbytes & 1u) r = x3_gf_mul(r, base);
-          base = x3_gf_mul(base, base);
-          nbytes >>= 1;
-        }
-        return r;
-      };
-      uint32_t part = x3_gf_mul(c, xpow8(plen - b));
-      if (lane == 0) part ^= x3_gf_mul(0xFFFFu, xpow8(plen));
-#pragma unroll
-      for (int o = 32; o >= 1; o >>= 1) part ^= (uint32_t)__shfl_xor((int)part, o, X3_WAVE);
-      if ((part & 0xFFFFu) != pcrc) st = X3D_FRAME_HEADER_INVALID_PAYLOAD_CRC;
-    }
-    // what x3_decode_dev's decoders refuse behind the check, and the caller's offsets against the header
-    if (st == X3D_OK && (samples == 0u || plen < 2u)) st = X3D_BAD_ARG;
-    if (st == X3D_OK && (so[f + 1u] < so[f] || so[f + 1u] - so[f] != samples)) st = X3D_BAD_ARG;
+    const int32_t st = x3w_check_frame(x3, len, frame_off[f], so, f, lane);
     if (lane == 0) fst[f] = st;
   }
 }
 
 // ---- decode: a lane per (window, covering frame, stretch)
+// Stretch j of checked frame f by one lane: from block 0 or from usable entry j to the next usable entry, whose bit position
+// and last sample it must meet.  Sample s of the frame goes to put_at(s, value).  0: entry j starts no stretch (the
+// stretch in front runs through its blocks), 1: decoded and proven, -1: the frame is one for the reference's reader.
+template <class Put>
+__device__ __forceinline__ int x3w_stretch(const uint8_t* __restrict__ x3, uint64_t len, uint64_t off, const X3DevParams& p,
+                                           const uint2* __restrict__ idx, bool segd, uint32_t sb, uint32_t nseg, uint64_t f,
+                                           uint32_t j, Put put_at) {
+  const uint32_t pitch = nseg - 1u;
+  const uint64_t p0 = off + 20u;
+  const uint32_t h1 = x3w_be32_at(x3, len, off + 4u);
+  const uint32_t samples = h1 >> 16, plen = h1 & 0xFFFFu;
+  const uint32_t nbf = (samples - 1u + p.block_len - 1u) / p.block_len;   // blocks of the frame
+  const uint2* const e = segd ? idx + 1 + f * (uint64_t)pitch : nullptr;
+  auto usable = [&](uint32_t q) -> bool {   // entry q (1 .. nseg-1) is one to start from / end at
+    if (sb * q >= nbf) return false;
+    const uint2 h = e[q - 1u];
+    return (h.y & X3S_SEG_VALID) && h.x >= 16u && h.x <= 8u * plen;
+  };
+  if (j && !usable(j)) return 0;   // (the stretch in front runs through these blocks)
+  uint32_t q = j + 1u;             // the next usable entry, nseg if none
+  if (segd)
+    while (q < nseg && !usable(q)) ++q;
+  else
+    q = 1u;
+  const uint32_t b0 = sb * j;
+  const uint32_t b1 = (segd && q < nseg) ? sb * q : nbf;
+  uint32_t last;
+  X3WinBits br;
+  if (j == 0u) {
+    last = x3w_be32_at(x3, len, p0) >> 16;
+    put_at(0u, last);
+    br.open(x3, len, p0 * 8u + 16u);
+  } else {
+    const uint2 h = e[j - 1u];
+    last = h.y & 0xFFFFu;
+    br.open(x3, len, p0 * 8u + h.x);
+  }
+  const uint64_t end_bit = (p0 + plen) * 8u;
+  bool ok = true;
+  for (uint32_t b = b0; b < b1 && ok; ++b) {
+    const uint32_t s0 = 1u + b * p.block_len;
+    const uint32_t n = min(p.block_len, samples - s0);
+    ok = x3w_block(br, n, p, last, [&](uint32_t t, uint32_t v) { put_at(s0 + t, v); });
+    ok = ok && br.pos <= end_bit;
+  }
+  if (ok && segd && q < nseg) {
+    const uint2 h = e[q - 1u];
+    ok = br.pos - p0 * 8u == h.x && last == (h.y & 0xFFFFu);
+  }
+  return ok ? 1 : -1;
+}
+
 __global__ void __launch_bounds__(256)
 x3_window_decode_kernel(const uint8_t* __restrict__ x3, uint64_t len, const uint64_t* __restrict__ frame_off,
                         const uint64_t* __restrict__ so, const uint64_t* __restrict__ starts, const X3WinPlan* __restrict__ plan,
@@ -378,7 +437,6 @@ x3_window_decode_kernel(const uint8_t* __restrict__ x3, uint64_t len, const uint
                         int32_t* __restrict__ fst) {
   const bool segd = x3w_index_ok(idx, sb);
   const uint32_t ns = segd ? nseg : 1u;
-  const uint32_t pitch = nseg - 1u;
   const uint64_t n_items = item_off[n_windows];
   const uint64_t lanes = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_items; i += lanes) {
@@ -387,54 +445,37 @@ x3_window_decode_kernel(const uint8_t* __restrict__ x3, uint64_t len, const uint
     const uint64_t f = plan[w].fa + k / ns;
     const uint32_t j = (uint32_t)(k % ns);
     if (fst[f] != X3D_OK) continue;   // (checked: header, CRC, sample count; a frame that failed is not decoded)
-    const uint64_t off = frame_off[f], p0 = off + 20u;
-    const uint32_t h1 = x3w_be32_at(x3, len, off + 4u);
-    const uint32_t samples = h1 >> 16, plen = h1 & 0xFFFFu;
-    const uint32_t nbf = (samples - 1u + p.block_len - 1u) / p.block_len;   // blocks of the frame
-    const uint2* const e = segd ? idx + 1 + f * (uint64_t)pitch : nullptr;
-    auto usable = [&](uint32_t q) -> bool {   // entry q (1 .. nseg-1) is one to start from / end at
-      if (sb * q >= nbf) return false;
-      const uint2 h = e[q - 1u];
-      return (h.y & X3S_SEG_VALID) && h.x >= 16u && h.x <= 8u * plen;
-    };
-    if (j && !usable(j)) continue;   // (the stretch in front runs through these blocks)
-    uint32_t q = j + 1u;             // the next usable entry, nseg if none
-    if (segd)
-      while (q < nseg && !usable(q)) ++q;
-    else
-      q = 1u;
-    const uint32_t b0 = sb * j;
-    const uint32_t b1 = (segd && q < nseg) ? sb * q : nbf;
     const uint64_t rbase = w * (uint64_t)L, start = starts[w], fpos = so[f];
     auto put_at = [&](uint32_t s, uint32_t v) {   // sample s of the frame
       const uint64_t g = fpos + s;
       if (g >= start && g - start < (uint64_t)L) x3w_store(out, fmt, rbase + (g - start), v);
     };
-    uint32_t last;
-    X3WinBits br;
-    if (j == 0u) {
-      last = x3w_be32_at(x3, len, p0) >> 16;
-      put_at(0u, last);
-      br.open(x3, len, p0 * 8u + 16u);
-    } else {
-      const uint2 h = e[j - 1u];
-      last = h.y & 0xFFFFu;
-      br.open(x3, len, p0 * 8u + h.x);
-    }
-    const uint64_t end_bit = (p0 + plen) * 8u;
-    bool ok = true;
-    for (uint32_t b = b0; b < b1 && ok; ++b) {
-      const uint32_t s0 = 1u + b * p.block_len;
-      const uint32_t n = min(p.block_len, samples - s0);
-      ok = x3w_block(br, n, p, last, [&](uint32_t t, uint32_t v) { put_at(s0 + t, v); });
-      ok = ok && br.pos <= end_bit;
-    }
-    if (ok && segd && q < nseg) {
-      const uint2 h = e[q - 1u];
-      ok = br.pos - p0 * 8u == h.x && last == (h.y & 0xFFFFu);
-    }
-    if (!ok) atomicOr(&fst[f], X3W_FLAG);
+    if (x3w_stretch(x3, len, frame_off[f], p, idx, segd, sb, nseg, f, j, put_at) < 0) atomicOr(&fst[f], X3W_FLAG);
   }
+}
+
+// decoder::decode_frame of a checked frame through the reference's reader (x3_replay_frame's loop), block by block into
+// `blk` (a block's samples); sample s of the frame goes to put_at(s, value), a failing block hands over nothing.
+template <class Put>
+__device__ __forceinline__ int32_t x3w_replay_frame(const uint8_t* __restrict__ payload, const X3DevParams& p,
+                                                    int16_t* __restrict__ blk, Put put_at) {
+  const uint32_t samples = ((uint32_t)payload[-16] << 8) | payload[-15];
+  const uint32_t plen = ((uint32_t)payload[-14] << 8) | payload[-13];
+  uint32_t last = ((uint32_t)payload[0] << 8) | payload[1];
+  put_at(0u, last);
+  X3RefReader br;
+  br.open(payload + 2, plen - 2u);
+  uint32_t at = 1u, remaining = samples - 1u;
+  int32_t fs = X3D_OK;
+  while (remaining && fs == X3D_OK) {
+    const uint32_t n = remaining < p.block_len ? remaining : p.block_len;
+    fs = x3_replay_block(br, n, p, last, blk);
+    if (fs == X3D_OK)
+      for (uint32_t t = 0; t < n; ++t) put_at(at + t, (uint16_t)blk[t]);
+    remaining -= n;
+    at += n;
+  }
+  return fs;
 }
 
 // ---- fix-up: a wave per window, frames in order; scratch: a block's samples per window (x3_replay_block's output)
@@ -457,30 +498,13 @@ x3_window_fixup_kernel(const uint8_t* __restrict__ x3, const uint64_t* __restric
       for (uint64_t f = pl.fa; f < pl.fa + pl.ncov; ++f) {
         int32_t fs = fst[f];
         if (fs == X3W_FLAG) {
-          // decoder::decode_frame through the reference's reader (x3_replay_frame's loop), block by block into the scratch
-          const uint8_t* const payload = x3 + frame_off[f] + 20u;
-          const uint32_t samples = ((uint32_t)payload[-16] << 8) | payload[-15];
-          const uint32_t plen = ((uint32_t)payload[-14] << 8) | payload[-13];
           const uint64_t fpos = so[f];
           auto put_at = [&](uint32_t s, uint32_t v) {
             const uint64_t g = fpos + s;
             if (g >= start && g - start < (uint64_t)L) x3w_store(out, fmt, rbase + (g - start), v);
           };
-          uint32_t last = ((uint32_t)payload[0] << 8) | payload[1];
-          put_at(0u, last);
-          X3RefReader br;
-          br.open(payload + 2, plen - 2u);
-          uint32_t at = 1u, remaining = samples - 1u;
-          fs = X3D_OK;
+          fs = x3w_replay_frame(x3 + frame_off[f] + 20u, p, blk, put_at);
           ++replayed;
-          while (remaining && fs == X3D_OK) {
-            const uint32_t n = remaining < p.block_len ? remaining : p.block_len;
-            fs = x3_replay_block(br, n, p, last, blk);
-            if (fs == X3D_OK)
-              for (uint32_t t = 0; t < n; ++t) put_at(at + t, (uint16_t)blk[t]);
-            remaining -= n;
-            at += n;
-          }
         }
         if (fs != X3D_OK) {
           st = fs;

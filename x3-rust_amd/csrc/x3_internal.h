@@ -152,6 +152,7 @@ struct x3_ctx {
   DevBuf in_more[2], out_more[2];  // x3_decode_stream on a long host buffer: rings of three buffers on either side of the decoder
   DevBuf idx_cand, idx_keys, idx_vals, idx_J, idx_S, idx_L, idx_sum;  // x3_index_dev scratch
   DevBuf idx_wg, idx_sorted, idx_scan;  // ... of its fast path: candidates per scanning workgroup, in order, the scans
+  DevBuf lev_ws;   // x3_levels_dev / x3_corpus_levels_dev: verdicts, plans, the frames' partial rows, replay scratch, summary (x3_levels_kernel.h)
   DevBuf win_ws;   // x3_decode_windows_dev: plans, scans, per-frame verdicts, replay scratch, summary (x3_decode_window_kernel.h)
   // x3_decode_streams_dev (x3_streams_kernel.h): the call's block (the segmented walk's workspace and the call's own words:
   // streams_carve, x3_decode.hip), the int16 rows of a float32 call, an entry the general walk takes (aligned copy, int16 row)
@@ -178,6 +179,9 @@ struct x3_ctx {
   bool windows_pending = false;    // x3_decode_windows_dev: its own pending state (x3_decode_result is not touched)
   uint64_t win_windows = 0;        // ... its window count and where its summary lies in win_ws
   size_t win_sum_off = 0;
+  bool levels_pending = false;     // x3_levels_dev / x3_corpus_levels_dev: a pending state of their own, as the windows'
+  uint64_t lev_frames = 0;         // ... their frame count and where their summary lies in lev_ws
+  size_t lev_sum_off = 0;
   bool force_two_pass = false;
   // Contexts that encode concurrently on ONE GPU (the file pipeline's workers) share this gate: the single-pass encoders
   // are persistent grids whose workgroups wait for each other, so only one of them may be in flight on a device.  A
@@ -198,6 +202,7 @@ struct x3_ctx {
   // decode_replays sums every summary read so far, the stream entry points take their difference
   unsigned long long last_decode_replays = 0, decode_replays = 0;
   unsigned long long last_window_replays = 0;   // (window, covering frame) pairs x3_window_fixup_kernel re-decoded
+  unsigned long long last_levels_replays = 0;   // frames x3_levels_fixup_kernel decoded through the reference's reader
   unsigned long long last_corpus_slices = 0;    // x3_corpus_build: slices of frames its recording decode took (option)
   struct LastEnc {
     const int16_t* d_wav; x3_batch b; x3_params p; uint64_t spf; uint8_t* d_out; uint64_t out_cap, start_pos; uint64_t* d_off;

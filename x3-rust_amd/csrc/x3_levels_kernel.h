@@ -1,0 +1,356 @@
+// x3_levels_kernel.h -- LEVELS: min, max, count, sum and sum of squares per bin of sample positions, for a stream
+// (x3_levels_dev) or every entry of a corpus (x3_corpus_levels_dev), without a sample buffer.
+//
+// The decode is x3_decode_window_kernel.h's: x3w_check_frame per frame, x3w_stretch per (frame, stretch) with its proof
+// against the next usable index entry, x3w_replay_frame for the frames a stretch flags.  What differs is the consumer: put()
+// adds the sample to five registers and stores nothing; a lane touches memory (beyond the bit window's refills) only where
+// its position crosses a bin boundary and at its end.  All five quantities are integers: the result does not depend on the
+// order in which lanes arrive.
+//
+// ROLLBACK.  A frame whose status is not 0 must add nothing, also when its first stretches decoded cleanly, and a stretch
+// cannot know how the frame's other stretches end.  So a stretch never adds to the caller's bins.  It adds to the FRAME'S
+// OWN partial rows in the workspace: frame f touches bins b0 .. b1 (clipped to its stream's bins), an exclusive scan of
+// b1 - b0 + 1 gives it rows [row[f], row[f + 1]) -- with the positions of consecutive frames back to back that is at most
+// n_bins + n_frames rows in all, which is what the workspace holds.  Only when every stretch of the frame has been proven
+// (its word is still X3D_OK behind the accumulate kernel) does the merge kernel add the frame's rows to the caller's bins.  A
+// flagged frame's rows are never read again: the fix-up kernel decodes it through the reference's reader, once for its
+// status and, if that is 0, a second time straight into the caller's bins.  Frames whose rows would not fit (offsets out
+// of order: not this stream's) are flagged by the scan and take that path too.
+//
+//  x3_levels_init_kernel     -- identities into every caller's record and every partial row; the summary
+//  x3_levels_check_kernel    -- a wave per frame of the table: x3w_check_frame
+//  x3_corpus_levels_rows_kernel / x3_levels_prep_kernel / x3_corpus_levels_prep_kernel
+//                            -- per frame: its position, its stream's rows in d_levels, its first bin, its row count
+//  x3_levels_scan_kernel     -- one workgroup: the exclusive scan of the row counts; frames that do not fit are flagged
+//  x3_levels_accum_kernel    -- a lane per (frame, stretch)
+//  x3_levels_fixup_kernel    -- a wave per frame: flagged frames through the reference's reader; d_frame_status, summary
+//  x3_levels_merge_kernel    -- a lane per partial row; rows of one bin that lie side by side in a wave are joined first
+//
+// Nothing trusts offsets, sample offsets, index, entry table or bytes: stream reads are those of the window kernels, every
+// partial row index is below the workspace's row count, every caller's record index below n_rows.
+#pragma once
+#include "x3_decode_window_kernel.h"
+
+#define X3L_DONE 0x20000      // per-frame word: the fix-up has given the frame its status (low 16 bits) by the reader
+#define X3L_FAR 0x20000u      // "the bin does not end inside this frame": more than a frame's 65 535 samples
+
+struct X3LevSummary {
+  unsigned long long n_bad;     // frames with status != 0
+  unsigned long long first;     // min(f << 8 | status) over them
+  unsigned long long replays;   // frames the fix-up decoded through the reference's reader (option "last_levels_replays")
+};
+
+struct X3LevFrame {
+  uint64_t pos;     // position of the frame's sample 0 in its stream / entry
+  uint64_t obase;   // d_levels record of that stream's / entry's bin 0
+  uint64_t nlim;    // its bins (0: the frame belongs to no entry, nothing is counted)
+  uint64_t b0;      // the frame's first bin
+};
+
+__device__ __forceinline__ uint64_t x3l_bin_len(uint64_t bin_len) { return bin_len ? bin_len : ~0ull; }   // 0: one bin
+
+// the registers of a bin
+struct X3LevAcc {
+  uint64_t sum_sq;
+  int64_t sum;
+  int32_t mn, mx;
+  uint32_t n;
+  __device__ __forceinline__ void reset() {
+    sum_sq = 0;
+    sum = 0;
+    mn = 32767;
+    mx = -32768;
+    n = 0;
+  }
+  __device__ __forceinline__ void add(uint32_t v) {
+    const int32_t s = (int32_t)(int16_t)(uint16_t)v;
+    sum_sq += (uint32_t)(s * s);
+    sum += s;
+    mn = min(mn, s);
+    mx = max(mx, s);
+    ++n;
+  }
+  __device__ __forceinline__ void join(const X3LevAcc& o) {
+    sum_sq += o.sum_sq;
+    sum += o.sum;
+    mn = min(mn, o.mn);
+    mx = max(mx, o.mx);
+    n += o.n;
+  }
+};
+
+// ... into a record that other lanes add to as well
+__device__ __forceinline__ void x3l_merge(x3_level* __restrict__ r, const X3LevAcc& a) {
+  if (a.n == 0u) return;
+  atomicAdd(reinterpret_cast<unsigned long long*>(&r->sum_sq), (unsigned long long)a.sum_sq);
+  atomicAdd(reinterpret_cast<unsigned long long*>(&r->sum), (unsigned long long)a.sum);
+  atomicMin(&r->min, a.mn);
+  atomicMax(&r->max, a.mx);
+  atomicAdd(&r->n, a.n);
+}
+
+// Consecutive positions from g on: `left` samples are still missing in bin `bin` (X3L_FAR: more than any frame has, so
+// a count that reaches 0 is always a real boundary).  flush(bin, acc) takes a finished or abandoned bin.
+struct X3LevBinner {
+  X3LevAcc a;
+  uint64_t bin;
+  uint32_t left, step;
+  __device__ __forceinline__ void open(uint64_t g, uint64_t bl) {
+    a.reset();
+    bin = g / bl;
+    const uint64_t rem = bl - (g - bin * bl);
+    left = rem < X3L_FAR ? (uint32_t)rem : X3L_FAR;
+    step = bl < X3L_FAR ? (uint32_t)bl : X3L_FAR;
+  }
+  template <class Flush>
+  __device__ __forceinline__ void add(uint32_t v, Flush flush) {
+    a.add(v);
+    if (--left == 0u) {
+      flush(bin, a);
+      a.reset();
+      ++bin;
+      left = step;
+    }
+  }
+};
+
+// ---- identities; the summary
+__global__ void __launch_bounds__(256)
+x3_levels_init_kernel(x3_level* __restrict__ levels, uint64_t n_rows, x3_level* __restrict__ rows, uint64_t cap,
+                      X3LevSummary* __restrict__ sum) {
+  const uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (uint64_t)gridDim.x * blockDim.x;
+  if (i0 == 0) {
+    sum->n_bad = 0;
+    sum->first = ~0ull;
+    sum->replays = 0;
+  }
+  const x3_level id{0, 0, 32767, -32768, 0, 0};
+  for (uint64_t i = i0; i < n_rows + cap; i += stride) {
+    if (i < n_rows) levels[i] = id;
+    else rows[i - n_rows] = id;
+  }
+}
+
+// ---- check: a wave per frame
+__global__ void __launch_bounds__(256)
+x3_levels_check_kernel(const uint8_t* __restrict__ x3, uint64_t len, const uint64_t* __restrict__ frame_off,
+                       const uint64_t* __restrict__ so, uint64_t F, int32_t* __restrict__ fst) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+  for (uint64_t f = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); f < F; f += waves) {
+    const int32_t st = x3w_check_frame(x3, len, frame_off[f], so, f, lane);
+    if (lane == 0) fst[f] = st;
+  }
+}
+
+// the rows of a checked frame (so[f + 1] - so[f] = its samples >= 1): bins b0 .. b1 below nlim
+__device__ __forceinline__ void x3l_frame_rows(X3LevFrame& fr, uint64_t samples, uint64_t bl, bool ok, uint32_t* cnt) {
+  if (fr.pos > ~0ull - 0x10000u) fr.nlim = 0;   // (no checked frame's positions wrap: its samples end at so[f + 1])
+  fr.b0 = fr.pos / bl;
+  uint32_t c = 0;
+  if (ok && samples && fr.b0 < fr.nlim) {
+    const uint64_t b1 = min((fr.pos + (samples - 1u)) / bl, fr.nlim - 1u);
+    c = (uint32_t)(b1 - fr.b0 + 1u);   // (at most `samples`, which the check holds to 16 bits)
+  }
+  *cnt = c;
+}
+
+// ---- prep, stream: positions are the sample offsets, one stream of n_bins bins
+__global__ void __launch_bounds__(256)
+x3_levels_prep_kernel(const uint64_t* __restrict__ so, uint64_t F, uint64_t bin_len, uint64_t n_bins,
+                      const int32_t* __restrict__ fst, X3LevFrame* __restrict__ frames, uint32_t* __restrict__ cnt) {
+  const uint64_t bl = x3l_bin_len(bin_len);
+  for (uint64_t f = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; f < F; f += (uint64_t)gridDim.x * blockDim.x) {
+    X3LevFrame fr{so[f], 0, n_bins, 0};
+    const bool ok = fst[f] == X3D_OK;
+    x3l_frame_rows(fr, ok ? so[f + 1u] - so[f] : 0u, bl, ok, &cnt[f]);
+    frames[f] = fr;
+  }
+}
+
+// ---- corpus: rows per entry, max(1, ceil(n_samples / bin_len)), and their exclusive scan (n + 1 words); one workgroup
+__device__ __forceinline__ unsigned long long x3l_entry_rows(uint64_t n_samples, uint64_t bin_len) {
+  if (bin_len == 0 || n_samples == 0) return 1ull;
+  return n_samples / bin_len + (n_samples % bin_len ? 1u : 0u);
+}
+
+__global__ void __launch_bounds__(1024)
+x3_corpus_levels_rows_kernel(const x3_corpus_entry* __restrict__ ent, uint64_t n, uint64_t bin_len,
+                             unsigned long long* __restrict__ row_first) {
+  __shared__ unsigned long long s[1024];
+  const uint64_t per = (n + blockDim.x - 1) / blockDim.x;
+  const uint64_t a = min((uint64_t)threadIdx.x * per, n), b = min(a + per, n);
+  unsigned long long c = 0;
+  for (uint64_t e = a; e < b; ++e) c += x3l_entry_rows(ent[e].n_samples, bin_len);
+  unsigned long long total;
+  unsigned long long run = x3w_block_excl_scan(c, s, &total);
+  for (uint64_t e = a; e < b; ++e) {
+    row_first[e] = run;
+    run += x3l_entry_rows(ent[e].n_samples, bin_len);
+  }
+  if (threadIdx.x == 0) row_first[n] = total;
+}
+
+// ---- prep, corpus: the frame's entry by a search of the entry table (checked, not trusted: its frames inside the table,
+// its positions as the sample offsets give them, its rows inside d_levels); positions are relative to the entry
+__global__ void __launch_bounds__(256)
+x3_corpus_levels_prep_kernel(const x3_corpus_entry* __restrict__ ent, uint64_t n_ent, const unsigned long long* __restrict__ row_first,
+                             const uint64_t* __restrict__ so, uint64_t F, uint64_t bin_len, uint64_t n_rows,
+                             const int32_t* __restrict__ fst, X3LevFrame* __restrict__ frames, uint32_t* __restrict__ cnt) {
+  const uint64_t bl = x3l_bin_len(bin_len);
+  for (uint64_t f = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; f < F; f += (uint64_t)gridDim.x * blockDim.x) {
+    uint64_t lo = 0, hi = n_ent;   // the last entry whose first frame is at or in front of f
+    while (hi - lo > 1u) {
+      const uint64_t mid = lo + ((hi - lo) >> 1);
+      if (ent[mid].first_frame <= f) lo = mid;
+      else hi = mid;
+    }
+    const x3_corpus_entry en = ent[lo];
+    X3LevFrame fr{0, 0, 0, 0};
+    const unsigned long long r0 = row_first[lo];
+    if (en.first_frame <= f && f - en.first_frame < en.n_frames && en.n_frames <= F - en.first_frame &&
+        so[f] >= so[en.first_frame] && r0 <= n_rows) {
+      fr.pos = so[f] - so[en.first_frame];
+      fr.obase = r0;
+      fr.nlim = min((uint64_t)x3l_entry_rows(en.n_samples, bin_len), n_rows - r0);
+    }
+    const bool ok = fst[f] == X3D_OK;
+    x3l_frame_rows(fr, ok ? so[f + 1u] - so[f] : 0u, bl, ok, &cnt[f]);
+    frames[f] = fr;
+  }
+}
+
+// ---- exclusive scan of the row counts (F + 1 words); a frame whose rows end behind `cap` is flagged for the fix-up
+__global__ void __launch_bounds__(1024)
+x3_levels_scan_kernel(const uint32_t* __restrict__ cnt, uint64_t F, uint64_t cap, unsigned long long* __restrict__ row,
+                      int32_t* __restrict__ fst) {
+  __shared__ unsigned long long s[1024];
+  const uint64_t per = (F + blockDim.x - 1) / blockDim.x;
+  const uint64_t a = min((uint64_t)threadIdx.x * per, F), b = min(a + per, F);
+  unsigned long long c = 0;
+  for (uint64_t f = a; f < b; ++f) c += cnt[f];
+  unsigned long long total;
+  unsigned long long run = x3w_block_excl_scan(c, s, &total);
+  for (uint64_t f = a; f < b; ++f) {
+    row[f] = run;
+    run += cnt[f];
+    if (cnt[f] && run > cap) fst[f] = X3W_FLAG;
+  }
+  if (threadIdx.x == 0) row[F] = total;
+}
+
+// ---- accumulate: a lane per (frame, stretch) into the frame's own rows
+__global__ void __launch_bounds__(256)
+x3_levels_accum_kernel(const uint8_t* __restrict__ x3, uint64_t len, const uint64_t* __restrict__ frame_off, uint64_t F,
+                       X3DevParams p, const uint2* __restrict__ idx, uint32_t sb, uint32_t nseg, uint64_t bin_len,
+                       const X3LevFrame* __restrict__ frames, const unsigned long long* __restrict__ row,
+                       x3_level* __restrict__ rows, int32_t* __restrict__ fst) {
+  const bool segd = x3w_index_ok(idx, sb);
+  const uint32_t ns = segd ? nseg : 1u;
+  const uint64_t bl = x3l_bin_len(bin_len);
+  const uint64_t n_items = F * ns;
+  const uint64_t lanes = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_items; i += lanes) {
+    const uint64_t f = i / ns;
+    const uint32_t j = (uint32_t)(i - f * ns);
+    if (fst[f] != X3D_OK) continue;   // (failed its check, or its rows do not fit: nothing to prove here)
+    const X3LevFrame fr = frames[f];
+    x3_level* const mine = rows + row[f];
+    const uint64_t nlim = fr.nlim, b0 = fr.b0;
+    auto flush = [&](uint64_t bin, const X3LevAcc& a) {
+      if (bin < nlim) x3l_merge(mine + (bin - b0), a);
+    };
+    // a stretch's samples come in order, from sample 0 or from the first sample of block sb * j
+    X3LevBinner bn;
+    bn.open(fr.pos + (j ? 1u + (uint64_t)sb * j * p.block_len : 0u), bl);
+    const int r = x3w_stretch(x3, len, frame_off[f], p, idx, segd, sb, nseg, f, j,
+                              [&](uint32_t, uint32_t v) { bn.add(v, flush); });
+    flush(bn.bin, bn.a);
+    if (r < 0) atomicOr(&fst[f], X3W_FLAG);
+  }
+}
+
+// ---- fix-up: a wave per frame (lane 0 works); scratch: a block's samples per wave of the grid
+__global__ void __launch_bounds__(256)
+x3_levels_fixup_kernel(const uint8_t* __restrict__ x3, const uint64_t* __restrict__ frame_off, uint64_t F, X3DevParams p,
+                       uint64_t bin_len, const X3LevFrame* __restrict__ frames, int32_t* __restrict__ fst,
+                       x3_level* __restrict__ levels, int32_t* __restrict__ status, int16_t* __restrict__ scratch,
+                       uint32_t scratch_per, X3LevSummary* __restrict__ sum) {
+  const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+  const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (threadIdx.x & 63u) return;
+  int16_t* const blk = scratch + wave * (uint64_t)scratch_per;
+  const uint64_t bl = x3l_bin_len(bin_len);
+  for (uint64_t f = wave; f < F; f += waves) {
+    int32_t fs = fst[f];
+    if (fs == X3W_FLAG) {
+      const uint8_t* const payload = x3 + frame_off[f] + 20u;
+      fs = x3w_replay_frame(payload, p, blk, [](uint32_t, uint32_t) {});
+      if (fs == X3D_OK) {   // every block decodes: once more, now into the caller's bins
+        const X3LevFrame fr = frames[f];
+        auto flush = [&](uint64_t bin, const X3LevAcc& a) {
+          if (bin < fr.nlim) x3l_merge(levels + fr.obase + bin, a);
+        };
+        X3LevBinner bn;
+        bn.open(fr.pos, bl);
+        (void)x3w_replay_frame(payload, p, blk, [&](uint32_t, uint32_t v) { bn.add(v, flush); });
+        flush(bn.bin, bn.a);
+      }
+      fst[f] = fs | X3L_DONE;
+      atomicAdd(&sum->replays, 1ull);
+    }
+    if (status) status[f] = fs;
+    if (fs != X3D_OK) {
+      atomicAdd(&sum->n_bad, 1ull);
+      atomicMin(&sum->first, (unsigned long long)(f << 8) | (uint32_t)fs);
+    }
+  }
+}
+
+// ---- merge: a lane per partial row.  A row counts when its frame's word is X3D_OK: checked, every stretch proven.  Rows
+// of the same record that lie side by side in a wave (the boundary bin of neighbouring frames; with one bin, all of them)
+// are joined in registers, and the first lane of each run adds the sum.
+__global__ void __launch_bounds__(256)
+x3_levels_merge_kernel(const X3LevFrame* __restrict__ frames, const unsigned long long* __restrict__ row, uint64_t F,
+                       uint64_t cap, const x3_level* __restrict__ rows, const int32_t* __restrict__ fst,
+                       x3_level* __restrict__ levels) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t n = min((uint64_t)row[F], cap);
+  const uint64_t lanes = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u); i0 < n; i0 += lanes) {   // (whole waves)
+    const uint64_t i = i0 + lane;
+    X3LevAcc a;
+    a.reset();
+    uint64_t key = ~0ull;
+    if (i < n) {
+      const uint64_t f = x3w_owner(row, F, i);
+      if (fst[f] == X3D_OK) {
+        const X3LevFrame fr = frames[f];
+        const x3_level r = rows[i];
+        key = fr.obase + fr.b0 + (i - row[f]);   // (below obase + nlim <= the caller's rows: x3l_frame_rows)
+        a.sum_sq = r.sum_sq;
+        a.sum = r.sum;
+        a.mn = r.min;
+        a.mx = r.max;
+        a.n = r.n;
+      }
+    }
+    // runs of equal keys: a lane starts one where its key differs from its left neighbour's (or it has none)
+    const uint64_t left = (uint64_t)__shfl_up((long long)key, 1, X3_WAVE);
+    const bool head = lane == 0u || key == ~0ull || left != key;
+    const unsigned long long heads = __ballot(head);
+    const uint32_t run = (uint32_t)__popcll(heads & (~0ull >> (63u - lane)));
+#pragma unroll
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+      X3LevAcc o;
+      o.sum_sq = (uint64_t)__shfl_down((long long)a.sum_sq, d, X3_WAVE);
+      o.sum = (int64_t)__shfl_down((long long)a.sum, d, X3_WAVE);
+      o.mn = __shfl_down(a.mn, d, X3_WAVE);
+      o.mx = __shfl_down(a.mx, d, X3_WAVE);
+      o.n = (uint32_t)__shfl_down((int)a.n, d, X3_WAVE);
+      const uint32_t orun = (uint32_t)__shfl_down((int)run, d, X3_WAVE);
+      if (lane + d < 64u && orun == run) a.join(o);
+    }
+    if (head && key != ~0ull) x3l_merge(levels + key, a);
+  }
+}

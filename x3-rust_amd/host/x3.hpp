@@ -744,6 +744,23 @@ inline X3Error decode_windows(Context& ctx, const EncodedStream& s, const Parame
   return static_cast<X3Error>(rc);
 }
 
+// Levels (x3_levels_dev): min, max, count, sum and sum of squares of the samples per bin of bin_len positions (0: one bin),
+// n_bins records in d_levels, every one written; d_frame_status (n_frames int32, may be nullptr): a frame with a status
+// other than 0 adds nothing.  No sample buffer.  Waits for the call: res = frames with status != 0, the first, its status.
+inline X3Error levels(Context& ctx, const EncodedStream& s, const Parameters& params, const Buffer& d_sample_offsets,
+                      uint64_t bin_len, x3_level* d_levels, uint64_t n_bins, int32_t* d_frame_status, WindowsResult* res) {
+  if (!s.bytes.ok() || !s.frame_offsets.ok() || !d_sample_offsets.ok()) return X3Error::BadArg;
+  const x3_params c = params.c_params();
+  int rc = x3_levels_dev(ctx.raw(), s.bytes.as<uint8_t>(), s.len, s.frame_offsets.as<uint64_t>(), d_sample_offsets.as<uint64_t>(),
+                         s.n_frames, &c, s.seg_blocks ? s.seg_index.as<uint64_t>() : nullptr, s.seg_blocks, bin_len, d_levels,
+                         n_bins, d_frame_status);
+  if (rc != X3_OK) return static_cast<X3Error>(rc);
+  WindowsResult r;
+  rc = x3_levels_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status);
+  if (res) *res = r;
+  return static_cast<X3Error>(rc);
+}
+
 // A batch of independent streams (x3_decode_streams_dev): entry s = bytes [offsets[s], offsets[s] + lengths[s]) of d_x3 (flags:
 // X3_STREAMS_ARCHIVE_FRAMES for the frame parts of .x3a archives), decoded into row s of d_out (offsets.size() rows of row_len
 // samples, X3_WINDOW_I16 / X3_WINDOW_F32, zeros behind each entry's samples); d_results[s] = x3_decode_stream_dev's results on
@@ -810,6 +827,22 @@ class Corpus {
     if (rc != X3_OK) return static_cast<X3Error>(rc);
     WindowsResult r;
     rc = x3_decode_windows_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status);
+    if (res) *res = r;
+    return static_cast<X3Error>(rc);
+  }
+  // Levels of every entry (x3_corpus_levels_dev): entry e's records are [row_first[e], row_first[e + 1]) of d_levels, positions
+  // relative to the entry; levels_rows(bin_len) is that prefix, d_levels holds its last word of records.  Waits for the call.
+  std::vector<uint64_t> levels_rows(uint64_t bin_len) const {
+    std::vector<uint64_t> v(raw_ ? n_entries() + 1 : 0);
+    if (raw_) x3_corpus_levels_rows(raw_, bin_len, v.data());
+    return v;
+  }
+  X3Error levels(Context& ctx, uint64_t bin_len, x3_level* d_levels, uint64_t n_rows, int32_t* d_frame_status,
+                 WindowsResult* res) const {
+    int rc = x3_corpus_levels_dev(ctx.raw(), raw_, bin_len, d_levels, n_rows, d_frame_status);
+    if (rc != X3_OK) return static_cast<X3Error>(rc);
+    WindowsResult r;
+    rc = x3_levels_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status);
     if (res) *res = r;
     return static_cast<X3Error>(rc);
   }

@@ -59,6 +59,17 @@ pub mod ffi {
         pub walk_status: i32,
         pub general_walk: u32,
     }
+    /// `x3_level`: one bin of `x3_levels_dev` / `x3_corpus_levels_dev` (32 bytes)
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+    pub struct x3_level {
+        pub sum_sq: u64,
+        pub sum: i64,
+        pub min: i32,
+        pub max: i32,
+        pub n: u32,
+        pub reserved: u32,
+    }
     #[repr(C)]
     #[derive(Clone, Copy, Debug)]
     pub struct x3_rice_code {
@@ -161,6 +172,13 @@ pub mod ffi {
         pub fn x3_corpus_seg_index(corpus: *const x3_corpus, d_seg_index: *mut *const u64, n_words: *mut u64) -> c_int;
         pub fn x3_corpus_windows_dev(ctx: *mut x3_ctx, corpus: *const x3_corpus, d_entries: *const u32, d_starts: *const u64,
                                      n_windows: u64, window_len: u32, d_out: *mut c_void, out_format: c_int, d_status: *mut i32) -> c_int;
+        pub fn x3_levels_dev(ctx: *mut x3_ctx, d_x3: *const u8, x3_len: u64, d_frame_offsets: *const u64,
+                             d_sample_offsets: *const u64, n_frames: u64, p: *const x3_params, d_seg_index: *const u64,
+                             seg_blocks: u32, bin_len: u64, d_levels: *mut x3_level, n_bins: u64, d_frame_status: *mut i32) -> c_int;
+        pub fn x3_levels_result(ctx: *mut x3_ctx, n_bad_frames: *mut u64, first_bad: *mut u64, first_bad_status: *mut c_int) -> c_int;
+        pub fn x3_corpus_levels_rows(corpus: *const x3_corpus, bin_len: u64, row_first: *mut u64) -> c_int;
+        pub fn x3_corpus_levels_dev(ctx: *mut x3_ctx, corpus: *const x3_corpus, bin_len: u64, d_levels: *mut x3_level, n_rows: u64,
+                                    d_frame_status: *mut i32) -> c_int;
         pub fn x3_corpus_destroy(corpus: *mut x3_corpus);
         pub fn x3_place_buffers(ctx: *mut x3_ctx, d_wav: *const i16, n: u64, p: *const x3_params, d_streams: *const *mut u8,
                                 n_streams: u32, cap: u64, d_frame_offsets: *mut u64, d_backs: *const *mut i16, n_backs: u32,
@@ -1257,6 +1275,33 @@ pub mod device {
         Ok((n_bad, first_bad, st))
     }
 
+    /// One bin of `levels` / `Corpus::levels` (`x3_level`): `sum_sq`, `sum`, `min`, `max`, `n`; an empty bin holds the identities
+    /// (`min` 32767, `max` -32768, `n` 0)
+    pub type Level = ffi::x3_level;
+
+    /// Levels (`x3_levels_dev`; not in the reference crate): min, max, count, sum and sum of squares of the samples per bin of
+    /// `bin_len` positions (0: one bin) into `n_bins` records of `d_levels`, every one written, without a sample buffer.
+    /// `d_frame_status` (`n_frames` x i32, optional): a frame with a status other than 0 adds nothing.  Waits: -> (frames with
+    /// status != 0, the first of them, its status)
+    #[allow(clippy::too_many_arguments)]
+    pub fn levels<'g>(gpu: &'g Gpu, s: &EncodedStream<'g>, params: &x3::Parameters, sample_offsets: &Buffer<'g>, bin_len: u64,
+                      d_levels: &mut Buffer<'g>, n_bins: usize, d_frame_status: Option<&mut Buffer<'g>>) -> error::Result<(u64, u64, i32)> {
+        if d_levels.len() < core::mem::size_of::<Level>() * n_bins || d_frame_status.as_ref().map_or(false, |b| b.len() < 4 * s.n_frames) {
+            return Err(X3Error::BadArg);
+        }
+        let p = params.c()?;
+        let idx = match &s.seg_index { Some(i) => i.as_ptr::<u64>() as *const u64, None => core::ptr::null() };
+        let st_ptr = match d_frame_status { Some(b) => b.as_ptr::<i32>(), None => core::ptr::null_mut() };
+        error::check(unsafe {
+            ffi::x3_levels_dev(gpu.raw(), s.bytes.as_ptr::<u8>(), s.len as u64, s.frame_offsets.as_ptr::<u64>(),
+                               sample_offsets.as_ptr::<u64>(), s.n_frames as u64, &p, idx, s.seg_blocks, bin_len,
+                               d_levels.as_ptr::<Level>(), n_bins as u64, st_ptr)
+        })?;
+        let (mut n_bad, mut first_bad, mut st) = (0u64, 0u64, 0);
+        error::check(unsafe { ffi::x3_levels_result(gpu.raw(), &mut n_bad, &mut first_bad, &mut st) })?;
+        Ok((n_bad, first_bad, st))
+    }
+
     /// `decode_streams` flag: the entries are the frame part of .x3a archives (walked with the reader's 8 phantom bytes)
     pub const STREAMS_ARCHIVE_FRAMES: u32 = 1;
     /// `Corpus::build` flag: the segment index by `x3_seg_index_build_dev` -- for every parameter set, not only where a
@@ -1351,6 +1396,34 @@ pub mod device {
             })?;
             let (mut n_bad, mut first_bad, mut st) = (0u64, 0u64, 0);
             error::check(unsafe { ffi::x3_decode_windows_result(self.gpu.raw(), &mut n_bad, &mut first_bad, &mut st) })?;
+            Ok((n_bad, first_bad, st))
+        }
+    }
+
+    impl<'g> Corpus<'g> {
+        /// Entry e's records of `levels` are `[row_first[e], row_first[e + 1])`: max(1, ceil(n_samples / bin_len)) each, one with
+        /// `bin_len` 0 (`x3_corpus_levels_rows`; `n_entries + 1` words)
+        pub fn levels_rows(&self, bin_len: u64) -> Vec<u64> {
+            let mut v = vec![0u64; self.info().0 as usize + 1];
+            unsafe { ffi::x3_corpus_levels_rows(self.raw, bin_len, v.as_mut_ptr()) };
+            v
+        }
+
+        /// Levels of every entry (`x3_corpus_levels_dev`), positions relative to the entry; `d_levels` holds `n_rows` =
+        /// `levels_rows(bin_len)`'s last word records, `d_frame_status` one i32 per frame of the corpus (optional).  Waits: ->
+        /// (frames with status != 0, the first of them, its status)
+        pub fn levels(&self, bin_len: u64, d_levels: &mut Buffer<'g>, n_rows: usize, d_frame_status: Option<&mut Buffer<'g>>)
+                      -> error::Result<(u64, u64, i32)> {
+            if d_levels.len() < core::mem::size_of::<Level>() * n_rows
+                || d_frame_status.as_ref().map_or(false, |b| b.len() < 4 * self.info().1 as usize) {
+                return Err(X3Error::BadArg);
+            }
+            let st_ptr = match d_frame_status { Some(b) => b.as_ptr::<i32>(), None => core::ptr::null_mut() };
+            error::check(unsafe {
+                ffi::x3_corpus_levels_dev(self.gpu.raw(), self.raw, bin_len, d_levels.as_ptr::<Level>(), n_rows as u64, st_ptr)
+            })?;
+            let (mut n_bad, mut first_bad, mut st) = (0u64, 0u64, 0);
+            error::check(unsafe { ffi::x3_levels_result(self.gpu.raw(), &mut n_bad, &mut first_bad, &mut st) })?;
             Ok((n_bad, first_bad, st))
         }
     }

@@ -60,6 +60,7 @@ SYMBOLS = [
     "x3_decode_streams_dev", "x3_decode_streams_result",
     "x3_corpus_build", "x3_corpus_info", "x3_corpus_entries", "x3_corpus_seg_index", "x3_corpus_windows_dev",
     "x3_corpus_destroy",
+    "x3_levels_dev", "x3_levels_result", "x3_corpus_levels_rows", "x3_corpus_levels_dev",
     "x3_tune_candidate", "x3_tuner_create", "x3_tuner_add_dev", "x3_tuner_result", "x3_tuner_max_payloads",
     "x3_tuner_reset", "x3_tuner_destroy", "x3_tune", "x3_x3a_encode_tuned",
 ]
@@ -69,6 +70,11 @@ TUNE_CANDIDATES, TUNE_DEFAULT_INDEX, TUNE_DEFAULT_SPF = 2184, 1188, 10000   # in
 WINDOW_I16, WINDOW_F32 = 0, 1   # x3_decode_windows_dev output formats
 STREAMS_ARCHIVE_FRAMES = 1       # x3_decode_streams_dev: entries are the frame part of .x3a archives
 CORPUS_INDEX_WALK = 0x100        # x3_corpus_build: the segment index by x3_seg_index_build_dev (any parameters)
+
+
+# x3_level: one bin of x3_levels_dev / x3_corpus_levels_dev (32 bytes)
+LEVEL_DTYPE = np.dtype([("sum_sq", np.uint64), ("sum", np.int64), ("min", np.int32), ("max", np.int32), ("n", np.uint32),
+                        ("reserved", np.uint32)])
 
 
 class StreamResult(C.Structure):
@@ -224,6 +230,10 @@ def lib():
     L.x3_corpus_seg_index.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
     L.x3_corpus_windows_dev.argtypes = [vp, vp, vp, vp, u64, u32, vp, i32, vp]
     L.x3_corpus_destroy.argtypes = [vp]
+    L.x3_levels_dev.argtypes = [vp, vp, u64, vp, vp, u64, PP, vp, u32, u64, vp, u64, vp]
+    L.x3_levels_result.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(i32)]
+    L.x3_corpus_levels_rows.argtypes = [vp, u64, vp]
+    L.x3_corpus_levels_dev.argtypes = [vp, vp, u64, vp, u64, vp]
     L.x3_corpus_destroy.restype = None
     L.x3_synth.argtypes = [i32, u64, u64, u64, vp]
     L.x3_synth_dev.argtypes = [vp, i32, u64, u64, u64, vp]
@@ -924,6 +934,22 @@ class Context:
         rc = lib().x3_decode_windows_result(self._h, C.byref(nb), C.byref(fb), C.byref(st))
         return rc, nb.value, fb.value, st.value
 
+    def levels_dev(self, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, params, bin_len, d_levels, n_bins,
+                   d_frame_status=None, d_seg_index=None, seg_blocks=0):
+        """x3_levels_dev: n_bins x3_level records (LEVEL_DTYPE) of bins of bin_len positions (0: one bin); asynchronous"""
+        return lib().x3_levels_dev(self._h, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, C.byref(params),
+                                   d_seg_index, seg_blocks, bin_len, d_levels, n_bins, d_frame_status)
+
+    def levels_result(self):
+        """-> (rc, n_bad_frames, first_bad, first_bad_status) of the last levels_dev / corpus_levels_dev"""
+        nb, fb, st = C.c_uint64(0), C.c_uint64(0), C.c_int32(0)
+        rc = lib().x3_levels_result(self._h, C.byref(nb), C.byref(fb), C.byref(st))
+        return rc, nb.value, fb.value, st.value
+
+    def corpus_levels_dev(self, corpus, bin_len, d_levels, n_rows, d_frame_status=None):
+        """x3_corpus_levels_dev: the levels of every entry of `corpus` (a Corpus), rows as Corpus.levels_rows; asynchronous"""
+        return lib().x3_corpus_levels_dev(self._h, corpus._h, bin_len, d_levels, n_rows, d_frame_status)
+
     def decode_streams_dev(self, d_x3, x3_len, offsets, lengths, params, d_out, row_len, out_format, d_results, flags=0):
         """x3_decode_streams_dev: entry s = bytes [offsets[s], offsets[s] + lengths[s]) of d_x3 -> row s of d_out
         (len(offsets) x row_len samples) and d_results[s] (asynchronous; offsets / lengths: host sequences)"""
@@ -1100,6 +1126,26 @@ class WindowSource:
             return rows.reshape(n, length), self.ctx.download(d_st, 4 * n, np.int32)
         finally:
             for p in (d_starts, d_out, d_st):
+                self.ctx.free(p)
+
+    def levels(self, bin_len, n_bins=None):
+        """-> (records np.ndarray of LEVEL_DTYPE [n_bins], frame statuses np.int32 [n_frames]): min, max, n, sum and sum of
+        squares per bin of bin_len positions (0: one bin); n_bins: as many as cover the stream unless given"""
+        if n_bins is None:
+            n_bins = max(1, -(-self.total // bin_len)) if bin_len else 1
+        d_lv, d_st = self.ctx.alloc(LEVEL_DTYPE.itemsize * n_bins), self.ctx.alloc(4 * self.n_frames)
+        try:
+            rc = self.ctx.levels_dev(self.d_x3, self.x3_len, self.d_frame_offsets, self.d_sample_offsets, self.n_frames,
+                                     self.params, bin_len, d_lv, n_bins, d_st, self.d_seg_index, self.seg_blocks)
+            if rc:
+                raise X3Error(rc, "x3_levels_dev: " + self.ctx.last_error())
+            rc = self.ctx.levels_result()[0]
+            if rc:
+                raise X3Error(rc, "x3_levels_result: " + self.ctx.last_error())
+            return (self.ctx.download(d_lv, LEVEL_DTYPE.itemsize * n_bins, LEVEL_DTYPE),
+                    self.ctx.download(d_st, 4 * self.n_frames, np.int32))
+        finally:
+            for p in (d_lv, d_st):
                 self.ctx.free(p)
 
     def close(self):
@@ -1311,6 +1357,35 @@ class Corpus:
         finally:
             for ptr in (d_ent, d_starts, d_out, d_st):
                 self.ctx.free(ptr)
+
+    def levels_rows(self, bin_len):
+        """-> row_first np.uint64 [n_entries + 1]: entry e's rows of levels() are [row_first[e], row_first[e + 1])"""
+        if self._h is None:
+            raise ValueError("the corpus is closed")
+        rf = np.zeros(self.entries.size + 1, dtype=np.uint64)
+        rc = lib().x3_corpus_levels_rows(self._h, bin_len, rf.ctypes.data)
+        if rc:
+            raise X3Error(rc, "x3_corpus_levels_rows")
+        return rf
+
+    def levels(self, bin_len):
+        """-> (records np.ndarray of LEVEL_DTYPE [rows], row_first np.uint64 [n_entries + 1], frame statuses np.int32
+        [n_frames]): the levels of every entry, positions relative to the entry, bins of bin_len positions (0: one bin)"""
+        rf = self.levels_rows(bin_len)
+        n_rows = int(rf[-1])
+        d_lv, d_st = self.ctx.alloc(LEVEL_DTYPE.itemsize * n_rows), self.ctx.alloc(4 * max(self.n_frames, 1))
+        try:
+            rc = self.ctx.corpus_levels_dev(self, bin_len, d_lv, n_rows, d_st)
+            if rc:
+                raise X3Error(rc, "x3_corpus_levels_dev: " + self.ctx.last_error())
+            rc = self.ctx.levels_result()[0]
+            if rc:
+                raise X3Error(rc, "x3_levels_result: " + self.ctx.last_error())
+            st = self.ctx.download(d_st, 4 * self.n_frames, np.int32) if self.n_frames else np.zeros(0, dtype=np.int32)
+            return self.ctx.download(d_lv, LEVEL_DTYPE.itemsize * n_rows, LEVEL_DTYPE), rf, st
+        finally:
+            for p in (d_lv, d_st):
+                self.ctx.free(p)
 
     def close(self):
         if self._h is not None:
