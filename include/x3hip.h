@@ -607,6 +607,40 @@ int x3_decode_windows_dev(x3_ctx* ctx, const uint8_t* d_x3, uint64_t x3_len, con
                           uint64_t n_windows, uint32_t window_len, void* d_out, int out_format, int32_t* d_status);
 /* Waits for the last x3_decode_windows_dev: windows with status != 0, the first of them (n_windows if none) and its status. */
 int x3_decode_windows_result(x3_ctx* ctx, uint64_t* n_bad, uint64_t* first_bad, int* first_bad_status);
+/* RANGES: windows with a length each.  Range w = positions [d_starts[w], d_starts[w] + d_lens[w]) (device arrays: uint64 /
+ * uint32; positions as above).  Row and status of range w are exactly what x3_decode_windows_dev gives the single window
+ * (d_starts[w], window_len = d_lens[w]) of the same stream: the exact prefix in front of the first covering frame that
+ * fails, zeros behind it and that frame's status; a range off the end (start + len > total, any wild start) is
+ * X3_ERR_BAD_ARG and zeros.  d_lens[w] == 0 is legal: status 0 when start <= total, X3_ERR_BAD_ARG otherwise, no frame is
+ * covered, nothing of the row is written (start + len - 1 is never formed for it).
+ *   PACKED (row_stride == 0): row w begins at off[w], the exclusive sum of ALL lengths -- those of bad ranges too, so the
+ * layout depends on the lengths alone.  d_out_offsets (required) receives off[0 .. n_ranges], the last being the total.  A
+ * range with off[w] + d_lens[w] > out_cap is X3_ERR_BAD_ARG and none of its samples is written; ranges that fit are
+ * complete, and x3_decode_ranges_result reports the total, so a caller can grow d_out and repeat the call.
+ *   PADDED (row_stride > 0): row w begins at w * row_stride and [d_lens[w], row_stride) of EVERY row is written as zero.
+ * A range with d_lens[w] > row_stride is X3_ERR_BAD_ARG and a row of zeros.  n_ranges * row_stride > out_cap fails the
+ * call.  d_out_offsets may be NULL; when given it receives w * row_stride (n_ranges + 1 words).
+ *   out_cap counts samples of out_format.  Starts and lengths are untrusted like everything the window calls take: nothing
+ * outside d_out[0 .. out_cap), d_status[0 .. n_ranges) and d_out_offsets[0 .. n_ranges] is written, nothing outside
+ * [d_x3, d_x3 + x3_len) is read; the sums of the lengths are 64-bit and cannot wrap (n_ranges <= 0x7FFFFFFF, 32-bit lengths).
+ *   Asynchronous on the context's stream: one launch set, no host trip, nothing allocated after the first call of a size.
+ * The call shares the window calls' workspace and pending slot: a ranges call REPLACES the state of a pending
+ * x3_decode_windows_dev / x3_corpus_windows_dev and the other way round (the kernels are ordered on the stream; only the
+ * summary of the earlier call is lost).  x3_decode_ranges_result belongs to the last ranges call, x3_decode_windows_result to
+ * the last windows call; each is X3_ERR_BAD_ARG when the pending call is of the other kind.  The pending states of
+ * x3_decode_dev and of the levels calls are left alone.  X3_ERR_BAD_ARG with nothing enqueued for n_ranges == 0 or above
+ * 0x7FFFFFFF, a NULL or misaligned pointer (d_out_offsets: NULL only when padded), an unknown format, a seg_blocks that
+ * x3_decode_dev_seg refuses, parameters that x3_decode_windows_dev refuses, and a context that is recording a graph.
+ * DESIGN.md section 16. */
+int x3_decode_ranges_dev(x3_ctx* ctx, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
+                         const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
+                         const uint64_t* d_seg_index, uint32_t seg_blocks, const uint64_t* d_starts,
+                         const uint32_t* d_lens, uint64_t n_ranges, uint64_t row_stride, void* d_out, uint64_t out_cap,
+                         int out_format, uint64_t* d_out_offsets, int32_t* d_status);
+/* Waits for the last x3_decode_ranges_dev / x3_corpus_ranges_dev: ranges with status != 0, the first of them (n_ranges if
+ * none), its status, and the sum of all lengths (what a packed d_out must hold for no range to be refused). */
+int x3_decode_ranges_result(x3_ctx* ctx, uint64_t* n_bad, uint64_t* first_bad, int* first_bad_status,
+                            uint64_t* total_samples);
 /* out_format of x3_decode_windows_dev */
 #define X3_WINDOW_I16 0     /* int16 samples */
 #define X3_WINDOW_F32 1     /* float32 samples, s / 32768.0f (exact) */
@@ -735,6 +769,13 @@ int x3_corpus_seg_index(const x3_corpus* corpus, const uint64_t** d_seg_index, u
  * d_entries not on a 4-byte boundary, and a context on another device than the build's. */
 int x3_corpus_windows_dev(x3_ctx* ctx, const x3_corpus* corpus, const uint32_t* d_entries, const uint64_t* d_starts,
                           uint64_t n_windows, uint32_t window_len, void* d_out, int out_format, int32_t* d_status);
+/* Range w = samples [d_starts[w], d_starts[w] + d_lens[w]) of entry d_entries[w].  Layout (packed / padded), out_cap,
+ * d_out_offsets, zero lengths, refusals and x3_decode_ranges_result as for x3_decode_ranges_dev; entries and the end of an
+ * entry as for x3_corpus_windows_dev (a range never runs into the next entry; with d_lens[w] == 0 the status is 0 when the
+ * entry is in the corpus and start <= its n_samples).  Each result equals x3_decode_ranges_dev on that entry alone. */
+int x3_corpus_ranges_dev(x3_ctx* ctx, const x3_corpus* corpus, const uint32_t* d_entries, const uint64_t* d_starts,
+                         const uint32_t* d_lens, uint64_t n_ranges, uint64_t row_stride, void* d_out, uint64_t out_cap,
+                         int out_format, uint64_t* d_out_offsets, int32_t* d_status);
 /* LEVELS of every entry of a corpus.  Entry e has max(1, ceil(n_samples[e] / bin_len)) rows (one with bin_len == 0), the
  * rows lie entry after entry; x3_corpus_levels_rows writes that prefix (HOST array of n_entries + 1 words, from the entry
  * table).  Positions are relative to the entry, and entry e's rows are exactly what x3_levels_dev gives on that entry alone

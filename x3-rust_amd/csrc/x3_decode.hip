@@ -1053,24 +1053,36 @@ static bool windows_args_ok(uint64_t n_windows, uint32_t window_len, const void*
   return (reinterpret_cast<uintptr_t>(d_starts) & 7u) == 0 && (reinterpret_cast<uintptr_t>(d_status) & 3u) == 0;
 }
 
-// The launch set of a windows call (x3_decode_window_kernel.h) behind its plan step: plan(grid, plan, gstart, sum) enqueues
-// the plan kernel and returns the starts the decode and fix-up kernels read (the caller's, or the plan's gstart).
+// the rows of a ranges call (x3_decode_ranges_dev / x3_corpus_ranges_dev); a windows call has none: its rows are w * L
+struct RangeRows {
+  const uint32_t* d_lens;
+  uint64_t row_stride, out_cap;
+  uint64_t* d_out_offsets;
+  uint64_t max_frames;   // the most frames a range can cover: the stream's, or the longest entry's
+};
+
+// The launch set of a windows or ranges call (x3_decode_window_kernel.h) behind its plan step: plan(grid, plan, gstart, sum)
+// enqueues the plan kernel and returns the starts the decode and fix-up kernels read (the caller's, or the plan's gstart).
+// rows: the geometry of a ranges call (the scan, decode and fix-up kernels are then the range siblings), NULL for windows of
+// window_len; len_hint sizes the grids (the window length, or what a range can have on average).
 template <class Plan>
 static int windows_launch(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
                           const uint64_t* d_sample_offsets, uint64_t n_frames, const X3DevParams& dp, uint64_t spf,
                           const uint64_t* d_seg_index, uint32_t seg_blocks, uint64_t n_windows, uint32_t window_len,
-                          void* d_out, int out_format, int32_t* d_status, Plan plan_step) {
+                          const RangeRows* rows, void* d_out, int out_format, int32_t* d_status, Plan plan_step) {
   // the stretches of a frame as the index tells them apart (x3_seg_index_entries); 1 = whole frames
   const uint64_t nidx = d_seg_index ? seg_stretches(dp.blocks_per_frame, seg_blocks) : 1;
   const uint32_t nseg = nidx >= 2 ? (uint32_t)nidx : 1u;
   const uint2* idx = nseg >= 2 ? reinterpret_cast<const uint2*>(d_seg_index) : nullptr;
-  // workspace: plans, the two scans, per-frame verdicts, a block of replay scratch per window, the summary, the plan's starts
-  const uint64_t n = n_windows;
+  // workspace: plans, the two scans, per-frame verdicts, a block of replay scratch per window, the summary, the plan's starts;
+  // ranges: the scan of the lengths and the lengths that have room
+  const uint64_t n = n_windows, nr = rows ? n : 0;
   const uint32_t scratch_per = (dp.block_len + 7u) & ~7u;
   auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
   const size_t o_plan = 0, o_cov = up(o_plan + n * sizeof(X3WinPlan)), o_item = up(o_cov + (n + 1) * 8),
                o_fst = up(o_item + (n + 1) * 8), o_scr = up(o_fst + n_frames * 4), o_sum = up(o_scr + n * scratch_per * 2),
-               o_gs = up(o_sum + sizeof(X3WinSummary)), total = o_gs + n * 8;
+               o_gs = up(o_sum + sizeof(X3WinSummary)), end_gs = o_gs + n * 8, o_off = up(end_gs), o_elen = up(o_off + (nr + 1) * 8),
+               total = rows ? o_elen + nr * 4 : end_gs;
   int rc;
   if ((rc = ensure(c, c->win_ws, total))) return rc;
   char* const ws = (char*)c->win_ws.p;
@@ -1081,23 +1093,44 @@ static int windows_launch(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const
   int16_t* scratch = (int16_t*)(ws + o_scr);
   X3WinSummary* sum = (X3WinSummary*)(ws + o_sum);
   // grids: the plan covers the windows; the grid-stride kernels take as many groups as the work of full-length frames needs,
-  // at most X3W_GRID_LIMIT (their counts are on the device)
-  const uint64_t frames_per = (uint64_t)window_len / (spf ? spf : 1) + 2;
+  // at most X3W_GRID_LIMIT (their counts are on the device).  Ranges: the lengths are device data; what fits the rows is
+  // out_cap / n (packed) or the stride on average, and ranges without room cover nothing.  Both are the caller's words and
+  // may be far above what is drawn: a length has 32 bits and a range covers no more frames than the stream (or the longest
+  // entry) has, so a roomy buffer does not size the grids.
+  const uint64_t len_hint = !rows ? window_len : std::min<uint64_t>(rows->row_stride ? rows->row_stride : rows->out_cap / n, 0xFFFFFFFFull);
+  uint64_t frames_per = len_hint / (spf ? spf : 1) + 2;
+  if (rows) frames_per = std::max<uint64_t>(1, std::min(frames_per, rows->max_frames));
   auto groups = [&](uint64_t units, uint64_t per_group) {
     return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((units + per_group - 1) / per_group, X3W_GRID_LIMIT));
   };
   const uint64_t* d_starts = plan_step(dim3(groups(n, 256)), plan, (uint64_t*)(ws + o_gs), sum);
-  hipLaunchKernelGGL(x3_window_scan_kernel, dim3(1), dim3(1024), 0, c->stream, plan, n, idx, seg_blocks, nseg, cov_off, item_off);
-  hipLaunchKernelGGL(x3_window_check_kernel, dim3(groups(n * frames_per, 4)), dim3(256), 0, c->stream, d_x3, x3_len,
-                     d_frame_offsets, d_sample_offsets, plan, n, cov_off, fst);
-  hipLaunchKernelGGL(x3_window_decode_kernel, dim3(groups(n * frames_per * nseg, 256)), dim3(256), 0, c->stream, d_x3, x3_len,
-                     d_frame_offsets, d_sample_offsets, d_starts, plan, n, window_len, item_off, dp, idx, seg_blocks, nseg,
-                     d_out, out_format, fst);
-  hipLaunchKernelGGL(x3_window_fixup_kernel, dim3(groups(n, 4)), dim3(256), 0, c->stream, d_x3, d_frame_offsets,
-                     d_sample_offsets, d_starts, plan, n, window_len, dp, fst, d_out, out_format, d_status, scratch,
-                     scratch_per, sum);
+  // (ranges: n < 2^31 and frames_per < 2^32 + 3, the first product cannot wrap; the second is capped before it is formed)
+  const uint64_t cov_hint = n * frames_per, item_hint = std::min<uint64_t>(cov_hint, 256ull * X3W_GRID_LIMIT) * nseg;
+  const dim3 g_check(groups(cov_hint, 4)), g_decode(groups(item_hint, 256)), g_fix(groups(n, 4));
+  if (rows)
+    hipLaunchKernelGGL(x3_range_scan_kernel, dim3(1), dim3(1024), 0, c->stream, plan, n, rows->d_lens, rows->row_stride,
+                       rows->out_cap, idx, seg_blocks, nseg, cov_off, item_off, (unsigned long long*)(ws + o_off),
+                       (uint32_t*)(ws + o_elen), rows->d_out_offsets, sum);
+  else
+    hipLaunchKernelGGL(x3_window_scan_kernel, dim3(1), dim3(1024), 0, c->stream, plan, n, idx, seg_blocks, nseg, cov_off, item_off);
+  hipLaunchKernelGGL(x3_window_check_kernel, g_check, dim3(256), 0, c->stream, d_x3, x3_len, d_frame_offsets, d_sample_offsets,
+                     plan, n, cov_off, fst);
+  auto decode_fixup = [&](auto g) {   // g: the rows, X3WinFixedGeo or X3WinRangeGeo
+    using Geo = decltype(g);
+    hipLaunchKernelGGL((x3_window_decode_kernel<Geo>), g_decode, dim3(256), 0, c->stream, d_x3, x3_len, d_frame_offsets,
+                       d_sample_offsets, d_starts, (const X3WinPlan*)plan, n, g, (const unsigned long long*)item_off, dp, idx,
+                       seg_blocks, nseg, d_out, out_format, fst);
+    hipLaunchKernelGGL((x3_window_fixup_kernel<Geo>), g_fix, dim3(256), 0, c->stream, d_x3, d_frame_offsets, d_sample_offsets,
+                       d_starts, (const X3WinPlan*)plan, n, g, dp, (const int32_t*)fst, d_out, out_format, d_status, scratch,
+                       scratch_per, sum);
+  };
+  if (rows)
+    decode_fixup(X3WinRangeGeo{(const uint32_t*)(ws + o_elen), (const unsigned long long*)(ws + o_off), rows->row_stride});
+  else
+    decode_fixup(X3WinFixedGeo{window_len});
   HIPCHK(c, hipGetLastError());
   c->windows_pending = true;
+  c->win_ranges = rows != nullptr;
   c->win_windows = n;
   c->win_sum_off = o_sum;
   return X3_OK;
@@ -1118,7 +1151,7 @@ extern "C" int x3_decode_windows_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3
   if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   return windows_launch(c, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, dp, spf, d_seg_index, seg_blocks, n_windows,
-                        window_len, d_out, out_format, d_status,
+                        window_len, nullptr, d_out, out_format, d_status,
                         [&](dim3 grid, X3WinPlan* plan, uint64_t*, X3WinSummary* sum) -> const uint64_t* {
                           hipLaunchKernelGGL(x3_window_plan_kernel, grid, dim3(256), 0, c->stream, d_sample_offsets, n_frames,
                                              d_starts, n_windows, window_len, plan, sum);
@@ -1126,17 +1159,78 @@ extern "C" int x3_decode_windows_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3
                         });
 }
 
-extern "C" int x3_decode_windows_result(x3_ctx* c, uint64_t* n_bad, uint64_t* first_bad, int* first_bad_status) {
-  if (!c || !c->windows_pending) return X3_ERR_BAD_ARG;
-  X3WinSummary h{0, 0, 0};
-  HIPCHK(c, hipMemcpyAsync(&h, (char*)c->win_ws.p + c->win_sum_off, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+// waits for the pending windows (ranges: false) or ranges (true) call and reads its summary
+static int windows_summary(x3_ctx* c, bool ranges, X3WinSummary* h) {
+  if (!c || !c->windows_pending || c->win_ranges != ranges) return X3_ERR_BAD_ARG;
+  HIPCHK(c, hipMemcpyAsync(h, (char*)c->win_ws.p + c->win_sum_off, sizeof(*h), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->windows_pending = false;
-  c->last_window_replays = h.replays;
+  c->last_window_replays = h->replays;
+  return X3_OK;
+}
+
+extern "C" int x3_decode_windows_result(x3_ctx* c, uint64_t* n_bad, uint64_t* first_bad, int* first_bad_status) {
+  X3WinSummary h{0, 0, 0, 0};
+  const int rc = windows_summary(c, false, &h);
+  if (rc) return rc;
   const bool any = h.n_bad != 0;
   if (n_bad) *n_bad = h.n_bad;
   if (first_bad) *first_bad = any ? (h.first >> 8) : c->win_windows;
   if (first_bad_status) *first_bad_status = any ? (int)(h.first & 0xFFu) : 0;
+  return X3_OK;
+}
+
+// ranges: a length per range, rows packed or padded
+// the argument checks x3_decode_ranges_dev and x3_corpus_ranges_dev share
+static bool ranges_args_ok(const x3_ctx* c, uint64_t n_ranges, const uint32_t* d_lens, uint64_t row_stride, const void* d_out,
+                           uint64_t out_cap, int out_format, const uint64_t* d_starts, const uint64_t* d_out_offsets,
+                           const int32_t* d_status) {
+  if (!d_starts || !d_lens || !d_out || !d_status || c->capturing) return false;
+  if (n_ranges == 0 || n_ranges > 0x7FFFFFFFull) return false;
+  if (out_format != X3_WINDOW_I16 && out_format != X3_WINDOW_F32) return false;
+  const uint64_t esz = out_format == X3_WINDOW_F32 ? 4u : 2u;
+  if (reinterpret_cast<uintptr_t>(d_out) % esz || out_cap > ~0ull / esz) return false;
+  if (row_stride ? row_stride > out_cap / n_ranges : !d_out_offsets) return false;
+  return (reinterpret_cast<uintptr_t>(d_starts) & 7u) == 0 && (reinterpret_cast<uintptr_t>(d_lens) & 3u) == 0 &&
+         (reinterpret_cast<uintptr_t>(d_out_offsets) & 7u) == 0 && (reinterpret_cast<uintptr_t>(d_status) & 3u) == 0;
+}
+
+extern "C" int x3_decode_ranges_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
+                                    const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
+                                    const uint64_t* d_seg_index, uint32_t seg_blocks, const uint64_t* d_starts,
+                                    const uint32_t* d_lens, uint64_t n_ranges, uint64_t row_stride, void* d_out,
+                                    uint64_t out_cap, int out_format, uint64_t* d_out_offsets, int32_t* d_status) {
+  if (!c || !d_x3 || !d_frame_offsets || !d_sample_offsets || !p) return X3_ERR_BAD_ARG;
+  if (!ranges_args_ok(c, n_ranges, d_lens, row_stride, d_out, out_cap, out_format, d_starts, d_out_offsets, d_status))
+    return X3_ERR_BAD_ARG;
+  if (!frame_table_args_ok(d_x3, d_frame_offsets, n_frames) || (reinterpret_cast<uintptr_t>(d_sample_offsets) & 7u))
+    return X3_ERR_BAD_ARG;
+  if (d_seg_index && !seg_index_args_ok(d_seg_index, seg_blocks)) return X3_ERR_BAD_ARG;
+  X3DevParams dp;
+  const uint64_t spf = spf_of(p);
+  int rc = derive_block_params(p, &dp);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  const RangeRows rows{d_lens, row_stride, out_cap, d_out_offsets, n_frames};
+  return windows_launch(c, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, dp, spf, d_seg_index, seg_blocks, n_ranges,
+                        0, &rows, d_out, out_format, d_status,
+                        [&](dim3 grid, X3WinPlan* plan, uint64_t*, X3WinSummary* sum) -> const uint64_t* {
+                          hipLaunchKernelGGL(x3_range_plan_kernel, grid, dim3(256), 0, c->stream, d_sample_offsets, n_frames,
+                                             d_starts, d_lens, n_ranges, plan, sum);
+                          return d_starts;
+                        });
+}
+
+extern "C" int x3_decode_ranges_result(x3_ctx* c, uint64_t* n_bad, uint64_t* first_bad, int* first_bad_status,
+                                       uint64_t* total_samples) {
+  X3WinSummary h{0, 0, 0, 0};
+  const int rc = windows_summary(c, true, &h);
+  if (rc) return rc;
+  const bool any = h.n_bad != 0;
+  if (n_bad) *n_bad = h.n_bad;
+  if (first_bad) *first_bad = any ? (h.first >> 8) : c->win_windows;
+  if (first_bad_status) *first_bad_status = any ? (int)(h.first & 0xFFu) : 0;
+  if (total_samples) *total_samples = h.total;
   return X3_OK;
 }
 
@@ -1569,6 +1663,7 @@ struct x3_corpus {
   int device = 0;
   const uint8_t* d_x3 = nullptr;
   uint64_t x3_len = 0, n = 0, F = 0, total = 0;
+  uint64_t max_frames = 0;             // the longest entry's frames (sizes the grids of a ranges call)
   x3_params p{};
   uint32_t seg_blocks = 0;             // in use (0: no index)
   uint64_t* d_frame_off = nullptr;     // F words (at least one): the frames' byte offsets in d_x3, entries in order
@@ -1704,6 +1799,7 @@ static int corpus_build_impl(x3_ctx* c, x3_corpus* k, const uint64_t* offsets, c
     }
     en.first_frame = F;
     F += en.n_frames;
+    k->max_frames = std::max<uint64_t>(k->max_frames, en.n_frames);
   }
   if (F > 0x7FFFFFFFull) {
     c->last_error = "x3_corpus_build: more than 0x7FFFFFFF frames";
@@ -1818,10 +1914,38 @@ extern "C" int x3_corpus_windows_dev(x3_ctx* c, const x3_corpus* k, const uint32
   const x3_corpus_entry* ent = k->d_ent;
   const uint64_t* so = k->d_so;
   return windows_launch(c, k->d_x3, k->x3_len, k->d_frame_off, k->d_so, F, dp, spf, k->d_index, k->seg_blocks, n_windows,
-                        window_len, d_out, out_format, d_status,
+                        window_len, nullptr, d_out, out_format, d_status,
                         [&](dim3 grid, X3WinPlan* plan, uint64_t* gstart, X3WinSummary* sum) -> const uint64_t* {
                           hipLaunchKernelGGL(x3_corpus_plan_kernel, grid, dim3(256), 0, c->stream, ent, n_ent, so, F, d_entries,
                                              d_starts, n_windows, window_len, plan, gstart, sum);
+                          return gstart;
+                        });
+}
+
+extern "C" int x3_corpus_ranges_dev(x3_ctx* c, const x3_corpus* k, const uint32_t* d_entries, const uint64_t* d_starts,
+                                    const uint32_t* d_lens, uint64_t n_ranges, uint64_t row_stride, void* d_out,
+                                    uint64_t out_cap, int out_format, uint64_t* d_out_offsets, int32_t* d_status) {
+  if (!c || !k || !d_entries || (reinterpret_cast<uintptr_t>(d_entries) & 3u)) return X3_ERR_BAD_ARG;
+  if (!ranges_args_ok(c, n_ranges, d_lens, row_stride, d_out, out_cap, out_format, d_starts, d_out_offsets, d_status))
+    return X3_ERR_BAD_ARG;
+  if (c->device != k->device) {
+    c->last_error = "x3_corpus_ranges_dev: the corpus was built on another device";
+    return X3_ERR_BAD_ARG;
+  }
+  X3DevParams dp;
+  const uint64_t spf = spf_of(&k->p);
+  int rc = derive_params(&k->p, &dp);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  const uint64_t n_ent = k->n, F = k->F;
+  const x3_corpus_entry* ent = k->d_ent;
+  const uint64_t* so = k->d_so;
+  const RangeRows rows{d_lens, row_stride, out_cap, d_out_offsets, k->max_frames};
+  return windows_launch(c, k->d_x3, k->x3_len, k->d_frame_off, k->d_so, F, dp, spf, k->d_index, k->seg_blocks, n_ranges, 0,
+                        &rows, d_out, out_format, d_status,
+                        [&](dim3 grid, X3WinPlan* plan, uint64_t* gstart, X3WinSummary* sum) -> const uint64_t* {
+                          hipLaunchKernelGGL(x3_corpus_range_plan_kernel, grid, dim3(256), 0, c->stream, ent, n_ent, so, F,
+                                             d_entries, d_starts, d_lens, n_ranges, plan, gstart, sum);
                           return gstart;
                         });
 }

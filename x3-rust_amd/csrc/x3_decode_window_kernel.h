@@ -24,6 +24,10 @@
 //
 // Nothing here trusts the caller's offsets, starts or index: every stream read is bounds-checked against x3_len (a
 // partial last dword is read byte by byte), every store is at a row position in [0, L).
+//
+// RANGES (x3_decode_ranges_dev): the same launch set with a length per window.  x3_range_plan_kernel / x3_corpus_range_plan_kernel
+// read lens[w], x3_range_scan_kernel scans the lengths in front of the covering frames, and the decode and fix-up kernels are
+// the templates' other instance: their rows come from X3WinRangeGeo instead of w * L and L.
 #pragma once
 #include "x3_device.h"
 #include "x3_decode_kernel.h"
@@ -46,6 +50,7 @@ struct X3WinSummary {
   unsigned long long n_bad;
   unsigned long long first;
   unsigned long long replays;
+  unsigned long long total;   // ranges only: the sum of all lengths (x3_range_scan_kernel)
 };
 
 // stream dword j (bytes 4j .. 4j+3) as a big-endian value, bytes at or beyond len read as zero
@@ -262,30 +267,50 @@ x3_window_sample_offsets_kernel(const uint8_t* __restrict__ x3, uint64_t len, co
   if (threadIdx.x == 0) so[F] = total;
 }
 
+// The plan of positions [start, start + L) of a stream: BAD_ARG off the end, else the covering frames by binary search.
+// ZeroLen (the range plans; the window calls refuse L == 0 on the host and their instances hold no test of it): L == 0 covers
+// nothing and start + L - 1 is not formed.
+template <bool ZeroLen>
+__device__ __forceinline__ X3WinPlan x3w_plan_stream(const uint64_t* __restrict__ so, uint64_t F, uint64_t total, uint64_t start,
+                                                     uint32_t L) {
+  X3WinPlan pl{0, 0, X3D_BAD_ARG};
+  // (so[0] <= start and so[F] > start + L - 1 are the search's invariants; offsets that break them are not this stream's)
+  if (L <= total && start <= total - L && so[0] <= start) {
+    if (ZeroLen && L == 0u) return X3WinPlan{0, 0, X3D_OK};
+    const uint64_t e = start + (L - 1u);
+    const uint64_t fa = x3w_search(so, 0, F, start);
+    const uint64_t fb = x3w_search(so, fa, F, e);
+    // more covering frames than samples: a frame of 0 samples or offsets out of order, no stream's frames
+    if (fb - fa < (uint64_t)L) pl = X3WinPlan{fa, (uint32_t)(fb - fa + 1u), X3D_OK};
+  }
+  return pl;
+}
+
 // ---- plan: a thread per window, grid-stride (the grid is capped at X3W_GRID_LIMIT groups; every window gets its plan)
+__device__ __forceinline__ void x3w_summary_init(X3WinSummary* __restrict__ sum) {
+  sum->n_bad = 0;
+  sum->first = ~0ull;
+  sum->replays = 0;
+}
+
 __global__ void __launch_bounds__(256)
 x3_window_plan_kernel(const uint64_t* __restrict__ so, uint64_t F, const uint64_t* __restrict__ starts, uint64_t n_windows,
                       uint32_t L, X3WinPlan* __restrict__ plan, X3WinSummary* __restrict__ sum) {
   const uint64_t w0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (w0 == 0) {
-    sum->n_bad = 0;
-    sum->first = ~0ull;
-    sum->replays = 0;
-  }
+  if (w0 == 0) x3w_summary_init(sum);
   const uint64_t total = so[F];
-  for (uint64_t w = w0; w < n_windows; w += (uint64_t)gridDim.x * blockDim.x) {
-    const uint64_t start = starts[w];
-    X3WinPlan pl{0, 0, X3D_BAD_ARG};
-    // (so[0] <= start and so[F] > start + L - 1 are the search's invariants; offsets that break them are not this stream's)
-    if (L <= total && start <= total - L && so[0] <= start) {
-      const uint64_t e = start + (L - 1u);
-      const uint64_t fa = x3w_search(so, 0, F, start);
-      const uint64_t fb = x3w_search(so, fa, F, e);
-      // more covering frames than samples: a frame of 0 samples or offsets out of order, no stream's frames
-      if (fb - fa < (uint64_t)L) pl = X3WinPlan{fa, (uint32_t)(fb - fa + 1u), X3D_OK};
-    }
-    plan[w] = pl;
-  }
+  for (uint64_t w = w0; w < n_windows; w += (uint64_t)gridDim.x * blockDim.x) plan[w] = x3w_plan_stream<false>(so, F, total, starts[w], L);
+}
+
+// the same with a length per range (x3_decode_ranges_dev)
+__global__ void __launch_bounds__(256)
+x3_range_plan_kernel(const uint64_t* __restrict__ so, uint64_t F, const uint64_t* __restrict__ starts,
+                     const uint32_t* __restrict__ lens, uint64_t n_ranges, X3WinPlan* __restrict__ plan,
+                     X3WinSummary* __restrict__ sum) {
+  const uint64_t w0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (w0 == 0) x3w_summary_init(sum);
+  const uint64_t total = so[F];
+  for (uint64_t w = w0; w < n_ranges; w += (uint64_t)gridDim.x * blockDim.x) plan[w] = x3w_plan_stream<true>(so, F, total, starts[w], lens[w]);
 }
 
 // ---- exclusive scans of the covering frames (cov) and the work items (cov * stretches) per window; n + 1 entries each
@@ -300,6 +325,74 @@ x3_window_scan_kernel(const X3WinPlan* __restrict__ plan, uint64_t n, const uint
   for (uint64_t w = a; w < b; ++w) c += plan[w].ncov;
   unsigned long long total;
   unsigned long long run = x3w_block_excl_scan(c, s, &total);
+  for (uint64_t w = a; w < b; ++w) {
+    cov_off[w] = run;
+    item_off[w] = run * ns;
+    run += plan[w].ncov;
+  }
+  if (threadIdx.x == 0) {
+    cov_off[n] = total;
+    item_off[n] = total * ns;
+  }
+}
+
+// ---- RANGES (x3_decode_ranges_dev / x3_corpus_ranges_dev): a length per range, rows packed at the
+// exclusive scan of the lengths (stride 0) or padded to a common stride.
+// The rows of a call: where row w begins and how many samples of it are the range's.  X3WinFixedGeo is the window calls'
+// w * L and L; X3WinRangeGeo reads what x3_range_scan_kernel left in the workspace.  kTails: the fix-up zeroes
+// [len, row_end) of every row.
+struct X3WinFixedGeo {
+  uint32_t L;
+  static constexpr bool kTails = false;
+  __device__ __forceinline__ uint64_t base(uint64_t w) const { return w * (uint64_t)L; }
+  __device__ __forceinline__ uint32_t len(uint64_t) const { return L; }
+  __device__ __forceinline__ uint64_t row_end(uint64_t) const { return (uint64_t)L; }
+};
+struct X3WinRangeGeo {
+  const uint32_t* __restrict__ elen;            // the range's length, 0 for a range that has no room in its row
+  const unsigned long long* __restrict__ off;   // packed: the exclusive scan of ALL lengths, n + 1 words
+  uint64_t stride;                              // padded: the row stride; 0 = packed
+  static constexpr bool kTails = true;
+  __device__ __forceinline__ uint64_t base(uint64_t w) const { return stride ? w * stride : off[w]; }
+  __device__ __forceinline__ uint32_t len(uint64_t w) const { return elen[w]; }
+  __device__ __forceinline__ uint64_t row_end(uint64_t w) const { return stride ? stride : elen[w]; }
+};
+
+// x3_window_scan_kernel with the scan of the lengths in front of it: off[w] (packed; n + 1 words, also to the caller's
+// out_off, which gets w * stride when padded), the verdict on the row -- a range with off[w] + len > out_cap (packed) or
+// len > stride (padded) is X3D_BAD_ARG, covers nothing and stores nothing: elen[w] = 0 -- and then the covering frames and
+// work items of what is left.  64-bit sums of at most 2^31 32-bit lengths: no wrap.
+__global__ void __launch_bounds__(1024)
+x3_range_scan_kernel(X3WinPlan* __restrict__ plan, uint64_t n, const uint32_t* __restrict__ lens, uint64_t stride,
+                     uint64_t out_cap, const uint2* __restrict__ idx, uint32_t sb, uint32_t nseg,
+                     unsigned long long* __restrict__ cov_off, unsigned long long* __restrict__ item_off,
+                     unsigned long long* __restrict__ off, uint32_t* __restrict__ elen, uint64_t* __restrict__ out_off,
+                     X3WinSummary* __restrict__ sum) {
+  __shared__ unsigned long long s[1024];
+  const uint32_t ns = x3w_index_ok(idx, sb) ? nseg : 1u;
+  const uint64_t per = (n + blockDim.x - 1) / blockDim.x;
+  const uint64_t a = min((uint64_t)threadIdx.x * per, n), b = min(a + per, n);
+  unsigned long long c = 0;
+  for (uint64_t w = a; w < b; ++w) c += lens[w];
+  unsigned long long total;
+  unsigned long long run = x3w_block_excl_scan(c, s, &total);
+  c = 0;
+  for (uint64_t w = a; w < b; ++w) {
+    const uint32_t len = lens[w];
+    const bool fits = stride ? (uint64_t)len <= stride : (run <= out_cap && (uint64_t)len <= out_cap - run);
+    if (!fits) plan[w] = X3WinPlan{0, 0, X3D_BAD_ARG};
+    elen[w] = fits ? len : 0u;
+    off[w] = run;
+    if (out_off) out_off[w] = stride ? w * stride : run;
+    run += len;
+    c += fits ? plan[w].ncov : 0u;
+  }
+  if (threadIdx.x == 0) {
+    off[n] = total;
+    if (out_off) out_off[n] = stride ? n * stride : total;
+    sum->total = total;
+  }
+  run = x3w_block_excl_scan(c, s, &total);
   for (uint64_t w = a; w < b; ++w) {
     cov_off[w] = run;
     item_off[w] = run * ns;
@@ -429,10 +522,12 @@ __device__ __forceinline__ int x3w_stretch(const uint8_t* __restrict__ x3, uint6
   return ok ? 1 : -1;
 }
 
+// (Geo: the rows -- X3WinFixedGeo for the window calls, X3WinRangeGeo for the ranges)
+template <class Geo>
 __global__ void __launch_bounds__(256)
 x3_window_decode_kernel(const uint8_t* __restrict__ x3, uint64_t len, const uint64_t* __restrict__ frame_off,
                         const uint64_t* __restrict__ so, const uint64_t* __restrict__ starts, const X3WinPlan* __restrict__ plan,
-                        uint64_t n_windows, uint32_t L, const unsigned long long* __restrict__ item_off, X3DevParams p,
+                        uint64_t n_windows, Geo geo, const unsigned long long* __restrict__ item_off, X3DevParams p,
                         const uint2* __restrict__ idx, uint32_t sb, uint32_t nseg, void* __restrict__ out, int fmt,
                         int32_t* __restrict__ fst) {
   const bool segd = x3w_index_ok(idx, sb);
@@ -445,7 +540,8 @@ x3_window_decode_kernel(const uint8_t* __restrict__ x3, uint64_t len, const uint
     const uint64_t f = plan[w].fa + k / ns;
     const uint32_t j = (uint32_t)(k % ns);
     if (fst[f] != X3D_OK) continue;   // (checked: header, CRC, sample count; a frame that failed is not decoded)
-    const uint64_t rbase = w * (uint64_t)L, start = starts[w], fpos = so[f];
+    const uint64_t rbase = geo.base(w), start = starts[w], fpos = so[f];
+    const auto L = geo.len(w);
     auto put_at = [&](uint32_t s, uint32_t v) {   // sample s of the frame
       const uint64_t g = fpos + s;
       if (g >= start && g - start < (uint64_t)L) x3w_store(out, fmt, rbase + (g - start), v);
@@ -479,9 +575,11 @@ __device__ __forceinline__ int32_t x3w_replay_frame(const uint8_t* __restrict__ 
 }
 
 // ---- fix-up: a wave per window, frames in order; scratch: a block's samples per window (x3_replay_block's output)
+// (Geo: the rows, as in x3_window_decode_kernel)
+template <class Geo>
 __global__ void __launch_bounds__(256)
 x3_window_fixup_kernel(const uint8_t* __restrict__ x3, const uint64_t* __restrict__ frame_off, const uint64_t* __restrict__ so,
-                       const uint64_t* __restrict__ starts, const X3WinPlan* __restrict__ plan, uint64_t n_windows, uint32_t L,
+                       const uint64_t* __restrict__ starts, const X3WinPlan* __restrict__ plan, uint64_t n_windows, Geo geo,
                        X3DevParams p, const int32_t* __restrict__ fst, void* __restrict__ out, int fmt,
                        int32_t* __restrict__ status, int16_t* __restrict__ scratch, uint32_t scratch_per,
                        X3WinSummary* __restrict__ sum) {
@@ -489,7 +587,8 @@ x3_window_fixup_kernel(const uint8_t* __restrict__ x3, const uint64_t* __restric
   const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
   for (uint64_t w = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); w < n_windows; w += waves) {
     const X3WinPlan pl = plan[w];
-    const uint64_t start = starts[w], rbase = w * (uint64_t)L;
+    const uint64_t start = starts[w], rbase = geo.base(w);
+    const auto L = geo.len(w);
     int32_t st = pl.status;
     uint64_t zero_from = 0;   // (st != 0) the row from here on is zero
     uint32_t replayed = 0;
@@ -515,8 +614,13 @@ x3_window_fixup_kernel(const uint8_t* __restrict__ x3, const uint64_t* __restric
     }
     st = __shfl(st, 0, X3_WAVE);
     zero_from = (uint64_t)__shfl((long long)zero_from, 0, X3_WAVE);
-    if (st != X3D_OK)
-      for (uint64_t t = zero_from + lane; t < L; t += 64u) x3w_store(out, fmt, rbase + t, 0u);
+    if constexpr (Geo::kTails) {   // a bad range's zeros and the tail behind every length, in one run
+      const uint64_t row_end = geo.row_end(w);
+      for (uint64_t t = (st != X3D_OK ? zero_from : (uint64_t)L) + lane; t < row_end; t += 64u) x3w_store(out, fmt, rbase + t, 0u);
+    } else {
+      if (st != X3D_OK)
+        for (uint64_t t = zero_from + lane; t < L; t += 64u) x3w_store(out, fmt, rbase + t, 0u);
+    }
     if (lane == 0) {
       if (replayed) atomicAdd(&sum->replays, (unsigned long long)replayed);
       status[w] = st;
@@ -541,37 +645,55 @@ x3_corpus_samples_kernel(const uint64_t* __restrict__ so, uint64_t F, x3_corpus_
 // plan: a thread per window (entry, start), grid-stride as x3_window_plan_kernel.  The entry's positions are consecutive in
 // the corpus's sample offsets, so its start s is the global position so[first_frame] + s; the covering frames are searched
 // inside the entry's frames as x3_window_plan_kernel searches a stream's.  gstart[w]: the position the later kernels read
-// where they read d_starts.
+// where they read d_starts.  ZeroLen: L == 0 (a range) covers nothing, as in x3w_plan_stream.
+template <bool ZeroLen>
+__device__ __forceinline__ X3WinPlan x3w_plan_entry(const x3_corpus_entry* __restrict__ ent, uint64_t n_ent,
+                                                    const uint64_t* __restrict__ so, uint64_t F, uint32_t e, uint64_t start,
+                                                    uint32_t L, uint64_t& g) {
+  X3WinPlan pl{0, 0, X3D_BAD_ARG};
+  g = 0;
+  if (e < n_ent) {
+    const x3_corpus_entry en = ent[e];
+    const uint64_t fa0 = en.first_frame, fb0 = en.first_frame + en.n_frames;
+    // (the table's words are checked, not trusted: the entry's frames inside the table, its positions inside so's range)
+    if (en.n_frames && fa0 < F && en.n_frames <= F - fa0 && L <= en.n_samples && start <= en.n_samples - L) {
+      const uint64_t base = so[fa0], total = so[fb0];
+      if (total >= base && total - base == en.n_samples) {
+        g = base + start;
+        if (ZeroLen && L == 0u) return X3WinPlan{0, 0, X3D_OK};
+        const uint64_t fa = x3w_search(so, fa0, fb0, g);
+        const uint64_t fb = x3w_search(so, fa, fb0, g + (L - 1u));
+        if (fb - fa < (uint64_t)L) pl = X3WinPlan{fa, (uint32_t)(fb - fa + 1u), X3D_OK};
+      }
+    }
+  }
+  return pl;
+}
+
 __global__ void __launch_bounds__(256)
 x3_corpus_plan_kernel(const x3_corpus_entry* __restrict__ ent, uint64_t n_ent, const uint64_t* __restrict__ so, uint64_t F,
                       const uint32_t* __restrict__ entries, const uint64_t* __restrict__ starts, uint64_t n_windows, uint32_t L,
                       X3WinPlan* __restrict__ plan, uint64_t* __restrict__ gstart, X3WinSummary* __restrict__ sum) {
   const uint64_t w0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (w0 == 0) {
-    sum->n_bad = 0;
-    sum->first = ~0ull;
-    sum->replays = 0;
-  }
+  if (w0 == 0) x3w_summary_init(sum);
   for (uint64_t w = w0; w < n_windows; w += (uint64_t)gridDim.x * blockDim.x) {
-    const uint32_t e = entries[w];
-    const uint64_t start = starts[w];
-    X3WinPlan pl{0, 0, X3D_BAD_ARG};
-    uint64_t g = 0;
-    if (e < n_ent) {
-      const x3_corpus_entry en = ent[e];
-      const uint64_t fa0 = en.first_frame, fb0 = en.first_frame + en.n_frames;
-      // (the table's words are checked, not trusted: the entry's frames inside the table, its positions inside so's range)
-      if (en.n_frames && fa0 < F && en.n_frames <= F - fa0 && L <= en.n_samples && start <= en.n_samples - L) {
-        const uint64_t base = so[fa0], total = so[fb0];
-        if (total >= base && total - base == en.n_samples) {
-          g = base + start;
-          const uint64_t fa = x3w_search(so, fa0, fb0, g);
-          const uint64_t fb = x3w_search(so, fa, fb0, g + (L - 1u));
-          if (fb - fa < (uint64_t)L) pl = X3WinPlan{fa, (uint32_t)(fb - fa + 1u), X3D_OK};
-        }
-      }
-    }
-    plan[w] = pl;
+    uint64_t g;
+    plan[w] = x3w_plan_entry<false>(ent, n_ent, so, F, entries[w], starts[w], L, g);
+    gstart[w] = g;
+  }
+}
+
+// the same with a length per range (x3_corpus_ranges_dev)
+__global__ void __launch_bounds__(256)
+x3_corpus_range_plan_kernel(const x3_corpus_entry* __restrict__ ent, uint64_t n_ent, const uint64_t* __restrict__ so, uint64_t F,
+                            const uint32_t* __restrict__ entries, const uint64_t* __restrict__ starts,
+                            const uint32_t* __restrict__ lens, uint64_t n_ranges, X3WinPlan* __restrict__ plan,
+                            uint64_t* __restrict__ gstart, X3WinSummary* __restrict__ sum) {
+  const uint64_t w0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (w0 == 0) x3w_summary_init(sum);
+  for (uint64_t w = w0; w < n_ranges; w += (uint64_t)gridDim.x * blockDim.x) {
+    uint64_t g;
+    plan[w] = x3w_plan_entry<true>(ent, n_ent, so, F, entries[w], starts[w], lens[w], g);
     gstart[w] = g;
   }
 }

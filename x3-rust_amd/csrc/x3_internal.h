@@ -179,6 +179,7 @@ struct x3_ctx {
   bool windows_pending = false;    // x3_decode_windows_dev: its own pending state (x3_decode_result is not touched)
   uint64_t win_windows = 0;        // ... its window count and where its summary lies in win_ws
   size_t win_sum_off = 0;
+  bool win_ranges = false;         // the pending call is x3_decode_ranges_dev / x3_corpus_ranges_dev (x3_decode_ranges_result's)
   bool levels_pending = false;     // x3_levels_dev / x3_corpus_levels_dev: a pending state of their own, as the windows'
   uint64_t lev_frames = 0;         // ... their frame count and where their summary lies in lev_ws
   size_t lev_sum_off = 0;

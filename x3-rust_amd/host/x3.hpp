@@ -744,6 +744,30 @@ inline X3Error decode_windows(Context& ctx, const EncodedStream& s, const Parame
   return static_cast<X3Error>(rc);
 }
 
+// Ranges (x3_decode_ranges_dev): windows with a length each, range w = positions [d_starts[w], d_starts[w] + d_lens[w]).
+// row_stride 0: rows packed at the exclusive sum of all lengths, written to d_out_offsets (n_ranges + 1 words, required); a
+// range without room in out_cap samples is BadArg and not written.  row_stride > 0: row w at w * row_stride with zeros
+// behind its length (d_out_offsets may be nullptr).  Row and status of a range are the single window's of that length.
+// Waits for the call: res = ranges with status != 0, the first, its status, and the sum of all lengths.
+struct RangesResult : WindowsResult {
+  uint64_t total_samples = 0;
+};
+inline X3Error decode_ranges(Context& ctx, const EncodedStream& s, const Parameters& params, const Buffer& d_sample_offsets,
+                             const uint64_t* d_starts, const uint32_t* d_lens, size_t n_ranges, uint64_t row_stride, void* d_out,
+                             uint64_t out_cap, int out_format, uint64_t* d_out_offsets, int32_t* d_status, RangesResult* res) {
+  if (!s.bytes.ok() || !s.frame_offsets.ok() || !d_sample_offsets.ok()) return X3Error::BadArg;
+  const x3_params c = params.c_params();
+  int rc = x3_decode_ranges_dev(ctx.raw(), s.bytes.as<uint8_t>(), s.len, s.frame_offsets.as<uint64_t>(),
+                                d_sample_offsets.as<uint64_t>(), s.n_frames, &c,
+                                s.seg_blocks ? s.seg_index.as<uint64_t>() : nullptr, s.seg_blocks, d_starts, d_lens, n_ranges,
+                                row_stride, d_out, out_cap, out_format, d_out_offsets, d_status);
+  if (rc != X3_OK) return static_cast<X3Error>(rc);
+  RangesResult r;
+  rc = x3_decode_ranges_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status, &r.total_samples);
+  if (res) *res = r;
+  return static_cast<X3Error>(rc);
+}
+
 // Levels (x3_levels_dev): min, max, count, sum and sum of squares of the samples per bin of bin_len positions (0: one bin),
 // n_bins records in d_levels, every one written; d_frame_status (n_frames int32, may be nullptr): a frame with a status
 // other than 0 adds nothing.  No sample buffer.  Waits for the call: res = frames with status != 0, the first, its status.
@@ -827,6 +851,19 @@ class Corpus {
     if (rc != X3_OK) return static_cast<X3Error>(rc);
     WindowsResult r;
     rc = x3_decode_windows_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status);
+    if (res) *res = r;
+    return static_cast<X3Error>(rc);
+  }
+  // Ranges of entries (x3_corpus_ranges_dev): range w = samples [d_starts[w], d_starts[w] + d_lens[w]) of entry d_entries[w];
+  // layout, capacity and result as device::decode_ranges.  Waits for the call.
+  X3Error ranges(Context& ctx, const uint32_t* d_entries, const uint64_t* d_starts, const uint32_t* d_lens, uint64_t n_ranges,
+                 uint64_t row_stride, void* d_out, uint64_t out_cap, int out_format, uint64_t* d_out_offsets, int32_t* d_status,
+                 RangesResult* res) const {
+    int rc = x3_corpus_ranges_dev(ctx.raw(), raw_, d_entries, d_starts, d_lens, n_ranges, row_stride, d_out, out_cap, out_format,
+                                  d_out_offsets, d_status);
+    if (rc != X3_OK) return static_cast<X3Error>(rc);
+    RangesResult r;
+    rc = x3_decode_ranges_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status, &r.total_samples);
     if (res) *res = r;
     return static_cast<X3Error>(rc);
   }

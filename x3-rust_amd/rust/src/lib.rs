@@ -160,6 +160,13 @@ pub mod ffi {
                                      seg_blocks: u32, d_starts: *const u64, n_windows: u64, window_len: u32, d_out: *mut c_void,
                                      out_format: c_int, d_status: *mut i32) -> c_int;
         pub fn x3_decode_windows_result(ctx: *mut x3_ctx, n_bad: *mut u64, first_bad: *mut u64, first_bad_status: *mut c_int) -> c_int;
+        pub fn x3_decode_ranges_dev(ctx: *mut x3_ctx, d_x3: *const u8, x3_len: u64, d_frame_offsets: *const u64,
+                                    d_sample_offsets: *const u64, n_frames: u64, p: *const x3_params, d_seg_index: *const u64,
+                                    seg_blocks: u32, d_starts: *const u64, d_lens: *const u32, n_ranges: u64, row_stride: u64,
+                                    d_out: *mut c_void, out_cap: u64, out_format: c_int, d_out_offsets: *mut u64,
+                                    d_status: *mut i32) -> c_int;
+        pub fn x3_decode_ranges_result(ctx: *mut x3_ctx, n_bad: *mut u64, first_bad: *mut u64, first_bad_status: *mut c_int,
+                                       total_samples: *mut u64) -> c_int;
         pub fn x3_decode_streams_dev(ctx: *mut x3_ctx, d_x3: *const u8, x3_len: u64, offsets: *const u64, lengths: *const u64,
                                      n_streams: u64, flags: u32, p: *const x3_params, d_out: *mut c_void, row_len: u64,
                                      out_format: c_int, d_results: *mut x3_stream_result) -> c_int;
@@ -172,6 +179,9 @@ pub mod ffi {
         pub fn x3_corpus_seg_index(corpus: *const x3_corpus, d_seg_index: *mut *const u64, n_words: *mut u64) -> c_int;
         pub fn x3_corpus_windows_dev(ctx: *mut x3_ctx, corpus: *const x3_corpus, d_entries: *const u32, d_starts: *const u64,
                                      n_windows: u64, window_len: u32, d_out: *mut c_void, out_format: c_int, d_status: *mut i32) -> c_int;
+        pub fn x3_corpus_ranges_dev(ctx: *mut x3_ctx, corpus: *const x3_corpus, d_entries: *const u32, d_starts: *const u64,
+                                    d_lens: *const u32, n_ranges: u64, row_stride: u64, d_out: *mut c_void, out_cap: u64,
+                                    out_format: c_int, d_out_offsets: *mut u64, d_status: *mut i32) -> c_int;
         pub fn x3_levels_dev(ctx: *mut x3_ctx, d_x3: *const u8, x3_len: u64, d_frame_offsets: *const u64,
                              d_sample_offsets: *const u64, n_frames: u64, p: *const x3_params, d_seg_index: *const u64,
                              seg_blocks: u32, bin_len: u64, d_levels: *mut x3_level, n_bins: u64, d_frame_status: *mut i32) -> c_int;
@@ -1275,6 +1285,35 @@ pub mod device {
         Ok((n_bad, first_bad, st))
     }
 
+    /// Ranges (`x3_decode_ranges_dev`): windows with a length each, range w = positions `[starts[w], starts[w] + lens[w])`
+    /// (`d_starts`: device u64s, `d_lens`: device u32s).  `row_stride` 0: rows packed at the exclusive sum of all lengths, which
+    /// `d_out_offsets` (`n_ranges + 1` u64s, required) receives; a range without room in `out_cap` samples is `BadArg` and not
+    /// written.  `row_stride` > 0: row w at `w * row_stride`, zeros behind its length.  Waits: -> (ranges with status != 0, the
+    /// first of them, its status, the sum of all lengths)
+    #[allow(clippy::too_many_arguments)]
+    pub fn decode_ranges<'g>(gpu: &'g Gpu, s: &EncodedStream<'g>, params: &x3::Parameters, sample_offsets: &Buffer<'g>,
+                             d_starts: &Buffer<'g>, d_lens: &Buffer<'g>, n_ranges: usize, row_stride: u64, d_out: &mut Buffer<'g>,
+                             out_cap: u64, out_format: i32, d_out_offsets: Option<&mut Buffer<'g>>, d_status: &mut Buffer<'g>)
+                             -> error::Result<(u64, u64, i32, u64)> {
+        let esz = if out_format == WINDOW_F32 { 4 } else { 2 };
+        if d_starts.len() < 8 * n_ranges || d_lens.len() < 4 * n_ranges || (d_out.len() as u64) < esz * out_cap
+            || d_status.len() < 4 * n_ranges || d_out_offsets.as_ref().map_or(false, |b| b.len() < 8 * (n_ranges + 1)) {
+            return Err(X3Error::BadArg);
+        }
+        let p = params.c()?;
+        let idx = match &s.seg_index { Some(i) => i.as_ptr::<u64>() as *const u64, None => core::ptr::null() };
+        let off = d_out_offsets.map_or(core::ptr::null_mut(), |b| b.as_ptr::<u64>());
+        error::check(unsafe {
+            ffi::x3_decode_ranges_dev(gpu.raw(), s.bytes.as_ptr::<u8>(), s.len as u64, s.frame_offsets.as_ptr::<u64>(),
+                                      sample_offsets.as_ptr::<u64>(), s.n_frames as u64, &p, idx, s.seg_blocks,
+                                      d_starts.as_ptr::<u64>(), d_lens.as_ptr::<u32>(), n_ranges as u64, row_stride,
+                                      d_out.as_ptr::<c_void>(), out_cap, out_format, off, d_status.as_ptr::<i32>())
+        })?;
+        let (mut n_bad, mut first_bad, mut st, mut total) = (0u64, 0u64, 0, 0u64);
+        error::check(unsafe { ffi::x3_decode_ranges_result(gpu.raw(), &mut n_bad, &mut first_bad, &mut st, &mut total) })?;
+        Ok((n_bad, first_bad, st, total))
+    }
+
     /// One bin of `levels` / `Corpus::levels` (`x3_level`): `sum_sq`, `sum`, `min`, `max`, `n`; an empty bin holds the identities
     /// (`min` 32767, `max` -32768, `n` 0)
     pub type Level = ffi::x3_level;
@@ -1397,6 +1436,28 @@ pub mod device {
             let (mut n_bad, mut first_bad, mut st) = (0u64, 0u64, 0);
             error::check(unsafe { ffi::x3_decode_windows_result(self.gpu.raw(), &mut n_bad, &mut first_bad, &mut st) })?;
             Ok((n_bad, first_bad, st))
+        }
+
+        /// Ranges of entries (`x3_corpus_ranges_dev`): range w = samples `[starts[w], starts[w] + lens[w])` of entry
+        /// `entries[w]`; layout, capacity and result as `decode_ranges`
+        #[allow(clippy::too_many_arguments)]
+        pub fn ranges(&self, d_entries: &Buffer<'g>, d_starts: &Buffer<'g>, d_lens: &Buffer<'g>, n: usize, row_stride: u64,
+                      d_out: &mut Buffer<'g>, out_cap: u64, out_format: i32, d_out_offsets: Option<&mut Buffer<'g>>,
+                      d_status: &mut Buffer<'g>) -> error::Result<(u64, u64, i32, u64)> {
+            let esz = if out_format == WINDOW_F32 { 4 } else { 2 };
+            if d_entries.len() < 4 * n || d_starts.len() < 8 * n || d_lens.len() < 4 * n || (d_out.len() as u64) < esz * out_cap
+                || d_status.len() < 4 * n || d_out_offsets.as_ref().map_or(false, |b| b.len() < 8 * (n + 1)) {
+                return Err(X3Error::BadArg);
+            }
+            let off = d_out_offsets.map_or(core::ptr::null_mut(), |b| b.as_ptr::<u64>());
+            error::check(unsafe {
+                ffi::x3_corpus_ranges_dev(self.gpu.raw(), self.raw, d_entries.as_ptr::<u32>(), d_starts.as_ptr::<u64>(),
+                                          d_lens.as_ptr::<u32>(), n as u64, row_stride, d_out.as_ptr::<c_void>(), out_cap,
+                                          out_format, off, d_status.as_ptr::<i32>())
+            })?;
+            let (mut n_bad, mut first_bad, mut st, mut total) = (0u64, 0u64, 0, 0u64);
+            error::check(unsafe { ffi::x3_decode_ranges_result(self.gpu.raw(), &mut n_bad, &mut first_bad, &mut st, &mut total) })?;
+            Ok((n_bad, first_bad, st, total))
         }
     }
 

@@ -57,6 +57,7 @@ SYMBOLS = [
     "x3_mgpu_encode", "x3_mgpu_decode_stream",
     "x3_encode_mc", "x3_decode_stream_mc",
     "x3_sample_offsets_dev", "x3_decode_windows_dev", "x3_decode_windows_result",
+    "x3_decode_ranges_dev", "x3_corpus_ranges_dev", "x3_decode_ranges_result",
     "x3_decode_streams_dev", "x3_decode_streams_result",
     "x3_corpus_build", "x3_corpus_info", "x3_corpus_entries", "x3_corpus_seg_index", "x3_corpus_windows_dev",
     "x3_corpus_destroy",
@@ -222,6 +223,9 @@ def lib():
     L.x3_sample_offsets_dev.argtypes = [vp, vp, u64, vp, u64, vp]
     L.x3_decode_windows_dev.argtypes = [vp, vp, u64, vp, vp, u64, PP, vp, u32, vp, u64, u32, vp, i32, vp]
     L.x3_decode_windows_result.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(i32)]
+    L.x3_decode_ranges_dev.argtypes = [vp, vp, u64, vp, vp, u64, PP, vp, u32, vp, vp, u64, u64, vp, u64, i32, vp, vp]
+    L.x3_corpus_ranges_dev.argtypes = [vp, vp, vp, vp, vp, u64, u64, vp, u64, i32, vp, vp]
+    L.x3_decode_ranges_result.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(i32), C.POINTER(u64)]
     L.x3_decode_streams_dev.argtypes = [vp, vp, u64, vp, vp, u64, u32, PP, vp, u64, i32, vp]
     L.x3_decode_streams_result.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(i32)]
     L.x3_corpus_build.argtypes = [vp, vp, u64, vp, vp, u64, u32, PP, u32, C.POINTER(vp)]
@@ -934,6 +938,20 @@ class Context:
         rc = lib().x3_decode_windows_result(self._h, C.byref(nb), C.byref(fb), C.byref(st))
         return rc, nb.value, fb.value, st.value
 
+    def decode_ranges_dev(self, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, params, d_starts, d_lens, n_ranges,
+                          row_stride, d_out, out_cap, out_format, d_out_offsets, d_status, d_seg_index=None, seg_blocks=0):
+        """x3_decode_ranges_dev: range w = [d_starts[w], d_starts[w] + d_lens[w]), rows packed (row_stride 0) or padded;
+        asynchronous"""
+        return lib().x3_decode_ranges_dev(self._h, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames,
+                                          C.byref(params), d_seg_index, seg_blocks, d_starts, d_lens, n_ranges, row_stride,
+                                          d_out, out_cap, out_format, d_out_offsets, d_status)
+
+    def decode_ranges_result(self):
+        """-> (rc, n_bad, first_bad, first_bad_status, total_samples) of the last decode_ranges_dev / Corpus.ranges_into"""
+        nb, fb, st, tot = C.c_uint64(0), C.c_uint64(0), C.c_int(0), C.c_uint64(0)
+        rc = lib().x3_decode_ranges_result(self._h, C.byref(nb), C.byref(fb), C.byref(st), C.byref(tot))
+        return rc, nb.value, fb.value, st.value, tot.value
+
     def levels_dev(self, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, params, bin_len, d_levels, n_bins,
                    d_frame_status=None, d_seg_index=None, seg_blocks=0):
         """x3_levels_dev: n_bins x3_level records (LEVEL_DTYPE) of bins of bin_len positions (0: one bin); asynchronous"""
@@ -1026,6 +1044,55 @@ class Context:
         if rc:
             raise X3Error(rc, "x3_dev_download: " + self.last_error())
         return out
+
+
+def _ranges_torch(ctx, enqueue, what, starts, lens, padded_to, capacity, dtype, entries=None):
+    """The torch side of WindowSource.ranges / Corpus.ranges: device tensors in, (out, offsets, status) device tensors out.
+    enqueue(d_entries, d_starts, d_lens, n, stride, d_out, cap, fmt, d_off, d_status) -> rc."""
+    import torch
+    if dtype not in (torch.int16, torch.float32):
+        raise ValueError("dtype: torch.int16 or torch.float32")
+    dev = torch.device("cuda", torch.cuda.current_device())
+
+    def on_dev(a, dt):   # (unsigned words travel as the signed tensors of the same bits: torch's unsigned types do little)
+        signed = {np.uint64: torch.int64, np.uint32: torch.int32}[dt]
+        if not isinstance(a, torch.Tensor):
+            a = torch.from_numpy(np.ascontiguousarray(a, dtype=dt).view(np.int64 if dt is np.uint64 else np.int32))
+        elif a.dtype.itemsize == signed.itemsize and not a.dtype.is_floating_point:
+            a = a.view(signed)
+        else:
+            a = a.to(signed)
+        return a.to(dev).contiguous()
+    starts, lens = on_dev(starts, np.uint64), on_dev(lens, np.uint32)
+    n = starts.numel()
+    if starts.dim() != 1 or lens.shape != starts.shape or n == 0:
+        raise ValueError("starts and lens: 1-D, non-empty, of one length")
+    d_ent = None
+    if entries is not None:
+        entries = on_dev(entries, np.uint32)
+        if entries.shape != starts.shape:
+            raise ValueError("entries: as many as starts")
+        d_ent = entries.data_ptr()
+    if padded_to is not None:
+        if padded_to <= 0:
+            raise ValueError("padded_to: a positive row stride")
+        stride, cap = int(padded_to), n * int(padded_to)
+        out = torch.empty((n, stride), dtype=dtype, device=dev)
+    else:
+        stride = 0
+        cap = int(capacity) if capacity is not None else int((lens.to(torch.int64) & 0xFFFFFFFF).sum().item())   # (the one host trip)
+        out = torch.empty(max(cap, 1), dtype=dtype, device=dev)
+    offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)   # (below 2^63: n < 2^31 lengths of 32 bits)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    torch.cuda.current_stream().synchronize()    # (the context's stream is not torch's: the inputs are ready from here)
+    rc = enqueue(d_ent, starts.data_ptr(), lens.data_ptr(), n, stride, out.data_ptr(), cap,
+                 WINDOW_F32 if dtype == torch.float32 else WINDOW_I16, offsets.data_ptr(), status.data_ptr())
+    if rc:
+        raise X3Error(rc, what + ": " + ctx.last_error())
+    rc = ctx.decode_ranges_result()[0]
+    if rc:
+        raise X3Error(rc, "x3_decode_ranges_result: " + ctx.last_error())
+    return out[:cap] if padded_to is None else out, offsets, status
 
 
 class WindowSource:
@@ -1127,6 +1194,24 @@ class WindowSource:
         finally:
             for p in (d_starts, d_out, d_st):
                 self.ctx.free(p)
+
+    def ranges_into(self, d_starts, d_lens, n, row_stride, d_out, out_cap, fmt, d_out_offsets, d_status):
+        """enqueue n ranges (device pointers: d_starts n x u64, d_lens n x u32, d_out out_cap samples, d_out_offsets
+        (n + 1) x u64 or None when padded, d_status n x i32); row_stride 0: packed; -> rc; decode_ranges_result waits"""
+        return self.ctx.decode_ranges_dev(self.d_x3, self.x3_len, self.d_frame_offsets, self.d_sample_offsets, self.n_frames,
+                                          self.params, d_starts, d_lens, n, row_stride, d_out, out_cap, fmt, d_out_offsets,
+                                          d_status, self.d_seg_index, self.seg_blocks)
+
+    def ranges(self, starts, lens, *, padded_to=None, capacity=None, dtype=None):
+        """Variable-length windows [starts[w], starts[w] + lens[w]) -> (out, offsets, status), torch tensors on the device.
+        starts / lens: torch tensors (device data stays on the device) or array-likes.  Packed (default): out is 1-D, range
+        w at out[offsets[w]:offsets[w + 1]]; it holds `capacity` samples when given -- ranges without room are
+        ERR_BAD_ARG, offsets[-1] tells what is needed -- and otherwise the sum of the lengths, which costs ONE
+        synchronising sum on the host.  padded_to=S: out is [n, S], zeros behind each length, no host trip for sizes.
+        dtype: torch.int16 (default) or torch.float32.  The call waits for its result (x3_decode_ranges_result)."""
+        import torch
+        return _ranges_torch(self.ctx, lambda e, *a: self.ranges_into(*a), "x3_decode_ranges_dev", starts, lens, padded_to,
+                             capacity, dtype or torch.int16)
 
     def levels(self, bin_len, n_bins=None):
         """-> (records np.ndarray of LEVEL_DTYPE [n_bins], frame statuses np.int32 [n_frames]): min, max, n, sum and sum of
@@ -1357,6 +1442,23 @@ class Corpus:
         finally:
             for ptr in (d_ent, d_starts, d_out, d_st):
                 self.ctx.free(ptr)
+
+    def ranges_into(self, d_entries, d_starts, d_lens, n, row_stride, d_out, out_cap, fmt, d_out_offsets, d_status):
+        """enqueue n ranges (device pointers: d_entries n x u32, d_starts n x u64, d_lens n x u32, d_out out_cap samples,
+        d_out_offsets (n + 1) x u64 or None when padded, d_status n x i32); row_stride 0: packed; -> rc;
+        Context.decode_ranges_result waits"""
+        if self._h is None:
+            raise ValueError("the corpus is closed")
+        return lib().x3_corpus_ranges_dev(self.ctx._h, self._h, d_entries, d_starts, d_lens, n, row_stride, d_out, out_cap,
+                                          fmt, d_out_offsets, d_status)
+
+    def ranges(self, entries, starts, lens, *, padded_to=None, capacity=None, dtype=None):
+        """Variable-length windows [starts[w], starts[w] + lens[w]) of entry entries[w] -> (out, offsets, status), torch
+        tensors on the device; layout, capacity (default: one synchronising sum of the lengths), padded_to and dtype as
+        WindowSource.ranges."""
+        import torch
+        return _ranges_torch(self.ctx, self.ranges_into, "x3_corpus_ranges_dev", starts, lens, padded_to, capacity,
+                             dtype or torch.int16, entries=entries)
 
     def levels_rows(self, bin_len):
         """-> row_first np.uint64 [n_entries + 1]: entry e's rows of levels() are [row_first[e], row_first[e + 1])"""
