@@ -585,10 +585,12 @@ def test_state_argument_errors_and_a_pending_decode(ctx, x3):
         ctx.upload(d_fo, fo)
         assert ctx.decode_dev(corpus.d_x3, s.size, d_fo, fo.size, x3.Params.default(), d_wav, 30_000, n_per_clip=30_000) == 0
         assert call() == 0
+        assert ctx.decode_ranges_result()[0] == BAD        # (the pending call is a windows call, and stays pending)
         assert ctx.decode_windows_result()[0] == 0
         rc, first_bad, _, _ = ctx.decode_result()
         assert (rc, first_bad) == (0, fo.size)
         assert np.array_equal(ctx.download(d_wav, 60_000, np.int16), wav)
+        assert call(n=2) == 0 and ctx.decode_windows_result() == (0, 0, 2, 0)      # none bad: the count, status 0
         # build refusals
         p = x3.Params.default()
         offs = np.array([0], dtype=np.uint64)

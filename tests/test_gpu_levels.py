@@ -440,6 +440,27 @@ def test_arguments_and_pending_states(ctx, x3):
         # the corpus call: a wrong device is covered by the C ABI's check; NULL handles
         assert L.x3_corpus_levels_dev(ctx._h, None, 0, d_lv, 1, None) == BAD
         assert L.x3_corpus_levels_rows(None, 0, None) == BAD
+        # ... a recording context is refused, and a call with no bad frame reports the frame count and status 0
+        corpus = x3.Corpus(ctx, (dev.d_x3, dev.len), [0], [dev.len], params=dev.p, seg_blocks=32, index="walk")
+        try:
+            n_rows = int(corpus.levels_rows(4_000)[-1])
+            assert n_rows == 6 and corpus.n_frames == dev.F
+            ctx.upload(d_lv, poison)
+            ctx.graph_begin()
+            try:
+                assert ctx.corpus_levels_dev(corpus, 4_000, d_lv, n_rows) == BAD
+            finally:
+                try:
+                    ctx.graph_destroy(ctx.graph_end())
+                except x3.X3Error:
+                    pass
+            assert ctx.levels_result()[0] == BAD
+            assert np.array_equal(ctx.download(d_lv, 32 * 8, np.uint8), poison)
+            assert ctx.corpus_levels_dev(corpus, 4_000, d_lv, n_rows) == 0
+            assert ctx.levels_result() == (0, 0, dev.F, 0)
+            _same(ctx.download(d_lv, 32 * n_rows, R.LEVEL_DTYPE), want[:n_rows], "corpus, one entry")
+        finally:
+            corpus.close()
     finally:
         dev.close()
 

@@ -437,6 +437,7 @@ def test_argument_refusals_enqueue_nothing(ctx, x3):
     assert (ctx.download(d["off"], sizes["off"]) == 0x5A).all()
     assert np.array_equal(ctx.download(d["out"], 128, np.int16), np.tile(base_wav(x3)[:16], 4))
     assert corpus.ranges_into(**cok) == 0                                # (what the corpus refusals were cut from is a good call)
+    assert ctx.decode_windows_result()[0] == BAD                         # (the corpus form's pending call is a ranges call too)
     assert ctx.decode_ranges_result() == (0, 0, n, 0, 64)
     corpus.close()
     dev.close()

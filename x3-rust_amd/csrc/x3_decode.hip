@@ -27,6 +27,12 @@ static int derive_params(const x3_params* p, X3DevParams* d) {
 static uint64_t seg_stretches(uint64_t blocks_per_frame, uint32_t seg_blocks) {
   return (blocks_per_frame + seg_blocks - 1) / seg_blocks;
 }
+// ... as a launch takes them: 1 where the index has no entries (x3_seg_index_entries() == 0: frames of one stretch, or
+// seg_blocks 0, no index) -- whole frames
+static uint32_t seg_index_nseg(uint64_t blocks_per_frame, uint32_t seg_blocks) {
+  const uint64_t nidx = seg_blocks ? seg_stretches(blocks_per_frame, seg_blocks) : 1;
+  return nidx >= 2 ? (uint32_t)nidx : 1u;
+}
 
 // The parameters as the decoders take them: block length 0 travels as 1 (frames that need it are BAD_ARG frames of the walk)
 static x3_params decoder_params(const x3_params* p) {
@@ -190,7 +196,7 @@ int decode_dev_impl(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint6
       X3SegArgs sg{nullptr, nullptr, 0u, 1u, 0u, 1u};
       uint64_t groups = (F + 63) / 64;
       if (by_seg) {
-        const uint64_t nidx = seg_stretches((dp.spf + X3S_BL - 1) / X3S_BL, seg->seg_blocks);
+        const uint64_t nidx = seg_index_nseg((dp.spf + X3S_BL - 1) / X3S_BL, seg->seg_blocks);
         if (nidx >= 2) {
           sg.pitch = (uint32_t)(nidx - 1);
           if (seg->mode == 1) {
@@ -1042,6 +1048,73 @@ extern "C" int x3_sample_offsets_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3
   return X3_OK;
 }
 
+// ---- what the access calls share on the host (windows, ranges, levels; a stream's and a corpus's): the frames they read,
+// the carver of their workspaces, the grids, the read-back of a result
+// the pieces of one block, each a multiple of 256 bytes behind its base
+struct BlockCarver {
+  char* base; size_t at;
+  template <class T> T* take(uint64_t count, size_t round = 256) {   // (round 1: the next piece follows directly)
+    T* const piece = reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(base) + at);
+    at = (at + count * sizeof(T) + round - 1) & ~(round - 1);
+    return piece;
+  }
+};
+
+// workgroups of a grid-stride kernel: one per `per_group` units, at most X3W_GRID_LIMIT (the counts are on the device)
+static unsigned grid_for(uint64_t units, uint64_t per_group) {
+  return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((units + per_group - 1) / per_group, X3W_GRID_LIMIT));
+}
+
+// The frames a call reads: the stream, its frame and sample offsets, the parameters, and the segment index as the kernels
+// take it -- idx NULL and nseg 1 where there is no usable one (none given, or frames of one stretch).  max_frames: the most
+// frames one window or range can cover, the stream's or the longest entry's.
+struct FrameSource {
+  const uint8_t* d_x3; uint64_t x3_len;
+  const uint64_t* d_frame_offsets; const uint64_t* d_sample_offsets; uint64_t F;
+  X3DevParams dp; uint64_t spf;
+  const uint2* idx; uint32_t seg_blocks, nseg;
+  uint64_t max_frames;
+  void index(const uint64_t* d_seg_index, uint32_t sb) {
+    seg_blocks = sb;
+    nseg = d_seg_index ? seg_index_nseg(dp.blocks_per_frame, sb) : 1u;
+    idx = nseg >= 2 ? reinterpret_cast<const uint2*>(d_seg_index) : nullptr;
+  }
+};
+
+// ... of a caller's stream: the checks every stream entry point makes on its frame table, index and parameters
+static int stream_source(const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets, const uint64_t* d_sample_offsets,
+                         uint64_t n_frames, const x3_params* p, const uint64_t* d_seg_index, uint32_t seg_blocks, FrameSource* s) {
+  if (!d_x3 || !d_frame_offsets || !d_sample_offsets || !p) return X3_ERR_BAD_ARG;
+  if (!frame_table_args_ok(d_x3, d_frame_offsets, n_frames) || (reinterpret_cast<uintptr_t>(d_sample_offsets) & 7u))
+    return X3_ERR_BAD_ARG;
+  if (d_seg_index && !seg_index_args_ok(d_seg_index, seg_blocks)) return X3_ERR_BAD_ARG;
+  s->d_x3 = d_x3, s->x3_len = x3_len;
+  s->d_frame_offsets = d_frame_offsets, s->d_sample_offsets = d_sample_offsets, s->F = s->max_frames = n_frames;
+  s->spf = spf_of(p);
+  const int rc = derive_block_params(p, &s->dp);
+  if (rc == X3_OK) s->index(d_seg_index, seg_blocks);
+  return rc;
+}
+
+// The read-back of a pending call: its summary (`bytes` of it, in `ws`) to h and the wait for it; the slot is free again
+static int pending_fetch(x3_ctx* c, x3_ctx::PendingCall& call, const DevBuf& ws, void* h, size_t bytes) {
+  if (!call.pending) return X3_ERR_BAD_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(h, (char*)ws.p + call.sum_off, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  call.pending = false;
+  return X3_OK;
+}
+
+// a summary's (n_bad, first = min(unit << 8 | status) over the bad units) as the result calls give them; none bad: the
+// count of units and status 0
+static void first_bad_of(uint64_t bad, uint64_t first, uint64_t count, uint64_t* n_bad, uint64_t* first_bad,
+                         int* first_bad_status) {
+  if (n_bad) *n_bad = bad;
+  if (first_bad) *first_bad = bad ? (first >> 8) : count;
+  if (first_bad_status) *first_bad_status = bad ? (int)(first & 0xFFu) : 0;
+}
+
 // the argument checks x3_decode_windows_dev and x3_corpus_windows_dev share
 static bool windows_args_ok(uint64_t n_windows, uint32_t window_len, const void* d_out, int out_format, const uint64_t* d_starts,
                             const int32_t* d_status) {
@@ -1058,81 +1131,78 @@ struct RangeRows {
   const uint32_t* d_lens;
   uint64_t row_stride, out_cap;
   uint64_t* d_out_offsets;
-  uint64_t max_frames;   // the most frames a range can cover: the stream's, or the longest entry's
 };
+
+// The workspace (WinWs, x3_internal.h): plans, the two scans, per-frame verdicts, a block of replay scratch per window, the
+// summary, the plan's starts; ranges: the scan of the lengths and the lengths that have room
+uint32_t windows_scratch_per(uint32_t block_len) { return (block_len + 7u) & ~7u; }
+
+size_t windows_carve(char* base, uint64_t n, uint64_t F, uint32_t scratch_per, bool ranges, WinWs* w) {
+  BlockCarver k{base, 0};
+  w->plan = k.take<X3WinPlan>(n);
+  w->cov_off = k.take<unsigned long long>(n + 1);
+  w->item_off = k.take<unsigned long long>(n + 1);
+  w->fst = k.take<int32_t>(F);
+  w->scratch = k.take<int16_t>(n * scratch_per);
+  w->sum = k.take<X3WinSummary>(1);
+  w->gstart = k.take<uint64_t>(n, ranges ? 256 : 1);   // (a windows call's block ends here)
+  w->off = ranges ? k.take<unsigned long long>(n + 1) : nullptr;
+  w->elen = ranges ? k.take<uint32_t>(n, 1) : nullptr;
+  return k.at;
+}
 
 // The launch set of a windows or ranges call (x3_decode_window_kernel.h) behind its plan step: plan(grid, plan, gstart, sum)
 // enqueues the plan kernel and returns the starts the decode and fix-up kernels read (the caller's, or the plan's gstart).
 // rows: the geometry of a ranges call (the scan, decode and fix-up kernels are then the range siblings), NULL for windows of
 // window_len; len_hint sizes the grids (the window length, or what a range can have on average).
 template <class Plan>
-static int windows_launch(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
-                          const uint64_t* d_sample_offsets, uint64_t n_frames, const X3DevParams& dp, uint64_t spf,
-                          const uint64_t* d_seg_index, uint32_t seg_blocks, uint64_t n_windows, uint32_t window_len,
-                          const RangeRows* rows, void* d_out, int out_format, int32_t* d_status, Plan plan_step) {
-  // the stretches of a frame as the index tells them apart (x3_seg_index_entries); 1 = whole frames
-  const uint64_t nidx = d_seg_index ? seg_stretches(dp.blocks_per_frame, seg_blocks) : 1;
-  const uint32_t nseg = nidx >= 2 ? (uint32_t)nidx : 1u;
-  const uint2* idx = nseg >= 2 ? reinterpret_cast<const uint2*>(d_seg_index) : nullptr;
-  // workspace: plans, the two scans, per-frame verdicts, a block of replay scratch per window, the summary, the plan's starts;
-  // ranges: the scan of the lengths and the lengths that have room
-  const uint64_t n = n_windows, nr = rows ? n : 0;
-  const uint32_t scratch_per = (dp.block_len + 7u) & ~7u;
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t o_plan = 0, o_cov = up(o_plan + n * sizeof(X3WinPlan)), o_item = up(o_cov + (n + 1) * 8),
-               o_fst = up(o_item + (n + 1) * 8), o_scr = up(o_fst + n_frames * 4), o_sum = up(o_scr + n * scratch_per * 2),
-               o_gs = up(o_sum + sizeof(X3WinSummary)), end_gs = o_gs + n * 8, o_off = up(end_gs), o_elen = up(o_off + (nr + 1) * 8),
-               total = rows ? o_elen + nr * 4 : end_gs;
+static int windows_launch(x3_ctx* c, const FrameSource& s, uint64_t n, uint32_t window_len, const RangeRows* rows, void* d_out,
+                          int out_format, int32_t* d_status, Plan plan_step) {
+  HIPCHK(c, hipSetDevice(c->device));
+  const uint32_t scratch_per = windows_scratch_per(s.dp.block_len);
+  WinWs w;
   int rc;
-  if ((rc = ensure(c, c->win_ws, total))) return rc;
-  char* const ws = (char*)c->win_ws.p;
-  X3WinPlan* plan = (X3WinPlan*)(ws + o_plan);
-  unsigned long long* cov_off = (unsigned long long*)(ws + o_cov);
-  unsigned long long* item_off = (unsigned long long*)(ws + o_item);
-  int32_t* fst = (int32_t*)(ws + o_fst);
-  int16_t* scratch = (int16_t*)(ws + o_scr);
-  X3WinSummary* sum = (X3WinSummary*)(ws + o_sum);
+  if ((rc = ensure(c, c->win_ws, windows_carve(nullptr, n, s.F, scratch_per, rows != nullptr, &w)))) return rc;
+  windows_carve((char*)c->win_ws.p, n, s.F, scratch_per, rows != nullptr, &w);
   // grids: the plan covers the windows; the grid-stride kernels take as many groups as the work of full-length frames needs,
   // at most X3W_GRID_LIMIT (their counts are on the device).  Ranges: the lengths are device data; what fits the rows is
   // out_cap / n (packed) or the stride on average, and ranges without room cover nothing.  Both are the caller's words and
   // may be far above what is drawn: a length has 32 bits and a range covers no more frames than the stream (or the longest
   // entry) has, so a roomy buffer does not size the grids.
   const uint64_t len_hint = !rows ? window_len : std::min<uint64_t>(rows->row_stride ? rows->row_stride : rows->out_cap / n, 0xFFFFFFFFull);
-  uint64_t frames_per = len_hint / (spf ? spf : 1) + 2;
-  if (rows) frames_per = std::max<uint64_t>(1, std::min(frames_per, rows->max_frames));
-  auto groups = [&](uint64_t units, uint64_t per_group) {
-    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((units + per_group - 1) / per_group, X3W_GRID_LIMIT));
-  };
-  const uint64_t* d_starts = plan_step(dim3(groups(n, 256)), plan, (uint64_t*)(ws + o_gs), sum);
+  uint64_t frames_per = len_hint / (s.spf ? s.spf : 1) + 2;
+  if (rows) frames_per = std::max<uint64_t>(1, std::min(frames_per, s.max_frames));
+  const uint64_t* d_starts = plan_step(dim3(grid_for(n, 256)), w.plan, w.gstart, w.sum);
   // (ranges: n < 2^31 and frames_per < 2^32 + 3, the first product cannot wrap; the second is capped before it is formed)
-  const uint64_t cov_hint = n * frames_per, item_hint = std::min<uint64_t>(cov_hint, 256ull * X3W_GRID_LIMIT) * nseg;
-  const dim3 g_check(groups(cov_hint, 4)), g_decode(groups(item_hint, 256)), g_fix(groups(n, 4));
+  const uint64_t cov_hint = n * frames_per, item_hint = std::min<uint64_t>(cov_hint, 256ull * X3W_GRID_LIMIT) * s.nseg;
+  const dim3 g_check(grid_for(cov_hint, 4)), g_decode(grid_for(item_hint, 256)), g_fix(grid_for(n, 4));
   if (rows)
-    hipLaunchKernelGGL(x3_range_scan_kernel, dim3(1), dim3(1024), 0, c->stream, plan, n, rows->d_lens, rows->row_stride,
-                       rows->out_cap, idx, seg_blocks, nseg, cov_off, item_off, (unsigned long long*)(ws + o_off),
-                       (uint32_t*)(ws + o_elen), rows->d_out_offsets, sum);
+    hipLaunchKernelGGL(x3_range_scan_kernel, dim3(1), dim3(1024), 0, c->stream, w.plan, n, rows->d_lens, rows->row_stride,
+                       rows->out_cap, s.idx, s.seg_blocks, s.nseg, w.cov_off, w.item_off, w.off, w.elen, rows->d_out_offsets,
+                       w.sum);
   else
-    hipLaunchKernelGGL(x3_window_scan_kernel, dim3(1), dim3(1024), 0, c->stream, plan, n, idx, seg_blocks, nseg, cov_off, item_off);
-  hipLaunchKernelGGL(x3_window_check_kernel, g_check, dim3(256), 0, c->stream, d_x3, x3_len, d_frame_offsets, d_sample_offsets,
-                     plan, n, cov_off, fst);
+    hipLaunchKernelGGL(x3_window_scan_kernel, dim3(1), dim3(1024), 0, c->stream, w.plan, n, s.idx, s.seg_blocks, s.nseg,
+                       w.cov_off, w.item_off);
+  hipLaunchKernelGGL(x3_window_check_kernel, g_check, dim3(256), 0, c->stream, s.d_x3, s.x3_len, s.d_frame_offsets,
+                     s.d_sample_offsets, w.plan, n, w.cov_off, w.fst);
   auto decode_fixup = [&](auto g) {   // g: the rows, X3WinFixedGeo or X3WinRangeGeo
     using Geo = decltype(g);
-    hipLaunchKernelGGL((x3_window_decode_kernel<Geo>), g_decode, dim3(256), 0, c->stream, d_x3, x3_len, d_frame_offsets,
-                       d_sample_offsets, d_starts, (const X3WinPlan*)plan, n, g, (const unsigned long long*)item_off, dp, idx,
-                       seg_blocks, nseg, d_out, out_format, fst);
-    hipLaunchKernelGGL((x3_window_fixup_kernel<Geo>), g_fix, dim3(256), 0, c->stream, d_x3, d_frame_offsets, d_sample_offsets,
-                       d_starts, (const X3WinPlan*)plan, n, g, dp, (const int32_t*)fst, d_out, out_format, d_status, scratch,
-                       scratch_per, sum);
+    hipLaunchKernelGGL((x3_window_decode_kernel<Geo>), g_decode, dim3(256), 0, c->stream, s.d_x3, s.x3_len, s.d_frame_offsets,
+                       s.d_sample_offsets, d_starts, (const X3WinPlan*)w.plan, n, g, (const unsigned long long*)w.item_off, s.dp,
+                       s.idx, s.seg_blocks, s.nseg, d_out, out_format, w.fst);
+    hipLaunchKernelGGL((x3_window_fixup_kernel<Geo>), g_fix, dim3(256), 0, c->stream, s.d_x3, s.d_frame_offsets,
+                       s.d_sample_offsets, d_starts, (const X3WinPlan*)w.plan, n, g, s.dp, (const int32_t*)w.fst, d_out, out_format,
+                       d_status, w.scratch, scratch_per, w.sum);
   };
   if (rows)
-    decode_fixup(X3WinRangeGeo{(const uint32_t*)(ws + o_elen), (const unsigned long long*)(ws + o_off), rows->row_stride});
+    decode_fixup(X3WinRangeGeo{(const uint32_t*)w.elen, (const unsigned long long*)w.off, rows->row_stride});
   else
     decode_fixup(X3WinFixedGeo{window_len});
   HIPCHK(c, hipGetLastError());
-  c->windows_pending = true;
-  c->win_ranges = rows != nullptr;
-  c->win_windows = n;
-  c->win_sum_off = o_sum;
+  c->windows.pending = true;
+  c->windows.ranges = rows != nullptr;
+  c->windows.count = n;
+  c->windows.sum_off = (size_t)((char*)w.sum - (char*)c->win_ws.p);
   return X3_OK;
 }
 
@@ -1140,18 +1210,11 @@ extern "C" int x3_decode_windows_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3
                                      const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
                                      const uint64_t* d_seg_index, uint32_t seg_blocks, const uint64_t* d_starts,
                                      uint64_t n_windows, uint32_t window_len, void* d_out, int out_format, int32_t* d_status) {
-  if (!c || !d_x3 || !d_frame_offsets || !d_sample_offsets || !p) return X3_ERR_BAD_ARG;
-  if (!windows_args_ok(n_windows, window_len, d_out, out_format, d_starts, d_status)) return X3_ERR_BAD_ARG;
-  if (!frame_table_args_ok(d_x3, d_frame_offsets, n_frames) || (reinterpret_cast<uintptr_t>(d_sample_offsets) & 7u))
-    return X3_ERR_BAD_ARG;
-  if (d_seg_index && !seg_index_args_ok(d_seg_index, seg_blocks)) return X3_ERR_BAD_ARG;
-  X3DevParams dp;
-  const uint64_t spf = spf_of(p);
-  int rc = derive_block_params(p, &dp);
+  if (!c || !windows_args_ok(n_windows, window_len, d_out, out_format, d_starts, d_status)) return X3_ERR_BAD_ARG;
+  FrameSource s;
+  const int rc = stream_source(d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, p, d_seg_index, seg_blocks, &s);
   if (rc) return rc;
-  HIPCHK(c, hipSetDevice(c->device));
-  return windows_launch(c, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, dp, spf, d_seg_index, seg_blocks, n_windows,
-                        window_len, nullptr, d_out, out_format, d_status,
+  return windows_launch(c, s, n_windows, window_len, nullptr, d_out, out_format, d_status,
                         [&](dim3 grid, X3WinPlan* plan, uint64_t*, X3WinSummary* sum) -> const uint64_t* {
                           hipLaunchKernelGGL(x3_window_plan_kernel, grid, dim3(256), 0, c->stream, d_sample_offsets, n_frames,
                                              d_starts, n_windows, window_len, plan, sum);
@@ -1159,25 +1222,21 @@ extern "C" int x3_decode_windows_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3
                         });
 }
 
-// waits for the pending windows (ranges: false) or ranges (true) call and reads its summary
-static int windows_summary(x3_ctx* c, bool ranges, X3WinSummary* h) {
-  if (!c || !c->windows_pending || c->win_ranges != ranges) return X3_ERR_BAD_ARG;
-  HIPCHK(c, hipMemcpyAsync(h, (char*)c->win_ws.p + c->win_sum_off, sizeof(*h), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->windows_pending = false;
-  c->last_window_replays = h->replays;
+// the result of the pending windows (ranges: false) or ranges (true) call; a call of the other kind stays pending
+static int windows_result(x3_ctx* c, bool ranges, uint64_t* n_bad, uint64_t* first_bad, int* first_bad_status,
+                          uint64_t* total_samples) {
+  if (!c || c->windows.ranges != ranges) return X3_ERR_BAD_ARG;
+  X3WinSummary h{0, 0, 0, 0};
+  const int rc = pending_fetch(c, c->windows, c->win_ws, &h, sizeof h);
+  if (rc) return rc;
+  c->last_window_replays = h.replays;
+  first_bad_of(h.n_bad, h.first, c->windows.count, n_bad, first_bad, first_bad_status);
+  if (total_samples) *total_samples = h.total;
   return X3_OK;
 }
 
 extern "C" int x3_decode_windows_result(x3_ctx* c, uint64_t* n_bad, uint64_t* first_bad, int* first_bad_status) {
-  X3WinSummary h{0, 0, 0, 0};
-  const int rc = windows_summary(c, false, &h);
-  if (rc) return rc;
-  const bool any = h.n_bad != 0;
-  if (n_bad) *n_bad = h.n_bad;
-  if (first_bad) *first_bad = any ? (h.first >> 8) : c->win_windows;
-  if (first_bad_status) *first_bad_status = any ? (int)(h.first & 0xFFu) : 0;
-  return X3_OK;
+  return windows_result(c, false, n_bad, first_bad, first_bad_status, nullptr);
 }
 
 // ranges: a length per range, rows packed or padded
@@ -1200,20 +1259,13 @@ extern "C" int x3_decode_ranges_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_
                                     const uint64_t* d_seg_index, uint32_t seg_blocks, const uint64_t* d_starts,
                                     const uint32_t* d_lens, uint64_t n_ranges, uint64_t row_stride, void* d_out,
                                     uint64_t out_cap, int out_format, uint64_t* d_out_offsets, int32_t* d_status) {
-  if (!c || !d_x3 || !d_frame_offsets || !d_sample_offsets || !p) return X3_ERR_BAD_ARG;
-  if (!ranges_args_ok(c, n_ranges, d_lens, row_stride, d_out, out_cap, out_format, d_starts, d_out_offsets, d_status))
+  if (!c || !ranges_args_ok(c, n_ranges, d_lens, row_stride, d_out, out_cap, out_format, d_starts, d_out_offsets, d_status))
     return X3_ERR_BAD_ARG;
-  if (!frame_table_args_ok(d_x3, d_frame_offsets, n_frames) || (reinterpret_cast<uintptr_t>(d_sample_offsets) & 7u))
-    return X3_ERR_BAD_ARG;
-  if (d_seg_index && !seg_index_args_ok(d_seg_index, seg_blocks)) return X3_ERR_BAD_ARG;
-  X3DevParams dp;
-  const uint64_t spf = spf_of(p);
-  int rc = derive_block_params(p, &dp);
+  FrameSource s;
+  const int rc = stream_source(d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, p, d_seg_index, seg_blocks, &s);
   if (rc) return rc;
-  HIPCHK(c, hipSetDevice(c->device));
-  const RangeRows rows{d_lens, row_stride, out_cap, d_out_offsets, n_frames};
-  return windows_launch(c, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, dp, spf, d_seg_index, seg_blocks, n_ranges,
-                        0, &rows, d_out, out_format, d_status,
+  const RangeRows rows{d_lens, row_stride, out_cap, d_out_offsets};
+  return windows_launch(c, s, n_ranges, 0, &rows, d_out, out_format, d_status,
                         [&](dim3 grid, X3WinPlan* plan, uint64_t*, X3WinSummary* sum) -> const uint64_t* {
                           hipLaunchKernelGGL(x3_range_plan_kernel, grid, dim3(256), 0, c->stream, d_sample_offsets, n_frames,
                                              d_starts, d_lens, n_ranges, plan, sum);
@@ -1223,15 +1275,7 @@ extern "C" int x3_decode_ranges_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_
 
 extern "C" int x3_decode_ranges_result(x3_ctx* c, uint64_t* n_bad, uint64_t* first_bad, int* first_bad_status,
                                        uint64_t* total_samples) {
-  X3WinSummary h{0, 0, 0, 0};
-  const int rc = windows_summary(c, true, &h);
-  if (rc) return rc;
-  const bool any = h.n_bad != 0;
-  if (n_bad) *n_bad = h.n_bad;
-  if (first_bad) *first_bad = any ? (h.first >> 8) : c->win_windows;
-  if (first_bad_status) *first_bad_status = any ? (int)(h.first & 0xFFu) : 0;
-  if (total_samples) *total_samples = h.total;
-  return X3_OK;
+  return windows_result(c, true, n_bad, first_bad, first_bad_status, total_samples);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1243,55 +1287,64 @@ static bool levels_args_ok(const x3_ctx* c, const x3_level* d_levels, uint64_t n
   return (reinterpret_cast<uintptr_t>(d_levels) & 7u) == 0 && (reinterpret_cast<uintptr_t>(d_frame_status) & 3u) == 0;
 }
 
+// the rows of n_samples positions: max(1, ceil(n_samples / bin_len)), one with bin_len 0
+static uint64_t levels_rows_of(uint64_t n_samples, uint64_t bin_len) {
+  return bin_len == 0 || n_samples == 0 ? 1 : n_samples / bin_len + (n_samples % bin_len ? 1 : 0);
+}
+
+// The workspace (LevWs, x3_internal.h): per-frame verdicts, plans, row counts and their scan; the partial rows; replay
+// scratch; summary; row prefix.  The fix-up's waves: one block of replay scratch each, 32 MiB of it at most.
+uint32_t levels_scratch_per(uint32_t block_len) { return (std::min<uint32_t>(block_len, 0x10000u) + 7u) & ~7u; }
+
+uint64_t levels_fix_waves(uint64_t F, uint32_t scratch_per) {
+  return std::max<uint64_t>(1, std::min<uint64_t>({(F + 3) / 4 * 4, 4096, (32ull << 20) / (2ull * scratch_per) / 4 * 4}));
+}
+
+size_t levels_carve(char* base, uint64_t F, uint64_t n_rows, uint64_t fix_waves, uint32_t scratch_per, uint64_t n_ent, LevWs* w) {
+  BlockCarver k{base, 0};
+  w->fst = k.take<int32_t>(F);
+  w->frames = k.take<X3LevFrame>(F);
+  w->cnt = k.take<uint32_t>(F);
+  w->row = k.take<unsigned long long>(F + 1);
+  w->rows = k.take<x3_level>(n_rows + F);
+  w->scratch = k.take<int16_t>(std::max<uint64_t>(fix_waves, 4) * scratch_per);
+  w->sum = k.take<X3LevSummary>(1);
+  w->row_first = k.take<unsigned long long>(n_ent + 1, 1);
+  return k.at;
+}
+
 // The launch set of a levels call behind its prep step: prep(grid, row_first, fst, frames, cnt) enqueues the kernels that
 // give every frame its position, its records and its row count.  n_ent: entries of a corpus call (their row prefix lives
 // in the workspace), 0 for a stream.
 template <class Prep>
-static int levels_launch(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
-                         const uint64_t* d_sample_offsets, uint64_t F, const X3DevParams& dp, const uint64_t* d_seg_index,
-                         uint32_t seg_blocks, uint64_t bin_len, x3_level* d_levels, uint64_t n_rows, int32_t* d_frame_status,
-                         uint64_t n_ent, Prep prep) {
-  const uint64_t nidx = d_seg_index ? seg_stretches(dp.blocks_per_frame, seg_blocks) : 1;
-  const uint32_t nseg = nidx >= 2 ? (uint32_t)nidx : 1u;
-  const uint2* idx = nseg >= 2 ? reinterpret_cast<const uint2*>(d_seg_index) : nullptr;
-  // the fix-up's waves: one block of replay scratch each, 32 MiB of it at most
-  const uint32_t scratch_per = (std::min<uint32_t>(dp.block_len, 0x10000u) + 7u) & ~7u;
-  const uint64_t fix_waves = std::max<uint64_t>(1, std::min<uint64_t>({(F + 3) / 4 * 4, 4096, (32ull << 20) / (2ull * scratch_per) / 4 * 4}));
-  // workspace: per-frame verdicts, plans, row counts and their scan; the partial rows; replay scratch; summary; row prefix
-  const uint64_t cap = n_rows + F;
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t o_fst = 0, o_fr = up(o_fst + F * 4), o_cnt = up(o_fr + F * sizeof(X3LevFrame)), o_row = up(o_cnt + F * 4),
-               o_rows = up(o_row + (F + 1) * 8), o_scr = up(o_rows + cap * sizeof(x3_level)),
-               o_sum = up(o_scr + std::max<uint64_t>(fix_waves, 4) * scratch_per * 2), o_rf = up(o_sum + sizeof(X3LevSummary)),
-               total = o_rf + (n_ent + 1) * 8;
+static int levels_launch(x3_ctx* c, const FrameSource& s, uint64_t bin_len, x3_level* d_levels, uint64_t n_rows,
+                         int32_t* d_frame_status, uint64_t n_ent, Prep prep) {
+  HIPCHK(c, hipSetDevice(c->device));
+  const uint64_t F = s.F, cap = n_rows + F;
+  const uint32_t scratch_per = levels_scratch_per(s.dp.block_len);
+  const uint64_t fix_waves = levels_fix_waves(F, scratch_per);
+  LevWs w;
   int rc;
-  if ((rc = ensure(c, c->lev_ws, total))) return rc;
-  char* const ws = (char*)c->lev_ws.p;
-  int32_t* fst = (int32_t*)(ws + o_fst);
-  X3LevFrame* frames = (X3LevFrame*)(ws + o_fr);
-  uint32_t* cnt = (uint32_t*)(ws + o_cnt);
-  unsigned long long* row = (unsigned long long*)(ws + o_row);
-  x3_level* rows = (x3_level*)(ws + o_rows);
-  int16_t* scratch = (int16_t*)(ws + o_scr);
-  X3LevSummary* sum = (X3LevSummary*)(ws + o_sum);
-  auto groups = [&](uint64_t units, uint64_t per_group) {
-    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((units + per_group - 1) / per_group, X3W_GRID_LIMIT));
-  };
-  hipLaunchKernelGGL(x3_levels_init_kernel, dim3(groups(n_rows + cap, 256)), dim3(256), 0, c->stream, d_levels, n_rows, rows, cap, sum);
-  hipLaunchKernelGGL(x3_levels_check_kernel, dim3(groups(F, 4)), dim3(256), 0, c->stream, d_x3, x3_len, d_frame_offsets,
-                     d_sample_offsets, F, fst);
-  prep(dim3(groups(F, 256)), (unsigned long long*)(ws + o_rf), (const int32_t*)fst, frames, cnt);
-  hipLaunchKernelGGL(x3_levels_scan_kernel, dim3(1), dim3(1024), 0, c->stream, (const uint32_t*)cnt, F, cap, row, fst);
-  hipLaunchKernelGGL(x3_levels_accum_kernel, dim3(groups(F * nseg, 256)), dim3(256), 0, c->stream, d_x3, x3_len, d_frame_offsets,
-                     F, dp, idx, seg_blocks, nseg, bin_len, (const X3LevFrame*)frames, (const unsigned long long*)row, rows, fst);
-  hipLaunchKernelGGL(x3_levels_fixup_kernel, dim3((unsigned)((fix_waves + 3) / 4)), dim3(256), 0, c->stream, d_x3, d_frame_offsets,
-                     F, dp, bin_len, (const X3LevFrame*)frames, fst, d_levels, d_frame_status, scratch, scratch_per, sum);
-  hipLaunchKernelGGL(x3_levels_merge_kernel, dim3(groups(cap, 256)), dim3(256), 0, c->stream, (const X3LevFrame*)frames,
-                     (const unsigned long long*)row, F, cap, (const x3_level*)rows, (const int32_t*)fst, d_levels);
+  if ((rc = ensure(c, c->lev_ws, levels_carve(nullptr, F, n_rows, fix_waves, scratch_per, n_ent, &w)))) return rc;
+  levels_carve((char*)c->lev_ws.p, F, n_rows, fix_waves, scratch_per, n_ent, &w);
+  hipLaunchKernelGGL(x3_levels_init_kernel, dim3(grid_for(n_rows + cap, 256)), dim3(256), 0, c->stream, d_levels, n_rows, w.rows,
+                     cap, w.sum);
+  hipLaunchKernelGGL(x3_levels_check_kernel, dim3(grid_for(F, 4)), dim3(256), 0, c->stream, s.d_x3, s.x3_len, s.d_frame_offsets,
+                     s.d_sample_offsets, F, w.fst);
+  prep(dim3(grid_for(F, 256)), w.row_first, (const int32_t*)w.fst, w.frames, w.cnt);
+  hipLaunchKernelGGL(x3_levels_scan_kernel, dim3(1), dim3(1024), 0, c->stream, (const uint32_t*)w.cnt, F, cap, w.row, w.fst);
+  hipLaunchKernelGGL(x3_levels_accum_kernel, dim3(grid_for(F * s.nseg, 256)), dim3(256), 0, c->stream, s.d_x3, s.x3_len,
+                     s.d_frame_offsets, F, s.dp, s.idx, s.seg_blocks, s.nseg, bin_len, (const X3LevFrame*)w.frames,
+                     (const unsigned long long*)w.row, w.rows, w.fst);
+  hipLaunchKernelGGL(x3_levels_fixup_kernel, dim3((unsigned)((fix_waves + 3) / 4)), dim3(256), 0, c->stream, s.d_x3,
+                     s.d_frame_offsets, F, s.dp, bin_len, (const X3LevFrame*)w.frames, w.fst, d_levels, d_frame_status, w.scratch,
+                     scratch_per, w.sum);
+  hipLaunchKernelGGL(x3_levels_merge_kernel, dim3(grid_for(cap, 256)), dim3(256), 0, c->stream, (const X3LevFrame*)w.frames,
+                     (const unsigned long long*)w.row, F, cap, (const x3_level*)w.rows, (const int32_t*)w.fst, d_levels);
   HIPCHK(c, hipGetLastError());
-  c->levels_pending = true;
-  c->lev_frames = F;
-  c->lev_sum_off = o_sum;
+  c->levels.pending = true;
+  c->levels.count = F;
+  c->levels.sum_off = (size_t)((char*)w.sum - (char*)c->lev_ws.p);
   return X3_OK;
 }
 
@@ -1299,17 +1352,11 @@ extern "C" int x3_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, co
                              const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
                              const uint64_t* d_seg_index, uint32_t seg_blocks, uint64_t bin_len, x3_level* d_levels,
                              uint64_t n_bins, int32_t* d_frame_status) {
-  if (!c || !d_x3 || !d_frame_offsets || !d_sample_offsets || !p) return X3_ERR_BAD_ARG;
-  if (!levels_args_ok(c, d_levels, n_bins, d_frame_status)) return X3_ERR_BAD_ARG;
-  if (!frame_table_args_ok(d_x3, d_frame_offsets, n_frames) || (reinterpret_cast<uintptr_t>(d_sample_offsets) & 7u))
-    return X3_ERR_BAD_ARG;
-  if (d_seg_index && !seg_index_args_ok(d_seg_index, seg_blocks)) return X3_ERR_BAD_ARG;
-  X3DevParams dp;
-  int rc = derive_block_params(p, &dp);
+  if (!c || !levels_args_ok(c, d_levels, n_bins, d_frame_status)) return X3_ERR_BAD_ARG;
+  FrameSource s;
+  const int rc = stream_source(d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, p, d_seg_index, seg_blocks, &s);
   if (rc) return rc;
-  HIPCHK(c, hipSetDevice(c->device));
-  return levels_launch(c, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, dp, d_seg_index, seg_blocks, bin_len,
-                       d_levels, n_bins, d_frame_status, 0,
+  return levels_launch(c, s, bin_len, d_levels, n_bins, d_frame_status, 0,
                        [&](dim3 grid, unsigned long long*, const int32_t* fst, X3LevFrame* frames, uint32_t* cnt) {
                          hipLaunchKernelGGL(x3_levels_prep_kernel, grid, dim3(256), 0, c->stream, d_sample_offsets, n_frames,
                                             bin_len, n_bins, fst, frames, cnt);
@@ -1317,17 +1364,12 @@ extern "C" int x3_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, co
 }
 
 extern "C" int x3_levels_result(x3_ctx* c, uint64_t* n_bad_frames, uint64_t* first_bad, int* first_bad_status) {
-  if (!c || !c->levels_pending) return X3_ERR_BAD_ARG;
+  if (!c) return X3_ERR_BAD_ARG;
   X3LevSummary h{0, 0, 0};
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipMemcpyAsync(&h, (char*)c->lev_ws.p + c->lev_sum_off, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->levels_pending = false;
+  const int rc = pending_fetch(c, c->levels, c->lev_ws, &h, sizeof h);
+  if (rc) return rc;
   c->last_levels_replays = h.replays;
-  const bool any = h.n_bad != 0;
-  if (n_bad_frames) *n_bad_frames = h.n_bad;
-  if (first_bad) *first_bad = any ? (h.first >> 8) : c->lev_frames;
-  if (first_bad_status) *first_bad_status = any ? (int)(h.first & 0xFFu) : 0;
+  first_bad_of(h.n_bad, h.first, c->levels.count, n_bad_frames, first_bad, first_bad_status);
   return X3_OK;
 }
 
@@ -1337,12 +1379,12 @@ extern "C" int x3_levels_result(x3_ctx* c, uint64_t* n_bad_frames, uint64_t* fir
 // One launch behind a 8-byte memset of the counter; nothing is allocated, nothing waits, no pending state is touched.
 static int seg_index_launch(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets, uint64_t F,
                             const X3DevParams& dp, uint64_t* d_seg_index, uint32_t seg_blocks) {
-  const uint64_t nidx = seg_stretches(dp.blocks_per_frame, seg_blocks);
+  const uint32_t nseg = seg_index_nseg(dp.blocks_per_frame, seg_blocks);
   HIPCHK(c, hipMemsetAsync(c->d_seg_irregular, 0, sizeof(unsigned long long), c->stream));
-  if (nidx < 2) return X3_OK;   // (x3_seg_index_entries() == 0: frames of one stretch have no index)
+  if (nseg < 2) return X3_OK;   // (x3_seg_index_entries() == 0: frames of one stretch have no index)
   const uint64_t groups = std::min<uint64_t>((F + 63) / 64, (uint64_t)c->n_cus * X3X_WAVES_PER_CU);
   hipLaunchKernelGGL(x3_seg_index_kernel, dim3((unsigned)groups), dim3(64), 0, c->stream, d_x3, x3_len, d_frame_offsets, F, dp,
-                     reinterpret_cast<uint2*>(d_seg_index), seg_blocks, (uint32_t)nidx, c->d_seg_irregular);
+                     reinterpret_cast<uint2*>(d_seg_index), seg_blocks, nseg, c->d_seg_irregular);
   HIPCHK(c, hipGetLastError());
   return X3_OK;
 }
@@ -1381,19 +1423,9 @@ int seg_entries(const uint64_t* offsets, const uint64_t* lengths, uint64_t n, ui
   return X3_OK;
 }
 
-// the pieces of one block, each a multiple of 256 bytes behind its base
-struct SegCarver {
-  char* base; size_t at;
-  template <class T> T* take(uint64_t count, size_t round = 256) {   // (round 1: the next piece follows directly)
-    T* const piece = reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(base) + at);
-    at = (at + count * sizeof(T) + round - 1) & ~(round - 1);
-    return piece;
-  }
-};
-
 size_t segwalk_carve(char* base, uint64_t n, uint64_t G, SegWalkWs* w) {
   const uint64_t cap = seg_cands(G);
-  SegCarver k{base, 0};
+  BlockCarver k{base, 0};
   w->eoff = k.take<uint64_t>(n, 1);   // eoff | elen | span_first back to back: segwalk_launch uploads them in one copy
   w->elen = k.take<uint64_t>(n, 1);
   w->span_first = k.take<uint32_t>(n + 1);
@@ -1447,7 +1479,7 @@ static int entry_copy(x3_ctx* c, const uint8_t* d_x3, uint64_t off, uint64_t len
 
 // ---- the batch decode.  A call's block (st_walk): the walk's workspace, then the call's own words (StreamsWs)
 size_t streams_carve(char* base, uint64_t n, uint64_t G, StreamsWs* s) {
-  SegCarver k{base, segwalk_carve(base, n, G, s)};
+  BlockCarver k{base, segwalk_carve(base, n, G, s)};
   s->sum = k.take<X3StreamsSum>(1);
   s->status = k.take<int32_t>(seg_cands(G));
   s->ent_bad = k.take<unsigned long long>(n);
@@ -1624,11 +1656,7 @@ extern "C" int x3_decode_streams_result(x3_ctx* c, uint64_t* n_bad, uint64_t* fi
       if ((rc = streams_finish(c, total, false))) return rc;
       if ((rc = streams_fetch(c, l, &total, &sum))) return rc;
     }
-    nb = sum.n_bad;
-    if (sum.n_bad) {
-      fb = sum.bad_first >> 8;
-      fst = (int)(sum.bad_first & 0xFFull);
-    }
+    first_bad_of(sum.n_bad, sum.bad_first, s.n, &nb, &fb, &fst);
     if (sum.n_dirty) {
       general.resize(sum.n_dirty);
       HIPCHK(c, hipMemcpyAsync(general.data(), l.dirty, 4ull * sum.n_dirty, hipMemcpyDeviceToHost, c->stream));
@@ -1717,14 +1745,14 @@ static int corpus_general_walk(x3_ctx* c, const uint8_t* d_x3, uint64_t off, uin
 #define X3K_RECORD_SCRATCH (256ull << 20)   // bytes of samples one slice decodes into
 static int corpus_record(x3_ctx* c, x3_corpus* k, const X3DevParams& dp, uint32_t seg_blocks, CorpusBlock& blk) {
   const uint64_t F = k->F;
-  const uint64_t nidx = seg_stretches(dp.blocks_per_frame, seg_blocks);
+  const uint64_t nidx = seg_index_nseg(dp.blocks_per_frame, seg_blocks);
   const uint64_t pitch = ((uint64_t)dp.spf + 3) & ~3ull;
   const uint64_t S = std::min<uint64_t>(F, std::max<uint64_t>(X3K_RECORD_SCRATCH / 2 / pitch, 1));
   int rc;
   int16_t* wav;
   uint64_t *woff, *sidx;
   auto carve = [&](char* base) {
-    SegCarver q{base, 0};
+    BlockCarver q{base, 0};
     wav = q.take<int16_t>(S * pitch), woff = q.take<uint64_t>(S), sidx = q.take<uint64_t>(1 + S * (nidx - 1));
     return q.at;
   };
@@ -1765,7 +1793,7 @@ static int corpus_build_impl(x3_ctx* c, x3_corpus* k, const uint64_t* offsets, c
   int32_t* ent_st = nullptr;                                // how its walk ends
   if (fast) {
     auto carve = [&](char* base) {   // the walk's workspace, then the build's own words
-      SegCarver q{base, segwalk_carve(base, n, G, &w)};
+      BlockCarver q{base, segwalk_carve(base, n, G, &w)};
       ent_k0 = q.take<unsigned long long>(n), ent_m = q.take<unsigned long long>(n), ent_st = q.take<int32_t>(n);
       return q.at;
     };
@@ -1828,7 +1856,7 @@ static int corpus_build_impl(x3_ctx* c, x3_corpus* k, const uint64_t* offsets, c
   HIPCHK(c, hipStreamSynchronize(c->stream));
   // ---- 3. the segment index: by one walk over the whole frame table for any parameters (X3_CORPUS_INDEX_WALK), or by
   // the recording decode where the parameters route to the decoder that records it
-  const uint64_t nidx = seg_blocks && F ? seg_stretches(dp.blocks_per_frame, seg_blocks) : 0;
+  const uint64_t nidx = F ? seg_index_nseg(dp.blocks_per_frame, seg_blocks) : 1;
   if (nidx >= 2 && (index_walk || decode_route(dp, X3Geom{0, 0, 1, F}, (const int16_t*)nullptr, true, true, 2, c->opt).kernel == X3_DEC_SPLIT)) {
     HIPCHK(c, hipMalloc(&k->d_index, 8 * (1 + F * (nidx - 1))));
     if (index_walk) {
@@ -1897,26 +1925,31 @@ extern "C" int x3_corpus_seg_index(const x3_corpus* k, const uint64_t** d_seg_in
   return X3_OK;
 }
 
+// The frames of a corpus for a call of this context; a corpus of another device is refused in `entry_point`'s name
+static int corpus_source(x3_ctx* c, const x3_corpus* k, const char* entry_point, FrameSource* s) {
+  if (c->device != k->device) {
+    c->last_error = std::string(entry_point) + ": the corpus was built on another device";
+    return X3_ERR_BAD_ARG;
+  }
+  s->d_x3 = k->d_x3, s->x3_len = k->x3_len;
+  s->d_frame_offsets = k->d_frame_off, s->d_sample_offsets = k->d_so, s->F = k->F, s->max_frames = k->max_frames;
+  s->spf = spf_of(&k->p);
+  const int rc = derive_params(&k->p, &s->dp);
+  if (rc == X3_OK) s->index(k->d_index, k->seg_blocks);
+  return rc;
+}
+
 extern "C" int x3_corpus_windows_dev(x3_ctx* c, const x3_corpus* k, const uint32_t* d_entries, const uint64_t* d_starts,
                                      uint64_t n_windows, uint32_t window_len, void* d_out, int out_format, int32_t* d_status) {
   if (!c || !k || !d_entries || (reinterpret_cast<uintptr_t>(d_entries) & 3u)) return X3_ERR_BAD_ARG;
   if (!windows_args_ok(n_windows, window_len, d_out, out_format, d_starts, d_status)) return X3_ERR_BAD_ARG;
-  if (c->device != k->device) {
-    c->last_error = "x3_corpus_windows_dev: the corpus was built on another device";
-    return X3_ERR_BAD_ARG;
-  }
-  X3DevParams dp;
-  const uint64_t spf = spf_of(&k->p);
-  int rc = derive_params(&k->p, &dp);
+  FrameSource s;
+  const int rc = corpus_source(c, k, "x3_corpus_windows_dev", &s);
   if (rc) return rc;
-  HIPCHK(c, hipSetDevice(c->device));
-  const uint64_t n_ent = k->n, F = k->F;
-  const x3_corpus_entry* ent = k->d_ent;
-  const uint64_t* so = k->d_so;
-  return windows_launch(c, k->d_x3, k->x3_len, k->d_frame_off, k->d_so, F, dp, spf, k->d_index, k->seg_blocks, n_windows,
-                        window_len, nullptr, d_out, out_format, d_status,
+  return windows_launch(c, s, n_windows, window_len, nullptr, d_out, out_format, d_status,
                         [&](dim3 grid, X3WinPlan* plan, uint64_t* gstart, X3WinSummary* sum) -> const uint64_t* {
-                          hipLaunchKernelGGL(x3_corpus_plan_kernel, grid, dim3(256), 0, c->stream, ent, n_ent, so, F, d_entries,
+                          hipLaunchKernelGGL(x3_corpus_plan_kernel, grid, dim3(256), 0, c->stream,
+                                             k->d_ent, k->n, s.d_sample_offsets, s.F, d_entries,
                                              d_starts, n_windows, window_len, plan, gstart, sum);
                           return gstart;
                         });
@@ -1928,36 +1961,26 @@ extern "C" int x3_corpus_ranges_dev(x3_ctx* c, const x3_corpus* k, const uint32_
   if (!c || !k || !d_entries || (reinterpret_cast<uintptr_t>(d_entries) & 3u)) return X3_ERR_BAD_ARG;
   if (!ranges_args_ok(c, n_ranges, d_lens, row_stride, d_out, out_cap, out_format, d_starts, d_out_offsets, d_status))
     return X3_ERR_BAD_ARG;
-  if (c->device != k->device) {
-    c->last_error = "x3_corpus_ranges_dev: the corpus was built on another device";
-    return X3_ERR_BAD_ARG;
-  }
-  X3DevParams dp;
-  const uint64_t spf = spf_of(&k->p);
-  int rc = derive_params(&k->p, &dp);
+  FrameSource s;
+  const int rc = corpus_source(c, k, "x3_corpus_ranges_dev", &s);
   if (rc) return rc;
-  HIPCHK(c, hipSetDevice(c->device));
-  const uint64_t n_ent = k->n, F = k->F;
-  const x3_corpus_entry* ent = k->d_ent;
-  const uint64_t* so = k->d_so;
-  const RangeRows rows{d_lens, row_stride, out_cap, d_out_offsets, k->max_frames};
-  return windows_launch(c, k->d_x3, k->x3_len, k->d_frame_off, k->d_so, F, dp, spf, k->d_index, k->seg_blocks, n_ranges, 0,
-                        &rows, d_out, out_format, d_status,
+  const RangeRows rows{d_lens, row_stride, out_cap, d_out_offsets};
+  return windows_launch(c, s, n_ranges, 0, &rows, d_out, out_format, d_status,
                         [&](dim3 grid, X3WinPlan* plan, uint64_t* gstart, X3WinSummary* sum) -> const uint64_t* {
-                          hipLaunchKernelGGL(x3_corpus_range_plan_kernel, grid, dim3(256), 0, c->stream, ent, n_ent, so, F,
-                                             d_entries, d_starts, d_lens, n_ranges, plan, gstart, sum);
+                          hipLaunchKernelGGL(x3_corpus_range_plan_kernel, grid, dim3(256), 0, c->stream,
+                                             k->d_ent, k->n, s.d_sample_offsets, s.F, d_entries,
+                                             d_starts, d_lens, n_ranges, plan, gstart, sum);
                           return gstart;
                         });
 }
 
-// the rows of entry e (max(1, ceil(n_samples / bin_len)), one with bin_len 0) in front of each other: n_entries + 1 words
+// the rows of entry e (levels_rows_of its samples) in front of each other: n_entries + 1 words
 extern "C" int x3_corpus_levels_rows(const x3_corpus* k, uint64_t bin_len, uint64_t* row_first) {
   if (!k || !row_first) return X3_ERR_BAD_ARG;
   uint64_t run = 0;
   for (uint64_t e = 0; e < k->n; ++e) {
     row_first[e] = run;
-    const uint64_t ns = k->ent[e].n_samples;
-    run += bin_len == 0 || ns == 0 ? 1 : ns / bin_len + (ns % bin_len ? 1 : 0);
+    run += levels_rows_of(k->ent[e].n_samples, bin_len);
   }
   row_first[k->n] = run;
   return X3_OK;
@@ -1966,27 +1989,18 @@ extern "C" int x3_corpus_levels_rows(const x3_corpus* k, uint64_t bin_len, uint6
 extern "C" int x3_corpus_levels_dev(x3_ctx* c, const x3_corpus* k, uint64_t bin_len, x3_level* d_levels, uint64_t n_rows,
                                     int32_t* d_frame_status) {
   if (!c || !k || !levels_args_ok(c, d_levels, n_rows, d_frame_status)) return X3_ERR_BAD_ARG;
-  if (c->device != k->device) {
-    c->last_error = "x3_corpus_levels_dev: the corpus was built on another device";
-    return X3_ERR_BAD_ARG;
-  }
-  uint64_t want = 0;
-  for (const x3_corpus_entry& en : k->ent)
-    want += bin_len == 0 || en.n_samples == 0 ? 1 : en.n_samples / bin_len + (en.n_samples % bin_len ? 1 : 0);
-  if (n_rows != want) return X3_ERR_BAD_ARG;
-  X3DevParams dp;
-  int rc = derive_params(&k->p, &dp);
+  FrameSource s;
+  const int rc = corpus_source(c, k, "x3_corpus_levels_dev", &s);
   if (rc) return rc;
-  HIPCHK(c, hipSetDevice(c->device));
-  const uint64_t n_ent = k->n, F = k->F;
-  const x3_corpus_entry* ent = k->d_ent;
-  const uint64_t* so = k->d_so;
-  return levels_launch(c, k->d_x3, k->x3_len, k->d_frame_off, k->d_so, F, dp, k->d_index, k->seg_blocks, bin_len, d_levels,
-                       n_rows, d_frame_status, n_ent,
+  uint64_t want = 0;   // (behind the device check, as ever: a call that fails both leaves that check's last_error)
+  for (const x3_corpus_entry& en : k->ent) want += levels_rows_of(en.n_samples, bin_len);
+  if (n_rows != want) return X3_ERR_BAD_ARG;
+  return levels_launch(c, s, bin_len, d_levels, n_rows, d_frame_status, k->n,
                        [&](dim3 grid, unsigned long long* row_first, const int32_t* fst, X3LevFrame* frames, uint32_t* cnt) {
-                         hipLaunchKernelGGL(x3_corpus_levels_rows_kernel, dim3(1), dim3(1024), 0, c->stream, ent, n_ent, bin_len,
-                                            row_first);
-                         hipLaunchKernelGGL(x3_corpus_levels_prep_kernel, grid, dim3(256), 0, c->stream, ent, n_ent,
-                                            (const unsigned long long*)row_first, so, F, bin_len, n_rows, fst, frames, cnt);
+                         hipLaunchKernelGGL(x3_corpus_levels_rows_kernel, dim3(1), dim3(1024), 0, c->stream,
+                                            k->d_ent, k->n, bin_len, row_first);
+                         hipLaunchKernelGGL(x3_corpus_levels_prep_kernel, grid, dim3(256), 0, c->stream,
+                                            k->d_ent, k->n, (const unsigned long long*)row_first,
+                                            s.d_sample_offsets, s.F, bin_len, n_rows, fst, frames, cnt);
                        });
 }

@@ -176,13 +176,17 @@ struct x3_ctx {
   uint64_t stream_wg_key = 0; // ... of which instantiation with how much LDS (block length, table form, bytes)
   // bookkeeping of the last async calls
   bool encode_pending = false, decode_pending = false;
-  bool windows_pending = false;    // x3_decode_windows_dev: its own pending state (x3_decode_result is not touched)
-  uint64_t win_windows = 0;        // ... its window count and where its summary lies in win_ws
-  size_t win_sum_off = 0;
-  bool win_ranges = false;         // the pending call is x3_decode_ranges_dev / x3_corpus_ranges_dev (x3_decode_ranges_result's)
-  bool levels_pending = false;     // x3_levels_dev / x3_corpus_levels_dev: a pending state of their own, as the windows'
-  uint64_t lev_frames = 0;         // ... their frame count and where their summary lies in lev_ws
-  size_t lev_sum_off = 0;
+  // The access calls' pending slots, each its own (x3_decode_result is not touched): the units the summary counts (windows
+  // or ranges; frames) and where the summary lies in the slot's workspace.  DESIGN.md section 12 says who owns which.
+  struct PendingCall {
+    bool pending = false;
+    uint64_t count = 0;
+    size_t sum_off = 0;
+  };
+  struct WindowsCall : PendingCall {
+    bool ranges = false;   // the pending call is a ranges call (x3_decode_ranges_result's), not a windows call
+  } windows;               // x3_decode_windows_dev / x3_decode_ranges_dev and their corpus forms: win_ws
+  PendingCall levels;      // x3_levels_dev / x3_corpus_levels_dev: lev_ws
   bool force_two_pass = false;
   // Contexts that encode concurrently on ONE GPU (the file pipeline's workers) share this gate: the single-pass encoders
   // are persistent grids whose workgroups wait for each other, so only one of them may be in flight on a device.  A
@@ -435,6 +439,30 @@ struct StreamsWs : SegWalkWs {
   unsigned long long* ent_bad; unsigned long long* nout; uint32_t* dirty;   // per entry
 };
 X3_INTERNAL size_t streams_carve(char* base, uint64_t n, uint64_t G, StreamsWs* s);
+// The workspace of a windows or ranges call (win_ws; x3_decode_window_kernel.h), by the same contract: n windows or ranges
+// over F frames, `scratch_per` samples of replay scratch each.  A windows call's block ends behind gstart, unrounded; a
+// ranges call's has the scan of the lengths and the lengths that have room behind it.
+struct X3WinPlan;
+struct X3WinSummary;
+struct WinWs {
+  X3WinPlan* plan; unsigned long long* cov_off; unsigned long long* item_off;   // per window; the two scans (n + 1 words each)
+  int32_t* fst; int16_t* scratch; X3WinSummary* sum; uint64_t* gstart;          // per frame; per window; the summary; per window
+  unsigned long long* off; uint32_t* elen;                                      // ranges only: n + 1 and n words
+};
+X3_INTERNAL uint32_t windows_scratch_per(uint32_t block_len);
+X3_INTERNAL size_t windows_carve(char* base, uint64_t n, uint64_t F, uint32_t scratch_per, bool ranges, WinWs* w);
+// ... and of a levels call (lev_ws; x3_levels_kernel.h): F frames, n_rows records of the caller's (the partial rows are
+// n_rows + F), `fix_waves` waves of the fix-up with `scratch_per` samples each, the row prefix of n_ent corpus entries
+struct X3LevFrame;
+struct X3LevSummary;
+struct LevWs {
+  int32_t* fst; X3LevFrame* frames; uint32_t* cnt; unsigned long long* row;   // per frame (row: F + 1 words)
+  x3_level* rows; int16_t* scratch; X3LevSummary* sum; unsigned long long* row_first;
+};
+X3_INTERNAL uint32_t levels_scratch_per(uint32_t block_len);
+X3_INTERNAL uint64_t levels_fix_waves(uint64_t F, uint32_t scratch_per);
+X3_INTERNAL size_t levels_carve(char* base, uint64_t F, uint64_t n_rows, uint64_t fix_waves, uint32_t scratch_per, uint64_t n_ent,
+                                LevWs* w);
 // ---- x3_files.hip (x3_reader.h)
 // the RIFF/WAVE header parser of x3_wav_to_x3a on an open file, for the sanitised host tests (tests/host_cpp/fuzz_host_parsers.cpp)
 X3_INTERNAL int x3_wav_parse_fd_for_tests(int fd, uint64_t file_len, uint32_t* sample_rate, uint16_t* channels, uint16_t* bits,
