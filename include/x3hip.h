@@ -162,6 +162,8 @@ const char* x3_last_error(const x3_ctx* ctx);
  * x3_levels_dev / x3_corpus_levels_dev: read-only "last_levels_replays" (frames of the last call that were decoded through
  * the reference's reader instead of by stretches: flagged ones, and frames whose offsets are out of order; read after
  * x3_levels_result).
+ * x3_events_dev / x3_corpus_events_dev: read-only "events_tile_rows" (rows a workgroup of the events kernels takes at a
+ * time; for tests that lay rows at tile edges).
  * x3_corpus_build: read-only "last_corpus_record_slices" (slices of frames the last build recorded its segment index in;
  * 0 without an index).
  * x3_seg_index_build_dev: read-only "last_seg_index_irregular" (frames of the last build -- x3_corpus_build's with
@@ -757,6 +759,12 @@ int x3_corpus_info(const x3_corpus* corpus, uint64_t* n_entries, uint64_t* n_fra
                    uint32_t* seg_blocks_in_use);
 /* the entry table (host array of n_entries) */
 int x3_corpus_entries(const x3_corpus* corpus, x3_corpus_entry* out);
+/* The device copy of the entry table the corpus calls read (device memory the corpus owns, n_entries records).  Nothing
+ * trusts it: written to after the build it can move or empty entries, give statuses or slower paths, never an access outside
+ * the caller's buffers -- which is what a test of that claim needs the pointer for.  The pointer is const because no caller
+ * has a reason to write there; one who casts it away and writes gets exactly that outcome, by design, for every corpus call
+ * enqueued afterwards, until the corpus is freed (the host copy x3_corpus_entries returns is not changed by it). */
+int x3_corpus_entries_dev(const x3_corpus* corpus, const x3_corpus_entry** d_entries);
 /* The segment index the build recorded (device memory the corpus owns; layout as x3_decode_dev_seg's, over the corpus's frame
  * table): *d_seg_index and *n_words, or NULL and 0 without one. */
 int x3_corpus_seg_index(const x3_corpus* corpus, const uint64_t** d_seg_index, uint64_t* n_words);
@@ -786,6 +794,54 @@ int x3_corpus_ranges_dev(x3_ctx* ctx, const x3_corpus* corpus, const uint32_t* d
 int x3_corpus_levels_rows(const x3_corpus* corpus, uint64_t bin_len, uint64_t* row_first);
 int x3_corpus_levels_dev(x3_ctx* ctx, const x3_corpus* corpus, uint64_t bin_len, x3_level* d_levels, uint64_t n_rows,
                          int32_t* d_frame_status);
+/* ---- EVENTS (no counterpart in the reference): runs of loud bins of level records as ranges (entry, start, len), found on
+ * the device -- the link between the levels calls and the ranges calls, with no host trip.
+ *   Row b of d_levels is a bin of bin_len positions as x3_levels_dev / x3_corpus_levels_dev write it.  A bin is HOT when
+ * its n != 0 and sum_sq >= mean_sq_min * n (mean_sq_min != 0) or max(max, -min) >= peak_min (peak_min != 0); a bin with
+ * n == 0 -- every bin of a frame that failed -- is never hot.  A RUN is a maximal set of hot bins of ONE entry whose gaps
+ * are at most join_bins cold bins; it spans [first hot, last hot].  Runs of fewer than min_bins bins are dropped and do not
+ * exist for anything that follows.  A kept run is padded by pad_bins bins on both sides, clipped to its entry's rows, to bins
+ * [b0, b1), and cut into pieces of max_bins bins, the last one shorter.  Piece [p0, p1) is the EVENT start = p0 * bin_len,
+ * len = min(p1 * bin_len, n_samples) - start, positions relative to the entry.  2 * pad_bins <= join_bins leaves a cold bin
+ * between padded runs: events are disjoint and strictly increasing in (entry, start).  An event's x3_level is the merge of
+ * the records of ALL its bins, padding included, from the identities on: sum_sq, sum and n added (n modulo 2^32), min and
+ * max taken.  Everything is integer arithmetic; the result is exact. */
+typedef struct x3_event_rule {   /* 32 bytes */
+  uint64_t mean_sq_min;  /* 0: off.  A bin is hot when sum_sq >= mean_sq_min * n          (<= 1 << 30) */
+  uint32_t peak_min;     /* 0: off.  A bin is hot when max(max, -min) >= peak_min         (<= 32768)   */
+  uint32_t join_bins;    /* hot bins with at most this many cold bins between them are one run */
+  uint32_t min_bins;     /* runs spanning fewer bins (first hot .. last hot) are dropped; 0 and 1: none */
+  uint32_t pad_bins;     /* bins added on both sides of a kept run, clipped to the entry; 2 * pad_bins <= join_bins */
+  uint32_t max_bins;     /* a longer event is cut into pieces of max_bins, the last one shorter; 0: floor(0xFFFFFFFF / bin_len) */
+  uint32_t reserved;     /* 0 */
+} x3_event_rule;
+/* The stream form: ONE entry.  d_total: a device pointer to one word, the stream's sample count (d_sample_offsets +
+ * n_frames is the natural argument); it is untrusted, the rows counted are min(n_bins, ceil(*d_total / bin_len)).
+ *   Outputs (device arrays of cap elements): d_starts (uint64), d_lens (uint32), d_event_levels (x3_level; may be NULL);
+ * d_count (one uint64) receives the number of events FOUND, which may exceed cap -- the caller grows the arrays and repeats,
+ * as with the packed ranges.  Slots [0, min(count, cap)) hold the first events in order; EVERY slot behind them up to cap
+ * is written as the filler (entry 0, start 0, len 0, the identity record), so the arrays can go to x3_decode_ranges_dev with
+ * n_ranges = cap as they are: a filler range has status 0 and writes nothing.  Nothing outside these arrays is written,
+ * nothing outside d_levels[0 .. n_bins) and *d_total is read.
+ *   Asynchronous on the context's stream: one launch set, no host trip, nothing allocated after the first call of a size.
+ * The call has a pending slot and a workspace of its own; the states of x3_decode_dev, the window / ranges calls and the
+ * levels calls are left alone.  X3_ERR_BAD_ARG with nothing enqueued for bin_len == 0 or above 0xFFFFFFFF, both criteria
+ * 0, mean_sq_min above 1 << 30, peak_min above 32768, 2 * pad_bins > join_bins, max_bins * bin_len > 0xFFFFFFFF,
+ * reserved != 0, cap == 0 or above 0x7FFFFFFF, n_bins == 0 or above 0x7FFFFFFF, a NULL or misaligned pointer (8 bytes;
+ * d_lens 4) other than d_event_levels, and a context that is recording a graph. */
+int x3_events_dev(x3_ctx* ctx, const x3_level* d_levels, uint64_t n_bins, uint64_t bin_len, const uint64_t* d_total,
+                  const x3_event_rule* rule, uint64_t* d_starts, uint32_t* d_lens, x3_level* d_event_levels, uint64_t cap,
+                  uint64_t* d_count);
+/* The corpus form: rows as x3_corpus_levels_dev lays them (n_rows must be x3_corpus_levels_rows' last word, as there); the
+ * row prefix is computed on the device from the corpus's entry table, an entry's rows are clipped to n_rows.  Entry e's
+ * events are exactly x3_events_dev's on that entry's rows alone with *d_total = its n_samples; d_entries (uint32, cap
+ * elements, required) receives the events' entries.  Otherwise as x3_events_dev; also X3_ERR_BAD_ARG with nothing enqueued
+ * for a context on another device than the build's.  The arrays go to x3_corpus_ranges_dev as they are. */
+int x3_corpus_events_dev(x3_ctx* ctx, const x3_corpus* corpus, const x3_level* d_levels, uint64_t n_rows, uint64_t bin_len,
+                         const x3_event_rule* rule, uint32_t* d_entries, uint64_t* d_starts, uint32_t* d_lens,
+                         x3_level* d_event_levels, uint64_t cap, uint64_t* d_count);
+/* Waits for the last x3_events_dev / x3_corpus_events_dev: the number of events found (what d_count holds). */
+int x3_events_result(x3_ctx* ctx, uint64_t* count);
 void x3_corpus_destroy(x3_corpus* corpus);
 
 /* ------------------------------------------------------------------ multi-GPU (no reference analogue) */

@@ -10,6 +10,7 @@
 #include "x3_decode_window_kernel.h"
 #include "x3_seg_index_kernel.h"
 #include "x3_levels_kernel.h"
+#include "x3_events_kernel.h"
 
 // ------------------------------------------------------------------------------------------------
 // decode
@@ -1918,6 +1919,12 @@ extern "C" int x3_corpus_entries(const x3_corpus* k, x3_corpus_entry* out) {
   return X3_OK;
 }
 
+extern "C" int x3_corpus_entries_dev(const x3_corpus* k, const x3_corpus_entry** d_entries) {
+  if (!k || !d_entries) return X3_ERR_BAD_ARG;
+  *d_entries = k->d_ent;
+  return X3_OK;
+}
+
 extern "C" int x3_corpus_seg_index(const x3_corpus* k, const uint64_t** d_seg_index, uint64_t* n_words) {
   if (!k || !d_seg_index || !n_words) return X3_ERR_BAD_ARG;
   *d_seg_index = k->d_index;
@@ -2003,4 +2010,115 @@ extern "C" int x3_corpus_levels_dev(x3_ctx* c, const x3_corpus* k, uint64_t bin_
                                             k->d_ent, k->n, (const unsigned long long*)row_first,
                                             s.d_sample_offsets, s.F, bin_len, n_rows, fst, frames, cnt);
                        });
+}
+
+// ------------------------------------------------------------------------------------------------
+// events: runs of loud bins of level records as ranges (x3_events_kernel.h)
+// ------------------------------------------------------------------------------------------------
+static_assert(X3E_TILE == X3_EVENTS_TILE_ROWS, "the option \"events_tile_rows\" reports the kernels' tile");
+
+// The workspace (EvWs, x3_internal.h): a byte per row; four words per tile; the run tables and the scan of their pieces (a
+// row starts at most one run); the summary; a corpus's row prefix
+size_t events_carve(char* base, uint64_t n_rows, uint64_t n_ent, EvWs* w) {
+  BlockCarver k{base, 0};
+  const uint64_t n_tiles = (n_rows + X3E_TILE - 1) / X3E_TILE;
+  w->hot = k.take<uint8_t>(n_rows);
+  w->tile_prev = k.take<uint32_t>(n_tiles);
+  w->tile_next = k.take<uint32_t>(n_tiles);
+  w->tile_ns = k.take<uint32_t>(n_tiles);
+  w->tile_ne = k.take<uint32_t>(n_tiles);
+  w->run_first = k.take<uint32_t>(n_rows);
+  w->run_last = k.take<uint32_t>(n_rows);
+  w->piece_off = k.take<unsigned long long>(n_rows + 1);
+  w->sum = k.take<X3EvSummary>(1);
+  w->row_first = k.take<unsigned long long>(n_ent + 1, 1);
+  return k.at;
+}
+
+// the argument checks x3_events_dev and x3_corpus_events_dev share; *eff: the rule the kernels take (max_bins never 0)
+static bool events_args_ok(const x3_ctx* c, const x3_level* d_levels, uint64_t n_rows, uint64_t bin_len, const x3_event_rule* rule,
+                           const uint64_t* d_starts, const uint32_t* d_lens, const x3_level* d_event_levels, uint64_t cap,
+                           const uint64_t* d_count, x3_event_rule* eff) {
+  if (!c || !d_levels || !rule || !d_starts || !d_lens || !d_count || c->capturing) return false;
+  if (bin_len == 0 || bin_len > 0xFFFFFFFFull || n_rows == 0 || n_rows > 0x7FFFFFFFull || cap == 0 || cap > 0x7FFFFFFFull) return false;
+  if ((rule->mean_sq_min == 0 && rule->peak_min == 0) || rule->mean_sq_min > (1ull << 30) || rule->peak_min > 32768u) return false;
+  if (2ull * rule->pad_bins > rule->join_bins || (uint64_t)rule->max_bins * bin_len > 0xFFFFFFFFull || rule->reserved) return false;
+  const uintptr_t p8 = reinterpret_cast<uintptr_t>(d_levels) | reinterpret_cast<uintptr_t>(d_starts) |
+                       reinterpret_cast<uintptr_t>(d_event_levels) | reinterpret_cast<uintptr_t>(d_count);
+  if ((p8 & 7u) || (reinterpret_cast<uintptr_t>(d_lens) & 3u)) return false;
+  *eff = *rule;
+  if (!eff->max_bins) eff->max_bins = (uint32_t)(0xFFFFFFFFull / bin_len);
+  return true;
+}
+
+// The launch set of an events call.  q: the rows (its row_first is set here); k: the corpus of a corpus call, whose row
+// prefix the levels' kernel computes into the workspace first.
+static int events_launch(x3_ctx* c, X3EvRows q, const x3_corpus* k, const x3_event_rule& rule, uint32_t* d_entries,
+                         uint64_t* d_starts, uint32_t* d_lens, x3_level* d_event_levels, uint64_t cap, uint64_t* d_count) {
+  HIPCHK(c, hipSetDevice(c->device));
+  EvWs w;
+  int rc;
+  if ((rc = ensure(c, c->ev_ws, events_carve(nullptr, q.n_rows, q.n_ent, &w)))) return rc;
+  events_carve((char*)c->ev_ws.p, q.n_rows, q.n_ent, &w);
+  const uint64_t n_tiles = (q.n_rows + X3E_TILE - 1) / X3E_TILE;
+  const dim3 g_tiles(grid_for(n_tiles, 1));
+  if (k) {
+    hipLaunchKernelGGL(x3_corpus_levels_rows_kernel, dim3(1), dim3(1024), 0, c->stream, k->d_ent, k->n, q.bin_len, w.row_first);
+    q.row_first = w.row_first;
+  }
+  hipLaunchKernelGGL(x3_events_flag_kernel, g_tiles, dim3(256), 0, c->stream, q, rule, n_tiles, w.hot, w.tile_prev, w.tile_next);
+  hipLaunchKernelGGL(x3_events_near_kernel, dim3(1), dim3(1024), 0, c->stream, n_tiles, w.tile_prev, w.tile_next);
+  hipLaunchKernelGGL(x3_events_mark_kernel, g_tiles, dim3(256), 0, c->stream, q, rule.join_bins, n_tiles, w.hot,
+                     (const uint32_t*)w.tile_prev, (const uint32_t*)w.tile_next, w.tile_ns, w.tile_ne);
+  hipLaunchKernelGGL(x3_events_count_kernel, dim3(1), dim3(1024), 0, c->stream, n_tiles, w.tile_ns, w.tile_ne, w.sum);
+  hipLaunchKernelGGL(x3_events_table_kernel, g_tiles, dim3(256), 0, c->stream, q.n_rows, n_tiles, (const uint8_t*)w.hot,
+                     (const uint32_t*)w.tile_ns, (const uint32_t*)w.tile_ne, w.run_first, w.run_last);
+  hipLaunchKernelGGL(x3_events_runs_kernel, dim3(1), dim3(1024), 0, c->stream, q, rule, w.run_first, w.run_last, w.piece_off, w.sum,
+                     d_count);
+  // (the count is on the device: a wave per slot of the caller's arrays at most, grid-stride)
+  hipLaunchKernelGGL(x3_events_emit_kernel, dim3(grid_for(cap, 4)), dim3(256), 0, c->stream, q, rule, (const uint32_t*)w.run_first,
+                     (const uint32_t*)w.run_last, (const unsigned long long*)w.piece_off, (const X3EvSummary*)w.sum, cap, d_entries,
+                     d_starts, d_lens, d_event_levels);
+  HIPCHK(c, hipGetLastError());
+  c->events.pending = true;
+  c->events.count = cap;
+  c->events.sum_off = (size_t)((char*)w.sum - (char*)c->ev_ws.p);
+  return X3_OK;
+}
+
+extern "C" int x3_events_dev(x3_ctx* c, const x3_level* d_levels, uint64_t n_bins, uint64_t bin_len, const uint64_t* d_total,
+                             const x3_event_rule* rule, uint64_t* d_starts, uint32_t* d_lens, x3_level* d_event_levels,
+                             uint64_t cap, uint64_t* d_count) {
+  x3_event_rule eff;
+  if (!events_args_ok(c, d_levels, n_bins, bin_len, rule, d_starts, d_lens, d_event_levels, cap, d_count, &eff)) return X3_ERR_BAD_ARG;
+  if (!d_total || (reinterpret_cast<uintptr_t>(d_total) & 7u)) return X3_ERR_BAD_ARG;
+  return events_launch(c, X3EvRows{d_levels, n_bins, bin_len, d_total, nullptr, 0, nullptr}, nullptr, eff, nullptr, d_starts, d_lens,
+                       d_event_levels, cap, d_count);
+}
+
+extern "C" int x3_corpus_events_dev(x3_ctx* c, const x3_corpus* k, const x3_level* d_levels, uint64_t n_rows, uint64_t bin_len,
+                                    const x3_event_rule* rule, uint32_t* d_entries, uint64_t* d_starts, uint32_t* d_lens,
+                                    x3_level* d_event_levels, uint64_t cap, uint64_t* d_count) {
+  x3_event_rule eff;
+  if (!k || !events_args_ok(c, d_levels, n_rows, bin_len, rule, d_starts, d_lens, d_event_levels, cap, d_count, &eff))
+    return X3_ERR_BAD_ARG;
+  if (!d_entries || (reinterpret_cast<uintptr_t>(d_entries) & 3u)) return X3_ERR_BAD_ARG;
+  if (c->device != k->device) {
+    c->last_error = "x3_corpus_events_dev: the corpus was built on another device";
+    return X3_ERR_BAD_ARG;
+  }
+  uint64_t want = 0;
+  for (const x3_corpus_entry& en : k->ent) want += levels_rows_of(en.n_samples, bin_len);
+  if (n_rows != want) return X3_ERR_BAD_ARG;
+  return events_launch(c, X3EvRows{d_levels, n_rows, bin_len, nullptr, k->d_ent, k->n, nullptr}, k, eff, d_entries, d_starts, d_lens,
+                       d_event_levels, cap, d_count);
+}
+
+extern "C" int x3_events_result(x3_ctx* c, uint64_t* count) {
+  if (!c) return X3_ERR_BAD_ARG;
+  X3EvSummary h{0, 0};
+  const int rc = pending_fetch(c, c->events, c->ev_ws, &h, sizeof h);
+  if (rc) return rc;
+  if (count) *count = h.count;
+  return X3_OK;
 }

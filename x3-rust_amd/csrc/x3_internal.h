@@ -153,6 +153,7 @@ struct x3_ctx {
   DevBuf idx_cand, idx_keys, idx_vals, idx_J, idx_S, idx_L, idx_sum;  // x3_index_dev scratch
   DevBuf idx_wg, idx_sorted, idx_scan;  // ... of its fast path: candidates per scanning workgroup, in order, the scans
   DevBuf lev_ws;   // x3_levels_dev / x3_corpus_levels_dev: verdicts, plans, the frames' partial rows, replay scratch, summary (x3_levels_kernel.h)
+  DevBuf ev_ws;    // x3_events_dev / x3_corpus_events_dev: row flags, tile totals, run tables, piece scan, summary, row prefix (x3_events_kernel.h)
   DevBuf win_ws;   // x3_decode_windows_dev: plans, scans, per-frame verdicts, replay scratch, summary (x3_decode_window_kernel.h)
   // x3_decode_streams_dev (x3_streams_kernel.h): the call's block (the segmented walk's workspace and the call's own words:
   // streams_carve, x3_decode.hip), the int16 rows of a float32 call, an entry the general walk takes (aligned copy, int16 row)
@@ -187,6 +188,7 @@ struct x3_ctx {
     bool ranges = false;   // the pending call is a ranges call (x3_decode_ranges_result's), not a windows call
   } windows;               // x3_decode_windows_dev / x3_decode_ranges_dev and their corpus forms: win_ws
   PendingCall levels;      // x3_levels_dev / x3_corpus_levels_dev: lev_ws
+  PendingCall events;      // x3_events_dev / x3_corpus_events_dev: ev_ws (count: the call's cap)
   bool force_two_pass = false;
   // Contexts that encode concurrently on ONE GPU (the file pipeline's workers) share this gate: the single-pass encoders
   // are persistent grids whose workgroups wait for each other, so only one of them may be in flight on a device.  A
@@ -463,6 +465,17 @@ X3_INTERNAL uint32_t levels_scratch_per(uint32_t block_len);
 X3_INTERNAL uint64_t levels_fix_waves(uint64_t F, uint32_t scratch_per);
 X3_INTERNAL size_t levels_carve(char* base, uint64_t F, uint64_t n_rows, uint64_t fix_waves, uint32_t scratch_per, uint64_t n_ent,
                                 LevWs* w);
+// ... and of an events call (ev_ws; x3_events_kernel.h): n_rows records in tiles of X3_EVENTS_TILE_ROWS, the row prefix of
+// n_ent corpus entries.  A row starts at most one run: the run tables and the piece scan hold n_rows (+ 1) words.
+#define X3_EVENTS_TILE_ROWS 256
+struct X3EvSummary;
+struct EvWs {
+  uint8_t* hot;                                                       // per row
+  uint32_t* tile_prev; uint32_t* tile_next; uint32_t* tile_ns; uint32_t* tile_ne;   // per tile
+  uint32_t* run_first; uint32_t* run_last; unsigned long long* piece_off;           // per run (piece_off: one more)
+  X3EvSummary* sum; unsigned long long* row_first;
+};
+X3_INTERNAL size_t events_carve(char* base, uint64_t n_rows, uint64_t n_ent, EvWs* w);
 // ---- x3_files.hip (x3_reader.h)
 // the RIFF/WAVE header parser of x3_wav_to_x3a on an open file, for the sanitised host tests (tests/host_cpp/fuzz_host_parsers.cpp)
 X3_INTERNAL int x3_wav_parse_fd_for_tests(int fd, uint64_t file_len, uint32_t* sample_rate, uint16_t* channels, uint16_t* bits,

@@ -785,6 +785,19 @@ inline X3Error levels(Context& ctx, const EncodedStream& s, const Parameters& pa
   return static_cast<X3Error>(rc);
 }
 
+// Events (x3_events_dev): the runs of hot bins of n_bins level records (as device::levels writes them; bins of bin_len
+// positions) under `rule`, as cap slots of (d_starts, d_lens, d_event_levels or nullptr); d_count receives the number found,
+// which may exceed cap; every slot behind the events is a zero-length range, so the arrays go to device::decode_ranges with
+// n_ranges = cap as they are.  d_total: device pointer to the stream's sample count (the last word of the sample offsets).
+// Waits for the call: *count = the events found.
+inline X3Error events(Context& ctx, const x3_level* d_levels, uint64_t n_bins, uint64_t bin_len, const uint64_t* d_total,
+                      const x3_event_rule& rule, uint64_t* d_starts, uint32_t* d_lens, x3_level* d_event_levels, uint64_t cap,
+                      uint64_t* d_count, uint64_t* count) {
+  int rc = x3_events_dev(ctx.raw(), d_levels, n_bins, bin_len, d_total, &rule, d_starts, d_lens, d_event_levels, cap, d_count);
+  if (rc != X3_OK) return static_cast<X3Error>(rc);
+  return static_cast<X3Error>(x3_events_result(ctx.raw(), count));
+}
+
 // A batch of independent streams (x3_decode_streams_dev): entry s = bytes [offsets[s], offsets[s] + lengths[s]) of d_x3 (flags:
 // X3_STREAMS_ARCHIVE_FRAMES for the frame parts of .x3a archives), decoded into row s of d_out (offsets.size() rows of row_len
 // samples, X3_WINDOW_I16 / X3_WINDOW_F32, zeros behind each entry's samples); d_results[s] = x3_decode_stream_dev's results on
@@ -882,6 +895,16 @@ class Corpus {
     rc = x3_levels_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status);
     if (res) *res = r;
     return static_cast<X3Error>(rc);
+  }
+  // Events of every entry (x3_corpus_events_dev) over the n_rows records levels() wrote: as device::events, with the events'
+  // entries in d_entries; the arrays go to ranges() with n_ranges = cap as they are.  Waits for the call.
+  X3Error events(Context& ctx, const x3_level* d_levels, uint64_t n_rows, uint64_t bin_len, const x3_event_rule& rule,
+                 uint32_t* d_entries, uint64_t* d_starts, uint32_t* d_lens, x3_level* d_event_levels, uint64_t cap,
+                 uint64_t* d_count, uint64_t* count) const {
+    int rc = x3_corpus_events_dev(ctx.raw(), raw_, d_levels, n_rows, bin_len, &rule, d_entries, d_starts, d_lens, d_event_levels,
+                                  cap, d_count);
+    if (rc != X3_OK) return static_cast<X3Error>(rc);
+    return static_cast<X3Error>(x3_events_result(ctx.raw(), count));
   }
   // the recorded segment index (device memory the corpus owns), nullptr and 0 words without one
   const uint64_t* seg_index(uint64_t* n_words) const {

@@ -70,6 +70,18 @@ pub mod ffi {
         pub n: u32,
         pub reserved: u32,
     }
+    /// `x3_event_rule`: which bins are hot and how runs of them become events (`x3_events_dev`; 32 bytes)
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+    pub struct x3_event_rule {
+        pub mean_sq_min: u64,
+        pub peak_min: u32,
+        pub join_bins: u32,
+        pub min_bins: u32,
+        pub pad_bins: u32,
+        pub max_bins: u32,
+        pub reserved: u32,
+    }
     #[repr(C)]
     #[derive(Clone, Copy, Debug)]
     pub struct x3_rice_code {
@@ -177,6 +189,7 @@ pub mod ffi {
                               seg_blocks_in_use: *mut u32) -> c_int;
         pub fn x3_corpus_entries(corpus: *const x3_corpus, out: *mut x3_corpus_entry) -> c_int;
         pub fn x3_corpus_seg_index(corpus: *const x3_corpus, d_seg_index: *mut *const u64, n_words: *mut u64) -> c_int;
+        pub fn x3_corpus_entries_dev(corpus: *const x3_corpus, d_entries: *mut *const x3_corpus_entry) -> c_int;
         pub fn x3_corpus_windows_dev(ctx: *mut x3_ctx, corpus: *const x3_corpus, d_entries: *const u32, d_starts: *const u64,
                                      n_windows: u64, window_len: u32, d_out: *mut c_void, out_format: c_int, d_status: *mut i32) -> c_int;
         pub fn x3_corpus_ranges_dev(ctx: *mut x3_ctx, corpus: *const x3_corpus, d_entries: *const u32, d_starts: *const u64,
@@ -189,6 +202,13 @@ pub mod ffi {
         pub fn x3_corpus_levels_rows(corpus: *const x3_corpus, bin_len: u64, row_first: *mut u64) -> c_int;
         pub fn x3_corpus_levels_dev(ctx: *mut x3_ctx, corpus: *const x3_corpus, bin_len: u64, d_levels: *mut x3_level, n_rows: u64,
                                     d_frame_status: *mut i32) -> c_int;
+        pub fn x3_events_dev(ctx: *mut x3_ctx, d_levels: *const x3_level, n_bins: u64, bin_len: u64, d_total: *const u64,
+                             rule: *const x3_event_rule, d_starts: *mut u64, d_lens: *mut u32, d_event_levels: *mut x3_level,
+                             cap: u64, d_count: *mut u64) -> c_int;
+        pub fn x3_corpus_events_dev(ctx: *mut x3_ctx, corpus: *const x3_corpus, d_levels: *const x3_level, n_rows: u64, bin_len: u64,
+                                    rule: *const x3_event_rule, d_entries: *mut u32, d_starts: *mut u64, d_lens: *mut u32,
+                                    d_event_levels: *mut x3_level, cap: u64, d_count: *mut u64) -> c_int;
+        pub fn x3_events_result(ctx: *mut x3_ctx, count: *mut u64) -> c_int;
         pub fn x3_corpus_destroy(corpus: *mut x3_corpus);
         pub fn x3_place_buffers(ctx: *mut x3_ctx, d_wav: *const i16, n: u64, p: *const x3_params, d_streams: *const *mut u8,
                                 n_streams: u32, cap: u64, d_frame_offsets: *mut u64, d_backs: *const *mut i16, n_backs: u32,
@@ -1341,6 +1361,36 @@ pub mod device {
         Ok((n_bad, first_bad, st))
     }
 
+    /// The rule of `events` / `Corpus::events` (`x3_event_rule`): a bin is hot when `sum_sq >= mean_sq_min * n` or `max(max,
+    /// -min) >= peak_min` (0: off); hot bins with at most `join_bins` cold ones between them are one run; runs of fewer than
+    /// `min_bins` bins are dropped; `pad_bins` on both sides (`2 * pad_bins <= join_bins`); pieces of `max_bins` (0: no cut)
+    pub type EventRule = ffi::x3_event_rule;
+
+    /// Events (`x3_events_dev`; not in the reference crate): the runs of hot bins of `n_bins` level records (as `levels` writes
+    /// them) as `cap` slots of `d_starts` (u64), `d_lens` (u32) and, optionally, merged records in `d_event_levels`; `d_count`
+    /// (one u64) receives the number found, which may exceed `cap`.  Slots behind the events are zero-length ranges: the arrays
+    /// go to `decode_ranges` with `n_ranges = cap` as they are.  `sample_offsets`: the stream's (its last word is the sample
+    /// count the rows are clipped to).  Waits: -> the events found
+    #[allow(clippy::too_many_arguments)]
+    pub fn events<'g>(gpu: &'g Gpu, d_levels: &Buffer<'g>, n_bins: usize, bin_len: u64, sample_offsets: &Buffer<'g>, n_frames: usize,
+                      rule: &EventRule, d_starts: &mut Buffer<'g>, d_lens: &mut Buffer<'g>, d_event_levels: Option<&mut Buffer<'g>>,
+                      cap: usize, d_count: &mut Buffer<'g>) -> error::Result<u64> {
+        if d_levels.len() < core::mem::size_of::<Level>() * n_bins || sample_offsets.len() < 8 * (n_frames + 1)
+            || d_starts.len() < 8 * cap || d_lens.len() < 4 * cap || d_count.len() < 8
+            || d_event_levels.as_ref().map_or(false, |b| b.len() < core::mem::size_of::<Level>() * cap) {
+            return Err(X3Error::BadArg);
+        }
+        let el_ptr = match d_event_levels { Some(b) => b.as_ptr::<Level>(), None => core::ptr::null_mut() };
+        error::check(unsafe {
+            ffi::x3_events_dev(gpu.raw(), d_levels.as_ptr::<Level>() as *const Level, n_bins as u64, bin_len,
+                               (sample_offsets.as_ptr::<u64>() as *const u64).add(n_frames), rule, d_starts.as_ptr::<u64>(),
+                               d_lens.as_ptr::<u32>(), el_ptr, cap as u64, d_count.as_ptr::<u64>())
+        })?;
+        let mut count = 0u64;
+        error::check(unsafe { ffi::x3_events_result(gpu.raw(), &mut count) })?;
+        Ok(count)
+    }
+
     /// `decode_streams` flag: the entries are the frame part of .x3a archives (walked with the reader's 8 phantom bytes)
     pub const STREAMS_ARCHIVE_FRAMES: u32 = 1;
     /// `Corpus::build` flag: the segment index by `x3_seg_index_build_dev` -- for every parameter set, not only where a
@@ -1486,6 +1536,31 @@ pub mod device {
             let (mut n_bad, mut first_bad, mut st) = (0u64, 0u64, 0);
             error::check(unsafe { ffi::x3_levels_result(self.gpu.raw(), &mut n_bad, &mut first_bad, &mut st) })?;
             Ok((n_bad, first_bad, st))
+        }
+    }
+
+    impl<'g> Corpus<'g> {
+        /// Events of every entry (`x3_corpus_events_dev`) over the `n_rows` records `levels` wrote: as `device::events`, with
+        /// the events' entries in `d_entries` (u32); the arrays go to `ranges` with `n_ranges = cap` as they are.  Waits: ->
+        /// the events found
+        #[allow(clippy::too_many_arguments)]
+        pub fn events(&self, d_levels: &Buffer<'g>, n_rows: usize, bin_len: u64, rule: &EventRule, d_entries: &mut Buffer<'g>,
+                      d_starts: &mut Buffer<'g>, d_lens: &mut Buffer<'g>, d_event_levels: Option<&mut Buffer<'g>>, cap: usize,
+                      d_count: &mut Buffer<'g>) -> error::Result<u64> {
+            if d_levels.len() < core::mem::size_of::<Level>() * n_rows || d_entries.len() < 4 * cap || d_starts.len() < 8 * cap
+                || d_lens.len() < 4 * cap || d_count.len() < 8
+                || d_event_levels.as_ref().map_or(false, |b| b.len() < core::mem::size_of::<Level>() * cap) {
+                return Err(X3Error::BadArg);
+            }
+            let el_ptr = match d_event_levels { Some(b) => b.as_ptr::<Level>(), None => core::ptr::null_mut() };
+            error::check(unsafe {
+                ffi::x3_corpus_events_dev(self.gpu.raw(), self.raw, d_levels.as_ptr::<Level>() as *const Level, n_rows as u64, bin_len,
+                                          rule, d_entries.as_ptr::<u32>(), d_starts.as_ptr::<u64>(), d_lens.as_ptr::<u32>(), el_ptr,
+                                          cap as u64, d_count.as_ptr::<u64>())
+            })?;
+            let mut count = 0u64;
+            error::check(unsafe { ffi::x3_events_result(self.gpu.raw(), &mut count) })?;
+            Ok(count)
         }
     }
 

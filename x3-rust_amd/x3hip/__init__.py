@@ -59,9 +59,10 @@ SYMBOLS = [
     "x3_sample_offsets_dev", "x3_decode_windows_dev", "x3_decode_windows_result",
     "x3_decode_ranges_dev", "x3_corpus_ranges_dev", "x3_decode_ranges_result",
     "x3_decode_streams_dev", "x3_decode_streams_result",
-    "x3_corpus_build", "x3_corpus_info", "x3_corpus_entries", "x3_corpus_seg_index", "x3_corpus_windows_dev",
+    "x3_corpus_build", "x3_corpus_info", "x3_corpus_entries", "x3_corpus_entries_dev", "x3_corpus_seg_index", "x3_corpus_windows_dev",
     "x3_corpus_destroy",
     "x3_levels_dev", "x3_levels_result", "x3_corpus_levels_rows", "x3_corpus_levels_dev",
+    "x3_events_dev", "x3_corpus_events_dev", "x3_events_result",
     "x3_tune_candidate", "x3_tuner_create", "x3_tuner_add_dev", "x3_tuner_result", "x3_tuner_max_payloads",
     "x3_tuner_reset", "x3_tuner_destroy", "x3_tune", "x3_x3a_encode_tuned",
 ]
@@ -76,6 +77,26 @@ CORPUS_INDEX_WALK = 0x100        # x3_corpus_build: the segment index by x3_seg_
 # x3_level: one bin of x3_levels_dev / x3_corpus_levels_dev (32 bytes)
 LEVEL_DTYPE = np.dtype([("sum_sq", np.uint64), ("sum", np.int64), ("min", np.int32), ("max", np.int32), ("n", np.uint32),
                         ("reserved", np.uint32)])
+
+
+class EventRule(C.Structure):
+    """x3_event_rule: which bins of level records are hot and how runs of them become events (x3_events_dev)"""
+    _fields_ = [("mean_sq_min", C.c_uint64), ("peak_min", C.c_uint32), ("join_bins", C.c_uint32), ("min_bins", C.c_uint32),
+                ("pad_bins", C.c_uint32), ("max_bins", C.c_uint32), ("reserved", C.c_uint32)]
+
+    @classmethod
+    def make(cls, mean_sq_min=0, peak_min=0, join_bins=0, min_bins=0, pad_bins=0, max_bins=0):
+        return cls(mean_sq_min, peak_min, join_bins, min_bins, pad_bins, max_bins, 0)
+
+
+EVENT_RULE_DTYPE = np.dtype([("mean_sq_min", "<u8"), ("peak_min", "<u4"), ("join_bins", "<u4"), ("min_bins", "<u4"),
+                             ("pad_bins", "<u4"), ("max_bins", "<u4"), ("reserved", "<u4")])
+
+
+def event_levels_view(t):
+    """the merged records of events() / a [n, 32] uint8 tensor or array of x3_level records -> np.ndarray of LEVEL_DTYPE [n]"""
+    a = t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
+    return np.ascontiguousarray(a).view(np.uint8).reshape(-1).view(LEVEL_DTYPE)
 
 
 class StreamResult(C.Structure):
@@ -232,12 +253,16 @@ def lib():
     L.x3_corpus_info.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]
     L.x3_corpus_entries.argtypes = [vp, vp]
     L.x3_corpus_seg_index.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
+    L.x3_corpus_entries_dev.argtypes = [vp, C.POINTER(vp)]
     L.x3_corpus_windows_dev.argtypes = [vp, vp, vp, vp, u64, u32, vp, i32, vp]
     L.x3_corpus_destroy.argtypes = [vp]
     L.x3_levels_dev.argtypes = [vp, vp, u64, vp, vp, u64, PP, vp, u32, u64, vp, u64, vp]
     L.x3_levels_result.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(i32)]
     L.x3_corpus_levels_rows.argtypes = [vp, u64, vp]
     L.x3_corpus_levels_dev.argtypes = [vp, vp, u64, vp, u64, vp]
+    L.x3_events_dev.argtypes = [vp, vp, u64, u64, vp, C.POINTER(EventRule), vp, vp, vp, u64, vp]
+    L.x3_corpus_events_dev.argtypes = [vp, vp, vp, u64, u64, C.POINTER(EventRule), vp, vp, vp, vp, u64, vp]
+    L.x3_events_result.argtypes = [vp, C.POINTER(u64)]
     L.x3_corpus_destroy.restype = None
     L.x3_synth.argtypes = [i32, u64, u64, u64, vp]
     L.x3_synth_dev.argtypes = [vp, i32, u64, u64, u64, vp]
@@ -968,6 +993,24 @@ class Context:
         """x3_corpus_levels_dev: the levels of every entry of `corpus` (a Corpus), rows as Corpus.levels_rows; asynchronous"""
         return lib().x3_corpus_levels_dev(self._h, corpus._h, bin_len, d_levels, n_rows, d_frame_status)
 
+    def events_dev(self, d_levels, n_bins, bin_len, d_total, rule, d_starts, d_lens, d_event_levels, cap, d_count):
+        """x3_events_dev: runs of hot bins of n_bins level records (rule: an EventRule) as cap slots of (start u64, len u32,
+        merged x3_level or None), the number found to d_count (u64); d_total: device pointer to the sample count; asynchronous"""
+        return lib().x3_events_dev(self._h, d_levels, n_bins, bin_len, d_total, C.byref(rule), d_starts, d_lens, d_event_levels,
+                                   cap, d_count)
+
+    def corpus_events_dev(self, corpus, d_levels, n_rows, bin_len, rule, d_entries, d_starts, d_lens, d_event_levels, cap,
+                          d_count):
+        """x3_corpus_events_dev: the same over the rows of Context.corpus_levels_dev, d_entries (u32) as well; asynchronous"""
+        return lib().x3_corpus_events_dev(self._h, corpus._h, d_levels, n_rows, bin_len, C.byref(rule), d_entries, d_starts,
+                                          d_lens, d_event_levels, cap, d_count)
+
+    def events_result(self):
+        """-> (rc, count) of the last events_dev / corpus_events_dev: the events found (may exceed the call's cap)"""
+        n = C.c_uint64(0)
+        rc = lib().x3_events_result(self._h, C.byref(n))
+        return rc, n.value
+
     def decode_streams_dev(self, d_x3, x3_len, offsets, lengths, params, d_out, row_len, out_format, d_results, flags=0):
         """x3_decode_streams_dev: entry s = bytes [offsets[s], offsets[s] + lengths[s]) of d_x3 -> row s of d_out
         (len(offsets) x row_len samples) and d_results[s] (asynchronous; offsets / lengths: host sequences)"""
@@ -1093,6 +1136,39 @@ def _ranges_torch(ctx, enqueue, what, starts, lens, padded_to, capacity, dtype, 
     if rc:
         raise X3Error(rc, "x3_decode_ranges_result: " + ctx.last_error())
     return out[:cap] if padded_to is None else out, offsets, status
+
+
+def _events_torch(ctx, n_rows, capacity, with_entries, enqueue_levels, enqueue_events):
+    """The torch side of WindowSource.events / Corpus.events: the levels call and the events call back to back on the
+    context's stream, no host trip in between -> ([entries,] starts, lens, count, event_levels), device tensors of `capacity`
+    slots (count: 0-d; event_levels: [capacity, 32] uint8, see event_levels_view).  enqueue_levels(d_levels) -> rc,
+    enqueue_events(d_levels, d_entries, d_starts, d_lens, d_event_levels, d_count) -> rc."""
+    import torch
+    capacity = int(capacity)
+    if capacity <= 0:
+        raise ValueError("capacity: at least one slot")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    levels = torch.empty((n_rows, LEVEL_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    entries = torch.empty(capacity, dtype=torch.int32, device=dev) if with_entries else None
+    starts = torch.empty(capacity, dtype=torch.int64, device=dev)
+    lens = torch.empty(capacity, dtype=torch.int32, device=dev)
+    event_levels = torch.empty((capacity, LEVEL_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    count = torch.empty((), dtype=torch.int64, device=dev)
+    torch.cuda.current_stream().synchronize()    # (the context's stream is not torch's)
+    rc = enqueue_levels(levels.data_ptr())
+    if rc:
+        raise X3Error(rc, "levels: " + ctx.last_error())
+    rc = enqueue_events(levels.data_ptr(), entries.data_ptr() if with_entries else None, starts.data_ptr(), lens.data_ptr(),
+                        event_levels.data_ptr(), count.data_ptr())
+    if rc:
+        ctx.levels_result()
+        raise X3Error(rc, "events: " + ctx.last_error())
+    rc_ev, rc_lv = ctx.events_result()[0], ctx.levels_result()[0]   # (both slots are read, whatever the first says)
+    rc = rc_ev or rc_lv
+    if rc:
+        raise X3Error(rc, "x3_events_result: " + ctx.last_error())
+    out = (starts, lens, count, event_levels)
+    return (entries,) + out if with_entries else out
 
 
 class WindowSource:
@@ -1232,6 +1308,26 @@ class WindowSource:
         finally:
             for p in (d_lv, d_st):
                 self.ctx.free(p)
+
+    def events_into(self, d_levels, n_bins, bin_len, rule, d_starts, d_lens, d_event_levels, cap, d_count):
+        """enqueue x3_events_dev over n_bins records this source's levels_dev wrote (device pointers; the sample count is the
+        last word of the source's sample offsets); -> rc; Context.events_result waits"""
+        return self.ctx.events_dev(d_levels, n_bins, bin_len, self.d_sample_offsets + 8 * self.n_frames, rule, d_starts, d_lens,
+                                   d_event_levels, cap, d_count)
+
+    def events(self, bin_len, rule, capacity):
+        """Levels of bins of bin_len positions, then the runs of hot bins under `rule` (an EventRule) as ranges, all on the
+        device -> (starts int64 [capacity], lens int32 [capacity], count 0-d int64, event_levels uint8 [capacity, 32]),
+        torch tensors on the device.  Slots behind the events are zero-length ranges: ranges(starts, lens, padded_to=...)
+        takes the tensors as they are.  count may exceed capacity: repeat with more."""
+        if not 0 < bin_len <= 0xFFFFFFFF:
+            raise ValueError("bin_len: 1 .. 2^32 - 1")
+        n_bins = max(1, -(-self.total // bin_len))
+        return _events_torch(
+            self.ctx, n_bins, capacity, False,
+            lambda d_lv: self.ctx.levels_dev(self.d_x3, self.x3_len, self.d_frame_offsets, self.d_sample_offsets, self.n_frames,
+                                             self.params, bin_len, d_lv, n_bins, None, self.d_seg_index, self.seg_blocks),
+            lambda d_lv, d_e, d_s, d_l, d_el, d_c: self.events_into(d_lv, n_bins, bin_len, rule, d_s, d_l, d_el, capacity, d_c))
 
     def close(self):
         for p in self._own:
@@ -1382,6 +1478,9 @@ class Corpus:
         lib().x3_corpus_entries(h, self.entries.ctypes.data)
         d_idx, nw = C.c_void_p(0), C.c_uint64(0)
         lib().x3_corpus_seg_index(h, C.byref(d_idx), C.byref(nw))
+        d_ent = C.c_void_p(0)
+        lib().x3_corpus_entries_dev(h, C.byref(d_ent))
+        self.d_entries = d_ent.value   # (the device copy of the entry table; the corpus owns it)
         self.d_seg_index, self.seg_index_words = d_idx.value, nw.value   # (device memory the corpus owns; None, 0: no index)
 
     @classmethod
@@ -1488,6 +1587,26 @@ class Corpus:
         finally:
             for p in (d_lv, d_st):
                 self.ctx.free(p)
+
+    def events_into(self, d_levels, n_rows, bin_len, rule, d_entries, d_starts, d_lens, d_event_levels, cap, d_count):
+        """enqueue x3_corpus_events_dev over the n_rows records Context.corpus_levels_dev wrote (device pointers); -> rc;
+        Context.events_result waits"""
+        if self._h is None:
+            raise ValueError("the corpus is closed")
+        return self.ctx.corpus_events_dev(self, d_levels, n_rows, bin_len, rule, d_entries, d_starts, d_lens, d_event_levels,
+                                          cap, d_count)
+
+    def events(self, bin_len, rule, capacity):
+        """Levels of every entry, then the runs of hot bins under `rule` as ranges, all on the device -> (entries int32,
+        starts int64, lens int32 [capacity each], count 0-d int64, event_levels uint8 [capacity, 32]), as
+        WindowSource.events; ranges(entries, starts, lens, padded_to=...) takes the tensors as they are."""
+        if not 0 < bin_len <= 0xFFFFFFFF:
+            raise ValueError("bin_len: 1 .. 2^32 - 1")
+        n_rows = int(self.levels_rows(bin_len)[-1])
+        return _events_torch(
+            self.ctx, n_rows, capacity, True,
+            lambda d_lv: self.ctx.corpus_levels_dev(self, bin_len, d_lv, n_rows, None),
+            lambda d_lv, d_e, d_s, d_l, d_el, d_c: self.events_into(d_lv, n_rows, bin_len, rule, d_e, d_s, d_l, d_el, capacity, d_c))
 
     def close(self):
         if self._h is not None:
