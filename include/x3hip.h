@@ -164,6 +164,10 @@ const char* x3_last_error(const x3_ctx* ctx);
  * x3_levels_result).
  * x3_events_dev / x3_corpus_events_dev: read-only "events_tile_rows" (rows a workgroup of the events kernels takes at a
  * time; for tests that lay rows at tile edges).
+ * x3_range_levels_dev / x3_corpus_range_levels_dev: read-only "last_range_levels_replays" (the (range, covering frame)
+ * pairs of the last call that its fix-up decoded through the reference's reader) and "last_range_levels_overflow" (its pairs
+ * that had no partial rows in the workspace: those beyond the P pairs it holds, and those whose bins end behind its rows; the
+ * fix-up decodes them where their frame passed its check, so the two need not be equal); read after x3_range_levels_result.
  * x3_corpus_build: read-only "last_corpus_record_slices" (slices of frames the last build recorded its segment index in;
  * 0 without an index).
  * x3_seg_index_build_dev: read-only "last_seg_index_irregular" (frames of the last build -- x3_corpus_build's with
@@ -842,6 +846,57 @@ int x3_corpus_events_dev(x3_ctx* ctx, const x3_corpus* corpus, const x3_level* d
                          x3_level* d_event_levels, uint64_t cap, uint64_t* d_count);
 /* Waits for the last x3_events_dev / x3_corpus_events_dev: the number of events found (what d_count holds). */
 int x3_events_result(x3_ctx* ctx, uint64_t* count);
+/* ---- RANGE LEVELS (no counterpart in the reference): the level records of ranges (entry, start, len), bins counted from
+ * each range's own start -- a second look inside events at finer bins, a zoomed overview, peak and RMS of any sample-exact
+ * cut.  The work follows the ranges (their covering frames), not the stream.
+ *   RANGE AND BINS.  Range w is positions [d_starts[w], d_starts[w] + d_lens[w]) exactly as x3_decode_ranges_dev defines
+ * them (the corpus form: relative to entry d_entries[w], as x3_corpus_ranges_dev).  Bin b of range w covers positions
+ * [start + b * bin_len, start + (b + 1) * bin_len) cut to the range.  bin_len == 0 is one bin; a length has 32 bits, so any
+ * bin_len >= 2^32 is one bin too.
+ *   ROWS.  Range w has R(w) = max(1, ceil(d_lens[w] / bin_len)) rows, 1 with bin_len == 0: the rule x3_corpus_levels_dev has
+ * for entries.  R(w) depends on the length alone, for bad ranges too.
+ *   SAMPLES COUNTED.  A sample is added to its bin when the frame that holds it has status 0 -- the status a window that is
+ * exactly that frame gets from x3_decode_windows_dev.  Any other frame adds nothing, also when some of its blocks decode
+ * cleanly.  This is x3_levels_dev's rule, not the ranges' "prefix, then zeros": n tells what was counted, and the range
+ * (0, total) at the same bin_len equals x3_levels_dev's records on the same stream, damaged frames included.
+ *   STATUS.  d_status[w] is the status of the first covering frame, in frame order, that is not 0, and 0 if there is none.
+ * A range with start > total or len > total - start is X3_ERR_BAD_ARG, and so is an entry outside the corpus; all rows of
+ * such a range are the identity {0, 0, 32767, -32768, 0, 0}.  A length of 0 with start <= total is status 0 and one identity
+ * row (start + len - 1 is never formed).
+ *   PACKED (row_stride == 0): range w's rows begin at row_off[w], the exclusive sum of ALL R(w).  d_row_offsets (required)
+ * receives row_off[0 .. n_ranges].  A range with row_off[w] + R(w) > rows_cap is X3_ERR_BAD_ARG and none of its records is
+ * written; what fits is complete, and x3_range_levels_result reports the total, so a caller grows d_levels and repeats.
+ *   PADDED (row_stride > 0): range w's rows begin at w * row_stride, and records [R(w), row_stride) of every row are the
+ * identity.  R(w) > row_stride is X3_ERR_BAD_ARG and a row of identities.  n_ranges * row_stride > rows_cap fails the call.
+ * d_row_offsets may be NULL; when given it receives w * row_stride (n_ranges + 1 words).
+ *   Every record of a range that has room is written, with identities where nothing falls.  All five quantities are
+ * integers: the records are exact whatever the order of execution; n counts modulo 2^32.  Nothing outside
+ * d_levels[0 .. rows_cap), d_status[0 .. n_ranges) and d_row_offsets[0 .. n_ranges] is written, nothing outside
+ * [d_x3, d_x3 + x3_len) is read: starts, lengths, offsets, sample offsets, index and bytes are untrusted as in
+ * x3_decode_ranges_dev.  The segment index is a hint that changes time, never results.
+ *   How: the ranges' plan and check, x3_levels_dev's consumer.  A PAIR is (range, covering frame); its stretches add to rows
+ * of the pair's own in a workspace, and only a frame whose every stretch has been proven is added to d_levels; a flagged one
+ * goes through the reference's reader.  The workspace holds P = min(n_ranges * max frames of a range, 4 * (n_frames +
+ * n_ranges)) pairs and rows_cap + P partial rows; pairs beyond either go through the reader too (time, never a result).
+ *   Asynchronous on the context's stream: one launch set, no host trip, nothing allocated after the first call of a size.
+ * The call has a pending slot and a workspace of its own: the states of x3_decode_dev, the window / ranges calls, the levels
+ * calls and the events calls are left alone.  X3_ERR_BAD_ARG with nothing enqueued for n_ranges == 0 or above 0x7FFFFFFF,
+ * rows_cap == 0 or above 0x7FFFFFFF, a NULL or misaligned pointer (d_starts, d_levels, d_row_offsets: 8 bytes; d_lens,
+ * d_entries, d_status: 4; d_row_offsets NULL only when padded), a seg_blocks or parameters that x3_decode_ranges_dev refuses,
+ * a context that is recording a graph, and (corpus form) a context on another device than the build's. */
+int x3_range_levels_dev(x3_ctx* ctx, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
+                        const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
+                        const uint64_t* d_seg_index, uint32_t seg_blocks, const uint64_t* d_starts,
+                        const uint32_t* d_lens, uint64_t n_ranges, uint64_t bin_len, uint64_t row_stride,
+                        x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status);
+/* The corpus form: range w lies in entry d_entries[w]; each result equals x3_range_levels_dev on that entry alone.  The
+ * arrays x3_corpus_events_dev wrote go in as they are (a filler is a zero-length range: one identity row, status 0). */
+int x3_corpus_range_levels_dev(x3_ctx* ctx, const x3_corpus* corpus, const uint32_t* d_entries, const uint64_t* d_starts,
+                               const uint32_t* d_lens, uint64_t n_ranges, uint64_t bin_len, uint64_t row_stride,
+                               x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status);
+/* Waits for the last x3_range_levels_dev / x3_corpus_range_levels_dev: ranges with status != 0, the first of them (n_ranges
+ * if none), its status, and the sum of all R(w) (what a packed d_levels must hold for no range to be refused). */
+int x3_range_levels_result(x3_ctx* ctx, uint64_t* n_bad, uint64_t* first_bad, int* first_bad_status, uint64_t* total_rows);
 void x3_corpus_destroy(x3_corpus* corpus);
 
 /* ------------------------------------------------------------------ multi-GPU (no reference analogue) */

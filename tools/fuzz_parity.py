@@ -13,7 +13,8 @@ Families: (e) the single-pass encoders on block_len 20 with mixed content, many 
           windows (x3_decode_windows_dev) of random streams, geometries and lengths, with damaged frames, damaged indexes
           and wild starts, against the oracle's frame verdicts (not in the default family set); (x) the same with the
           index built by x3_seg_index_build_dev on the stream as it is -- any block length and code set, damage included
-          (not in the default family set)."""
+          (not in the default family set); (r) range levels (x3_range_levels_dev): random ranges x bin lengths x layouts x
+          damage, with and without an index, GPU == tests/range_levels_ref.py (not in the default family set)."""
 import argparse, ctypes as C, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "x3-rust_amd"))
@@ -789,6 +790,135 @@ def fam_x(rng, tag):
 
 fams["c"] = fam_c
 fams["x"] = fam_x
+
+
+def fam_r(rng, tag):
+    """range levels: the records, row offsets and statuses of random ranges of a random stream -- any geometry, damaged
+    frames, a damaged or walk-built index, packed (exact, cut or roomy capacity) and padded -- against range_levels_ref on
+    the oracle's frame verdicts; the output arrays are filled with 0x5A and what no call may write must keep it"""
+    import range_levels_ref as RL
+    r = rng.random()
+    if r < 0.5:
+        p = x3hip.Params.make(20, int(rng.choice([20, 100, 500])))
+    elif r < 0.8:
+        p = x3hip.Params.make(int(rng.choice([10, 40])), int(rng.choice([25, 100, 256])))
+    else:
+        bl = int(rng.integers(2, 61))
+        codes = (0, 1, 3) if rng.random() < 0.5 else tuple(int(c) for c in rng.integers(0, 4, size=3))
+        p = x3hip.Params.make(bl, int(rng.integers(1, max(2, 8000 // bl))), codes)
+        if x3hip.lib().x3_params_validate(C.byref(p)) != 0:
+            return
+    spf = p.block_len * p.blocks_per_frame
+    n = int(rng.integers(1, 10 * spf + 100))
+    wav = content(rng, n)
+    rc, stream, _ = O.encode(wav, oparams(p))
+    if rc != 0:
+        return
+    offs = frame_offsets(stream)
+    so = [0]
+    for off in offs:
+        so.append(so[-1] + (int(stream[off + 4]) << 8 | int(stream[off + 5])))
+    if so[-1] != n:
+        return
+    bad = stream.copy()
+    if rng.random() < 0.5:
+        for _ in range(int(rng.integers(1, 4))):
+            off = offs[int(rng.integers(0, len(offs)))]
+            plen = int(stream[off + 6]) << 8 | int(stream[off + 7])
+            kind = int(rng.integers(0, 3))
+            if kind == 0 and plen > 2:      # payload bits, CRC refreshed (a decode error or other samples) or not
+                q = off + 20 + int(rng.integers(2, plen))
+                k = min(int(rng.integers(1, 12)), off + 20 + plen - q)
+                bad[q:q + k] = 0 if rng.random() < 0.5 else rng.integers(0, 256, size=k, dtype=np.uint8)
+                if rng.random() < 0.7:
+                    refresh_crcs(bad, off)
+            elif kind == 1:                 # a header byte other than the sample count
+                q = off + int(rng.choice([0, 1, 2, 3, 6, 7, 8, 12, 16, 17, 18, 19]))
+                bad[q] ^= np.uint8(1 << int(rng.integers(0, 8)))
+            elif plen > 2:                  # one payload bit
+                bad[off + 20 + int(rng.integers(0, plen))] ^= np.uint8(1 << int(rng.integers(0, 8)))
+    verdicts = _frame_verdicts(bad, offs, p)
+    so_a = np.array(so, dtype=np.uint64)
+    nr = int(rng.integers(1, 60))
+    kind = int(rng.integers(0, 4))
+    if kind == 0:      # anything
+        lens = [int(rng.choice([0, 1, 19, 20, 21, spf - 1, spf, spf + 1, int(rng.integers(0, n + 1))])) for _ in range(nr)]
+    elif kind == 1:    # short
+        lens = [int(v) for v in rng.integers(0, 64, nr)]
+    elif kind == 2:    # all long: many ranges over the same frames (pairs beyond the workspace's)
+        lens = [int(rng.integers(max(1, n - 7), n + 1)) for _ in range(nr)]
+    else:              # sliding
+        L0, hop = int(rng.integers(1, n + 1)), int(rng.integers(1, spf + 1))
+        lens = [L0] * nr
+    lens = [min(v, n) for v in lens]
+    starts = [int(rng.integers(0, n - v + 1)) for v in lens]
+    if kind == 3:
+        starts = [min(w * hop, n - L0) for w in range(nr)]
+    wild = [n, n + 1, 2 ** 63, 2 ** 64 - 1, int(rng.integers(n + 1, 2 ** 62))]
+    for _ in range(int(rng.integers(0, 3))):
+        w = int(rng.integers(0, nr))
+        starts[w] = wild[int(rng.integers(0, len(wild)))]
+    for _ in range(int(rng.integers(0, 2))):
+        lens[int(rng.integers(0, nr))] = int(rng.choice([n + 1, 2 ** 32 - 1]))
+    bin_len = int(rng.choice([0, 1, 2, 7, 20, 100, spf - 1, spf, spf + 1, 2 ** 32, int(rng.integers(1, n + 2))]))
+    rows = [RL.rows_of(v, bin_len) for v in lens]
+    if sum(rows) > 1 << 21:               # (a 2^32 - 1 length at a fine bin: bound the buffers of a trial)
+        bin_len = 1 << 20
+        rows = [RL.rows_of(v, bin_len) for v in lens]
+    layout = int(rng.integers(0, 4))
+    if layout == 0:
+        stride, cap = 0, sum(rows)
+    elif layout == 1:
+        stride, cap = 0, max(1, int(rng.integers(1, sum(rows) + 1)))
+    elif layout == 2:
+        stride, cap = 0, sum(rows) + int(rng.integers(1, 5000))
+    else:
+        stride = int(rng.choice([1, max(rows), max(1, max(rows) // 2), max(rows) + 3]))
+        cap = nr * stride + int(rng.integers(0, 3))
+    want = RL.range_levels(verdicts, so_a, starts, lens, bin_len, stride, cap)
+    d = []
+    try:
+        d_off = ctx.alloc(8 * (len(offs) + 1)); d.append(d_off)
+        ctx.upload(d_off, np.array(offs + [stream.size], dtype=np.uint64))
+        index = "walk" if rng.random() < 0.6 or p.block_len != 20 or tuple(p.codes) != (0, 1, 3) else "decode"
+        sb = int(rng.choice([0, 4, 8, 32]))
+        src = x3hip.WindowSource(ctx, bad, p, seg_blocks=sb, frame_offsets=d_off, n_frames=len(offs), index=index)
+        d.extend(src._own); src._own = []
+        assert src.total == n, (tag, "total", src.total, n)
+        if src.d_seg_index is not None and rng.random() < 0.3:   # a damaged index: a hint, never trusted
+            ne = x3hip.lib().x3_seg_index_entries(len(offs), C.byref(p), src.seg_blocks)
+            idx = ctx.download(src.d_seg_index, 8 * ne, np.uint64)
+            if ne > 1:
+                sel = rng.random(ne) < 0.2; sel[0] = False
+                idx[sel] = rng.integers(0, 1 << 49, int(sel.sum()), dtype=np.uint64)
+            ctx.upload(src.d_seg_index, idx)
+        sizes = (32 * cap, 8 * (nr + 1), 4 * nr)
+        guard = 64
+        bufs = [ctx.alloc(v + guard) for v in sizes] + [ctx.alloc(8 * nr), ctx.alloc(4 * nr)]
+        d.extend(bufs)
+        for q, v in zip(bufs[:3], sizes):
+            ctx.upload(q, np.full(v + guard, 0x5A, dtype=np.uint8))
+        ctx.upload(bufs[3], np.array(starts, dtype=np.uint64))
+        ctx.upload(bufs[4], np.array(lens, dtype=np.uint32))
+        rc = src.range_levels_into(bufs[3], bufs[4], nr, bin_len, stride, bufs[0], cap, bufs[1], bufs[2])
+        assert rc == 0, (tag, "rc", rc, ctx.last_error())
+        res = ctx.range_levels_result()
+        raw = [ctx.download(q, v + guard) for q, v in zip(bufs[:3], sizes)]
+        for name, a, v in zip(("levels", "offsets", "status"), raw, sizes):
+            assert (a[v:] == 0x5A).all(), (tag, "canary", name)
+        st = raw[2][:sizes[2]].view(np.int32)
+        assert np.array_equal(st, want[2]), (tag, "status", np.flatnonzero(st != want[2])[:8].tolist(), bin_len, stride, cap)
+        assert np.array_equal(raw[1][:sizes[1]].view(np.uint64), want[1]), (tag, "offsets")
+        got = raw[0][:sizes[0]].reshape(cap, 32)
+        assert np.array_equal(got, want[0]), (tag, "records", np.flatnonzero((got != want[0]).any(axis=1))[:8].tolist(), bin_len, stride, cap)
+        nbad = np.flatnonzero(st)
+        assert res == (0, nbad.size, int(nbad[0]) if nbad.size else nr, int(st[nbad[0]]) if nbad.size else 0, sum(rows)), (tag, res)
+    finally:
+        for q in d:
+            ctx.free(q)
+
+
+fams["r"] = fam_r
 
 
 def run(seed=1, minutes=None, trials=None, families="egdbaf", only=-1, context=None):

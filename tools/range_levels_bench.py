@@ -1,0 +1,298 @@
+#!/usr/bin/env python3
+"""Range levels (x3_range_levels_dev / x3_corpus_range_levels_dev) against the two routes a caller has without them, in one
+process, the routes alternating rep by rep; medians of --reps, host time from the first call to the last synchronised result.
+  route a   the ranges call into a sample buffer, then the five reductions in torch (min, max, sum and sum of squares in
+            int64 over an int32 copy; the count is known)
+  route b   the full levels call at that bin length (every frame of the stream, every entry of the corpus)
+on
+  config3   the stream kbench.py makes (691.2 M hydrophone samples at 192 kHz, block length 20, the encoder's index)
+  corpus_a  tools/corpus_bench.py's corpus (a): 4 000 clips of 10-15 s at 44.1 kHz
+Cases:
+  1  1 024 ranges of 0.25-4 s at 1 ms bins (192 / 44 positions); starts and lengths are whole bins, so that route a's
+     packed samples reshape to [rows, bin] and route b's records are the same bins
+  2  one 10 s range at 2 000 bins
+  3  the events of tools/events_bench.py (levels at 10 ms, its rule, --cap slots with fillers) at bin_len 0: one record an
+     event; route a masks the tails of its padded rows, route b is the levels call plus the events call's own merged records
+Every route's records are compared with == at the end of every case and the tool fails otherwise.  Kernel times: run it under
+`rocprofv3 --kernel-trace --stats -- python3 tools/range_levels_bench.py ...`.  Prints one JSON line.
+    python3 tools/range_levels_bench.py [--samples N] [--reps 10] [--warmup 2] [--cap 4096] [--cases config3,corpus] [--out file.json]"""
+import argparse, ctypes as C, json, os, sys, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "x3-rust_amd"))
+import numpy as np
+import torch
+import x3hip
+
+now = time.perf_counter
+JOIN, MIN_BINS, PAD, MAX_BINS = 5, 1, 2, 25      # tools/events_bench.py's rule
+
+
+class Source:
+    """what a case needs of a stream or a corpus: the three calls, the entries' sample counts and their rows of a levels call"""
+
+    def __init__(self, ctx, name, rate, n_samples, range_levels, ranges, levels, events, levels_rows):
+        self.ctx, self.name, self.rate, self.n_samples = ctx, name, rate, n_samples
+        self.range_levels, self.ranges, self.levels, self.events, self.levels_rows = range_levels, ranges, levels, events, levels_rows
+
+
+def records(t):
+    return t.cpu().numpy().view(x3hip.LEVEL_DTYPE).reshape(-1)
+
+
+def as_records(mn, mx, sm, sq, n):
+    out = np.zeros(len(n), dtype=x3hip.LEVEL_DTYPE)
+    out["min"], out["max"], out["sum"], out["sum_sq"], out["n"] = mn, mx, sm, sq, n
+    return out
+
+
+def timed(results, key, rep, warmup, t):
+    if rep >= warmup:
+        results.setdefault(key, []).append(t * 1e3)
+
+
+def bins_case(src, a, results, info, case, ent, starts, lens, bin_len):
+    """cases 1 and 2: starts and lengths in whole bins, packed"""
+    ctx, n = src.ctx, len(starts)
+    name = "%s_case%d" % (src.name, case)
+    rows = [v // bin_len for v in lens]
+    total_rows, total = sum(rows), sum(lens)
+    d_ent = torch.tensor(ent, dtype=torch.int32, device="cuda")
+    d_st = torch.tensor(starts, dtype=torch.int64, device="cuda")
+    d_ln = torch.tensor(lens, dtype=torch.int32, device="cuda")
+    lv = torch.empty((total_rows, 32), dtype=torch.uint8, device="cuda")
+    off, off2 = (torch.empty(n + 1, dtype=torch.int64, device="cuda") for _ in range(2))
+    st, st2 = (torch.empty(n, dtype=torch.int32, device="cuda") for _ in range(2))
+    buf = torch.empty(total, dtype=torch.int16, device="cuda")
+    rf = src.levels_rows(bin_len)
+    full_rows = int(rf[-1])
+    full = torch.empty((full_rows, 32), dtype=torch.uint8, device="cuda") if 64 * full_rows < a.levels_bytes else None
+    torch.cuda.synchronize()
+    red = None
+    for rep in range(a.warmup + a.reps):
+        t0 = now()
+        assert src.range_levels(d_ent.data_ptr(), d_st.data_ptr(), d_ln.data_ptr(), n, bin_len, 0, lv.data_ptr(), total_rows,
+                                off.data_ptr(), st.data_ptr()) == 0, ctx.last_error()
+        r = ctx.range_levels_result()
+        t1 = now()
+        assert r == (0, 0, n, 0, total_rows), r
+        assert src.ranges(d_ent.data_ptr(), d_st.data_ptr(), d_ln.data_ptr(), n, 0, buf.data_ptr(), total, off2.data_ptr(),
+                          st2.data_ptr()) == 0, ctx.last_error()
+        r = ctx.decode_ranges_result()
+        t2 = now()
+        assert r[:2] == (0, 0), r
+        x = buf.view(total_rows, bin_len)
+        w = x.to(torch.int32)
+        red = (x.min(1).values, x.max(1).values, w.sum(1, dtype=torch.int64), (w * w).sum(1, dtype=torch.int64))
+        torch.cuda.synchronize()
+        t3 = now()
+        timed(results, name + "_range_levels", rep, a.warmup, t1 - t0)
+        timed(results, name + "_route_a", rep, a.warmup, t3 - t1)
+        timed(results, name + "_route_a_ranges", rep, a.warmup, t2 - t1)
+        timed(results, name + "_route_a_torch", rep, a.warmup, t3 - t2)
+        if full is not None:
+            t4 = now()
+            assert src.levels(bin_len, full.data_ptr(), full_rows) == 0, ctx.last_error()
+            assert ctx.levels_result()[0] == 0
+            timed(results, name + "_route_b", rep, a.warmup, now() - t4)
+    got = records(lv)
+    want_a = as_records(*(t.cpu().numpy() for t in red), np.full(total_rows, bin_len, dtype=np.uint32))
+    same = np.array_equal(got, want_a) and not st.cpu().numpy().any()
+    if full is not None:
+        frec = records(full)
+        pick = np.concatenate([int(rf[e]) + s // bin_len + np.arange(k) for e, s, k in zip(ent, starts, rows)])
+        same = same and np.array_equal(got, frec[pick])
+    if not same:
+        raise SystemExit("%s: the routes' records differ" % name)
+    info[name] = {"ranges": n, "bin_len": bin_len, "rows": total_rows, "samples": total, "levels_rows": full_rows,
+                  "route_b": full is not None, "equal": bool(same),
+                  "replays": ctx.get_option("last_range_levels_replays"), "overflow": ctx.get_option("last_range_levels_overflow")}
+
+
+def events_case(src, a, results, info, bin_len):
+    """case 3: the slots of an events call, fillers included, at bin_len 0"""
+    ctx, cap, name = src.ctx, a.cap, src.name + "_case3"
+    stride = MAX_BINS * bin_len
+    rf = src.levels_rows(bin_len)
+    n_rows = int(rf[-1])
+    full = torch.empty((n_rows, 32), dtype=torch.uint8, device="cuda")
+    ent, st, ln = (torch.empty(cap, dtype=dt, device="cuda") for dt in (torch.int32, torch.int64, torch.int32))
+    ent.zero_()
+    cnt = torch.zeros((), dtype=torch.int64, device="cuda")
+    ev_lv, ev_lv2, lv = (torch.empty((cap, 32), dtype=torch.uint8, device="cuda") for _ in range(3))
+    status, status2 = (torch.empty(cap, dtype=torch.int32, device="cuda") for _ in range(2))
+    off = torch.empty(cap + 1, dtype=torch.int64, device="cuda")
+    buf = torch.empty((cap, stride), dtype=torch.int16, device="cuda")
+    torch.cuda.synchronize()
+    assert src.levels(bin_len, full.data_ptr(), n_rows) == 0 and ctx.levels_result()[0] == 0
+    rec = records(full)
+    q = 100.0 * (1.0 - min(0.002, cap / (4.0 * n_rows)))
+    peak_min = int(min(max(np.percentile(np.maximum(rec["max"], -rec["min"])[rec["n"] != 0], q) + 1, 1), 32768))
+    rule = x3hip.EventRule.make(0, peak_min, JOIN, MIN_BINS, PAD, MAX_BINS)
+    assert src.events(full.data_ptr(), n_rows, bin_len, rule, ent.data_ptr(), st.data_ptr(), ln.data_ptr(), ev_lv.data_ptr(), cap,
+                      cnt.data_ptr()) == 0
+    rc, found = ctx.events_result()
+    assert rc == 0 and 0 < found <= cap, (rc, found)
+    col = torch.arange(stride, device="cuda")[None, :]
+    red = None
+    for rep in range(a.warmup + a.reps):
+        t0 = now()
+        assert src.range_levels(ent.data_ptr(), st.data_ptr(), ln.data_ptr(), cap, 0, 0, lv.data_ptr(), cap, off.data_ptr(),
+                                status.data_ptr()) == 0, ctx.last_error()
+        r = ctx.range_levels_result()
+        t1 = now()
+        assert r == (0, 0, cap, 0, cap), r
+        assert src.ranges(ent.data_ptr(), st.data_ptr(), ln.data_ptr(), cap, stride, buf.data_ptr(), cap * stride, None,
+                          status2.data_ptr()) == 0, ctx.last_error()
+        r = ctx.decode_ranges_result()
+        t2 = now()
+        assert r[:2] == (0, 0), r
+        mask = col < ln[:, None]
+        w = buf.to(torch.int32)
+        red = (torch.where(mask, w, 32767).min(1).values, torch.where(mask, w, -32768).max(1).values,
+               w.sum(1, dtype=torch.int64), (w * w).sum(1, dtype=torch.int64))
+        torch.cuda.synchronize()
+        t3 = now()
+        assert src.levels(bin_len, full.data_ptr(), n_rows) == 0
+        assert src.events(full.data_ptr(), n_rows, bin_len, rule, ent.data_ptr(), st.data_ptr(), ln.data_ptr(), ev_lv2.data_ptr(),
+                          cap, cnt.data_ptr()) == 0
+        assert ctx.events_result()[0] == 0 and ctx.levels_result()[0] == 0
+        t4 = now()
+        timed(results, name + "_range_levels", rep, a.warmup, t1 - t0)
+        timed(results, name + "_route_a", rep, a.warmup, t3 - t1)
+        timed(results, name + "_route_a_ranges", rep, a.warmup, t2 - t1)
+        timed(results, name + "_route_a_torch", rep, a.warmup, t3 - t2)
+        timed(results, name + "_route_b", rep, a.warmup, t4 - t3)
+    got = records(lv)
+    want_a = as_records(*(t.cpu().numpy() for t in red), ln.cpu().numpy().view(np.uint32))
+    same = np.array_equal(got, want_a) and np.array_equal(got, records(ev_lv)) and np.array_equal(got, records(ev_lv2)) and \
+        not status.cpu().numpy().any()
+    if not same:
+        raise SystemExit("%s: the routes' records differ" % name)
+    info[name] = {"ranges": cap, "events": int(found), "bin_len": 0, "events_bin_len": bin_len, "peak_min": peak_min,
+                  "samples": int(ln.sum().item()), "equal": bool(same),
+                  "replays": ctx.get_option("last_range_levels_replays"), "overflow": ctx.get_option("last_range_levels_overflow")}
+
+
+def cases(src, a, results, info):
+    rng = np.random.default_rng(11)
+    ms = src.rate // 1000                    # 1 ms in whole positions: 192, 44
+    ns = src.n_samples
+    ent, starts, lens = [], [], []
+    for _ in range(1024):
+        e = int(rng.integers(0, len(ns)))
+        k = int(rng.integers(250, 4001))     # 0.25 - 4 s in bins of 1 ms
+        k = min(k, ns[e] // ms)
+        ent.append(e)
+        lens.append(k * ms)
+        starts.append(int(rng.integers(0, ns[e] // ms - k + 1)) * ms)
+    bins_case(src, a, results, info, 1, ent, starts, lens, ms)
+    e = int(np.argmax(ns))
+    bl = (10 * src.rate) // 2000             # 10 s in 2 000 bins: 960, 220
+    s0 = (ns[e] // bl - 2000) // 2 * bl
+    bins_case(src, a, results, info, 2, [e], [s0], [2000 * bl], bl)
+    events_case(src, a, results, info, src.rate // 100)
+    torch.cuda.empty_cache()
+
+
+def config3(ctx, a, results, info):
+    lib = x3hip.lib()
+    n, p = a.samples, x3hip.Params.default()
+    wav = torch.empty(n + 32, dtype=torch.int16, device="cuda")
+    ctx.synth_dev(2, 0x58330003, 0, n, wav.data_ptr())
+    ctx.sync()
+    F, cap = lib.x3_num_frames(n, C.byref(p)), lib.x3_encode_bound(n, C.byref(p))
+    ne = lib.x3_seg_index_entries(F, C.byref(p), 32)
+    x = torch.empty(cap + 64, dtype=torch.uint8, device="cuda")
+    off, so = (torch.empty(F + 1, dtype=torch.int64, device="cuda") for _ in range(2))
+    idx = torch.zeros(ne, dtype=torch.int64, device="cuda")
+    assert ctx.encode_dev_seg(wav.data_ptr(), n, p, x.data_ptr(), cap, idx.data_ptr(), 32, 0, off.data_ptr()) == 0
+    rc, pos, _ = ctx.encode_result()
+    assert rc == 0
+    del wav
+    assert ctx.sample_offsets_dev(x.data_ptr(), pos, off.data_ptr(), F, so.data_ptr()) == 0
+    ctx.sync()
+    s = (x.data_ptr(), pos, off.data_ptr(), so.data_ptr(), F, p)
+    src = Source(
+        ctx, "config3", 192_000, [n],
+        lambda d_e, d_s, d_l, k, bl, stride, d_lv, c, d_off, d_st: ctx.range_levels_dev(*s, d_s, d_l, k, bl, stride, d_lv, c, d_off,
+                                                                                        d_st, idx.data_ptr(), 32),
+        lambda d_e, d_s, d_l, k, stride, d_out, oc, d_off, d_st: ctx.decode_ranges_dev(*s, d_s, d_l, k, stride, d_out, oc, 0, d_off,
+                                                                                       d_st, idx.data_ptr(), 32),
+        lambda bl, d_lv, rows: ctx.levels_dev(*s, bl, d_lv, rows, None, idx.data_ptr(), 32),
+        lambda d_lv, rows, bl, rule, d_e, d_s, d_l, d_el, c, d_c: ctx.events_dev(d_lv, rows, bl, so.data_ptr() + 8 * F, rule, d_s, d_l,
+                                                                                d_el, c, d_c),
+        lambda bl: np.array([0, -(-n // bl)], dtype=np.uint64))
+    cases(src, a, results, info)
+
+
+def corpus_a(ctx, a, results, info):
+    lib = x3hip.lib()
+    rng = np.random.default_rng(7)
+    ns = [int(v) for v in rng.integers(441_000, 661_500 + 1, 4000)]
+    n_clips, total = len(ns), int(sum(ns))
+    p = x3hip.Params.default()
+    spf = p.block_len * p.blocks_per_frame
+    base = np.concatenate([[0], np.cumsum(ns)[:-1]]).astype(np.int64)
+    so, sn, first = [], [], []
+    for c, n in enumerate(ns):
+        first.append(len(so))
+        for s in range(0, n, spf):
+            so.append(int(base[c]) + s)
+            sn.append(min(spf, n - s))
+    F = len(so)
+    first.append(F)
+    cap = sum(lib.x3_encode_bound(n, C.byref(p)) + 2 for n in ns) + 64
+    d_wav, d_x3, d_off = ctx.alloc(2 * total), ctx.alloc(cap), ctx.alloc(8 * (F + 1))
+    ctx.synth_dev(x3hip.SYNTH_HYDROPHONE, 0x5336, 0, total, d_wav)
+    assert ctx.encode_frames_dev(d_wav, so, sn, p, d_x3, cap, 0, d_off) == 0
+    rc, pos, _ = ctx.encode_result()
+    assert rc == 0
+    ctx.free(d_wav)
+    fo = ctx.download(d_off, 8 * (F + 1), np.uint64)
+    offs = [int(fo[first[c]]) for c in range(n_clips)]
+    lens = [int(fo[first[c + 1]]) - offs[c] for c in range(n_clips)]
+    corpus = x3hip.Corpus(ctx, (d_x3, pos), offs, lens, seg_blocks=32)
+    src = Source(
+        ctx, "corpus_a", 44_100, ns,
+        lambda d_e, d_s, d_l, k, bl, stride, d_lv, c, d_o, d_st: corpus.range_levels_into(d_e, d_s, d_l, k, bl, stride, d_lv, c, d_o, d_st),
+        lambda d_e, d_s, d_l, k, stride, d_out, oc, d_o, d_st: corpus.ranges_into(d_e, d_s, d_l, k, stride, d_out, oc, 0, d_o, d_st),
+        lambda bl, d_lv, rows: ctx.corpus_levels_dev(corpus, bl, d_lv, rows),
+        lambda d_lv, rows, bl, rule, d_e, d_s, d_l, d_el, c, d_c: corpus.events_into(d_lv, rows, bl, rule, d_e, d_s, d_l, d_el, c, d_c),
+        lambda bl: corpus.levels_rows(bl))
+    cases(src, a, results, info)
+    corpus.close()
+    for q in (d_x3, d_off):
+        ctx.free(q)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--samples", type=int, default=691_200_000)
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--cap", type=int, default=4096)
+    ap.add_argument("--cases", default="config3,corpus")
+    ap.add_argument("--levels-bytes", type=float, default=16e9, help="route b runs where its records and workspace fit in this")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    torch.cuda.init()
+    ctx = x3hip.Context(0)
+    results, info = {}, {}
+    if "config3" in a.cases:
+        config3(ctx, a, results, info)
+    if "corpus" in a.cases:
+        corpus_a(ctx, a, results, info)
+    out = {"samples": a.samples, "reps": a.reps, "cases": info,
+           "ms_median": {k: round(float(np.median(v)), 4) for k, v in results.items()},
+           "ms_min": {k: round(float(np.min(v)), 4) for k, v in results.items()},
+           "ms_max": {k: round(float(np.max(v)), 4) for k, v in results.items()}}
+    line = json.dumps(out, sort_keys=True)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()

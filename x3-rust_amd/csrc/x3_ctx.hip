@@ -295,7 +295,7 @@ extern "C" void x3_ctx_destroy(x3_ctx* c) {
   if (c->fcache) x3_reader_close(c->fcache);
   for (DevBuf* b : {&c->in, &c->out, &c->in_more[0], &c->in_more[1], &c->out_more[0], &c->out_more[1], &c->frame_bytes, &c->frame_off, &c->dec_status, &c->dec_cstatus, &c->dec_meta, &c->wav_off,
                     &c->seg_crc, &c->desc, &c->idx_cand, &c->idx_keys, &c->idx_vals, &c->idx_J, &c->idx_S,
-                    &c->idx_L, &c->idx_sum, &c->idx_wg, &c->idx_sorted, &c->idx_scan, &c->dense_list, &c->lb_desc, &c->src_tab, &c->win_ws, &c->lev_ws, &c->ev_ws, &c->st_walk, &c->st_ws,
+                    &c->idx_L, &c->idx_sum, &c->idx_wg, &c->idx_sorted, &c->idx_scan, &c->dense_list, &c->lb_desc, &c->src_tab, &c->win_ws, &c->lev_ws, &c->ev_ws, &c->rlev_ws, &c->st_walk, &c->st_ws,
                     &c->st_one, &c->st_row})
     if (b->p) (void)x3_dfree(b->p);
   for (auto& t : c->timers) {
@@ -476,6 +476,8 @@ extern "C" int x3_ctx_get_option(const x3_ctx* c, const char* name, long long* v
   else if (n == "last_decode_replays") *value = (long long)c->last_decode_replays;   // read-only: frames of the last decode the reference's reader re-decoded
   else if (n == "last_window_replays") *value = (long long)c->last_window_replays;   // read-only: (window, frame) pairs of the last x3_decode_windows_dev re-decoded
   else if (n == "last_levels_replays") *value = (long long)c->last_levels_replays;   // read-only: frames of the last levels call the reference's reader decoded (after x3_levels_result)
+  else if (n == "last_range_levels_replays") *value = (long long)c->last_range_levels_replays;     // read-only: (range, frame) pairs of the last range-levels call the reference's reader decoded (after x3_range_levels_result)
+  else if (n == "last_range_levels_overflow") *value = (long long)c->last_range_levels_overflow;   // read-only: ... its pairs that had no partial rows in the workspace
   else if (n == "events_tile_rows") *value = X3_EVENTS_TILE_ROWS;   // read-only: rows a workgroup of the events kernels takes at a time (x3_events_kernel.h)
   else if (n == "last_corpus_record_slices") *value = (long long)c->last_corpus_slices;   // read-only: slices the last x3_corpus_build recorded its index in
   else if (n == "enc_gen_in_use") *value = c->last_enc_gen;                          // read-only: 3 = wave encoder, 2 = second generation, 1 = the general kernel in one pass (look-back), 0 = two passes

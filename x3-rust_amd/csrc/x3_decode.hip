@@ -11,6 +11,7 @@
 #include "x3_seg_index_kernel.h"
 #include "x3_levels_kernel.h"
 #include "x3_events_kernel.h"
+#include "x3_range_levels_kernel.h"
 
 // ------------------------------------------------------------------------------------------------
 // decode
@@ -2120,5 +2121,151 @@ extern "C" int x3_events_result(x3_ctx* c, uint64_t* count) {
   const int rc = pending_fetch(c, c->events, c->ev_ws, &h, sizeof h);
   if (rc) return rc;
   if (count) *count = h.count;
+  return X3_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// range levels: the level records of (entry, start, len) ranges (x3_range_levels_kernel.h)
+// ------------------------------------------------------------------------------------------------
+// the argument checks x3_range_levels_dev and x3_corpus_range_levels_dev share
+static bool range_levels_args_ok(const x3_ctx* c, const uint64_t* d_starts, const uint32_t* d_lens, uint64_t n_ranges,
+                                 uint64_t row_stride, const x3_level* d_levels, uint64_t rows_cap, const uint64_t* d_row_offsets,
+                                 const int32_t* d_status) {
+  if (!d_starts || !d_lens || !d_levels || !d_status || c->capturing) return false;
+  if (n_ranges == 0 || n_ranges > 0x7FFFFFFFull || rows_cap == 0 || rows_cap > 0x7FFFFFFFull) return false;
+  if (row_stride ? row_stride > rows_cap / n_ranges : !d_row_offsets) return false;
+  return ((reinterpret_cast<uintptr_t>(d_starts) | reinterpret_cast<uintptr_t>(d_levels) | reinterpret_cast<uintptr_t>(d_row_offsets)) & 7u) == 0 &&
+         ((reinterpret_cast<uintptr_t>(d_lens) | reinterpret_cast<uintptr_t>(d_status)) & 3u) == 0;
+}
+
+// The pairs (range, covering frame) the workspace holds: all a call can have, or four times what disjoint ranges need
+// (n_frames + n_ranges: sliding windows with up to 75 % overlap fit).  Pairs beyond it are the fix-up's: time, not results.
+uint64_t range_levels_pairs(uint64_t n, uint64_t F, uint64_t max_frames) {
+  return std::min<uint64_t>(n * max_frames, 4 * (F + n));   // (n < 2^31, max_frames <= F < 2^31: no wrap)
+}
+
+// The workspace (RLevWs, x3_internal.h): per range the plan, the two scans, the rows that have room, the plan's starts; per
+// frame the verdicts; per pair its cut, the scan of the bin counts; the partial rows; replay scratch; the summary
+size_t range_levels_carve(char* base, uint64_t n, uint64_t F, uint64_t P, uint64_t rows_cap, uint64_t fix_waves,
+                          uint32_t scratch_per, RLevWs* w) {
+  BlockCarver k{base, 0};
+  w->plan = k.take<X3WinPlan>(n);
+  w->cov_off = k.take<unsigned long long>(n + 1);
+  w->row_off = k.take<unsigned long long>(n + 1);
+  w->erows = k.take<uint32_t>(n);
+  w->gstart = k.take<uint64_t>(n);
+  w->fst = k.take<int32_t>(F);
+  w->pairs = k.take<X3RLevPair>(P);
+  w->prow = k.take<unsigned long long>(P + 1);
+  w->rows = k.take<x3_level>(rows_cap + P);
+  w->scratch = k.take<int16_t>(std::max<uint64_t>(fix_waves, 4) * scratch_per);
+  w->sum = k.take<X3RLevSummary>(1, 1);
+  return k.at;
+}
+
+// The launch set of a range-levels call behind its plan step: plan(grid, plan, gstart, sum) enqueues the ranges' plan kernel
+// and returns the starts the later kernels read (the caller's, or the plan's gstart), as in windows_launch.
+template <class Plan>
+static int range_levels_launch(x3_ctx* c, const FrameSource& s, const uint32_t* d_lens, uint64_t n, uint64_t bin_len,
+                               uint64_t row_stride, x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets,
+                               int32_t* d_status, Plan plan_step) {
+  HIPCHK(c, hipSetDevice(c->device));
+  const uint64_t P = range_levels_pairs(n, s.F, s.max_frames), cap = rows_cap + P;
+  const uint32_t scratch_per = levels_scratch_per(s.dp.block_len);
+  const uint64_t fix_waves = levels_fix_waves(n, scratch_per);
+  RLevWs w;
+  int rc;
+  if ((rc = ensure(c, c->rlev_ws, range_levels_carve(nullptr, n, s.F, P, rows_cap, fix_waves, scratch_per, &w)))) return rc;
+  range_levels_carve((char*)c->rlev_ws.p, n, s.F, P, rows_cap, fix_waves, scratch_per, &w);
+  // grids: the counts are on the device and every kernel walks them grid-stride.  What a range has on average is at most
+  // rows_cap / n rows (or the stride) of bin_len positions: the caller's words, possibly far above what is drawn, so a range
+  // covers no more frames than the stream (or the longest entry) has and a call no more pairs than P.
+  const uint64_t rows_hint = row_stride ? row_stride : std::max<uint64_t>(rows_cap / n, 1);
+  const uint64_t len_hint = bin_len && bin_len <= 0xFFFFFFFFull / rows_hint ? rows_hint * bin_len : 0xFFFFFFFFull;
+  const uint64_t frames_per = std::max<uint64_t>(1, std::min(len_hint / (s.spf ? s.spf : 1) + 2, s.max_frames));
+  const uint64_t cov_hint = std::min(n * frames_per, P), item_hint = std::min<uint64_t>(cov_hint, 256ull * X3W_GRID_LIMIT) * s.nseg;
+  // the caller's records: padded, all n * stride are written; packed, a range has no more rows than the frames it can cover
+  // hold bins (one with bin_len 0 or above any length), so a roomy rows_cap does not size the prep, init and merge grids
+  const uint64_t drawn_rows = row_stride ? rows_hint
+                              : bin_len && bin_len <= 0xFFFFFFFFull ? std::min(rows_hint, frames_per * (s.spf ? s.spf : 1) / bin_len + 1) : 1;
+  const uint64_t rec_hint = std::min(n * drawn_rows, rows_cap);
+  const uint64_t* d_starts = plan_step(dim3(grid_for(n, 256)), w.plan, w.gstart, &w.sum->w);
+  hipLaunchKernelGGL(x3_range_levels_scan_kernel, dim3(1), dim3(1024), 0, c->stream, w.plan, n, d_lens, bin_len, row_stride, rows_cap,
+                     w.cov_off, w.row_off, w.erows, d_row_offsets, w.sum);
+  hipLaunchKernelGGL(x3_window_check_kernel, dim3(grid_for(cov_hint, 4)), dim3(256), 0, c->stream, s.d_x3, s.x3_len, s.d_frame_offsets,
+                     s.d_sample_offsets, (const X3WinPlan*)w.plan, n, (const unsigned long long*)w.cov_off, w.fst);
+  hipLaunchKernelGGL(x3_range_levels_prep_kernel, dim3(grid_for(std::max(cov_hint, rec_hint), 256)), dim3(256), 0, c->stream,
+                     s.d_sample_offsets, d_starts, d_lens, (const X3WinPlan*)w.plan, n, (const unsigned long long*)w.cov_off,
+                     (const unsigned long long*)w.row_off, (const uint32_t*)w.erows, bin_len, row_stride, rows_cap, P,
+                     (const int32_t*)w.fst, w.pairs, d_levels);
+  hipLaunchKernelGGL(x3_range_levels_pair_scan_kernel, dim3(1), dim3(1024), 0, c->stream, (const X3RLevPair*)w.pairs,
+                     (const unsigned long long*)w.cov_off, n, P, cap, w.prow, w.sum);
+  hipLaunchKernelGGL(x3_range_levels_init_kernel, dim3(grid_for(rec_hint + cov_hint, 256)), dim3(256), 0, c->stream,
+                     (const unsigned long long*)w.cov_off, n, P, cap, (const unsigned long long*)w.prow, w.rows);
+  hipLaunchKernelGGL(x3_range_levels_accum_kernel, dim3(grid_for(item_hint, 256)), dim3(256), 0, c->stream, s.d_x3, s.x3_len,
+                     s.d_frame_offsets, s.dp, s.idx, s.seg_blocks, s.nseg, bin_len, (const unsigned long long*)w.cov_off, n, P, cap,
+                     (const X3RLevPair*)w.pairs, (const unsigned long long*)w.prow, w.rows, w.fst);
+  hipLaunchKernelGGL(x3_range_levels_fixup_kernel, dim3((unsigned)((fix_waves + 3) / 4)), dim3(256), 0, c->stream, s.d_x3,
+                     s.d_frame_offsets, s.d_sample_offsets, d_starts, d_lens, (const X3WinPlan*)w.plan, n, s.dp, bin_len,
+                     (const unsigned long long*)w.cov_off, (const unsigned long long*)w.row_off, (const uint32_t*)w.erows,
+                     row_stride, P, cap, (const unsigned long long*)w.prow, (const int32_t*)w.fst, d_levels, d_status, w.scratch,
+                     scratch_per, w.sum);
+  hipLaunchKernelGGL(x3_range_levels_merge_kernel, dim3(grid_for(rec_hint + cov_hint, 256)), dim3(256), 0, c->stream,
+                     (const X3RLevPair*)w.pairs, (const unsigned long long*)w.cov_off, n, P, cap, (const unsigned long long*)w.prow,
+                     (const unsigned long long*)w.row_off, (const uint32_t*)w.erows, row_stride, (const x3_level*)w.rows,
+                     (const int32_t*)w.fst, d_levels);
+  HIPCHK(c, hipGetLastError());
+  c->range_levels.pending = true;
+  c->range_levels.count = n;
+  c->range_levels.sum_off = (size_t)((char*)w.sum - (char*)c->rlev_ws.p);
+  return X3_OK;
+}
+
+extern "C" int x3_range_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
+                                   const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
+                                   const uint64_t* d_seg_index, uint32_t seg_blocks, const uint64_t* d_starts,
+                                   const uint32_t* d_lens, uint64_t n_ranges, uint64_t bin_len, uint64_t row_stride,
+                                   x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status) {
+  if (!c || !range_levels_args_ok(c, d_starts, d_lens, n_ranges, row_stride, d_levels, rows_cap, d_row_offsets, d_status))
+    return X3_ERR_BAD_ARG;
+  FrameSource s;
+  const int rc = stream_source(d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, p, d_seg_index, seg_blocks, &s);
+  if (rc) return rc;
+  return range_levels_launch(c, s, d_lens, n_ranges, bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status,
+                             [&](dim3 grid, X3WinPlan* plan, uint64_t*, X3WinSummary* sum) -> const uint64_t* {
+                               hipLaunchKernelGGL(x3_range_plan_kernel, grid, dim3(256), 0, c->stream, d_sample_offsets, n_frames,
+                                                  d_starts, d_lens, n_ranges, plan, sum);
+                               return d_starts;
+                             });
+}
+
+extern "C" int x3_corpus_range_levels_dev(x3_ctx* c, const x3_corpus* k, const uint32_t* d_entries, const uint64_t* d_starts,
+                                          const uint32_t* d_lens, uint64_t n_ranges, uint64_t bin_len, uint64_t row_stride,
+                                          x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status) {
+  if (!c || !k || !d_entries || (reinterpret_cast<uintptr_t>(d_entries) & 3u)) return X3_ERR_BAD_ARG;
+  if (!range_levels_args_ok(c, d_starts, d_lens, n_ranges, row_stride, d_levels, rows_cap, d_row_offsets, d_status))
+    return X3_ERR_BAD_ARG;
+  FrameSource s;
+  const int rc = corpus_source(c, k, "x3_corpus_range_levels_dev", &s);
+  if (rc) return rc;
+  return range_levels_launch(c, s, d_lens, n_ranges, bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status,
+                             [&](dim3 grid, X3WinPlan* plan, uint64_t* gstart, X3WinSummary* sum) -> const uint64_t* {
+                               hipLaunchKernelGGL(x3_corpus_range_plan_kernel, grid, dim3(256), 0, c->stream, k->d_ent, k->n,
+                                                  s.d_sample_offsets, s.F, d_entries, d_starts, d_lens, n_ranges, plan, gstart,
+                                                  sum);
+                               return gstart;
+                             });
+}
+
+extern "C" int x3_range_levels_result(x3_ctx* c, uint64_t* n_bad, uint64_t* first_bad, int* first_bad_status,
+                                      uint64_t* total_rows) {
+  if (!c) return X3_ERR_BAD_ARG;
+  X3RLevSummary h{{0, 0, 0, 0}, 0};
+  const int rc = pending_fetch(c, c->range_levels, c->rlev_ws, &h, sizeof h);
+  if (rc) return rc;
+  c->last_range_levels_replays = h.w.replays;
+  c->last_range_levels_overflow = h.overflow;
+  first_bad_of(h.w.n_bad, h.w.first, c->range_levels.count, n_bad, first_bad, first_bad_status);
+  if (total_rows) *total_rows = h.w.total;
   return X3_OK;
 }

@@ -154,6 +154,7 @@ struct x3_ctx {
   DevBuf idx_wg, idx_sorted, idx_scan;  // ... of its fast path: candidates per scanning workgroup, in order, the scans
   DevBuf lev_ws;   // x3_levels_dev / x3_corpus_levels_dev: verdicts, plans, the frames' partial rows, replay scratch, summary (x3_levels_kernel.h)
   DevBuf ev_ws;    // x3_events_dev / x3_corpus_events_dev: row flags, tile totals, run tables, piece scan, summary, row prefix (x3_events_kernel.h)
+  DevBuf rlev_ws;  // x3_range_levels_dev / x3_corpus_range_levels_dev: plans, scans, verdicts, pairs, their partial rows, replay scratch, summary (x3_range_levels_kernel.h)
   DevBuf win_ws;   // x3_decode_windows_dev: plans, scans, per-frame verdicts, replay scratch, summary (x3_decode_window_kernel.h)
   // x3_decode_streams_dev (x3_streams_kernel.h): the call's block (the segmented walk's workspace and the call's own words:
   // streams_carve, x3_decode.hip), the int16 rows of a float32 call, an entry the general walk takes (aligned copy, int16 row)
@@ -189,6 +190,7 @@ struct x3_ctx {
   } windows;               // x3_decode_windows_dev / x3_decode_ranges_dev and their corpus forms: win_ws
   PendingCall levels;      // x3_levels_dev / x3_corpus_levels_dev: lev_ws
   PendingCall events;      // x3_events_dev / x3_corpus_events_dev: ev_ws (count: the call's cap)
+  PendingCall range_levels;   // x3_range_levels_dev / x3_corpus_range_levels_dev: rlev_ws (count: the ranges)
   bool force_two_pass = false;
   // Contexts that encode concurrently on ONE GPU (the file pipeline's workers) share this gate: the single-pass encoders
   // are persistent grids whose workgroups wait for each other, so only one of them may be in flight on a device.  A
@@ -210,6 +212,7 @@ struct x3_ctx {
   unsigned long long last_decode_replays = 0, decode_replays = 0;
   unsigned long long last_window_replays = 0;   // (window, covering frame) pairs x3_window_fixup_kernel re-decoded
   unsigned long long last_levels_replays = 0;   // frames x3_levels_fixup_kernel decoded through the reference's reader
+  unsigned long long last_range_levels_replays = 0, last_range_levels_overflow = 0;   // pairs x3_range_levels_fixup_kernel decoded; pairs without partial rows
   unsigned long long last_corpus_slices = 0;    // x3_corpus_build: slices of frames its recording decode took (option)
   struct LastEnc {
     const int16_t* d_wav; x3_batch b; x3_params p; uint64_t spf; uint8_t* d_out; uint64_t out_cap, start_pos; uint64_t* d_off;
@@ -476,6 +479,19 @@ struct EvWs {
   X3EvSummary* sum; unsigned long long* row_first;
 };
 X3_INTERNAL size_t events_carve(char* base, uint64_t n_rows, uint64_t n_ent, EvWs* w);
+// ... and of a range-levels call (rlev_ws; x3_range_levels_kernel.h): n ranges over F frames, P pairs (range, covering
+// frame) with rows_cap + P partial rows, `fix_waves` waves of the fix-up with `scratch_per` samples each
+struct X3RLevPair;
+struct X3RLevSummary;
+struct RLevWs {
+  X3WinPlan* plan; unsigned long long* cov_off; unsigned long long* row_off; uint32_t* erows; uint64_t* gstart;   // per range (the scans: n + 1 words)
+  int32_t* fst;                                                                                                  // per frame
+  X3RLevPair* pairs; unsigned long long* prow; x3_level* rows;   // per pair (prow: P + 1 words); the partial rows
+  int16_t* scratch; X3RLevSummary* sum;
+};
+X3_INTERNAL uint64_t range_levels_pairs(uint64_t n, uint64_t F, uint64_t max_frames);
+X3_INTERNAL size_t range_levels_carve(char* base, uint64_t n, uint64_t F, uint64_t P, uint64_t rows_cap, uint64_t fix_waves,
+                                      uint32_t scratch_per, RLevWs* w);
 // ---- x3_files.hip (x3_reader.h)
 // the RIFF/WAVE header parser of x3_wav_to_x3a on an open file, for the sanitised host tests (tests/host_cpp/fuzz_host_parsers.cpp)
 X3_INTERNAL int x3_wav_parse_fd_for_tests(int fd, uint64_t file_len, uint32_t* sample_rate, uint16_t* channels, uint16_t* bits,

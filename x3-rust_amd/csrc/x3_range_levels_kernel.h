@@ -1,0 +1,323 @@
+// x3_range_levels_kernel.h -- RANGE LEVELS: the level records (x3_levels_kernel.h) of (entry, start, len) ranges of a stream
+// (x3_range_levels_dev) or a corpus (x3_corpus_range_levels_dev), bins counted from each range's own start (DESIGN.md
+// section 18).
+//
+// The work follows the ranges, as the window and ranges calls' does: the plan is theirs (x3_range_plan_kernel /
+// x3_corpus_range_plan_kernel), the check is theirs (x3_window_check_kernel), the decode is x3w_stretch with the levels'
+// consumer (X3LevBinner: a bin in registers, atomics at a bin boundary and at the stretch's end, no store per sample).
+//
+// ROLLBACK PER PAIR.  A pair is (range, covering frame).  A frame whose status is not 0 adds nothing, so a stretch never adds
+// to the caller's records: it adds to the PAIR'S OWN partial rows in the workspace -- per pair, not per frame, because bins are
+// counted from the range's start and a frame under two ranges has two sets of bins.  The frame's word is shared by every
+// range that covers it: a stretch that fails flags it for all of them.  The merge kernel adds a pair's rows to the caller's
+// records only when the word is still X3D_OK behind the accumulate kernel; a flagged frame goes through the reference's
+// reader in the fix-up, per pair, once for its status and, if that is 0, once more straight into the caller's records.
+//
+//  x3_range_plan_kernel / x3_corpus_range_plan_kernel -- as they are
+//  x3_range_levels_scan_kernel   -- one workgroup: rows per range R(w), their exclusive scan (row_off, also to the caller),
+//      the verdict on ranges without room ({0 frames, X3D_BAD_ARG}, erows[w] = 0), then the scan of the covering frames
+//  x3_window_check_kernel        -- as it is
+//  x3_range_levels_prep_kernel   -- a lane per pair q = cov_off[w] + k: the frame's samples cut to the range, its first bin
+//      and its bin count; and a lane per caller's record: the identities (here the layout is known)
+//  x3_range_levels_pair_scan_kernel -- one workgroup: the exclusive scan of the bin counts; pairs that do not fit are counted
+//  x3_range_levels_init_kernel   -- identities into the partial rows in use
+//  x3_range_levels_accum_kernel  -- a lane per (pair, stretch)
+//  x3_range_levels_fixup_kernel  -- a wave per range, frames in order: flagged frames and pairs without rows through the
+//      reference's reader; the range's status; the summary
+//  x3_range_levels_merge_kernel  -- a lane per partial row, rows of one record side by side in a wave joined first
+//
+// CAPACITY.  The workspace holds P pairs and cap = rows_cap + P partial rows, both sized on the host.  A pair with q >= P or
+// whose rows end behind cap has no rows: accumulate and merge skip it (x3rl_no_rows, recomputed from q and the scan) and the
+// fix-up decodes it through the reader.  The bounds cost time, never memory or a result.
+//
+// Nothing trusts starts, lengths, offsets, sample offsets, index, entry table or bytes: stream reads are the window
+// kernels', a pair index is below P, a partial row index below cap, a caller's record index below rows_cap (the range scan
+// gives range w records [base, base + erows[w]) inside rows_cap, and every add checks its bin against erows[w]).
+#pragma once
+#include "x3_levels_kernel.h"
+
+struct X3RLevSummary {
+  X3WinSummary w;                // n_bad, first (range << 8 | status), replays (pairs the fix-up decoded), total (rows)
+  unsigned long long overflow;   // pairs without partial rows (option "last_range_levels_overflow")
+};
+
+struct X3RLevPair {
+  uint64_t f;      // the covering frame
+  uint32_t w;      // the range
+  uint32_t lo, hi; // samples [lo, hi) of the frame lie in the range
+  uint32_t r0;     // position of sample lo, counted from the range's start
+  uint32_t b0;     // its bin: the pair's first
+  uint32_t cnt;    // bins the pair touches (0: the frame failed its check, or nothing of it lies in the range)
+};
+
+// samples [lo, hi) of checked frame f (so[f + 1] - so[f] = its samples, 1 .. 65535) in positions [start, start + L), and
+// the position of sample lo behind `start`; false: none.  start + L does not wrap (the plan: L <= total, start <= total - L).
+__device__ __forceinline__ bool x3rl_cut(const uint64_t* __restrict__ so, uint64_t f, uint64_t start, uint32_t L, uint32_t& lo,
+                                         uint32_t& hi, uint32_t& r0) {
+  const uint64_t fpos = so[f], end = start + L;
+  const uint64_t samples = min(so[f + 1u] - fpos, (uint64_t)0xFFFFu);
+  const uint64_t a = start > fpos ? start - fpos : 0u;
+  const uint64_t b = end > fpos ? min(end - fpos, samples) : 0u;
+  lo = hi = r0 = 0;
+  if (a >= b) return false;
+  lo = (uint32_t)a;
+  hi = (uint32_t)b;
+  r0 = (uint32_t)(fpos + a - start);   // (below L: fpos + a < end)
+  return true;
+}
+
+// the caller's records of range w: where they begin
+__device__ __forceinline__ uint64_t x3rl_base(const unsigned long long* __restrict__ row_off, uint64_t stride, uint64_t w) {
+  return stride ? w * stride : row_off[w];
+}
+
+// pair q has no partial rows of its own: it lies beyond the P pairs the workspace holds, or it touches bins and they end
+// behind the capacity (a pair that touches none needs no rows)
+__device__ __forceinline__ bool x3rl_no_rows(const unsigned long long* __restrict__ prow, uint64_t q, uint64_t P, uint64_t cap) {
+  return q >= P || (prow[q + 1u] > cap && prow[q + 1u] > prow[q]);
+}
+
+// ---- range scan: x3_range_scan_kernel with rows where it has lengths
+__global__ void __launch_bounds__(1024)
+x3_range_levels_scan_kernel(X3WinPlan* __restrict__ plan, uint64_t n, const uint32_t* __restrict__ lens, uint64_t bin_len,
+                            uint64_t stride, uint64_t rows_cap, unsigned long long* __restrict__ cov_off,
+                            unsigned long long* __restrict__ row_off, uint32_t* __restrict__ erows,
+                            uint64_t* __restrict__ out_off, X3RLevSummary* __restrict__ sum) {
+  __shared__ unsigned long long s[1024];
+  const uint64_t per = (n + blockDim.x - 1) / blockDim.x;
+  const uint64_t a = min((uint64_t)threadIdx.x * per, n), b = min(a + per, n);
+  unsigned long long c = 0;
+  for (uint64_t w = a; w < b; ++w) c += x3l_entry_rows(lens[w], bin_len);
+  unsigned long long total;
+  unsigned long long run = x3w_block_excl_scan(c, s, &total);
+  c = 0;
+  for (uint64_t w = a; w < b; ++w) {
+    const unsigned long long R = x3l_entry_rows(lens[w], bin_len);   // (at most 2^32 - 1: a length has 32 bits)
+    const bool fits = stride ? R <= stride : (run <= rows_cap && R <= rows_cap - run);
+    if (!fits) plan[w] = X3WinPlan{0, 0, X3D_BAD_ARG};
+    erows[w] = fits ? (uint32_t)R : 0u;
+    row_off[w] = run;
+    if (out_off) out_off[w] = stride ? w * stride : run;
+    run += R;
+    c += fits ? plan[w].ncov : 0u;
+  }
+  if (threadIdx.x == 0) {
+    row_off[n] = total;
+    if (out_off) out_off[n] = stride ? n * stride : total;
+    sum->w.total = total;
+  }
+  run = x3w_block_excl_scan(c, s, &total);
+  for (uint64_t w = a; w < b; ++w) {
+    cov_off[w] = run;
+    run += plan[w].ncov;
+  }
+  if (threadIdx.x == 0) cov_off[n] = total;
+}
+
+// ---- prep: a lane per pair (below P), and a lane per caller's record: the identities.  Packed: the records of ranges that
+// have room (the others stay untouched); padded: all n * stride.
+__global__ void __launch_bounds__(256)
+x3_range_levels_prep_kernel(const uint64_t* __restrict__ so, const uint64_t* __restrict__ starts, const uint32_t* __restrict__ lens,
+                            const X3WinPlan* __restrict__ plan, uint64_t n, const unsigned long long* __restrict__ cov_off,
+                            const unsigned long long* __restrict__ row_off, const uint32_t* __restrict__ erows, uint64_t bin_len,
+                            uint64_t stride, uint64_t rows_cap, uint64_t P, const int32_t* __restrict__ fst,
+                            X3RLevPair* __restrict__ pairs, x3_level* __restrict__ levels) {
+  const uint64_t bl = x3l_bin_len(bin_len);
+  const uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, lanes = (uint64_t)gridDim.x * blockDim.x;
+  const uint64_t np = min((uint64_t)cov_off[n], P);
+  for (uint64_t q = i0; q < np; q += lanes) {
+    const uint64_t w = x3w_owner(cov_off, n, q);
+    X3RLevPair pr{plan[w].fa + (q - cov_off[w]), (uint32_t)w, 0, 0, 0, 0, 0};
+    if (fst[pr.f] == X3D_OK && x3rl_cut(so, pr.f, starts[w], lens[w], pr.lo, pr.hi, pr.r0)) {
+      pr.b0 = (uint32_t)(pr.r0 / bl);
+      pr.cnt = (uint32_t)((pr.r0 + (uint64_t)(pr.hi - pr.lo - 1u)) / bl) - pr.b0 + 1u;   // (at most hi - lo <= 65535)
+    }
+    pairs[q] = pr;
+  }
+  const x3_level id{0, 0, 32767, -32768, 0, 0};
+  const uint64_t n_rec = stride ? n * stride : min((uint64_t)row_off[n], rows_cap);   // (n * stride <= rows_cap: the host)
+  for (uint64_t i = i0; i < n_rec; i += lanes) {
+    if (!stride) {
+      const uint64_t w = x3w_owner(row_off, n, i);
+      if (i - row_off[w] >= erows[w]) continue;   // (no room: [row_off[w], ..) is not this call's to write)
+    }
+    levels[i] = id;
+  }
+}
+
+// ---- pair scan: the exclusive scan of the pairs' bin counts (np + 1 words); pairs without rows (x3rl_no_rows: those beyond P,
+// whatever their frames hold, and those below it whose bins end behind cap) are counted
+__global__ void __launch_bounds__(1024)
+x3_range_levels_pair_scan_kernel(const X3RLevPair* __restrict__ pairs, const unsigned long long* __restrict__ cov_off, uint64_t n,
+                                 uint64_t P, uint64_t cap, unsigned long long* __restrict__ prow, X3RLevSummary* __restrict__ sum) {
+  __shared__ unsigned long long s[1024];
+  const uint64_t n_cov = cov_off[n], np = min(n_cov, P);
+  const uint64_t per = (np + blockDim.x - 1) / blockDim.x;
+  const uint64_t a = min((uint64_t)threadIdx.x * per, np), b = min(a + per, np);
+  unsigned long long c = 0;
+  for (uint64_t q = a; q < b; ++q) c += pairs[q].cnt;
+  unsigned long long total;
+  unsigned long long run = x3w_block_excl_scan(c, s, &total);
+  unsigned long long over = 0;
+  for (uint64_t q = a; q < b; ++q) {
+    prow[q] = run;
+    run += pairs[q].cnt;
+    over += pairs[q].cnt && run > cap ? 1u : 0u;   // (x3rl_no_rows)
+  }
+  if (threadIdx.x == 0) prow[np] = total;
+  (void)x3w_block_excl_scan(over, s, &total);
+  if (threadIdx.x == 0) sum->overflow = total + (n_cov - np);
+}
+
+// ---- identities into the partial rows in use
+__global__ void __launch_bounds__(256)
+x3_range_levels_init_kernel(const unsigned long long* __restrict__ cov_off, uint64_t n, uint64_t P, uint64_t cap,
+                            const unsigned long long* __restrict__ prow, x3_level* __restrict__ rows) {
+  const uint64_t used = min((uint64_t)prow[min((uint64_t)cov_off[n], P)], cap);
+  const x3_level id{0, 0, 32767, -32768, 0, 0};
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < used; i += (uint64_t)gridDim.x * blockDim.x) rows[i] = id;
+}
+
+// ---- accumulate: a lane per (pair, stretch) into the pair's own rows
+__global__ void __launch_bounds__(256)
+x3_range_levels_accum_kernel(const uint8_t* __restrict__ x3, uint64_t len, const uint64_t* __restrict__ frame_off, X3DevParams p,
+                             const uint2* __restrict__ idx, uint32_t sb, uint32_t nseg, uint64_t bin_len,
+                             const unsigned long long* __restrict__ cov_off, uint64_t n, uint64_t P, uint64_t cap,
+                             const X3RLevPair* __restrict__ pairs, const unsigned long long* __restrict__ prow,
+                             x3_level* __restrict__ rows, int32_t* __restrict__ fst) {
+  const bool segd = x3w_index_ok(idx, sb);
+  const uint32_t ns = segd ? nseg : 1u;
+  const uint64_t bl = x3l_bin_len(bin_len);
+  const uint64_t n_items = min((uint64_t)cov_off[n], P) * ns;
+  const uint64_t lanes = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_items; i += lanes) {
+    const uint64_t q = i / ns;
+    const uint32_t j = (uint32_t)(i - q * ns);
+    const X3RLevPair pr = pairs[q];
+    if (fst[pr.f] != X3D_OK) continue;            // (failed its check, or flagged already: nothing to prove here)
+    if (x3rl_no_rows(prow, q, P, cap)) continue;   // (the fix-up's)
+    x3_level* const mine = rows + prow[q];
+    const uint32_t b0 = pr.b0, cnt = pr.cnt, lo = pr.lo, span = pr.hi - pr.lo;
+    auto flush = [&](uint64_t bin, const X3LevAcc& a) {
+      if (bin - b0 < (uint64_t)cnt) x3l_merge(mine + (bin - b0), a);
+    };
+    // a stretch's samples come in order, from sample 0 or from the first sample of block sb * j; the first of them inside
+    // the range, if any, is sample max(s0, lo)
+    const uint64_t s0 = j ? 1u + (uint64_t)sb * j * p.block_len : 0u;
+    X3LevBinner bn;
+    bn.open((uint64_t)pr.r0 + (s0 > lo ? s0 - lo : 0u), bl);
+    const int r = x3w_stretch(x3, len, frame_off[pr.f], p, idx, segd, sb, nseg, pr.f, j, [&](uint32_t s, uint32_t v) {
+      if (s - lo < span) bn.add(v, flush);
+    });
+    flush(bn.bin, bn.a);
+    if (r < 0) atomicOr(&fst[pr.f], X3W_FLAG);
+  }
+}
+
+// ---- fix-up: a wave per range (lane 0 works), frames in order; scratch: a block's samples per wave of the grid.  The
+// frame words are read, never written: a frame may lie under other ranges, whose waves read it too.
+__global__ void __launch_bounds__(256)
+x3_range_levels_fixup_kernel(const uint8_t* __restrict__ x3, const uint64_t* __restrict__ frame_off, const uint64_t* __restrict__ so,
+                             const uint64_t* __restrict__ starts, const uint32_t* __restrict__ lens,
+                             const X3WinPlan* __restrict__ plan, uint64_t n, X3DevParams p, uint64_t bin_len,
+                             const unsigned long long* __restrict__ cov_off, const unsigned long long* __restrict__ row_off,
+                             const uint32_t* __restrict__ erows, uint64_t stride, uint64_t P, uint64_t cap,
+                             const unsigned long long* __restrict__ prow, const int32_t* __restrict__ fst,
+                             x3_level* __restrict__ levels, int32_t* __restrict__ status, int16_t* __restrict__ scratch,
+                             uint32_t scratch_per, X3RLevSummary* __restrict__ sum) {
+  const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+  const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (threadIdx.x & 63u) return;
+  int16_t* const blk = scratch + wave * (uint64_t)scratch_per;
+  const uint64_t bl = x3l_bin_len(bin_len);
+  for (uint64_t w = wave; w < n; w += waves) {
+    const X3WinPlan pl = plan[w];
+    int32_t st = pl.status;
+    uint32_t replayed = 0;
+    if (st == X3D_OK) {
+      const uint64_t start = starts[w], q0 = cov_off[w];
+      const uint32_t L = lens[w], R = erows[w];
+      x3_level* const mine = levels + x3rl_base(row_off, stride, w);
+      for (uint32_t k = 0; k < pl.ncov; ++k) {
+        const uint64_t f = pl.fa + k;
+        int32_t fs = fst[f];
+        if (fs == X3W_FLAG || (fs == X3D_OK && x3rl_no_rows(prow, q0 + k, P, cap))) {
+          const uint8_t* const payload = x3 + frame_off[f] + 20u;
+          fs = x3w_replay_frame(payload, p, blk, [](uint32_t, uint32_t) {});
+          uint32_t lo, hi, r0;
+          if (fs == X3D_OK && x3rl_cut(so, f, start, L, lo, hi, r0)) {   // every block decodes: once more, into the records
+            auto flush = [&](uint64_t bin, const X3LevAcc& a) {
+              if (bin < (uint64_t)R) x3l_merge(mine + bin, a);
+            };
+            const uint32_t span = hi - lo;
+            X3LevBinner bn;
+            bn.open(r0, bl);
+            (void)x3w_replay_frame(payload, p, blk, [&](uint32_t s, uint32_t v) {
+              if (s - lo < span) bn.add(v, flush);
+            });
+            flush(bn.bin, bn.a);
+          }
+          ++replayed;
+        }
+        if (fs != X3D_OK && st == X3D_OK) st = fs;   // (the first in frame order; the frames behind it still count)
+      }
+    }
+    if (replayed) atomicAdd(&sum->w.replays, (unsigned long long)replayed);
+    status[w] = st;
+    if (st != X3D_OK) {
+      atomicAdd(&sum->w.n_bad, 1ull);
+      atomicMin(&sum->w.first, (unsigned long long)(w << 8) | (uint32_t)st);
+    }
+  }
+}
+
+// ---- merge: a lane per partial row.  A row counts when its frame's word is X3D_OK: checked, every stretch proven.  Rows of
+// the same record that lie side by side in a wave (the boundary bin of a range's neighbouring frames; with one bin, all of
+// them) are joined in registers as in x3_levels_merge_kernel, and the first lane of each run adds the sum.
+__global__ void __launch_bounds__(256)
+x3_range_levels_merge_kernel(const X3RLevPair* __restrict__ pairs, const unsigned long long* __restrict__ cov_off, uint64_t n,
+                             uint64_t P, uint64_t cap, const unsigned long long* __restrict__ prow,
+                             const unsigned long long* __restrict__ row_off, const uint32_t* __restrict__ erows, uint64_t stride,
+                             const x3_level* __restrict__ rows, const int32_t* __restrict__ fst, x3_level* __restrict__ levels) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t np = min((uint64_t)cov_off[n], P);
+  const uint64_t n_rows = min((uint64_t)prow[np], cap);
+  const uint64_t lanes = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u); i0 < n_rows; i0 += lanes) {   // (whole waves)
+    const uint64_t i = i0 + lane;
+    X3LevAcc a;
+    a.reset();
+    uint64_t key = ~0ull;
+    if (i < n_rows && np) {
+      const uint64_t q = x3w_owner(prow, np, i);
+      const X3RLevPair pr = pairs[q];
+      const uint64_t bin = (uint64_t)pr.b0 + (i - prow[q]);
+      if (fst[pr.f] == X3D_OK && !x3rl_no_rows(prow, q, P, cap) && bin < (uint64_t)erows[pr.w]) {
+        const x3_level r = rows[i];
+        key = x3rl_base(row_off, stride, pr.w) + bin;   // (below the range's base + erows: inside rows_cap, the range scan)
+        a.sum_sq = r.sum_sq;
+        a.sum = r.sum;
+        a.mn = r.min;
+        a.mx = r.max;
+        a.n = r.n;
+      }
+    }
+    // runs of equal keys: a lane starts one where its key differs from its left neighbour's (or it has none)
+    const uint64_t left = (uint64_t)__shfl_up((long long)key, 1, X3_WAVE);
+    const bool head = lane == 0u || key == ~0ull || left != key;
+    const unsigned long long heads = __ballot(head);
+    const uint32_t run = (uint32_t)__popcll(heads & (~0ull >> (63u - lane)));
+#pragma unroll
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+      X3LevAcc o;
+      o.sum_sq = (uint64_t)__shfl_down((long long)a.sum_sq, d, X3_WAVE);
+      o.sum = (int64_t)__shfl_down((long long)a.sum, d, X3_WAVE);
+      o.mn = __shfl_down(a.mn, d, X3_WAVE);
+      o.mx = __shfl_down(a.mx, d, X3_WAVE);
+      o.n = (uint32_t)__shfl_down((int)a.n, d, X3_WAVE);
+      const uint32_t orun = (uint32_t)__shfl_down((int)run, d, X3_WAVE);
+      if (lane + d < 64u && orun == run) a.join(o);
+    }
+    if (head && key != ~0ull) x3l_merge(levels + key, a);
+  }
+}

@@ -798,6 +798,33 @@ inline X3Error events(Context& ctx, const x3_level* d_levels, uint64_t n_bins, u
   return static_cast<X3Error>(x3_events_result(ctx.raw(), count));
 }
 
+// Range levels (x3_range_levels_dev): the x3_level records of range w = positions [d_starts[w], d_starts[w] + d_lens[w]), bins
+// of bin_len positions counted from the range's own start (0: one bin), max(1, ceil(len / bin_len)) rows each; a frame with a
+// status other than 0 adds nothing and gives the range its status.  row_stride 0: rows packed at the exclusive sum of all row
+// counts, written to d_row_offsets (n_ranges + 1 words, required); a range without room in rows_cap records is BadArg and not
+// written.  row_stride > 0: range w at w * row_stride with identities behind its rows (d_row_offsets may be nullptr).  The
+// arrays device::events wrote go in as they are.  Waits for the call: res = ranges with status != 0, the first, its status,
+// and the sum of all row counts.
+struct RangeLevelsResult : WindowsResult {
+  uint64_t total_rows = 0;
+};
+inline X3Error range_levels(Context& ctx, const EncodedStream& s, const Parameters& params, const Buffer& d_sample_offsets,
+                            const uint64_t* d_starts, const uint32_t* d_lens, size_t n_ranges, uint64_t bin_len,
+                            uint64_t row_stride, x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status,
+                            RangeLevelsResult* res) {
+  if (!s.bytes.ok() || !s.frame_offsets.ok() || !d_sample_offsets.ok()) return X3Error::BadArg;
+  const x3_params c = params.c_params();
+  int rc = x3_range_levels_dev(ctx.raw(), s.bytes.as<uint8_t>(), s.len, s.frame_offsets.as<uint64_t>(),
+                               d_sample_offsets.as<uint64_t>(), s.n_frames, &c,
+                               s.seg_blocks ? s.seg_index.as<uint64_t>() : nullptr, s.seg_blocks, d_starts, d_lens, n_ranges,
+                               bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status);
+  if (rc != X3_OK) return static_cast<X3Error>(rc);
+  RangeLevelsResult r;
+  rc = x3_range_levels_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status, &r.total_rows);
+  if (res) *res = r;
+  return static_cast<X3Error>(rc);
+}
+
 // A batch of independent streams (x3_decode_streams_dev): entry s = bytes [offsets[s], offsets[s] + lengths[s]) of d_x3 (flags:
 // X3_STREAMS_ARCHIVE_FRAMES for the frame parts of .x3a archives), decoded into row s of d_out (offsets.size() rows of row_len
 // samples, X3_WINDOW_I16 / X3_WINDOW_F32, zeros behind each entry's samples); d_results[s] = x3_decode_stream_dev's results on
@@ -905,6 +932,20 @@ class Corpus {
                                   cap, d_count);
     if (rc != X3_OK) return static_cast<X3Error>(rc);
     return static_cast<X3Error>(x3_events_result(ctx.raw(), count));
+  }
+  // Range levels of entries (x3_corpus_range_levels_dev): the records of range w = samples [d_starts[w], d_starts[w] +
+  // d_lens[w]) of entry d_entries[w]; bins, layout, capacity and result as device::range_levels; the arrays events() wrote go
+  // in as they are.  Waits for the call.
+  X3Error range_levels(Context& ctx, const uint32_t* d_entries, const uint64_t* d_starts, const uint32_t* d_lens,
+                       uint64_t n_ranges, uint64_t bin_len, uint64_t row_stride, x3_level* d_levels, uint64_t rows_cap,
+                       uint64_t* d_row_offsets, int32_t* d_status, RangeLevelsResult* res) const {
+    int rc = x3_corpus_range_levels_dev(ctx.raw(), raw_, d_entries, d_starts, d_lens, n_ranges, bin_len, row_stride, d_levels,
+                                        rows_cap, d_row_offsets, d_status);
+    if (rc != X3_OK) return static_cast<X3Error>(rc);
+    RangeLevelsResult r;
+    rc = x3_range_levels_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status, &r.total_rows);
+    if (res) *res = r;
+    return static_cast<X3Error>(rc);
   }
   // the recorded segment index (device memory the corpus owns), nullptr and 0 words without one
   const uint64_t* seg_index(uint64_t* n_words) const {

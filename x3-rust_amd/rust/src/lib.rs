@@ -209,6 +209,16 @@ pub mod ffi {
                                     rule: *const x3_event_rule, d_entries: *mut u32, d_starts: *mut u64, d_lens: *mut u32,
                                     d_event_levels: *mut x3_level, cap: u64, d_count: *mut u64) -> c_int;
         pub fn x3_events_result(ctx: *mut x3_ctx, count: *mut u64) -> c_int;
+        pub fn x3_range_levels_dev(ctx: *mut x3_ctx, d_x3: *const u8, x3_len: u64, d_frame_offsets: *const u64,
+                                   d_sample_offsets: *const u64, n_frames: u64, p: *const x3_params, d_seg_index: *const u64,
+                                   seg_blocks: u32, d_starts: *const u64, d_lens: *const u32, n_ranges: u64, bin_len: u64,
+                                   row_stride: u64, d_levels: *mut x3_level, rows_cap: u64, d_row_offsets: *mut u64,
+                                   d_status: *mut i32) -> c_int;
+        pub fn x3_corpus_range_levels_dev(ctx: *mut x3_ctx, corpus: *const x3_corpus, d_entries: *const u32, d_starts: *const u64,
+                                          d_lens: *const u32, n_ranges: u64, bin_len: u64, row_stride: u64, d_levels: *mut x3_level,
+                                          rows_cap: u64, d_row_offsets: *mut u64, d_status: *mut i32) -> c_int;
+        pub fn x3_range_levels_result(ctx: *mut x3_ctx, n_bad: *mut u64, first_bad: *mut u64, first_bad_status: *mut c_int,
+                                      total_rows: *mut u64) -> c_int;
         pub fn x3_corpus_destroy(corpus: *mut x3_corpus);
         pub fn x3_place_buffers(ctx: *mut x3_ctx, d_wav: *const i16, n: u64, p: *const x3_params, d_streams: *const *mut u8,
                                 n_streams: u32, cap: u64, d_frame_offsets: *mut u64, d_backs: *const *mut i16, n_backs: u32,
@@ -1391,6 +1401,37 @@ pub mod device {
         Ok(count)
     }
 
+    /// Range levels (`x3_range_levels_dev`; not in the reference crate): the `Level` records of range w = positions
+    /// `[starts[w], starts[w] + lens[w])`, bins of `bin_len` positions counted from the range's own start (0: one bin), max(1,
+    /// ceil(len / bin_len)) rows each.  A frame with a status other than 0 adds nothing and gives the range its status.
+    /// `row_stride` 0: rows packed at the exclusive sum of all row counts, which `d_row_offsets` (`n_ranges + 1` u64s,
+    /// required) receives; a range without room in `rows_cap` records is `BadArg` and not written.  `row_stride` > 0: range w
+    /// at `w * row_stride`, identities behind its rows.  The arrays `events` wrote go in as they are.  Waits: -> (ranges with
+    /// status != 0, the first of them, its status, the sum of all row counts)
+    #[allow(clippy::too_many_arguments)]
+    pub fn range_levels<'g>(gpu: &'g Gpu, s: &EncodedStream<'g>, params: &x3::Parameters, sample_offsets: &Buffer<'g>,
+                            d_starts: &Buffer<'g>, d_lens: &Buffer<'g>, n_ranges: usize, bin_len: u64, row_stride: u64,
+                            d_levels: &mut Buffer<'g>, rows_cap: u64, d_row_offsets: Option<&mut Buffer<'g>>,
+                            d_status: &mut Buffer<'g>) -> error::Result<(u64, u64, i32, u64)> {
+        if d_starts.len() < 8 * n_ranges || d_lens.len() < 4 * n_ranges
+            || (d_levels.len() as u64) < core::mem::size_of::<Level>() as u64 * rows_cap
+            || d_status.len() < 4 * n_ranges || d_row_offsets.as_ref().map_or(false, |b| b.len() < 8 * (n_ranges + 1)) {
+            return Err(X3Error::BadArg);
+        }
+        let p = params.c()?;
+        let idx = match &s.seg_index { Some(i) => i.as_ptr::<u64>() as *const u64, None => core::ptr::null() };
+        let off = d_row_offsets.map_or(core::ptr::null_mut(), |b| b.as_ptr::<u64>());
+        error::check(unsafe {
+            ffi::x3_range_levels_dev(gpu.raw(), s.bytes.as_ptr::<u8>(), s.len as u64, s.frame_offsets.as_ptr::<u64>(),
+                                     sample_offsets.as_ptr::<u64>(), s.n_frames as u64, &p, idx, s.seg_blocks,
+                                     d_starts.as_ptr::<u64>(), d_lens.as_ptr::<u32>(), n_ranges as u64, bin_len, row_stride,
+                                     d_levels.as_ptr::<Level>(), rows_cap, off, d_status.as_ptr::<i32>())
+        })?;
+        let (mut n_bad, mut first_bad, mut st, mut total) = (0u64, 0u64, 0, 0u64);
+        error::check(unsafe { ffi::x3_range_levels_result(gpu.raw(), &mut n_bad, &mut first_bad, &mut st, &mut total) })?;
+        Ok((n_bad, first_bad, st, total))
+    }
+
     /// `decode_streams` flag: the entries are the frame part of .x3a archives (walked with the reader's 8 phantom bytes)
     pub const STREAMS_ARCHIVE_FRAMES: u32 = 1;
     /// `Corpus::build` flag: the segment index by `x3_seg_index_build_dev` -- for every parameter set, not only where a
@@ -1561,6 +1602,31 @@ pub mod device {
             let mut count = 0u64;
             error::check(unsafe { ffi::x3_events_result(self.gpu.raw(), &mut count) })?;
             Ok(count)
+        }
+    }
+
+    impl<'g> Corpus<'g> {
+        /// Range levels of entries (`x3_corpus_range_levels_dev`): the records of range w = samples `[starts[w], starts[w] +
+        /// lens[w])` of entry `entries[w]`; bins, layout, capacity and result as `device::range_levels`.  The arrays `events`
+        /// wrote go in as they are
+        #[allow(clippy::too_many_arguments)]
+        pub fn range_levels(&self, d_entries: &Buffer<'g>, d_starts: &Buffer<'g>, d_lens: &Buffer<'g>, n: usize, bin_len: u64,
+                            row_stride: u64, d_levels: &mut Buffer<'g>, rows_cap: u64, d_row_offsets: Option<&mut Buffer<'g>>,
+                            d_status: &mut Buffer<'g>) -> error::Result<(u64, u64, i32, u64)> {
+            if d_entries.len() < 4 * n || d_starts.len() < 8 * n || d_lens.len() < 4 * n
+                || (d_levels.len() as u64) < core::mem::size_of::<Level>() as u64 * rows_cap
+                || d_status.len() < 4 * n || d_row_offsets.as_ref().map_or(false, |b| b.len() < 8 * (n + 1)) {
+                return Err(X3Error::BadArg);
+            }
+            let off = d_row_offsets.map_or(core::ptr::null_mut(), |b| b.as_ptr::<u64>());
+            error::check(unsafe {
+                ffi::x3_corpus_range_levels_dev(self.gpu.raw(), self.raw, d_entries.as_ptr::<u32>(), d_starts.as_ptr::<u64>(),
+                                                d_lens.as_ptr::<u32>(), n as u64, bin_len, row_stride, d_levels.as_ptr::<Level>(),
+                                                rows_cap, off, d_status.as_ptr::<i32>())
+            })?;
+            let (mut n_bad, mut first_bad, mut st, mut total) = (0u64, 0u64, 0, 0u64);
+            error::check(unsafe { ffi::x3_range_levels_result(self.gpu.raw(), &mut n_bad, &mut first_bad, &mut st, &mut total) })?;
+            Ok((n_bad, first_bad, st, total))
         }
     }
 

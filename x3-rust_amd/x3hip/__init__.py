@@ -63,6 +63,7 @@ SYMBOLS = [
     "x3_corpus_destroy",
     "x3_levels_dev", "x3_levels_result", "x3_corpus_levels_rows", "x3_corpus_levels_dev",
     "x3_events_dev", "x3_corpus_events_dev", "x3_events_result",
+    "x3_range_levels_dev", "x3_corpus_range_levels_dev", "x3_range_levels_result",
     "x3_tune_candidate", "x3_tuner_create", "x3_tuner_add_dev", "x3_tuner_result", "x3_tuner_max_payloads",
     "x3_tuner_reset", "x3_tuner_destroy", "x3_tune", "x3_x3a_encode_tuned",
 ]
@@ -263,6 +264,9 @@ def lib():
     L.x3_events_dev.argtypes = [vp, vp, u64, u64, vp, C.POINTER(EventRule), vp, vp, vp, u64, vp]
     L.x3_corpus_events_dev.argtypes = [vp, vp, vp, u64, u64, C.POINTER(EventRule), vp, vp, vp, vp, u64, vp]
     L.x3_events_result.argtypes = [vp, C.POINTER(u64)]
+    L.x3_range_levels_dev.argtypes = [vp, vp, u64, vp, vp, u64, PP, vp, u32, vp, vp, u64, u64, u64, vp, u64, vp, vp]
+    L.x3_corpus_range_levels_dev.argtypes = [vp, vp, vp, vp, vp, u64, u64, u64, vp, u64, vp, vp]
+    L.x3_range_levels_result.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(i32), C.POINTER(u64)]
     L.x3_corpus_destroy.restype = None
     L.x3_synth.argtypes = [i32, u64, u64, u64, vp]
     L.x3_synth_dev.argtypes = [vp, i32, u64, u64, u64, vp]
@@ -1011,6 +1015,26 @@ class Context:
         rc = lib().x3_events_result(self._h, C.byref(n))
         return rc, n.value
 
+    def range_levels_dev(self, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, params, d_starts, d_lens, n_ranges,
+                         bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status, d_seg_index=None, seg_blocks=0):
+        """x3_range_levels_dev: the x3_level records of range w = [d_starts[w], d_starts[w] + d_lens[w]), bins of bin_len
+        positions from the range's start (0: one bin), rows packed (row_stride 0) or padded; asynchronous"""
+        return lib().x3_range_levels_dev(self._h, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, C.byref(params),
+                                         d_seg_index, seg_blocks, d_starts, d_lens, n_ranges, bin_len, row_stride, d_levels,
+                                         rows_cap, d_row_offsets, d_status)
+
+    def corpus_range_levels_dev(self, corpus, d_entries, d_starts, d_lens, n_ranges, bin_len, row_stride, d_levels, rows_cap,
+                                d_row_offsets, d_status):
+        """x3_corpus_range_levels_dev: the same for ranges of entry d_entries[w] of `corpus` (a Corpus); asynchronous"""
+        return lib().x3_corpus_range_levels_dev(self._h, corpus._h, d_entries, d_starts, d_lens, n_ranges, bin_len, row_stride,
+                                                d_levels, rows_cap, d_row_offsets, d_status)
+
+    def range_levels_result(self):
+        """-> (rc, n_bad, first_bad, first_bad_status, total_rows) of the last range_levels_dev / corpus_range_levels_dev"""
+        nb, fb, st, tot = C.c_uint64(0), C.c_uint64(0), C.c_int32(0), C.c_uint64(0)
+        rc = lib().x3_range_levels_result(self._h, C.byref(nb), C.byref(fb), C.byref(st), C.byref(tot))
+        return rc, nb.value, fb.value, st.value, tot.value
+
     def decode_streams_dev(self, d_x3, x3_len, offsets, lengths, params, d_out, row_len, out_format, d_results, flags=0):
         """x3_decode_streams_dev: entry s = bytes [offsets[s], offsets[s] + lengths[s]) of d_x3 -> row s of d_out
         (len(offsets) x row_len samples) and d_results[s] (asynchronous; offsets / lengths: host sequences)"""
@@ -1136,6 +1160,62 @@ def _ranges_torch(ctx, enqueue, what, starts, lens, padded_to, capacity, dtype, 
     if rc:
         raise X3Error(rc, "x3_decode_ranges_result: " + ctx.last_error())
     return out[:cap] if padded_to is None else out, offsets, status
+
+
+def _range_levels_torch(ctx, enqueue, what, starts, lens, bin_len, padded_to, capacity, entries=None):
+    """The torch side of WindowSource.range_levels / Corpus.range_levels: device tensors in, (levels uint8 [rows, 32],
+    row_offsets int64 [n + 1], status int32 [n]) device tensors out (levels: see event_levels_view).
+    enqueue(d_entries, d_starts, d_lens, n, bin_len, stride, d_levels, cap, d_off, d_status) -> rc."""
+    import torch
+    dev = torch.device("cuda", torch.cuda.current_device())
+    bin_len = int(bin_len)
+    if bin_len < 0:
+        raise ValueError("bin_len: 0 (one bin) or a positive bin length")
+
+    def on_dev(a, dt):   # (as in _ranges_torch: unsigned words travel as the signed tensors of the same bits)
+        signed = {np.uint64: torch.int64, np.uint32: torch.int32}[dt]
+        if not isinstance(a, torch.Tensor):
+            a = torch.from_numpy(np.ascontiguousarray(a, dtype=dt).view(np.int64 if dt is np.uint64 else np.int32))
+        elif a.dtype.itemsize == signed.itemsize and not a.dtype.is_floating_point:
+            a = a.view(signed)
+        else:
+            a = a.to(signed)
+        return a.to(dev).contiguous()
+    starts, lens = on_dev(starts, np.uint64), on_dev(lens, np.uint32)
+    n = starts.numel()
+    if starts.dim() != 1 or lens.shape != starts.shape or n == 0:
+        raise ValueError("starts and lens: 1-D, non-empty, of one length")
+    d_ent = None
+    if entries is not None:
+        entries = on_dev(entries, np.uint32)
+        if entries.shape != starts.shape:
+            raise ValueError("entries: as many as starts")
+        d_ent = entries.data_ptr()
+    if padded_to is not None:
+        if padded_to <= 0:
+            raise ValueError("padded_to: a positive row stride")
+        stride, cap = int(padded_to), n * int(padded_to)
+    else:
+        stride = 0
+        if capacity is not None:
+            cap = int(capacity)
+        elif bin_len == 0 or bin_len >= 1 << 32:   # (a length has 32 bits: one bin a range)
+            cap = n
+        else:   # (the one host trip: the sum of max(1, ceil(len / bin_len)))
+            ln = lens.to(torch.int64) & 0xFFFFFFFF
+            cap = int(torch.clamp((ln + (bin_len - 1)) // bin_len, min=1).sum().item())
+    levels = torch.empty((max(cap, 1), LEVEL_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    torch.cuda.current_stream().synchronize()    # (the context's stream is not torch's: the inputs are ready from here)
+    rc = enqueue(d_ent, starts.data_ptr(), lens.data_ptr(), n, bin_len, stride, levels.data_ptr(), cap, offsets.data_ptr(),
+                 status.data_ptr())
+    if rc:
+        raise X3Error(rc, what + ": " + ctx.last_error())
+    rc = ctx.range_levels_result()[0]
+    if rc:
+        raise X3Error(rc, "x3_range_levels_result: " + ctx.last_error())
+    return levels[:cap], offsets, status
 
 
 def _events_torch(ctx, n_rows, capacity, with_entries, enqueue_levels, enqueue_events):
@@ -1288,6 +1368,24 @@ class WindowSource:
         import torch
         return _ranges_torch(self.ctx, lambda e, *a: self.ranges_into(*a), "x3_decode_ranges_dev", starts, lens, padded_to,
                              capacity, dtype or torch.int16)
+
+    def range_levels_into(self, d_starts, d_lens, n, bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status):
+        """enqueue the level records of n ranges (device pointers: d_starts n x u64, d_lens n x u32, d_levels rows_cap x
+        x3_level, d_row_offsets (n + 1) x u64 or None when padded, d_status n x i32); row_stride 0: packed; -> rc;
+        Context.range_levels_result waits"""
+        return self.ctx.range_levels_dev(self.d_x3, self.x3_len, self.d_frame_offsets, self.d_sample_offsets, self.n_frames,
+                                         self.params, d_starts, d_lens, n, bin_len, row_stride, d_levels, rows_cap,
+                                         d_row_offsets, d_status, self.d_seg_index, self.seg_blocks)
+
+    def range_levels(self, starts, lens, bin_len, *, padded_to=None, capacity=None):
+        """The x3_level records of the ranges [starts[w], starts[w] + lens[w]), bins of bin_len positions counted from each
+        range's start (0: one record per range) -> (levels uint8 [rows, 32], row_offsets int64 [n + 1], status int32 [n]),
+        torch tensors on the device (event_levels_view reads the records).  Packed (default): range w's records are
+        levels[row_offsets[w]:row_offsets[w + 1]]; `capacity` records when given (ranges without room are ERR_BAD_ARG and
+        row_offsets[-1] says what all need), otherwise one synchronising sum on the host.  padded_to: row w begins at
+        w * padded_to.  The tensors events() returns go in as they are.  The call waits for its result."""
+        return _range_levels_torch(self.ctx, lambda e, *a: self.range_levels_into(*a), "x3_range_levels_dev", starts, lens,
+                                   bin_len, padded_to, capacity)
 
     def levels(self, bin_len, n_bins=None):
         """-> (records np.ndarray of LEVEL_DTYPE [n_bins], frame statuses np.int32 [n_frames]): min, max, n, sum and sum of
@@ -1558,6 +1656,20 @@ class Corpus:
         import torch
         return _ranges_torch(self.ctx, self.ranges_into, "x3_corpus_ranges_dev", starts, lens, padded_to, capacity,
                              dtype or torch.int16, entries=entries)
+
+    def range_levels_into(self, d_entries, d_starts, d_lens, n, bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status):
+        """enqueue the level records of n ranges of entries (device pointers: d_entries n x u32, the rest as
+        WindowSource.range_levels_into); -> rc; Context.range_levels_result waits"""
+        if self._h is None:
+            raise ValueError("the corpus is closed")
+        return self.ctx.corpus_range_levels_dev(self, d_entries, d_starts, d_lens, n, bin_len, row_stride, d_levels, rows_cap,
+                                                d_row_offsets, d_status)
+
+    def range_levels(self, entries, starts, lens, bin_len, *, padded_to=None, capacity=None):
+        """The x3_level records of the ranges [starts[w], starts[w] + lens[w]) of entry entries[w] -> (levels, row_offsets,
+        status) as WindowSource.range_levels; the tensors events() returns go in as they are."""
+        return _range_levels_torch(self.ctx, self.range_levels_into, "x3_corpus_range_levels_dev", starts, lens, bin_len,
+                                   padded_to, capacity, entries=entries)
 
     def levels_rows(self, bin_len):
         """-> row_first np.uint64 [n_entries + 1]: entry e's rows of levels() are [row_first[e], row_first[e + 1])"""
