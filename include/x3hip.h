@@ -846,6 +846,72 @@ int x3_corpus_events_dev(x3_ctx* ctx, const x3_corpus* corpus, const x3_level* d
                          x3_level* d_event_levels, uint64_t cap, uint64_t* d_count);
 /* Waits for the last x3_events_dev / x3_corpus_events_dev: the number of events found (what d_count holds). */
 int x3_events_result(x3_ctx* ctx, uint64_t* count);
+/* ---- LEVEL QUANTILES AND ADAPTIVE THRESHOLDS (no counterpart in the reference): the threshold the events rule needs, chosen
+ * on the device per entry, so that levels -> thresholds -> events -> ranges never leaves HBM.
+ *   ROWS AND ENTRIES are exactly the events calls': the stream form is one entry of min(n_bins, ceil(*d_total / bin_len))
+ * rows (d_total untrusted), the corpus form has the rows of x3_corpus_levels_dev, the row prefix computed on the device from
+ * the corpus's entry table and clipped to n_rows.  A row COUNTS for its entry when it lies in one and its n != 0; K(e) is the
+ * number of counting rows of entry e.
+ *   KEYS.  X3_LEVEL_KEY_PEAK: max(max, -min), 0 .. 32768.  X3_LEVEL_KEY_MEAN_SQ: floor(sum_sq / n), 0 .. 1 << 30.  These are
+ * the largest peak_min / mean_sq_min at which the events rule still calls the row hot (sum_sq >= m * n is
+ * floor(sum_sq / n) >= m), so a quantile of keys is directly a threshold.  A key outside its range (hand-made records) is
+ * clamped into it.
+ *   QUANTILES.  q_ppm: a HOST array of n_q values (1 .. 8) in millionths, each <= 1000000, in any order, duplicates
+ * allowed.  d_values[e * n_q + j] (uint32) is the key of rank floor((K(e) - 1) * q_ppm[j] / 1000000), 0-based, among the
+ * entry's counting keys in ascending order -- np.sort(keys)[(K - 1) * q // 1000000], no interpolation, exact -- or 0 when
+ * K(e) == 0.  d_counted[e] (uint32) is K(e).  Nothing else is written; nothing outside d_levels[0 .. n_rows), *d_total and
+ * the corpus's tables is read.
+ *   Asynchronous on the context's stream: one launch set, no host trip, nothing allocated after the first call of a size
+ * (a workspace of 8 bytes a row and 1 KiB per entry and quantile).  The calls have a pending slot and a workspace of their
+ * own: the states of x3_decode_dev, the window / ranges calls, the levels, events and range-levels calls are left alone.
+ * X3_ERR_BAD_ARG with nothing enqueued, and an earlier pending result left as it was, for bin_len == 0 or above 0xFFFFFFFF,
+ * n_bins == 0 or above 0x7FFFFFFF, an unknown key, n_q outside 1 .. 8, a q_ppm above 1000000, a NULL or misaligned pointer
+ * (d_levels, d_total: 8 bytes; d_values, d_counted: 4), a context that is recording a graph, and (corpus form) a context on
+ * another device than the build's or n_rows other than x3_corpus_levels_rows' last word. */
+int x3_level_quantiles_dev(x3_ctx* ctx, const x3_level* d_levels, uint64_t n_bins, uint64_t bin_len, const uint64_t* d_total,
+                           int key, const uint32_t* q_ppm, uint32_t n_q, uint32_t* d_values, uint32_t* d_counted);
+/* The corpus form: n_entries * n_q values, n_entries counts. */
+int x3_corpus_level_quantiles_dev(x3_ctx* ctx, const x3_corpus* corpus, const x3_level* d_levels, uint64_t n_rows,
+                                  uint64_t bin_len, int key, const uint32_t* q_ppm, uint32_t n_q, uint32_t* d_values,
+                                  uint32_t* d_counted);
+/* Waits for the last quantiles or thresholds call: the number of entries with K == 0 and the first of them (the entry count
+ * if none). */
+int x3_level_quantiles_result(x3_ctx* ctx, uint64_t* n_empty, uint64_t* first_empty);
+/* THRESHOLDS from quantiles: per entry, for a criterion that is on (its div != 0) and K(e) > 0,
+ * thr = clamp(floor(value * mul / div) + add, 1, limit), value the quantile q_ppm of the criterion's key, limit 32768 (peak)
+ * or 1 << 30 (mean square), in 64-bit arithmetic that cannot wrap; for a criterion that is off, or K(e) == 0, thr = 0.
+ * "6 dB over the median mean square" is {mean_sq_q_ppm = 500000, mean_sq_mul = 4, mean_sq_div = 1, mean_sq_add = 0}.
+ * d_thr (8-byte aligned) receives ONE record (stream form) or n_entries records (corpus form); counted is K(e).  Contract,
+ * refusals and result call as for the quantiles calls; also X3_ERR_BAD_ARG for both criteria off and a q_ppm above 1000000
+ * of a criterion that is on. */
+#define X3_LEVEL_KEY_PEAK 0      /* the keys of x3_level_quantiles_dev */
+#define X3_LEVEL_KEY_MEAN_SQ 1
+typedef struct x3_threshold_rule {   /* 32 bytes */
+  uint32_t peak_q_ppm, peak_mul, peak_div, peak_add;             /* peak_div == 0: criterion off */
+  uint32_t mean_sq_q_ppm, mean_sq_mul, mean_sq_div, mean_sq_add; /* mean_sq_div == 0: off */
+} x3_threshold_rule;
+typedef struct x3_event_threshold {  /* 16 bytes, per entry */
+  uint64_t mean_sq_min;  /* 0: off for this entry */
+  uint32_t peak_min;     /* 0: off for this entry */
+  uint32_t counted;      /* K(e) */
+} x3_event_threshold;
+int x3_level_thresholds_dev(x3_ctx* ctx, const x3_level* d_levels, uint64_t n_bins, uint64_t bin_len, const uint64_t* d_total,
+                            const x3_threshold_rule* rule, x3_event_threshold* d_thr);
+int x3_corpus_level_thresholds_dev(x3_ctx* ctx, const x3_corpus* corpus, const x3_level* d_levels, uint64_t n_rows,
+                                   uint64_t bin_len, const x3_threshold_rule* rule, x3_event_threshold* d_thr);
+/* EVENTS with a threshold per entry: x3_events_dev / x3_corpus_events_dev with the rule's two values taken from d_thr[e]
+ * (device memory, 8-byte aligned, 1 record or n_entries) for the rows of entry e.  rule->mean_sq_min and rule->peak_min must
+ * both be 0 (anything else: X3_ERR_BAD_ARG).  d_thr is untrusted: a value above its limit makes that criterion never hot,
+ * both values 0 leave the entry without hot rows, counted is ignored.  Everything behind "hot" is the events' definition word
+ * for word -- runs, min_bins, padding, pieces, fillers, d_count -- and x3_events_result serves these calls: they share the
+ * events' pending slot and workspace.  With every d_thr[e] = (m, p) the arrays are those of the events call with that rule. */
+int x3_events_adaptive_dev(x3_ctx* ctx, const x3_level* d_levels, uint64_t n_bins, uint64_t bin_len, const uint64_t* d_total,
+                           const x3_event_rule* rule, const x3_event_threshold* d_thr, uint64_t* d_starts, uint32_t* d_lens,
+                           x3_level* d_event_levels, uint64_t cap, uint64_t* d_count);
+int x3_corpus_events_adaptive_dev(x3_ctx* ctx, const x3_corpus* corpus, const x3_level* d_levels, uint64_t n_rows,
+                                  uint64_t bin_len, const x3_event_rule* rule, const x3_event_threshold* d_thr,
+                                  uint32_t* d_entries, uint64_t* d_starts, uint32_t* d_lens, x3_level* d_event_levels,
+                                  uint64_t cap, uint64_t* d_count);
 /* ---- RANGE LEVELS (no counterpart in the reference): the level records of ranges (entry, start, len), bins counted from
  * each range's own start -- a second look inside events at finer bins, a zoomed overview, peak and RMS of any sample-exact
  * cut.  The work follows the ranges (their covering frames), not the stream.

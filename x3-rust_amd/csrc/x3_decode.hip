@@ -11,6 +11,7 @@
 #include "x3_seg_index_kernel.h"
 #include "x3_levels_kernel.h"
 #include "x3_events_kernel.h"
+#include "x3_quantiles_kernel.h"
 #include "x3_range_levels_kernel.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -2039,10 +2040,12 @@ size_t events_carve(char* base, uint64_t n_rows, uint64_t n_ent, EvWs* w) {
 // the argument checks x3_events_dev and x3_corpus_events_dev share; *eff: the rule the kernels take (max_bins never 0)
 static bool events_args_ok(const x3_ctx* c, const x3_level* d_levels, uint64_t n_rows, uint64_t bin_len, const x3_event_rule* rule,
                            const uint64_t* d_starts, const uint32_t* d_lens, const x3_level* d_event_levels, uint64_t cap,
-                           const uint64_t* d_count, x3_event_rule* eff) {
+                           const uint64_t* d_count, x3_event_rule* eff, bool adaptive = false) {
   if (!c || !d_levels || !rule || !d_starts || !d_lens || !d_count || c->capturing) return false;
   if (bin_len == 0 || bin_len > 0xFFFFFFFFull || n_rows == 0 || n_rows > 0x7FFFFFFFull || cap == 0 || cap > 0x7FFFFFFFull) return false;
-  if ((rule->mean_sq_min == 0 && rule->peak_min == 0) || rule->mean_sq_min > (1ull << 30) || rule->peak_min > 32768u) return false;
+  if (adaptive ? (rule->mean_sq_min != 0 || rule->peak_min != 0)   // (the two values come from d_thr, per entry)
+               : ((rule->mean_sq_min == 0 && rule->peak_min == 0) || rule->mean_sq_min > (1ull << 30) || rule->peak_min > 32768u))
+    return false;
   if (2ull * rule->pad_bins > rule->join_bins || (uint64_t)rule->max_bins * bin_len > 0xFFFFFFFFull || rule->reserved) return false;
   const uintptr_t p8 = reinterpret_cast<uintptr_t>(d_levels) | reinterpret_cast<uintptr_t>(d_starts) |
                        reinterpret_cast<uintptr_t>(d_event_levels) | reinterpret_cast<uintptr_t>(d_count);
@@ -2053,9 +2056,11 @@ static bool events_args_ok(const x3_ctx* c, const x3_level* d_levels, uint64_t n
 }
 
 // The launch set of an events call.  q: the rows (its row_first is set here); k: the corpus of a corpus call, whose row
-// prefix the levels' kernel computes into the workspace first.
-static int events_launch(x3_ctx* c, X3EvRows q, const x3_corpus* k, const x3_event_rule& rule, uint32_t* d_entries,
-                         uint64_t* d_starts, uint32_t* d_lens, x3_level* d_event_levels, uint64_t cap, uint64_t* d_count) {
+// prefix the levels' kernel computes into the workspace first.  d_thr: the thresholds of an adaptive call, which differs in
+// its flag kernel alone (the other six take join_bins, min_bins, pad_bins and max_bins of the rule, never its two values).
+static int events_launch(x3_ctx* c, X3EvRows q, const x3_corpus* k, const x3_event_rule& rule, const x3_event_threshold* d_thr,
+                         uint32_t* d_entries, uint64_t* d_starts, uint32_t* d_lens, x3_level* d_event_levels, uint64_t cap,
+                         uint64_t* d_count) {
   HIPCHK(c, hipSetDevice(c->device));
   EvWs w;
   int rc;
@@ -2067,7 +2072,11 @@ static int events_launch(x3_ctx* c, X3EvRows q, const x3_corpus* k, const x3_eve
     hipLaunchKernelGGL(x3_corpus_levels_rows_kernel, dim3(1), dim3(1024), 0, c->stream, k->d_ent, k->n, q.bin_len, w.row_first);
     q.row_first = w.row_first;
   }
-  hipLaunchKernelGGL(x3_events_flag_kernel, g_tiles, dim3(256), 0, c->stream, q, rule, n_tiles, w.hot, w.tile_prev, w.tile_next);
+  if (d_thr)
+    hipLaunchKernelGGL(x3_events_adaptive_flag_kernel, g_tiles, dim3(256), 0, c->stream, q, d_thr, n_tiles, w.hot, w.tile_prev,
+                       w.tile_next);
+  else
+    hipLaunchKernelGGL(x3_events_flag_kernel, g_tiles, dim3(256), 0, c->stream, q, rule, n_tiles, w.hot, w.tile_prev, w.tile_next);
   hipLaunchKernelGGL(x3_events_near_kernel, dim3(1), dim3(1024), 0, c->stream, n_tiles, w.tile_prev, w.tile_next);
   hipLaunchKernelGGL(x3_events_mark_kernel, g_tiles, dim3(256), 0, c->stream, q, rule.join_bins, n_tiles, w.hot,
                      (const uint32_t*)w.tile_prev, (const uint32_t*)w.tile_next, w.tile_ns, w.tile_ne);
@@ -2093,8 +2102,8 @@ extern "C" int x3_events_dev(x3_ctx* c, const x3_level* d_levels, uint64_t n_bin
   x3_event_rule eff;
   if (!events_args_ok(c, d_levels, n_bins, bin_len, rule, d_starts, d_lens, d_event_levels, cap, d_count, &eff)) return X3_ERR_BAD_ARG;
   if (!d_total || (reinterpret_cast<uintptr_t>(d_total) & 7u)) return X3_ERR_BAD_ARG;
-  return events_launch(c, X3EvRows{d_levels, n_bins, bin_len, d_total, nullptr, 0, nullptr}, nullptr, eff, nullptr, d_starts, d_lens,
-                       d_event_levels, cap, d_count);
+  return events_launch(c, X3EvRows{d_levels, n_bins, bin_len, d_total, nullptr, 0, nullptr}, nullptr, eff, nullptr, nullptr, d_starts,
+                       d_lens, d_event_levels, cap, d_count);
 }
 
 extern "C" int x3_corpus_events_dev(x3_ctx* c, const x3_corpus* k, const x3_level* d_levels, uint64_t n_rows, uint64_t bin_len,
@@ -2111,8 +2120,8 @@ extern "C" int x3_corpus_events_dev(x3_ctx* c, const x3_corpus* k, const x3_leve
   uint64_t want = 0;
   for (const x3_corpus_entry& en : k->ent) want += levels_rows_of(en.n_samples, bin_len);
   if (n_rows != want) return X3_ERR_BAD_ARG;
-  return events_launch(c, X3EvRows{d_levels, n_rows, bin_len, nullptr, k->d_ent, k->n, nullptr}, k, eff, d_entries, d_starts, d_lens,
-                       d_event_levels, cap, d_count);
+  return events_launch(c, X3EvRows{d_levels, n_rows, bin_len, nullptr, k->d_ent, k->n, nullptr}, k, eff, nullptr, d_entries, d_starts,
+                       d_lens, d_event_levels, cap, d_count);
 }
 
 extern "C" int x3_events_result(x3_ctx* c, uint64_t* count) {
@@ -2121,6 +2130,202 @@ extern "C" int x3_events_result(x3_ctx* c, uint64_t* count) {
   const int rc = pending_fetch(c, c->events, c->ev_ws, &h, sizeof h);
   if (rc) return rc;
   if (count) *count = h.count;
+  return X3_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// level quantiles, thresholds from them, events with a threshold per entry (x3_quantiles_kernel.h)
+// ------------------------------------------------------------------------------------------------
+static_assert(X3Q_BINS == X3E_TILE, "a lane of a tile flushes one bin of the tile's histogram");
+static_assert(sizeof(x3_threshold_rule) == 32 && sizeof(x3_event_threshold) == 16, "include/x3hip.h states these sizes");
+
+extern "C" int x3_events_adaptive_dev(x3_ctx* c, const x3_level* d_levels, uint64_t n_bins, uint64_t bin_len, const uint64_t* d_total,
+                                      const x3_event_rule* rule, const x3_event_threshold* d_thr, uint64_t* d_starts,
+                                      uint32_t* d_lens, x3_level* d_event_levels, uint64_t cap, uint64_t* d_count) {
+  x3_event_rule eff;
+  if (!events_args_ok(c, d_levels, n_bins, bin_len, rule, d_starts, d_lens, d_event_levels, cap, d_count, &eff, true))
+    return X3_ERR_BAD_ARG;
+  if (!d_total || !d_thr || ((reinterpret_cast<uintptr_t>(d_total) | reinterpret_cast<uintptr_t>(d_thr)) & 7u)) return X3_ERR_BAD_ARG;
+  return events_launch(c, X3EvRows{d_levels, n_bins, bin_len, d_total, nullptr, 0, nullptr}, nullptr, eff, d_thr, nullptr, d_starts,
+                       d_lens, d_event_levels, cap, d_count);
+}
+
+// the checks of a corpus call behind the shared ones: the device, n_rows against the host's entry table
+static bool corpus_rows_ok(x3_ctx* c, const x3_corpus* k, uint64_t n_rows, uint64_t bin_len, const char* what) {
+  if (c->device != k->device) {
+    c->last_error = std::string(what) + ": the corpus was built on another device";
+    return false;
+  }
+  uint64_t want = 0;
+  for (const x3_corpus_entry& en : k->ent) want += levels_rows_of(en.n_samples, bin_len);
+  return n_rows == want;
+}
+
+extern "C" int x3_corpus_events_adaptive_dev(x3_ctx* c, const x3_corpus* k, const x3_level* d_levels, uint64_t n_rows,
+                                             uint64_t bin_len, const x3_event_rule* rule, const x3_event_threshold* d_thr,
+                                             uint32_t* d_entries, uint64_t* d_starts, uint32_t* d_lens, x3_level* d_event_levels,
+                                             uint64_t cap, uint64_t* d_count) {
+  x3_event_rule eff;
+  if (!k || !events_args_ok(c, d_levels, n_rows, bin_len, rule, d_starts, d_lens, d_event_levels, cap, d_count, &eff, true))
+    return X3_ERR_BAD_ARG;
+  if (!d_entries || (reinterpret_cast<uintptr_t>(d_entries) & 3u) || !d_thr || (reinterpret_cast<uintptr_t>(d_thr) & 7u))
+    return X3_ERR_BAD_ARG;
+  if (!corpus_rows_ok(c, k, n_rows, bin_len, "x3_corpus_events_adaptive_dev")) return X3_ERR_BAD_ARG;
+  return events_launch(c, X3EvRows{d_levels, n_rows, bin_len, nullptr, k->d_ent, k->n, nullptr}, k, eff, d_thr, d_entries, d_starts,
+                       d_lens, d_event_levels, cap, d_count);
+}
+
+// The workspace of a quantiles or thresholds call (q_ws; the formula: x3_quantiles_kernel.h)
+struct QWs {
+  uint2* keys;                                  // per row
+  uint32_t* hist; X3QSlot* slots;               // per (entry, j): 256 bins; prefix and rank
+  uint32_t* val[2]; uint32_t* counted;          // per entry: the two values and K of a thresholds call
+  X3QSummary* sum; unsigned long long* row_first;
+};
+static size_t quantiles_carve(char* base, uint64_t n_rows, uint64_t n_ent, uint32_t n_q, QWs* w) {
+  BlockCarver k{base, 0};
+  w->keys = k.take<uint2>(n_rows);
+  w->hist = k.take<uint32_t>(n_ent * n_q * X3Q_BINS);
+  w->slots = k.take<X3QSlot>(n_ent * n_q);
+  w->val[0] = k.take<uint32_t>(n_ent);
+  w->val[1] = k.take<uint32_t>(n_ent);
+  w->counted = k.take<uint32_t>(n_ent);
+  w->sum = k.take<X3QSummary>(1);
+  w->row_first = k.take<unsigned long long>(n_ent + 1, 1);
+  return k.at;
+}
+
+// the argument checks the quantiles and thresholds calls share
+static bool quantiles_args_ok(const x3_ctx* c, const x3_level* d_levels, uint64_t n_rows, uint64_t bin_len) {
+  if (!c || !d_levels || c->capturing) return false;
+  if (bin_len == 0 || bin_len > 0xFFFFFFFFull || n_rows == 0 || n_rows > 0x7FFFFFFFull) return false;
+  return (reinterpret_cast<uintptr_t>(d_levels) & 7u) == 0;
+}
+
+// One select: the n_q quantiles `ppm` of key `key` of every entry into values (n_ent * n_q words), K into counted
+struct QRun { int key; uint32_t n_q; X3QPpm ppm; uint32_t* values; };
+
+// The launch set of a quantiles call (runs[0], into the caller's arrays) or a thresholds call (one run per criterion that
+// is on, into the workspace, then the map into d_thr).  q, k: as in events_launch.
+static int quantiles_launch(x3_ctx* c, X3EvRows q, const x3_corpus* k, QRun* runs, uint32_t n_runs, uint32_t* d_counted,
+                            const x3_threshold_rule* trule, x3_event_threshold* d_thr) {
+  HIPCHK(c, hipSetDevice(c->device));
+  const uint64_t n_ent = k ? k->n : 1u;
+  const uint32_t n_q = runs[0].n_q;   // (a thresholds call: 1 in every run)
+  QWs w;
+  int rc;
+  if ((rc = ensure(c, c->q_ws, quantiles_carve(nullptr, q.n_rows, n_ent, n_q, &w)))) return rc;
+  quantiles_carve((char*)c->q_ws.p, q.n_rows, n_ent, n_q, &w);
+  const uint64_t n_tiles = (q.n_rows + X3E_TILE - 1) / X3E_TILE;
+  const dim3 g_rows(grid_for(q.n_rows, 256)), g_tiles(grid_for(n_tiles, 1)), g_ent(grid_for(n_ent, 1));
+  if (k) {
+    hipLaunchKernelGGL(x3_corpus_levels_rows_kernel, dim3(1), dim3(1024), 0, c->stream, k->d_ent, k->n, q.bin_len, w.row_first);
+    q.row_first = w.row_first;
+  }
+  uint32_t* const counted = trule ? w.counted : d_counted;
+  for (uint32_t i = 0; i < n_runs; ++i) {
+    const QRun& r = runs[i];
+    const uint32_t passes = r.key == X3_LEVEL_KEY_PEAK ? 2u : 4u;
+    uint32_t* const values = trule ? w.val[i] : r.values;
+    X3QSummary* const sum = i ? nullptr : w.sum;   // (K is the same in every run: entries without rows are counted once)
+    HIPCHK(c, hipMemsetAsync(w.hist, 0, (size_t)(n_ent * n_q * X3Q_BINS) * sizeof(uint32_t), c->stream));
+    hipLaunchKernelGGL(x3_quantiles_key_kernel, g_rows, dim3(256), 0, c->stream, q, r.key, w.keys, sum);
+    for (uint32_t pass = 0; pass < passes; ++pass) {
+      hipLaunchKernelGGL(x3_quantiles_hist_kernel, g_tiles, dim3(256), 0, c->stream, (const uint2*)w.keys, q.n_rows, n_tiles,
+                         n_ent, n_q, pass, passes, (const X3QSlot*)w.slots, w.hist);
+      hipLaunchKernelGGL(x3_quantiles_select_kernel, g_ent, dim3(64u * n_q), 0, c->stream, n_ent, n_q, r.ppm, pass, passes,
+                         w.hist, w.slots, values, counted, sum);
+    }
+  }
+  if (trule) {
+    // (a criterion that is off has no run: its value is not read)
+    const uint32_t* const vp = trule->peak_div ? w.val[0] : nullptr;
+    const uint32_t* const vm = trule->mean_sq_div ? w.val[trule->peak_div ? 1 : 0] : nullptr;
+    hipLaunchKernelGGL(x3_quantiles_map_kernel, dim3(grid_for(n_ent, 256)), dim3(256), 0, c->stream, n_ent, *trule, vp, vm,
+                       (const uint32_t*)w.counted, d_thr);
+  }
+  HIPCHK(c, hipGetLastError());
+  c->quantiles.pending = true;
+  c->quantiles.count = n_ent;
+  c->quantiles.sum_off = (size_t)((char*)w.sum - (char*)c->q_ws.p);
+  return X3_OK;
+}
+
+static bool quantiles_run_ok(int key, const uint32_t* q_ppm, uint32_t n_q, uint32_t* d_values, uint32_t* d_counted, QRun* r) {
+  if ((key != X3_LEVEL_KEY_PEAK && key != X3_LEVEL_KEY_MEAN_SQ) || !q_ppm || n_q == 0 || n_q > X3Q_MAX_Q) return false;
+  if (!d_values || !d_counted || ((reinterpret_cast<uintptr_t>(d_values) | reinterpret_cast<uintptr_t>(d_counted)) & 3u)) return false;
+  *r = QRun{key, n_q, {}, d_values};
+  for (uint32_t j = 0; j < n_q; ++j) {
+    if (q_ppm[j] > 1000000u) return false;
+    r->ppm.v[j] = q_ppm[j];
+  }
+  return true;
+}
+
+extern "C" int x3_level_quantiles_dev(x3_ctx* c, const x3_level* d_levels, uint64_t n_bins, uint64_t bin_len, const uint64_t* d_total,
+                                      int key, const uint32_t* q_ppm, uint32_t n_q, uint32_t* d_values, uint32_t* d_counted) {
+  QRun r;
+  if (!quantiles_args_ok(c, d_levels, n_bins, bin_len) || !quantiles_run_ok(key, q_ppm, n_q, d_values, d_counted, &r))
+    return X3_ERR_BAD_ARG;
+  if (!d_total || (reinterpret_cast<uintptr_t>(d_total) & 7u)) return X3_ERR_BAD_ARG;
+  return quantiles_launch(c, X3EvRows{d_levels, n_bins, bin_len, d_total, nullptr, 0, nullptr}, nullptr, &r, 1, d_counted, nullptr,
+                          nullptr);
+}
+
+extern "C" int x3_corpus_level_quantiles_dev(x3_ctx* c, const x3_corpus* k, const x3_level* d_levels, uint64_t n_rows,
+                                             uint64_t bin_len, int key, const uint32_t* q_ppm, uint32_t n_q, uint32_t* d_values,
+                                             uint32_t* d_counted) {
+  QRun r;
+  if (!k || !quantiles_args_ok(c, d_levels, n_rows, bin_len) || !quantiles_run_ok(key, q_ppm, n_q, d_values, d_counted, &r))
+    return X3_ERR_BAD_ARG;
+  if (!corpus_rows_ok(c, k, n_rows, bin_len, "x3_corpus_level_quantiles_dev")) return X3_ERR_BAD_ARG;
+  return quantiles_launch(c, X3EvRows{d_levels, n_rows, bin_len, nullptr, k->d_ent, k->n, nullptr}, k, &r, 1, d_counted, nullptr,
+                          nullptr);
+}
+
+// the runs of a thresholds call: one per criterion that is on, the peak's first; 0: refused
+static uint32_t threshold_runs(const x3_threshold_rule* rule, const x3_event_threshold* d_thr, QRun runs[2]) {
+  if (!rule || !d_thr || (reinterpret_cast<uintptr_t>(d_thr) & 7u)) return 0;
+  uint32_t n = 0;
+  if (rule->peak_div) {
+    if (rule->peak_q_ppm > 1000000u) return 0;
+    runs[n] = QRun{X3_LEVEL_KEY_PEAK, 1u, {}, nullptr};
+    runs[n++].ppm.v[0] = rule->peak_q_ppm;
+  }
+  if (rule->mean_sq_div) {
+    if (rule->mean_sq_q_ppm > 1000000u) return 0;
+    runs[n] = QRun{X3_LEVEL_KEY_MEAN_SQ, 1u, {}, nullptr};
+    runs[n++].ppm.v[0] = rule->mean_sq_q_ppm;
+  }
+  return n;
+}
+
+extern "C" int x3_level_thresholds_dev(x3_ctx* c, const x3_level* d_levels, uint64_t n_bins, uint64_t bin_len, const uint64_t* d_total,
+                                       const x3_threshold_rule* rule, x3_event_threshold* d_thr) {
+  QRun runs[2];
+  if (!quantiles_args_ok(c, d_levels, n_bins, bin_len) || !d_total || (reinterpret_cast<uintptr_t>(d_total) & 7u)) return X3_ERR_BAD_ARG;
+  const uint32_t n = threshold_runs(rule, d_thr, runs);
+  if (!n) return X3_ERR_BAD_ARG;
+  return quantiles_launch(c, X3EvRows{d_levels, n_bins, bin_len, d_total, nullptr, 0, nullptr}, nullptr, runs, n, nullptr, rule, d_thr);
+}
+
+extern "C" int x3_corpus_level_thresholds_dev(x3_ctx* c, const x3_corpus* k, const x3_level* d_levels, uint64_t n_rows,
+                                              uint64_t bin_len, const x3_threshold_rule* rule, x3_event_threshold* d_thr) {
+  QRun runs[2];
+  if (!k || !quantiles_args_ok(c, d_levels, n_rows, bin_len)) return X3_ERR_BAD_ARG;
+  const uint32_t n = threshold_runs(rule, d_thr, runs);
+  if (!n || !corpus_rows_ok(c, k, n_rows, bin_len, "x3_corpus_level_thresholds_dev")) return X3_ERR_BAD_ARG;
+  return quantiles_launch(c, X3EvRows{d_levels, n_rows, bin_len, nullptr, k->d_ent, k->n, nullptr}, k, runs, n, nullptr, rule, d_thr);
+}
+
+extern "C" int x3_level_quantiles_result(x3_ctx* c, uint64_t* n_empty, uint64_t* first_empty) {
+  if (!c) return X3_ERR_BAD_ARG;
+  X3QSummary h{0, 0};
+  const uint64_t n_ent = c->quantiles.count;
+  const int rc = pending_fetch(c, c->quantiles, c->q_ws, &h, sizeof h);
+  if (rc) return rc;
+  if (n_empty) *n_empty = h.n_empty;
+  if (first_empty) *first_empty = h.n_empty ? h.first_empty : n_ent;
   return X3_OK;
 }
 

@@ -154,6 +154,7 @@ struct x3_ctx {
   DevBuf idx_wg, idx_sorted, idx_scan;  // ... of its fast path: candidates per scanning workgroup, in order, the scans
   DevBuf lev_ws;   // x3_levels_dev / x3_corpus_levels_dev: verdicts, plans, the frames' partial rows, replay scratch, summary (x3_levels_kernel.h)
   DevBuf ev_ws;    // x3_events_dev / x3_corpus_events_dev: row flags, tile totals, run tables, piece scan, summary, row prefix (x3_events_kernel.h)
+  DevBuf q_ws;     // x3_level_quantiles_dev / x3_level_thresholds_dev and their corpus forms: (key, entry) per row, histograms, select state, summary, row prefix (x3_quantiles_kernel.h)
   DevBuf rlev_ws;  // x3_range_levels_dev / x3_corpus_range_levels_dev: plans, scans, verdicts, pairs, their partial rows, replay scratch, summary (x3_range_levels_kernel.h)
   DevBuf win_ws;   // x3_decode_windows_dev: plans, scans, per-frame verdicts, replay scratch, summary (x3_decode_window_kernel.h)
   // x3_decode_streams_dev (x3_streams_kernel.h): the call's block (the segmented walk's workspace and the call's own words:
@@ -190,6 +191,7 @@ struct x3_ctx {
   } windows;               // x3_decode_windows_dev / x3_decode_ranges_dev and their corpus forms: win_ws
   PendingCall levels;      // x3_levels_dev / x3_corpus_levels_dev: lev_ws
   PendingCall events;      // x3_events_dev / x3_corpus_events_dev: ev_ws (count: the call's cap)
+  PendingCall quantiles;   // the quantiles and thresholds calls: q_ws (count: the entries)
   PendingCall range_levels;   // x3_range_levels_dev / x3_corpus_range_levels_dev: rlev_ws (count: the ranges)
   bool force_two_pass = false;
   // Contexts that encode concurrently on ONE GPU (the file pipeline's workers) share this gate: the single-pass encoders

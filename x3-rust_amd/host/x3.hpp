@@ -798,6 +798,49 @@ inline X3Error events(Context& ctx, const x3_level* d_levels, uint64_t n_bins, u
   return static_cast<X3Error>(x3_events_result(ctx.raw(), count));
 }
 
+// Level quantiles (x3_level_quantiles_dev): the quantiles q_ppm (millionths, 1 .. 8 of them, host array) of the keys
+// (X3_LEVEL_KEY_PEAK: max(max, -min); X3_LEVEL_KEY_MEAN_SQ: floor(sum_sq / n)) of the counting rows of n_bins level records
+// into d_values (uint32, q_ppm.size() words) and their number into d_counted (one uint32); value j is
+// sorted(keys)[(K - 1) * q_ppm[j] / 1000000], 0 when K == 0.  Waits for the call: res = entries without a counting row and
+// the first of them (the entry count if none).
+struct QuantilesResult {
+  uint64_t n_empty = 0, first_empty = 0;
+};
+inline X3Error level_quantiles(Context& ctx, const x3_level* d_levels, uint64_t n_bins, uint64_t bin_len, const uint64_t* d_total,
+                               int key, const std::vector<uint32_t>& q_ppm, uint32_t* d_values, uint32_t* d_counted,
+                               QuantilesResult* res) {
+  int rc = x3_level_quantiles_dev(ctx.raw(), d_levels, n_bins, bin_len, d_total, key, q_ppm.data(), (uint32_t)q_ppm.size(), d_values,
+                                  d_counted);
+  if (rc != X3_OK) return static_cast<X3Error>(rc);
+  QuantilesResult r;
+  rc = x3_level_quantiles_result(ctx.raw(), &r.n_empty, &r.first_empty);
+  if (res) *res = r;
+  return static_cast<X3Error>(rc);
+}
+
+// Thresholds from quantiles (x3_level_thresholds_dev): one x3_event_threshold at d_thr, per criterion of `rule` that is on
+// clamp(floor(quantile * mul / div) + add, 1, limit), 0 for one that is off or without a counting row.  Waits for the call.
+inline X3Error level_thresholds(Context& ctx, const x3_level* d_levels, uint64_t n_bins, uint64_t bin_len, const uint64_t* d_total,
+                                const x3_threshold_rule& rule, x3_event_threshold* d_thr, QuantilesResult* res) {
+  int rc = x3_level_thresholds_dev(ctx.raw(), d_levels, n_bins, bin_len, d_total, &rule, d_thr);
+  if (rc != X3_OK) return static_cast<X3Error>(rc);
+  QuantilesResult r;
+  rc = x3_level_quantiles_result(ctx.raw(), &r.n_empty, &r.first_empty);
+  if (res) *res = r;
+  return static_cast<X3Error>(rc);
+}
+
+// Events with the rule's two values (both 0 in `rule`) taken from the record at d_thr (x3_events_adaptive_dev); otherwise as
+// device::events.  Waits for the call.
+inline X3Error events_adaptive(Context& ctx, const x3_level* d_levels, uint64_t n_bins, uint64_t bin_len, const uint64_t* d_total,
+                               const x3_event_rule& rule, const x3_event_threshold* d_thr, uint64_t* d_starts, uint32_t* d_lens,
+                               x3_level* d_event_levels, uint64_t cap, uint64_t* d_count, uint64_t* count) {
+  int rc = x3_events_adaptive_dev(ctx.raw(), d_levels, n_bins, bin_len, d_total, &rule, d_thr, d_starts, d_lens, d_event_levels, cap,
+                                  d_count);
+  if (rc != X3_OK) return static_cast<X3Error>(rc);
+  return static_cast<X3Error>(x3_events_result(ctx.raw(), count));
+}
+
 // Range levels (x3_range_levels_dev): the x3_level records of range w = positions [d_starts[w], d_starts[w] + d_lens[w]), bins
 // of bin_len positions counted from the range's own start (0: one bin), max(1, ceil(len / bin_len)) rows each; a frame with a
 // status other than 0 adds nothing and gives the range its status.  row_stride 0: rows packed at the exclusive sum of all row
@@ -930,6 +973,37 @@ class Corpus {
                  uint64_t* d_count, uint64_t* count) const {
     int rc = x3_corpus_events_dev(ctx.raw(), raw_, d_levels, n_rows, bin_len, &rule, d_entries, d_starts, d_lens, d_event_levels,
                                   cap, d_count);
+    if (rc != X3_OK) return static_cast<X3Error>(rc);
+    return static_cast<X3Error>(x3_events_result(ctx.raw(), count));
+  }
+  // Level quantiles of every entry (x3_corpus_level_quantiles_dev) over the n_rows records levels() wrote: as
+  // device::level_quantiles, d_values n_entries * q_ppm.size() words, d_counted n_entries.  Waits for the call.
+  X3Error level_quantiles(Context& ctx, const x3_level* d_levels, uint64_t n_rows, uint64_t bin_len, int key,
+                          const std::vector<uint32_t>& q_ppm, uint32_t* d_values, uint32_t* d_counted, QuantilesResult* res) const {
+    int rc = x3_corpus_level_quantiles_dev(ctx.raw(), raw_, d_levels, n_rows, bin_len, key, q_ppm.data(), (uint32_t)q_ppm.size(),
+                                           d_values, d_counted);
+    if (rc != X3_OK) return static_cast<X3Error>(rc);
+    QuantilesResult r;
+    rc = x3_level_quantiles_result(ctx.raw(), &r.n_empty, &r.first_empty);
+    if (res) *res = r;
+    return static_cast<X3Error>(rc);
+  }
+  // Thresholds of every entry (x3_corpus_level_thresholds_dev): n_entries records at d_thr.  Waits for the call.
+  X3Error level_thresholds(Context& ctx, const x3_level* d_levels, uint64_t n_rows, uint64_t bin_len, const x3_threshold_rule& rule,
+                           x3_event_threshold* d_thr, QuantilesResult* res) const {
+    int rc = x3_corpus_level_thresholds_dev(ctx.raw(), raw_, d_levels, n_rows, bin_len, &rule, d_thr);
+    if (rc != X3_OK) return static_cast<X3Error>(rc);
+    QuantilesResult r;
+    rc = x3_level_quantiles_result(ctx.raw(), &r.n_empty, &r.first_empty);
+    if (res) *res = r;
+    return static_cast<X3Error>(rc);
+  }
+  // Events with entry e's two values at d_thr[e] (x3_corpus_events_adaptive_dev); otherwise as events().  Waits for the call.
+  X3Error events_adaptive(Context& ctx, const x3_level* d_levels, uint64_t n_rows, uint64_t bin_len, const x3_event_rule& rule,
+                          const x3_event_threshold* d_thr, uint32_t* d_entries, uint64_t* d_starts, uint32_t* d_lens,
+                          x3_level* d_event_levels, uint64_t cap, uint64_t* d_count, uint64_t* count) const {
+    int rc = x3_corpus_events_adaptive_dev(ctx.raw(), raw_, d_levels, n_rows, bin_len, &rule, d_thr, d_entries, d_starts, d_lens,
+                                           d_event_levels, cap, d_count);
     if (rc != X3_OK) return static_cast<X3Error>(rc);
     return static_cast<X3Error>(x3_events_result(ctx.raw(), count));
   }

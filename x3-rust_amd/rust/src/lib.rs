@@ -82,6 +82,28 @@ pub mod ffi {
         pub max_bins: u32,
         pub reserved: u32,
     }
+    /// `x3_threshold_rule`: per criterion `thr = clamp(floor(quantile(q_ppm) * mul / div) + add, 1, limit)`; `div == 0`: off
+    /// (`x3_level_thresholds_dev`; 32 bytes)
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+    pub struct x3_threshold_rule {
+        pub peak_q_ppm: u32,
+        pub peak_mul: u32,
+        pub peak_div: u32,
+        pub peak_add: u32,
+        pub mean_sq_q_ppm: u32,
+        pub mean_sq_mul: u32,
+        pub mean_sq_div: u32,
+        pub mean_sq_add: u32,
+    }
+    /// `x3_event_threshold`: the events rule's two values for one entry and its counting rows (16 bytes)
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+    pub struct x3_event_threshold {
+        pub mean_sq_min: u64,
+        pub peak_min: u32,
+        pub counted: u32,
+    }
     #[repr(C)]
     #[derive(Clone, Copy, Debug)]
     pub struct x3_rice_code {
@@ -209,6 +231,23 @@ pub mod ffi {
                                     rule: *const x3_event_rule, d_entries: *mut u32, d_starts: *mut u64, d_lens: *mut u32,
                                     d_event_levels: *mut x3_level, cap: u64, d_count: *mut u64) -> c_int;
         pub fn x3_events_result(ctx: *mut x3_ctx, count: *mut u64) -> c_int;
+        pub fn x3_level_quantiles_dev(ctx: *mut x3_ctx, d_levels: *const x3_level, n_bins: u64, bin_len: u64, d_total: *const u64,
+                                      key: c_int, q_ppm: *const u32, n_q: u32, d_values: *mut u32, d_counted: *mut u32) -> c_int;
+        pub fn x3_corpus_level_quantiles_dev(ctx: *mut x3_ctx, corpus: *const x3_corpus, d_levels: *const x3_level, n_rows: u64,
+                                             bin_len: u64, key: c_int, q_ppm: *const u32, n_q: u32, d_values: *mut u32,
+                                             d_counted: *mut u32) -> c_int;
+        pub fn x3_level_quantiles_result(ctx: *mut x3_ctx, n_empty: *mut u64, first_empty: *mut u64) -> c_int;
+        pub fn x3_level_thresholds_dev(ctx: *mut x3_ctx, d_levels: *const x3_level, n_bins: u64, bin_len: u64, d_total: *const u64,
+                                       rule: *const x3_threshold_rule, d_thr: *mut x3_event_threshold) -> c_int;
+        pub fn x3_corpus_level_thresholds_dev(ctx: *mut x3_ctx, corpus: *const x3_corpus, d_levels: *const x3_level, n_rows: u64,
+                                              bin_len: u64, rule: *const x3_threshold_rule, d_thr: *mut x3_event_threshold) -> c_int;
+        pub fn x3_events_adaptive_dev(ctx: *mut x3_ctx, d_levels: *const x3_level, n_bins: u64, bin_len: u64, d_total: *const u64,
+                                      rule: *const x3_event_rule, d_thr: *const x3_event_threshold, d_starts: *mut u64,
+                                      d_lens: *mut u32, d_event_levels: *mut x3_level, cap: u64, d_count: *mut u64) -> c_int;
+        pub fn x3_corpus_events_adaptive_dev(ctx: *mut x3_ctx, corpus: *const x3_corpus, d_levels: *const x3_level, n_rows: u64,
+                                             bin_len: u64, rule: *const x3_event_rule, d_thr: *const x3_event_threshold,
+                                             d_entries: *mut u32, d_starts: *mut u64, d_lens: *mut u32,
+                                             d_event_levels: *mut x3_level, cap: u64, d_count: *mut u64) -> c_int;
         pub fn x3_range_levels_dev(ctx: *mut x3_ctx, d_x3: *const u8, x3_len: u64, d_frame_offsets: *const u64,
                                    d_sample_offsets: *const u64, n_frames: u64, p: *const x3_params, d_seg_index: *const u64,
                                    seg_blocks: u32, d_starts: *const u64, d_lens: *const u32, n_ranges: u64, bin_len: u64,
@@ -1401,6 +1440,83 @@ pub mod device {
         Ok(count)
     }
 
+    /// The key of a level record the quantiles are taken of: `max(max, -min)` or `floor(sum_sq / n)` -- the largest `peak_min` /
+    /// `mean_sq_min` at which the events rule still calls the bin hot
+    #[derive(Clone, Copy, Debug, PartialEq, Eq)]
+    pub enum LevelKey {
+        Peak = 0,
+        MeanSq = 1,
+    }
+    /// `x3_threshold_rule`: per criterion `(q_ppm, mul, div, add)`, `div == 0`: off
+    pub type ThresholdRule = ffi::x3_threshold_rule;
+    /// `x3_event_threshold`: `mean_sq_min`, `peak_min` (0: off) and `counted` of one entry
+    pub type EventThreshold = ffi::x3_event_threshold;
+
+    /// Level quantiles (`x3_level_quantiles_dev`; not in the reference crate): quantile j (`q_ppm[j]` millionths, 1 .. 8 of
+    /// them) of the keys of the counting rows (inside the stream, `n != 0`) of `n_bins` level records into `d_values` (u32 per
+    /// quantile), their number K into `d_counted` (one u32): `sorted(keys)[(K - 1) * q / 1_000_000]`, 0 when K == 0.
+    /// `sample_offsets` as in `events`.  Waits: -> (entries without a counting row, the first of them or 1)
+    #[allow(clippy::too_many_arguments)]
+    pub fn level_quantiles<'g>(gpu: &'g Gpu, d_levels: &Buffer<'g>, n_bins: usize, bin_len: u64, sample_offsets: &Buffer<'g>,
+                               n_frames: usize, key: LevelKey, q_ppm: &[u32], d_values: &mut Buffer<'g>, d_counted: &mut Buffer<'g>)
+                               -> error::Result<(u64, u64)> {
+        if d_levels.len() < core::mem::size_of::<Level>() * n_bins || sample_offsets.len() < 8 * (n_frames + 1)
+            || d_values.len() < 4 * q_ppm.len() || d_counted.len() < 4 {
+            return Err(X3Error::BadArg);
+        }
+        error::check(unsafe {
+            ffi::x3_level_quantiles_dev(gpu.raw(), d_levels.as_ptr::<Level>() as *const Level, n_bins as u64, bin_len,
+                                        (sample_offsets.as_ptr::<u64>() as *const u64).add(n_frames), key as i32, q_ppm.as_ptr(),
+                                        q_ppm.len() as u32, d_values.as_ptr::<u32>(), d_counted.as_ptr::<u32>())
+        })?;
+        let (mut n_empty, mut first) = (0u64, 0u64);
+        error::check(unsafe { ffi::x3_level_quantiles_result(gpu.raw(), &mut n_empty, &mut first) })?;
+        Ok((n_empty, first))
+    }
+
+    /// Thresholds from quantiles (`x3_level_thresholds_dev`): one `EventThreshold` into `d_thr` (16 bytes) by `rule`.  Waits:
+    /// -> as `level_quantiles`
+    pub fn level_thresholds<'g>(gpu: &'g Gpu, d_levels: &Buffer<'g>, n_bins: usize, bin_len: u64, sample_offsets: &Buffer<'g>,
+                                n_frames: usize, rule: &ThresholdRule, d_thr: &mut Buffer<'g>) -> error::Result<(u64, u64)> {
+        if d_levels.len() < core::mem::size_of::<Level>() * n_bins || sample_offsets.len() < 8 * (n_frames + 1)
+            || d_thr.len() < core::mem::size_of::<EventThreshold>() {
+            return Err(X3Error::BadArg);
+        }
+        error::check(unsafe {
+            ffi::x3_level_thresholds_dev(gpu.raw(), d_levels.as_ptr::<Level>() as *const Level, n_bins as u64, bin_len,
+                                         (sample_offsets.as_ptr::<u64>() as *const u64).add(n_frames), rule,
+                                         d_thr.as_ptr::<EventThreshold>())
+        })?;
+        let (mut n_empty, mut first) = (0u64, 0u64);
+        error::check(unsafe { ffi::x3_level_quantiles_result(gpu.raw(), &mut n_empty, &mut first) })?;
+        Ok((n_empty, first))
+    }
+
+    /// Events with the rule's two values (both 0 in `rule`) taken from the `EventThreshold` in `d_thr`
+    /// (`x3_events_adaptive_dev`); otherwise as `events`.  Waits: -> the events found
+    #[allow(clippy::too_many_arguments)]
+    pub fn events_adaptive<'g>(gpu: &'g Gpu, d_levels: &Buffer<'g>, n_bins: usize, bin_len: u64, sample_offsets: &Buffer<'g>,
+                               n_frames: usize, rule: &EventRule, d_thr: &Buffer<'g>, d_starts: &mut Buffer<'g>,
+                               d_lens: &mut Buffer<'g>, d_event_levels: Option<&mut Buffer<'g>>, cap: usize,
+                               d_count: &mut Buffer<'g>) -> error::Result<u64> {
+        if d_levels.len() < core::mem::size_of::<Level>() * n_bins || sample_offsets.len() < 8 * (n_frames + 1)
+            || d_thr.len() < core::mem::size_of::<EventThreshold>()
+            || d_starts.len() < 8 * cap || d_lens.len() < 4 * cap || d_count.len() < 8
+            || d_event_levels.as_ref().map_or(false, |b| b.len() < core::mem::size_of::<Level>() * cap) {
+            return Err(X3Error::BadArg);
+        }
+        let el_ptr = match d_event_levels { Some(b) => b.as_ptr::<Level>(), None => core::ptr::null_mut() };
+        error::check(unsafe {
+            ffi::x3_events_adaptive_dev(gpu.raw(), d_levels.as_ptr::<Level>() as *const Level, n_bins as u64, bin_len,
+                                        (sample_offsets.as_ptr::<u64>() as *const u64).add(n_frames), rule,
+                                        d_thr.as_ptr::<EventThreshold>() as *const EventThreshold, d_starts.as_ptr::<u64>(),
+                                        d_lens.as_ptr::<u32>(), el_ptr, cap as u64, d_count.as_ptr::<u64>())
+        })?;
+        let mut count = 0u64;
+        error::check(unsafe { ffi::x3_events_result(gpu.raw(), &mut count) })?;
+        Ok(count)
+    }
+
     /// Range levels (`x3_range_levels_dev`; not in the reference crate): the `Level` records of range w = positions
     /// `[starts[w], starts[w] + lens[w])`, bins of `bin_len` positions counted from the range's own start (0: one bin), max(1,
     /// ceil(len / bin_len)) rows each.  A frame with a status other than 0 adds nothing and gives the range its status.
@@ -1598,6 +1714,70 @@ pub mod device {
                 ffi::x3_corpus_events_dev(self.gpu.raw(), self.raw, d_levels.as_ptr::<Level>() as *const Level, n_rows as u64, bin_len,
                                           rule, d_entries.as_ptr::<u32>(), d_starts.as_ptr::<u64>(), d_lens.as_ptr::<u32>(), el_ptr,
                                           cap as u64, d_count.as_ptr::<u64>())
+            })?;
+            let mut count = 0u64;
+            error::check(unsafe { ffi::x3_events_result(self.gpu.raw(), &mut count) })?;
+            Ok(count)
+        }
+    }
+
+    impl<'g> Corpus<'g> {
+        /// Level quantiles of every entry (`x3_corpus_level_quantiles_dev`) over the `n_rows` records `levels` wrote: as
+        /// `device::level_quantiles`, `d_values` u32 `[n_entries * q_ppm.len()]`, `d_counted` u32 `[n_entries]`.  Waits: ->
+        /// (entries without a counting row, the first of them or the entry count)
+        #[allow(clippy::too_many_arguments)]
+        pub fn level_quantiles(&self, d_levels: &Buffer<'g>, n_rows: usize, bin_len: u64, key: LevelKey, q_ppm: &[u32],
+                               d_values: &mut Buffer<'g>, d_counted: &mut Buffer<'g>) -> error::Result<(u64, u64)> {
+            let n_ent = self.info().0 as usize;
+            if d_levels.len() < core::mem::size_of::<Level>() * n_rows || d_values.len() < 4 * n_ent * q_ppm.len()
+                || d_counted.len() < 4 * n_ent {
+                return Err(X3Error::BadArg);
+            }
+            error::check(unsafe {
+                ffi::x3_corpus_level_quantiles_dev(self.gpu.raw(), self.raw, d_levels.as_ptr::<Level>() as *const Level, n_rows as u64,
+                                                   bin_len, key as i32, q_ppm.as_ptr(), q_ppm.len() as u32,
+                                                   d_values.as_ptr::<u32>(), d_counted.as_ptr::<u32>())
+            })?;
+            let (mut n_empty, mut first) = (0u64, 0u64);
+            error::check(unsafe { ffi::x3_level_quantiles_result(self.gpu.raw(), &mut n_empty, &mut first) })?;
+            Ok((n_empty, first))
+        }
+
+        /// Thresholds of every entry (`x3_corpus_level_thresholds_dev`): `n_entries` `EventThreshold` records into `d_thr`.
+        /// Waits: -> as `level_quantiles`
+        pub fn level_thresholds(&self, d_levels: &Buffer<'g>, n_rows: usize, bin_len: u64, rule: &ThresholdRule,
+                                d_thr: &mut Buffer<'g>) -> error::Result<(u64, u64)> {
+            let n_ent = self.info().0 as usize;
+            if d_levels.len() < core::mem::size_of::<Level>() * n_rows || d_thr.len() < core::mem::size_of::<EventThreshold>() * n_ent {
+                return Err(X3Error::BadArg);
+            }
+            error::check(unsafe {
+                ffi::x3_corpus_level_thresholds_dev(self.gpu.raw(), self.raw, d_levels.as_ptr::<Level>() as *const Level, n_rows as u64,
+                                                    bin_len, rule, d_thr.as_ptr::<EventThreshold>())
+            })?;
+            let (mut n_empty, mut first) = (0u64, 0u64);
+            error::check(unsafe { ffi::x3_level_quantiles_result(self.gpu.raw(), &mut n_empty, &mut first) })?;
+            Ok((n_empty, first))
+        }
+
+        /// Events with entry e's two values in `d_thr[e]` (`x3_corpus_events_adaptive_dev`; both 0 in `rule`); otherwise as
+        /// `events`.  Waits: -> the events found
+        #[allow(clippy::too_many_arguments)]
+        pub fn events_adaptive(&self, d_levels: &Buffer<'g>, n_rows: usize, bin_len: u64, rule: &EventRule, d_thr: &Buffer<'g>,
+                               d_entries: &mut Buffer<'g>, d_starts: &mut Buffer<'g>, d_lens: &mut Buffer<'g>,
+                               d_event_levels: Option<&mut Buffer<'g>>, cap: usize, d_count: &mut Buffer<'g>) -> error::Result<u64> {
+            let n_ent = self.info().0 as usize;
+            if d_levels.len() < core::mem::size_of::<Level>() * n_rows || d_thr.len() < core::mem::size_of::<EventThreshold>() * n_ent
+                || d_entries.len() < 4 * cap || d_starts.len() < 8 * cap || d_lens.len() < 4 * cap || d_count.len() < 8
+                || d_event_levels.as_ref().map_or(false, |b| b.len() < core::mem::size_of::<Level>() * cap) {
+                return Err(X3Error::BadArg);
+            }
+            let el_ptr = match d_event_levels { Some(b) => b.as_ptr::<Level>(), None => core::ptr::null_mut() };
+            error::check(unsafe {
+                ffi::x3_corpus_events_adaptive_dev(self.gpu.raw(), self.raw, d_levels.as_ptr::<Level>() as *const Level, n_rows as u64,
+                                                   bin_len, rule, d_thr.as_ptr::<EventThreshold>() as *const EventThreshold,
+                                                   d_entries.as_ptr::<u32>(), d_starts.as_ptr::<u64>(), d_lens.as_ptr::<u32>(), el_ptr,
+                                                   cap as u64, d_count.as_ptr::<u64>())
             })?;
             let mut count = 0u64;
             error::check(unsafe { ffi::x3_events_result(self.gpu.raw(), &mut count) })?;

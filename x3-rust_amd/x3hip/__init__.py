@@ -63,6 +63,8 @@ SYMBOLS = [
     "x3_corpus_destroy",
     "x3_levels_dev", "x3_levels_result", "x3_corpus_levels_rows", "x3_corpus_levels_dev",
     "x3_events_dev", "x3_corpus_events_dev", "x3_events_result",
+    "x3_level_quantiles_dev", "x3_corpus_level_quantiles_dev", "x3_level_quantiles_result",
+    "x3_level_thresholds_dev", "x3_corpus_level_thresholds_dev", "x3_events_adaptive_dev", "x3_corpus_events_adaptive_dev",
     "x3_range_levels_dev", "x3_corpus_range_levels_dev", "x3_range_levels_result",
     "x3_tune_candidate", "x3_tuner_create", "x3_tuner_add_dev", "x3_tuner_result", "x3_tuner_max_payloads",
     "x3_tuner_reset", "x3_tuner_destroy", "x3_tune", "x3_x3a_encode_tuned",
@@ -92,6 +94,25 @@ class EventRule(C.Structure):
 
 EVENT_RULE_DTYPE = np.dtype([("mean_sq_min", "<u8"), ("peak_min", "<u4"), ("join_bins", "<u4"), ("min_bins", "<u4"),
                              ("pad_bins", "<u4"), ("max_bins", "<u4"), ("reserved", "<u4")])
+
+
+LEVEL_KEY_PEAK, LEVEL_KEY_MEAN_SQ = 0, 1   # x3_level_quantiles_dev: max(max, -min) / floor(sum_sq / n)
+
+
+class ThresholdRule(C.Structure):
+    """x3_threshold_rule: per criterion thr = clamp(floor(quantile(q_ppm) * mul / div) + add, 1, limit); div == 0: off"""
+    _fields_ = [("peak_q_ppm", C.c_uint32), ("peak_mul", C.c_uint32), ("peak_div", C.c_uint32), ("peak_add", C.c_uint32),
+                ("mean_sq_q_ppm", C.c_uint32), ("mean_sq_mul", C.c_uint32), ("mean_sq_div", C.c_uint32),
+                ("mean_sq_add", C.c_uint32)]
+
+    @classmethod
+    def make(cls, peak=None, mean_sq=None):
+        """peak / mean_sq: (q_ppm, mul, div, add) or None for a criterion that is off"""
+        return cls(*(tuple(peak or (0, 0, 0, 0)) + tuple(mean_sq or (0, 0, 0, 0))))
+
+
+# x3_event_threshold: the two values of the events rule for one entry, and its counting rows (16 bytes)
+EVENT_THRESHOLD_DTYPE = np.dtype([("mean_sq_min", "<u8"), ("peak_min", "<u4"), ("counted", "<u4")])
 
 
 def event_levels_view(t):
@@ -264,6 +285,13 @@ def lib():
     L.x3_events_dev.argtypes = [vp, vp, u64, u64, vp, C.POINTER(EventRule), vp, vp, vp, u64, vp]
     L.x3_corpus_events_dev.argtypes = [vp, vp, vp, u64, u64, C.POINTER(EventRule), vp, vp, vp, vp, u64, vp]
     L.x3_events_result.argtypes = [vp, C.POINTER(u64)]
+    L.x3_level_quantiles_dev.argtypes = [vp, vp, u64, u64, vp, C.c_int, C.POINTER(C.c_uint32), C.c_uint32, vp, vp]
+    L.x3_corpus_level_quantiles_dev.argtypes = [vp, vp, vp, u64, u64, C.c_int, C.POINTER(C.c_uint32), C.c_uint32, vp, vp]
+    L.x3_level_quantiles_result.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
+    L.x3_level_thresholds_dev.argtypes = [vp, vp, u64, u64, vp, C.POINTER(ThresholdRule), vp]
+    L.x3_corpus_level_thresholds_dev.argtypes = [vp, vp, vp, u64, u64, C.POINTER(ThresholdRule), vp]
+    L.x3_events_adaptive_dev.argtypes = [vp, vp, u64, u64, vp, C.POINTER(EventRule), vp, vp, vp, vp, u64, vp]
+    L.x3_corpus_events_adaptive_dev.argtypes = [vp, vp, vp, u64, u64, C.POINTER(EventRule), vp, vp, vp, vp, vp, u64, vp]
     L.x3_range_levels_dev.argtypes = [vp, vp, u64, vp, vp, u64, PP, vp, u32, vp, vp, u64, u64, u64, vp, u64, vp, vp]
     L.x3_corpus_range_levels_dev.argtypes = [vp, vp, vp, vp, vp, u64, u64, u64, vp, u64, vp, vp]
     L.x3_range_levels_result.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(i32), C.POINTER(u64)]
@@ -1015,6 +1043,48 @@ class Context:
         rc = lib().x3_events_result(self._h, C.byref(n))
         return rc, n.value
 
+    def level_quantiles_dev(self, d_levels, n_bins, bin_len, d_total, key, q_ppm, d_values, d_counted):
+        """x3_level_quantiles_dev: the quantiles q_ppm (millionths, 1 .. 8 of them) of the keys (LEVEL_KEY_PEAK /
+        LEVEL_KEY_MEAN_SQ) of n_bins level records into d_values (u32 [len(q_ppm)]) and K into d_counted (u32);
+        asynchronous -> rc"""
+        q = (C.c_uint32 * len(q_ppm))(*q_ppm)
+        return lib().x3_level_quantiles_dev(self._h, d_levels, n_bins, bin_len, d_total, key, q, len(q_ppm), d_values, d_counted)
+
+    def corpus_level_quantiles_dev(self, corpus, d_levels, n_rows, bin_len, key, q_ppm, d_values, d_counted):
+        """x3_corpus_level_quantiles_dev: the same per entry over the rows of corpus_levels_dev: d_values u32
+        [n_entries * len(q_ppm)], d_counted u32 [n_entries]; asynchronous"""
+        q = (C.c_uint32 * len(q_ppm))(*q_ppm)
+        return lib().x3_corpus_level_quantiles_dev(self._h, corpus._h, d_levels, n_rows, bin_len, key, q, len(q_ppm), d_values,
+                                                   d_counted)
+
+    def level_quantiles_result(self):
+        """-> (rc, n_empty, first_empty) of the last quantiles or thresholds call: entries without a counting row, the first
+        of them (the entry count if none)"""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        rc = lib().x3_level_quantiles_result(self._h, C.byref(a), C.byref(b))
+        return rc, a.value, b.value
+
+    def level_thresholds_dev(self, d_levels, n_bins, bin_len, d_total, threshold_rule, d_thr):
+        """x3_level_thresholds_dev: one EVENT_THRESHOLD_DTYPE record from the quantiles a ThresholdRule names; asynchronous;
+        level_quantiles_result waits"""
+        return lib().x3_level_thresholds_dev(self._h, d_levels, n_bins, bin_len, d_total, C.byref(threshold_rule), d_thr)
+
+    def corpus_level_thresholds_dev(self, corpus, d_levels, n_rows, bin_len, threshold_rule, d_thr):
+        """x3_corpus_level_thresholds_dev: a record per entry; asynchronous"""
+        return lib().x3_corpus_level_thresholds_dev(self._h, corpus._h, d_levels, n_rows, bin_len, C.byref(threshold_rule), d_thr)
+
+    def events_adaptive_dev(self, d_levels, n_bins, bin_len, d_total, rule, d_thr, d_starts, d_lens, d_event_levels, cap, d_count):
+        """x3_events_adaptive_dev: events_dev with the rule's two values (both 0 in `rule`) taken from the record at d_thr;
+        asynchronous; events_result waits"""
+        return lib().x3_events_adaptive_dev(self._h, d_levels, n_bins, bin_len, d_total, C.byref(rule), d_thr, d_starts, d_lens,
+                                            d_event_levels, cap, d_count)
+
+    def corpus_events_adaptive_dev(self, corpus, d_levels, n_rows, bin_len, rule, d_thr, d_entries, d_starts, d_lens,
+                                   d_event_levels, cap, d_count):
+        """x3_corpus_events_adaptive_dev: corpus_events_dev with the thresholds of entry e at d_thr[e]; asynchronous"""
+        return lib().x3_corpus_events_adaptive_dev(self._h, corpus._h, d_levels, n_rows, bin_len, C.byref(rule), d_thr, d_entries,
+                                                   d_starts, d_lens, d_event_levels, cap, d_count)
+
     def range_levels_dev(self, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, params, d_starts, d_lens, n_ranges,
                          bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status, d_seg_index=None, seg_blocks=0):
         """x3_range_levels_dev: the x3_level records of range w = [d_starts[w], d_starts[w] + d_lens[w]), bins of bin_len
@@ -1251,6 +1321,45 @@ def _events_torch(ctx, n_rows, capacity, with_entries, enqueue_levels, enqueue_e
     return (entries,) + out if with_entries else out
 
 
+def _level_quantiles_torch(ctx, n_rows, n_ent, n_q, enqueue_levels, enqueue_quantiles):
+    """The torch side of WindowSource.level_quantiles / Corpus.level_quantiles: the levels call and the quantiles call back
+    to back -> (values int32 [n_ent, n_q], counted int32 [n_ent]) on the device (the bits of the uint32 words)."""
+    import torch
+    dev = torch.device("cuda", torch.cuda.current_device())
+    levels = torch.empty((n_rows, LEVEL_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    values = torch.empty((n_ent, n_q), dtype=torch.int32, device=dev)
+    counted = torch.empty(n_ent, dtype=torch.int32, device=dev)
+    torch.cuda.current_stream().synchronize()    # (the context's stream is not torch's)
+    rc = enqueue_levels(levels.data_ptr())
+    if rc:
+        raise X3Error(rc, "levels: " + ctx.last_error())
+    rc = enqueue_quantiles(levels.data_ptr(), values.data_ptr(), counted.data_ptr())
+    if rc:
+        ctx.levels_result()
+        raise X3Error(rc, "level quantiles: " + ctx.last_error())
+    rc = ctx.level_quantiles_result()[0] or ctx.levels_result()[0]
+    if rc:
+        raise X3Error(rc, "x3_level_quantiles_result: " + ctx.last_error())
+    return values, counted
+
+
+def _adaptive_events_torch(ctx, n_rows, n_ent, capacity, with_entries, enqueue_levels, enqueue_thresholds, enqueue_events):
+    """The torch side of WindowSource.adaptive_events / Corpus.adaptive_events: levels, thresholds and events back to back,
+    no host trip in between -> what _events_torch returns plus thresholds uint8 [n_ent, 16] (EVENT_THRESHOLD_DTYPE records)."""
+    import torch
+    dev = torch.device("cuda", torch.cuda.current_device())
+    thr = torch.empty((n_ent, EVENT_THRESHOLD_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+
+    def both(d_lv, d_e, d_s, d_l, d_el, d_c):
+        rc = enqueue_thresholds(d_lv, thr.data_ptr())
+        if rc:
+            return rc
+        rc = enqueue_events(d_lv, thr.data_ptr(), d_e, d_s, d_l, d_el, d_c)
+        rq = ctx.level_quantiles_result()[0]    # (its own slot: read whatever the events call said)
+        return rc or rq
+    return _events_torch(ctx, n_rows, capacity, with_entries, enqueue_levels, both) + (thr,)
+
+
 class WindowSource:
     """Random access to one mono stream in HBM: windows of samples [start, start + length) as rows of a batch.
 
@@ -1426,6 +1535,48 @@ class WindowSource:
             lambda d_lv: self.ctx.levels_dev(self.d_x3, self.x3_len, self.d_frame_offsets, self.d_sample_offsets, self.n_frames,
                                              self.params, bin_len, d_lv, n_bins, None, self.d_seg_index, self.seg_blocks),
             lambda d_lv, d_e, d_s, d_l, d_el, d_c: self.events_into(d_lv, n_bins, bin_len, rule, d_s, d_l, d_el, capacity, d_c))
+
+    def level_quantiles_into(self, d_levels, n_bins, bin_len, key, q_ppm, d_values, d_counted):
+        """enqueue x3_level_quantiles_dev over n_bins records this source's levels_dev wrote (device pointers); -> rc;
+        Context.level_quantiles_result waits"""
+        return self.ctx.level_quantiles_dev(d_levels, n_bins, bin_len, self.d_sample_offsets + 8 * self.n_frames, key, q_ppm,
+                                            d_values, d_counted)
+
+    def level_thresholds_into(self, d_levels, n_bins, bin_len, threshold_rule, d_thr):
+        """enqueue x3_level_thresholds_dev (one record at d_thr); -> rc; Context.level_quantiles_result waits"""
+        return self.ctx.level_thresholds_dev(d_levels, n_bins, bin_len, self.d_sample_offsets + 8 * self.n_frames, threshold_rule,
+                                             d_thr)
+
+    def adaptive_events_into(self, d_levels, n_bins, bin_len, rule, d_thr, d_starts, d_lens, d_event_levels, cap, d_count):
+        """enqueue x3_events_adaptive_dev with the record at d_thr; -> rc; Context.events_result waits"""
+        return self.ctx.events_adaptive_dev(d_levels, n_bins, bin_len, self.d_sample_offsets + 8 * self.n_frames, rule, d_thr,
+                                            d_starts, d_lens, d_event_levels, cap, d_count)
+
+    def level_quantiles(self, bin_len, key, q_ppm):
+        """Levels of bins of bin_len positions, then the quantiles q_ppm (millionths) of their keys, on the device ->
+        (values int32 [1, len(q_ppm)], counted int32 [1]) torch tensors"""
+        if not 0 < bin_len <= 0xFFFFFFFF:
+            raise ValueError("bin_len: 1 .. 2^32 - 1")
+        n_bins = max(1, -(-self.total // bin_len))
+        return _level_quantiles_torch(
+            self.ctx, n_bins, 1, len(q_ppm),
+            lambda d_lv: self.ctx.levels_dev(self.d_x3, self.x3_len, self.d_frame_offsets, self.d_sample_offsets, self.n_frames,
+                                             self.params, bin_len, d_lv, n_bins, None, self.d_seg_index, self.seg_blocks),
+            lambda d_lv, d_v, d_k: self.level_quantiles_into(d_lv, n_bins, bin_len, key, q_ppm, d_v, d_k))
+
+    def adaptive_events(self, bin_len, threshold_rule, rule, capacity):
+        """events() with the rule's two values (both 0 in `rule`) chosen on the device by `threshold_rule` (a ThresholdRule)
+        -> (starts, lens, count, event_levels, thresholds uint8 [1, 16])"""
+        if not 0 < bin_len <= 0xFFFFFFFF:
+            raise ValueError("bin_len: 1 .. 2^32 - 1")
+        n_bins = max(1, -(-self.total // bin_len))
+        return _adaptive_events_torch(
+            self.ctx, n_bins, 1, capacity, False,
+            lambda d_lv: self.ctx.levels_dev(self.d_x3, self.x3_len, self.d_frame_offsets, self.d_sample_offsets, self.n_frames,
+                                             self.params, bin_len, d_lv, n_bins, None, self.d_seg_index, self.seg_blocks),
+            lambda d_lv, d_t: self.level_thresholds_into(d_lv, n_bins, bin_len, threshold_rule, d_t),
+            lambda d_lv, d_t, d_e, d_s, d_l, d_el, d_c: self.adaptive_events_into(d_lv, n_bins, bin_len, rule, d_t, d_s, d_l, d_el,
+                                                                                  capacity, d_c))
 
     def close(self):
         for p in self._own:
@@ -1719,6 +1870,51 @@ class Corpus:
             self.ctx, n_rows, capacity, True,
             lambda d_lv: self.ctx.corpus_levels_dev(self, bin_len, d_lv, n_rows, None),
             lambda d_lv, d_e, d_s, d_l, d_el, d_c: self.events_into(d_lv, n_rows, bin_len, rule, d_e, d_s, d_l, d_el, capacity, d_c))
+
+    def level_quantiles_into(self, d_levels, n_rows, bin_len, key, q_ppm, d_values, d_counted):
+        """enqueue x3_corpus_level_quantiles_dev over the n_rows records Context.corpus_levels_dev wrote; -> rc;
+        Context.level_quantiles_result waits"""
+        if self._h is None:
+            raise ValueError("the corpus is closed")
+        return self.ctx.corpus_level_quantiles_dev(self, d_levels, n_rows, bin_len, key, q_ppm, d_values, d_counted)
+
+    def level_thresholds_into(self, d_levels, n_rows, bin_len, threshold_rule, d_thr):
+        """enqueue x3_corpus_level_thresholds_dev (n_entries records at d_thr); -> rc"""
+        if self._h is None:
+            raise ValueError("the corpus is closed")
+        return self.ctx.corpus_level_thresholds_dev(self, d_levels, n_rows, bin_len, threshold_rule, d_thr)
+
+    def adaptive_events_into(self, d_levels, n_rows, bin_len, rule, d_thr, d_entries, d_starts, d_lens, d_event_levels, cap,
+                             d_count):
+        """enqueue x3_corpus_events_adaptive_dev with entry e's thresholds at d_thr[e]; -> rc; Context.events_result waits"""
+        if self._h is None:
+            raise ValueError("the corpus is closed")
+        return self.ctx.corpus_events_adaptive_dev(self, d_levels, n_rows, bin_len, rule, d_thr, d_entries, d_starts, d_lens,
+                                                   d_event_levels, cap, d_count)
+
+    def level_quantiles(self, bin_len, key, q_ppm):
+        """Levels of every entry, then per entry the quantiles q_ppm (millionths) of their keys, on the device ->
+        (values int32 [n_entries, len(q_ppm)], counted int32 [n_entries]) torch tensors"""
+        if not 0 < bin_len <= 0xFFFFFFFF:
+            raise ValueError("bin_len: 1 .. 2^32 - 1")
+        n_rows = int(self.levels_rows(bin_len)[-1])
+        return _level_quantiles_torch(
+            self.ctx, n_rows, self.n_entries, len(q_ppm),
+            lambda d_lv: self.ctx.corpus_levels_dev(self, bin_len, d_lv, n_rows, None),
+            lambda d_lv, d_v, d_k: self.level_quantiles_into(d_lv, n_rows, bin_len, key, q_ppm, d_v, d_k))
+
+    def adaptive_events(self, bin_len, threshold_rule, rule, capacity):
+        """events() with a threshold per entry chosen on the device by `threshold_rule` -> (entries, starts, lens, count,
+        event_levels, thresholds uint8 [n_entries, 16])"""
+        if not 0 < bin_len <= 0xFFFFFFFF:
+            raise ValueError("bin_len: 1 .. 2^32 - 1")
+        n_rows = int(self.levels_rows(bin_len)[-1])
+        return _adaptive_events_torch(
+            self.ctx, n_rows, self.n_entries, capacity, True,
+            lambda d_lv: self.ctx.corpus_levels_dev(self, bin_len, d_lv, n_rows, None),
+            lambda d_lv, d_t: self.level_thresholds_into(d_lv, n_rows, bin_len, threshold_rule, d_t),
+            lambda d_lv, d_t, d_e, d_s, d_l, d_el, d_c: self.adaptive_events_into(d_lv, n_rows, bin_len, rule, d_t, d_e, d_s, d_l,
+                                                                                  d_el, capacity, d_c))
 
     def close(self):
         if self._h is not None:
