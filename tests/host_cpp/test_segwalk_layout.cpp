@@ -2,10 +2,13 @@
 // span counts against their formula, the refusals, and the carved pieces -- disjoint, aligned for their elements, long
 // enough for what the kernels of x3_streams_kernel.h index, inside the returned size, the entry table in ONE piece (it
 // goes up in one copy); the batch decode's block: the same walk pieces, its own behind them.  The workspaces of the windows /
-// ranges calls and of the levels calls (windows_carve, levels_carve): every piece's offset and the total against the chains
-// of rounded offsets that laid them out before there was a carver, written out below -- the layout must not move, a
-// same-size workspace keeps the context's allocations where they are.  Host code only: no context.
-// Prints "ok tables=<cases> carves=<cases> windows=<cases> levels=<cases>", or the first cases that disagree and exits 1.
+// ranges calls, the levels calls, the events calls, the range-levels calls and the quantiles / thresholds calls (windows_carve,
+// levels_carve, events_carve, range_levels_carve with range_levels_pairs, quantiles_carve): every piece's offset and the
+// total against the chains of rounded offsets that laid them out before there was a carver (or, for the later three, that
+// their first carve gave), written out below -- the layout must not move, a same-size workspace keeps the context's
+// allocations where they are.  Host code only: no context.
+// Prints "ok tables=<cases> carves=<cases> windows=<cases> levels=<cases> events=<cases> range_levels=<cases>
+// quantiles=<cases>", or the first cases that disagree and exits 1.
 #include <cstdio>
 #include <cstdint>
 #include <vector>
@@ -21,6 +24,12 @@ struct X3WinPlan { uint64_t fa; uint32_t ncov; int32_t status; };
 struct X3WinSummary { unsigned long long n_bad, first, replays, total; };
 struct X3LevSummary { unsigned long long n_bad, first, replays; };
 struct X3LevFrame { uint64_t pos, obase, nlim, b0; };
+// (as x3_events_kernel.h, x3_range_levels_kernel.h and x3_quantiles_kernel.h have them)
+struct X3EvSummary { unsigned long long count, n_runs; };
+struct X3RLevPair { uint64_t f; uint32_t w, lo, hi, r0, b0, cnt; };
+struct X3RLevSummary { X3WinSummary w; unsigned long long overflow; };
+struct X3QSlot { uint32_t prefix, rank; };
+struct X3QSummary { unsigned long long n_empty, first_empty; };
 
 static const uint64_t NS[] = {1, 2, 3, 7, 8, 1000};
 static const uint64_t LENGTHS[] = {0, 1, 21, 65535, 65536, 65537, 3 * 65536};
@@ -142,8 +151,85 @@ static long check_levels(uint64_t F, uint32_t block_len, uint64_t n_rows, uint64
   return 1;
 }
 
+// the events' block: a byte per row, four words per tile of 256 rows, the run tables and the scan of their pieces, the
+// summary, the entries' row prefix
+static long check_events(uint64_t n_rows, uint64_t n_ent) {
+  const uint64_t nt = (n_rows + X3_EVENTS_TILE_ROWS - 1) / X3_EVENTS_TILE_ROWS;
+  const size_t o_hot = 0, o_tp = up(o_hot + n_rows), o_tn = up(o_tp + nt * 4), o_ns = up(o_tn + nt * 4), o_ne = up(o_ns + nt * 4),
+               o_rf = up(o_ne + nt * 4), o_rl = up(o_rf + n_rows * 4), o_po = up(o_rl + n_rows * 4), o_sum = up(o_po + (n_rows + 1) * 8),
+               o_rowf = up(o_sum + sizeof(X3EvSummary)), want_total = o_rowf + (n_ent + 1) * 8;
+  EvWs w, w0;
+  const size_t total = events_carve(reinterpret_cast<char*>(BASE), n_rows, n_ent, &w);
+  if (events_carve(nullptr, n_rows, n_ent, &w0) != total) fail("size without a base differs", n_rows, n_ent);
+  const Placed pieces[] = {PLACED(w, hot, o_hot, n_rows), PLACED(w, tile_prev, o_tp, nt), PLACED(w, tile_next, o_tn, nt),
+                           PLACED(w, tile_ns, o_ns, nt), PLACED(w, tile_ne, o_ne, nt), PLACED(w, run_first, o_rf, n_rows),
+                           PLACED(w, run_last, o_rl, n_rows), PLACED(w, piece_off, o_po, n_rows + 1), PLACED(w, sum, o_sum, 1),
+                           PLACED(w, row_first, o_rowf, n_ent + 1)};
+  check_placed(pieces, 10, total, want_total, n_rows, n_ent);
+  return 1;
+}
+
+// the range levels' block: per range the plan, two scans, the rows that have room, the plan's starts; per frame the verdicts;
+// per pair its cut and the scan of the bin counts; the partial rows; scratch; the summary (the end, not rounded).  P: the
+// pairs, n * max_frames or 4 * (F + n), whichever is less; *arm: which it was
+static long check_range_levels(uint64_t n, uint64_t F, uint64_t max_frames, uint64_t rows_cap, uint32_t block_len, int* arm) {
+  const uint64_t P = n * max_frames < 4 * (F + n) ? n * max_frames : 4 * (F + n);
+  *arm = n * max_frames < 4 * (F + n) ? 0 : 1;
+  if (range_levels_pairs(n, F, max_frames) != P) fail("range_levels_pairs", n, F);
+  const uint32_t scratch_per = levels_scratch_per(block_len);   // (pinned by check_levels)
+  const uint64_t fix_waves = levels_fix_waves(n, scratch_per), scr = (fix_waves > 4 ? fix_waves : 4) * scratch_per;
+  const size_t o_plan = 0, o_cov = up(o_plan + n * sizeof(X3WinPlan)), o_row = up(o_cov + (n + 1) * 8), o_er = up(o_row + (n + 1) * 8),
+               o_gs = up(o_er + n * 4), o_fst = up(o_gs + n * 8), o_pairs = up(o_fst + F * 4), o_prow = up(o_pairs + P * sizeof(X3RLevPair)),
+               o_rows = up(o_prow + (P + 1) * 8), o_scr = up(o_rows + (rows_cap + P) * sizeof(x3_level)), o_sum = up(o_scr + scr * 2),
+               want_total = o_sum + sizeof(X3RLevSummary);
+  RLevWs w, w0;
+  const size_t total = range_levels_carve(reinterpret_cast<char*>(BASE), n, F, P, rows_cap, fix_waves, scratch_per, &w);
+  if (range_levels_carve(nullptr, n, F, P, rows_cap, fix_waves, scratch_per, &w0) != total) fail("size without a base differs", n, F);
+  const Placed pieces[] = {PLACED(w, plan, o_plan, n), PLACED(w, cov_off, o_cov, n + 1), PLACED(w, row_off, o_row, n + 1),
+                           PLACED(w, erows, o_er, n), PLACED(w, gstart, o_gs, n), PLACED(w, fst, o_fst, F), PLACED(w, pairs, o_pairs, P),
+                           PLACED(w, prow, o_prow, P + 1), PLACED(w, rows, o_rows, rows_cap + P), PLACED(w, scratch, o_scr, scr),
+                           PLACED(w, sum, o_sum, 1)};
+  check_placed(pieces, 11, total, want_total, n, F);
+  return 1;
+}
+
+// the quantiles' block: (key, entry) per row, 256 bins and (prefix, rank) per (entry, j), the two values and K per entry,
+// the summary, the entries' row prefix
+static long check_quantiles(uint64_t n_rows, uint64_t n_ent, uint32_t n_q) {
+  const size_t o_keys = 0, o_hist = up(o_keys + n_rows * 8), o_slots = up(o_hist + n_ent * n_q * 256 * 4),
+               o_v0 = up(o_slots + n_ent * n_q * sizeof(X3QSlot)), o_v1 = up(o_v0 + n_ent * 4), o_cnt = up(o_v1 + n_ent * 4),
+               o_sum = up(o_cnt + n_ent * 4), o_rowf = up(o_sum + sizeof(X3QSummary)), want_total = o_rowf + (n_ent + 1) * 8;
+  QWs w, w0;
+  const size_t total = quantiles_carve(reinterpret_cast<char*>(BASE), n_rows, n_ent, n_q, &w);
+  if (quantiles_carve(nullptr, n_rows, n_ent, n_q, &w0) != total) fail("size without a base differs", n_rows, n_ent);
+  const Placed pieces[] = {PLACED(w, keys, o_keys, n_rows), PLACED(w, hist, o_hist, n_ent * n_q * 256), PLACED(w, slots, o_slots, n_ent * n_q),
+                           PLACED(w, val[0], o_v0, n_ent), PLACED(w, val[1], o_v1, n_ent), PLACED(w, counted, o_cnt, n_ent),
+                           PLACED(w, sum, o_sum, 1), PLACED(w, row_first, o_rowf, n_ent + 1)};
+  check_placed(pieces, 8, total, want_total, n_rows, n_ent);
+  return 1;
+}
+
+// rows around the rounding of 256 bytes (a byte, 4 and 8 bytes a row) and around one, two and 256 tiles of 256 rows
+static const uint64_t ROWS[] = {1, 31, 32, 33, 63, 64, 65, 255, 256, 257, 511, 512, 513, 65535, 65536, 65537, 1000003};
+
 int main() {
-  long tables = 0, carves = 0, windows = 0, levels = 0;
+  long tables = 0, carves = 0, windows = 0, levels = 0, events = 0, range_levels = 0, quantiles = 0;
+  for (uint64_t n_rows : ROWS)
+    for (uint64_t n_ent : {(uint64_t)0, (uint64_t)1, (uint64_t)1000}) {
+      events += check_events(n_rows, n_ent);
+      for (uint32_t n_q : {1u, 8u}) quantiles += check_quantiles(n_rows, n_ent, n_q);
+    }
+  long arms[2] = {0, 0};
+  for (uint64_t n : {(uint64_t)1, (uint64_t)2, (uint64_t)255, (uint64_t)256, (uint64_t)257, (uint64_t)1000})
+    for (uint64_t F : FRAMES)
+      for (uint64_t max_frames : {(uint64_t)1, (F + 1) / 2, F})
+        for (uint64_t rows_cap : {(uint64_t)1, n, 3 * n + 1})
+          for (uint32_t bl : {10u, 70000u}) {
+            int arm;
+            range_levels += check_range_levels(n, F, max_frames, rows_cap, bl, &arm);
+            ++arms[arm];
+          }
+  if (!arms[0] || !arms[1]) fail("range_levels_pairs: one arm of the min was never taken", arms[0], arms[1]);
   for (uint64_t F : FRAMES)
     for (uint32_t bl : BLOCK_LENS) {
       for (uint64_t n : WIN_N)
@@ -206,6 +292,7 @@ int main() {
     std::printf("FAILED %d checks\n", failures);
     return 1;
   }
-  std::printf("ok tables=%ld carves=%ld windows=%ld levels=%ld\n", tables, carves, windows, levels);
+  std::printf("ok tables=%ld carves=%ld windows=%ld levels=%ld events=%ld range_levels=%ld quantiles=%ld\n", tables, carves, windows,
+              levels, events, range_levels, quantiles);
   return 0;
 }

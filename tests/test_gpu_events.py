@@ -202,6 +202,21 @@ def test_runs_and_gaps_across_tile_edges(ctx, x3, T):
         check(ctx, x3, records(hot), rule, 2 * n, total=tot, what=rule)
 
 
+def test_more_tiles_and_runs_than_threads_of_the_scans(ctx, x3, T):
+    """x3_events_count_kernel and x3_events_runs_kernel are one workgroup of 1 024 that walks a run of tiles, or of runs, per
+    thread: 1 025 tiles with hot rows at the tile edges (two tiles a thread), 2 049 runs of one row (three runs a thread)"""
+    n = 1025 * T
+    k = np.arange(n)
+    hot = (k % T == 0) | (k % T == T - 1)
+    ev = check(ctx, x3, records(hot), PEAK, 1030, total=BL * n, what="1 025 tiles")
+    assert len(ev) == 1026                                   # (the first row, 1 024 pairs across an edge, the last row)
+    ev = check(ctx, x3, records(hot), PEAK._replace(join_bins=T - 2), 8, total=BL * n, what="1 025 tiles, one run")
+    assert len(ev) == 1
+    n = 2 * 2049 - 1
+    ev = check(ctx, x3, records(np.arange(n) % 2 == 0), PEAK, 2049 + 3, total=BL * n, what="2 049 runs")
+    assert len(ev) == 2049
+
+
 def test_the_mean_square_criterion_at_equality(ctx, x3):
     lv = R.empty(4)
     lv["n"] = [10, 10, 10, 0]

@@ -374,6 +374,59 @@ def test_corpus_rows_are_each_entrys_own_levels(ctx, x3, bin_len, walk):
         corpus.close()
 
 
+# ---- 5b. more items than the one-workgroup scans have threads
+def test_more_frames_than_threads_of_the_scans(ctx, x3):
+    """2 049 frames of 40 samples (the last of 17): x3_window_sample_offsets_kernel and x3_levels_scan_kernel, one workgroup
+    of 1 024 each, walk a run of three frames per thread"""
+    bl, bpf, spf = 20, 2, 40
+    p, op = x3.Params.make(bl, bpf, (0, 1, 3)), O.Params.make(bl, bpf, (0, 1, 3))
+    n = 2048 * spf + 17
+    wav = _content("rice3", n, seed=9)
+    rc, stream, _ = O.encode(wav, op)
+    assert rc == 0
+    dev = TW.Dev(ctx, x3, stream=stream, p=p)
+    try:
+        fo = XC.frame_offsets(stream)
+        frames, ost = _oracle_frames(stream, fo, op)
+        assert dev.F == len(frames) == 2049
+        assert np.array_equal(dev.so, np.concatenate([[0], np.cumsum([len(w) for w in frames])]).astype(np.uint64))
+        for bin_len in (0, 7, spf, 1_000):
+            n_bins = R.n_bins_for(n, bin_len)
+            got, st, res, replays = _levels(dev, bin_len, n_bins, d_seg=None)
+            assert np.array_equal(st, np.array(ost, dtype=np.int32))
+            _same(got, R.levels(frames, ost, dev.so[:-1], bin_len, n_bins), bin_len)
+    finally:
+        dev.close()
+
+
+def test_more_entries_than_threads_of_the_row_scan(ctx, x3):
+    """a corpus of 1 025 one-frame entries of 30 to 90 samples: x3_corpus_levels_rows_kernel's workgroup of 1 024 walks a run
+    of two entries per thread; the rows of every entry lie where the host's prefix and levels_ref put them"""
+    p = x3.Params.default()
+    op = XC.oparams(p)
+    rng = np.random.default_rng(1025)
+    ents, ref_entries = [], []
+    for e in range(1025):
+        w = _content("rice3", int(rng.integers(30, 91)), seed=100 + e)
+        rc, s, _ = O.encode(w, op)
+        assert rc == 0
+        frames, ost = _oracle_frames(s, XC.frame_offsets(s), op)
+        assert len(frames) == 1
+        ents.append(s)
+        ref_entries.append((frames, ost, [0], w.size))
+    buf, offs, lens = _place_even(ents)
+    corpus = x3.Corpus(ctx, buf, offs, lens, params=p, seg_blocks=32, index="walk")
+    try:
+        for bin_len in (16, 0):
+            want, rf = R.corpus_levels(ref_entries, bin_len)
+            assert np.array_equal(corpus.levels_rows(bin_len), rf)
+            rows, rf2, st = corpus.levels(bin_len)
+            assert np.array_equal(rf2, rf) and st.tolist() == [o for _, ost, _, _ in ref_entries for o in ost]
+            _same(rows, want, bin_len)
+    finally:
+        corpus.close()
+
+
 def _place_even(entries):
     blob, offs = bytearray(), []
     for e in entries:

@@ -304,6 +304,21 @@ def test_more_ranges_than_threads_of_the_scan(ctx, x3):
     dev.close()
 
 
+@pytest.mark.parametrize("n", [1023, 1024, 1025, 2049])
+def test_range_counts_round_the_threads_of_the_scan(ctx, x3, n):
+    """x3_range_scan_kernel's workgroup of 1 024 walks a run of ranges per thread: one each up to 1 024, then two, three at
+    2 049.  Packed with room for all, packed with the last ranges left without room, padded."""
+    dev = base(ctx, x3)
+    rng = np.random.default_rng(n)
+    lens = rng.integers(1, 4, n).tolist()
+    starts = rng.integers(0, N - 3, n).tolist()
+    frames = dev.frames()
+    check(ctx, dev, frames, dev.so, starts, lens, 0, sum(lens), 0)
+    check(ctx, dev, frames, dev.so, starts, lens, 0, sum(lens) - 4, 0)
+    check(ctx, dev, frames, dev.so, starts, lens, 4, 4 * n, 1)
+    dev.close()
+
+
 def test_block_length_40_with_a_walk_built_index(ctx, x3):
     dev = base(ctx, x3, index=None, bl=40, bpf=10)
     ne = x3.lib().x3_seg_index_entries(dev.F, C.byref(dev.p), SB)

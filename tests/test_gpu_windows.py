@@ -427,6 +427,22 @@ def test_other_parameter_sets(ctx, x3, bl, bpf, codes):
         src.close()
 
 
+@pytest.mark.parametrize("n", [1023, 1024, 1025, 2049])
+def test_window_counts_round_the_threads_of_the_scan(ctx, x3, n):
+    """x3_window_scan_kernel's workgroup of 1 024 walks a run of windows per thread: one each up to 1 024, then two, three
+    at 2 049.  Windows of 1 to 3 samples over six frames of 400 (the last of 137)."""
+    total = 2137
+    wav = x3.synth(2, 1616, 0, total)
+    rc, stream, _ = O.encode(wav, O.Params.make(20, 20, (0, 1, 3), (3, 8, 20)))
+    assert rc == 0
+    dev = Dev(ctx, x3, stream=stream, p=x3.Params.make(block_len=20, blocks_per_frame=20, codes=(0, 1, 3)))
+    assert dev.F == 6 and dev.total == total
+    rng = np.random.default_rng(n)
+    for L in (1, 2, 3):
+        _check_exact(dev, wav, L, rng.integers(0, total - L + 1, n).tolist(), seg=False, replays=None)
+    dev.close()
+
+
 def test_full_size_1024_random_one_second_windows(ctx, x3):
     """config 3's size: 691.2 M samples (1 h at 192 kHz), 1 024 random one-second windows in both formats"""
     n, L, nw, kind, seed = 691_200_000, 192_000, 1024, x3.SYNTH_HYDROPHONE, 0x58330003

@@ -1934,12 +1934,16 @@ extern "C" int x3_corpus_seg_index(const x3_corpus* k, const uint64_t** d_seg_in
   return X3_OK;
 }
 
-// The frames of a corpus for a call of this context; a corpus of another device is refused in `entry_point`'s name
+// a corpus of another device is refused in `entry_point`'s name
+static bool corpus_device_ok(x3_ctx* c, const x3_corpus* k, const char* entry_point) {
+  if (c->device == k->device) return true;
+  c->last_error = std::string(entry_point) + ": the corpus was built on another device";
+  return false;
+}
+
+// The frames of a corpus for a call of this context
 static int corpus_source(x3_ctx* c, const x3_corpus* k, const char* entry_point, FrameSource* s) {
-  if (c->device != k->device) {
-    c->last_error = std::string(entry_point) + ": the corpus was built on another device";
-    return X3_ERR_BAD_ARG;
-  }
+  if (!corpus_device_ok(c, k, entry_point)) return X3_ERR_BAD_ARG;
   s->d_x3 = k->d_x3, s->x3_len = k->x3_len;
   s->d_frame_offsets = k->d_frame_off, s->d_sample_offsets = k->d_so, s->F = k->F, s->max_frames = k->max_frames;
   s->spf = spf_of(&k->p);
@@ -1983,31 +1987,59 @@ extern "C" int x3_corpus_ranges_dev(x3_ctx* c, const x3_corpus* k, const uint32_
                         });
 }
 
-// the rows of entry e (levels_rows_of its samples) in front of each other: n_entries + 1 words
-extern "C" int x3_corpus_levels_rows(const x3_corpus* k, uint64_t bin_len, uint64_t* row_first) {
-  if (!k || !row_first) return X3_ERR_BAD_ARG;
+// the rows of entry e (levels_rows_of its samples) in front of each other, n_entries + 1 words to row_first if it is given;
+// their sum
+static uint64_t corpus_rows_total(const x3_corpus* k, uint64_t bin_len, uint64_t* row_first = nullptr) {
   uint64_t run = 0;
   for (uint64_t e = 0; e < k->n; ++e) {
-    row_first[e] = run;
+    if (row_first) row_first[e] = run;
     run += levels_rows_of(k->ent[e].n_samples, bin_len);
   }
-  row_first[k->n] = run;
+  if (row_first) row_first[k->n] = run;
+  return run;
+}
+
+extern "C" int x3_corpus_levels_rows(const x3_corpus* k, uint64_t bin_len, uint64_t* row_first) {
+  if (!k || !row_first) return X3_ERR_BAD_ARG;
+  corpus_rows_total(k, bin_len, row_first);
   return X3_OK;
+}
+
+// The level records a call reads or writes (X3EvRows, x3_events_kernel.h), FrameSource's counterpart: what every such call
+// checks behind its own arguments.  A stream's: one entry, its samples in *d_total on the device.
+static int stream_rows(const x3_level* d_levels, uint64_t n_bins, uint64_t bin_len, const uint64_t* d_total, X3EvRows* q) {
+  if (!d_total || (reinterpret_cast<uintptr_t>(d_total) & 7u)) return X3_ERR_BAD_ARG;
+  *q = X3EvRows{d_levels, n_bins, bin_len, d_total, nullptr, 0, nullptr};
+  return X3_OK;
+}
+
+// ... a corpus's, entry after entry: the corpus is this device's, n_rows is what the host's entry table gives (row_first:
+// corpus_row_prefix, in the call's workspace)
+static int corpus_rows(x3_ctx* c, const x3_corpus* k, const x3_level* d_levels, uint64_t n_rows, uint64_t bin_len,
+                       const char* entry_point, X3EvRows* q) {
+  if (!corpus_device_ok(c, k, entry_point) || n_rows != corpus_rows_total(k, bin_len)) return X3_ERR_BAD_ARG;
+  *q = X3EvRows{d_levels, n_rows, bin_len, nullptr, k->d_ent, k->n, nullptr};
+  return X3_OK;
+}
+
+// the row prefix of a corpus call (k != NULL) by the device into its workspace, and into the call's rows
+static void corpus_row_prefix(x3_ctx* c, const x3_corpus* k, uint64_t bin_len, unsigned long long* row_first, X3EvRows* q = nullptr) {
+  if (!k) return;
+  hipLaunchKernelGGL(x3_corpus_levels_rows_kernel, dim3(1), dim3(1024), 0, c->stream, k->d_ent, k->n, bin_len, row_first);
+  if (q) q->row_first = row_first;
 }
 
 extern "C" int x3_corpus_levels_dev(x3_ctx* c, const x3_corpus* k, uint64_t bin_len, x3_level* d_levels, uint64_t n_rows,
                                     int32_t* d_frame_status) {
   if (!c || !k || !levels_args_ok(c, d_levels, n_rows, d_frame_status)) return X3_ERR_BAD_ARG;
   FrameSource s;
-  const int rc = corpus_source(c, k, "x3_corpus_levels_dev", &s);
-  if (rc) return rc;
-  uint64_t want = 0;   // (behind the device check, as ever: a call that fails both leaves that check's last_error)
-  for (const x3_corpus_entry& en : k->ent) want += levels_rows_of(en.n_samples, bin_len);
-  if (n_rows != want) return X3_ERR_BAD_ARG;
+  X3EvRows q;
+  int rc;
+  if ((rc = corpus_source(c, k, "x3_corpus_levels_dev", &s))) return rc;
+  if ((rc = corpus_rows(c, k, d_levels, n_rows, bin_len, "x3_corpus_levels_dev", &q))) return rc;
   return levels_launch(c, s, bin_len, d_levels, n_rows, d_frame_status, k->n,
                        [&](dim3 grid, unsigned long long* row_first, const int32_t* fst, X3LevFrame* frames, uint32_t* cnt) {
-                         hipLaunchKernelGGL(x3_corpus_levels_rows_kernel, dim3(1), dim3(1024), 0, c->stream,
-                                            k->d_ent, k->n, bin_len, row_first);
+                         corpus_row_prefix(c, k, bin_len, row_first);
                          hipLaunchKernelGGL(x3_corpus_levels_prep_kernel, grid, dim3(256), 0, c->stream,
                                             k->d_ent, k->n, (const unsigned long long*)row_first,
                                             s.d_sample_offsets, s.F, bin_len, n_rows, fst, frames, cnt);
@@ -2068,10 +2100,7 @@ static int events_launch(x3_ctx* c, X3EvRows q, const x3_corpus* k, const x3_eve
   events_carve((char*)c->ev_ws.p, q.n_rows, q.n_ent, &w);
   const uint64_t n_tiles = (q.n_rows + X3E_TILE - 1) / X3E_TILE;
   const dim3 g_tiles(grid_for(n_tiles, 1));
-  if (k) {
-    hipLaunchKernelGGL(x3_corpus_levels_rows_kernel, dim3(1), dim3(1024), 0, c->stream, k->d_ent, k->n, q.bin_len, w.row_first);
-    q.row_first = w.row_first;
-  }
+  corpus_row_prefix(c, k, q.bin_len, w.row_first, &q);
   if (d_thr)
     hipLaunchKernelGGL(x3_events_adaptive_flag_kernel, g_tiles, dim3(256), 0, c->stream, q, d_thr, n_tiles, w.hot, w.tile_prev,
                        w.tile_next);
@@ -2096,32 +2125,52 @@ static int events_launch(x3_ctx* c, X3EvRows q, const x3_corpus* k, const x3_eve
   return X3_OK;
 }
 
+// One checked events call.  corpus_entry: the entry point's name of a corpus form (k, d_entries), NULL for a stream form
+// (d_total); d_thr: the thresholds of an adaptive form, whose rule carries no values of its own.
+static int events_call(x3_ctx* c, const x3_corpus* k, const char* corpus_entry, const x3_level* d_levels, uint64_t n_rows,
+                       uint64_t bin_len, const uint64_t* d_total, const x3_event_rule* rule, bool adaptive,
+                       const x3_event_threshold* d_thr, uint32_t* d_entries, uint64_t* d_starts, uint32_t* d_lens,
+                       x3_level* d_event_levels, uint64_t cap, uint64_t* d_count) {
+  x3_event_rule eff;
+  if ((corpus_entry && !k) ||
+      !events_args_ok(c, d_levels, n_rows, bin_len, rule, d_starts, d_lens, d_event_levels, cap, d_count, &eff, adaptive))
+    return X3_ERR_BAD_ARG;
+  if (corpus_entry && (!d_entries || (reinterpret_cast<uintptr_t>(d_entries) & 3u))) return X3_ERR_BAD_ARG;
+  if (adaptive && (!d_thr || (reinterpret_cast<uintptr_t>(d_thr) & 7u))) return X3_ERR_BAD_ARG;
+  X3EvRows q;
+  const int rc = corpus_entry ? corpus_rows(c, k, d_levels, n_rows, bin_len, corpus_entry, &q)
+                              : stream_rows(d_levels, n_rows, bin_len, d_total, &q);
+  if (rc) return rc;
+  return events_launch(c, q, k, eff, d_thr, d_entries, d_starts, d_lens, d_event_levels, cap, d_count);
+}
+
 extern "C" int x3_events_dev(x3_ctx* c, const x3_level* d_levels, uint64_t n_bins, uint64_t bin_len, const uint64_t* d_total,
                              const x3_event_rule* rule, uint64_t* d_starts, uint32_t* d_lens, x3_level* d_event_levels,
                              uint64_t cap, uint64_t* d_count) {
-  x3_event_rule eff;
-  if (!events_args_ok(c, d_levels, n_bins, bin_len, rule, d_starts, d_lens, d_event_levels, cap, d_count, &eff)) return X3_ERR_BAD_ARG;
-  if (!d_total || (reinterpret_cast<uintptr_t>(d_total) & 7u)) return X3_ERR_BAD_ARG;
-  return events_launch(c, X3EvRows{d_levels, n_bins, bin_len, d_total, nullptr, 0, nullptr}, nullptr, eff, nullptr, nullptr, d_starts,
-                       d_lens, d_event_levels, cap, d_count);
+  return events_call(c, nullptr, nullptr, d_levels, n_bins, bin_len, d_total, rule, false, nullptr, nullptr, d_starts, d_lens,
+                     d_event_levels, cap, d_count);
 }
 
 extern "C" int x3_corpus_events_dev(x3_ctx* c, const x3_corpus* k, const x3_level* d_levels, uint64_t n_rows, uint64_t bin_len,
                                     const x3_event_rule* rule, uint32_t* d_entries, uint64_t* d_starts, uint32_t* d_lens,
                                     x3_level* d_event_levels, uint64_t cap, uint64_t* d_count) {
-  x3_event_rule eff;
-  if (!k || !events_args_ok(c, d_levels, n_rows, bin_len, rule, d_starts, d_lens, d_event_levels, cap, d_count, &eff))
-    return X3_ERR_BAD_ARG;
-  if (!d_entries || (reinterpret_cast<uintptr_t>(d_entries) & 3u)) return X3_ERR_BAD_ARG;
-  if (c->device != k->device) {
-    c->last_error = "x3_corpus_events_dev: the corpus was built on another device";
-    return X3_ERR_BAD_ARG;
-  }
-  uint64_t want = 0;
-  for (const x3_corpus_entry& en : k->ent) want += levels_rows_of(en.n_samples, bin_len);
-  if (n_rows != want) return X3_ERR_BAD_ARG;
-  return events_launch(c, X3EvRows{d_levels, n_rows, bin_len, nullptr, k->d_ent, k->n, nullptr}, k, eff, nullptr, d_entries, d_starts,
-                       d_lens, d_event_levels, cap, d_count);
+  return events_call(c, k, "x3_corpus_events_dev", d_levels, n_rows, bin_len, nullptr, rule, false, nullptr, d_entries, d_starts,
+                     d_lens, d_event_levels, cap, d_count);
+}
+
+extern "C" int x3_events_adaptive_dev(x3_ctx* c, const x3_level* d_levels, uint64_t n_bins, uint64_t bin_len, const uint64_t* d_total,
+                                      const x3_event_rule* rule, const x3_event_threshold* d_thr, uint64_t* d_starts,
+                                      uint32_t* d_lens, x3_level* d_event_levels, uint64_t cap, uint64_t* d_count) {
+  return events_call(c, nullptr, nullptr, d_levels, n_bins, bin_len, d_total, rule, true, d_thr, nullptr, d_starts, d_lens,
+                     d_event_levels, cap, d_count);
+}
+
+extern "C" int x3_corpus_events_adaptive_dev(x3_ctx* c, const x3_corpus* k, const x3_level* d_levels, uint64_t n_rows,
+                                             uint64_t bin_len, const x3_event_rule* rule, const x3_event_threshold* d_thr,
+                                             uint32_t* d_entries, uint64_t* d_starts, uint32_t* d_lens, x3_level* d_event_levels,
+                                             uint64_t cap, uint64_t* d_count) {
+  return events_call(c, k, "x3_corpus_events_adaptive_dev", d_levels, n_rows, bin_len, nullptr, rule, true, d_thr, d_entries,
+                     d_starts, d_lens, d_event_levels, cap, d_count);
 }
 
 extern "C" int x3_events_result(x3_ctx* c, uint64_t* count) {
@@ -2139,50 +2188,8 @@ extern "C" int x3_events_result(x3_ctx* c, uint64_t* count) {
 static_assert(X3Q_BINS == X3E_TILE, "a lane of a tile flushes one bin of the tile's histogram");
 static_assert(sizeof(x3_threshold_rule) == 32 && sizeof(x3_event_threshold) == 16, "include/x3hip.h states these sizes");
 
-extern "C" int x3_events_adaptive_dev(x3_ctx* c, const x3_level* d_levels, uint64_t n_bins, uint64_t bin_len, const uint64_t* d_total,
-                                      const x3_event_rule* rule, const x3_event_threshold* d_thr, uint64_t* d_starts,
-                                      uint32_t* d_lens, x3_level* d_event_levels, uint64_t cap, uint64_t* d_count) {
-  x3_event_rule eff;
-  if (!events_args_ok(c, d_levels, n_bins, bin_len, rule, d_starts, d_lens, d_event_levels, cap, d_count, &eff, true))
-    return X3_ERR_BAD_ARG;
-  if (!d_total || !d_thr || ((reinterpret_cast<uintptr_t>(d_total) | reinterpret_cast<uintptr_t>(d_thr)) & 7u)) return X3_ERR_BAD_ARG;
-  return events_launch(c, X3EvRows{d_levels, n_bins, bin_len, d_total, nullptr, 0, nullptr}, nullptr, eff, d_thr, nullptr, d_starts,
-                       d_lens, d_event_levels, cap, d_count);
-}
-
-// the checks of a corpus call behind the shared ones: the device, n_rows against the host's entry table
-static bool corpus_rows_ok(x3_ctx* c, const x3_corpus* k, uint64_t n_rows, uint64_t bin_len, const char* what) {
-  if (c->device != k->device) {
-    c->last_error = std::string(what) + ": the corpus was built on another device";
-    return false;
-  }
-  uint64_t want = 0;
-  for (const x3_corpus_entry& en : k->ent) want += levels_rows_of(en.n_samples, bin_len);
-  return n_rows == want;
-}
-
-extern "C" int x3_corpus_events_adaptive_dev(x3_ctx* c, const x3_corpus* k, const x3_level* d_levels, uint64_t n_rows,
-                                             uint64_t bin_len, const x3_event_rule* rule, const x3_event_threshold* d_thr,
-                                             uint32_t* d_entries, uint64_t* d_starts, uint32_t* d_lens, x3_level* d_event_levels,
-                                             uint64_t cap, uint64_t* d_count) {
-  x3_event_rule eff;
-  if (!k || !events_args_ok(c, d_levels, n_rows, bin_len, rule, d_starts, d_lens, d_event_levels, cap, d_count, &eff, true))
-    return X3_ERR_BAD_ARG;
-  if (!d_entries || (reinterpret_cast<uintptr_t>(d_entries) & 3u) || !d_thr || (reinterpret_cast<uintptr_t>(d_thr) & 7u))
-    return X3_ERR_BAD_ARG;
-  if (!corpus_rows_ok(c, k, n_rows, bin_len, "x3_corpus_events_adaptive_dev")) return X3_ERR_BAD_ARG;
-  return events_launch(c, X3EvRows{d_levels, n_rows, bin_len, nullptr, k->d_ent, k->n, nullptr}, k, eff, d_thr, d_entries, d_starts,
-                       d_lens, d_event_levels, cap, d_count);
-}
-
-// The workspace of a quantiles or thresholds call (q_ws; the formula: x3_quantiles_kernel.h)
-struct QWs {
-  uint2* keys;                                  // per row
-  uint32_t* hist; X3QSlot* slots;               // per (entry, j): 256 bins; prefix and rank
-  uint32_t* val[2]; uint32_t* counted;          // per entry: the two values and K of a thresholds call
-  X3QSummary* sum; unsigned long long* row_first;
-};
-static size_t quantiles_carve(char* base, uint64_t n_rows, uint64_t n_ent, uint32_t n_q, QWs* w) {
+// The workspace of a quantiles or thresholds call (QWs, x3_internal.h; the formula: x3_quantiles_kernel.h)
+size_t quantiles_carve(char* base, uint64_t n_rows, uint64_t n_ent, uint32_t n_q, QWs* w) {
   BlockCarver k{base, 0};
   w->keys = k.take<uint2>(n_rows);
   w->hist = k.take<uint32_t>(n_ent * n_q * X3Q_BINS);
@@ -2218,10 +2225,7 @@ static int quantiles_launch(x3_ctx* c, X3EvRows q, const x3_corpus* k, QRun* run
   quantiles_carve((char*)c->q_ws.p, q.n_rows, n_ent, n_q, &w);
   const uint64_t n_tiles = (q.n_rows + X3E_TILE - 1) / X3E_TILE;
   const dim3 g_rows(grid_for(q.n_rows, 256)), g_tiles(grid_for(n_tiles, 1)), g_ent(grid_for(n_ent, 1));
-  if (k) {
-    hipLaunchKernelGGL(x3_corpus_levels_rows_kernel, dim3(1), dim3(1024), 0, c->stream, k->d_ent, k->n, q.bin_len, w.row_first);
-    q.row_first = w.row_first;
-  }
+  corpus_row_prefix(c, k, q.bin_len, w.row_first, &q);
   uint32_t* const counted = trule ? w.counted : d_counted;
   for (uint32_t i = 0; i < n_runs; ++i) {
     const QRun& r = runs[i];
@@ -2262,25 +2266,32 @@ static bool quantiles_run_ok(int key, const uint32_t* q_ppm, uint32_t n_q, uint3
   return true;
 }
 
+// One checked quantiles (n_runs 1, into the caller's arrays) or thresholds call (trule, d_thr).  corpus_entry: as in
+// events_call; n_runs 0: the wrapper has refused its runs.
+static int quantiles_call(x3_ctx* c, const x3_corpus* k, const char* corpus_entry, const x3_level* d_levels, uint64_t n_rows,
+                          uint64_t bin_len, const uint64_t* d_total, QRun* runs, uint32_t n_runs, uint32_t* d_counted,
+                          const x3_threshold_rule* trule, x3_event_threshold* d_thr) {
+  if ((corpus_entry && !k) || !quantiles_args_ok(c, d_levels, n_rows, bin_len) || !n_runs) return X3_ERR_BAD_ARG;
+  X3EvRows q;
+  const int rc = corpus_entry ? corpus_rows(c, k, d_levels, n_rows, bin_len, corpus_entry, &q)
+                              : stream_rows(d_levels, n_rows, bin_len, d_total, &q);
+  if (rc) return rc;
+  return quantiles_launch(c, q, k, runs, n_runs, d_counted, trule, d_thr);
+}
+
 extern "C" int x3_level_quantiles_dev(x3_ctx* c, const x3_level* d_levels, uint64_t n_bins, uint64_t bin_len, const uint64_t* d_total,
                                       int key, const uint32_t* q_ppm, uint32_t n_q, uint32_t* d_values, uint32_t* d_counted) {
   QRun r;
-  if (!quantiles_args_ok(c, d_levels, n_bins, bin_len) || !quantiles_run_ok(key, q_ppm, n_q, d_values, d_counted, &r))
-    return X3_ERR_BAD_ARG;
-  if (!d_total || (reinterpret_cast<uintptr_t>(d_total) & 7u)) return X3_ERR_BAD_ARG;
-  return quantiles_launch(c, X3EvRows{d_levels, n_bins, bin_len, d_total, nullptr, 0, nullptr}, nullptr, &r, 1, d_counted, nullptr,
-                          nullptr);
+  const uint32_t n = quantiles_run_ok(key, q_ppm, n_q, d_values, d_counted, &r) ? 1u : 0u;
+  return quantiles_call(c, nullptr, nullptr, d_levels, n_bins, bin_len, d_total, &r, n, d_counted, nullptr, nullptr);
 }
 
 extern "C" int x3_corpus_level_quantiles_dev(x3_ctx* c, const x3_corpus* k, const x3_level* d_levels, uint64_t n_rows,
                                              uint64_t bin_len, int key, const uint32_t* q_ppm, uint32_t n_q, uint32_t* d_values,
                                              uint32_t* d_counted) {
   QRun r;
-  if (!k || !quantiles_args_ok(c, d_levels, n_rows, bin_len) || !quantiles_run_ok(key, q_ppm, n_q, d_values, d_counted, &r))
-    return X3_ERR_BAD_ARG;
-  if (!corpus_rows_ok(c, k, n_rows, bin_len, "x3_corpus_level_quantiles_dev")) return X3_ERR_BAD_ARG;
-  return quantiles_launch(c, X3EvRows{d_levels, n_rows, bin_len, nullptr, k->d_ent, k->n, nullptr}, k, &r, 1, d_counted, nullptr,
-                          nullptr);
+  const uint32_t n = quantiles_run_ok(key, q_ppm, n_q, d_values, d_counted, &r) ? 1u : 0u;
+  return quantiles_call(c, k, "x3_corpus_level_quantiles_dev", d_levels, n_rows, bin_len, nullptr, &r, n, d_counted, nullptr, nullptr);
 }
 
 // the runs of a thresholds call: one per criterion that is on, the peak's first; 0: refused
@@ -2303,19 +2314,15 @@ static uint32_t threshold_runs(const x3_threshold_rule* rule, const x3_event_thr
 extern "C" int x3_level_thresholds_dev(x3_ctx* c, const x3_level* d_levels, uint64_t n_bins, uint64_t bin_len, const uint64_t* d_total,
                                        const x3_threshold_rule* rule, x3_event_threshold* d_thr) {
   QRun runs[2];
-  if (!quantiles_args_ok(c, d_levels, n_bins, bin_len) || !d_total || (reinterpret_cast<uintptr_t>(d_total) & 7u)) return X3_ERR_BAD_ARG;
   const uint32_t n = threshold_runs(rule, d_thr, runs);
-  if (!n) return X3_ERR_BAD_ARG;
-  return quantiles_launch(c, X3EvRows{d_levels, n_bins, bin_len, d_total, nullptr, 0, nullptr}, nullptr, runs, n, nullptr, rule, d_thr);
+  return quantiles_call(c, nullptr, nullptr, d_levels, n_bins, bin_len, d_total, runs, n, nullptr, rule, d_thr);
 }
 
 extern "C" int x3_corpus_level_thresholds_dev(x3_ctx* c, const x3_corpus* k, const x3_level* d_levels, uint64_t n_rows,
                                               uint64_t bin_len, const x3_threshold_rule* rule, x3_event_threshold* d_thr) {
   QRun runs[2];
-  if (!k || !quantiles_args_ok(c, d_levels, n_rows, bin_len)) return X3_ERR_BAD_ARG;
   const uint32_t n = threshold_runs(rule, d_thr, runs);
-  if (!n || !corpus_rows_ok(c, k, n_rows, bin_len, "x3_corpus_level_thresholds_dev")) return X3_ERR_BAD_ARG;
-  return quantiles_launch(c, X3EvRows{d_levels, n_rows, bin_len, nullptr, k->d_ent, k->n, nullptr}, k, runs, n, nullptr, rule, d_thr);
+  return quantiles_call(c, k, "x3_corpus_level_thresholds_dev", d_levels, n_rows, bin_len, nullptr, runs, n, nullptr, rule, d_thr);
 }
 
 extern "C" int x3_level_quantiles_result(x3_ctx* c, uint64_t* n_empty, uint64_t* first_empty) {

@@ -7,7 +7,8 @@
 //
 //  x3_window_plan_kernel    -- a thread per window: the start is checked against the total (sample_offsets[F]), the
 //      covering frames [fa, fb] are found by binary search.  A window off the end is X3_ERR_BAD_ARG and covers nothing.
-//  x3_window_scan_kernel    -- one workgroup: exclusive scans of the covering frames and of the work items per window.
+//  x3_window_scan_kernel    -- one workgroup: exclusive scans of the covering frames and of the work items per window
+//      (x3w_scan_items, the run-per-thread scan of every one-workgroup scan kernel here and in the levels family).
 //  x3_window_check_kernel   -- a WAVE per (window, covering frame): header (x3_frame_header_check_words), payload CRC as a
 //      segmented reduction over the wave, `samples` against sample_offsets[f + 1] - sample_offsets[f].  The verdict goes
 //      to the frame's word of a per-frame array (every window that covers the frame writes the same word).
@@ -26,7 +27,8 @@
 // partial last dword is read byte by byte), every store is at a row position in [0, L).
 //
 // RANGES (x3_decode_ranges_dev): the same launch set with a length per window.  x3_range_plan_kernel / x3_corpus_range_plan_kernel
-// read lens[w], x3_range_scan_kernel scans the lengths in front of the covering frames, and the decode and fix-up kernels are
+// read lens[w], x3_range_scan_kernel scans the lengths in front of the covering frames (x3w_range_scan, the body it shares with
+// x3_range_levels_scan_kernel), and the decode and fix-up kernels are
 // the templates' other instance: their rows come from X3WinRangeGeo instead of w * L and L.
 #pragma once
 #include "x3_device.h"
@@ -245,6 +247,38 @@ __device__ __forceinline__ unsigned long long x3w_block_excl_scan(unsigned long 
   return incl - v;
 }
 
+// The scan of n items by one workgroup, a contiguous run of items per thread (x3w_own_items: each(i) for the thread's own).
+// count(i) is item i's weight, put(i, sum) takes the sum of the weights in front of it (count(i) is read before put(i) runs,
+// so put may overwrite what count reads); the total comes back to every thread.  s: blockDim.x words of LDS.
+// x3w_scan_own_items: `mine` is the sum of the thread's own weights already -- a site that forms the weights in a first walk
+// over its items, or while it writes an earlier scan, sums them there.
+template <class Each>
+__device__ __forceinline__ void x3w_own_items(uint64_t n, Each each) {
+  const uint64_t per = (n + blockDim.x - 1) / blockDim.x;
+  const uint64_t a = min((uint64_t)threadIdx.x * per, n), b = min(a + per, n);
+  for (uint64_t i = a; i < b; ++i) each(i);
+}
+
+template <class Count, class Put>
+__device__ __forceinline__ unsigned long long x3w_scan_own_items(uint64_t n, unsigned long long* s, unsigned long long mine,
+                                                                 Count count, Put put) {
+  unsigned long long total;
+  unsigned long long run = x3w_block_excl_scan(mine, s, &total);
+  x3w_own_items(n, [&](uint64_t i) {
+    const unsigned long long own = count(i);
+    put(i, run);
+    run += own;
+  });
+  return total;
+}
+
+template <class Count, class Put>
+__device__ __forceinline__ unsigned long long x3w_scan_items(uint64_t n, unsigned long long* s, Count count, Put put) {
+  unsigned long long mine = 0;
+  x3w_own_items(n, [&](uint64_t i) { mine += count(i); });
+  return x3w_scan_own_items(n, s, mine, count, put);
+}
+
 __device__ __forceinline__ uint32_t x3w_header_samples(const uint8_t* __restrict__ x3, uint64_t len, uint64_t off) {
   if (len < 20u || off > len - 20u) return 0u;
   return ((uint32_t)x3[off + 4u] << 8) | x3[off + 5u];
@@ -254,16 +288,9 @@ __global__ void __launch_bounds__(1024)
 x3_window_sample_offsets_kernel(const uint8_t* __restrict__ x3, uint64_t len, const uint64_t* __restrict__ frame_off,
                                 uint64_t F, uint64_t* __restrict__ so) {
   __shared__ unsigned long long s[1024];
-  const uint64_t per = (F + blockDim.x - 1) / blockDim.x;
-  const uint64_t a = min((uint64_t)threadIdx.x * per, F), b = min(a + per, F);
-  unsigned long long sum = 0;
-  for (uint64_t f = a; f < b; ++f) sum += x3w_header_samples(x3, len, frame_off[f]);
-  unsigned long long total;
-  unsigned long long run = x3w_block_excl_scan(sum, s, &total);
-  for (uint64_t f = a; f < b; ++f) {
-    so[f] = run;
-    run += x3w_header_samples(x3, len, frame_off[f]);
-  }
+  const unsigned long long total = x3w_scan_items(
+      F, s, [&](uint64_t f) { return (unsigned long long)x3w_header_samples(x3, len, frame_off[f]); },
+      [&](uint64_t f, unsigned long long run) { so[f] = run; });
   if (threadIdx.x == 0) so[F] = total;
 }
 
@@ -319,17 +346,12 @@ x3_window_scan_kernel(const X3WinPlan* __restrict__ plan, uint64_t n, const uint
                       unsigned long long* __restrict__ cov_off, unsigned long long* __restrict__ item_off) {
   __shared__ unsigned long long s[1024];
   const uint32_t ns = x3w_index_ok(idx, sb) ? nseg : 1u;
-  const uint64_t per = (n + blockDim.x - 1) / blockDim.x;
-  const uint64_t a = min((uint64_t)threadIdx.x * per, n), b = min(a + per, n);
-  unsigned long long c = 0;
-  for (uint64_t w = a; w < b; ++w) c += plan[w].ncov;
-  unsigned long long total;
-  unsigned long long run = x3w_block_excl_scan(c, s, &total);
-  for (uint64_t w = a; w < b; ++w) {
-    cov_off[w] = run;
-    item_off[w] = run * ns;
-    run += plan[w].ncov;
-  }
+  const unsigned long long total = x3w_scan_items(
+      n, s, [&](uint64_t w) { return (unsigned long long)plan[w].ncov; },
+      [&](uint64_t w, unsigned long long run) {
+        cov_off[w] = run;
+        item_off[w] = run * ns;
+      });
   if (threadIdx.x == 0) {
     cov_off[n] = total;
     item_off[n] = total * ns;
@@ -358,10 +380,45 @@ struct X3WinRangeGeo {
   __device__ __forceinline__ uint64_t row_end(uint64_t w) const { return stride ? stride : elen[w]; }
 };
 
-// x3_window_scan_kernel with the scan of the lengths in front of it: off[w] (packed; n + 1 words, also to the caller's
-// out_off, which gets w * stride when padded), the verdict on the row -- a range with off[w] + len > out_cap (packed) or
-// len > stride (padded) is X3D_BAD_ARG, covers nothing and stores nothing: elen[w] = 0 -- and then the covering frames and
-// work items of what is left.  64-bit sums of at most 2^31 32-bit lengths: no wrap.
+// x3_window_scan_kernel with the scan of the ranges' sizes in front of it -- size(w): the length of range w (the ranges calls)
+// or its level records (the range-levels calls, x3_range_levels_kernel.h): off[w] (packed; n + 1 words, also to the caller's
+// out_off, which gets w * stride when padded), the verdict on the row -- a range with off[w] + size > cap (packed) or
+// size > stride (padded) is X3D_BAD_ARG, covers nothing and stores nothing: esize[w] = 0 -- and then the covering frames
+// and, with Items, the work items of what is left.  Returns the sum of all sizes (64-bit sums of at most 2^31 32-bit sizes:
+// no wrap).
+template <bool Items, class Size>
+__device__ __forceinline__ unsigned long long x3w_range_scan(X3WinPlan* __restrict__ plan, uint64_t n, Size size, uint64_t stride,
+                                                             uint64_t cap, uint32_t ns, unsigned long long* __restrict__ cov_off,
+                                                             unsigned long long* __restrict__ item_off,
+                                                             unsigned long long* __restrict__ off, uint32_t* __restrict__ esize,
+                                                             uint64_t* __restrict__ out_off, unsigned long long* s) {
+  unsigned long long covers = 0;   // (the thread's own ranges: the covering frames of those that have room)
+  unsigned long long sz = 0;       // (size(w), at most 2^32 - 1: the scan reads a range's size in front of its put)
+  const unsigned long long total = x3w_scan_items(n, s, [&](uint64_t w) { return sz = size(w); }, [&](uint64_t w, unsigned long long run) {
+    const bool fits = stride ? sz <= stride : (run <= cap && sz <= cap - run);
+    if (!fits) plan[w] = X3WinPlan{0, 0, X3D_BAD_ARG};
+    esize[w] = fits ? (uint32_t)sz : 0u;
+    off[w] = run;
+    if (out_off) out_off[w] = stride ? w * stride : run;
+    covers += fits ? plan[w].ncov : 0u;
+  });
+  if (threadIdx.x == 0) {
+    off[n] = total;
+    if (out_off) out_off[n] = stride ? n * stride : total;
+  }
+  const unsigned long long n_cov = x3w_scan_own_items(
+      n, s, covers, [&](uint64_t w) { return (unsigned long long)plan[w].ncov; },
+      [&](uint64_t w, unsigned long long run) {
+        cov_off[w] = run;
+        if (Items) item_off[w] = run * ns;
+      });
+  if (threadIdx.x == 0) {
+    cov_off[n] = n_cov;
+    if (Items) item_off[n] = n_cov * ns;
+  }
+  return total;
+}
+
 __global__ void __launch_bounds__(1024)
 x3_range_scan_kernel(X3WinPlan* __restrict__ plan, uint64_t n, const uint32_t* __restrict__ lens, uint64_t stride,
                      uint64_t out_cap, const uint2* __restrict__ idx, uint32_t sb, uint32_t nseg,
@@ -370,38 +427,9 @@ x3_range_scan_kernel(X3WinPlan* __restrict__ plan, uint64_t n, const uint32_t* _
                      X3WinSummary* __restrict__ sum) {
   __shared__ unsigned long long s[1024];
   const uint32_t ns = x3w_index_ok(idx, sb) ? nseg : 1u;
-  const uint64_t per = (n + blockDim.x - 1) / blockDim.x;
-  const uint64_t a = min((uint64_t)threadIdx.x * per, n), b = min(a + per, n);
-  unsigned long long c = 0;
-  for (uint64_t w = a; w < b; ++w) c += lens[w];
-  unsigned long long total;
-  unsigned long long run = x3w_block_excl_scan(c, s, &total);
-  c = 0;
-  for (uint64_t w = a; w < b; ++w) {
-    const uint32_t len = lens[w];
-    const bool fits = stride ? (uint64_t)len <= stride : (run <= out_cap && (uint64_t)len <= out_cap - run);
-    if (!fits) plan[w] = X3WinPlan{0, 0, X3D_BAD_ARG};
-    elen[w] = fits ? len : 0u;
-    off[w] = run;
-    if (out_off) out_off[w] = stride ? w * stride : run;
-    run += len;
-    c += fits ? plan[w].ncov : 0u;
-  }
-  if (threadIdx.x == 0) {
-    off[n] = total;
-    if (out_off) out_off[n] = stride ? n * stride : total;
-    sum->total = total;
-  }
-  run = x3w_block_excl_scan(c, s, &total);
-  for (uint64_t w = a; w < b; ++w) {
-    cov_off[w] = run;
-    item_off[w] = run * ns;
-    run += plan[w].ncov;
-  }
-  if (threadIdx.x == 0) {
-    cov_off[n] = total;
-    item_off[n] = total * ns;
-  }
+  const unsigned long long total = x3w_range_scan<true>(
+      plan, n, [&](uint64_t w) { return (unsigned long long)lens[w]; }, stride, out_cap, ns, cov_off, item_off, off, elen, out_off, s);
+  if (threadIdx.x == 0) sum->total = total;
 }
 
 // ---- check: a wave per (window, covering frame)

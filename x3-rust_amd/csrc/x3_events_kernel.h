@@ -83,19 +83,17 @@ __device__ __forceinline__ uint32_t x3e_last_of(unsigned long long m, uint32_t b
   return m ? base + 63u - (uint32_t)__clzll((long long)m) : X3E_NONE;
 }
 
-// ---- flag: a lane per row
-__global__ void __launch_bounds__(256)
-x3_events_flag_kernel(X3EvRows q, x3_event_rule rule, uint64_t n_tiles, uint8_t* __restrict__ hot,
-                      uint32_t* __restrict__ tile_prev, uint32_t* __restrict__ tile_next) {
+// ---- flag: a lane per row.  verdict(q, r): is row r < n_rows hot -- the rule on its record and its entry, each caller's own
+template <class Verdict>
+__device__ __forceinline__ void x3e_flag_tiles(const X3EvRows& q, Verdict verdict, uint64_t n_tiles, uint8_t* __restrict__ hot,
+                                               uint32_t* __restrict__ tile_prev, uint32_t* __restrict__ tile_next) {
   __shared__ uint32_t s_first[4], s_last[4];
   const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
   for (uint64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
     const uint64_t r = t * X3E_TILE + threadIdx.x;
     bool h = false;
     if (r < q.n_rows) {
-      h = x3e_loud(q.levels[r], rule);
-      X3EvEntry en;
-      if (h) h = x3e_entry_of(q, r, &en);
+      h = verdict(q, r);
       hot[r] = h ? X3E_HOT : 0u;
     }
     const unsigned long long m = __ballot(h);
@@ -115,6 +113,16 @@ x3_events_flag_kernel(X3EvRows q, x3_event_rule rule, uint64_t n_tiles, uint8_t*
     }
     __syncthreads();
   }
+}
+
+// (one rule for every row: the record first, the entry only of a loud one)
+__global__ void __launch_bounds__(256)
+x3_events_flag_kernel(X3EvRows q, x3_event_rule rule, uint64_t n_tiles, uint8_t* __restrict__ hot,
+                      uint32_t* __restrict__ tile_prev, uint32_t* __restrict__ tile_next) {
+  x3e_flag_tiles(q, [&](const X3EvRows& q, uint64_t r) {
+    X3EvEntry en;
+    return x3e_loud(q.levels[r], rule) && x3e_entry_of(q, r, &en);
+  }, n_tiles, hot, tile_prev, tile_next);
 }
 
 // ---- near: tile_prev[t] = the last hot row in front of tile t, tile_next[t] = the first one behind it (exclusive scans
@@ -206,21 +214,14 @@ __global__ void __launch_bounds__(1024)
 x3_events_count_kernel(uint64_t n_tiles, uint32_t* __restrict__ tile_ns, uint32_t* __restrict__ tile_ne,
                        X3EvSummary* __restrict__ sum) {
   __shared__ unsigned long long s[1024];
-  const uint64_t per = (n_tiles + blockDim.x - 1) / blockDim.x;
-  const uint64_t a = min((uint64_t)threadIdx.x * per, n_tiles), b = min(a + per, n_tiles);
   unsigned long long total[2];
   uint32_t* const tabs[2] = {tile_ns, tile_ne};
 #pragma unroll
   for (uint32_t k = 0; k < 2u; ++k) {
     uint32_t* const tab = tabs[k];
-    unsigned long long c = 0;
-    for (uint64_t i = a; i < b; ++i) c += tab[i];
-    unsigned long long run = x3w_block_excl_scan(c, s, &total[k]);
-    for (uint64_t i = a; i < b; ++i) {
-      const uint32_t own = tab[i];
-      tab[i] = (uint32_t)run;
-      run += own;
-    }
+    total[k] = x3w_scan_items(
+        n_tiles, s, [&](uint64_t i) { return (unsigned long long)tab[i]; },
+        [&](uint64_t i, unsigned long long run) { tab[i] = (uint32_t)run; });
   }
   if (threadIdx.x == 0) sum->n_runs = min(total[0], total[1]);   // (equal: the k-th start and the k-th end are one run)
 }
@@ -259,11 +260,10 @@ x3_events_runs_kernel(X3EvRows q, x3_event_rule rule, uint32_t* __restrict__ run
                       unsigned long long* __restrict__ piece_off, X3EvSummary* __restrict__ sum, uint64_t* __restrict__ d_count) {
   __shared__ unsigned long long s[1024];
   const uint64_t n = min((uint64_t)sum->n_runs, q.n_rows);
-  const uint64_t per = (n + blockDim.x - 1) / blockDim.x;
-  const uint64_t a = min((uint64_t)threadIdx.x * per, n), b = min(a + per, n);
   const uint64_t mb = rule.max_bins;   // (the host has put the default in: at least 1)
-  unsigned long long c = 0;
-  for (uint64_t k = a; k < b; ++k) {
+  auto pieces = [&](uint64_t k) { return (unsigned long long)(((uint64_t)run_last[k] - run_first[k] + mb - 1u) / mb); };
+  unsigned long long mine = 0;
+  x3w_own_items(n, [&](uint64_t k) {
     const uint64_t first = run_first[k], last = run_last[k];
     uint64_t b0 = 0, b1 = 0;
     if (first <= last && last < q.n_rows && last - first + 1u >= rule.min_bins) {
@@ -275,14 +275,10 @@ x3_events_runs_kernel(X3EvRows q, x3_event_rule rule, uint32_t* __restrict__ run
     }
     run_first[k] = (uint32_t)b0;
     run_last[k] = (uint32_t)b1;
-    c += (b1 - b0 + mb - 1u) / mb;
-  }
-  unsigned long long total;
-  unsigned long long run = x3w_block_excl_scan(c, s, &total);
-  for (uint64_t k = a; k < b; ++k) {
-    piece_off[k] = run;
-    run += ((uint64_t)run_last[k] - run_first[k] + mb - 1u) / mb;
-  }
+    mine += (b1 - b0 + mb - 1u) / mb;
+  });
+  const unsigned long long total =
+      x3w_scan_own_items(n, s, mine, pieces, [&](uint64_t k, unsigned long long run) { piece_off[k] = run; });
   if (threadIdx.x == 0) {
     piece_off[n] = total;
     sum->count = total;
@@ -316,9 +312,8 @@ x3_events_emit_kernel(X3EvRows q, x3_event_rule rule, const uint32_t* __restrict
       X3LevAcc acc;
       acc.reset();
       for (uint64_t r = p0 + lane; r < p1; r += 64u) {
-        const x3_level v = q.levels[r];
         X3LevAcc o;
-        o.sum_sq = v.sum_sq, o.sum = v.sum, o.mn = v.min, o.mx = v.max, o.n = v.n;
+        o.load(q.levels[r]);
         acc.join(o);
       }
 #pragma unroll
@@ -331,10 +326,10 @@ x3_events_emit_kernel(X3EvRows q, x3_event_rule rule, const uint32_t* __restrict
         o.n = (uint32_t)__shfl_xor((int)acc.n, d, X3_WAVE);
         acc.join(o);
       }
-      if (lane == 0) ev_levels[i] = x3_level{acc.sum_sq, acc.sum, acc.mn, acc.mx, acc.n, 0};
+      if (lane == 0) ev_levels[i] = acc.record();
     }
   }
-  const x3_level id{0, 0, 32767, -32768, 0, 0};
+  const x3_level id = X3L_IDENTITY;
   const uint64_t lanes = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t i = n_emit + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cap; i += lanes) {
     if (entries) entries[i] = 0u;

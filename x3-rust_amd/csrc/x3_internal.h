@@ -494,6 +494,17 @@ struct RLevWs {
 X3_INTERNAL uint64_t range_levels_pairs(uint64_t n, uint64_t F, uint64_t max_frames);
 X3_INTERNAL size_t range_levels_carve(char* base, uint64_t n, uint64_t F, uint64_t P, uint64_t rows_cap, uint64_t fix_waves,
                                       uint32_t scratch_per, RLevWs* w);
+// ... and of a quantiles or thresholds call (q_ws; x3_quantiles_kernel.h): n_rows records, n_ent entries (1 for a stream),
+// n_q quantiles of each
+struct X3QSlot;
+struct X3QSummary;
+struct QWs {
+  uint2* keys;                                  // per row
+  uint32_t* hist; X3QSlot* slots;               // per (entry, j): 256 bins; prefix and rank
+  uint32_t* val[2]; uint32_t* counted;          // per entry: the two values and K of a thresholds call
+  X3QSummary* sum; unsigned long long* row_first;
+};
+X3_INTERNAL size_t quantiles_carve(char* base, uint64_t n_rows, uint64_t n_ent, uint32_t n_q, QWs* w);
 // ---- x3_files.hip (x3_reader.h)
 // the RIFF/WAVE header parser of x3_wav_to_x3a on an open file, for the sanitised host tests (tests/host_cpp/fuzz_host_parsers.cpp)
 X3_INTERNAL int x3_wav_parse_fd_for_tests(int fd, uint64_t file_len, uint32_t* sample_rate, uint16_t* channels, uint16_t* bits,

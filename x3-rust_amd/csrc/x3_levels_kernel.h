@@ -26,6 +26,10 @@
 //  x3_levels_fixup_kernel    -- a wave per frame: flagged frames through the reference's reader; d_frame_status, summary
 //  x3_levels_merge_kernel    -- a lane per partial row; rows of one bin that lie side by side in a wave are joined first
 //
+// What the range levels, events and quantiles kernels (x3_range_levels_kernel.h, x3_events_kernel.h, x3_quantiles_kernel.h)
+// share with these: X3L_IDENTITY, the record of an empty bin; X3LevAcc, a record in registers (load, record, join);
+// x3l_bin_samples, the sequence "open a binner, decode into it, flush the open bin"; x3l_merge_runs, the keyed wave join.
+//
 // Nothing trusts offsets, sample offsets, index, entry table or bytes: stream reads are those of the window kernels, every
 // partial row index is below the workspace's row count, every caller's record index below n_rows.
 #pragma once
@@ -49,19 +53,24 @@ struct X3LevFrame {
 
 __device__ __forceinline__ uint64_t x3l_bin_len(uint64_t bin_len) { return bin_len ? bin_len : ~0ull; }   // 0: one bin
 
+// the record of a bin without samples: what every join leaves as it is
+constexpr x3_level X3L_IDENTITY{0, 0, 32767, -32768, 0, 0};
+
 // the registers of a bin
 struct X3LevAcc {
   uint64_t sum_sq;
   int64_t sum;
   int32_t mn, mx;
   uint32_t n;
-  __device__ __forceinline__ void reset() {
-    sum_sq = 0;
-    sum = 0;
-    mn = 32767;
-    mx = -32768;
-    n = 0;
+  __device__ __forceinline__ void load(const x3_level& r) {
+    sum_sq = r.sum_sq;
+    sum = r.sum;
+    mn = r.min;
+    mx = r.max;
+    n = r.n;
   }
+  __device__ __forceinline__ x3_level record() const { return x3_level{sum_sq, sum, mn, mx, n, 0}; }
+  __device__ __forceinline__ void reset() { load(X3L_IDENTITY); }
   __device__ __forceinline__ void add(uint32_t v) {
     const int32_t s = (int32_t)(int16_t)(uint16_t)v;
     sum_sq += (uint32_t)(s * s);
@@ -89,6 +98,28 @@ __device__ __forceinline__ void x3l_merge(x3_level* __restrict__ r, const X3LevA
   atomicAdd(&r->n, a.n);
 }
 
+// The keyed join of a wave: lane `lane` holds the registers `a` of record levels[key] (~0: none).  Lanes with the same key
+// that lie side by side form a run -- a lane starts one where its key differs from its left neighbour's (or it has none) --
+// whose registers are joined, and the first lane of each run adds the sum to the record.  Every lane of the wave calls.
+__device__ __forceinline__ void x3l_merge_runs(x3_level* __restrict__ levels, uint64_t key, X3LevAcc a, uint32_t lane) {
+  const uint64_t left = (uint64_t)__shfl_up((long long)key, 1, X3_WAVE);
+  const bool head = lane == 0u || key == ~0ull || left != key;
+  const unsigned long long heads = __ballot(head);
+  const uint32_t run = (uint32_t)__popcll(heads & (~0ull >> (63u - lane)));
+#pragma unroll
+  for (uint32_t d = 1; d < 64u; d <<= 1) {
+    X3LevAcc o;
+    o.sum_sq = (uint64_t)__shfl_down((long long)a.sum_sq, d, X3_WAVE);
+    o.sum = (int64_t)__shfl_down((long long)a.sum, d, X3_WAVE);
+    o.mn = __shfl_down(a.mn, d, X3_WAVE);
+    o.mx = __shfl_down(a.mx, d, X3_WAVE);
+    o.n = (uint32_t)__shfl_down((int)a.n, d, X3_WAVE);
+    const uint32_t orun = (uint32_t)__shfl_down((int)run, d, X3_WAVE);
+    if (lane + d < 64u && orun == run) a.join(o);
+  }
+  if (head && key != ~0ull) x3l_merge(levels + key, a);
+}
+
 // Consecutive positions from g on: `left` samples are still missing in bin `bin` (X3L_FAR: more than any frame has, so
 // a count that reaches 0 is always a real boundary).  flush(bin, acc) takes a finished or abandoned bin.
 struct X3LevBinner {
@@ -114,6 +145,23 @@ struct X3LevBinner {
   }
 };
 
+// The bins of consecutive positions from g on: decode(put_at) hands sample s of a frame to put_at(s, value), in order;
+// the samples with keep(s) are added, bins that fill go to flush, and so does the open one at the end.  Returns decode's.
+template <class Decode, class Keep, class Flush>
+__device__ __forceinline__ int32_t x3l_bin_samples(uint64_t g, uint64_t bl, Decode decode, Keep keep, Flush flush) {
+  X3LevBinner bn;
+  bn.open(g, bl);
+  const int32_t r = decode([&](uint32_t s, uint32_t v) {
+    if (keep(s)) bn.add(v, flush);
+  });
+  flush(bn.bin, bn.a);
+  return r;
+}
+// (the levels calls: every sample of the frame)
+struct X3LevKeepAll {
+  __device__ __forceinline__ bool operator()(uint32_t) const { return true; }
+};
+
 // ---- identities; the summary
 __global__ void __launch_bounds__(256)
 x3_levels_init_kernel(x3_level* __restrict__ levels, uint64_t n_rows, x3_level* __restrict__ rows, uint64_t cap,
@@ -124,7 +172,7 @@ x3_levels_init_kernel(x3_level* __restrict__ levels, uint64_t n_rows, x3_level* 
     sum->first = ~0ull;
     sum->replays = 0;
   }
-  const x3_level id{0, 0, 32767, -32768, 0, 0};
+  const x3_level id = X3L_IDENTITY;
   for (uint64_t i = i0; i < n_rows + cap; i += stride) {
     if (i < n_rows) levels[i] = id;
     else rows[i - n_rows] = id;
@@ -178,16 +226,9 @@ __global__ void __launch_bounds__(1024)
 x3_corpus_levels_rows_kernel(const x3_corpus_entry* __restrict__ ent, uint64_t n, uint64_t bin_len,
                              unsigned long long* __restrict__ row_first) {
   __shared__ unsigned long long s[1024];
-  const uint64_t per = (n + blockDim.x - 1) / blockDim.x;
-  const uint64_t a = min((uint64_t)threadIdx.x * per, n), b = min(a + per, n);
-  unsigned long long c = 0;
-  for (uint64_t e = a; e < b; ++e) c += x3l_entry_rows(ent[e].n_samples, bin_len);
-  unsigned long long total;
-  unsigned long long run = x3w_block_excl_scan(c, s, &total);
-  for (uint64_t e = a; e < b; ++e) {
-    row_first[e] = run;
-    run += x3l_entry_rows(ent[e].n_samples, bin_len);
-  }
+  const unsigned long long total = x3w_scan_items(
+      n, s, [&](uint64_t e) { return x3l_entry_rows(ent[e].n_samples, bin_len); },
+      [&](uint64_t e, unsigned long long run) { row_first[e] = run; });
   if (threadIdx.x == 0) row_first[n] = total;
 }
 
@@ -225,17 +266,12 @@ __global__ void __launch_bounds__(1024)
 x3_levels_scan_kernel(const uint32_t* __restrict__ cnt, uint64_t F, uint64_t cap, unsigned long long* __restrict__ row,
                       int32_t* __restrict__ fst) {
   __shared__ unsigned long long s[1024];
-  const uint64_t per = (F + blockDim.x - 1) / blockDim.x;
-  const uint64_t a = min((uint64_t)threadIdx.x * per, F), b = min(a + per, F);
-  unsigned long long c = 0;
-  for (uint64_t f = a; f < b; ++f) c += cnt[f];
-  unsigned long long total;
-  unsigned long long run = x3w_block_excl_scan(c, s, &total);
-  for (uint64_t f = a; f < b; ++f) {
-    row[f] = run;
-    run += cnt[f];
-    if (cnt[f] && run > cap) fst[f] = X3W_FLAG;
-  }
+  const unsigned long long total = x3w_scan_items(
+      F, s, [&](uint64_t f) { return (unsigned long long)cnt[f]; },
+      [&](uint64_t f, unsigned long long run) {
+        row[f] = run;
+        if (cnt[f] && run + cnt[f] > cap) fst[f] = X3W_FLAG;
+      });
   if (threadIdx.x == 0) row[F] = total;
 }
 
@@ -261,11 +297,9 @@ x3_levels_accum_kernel(const uint8_t* __restrict__ x3, uint64_t len, const uint6
       if (bin < nlim) x3l_merge(mine + (bin - b0), a);
     };
     // a stretch's samples come in order, from sample 0 or from the first sample of block sb * j
-    X3LevBinner bn;
-    bn.open(fr.pos + (j ? 1u + (uint64_t)sb * j * p.block_len : 0u), bl);
-    const int r = x3w_stretch(x3, len, frame_off[f], p, idx, segd, sb, nseg, f, j,
-                              [&](uint32_t, uint32_t v) { bn.add(v, flush); });
-    flush(bn.bin, bn.a);
+    const int r = x3l_bin_samples(
+        fr.pos + (j ? 1u + (uint64_t)sb * j * p.block_len : 0u), bl,
+        [&](auto put_at) { return x3w_stretch(x3, len, frame_off[f], p, idx, segd, sb, nseg, f, j, put_at); }, X3LevKeepAll{}, flush);
     if (r < 0) atomicOr(&fst[f], X3W_FLAG);
   }
 }
@@ -291,10 +325,7 @@ x3_levels_fixup_kernel(const uint8_t* __restrict__ x3, const uint64_t* __restric
         auto flush = [&](uint64_t bin, const X3LevAcc& a) {
           if (bin < fr.nlim) x3l_merge(levels + fr.obase + bin, a);
         };
-        X3LevBinner bn;
-        bn.open(fr.pos, bl);
-        (void)x3w_replay_frame(payload, p, blk, [&](uint32_t, uint32_t v) { bn.add(v, flush); });
-        flush(bn.bin, bn.a);
+        (void)x3l_bin_samples(fr.pos, bl, [&](auto put_at) { return x3w_replay_frame(payload, p, blk, put_at); }, X3LevKeepAll{}, flush);
       }
       fst[f] = fs | X3L_DONE;
       atomicAdd(&sum->replays, 1ull);
@@ -328,29 +359,9 @@ x3_levels_merge_kernel(const X3LevFrame* __restrict__ frames, const unsigned lon
         const X3LevFrame fr = frames[f];
         const x3_level r = rows[i];
         key = fr.obase + fr.b0 + (i - row[f]);   // (below obase + nlim <= the caller's rows: x3l_frame_rows)
-        a.sum_sq = r.sum_sq;
-        a.sum = r.sum;
-        a.mn = r.min;
-        a.mx = r.max;
-        a.n = r.n;
+        a.load(r);
       }
     }
-    // runs of equal keys: a lane starts one where its key differs from its left neighbour's (or it has none)
-    const uint64_t left = (uint64_t)__shfl_up((long long)key, 1, X3_WAVE);
-    const bool head = lane == 0u || key == ~0ull || left != key;
-    const unsigned long long heads = __ballot(head);
-    const uint32_t run = (uint32_t)__popcll(heads & (~0ull >> (63u - lane)));
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-      X3LevAcc o;
-      o.sum_sq = (uint64_t)__shfl_down((long long)a.sum_sq, d, X3_WAVE);
-      o.sum = (int64_t)__shfl_down((long long)a.sum, d, X3_WAVE);
-      o.mn = __shfl_down(a.mn, d, X3_WAVE);
-      o.mx = __shfl_down(a.mx, d, X3_WAVE);
-      o.n = (uint32_t)__shfl_down((int)a.n, d, X3_WAVE);
-      const uint32_t orun = (uint32_t)__shfl_down((int)run, d, X3_WAVE);
-      if (lane + d < 64u && orun == run) a.join(o);
-    }
-    if (head && key != ~0ull) x3l_merge(levels + key, a);
+    x3l_merge_runs(levels, key, a, lane);
   }
 }

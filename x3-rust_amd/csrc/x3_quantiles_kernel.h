@@ -22,7 +22,8 @@
 //                                 the rank becomes the rank inside that bin, the bins are cleared for the next pass.  After
 //                                 the last pass the prefix is the value.
 //  x3_quantiles_map_kernel     -- a lane per entry: x3_event_threshold from the two values by x3_threshold_rule
-//  x3_events_adaptive_flag_kernel -- x3_events_flag_kernel with the rule's two values taken from d_thr[entry]
+//  x3_events_adaptive_flag_kernel -- x3_events_flag_kernel's body (x3e_flag_tiles) with the rule's two values taken from
+//                                 d_thr[entry]
 //
 // Workspace (q_ws), from host-known arguments: 8 * n_rows bytes of (key, entry) + 4 * n_ent * n_q * 256 bytes of
 // histograms + 8 * n_ent * n_q bytes of (prefix, rank) + 3 * 4 * n_ent bytes (the two values and K of a thresholds call) +
@@ -214,37 +215,14 @@ __device__ __forceinline__ bool x3q_loud(const x3_level& r, uint64_t mean_sq_min
          (peak_min && peak_min <= X3Q_PEAK_MAX && peak >= (int64_t)peak_min);
 }
 
+// (the entry first: its thresholds are the rule)
 __global__ void __launch_bounds__(256)
 x3_events_adaptive_flag_kernel(X3EvRows q, const x3_event_threshold* __restrict__ thr, uint64_t n_tiles, uint8_t* __restrict__ hot,
                                uint32_t* __restrict__ tile_prev, uint32_t* __restrict__ tile_next) {
-  __shared__ uint32_t s_first[4], s_last[4];
-  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-  for (uint64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
-    const uint64_t r = t * X3E_TILE + threadIdx.x;
-    bool h = false;
-    if (r < q.n_rows) {
-      X3EvEntry en;
-      if (x3e_entry_of(q, r, &en)) {      // (en.e: below n_ent, 0 in the stream form)
-        const x3_event_threshold k = thr[en.e];
-        h = x3q_loud(q.levels[r], k.mean_sq_min, k.peak_min);
-      }
-      hot[r] = h ? X3E_HOT : 0u;
-    }
-    const unsigned long long m = __ballot(h);
-    if (lane == 0) {
-      s_first[wv] = x3e_first_of(m, (uint32_t)(r - lane));
-      s_last[wv] = x3e_last_of(m, (uint32_t)(r - lane));
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      uint32_t first = X3E_NONE, last = X3E_NONE;
-      for (uint32_t w = 0; w < 4u; ++w) {
-        if (s_last[w] != X3E_NONE) last = s_last[w];
-        if (s_first[3u - w] != X3E_NONE) first = s_first[3u - w];
-      }
-      tile_prev[t] = last;
-      tile_next[t] = first;
-    }
-    __syncthreads();
-  }
+  x3e_flag_tiles(q, [&](const X3EvRows& q, uint64_t r) {
+    X3EvEntry en;
+    if (!x3e_entry_of(q, r, &en)) return false;   // (en.e: below n_ent, 0 in the stream form)
+    const x3_event_threshold k = thr[en.e];
+    return x3q_loud(q.levels[r], k.mean_sq_min, k.peak_min);
+  }, n_tiles, hot, tile_prev, tile_next);
 }

@@ -77,41 +77,17 @@ __device__ __forceinline__ bool x3rl_no_rows(const unsigned long long* __restric
   return q >= P || (prow[q + 1u] > cap && prow[q + 1u] > prow[q]);
 }
 
-// ---- range scan: x3_range_scan_kernel with rows where it has lengths
+// ---- range scan: x3w_range_scan with rows where x3_range_scan_kernel has lengths, and no work items
 __global__ void __launch_bounds__(1024)
 x3_range_levels_scan_kernel(X3WinPlan* __restrict__ plan, uint64_t n, const uint32_t* __restrict__ lens, uint64_t bin_len,
                             uint64_t stride, uint64_t rows_cap, unsigned long long* __restrict__ cov_off,
                             unsigned long long* __restrict__ row_off, uint32_t* __restrict__ erows,
                             uint64_t* __restrict__ out_off, X3RLevSummary* __restrict__ sum) {
   __shared__ unsigned long long s[1024];
-  const uint64_t per = (n + blockDim.x - 1) / blockDim.x;
-  const uint64_t a = min((uint64_t)threadIdx.x * per, n), b = min(a + per, n);
-  unsigned long long c = 0;
-  for (uint64_t w = a; w < b; ++w) c += x3l_entry_rows(lens[w], bin_len);
-  unsigned long long total;
-  unsigned long long run = x3w_block_excl_scan(c, s, &total);
-  c = 0;
-  for (uint64_t w = a; w < b; ++w) {
-    const unsigned long long R = x3l_entry_rows(lens[w], bin_len);   // (at most 2^32 - 1: a length has 32 bits)
-    const bool fits = stride ? R <= stride : (run <= rows_cap && R <= rows_cap - run);
-    if (!fits) plan[w] = X3WinPlan{0, 0, X3D_BAD_ARG};
-    erows[w] = fits ? (uint32_t)R : 0u;
-    row_off[w] = run;
-    if (out_off) out_off[w] = stride ? w * stride : run;
-    run += R;
-    c += fits ? plan[w].ncov : 0u;
-  }
-  if (threadIdx.x == 0) {
-    row_off[n] = total;
-    if (out_off) out_off[n] = stride ? n * stride : total;
-    sum->w.total = total;
-  }
-  run = x3w_block_excl_scan(c, s, &total);
-  for (uint64_t w = a; w < b; ++w) {
-    cov_off[w] = run;
-    run += plan[w].ncov;
-  }
-  if (threadIdx.x == 0) cov_off[n] = total;
+  const unsigned long long total = x3w_range_scan<false>(
+      plan, n, [&](uint64_t w) { return x3l_entry_rows(lens[w], bin_len); }, stride, rows_cap, 1u, cov_off, nullptr, row_off, erows,
+      out_off, s);
+  if (threadIdx.x == 0) sum->w.total = total;
 }
 
 // ---- prep: a lane per pair (below P), and a lane per caller's record: the identities.  Packed: the records of ranges that
@@ -134,7 +110,7 @@ x3_range_levels_prep_kernel(const uint64_t* __restrict__ so, const uint64_t* __r
     }
     pairs[q] = pr;
   }
-  const x3_level id{0, 0, 32767, -32768, 0, 0};
+  const x3_level id = X3L_IDENTITY;
   const uint64_t n_rec = stride ? n * stride : min((uint64_t)row_off[n], rows_cap);   // (n * stride <= rows_cap: the host)
   for (uint64_t i = i0; i < n_rec; i += lanes) {
     if (!stride) {
@@ -152,18 +128,13 @@ x3_range_levels_pair_scan_kernel(const X3RLevPair* __restrict__ pairs, const uns
                                  uint64_t P, uint64_t cap, unsigned long long* __restrict__ prow, X3RLevSummary* __restrict__ sum) {
   __shared__ unsigned long long s[1024];
   const uint64_t n_cov = cov_off[n], np = min(n_cov, P);
-  const uint64_t per = (np + blockDim.x - 1) / blockDim.x;
-  const uint64_t a = min((uint64_t)threadIdx.x * per, np), b = min(a + per, np);
-  unsigned long long c = 0;
-  for (uint64_t q = a; q < b; ++q) c += pairs[q].cnt;
-  unsigned long long total;
-  unsigned long long run = x3w_block_excl_scan(c, s, &total);
   unsigned long long over = 0;
-  for (uint64_t q = a; q < b; ++q) {
-    prow[q] = run;
-    run += pairs[q].cnt;
-    over += pairs[q].cnt && run > cap ? 1u : 0u;   // (x3rl_no_rows)
-  }
+  unsigned long long total = x3w_scan_items(
+      np, s, [&](uint64_t q) { return (unsigned long long)pairs[q].cnt; },
+      [&](uint64_t q, unsigned long long run) {
+        prow[q] = run;
+        over += pairs[q].cnt && run + pairs[q].cnt > cap ? 1u : 0u;   // (x3rl_no_rows)
+      });
   if (threadIdx.x == 0) prow[np] = total;
   (void)x3w_block_excl_scan(over, s, &total);
   if (threadIdx.x == 0) sum->overflow = total + (n_cov - np);
@@ -174,7 +145,7 @@ __global__ void __launch_bounds__(256)
 x3_range_levels_init_kernel(const unsigned long long* __restrict__ cov_off, uint64_t n, uint64_t P, uint64_t cap,
                             const unsigned long long* __restrict__ prow, x3_level* __restrict__ rows) {
   const uint64_t used = min((uint64_t)prow[min((uint64_t)cov_off[n], P)], cap);
-  const x3_level id{0, 0, 32767, -32768, 0, 0};
+  const x3_level id = X3L_IDENTITY;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < used; i += (uint64_t)gridDim.x * blockDim.x) rows[i] = id;
 }
 
@@ -204,12 +175,10 @@ x3_range_levels_accum_kernel(const uint8_t* __restrict__ x3, uint64_t len, const
     // a stretch's samples come in order, from sample 0 or from the first sample of block sb * j; the first of them inside
     // the range, if any, is sample max(s0, lo)
     const uint64_t s0 = j ? 1u + (uint64_t)sb * j * p.block_len : 0u;
-    X3LevBinner bn;
-    bn.open((uint64_t)pr.r0 + (s0 > lo ? s0 - lo : 0u), bl);
-    const int r = x3w_stretch(x3, len, frame_off[pr.f], p, idx, segd, sb, nseg, pr.f, j, [&](uint32_t s, uint32_t v) {
-      if (s - lo < span) bn.add(v, flush);
-    });
-    flush(bn.bin, bn.a);
+    const int r = x3l_bin_samples(
+        (uint64_t)pr.r0 + (s0 > lo ? s0 - lo : 0u), bl,
+        [&](auto put_at) { return x3w_stretch(x3, len, frame_off[pr.f], p, idx, segd, sb, nseg, pr.f, j, put_at); },
+        [&](uint32_t s) { return s - lo < span; }, flush);
     if (r < 0) atomicOr(&fst[pr.f], X3W_FLAG);
   }
 }
@@ -250,12 +219,9 @@ x3_range_levels_fixup_kernel(const uint8_t* __restrict__ x3, const uint64_t* __r
               if (bin < (uint64_t)R) x3l_merge(mine + bin, a);
             };
             const uint32_t span = hi - lo;
-            X3LevBinner bn;
-            bn.open(r0, bl);
-            (void)x3w_replay_frame(payload, p, blk, [&](uint32_t s, uint32_t v) {
-              if (s - lo < span) bn.add(v, flush);
-            });
-            flush(bn.bin, bn.a);
+            (void)x3l_bin_samples(
+                r0, bl, [&](auto put_at) { return x3w_replay_frame(payload, p, blk, put_at); },
+                [&](uint32_t s) { return s - lo < span; }, flush);
           }
           ++replayed;
         }
@@ -295,29 +261,9 @@ x3_range_levels_merge_kernel(const X3RLevPair* __restrict__ pairs, const unsigne
       if (fst[pr.f] == X3D_OK && !x3rl_no_rows(prow, q, P, cap) && bin < (uint64_t)erows[pr.w]) {
         const x3_level r = rows[i];
         key = x3rl_base(row_off, stride, pr.w) + bin;   // (below the range's base + erows: inside rows_cap, the range scan)
-        a.sum_sq = r.sum_sq;
-        a.sum = r.sum;
-        a.mn = r.min;
-        a.mx = r.max;
-        a.n = r.n;
+        a.load(r);
       }
     }
-    // runs of equal keys: a lane starts one where its key differs from its left neighbour's (or it has none)
-    const uint64_t left = (uint64_t)__shfl_up((long long)key, 1, X3_WAVE);
-    const bool head = lane == 0u || key == ~0ull || left != key;
-    const unsigned long long heads = __ballot(head);
-    const uint32_t run = (uint32_t)__popcll(heads & (~0ull >> (63u - lane)));
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-      X3LevAcc o;
-      o.sum_sq = (uint64_t)__shfl_down((long long)a.sum_sq, d, X3_WAVE);
-      o.sum = (int64_t)__shfl_down((long long)a.sum, d, X3_WAVE);
-      o.mn = __shfl_down(a.mn, d, X3_WAVE);
-      o.mx = __shfl_down(a.mx, d, X3_WAVE);
-      o.n = (uint32_t)__shfl_down((int)a.n, d, X3_WAVE);
-      const uint32_t orun = (uint32_t)__shfl_down((int)run, d, X3_WAVE);
-      if (lane + d < 64u && orun == run) a.join(o);
-    }
-    if (head && key != ~0ull) x3l_merge(levels + key, a);
+    x3l_merge_runs(levels, key, a, lane);
   }
 }
