@@ -798,6 +798,33 @@ int x3_corpus_ranges_dev(x3_ctx* ctx, const x3_corpus* corpus, const uint32_t* d
 int x3_corpus_levels_rows(const x3_corpus* corpus, uint64_t bin_len, uint64_t* row_first);
 int x3_corpus_levels_dev(x3_ctx* ctx, const x3_corpus* corpus, uint64_t bin_len, x3_level* d_levels, uint64_t n_rows,
                          int32_t* d_frame_status);
+/* ---- SIGNAL LEVELS (no counterpart in the reference): the levels of the samples' FIRST DIFFERENCE -- a one-tap high-pass
+ * in front of the detection chain at no extra read.  `signal` selects what is binned; any other
+ * value is X3_ERR_BAD_ARG with nothing enqueued.
+ *   X3_LEVEL_SIGNAL_SAMPLES: the records of x3_levels_dev / x3_corpus_levels_dev on the same arguments, field for field.
+ *   X3_LEVEL_SIGNAL_DIFF: positions, bins, n_bins * bin_len, frame statuses and "every record is written" are exactly
+ * x3_levels_dev's.  What the position of sample i of frame f adds:
+ *     i >= 1: y = clamp(x_f[i] - x_f[i-1], -32768, 32767), counted iff frame f has status 0;
+ *     i == 0: y = clamp(x_f[0] - x_{f-1}[last], -32768, 32767), counted iff f >= 1, frames f - 1 and f BOTH have status 0
+ *             and, in the corpus form, both belong to the same entry.  (A checked frame's sample count equals
+ *             d_sample_offsets[f + 1] - d_sample_offsets[f], so two good neighbours in the table are always adjacent in
+ *             position: the two samples are neighbours of the signal.)
+ * Otherwise the position adds nothing and n is not incremented: the first sample of a stream or entry has no difference,
+ * and a failed frame takes both of its seams with it, the one in front of it and the one behind it.  n counts differences: a
+ * clean stream or entry of N samples has records whose n sum to N - 1.  Empty bins hold the identities.
+ *   y is an int16 signal like any other: the records obey what x3_events_dev, x3_level_quantiles_dev,
+ * x3_level_thresholds_dev and x3_events_adaptive_dev rely on (|y| <= 32768, sum_sq / n <= 1 << 30) and go into them unchanged.
+ *   Argument checks, the asynchronous contract, x3_levels_result and the option "last_levels_replays" are those of
+ * x3_levels_dev / x3_corpus_levels_dev.  The segment index stays a hint: the sample in front of a stretch comes from the
+ * index entry, and an entry with a wrong sample is contradicted by the stretch that ends there, as a wrong bit position is. */
+int x3_signal_levels_dev(x3_ctx* ctx, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
+                         const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
+                         const uint64_t* d_seg_index, uint32_t seg_blocks, uint64_t bin_len,
+                         x3_level* d_levels, uint64_t n_bins, int32_t* d_frame_status, int signal);
+int x3_corpus_signal_levels_dev(x3_ctx* ctx, const x3_corpus* corpus, uint64_t bin_len, x3_level* d_levels, uint64_t n_rows,
+                                int32_t* d_frame_status, int signal);
+#define X3_LEVEL_SIGNAL_SAMPLES 0   /* the signals of x3_signal_levels_dev */
+#define X3_LEVEL_SIGNAL_DIFF 1
 /* ---- EVENTS (no counterpart in the reference): runs of loud bins of level records as ranges (entry, start, len), found on
  * the device -- the link between the levels calls and the ranges calls, with no host trip.
  *   Row b of d_levels is a bin of bin_len positions as x3_levels_dev / x3_corpus_levels_dev write it.  A bin is HOT when

@@ -14,7 +14,10 @@ Families: (e) the single-pass encoders on block_len 20 with mixed content, many 
           and wild starts, against the oracle's frame verdicts (not in the default family set); (x) the same with the
           index built by x3_seg_index_build_dev on the stream as it is -- any block length and code set, damage included
           (not in the default family set); (r) range levels (x3_range_levels_dev): random ranges x bin lengths x layouts x
-          damage, with and without an index, GPU == tests/range_levels_ref.py (not in the default family set)."""
+          damage, with and without an index, GPU == tests/range_levels_ref.py (not in the default family set); (h) levels of the
+          first difference (x3_signal_levels_dev / x3_corpus_signal_levels_dev, X3_LEVEL_SIGNAL_DIFF): random content x
+          geometry x bin lengths x damage, with, without and with a damaged index, a stream and the same stream cut into
+          corpus entries, GPU == tests/diff_levels_ref.py on the oracle's frame verdicts (not in the default family set)."""
 import argparse, ctypes as C, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "x3-rust_amd"))
@@ -919,6 +922,127 @@ def fam_r(rng, tag):
 
 
 fams["r"] = fam_r
+
+
+def fam_h(rng, tag):
+    """signal levels: the DIFF records and frame statuses of a random stream -- any geometry, damaged frames, a damaged or
+    walk-built index or none -- against diff_levels_ref on the oracle's frame verdicts; then the same frames as a corpus of
+    random entries, where no difference may cross from one entry into the next; SAMPLES against x3_levels_dev byte for byte"""
+    import diff_levels_ref as DL
+    import levels_ref as LR
+    r = rng.random()
+    if r < 0.5:
+        p = x3hip.Params.default()
+    elif r < 0.75:
+        p = x3hip.Params.make(int(rng.choice([10, 40])), int(rng.choice([100, 256, 500])))
+    else:
+        bl = int(rng.integers(2, 61))
+        codes = (0, 1, 3) if rng.random() < 0.5 else tuple(int(c) for c in rng.integers(0, 4, size=3))
+        p = x3hip.Params.make(bl, int(rng.integers(1, max(2, 30000 // bl))), codes)
+        if x3hip.lib().x3_params_validate(C.byref(p)) != 0:
+            return
+    spf = p.block_len * p.blocks_per_frame
+    n = int(rng.integers(1, (12 if rng.random() < 0.8 else 80) * min(spf, 4000) + 100))
+    wav = content(rng, n)
+    if rng.random() < 0.2:   # full-scale steps: differences that clamp
+        k = int(rng.integers(1, 200))
+        at = rng.integers(0, n, k)
+        wav[at] = np.where(rng.random(k) < 0.5, -32768, 32767).astype(np.int16)
+    rc, stream, _ = O.encode(wav, oparams(p))
+    if rc != 0:
+        return
+    offs = frame_offsets(stream)
+    so = [0]
+    for off in offs:
+        so.append(so[-1] + (int(stream[off + 4]) << 8 | int(stream[off + 5])))
+    if so[-1] != n:
+        return
+    F = len(offs)
+    bad = stream.copy()
+    if rng.random() < 0.5:
+        for _ in range(int(rng.integers(1, 4))):
+            off = offs[int(rng.integers(0, F))]
+            plen = int(stream[off + 6]) << 8 | int(stream[off + 7])
+            kind = int(rng.integers(0, 3))
+            if kind == 0 and plen > 2:      # payload bits, CRC refreshed (a decode error or other samples) or not
+                q = off + 20 + int(rng.integers(2, plen))
+                k = min(int(rng.integers(1, 12)), off + 20 + plen - q)
+                bad[q:q + k] = 0 if rng.random() < 0.5 else rng.integers(0, 256, size=k, dtype=np.uint8)
+                if rng.random() < 0.7:
+                    refresh_crcs(bad, off)
+            elif kind == 1:                 # a header byte other than the sample count and the payload length
+                q = off + int(rng.choice([0, 1, 2, 3, 8, 12, 16, 17, 18, 19]))
+                bad[q] ^= np.uint8(1 << int(rng.integers(0, 8)))
+            else:                           # one payload bit -- the first sample's among them: the seam's head
+                bad[off + 20 + int(rng.integers(0, min(plen, 4) if rng.random() < 0.5 else plen))] ^= np.uint8(1 << int(rng.integers(0, 8)))
+    verdicts = _frame_verdicts(bad, offs, p)
+    statuses = [v for v, _ in verdicts]
+    frames = [w if v == 0 else np.zeros(0, dtype=np.int16) for v, w in verdicts]
+    bin_len = int(rng.choice([0, 1, 2, 7, p.block_len, spf, spf + 1, max(1, spf - 1), int(rng.integers(1, n + 2)), 1 << 20]))
+    if bin_len == 1 and n > 200_000:
+        bin_len = 3
+    exact = LR.n_bins_for(n, bin_len)
+    n_bins = max(1, exact + int(rng.choice([0, 0, -1, 3])))
+    d = []
+    try:
+        d_off = ctx.alloc(8 * (F + 1)); d.append(d_off)
+        ctx.upload(d_off, np.array(offs + [stream.size], dtype=np.uint64))
+        sb = int(rng.choice([0, 2, 4, 32, 64]))
+        index = "walk" if rng.random() < 0.5 else "decode"
+        if index == "walk" and sb == 0:
+            sb = 8
+        src = x3hip.WindowSource(ctx, bad, p, seg_blocks=sb, frame_offsets=d_off, n_frames=F, index=index)
+        d.extend(src._own); src._own = []
+        assert src.total == n, (tag, "total", src.total, n)
+        if src.d_seg_index is not None and rng.random() < 0.3:   # a damaged index: a hint, never trusted -- seeds included
+            ne = x3hip.lib().x3_seg_index_entries(F, C.byref(p), src.seg_blocks)
+            idx = ctx.download(src.d_seg_index, 8 * ne, np.uint64)
+            if ne > 1:
+                sel = rng.random(ne) < 0.2; sel[0] = False
+                how = rng.random()
+                if how < 0.4:      # the sample alone
+                    idx[sel] ^= (rng.integers(1, 1 << 16, int(sel.sum()), dtype=np.uint64) << np.uint64(32))
+                elif how < 0.7:    # the bit offset alone
+                    idx[sel] += rng.integers(1, 9, int(sel.sum()), dtype=np.uint64)
+                else:
+                    idx[sel] = rng.integers(0, 1 << 49, int(sel.sum()), dtype=np.uint64)
+            ctx.upload(src.d_seg_index, idx)
+        got, st = src.levels(bin_len, n_bins, signal="diff")
+        assert st.tolist() == statuses, (tag, "statuses", st.tolist(), statuses)
+        want = DL.signal_levels(frames, statuses, so[:-1], bin_len, n_bins, DL.DIFF)
+        for k in LR.LEVEL_DTYPE.names:
+            assert np.array_equal(got[k], want[k]), (tag, "stream", k, bin_len, n_bins, np.flatnonzero(got[k] != want[k])[:8].tolist())
+        same, _ = src.levels(bin_len, n_bins, signal="samples")
+        old, _ = src.levels(bin_len, n_bins)
+        assert same.tobytes() == old.tobytes(), (tag, "samples")
+        # the same bytes as a corpus: the frames cut into entries at random frame boundaries
+        if F >= 1 and bin_len <= 0xFFFFFFFF:
+            cuts = sorted(set([0, F] + [int(v) for v in rng.integers(0, F + 1, int(rng.integers(0, 5)))]))
+            ends = offs + [stream.size]
+            e_off = [ends[a] for a in cuts[:-1]]
+            e_len = [ends[b] - ends[a] for a, b in zip(cuts[:-1], cuts[1:])]
+            try:
+                corpus = x3hip.Corpus(ctx, bad, e_off, e_len, params=p, seg_blocks=src.seg_blocks or 8, index="walk")
+            except x3hip.X3Error:   # (a geometry the corpus build refuses an index for)
+                return
+            try:
+                if corpus.entries["n_frames"].tolist() == [b - a for a, b in zip(cuts[:-1], cuts[1:])]:
+                    rows, rf, cst = corpus.levels(bin_len, signal="diff")
+                    ref = []
+                    for a, b in zip(cuts[:-1], cuts[1:]):
+                        ref.append((frames[a:b], statuses[a:b], [so[f] - so[a] for f in range(a, b)], so[b] - so[a]))
+                    wrows, wrf = DL.corpus_signal_levels(ref, bin_len, DL.DIFF)
+                    assert np.array_equal(rf, wrf) and cst.tolist() == statuses, (tag, "corpus layout")
+                    for k in LR.LEVEL_DTYPE.names:
+                        assert np.array_equal(rows[k], wrows[k]), (tag, "corpus", k, bin_len, cuts, np.flatnonzero(rows[k] != wrows[k])[:8].tolist())
+            finally:
+                corpus.close()
+    finally:
+        for q in d:
+            ctx.free(q)
+
+
+fams["h"] = fam_h
 
 
 def run(seed=1, minutes=None, trials=None, families="egdbaf", only=-1, context=None):

@@ -1313,15 +1313,18 @@ size_t levels_carve(char* base, uint64_t F, uint64_t n_rows, uint64_t fix_waves,
   w->scratch = k.take<int16_t>(std::max<uint64_t>(fix_waves, 4) * scratch_per);
   w->sum = k.take<X3LevSummary>(1);
   w->row_first = k.take<unsigned long long>(n_ent + 1, 1);
+  w->tail = reinterpret_cast<int32_t*>(w->cnt);   // (the scan kernel is the row counts' last reader)
   return k.at;
 }
 
 // The launch set of a levels call behind its prep step: prep(grid, row_first, fst, frames, cnt) enqueues the kernels that
 // give every frame its position, its records and its row count.  n_ent: entries of a corpus call (their row prefix lives
-// in the workspace), 0 for a stream.
+// in the workspace), 0 for a stream.  signal: X3_LEVEL_SIGNAL_SAMPLES, or X3_LEVEL_SIGNAL_DIFF -- the other instance of the
+// accumulate and fix-up kernels, which leave every good frame's last sample in the workspace, and the seam kernel behind them.
 template <class Prep>
 static int levels_launch(x3_ctx* c, const FrameSource& s, uint64_t bin_len, x3_level* d_levels, uint64_t n_rows,
-                         int32_t* d_frame_status, uint64_t n_ent, Prep prep) {
+                         int32_t* d_frame_status, uint64_t n_ent, int signal, Prep prep) {
+  const bool diff = signal == X3_LEVEL_SIGNAL_DIFF;
   HIPCHK(c, hipSetDevice(c->device));
   const uint64_t F = s.F, cap = n_rows + F;
   const uint32_t scratch_per = levels_scratch_per(s.dp.block_len);
@@ -1336,14 +1339,22 @@ static int levels_launch(x3_ctx* c, const FrameSource& s, uint64_t bin_len, x3_l
                      s.d_sample_offsets, F, w.fst);
   prep(dim3(grid_for(F, 256)), w.row_first, (const int32_t*)w.fst, w.frames, w.cnt);
   hipLaunchKernelGGL(x3_levels_scan_kernel, dim3(1), dim3(1024), 0, c->stream, (const uint32_t*)w.cnt, F, cap, w.row, w.fst);
-  hipLaunchKernelGGL(x3_levels_accum_kernel, dim3(grid_for(F * s.nseg, 256)), dim3(256), 0, c->stream, s.d_x3, s.x3_len,
-                     s.d_frame_offsets, F, s.dp, s.idx, s.seg_blocks, s.nseg, bin_len, (const X3LevFrame*)w.frames,
-                     (const unsigned long long*)w.row, w.rows, w.fst);
-  hipLaunchKernelGGL(x3_levels_fixup_kernel, dim3((unsigned)((fix_waves + 3) / 4)), dim3(256), 0, c->stream, s.d_x3,
-                     s.d_frame_offsets, F, s.dp, bin_len, (const X3LevFrame*)w.frames, w.fst, d_levels, d_frame_status, w.scratch,
-                     scratch_per, w.sum);
+  auto decode = [&](auto sig, auto tail) {   // the two kernels that decode, for a signal
+    using Signal = decltype(sig);
+    hipLaunchKernelGGL(x3_levels_accum_kernel<Signal>, dim3(grid_for(F * s.nseg, 256)), dim3(256), 0, c->stream, s.d_x3, s.x3_len,
+                       s.d_frame_offsets, F, s.dp, s.idx, s.seg_blocks, s.nseg, bin_len, (const X3LevFrame*)w.frames,
+                       (const unsigned long long*)w.row, w.rows, w.fst, tail);
+    hipLaunchKernelGGL(x3_levels_fixup_kernel<Signal>, dim3((unsigned)((fix_waves + 3) / 4)), dim3(256), 0, c->stream, s.d_x3,
+                       s.d_frame_offsets, F, s.dp, bin_len, (const X3LevFrame*)w.frames, w.fst, d_levels, d_frame_status,
+                       w.scratch, scratch_per, w.sum, tail);
+  };
+  if (diff) decode(X3LevDiff{}, w.tail);
+  else decode(X3LevSamples{}, X3LevNoTail{});
   hipLaunchKernelGGL(x3_levels_merge_kernel, dim3(grid_for(cap, 256)), dim3(256), 0, c->stream, (const X3LevFrame*)w.frames,
                      (const unsigned long long*)w.row, F, cap, (const x3_level*)w.rows, (const int32_t*)w.fst, d_levels);
+  if (diff && F > 1)
+    hipLaunchKernelGGL(x3_levels_seam_kernel, dim3(grid_for(F, 256)), dim3(256), 0, c->stream, s.d_x3, s.x3_len, s.d_frame_offsets,
+                       F, bin_len, (const X3LevFrame*)w.frames, (const int32_t*)w.fst, (const int32_t*)w.tail, d_levels);
   HIPCHK(c, hipGetLastError());
   c->levels.pending = true;
   c->levels.count = F;
@@ -1351,19 +1362,29 @@ static int levels_launch(x3_ctx* c, const FrameSource& s, uint64_t bin_len, x3_l
   return X3_OK;
 }
 
-extern "C" int x3_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
-                             const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
-                             const uint64_t* d_seg_index, uint32_t seg_blocks, uint64_t bin_len, x3_level* d_levels,
-                             uint64_t n_bins, int32_t* d_frame_status) {
-  if (!c || !levels_args_ok(c, d_levels, n_bins, d_frame_status)) return X3_ERR_BAD_ARG;
+static bool levels_signal_ok(int signal) { return signal == X3_LEVEL_SIGNAL_SAMPLES || signal == X3_LEVEL_SIGNAL_DIFF; }
+
+extern "C" int x3_signal_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
+                                    const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
+                                    const uint64_t* d_seg_index, uint32_t seg_blocks, uint64_t bin_len, x3_level* d_levels,
+                                    uint64_t n_bins, int32_t* d_frame_status, int signal) {
+  if (!c || !levels_signal_ok(signal) || !levels_args_ok(c, d_levels, n_bins, d_frame_status)) return X3_ERR_BAD_ARG;
   FrameSource s;
   const int rc = stream_source(d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, p, d_seg_index, seg_blocks, &s);
   if (rc) return rc;
-  return levels_launch(c, s, bin_len, d_levels, n_bins, d_frame_status, 0,
+  return levels_launch(c, s, bin_len, d_levels, n_bins, d_frame_status, 0, signal,
                        [&](dim3 grid, unsigned long long*, const int32_t* fst, X3LevFrame* frames, uint32_t* cnt) {
                          hipLaunchKernelGGL(x3_levels_prep_kernel, grid, dim3(256), 0, c->stream, d_sample_offsets, n_frames,
                                             bin_len, n_bins, fst, frames, cnt);
                        });
+}
+
+extern "C" int x3_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
+                             const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
+                             const uint64_t* d_seg_index, uint32_t seg_blocks, uint64_t bin_len, x3_level* d_levels,
+                             uint64_t n_bins, int32_t* d_frame_status) {
+  return x3_signal_levels_dev(c, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, p, d_seg_index, seg_blocks, bin_len,
+                              d_levels, n_bins, d_frame_status, X3_LEVEL_SIGNAL_SAMPLES);
 }
 
 extern "C" int x3_levels_result(x3_ctx* c, uint64_t* n_bad_frames, uint64_t* first_bad, int* first_bad_status) {
@@ -2029,21 +2050,31 @@ static void corpus_row_prefix(x3_ctx* c, const x3_corpus* k, uint64_t bin_len, u
   if (q) q->row_first = row_first;
 }
 
-extern "C" int x3_corpus_levels_dev(x3_ctx* c, const x3_corpus* k, uint64_t bin_len, x3_level* d_levels, uint64_t n_rows,
-                                    int32_t* d_frame_status) {
-  if (!c || !k || !levels_args_ok(c, d_levels, n_rows, d_frame_status)) return X3_ERR_BAD_ARG;
+static int corpus_levels_call(x3_ctx* c, const x3_corpus* k, const char* entry, uint64_t bin_len, x3_level* d_levels,
+                              uint64_t n_rows, int32_t* d_frame_status, int signal) {
+  if (!c || !k || !levels_signal_ok(signal) || !levels_args_ok(c, d_levels, n_rows, d_frame_status)) return X3_ERR_BAD_ARG;
   FrameSource s;
   X3EvRows q;
   int rc;
-  if ((rc = corpus_source(c, k, "x3_corpus_levels_dev", &s))) return rc;
-  if ((rc = corpus_rows(c, k, d_levels, n_rows, bin_len, "x3_corpus_levels_dev", &q))) return rc;
-  return levels_launch(c, s, bin_len, d_levels, n_rows, d_frame_status, k->n,
+  if ((rc = corpus_source(c, k, entry, &s))) return rc;
+  if ((rc = corpus_rows(c, k, d_levels, n_rows, bin_len, entry, &q))) return rc;
+  return levels_launch(c, s, bin_len, d_levels, n_rows, d_frame_status, k->n, signal,
                        [&](dim3 grid, unsigned long long* row_first, const int32_t* fst, X3LevFrame* frames, uint32_t* cnt) {
                          corpus_row_prefix(c, k, bin_len, row_first);
                          hipLaunchKernelGGL(x3_corpus_levels_prep_kernel, grid, dim3(256), 0, c->stream,
                                             k->d_ent, k->n, (const unsigned long long*)row_first,
                                             s.d_sample_offsets, s.F, bin_len, n_rows, fst, frames, cnt);
                        });
+}
+
+extern "C" int x3_corpus_levels_dev(x3_ctx* c, const x3_corpus* k, uint64_t bin_len, x3_level* d_levels, uint64_t n_rows,
+                                    int32_t* d_frame_status) {
+  return corpus_levels_call(c, k, "x3_corpus_levels_dev", bin_len, d_levels, n_rows, d_frame_status, X3_LEVEL_SIGNAL_SAMPLES);
+}
+
+extern "C" int x3_corpus_signal_levels_dev(x3_ctx* c, const x3_corpus* k, uint64_t bin_len, x3_level* d_levels, uint64_t n_rows,
+                                           int32_t* d_frame_status, int signal) {
+  return corpus_levels_call(c, k, "x3_corpus_signal_levels_dev", bin_len, d_levels, n_rows, d_frame_status, signal);
 }
 
 // ------------------------------------------------------------------------------------------------

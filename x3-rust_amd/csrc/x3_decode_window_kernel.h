@@ -501,10 +501,18 @@ x3_window_check_kernel(const uint8_t* __restrict__ x3, uint64_t len, const uint6
 // Stretch j of checked frame f by one lane: from block 0 or from usable entry j to the next usable entry, whose bit position
 // and last sample it must meet.  Sample s of the frame goes to put_at(s, value).  0: entry j starts no stretch (the
 // stretch in front runs through its blocks), 1: decoded and proven, -1: the frame is one for the reference's reader.
-template <class Put>
+// `watch` (optional) sees the two samples a consumer with one sample of history needs and put_at does not carry:
+// watch.seed(v), the sample in front of a stretch that starts at an index entry -- the entry's, unproven like its bit
+// position until the stretch in front has met it -- and watch.end(v), the frame's last sample, from the one stretch that
+// runs to the frame's end.  This function stays the only reader of the entry format.
+struct X3WNoWatch {
+  __device__ __forceinline__ void seed(uint32_t) const {}
+  __device__ __forceinline__ void end(uint32_t) const {}
+};
+template <class Put, class Watch = X3WNoWatch>
 __device__ __forceinline__ int x3w_stretch(const uint8_t* __restrict__ x3, uint64_t len, uint64_t off, const X3DevParams& p,
                                            const uint2* __restrict__ idx, bool segd, uint32_t sb, uint32_t nseg, uint64_t f,
-                                           uint32_t j, Put put_at) {
+                                           uint32_t j, Put put_at, Watch watch = Watch{}) {
   const uint32_t pitch = nseg - 1u;
   const uint64_t p0 = off + 20u;
   const uint32_t h1 = x3w_be32_at(x3, len, off + 4u);
@@ -533,6 +541,7 @@ __device__ __forceinline__ int x3w_stretch(const uint8_t* __restrict__ x3, uint6
   } else {
     const uint2 h = e[j - 1u];
     last = h.y & 0xFFFFu;
+    watch.seed(last);
     br.open(x3, len, p0 * 8u + h.x);
   }
   const uint64_t end_bit = (p0 + plen) * 8u;
@@ -547,6 +556,7 @@ __device__ __forceinline__ int x3w_stretch(const uint8_t* __restrict__ x3, uint6
     const uint2 h = e[q - 1u];
     ok = br.pos - p0 * 8u == h.x && last == (h.y & 0xFFFFu);
   }
+  if (ok && b1 == nbf) watch.end(last);
   return ok ? 1 : -1;
 }
 

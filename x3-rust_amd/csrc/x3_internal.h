@@ -465,6 +465,8 @@ struct X3LevSummary;
 struct LevWs {
   int32_t* fst; X3LevFrame* frames; uint32_t* cnt; unsigned long long* row;   // per frame (row: F + 1 words)
   x3_level* rows; int16_t* scratch; X3LevSummary* sum; unsigned long long* row_first;
+  int32_t* tail;   // per frame: its last sample (X3_LEVEL_SIGNAL_DIFF: what the seam to the next frame is formed against),
+                   // in cnt's words: the row counts are dead behind the scan kernel, in front of the first kernel that decodes
 };
 X3_INTERNAL uint32_t levels_scratch_per(uint32_t block_len);
 X3_INTERNAL uint64_t levels_fix_waves(uint64_t F, uint32_t scratch_per);

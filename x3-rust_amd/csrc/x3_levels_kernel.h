@@ -25,6 +25,9 @@
 //  x3_levels_accum_kernel    -- a lane per (frame, stretch)
 //  x3_levels_fixup_kernel    -- a wave per frame: flagged frames through the reference's reader; d_frame_status, summary
 //  x3_levels_merge_kernel    -- a lane per partial row; rows of one bin that lie side by side in a wave are joined first
+//  x3_levels_seam_kernel     -- X3_LEVEL_SIGNAL_DIFF only: a lane per frame, the one difference across the frame's front seam
+// The accumulate and fix-up kernels are templates over the SIGNAL, what a position adds to its bin: X3LevSamples (the levels
+// calls) or X3LevDiff (x3_signal_levels_dev).
 //
 // What the range levels, events and quantiles kernels (x3_range_levels_kernel.h, x3_events_kernel.h, x3_quantiles_kernel.h)
 // share with these: X3L_IDENTITY, the record of an empty bin; X3LevAcc, a record in registers (load, record, join);
@@ -71,8 +74,8 @@ struct X3LevAcc {
   }
   __device__ __forceinline__ x3_level record() const { return x3_level{sum_sq, sum, mn, mx, n, 0}; }
   __device__ __forceinline__ void reset() { load(X3L_IDENTITY); }
-  __device__ __forceinline__ void add(uint32_t v) {
-    const int32_t s = (int32_t)(int16_t)(uint16_t)v;
+  __device__ __forceinline__ void add(uint32_t v) { add_value((int32_t)(int16_t)(uint16_t)v); }
+  __device__ __forceinline__ void add_value(int32_t s) {   // -32768 <= s <= 32767
     sum_sq += (uint32_t)(s * s);
     sum += s;
     mn = min(mn, s);
@@ -133,9 +136,10 @@ struct X3LevBinner {
     left = rem < X3L_FAR ? (uint32_t)rem : X3L_FAR;
     step = bl < X3L_FAR ? (uint32_t)bl : X3L_FAR;
   }
-  template <class Flush>
-  __device__ __forceinline__ void add(uint32_t v, Flush flush) {
-    a.add(v);
+  // one position: the signal decides what it adds to the open bin, if anything; the position counts either way
+  template <class Signal, class Flush>
+  __device__ __forceinline__ void put(Signal&& sig, uint32_t v, Flush flush) {
+    sig.add(a, v);
     if (--left == 0u) {
       flush(bin, a);
       a.reset();
@@ -145,14 +149,48 @@ struct X3LevBinner {
   }
 };
 
+// THE SIGNAL (x3_signal_levels_dev): what a position adds to its bin.
+// X3LevSamples: the sample.  X3LevDiff: the sample minus the one in front of it, clamped to 16 bits -- `prev` in a register;
+// the first sample a lane sees without a seed (sample 0 of a frame) adds nothing: that difference crosses the frame's seam
+// and is x3_levels_seam_kernel's.  seed(v): the sample in front of a stretch (x3w_stretch's watch).  Tail: the kernels'
+// last argument, the per-frame array of last samples that only X3LevDiff has.
+struct X3LevNoTail {};
+struct X3LevSamples {
+  static constexpr bool kDiff = false;
+  using Tail = X3LevNoTail;
+  __device__ __forceinline__ void add(X3LevAcc& a, uint32_t v) { a.add(v); }
+};
+__device__ __forceinline__ int32_t x3l_diff(int32_t s, int32_t prev) { return min(max(s - prev, -32768), 32767); }
+struct X3LevDiff {
+  static constexpr bool kDiff = true;
+  using Tail = int32_t*;   // per frame: its last sample
+  int32_t prev = 0;
+  bool have = false;
+  __device__ __forceinline__ void seed(uint32_t v) {
+    prev = (int32_t)(int16_t)(uint16_t)v;
+    have = true;
+  }
+  __device__ __forceinline__ void add(X3LevAcc& a, uint32_t v) {
+    const int32_t s = (int32_t)(int16_t)(uint16_t)v;
+    if (have) a.add_value(x3l_diff(s, prev));
+    prev = s;
+    have = true;
+  }
+};
+
 // The bins of consecutive positions from g on: decode(put_at) hands sample s of a frame to put_at(s, value), in order;
-// the samples with keep(s) are added, bins that fill go to flush, and so does the open one at the end.  Returns decode's.
-template <class Decode, class Keep, class Flush>
-__device__ __forceinline__ int32_t x3l_bin_samples(uint64_t g, uint64_t bl, Decode decode, Keep keep, Flush flush) {
+// the positions with keep(s) go to the signal, bins that fill go to flush, and so does the open one at the end.  Returns
+// decode's.  A signal with state (X3LevDiff) is the caller's, at `sig`; X3LevSamples has none and nothing of it is captured.
+template <class Signal = X3LevSamples, class Decode, class Keep, class Flush>
+__device__ __forceinline__ int32_t x3l_bin_samples(uint64_t g, uint64_t bl, Decode decode, Keep keep, Flush flush,
+                                                   Signal* sig = nullptr) {
   X3LevBinner bn;
   bn.open(g, bl);
   const int32_t r = decode([&](uint32_t s, uint32_t v) {
-    if (keep(s)) bn.add(v, flush);
+    if (keep(s)) {
+      if constexpr (Signal::kDiff) bn.put(*sig, v, flush);
+      else bn.put(Signal{}, v, flush);
+    }
   });
   flush(bn.bin, bn.a);
   return r;
@@ -275,12 +313,14 @@ x3_levels_scan_kernel(const uint32_t* __restrict__ cnt, uint64_t F, uint64_t cap
   if (threadIdx.x == 0) row[F] = total;
 }
 
-// ---- accumulate: a lane per (frame, stretch) into the frame's own rows
+// ---- accumulate: a lane per (frame, stretch) into the frame's own rows.  Signal: X3LevSamples, or X3LevDiff, whose lanes
+// take the stretch's seed from x3w_stretch and whose lane at the frame's end stores the frame's last sample to tail[f]
+template <class Signal>
 __global__ void __launch_bounds__(256)
 x3_levels_accum_kernel(const uint8_t* __restrict__ x3, uint64_t len, const uint64_t* __restrict__ frame_off, uint64_t F,
                        X3DevParams p, const uint2* __restrict__ idx, uint32_t sb, uint32_t nseg, uint64_t bin_len,
                        const X3LevFrame* __restrict__ frames, const unsigned long long* __restrict__ row,
-                       x3_level* __restrict__ rows, int32_t* __restrict__ fst) {
+                       x3_level* __restrict__ rows, int32_t* __restrict__ fst, typename Signal::Tail tail) {
   const bool segd = x3w_index_ok(idx, sb);
   const uint32_t ns = segd ? nseg : 1u;
   const uint64_t bl = x3l_bin_len(bin_len);
@@ -297,19 +337,36 @@ x3_levels_accum_kernel(const uint8_t* __restrict__ x3, uint64_t len, const uint6
       if (bin < nlim) x3l_merge(mine + (bin - b0), a);
     };
     // a stretch's samples come in order, from sample 0 or from the first sample of block sb * j
-    const int r = x3l_bin_samples(
-        fr.pos + (j ? 1u + (uint64_t)sb * j * p.block_len : 0u), bl,
-        [&](auto put_at) { return x3w_stretch(x3, len, frame_off[f], p, idx, segd, sb, nseg, f, j, put_at); }, X3LevKeepAll{}, flush);
-    if (r < 0) atomicOr(&fst[f], X3W_FLAG);
+    if constexpr (Signal::kDiff) {
+      struct Watch {
+        Signal& sig;
+        int32_t* at;
+        __device__ __forceinline__ void seed(uint32_t v) const { sig.seed(v); }
+        __device__ __forceinline__ void end(uint32_t v) const { *at = (int32_t)(int16_t)(uint16_t)v; }
+      };
+      Signal sig;
+      const int r = x3l_bin_samples(
+          fr.pos + (j ? 1u + (uint64_t)sb * j * p.block_len : 0u), bl,
+          [&](auto put_at) { return x3w_stretch(x3, len, frame_off[f], p, idx, segd, sb, nseg, f, j, put_at, Watch{sig, tail + f}); },
+          X3LevKeepAll{}, flush, &sig);
+      if (r < 0) atomicOr(&fst[f], X3W_FLAG);
+    } else {
+      const int r = x3l_bin_samples(
+          fr.pos + (j ? 1u + (uint64_t)sb * j * p.block_len : 0u), bl,
+          [&](auto put_at) { return x3w_stretch(x3, len, frame_off[f], p, idx, segd, sb, nseg, f, j, put_at); }, X3LevKeepAll{}, flush);
+      if (r < 0) atomicOr(&fst[f], X3W_FLAG);
+    }
   }
 }
 
-// ---- fix-up: a wave per frame (lane 0 works); scratch: a block's samples per wave of the grid
+// ---- fix-up: a wave per frame (lane 0 works); scratch: a block's samples per wave of the grid.  X3LevDiff: tail[f] of
+// every frame it replays to status 0
+template <class Signal>
 __global__ void __launch_bounds__(256)
 x3_levels_fixup_kernel(const uint8_t* __restrict__ x3, const uint64_t* __restrict__ frame_off, uint64_t F, X3DevParams p,
                        uint64_t bin_len, const X3LevFrame* __restrict__ frames, int32_t* __restrict__ fst,
                        x3_level* __restrict__ levels, int32_t* __restrict__ status, int16_t* __restrict__ scratch,
-                       uint32_t scratch_per, X3LevSummary* __restrict__ sum) {
+                       uint32_t scratch_per, X3LevSummary* __restrict__ sum, typename Signal::Tail tail) {
   const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
   const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (threadIdx.x & 63u) return;
@@ -325,7 +382,13 @@ x3_levels_fixup_kernel(const uint8_t* __restrict__ x3, const uint64_t* __restric
         auto flush = [&](uint64_t bin, const X3LevAcc& a) {
           if (bin < fr.nlim) x3l_merge(levels + fr.obase + bin, a);
         };
-        (void)x3l_bin_samples(fr.pos, bl, [&](auto put_at) { return x3w_replay_frame(payload, p, blk, put_at); }, X3LevKeepAll{}, flush);
+        if constexpr (Signal::kDiff) {
+          Signal sig;
+          (void)x3l_bin_samples(fr.pos, bl, [&](auto put_at) { return x3w_replay_frame(payload, p, blk, put_at); }, X3LevKeepAll{}, flush, &sig);
+          tail[f] = sig.prev;
+        } else {
+          (void)x3l_bin_samples(fr.pos, bl, [&](auto put_at) { return x3w_replay_frame(payload, p, blk, put_at); }, X3LevKeepAll{}, flush);
+        }
       }
       fst[f] = fs | X3L_DONE;
       atomicAdd(&sum->replays, 1ull);
@@ -360,6 +423,41 @@ x3_levels_merge_kernel(const X3LevFrame* __restrict__ frames, const unsigned lon
         const x3_level r = rows[i];
         key = fr.obase + fr.b0 + (i - row[f]);   // (below obase + nlim <= the caller's rows: x3l_frame_rows)
         a.load(r);
+      }
+    }
+    x3l_merge_runs(levels, key, a, lane);
+  }
+}
+
+// ---- seam (X3LevDiff only): a lane per frame f >= 1, behind the fix-up, when every frame's word is final -- X3D_OK, or
+// X3L_DONE | status.  The difference at the position of frame f's sample 0 is the frame's first sample (the 16-bit literal
+// at the start of its payload) minus frame f - 1's last (tail[f - 1]); it counts when both frames have status 0 and belong
+// to the same stream or entry: the same records (obase) with nlim != 0 -- positions of two good neighbours are then back to
+// back, since a checked frame's samples are so[f + 1] - so[f].  Lanes are joined by record as in x3_levels_merge_kernel: with
+// one bin every seam of a stream is the same record's.
+__device__ __forceinline__ bool x3l_frame_good(int32_t w) { return w == X3D_OK || w == X3L_DONE; }
+
+__global__ void __launch_bounds__(256)
+x3_levels_seam_kernel(const uint8_t* __restrict__ x3, uint64_t len, const uint64_t* __restrict__ frame_off, uint64_t F,
+                      uint64_t bin_len, const X3LevFrame* __restrict__ frames, const int32_t* __restrict__ fst,
+                      const int32_t* __restrict__ tail, x3_level* __restrict__ levels) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t bl = x3l_bin_len(bin_len);
+  const uint64_t lanes = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t f0 = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u); f0 < F; f0 += lanes) {   // (whole waves)
+    const uint64_t f = f0 + lane;
+    X3LevAcc a;
+    a.reset();
+    uint64_t key = ~0ull;
+    if (f >= 1u && f < F && x3l_frame_good(fst[f]) && x3l_frame_good(fst[f - 1u])) {
+      const X3LevFrame fr = frames[f];
+      const X3LevFrame fp = frames[f - 1u];
+      const uint64_t bin = fr.pos / bl;
+      if (fr.nlim && fp.nlim && fr.obase == fp.obase && bin < fr.nlim) {
+        // (a checked frame: its header and payload lie inside the stream)
+        const int32_t head = (int32_t)(int16_t)(uint16_t)(x3w_be32_at(x3, len, frame_off[f] + 20u) >> 16);
+        a.add_value(x3l_diff(head, tail[f - 1u]));
+        key = fr.obase + bin;   // (below obase + nlim <= the caller's rows: x3l_frame_rows)
       }
     }
     x3l_merge_runs(levels, key, a, lane);

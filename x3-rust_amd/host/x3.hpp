@@ -771,13 +771,18 @@ inline X3Error decode_ranges(Context& ctx, const EncodedStream& s, const Paramet
 // Levels (x3_levels_dev): min, max, count, sum and sum of squares of the samples per bin of bin_len positions (0: one bin),
 // n_bins records in d_levels, every one written; d_frame_status (n_frames int32, may be nullptr): a frame with a status
 // other than 0 adds nothing.  No sample buffer.  Waits for the call: res = frames with status != 0, the first, its status.
+// signal (x3_signal_levels_dev): the samples, or their first difference clamped to 16 bits -- x[i] - x[i-1] at the position
+// of sample i, across the seam of two frames that both have status 0; the first sample of a stream or entry adds nothing.
+enum class LevelSignal : int { Samples = X3_LEVEL_SIGNAL_SAMPLES, Diff = X3_LEVEL_SIGNAL_DIFF };
+
 inline X3Error levels(Context& ctx, const EncodedStream& s, const Parameters& params, const Buffer& d_sample_offsets,
-                      uint64_t bin_len, x3_level* d_levels, uint64_t n_bins, int32_t* d_frame_status, WindowsResult* res) {
+                      uint64_t bin_len, x3_level* d_levels, uint64_t n_bins, int32_t* d_frame_status, WindowsResult* res,
+                      LevelSignal signal = LevelSignal::Samples) {
   if (!s.bytes.ok() || !s.frame_offsets.ok() || !d_sample_offsets.ok()) return X3Error::BadArg;
   const x3_params c = params.c_params();
-  int rc = x3_levels_dev(ctx.raw(), s.bytes.as<uint8_t>(), s.len, s.frame_offsets.as<uint64_t>(), d_sample_offsets.as<uint64_t>(),
-                         s.n_frames, &c, s.seg_blocks ? s.seg_index.as<uint64_t>() : nullptr, s.seg_blocks, bin_len, d_levels,
-                         n_bins, d_frame_status);
+  int rc = x3_signal_levels_dev(ctx.raw(), s.bytes.as<uint8_t>(), s.len, s.frame_offsets.as<uint64_t>(),
+                                d_sample_offsets.as<uint64_t>(), s.n_frames, &c, s.seg_blocks ? s.seg_index.as<uint64_t>() : nullptr,
+                                s.seg_blocks, bin_len, d_levels, n_bins, d_frame_status, static_cast<int>(signal));
   if (rc != X3_OK) return static_cast<X3Error>(rc);
   WindowsResult r;
   rc = x3_levels_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status);
@@ -952,14 +957,15 @@ class Corpus {
   }
   // Levels of every entry (x3_corpus_levels_dev): entry e's records are [row_first[e], row_first[e + 1]) of d_levels, positions
   // relative to the entry; levels_rows(bin_len) is that prefix, d_levels holds its last word of records.  Waits for the call.
+  // signal: as device::levels (x3_corpus_signal_levels_dev); no difference crosses from one entry into the next.
   std::vector<uint64_t> levels_rows(uint64_t bin_len) const {
     std::vector<uint64_t> v(raw_ ? n_entries() + 1 : 0);
     if (raw_) x3_corpus_levels_rows(raw_, bin_len, v.data());
     return v;
   }
   X3Error levels(Context& ctx, uint64_t bin_len, x3_level* d_levels, uint64_t n_rows, int32_t* d_frame_status,
-                 WindowsResult* res) const {
-    int rc = x3_corpus_levels_dev(ctx.raw(), raw_, bin_len, d_levels, n_rows, d_frame_status);
+                 WindowsResult* res, LevelSignal signal = LevelSignal::Samples) const {
+    int rc = x3_corpus_signal_levels_dev(ctx.raw(), raw_, bin_len, d_levels, n_rows, d_frame_status, static_cast<int>(signal));
     if (rc != X3_OK) return static_cast<X3Error>(rc);
     WindowsResult r;
     rc = x3_levels_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status);

@@ -224,6 +224,12 @@ pub mod ffi {
         pub fn x3_corpus_levels_rows(corpus: *const x3_corpus, bin_len: u64, row_first: *mut u64) -> c_int;
         pub fn x3_corpus_levels_dev(ctx: *mut x3_ctx, corpus: *const x3_corpus, bin_len: u64, d_levels: *mut x3_level, n_rows: u64,
                                     d_frame_status: *mut i32) -> c_int;
+        pub fn x3_signal_levels_dev(ctx: *mut x3_ctx, d_x3: *const u8, x3_len: u64, d_frame_offsets: *const u64,
+                                    d_sample_offsets: *const u64, n_frames: u64, p: *const x3_params, d_seg_index: *const u64,
+                                    seg_blocks: u32, bin_len: u64, d_levels: *mut x3_level, n_bins: u64, d_frame_status: *mut i32,
+                                    signal: c_int) -> c_int;
+        pub fn x3_corpus_signal_levels_dev(ctx: *mut x3_ctx, corpus: *const x3_corpus, bin_len: u64, d_levels: *mut x3_level,
+                                           n_rows: u64, d_frame_status: *mut i32, signal: c_int) -> c_int;
         pub fn x3_events_dev(ctx: *mut x3_ctx, d_levels: *const x3_level, n_bins: u64, bin_len: u64, d_total: *const u64,
                              rule: *const x3_event_rule, d_starts: *mut u64, d_lens: *mut u32, d_event_levels: *mut x3_level,
                              cap: u64, d_count: *mut u64) -> c_int;
@@ -1394,6 +1400,24 @@ pub mod device {
     #[allow(clippy::too_many_arguments)]
     pub fn levels<'g>(gpu: &'g Gpu, s: &EncodedStream<'g>, params: &x3::Parameters, sample_offsets: &Buffer<'g>, bin_len: u64,
                       d_levels: &mut Buffer<'g>, n_bins: usize, d_frame_status: Option<&mut Buffer<'g>>) -> error::Result<(u64, u64, i32)> {
+        signal_levels(gpu, s, params, sample_offsets, bin_len, d_levels, n_bins, d_frame_status, LevelSignal::Samples)
+    }
+
+    /// What `signal_levels` / `Corpus::signal_levels` bin (`X3_LEVEL_SIGNAL_*`): the samples, or their first difference clamped
+    /// to 16 bits -- `x[i] - x[i-1]` at the position of sample i, across the seam of two frames that both have status 0; the
+    /// first sample of a stream or entry adds nothing
+    #[derive(Clone, Copy, Debug, PartialEq, Eq)]
+    #[repr(i32)]
+    pub enum LevelSignal {
+        Samples = 0,
+        Diff = 1,
+    }
+
+    /// `levels` of a signal (`x3_signal_levels_dev`; not in the reference crate): arguments and result as `levels`
+    #[allow(clippy::too_many_arguments)]
+    pub fn signal_levels<'g>(gpu: &'g Gpu, s: &EncodedStream<'g>, params: &x3::Parameters, sample_offsets: &Buffer<'g>, bin_len: u64,
+                             d_levels: &mut Buffer<'g>, n_bins: usize, d_frame_status: Option<&mut Buffer<'g>>, signal: LevelSignal)
+                             -> error::Result<(u64, u64, i32)> {
         if d_levels.len() < core::mem::size_of::<Level>() * n_bins || d_frame_status.as_ref().map_or(false, |b| b.len() < 4 * s.n_frames) {
             return Err(X3Error::BadArg);
         }
@@ -1401,9 +1425,9 @@ pub mod device {
         let idx = match &s.seg_index { Some(i) => i.as_ptr::<u64>() as *const u64, None => core::ptr::null() };
         let st_ptr = match d_frame_status { Some(b) => b.as_ptr::<i32>(), None => core::ptr::null_mut() };
         error::check(unsafe {
-            ffi::x3_levels_dev(gpu.raw(), s.bytes.as_ptr::<u8>(), s.len as u64, s.frame_offsets.as_ptr::<u64>(),
-                               sample_offsets.as_ptr::<u64>(), s.n_frames as u64, &p, idx, s.seg_blocks, bin_len,
-                               d_levels.as_ptr::<Level>(), n_bins as u64, st_ptr)
+            ffi::x3_signal_levels_dev(gpu.raw(), s.bytes.as_ptr::<u8>(), s.len as u64, s.frame_offsets.as_ptr::<u64>(),
+                                      sample_offsets.as_ptr::<u64>(), s.n_frames as u64, &p, idx, s.seg_blocks, bin_len,
+                                      d_levels.as_ptr::<Level>(), n_bins as u64, st_ptr, signal as std::os::raw::c_int)
         })?;
         let (mut n_bad, mut first_bad, mut st) = (0u64, 0u64, 0);
         error::check(unsafe { ffi::x3_levels_result(gpu.raw(), &mut n_bad, &mut first_bad, &mut st) })?;
@@ -1682,13 +1706,21 @@ pub mod device {
         /// (frames with status != 0, the first of them, its status)
         pub fn levels(&self, bin_len: u64, d_levels: &mut Buffer<'g>, n_rows: usize, d_frame_status: Option<&mut Buffer<'g>>)
                       -> error::Result<(u64, u64, i32)> {
+            self.signal_levels(bin_len, d_levels, n_rows, d_frame_status, LevelSignal::Samples)
+        }
+
+        /// `levels` of a signal (`x3_corpus_signal_levels_dev`): arguments and result as `levels`; no difference crosses from
+        /// one entry into the next
+        pub fn signal_levels(&self, bin_len: u64, d_levels: &mut Buffer<'g>, n_rows: usize, d_frame_status: Option<&mut Buffer<'g>>,
+                             signal: LevelSignal) -> error::Result<(u64, u64, i32)> {
             if d_levels.len() < core::mem::size_of::<Level>() * n_rows
                 || d_frame_status.as_ref().map_or(false, |b| b.len() < 4 * self.info().1 as usize) {
                 return Err(X3Error::BadArg);
             }
             let st_ptr = match d_frame_status { Some(b) => b.as_ptr::<i32>(), None => core::ptr::null_mut() };
             error::check(unsafe {
-                ffi::x3_corpus_levels_dev(self.gpu.raw(), self.raw, bin_len, d_levels.as_ptr::<Level>(), n_rows as u64, st_ptr)
+                ffi::x3_corpus_signal_levels_dev(self.gpu.raw(), self.raw, bin_len, d_levels.as_ptr::<Level>(), n_rows as u64, st_ptr,
+                                                 signal as std::os::raw::c_int)
             })?;
             let (mut n_bad, mut first_bad, mut st) = (0u64, 0u64, 0);
             error::check(unsafe { ffi::x3_levels_result(self.gpu.raw(), &mut n_bad, &mut first_bad, &mut st) })?;

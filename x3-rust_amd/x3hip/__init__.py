@@ -62,6 +62,7 @@ SYMBOLS = [
     "x3_corpus_build", "x3_corpus_info", "x3_corpus_entries", "x3_corpus_entries_dev", "x3_corpus_seg_index", "x3_corpus_windows_dev",
     "x3_corpus_destroy",
     "x3_levels_dev", "x3_levels_result", "x3_corpus_levels_rows", "x3_corpus_levels_dev",
+    "x3_signal_levels_dev", "x3_corpus_signal_levels_dev",
     "x3_events_dev", "x3_corpus_events_dev", "x3_events_result",
     "x3_level_quantiles_dev", "x3_corpus_level_quantiles_dev", "x3_level_quantiles_result",
     "x3_level_thresholds_dev", "x3_corpus_level_thresholds_dev", "x3_events_adaptive_dev", "x3_corpus_events_adaptive_dev",
@@ -75,6 +76,17 @@ TUNE_CANDIDATES, TUNE_DEFAULT_INDEX, TUNE_DEFAULT_SPF = 2184, 1188, 10000   # in
 WINDOW_I16, WINDOW_F32 = 0, 1   # x3_decode_windows_dev output formats
 STREAMS_ARCHIVE_FRAMES = 1       # x3_decode_streams_dev: entries are the frame part of .x3a archives
 CORPUS_INDEX_WALK = 0x100        # x3_corpus_build: the segment index by x3_seg_index_build_dev (any parameters)
+LEVEL_SIGNAL_SAMPLES, LEVEL_SIGNAL_DIFF = 0, 1   # x3_signal_levels_dev: the samples, or their clamped first difference
+LEVEL_SIGNALS = {"samples": LEVEL_SIGNAL_SAMPLES, "diff": LEVEL_SIGNAL_DIFF}   # the mirrors' keyword `signal`
+
+
+def level_signal(signal):
+    """the keyword `signal` of the levels methods ("samples" | "diff", or a LEVEL_SIGNAL_* value) -> the C ABI's int"""
+    if signal in LEVEL_SIGNALS:
+        return LEVEL_SIGNALS[signal]
+    if signal in LEVEL_SIGNALS.values() and not isinstance(signal, bool):
+        return int(signal)
+    raise ValueError('signal: "samples" or "diff"')
 
 
 # x3_level: one bin of x3_levels_dev / x3_corpus_levels_dev (32 bytes)
@@ -282,6 +294,8 @@ def lib():
     L.x3_levels_result.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(i32)]
     L.x3_corpus_levels_rows.argtypes = [vp, u64, vp]
     L.x3_corpus_levels_dev.argtypes = [vp, vp, u64, vp, u64, vp]
+    L.x3_signal_levels_dev.argtypes = [vp, vp, u64, vp, vp, u64, PP, vp, u32, u64, vp, u64, vp, C.c_int]
+    L.x3_corpus_signal_levels_dev.argtypes = [vp, vp, u64, vp, u64, vp, C.c_int]
     L.x3_events_dev.argtypes = [vp, vp, u64, u64, vp, C.POINTER(EventRule), vp, vp, vp, u64, vp]
     L.x3_corpus_events_dev.argtypes = [vp, vp, vp, u64, u64, C.POINTER(EventRule), vp, vp, vp, vp, u64, vp]
     L.x3_events_result.argtypes = [vp, C.POINTER(u64)]
@@ -1015,6 +1029,17 @@ class Context:
         return lib().x3_levels_dev(self._h, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, C.byref(params),
                                    d_seg_index, seg_blocks, bin_len, d_levels, n_bins, d_frame_status)
 
+    def signal_levels_dev(self, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, params, bin_len, d_levels, n_bins,
+                          d_frame_status=None, d_seg_index=None, seg_blocks=0, signal=LEVEL_SIGNAL_SAMPLES):
+        """x3_signal_levels_dev: levels_dev of the samples (LEVEL_SIGNAL_SAMPLES) or of their first difference, clamped to 16
+        bits (LEVEL_SIGNAL_DIFF); asynchronous, levels_result waits"""
+        return lib().x3_signal_levels_dev(self._h, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, C.byref(params),
+                                          d_seg_index, seg_blocks, bin_len, d_levels, n_bins, d_frame_status, signal)
+
+    def corpus_signal_levels_dev(self, corpus, bin_len, d_levels, n_rows, d_frame_status=None, signal=LEVEL_SIGNAL_SAMPLES):
+        """x3_corpus_signal_levels_dev: corpus_levels_dev with a signal; asynchronous, levels_result waits"""
+        return lib().x3_corpus_signal_levels_dev(self._h, corpus._h, bin_len, d_levels, n_rows, d_frame_status, signal)
+
     def levels_result(self):
         """-> (rc, n_bad_frames, first_bad, first_bad_status) of the last levels_dev / corpus_levels_dev"""
         nb, fb, st = C.c_uint64(0), C.c_uint64(0), C.c_int32(0)
@@ -1496,17 +1521,25 @@ class WindowSource:
         return _range_levels_torch(self.ctx, lambda e, *a: self.range_levels_into(*a), "x3_range_levels_dev", starts, lens,
                                    bin_len, padded_to, capacity)
 
-    def levels(self, bin_len, n_bins=None):
+    def levels_into(self, bin_len, d_levels, n_bins, d_frame_status=None, signal=LEVEL_SIGNAL_SAMPLES):
+        """enqueue x3_signal_levels_dev over this source (device pointers; signal: a LEVEL_SIGNAL_* value); -> rc;
+        Context.levels_result waits"""
+        return self.ctx.signal_levels_dev(self.d_x3, self.x3_len, self.d_frame_offsets, self.d_sample_offsets, self.n_frames,
+                                          self.params, bin_len, d_levels, n_bins, d_frame_status, self.d_seg_index,
+                                          self.seg_blocks, signal)
+
+    def levels(self, bin_len, n_bins=None, *, signal="samples"):
         """-> (records np.ndarray of LEVEL_DTYPE [n_bins], frame statuses np.int32 [n_frames]): min, max, n, sum and sum of
-        squares per bin of bin_len positions (0: one bin); n_bins: as many as cover the stream unless given"""
+        squares per bin of bin_len positions (0: one bin); n_bins: as many as cover the stream unless given.
+        signal: "samples", or "diff" -- the samples' first difference, clamped to 16 bits (x3_signal_levels_dev)"""
+        sig = level_signal(signal)
         if n_bins is None:
             n_bins = max(1, -(-self.total // bin_len)) if bin_len else 1
         d_lv, d_st = self.ctx.alloc(LEVEL_DTYPE.itemsize * n_bins), self.ctx.alloc(4 * self.n_frames)
         try:
-            rc = self.ctx.levels_dev(self.d_x3, self.x3_len, self.d_frame_offsets, self.d_sample_offsets, self.n_frames,
-                                     self.params, bin_len, d_lv, n_bins, d_st, self.d_seg_index, self.seg_blocks)
+            rc = self.levels_into(bin_len, d_lv, n_bins, d_st, sig)
             if rc:
-                raise X3Error(rc, "x3_levels_dev: " + self.ctx.last_error())
+                raise X3Error(rc, "x3_signal_levels_dev: " + self.ctx.last_error())
             rc = self.ctx.levels_result()[0]
             if rc:
                 raise X3Error(rc, "x3_levels_result: " + self.ctx.last_error())
@@ -1522,18 +1555,18 @@ class WindowSource:
         return self.ctx.events_dev(d_levels, n_bins, bin_len, self.d_sample_offsets + 8 * self.n_frames, rule, d_starts, d_lens,
                                    d_event_levels, cap, d_count)
 
-    def events(self, bin_len, rule, capacity):
-        """Levels of bins of bin_len positions, then the runs of hot bins under `rule` (an EventRule) as ranges, all on the
+    def events(self, bin_len, rule, capacity, *, signal="samples"):
+        """Levels (of `signal`, as in levels()) of bins of bin_len positions, then the runs of hot bins under `rule` (an EventRule) as ranges, all on the
         device -> (starts int64 [capacity], lens int32 [capacity], count 0-d int64, event_levels uint8 [capacity, 32]),
         torch tensors on the device.  Slots behind the events are zero-length ranges: ranges(starts, lens, padded_to=...)
         takes the tensors as they are.  count may exceed capacity: repeat with more."""
         if not 0 < bin_len <= 0xFFFFFFFF:
             raise ValueError("bin_len: 1 .. 2^32 - 1")
+        sig = level_signal(signal)
         n_bins = max(1, -(-self.total // bin_len))
         return _events_torch(
             self.ctx, n_bins, capacity, False,
-            lambda d_lv: self.ctx.levels_dev(self.d_x3, self.x3_len, self.d_frame_offsets, self.d_sample_offsets, self.n_frames,
-                                             self.params, bin_len, d_lv, n_bins, None, self.d_seg_index, self.seg_blocks),
+            lambda d_lv: self.levels_into(bin_len, d_lv, n_bins, None, sig),
             lambda d_lv, d_e, d_s, d_l, d_el, d_c: self.events_into(d_lv, n_bins, bin_len, rule, d_s, d_l, d_el, capacity, d_c))
 
     def level_quantiles_into(self, d_levels, n_bins, bin_len, key, q_ppm, d_values, d_counted):
@@ -1552,28 +1585,28 @@ class WindowSource:
         return self.ctx.events_adaptive_dev(d_levels, n_bins, bin_len, self.d_sample_offsets + 8 * self.n_frames, rule, d_thr,
                                             d_starts, d_lens, d_event_levels, cap, d_count)
 
-    def level_quantiles(self, bin_len, key, q_ppm):
-        """Levels of bins of bin_len positions, then the quantiles q_ppm (millionths) of their keys, on the device ->
+    def level_quantiles(self, bin_len, key, q_ppm, *, signal="samples"):
+        """Levels (of `signal`, as in levels()) of bins of bin_len positions, then the quantiles q_ppm (millionths) of their keys, on the device ->
         (values int32 [1, len(q_ppm)], counted int32 [1]) torch tensors"""
         if not 0 < bin_len <= 0xFFFFFFFF:
             raise ValueError("bin_len: 1 .. 2^32 - 1")
+        sig = level_signal(signal)
         n_bins = max(1, -(-self.total // bin_len))
         return _level_quantiles_torch(
             self.ctx, n_bins, 1, len(q_ppm),
-            lambda d_lv: self.ctx.levels_dev(self.d_x3, self.x3_len, self.d_frame_offsets, self.d_sample_offsets, self.n_frames,
-                                             self.params, bin_len, d_lv, n_bins, None, self.d_seg_index, self.seg_blocks),
+            lambda d_lv: self.levels_into(bin_len, d_lv, n_bins, None, sig),
             lambda d_lv, d_v, d_k: self.level_quantiles_into(d_lv, n_bins, bin_len, key, q_ppm, d_v, d_k))
 
-    def adaptive_events(self, bin_len, threshold_rule, rule, capacity):
+    def adaptive_events(self, bin_len, threshold_rule, rule, capacity, *, signal="samples"):
         """events() with the rule's two values (both 0 in `rule`) chosen on the device by `threshold_rule` (a ThresholdRule)
         -> (starts, lens, count, event_levels, thresholds uint8 [1, 16])"""
         if not 0 < bin_len <= 0xFFFFFFFF:
             raise ValueError("bin_len: 1 .. 2^32 - 1")
+        sig = level_signal(signal)
         n_bins = max(1, -(-self.total // bin_len))
         return _adaptive_events_torch(
             self.ctx, n_bins, 1, capacity, False,
-            lambda d_lv: self.ctx.levels_dev(self.d_x3, self.x3_len, self.d_frame_offsets, self.d_sample_offsets, self.n_frames,
-                                             self.params, bin_len, d_lv, n_bins, None, self.d_seg_index, self.seg_blocks),
+            lambda d_lv: self.levels_into(bin_len, d_lv, n_bins, None, sig),
             lambda d_lv, d_t: self.level_thresholds_into(d_lv, n_bins, bin_len, threshold_rule, d_t),
             lambda d_lv, d_t, d_e, d_s, d_l, d_el, d_c: self.adaptive_events_into(d_lv, n_bins, bin_len, rule, d_t, d_s, d_l, d_el,
                                                                                   capacity, d_c))
@@ -1832,16 +1865,25 @@ class Corpus:
             raise X3Error(rc, "x3_corpus_levels_rows")
         return rf
 
-    def levels(self, bin_len):
+    def levels_into(self, bin_len, d_levels, n_rows, d_frame_status=None, signal=LEVEL_SIGNAL_SAMPLES):
+        """enqueue x3_corpus_signal_levels_dev (device pointers; signal: a LEVEL_SIGNAL_* value); -> rc;
+        Context.levels_result waits"""
+        if self._h is None:
+            raise ValueError("the corpus is closed")
+        return self.ctx.corpus_signal_levels_dev(self, bin_len, d_levels, n_rows, d_frame_status, signal)
+
+    def levels(self, bin_len, *, signal="samples"):
         """-> (records np.ndarray of LEVEL_DTYPE [rows], row_first np.uint64 [n_entries + 1], frame statuses np.int32
-        [n_frames]): the levels of every entry, positions relative to the entry, bins of bin_len positions (0: one bin)"""
+        [n_frames]): the levels of every entry, positions relative to the entry, bins of bin_len positions (0: one bin).
+        signal: "samples", or "diff" -- the samples' first difference, clamped to 16 bits (x3_signal_levels_dev); no difference crosses from one entry into the next"""
+        sig = level_signal(signal)
         rf = self.levels_rows(bin_len)
         n_rows = int(rf[-1])
         d_lv, d_st = self.ctx.alloc(LEVEL_DTYPE.itemsize * n_rows), self.ctx.alloc(4 * max(self.n_frames, 1))
         try:
-            rc = self.ctx.corpus_levels_dev(self, bin_len, d_lv, n_rows, d_st)
+            rc = self.levels_into(bin_len, d_lv, n_rows, d_st, sig)
             if rc:
-                raise X3Error(rc, "x3_corpus_levels_dev: " + self.ctx.last_error())
+                raise X3Error(rc, "x3_corpus_signal_levels_dev: " + self.ctx.last_error())
             rc = self.ctx.levels_result()[0]
             if rc:
                 raise X3Error(rc, "x3_levels_result: " + self.ctx.last_error())
@@ -1859,16 +1901,17 @@ class Corpus:
         return self.ctx.corpus_events_dev(self, d_levels, n_rows, bin_len, rule, d_entries, d_starts, d_lens, d_event_levels,
                                           cap, d_count)
 
-    def events(self, bin_len, rule, capacity):
-        """Levels of every entry, then the runs of hot bins under `rule` as ranges, all on the device -> (entries int32,
+    def events(self, bin_len, rule, capacity, *, signal="samples"):
+        """Levels (of `signal`, as in levels()) of every entry, then the runs of hot bins under `rule` as ranges, all on the device -> (entries int32,
         starts int64, lens int32 [capacity each], count 0-d int64, event_levels uint8 [capacity, 32]), as
         WindowSource.events; ranges(entries, starts, lens, padded_to=...) takes the tensors as they are."""
         if not 0 < bin_len <= 0xFFFFFFFF:
             raise ValueError("bin_len: 1 .. 2^32 - 1")
+        sig = level_signal(signal)
         n_rows = int(self.levels_rows(bin_len)[-1])
         return _events_torch(
             self.ctx, n_rows, capacity, True,
-            lambda d_lv: self.ctx.corpus_levels_dev(self, bin_len, d_lv, n_rows, None),
+            lambda d_lv: self.levels_into(bin_len, d_lv, n_rows, None, sig),
             lambda d_lv, d_e, d_s, d_l, d_el, d_c: self.events_into(d_lv, n_rows, bin_len, rule, d_e, d_s, d_l, d_el, capacity, d_c))
 
     def level_quantiles_into(self, d_levels, n_rows, bin_len, key, q_ppm, d_values, d_counted):
@@ -1892,26 +1935,28 @@ class Corpus:
         return self.ctx.corpus_events_adaptive_dev(self, d_levels, n_rows, bin_len, rule, d_thr, d_entries, d_starts, d_lens,
                                                    d_event_levels, cap, d_count)
 
-    def level_quantiles(self, bin_len, key, q_ppm):
-        """Levels of every entry, then per entry the quantiles q_ppm (millionths) of their keys, on the device ->
+    def level_quantiles(self, bin_len, key, q_ppm, *, signal="samples"):
+        """Levels (of `signal`, as in levels()) of every entry, then per entry the quantiles q_ppm (millionths) of their keys, on the device ->
         (values int32 [n_entries, len(q_ppm)], counted int32 [n_entries]) torch tensors"""
         if not 0 < bin_len <= 0xFFFFFFFF:
             raise ValueError("bin_len: 1 .. 2^32 - 1")
+        sig = level_signal(signal)
         n_rows = int(self.levels_rows(bin_len)[-1])
         return _level_quantiles_torch(
             self.ctx, n_rows, self.n_entries, len(q_ppm),
-            lambda d_lv: self.ctx.corpus_levels_dev(self, bin_len, d_lv, n_rows, None),
+            lambda d_lv: self.levels_into(bin_len, d_lv, n_rows, None, sig),
             lambda d_lv, d_v, d_k: self.level_quantiles_into(d_lv, n_rows, bin_len, key, q_ppm, d_v, d_k))
 
-    def adaptive_events(self, bin_len, threshold_rule, rule, capacity):
+    def adaptive_events(self, bin_len, threshold_rule, rule, capacity, *, signal="samples"):
         """events() with a threshold per entry chosen on the device by `threshold_rule` -> (entries, starts, lens, count,
         event_levels, thresholds uint8 [n_entries, 16])"""
         if not 0 < bin_len <= 0xFFFFFFFF:
             raise ValueError("bin_len: 1 .. 2^32 - 1")
+        sig = level_signal(signal)
         n_rows = int(self.levels_rows(bin_len)[-1])
         return _adaptive_events_torch(
             self.ctx, n_rows, self.n_entries, capacity, True,
-            lambda d_lv: self.ctx.corpus_levels_dev(self, bin_len, d_lv, n_rows, None),
+            lambda d_lv: self.levels_into(bin_len, d_lv, n_rows, None, sig),
             lambda d_lv, d_t: self.level_thresholds_into(d_lv, n_rows, bin_len, threshold_rule, d_t),
             lambda d_lv, d_t, d_e, d_s, d_l, d_el, d_c: self.adaptive_events_into(d_lv, n_rows, bin_len, rule, d_t, d_e, d_s, d_l,
                                                                                   d_el, capacity, d_c))
