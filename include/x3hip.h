@@ -990,6 +990,43 @@ int x3_corpus_range_levels_dev(x3_ctx* ctx, const x3_corpus* corpus, const uint3
 /* Waits for the last x3_range_levels_dev / x3_corpus_range_levels_dev: ranges with status != 0, the first of them (n_ranges
  * if none), its status, and the sum of all R(w) (what a packed d_levels must hold for no range to be refused). */
 int x3_range_levels_result(x3_ctx* ctx, uint64_t* n_bad, uint64_t* first_bad, int* first_bad_status, uint64_t* total_rows);
+/* ---- SIGNAL RANGE LEVELS: the range-levels calls with the signal of x3_signal_levels_dev, so that events found on the first
+ * difference can be looked at again on the signal they were found on.  The arguments of
+ * x3_range_levels_dev / x3_corpus_range_levels_dev plus a last `signal`; any value but the two below is X3_ERR_BAD_ARG with
+ * nothing enqueued, tested before every other argument.
+ *   X3_LEVEL_SIGNAL_SAMPLES: the bytes of x3_range_levels_dev / x3_corpus_range_levels_dev, which are this form.
+ *   X3_LEVEL_SIGNAL_DIFF: ONE RULE -- the call cuts the stream's (or entry's) difference signal; it does not difference the
+ * cut.  With y the signal x3_signal_levels_dev defines on the stream or entry that holds the range (y[pos] = clamp(x[pos] -
+ * x[pos - 1], -32768, 32767); counted inside a frame iff the frame has status 0, at a frame's sample 0 iff the frame and the
+ * one in front of it both have status 0 and belong to the same entry, never at the first position of a stream or entry),
+ * range w has the records of the SAMPLES form with y[start + r] in place of x[start + r], r in [0, len).  Rows R(w), bins
+ * from the range's start, packed and padded layouts, row offsets, rows_cap rules, refusals and identities are unchanged.
+ *   - The difference at the range's own first position IS counted when y counts it: its x[pos - 1] lies outside the range,
+ *     and possibly in the frame in front of the first covering frame (the LEAD FRAME).
+ *   - The range (0, total) at bin length b equals x3_signal_levels_dev(..., X3_LEVEL_SIGNAL_DIFF) at b, record for record,
+ *     damaged frames included.
+ *   - A range whose start and length are multiples of b equals the slice of those records, the last record cut to the
+ *     range's length.
+ *   - d_status[w] is exactly the SAMPLES form's: the status of the first covering frame in frame order that is not 0.  The
+ *     lead frame never gives the range its status; if it fails, the one seam it shares with the range is not counted ("a
+ *     failed frame takes both of its seams with it").
+ *   - n counts differences: a clean range (0, N) over a clean entry of N samples has n == N - 1 in all; a clean range that
+ *     does not start at the entry's first position has n == len.
+ *   - The records are int16-signal records (the identity for empty bins, peak <= 32768): they go into the events,
+ *     quantiles and thresholds calls unchanged.
+ *   x3_range_levels_result, the pending slot, the workspace and the options "last_range_levels_replays" /
+ * "last_range_levels_overflow" are shared with the SAMPLES form; a lead-frame pair that the fix-up decodes counts as a
+ * replay.  With DIFF the workspace holds one more pair per range (the second arm of P is 4 * (n_frames + n_ranges) +
+ * n_ranges), a word per frame (its last sample) and a word per range. */
+int x3_signal_range_levels_dev(x3_ctx* ctx, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
+                               const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
+                               const uint64_t* d_seg_index, uint32_t seg_blocks, const uint64_t* d_starts,
+                               const uint32_t* d_lens, uint64_t n_ranges, uint64_t bin_len, uint64_t row_stride,
+                               x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status, int signal);
+int x3_corpus_signal_range_levels_dev(x3_ctx* ctx, const x3_corpus* corpus, const uint32_t* d_entries, const uint64_t* d_starts,
+                                      const uint32_t* d_lens, uint64_t n_ranges, uint64_t bin_len, uint64_t row_stride,
+                                      x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status,
+                                      int signal);
 void x3_corpus_destroy(x3_corpus* corpus);
 
 /* ------------------------------------------------------------------ multi-GPU (no reference analogue) */

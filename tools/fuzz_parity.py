@@ -17,7 +17,10 @@ Families: (e) the single-pass encoders on block_len 20 with mixed content, many 
           damage, with and without an index, GPU == tests/range_levels_ref.py (not in the default family set); (h) levels of the
           first difference (x3_signal_levels_dev / x3_corpus_signal_levels_dev, X3_LEVEL_SIGNAL_DIFF): random content x
           geometry x bin lengths x damage, with, without and with a damaged index, a stream and the same stream cut into
-          corpus entries, GPU == tests/diff_levels_ref.py on the oracle's frame verdicts (not in the default family set)."""
+          corpus entries, GPU == tests/diff_levels_ref.py on the oracle's frame verdicts (not in the default family set);
+          (l) family (r) on the first difference (x3_signal_range_levels_dev, X3_LEVEL_SIGNAL_DIFF), with starts drawn to
+          frame and stretch boundaries as well (lead frames, seeds from the index), GPU == tests/signal_range_levels_ref.py
+          (not in the default family set)."""
 import argparse, ctypes as C, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "x3-rust_amd"))
@@ -795,8 +798,8 @@ fams["c"] = fam_c
 fams["x"] = fam_x
 
 
-def fam_r(rng, tag):
-    """range levels: the records, row offsets and statuses of random ranges of a random stream -- any geometry, damaged
+def fam_r(rng, tag, diff=False):
+    """range levels (diff: of the first difference, against signal_range_levels_ref -- family (l)): the records, row offsets and statuses of random ranges of a random stream -- any geometry, damaged
     frames, a damaged or walk-built index, packed (exact, cut or roomy capacity) and padded -- against range_levels_ref on
     the oracle's frame verdicts; the output arrays are filled with 0x5A and what no call may write must keep it"""
     import range_levels_ref as RL
@@ -857,6 +860,11 @@ def fam_r(rng, tag):
     starts = [int(rng.integers(0, n - v + 1)) for v in lens]
     if kind == 3:
         starts = [min(w * hop, n - L0) for w in range(nr)]
+    if diff:           # starts at a frame's or a stretch's first sample, and one behind it
+        for w in range(nr):
+            if rng.random() < 0.4:
+                at = int(rng.integers(0, len(offs))) * spf + int(rng.choice([0, 1, 1 + 4 * p.block_len, 1 + 32 * p.block_len]))
+                starts[w] = min(at, n - lens[w])
     wild = [n, n + 1, 2 ** 63, 2 ** 64 - 1, int(rng.integers(n + 1, 2 ** 62))]
     for _ in range(int(rng.integers(0, 3))):
         w = int(rng.integers(0, nr))
@@ -878,7 +886,11 @@ def fam_r(rng, tag):
     else:
         stride = int(rng.choice([1, max(rows), max(1, max(rows) // 2), max(rows) + 3]))
         cap = nr * stride + int(rng.integers(0, 3))
-    want = RL.range_levels(verdicts, so_a, starts, lens, bin_len, stride, cap)
+    if diff:
+        import signal_range_levels_ref as SRL
+        want = SRL.range_levels(verdicts, so_a, starts, lens, bin_len, stride, cap, SRL.DIFF)
+    else:
+        want = RL.range_levels(verdicts, so_a, starts, lens, bin_len, stride, cap)
     d = []
     try:
         d_off = ctx.alloc(8 * (len(offs) + 1)); d.append(d_off)
@@ -903,7 +915,8 @@ def fam_r(rng, tag):
             ctx.upload(q, np.full(v + guard, 0x5A, dtype=np.uint8))
         ctx.upload(bufs[3], np.array(starts, dtype=np.uint64))
         ctx.upload(bufs[4], np.array(lens, dtype=np.uint32))
-        rc = src.range_levels_into(bufs[3], bufs[4], nr, bin_len, stride, bufs[0], cap, bufs[1], bufs[2])
+        rc = src.range_levels_into(bufs[3], bufs[4], nr, bin_len, stride, bufs[0], cap, bufs[1], bufs[2],
+                                   signal=x3hip.LEVEL_SIGNAL_DIFF if diff else x3hip.LEVEL_SIGNAL_SAMPLES)
         assert rc == 0, (tag, "rc", rc, ctx.last_error())
         res = ctx.range_levels_result()
         raw = [ctx.download(q, v + guard) for q, v in zip(bufs[:3], sizes)]
@@ -922,6 +935,7 @@ def fam_r(rng, tag):
 
 
 fams["r"] = fam_r
+fams["l"] = lambda rng, tag: fam_r(rng, tag, diff=True)
 
 
 def fam_h(rng, tag):

@@ -13,9 +13,15 @@ Cases:
   2  one 10 s range at 2 000 bins
   3  the events of tools/events_bench.py (levels at 10 ms, its rule, --cap slots with fillers) at bin_len 0: one record an
      event; route a masks the tails of its padded rows, route b is the levels call plus the events call's own merged records
+--signal diff: the same cases on the first difference (x3_signal_range_levels_dev / x3_corpus_signal_range_levels_dev with
+X3_LEVEL_SIGNAL_DIFF).  Route a decodes every range with the sample in front of it (start - 1, len + 1; a range at its
+entry's position 0 has none and its first position counts nothing), takes torch's difference, clamps it to 16 bits and
+reduces; the index plan that drops each range's leading sample is made once, outside the timed part.  Route b is the DIFF
+levels call, and case 3's events are found on the DIFF levels.
 Every route's records are compared with == at the end of every case and the tool fails otherwise.  Kernel times: run it under
 `rocprofv3 --kernel-trace --stats -- python3 tools/range_levels_bench.py ...`.  Prints one JSON line.
-    python3 tools/range_levels_bench.py [--samples N] [--reps 10] [--warmup 2] [--cap 4096] [--cases config3,corpus] [--out file.json]"""
+    python3 tools/range_levels_bench.py [--signal samples|diff] [--samples N] [--reps 10] [--warmup 2] [--cap 4096]
+                                        [--cases config3,corpus] [--out file.json]"""
 import argparse, ctypes as C, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "x3-rust_amd"))
@@ -62,7 +68,18 @@ def bins_case(src, a, results, info, case, ent, starts, lens, bin_len):
     lv = torch.empty((total_rows, 32), dtype=torch.uint8, device="cuda")
     off, off2 = (torch.empty(n + 1, dtype=torch.int64, device="cuda") for _ in range(2))
     st, st2 = (torch.empty(n, dtype=torch.int32, device="cuda") for _ in range(2))
-    buf = torch.empty(total, dtype=torch.int16, device="cuda")
+    diff = a.signal == "diff"
+    pre = [1 if diff and s > 0 else 0 for s in starts]          # route a, diff: the sample in front of the range comes with it
+    total_a = total + sum(pre)
+    buf = torch.empty(total_a, dtype=torch.int16, device="cuda")
+    d_st_a = torch.tensor([s - k for s, k in zip(starts, pre)], dtype=torch.int64, device="cuda")
+    d_ln_a = torch.tensor([v + k for v, k in zip(lens, pre)], dtype=torch.int32, device="cuda")
+    if diff:   # where each range's own positions lie in route a's packed buffer; a range at position 0 has no first difference
+        first = np.concatenate([[0], np.cumsum([v + k for v, k in zip(lens, pre)])[:-1]]) + np.array(pre)
+        keep = torch.from_numpy(np.concatenate([f + np.arange(v) for f, v in zip(first, lens)]).astype(np.int64)).cuda()
+        ok = np.ones(total, dtype=bool)
+        ok[np.concatenate([[0], np.cumsum(lens)[:-1]])[np.array(pre) == 0]] = False
+        valid = torch.from_numpy(ok).cuda().view(total_rows, bin_len)
     rf = src.levels_rows(bin_len)
     full_rows = int(rf[-1])
     full = torch.empty((full_rows, 32), dtype=torch.uint8, device="cuda") if 64 * full_rows < a.levels_bytes else None
@@ -75,14 +92,21 @@ def bins_case(src, a, results, info, case, ent, starts, lens, bin_len):
         r = ctx.range_levels_result()
         t1 = now()
         assert r == (0, 0, n, 0, total_rows), r
-        assert src.ranges(d_ent.data_ptr(), d_st.data_ptr(), d_ln.data_ptr(), n, 0, buf.data_ptr(), total, off2.data_ptr(),
+        assert src.ranges(d_ent.data_ptr(), d_st_a.data_ptr(), d_ln_a.data_ptr(), n, 0, buf.data_ptr(), total_a, off2.data_ptr(),
                           st2.data_ptr()) == 0, ctx.last_error()
         r = ctx.decode_ranges_result()
         t2 = now()
         assert r[:2] == (0, 0), r
-        x = buf.view(total_rows, bin_len)
-        w = x.to(torch.int32)
-        red = (x.min(1).values, x.max(1).values, w.sum(1, dtype=torch.int64), (w * w).sum(1, dtype=torch.int64))
+        if diff:
+            w = buf.to(torch.int32)
+            y = torch.clamp(w[1:] - w[:-1], -32768, 32767)[(keep - 1).clamp(min=0)].view(total_rows, bin_len)
+            red = (torch.where(valid, y, 32767).min(1).values, torch.where(valid, y, -32768).max(1).values,
+                   torch.where(valid, y, 0).sum(1, dtype=torch.int64), torch.where(valid, y * y, 0).sum(1, dtype=torch.int64),
+                   valid.sum(1))
+        else:
+            x = buf.view(total_rows, bin_len)
+            w = x.to(torch.int32)
+            red = (x.min(1).values, x.max(1).values, w.sum(1, dtype=torch.int64), (w * w).sum(1, dtype=torch.int64))
         torch.cuda.synchronize()
         t3 = now()
         timed(results, name + "_range_levels", rep, a.warmup, t1 - t0)
@@ -95,7 +119,8 @@ def bins_case(src, a, results, info, case, ent, starts, lens, bin_len):
             assert ctx.levels_result()[0] == 0
             timed(results, name + "_route_b", rep, a.warmup, now() - t4)
     got = records(lv)
-    want_a = as_records(*(t.cpu().numpy() for t in red), np.full(total_rows, bin_len, dtype=np.uint32))
+    counts = red[4].cpu().numpy().astype(np.uint32) if diff else np.full(total_rows, bin_len, dtype=np.uint32)
+    want_a = as_records(*(t.cpu().numpy() for t in red[:4]), counts)
     same = np.array_equal(got, want_a) and not st.cpu().numpy().any()
     if full is not None:
         frec = records(full)
@@ -103,7 +128,7 @@ def bins_case(src, a, results, info, case, ent, starts, lens, bin_len):
         same = same and np.array_equal(got, frec[pick])
     if not same:
         raise SystemExit("%s: the routes' records differ" % name)
-    info[name] = {"ranges": n, "bin_len": bin_len, "rows": total_rows, "samples": total, "levels_rows": full_rows,
+    info[name] = {"signal": a.signal, "ranges": n, "bin_len": bin_len, "rows": total_rows, "samples": total, "levels_rows": full_rows,
                   "route_b": full is not None, "equal": bool(same),
                   "replays": ctx.get_option("last_range_levels_replays"), "overflow": ctx.get_option("last_range_levels_overflow")}
 
@@ -121,7 +146,9 @@ def events_case(src, a, results, info, bin_len):
     ev_lv, ev_lv2, lv = (torch.empty((cap, 32), dtype=torch.uint8, device="cuda") for _ in range(3))
     status, status2 = (torch.empty(cap, dtype=torch.int32, device="cuda") for _ in range(2))
     off = torch.empty(cap + 1, dtype=torch.int64, device="cuda")
-    buf = torch.empty((cap, stride), dtype=torch.int16, device="cuda")
+    diff = a.signal == "diff"
+    width = stride + (1 if diff else 0)          # route a, diff: a column for the sample in front of the range
+    buf = torch.empty((cap, width), dtype=torch.int16, device="cuda")
     torch.cuda.synchronize()
     assert src.levels(bin_len, full.data_ptr(), n_rows) == 0 and ctx.levels_result()[0] == 0
     rec = records(full)
@@ -131,7 +158,8 @@ def events_case(src, a, results, info, bin_len):
     assert src.events(full.data_ptr(), n_rows, bin_len, rule, ent.data_ptr(), st.data_ptr(), ln.data_ptr(), ev_lv.data_ptr(), cap,
                       cnt.data_ptr()) == 0
     rc, found = ctx.events_result()
-    assert rc == 0 and 0 < found <= cap, (rc, found)
+    assert rc == 0 and found > 0 and (found <= cap or a.signal == "diff"), (rc, found)   # (diff: peaks saturate, ties at the
+    # threshold can make more events than slots; the slots then hold the first `cap` of them and no filler)
     col = torch.arange(stride, device="cuda")[None, :]
     red = None
     for rep in range(a.warmup + a.reps):
@@ -141,15 +169,29 @@ def events_case(src, a, results, info, bin_len):
         r = ctx.range_levels_result()
         t1 = now()
         assert r == (0, 0, cap, 0, cap), r
-        assert src.ranges(ent.data_ptr(), st.data_ptr(), ln.data_ptr(), cap, stride, buf.data_ptr(), cap * stride, None,
+        if diff:   # (start - 1, len + 1) where there is a sample in front; position r of the range is column r + pre
+            pre = ((st > 0) & (ln > 0)).to(torch.int64)
+            st_a, ln_a = st - pre, ln + pre.to(torch.int32)
+            torch.cuda.synchronize()
+        else:
+            st_a, ln_a = st, ln
+        assert src.ranges(ent.data_ptr(), st_a.data_ptr(), ln_a.data_ptr(), cap, width, buf.data_ptr(), cap * width, None,
                           status2.data_ptr()) == 0, ctx.last_error()
         r = ctx.decode_ranges_result()
         t2 = now()
         assert r[:2] == (0, 0), r
         mask = col < ln[:, None]
         w = buf.to(torch.int32)
-        red = (torch.where(mask, w, 32767).min(1).values, torch.where(mask, w, -32768).max(1).values,
-               w.sum(1, dtype=torch.int64), (w * w).sum(1, dtype=torch.int64))
+        if diff:
+            at = col + pre[:, None]
+            y = torch.clamp(w.gather(1, at) - w.gather(1, (at - 1).clamp(min=0)), -32768, 32767)
+            mask = mask & ~((pre == 0)[:, None] & (col == 0))
+            red = (torch.where(mask, y, 32767).min(1).values, torch.where(mask, y, -32768).max(1).values,
+                   torch.where(mask, y, 0).sum(1, dtype=torch.int64), torch.where(mask, y * y, 0).sum(1, dtype=torch.int64),
+                   mask.sum(1))
+        else:
+            red = (torch.where(mask, w, 32767).min(1).values, torch.where(mask, w, -32768).max(1).values,
+                   w.sum(1, dtype=torch.int64), (w * w).sum(1, dtype=torch.int64))
         torch.cuda.synchronize()
         t3 = now()
         assert src.levels(bin_len, full.data_ptr(), n_rows) == 0
@@ -163,12 +205,13 @@ def events_case(src, a, results, info, bin_len):
         timed(results, name + "_route_a_torch", rep, a.warmup, t3 - t2)
         timed(results, name + "_route_b", rep, a.warmup, t4 - t3)
     got = records(lv)
-    want_a = as_records(*(t.cpu().numpy() for t in red), ln.cpu().numpy().view(np.uint32))
+    counts = red[4].cpu().numpy().astype(np.uint32) if diff else ln.cpu().numpy().view(np.uint32)
+    want_a = as_records(*(t.cpu().numpy() for t in red[:4]), counts)
     same = np.array_equal(got, want_a) and np.array_equal(got, records(ev_lv)) and np.array_equal(got, records(ev_lv2)) and \
         not status.cpu().numpy().any()
     if not same:
         raise SystemExit("%s: the routes' records differ" % name)
-    info[name] = {"ranges": cap, "events": int(found), "bin_len": 0, "events_bin_len": bin_len, "peak_min": peak_min,
+    info[name] = {"signal": a.signal, "ranges": cap, "events": int(found), "bin_len": 0, "events_bin_len": bin_len, "peak_min": peak_min,
                   "samples": int(ln.sum().item()), "equal": bool(same),
                   "replays": ctx.get_option("last_range_levels_replays"), "overflow": ctx.get_option("last_range_levels_overflow")}
 
@@ -196,7 +239,7 @@ def cases(src, a, results, info):
 
 def config3(ctx, a, results, info):
     lib = x3hip.lib()
-    n, p = a.samples, x3hip.Params.default()
+    n, p, sig = a.samples, x3hip.Params.default(), x3hip.level_signal(a.signal)
     wav = torch.empty(n + 32, dtype=torch.int16, device="cuda")
     ctx.synth_dev(2, 0x58330003, 0, n, wav.data_ptr())
     ctx.sync()
@@ -214,11 +257,11 @@ def config3(ctx, a, results, info):
     s = (x.data_ptr(), pos, off.data_ptr(), so.data_ptr(), F, p)
     src = Source(
         ctx, "config3", 192_000, [n],
-        lambda d_e, d_s, d_l, k, bl, stride, d_lv, c, d_off, d_st: ctx.range_levels_dev(*s, d_s, d_l, k, bl, stride, d_lv, c, d_off,
-                                                                                        d_st, idx.data_ptr(), 32),
+        lambda d_e, d_s, d_l, k, bl, stride, d_lv, c, d_off, d_st: ctx.signal_range_levels_dev(*s, d_s, d_l, k, bl, stride, d_lv, c,
+                                                                                               d_off, d_st, idx.data_ptr(), 32, sig),
         lambda d_e, d_s, d_l, k, stride, d_out, oc, d_off, d_st: ctx.decode_ranges_dev(*s, d_s, d_l, k, stride, d_out, oc, 0, d_off,
                                                                                        d_st, idx.data_ptr(), 32),
-        lambda bl, d_lv, rows: ctx.levels_dev(*s, bl, d_lv, rows, None, idx.data_ptr(), 32),
+        lambda bl, d_lv, rows: ctx.signal_levels_dev(*s, bl, d_lv, rows, None, idx.data_ptr(), 32, sig),
         lambda d_lv, rows, bl, rule, d_e, d_s, d_l, d_el, c, d_c: ctx.events_dev(d_lv, rows, bl, so.data_ptr() + 8 * F, rule, d_s, d_l,
                                                                                 d_el, c, d_c),
         lambda bl: np.array([0, -(-n // bl)], dtype=np.uint64))
@@ -252,11 +295,13 @@ def corpus_a(ctx, a, results, info):
     offs = [int(fo[first[c]]) for c in range(n_clips)]
     lens = [int(fo[first[c + 1]]) - offs[c] for c in range(n_clips)]
     corpus = x3hip.Corpus(ctx, (d_x3, pos), offs, lens, seg_blocks=32)
+    sig = x3hip.level_signal(a.signal)
     src = Source(
         ctx, "corpus_a", 44_100, ns,
-        lambda d_e, d_s, d_l, k, bl, stride, d_lv, c, d_o, d_st: corpus.range_levels_into(d_e, d_s, d_l, k, bl, stride, d_lv, c, d_o, d_st),
+        lambda d_e, d_s, d_l, k, bl, stride, d_lv, c, d_o, d_st: corpus.range_levels_into(d_e, d_s, d_l, k, bl, stride, d_lv, c, d_o, d_st,
+                                                                                          signal=sig),
         lambda d_e, d_s, d_l, k, stride, d_out, oc, d_o, d_st: corpus.ranges_into(d_e, d_s, d_l, k, stride, d_out, oc, 0, d_o, d_st),
-        lambda bl, d_lv, rows: ctx.corpus_levels_dev(corpus, bl, d_lv, rows),
+        lambda bl, d_lv, rows: ctx.corpus_signal_levels_dev(corpus, bl, d_lv, rows, None, sig),
         lambda d_lv, rows, bl, rule, d_e, d_s, d_l, d_el, c, d_c: corpus.events_into(d_lv, rows, bl, rule, d_e, d_s, d_l, d_el, c, d_c),
         lambda bl: corpus.levels_rows(bl))
     cases(src, a, results, info)
@@ -272,6 +317,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--cap", type=int, default=4096)
     ap.add_argument("--cases", default="config3,corpus")
+    ap.add_argument("--signal", default="samples", choices=["samples", "diff"])
     ap.add_argument("--levels-bytes", type=float, default=16e9, help="route b runs where its records and workspace fit in this")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -282,7 +328,7 @@ def main():
         config3(ctx, a, results, info)
     if "corpus" in a.cases:
         corpus_a(ctx, a, results, info)
-    out = {"samples": a.samples, "reps": a.reps, "cases": info,
+    out = {"samples": a.samples, "reps": a.reps, "signal": a.signal, "cases": info,
            "ms_median": {k: round(float(np.median(v)), 4) for k, v in results.items()},
            "ms_min": {k: round(float(np.min(v)), 4) for k, v in results.items()},
            "ms_max": {k: round(float(np.max(v)), 4) for k, v in results.items()}}

@@ -2383,14 +2383,17 @@ static bool range_levels_args_ok(const x3_ctx* c, const uint64_t* d_starts, cons
 
 // The pairs (range, covering frame) the workspace holds: all a call can have, or four times what disjoint ranges need
 // (n_frames + n_ranges: sliding windows with up to 75 % overlap fit).  Pairs beyond it are the fix-up's: time, not results.
-uint64_t range_levels_pairs(uint64_t n, uint64_t F, uint64_t max_frames) {
-  return std::min<uint64_t>(n * max_frames, 4 * (F + n));   // (n < 2^31, max_frames <= F < 2^31: no wrap)
+// lead (X3_LEVEL_SIGNAL_DIFF): a range may have one more pair, its lead frame -- a frame of the same stream or entry, so
+// n * max_frames still holds them all.
+uint64_t range_levels_pairs(uint64_t n, uint64_t F, uint64_t max_frames, bool lead) {
+  return std::min<uint64_t>(n * max_frames, 4 * (F + n) + (lead ? n : 0));   // (n < 2^31, max_frames <= F < 2^31: no wrap)
 }
 
 // The workspace (RLevWs, x3_internal.h): per range the plan, the two scans, the rows that have room, the plan's starts; per
-// frame the verdicts; per pair its cut, the scan of the bin counts; the partial rows; replay scratch; the summary
+// frame the verdicts; per pair its cut, the scan of the bin counts; the partial rows; replay scratch; the summary; diff
+// (X3_LEVEL_SIGNAL_DIFF) only, behind it: per frame its last sample, per range whether its plan begins with a lead frame
 size_t range_levels_carve(char* base, uint64_t n, uint64_t F, uint64_t P, uint64_t rows_cap, uint64_t fix_waves,
-                          uint32_t scratch_per, RLevWs* w) {
+                          uint32_t scratch_per, RLevWs* w, bool diff) {
   BlockCarver k{base, 0};
   w->plan = k.take<X3WinPlan>(n);
   w->cov_off = k.take<unsigned long long>(n + 1);
@@ -2402,30 +2405,37 @@ size_t range_levels_carve(char* base, uint64_t n, uint64_t F, uint64_t P, uint64
   w->prow = k.take<unsigned long long>(P + 1);
   w->rows = k.take<x3_level>(rows_cap + P);
   w->scratch = k.take<int16_t>(std::max<uint64_t>(fix_waves, 4) * scratch_per);
-  w->sum = k.take<X3RLevSummary>(1, 1);
+  w->sum = k.take<X3RLevSummary>(1, diff ? 256 : 1);
+  w->tail = diff ? k.take<int32_t>(F) : nullptr;
+  w->lead = diff ? k.take<uint32_t>(n, 1) : nullptr;
   return k.at;
 }
 
 // The launch set of a range-levels call behind its plan step: plan(grid, plan, gstart, sum) enqueues the ranges' plan kernel
-// and returns the starts the later kernels read (the caller's, or the plan's gstart), as in windows_launch.
+// and returns the starts the later kernels read (the caller's, or the plan's gstart), as in windows_launch.  signal:
+// X3_LEVEL_SIGNAL_SAMPLES, or X3_LEVEL_SIGNAL_DIFF -- the lead kernel behind the plan (d_ent, n_ent, d_entries: the corpus's
+// table and the caller's entries, NULL for a stream), the other instance of the accumulate and fix-up kernels, which leave
+// every good frame's last sample in the workspace, and the seam kernel behind them.
 template <class Plan>
 static int range_levels_launch(x3_ctx* c, const FrameSource& s, const uint32_t* d_lens, uint64_t n, uint64_t bin_len,
                                uint64_t row_stride, x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets,
-                               int32_t* d_status, Plan plan_step) {
+                               int32_t* d_status, int signal, const x3_corpus_entry* d_ent, uint64_t n_ent,
+                               const uint32_t* d_entries, Plan plan_step) {
+  const bool diff = signal == X3_LEVEL_SIGNAL_DIFF;
   HIPCHK(c, hipSetDevice(c->device));
-  const uint64_t P = range_levels_pairs(n, s.F, s.max_frames), cap = rows_cap + P;
+  const uint64_t P = range_levels_pairs(n, s.F, s.max_frames, diff), cap = rows_cap + P;
   const uint32_t scratch_per = levels_scratch_per(s.dp.block_len);
   const uint64_t fix_waves = levels_fix_waves(n, scratch_per);
   RLevWs w;
   int rc;
-  if ((rc = ensure(c, c->rlev_ws, range_levels_carve(nullptr, n, s.F, P, rows_cap, fix_waves, scratch_per, &w)))) return rc;
-  range_levels_carve((char*)c->rlev_ws.p, n, s.F, P, rows_cap, fix_waves, scratch_per, &w);
+  if ((rc = ensure(c, c->rlev_ws, range_levels_carve(nullptr, n, s.F, P, rows_cap, fix_waves, scratch_per, &w, diff)))) return rc;
+  range_levels_carve((char*)c->rlev_ws.p, n, s.F, P, rows_cap, fix_waves, scratch_per, &w, diff);
   // grids: the counts are on the device and every kernel walks them grid-stride.  What a range has on average is at most
   // rows_cap / n rows (or the stride) of bin_len positions: the caller's words, possibly far above what is drawn, so a range
   // covers no more frames than the stream (or the longest entry) has and a call no more pairs than P.
   const uint64_t rows_hint = row_stride ? row_stride : std::max<uint64_t>(rows_cap / n, 1);
   const uint64_t len_hint = bin_len && bin_len <= 0xFFFFFFFFull / rows_hint ? rows_hint * bin_len : 0xFFFFFFFFull;
-  const uint64_t frames_per = std::max<uint64_t>(1, std::min(len_hint / (s.spf ? s.spf : 1) + 2, s.max_frames));
+  const uint64_t frames_per = std::max<uint64_t>(1, std::min(len_hint / (s.spf ? s.spf : 1) + 2 + (diff ? 1 : 0), s.max_frames));
   const uint64_t cov_hint = std::min(n * frames_per, P), item_hint = std::min<uint64_t>(cov_hint, 256ull * X3W_GRID_LIMIT) * s.nseg;
   // the caller's records: padded, all n * stride are written; packed, a range has no more rows than the frames it can cover
   // hold bins (one with bin_len 0 or above any length), so a roomy rows_cap does not size the prep, init and merge grids
@@ -2433,6 +2443,9 @@ static int range_levels_launch(x3_ctx* c, const FrameSource& s, const uint32_t* 
                               : bin_len && bin_len <= 0xFFFFFFFFull ? std::min(rows_hint, frames_per * (s.spf ? s.spf : 1) / bin_len + 1) : 1;
   const uint64_t rec_hint = std::min(n * drawn_rows, rows_cap);
   const uint64_t* d_starts = plan_step(dim3(grid_for(n, 256)), w.plan, w.gstart, &w.sum->w);
+  if (diff)
+    hipLaunchKernelGGL(x3_range_levels_lead_kernel, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, s.d_sample_offsets, d_ent, n_ent,
+                       d_entries, d_starts, d_lens, n, w.plan, w.lead);
   hipLaunchKernelGGL(x3_range_levels_scan_kernel, dim3(1), dim3(1024), 0, c->stream, w.plan, n, d_lens, bin_len, row_stride, rows_cap,
                      w.cov_off, w.row_off, w.erows, d_row_offsets, w.sum);
   hipLaunchKernelGGL(x3_window_check_kernel, dim3(grid_for(cov_hint, 4)), dim3(256), 0, c->stream, s.d_x3, s.x3_len, s.d_frame_offsets,
@@ -2445,18 +2458,28 @@ static int range_levels_launch(x3_ctx* c, const FrameSource& s, const uint32_t* 
                      (const unsigned long long*)w.cov_off, n, P, cap, w.prow, w.sum);
   hipLaunchKernelGGL(x3_range_levels_init_kernel, dim3(grid_for(rec_hint + cov_hint, 256)), dim3(256), 0, c->stream,
                      (const unsigned long long*)w.cov_off, n, P, cap, (const unsigned long long*)w.prow, w.rows);
-  hipLaunchKernelGGL(x3_range_levels_accum_kernel, dim3(grid_for(item_hint, 256)), dim3(256), 0, c->stream, s.d_x3, s.x3_len,
-                     s.d_frame_offsets, s.dp, s.idx, s.seg_blocks, s.nseg, bin_len, (const unsigned long long*)w.cov_off, n, P, cap,
-                     (const X3RLevPair*)w.pairs, (const unsigned long long*)w.prow, w.rows, w.fst);
-  hipLaunchKernelGGL(x3_range_levels_fixup_kernel, dim3((unsigned)((fix_waves + 3) / 4)), dim3(256), 0, c->stream, s.d_x3,
-                     s.d_frame_offsets, s.d_sample_offsets, d_starts, d_lens, (const X3WinPlan*)w.plan, n, s.dp, bin_len,
-                     (const unsigned long long*)w.cov_off, (const unsigned long long*)w.row_off, (const uint32_t*)w.erows,
-                     row_stride, P, cap, (const unsigned long long*)w.prow, (const int32_t*)w.fst, d_levels, d_status, w.scratch,
-                     scratch_per, w.sum);
+  auto decode = [&](auto sig, auto tail) {   // the two kernels that decode, for a signal
+    using Signal = decltype(sig);
+    hipLaunchKernelGGL(x3_range_levels_accum_kernel<Signal>, dim3(grid_for(item_hint, 256)), dim3(256), 0, c->stream, s.d_x3, s.x3_len,
+                       s.d_frame_offsets, s.dp, s.idx, s.seg_blocks, s.nseg, bin_len, (const unsigned long long*)w.cov_off, n, P, cap,
+                       (const X3RLevPair*)w.pairs, (const unsigned long long*)w.prow, w.rows, w.fst, tail);
+    hipLaunchKernelGGL(x3_range_levels_fixup_kernel<Signal>, dim3((unsigned)((fix_waves + 3) / 4)), dim3(256), 0, c->stream, s.d_x3,
+                       s.d_frame_offsets, s.d_sample_offsets, d_starts, d_lens, (const X3WinPlan*)w.plan, n, s.dp, bin_len,
+                       (const unsigned long long*)w.cov_off, (const unsigned long long*)w.row_off, (const uint32_t*)w.erows,
+                       row_stride, P, cap, (const unsigned long long*)w.prow, (const int32_t*)w.fst, d_levels, d_status, w.scratch,
+                       scratch_per, w.sum, tail, (const uint32_t*)w.lead);
+  };
+  if (diff) decode(X3LevDiff{}, w.tail);
+  else decode(X3LevSamples{}, X3LevNoTail{});
   hipLaunchKernelGGL(x3_range_levels_merge_kernel, dim3(grid_for(rec_hint + cov_hint, 256)), dim3(256), 0, c->stream,
                      (const X3RLevPair*)w.pairs, (const unsigned long long*)w.cov_off, n, P, cap, (const unsigned long long*)w.prow,
                      (const unsigned long long*)w.row_off, (const uint32_t*)w.erows, row_stride, (const x3_level*)w.rows,
                      (const int32_t*)w.fst, d_levels);
+  if (diff)
+    hipLaunchKernelGGL(x3_range_levels_seam_kernel, dim3(grid_for(cov_hint, 256)), dim3(256), 0, c->stream, s.d_x3, s.x3_len,
+                       s.d_frame_offsets, bin_len, (const X3RLevPair*)w.pairs, (const unsigned long long*)w.cov_off, n, P, cap,
+                       (const unsigned long long*)w.prow, (const unsigned long long*)w.row_off, (const uint32_t*)w.erows, row_stride,
+                       (const int32_t*)w.fst, (const int32_t*)w.tail, d_levels);
   HIPCHK(c, hipGetLastError());
   c->range_levels.pending = true;
   c->range_levels.count = n;
@@ -2464,17 +2487,20 @@ static int range_levels_launch(x3_ctx* c, const FrameSource& s, const uint32_t* 
   return X3_OK;
 }
 
-extern "C" int x3_range_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
-                                   const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
-                                   const uint64_t* d_seg_index, uint32_t seg_blocks, const uint64_t* d_starts,
-                                   const uint32_t* d_lens, uint64_t n_ranges, uint64_t bin_len, uint64_t row_stride,
-                                   x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status) {
-  if (!c || !range_levels_args_ok(c, d_starts, d_lens, n_ranges, row_stride, d_levels, rows_cap, d_row_offsets, d_status))
+extern "C" int x3_signal_range_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
+                                          const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
+                                          const uint64_t* d_seg_index, uint32_t seg_blocks, const uint64_t* d_starts,
+                                          const uint32_t* d_lens, uint64_t n_ranges, uint64_t bin_len, uint64_t row_stride,
+                                          x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status,
+                                          int signal) {
+  if (!c || !levels_signal_ok(signal) ||
+      !range_levels_args_ok(c, d_starts, d_lens, n_ranges, row_stride, d_levels, rows_cap, d_row_offsets, d_status))
     return X3_ERR_BAD_ARG;
   FrameSource s;
   const int rc = stream_source(d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, p, d_seg_index, seg_blocks, &s);
   if (rc) return rc;
-  return range_levels_launch(c, s, d_lens, n_ranges, bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status,
+  return range_levels_launch(c, s, d_lens, n_ranges, bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status, signal,
+                             nullptr, 0, nullptr,
                              [&](dim3 grid, X3WinPlan* plan, uint64_t*, X3WinSummary* sum) -> const uint64_t* {
                                hipLaunchKernelGGL(x3_range_plan_kernel, grid, dim3(256), 0, c->stream, d_sample_offsets, n_frames,
                                                   d_starts, d_lens, n_ranges, plan, sum);
@@ -2482,22 +2508,50 @@ extern "C" int x3_range_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_l
                              });
 }
 
-extern "C" int x3_corpus_range_levels_dev(x3_ctx* c, const x3_corpus* k, const uint32_t* d_entries, const uint64_t* d_starts,
-                                          const uint32_t* d_lens, uint64_t n_ranges, uint64_t bin_len, uint64_t row_stride,
-                                          x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status) {
-  if (!c || !k || !d_entries || (reinterpret_cast<uintptr_t>(d_entries) & 3u)) return X3_ERR_BAD_ARG;
+extern "C" int x3_range_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
+                                   const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
+                                   const uint64_t* d_seg_index, uint32_t seg_blocks, const uint64_t* d_starts,
+                                   const uint32_t* d_lens, uint64_t n_ranges, uint64_t bin_len, uint64_t row_stride,
+                                   x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status) {
+  return x3_signal_range_levels_dev(c, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, p, d_seg_index, seg_blocks,
+                                    d_starts, d_lens, n_ranges, bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status,
+                                    X3_LEVEL_SIGNAL_SAMPLES);
+}
+
+// (entry: the name errors carry -- the call the caller made)
+static int corpus_range_levels_call(x3_ctx* c, const x3_corpus* k, const char* entry, const uint32_t* d_entries,
+                                    const uint64_t* d_starts, const uint32_t* d_lens, uint64_t n_ranges, uint64_t bin_len,
+                                    uint64_t row_stride, x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets,
+                                    int32_t* d_status, int signal) {
+  if (!c || !levels_signal_ok(signal) || !k || !d_entries || (reinterpret_cast<uintptr_t>(d_entries) & 3u)) return X3_ERR_BAD_ARG;
   if (!range_levels_args_ok(c, d_starts, d_lens, n_ranges, row_stride, d_levels, rows_cap, d_row_offsets, d_status))
     return X3_ERR_BAD_ARG;
   FrameSource s;
-  const int rc = corpus_source(c, k, "x3_corpus_range_levels_dev", &s);
+  const int rc = corpus_source(c, k, entry, &s);
   if (rc) return rc;
-  return range_levels_launch(c, s, d_lens, n_ranges, bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status,
+  return range_levels_launch(c, s, d_lens, n_ranges, bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status, signal,
+                             (const x3_corpus_entry*)k->d_ent, k->n, d_entries,
                              [&](dim3 grid, X3WinPlan* plan, uint64_t* gstart, X3WinSummary* sum) -> const uint64_t* {
                                hipLaunchKernelGGL(x3_corpus_range_plan_kernel, grid, dim3(256), 0, c->stream, k->d_ent, k->n,
                                                   s.d_sample_offsets, s.F, d_entries, d_starts, d_lens, n_ranges, plan, gstart,
                                                   sum);
                                return gstart;
                              });
+}
+
+extern "C" int x3_corpus_range_levels_dev(x3_ctx* c, const x3_corpus* k, const uint32_t* d_entries, const uint64_t* d_starts,
+                                          const uint32_t* d_lens, uint64_t n_ranges, uint64_t bin_len, uint64_t row_stride,
+                                          x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status) {
+  return corpus_range_levels_call(c, k, "x3_corpus_range_levels_dev", d_entries, d_starts, d_lens, n_ranges, bin_len, row_stride,
+                                  d_levels, rows_cap, d_row_offsets, d_status, X3_LEVEL_SIGNAL_SAMPLES);
+}
+
+extern "C" int x3_corpus_signal_range_levels_dev(x3_ctx* c, const x3_corpus* k, const uint32_t* d_entries, const uint64_t* d_starts,
+                                                 const uint32_t* d_lens, uint64_t n_ranges, uint64_t bin_len, uint64_t row_stride,
+                                                 x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status,
+                                                 int signal) {
+  return corpus_range_levels_call(c, k, "x3_corpus_signal_range_levels_dev", d_entries, d_starts, d_lens, n_ranges, bin_len,
+                                  row_stride, d_levels, rows_cap, d_row_offsets, d_status, signal);
 }
 
 extern "C" int x3_range_levels_result(x3_ctx* c, uint64_t* n_bad, uint64_t* first_bad, int* first_bad_status,

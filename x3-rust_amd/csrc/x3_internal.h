@@ -484,7 +484,8 @@ struct EvWs {
 };
 X3_INTERNAL size_t events_carve(char* base, uint64_t n_rows, uint64_t n_ent, EvWs* w);
 // ... and of a range-levels call (rlev_ws; x3_range_levels_kernel.h): n ranges over F frames, P pairs (range, covering
-// frame) with rows_cap + P partial rows, `fix_waves` waves of the fix-up with `scratch_per` samples each
+// frame) with rows_cap + P partial rows, `fix_waves` waves of the fix-up with `scratch_per` samples each; diff
+// (X3_LEVEL_SIGNAL_DIFF): behind the summary, a word per frame (its last sample) and per range (a lead frame in its plan)
 struct X3RLevPair;
 struct X3RLevSummary;
 struct RLevWs {
@@ -492,10 +493,11 @@ struct RLevWs {
   int32_t* fst;                                                                                                  // per frame
   X3RLevPair* pairs; unsigned long long* prow; x3_level* rows;   // per pair (prow: P + 1 words); the partial rows
   int16_t* scratch; X3RLevSummary* sum;
+  int32_t* tail; uint32_t* lead;   // diff only (NULL otherwise): per frame, per range
 };
-X3_INTERNAL uint64_t range_levels_pairs(uint64_t n, uint64_t F, uint64_t max_frames);
+X3_INTERNAL uint64_t range_levels_pairs(uint64_t n, uint64_t F, uint64_t max_frames, bool lead = false);
 X3_INTERNAL size_t range_levels_carve(char* base, uint64_t n, uint64_t F, uint64_t P, uint64_t rows_cap, uint64_t fix_waves,
-                                      uint32_t scratch_per, RLevWs* w);
+                                      uint32_t scratch_per, RLevWs* w, bool diff = false);
 // ... and of a quantiles or thresholds call (q_ws; x3_quantiles_kernel.h): n_rows records, n_ent entries (1 for a stream),
 // n_q quantiles of each
 struct X3QSlot;

@@ -176,11 +176,25 @@ struct X3LevDiff {
     prev = s;
     have = true;
   }
+  // a position the lane sees and its bins do not hold (in front of or behind a range's cut of the frame): it is the next
+  // position's `prev` all the same
+  __device__ __forceinline__ void skip(uint32_t v) {
+    prev = (int32_t)(int16_t)(uint16_t)v;
+    have = true;
+  }
+};
+// x3w_stretch's watch for X3LevDiff: the stretch's seed into the signal, the frame's last sample to its word of the tails
+struct X3LevDiffWatch {
+  X3LevDiff& sig;
+  int32_t* at;
+  __device__ __forceinline__ void seed(uint32_t v) const { sig.seed(v); }
+  __device__ __forceinline__ void end(uint32_t v) const { *at = (int32_t)(int16_t)(uint16_t)v; }
 };
 
 // The bins of consecutive positions from g on: decode(put_at) hands sample s of a frame to put_at(s, value), in order;
-// the positions with keep(s) go to the signal, bins that fill go to flush, and so does the open one at the end.  Returns
-// decode's.  A signal with state (X3LevDiff) is the caller's, at `sig`; X3LevSamples has none and nothing of it is captured.
+// the positions with keep(s) go to the signal, bins that fill go to flush, and so does the open one at the end; a position
+// without keep(s) counts in no bin, and a signal with history (X3LevDiff) still sees its sample.  Returns decode's.  A
+// signal with state (X3LevDiff) is the caller's, at `sig`; X3LevSamples has none and nothing of it is captured.
 template <class Signal = X3LevSamples, class Decode, class Keep, class Flush>
 __device__ __forceinline__ int32_t x3l_bin_samples(uint64_t g, uint64_t bl, Decode decode, Keep keep, Flush flush,
                                                    Signal* sig = nullptr) {
@@ -190,6 +204,8 @@ __device__ __forceinline__ int32_t x3l_bin_samples(uint64_t g, uint64_t bl, Deco
     if (keep(s)) {
       if constexpr (Signal::kDiff) bn.put(*sig, v, flush);
       else bn.put(Signal{}, v, flush);
+    } else if constexpr (Signal::kDiff) {
+      sig->skip(v);
     }
   });
   flush(bn.bin, bn.a);
@@ -338,16 +354,10 @@ x3_levels_accum_kernel(const uint8_t* __restrict__ x3, uint64_t len, const uint6
     };
     // a stretch's samples come in order, from sample 0 or from the first sample of block sb * j
     if constexpr (Signal::kDiff) {
-      struct Watch {
-        Signal& sig;
-        int32_t* at;
-        __device__ __forceinline__ void seed(uint32_t v) const { sig.seed(v); }
-        __device__ __forceinline__ void end(uint32_t v) const { *at = (int32_t)(int16_t)(uint16_t)v; }
-      };
       Signal sig;
       const int r = x3l_bin_samples(
           fr.pos + (j ? 1u + (uint64_t)sb * j * p.block_len : 0u), bl,
-          [&](auto put_at) { return x3w_stretch(x3, len, frame_off[f], p, idx, segd, sb, nseg, f, j, put_at, Watch{sig, tail + f}); },
+          [&](auto put_at) { return x3w_stretch(x3, len, frame_off[f], p, idx, segd, sb, nseg, f, j, put_at, X3LevDiffWatch{sig, tail + f}); },
           X3LevKeepAll{}, flush, &sig);
       if (r < 0) atomicOr(&fst[f], X3W_FLAG);
     } else {

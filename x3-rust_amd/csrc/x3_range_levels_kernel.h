@@ -25,6 +25,11 @@
 //  x3_range_levels_fixup_kernel  -- a wave per range, frames in order: flagged frames and pairs without rows through the
 //      reference's reader; the range's status; the summary
 //  x3_range_levels_merge_kernel  -- a lane per partial row, rows of one record side by side in a wave joined first
+// The accumulate and fix-up kernels are templates over the SIGNAL (x3_levels_kernel.h): X3LevSamples (the range-levels calls) or
+// X3LevDiff (x3_signal_range_levels_dev / x3_corpus_signal_range_levels_dev), which has two kernels more:
+//  x3_range_levels_lead_kernel   -- behind the plan: a range that starts at a frame's first sample gets the frame in front
+//  x3_range_levels_seam_kernel   -- behind the accumulate kernel: a lane per pair, the difference across the frame's front seam
+// (both at the end of this file)
 //
 // CAPACITY.  The workspace holds P pairs and cap = rows_cap + P partial rows, both sized on the host.  A pair with q >= P or
 // whose rows end behind cap has no rows: accumulate and merge skip it (x3rl_no_rows, recomputed from q and the scan) and the
@@ -149,13 +154,17 @@ x3_range_levels_init_kernel(const unsigned long long* __restrict__ cov_off, uint
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < used; i += (uint64_t)gridDim.x * blockDim.x) rows[i] = id;
 }
 
-// ---- accumulate: a lane per (pair, stretch) into the pair's own rows
+// ---- accumulate: a lane per (pair, stretch) into the pair's own rows.  Signal: X3LevSamples, or X3LevDiff, whose lanes take
+// the stretch's seed from x3w_stretch, see the samples outside [lo, hi) without counting them (the sample in front of lo is
+// sample lo's `prev`), and whose lane at the frame's end stores the frame's last sample to tail[f].  A pair with an empty cut
+// (a lead frame) runs its stretches for the proof and the tail and touches no row: cnt is 0.
+template <class Signal>
 __global__ void __launch_bounds__(256)
 x3_range_levels_accum_kernel(const uint8_t* __restrict__ x3, uint64_t len, const uint64_t* __restrict__ frame_off, X3DevParams p,
                              const uint2* __restrict__ idx, uint32_t sb, uint32_t nseg, uint64_t bin_len,
                              const unsigned long long* __restrict__ cov_off, uint64_t n, uint64_t P, uint64_t cap,
                              const X3RLevPair* __restrict__ pairs, const unsigned long long* __restrict__ prow,
-                             x3_level* __restrict__ rows, int32_t* __restrict__ fst) {
+                             x3_level* __restrict__ rows, int32_t* __restrict__ fst, typename Signal::Tail tail) {
   const bool segd = x3w_index_ok(idx, sb);
   const uint32_t ns = segd ? nseg : 1u;
   const uint64_t bl = x3l_bin_len(bin_len);
@@ -175,16 +184,30 @@ x3_range_levels_accum_kernel(const uint8_t* __restrict__ x3, uint64_t len, const
     // a stretch's samples come in order, from sample 0 or from the first sample of block sb * j; the first of them inside
     // the range, if any, is sample max(s0, lo)
     const uint64_t s0 = j ? 1u + (uint64_t)sb * j * p.block_len : 0u;
-    const int r = x3l_bin_samples(
+    [[maybe_unused]] Signal sig;
+    const int r = x3l_bin_samples<Signal>(
         (uint64_t)pr.r0 + (s0 > lo ? s0 - lo : 0u), bl,
-        [&](auto put_at) { return x3w_stretch(x3, len, frame_off[pr.f], p, idx, segd, sb, nseg, pr.f, j, put_at); },
-        [&](uint32_t s) { return s - lo < span; }, flush);
+        [&](auto put_at) {
+          if constexpr (Signal::kDiff)
+            return x3w_stretch(x3, len, frame_off[pr.f], p, idx, segd, sb, nseg, pr.f, j, put_at, X3LevDiffWatch{sig, tail + pr.f});
+          else
+            return x3w_stretch(x3, len, frame_off[pr.f], p, idx, segd, sb, nseg, pr.f, j, put_at);
+        },
+        [&](uint32_t s) { return s - lo < span; }, flush, &sig);
     if (r < 0) atomicOr(&fst[pr.f], X3W_FLAG);
   }
 }
 
 // ---- fix-up: a wave per range (lane 0 works), frames in order; scratch: a block's samples per wave of the grid.  The
 // frame words are read, never written: a frame may lie under other ranges, whose waves read it too.
+// X3LevDiff: the wave carries the frame in front -- its final status, its last sample, whether its pair went the fast way
+// (x3rl_fast) -- and adds the seams x3_range_levels_seam_kernel leaves; a lead frame (lead[w]: the plan's first frame lies in
+// front of the range) never gives the range its status; tail[f] of every frame it replays to status 0.
+__device__ __forceinline__ bool x3rl_fast(int32_t word, const unsigned long long* __restrict__ prow, uint64_t q, uint64_t P, uint64_t cap) {
+  return word == X3D_OK && !x3rl_no_rows(prow, q, P, cap);
+}
+
+template <class Signal>
 __global__ void __launch_bounds__(256)
 x3_range_levels_fixup_kernel(const uint8_t* __restrict__ x3, const uint64_t* __restrict__ frame_off, const uint64_t* __restrict__ so,
                              const uint64_t* __restrict__ starts, const uint32_t* __restrict__ lens,
@@ -193,7 +216,8 @@ x3_range_levels_fixup_kernel(const uint8_t* __restrict__ x3, const uint64_t* __r
                              const uint32_t* __restrict__ erows, uint64_t stride, uint64_t P, uint64_t cap,
                              const unsigned long long* __restrict__ prow, const int32_t* __restrict__ fst,
                              x3_level* __restrict__ levels, int32_t* __restrict__ status, int16_t* __restrict__ scratch,
-                             uint32_t scratch_per, X3RLevSummary* __restrict__ sum) {
+                             uint32_t scratch_per, X3RLevSummary* __restrict__ sum, typename Signal::Tail tail,
+                             const uint32_t* __restrict__ lead) {
   const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
   const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (threadIdx.x & 63u) return;
@@ -207,25 +231,57 @@ x3_range_levels_fixup_kernel(const uint8_t* __restrict__ x3, const uint64_t* __r
       const uint64_t start = starts[w], q0 = cov_off[w];
       const uint32_t L = lens[w], R = erows[w];
       x3_level* const mine = levels + x3rl_base(row_off, stride, w);
+      // X3LevDiff: the frame in front -- its final status (none yet: not X3D_OK), its last sample, the way its pair went
+      [[maybe_unused]] int32_t pfs = X3D_BAD_ARG, ptail = 0;
+      [[maybe_unused]] bool pfast = false;
       for (uint32_t k = 0; k < pl.ncov; ++k) {
         const uint64_t f = pl.fa + k;
         int32_t fs = fst[f];
+        [[maybe_unused]] int32_t ftail = 0;
+        [[maybe_unused]] const bool fast = x3rl_fast(fs, prow, q0 + k, P, cap);
         if (fs == X3W_FLAG || (fs == X3D_OK && x3rl_no_rows(prow, q0 + k, P, cap))) {
           const uint8_t* const payload = x3 + frame_off[f] + 20u;
-          fs = x3w_replay_frame(payload, p, blk, [](uint32_t, uint32_t) {});
+          if constexpr (Signal::kDiff) {
+            fs = x3w_replay_frame(payload, p, blk, [&](uint32_t, uint32_t v) { ftail = (int32_t)(int16_t)(uint16_t)v; });
+            if (fs == X3D_OK) tail[f] = ftail;
+          } else {
+            fs = x3w_replay_frame(payload, p, blk, [](uint32_t, uint32_t) {});
+          }
           uint32_t lo, hi, r0;
           if (fs == X3D_OK && x3rl_cut(so, f, start, L, lo, hi, r0)) {   // every block decodes: once more, into the records
             auto flush = [&](uint64_t bin, const X3LevAcc& a) {
               if (bin < (uint64_t)R) x3l_merge(mine + bin, a);
             };
             const uint32_t span = hi - lo;
-            (void)x3l_bin_samples(
+            [[maybe_unused]] Signal sig;
+            (void)x3l_bin_samples<Signal>(
                 r0, bl, [&](auto put_at) { return x3w_replay_frame(payload, p, blk, put_at); },
-                [&](uint32_t s) { return s - lo < span; }, flush);
+                [&](uint32_t s) { return s - lo < span; }, flush, &sig);
           }
           ++replayed;
+        } else if constexpr (Signal::kDiff) {
+          if (fast) ftail = tail[f];   // (the accumulate kernel's: every stretch of the frame is proven, the last one stored it)
         }
-        if (fs != X3D_OK && st == X3D_OK) st = fs;   // (the first in frame order; the frames behind it still count)
+        if constexpr (Signal::kDiff) {
+          // the seam in front of frame f: both frames end with status 0, sample 0 of f lies in the range; the seam kernel has
+          // it iff both pairs went the fast way (the same tests there)
+          uint32_t lo, hi, r0;
+          if (k >= 1u && fs == X3D_OK && pfs == X3D_OK && !(fast && pfast) && x3rl_cut(so, f, start, L, lo, hi, r0) && lo == 0u &&
+              r0 / bl < (uint64_t)R) {
+            // (a checked frame: its payload's first two bytes lie inside the stream)
+            const uint8_t* const payload = x3 + frame_off[f] + 20u;
+            X3LevAcc a;
+            a.reset();
+            a.add_value(x3l_diff((int32_t)(int16_t)(uint16_t)(((uint32_t)payload[0] << 8) | payload[1]), ptail));
+            x3l_merge(mine + r0 / bl, a);
+          }
+          pfs = fs;
+          ptail = ftail;
+          pfast = fast;
+          if (fs != X3D_OK && st == X3D_OK && k >= (lead[w] ? 1u : 0u)) st = fs;   // (the first COVERING frame in frame order)
+        } else {
+          if (fs != X3D_OK && st == X3D_OK) st = fs;   // (the first in frame order; the frames behind it still count)
+        }
       }
     }
     if (replayed) atomicAdd(&sum->w.replays, (unsigned long long)replayed);
@@ -262,6 +318,82 @@ x3_range_levels_merge_kernel(const X3RLevPair* __restrict__ pairs, const unsigne
         const x3_level r = rows[i];
         key = x3rl_base(row_off, stride, pr.w) + bin;   // (below the range's base + erows: inside rows_cap, the range scan)
         a.load(r);
+      }
+    }
+    x3l_merge_runs(levels, key, a, lane);
+  }
+}
+
+// ---- X3_LEVEL_SIGNAL_DIFF (x3_signal_range_levels_dev / x3_corpus_signal_range_levels_dev)
+// THE LEAD FRAME.  The difference at a range's first position needs the sample in front of it.  Inside a frame a lane has
+// it: it decodes the frame from its start or takes a seed.  A range with len > 0 that starts at sample 0 of its first
+// covering frame fa, with fa not the first frame of its stream or entry, needs frame fa - 1: checked, proven by all its
+// stretches, its last sample known.  x3_range_levels_lead_kernel, behind the plan kernel and in front of the range scan, widens
+// such a plan by that one frame (fa - 1, ncov + 1) and notes it in lead[w]; the frame is then an ordinary pair whose cut is
+// empty (x3rl_cut false, cnt 0).  ent: the corpus's entry table (first: the entry's first frame), NULL for a stream (0).
+// Bounds: fa - 1 >= first >= 0 and fa - 1 < fa, a frame of the table the plan searched; ncov + 1 <= F.
+__global__ void __launch_bounds__(256)
+x3_range_levels_lead_kernel(const uint64_t* __restrict__ so, const x3_corpus_entry* __restrict__ ent, uint64_t n_ent,
+                            const uint32_t* __restrict__ entries, const uint64_t* __restrict__ starts,
+                            const uint32_t* __restrict__ lens, uint64_t n, X3WinPlan* __restrict__ plan, uint32_t* __restrict__ lead) {
+  for (uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; w < n; w += (uint64_t)gridDim.x * blockDim.x) {
+    X3WinPlan pl = plan[w];
+    uint32_t ld = 0;
+    if (pl.status == X3D_OK && pl.ncov && lens[w]) {
+      uint64_t first = 0;
+      bool known = true;
+      if (ent) {
+        const uint32_t e = entries[w];
+        known = e < n_ent;   // (the plan has refused the others)
+        if (known) first = ent[e].first_frame;
+      }
+      if (known && pl.fa > first && so[pl.fa] == starts[w]) {
+        --pl.fa;
+        ++pl.ncov;
+        ld = 1u;
+        plan[w] = pl;
+      }
+    }
+    lead[w] = ld;
+  }
+}
+
+// ---- seam: a lane per pair q (below P), behind the accumulate kernel.  The difference at the position of frame f's sample
+// 0 is the frame's first sample (the 16-bit literal at the start of its payload) minus frame f - 1's last (tail[f - 1]).  It
+// is the range's when sample 0 of f lies in the range (the pair's cut has lo == 0) and f - 1 is a frame of the same stream or
+// entry: pair q - 1 of the same range -- a covering frame, or the lead frame, which the plan holds only inside the entry.
+// This kernel takes the seam iff both pairs went the fast way: both words X3D_OK behind the accumulate kernel (checked, every
+// stretch proven, tail[f - 1] stored by the stretch that reached the frame's end) and both with rows (x3rl_fast; a pair with
+// cnt 0 needs none).  Every other seam is the fix-up wave's, which tests the same and takes the complement: a seam is counted
+// once.  Lanes are joined by record as in x3_range_levels_merge_kernel: with one bin every seam of a range is one record's.
+// Bounds: q < min(cov_off[n], P), so pairs[q], pairs[q - 1] and prow[q + 1] lie in the workspace; pr.f and pr.f - 1 are
+// frames of the plan; frame f is checked, so its payload's first bytes lie inside the stream; the record is below the
+// range's base + erows[w], inside rows_cap (the range scan).
+__global__ void __launch_bounds__(256)
+x3_range_levels_seam_kernel(const uint8_t* __restrict__ x3, uint64_t len, const uint64_t* __restrict__ frame_off, uint64_t bin_len,
+                            const X3RLevPair* __restrict__ pairs, const unsigned long long* __restrict__ cov_off, uint64_t n,
+                            uint64_t P, uint64_t cap, const unsigned long long* __restrict__ prow,
+                            const unsigned long long* __restrict__ row_off, const uint32_t* __restrict__ erows, uint64_t stride,
+                            const int32_t* __restrict__ fst, const int32_t* __restrict__ tail, x3_level* __restrict__ levels) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t bl = x3l_bin_len(bin_len);
+  const uint64_t np = min((uint64_t)cov_off[n], P);
+  const uint64_t lanes = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t q0 = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u); q0 < np; q0 += lanes) {   // (whole waves)
+    const uint64_t q = q0 + lane;
+    X3LevAcc a;
+    a.reset();
+    uint64_t key = ~0ull;
+    if (q >= 1u && q < np) {
+      const X3RLevPair pr = pairs[q], pp = pairs[q - 1u];
+      if (pp.w == pr.w && pp.f + 1u == pr.f && pr.cnt && pr.lo == 0u && x3rl_fast(fst[pr.f], prow, q, P, cap) &&
+          x3rl_fast(fst[pp.f], prow, q - 1u, P, cap)) {
+        const uint64_t bin = (uint64_t)pr.r0 / bl;
+        if (bin < (uint64_t)erows[pr.w]) {
+          const int32_t head = (int32_t)(int16_t)(uint16_t)(x3w_be32_at(x3, len, frame_off[pr.f] + 20u) >> 16);
+          a.add_value(x3l_diff(head, tail[pp.f]));
+          key = x3rl_base(row_off, stride, pr.w) + bin;
+        }
       }
     }
     x3l_merge_runs(levels, key, a, lane);

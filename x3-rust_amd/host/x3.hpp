@@ -852,20 +852,22 @@ inline X3Error events_adaptive(Context& ctx, const x3_level* d_levels, uint64_t 
 // counts, written to d_row_offsets (n_ranges + 1 words, required); a range without room in rows_cap records is BadArg and not
 // written.  row_stride > 0: range w at w * row_stride with identities behind its rows (d_row_offsets may be nullptr).  The
 // arrays device::events wrote go in as they are.  Waits for the call: res = ranges with status != 0, the first, its status,
-// and the sum of all row counts.
+// and the sum of all row counts.  signal (x3_signal_range_levels_dev): LevelSignal::Diff gives the records of the stream's
+// first difference cut to the ranges -- the difference at a range's first position counts, statuses are the Samples form's.
 struct RangeLevelsResult : WindowsResult {
   uint64_t total_rows = 0;
 };
 inline X3Error range_levels(Context& ctx, const EncodedStream& s, const Parameters& params, const Buffer& d_sample_offsets,
                             const uint64_t* d_starts, const uint32_t* d_lens, size_t n_ranges, uint64_t bin_len,
                             uint64_t row_stride, x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status,
-                            RangeLevelsResult* res) {
+                            RangeLevelsResult* res, LevelSignal signal = LevelSignal::Samples) {
   if (!s.bytes.ok() || !s.frame_offsets.ok() || !d_sample_offsets.ok()) return X3Error::BadArg;
   const x3_params c = params.c_params();
-  int rc = x3_range_levels_dev(ctx.raw(), s.bytes.as<uint8_t>(), s.len, s.frame_offsets.as<uint64_t>(),
-                               d_sample_offsets.as<uint64_t>(), s.n_frames, &c,
-                               s.seg_blocks ? s.seg_index.as<uint64_t>() : nullptr, s.seg_blocks, d_starts, d_lens, n_ranges,
-                               bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status);
+  int rc = x3_signal_range_levels_dev(ctx.raw(), s.bytes.as<uint8_t>(), s.len, s.frame_offsets.as<uint64_t>(),
+                                      d_sample_offsets.as<uint64_t>(), s.n_frames, &c,
+                                      s.seg_blocks ? s.seg_index.as<uint64_t>() : nullptr, s.seg_blocks, d_starts, d_lens,
+                                      n_ranges, bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status,
+                                      static_cast<int>(signal));
   if (rc != X3_OK) return static_cast<X3Error>(rc);
   RangeLevelsResult r;
   rc = x3_range_levels_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status, &r.total_rows);
@@ -1015,12 +1017,13 @@ class Corpus {
   }
   // Range levels of entries (x3_corpus_range_levels_dev): the records of range w = samples [d_starts[w], d_starts[w] +
   // d_lens[w]) of entry d_entries[w]; bins, layout, capacity and result as device::range_levels; the arrays events() wrote go
-  // in as they are.  Waits for the call.
+  // in as they are.  signal: as there (x3_corpus_signal_range_levels_dev).  Waits for the call.
   X3Error range_levels(Context& ctx, const uint32_t* d_entries, const uint64_t* d_starts, const uint32_t* d_lens,
                        uint64_t n_ranges, uint64_t bin_len, uint64_t row_stride, x3_level* d_levels, uint64_t rows_cap,
-                       uint64_t* d_row_offsets, int32_t* d_status, RangeLevelsResult* res) const {
-    int rc = x3_corpus_range_levels_dev(ctx.raw(), raw_, d_entries, d_starts, d_lens, n_ranges, bin_len, row_stride, d_levels,
-                                        rows_cap, d_row_offsets, d_status);
+                       uint64_t* d_row_offsets, int32_t* d_status, RangeLevelsResult* res,
+                       LevelSignal signal = LevelSignal::Samples) const {
+    int rc = x3_corpus_signal_range_levels_dev(ctx.raw(), raw_, d_entries, d_starts, d_lens, n_ranges, bin_len, row_stride,
+                                               d_levels, rows_cap, d_row_offsets, d_status, static_cast<int>(signal));
     if (rc != X3_OK) return static_cast<X3Error>(rc);
     RangeLevelsResult r;
     rc = x3_range_levels_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status, &r.total_rows);

@@ -67,6 +67,7 @@ SYMBOLS = [
     "x3_level_quantiles_dev", "x3_corpus_level_quantiles_dev", "x3_level_quantiles_result",
     "x3_level_thresholds_dev", "x3_corpus_level_thresholds_dev", "x3_events_adaptive_dev", "x3_corpus_events_adaptive_dev",
     "x3_range_levels_dev", "x3_corpus_range_levels_dev", "x3_range_levels_result",
+    "x3_signal_range_levels_dev", "x3_corpus_signal_range_levels_dev",
     "x3_tune_candidate", "x3_tuner_create", "x3_tuner_add_dev", "x3_tuner_result", "x3_tuner_max_payloads",
     "x3_tuner_reset", "x3_tuner_destroy", "x3_tune", "x3_x3a_encode_tuned",
 ]
@@ -308,6 +309,8 @@ def lib():
     L.x3_corpus_events_adaptive_dev.argtypes = [vp, vp, vp, u64, u64, C.POINTER(EventRule), vp, vp, vp, vp, vp, u64, vp]
     L.x3_range_levels_dev.argtypes = [vp, vp, u64, vp, vp, u64, PP, vp, u32, vp, vp, u64, u64, u64, vp, u64, vp, vp]
     L.x3_corpus_range_levels_dev.argtypes = [vp, vp, vp, vp, vp, u64, u64, u64, vp, u64, vp, vp]
+    L.x3_signal_range_levels_dev.argtypes = [vp, vp, u64, vp, vp, u64, PP, vp, u32, vp, vp, u64, u64, u64, vp, u64, vp, vp, C.c_int]
+    L.x3_corpus_signal_range_levels_dev.argtypes = [vp, vp, vp, vp, vp, u64, u64, u64, vp, u64, vp, vp, C.c_int]
     L.x3_range_levels_result.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(i32), C.POINTER(u64)]
     L.x3_corpus_destroy.restype = None
     L.x3_synth.argtypes = [i32, u64, u64, u64, vp]
@@ -1124,6 +1127,21 @@ class Context:
         return lib().x3_corpus_range_levels_dev(self._h, corpus._h, d_entries, d_starts, d_lens, n_ranges, bin_len, row_stride,
                                                 d_levels, rows_cap, d_row_offsets, d_status)
 
+    def signal_range_levels_dev(self, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, params, d_starts, d_lens,
+                                n_ranges, bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status, d_seg_index=None,
+                                seg_blocks=0, signal=LEVEL_SIGNAL_SAMPLES):
+        """x3_signal_range_levels_dev: range_levels_dev of the samples (LEVEL_SIGNAL_SAMPLES) or of the stream's first
+        difference cut to the ranges (LEVEL_SIGNAL_DIFF); asynchronous, range_levels_result waits"""
+        return lib().x3_signal_range_levels_dev(self._h, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames,
+                                                C.byref(params), d_seg_index, seg_blocks, d_starts, d_lens, n_ranges, bin_len,
+                                                row_stride, d_levels, rows_cap, d_row_offsets, d_status, signal)
+
+    def corpus_signal_range_levels_dev(self, corpus, d_entries, d_starts, d_lens, n_ranges, bin_len, row_stride, d_levels,
+                                       rows_cap, d_row_offsets, d_status, signal=LEVEL_SIGNAL_SAMPLES):
+        """x3_corpus_signal_range_levels_dev: corpus_range_levels_dev with a signal; asynchronous"""
+        return lib().x3_corpus_signal_range_levels_dev(self._h, corpus._h, d_entries, d_starts, d_lens, n_ranges, bin_len,
+                                                       row_stride, d_levels, rows_cap, d_row_offsets, d_status, signal)
+
     def range_levels_result(self):
         """-> (rc, n_bad, first_bad, first_bad_status, total_rows) of the last range_levels_dev / corpus_range_levels_dev"""
         nb, fb, st, tot = C.c_uint64(0), C.c_uint64(0), C.c_int32(0), C.c_uint64(0)
@@ -1503,23 +1521,27 @@ class WindowSource:
         return _ranges_torch(self.ctx, lambda e, *a: self.ranges_into(*a), "x3_decode_ranges_dev", starts, lens, padded_to,
                              capacity, dtype or torch.int16)
 
-    def range_levels_into(self, d_starts, d_lens, n, bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status):
+    def range_levels_into(self, d_starts, d_lens, n, bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status,
+                          signal=LEVEL_SIGNAL_SAMPLES):
         """enqueue the level records of n ranges (device pointers: d_starts n x u64, d_lens n x u32, d_levels rows_cap x
-        x3_level, d_row_offsets (n + 1) x u64 or None when padded, d_status n x i32); row_stride 0: packed; -> rc;
-        Context.range_levels_result waits"""
-        return self.ctx.range_levels_dev(self.d_x3, self.x3_len, self.d_frame_offsets, self.d_sample_offsets, self.n_frames,
-                                         self.params, d_starts, d_lens, n, bin_len, row_stride, d_levels, rows_cap,
-                                         d_row_offsets, d_status, self.d_seg_index, self.seg_blocks)
+        x3_level, d_row_offsets (n + 1) x u64 or None when padded, d_status n x i32); row_stride 0: packed; signal: a
+        LEVEL_SIGNAL_* value; -> rc; Context.range_levels_result waits"""
+        return self.ctx.signal_range_levels_dev(self.d_x3, self.x3_len, self.d_frame_offsets, self.d_sample_offsets,
+                                                self.n_frames, self.params, d_starts, d_lens, n, bin_len, row_stride, d_levels,
+                                                rows_cap, d_row_offsets, d_status, self.d_seg_index, self.seg_blocks, signal)
 
-    def range_levels(self, starts, lens, bin_len, *, padded_to=None, capacity=None):
+    def range_levels(self, starts, lens, bin_len, *, padded_to=None, capacity=None, signal="samples"):
         """The x3_level records of the ranges [starts[w], starts[w] + lens[w]), bins of bin_len positions counted from each
         range's start (0: one record per range) -> (levels uint8 [rows, 32], row_offsets int64 [n + 1], status int32 [n]),
         torch tensors on the device (event_levels_view reads the records).  Packed (default): range w's records are
         levels[row_offsets[w]:row_offsets[w + 1]]; `capacity` records when given (ranges without room are ERR_BAD_ARG and
         row_offsets[-1] says what all need), otherwise one synchronising sum on the host.  padded_to: row w begins at
-        w * padded_to.  The tensors events() returns go in as they are.  The call waits for its result."""
-        return _range_levels_torch(self.ctx, lambda e, *a: self.range_levels_into(*a), "x3_range_levels_dev", starts, lens,
-                                   bin_len, padded_to, capacity)
+        w * padded_to.  The tensors events() returns go in as they are.  The call waits for its result.
+        signal: "samples", or "diff" -- the stream's first difference (as in levels()) cut to the ranges: the difference at
+        a range's first position is counted, its earlier sample lies in front of the range (x3_signal_range_levels_dev)"""
+        sig = level_signal(signal)
+        return _range_levels_torch(self.ctx, lambda e, *a: self.range_levels_into(*a, signal=sig), "x3_signal_range_levels_dev",
+                                   starts, lens, bin_len, padded_to, capacity)
 
     def levels_into(self, bin_len, d_levels, n_bins, d_frame_status=None, signal=LEVEL_SIGNAL_SAMPLES):
         """enqueue x3_signal_levels_dev over this source (device pointers; signal: a LEVEL_SIGNAL_* value); -> rc;
@@ -1841,19 +1863,22 @@ class Corpus:
         return _ranges_torch(self.ctx, self.ranges_into, "x3_corpus_ranges_dev", starts, lens, padded_to, capacity,
                              dtype or torch.int16, entries=entries)
 
-    def range_levels_into(self, d_entries, d_starts, d_lens, n, bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status):
+    def range_levels_into(self, d_entries, d_starts, d_lens, n, bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status,
+                          signal=LEVEL_SIGNAL_SAMPLES):
         """enqueue the level records of n ranges of entries (device pointers: d_entries n x u32, the rest as
         WindowSource.range_levels_into); -> rc; Context.range_levels_result waits"""
         if self._h is None:
             raise ValueError("the corpus is closed")
-        return self.ctx.corpus_range_levels_dev(self, d_entries, d_starts, d_lens, n, bin_len, row_stride, d_levels, rows_cap,
-                                                d_row_offsets, d_status)
+        return self.ctx.corpus_signal_range_levels_dev(self, d_entries, d_starts, d_lens, n, bin_len, row_stride, d_levels,
+                                                       rows_cap, d_row_offsets, d_status, signal)
 
-    def range_levels(self, entries, starts, lens, bin_len, *, padded_to=None, capacity=None):
+    def range_levels(self, entries, starts, lens, bin_len, *, padded_to=None, capacity=None, signal="samples"):
         """The x3_level records of the ranges [starts[w], starts[w] + lens[w]) of entry entries[w] -> (levels, row_offsets,
-        status) as WindowSource.range_levels; the tensors events() returns go in as they are."""
-        return _range_levels_torch(self.ctx, self.range_levels_into, "x3_corpus_range_levels_dev", starts, lens, bin_len,
-                                   padded_to, capacity, entries=entries)
+        status) as WindowSource.range_levels; the tensors events() returns go in as they are.  signal: as there -- the
+        entry's first difference cut to the ranges; no difference crosses from one entry into the next"""
+        sig = level_signal(signal)
+        return _range_levels_torch(self.ctx, lambda *a: self.range_levels_into(*a, signal=sig),
+                                   "x3_corpus_signal_range_levels_dev", starts, lens, bin_len, padded_to, capacity, entries=entries)
 
     def levels_rows(self, bin_len):
         """-> row_first np.uint64 [n_entries + 1]: entry e's rows of levels() are [row_first[e], row_first[e + 1])"""
