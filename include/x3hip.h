@@ -295,6 +295,9 @@ int x3_decode_stream(x3_ctx* ctx, const uint8_t* x3, uint64_t len, const x3_para
  * as a mono block against its own channel; header byte 3 = n_channels, `samples` = samples per channel.  With
  * n_channels = 1 the bytes are x3_encode's.  wavs[k] = channel k, n samples each (host memory).  n_channels <= 8; a frame
  * whose payload would pass the 24 KB a reader takes is X3_ERR_FRAME_LENGTH (choose shorter frames).
+ * On BYTE_WRITER_INSUFFICIENT_MEMORY x3_encode_mc keeps x3_encode's prefix guarantee: every frame that fits is in out,
+ * complete and in place (with the pad byte in front of the first one), *out_pos = the end of the last of them, and
+ * nothing behind it or in front of start_pos is touched.
  * x3_decode_stream_mc walks, checks and decodes such a stream (x3_decode_stream's rules; a frame must announce exactly
  * n_channels) into wavs[k][0 .. *n_samples). */
 int x3_encode_mc(x3_ctx* ctx, const int16_t* const* wavs, uint32_t n_channels, uint64_t n, const x3_params* p, uint8_t* out,

@@ -7,6 +7,7 @@ import pytest
 
 import oracle_lib as O
 import x3hip
+from x3_cases import draw_codes, frame_offsets, refresh_crcs
 
 pytestmark = pytest.mark.gpu
 
@@ -129,14 +130,14 @@ def test_damaged_and_mismatched_streams(ctx):
 def test_random_multichannel_sweep(ctx):
     """seeded sweep: channels x geometry x codes/thresholds x content x damage, GPU == oracle (status, bytes, samples)"""
     rng = np.random.default_rng(2026)
+    damaged = 0
     for trial in range(60):
         n_ch = int(rng.integers(1, 9))
         bl = int(rng.choice([20, 20, 20, 7, 33, 60]))
         bpf = int(rng.integers(1, 120))
         n = int(rng.integers(1, 4 * bl * bpf + 50))
-        p = x3hip.Params.default(); po = O.Params.default()
-        for q in (p, po):
-            q.block_len, q.blocks_per_frame = bl, bpf
+        codes, thr = draw_codes(rng)
+        p, po = x3hip.Params.make(bl, bpf, codes, thr), O.Params.make(bl, bpf, codes, thr)
         wavs = []
         for k in range(n_ch):
             kind = int(rng.integers(0, 4))
@@ -158,10 +159,16 @@ def test_random_multichannel_sweep(ctx):
             continue
         assert np.array_equal(x_g[start:], x_o[start:]) and st_g.tolist() == st_o.tolist(), (trial, n_ch, bl, bpf, n)
         s = x_o[start + (start & 1):].copy()
-        if trial % 3 == 1 and s.size > 40:
-            s[int(rng.integers(0, s.size))] ^= 1 << int(rng.integers(0, 8))
-        elif trial % 3 == 2 and s.size > 40:
-            s = s[: int(rng.integers(1, s.size))]
+        if trial % 3 and s.size > 40:
+            damaged += 1
+            if damaged % 2 == 0:   # every second damaged trial: a bit flip in a frame whose CRCs are made good again
+                at = int(rng.integers(0, s.size))
+                s[at] ^= 1 << int(rng.integers(0, 8))
+                refresh_crcs(s, max(o for o in frame_offsets(x_o[start + (start & 1):]) if o <= at))
+            elif trial % 3 == 1:
+                s[int(rng.integers(0, s.size))] ^= 1 << int(rng.integers(0, 8))
+            else:
+                s = s[: int(rng.integers(1, s.size))]
         got = ctx.decode_stream_mc(s, n_ch, p, wav_cap=n + 8)
         want = O.decode_stream_mc(s, n_ch, po, wav_cap=n + 8)
         assert (got[0], got[2], got[3]) == (want[0], want[2], want[3]), (trial, got[0], got[2:], want[0], want[2:])

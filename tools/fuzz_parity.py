@@ -531,14 +531,14 @@ def fam_w(rng, tag):
 
 def fam_m(rng, tag):
     """multi-channel extension: x3_encode_mc / x3_decode_stream_mc == the oracle's x3o_encode_mc / x3o_decode_stream_mc over
-    channels x geometry x content x start position, intact, damaged and truncated streams, wrong channel counts"""
+    channels x geometry x codes / thresholds x content x start position, intact, damaged (CRCs refreshed or not) and
+    truncated streams, wrong channel counts"""
     n_ch = int(rng.integers(1, 9))
     bl = int(rng.choice([20, 20, 20, 7, 33, 60, 1]))
     bpf = int(rng.integers(1, 200))
     n = int(rng.integers(1, 5 * bl * bpf + 50)) if rng.random() < 0.9 else int(rng.integers(1, 4))
-    p, po = x3hip.Params.default(), O.Params.default()
-    for q in (p, po):
-        q.block_len, q.blocks_per_frame = bl, bpf
+    codes, thr = draw_codes(rng)
+    p, po = x3hip.Params.make(bl, bpf, codes, thr), O.Params.make(bl, bpf, codes, thr)
     wavs = [content(rng, n) for _ in range(n_ch)]
     start = int(rng.integers(0, 5))
     cap = n_ch * O.encode_bound(n, po) + start + 64   # (the same capacity on both sides: running out of it is part of the result)
@@ -551,7 +551,10 @@ def fam_m(rng, tag):
     s = x_o[start + (start & 1):].copy()
     what = int(rng.integers(0, 4))
     if what == 1 and s.size > 40:
-        s[int(rng.integers(0, s.size))] ^= 1 << int(rng.integers(0, 8))
+        at = int(rng.integers(0, s.size))
+        s[at] ^= 1 << int(rng.integers(0, 8))
+        if rng.random() < 0.5:       # CRCs made good again: the decoder, not the check pass, meets the damage
+            refresh_crcs(s, max(o for o in frame_offsets(x_o[start + (start & 1):]) if o <= at))
     elif what == 2 and s.size > 40:
         s = s[: int(rng.integers(1, s.size))]
     ask = n_ch if what != 3 else int(rng.integers(1, 9))

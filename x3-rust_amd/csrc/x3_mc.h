@@ -116,6 +116,37 @@ extern "C" int x3_encode_mc(x3_ctx* c, const int16_t* const* wavs, uint32_t n_ch
     if (rc != X3_RETRY_TWO_PASS) break;
     if (stats) std::memset(stats, 0, 6 * sizeof(uint64_t));
   }
+  if (rc == X3_ERR_BYTE_WRITER_INSUFFICIENT_MEMORY) {
+    // x3_encode's prefix (encode_host, x3_encode.hip): every frame that fits, complete and in place, the pad byte in front
+    // of the first one, *out_pos = the end of the last of them, nothing behind it touched.  The frame index holds every
+    // frame's offset as if there had been room.  The one-pass kernel has written exactly the frames that fit; the two-pass
+    // emission writes nothing once the scan has seen the overflow, so there the frames that fit are encoded again on
+    // their own.  (An error path: nobody times it.)
+    const bool one_pass = c->last_enc_gen == 1;
+    std::vector<uint64_t> offs(F + 1);
+    HIPCHK(c, hipMemcpyAsync(offs.data(), d_off, offs.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    uint64_t end = start_pos, first = start_pos, fit = 0;
+    if ((start_pos & 1ull) && start_pos < out_cap) end = first = start_pos + 1;
+    for (; fit < F; ++fit) {
+      if (offs[fit] != end || offs[fit + 1] < offs[fit] + 22 || offs[fit + 1] > out_cap) break;
+      end = offs[fit + 1];
+    }
+    if (fit && !one_pass) {
+      uint64_t end2 = 0;
+      const int rc2 = x3_encode_mc(c, wavs, n_ch, fit * spf, p, out, out_cap, start_pos, &end2, nullptr);
+      if (rc2 || end2 != end) {
+        if (out_pos) *out_pos = start_pos;
+        return rc2 ? rc2 : X3_ERR_BAD_ARG;   // (the second encode disagrees with the first about the sizes: not reached)
+      }
+    } else if (end > first) {
+      HIPCHK(c, hipMemcpy(out + first, (uint8_t*)c->out.p + first, end - first, hipMemcpyDeviceToHost));
+    }
+    if (first > start_pos) out[start_pos] = 0;   // writer.align's pad byte (encoder.rs:182)
+    c->needed_pos = pos;
+    if (out_pos) *out_pos = end;
+    return rc;
+  }
   if (out_pos) *out_pos = pos;
   if (rc) return rc;
   if (pos > start_pos)
