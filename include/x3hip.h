@@ -828,6 +828,37 @@ int x3_corpus_signal_levels_dev(x3_ctx* ctx, const x3_corpus* corpus, uint64_t b
                                 int32_t* d_frame_status, int signal);
 #define X3_LEVEL_SIGNAL_SAMPLES 0   /* the signals of x3_signal_levels_dev */
 #define X3_LEVEL_SIGNAL_DIFF 1
+/* ---- FIR LEVELS (no counterpart in the reference): the levels of an INTEGER FIR-FILTERED signal -- a band picked in front
+ * of the detection chain at no extra read and no sample buffer.  `fir` is a host struct, read at
+ * the call.  For a position i of a stream or corpus entry:
+ *     acc  = sum over t < T of c[t] * x[i - t], in int32;
+ *     y[i] = clamp(acc >> shift, -32768, 32767), where >> is arithmetic (floor).
+ *   The call is X3_ERR_BAD_ARG with nothing enqueued unless 1 <= T <= 8, shift <= 15 and sum |c[t]| <= 32768.  That bound
+ * on the taps gives |acc| <= 32768 * 32768 = 2^30: 32-bit arithmetic is exact.  A NULL fir is refused first, the way an
+ * unknown signal is; everything else is refused as in x3_levels_dev / x3_corpus_levels_dev.
+ *   Positions, bins, n_bins * bin_len, frame statuses, "every record is written", x3_levels_result, the pending slot and
+ * the option "last_levels_replays" are those of the levels calls.
+ *   THE HISTORY RULE.  Position i adds y[i] to its bin if and only if all T positions i - T + 1 .. i exist in the same
+ * stream or entry (i >= T - 1) and every one of them lies in a frame with status 0.  Otherwise the position adds nothing
+ * and n is not incremented: a failed frame takes its own positions and the T - 1 positions behind it, and a clean stream
+ * or entry of N samples has records whose n sum to max(0, N - T + 1).  No history crosses from one entry into the next.
+ *   Two identities follow: {T = 1, c = {1}, shift = 0} gives the records of X3_LEVEL_SIGNAL_SAMPLES, and
+ * {T = 2, c = {1, -1}, shift = 0} those of X3_LEVEL_SIGNAL_DIFF, field for field.
+ *   y is an int16 signal like any other: the records go into the events, quantiles, thresholds and ranges calls unchanged.
+ * The segment index stays a hint and nothing new rests on it: a stretch forms only the outputs whose whole history it
+ * decoded itself, and the positions at a stretch's front are formed behind it from the stretches' first and last samples.
+ * That takes a workspace of 32 bytes per (frame, stretch), allocated at the first FIR call of a size and kept. */
+typedef struct x3_level_fir {
+  uint32_t n_taps;      /* T: 1 .. 8 */
+  uint32_t shift;       /* 0 .. 15 */
+  int16_t  taps[8];     /* c[0 .. T-1]; entries at and behind T are ignored */
+} x3_level_fir;
+int x3_fir_levels_dev(x3_ctx* ctx, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
+                      const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
+                      const uint64_t* d_seg_index, uint32_t seg_blocks, uint64_t bin_len,
+                      x3_level* d_levels, uint64_t n_bins, int32_t* d_frame_status, const x3_level_fir* fir);
+int x3_corpus_fir_levels_dev(x3_ctx* ctx, const x3_corpus* corpus, uint64_t bin_len, x3_level* d_levels, uint64_t n_rows,
+                             int32_t* d_frame_status, const x3_level_fir* fir);
 /* ---- EVENTS (no counterpart in the reference): runs of loud bins of level records as ranges (entry, start, len), found on
  * the device -- the link between the levels calls and the ranges calls, with no host trip.
  *   Row b of d_levels is a bin of bin_len positions as x3_levels_dev / x3_corpus_levels_dev write it.  A bin is HOT when

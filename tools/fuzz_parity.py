@@ -20,7 +20,10 @@ Families: (e) the single-pass encoders on block_len 20 with mixed content, many 
           corpus entries, GPU == tests/diff_levels_ref.py on the oracle's frame verdicts (not in the default family set);
           (l) family (r) on the first difference (x3_signal_range_levels_dev, X3_LEVEL_SIGNAL_DIFF), with starts drawn to
           frame and stretch boundaries as well (lead frames, seeds from the index), GPU == tests/signal_range_levels_ref.py
-          (not in the default family set)."""
+          (not in the default family set); (i) family (h) behind an integer FIR filter (x3_fir_levels_dev /
+          x3_corpus_fir_levels_dev): random taps (1 .. 8, sum |c| <= 32768) and shifts as well, frames and stretches shorter
+          than the taps among them, GPU == tests/fir_levels_ref.py; {1} against x3_levels_dev byte for byte (not in the
+          default family set)."""
 import argparse, ctypes as C, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "x3-rust_amd"))
@@ -941,12 +944,35 @@ fams["r"] = fam_r
 fams["l"] = lambda rng, tag: fam_r(rng, tag, diff=True)
 
 
-def fam_h(rng, tag):
+def draw_fir(rng):
+    """random taps and shift of an x3hip.Fir: 1 .. 8 taps, small or as large as sum |c| <= 32768 lets them be"""
+    T = int(rng.integers(1, 9))
+    if rng.random() < 0.5:
+        taps = rng.integers(-4, 5, T)
+    else:
+        taps = rng.integers(-32768, 32768, T)
+        taps[rng.random(T) < 0.3] = 0
+        while int(np.abs(taps).sum()) > 32768:
+            taps = taps // 2
+    return x3hip.Fir([int(c) for c in taps], int(rng.choice([0, 0, 1, 7, 15, int(rng.integers(0, 16))])))
+
+
+def fam_h(rng, tag, fir=False):
     """signal levels: the DIFF records and frame statuses of a random stream -- any geometry, damaged frames, a damaged or
     walk-built index or none -- against diff_levels_ref on the oracle's frame verdicts; then the same frames as a corpus of
     random entries, where no difference may cross from one entry into the next; SAMPLES against x3_levels_dev byte for byte"""
     import diff_levels_ref as DL
     import levels_ref as LR
+    if fir:   # family (i): the same behind a drawn filter, against fir_levels_ref
+        import fir_levels_ref as FR
+        signal = draw_fir(rng)
+        ref_stream = lambda fr, st, so_, bl, nb: FR.fir_levels(fr, st, so_, bl, nb, signal.taps, signal.shift)
+        ref_corpus = lambda ref, bl: FR.corpus_fir_levels(ref, bl, signal.taps, signal.shift)
+        same_as = x3hip.Fir([1])
+    else:
+        signal, same_as = "diff", "samples"
+        ref_stream = lambda fr, st, so_, bl, nb: DL.signal_levels(fr, st, so_, bl, nb, DL.DIFF)
+        ref_corpus = lambda ref, bl: DL.corpus_signal_levels(ref, bl, DL.DIFF)
     r = rng.random()
     if r < 0.5:
         p = x3hip.Params.default()
@@ -1008,6 +1034,8 @@ def fam_h(rng, tag):
         index = "walk" if rng.random() < 0.5 else "decode"
         if index == "walk" and sb == 0:
             sb = 8
+        if sb == 2:   # (2 blocks per entry is no multiple of four: every index call refuses it, under either family;
+            sb = 8    #  the draw stays so that the trials of a seed keep their numbers)
         src = x3hip.WindowSource(ctx, bad, p, seg_blocks=sb, frame_offsets=d_off, n_frames=F, index=index)
         d.extend(src._own); src._own = []
         assert src.total == n, (tag, "total", src.total, n)
@@ -1024,12 +1052,12 @@ def fam_h(rng, tag):
                 else:
                     idx[sel] = rng.integers(0, 1 << 49, int(sel.sum()), dtype=np.uint64)
             ctx.upload(src.d_seg_index, idx)
-        got, st = src.levels(bin_len, n_bins, signal="diff")
+        got, st = src.levels(bin_len, n_bins, signal=signal)
         assert st.tolist() == statuses, (tag, "statuses", st.tolist(), statuses)
-        want = DL.signal_levels(frames, statuses, so[:-1], bin_len, n_bins, DL.DIFF)
+        want = ref_stream(frames, statuses, so[:-1], bin_len, n_bins)
         for k in LR.LEVEL_DTYPE.names:
             assert np.array_equal(got[k], want[k]), (tag, "stream", k, bin_len, n_bins, np.flatnonzero(got[k] != want[k])[:8].tolist())
-        same, _ = src.levels(bin_len, n_bins, signal="samples")
+        same, _ = src.levels(bin_len, n_bins, signal=same_as)
         old, _ = src.levels(bin_len, n_bins)
         assert same.tobytes() == old.tobytes(), (tag, "samples")
         # the same bytes as a corpus: the frames cut into entries at random frame boundaries
@@ -1044,11 +1072,11 @@ def fam_h(rng, tag):
                 return
             try:
                 if corpus.entries["n_frames"].tolist() == [b - a for a, b in zip(cuts[:-1], cuts[1:])]:
-                    rows, rf, cst = corpus.levels(bin_len, signal="diff")
+                    rows, rf, cst = corpus.levels(bin_len, signal=signal)
                     ref = []
                     for a, b in zip(cuts[:-1], cuts[1:]):
                         ref.append((frames[a:b], statuses[a:b], [so[f] - so[a] for f in range(a, b)], so[b] - so[a]))
-                    wrows, wrf = DL.corpus_signal_levels(ref, bin_len, DL.DIFF)
+                    wrows, wrf = ref_corpus(ref, bin_len)
                     assert np.array_equal(rf, wrf) and cst.tolist() == statuses, (tag, "corpus layout")
                     for k in LR.LEVEL_DTYPE.names:
                         assert np.array_equal(rows[k], wrows[k]), (tag, "corpus", k, bin_len, cuts, np.flatnonzero(rows[k] != wrows[k])[:8].tolist())
@@ -1060,6 +1088,7 @@ def fam_h(rng, tag):
 
 
 fams["h"] = fam_h
+fams["i"] = lambda rng, tag: fam_h(rng, tag, fir=True)
 
 
 def run(seed=1, minutes=None, trials=None, families="egdbaf", only=-1, context=None):

@@ -1321,10 +1321,12 @@ size_t levels_carve(char* base, uint64_t F, uint64_t n_rows, uint64_t fix_waves,
 // give every frame its position, its records and its row count.  n_ent: entries of a corpus call (their row prefix lives
 // in the workspace), 0 for a stream.  signal: X3_LEVEL_SIGNAL_SAMPLES, or X3_LEVEL_SIGNAL_DIFF -- the other instance of the
 // accumulate and fix-up kernels, which leave every good frame's last sample in the workspace, and the seam kernel behind them.
+// fir (checked: levels_fir_taps) instead of a signal: the X3LevFir instance, which leaves an edge record per (frame, stretch)
+// in a workspace of its own (fir_ws; lev_ws keeps its layout), and x3_levels_fir_seam_kernel behind the merge.
 template <class Prep>
 static int levels_launch(x3_ctx* c, const FrameSource& s, uint64_t bin_len, x3_level* d_levels, uint64_t n_rows,
-                         int32_t* d_frame_status, uint64_t n_ent, int signal, Prep prep) {
-  const bool diff = signal == X3_LEVEL_SIGNAL_DIFF;
+                         int32_t* d_frame_status, uint64_t n_ent, int signal, Prep prep, const X3FirTaps* fir = nullptr) {
+  const bool diff = !fir && signal == X3_LEVEL_SIGNAL_DIFF;
   HIPCHK(c, hipSetDevice(c->device));
   const uint64_t F = s.F, cap = n_rows + F;
   const uint32_t scratch_per = levels_scratch_per(s.dp.block_len);
@@ -1333,6 +1335,7 @@ static int levels_launch(x3_ctx* c, const FrameSource& s, uint64_t bin_len, x3_l
   int rc;
   if ((rc = ensure(c, c->lev_ws, levels_carve(nullptr, F, n_rows, fix_waves, scratch_per, n_ent, &w)))) return rc;
   levels_carve((char*)c->lev_ws.p, F, n_rows, fix_waves, scratch_per, n_ent, &w);
+  if (fir && (rc = ensure(c, c->fir_ws, (size_t)(F * s.nseg) * sizeof(X3FirEdge)))) return rc;
   hipLaunchKernelGGL(x3_levels_init_kernel, dim3(grid_for(n_rows + cap, 256)), dim3(256), 0, c->stream, d_levels, n_rows, w.rows,
                      cap, w.sum);
   hipLaunchKernelGGL(x3_levels_check_kernel, dim3(grid_for(F, 4)), dim3(256), 0, c->stream, s.d_x3, s.x3_len, s.d_frame_offsets,
@@ -1348,13 +1351,18 @@ static int levels_launch(x3_ctx* c, const FrameSource& s, uint64_t bin_len, x3_l
                        s.d_frame_offsets, F, s.dp, bin_len, (const X3LevFrame*)w.frames, w.fst, d_levels, d_frame_status,
                        w.scratch, scratch_per, w.sum, tail);
   };
-  if (diff) decode(X3LevDiff{}, w.tail);
+  if (fir) decode(X3LevFir{}, X3LevFirTail{*fir, (X3FirEdge*)c->fir_ws.p, s.nseg});
+  else if (diff) decode(X3LevDiff{}, w.tail);
   else decode(X3LevSamples{}, X3LevNoTail{});
   hipLaunchKernelGGL(x3_levels_merge_kernel, dim3(grid_for(cap, 256)), dim3(256), 0, c->stream, (const X3LevFrame*)w.frames,
                      (const unsigned long long*)w.row, F, cap, (const x3_level*)w.rows, (const int32_t*)w.fst, d_levels);
   if (diff && F > 1)
     hipLaunchKernelGGL(x3_levels_seam_kernel, dim3(grid_for(F, 256)), dim3(256), 0, c->stream, s.d_x3, s.x3_len, s.d_frame_offsets,
                        F, bin_len, (const X3LevFrame*)w.frames, (const int32_t*)w.fst, (const int32_t*)w.tail, d_levels);
+  if (fir && fir->T > 1)
+    hipLaunchKernelGGL(x3_levels_fir_seam_kernel, dim3(grid_for(F * s.nseg, 256)), dim3(256), 0, c->stream, F, s.dp.block_len, s.idx,
+                       s.seg_blocks, s.nseg, bin_len, (const X3LevFrame*)w.frames, (const int32_t*)w.fst,
+                       (const X3FirEdge*)c->fir_ws.p, s.nseg, *fir, d_levels);
   HIPCHK(c, hipGetLastError());
   c->levels.pending = true;
   c->levels.count = F;
@@ -1364,11 +1372,24 @@ static int levels_launch(x3_ctx* c, const FrameSource& s, uint64_t bin_len, x3_l
 
 static bool levels_signal_ok(int signal) { return signal == X3_LEVEL_SIGNAL_SAMPLES || signal == X3_LEVEL_SIGNAL_DIFF; }
 
-extern "C" int x3_signal_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
-                                    const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
-                                    const uint64_t* d_seg_index, uint32_t seg_blocks, uint64_t bin_len, x3_level* d_levels,
-                                    uint64_t n_bins, int32_t* d_frame_status, int signal) {
-  if (!c || !levels_signal_ok(signal) || !levels_args_ok(c, d_levels, n_bins, d_frame_status)) return X3_ERR_BAD_ARG;
+// x3_level_fir as the kernels take it, the taps at and behind T zero; false: not 1 <= T <= 8, shift <= 15, sum |c| <= 32768
+static bool levels_fir_taps(const x3_level_fir* fir, X3FirTaps* k) {
+  if (!fir || fir->n_taps < 1 || fir->n_taps > X3L_FIR_TAPS || fir->shift > 15) return false;
+  uint32_t mag = 0;
+  for (uint32_t t = 0; t < X3L_FIR_TAPS; ++t) {
+    k->c[t] = t < fir->n_taps ? fir->taps[t] : 0;
+    mag += (uint32_t)std::abs(k->c[t]);
+  }
+  k->T = fir->n_taps, k->shift = fir->shift;
+  return mag <= 32768u;
+}
+
+// the stream form of the levels calls behind the check of the signal or the taps (fir != NULL: the FIR call)
+static int stream_levels_call(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
+                              const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p, const uint64_t* d_seg_index,
+                              uint32_t seg_blocks, uint64_t bin_len, x3_level* d_levels, uint64_t n_bins, int32_t* d_frame_status,
+                              int signal, const X3FirTaps* fir) {
+  if (!levels_args_ok(c, d_levels, n_bins, d_frame_status)) return X3_ERR_BAD_ARG;
   FrameSource s;
   const int rc = stream_source(d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, p, d_seg_index, seg_blocks, &s);
   if (rc) return rc;
@@ -1376,7 +1397,26 @@ extern "C" int x3_signal_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_
                        [&](dim3 grid, unsigned long long*, const int32_t* fst, X3LevFrame* frames, uint32_t* cnt) {
                          hipLaunchKernelGGL(x3_levels_prep_kernel, grid, dim3(256), 0, c->stream, d_sample_offsets, n_frames,
                                             bin_len, n_bins, fst, frames, cnt);
-                       });
+                       }, fir);
+}
+
+extern "C" int x3_signal_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
+                                    const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
+                                    const uint64_t* d_seg_index, uint32_t seg_blocks, uint64_t bin_len, x3_level* d_levels,
+                                    uint64_t n_bins, int32_t* d_frame_status, int signal) {
+  if (!c || !levels_signal_ok(signal)) return X3_ERR_BAD_ARG;
+  return stream_levels_call(c, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, p, d_seg_index, seg_blocks, bin_len,
+                            d_levels, n_bins, d_frame_status, signal, nullptr);
+}
+
+extern "C" int x3_fir_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
+                                 const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
+                                 const uint64_t* d_seg_index, uint32_t seg_blocks, uint64_t bin_len, x3_level* d_levels,
+                                 uint64_t n_bins, int32_t* d_frame_status, const x3_level_fir* fir) {
+  X3FirTaps k;
+  if (!c || !levels_fir_taps(fir, &k)) return X3_ERR_BAD_ARG;
+  return stream_levels_call(c, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, p, d_seg_index, seg_blocks, bin_len,
+                            d_levels, n_bins, d_frame_status, X3_LEVEL_SIGNAL_SAMPLES, &k);
 }
 
 extern "C" int x3_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
@@ -2051,7 +2091,7 @@ static void corpus_row_prefix(x3_ctx* c, const x3_corpus* k, uint64_t bin_len, u
 }
 
 static int corpus_levels_call(x3_ctx* c, const x3_corpus* k, const char* entry, uint64_t bin_len, x3_level* d_levels,
-                              uint64_t n_rows, int32_t* d_frame_status, int signal) {
+                              uint64_t n_rows, int32_t* d_frame_status, int signal, const X3FirTaps* fir = nullptr) {
   if (!c || !k || !levels_signal_ok(signal) || !levels_args_ok(c, d_levels, n_rows, d_frame_status)) return X3_ERR_BAD_ARG;
   FrameSource s;
   X3EvRows q;
@@ -2064,7 +2104,7 @@ static int corpus_levels_call(x3_ctx* c, const x3_corpus* k, const char* entry, 
                          hipLaunchKernelGGL(x3_corpus_levels_prep_kernel, grid, dim3(256), 0, c->stream,
                                             k->d_ent, k->n, (const unsigned long long*)row_first,
                                             s.d_sample_offsets, s.F, bin_len, n_rows, fst, frames, cnt);
-                       });
+                       }, fir);
 }
 
 extern "C" int x3_corpus_levels_dev(x3_ctx* c, const x3_corpus* k, uint64_t bin_len, x3_level* d_levels, uint64_t n_rows,
@@ -2075,6 +2115,14 @@ extern "C" int x3_corpus_levels_dev(x3_ctx* c, const x3_corpus* k, uint64_t bin_
 extern "C" int x3_corpus_signal_levels_dev(x3_ctx* c, const x3_corpus* k, uint64_t bin_len, x3_level* d_levels, uint64_t n_rows,
                                            int32_t* d_frame_status, int signal) {
   return corpus_levels_call(c, k, "x3_corpus_signal_levels_dev", bin_len, d_levels, n_rows, d_frame_status, signal);
+}
+
+extern "C" int x3_corpus_fir_levels_dev(x3_ctx* c, const x3_corpus* k, uint64_t bin_len, x3_level* d_levels, uint64_t n_rows,
+                                        int32_t* d_frame_status, const x3_level_fir* fir) {
+  X3FirTaps taps;
+  if (!c || !levels_fir_taps(fir, &taps)) return X3_ERR_BAD_ARG;
+  return corpus_levels_call(c, k, "x3_corpus_fir_levels_dev", bin_len, d_levels, n_rows, d_frame_status, X3_LEVEL_SIGNAL_SAMPLES,
+                            &taps);
 }
 
 // ------------------------------------------------------------------------------------------------

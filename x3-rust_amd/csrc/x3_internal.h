@@ -153,6 +153,7 @@ struct x3_ctx {
   DevBuf idx_cand, idx_keys, idx_vals, idx_J, idx_S, idx_L, idx_sum;  // x3_index_dev scratch
   DevBuf idx_wg, idx_sorted, idx_scan;  // ... of its fast path: candidates per scanning workgroup, in order, the scans
   DevBuf lev_ws;   // x3_levels_dev / x3_corpus_levels_dev: verdicts, plans, the frames' partial rows, replay scratch, summary (x3_levels_kernel.h)
+  DevBuf fir_ws;   // x3_fir_levels_dev / x3_corpus_fir_levels_dev only, beside lev_ws: an edge record per (frame, stretch) (X3FirEdge, x3_levels_kernel.h)
   DevBuf ev_ws;    // x3_events_dev / x3_corpus_events_dev: row flags, tile totals, run tables, piece scan, summary, row prefix (x3_events_kernel.h)
   DevBuf q_ws;     // x3_level_quantiles_dev / x3_level_thresholds_dev and their corpus forms: (key, entry) per row, histograms, select state, summary, row prefix (x3_quantiles_kernel.h)
   DevBuf rlev_ws;  // x3_range_levels_dev / x3_corpus_range_levels_dev: plans, scans, verdicts, pairs, their partial rows, replay scratch, summary (x3_range_levels_kernel.h)

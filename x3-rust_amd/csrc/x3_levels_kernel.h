@@ -26,8 +26,9 @@
 //  x3_levels_fixup_kernel    -- a wave per frame: flagged frames through the reference's reader; d_frame_status, summary
 //  x3_levels_merge_kernel    -- a lane per partial row; rows of one bin that lie side by side in a wave are joined first
 //  x3_levels_seam_kernel     -- X3_LEVEL_SIGNAL_DIFF only: a lane per frame, the one difference across the frame's front seam
+//  x3_levels_fir_seam_kernel -- x3_fir_levels_dev only: a lane per (frame, stretch), the stretch's first T - 1 positions
 // The accumulate and fix-up kernels are templates over the SIGNAL, what a position adds to its bin: X3LevSamples (the levels
-// calls) or X3LevDiff (x3_signal_levels_dev).
+// calls), X3LevDiff (x3_signal_levels_dev) or X3LevFir (x3_fir_levels_dev).
 //
 // What the range levels, events and quantiles kernels (x3_range_levels_kernel.h, x3_events_kernel.h, x3_quantiles_kernel.h)
 // share with these: X3L_IDENTITY, the record of an empty bin; X3LevAcc, a record in registers (load, record, join);
@@ -154,15 +155,16 @@ struct X3LevBinner {
 // the first sample a lane sees without a seed (sample 0 of a frame) adds nothing: that difference crosses the frame's seam
 // and is x3_levels_seam_kernel's.  seed(v): the sample in front of a stretch (x3w_stretch's watch).  Tail: the kernels'
 // last argument, the per-frame array of last samples that only X3LevDiff has.
+// kState: the signal has registers of its own and is the caller's, at x3l_bin_samples' `sig`; kFir: it is X3LevFir (below).
 struct X3LevNoTail {};
 struct X3LevSamples {
-  static constexpr bool kDiff = false;
+  static constexpr bool kDiff = false, kFir = false, kState = false;
   using Tail = X3LevNoTail;
   __device__ __forceinline__ void add(X3LevAcc& a, uint32_t v) { a.add(v); }
 };
 __device__ __forceinline__ int32_t x3l_diff(int32_t s, int32_t prev) { return min(max(s - prev, -32768), 32767); }
 struct X3LevDiff {
-  static constexpr bool kDiff = true;
+  static constexpr bool kDiff = true, kFir = false, kState = true;
   using Tail = int32_t*;   // per frame: its last sample
   int32_t prev = 0;
   bool have = false;
@@ -191,6 +193,64 @@ struct X3LevDiffWatch {
   __device__ __forceinline__ void end(uint32_t v) const { *at = (int32_t)(int16_t)(uint16_t)v; }
 };
 
+// X3LevFir (x3_fir_levels_dev): y = clamp((sum over t < T of c[t] * x[i - t]) >> shift, 16 bits).  The
+// taps come uniform from a kernel argument, those at and behind T zero, so that one instance serves every T; sum |c| <= 32768
+// (the host's check) keeps the sum inside 2^30, and taps and samples inside the 24 bits of the multiply.  The lane holds the
+// seven samples in front of the current one in registers and counts the samples it has seen: a position adds y once the lane
+// has decoded T samples of its own.  It takes no seed: nothing rests on the index's sample field.  The positions a lane cannot
+// form -- the first T - 1 of its stretch -- are x3_levels_fir_seam_kernel's, from the EDGE RECORD the lane leaves: the
+// stretch's first and last min(n, 7) samples and n.  The heads are stored as they pass, the rest by end().
+#define X3L_FIR_TAPS 8
+#define X3L_FIR_HIST (X3L_FIR_TAPS - 1)
+struct X3FirTaps {
+  int32_t c[X3L_FIR_TAPS];   // c[t] = 0 for t >= T
+  uint32_t T, shift;
+};
+struct X3FirEdge {   // per (frame, stretch); a replayed frame is one stretch, at its stretch 0
+  int16_t head[X3L_FIR_HIST];   // sample k of the stretch, k < min(n, 7)
+  int16_t tail[X3L_FIR_HIST];   // sample n - 1 - k of the stretch, k < min(n, 7)
+  uint32_t n;                   // the stretch's samples (0: the stretch in front runs through its blocks)
+};
+static_assert(sizeof(X3FirEdge) == 32, "an edge record is 32 bytes");
+struct X3LevFirTail {   // the kernels' last argument
+  X3FirTaps k;
+  X3FirEdge* edges;   // F * stride records
+  uint32_t stride;    // records per frame: the stretches of a frame at most
+};
+__device__ __forceinline__ int32_t x3l_fir_value(const X3FirTaps& k, int32_t s, const int32_t (&d)[X3L_FIR_HIST]) {
+  int32_t acc = __mul24(k.c[0], s);
+#pragma unroll
+  for (int t = 1; t < X3L_FIR_TAPS; ++t) acc += __mul24(k.c[t], d[t - 1]);
+  return min(max(acc >> k.shift, -32768), 32767);
+}
+struct X3LevFir {
+  static constexpr bool kDiff = false, kFir = true, kState = true;
+  using Tail = X3LevFirTail;
+  X3FirTaps k;   // (uniform: the kernel's argument)
+  X3FirEdge* edge = nullptr;
+  int32_t d[X3L_FIR_HIST] = {0, 0, 0, 0, 0, 0, 0};   // d[t]: the sample t + 1 positions in front of the current one
+  uint32_t cnt = 0;                                  // samples seen
+  __device__ __forceinline__ void push(int32_t s) {
+    if (cnt < (uint32_t)X3L_FIR_HIST) edge->head[cnt] = (int16_t)s;
+    ++cnt;
+#pragma unroll
+    for (int t = X3L_FIR_HIST - 1; t >= 1; --t) d[t] = d[t - 1];
+    d[0] = s;
+  }
+  __device__ __forceinline__ void add(X3LevAcc& a, uint32_t v) {
+    const int32_t s = (int32_t)(int16_t)(uint16_t)v;
+    if (cnt + 1u >= k.T) a.add_value(x3l_fir_value(k, s, d));
+    push(s);
+  }
+  __device__ __forceinline__ void skip(uint32_t v) { push((int32_t)(int16_t)(uint16_t)v); }
+  // behind the stretch's or frame's last sample: the rest of the edge record
+  __device__ __forceinline__ void end() const {
+#pragma unroll
+    for (int t = 0; t < X3L_FIR_HIST; ++t) edge->tail[t] = (int16_t)d[t];
+    edge->n = cnt;
+  }
+};
+
 // The bins of consecutive positions from g on: decode(put_at) hands sample s of a frame to put_at(s, value), in order;
 // the positions with keep(s) go to the signal, bins that fill go to flush, and so does the open one at the end; a position
 // without keep(s) counts in no bin, and a signal with history (X3LevDiff) still sees its sample.  Returns decode's.  A
@@ -202,9 +262,9 @@ __device__ __forceinline__ int32_t x3l_bin_samples(uint64_t g, uint64_t bl, Deco
   bn.open(g, bl);
   const int32_t r = decode([&](uint32_t s, uint32_t v) {
     if (keep(s)) {
-      if constexpr (Signal::kDiff) bn.put(*sig, v, flush);
+      if constexpr (Signal::kState) bn.put(*sig, v, flush);
       else bn.put(Signal{}, v, flush);
-    } else if constexpr (Signal::kDiff) {
+    } else if constexpr (Signal::kState) {
       sig->skip(v);
     }
   });
@@ -353,7 +413,17 @@ x3_levels_accum_kernel(const uint8_t* __restrict__ x3, uint64_t len, const uint6
       if (bin < nlim) x3l_merge(mine + (bin - b0), a);
     };
     // a stretch's samples come in order, from sample 0 or from the first sample of block sb * j
-    if constexpr (Signal::kDiff) {
+    if constexpr (Signal::kFir) {
+      Signal sig;
+      sig.k = tail.k;
+      sig.edge = tail.edges + (f * tail.stride + j);   // (j < ns <= stride: below F * stride)
+      const int r = x3l_bin_samples(
+          fr.pos + (j ? 1u + (uint64_t)sb * j * p.block_len : 0u), bl,
+          [&](auto put_at) { return x3w_stretch(x3, len, frame_off[f], p, idx, segd, sb, nseg, f, j, put_at); }, X3LevKeepAll{}, flush,
+          &sig);
+      sig.end();
+      if (r < 0) atomicOr(&fst[f], X3W_FLAG);
+    } else if constexpr (Signal::kDiff) {
       Signal sig;
       const int r = x3l_bin_samples(
           fr.pos + (j ? 1u + (uint64_t)sb * j * p.block_len : 0u), bl,
@@ -392,7 +462,13 @@ x3_levels_fixup_kernel(const uint8_t* __restrict__ x3, const uint64_t* __restric
         auto flush = [&](uint64_t bin, const X3LevAcc& a) {
           if (bin < fr.nlim) x3l_merge(levels + fr.obase + bin, a);
         };
-        if constexpr (Signal::kDiff) {
+        if constexpr (Signal::kFir) {   // the frame is ONE stretch now: its record is its stretch 0's (X3L_DONE says so)
+          Signal sig;
+          sig.k = tail.k;
+          sig.edge = tail.edges + f * tail.stride;
+          (void)x3l_bin_samples(fr.pos, bl, [&](auto put_at) { return x3w_replay_frame(payload, p, blk, put_at); }, X3LevKeepAll{}, flush, &sig);
+          sig.end();
+        } else if constexpr (Signal::kDiff) {
           Signal sig;
           (void)x3l_bin_samples(fr.pos, bl, [&](auto put_at) { return x3w_replay_frame(payload, p, blk, put_at); }, X3LevKeepAll{}, flush, &sig);
           tail[f] = sig.prev;
@@ -468,6 +544,101 @@ x3_levels_seam_kernel(const uint8_t* __restrict__ x3, uint64_t len, const uint64
         const int32_t head = (int32_t)(int16_t)(uint16_t)(x3w_be32_at(x3, len, frame_off[f] + 20u) >> 16);
         a.add_value(x3l_diff(head, tail[f - 1u]));
         key = fr.obase + bin;   // (below obase + nlim <= the caller's rows: x3l_frame_rows)
+      }
+    }
+    x3l_merge_runs(levels, key, a, lane);
+  }
+}
+
+// ---- seam (X3LevFir only): a lane per (frame, stretch), behind the fix-up, when every frame's word is final.  The first
+// T - 1 positions of a stretch are the ones its lane could not form.  A frame whose word is X3D_OK has the records of its
+// stretches, every one written by a lane that ran to its proof; a frame whose word is X3L_DONE has ONE record, the fix-up's,
+// at its stretch 0.  The lane collects up to T - 1 samples of history by walking back over the records' tails -- earlier
+// stretches of the frame, then the frame in front while that one is good and belongs to the same stream or entry (the same
+// records, obase, with nlim != 0: as in x3_levels_seam_kernel, good neighbours are back to back in position) -- and stops at
+// a failed frame or the entry's first sample.  Every good frame has a sample, so a frame's step finds one: the walk ends after
+// at most (T - 1) * ns records.  Then y at the first min(n, T - 1) positions from history plus heads; a position whose history
+// is not complete adds nothing.  A bin edge can fall between those positions: a bin that fills goes to its record at once,
+// the open one is joined by record across the wave as in x3_levels_merge_kernel.  The stream is not read.
+// Every edge record read lies below F * stride (j < ns <= stride), every caller's record at obase + bin with bin < nlim.
+struct X3FirSeamValue {
+  int32_t y;
+  bool counts;
+  __device__ __forceinline__ void add(X3LevAcc& a, uint32_t) const {
+    if (counts) a.add_value(y);
+  }
+};
+
+__global__ void __launch_bounds__(256)
+x3_levels_fir_seam_kernel(uint64_t F, uint32_t block_len, const uint2* __restrict__ idx, uint32_t sb, uint32_t nseg, uint64_t bin_len,
+                          const X3LevFrame* __restrict__ frames, const int32_t* __restrict__ fst,
+                          const X3FirEdge* __restrict__ edges, uint32_t stride, X3FirTaps k, x3_level* __restrict__ levels) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t ns = x3w_index_ok(idx, sb) ? nseg : 1u;
+  const uint32_t need = k.T - 1u;   // samples of history a position takes
+  const uint64_t bl = x3l_bin_len(bin_len);
+  const uint64_t n_items = F * ns;
+  const uint64_t lanes = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u); i0 < n_items; i0 += lanes) {   // (whole waves)
+    const uint64_t i = i0 + lane;
+    X3LevAcc a;
+    a.reset();
+    uint64_t key = ~0ull;
+    const uint64_t f = i / ns;
+    const uint32_t j = (uint32_t)(i - f * ns);
+    const int32_t w = i < n_items ? fst[f] : -1;
+    if (w == X3D_OK || (w == X3L_DONE && j == 0u)) {
+      const X3LevFrame fr = frames[f];
+      const X3FirEdge e = edges[f * stride + j];
+      if (fr.nlim && e.n) {
+        // history: hist[h] = the sample h + 1 positions in front of the stretch, h < H
+        int32_t hist[X3L_FIR_HIST] = {0, 0, 0, 0, 0, 0, 0};
+        uint32_t H = 0;
+        uint64_t wf = f;
+        uint32_t wj = j;
+        while (H < need) {
+          if (wj) {
+            --wj;
+          } else {
+            if (wf == 0u) break;
+            const int32_t pw = fst[wf - 1u];
+            if (!x3l_frame_good(pw)) break;
+            const X3LevFrame fp = frames[wf - 1u];
+            if (!fp.nlim || fp.obase != fr.obase) break;
+            --wf;
+            wj = pw == X3D_OK ? ns - 1u : 0u;
+          }
+          const X3FirEdge h = edges[wf * stride + wj];
+          const uint32_t m = min(h.n, (uint32_t)X3L_FIR_HIST);
+#pragma unroll
+          for (int t = 0; t < X3L_FIR_HIST; ++t) {
+            if ((uint32_t)t < m && H < need) {
+#pragma unroll
+              for (int q = 0; q < X3L_FIR_HIST; ++q) hist[q] = (uint32_t)q == H ? (int32_t)h.tail[t] : hist[q];
+              ++H;
+            }
+          }
+        }
+        // y at sample c of the stretch, c < min(n, T - 1), from x[c - t]: a head (c >= t) or history (hist[t - c - 1])
+        const uint32_t m = min(e.n, need);
+        auto flush = [&](uint64_t bin, const X3LevAcc& acc) {
+          if (bin < fr.nlim) x3l_merge(levels + fr.obase + bin, acc);
+        };
+        X3LevBinner bn;
+        bn.open(fr.pos + (j ? 1u + (uint64_t)sb * j * block_len : 0u), bl);
+#pragma unroll
+        for (int c = 0; c < X3L_FIR_HIST; ++c) {
+          if ((uint32_t)c < m) {
+            int32_t d[X3L_FIR_HIST];
+#pragma unroll
+            for (int t = 1; t < X3L_FIR_TAPS; ++t) d[t - 1] = c >= t ? (int32_t)e.head[c - t] : hist[t - c - 1];
+            bn.put(X3FirSeamValue{x3l_fir_value(k, (int32_t)e.head[c], d), (uint32_t)c + H >= need}, 0u, flush);
+          }
+        }
+        if (bn.bin < fr.nlim) {
+          a = bn.a;
+          key = fr.obase + bn.bin;   // (below obase + nlim <= the caller's rows: x3l_frame_rows)
+        }
       }
     }
     x3l_merge_runs(levels, key, a, lane);

@@ -790,6 +790,37 @@ inline X3Error levels(Context& ctx, const EncodedStream& s, const Parameters& pa
   return static_cast<X3Error>(rc);
 }
 
+// An integer FIR filter in front of the levels (x3_fir_levels_dev): y[i] = clamp((sum over t of taps[t] * x[i - t]) >> shift,
+// 16 bits), counted where all taps.size() positions lie in frames with status 0 of the same stream or entry.  1 .. 8 taps with
+// sum |taps| <= 32768 and shift 0 .. 15: anything else is BadArg at the call.  {1} gives the levels, {1, -1} LevelSignal::Diff.
+struct Fir {
+  std::vector<int16_t> taps;
+  uint32_t shift = 0;
+  x3_level_fir c_fir() const {   // (more than 8 taps: n_taps says so and the call refuses it)
+    x3_level_fir f{};
+    f.n_taps = static_cast<uint32_t>(taps.size());
+    f.shift = shift;
+    for (size_t t = 0; t < taps.size() && t < 8; ++t) f.taps[t] = taps[t];
+    return f;
+  }
+};
+
+inline X3Error levels(Context& ctx, const EncodedStream& s, const Parameters& params, const Buffer& d_sample_offsets,
+                      uint64_t bin_len, x3_level* d_levels, uint64_t n_bins, int32_t* d_frame_status, WindowsResult* res,
+                      const Fir& fir) {
+  if (!s.bytes.ok() || !s.frame_offsets.ok() || !d_sample_offsets.ok()) return X3Error::BadArg;
+  const x3_params c = params.c_params();
+  const x3_level_fir f = fir.c_fir();
+  int rc = x3_fir_levels_dev(ctx.raw(), s.bytes.as<uint8_t>(), s.len, s.frame_offsets.as<uint64_t>(),
+                             d_sample_offsets.as<uint64_t>(), s.n_frames, &c, s.seg_blocks ? s.seg_index.as<uint64_t>() : nullptr,
+                             s.seg_blocks, bin_len, d_levels, n_bins, d_frame_status, &f);
+  if (rc != X3_OK) return static_cast<X3Error>(rc);
+  WindowsResult r;
+  rc = x3_levels_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status);
+  if (res) *res = r;
+  return static_cast<X3Error>(rc);
+}
+
 // Events (x3_events_dev): the runs of hot bins of n_bins level records (as device::levels writes them; bins of bin_len
 // positions) under `rule`, as cap slots of (d_starts, d_lens, d_event_levels or nullptr); d_count receives the number found,
 // which may exceed cap; every slot behind the events is a zero-length range, so the arrays go to device::decode_ranges with
@@ -968,6 +999,18 @@ class Corpus {
   X3Error levels(Context& ctx, uint64_t bin_len, x3_level* d_levels, uint64_t n_rows, int32_t* d_frame_status,
                  WindowsResult* res, LevelSignal signal = LevelSignal::Samples) const {
     int rc = x3_corpus_signal_levels_dev(ctx.raw(), raw_, bin_len, d_levels, n_rows, d_frame_status, static_cast<int>(signal));
+    if (rc != X3_OK) return static_cast<X3Error>(rc);
+    WindowsResult r;
+    rc = x3_levels_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status);
+    if (res) *res = r;
+    return static_cast<X3Error>(rc);
+  }
+  // ... behind an integer FIR filter (x3_corpus_fir_levels_dev): as device::levels with a Fir; no history crosses from one
+  // entry into the next.
+  X3Error levels(Context& ctx, uint64_t bin_len, x3_level* d_levels, uint64_t n_rows, int32_t* d_frame_status,
+                 WindowsResult* res, const Fir& fir) const {
+    const x3_level_fir f = fir.c_fir();
+    int rc = x3_corpus_fir_levels_dev(ctx.raw(), raw_, bin_len, d_levels, n_rows, d_frame_status, &f);
     if (rc != X3_OK) return static_cast<X3Error>(rc);
     WindowsResult r;
     rc = x3_levels_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status);

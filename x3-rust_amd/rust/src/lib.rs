@@ -70,6 +70,15 @@ pub mod ffi {
         pub n: u32,
         pub reserved: u32,
     }
+    /// `x3_level_fir`: the taps and shift of `x3_fir_levels_dev` / `x3_corpus_fir_levels_dev` (24 bytes); taps at and behind
+    /// `n_taps` are ignored
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+    pub struct x3_level_fir {
+        pub n_taps: u32,
+        pub shift: u32,
+        pub taps: [i16; 8],
+    }
     /// `x3_event_rule`: which bins are hot and how runs of them become events (`x3_events_dev`; 32 bytes)
     #[repr(C)]
     #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
@@ -230,6 +239,12 @@ pub mod ffi {
                                     signal: c_int) -> c_int;
         pub fn x3_corpus_signal_levels_dev(ctx: *mut x3_ctx, corpus: *const x3_corpus, bin_len: u64, d_levels: *mut x3_level,
                                            n_rows: u64, d_frame_status: *mut i32, signal: c_int) -> c_int;
+        pub fn x3_fir_levels_dev(ctx: *mut x3_ctx, d_x3: *const u8, x3_len: u64, d_frame_offsets: *const u64,
+                                 d_sample_offsets: *const u64, n_frames: u64, p: *const x3_params, d_seg_index: *const u64,
+                                 seg_blocks: u32, bin_len: u64, d_levels: *mut x3_level, n_bins: u64, d_frame_status: *mut i32,
+                                 fir: *const x3_level_fir) -> c_int;
+        pub fn x3_corpus_fir_levels_dev(ctx: *mut x3_ctx, corpus: *const x3_corpus, bin_len: u64, d_levels: *mut x3_level,
+                                        n_rows: u64, d_frame_status: *mut i32, fir: *const x3_level_fir) -> c_int;
         pub fn x3_events_dev(ctx: *mut x3_ctx, d_levels: *const x3_level, n_bins: u64, bin_len: u64, d_total: *const u64,
                              rule: *const x3_event_rule, d_starts: *mut u64, d_lens: *mut u32, d_event_levels: *mut x3_level,
                              cap: u64, d_count: *mut u64) -> c_int;
@@ -1443,6 +1458,42 @@ pub mod device {
         Ok((n_bad, first_bad, st))
     }
 
+    /// An integer FIR filter in front of the levels (`x3_level_fir`): `y[i] = clamp((sum over t of taps[t] * x[i - t]) >> shift,
+    /// 16 bits)`, counted where all `n_taps` positions lie in frames with status 0 of the same stream or entry.  1 .. 8 taps
+    /// with sum |taps| <= 32768 and shift 0 .. 15; the calls refuse anything else
+    pub type Fir = ffi::x3_level_fir;
+
+    /// `Fir` of a slice of taps (at most 8 are taken; more make `n_taps` say so, and the calls refuse it)
+    pub fn fir(taps: &[i16], shift: u32) -> Fir {
+        let mut f = Fir { n_taps: taps.len() as u32, shift, taps: [0; 8] };
+        for (d, s) in f.taps.iter_mut().zip(taps) {
+            *d = *s;
+        }
+        f
+    }
+
+    /// `levels` behind an integer FIR filter (`x3_fir_levels_dev`; not in the reference crate): arguments and result as
+    /// `levels`; `fir(&[1], 0)` gives its records, `fir(&[1, -1], 0)` those of `LevelSignal::Diff`
+    #[allow(clippy::too_many_arguments)]
+    pub fn fir_levels<'g>(gpu: &'g Gpu, s: &EncodedStream<'g>, params: &x3::Parameters, sample_offsets: &Buffer<'g>, bin_len: u64,
+                          d_levels: &mut Buffer<'g>, n_bins: usize, d_frame_status: Option<&mut Buffer<'g>>, fir: &Fir)
+                          -> error::Result<(u64, u64, i32)> {
+        if d_levels.len() < core::mem::size_of::<Level>() * n_bins || d_frame_status.as_ref().map_or(false, |b| b.len() < 4 * s.n_frames) {
+            return Err(X3Error::BadArg);
+        }
+        let p = params.c()?;
+        let idx = match &s.seg_index { Some(i) => i.as_ptr::<u64>() as *const u64, None => core::ptr::null() };
+        let st_ptr = match d_frame_status { Some(b) => b.as_ptr::<i32>(), None => core::ptr::null_mut() };
+        error::check(unsafe {
+            ffi::x3_fir_levels_dev(gpu.raw(), s.bytes.as_ptr::<u8>(), s.len as u64, s.frame_offsets.as_ptr::<u64>(),
+                                   sample_offsets.as_ptr::<u64>(), s.n_frames as u64, &p, idx, s.seg_blocks, bin_len,
+                                   d_levels.as_ptr::<Level>(), n_bins as u64, st_ptr, fir)
+        })?;
+        let (mut n_bad, mut first_bad, mut st) = (0u64, 0u64, 0);
+        error::check(unsafe { ffi::x3_levels_result(gpu.raw(), &mut n_bad, &mut first_bad, &mut st) })?;
+        Ok((n_bad, first_bad, st))
+    }
+
     /// The rule of `events` / `Corpus::events` (`x3_event_rule`): a bin is hot when `sum_sq >= mean_sq_min * n` or `max(max,
     /// -min) >= peak_min` (0: off); hot bins with at most `join_bins` cold ones between them are one run; runs of fewer than
     /// `min_bins` bins are dropped; `pad_bins` on both sides (`2 * pad_bins <= join_bins`); pieces of `max_bins` (0: no cut)
@@ -1750,6 +1801,23 @@ pub mod device {
     }
 
     impl<'g> Corpus<'g> {
+        /// `levels` behind an integer FIR filter (`x3_corpus_fir_levels_dev`): arguments and result as `levels`; no history
+        /// crosses from one entry into the next
+        pub fn fir_levels(&self, bin_len: u64, d_levels: &mut Buffer<'g>, n_rows: usize, d_frame_status: Option<&mut Buffer<'g>>,
+                          fir: &Fir) -> error::Result<(u64, u64, i32)> {
+            if d_levels.len() < core::mem::size_of::<Level>() * n_rows
+                || d_frame_status.as_ref().map_or(false, |b| b.len() < 4 * self.info().1 as usize) {
+                return Err(X3Error::BadArg);
+            }
+            let st_ptr = match d_frame_status { Some(b) => b.as_ptr::<i32>(), None => core::ptr::null_mut() };
+            error::check(unsafe {
+                ffi::x3_corpus_fir_levels_dev(self.gpu.raw(), self.raw, bin_len, d_levels.as_ptr::<Level>(), n_rows as u64, st_ptr, fir)
+            })?;
+            let (mut n_bad, mut first_bad, mut st) = (0u64, 0u64, 0);
+            error::check(unsafe { ffi::x3_levels_result(self.gpu.raw(), &mut n_bad, &mut first_bad, &mut st) })?;
+            Ok((n_bad, first_bad, st))
+        }
+
         /// Events of every entry (`x3_corpus_events_dev`) over the `n_rows` records `levels` wrote: as `device::events`, with
         /// the events' entries in `d_entries` (u32); the arrays go to `ranges` with `n_ranges = cap` as they are.  Waits: ->
         /// the events found

@@ -62,7 +62,7 @@ SYMBOLS = [
     "x3_corpus_build", "x3_corpus_info", "x3_corpus_entries", "x3_corpus_entries_dev", "x3_corpus_seg_index", "x3_corpus_windows_dev",
     "x3_corpus_destroy",
     "x3_levels_dev", "x3_levels_result", "x3_corpus_levels_rows", "x3_corpus_levels_dev",
-    "x3_signal_levels_dev", "x3_corpus_signal_levels_dev",
+    "x3_signal_levels_dev", "x3_corpus_signal_levels_dev", "x3_fir_levels_dev", "x3_corpus_fir_levels_dev",
     "x3_events_dev", "x3_corpus_events_dev", "x3_events_result",
     "x3_level_quantiles_dev", "x3_corpus_level_quantiles_dev", "x3_level_quantiles_result",
     "x3_level_thresholds_dev", "x3_corpus_level_thresholds_dev", "x3_events_adaptive_dev", "x3_corpus_events_adaptive_dev",
@@ -81,13 +81,61 @@ LEVEL_SIGNAL_SAMPLES, LEVEL_SIGNAL_DIFF = 0, 1   # x3_signal_levels_dev: the sam
 LEVEL_SIGNALS = {"samples": LEVEL_SIGNAL_SAMPLES, "diff": LEVEL_SIGNAL_DIFF}   # the mirrors' keyword `signal`
 
 
-def level_signal(signal):
-    """the keyword `signal` of the levels methods ("samples" | "diff", or a LEVEL_SIGNAL_* value) -> the C ABI's int"""
+class LevelFir(C.Structure):
+    """x3_level_fir: the taps and shift of x3_fir_levels_dev / x3_corpus_fir_levels_dev"""
+    _fields_ = [("n_taps", C.c_uint32), ("shift", C.c_uint32), ("taps", C.c_int16 * 8)]
+
+
+class Fir:
+    """An integer FIR filter in front of the levels: y[i] = clamp((sum over t of taps[t] * x[i - t]) >> shift, 16 bits),
+    counted where all len(taps) positions lie in good frames of the same stream or entry (x3_fir_levels_dev).  1 .. 8 taps
+    of 16 bits with sum |taps| <= 32768, shift 0 .. 15; immutable, checked here.  Goes wherever `signal=` goes."""
+    __slots__ = ("taps", "shift")
+
+    def __init__(self, taps, shift=0):
+        t = tuple(int(c) for c in taps)
+        if any(isinstance(c, bool) or int(c) != c for c in taps) or isinstance(shift, bool) or int(shift) != shift:
+            raise ValueError("Fir: integer taps and shift")
+        if not 1 <= len(t) <= 8:
+            raise ValueError("Fir: 1 .. 8 taps")
+        if not 0 <= int(shift) <= 15:
+            raise ValueError("Fir: shift 0 .. 15")
+        if any(not -32768 <= c <= 32767 for c in t) or sum(abs(c) for c in t) > 32768:
+            raise ValueError("Fir: taps of 16 bits with sum |taps| <= 32768")
+        object.__setattr__(self, "taps", t)
+        object.__setattr__(self, "shift", int(shift))
+
+    def __setattr__(self, name, value):
+        raise AttributeError("Fir is immutable")
+
+    __delattr__ = __setattr__
+
+    def __eq__(self, other):
+        return isinstance(other, Fir) and (self.taps, self.shift) == (other.taps, other.shift)
+
+    def __hash__(self):
+        return hash((self.taps, self.shift))
+
+    def __repr__(self):
+        return "Fir(%r, shift=%d)" % (list(self.taps), self.shift)
+
+    def c_struct(self):
+        """-> the x3_level_fir of this filter"""
+        return LevelFir(len(self.taps), self.shift, (C.c_int16 * 8)(*self.taps))
+
+
+def level_signal(signal, fir=True):
+    """the keyword `signal` of the levels methods ("samples" | "diff", or a LEVEL_SIGNAL_* value) -> the C ABI's int; a
+    Fir is handed through (fir=False: to a call that has no FIR form yet, which raises)"""
+    if isinstance(signal, Fir):
+        if not fir:
+            raise ValueError("signal: range levels of a Fir signal are not built yet (levels, events, level_quantiles and adaptive_events take one)")
+        return signal
     if signal in LEVEL_SIGNALS:
         return LEVEL_SIGNALS[signal]
     if signal in LEVEL_SIGNALS.values() and not isinstance(signal, bool):
         return int(signal)
-    raise ValueError('signal: "samples" or "diff"')
+    raise ValueError('signal: "samples", "diff" or a Fir')
 
 
 # x3_level: one bin of x3_levels_dev / x3_corpus_levels_dev (32 bytes)
@@ -297,6 +345,8 @@ def lib():
     L.x3_corpus_levels_dev.argtypes = [vp, vp, u64, vp, u64, vp]
     L.x3_signal_levels_dev.argtypes = [vp, vp, u64, vp, vp, u64, PP, vp, u32, u64, vp, u64, vp, C.c_int]
     L.x3_corpus_signal_levels_dev.argtypes = [vp, vp, u64, vp, u64, vp, C.c_int]
+    L.x3_fir_levels_dev.argtypes = [vp, vp, u64, vp, vp, u64, PP, vp, u32, u64, vp, u64, vp, C.POINTER(LevelFir)]
+    L.x3_corpus_fir_levels_dev.argtypes = [vp, vp, u64, vp, u64, vp, C.POINTER(LevelFir)]
     L.x3_events_dev.argtypes = [vp, vp, u64, u64, vp, C.POINTER(EventRule), vp, vp, vp, u64, vp]
     L.x3_corpus_events_dev.argtypes = [vp, vp, vp, u64, u64, C.POINTER(EventRule), vp, vp, vp, vp, u64, vp]
     L.x3_events_result.argtypes = [vp, C.POINTER(u64)]
@@ -1043,6 +1093,24 @@ class Context:
         """x3_corpus_signal_levels_dev: corpus_levels_dev with a signal; asynchronous, levels_result waits"""
         return lib().x3_corpus_signal_levels_dev(self._h, corpus._h, bin_len, d_levels, n_rows, d_frame_status, signal)
 
+    @staticmethod
+    def _fir_arg(fir):
+        """a Fir, a LevelFir or None (NULL, which the library refuses) as the calls' last argument"""
+        if fir is None:
+            return None
+        return C.byref(fir.c_struct() if isinstance(fir, Fir) else fir)
+
+    def fir_levels_dev(self, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, params, bin_len, d_levels, n_bins,
+                       d_frame_status=None, d_seg_index=None, seg_blocks=0, fir=None):
+        """x3_fir_levels_dev: levels_dev of the samples behind an integer FIR filter (fir: a Fir, or a LevelFir as it is);
+        asynchronous, levels_result waits"""
+        return lib().x3_fir_levels_dev(self._h, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, C.byref(params),
+                                       d_seg_index, seg_blocks, bin_len, d_levels, n_bins, d_frame_status, self._fir_arg(fir))
+
+    def corpus_fir_levels_dev(self, corpus, bin_len, d_levels, n_rows, d_frame_status=None, fir=None):
+        """x3_corpus_fir_levels_dev: corpus_levels_dev behind an integer FIR filter; asynchronous, levels_result waits"""
+        return lib().x3_corpus_fir_levels_dev(self._h, corpus._h, bin_len, d_levels, n_rows, d_frame_status, self._fir_arg(fir))
+
     def levels_result(self):
         """-> (rc, n_bad_frames, first_bad, first_bad_status) of the last levels_dev / corpus_levels_dev"""
         nb, fb, st = C.c_uint64(0), C.c_uint64(0), C.c_int32(0)
@@ -1525,7 +1593,9 @@ class WindowSource:
                           signal=LEVEL_SIGNAL_SAMPLES):
         """enqueue the level records of n ranges (device pointers: d_starts n x u64, d_lens n x u32, d_levels rows_cap x
         x3_level, d_row_offsets (n + 1) x u64 or None when padded, d_status n x i32); row_stride 0: packed; signal: a
-        LEVEL_SIGNAL_* value; -> rc; Context.range_levels_result waits"""
+        LEVEL_SIGNAL_* value (a Fir raises: not built yet); -> rc; Context.range_levels_result waits"""
+        if isinstance(signal, Fir):
+            level_signal(signal, fir=False)
         return self.ctx.signal_range_levels_dev(self.d_x3, self.x3_len, self.d_frame_offsets, self.d_sample_offsets,
                                                 self.n_frames, self.params, d_starts, d_lens, n, bin_len, row_stride, d_levels,
                                                 rows_cap, d_row_offsets, d_status, self.d_seg_index, self.seg_blocks, signal)
@@ -1539,13 +1609,17 @@ class WindowSource:
         w * padded_to.  The tensors events() returns go in as they are.  The call waits for its result.
         signal: "samples", or "diff" -- the stream's first difference (as in levels()) cut to the ranges: the difference at
         a range's first position is counted, its earlier sample lies in front of the range (x3_signal_range_levels_dev)"""
-        sig = level_signal(signal)
+        sig = level_signal(signal, fir=False)
         return _range_levels_torch(self.ctx, lambda e, *a: self.range_levels_into(*a, signal=sig), "x3_signal_range_levels_dev",
                                    starts, lens, bin_len, padded_to, capacity)
 
     def levels_into(self, bin_len, d_levels, n_bins, d_frame_status=None, signal=LEVEL_SIGNAL_SAMPLES):
-        """enqueue x3_signal_levels_dev over this source (device pointers; signal: a LEVEL_SIGNAL_* value); -> rc;
-        Context.levels_result waits"""
+        """enqueue x3_signal_levels_dev over this source (device pointers; signal: a LEVEL_SIGNAL_* value), or
+        x3_fir_levels_dev (signal: a Fir); -> rc; Context.levels_result waits"""
+        if isinstance(signal, Fir):
+            return self.ctx.fir_levels_dev(self.d_x3, self.x3_len, self.d_frame_offsets, self.d_sample_offsets, self.n_frames,
+                                           self.params, bin_len, d_levels, n_bins, d_frame_status, self.d_seg_index,
+                                           self.seg_blocks, signal)
         return self.ctx.signal_levels_dev(self.d_x3, self.x3_len, self.d_frame_offsets, self.d_sample_offsets, self.n_frames,
                                           self.params, bin_len, d_levels, n_bins, d_frame_status, self.d_seg_index,
                                           self.seg_blocks, signal)
@@ -1553,7 +1627,8 @@ class WindowSource:
     def levels(self, bin_len, n_bins=None, *, signal="samples"):
         """-> (records np.ndarray of LEVEL_DTYPE [n_bins], frame statuses np.int32 [n_frames]): min, max, n, sum and sum of
         squares per bin of bin_len positions (0: one bin); n_bins: as many as cover the stream unless given.
-        signal: "samples", or "diff" -- the samples' first difference, clamped to 16 bits (x3_signal_levels_dev)"""
+        signal: "samples", or "diff" -- the samples' first difference, clamped to 16 bits (x3_signal_levels_dev) -- or a
+        Fir: the samples behind an integer FIR filter (x3_fir_levels_dev)"""
         sig = level_signal(signal)
         if n_bins is None:
             n_bins = max(1, -(-self.total // bin_len)) if bin_len else 1
@@ -1869,6 +1944,8 @@ class Corpus:
         WindowSource.range_levels_into); -> rc; Context.range_levels_result waits"""
         if self._h is None:
             raise ValueError("the corpus is closed")
+        if isinstance(signal, Fir):
+            level_signal(signal, fir=False)   # (raises: range levels of a Fir signal are not built yet)
         return self.ctx.corpus_signal_range_levels_dev(self, d_entries, d_starts, d_lens, n, bin_len, row_stride, d_levels,
                                                        rows_cap, d_row_offsets, d_status, signal)
 
@@ -1876,7 +1953,7 @@ class Corpus:
         """The x3_level records of the ranges [starts[w], starts[w] + lens[w]) of entry entries[w] -> (levels, row_offsets,
         status) as WindowSource.range_levels; the tensors events() returns go in as they are.  signal: as there -- the
         entry's first difference cut to the ranges; no difference crosses from one entry into the next"""
-        sig = level_signal(signal)
+        sig = level_signal(signal, fir=False)
         return _range_levels_torch(self.ctx, lambda *a: self.range_levels_into(*a, signal=sig),
                                    "x3_corpus_signal_range_levels_dev", starts, lens, bin_len, padded_to, capacity, entries=entries)
 
@@ -1891,16 +1968,18 @@ class Corpus:
         return rf
 
     def levels_into(self, bin_len, d_levels, n_rows, d_frame_status=None, signal=LEVEL_SIGNAL_SAMPLES):
-        """enqueue x3_corpus_signal_levels_dev (device pointers; signal: a LEVEL_SIGNAL_* value); -> rc;
-        Context.levels_result waits"""
+        """enqueue x3_corpus_signal_levels_dev (device pointers; signal: a LEVEL_SIGNAL_* value), or
+        x3_corpus_fir_levels_dev (signal: a Fir); -> rc; Context.levels_result waits"""
         if self._h is None:
             raise ValueError("the corpus is closed")
+        if isinstance(signal, Fir):
+            return self.ctx.corpus_fir_levels_dev(self, bin_len, d_levels, n_rows, d_frame_status, signal)
         return self.ctx.corpus_signal_levels_dev(self, bin_len, d_levels, n_rows, d_frame_status, signal)
 
     def levels(self, bin_len, *, signal="samples"):
         """-> (records np.ndarray of LEVEL_DTYPE [rows], row_first np.uint64 [n_entries + 1], frame statuses np.int32
         [n_frames]): the levels of every entry, positions relative to the entry, bins of bin_len positions (0: one bin).
-        signal: "samples", or "diff" -- the samples' first difference, clamped to 16 bits (x3_signal_levels_dev); no difference crosses from one entry into the next"""
+        signal: "samples", or "diff" -- the samples' first difference, clamped to 16 bits (x3_signal_levels_dev) -- or a Fir (x3_corpus_fir_levels_dev); no difference and no filter history crosses from one entry into the next"""
         sig = level_signal(signal)
         rf = self.levels_rows(bin_len)
         n_rows = int(rf[-1])
