@@ -1061,6 +1061,42 @@ int x3_corpus_signal_range_levels_dev(x3_ctx* ctx, const x3_corpus* corpus, cons
                                       const uint32_t* d_lens, uint64_t n_ranges, uint64_t bin_len, uint64_t row_stride,
                                       x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status,
                                       int signal);
+/* ---- FIR RANGE LEVELS: the range-levels calls on the FIR signal of x3_fir_levels_dev, so that events found behind a filter
+ * can be looked at again on the signal they were found on.  The arguments of x3_range_levels_dev /
+ * x3_corpus_range_levels_dev plus a last `fir`, validated by the rule of x3_fir_levels_dev (1 .. 8 taps, shift <= 15, sum |c|
+ * <= 32768); a NULL or invalid fir is X3_ERR_BAD_ARG with nothing enqueued, tested before every other argument.
+ *   ONE RULE -- the call cuts the stream's (or entry's) FIR signal; it does not filter the cut.  With y the signal
+ * x3_fir_levels_dev defines on the stream or entry that holds the range (y[i] = clamp((sum over t < T of c[t] * x[i - t]) >>
+ * shift, -32768, 32767); counted by THE HISTORY RULE: all T positions i - T + 1 .. i exist in the same stream or entry and
+ * lie in frames with status 0), range w has the records of x3_range_levels_dev with y[start + r] in place of x[start + r],
+ * r in [0, len).  Rows R(w), bins from the range's start, packed and padded layouts, row offsets, rows_cap rules, refusals
+ * and identities are unchanged.
+ *   - The first T - 1 positions of a range ARE counted when y counts them: their earlier samples lie in front of the range,
+ *     possibly in up to T - 1 frames in front of the first covering frame (LEAD FRAMES; a frame can be one sample long).
+ *   - The range (0, total) at bin length b equals x3_fir_levels_dev at b, record for record, damaged frames included.
+ *   - A range whose start and length are multiples of b equals the slice of those records, the last record cut to the
+ *     range's length.
+ *   - Taps {1} give the bytes (records, offsets, statuses) of x3_range_levels_dev; taps {1, -1} give the bytes of
+ *     x3_signal_range_levels_dev(..., X3_LEVEL_SIGNAL_DIFF).
+ *   - d_status[w] is exactly the SAMPLES form's: the status of the first covering frame in frame order that is not 0.  A
+ *     lead frame never gives the range a status; a lead frame that fails takes away the range positions whose taps reach it
+ *     or reach past it, and nothing else.
+ *   - n counts filter outputs: a clean range that starts at least T - 1 positions into a clean entry has n == len in all.
+ *   - The records are int16-signal records: they go into the events, quantiles and thresholds calls unchanged.
+ *   x3_range_levels_result, the pending slot, the workspace and the options "last_range_levels_replays" /
+ * "last_range_levels_overflow" are shared with the other forms; a lead-frame pair that the fix-up decodes counts as a replay.
+ * The workspace holds up to T - 1 more pairs per range (the second arm of P is 4 * (n_frames + n_ranges) + (T - 1) *
+ * n_ranges) and, beside it, the 32-byte edge record per (frame, stretch) of x3_fir_levels_dev. */
+int x3_fir_range_levels_dev(x3_ctx* ctx, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
+                            const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
+                            const uint64_t* d_seg_index, uint32_t seg_blocks, const uint64_t* d_starts,
+                            const uint32_t* d_lens, uint64_t n_ranges, uint64_t bin_len, uint64_t row_stride,
+                            x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status,
+                            const x3_level_fir* fir);
+int x3_corpus_fir_range_levels_dev(x3_ctx* ctx, const x3_corpus* corpus, const uint32_t* d_entries, const uint64_t* d_starts,
+                                   const uint32_t* d_lens, uint64_t n_ranges, uint64_t bin_len, uint64_t row_stride,
+                                   x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status,
+                                   const x3_level_fir* fir);
 void x3_corpus_destroy(x3_corpus* corpus);
 
 /* ------------------------------------------------------------------ multi-GPU (no reference analogue) */

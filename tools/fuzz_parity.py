@@ -23,7 +23,9 @@ Families: (e) the single-pass encoders on block_len 20 with mixed content, many 
           (not in the default family set); (i) family (h) behind an integer FIR filter (x3_fir_levels_dev /
           x3_corpus_fir_levels_dev): random taps (1 .. 8, sum |c| <= 32768) and shifts as well, frames and stretches shorter
           than the taps among them, GPU == tests/fir_levels_ref.py; {1} against x3_levels_dev byte for byte (not in the
-          default family set)."""
+          default family set); (t) family (r) behind a random valid Fir (x3_fir_range_levels_dev; the letter (l) is the
+          difference's), with starts drawn to frame and stretch boundaries +- T - 1 (lead frames, stretch fronts), GPU ==
+          tests/fir_range_levels_ref.py (not in the default family set)."""
 import argparse, ctypes as C, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "x3-rust_amd"))
@@ -804,8 +806,9 @@ fams["c"] = fam_c
 fams["x"] = fam_x
 
 
-def fam_r(rng, tag, diff=False):
-    """range levels (diff: of the first difference, against signal_range_levels_ref -- family (l)): the records, row offsets and statuses of random ranges of a random stream -- any geometry, damaged
+def fam_r(rng, tag, diff=False, fir=None):
+    """range levels (diff: of the first difference, against signal_range_levels_ref -- family (l); fir: behind that filter,
+    against fir_range_levels_ref -- family (t)): the records, row offsets and statuses of random ranges of a random stream -- any geometry, damaged
     frames, a damaged or walk-built index, packed (exact, cut or roomy capacity) and padded -- against range_levels_ref on
     the oracle's frame verdicts; the output arrays are filled with 0x5A and what no call may write must keep it"""
     import range_levels_ref as RL
@@ -871,6 +874,13 @@ def fam_r(rng, tag, diff=False):
             if rng.random() < 0.4:
                 at = int(rng.integers(0, len(offs))) * spf + int(rng.choice([0, 1, 1 + 4 * p.block_len, 1 + 32 * p.block_len]))
                 starts[w] = min(at, n - lens[w])
+    if fir is not None:   # ... T - 1 either side of a frame's or a stretch's first sample
+        T = len(fir.taps)
+        for w in range(nr):
+            if rng.random() < 0.5:
+                at = int(rng.integers(0, len(offs))) * spf + int(rng.choice([0, 1, 1 + 4 * p.block_len, 1 + 32 * p.block_len]))
+                at += int(rng.choice([-(T - 1), -1, 0, 1, T - 2, T - 1, T]))
+                starts[w] = max(0, min(at, n - lens[w]))
     wild = [n, n + 1, 2 ** 63, 2 ** 64 - 1, int(rng.integers(n + 1, 2 ** 62))]
     for _ in range(int(rng.integers(0, 3))):
         w = int(rng.integers(0, nr))
@@ -892,7 +902,10 @@ def fam_r(rng, tag, diff=False):
     else:
         stride = int(rng.choice([1, max(rows), max(1, max(rows) // 2), max(rows) + 3]))
         cap = nr * stride + int(rng.integers(0, 3))
-    if diff:
+    if fir is not None:
+        import fir_range_levels_ref as FRL
+        want = FRL.range_levels(verdicts, so_a, starts, lens, bin_len, stride, cap, fir.taps, fir.shift)
+    elif diff:
         import signal_range_levels_ref as SRL
         want = SRL.range_levels(verdicts, so_a, starts, lens, bin_len, stride, cap, SRL.DIFF)
     else:
@@ -921,8 +934,11 @@ def fam_r(rng, tag, diff=False):
             ctx.upload(q, np.full(v + guard, 0x5A, dtype=np.uint8))
         ctx.upload(bufs[3], np.array(starts, dtype=np.uint64))
         ctx.upload(bufs[4], np.array(lens, dtype=np.uint32))
-        rc = src.range_levels_into(bufs[3], bufs[4], nr, bin_len, stride, bufs[0], cap, bufs[1], bufs[2],
-                                   signal=x3hip.LEVEL_SIGNAL_DIFF if diff else x3hip.LEVEL_SIGNAL_SAMPLES)
+        if fir is not None:
+            rc = src.fir_range_levels_into(bufs[3], bufs[4], nr, bin_len, stride, bufs[0], cap, bufs[1], bufs[2], fir)
+        else:
+            rc = src.range_levels_into(bufs[3], bufs[4], nr, bin_len, stride, bufs[0], cap, bufs[1], bufs[2],
+                                       signal=x3hip.LEVEL_SIGNAL_DIFF if diff else x3hip.LEVEL_SIGNAL_SAMPLES)
         assert rc == 0, (tag, "rc", rc, ctx.last_error())
         res = ctx.range_levels_result()
         raw = [ctx.download(q, v + guard) for q, v in zip(bufs[:3], sizes)]
@@ -1089,6 +1105,7 @@ def fam_h(rng, tag, fir=False):
 
 fams["h"] = fam_h
 fams["i"] = lambda rng, tag: fam_h(rng, tag, fir=True)
+fams["t"] = lambda rng, tag: fam_r(rng, tag, fir=draw_fir(rng))
 
 
 def run(seed=1, minutes=None, trials=None, families="egdbaf", only=-1, context=None):

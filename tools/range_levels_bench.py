@@ -18,9 +18,14 @@ X3_LEVEL_SIGNAL_DIFF).  Route a decodes every range with the sample in front of 
 entry's position 0 has none and its first position counts nothing), takes torch's difference, clamps it to 16 bits and
 reduces; the index plan that drops each range's leading sample is made once, outside the timed part.  Route b is the DIFF
 levels call, and case 3's events are found on the DIFF levels.
+--signal fir [--taps 1,-2,1 --shift 0]: the same cases behind an integer FIR filter (x3_fir_range_levels_dev /
+x3_corpus_fir_range_levels_dev).  Route a decodes every range with the T - 1 samples in front of it (fewer at its entry's
+start, where the first positions count nothing), runs torch's conv1d in float64 over the packed buffer (exact: the sums stay
+inside 2^30), shifts, clamps and reduces; case 3 sums T gathers of its padded rows instead.  Route b is the FIR levels call,
+and case 3's events are found on the FIR levels.
 Every route's records are compared with == at the end of every case and the tool fails otherwise.  Kernel times: run it under
 `rocprofv3 --kernel-trace --stats -- python3 tools/range_levels_bench.py ...`.  Prints one JSON line.
-    python3 tools/range_levels_bench.py [--signal samples|diff] [--samples N] [--reps 10] [--warmup 2] [--cap 4096]
+    python3 tools/range_levels_bench.py [--signal samples|diff|fir] [--taps c0,c1,..] [--shift k] [--samples N] [--reps 10] [--warmup 2] [--cap 4096]
                                         [--cases config3,corpus] [--out file.json]"""
 import argparse, ctypes as C, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -51,6 +56,15 @@ def as_records(mn, mx, sm, sq, n):
     return out
 
 
+def filtered(a, w):
+    """route a's signal over a packed int32 buffer w: y[i] belongs to buffer index i + a.hist"""
+    if a.signal == "diff":
+        return torch.clamp(w[1:] - w[:-1], -32768, 32767)
+    k = torch.tensor(a.taps[::-1], dtype=torch.float64, device="cuda")[None, None, :]      # (conv1d correlates: the taps reversed)
+    acc = torch.nn.functional.conv1d(w.to(torch.float64)[None, None, :], k)[0, 0].to(torch.int64)
+    return torch.clamp(acc >> a.shift, -32768, 32767)
+
+
 def timed(results, key, rep, warmup, t):
     if rep >= warmup:
         results.setdefault(key, []).append(t * 1e3)
@@ -68,17 +82,18 @@ def bins_case(src, a, results, info, case, ent, starts, lens, bin_len):
     lv = torch.empty((total_rows, 32), dtype=torch.uint8, device="cuda")
     off, off2 = (torch.empty(n + 1, dtype=torch.int64, device="cuda") for _ in range(2))
     st, st2 = (torch.empty(n, dtype=torch.int32, device="cuda") for _ in range(2))
-    diff = a.signal == "diff"
-    pre = [1 if diff and s > 0 else 0 for s in starts]          # route a, diff: the sample in front of the range comes with it
+    hist_on, hist = a.hist > 0, a.hist
+    pre = [min(hist, s) for s in starts]          # route a, diff / fir: the samples in front of the range come with it
     total_a = total + sum(pre)
     buf = torch.empty(total_a, dtype=torch.int16, device="cuda")
     d_st_a = torch.tensor([s - k for s, k in zip(starts, pre)], dtype=torch.int64, device="cuda")
     d_ln_a = torch.tensor([v + k for v, k in zip(lens, pre)], dtype=torch.int32, device="cuda")
-    if diff:   # where each range's own positions lie in route a's packed buffer; a range at position 0 has no first difference
+    if hist_on:   # where each range's own positions lie in route a's packed buffer; a range at position 0 has no first difference
         first = np.concatenate([[0], np.cumsum([v + k for v, k in zip(lens, pre)])[:-1]]) + np.array(pre)
         keep = torch.from_numpy(np.concatenate([f + np.arange(v) for f, v in zip(first, lens)]).astype(np.int64)).cuda()
         ok = np.ones(total, dtype=bool)
-        ok[np.concatenate([[0], np.cumsum(lens)[:-1]])[np.array(pre) == 0]] = False
+        for f, v, k in zip(np.concatenate([[0], np.cumsum(lens)[:-1]]), lens, pre):   # the positions without their history
+            ok[f:f + min(hist - k, v)] = False
         valid = torch.from_numpy(ok).cuda().view(total_rows, bin_len)
     rf = src.levels_rows(bin_len)
     full_rows = int(rf[-1])
@@ -97,9 +112,9 @@ def bins_case(src, a, results, info, case, ent, starts, lens, bin_len):
         r = ctx.decode_ranges_result()
         t2 = now()
         assert r[:2] == (0, 0), r
-        if diff:
+        if hist_on:
             w = buf.to(torch.int32)
-            y = torch.clamp(w[1:] - w[:-1], -32768, 32767)[(keep - 1).clamp(min=0)].view(total_rows, bin_len)
+            y = filtered(a, w)[(keep - hist).clamp(min=0)].view(total_rows, bin_len)
             red = (torch.where(valid, y, 32767).min(1).values, torch.where(valid, y, -32768).max(1).values,
                    torch.where(valid, y, 0).sum(1, dtype=torch.int64), torch.where(valid, y * y, 0).sum(1, dtype=torch.int64),
                    valid.sum(1))
@@ -119,7 +134,7 @@ def bins_case(src, a, results, info, case, ent, starts, lens, bin_len):
             assert ctx.levels_result()[0] == 0
             timed(results, name + "_route_b", rep, a.warmup, now() - t4)
     got = records(lv)
-    counts = red[4].cpu().numpy().astype(np.uint32) if diff else np.full(total_rows, bin_len, dtype=np.uint32)
+    counts = red[4].cpu().numpy().astype(np.uint32) if hist_on else np.full(total_rows, bin_len, dtype=np.uint32)
     want_a = as_records(*(t.cpu().numpy() for t in red[:4]), counts)
     same = np.array_equal(got, want_a) and not st.cpu().numpy().any()
     if full is not None:
@@ -146,8 +161,8 @@ def events_case(src, a, results, info, bin_len):
     ev_lv, ev_lv2, lv = (torch.empty((cap, 32), dtype=torch.uint8, device="cuda") for _ in range(3))
     status, status2 = (torch.empty(cap, dtype=torch.int32, device="cuda") for _ in range(2))
     off = torch.empty(cap + 1, dtype=torch.int64, device="cuda")
-    diff = a.signal == "diff"
-    width = stride + (1 if diff else 0)          # route a, diff: a column for the sample in front of the range
+    hist_on, hist = a.hist > 0, a.hist
+    width = stride + hist                        # route a, diff / fir: columns for the samples in front of the range
     buf = torch.empty((cap, width), dtype=torch.int16, device="cuda")
     torch.cuda.synchronize()
     assert src.levels(bin_len, full.data_ptr(), n_rows) == 0 and ctx.levels_result()[0] == 0
@@ -158,7 +173,7 @@ def events_case(src, a, results, info, bin_len):
     assert src.events(full.data_ptr(), n_rows, bin_len, rule, ent.data_ptr(), st.data_ptr(), ln.data_ptr(), ev_lv.data_ptr(), cap,
                       cnt.data_ptr()) == 0
     rc, found = ctx.events_result()
-    assert rc == 0 and found > 0 and (found <= cap or a.signal == "diff"), (rc, found)   # (diff: peaks saturate, ties at the
+    assert rc == 0 and found > 0 and (found <= cap or hist_on), (rc, found)   # (diff: peaks saturate, ties at the
     # threshold can make more events than slots; the slots then hold the first `cap` of them and no filler)
     col = torch.arange(stride, device="cuda")[None, :]
     red = None
@@ -169,8 +184,8 @@ def events_case(src, a, results, info, bin_len):
         r = ctx.range_levels_result()
         t1 = now()
         assert r == (0, 0, cap, 0, cap), r
-        if diff:   # (start - 1, len + 1) where there is a sample in front; position r of the range is column r + pre
-            pre = ((st > 0) & (ln > 0)).to(torch.int64)
+        if hist_on:   # (start - 1, len + 1) where there is a sample in front; position r of the range is column r + pre
+            pre = torch.where(ln > 0, st.clamp(max=hist), 0)
             st_a, ln_a = st - pre, ln + pre.to(torch.int32)
             torch.cuda.synchronize()
         else:
@@ -182,10 +197,14 @@ def events_case(src, a, results, info, bin_len):
         assert r[:2] == (0, 0), r
         mask = col < ln[:, None]
         w = buf.to(torch.int32)
-        if diff:
+        if hist_on:
             at = col + pre[:, None]
-            y = torch.clamp(w.gather(1, at) - w.gather(1, (at - 1).clamp(min=0)), -32768, 32767)
-            mask = mask & ~((pre == 0)[:, None] & (col == 0))
+            if a.signal == "diff":
+                y = torch.clamp(w.gather(1, at) - w.gather(1, (at - 1).clamp(min=0)), -32768, 32767)
+            else:
+                acc = sum(c * w.gather(1, (at - t).clamp(min=0)).to(torch.int64) for t, c in enumerate(a.taps))
+                y = torch.clamp(acc >> a.shift, -32768, 32767).to(torch.int32)
+            mask = mask & (col + pre[:, None] >= hist)
             red = (torch.where(mask, y, 32767).min(1).values, torch.where(mask, y, -32768).max(1).values,
                    torch.where(mask, y, 0).sum(1, dtype=torch.int64), torch.where(mask, y * y, 0).sum(1, dtype=torch.int64),
                    mask.sum(1))
@@ -205,7 +224,7 @@ def events_case(src, a, results, info, bin_len):
         timed(results, name + "_route_a_torch", rep, a.warmup, t3 - t2)
         timed(results, name + "_route_b", rep, a.warmup, t4 - t3)
     got = records(lv)
-    counts = red[4].cpu().numpy().astype(np.uint32) if diff else ln.cpu().numpy().view(np.uint32)
+    counts = red[4].cpu().numpy().astype(np.uint32) if hist_on else ln.cpu().numpy().view(np.uint32)
     want_a = as_records(*(t.cpu().numpy() for t in red[:4]), counts)
     same = np.array_equal(got, want_a) and np.array_equal(got, records(ev_lv)) and np.array_equal(got, records(ev_lv2)) and \
         not status.cpu().numpy().any()
@@ -239,7 +258,7 @@ def cases(src, a, results, info):
 
 def config3(ctx, a, results, info):
     lib = x3hip.lib()
-    n, p, sig = a.samples, x3hip.Params.default(), x3hip.level_signal(a.signal)
+    n, p, sig = a.samples, x3hip.Params.default(), a.fir or x3hip.level_signal(a.signal)
     wav = torch.empty(n + 32, dtype=torch.int16, device="cuda")
     ctx.synth_dev(2, 0x58330003, 0, n, wav.data_ptr())
     ctx.sync()
@@ -257,11 +276,15 @@ def config3(ctx, a, results, info):
     s = (x.data_ptr(), pos, off.data_ptr(), so.data_ptr(), F, p)
     src = Source(
         ctx, "config3", 192_000, [n],
-        lambda d_e, d_s, d_l, k, bl, stride, d_lv, c, d_off, d_st: ctx.signal_range_levels_dev(*s, d_s, d_l, k, bl, stride, d_lv, c,
-                                                                                               d_off, d_st, idx.data_ptr(), 32, sig),
+        (lambda d_e, d_s, d_l, k, bl, stride, d_lv, c, d_off, d_st: ctx.fir_range_levels_dev(*s, d_s, d_l, k, bl, stride, d_lv, c,
+                                                                                             d_off, d_st, idx.data_ptr(), 32, sig))
+        if a.fir else
+        (lambda d_e, d_s, d_l, k, bl, stride, d_lv, c, d_off, d_st: ctx.signal_range_levels_dev(*s, d_s, d_l, k, bl, stride, d_lv, c,
+                                                                                                d_off, d_st, idx.data_ptr(), 32, sig)),
         lambda d_e, d_s, d_l, k, stride, d_out, oc, d_off, d_st: ctx.decode_ranges_dev(*s, d_s, d_l, k, stride, d_out, oc, 0, d_off,
                                                                                        d_st, idx.data_ptr(), 32),
-        lambda bl, d_lv, rows: ctx.signal_levels_dev(*s, bl, d_lv, rows, None, idx.data_ptr(), 32, sig),
+        (lambda bl, d_lv, rows: ctx.fir_levels_dev(*s, bl, d_lv, rows, None, idx.data_ptr(), 32, sig)) if a.fir else
+        (lambda bl, d_lv, rows: ctx.signal_levels_dev(*s, bl, d_lv, rows, None, idx.data_ptr(), 32, sig)),
         lambda d_lv, rows, bl, rule, d_e, d_s, d_l, d_el, c, d_c: ctx.events_dev(d_lv, rows, bl, so.data_ptr() + 8 * F, rule, d_s, d_l,
                                                                                 d_el, c, d_c),
         lambda bl: np.array([0, -(-n // bl)], dtype=np.uint64))
@@ -295,13 +318,17 @@ def corpus_a(ctx, a, results, info):
     offs = [int(fo[first[c]]) for c in range(n_clips)]
     lens = [int(fo[first[c + 1]]) - offs[c] for c in range(n_clips)]
     corpus = x3hip.Corpus(ctx, (d_x3, pos), offs, lens, seg_blocks=32)
-    sig = x3hip.level_signal(a.signal)
+    sig = a.fir or x3hip.level_signal(a.signal)
     src = Source(
         ctx, "corpus_a", 44_100, ns,
-        lambda d_e, d_s, d_l, k, bl, stride, d_lv, c, d_o, d_st: corpus.range_levels_into(d_e, d_s, d_l, k, bl, stride, d_lv, c, d_o, d_st,
-                                                                                          signal=sig),
+        (lambda d_e, d_s, d_l, k, bl, stride, d_lv, c, d_o, d_st: corpus.fir_range_levels_into(d_e, d_s, d_l, k, bl, stride, d_lv, c, d_o,
+                                                                                               d_st, sig))
+        if a.fir else
+        (lambda d_e, d_s, d_l, k, bl, stride, d_lv, c, d_o, d_st: corpus.range_levels_into(d_e, d_s, d_l, k, bl, stride, d_lv, c, d_o,
+                                                                                           d_st, signal=sig)),
         lambda d_e, d_s, d_l, k, stride, d_out, oc, d_o, d_st: corpus.ranges_into(d_e, d_s, d_l, k, stride, d_out, oc, 0, d_o, d_st),
-        lambda bl, d_lv, rows: ctx.corpus_signal_levels_dev(corpus, bl, d_lv, rows, None, sig),
+        (lambda bl, d_lv, rows: ctx.corpus_fir_levels_dev(corpus, bl, d_lv, rows, None, sig)) if a.fir else
+        (lambda bl, d_lv, rows: ctx.corpus_signal_levels_dev(corpus, bl, d_lv, rows, None, sig)),
         lambda d_lv, rows, bl, rule, d_e, d_s, d_l, d_el, c, d_c: corpus.events_into(d_lv, rows, bl, rule, d_e, d_s, d_l, d_el, c, d_c),
         lambda bl: corpus.levels_rows(bl))
     cases(src, a, results, info)
@@ -317,10 +344,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--cap", type=int, default=4096)
     ap.add_argument("--cases", default="config3,corpus")
-    ap.add_argument("--signal", default="samples", choices=["samples", "diff"])
+    ap.add_argument("--signal", default="samples", choices=["samples", "diff", "fir"])
+    ap.add_argument("--taps", default="1,-2,1", help="--signal fir: the taps c[0], c[1], ..")
+    ap.add_argument("--shift", type=int, default=0)
     ap.add_argument("--levels-bytes", type=float, default=16e9, help="route b runs where its records and workspace fit in this")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    a.taps = [int(c) for c in a.taps.split(",")]
+    a.fir = x3hip.Fir(a.taps, a.shift) if a.signal == "fir" else None
+    a.hist = {"samples": 0, "diff": 1, "fir": len(a.taps) - 1}[a.signal]      # samples in front of a position that its value takes
     torch.cuda.init()
     ctx = x3hip.Context(0)
     results, info = {}, {}
@@ -329,6 +361,7 @@ def main():
     if "corpus" in a.cases:
         corpus_a(ctx, a, results, info)
     out = {"samples": a.samples, "reps": a.reps, "signal": a.signal, "cases": info,
+           **({"taps": a.taps, "shift": a.shift} if a.fir else {}),
            "ms_median": {k: round(float(np.median(v)), 4) for k, v in results.items()},
            "ms_min": {k: round(float(np.min(v)), 4) for k, v in results.items()},
            "ms_max": {k: round(float(np.max(v)), 4) for k, v in results.items()}}

@@ -2431,15 +2431,15 @@ static bool range_levels_args_ok(const x3_ctx* c, const uint64_t* d_starts, cons
 
 // The pairs (range, covering frame) the workspace holds: all a call can have, or four times what disjoint ranges need
 // (n_frames + n_ranges: sliding windows with up to 75 % overlap fit).  Pairs beyond it are the fix-up's: time, not results.
-// lead (X3_LEVEL_SIGNAL_DIFF): a range may have one more pair, its lead frame -- a frame of the same stream or entry, so
-// n * max_frames still holds them all.
-uint64_t range_levels_pairs(uint64_t n, uint64_t F, uint64_t max_frames, bool lead) {
-  return std::min<uint64_t>(n * max_frames, 4 * (F + n) + (lead ? n : 0));   // (n < 2^31, max_frames <= F < 2^31: no wrap)
+// lead_frames (1: X3_LEVEL_SIGNAL_DIFF; T - 1 <= 7: the FIR calls): a range may have that many more pairs, its lead frames
+// -- frames of the same stream or entry, so n * max_frames still holds them all.
+uint64_t range_levels_pairs(uint64_t n, uint64_t F, uint64_t max_frames, uint64_t lead_frames) {
+  return std::min<uint64_t>(n * max_frames, 4 * (F + n) + lead_frames * n);   // (n < 2^31, max_frames <= F < 2^31: no wrap)
 }
 
 // The workspace (RLevWs, x3_internal.h): per range the plan, the two scans, the rows that have room, the plan's starts; per
 // frame the verdicts; per pair its cut, the scan of the bin counts; the partial rows; replay scratch; the summary; diff
-// (X3_LEVEL_SIGNAL_DIFF) only, behind it: per frame its last sample, per range whether its plan begins with a lead frame
+// (X3_LEVEL_SIGNAL_DIFF, and the FIR calls) only, behind it: per frame its last sample, per range its plan's lead frames
 size_t range_levels_carve(char* base, uint64_t n, uint64_t F, uint64_t P, uint64_t rows_cap, uint64_t fix_waves,
                           uint32_t scratch_per, RLevWs* w, bool diff) {
   BlockCarver k{base, 0};
@@ -2463,27 +2463,32 @@ size_t range_levels_carve(char* base, uint64_t n, uint64_t F, uint64_t P, uint64
 // and returns the starts the later kernels read (the caller's, or the plan's gstart), as in windows_launch.  signal:
 // X3_LEVEL_SIGNAL_SAMPLES, or X3_LEVEL_SIGNAL_DIFF -- the lead kernel behind the plan (d_ent, n_ent, d_entries: the corpus's
 // table and the caller's entries, NULL for a stream), the other instance of the accumulate and fix-up kernels, which leave
-// every good frame's last sample in the workspace, and the seam kernel behind them.
+// every good frame's last sample in the workspace, and the seam kernel behind them.  fir (checked: levels_fir_taps) instead of
+// a signal (x3_fir_range_levels_dev / x3_corpus_fir_range_levels_dev): the lead kernel for T taps, the
+// X3RLevFir instance of the accumulate kernel, which leaves an edge record per (frame, stretch) in fir_ws as in levels_launch,
+// a fix-up of its own and x3_range_levels_fir_seam_kernel behind the merge.  The workspace is the DIFF call's (lead[]).
 template <class Plan>
 static int range_levels_launch(x3_ctx* c, const FrameSource& s, const uint32_t* d_lens, uint64_t n, uint64_t bin_len,
                                uint64_t row_stride, x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets,
                                int32_t* d_status, int signal, const x3_corpus_entry* d_ent, uint64_t n_ent,
-                               const uint32_t* d_entries, Plan plan_step) {
-  const bool diff = signal == X3_LEVEL_SIGNAL_DIFF;
+                               const uint32_t* d_entries, Plan plan_step, const X3FirTaps* fir = nullptr) {
+  const bool diff = !fir && signal == X3_LEVEL_SIGNAL_DIFF, lead = diff || fir;
+  const uint64_t lead_frames = fir ? fir->T - 1 : diff ? 1 : 0;   // what a range's plan may hold in front of its covering frames
   HIPCHK(c, hipSetDevice(c->device));
-  const uint64_t P = range_levels_pairs(n, s.F, s.max_frames, diff), cap = rows_cap + P;
+  const uint64_t P = range_levels_pairs(n, s.F, s.max_frames, lead_frames), cap = rows_cap + P;
   const uint32_t scratch_per = levels_scratch_per(s.dp.block_len);
   const uint64_t fix_waves = levels_fix_waves(n, scratch_per);
   RLevWs w;
   int rc;
-  if ((rc = ensure(c, c->rlev_ws, range_levels_carve(nullptr, n, s.F, P, rows_cap, fix_waves, scratch_per, &w, diff)))) return rc;
-  range_levels_carve((char*)c->rlev_ws.p, n, s.F, P, rows_cap, fix_waves, scratch_per, &w, diff);
+  if ((rc = ensure(c, c->rlev_ws, range_levels_carve(nullptr, n, s.F, P, rows_cap, fix_waves, scratch_per, &w, lead)))) return rc;
+  range_levels_carve((char*)c->rlev_ws.p, n, s.F, P, rows_cap, fix_waves, scratch_per, &w, lead);
+  if (fir && (rc = ensure(c, c->fir_ws, (size_t)(s.F * s.nseg) * sizeof(X3FirEdge)))) return rc;
   // grids: the counts are on the device and every kernel walks them grid-stride.  What a range has on average is at most
   // rows_cap / n rows (or the stride) of bin_len positions: the caller's words, possibly far above what is drawn, so a range
   // covers no more frames than the stream (or the longest entry) has and a call no more pairs than P.
   const uint64_t rows_hint = row_stride ? row_stride : std::max<uint64_t>(rows_cap / n, 1);
   const uint64_t len_hint = bin_len && bin_len <= 0xFFFFFFFFull / rows_hint ? rows_hint * bin_len : 0xFFFFFFFFull;
-  const uint64_t frames_per = std::max<uint64_t>(1, std::min(len_hint / (s.spf ? s.spf : 1) + 2 + (diff ? 1 : 0), s.max_frames));
+  const uint64_t frames_per = std::max<uint64_t>(1, std::min(len_hint / (s.spf ? s.spf : 1) + 2 + lead_frames, s.max_frames));
   const uint64_t cov_hint = std::min(n * frames_per, P), item_hint = std::min<uint64_t>(cov_hint, 256ull * X3W_GRID_LIMIT) * s.nseg;
   // the caller's records: padded, all n * stride are written; packed, a range has no more rows than the frames it can cover
   // hold bins (one with bin_len 0 or above any length), so a roomy rows_cap does not size the prep, init and merge grids
@@ -2494,6 +2499,9 @@ static int range_levels_launch(x3_ctx* c, const FrameSource& s, const uint32_t* 
   if (diff)
     hipLaunchKernelGGL(x3_range_levels_lead_kernel, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, s.d_sample_offsets, d_ent, n_ent,
                        d_entries, d_starts, d_lens, n, w.plan, w.lead);
+  if (fir)
+    hipLaunchKernelGGL(x3_range_levels_fir_lead_kernel, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, s.d_sample_offsets, d_ent,
+                       n_ent, d_entries, d_starts, d_lens, n, (uint32_t)lead_frames, w.plan, w.lead);
   hipLaunchKernelGGL(x3_range_levels_scan_kernel, dim3(1), dim3(1024), 0, c->stream, w.plan, n, d_lens, bin_len, row_stride, rows_cap,
                      w.cov_off, w.row_off, w.erows, d_row_offsets, w.sum);
   hipLaunchKernelGGL(x3_window_check_kernel, dim3(grid_for(cov_hint, 4)), dim3(256), 0, c->stream, s.d_x3, s.x3_len, s.d_frame_offsets,
@@ -2517,7 +2525,17 @@ static int range_levels_launch(x3_ctx* c, const FrameSource& s, const uint32_t* 
                        row_stride, P, cap, (const unsigned long long*)w.prow, (const int32_t*)w.fst, d_levels, d_status, w.scratch,
                        scratch_per, w.sum, tail, (const uint32_t*)w.lead);
   };
-  if (diff) decode(X3LevDiff{}, w.tail);
+  if (fir) {
+    const X3LevFirTail ft{*fir, (X3FirEdge*)c->fir_ws.p, s.nseg};
+    hipLaunchKernelGGL(x3_range_levels_accum_kernel<X3RLevFir>, dim3(grid_for(item_hint, 256)), dim3(256), 0, c->stream, s.d_x3,
+                       s.x3_len, s.d_frame_offsets, s.dp, s.idx, s.seg_blocks, s.nseg, bin_len, (const unsigned long long*)w.cov_off, n,
+                       P, cap, (const X3RLevPair*)w.pairs, (const unsigned long long*)w.prow, w.rows, w.fst, ft);
+    hipLaunchKernelGGL(x3_range_levels_fir_fixup_kernel, dim3((unsigned)((fix_waves + 3) / 4)), dim3(256), 0, c->stream, s.d_x3,
+                       s.d_frame_offsets, s.d_sample_offsets, d_starts, d_lens, (const X3WinPlan*)w.plan, n, s.dp, s.idx, s.seg_blocks,
+                       s.nseg, bin_len, (const unsigned long long*)w.cov_off, (const unsigned long long*)w.row_off,
+                       (const uint32_t*)w.erows, row_stride, P, cap, (const unsigned long long*)w.prow, (const int32_t*)w.fst,
+                       d_levels, d_status, w.scratch, scratch_per, w.sum, ft, (const uint32_t*)w.lead);
+  } else if (diff) decode(X3LevDiff{}, w.tail);
   else decode(X3LevSamples{}, X3LevNoTail{});
   hipLaunchKernelGGL(x3_range_levels_merge_kernel, dim3(grid_for(rec_hint + cov_hint, 256)), dim3(256), 0, c->stream,
                      (const X3RLevPair*)w.pairs, (const unsigned long long*)w.cov_off, n, P, cap, (const unsigned long long*)w.prow,
@@ -2528,6 +2546,11 @@ static int range_levels_launch(x3_ctx* c, const FrameSource& s, const uint32_t* 
                        s.d_frame_offsets, bin_len, (const X3RLevPair*)w.pairs, (const unsigned long long*)w.cov_off, n, P, cap,
                        (const unsigned long long*)w.prow, (const unsigned long long*)w.row_off, (const uint32_t*)w.erows, row_stride,
                        (const int32_t*)w.fst, (const int32_t*)w.tail, d_levels);
+  if (fir && fir->T > 1)
+    hipLaunchKernelGGL(x3_range_levels_fir_seam_kernel, dim3(grid_for(item_hint, 256)), dim3(256), 0, c->stream, s.dp.block_len, s.idx,
+                       s.seg_blocks, s.nseg, bin_len, (const X3RLevPair*)w.pairs, (const unsigned long long*)w.cov_off, n, P, cap,
+                       (const unsigned long long*)w.prow, (const unsigned long long*)w.row_off, (const uint32_t*)w.erows, row_stride,
+                       (const int32_t*)w.fst, (const X3FirEdge*)c->fir_ws.p, s.nseg, *fir, d_levels);
   HIPCHK(c, hipGetLastError());
   c->range_levels.pending = true;
   c->range_levels.count = n;
@@ -2535,14 +2558,14 @@ static int range_levels_launch(x3_ctx* c, const FrameSource& s, const uint32_t* 
   return X3_OK;
 }
 
-extern "C" int x3_signal_range_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
-                                          const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
-                                          const uint64_t* d_seg_index, uint32_t seg_blocks, const uint64_t* d_starts,
-                                          const uint32_t* d_lens, uint64_t n_ranges, uint64_t bin_len, uint64_t row_stride,
-                                          x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status,
-                                          int signal) {
-  if (!c || !levels_signal_ok(signal) ||
-      !range_levels_args_ok(c, d_starts, d_lens, n_ranges, row_stride, d_levels, rows_cap, d_row_offsets, d_status))
+// the stream form of the range-levels calls behind the check of the signal or the taps (fir != NULL: the FIR call)
+static int stream_range_levels_call(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
+                                    const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
+                                    const uint64_t* d_seg_index, uint32_t seg_blocks, const uint64_t* d_starts,
+                                    const uint32_t* d_lens, uint64_t n_ranges, uint64_t bin_len, uint64_t row_stride,
+                                    x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status, int signal,
+                                    const X3FirTaps* fir) {
+  if (!range_levels_args_ok(c, d_starts, d_lens, n_ranges, row_stride, d_levels, rows_cap, d_row_offsets, d_status))
     return X3_ERR_BAD_ARG;
   FrameSource s;
   const int rc = stream_source(d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, p, d_seg_index, seg_blocks, &s);
@@ -2553,7 +2576,31 @@ extern "C" int x3_signal_range_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64
                                hipLaunchKernelGGL(x3_range_plan_kernel, grid, dim3(256), 0, c->stream, d_sample_offsets, n_frames,
                                                   d_starts, d_lens, n_ranges, plan, sum);
                                return d_starts;
-                             });
+                             }, fir);
+}
+
+extern "C" int x3_signal_range_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
+                                          const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
+                                          const uint64_t* d_seg_index, uint32_t seg_blocks, const uint64_t* d_starts,
+                                          const uint32_t* d_lens, uint64_t n_ranges, uint64_t bin_len, uint64_t row_stride,
+                                          x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status,
+                                          int signal) {
+  if (!c || !levels_signal_ok(signal)) return X3_ERR_BAD_ARG;
+  return stream_range_levels_call(c, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, p, d_seg_index, seg_blocks, d_starts,
+                                  d_lens, n_ranges, bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status, signal, nullptr);
+}
+
+extern "C" int x3_fir_range_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
+                                       const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
+                                       const uint64_t* d_seg_index, uint32_t seg_blocks, const uint64_t* d_starts,
+                                       const uint32_t* d_lens, uint64_t n_ranges, uint64_t bin_len, uint64_t row_stride,
+                                       x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status,
+                                       const x3_level_fir* fir) {
+  X3FirTaps k;
+  if (!c || !levels_fir_taps(fir, &k)) return X3_ERR_BAD_ARG;
+  return stream_range_levels_call(c, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, p, d_seg_index, seg_blocks, d_starts,
+                                  d_lens, n_ranges, bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status,
+                                  X3_LEVEL_SIGNAL_SAMPLES, &k);
 }
 
 extern "C" int x3_range_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
@@ -2570,7 +2617,7 @@ extern "C" int x3_range_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_l
 static int corpus_range_levels_call(x3_ctx* c, const x3_corpus* k, const char* entry, const uint32_t* d_entries,
                                     const uint64_t* d_starts, const uint32_t* d_lens, uint64_t n_ranges, uint64_t bin_len,
                                     uint64_t row_stride, x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets,
-                                    int32_t* d_status, int signal) {
+                                    int32_t* d_status, int signal, const X3FirTaps* fir = nullptr) {
   if (!c || !levels_signal_ok(signal) || !k || !d_entries || (reinterpret_cast<uintptr_t>(d_entries) & 3u)) return X3_ERR_BAD_ARG;
   if (!range_levels_args_ok(c, d_starts, d_lens, n_ranges, row_stride, d_levels, rows_cap, d_row_offsets, d_status))
     return X3_ERR_BAD_ARG;
@@ -2584,7 +2631,7 @@ static int corpus_range_levels_call(x3_ctx* c, const x3_corpus* k, const char* e
                                                   s.d_sample_offsets, s.F, d_entries, d_starts, d_lens, n_ranges, plan, gstart,
                                                   sum);
                                return gstart;
-                             });
+                             }, fir);
 }
 
 extern "C" int x3_corpus_range_levels_dev(x3_ctx* c, const x3_corpus* k, const uint32_t* d_entries, const uint64_t* d_starts,
@@ -2600,6 +2647,16 @@ extern "C" int x3_corpus_signal_range_levels_dev(x3_ctx* c, const x3_corpus* k, 
                                                  int signal) {
   return corpus_range_levels_call(c, k, "x3_corpus_signal_range_levels_dev", d_entries, d_starts, d_lens, n_ranges, bin_len,
                                   row_stride, d_levels, rows_cap, d_row_offsets, d_status, signal);
+}
+
+extern "C" int x3_corpus_fir_range_levels_dev(x3_ctx* c, const x3_corpus* k, const uint32_t* d_entries, const uint64_t* d_starts,
+                                              const uint32_t* d_lens, uint64_t n_ranges, uint64_t bin_len, uint64_t row_stride,
+                                              x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status,
+                                              const x3_level_fir* fir) {
+  X3FirTaps taps;
+  if (!c || !levels_fir_taps(fir, &taps)) return X3_ERR_BAD_ARG;
+  return corpus_range_levels_call(c, k, "x3_corpus_fir_range_levels_dev", d_entries, d_starts, d_lens, n_ranges, bin_len, row_stride,
+                                  d_levels, rows_cap, d_row_offsets, d_status, X3_LEVEL_SIGNAL_SAMPLES, &taps);
 }
 
 extern "C" int x3_range_levels_result(x3_ctx* c, uint64_t* n_bad, uint64_t* first_bad, int* first_bad_status,

@@ -153,7 +153,7 @@ struct x3_ctx {
   DevBuf idx_cand, idx_keys, idx_vals, idx_J, idx_S, idx_L, idx_sum;  // x3_index_dev scratch
   DevBuf idx_wg, idx_sorted, idx_scan;  // ... of its fast path: candidates per scanning workgroup, in order, the scans
   DevBuf lev_ws;   // x3_levels_dev / x3_corpus_levels_dev: verdicts, plans, the frames' partial rows, replay scratch, summary (x3_levels_kernel.h)
-  DevBuf fir_ws;   // x3_fir_levels_dev / x3_corpus_fir_levels_dev only, beside lev_ws: an edge record per (frame, stretch) (X3FirEdge, x3_levels_kernel.h)
+  DevBuf fir_ws;   // the FIR calls only (x3_fir_levels_dev, x3_fir_range_levels_dev and their corpus forms), beside lev_ws / rlev_ws: an edge record per (frame, stretch) (X3FirEdge, x3_levels_kernel.h)
   DevBuf ev_ws;    // x3_events_dev / x3_corpus_events_dev: row flags, tile totals, run tables, piece scan, summary, row prefix (x3_events_kernel.h)
   DevBuf q_ws;     // x3_level_quantiles_dev / x3_level_thresholds_dev and their corpus forms: (key, entry) per row, histograms, select state, summary, row prefix (x3_quantiles_kernel.h)
   DevBuf rlev_ws;  // x3_range_levels_dev / x3_corpus_range_levels_dev: plans, scans, verdicts, pairs, their partial rows, replay scratch, summary (x3_range_levels_kernel.h)
@@ -494,9 +494,9 @@ struct RLevWs {
   int32_t* fst;                                                                                                  // per frame
   X3RLevPair* pairs; unsigned long long* prow; x3_level* rows;   // per pair (prow: P + 1 words); the partial rows
   int16_t* scratch; X3RLevSummary* sum;
-  int32_t* tail; uint32_t* lead;   // diff only (NULL otherwise): per frame, per range
+  int32_t* tail; uint32_t* lead;   // diff and FIR only (NULL otherwise): per frame (diff's last samples), per range (its lead frames)
 };
-X3_INTERNAL uint64_t range_levels_pairs(uint64_t n, uint64_t F, uint64_t max_frames, bool lead = false);
+X3_INTERNAL uint64_t range_levels_pairs(uint64_t n, uint64_t F, uint64_t max_frames, uint64_t lead_frames = 0);
 X3_INTERNAL size_t range_levels_carve(char* base, uint64_t n, uint64_t F, uint64_t P, uint64_t rows_cap, uint64_t fix_waves,
                                       uint32_t scratch_per, RLevWs* w, bool diff = false);
 // ... and of a quantiles or thresholds call (q_ws; x3_quantiles_kernel.h): n_rows records, n_ent entries (1 for a stream),

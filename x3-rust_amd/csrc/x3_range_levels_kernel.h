@@ -30,6 +30,11 @@
 //  x3_range_levels_lead_kernel   -- behind the plan: a range that starts at a frame's first sample gets the frame in front
 //  x3_range_levels_seam_kernel   -- behind the accumulate kernel: a lane per pair, the difference across the frame's front seam
 // (both at the end of this file)
+// x3_fir_range_levels_dev / x3_corpus_fir_range_levels_dev run the accumulate kernel's third instance,
+// X3RLevFir, between a lead kernel, a fix-up and a seam kernel of their own (FIR RANGE LEVELS, at the end of this file):
+//  x3_range_levels_fir_lead_kernel  -- behind the plan: up to T - 1 frames in front of a range that starts early in its frame
+//  x3_range_levels_fir_fixup_kernel -- x3_range_levels_fixup_kernel with the last seven samples carried from frame to frame
+//  x3_range_levels_fir_seam_kernel  -- behind the merge: a lane per (pair, stretch), the stretch's first T - 1 positions
 //
 // CAPACITY.  The workspace holds P pairs and cap = rows_cap + P partial rows, both sized on the host.  A pair with q >= P or
 // whose rows end behind cap has no rows: accumulate and merge skip it (x3rl_no_rows, recomputed from q and the scan) and the
@@ -154,7 +159,9 @@ x3_range_levels_init_kernel(const unsigned long long* __restrict__ cov_off, uint
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < used; i += (uint64_t)gridDim.x * blockDim.x) rows[i] = id;
 }
 
-// ---- accumulate: a lane per (pair, stretch) into the pair's own rows.  Signal: X3LevSamples, or X3LevDiff, whose lanes take
+// ---- accumulate: a lane per (pair, stretch) into the pair's own rows.  Signal: X3LevSamples; X3RLevFir, whose lanes add the
+// positions whose T samples they decoded themselves, inside or in front of [lo, hi), and leave the edge record of their
+// (frame, stretch) -- several pairs of one frame write the same values; or X3LevDiff, whose lanes take
 // the stretch's seed from x3w_stretch, see the samples outside [lo, hi) without counting them (the sample in front of lo is
 // sample lo's `prev`), and whose lane at the frame's end stores the frame's last sample to tail[f].  A pair with an empty cut
 // (a lead frame) runs its stretches for the proof and the tail and touches no row: cnt is 0.
@@ -185,6 +192,10 @@ x3_range_levels_accum_kernel(const uint8_t* __restrict__ x3, uint64_t len, const
     // the range, if any, is sample max(s0, lo)
     const uint64_t s0 = j ? 1u + (uint64_t)sb * j * p.block_len : 0u;
     [[maybe_unused]] Signal sig;
+    if constexpr (Signal::kFir) {
+      sig.k = tail.k;
+      sig.edge = tail.edges + (pr.f * tail.stride + j);   // (pr.f < F, j < ns <= stride: below F * stride)
+    }
     const int r = x3l_bin_samples<Signal>(
         (uint64_t)pr.r0 + (s0 > lo ? s0 - lo : 0u), bl,
         [&](auto put_at) {
@@ -194,6 +205,7 @@ x3_range_levels_accum_kernel(const uint8_t* __restrict__ x3, uint64_t len, const
             return x3w_stretch(x3, len, frame_off[pr.f], p, idx, segd, sb, nseg, pr.f, j, put_at);
         },
         [&](uint32_t s) { return s - lo < span; }, flush, &sig);
+    if constexpr (Signal::kFir) sig.end();
     if (r < 0) atomicOr(&fst[pr.f], X3W_FLAG);
   }
 }
@@ -393,6 +405,322 @@ x3_range_levels_seam_kernel(const uint8_t* __restrict__ x3, uint64_t len, const 
           const int32_t head = (int32_t)(int16_t)(uint16_t)(x3w_be32_at(x3, len, frame_off[pr.f] + 20u) >> 16);
           a.add_value(x3l_diff(head, tail[pp.f]));
           key = x3rl_base(row_off, stride, pr.w) + bin;
+        }
+      }
+    }
+    x3l_merge_runs(levels, key, a, lane);
+  }
+}
+
+// ---- FIR RANGE LEVELS (x3_fir_range_levels_dev / x3_corpus_fir_range_levels_dev)
+// The call cuts the stream's or entry's FIR signal (x3_levels_kernel.h, X3LevFir): position start + r adds y[start + r] when
+// all T samples under the taps exist in the stream or entry and lie in frames that end with status 0.
+//
+// WHO ADDS A POSITION.  Sample s of covering frame f of range w (pair q), inside the cut [lo, hi), one owner by two tests
+// that every side makes the same way:
+//   pair q is not fast (x3rl_fast)              -- the fix-up wave, which replays the frame and forms every position from the
+//                                                  history it carries;
+//   fast, s < T - 1                             -- the fix-up wave again: the taps reach in front of the frame, and what lies
+//                                                  there (a fast frame, a replayed one, a failed one, nothing) only the wave
+//                                                  that walks the range's frames in order knows.  It reads the frame's first
+//                                                  samples from its edge records' heads;
+//   fast, s >= T - 1, s - s0 >= T - 1           -- the accumulate lane of the stretch (s0: its first sample), which decoded all
+//                                                  T samples itself; into the pair's rows, merged because the pair is fast;
+//   fast, s >= T - 1, s - s0 < T - 1            -- x3_range_levels_fir_seam_kernel, from the heads of the stretch and the tails
+//                                                  of the stretches in front of it in the SAME frame: s >= T - 1, so they hold
+//                                                  all the history.
+// The fix-up writes no edge record: a frame it replays for one range (a pair without rows) may be another range's fast frame.
+// Edge records are read only for a fast pair's frame: q < P, the frame's word X3D_OK behind the accumulate kernel, so that
+// pair's own lanes ran every stretch to its proof and stored all ns records; index f * stride + j with f a frame of the
+// plan (< F) and j < ns <= stride.
+
+// x3l_fir_value without HIP's __mul24: that wrapper is a static inline function of the HIP headers, and every further kernel
+// that calls it changes how the compiler treats it in the kernels that already did -- the X3LevFir instances of the levels
+// kernels came out with other register numbers and one other multiply, and they are to stay the parent's instruction for
+// instruction.  Taps (16 bits by the host's check) and samples are sign-extended from 24 bits in the open, which is what
+// lets the compiler pick the full-rate 24-bit multiply by itself; the taps' extension is scalar and loop-invariant.
+__device__ __forceinline__ int32_t x3rl_mul24(int32_t c, int32_t v) {
+  return ((int32_t)((uint32_t)c << 8) >> 8) * ((int32_t)((uint32_t)v << 8) >> 8);
+}
+__device__ __forceinline__ int32_t x3rl_fir_value(const X3FirTaps& k, int32_t s, const int32_t (&d)[X3L_FIR_HIST]) {
+  int32_t acc = x3rl_mul24(k.c[0], s);
+#pragma unroll
+  for (int t = 1; t < X3L_FIR_TAPS; ++t) acc += x3rl_mul24(k.c[t], d[t - 1]);
+  return min(max(acc >> k.shift, -32768), 32767);
+}
+
+// The FIR signal of these kernels: X3LevFir's delay line and count (x3_levels_kernel.h) with x3rl_fir_value, in ONE copy for
+// both of its users.  kEdge (X3RLevFir, the accumulate kernel's): the lane leaves the edge record of its (frame, stretch) --
+// the heads stored as they pass, the rest by end().  Without (X3LevFirCarry, the fix-up's): no record is touched, the history
+// is the caller's to keep from frame to frame, and cnt is how many of the samples in d[] are valid.
+template <bool kEdge>
+struct X3RLevFirT {
+  static constexpr bool kDiff = false, kFir = true, kState = true;
+  using Tail = X3LevFirTail;
+  X3FirTaps k;   // (uniform: the kernel's argument)
+  X3FirEdge* edge = nullptr;
+  int32_t d[X3L_FIR_HIST] = {0, 0, 0, 0, 0, 0, 0};   // d[t]: the sample t + 1 positions in front of the current one
+  uint32_t cnt = 0;                                  // samples seen (what counts is cnt >= T - 1)
+  __device__ __forceinline__ void push(int32_t s) {
+    if constexpr (kEdge) {
+      if (cnt < (uint32_t)X3L_FIR_HIST) edge->head[cnt] = (int16_t)s;
+    }
+    ++cnt;
+#pragma unroll
+    for (int t = X3L_FIR_HIST - 1; t >= 1; --t) d[t] = d[t - 1];
+    d[0] = s;
+  }
+  __device__ __forceinline__ void add(X3LevAcc& a, uint32_t v) {
+    const int32_t s = (int32_t)(int16_t)(uint16_t)v;
+    if (cnt + 1u >= k.T) a.add_value(x3rl_fir_value(k, s, d));
+    push(s);
+  }
+  __device__ __forceinline__ void skip(uint32_t v) { push((int32_t)(int16_t)(uint16_t)v); }
+  // behind the stretch's last sample: the rest of the edge record
+  __device__ __forceinline__ void end() const {
+    static_assert(kEdge, "only the accumulate kernel's signal has an edge record");
+#pragma unroll
+    for (int t = 0; t < X3L_FIR_HIST; ++t) edge->tail[t] = (int16_t)d[t];
+    edge->n = cnt;
+  }
+};
+using X3RLevFir = X3RLevFirT<true>;
+using X3LevFirCarry = X3RLevFirT<false>;
+
+// hist[H] = v without a dynamic register index
+__device__ __forceinline__ void x3rl_fir_set(int32_t (&hist)[X3L_FIR_HIST], uint32_t H, int32_t v) {
+#pragma unroll
+  for (int q = 0; q < X3L_FIR_HIST; ++q) hist[q] = (uint32_t)q == H ? v : hist[q];
+}
+
+// y at the consecutive samples s_first + c, c < m <= 7, of a frame: hd[c] the samples, hist[h] the sample h + 1 in front of
+// s_first (h < H).  A position counts when its history is complete (c + H >= T - 1), s_from <= s < s_to and s lies in the
+// pair's cut (s - lo < span; its position behind the range's start is r0 + s - lo).  Bins that fill go to the range's records
+// `mine` (bin < R) at once; the open one stays in (a, cur) for the caller (cur ~0: none).
+__device__ __forceinline__ void x3rl_fir_front(const X3FirTaps& k, const int32_t (&hd)[X3L_FIR_HIST], uint32_t m,
+                                               const int32_t (&hist)[X3L_FIR_HIST], uint32_t H, uint32_t s_first, uint32_t s_from,
+                                               uint32_t s_to, uint32_t lo, uint32_t span, uint32_t r0, uint64_t bl, uint32_t R,
+                                               x3_level* __restrict__ mine, X3LevAcc& a, uint64_t& cur) {
+  const uint32_t need = k.T - 1u;
+#pragma unroll
+  for (int c = 0; c < X3L_FIR_HIST; ++c) {
+    const uint32_t s = s_first + (uint32_t)c;
+    if ((uint32_t)c < m && (uint32_t)c + H >= need && s >= s_from && s < s_to && s - lo < span) {
+      int32_t d[X3L_FIR_HIST];
+#pragma unroll
+      for (int t = 1; t < X3L_FIR_TAPS; ++t) d[t - 1] = c >= t ? hd[c - t] : hist[t - c - 1];
+      const uint64_t bin = ((uint64_t)r0 + (s - lo)) / bl;
+      if (bin < (uint64_t)R) {
+        if (bin != cur) {
+          if (cur != ~0ull) x3l_merge(mine + cur, a);
+          a.reset();
+          cur = bin;
+        }
+        a.add_value(x3rl_fir_value(k, hd[c], d));
+      }
+    }
+  }
+}
+
+// ---- lead: x3_range_levels_lead_kernel for T taps.  A range with len > 0 gets the ld frames in front of its first covering
+// frame fa, ld the smallest count with start - so[fa - ld] >= T - 1, not past the first frame of its stream or entry: those
+// frames hold the samples under the taps of the range's first positions.  At most T - 1 <= 7 steps whatever so[] says (a
+// checked frame has a sample; one that fails its check ends the history anyway).  lead[w] = ld; the frames are ordinary pairs
+// with an empty cut.  Bounds: fa - ld >= first >= 0, frames of the table the plan searched; ncov + ld <= F.
+__global__ void __launch_bounds__(256)
+x3_range_levels_fir_lead_kernel(const uint64_t* __restrict__ so, const x3_corpus_entry* __restrict__ ent, uint64_t n_ent,
+                                const uint32_t* __restrict__ entries, const uint64_t* __restrict__ starts,
+                                const uint32_t* __restrict__ lens, uint64_t n, uint32_t need, X3WinPlan* __restrict__ plan,
+                                uint32_t* __restrict__ lead) {
+  for (uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; w < n; w += (uint64_t)gridDim.x * blockDim.x) {
+    X3WinPlan pl = plan[w];
+    uint32_t ld = 0;
+    if (pl.status == X3D_OK && pl.ncov && lens[w] && need) {
+      uint64_t first = 0;
+      bool known = true;
+      if (ent) {
+        const uint32_t e = entries[w];
+        known = e < n_ent;   // (the plan has refused the others)
+        if (known) first = ent[e].first_frame;
+      }
+      const uint64_t start = starts[w];
+      if (known && pl.fa >= first) {
+        const uint32_t most = (uint32_t)min((uint64_t)min(need, (uint32_t)X3L_FIR_HIST), pl.fa - first);
+        while (ld < most) {
+          const uint64_t pos = so[pl.fa - ld];
+          if (pos <= start && start - pos >= (uint64_t)need) break;
+          ++ld;
+        }
+        if (ld) {
+          pl.fa -= ld;
+          pl.ncov += ld;
+          plan[w] = pl;
+        }
+      }
+    }
+    lead[w] = ld;
+  }
+}
+
+// ---- fix-up: a wave per range (lane 0 works), frames in order, as x3_range_levels_fixup_kernel.  The wave carries the last
+// seven samples in front of the current frame and how many of them are valid (X3LevFirCarry): none at the plan's first frame
+// and behind a frame that ends with a status, all that a frame with status 0 leaves.  A frame it replays (flagged, or a pair
+// without rows) is one stretch whose every position it forms from that history, into the caller's records.  Of a fast frame
+// it forms the positions s < T - 1 from the heads of the frame's edge records, and refills the history from their tails.  A
+// lead frame (k < lead[w]) never gives the range its status.  A lead-frame pair it decodes counts as a replay.
+__global__ void __launch_bounds__(256)
+x3_range_levels_fir_fixup_kernel(const uint8_t* __restrict__ x3, const uint64_t* __restrict__ frame_off, const uint64_t* __restrict__ so,
+                                 const uint64_t* __restrict__ starts, const uint32_t* __restrict__ lens,
+                                 const X3WinPlan* __restrict__ plan, uint64_t n, X3DevParams p, const uint2* __restrict__ idx,
+                                 uint32_t sb, uint32_t nseg, uint64_t bin_len, const unsigned long long* __restrict__ cov_off,
+                                 const unsigned long long* __restrict__ row_off, const uint32_t* __restrict__ erows, uint64_t stride,
+                                 uint64_t P, uint64_t cap, const unsigned long long* __restrict__ prow,
+                                 const int32_t* __restrict__ fst, x3_level* __restrict__ levels, int32_t* __restrict__ status,
+                                 int16_t* __restrict__ scratch, uint32_t scratch_per, X3RLevSummary* __restrict__ sum,
+                                 X3LevFirTail ft, const uint32_t* __restrict__ lead) {
+  const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+  const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (threadIdx.x & 63u) return;
+  int16_t* const blk = scratch + wave * (uint64_t)scratch_per;
+  const uint64_t bl = x3l_bin_len(bin_len);
+  const uint32_t ns = x3w_index_ok(idx, sb) ? nseg : 1u;
+  const uint32_t need = ft.k.T - 1u;
+  for (uint64_t w = wave; w < n; w += waves) {
+    const X3WinPlan pl = plan[w];
+    int32_t st = pl.status;
+    uint32_t replayed = 0;
+    if (st == X3D_OK) {
+      const uint64_t start = starts[w], q0 = cov_off[w];
+      const uint32_t L = lens[w], R = erows[w], ld = lead[w];
+      x3_level* const mine = levels + x3rl_base(row_off, stride, w);
+      X3LevFirCarry hs;
+      hs.k = ft.k;
+      for (uint32_t k = 0; k < pl.ncov; ++k) {
+        const uint64_t f = pl.fa + k;
+        int32_t fs = fst[f];
+        const bool fast = x3rl_fast(fs, prow, q0 + k, P, cap);
+        uint32_t lo, hi, r0;
+        (void)x3rl_cut(so, f, start, L, lo, hi, r0);   // (none: lo = hi = r0 = 0, no sample is kept)
+        const uint32_t span = hi - lo;
+        if (fs == X3W_FLAG || (fs == X3D_OK && !fast)) {
+          const uint8_t* const payload = x3 + frame_off[f] + 20u;
+          fs = x3w_replay_frame(payload, p, blk, [](uint32_t, uint32_t) {});
+          if (fs == X3D_OK) {   // every block decodes: once more, into the records and the history
+            auto flush = [&](uint64_t bin, const X3LevAcc& a) {
+              if (bin < (uint64_t)R) x3l_merge(mine + bin, a);
+            };
+            (void)x3l_bin_samples<X3LevFirCarry>(
+                r0, bl, [&](auto put_at) { return x3w_replay_frame(payload, p, blk, put_at); },
+                [&](uint32_t s) { return s - lo < span; }, flush, &hs);
+          }
+          ++replayed;
+        } else if (fs == X3D_OK) {   // fast: every stretch proven, its edge records stored by this pair's own lanes
+          const X3FirEdge* const fe = ft.edges + f * ft.stride;
+          if (need && span) {        // the positions s < T - 1: the frame's first samples are its first stretches' heads
+            int32_t hd[X3L_FIR_HIST] = {0, 0, 0, 0, 0, 0, 0};
+            uint32_t m = 0;
+            for (uint32_t j = 0; j < ns && m < need; ++j) {
+              const X3FirEdge e = fe[j];
+              const uint32_t c = min(e.n, (uint32_t)X3L_FIR_HIST);   // (n <= 7: all of the stretch; else m reaches 7)
+#pragma unroll
+              for (int t = 0; t < X3L_FIR_HIST; ++t) {
+                if ((uint32_t)t < c && m < need) {
+                  x3rl_fir_set(hd, m, (int32_t)e.head[t]);
+                  ++m;
+                }
+              }
+            }
+            X3LevAcc a;
+            a.reset();
+            uint64_t cur = ~0ull;
+            x3rl_fir_front(ft.k, hd, m, hs.d, hs.cnt, 0u, 0u, need, lo, span, r0, bl, R, mine, a, cur);
+            if (cur != ~0ull) x3l_merge(mine + cur, a);
+          }
+          // the frame's last samples, newest first, are its last stretches' tails
+          int32_t tl[X3L_FIR_HIST] = {0, 0, 0, 0, 0, 0, 0};
+          uint32_t tc = 0;
+          for (uint32_t j = ns; j-- > 0u && tc < (uint32_t)X3L_FIR_HIST;) {
+            const X3FirEdge e = fe[j];
+            const uint32_t c = min(e.n, (uint32_t)X3L_FIR_HIST);
+#pragma unroll
+            for (int t = 0; t < X3L_FIR_HIST; ++t) {
+              if ((uint32_t)t < c && tc < (uint32_t)X3L_FIR_HIST) {
+                x3rl_fir_set(tl, tc, (int32_t)e.tail[t]);
+                ++tc;
+              }
+            }
+          }
+#pragma unroll
+          for (int t = X3L_FIR_HIST - 1; t >= 0; --t) {
+            if ((uint32_t)t < tc) hs.push(tl[t]);
+          }
+        }
+        hs.cnt = fs == X3D_OK ? min(hs.cnt, (uint32_t)X3L_FIR_HIST) : 0u;
+        if (fs != X3D_OK && st == X3D_OK && k >= ld) st = fs;   // (the first COVERING frame in frame order)
+      }
+    }
+    if (replayed) atomicAdd(&sum->w.replays, (unsigned long long)replayed);
+    status[w] = st;
+    if (st != X3D_OK) {
+      atomicAdd(&sum->w.n_bad, 1ull);
+      atomicMin(&sum->w.first, (unsigned long long)(w << 8) | (uint32_t)st);
+    }
+  }
+}
+
+// ---- seam: a lane per (pair q below P, stretch j >= 1), behind the merge.  Of a fast pair's stretch it adds the positions
+// s0 + c, c < min(n, T - 1), with s0 + c >= T - 1 (the others are the fix-up's): the samples are the stretch's heads, the
+// history the tails of the stretches in front of it in the same frame, which hold s0 >= T - 1 - c samples.  The pair is
+// fast, so the frame's word is final and the records are the caller's; lanes are joined by record as in
+// x3_range_levels_merge_kernel.  The stream is not read.  Bounds: q < min(cov_off[n], P); edge index pr.f * estride + j with
+// j < ns <= estride; a record at the range's base + bin with bin < erows[w], inside rows_cap (the range scan).
+__global__ void __launch_bounds__(256)
+x3_range_levels_fir_seam_kernel(uint32_t block_len, const uint2* __restrict__ idx, uint32_t sb, uint32_t nseg, uint64_t bin_len,
+                                const X3RLevPair* __restrict__ pairs, const unsigned long long* __restrict__ cov_off, uint64_t n,
+                                uint64_t P, uint64_t cap, const unsigned long long* __restrict__ prow,
+                                const unsigned long long* __restrict__ row_off, const uint32_t* __restrict__ erows, uint64_t stride,
+                                const int32_t* __restrict__ fst, const X3FirEdge* __restrict__ edges, uint32_t estride, X3FirTaps k,
+                                x3_level* __restrict__ levels) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t ns = x3w_index_ok(idx, sb) ? nseg : 1u;
+  const uint32_t need = k.T - 1u;
+  const uint64_t bl = x3l_bin_len(bin_len);
+  const uint64_t n_items = min((uint64_t)cov_off[n], P) * ns;
+  const uint64_t lanes = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u); i0 < n_items; i0 += lanes) {   // (whole waves)
+    const uint64_t i = i0 + lane;
+    X3LevAcc a;
+    a.reset();
+    uint64_t key = ~0ull;
+    const uint64_t q = i / ns;
+    const uint32_t j = (uint32_t)(i - q * ns);
+    const uint64_t s0 = 1u + (uint64_t)sb * j * block_len;   // the stretch's first sample
+    if (i < n_items && j >= 1u && s0 < 0x10000u) {
+      const X3RLevPair pr = pairs[q];
+      if (pr.cnt && x3rl_fast(fst[pr.f], prow, q, P, cap)) {
+        const X3FirEdge* const fe = edges + pr.f * estride;
+        const X3FirEdge e = fe[j];
+        if (e.n) {
+          int32_t hist[X3L_FIR_HIST] = {0, 0, 0, 0, 0, 0, 0}, hd[X3L_FIR_HIST];
+          uint32_t H = 0;
+          for (uint32_t wj = j; wj-- > 0u && H < need;) {
+            const X3FirEdge h = fe[wj];
+            const uint32_t c = min(h.n, (uint32_t)X3L_FIR_HIST);
+#pragma unroll
+            for (int t = 0; t < X3L_FIR_HIST; ++t) {
+              if ((uint32_t)t < c && H < need) {
+                x3rl_fir_set(hist, H, (int32_t)h.tail[t]);
+                ++H;
+              }
+            }
+          }
+#pragma unroll
+          for (int t = 0; t < X3L_FIR_HIST; ++t) hd[t] = (int32_t)e.head[t];
+          x3_level* const mine = levels + x3rl_base(row_off, stride, pr.w);
+          uint64_t cur = ~0ull;
+          x3rl_fir_front(k, hd, min(e.n, need), hist, H, (uint32_t)s0, need, 0x10000u, pr.lo, pr.hi - pr.lo, pr.r0, bl, erows[pr.w],
+                         mine, a, cur);
+          if (cur != ~0ull) key = x3rl_base(row_off, stride, pr.w) + cur;
         }
       }
     }

@@ -68,6 +68,7 @@ SYMBOLS = [
     "x3_level_thresholds_dev", "x3_corpus_level_thresholds_dev", "x3_events_adaptive_dev", "x3_corpus_events_adaptive_dev",
     "x3_range_levels_dev", "x3_corpus_range_levels_dev", "x3_range_levels_result",
     "x3_signal_range_levels_dev", "x3_corpus_signal_range_levels_dev",
+    "x3_fir_range_levels_dev", "x3_corpus_fir_range_levels_dev",
     "x3_tune_candidate", "x3_tuner_create", "x3_tuner_add_dev", "x3_tuner_result", "x3_tuner_max_payloads",
     "x3_tuner_reset", "x3_tuner_destroy", "x3_tune", "x3_x3a_encode_tuned",
 ]
@@ -126,10 +127,10 @@ class Fir:
 
 def level_signal(signal, fir=True):
     """the keyword `signal` of the levels methods ("samples" | "diff", or a LEVEL_SIGNAL_* value) -> the C ABI's int; a
-    Fir is handed through (fir=False: to a call that has no FIR form yet, which raises)"""
+    Fir is handed through (fir=False: to the range-levels keyword, which takes no Fir and raises; fir_range_levels does)"""
     if isinstance(signal, Fir):
         if not fir:
-            raise ValueError("signal: range levels of a Fir signal are not built yet (levels, events, level_quantiles and adaptive_events take one)")
+            raise ValueError("signal: range levels of a Fir signal are not built yet on this keyword: call fir_range_levels")
         return signal
     if signal in LEVEL_SIGNALS:
         return LEVEL_SIGNALS[signal]
@@ -361,6 +362,9 @@ def lib():
     L.x3_corpus_range_levels_dev.argtypes = [vp, vp, vp, vp, vp, u64, u64, u64, vp, u64, vp, vp]
     L.x3_signal_range_levels_dev.argtypes = [vp, vp, u64, vp, vp, u64, PP, vp, u32, vp, vp, u64, u64, u64, vp, u64, vp, vp, C.c_int]
     L.x3_corpus_signal_range_levels_dev.argtypes = [vp, vp, vp, vp, vp, u64, u64, u64, vp, u64, vp, vp, C.c_int]
+    L.x3_fir_range_levels_dev.argtypes = [vp, vp, u64, vp, vp, u64, PP, vp, u32, vp, vp, u64, u64, u64, vp, u64, vp, vp,
+                                          C.POINTER(LevelFir)]
+    L.x3_corpus_fir_range_levels_dev.argtypes = [vp, vp, vp, vp, vp, u64, u64, u64, vp, u64, vp, vp, C.POINTER(LevelFir)]
     L.x3_range_levels_result.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(i32), C.POINTER(u64)]
     L.x3_corpus_destroy.restype = None
     L.x3_synth.argtypes = [i32, u64, u64, u64, vp]
@@ -1210,6 +1214,21 @@ class Context:
         return lib().x3_corpus_signal_range_levels_dev(self._h, corpus._h, d_entries, d_starts, d_lens, n_ranges, bin_len,
                                                        row_stride, d_levels, rows_cap, d_row_offsets, d_status, signal)
 
+    def fir_range_levels_dev(self, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, params, d_starts, d_lens,
+                             n_ranges, bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status, d_seg_index=None,
+                             seg_blocks=0, fir=None):
+        """x3_fir_range_levels_dev: range_levels_dev of the stream's FIR signal (fir: a Fir, or a LevelFir as it is) cut to
+        the ranges; asynchronous, range_levels_result waits"""
+        return lib().x3_fir_range_levels_dev(self._h, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames,
+                                             C.byref(params), d_seg_index, seg_blocks, d_starts, d_lens, n_ranges, bin_len,
+                                             row_stride, d_levels, rows_cap, d_row_offsets, d_status, self._fir_arg(fir))
+
+    def corpus_fir_range_levels_dev(self, corpus, d_entries, d_starts, d_lens, n_ranges, bin_len, row_stride, d_levels,
+                                    rows_cap, d_row_offsets, d_status, fir=None):
+        """x3_corpus_fir_range_levels_dev: corpus_range_levels_dev of each entry's FIR signal; asynchronous"""
+        return lib().x3_corpus_fir_range_levels_dev(self._h, corpus._h, d_entries, d_starts, d_lens, n_ranges, bin_len,
+                                                    row_stride, d_levels, rows_cap, d_row_offsets, d_status, self._fir_arg(fir))
+
     def range_levels_result(self):
         """-> (rc, n_bad, first_bad, first_bad_status, total_rows) of the last range_levels_dev / corpus_range_levels_dev"""
         nb, fb, st, tot = C.c_uint64(0), C.c_uint64(0), C.c_int32(0), C.c_uint64(0)
@@ -1593,7 +1612,8 @@ class WindowSource:
                           signal=LEVEL_SIGNAL_SAMPLES):
         """enqueue the level records of n ranges (device pointers: d_starts n x u64, d_lens n x u32, d_levels rows_cap x
         x3_level, d_row_offsets (n + 1) x u64 or None when padded, d_status n x i32); row_stride 0: packed; signal: a
-        LEVEL_SIGNAL_* value (a Fir raises: not built yet); -> rc; Context.range_levels_result waits"""
+        LEVEL_SIGNAL_* value (a Fir raises, "not built yet" on this keyword: fir_range_levels_into takes it); -> rc;
+        Context.range_levels_result waits"""
         if isinstance(signal, Fir):
             level_signal(signal, fir=False)
         return self.ctx.signal_range_levels_dev(self.d_x3, self.x3_len, self.d_frame_offsets, self.d_sample_offsets,
@@ -1608,9 +1628,26 @@ class WindowSource:
         row_offsets[-1] says what all need), otherwise one synchronising sum on the host.  padded_to: row w begins at
         w * padded_to.  The tensors events() returns go in as they are.  The call waits for its result.
         signal: "samples", or "diff" -- the stream's first difference (as in levels()) cut to the ranges: the difference at
-        a range's first position is counted, its earlier sample lies in front of the range (x3_signal_range_levels_dev)"""
+        a range's first position is counted, its earlier sample lies in front of the range (x3_signal_range_levels_dev).
+        A Fir raises on this keyword: fir_range_levels takes it"""
         sig = level_signal(signal, fir=False)
         return _range_levels_torch(self.ctx, lambda e, *a: self.range_levels_into(*a, signal=sig), "x3_signal_range_levels_dev",
+                                   starts, lens, bin_len, padded_to, capacity)
+
+    def fir_range_levels_into(self, d_starts, d_lens, n, bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status, fir):
+        """range_levels_into on the stream's FIR signal (fir: a Fir or a LevelFir; x3_fir_range_levels_dev); -> rc;
+        Context.range_levels_result waits"""
+        return self.ctx.fir_range_levels_dev(self.d_x3, self.x3_len, self.d_frame_offsets, self.d_sample_offsets, self.n_frames,
+                                             self.params, d_starts, d_lens, n, bin_len, row_stride, d_levels, rows_cap,
+                                             d_row_offsets, d_status, self.d_seg_index, self.seg_blocks, fir)
+
+    def fir_range_levels(self, starts, lens, bin_len, fir, *, padded_to=None, capacity=None):
+        """range_levels of the stream's FIR signal (levels(signal=fir)) cut to the ranges: the call cuts the filtered stream,
+        it does not filter the cut, so a range's first len(taps) - 1 positions are counted, their earlier samples lie in
+        front of the range (x3_fir_range_levels_dev).  fir: a Fir; the tensors events(signal=fir) returns go in as they are"""
+        if not isinstance(fir, Fir):
+            raise ValueError("fir: a Fir")
+        return _range_levels_torch(self.ctx, lambda e, *a: self.fir_range_levels_into(*a, fir), "x3_fir_range_levels_dev",
                                    starts, lens, bin_len, padded_to, capacity)
 
     def levels_into(self, bin_len, d_levels, n_bins, d_frame_status=None, signal=LEVEL_SIGNAL_SAMPLES):
@@ -1945,17 +1982,33 @@ class Corpus:
         if self._h is None:
             raise ValueError("the corpus is closed")
         if isinstance(signal, Fir):
-            level_signal(signal, fir=False)   # (raises: range levels of a Fir signal are not built yet)
+            level_signal(signal, fir=False)   # (raises: "not built yet" on this keyword; fir_range_levels_into takes a Fir)
         return self.ctx.corpus_signal_range_levels_dev(self, d_entries, d_starts, d_lens, n, bin_len, row_stride, d_levels,
                                                        rows_cap, d_row_offsets, d_status, signal)
 
     def range_levels(self, entries, starts, lens, bin_len, *, padded_to=None, capacity=None, signal="samples"):
         """The x3_level records of the ranges [starts[w], starts[w] + lens[w]) of entry entries[w] -> (levels, row_offsets,
         status) as WindowSource.range_levels; the tensors events() returns go in as they are.  signal: as there -- the
-        entry's first difference cut to the ranges; no difference crosses from one entry into the next"""
+        entry's first difference cut to the ranges; no difference crosses from one entry into the next.  A Fir raises on
+        this keyword: fir_range_levels takes it"""
         sig = level_signal(signal, fir=False)
         return _range_levels_torch(self.ctx, lambda *a: self.range_levels_into(*a, signal=sig),
                                    "x3_corpus_signal_range_levels_dev", starts, lens, bin_len, padded_to, capacity, entries=entries)
+
+    def fir_range_levels_into(self, d_entries, d_starts, d_lens, n, bin_len, row_stride, d_levels, rows_cap, d_row_offsets,
+                              d_status, fir):
+        """range_levels_into on each entry's FIR signal (fir: a Fir or a LevelFir; x3_corpus_fir_range_levels_dev); -> rc"""
+        if self._h is None:
+            raise ValueError("the corpus is closed")
+        return self.ctx.corpus_fir_range_levels_dev(self, d_entries, d_starts, d_lens, n, bin_len, row_stride, d_levels, rows_cap,
+                                                    d_row_offsets, d_status, fir)
+
+    def fir_range_levels(self, entries, starts, lens, bin_len, fir, *, padded_to=None, capacity=None):
+        """WindowSource.fir_range_levels for ranges of entries; no filter history crosses from one entry into the next"""
+        if not isinstance(fir, Fir):
+            raise ValueError("fir: a Fir")
+        return _range_levels_torch(self.ctx, lambda *a: self.fir_range_levels_into(*a, fir), "x3_corpus_fir_range_levels_dev",
+                                   starts, lens, bin_len, padded_to, capacity, entries=entries)
 
     def levels_rows(self, bin_len):
         """-> row_first np.uint64 [n_entries + 1]: entry e's rows of levels() are [row_first[e], row_first[e + 1])"""
