@@ -859,6 +859,55 @@ int x3_fir_levels_dev(x3_ctx* ctx, const uint8_t* d_x3, uint64_t x3_len, const u
                       x3_level* d_levels, uint64_t n_bins, int32_t* d_frame_status, const x3_level_fir* fir);
 int x3_corpus_fir_levels_dev(x3_ctx* ctx, const x3_corpus* corpus, uint64_t bin_len, x3_level* d_levels, uint64_t n_rows,
                              int32_t* d_frame_status, const x3_level_fir* fir);
+/* ---- TONE LEVELS (no counterpart in the reference): per bin, the QUADRATURE SUMS of the samples against one oscillator --
+ * the one-bin DFT (Goertzel) detector of a narrow band, which no filter of eight taps can pick, at no extra read and no
+ * sample buffer.  `tone` is a host struct, copied at the call; d_table is a caller-owned DEVICE array
+ * of 1 024 (cos, sin) int16 pairs (2 048 int16, 4 096 bytes, 4-byte aligned), read when the kernels run like every other
+ * device input.  Any contents are legal: the call defines nothing by floating point.  The usual table, which the mirrors
+ * supply, is (round(32767 * cos(2 pi k / 1024)), round(32767 * sin(2 pi k / 1024))) at pair k.
+ *   Position i of a stream or of a corpus entry has the phase ph(i) = (i * step) mod 2^32 -- every entry starts at phase 0 --
+ * and the table pair k(i) = ph(i) >> 22; step = round(f / fs * 2^32) puts the oscillator at frequency f.  The record of a bin
+ * is x3_tone_level, which has x3_level's layout slot for slot:
+ *     re = sum of x[i] * cos[k(i)],  im = sum of x[i] * sin[k(i)]   over the bin's positions in frames with status 0;
+ *     min, max, n: field for field those of the bin's x3_levels_dev record.
+ * An empty bin is {0, 0, 32767, -32768, 0, 0}.  |x * w| <= 2^30 and n < 2^32: the int64 sums are exact, in any order.
+ *   Positions, bins, bin_len 0 (one bin), n_bins * bin_len, "every record is written", a failed frame adding nothing,
+ * d_frame_status, x3_levels_result, the pending slot, the option "last_levels_replays", the segment index as a hint only and
+ * the asynchronous contract are those of x3_levels_dev / x3_corpus_levels_dev.  A NULL tone, a NULL or misaligned d_table or
+ * reserved != 0 is X3_ERR_BAD_ARG with nothing enqueued, checked before every other argument.
+ *   Two identities: a table of all (1, 0) gives re == the sum of x3_levels_dev's record and im == 0, with its min, max and
+ * n; step 0 with the usual table gives re == 32767 * that sum and im == 0. */
+typedef struct x3_level_tone {
+  uint32_t step;            /* phase per position, in units of 2^-32 turns */
+  uint32_t reserved;        /* 0 */
+  const int16_t* d_table;   /* device: 1 024 pairs (cos, sin) */
+} x3_level_tone;
+typedef struct x3_tone_level {  /* 32 bytes, 8-byte aligned: x3_level with re for sum_sq and im for sum */
+  int64_t  re;                 /* sum of x * cos[k] */
+  int64_t  im;                 /* sum of x * sin[k] */
+  int32_t  min, max;           /* of the samples; n == 0: 32767 / -32768 */
+  uint32_t n;                  /* samples counted into this bin */
+  uint32_t reserved;           /* 0 */
+} x3_tone_level;
+int x3_tone_levels_dev(x3_ctx* ctx, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
+                       const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
+                       const uint64_t* d_seg_index, uint32_t seg_blocks, uint64_t bin_len,
+                       x3_tone_level* d_levels, uint64_t n_bins, int32_t* d_frame_status, const x3_level_tone* tone);
+int x3_corpus_tone_levels_dev(x3_ctx* ctx, const x3_corpus* corpus, uint64_t bin_len, x3_tone_level* d_levels, uint64_t n_rows,
+                              int32_t* d_frame_status, const x3_level_tone* tone);
+/* THE ADAPTER into the detection chain: n_rows tone records -> the x3_level records of the BAND'S LEVEL, which the events,
+ * quantiles and thresholds calls take unchanged.  One elementwise kernel on the context's stream, asynchronous, with no
+ * result call and no pending state.  d_levels == d_tone (in place) is allowed; any other overlap, a NULL or misaligned
+ * (8 bytes) pointer, n_rows == 0 or n_rows > 2^31 - 1 is X3_ERR_BAD_ARG.  Per record, in integers (>> is arithmetic, isqrt
+ * the floor square root), n == 0 giving {0, 0, 32767, -32768, 0, 0}:
+ *     e = max(0, bitlen(n) - 15);  a = re >> (15 + e);  b = im >> (15 + e);  P = a * a + b * b  (below 2^62);
+ *     m = n >> e;  ms = min(2^30, floor(floor(2 * P / m) / m));  peak = min(32767, isqrt(2 * ms));
+ *     -> {sum_sq = ms * n, sum = 0, min = -peak, max = peak, n = n, reserved = 0}.
+ * For a tone of amplitude A at the oscillator's frequency ms is about A * A / 2, the tone's mean square, and peak about A.
+ * At DC (step 0) and at Nyquist (step 2^31) the two quadrature sums do not halve the power between them: the estimate is
+ * TWICE the component's mean square there.  |min|, |max| <= 32768 and sum_sq / n <= 2^30 hold as for any x3_level record;
+ * merged event records then carry the event's mean band level. */
+int x3_tone_power_levels_dev(x3_ctx* ctx, const x3_tone_level* d_tone, uint64_t n_rows, x3_level* d_levels);
 /* ---- EVENTS (no counterpart in the reference): runs of loud bins of level records as ranges (entry, start, len), found on
  * the device -- the link between the levels calls and the ranges calls, with no host trip.
  *   Row b of d_levels is a bin of bin_len positions as x3_levels_dev / x3_corpus_levels_dev write it.  A bin is HOT when

@@ -25,7 +25,11 @@ Families: (e) the single-pass encoders on block_len 20 with mixed content, many 
           than the taps among them, GPU == tests/fir_levels_ref.py; {1} against x3_levels_dev byte for byte (not in the
           default family set); (t) family (r) behind a random valid Fir (x3_fir_range_levels_dev; the letter (l) is the
           difference's), with starts drawn to frame and stretch boundaries +- T - 1 (lead frames, stretch fronts), GPU ==
-          tests/fir_range_levels_ref.py (not in the default family set)."""
+          tests/fir_range_levels_ref.py (not in the default family set); (o) family (h) against one oscillator
+          (x3_tone_levels_dev / x3_corpus_tone_levels_dev): a random step -- 0, 2^30, 2^31 and 2^32 - 1 among them -- and the
+          usual table or a random one, GPU == tests/tone_levels_ref.py; the adapter (x3_tone_power_levels_dev, by
+          levels(signal=Tone)) against the reference on the same records; a table of all (1, 0) against x3_levels_dev's sums
+          (not in the default family set)."""
 import argparse, ctypes as C, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "x3-rust_amd"))
@@ -973,7 +977,7 @@ def draw_fir(rng):
     return x3hip.Fir([int(c) for c in taps], int(rng.choice([0, 0, 1, 7, 15, int(rng.integers(0, 16))])))
 
 
-def fam_h(rng, tag, fir=False):
+def fam_h(rng, tag, fir=False, tone=False):
     """signal levels: the DIFF records and frame statuses of a random stream -- any geometry, damaged frames, a damaged or
     walk-built index or none -- against diff_levels_ref on the oracle's frame verdicts; then the same frames as a corpus of
     random entries, where no difference may cross from one entry into the next; SAMPLES against x3_levels_dev byte for byte"""
@@ -989,6 +993,27 @@ def fam_h(rng, tag, fir=False):
         signal, same_as = "diff", "samples"
         ref_stream = lambda fr, st, so_, bl, nb: DL.signal_levels(fr, st, so_, bl, nb, DL.DIFF)
         ref_corpus = lambda ref, bl: DL.corpus_signal_levels(ref, bl, DL.DIFF)
+    stream_levels = lambda src, bl, nb: src.levels(bl, nb, signal=signal)
+    corpus_levels = lambda corpus, bl: corpus.levels(bl, signal=signal)
+    tone_tabs = []
+    if tone:   # family (o): the tone records of a drawn step and table, against tone_levels_ref
+        import tone_levels_ref as TR
+        step = int(rng.choice([0, 1 << 30, 1 << 31, (1 << 32) - 1, int(rng.integers(0, 1 << 32)), int(rng.integers(0, 1 << 32)) | 1]))
+        tab = None if rng.random() < 0.5 else rng.integers(-32768, 32768, (1024, 2)).astype(np.int16)
+        ones = np.tile(np.array([[1, 0]], dtype=np.int16), (1024, 1))
+
+        def level_tone(t):   # an x3_level_tone of a table in device memory (freed behind the trial)
+            if t is None:
+                return x3hip.LevelTone(step, 0, ctx.tone_table_dev())
+            tone_tabs.append(ctx.alloc(4096))
+            ctx.upload(tone_tabs[-1], t)
+            return x3hip.LevelTone(step, 0, tone_tabs[-1])
+        ref_stream = lambda fr, st, so_, bl, nb: TR.tone_levels(fr, st, so_, bl, nb, step, tab)
+        ref_corpus = lambda ref, bl: TR.corpus_tone_levels(ref, bl, step, tab)
+        stream_levels = lambda src, bl, nb: src._levels_np("x3_tone_levels_dev", bl, nb, x3hip.TONE_DTYPE,
+                                                           lambda d_lv, n_, d_st: src.tone_levels_into(bl, level_tone(tab), d_lv, n_, d_st))
+        corpus_levels = lambda corpus, bl: corpus._levels_np("x3_corpus_tone_levels_dev", bl, x3hip.TONE_DTYPE,
+                                                             lambda d_lv, n_, d_st: corpus.tone_levels_into(bl, level_tone(tab), d_lv, n_, d_st))
     r = rng.random()
     if r < 0.5:
         p = x3hip.Params.default()
@@ -1068,14 +1093,23 @@ def fam_h(rng, tag, fir=False):
                 else:
                     idx[sel] = rng.integers(0, 1 << 49, int(sel.sum()), dtype=np.uint64)
             ctx.upload(src.d_seg_index, idx)
-        got, st = src.levels(bin_len, n_bins, signal=signal)
+        got, st = stream_levels(src, bin_len, n_bins)
         assert st.tolist() == statuses, (tag, "statuses", st.tolist(), statuses)
         want = ref_stream(frames, statuses, so[:-1], bin_len, n_bins)
-        for k in LR.LEVEL_DTYPE.names:
+        for k in want.dtype.names:
             assert np.array_equal(got[k], want[k]), (tag, "stream", k, bin_len, n_bins, np.flatnonzero(got[k] != want[k])[:8].tolist())
-        same, _ = src.levels(bin_len, n_bins, signal=same_as)
         old, _ = src.levels(bin_len, n_bins)
-        assert same.tobytes() == old.tobytes(), (tag, "samples")
+        if tone:   # a table of all (1, 0): the sums of the levels call; the adapter on the usual table's records
+            same, _ = src._levels_np("x3_tone_levels_dev", bin_len, n_bins, x3hip.TONE_DTYPE,
+                                     lambda d_lv, n_, d_st: src.tone_levels_into(bin_len, level_tone(ones), d_lv, n_, d_st))
+            assert np.array_equal(same["re"], old["sum"]) and not same["im"].any(), (tag, "ones")
+            assert all(np.array_equal(same[k], old[k]) for k in ("min", "max", "n")), (tag, "ones: min, max, n")
+            band, _ = src.levels(bin_len, n_bins, signal=x3hip.Tone(step))
+            usual = TR.tone_levels(frames, statuses, so[:-1], bin_len, n_bins, step)
+            assert band.tobytes() == TR.tone_power_levels(usual).tobytes(), (tag, "adapter")
+        else:
+            same, _ = src.levels(bin_len, n_bins, signal=same_as)
+            assert same.tobytes() == old.tobytes(), (tag, "samples")
         # the same bytes as a corpus: the frames cut into entries at random frame boundaries
         if F >= 1 and bin_len <= 0xFFFFFFFF:
             cuts = sorted(set([0, F] + [int(v) for v in rng.integers(0, F + 1, int(rng.integers(0, 5)))]))
@@ -1088,22 +1122,23 @@ def fam_h(rng, tag, fir=False):
                 return
             try:
                 if corpus.entries["n_frames"].tolist() == [b - a for a, b in zip(cuts[:-1], cuts[1:])]:
-                    rows, rf, cst = corpus.levels(bin_len, signal=signal)
+                    rows, rf, cst = corpus_levels(corpus, bin_len)
                     ref = []
                     for a, b in zip(cuts[:-1], cuts[1:]):
                         ref.append((frames[a:b], statuses[a:b], [so[f] - so[a] for f in range(a, b)], so[b] - so[a]))
                     wrows, wrf = ref_corpus(ref, bin_len)
                     assert np.array_equal(rf, wrf) and cst.tolist() == statuses, (tag, "corpus layout")
-                    for k in LR.LEVEL_DTYPE.names:
+                    for k in wrows.dtype.names:
                         assert np.array_equal(rows[k], wrows[k]), (tag, "corpus", k, bin_len, cuts, np.flatnonzero(rows[k] != wrows[k])[:8].tolist())
             finally:
                 corpus.close()
     finally:
-        for q in d:
+        for q in d + tone_tabs:
             ctx.free(q)
 
 
 fams["h"] = fam_h
+fams["o"] = lambda rng, tag: fam_h(rng, tag, tone=True)
 fams["i"] = lambda rng, tag: fam_h(rng, tag, fir=True)
 fams["t"] = lambda rng, tag: fam_r(rng, tag, fir=draw_fir(rng))
 

@@ -1323,10 +1323,13 @@ size_t levels_carve(char* base, uint64_t F, uint64_t n_rows, uint64_t fix_waves,
 // accumulate and fix-up kernels, which leave every good frame's last sample in the workspace, and the seam kernel behind them.
 // fir (checked: levels_fir_taps) instead of a signal: the X3LevFir instance, which leaves an edge record per (frame, stretch)
 // in a workspace of its own (fir_ws; lev_ws keeps its layout), and x3_levels_fir_seam_kernel behind the merge.
+// tone (checked: levels_tone_arg) instead of either: the X3LevTone instance, whose records hold re and im in x3_level's first
+// two slots; no workspace of its own and no kernel behind the merge.
 template <class Prep>
 static int levels_launch(x3_ctx* c, const FrameSource& s, uint64_t bin_len, x3_level* d_levels, uint64_t n_rows,
-                         int32_t* d_frame_status, uint64_t n_ent, int signal, Prep prep, const X3FirTaps* fir = nullptr) {
-  const bool diff = !fir && signal == X3_LEVEL_SIGNAL_DIFF;
+                         int32_t* d_frame_status, uint64_t n_ent, int signal, Prep prep, const X3FirTaps* fir = nullptr,
+                         const X3LevToneTail* tone = nullptr) {
+  const bool diff = !fir && !tone && signal == X3_LEVEL_SIGNAL_DIFF;
   HIPCHK(c, hipSetDevice(c->device));
   const uint64_t F = s.F, cap = n_rows + F;
   const uint32_t scratch_per = levels_scratch_per(s.dp.block_len);
@@ -1351,7 +1354,8 @@ static int levels_launch(x3_ctx* c, const FrameSource& s, uint64_t bin_len, x3_l
                        s.d_frame_offsets, F, s.dp, bin_len, (const X3LevFrame*)w.frames, w.fst, d_levels, d_frame_status,
                        w.scratch, scratch_per, w.sum, tail);
   };
-  if (fir) decode(X3LevFir{}, X3LevFirTail{*fir, (X3FirEdge*)c->fir_ws.p, s.nseg});
+  if (tone) decode(X3LevTone{}, *tone);
+  else if (fir) decode(X3LevFir{}, X3LevFirTail{*fir, (X3FirEdge*)c->fir_ws.p, s.nseg});
   else if (diff) decode(X3LevDiff{}, w.tail);
   else decode(X3LevSamples{}, X3LevNoTail{});
   hipLaunchKernelGGL(x3_levels_merge_kernel, dim3(grid_for(cap, 256)), dim3(256), 0, c->stream, (const X3LevFrame*)w.frames,
@@ -1384,11 +1388,25 @@ static bool levels_fir_taps(const x3_level_fir* fir, X3FirTaps* k) {
   return mag <= 32768u;
 }
 
-// the stream form of the levels calls behind the check of the signal or the taps (fir != NULL: the FIR call)
+// x3_level_tone as the kernels take it; false: NULL, a NULL or misaligned table, reserved != 0
+static bool levels_tone_arg(const x3_level_tone* tone, X3LevToneTail* t) {
+  if (!tone || !tone->d_table || (reinterpret_cast<uintptr_t>(tone->d_table) & 3u) != 0 || tone->reserved != 0) return false;
+  t->table = reinterpret_cast<const uint32_t*>(tone->d_table);
+  t->step = tone->step;
+  return true;
+}
+static_assert(sizeof(x3_tone_level) == sizeof(x3_level) && alignof(x3_tone_level) == alignof(x3_level) &&
+                  offsetof(x3_tone_level, re) == offsetof(x3_level, sum_sq) && offsetof(x3_tone_level, im) == offsetof(x3_level, sum) &&
+                  offsetof(x3_tone_level, min) == offsetof(x3_level, min) && offsetof(x3_tone_level, max) == offsetof(x3_level, max) &&
+                  offsetof(x3_tone_level, n) == offsetof(x3_level, n),
+              "x3_tone_level has x3_level's layout slot for slot");
+
+// the stream form of the levels calls behind the check of the signal, the taps (fir != NULL: the FIR call) or the
+// oscillator (tone != NULL: the tone call)
 static int stream_levels_call(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
                               const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p, const uint64_t* d_seg_index,
                               uint32_t seg_blocks, uint64_t bin_len, x3_level* d_levels, uint64_t n_bins, int32_t* d_frame_status,
-                              int signal, const X3FirTaps* fir) {
+                              int signal, const X3FirTaps* fir, const X3LevToneTail* tone = nullptr) {
   if (!levels_args_ok(c, d_levels, n_bins, d_frame_status)) return X3_ERR_BAD_ARG;
   FrameSource s;
   const int rc = stream_source(d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, p, d_seg_index, seg_blocks, &s);
@@ -1397,7 +1415,7 @@ static int stream_levels_call(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, c
                        [&](dim3 grid, unsigned long long*, const int32_t* fst, X3LevFrame* frames, uint32_t* cnt) {
                          hipLaunchKernelGGL(x3_levels_prep_kernel, grid, dim3(256), 0, c->stream, d_sample_offsets, n_frames,
                                             bin_len, n_bins, fst, frames, cnt);
-                       }, fir);
+                       }, fir, tone);
 }
 
 extern "C" int x3_signal_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
@@ -1417,6 +1435,29 @@ extern "C" int x3_fir_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len
   if (!c || !levels_fir_taps(fir, &k)) return X3_ERR_BAD_ARG;
   return stream_levels_call(c, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, p, d_seg_index, seg_blocks, bin_len,
                             d_levels, n_bins, d_frame_status, X3_LEVEL_SIGNAL_SAMPLES, &k);
+}
+
+extern "C" int x3_tone_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
+                                  const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
+                                  const uint64_t* d_seg_index, uint32_t seg_blocks, uint64_t bin_len, x3_tone_level* d_levels,
+                                  uint64_t n_bins, int32_t* d_frame_status, const x3_level_tone* tone) {
+  X3LevToneTail t;
+  if (!c || !levels_tone_arg(tone, &t)) return X3_ERR_BAD_ARG;
+  return stream_levels_call(c, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, p, d_seg_index, seg_blocks, bin_len,
+                            reinterpret_cast<x3_level*>(d_levels), n_bins, d_frame_status, X3_LEVEL_SIGNAL_SAMPLES, nullptr, &t);
+}
+
+// the adapter: tone records -> the level records of the band (x3_tone_power_kernel); in place, or rows that do not overlap
+extern "C" int x3_tone_power_levels_dev(x3_ctx* c, const x3_tone_level* d_tone, uint64_t n_rows, x3_level* d_levels) {
+  if (!c || !d_tone || !d_levels || n_rows == 0 || n_rows > 0x7FFFFFFFull) return X3_ERR_BAD_ARG;
+  const uintptr_t a = reinterpret_cast<uintptr_t>(d_tone), b = reinterpret_cast<uintptr_t>(d_levels);
+  const uintptr_t bytes = (uintptr_t)n_rows * sizeof(x3_level);
+  if (((a | b) & 7u) != 0 || (a != b && a < b + bytes && b < a + bytes)) return X3_ERR_BAD_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  hipLaunchKernelGGL(x3_tone_power_kernel, dim3(grid_for(n_rows, 256)), dim3(256), 0, c->stream,
+                     reinterpret_cast<const x3_level*>(d_tone), n_rows, d_levels);
+  HIPCHK(c, hipGetLastError());
+  return X3_OK;
 }
 
 extern "C" int x3_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
@@ -2091,7 +2132,8 @@ static void corpus_row_prefix(x3_ctx* c, const x3_corpus* k, uint64_t bin_len, u
 }
 
 static int corpus_levels_call(x3_ctx* c, const x3_corpus* k, const char* entry, uint64_t bin_len, x3_level* d_levels,
-                              uint64_t n_rows, int32_t* d_frame_status, int signal, const X3FirTaps* fir = nullptr) {
+                              uint64_t n_rows, int32_t* d_frame_status, int signal, const X3FirTaps* fir = nullptr,
+                              const X3LevToneTail* tone = nullptr) {
   if (!c || !k || !levels_signal_ok(signal) || !levels_args_ok(c, d_levels, n_rows, d_frame_status)) return X3_ERR_BAD_ARG;
   FrameSource s;
   X3EvRows q;
@@ -2104,7 +2146,7 @@ static int corpus_levels_call(x3_ctx* c, const x3_corpus* k, const char* entry, 
                          hipLaunchKernelGGL(x3_corpus_levels_prep_kernel, grid, dim3(256), 0, c->stream,
                                             k->d_ent, k->n, (const unsigned long long*)row_first,
                                             s.d_sample_offsets, s.F, bin_len, n_rows, fst, frames, cnt);
-                       }, fir);
+                       }, fir, tone);
 }
 
 extern "C" int x3_corpus_levels_dev(x3_ctx* c, const x3_corpus* k, uint64_t bin_len, x3_level* d_levels, uint64_t n_rows,
@@ -2123,6 +2165,14 @@ extern "C" int x3_corpus_fir_levels_dev(x3_ctx* c, const x3_corpus* k, uint64_t 
   if (!c || !levels_fir_taps(fir, &taps)) return X3_ERR_BAD_ARG;
   return corpus_levels_call(c, k, "x3_corpus_fir_levels_dev", bin_len, d_levels, n_rows, d_frame_status, X3_LEVEL_SIGNAL_SAMPLES,
                             &taps);
+}
+
+extern "C" int x3_corpus_tone_levels_dev(x3_ctx* c, const x3_corpus* k, uint64_t bin_len, x3_tone_level* d_levels, uint64_t n_rows,
+                                         int32_t* d_frame_status, const x3_level_tone* tone) {
+  X3LevToneTail t;
+  if (!c || !levels_tone_arg(tone, &t)) return X3_ERR_BAD_ARG;
+  return corpus_levels_call(c, k, "x3_corpus_tone_levels_dev", bin_len, reinterpret_cast<x3_level*>(d_levels), n_rows,
+                            d_frame_status, X3_LEVEL_SIGNAL_SAMPLES, nullptr, &t);
 }
 
 // ------------------------------------------------------------------------------------------------

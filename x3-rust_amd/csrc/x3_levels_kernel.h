@@ -27,8 +27,10 @@
 //  x3_levels_merge_kernel    -- a lane per partial row; rows of one bin that lie side by side in a wave are joined first
 //  x3_levels_seam_kernel     -- X3_LEVEL_SIGNAL_DIFF only: a lane per frame, the one difference across the frame's front seam
 //  x3_levels_fir_seam_kernel -- x3_fir_levels_dev only: a lane per (frame, stretch), the stretch's first T - 1 positions
+//  x3_tone_power_kernel      -- x3_tone_power_levels_dev: a lane per tone record, the record of the band's level
 // The accumulate and fix-up kernels are templates over the SIGNAL, what a position adds to its bin: X3LevSamples (the levels
-// calls), X3LevDiff (x3_signal_levels_dev) or X3LevFir (x3_fir_levels_dev).
+// calls), X3LevDiff (x3_signal_levels_dev), X3LevFir (x3_fir_levels_dev) or
+// X3LevTone (x3_tone_levels_dev).
 //
 // What the range levels, events and quantiles kernels (x3_range_levels_kernel.h, x3_events_kernel.h, x3_quantiles_kernel.h)
 // share with these: X3L_IDENTITY, the record of an empty bin; X3LevAcc, a record in registers (load, record, join);
@@ -155,16 +157,17 @@ struct X3LevBinner {
 // the first sample a lane sees without a seed (sample 0 of a frame) adds nothing: that difference crosses the frame's seam
 // and is x3_levels_seam_kernel's.  seed(v): the sample in front of a stretch (x3w_stretch's watch).  Tail: the kernels'
 // last argument, the per-frame array of last samples that only X3LevDiff has.
-// kState: the signal has registers of its own and is the caller's, at x3l_bin_samples' `sig`; kFir: it is X3LevFir (below).
+// kState: the signal has registers of its own and is the caller's, at x3l_bin_samples' `sig`; kFir: it is X3LevFir, kTone:
+// it is X3LevTone (both below).
 struct X3LevNoTail {};
 struct X3LevSamples {
-  static constexpr bool kDiff = false, kFir = false, kState = false;
+  static constexpr bool kDiff = false, kFir = false, kState = false, kTone = false;
   using Tail = X3LevNoTail;
   __device__ __forceinline__ void add(X3LevAcc& a, uint32_t v) { a.add(v); }
 };
 __device__ __forceinline__ int32_t x3l_diff(int32_t s, int32_t prev) { return min(max(s - prev, -32768), 32767); }
 struct X3LevDiff {
-  static constexpr bool kDiff = true, kFir = false, kState = true;
+  static constexpr bool kDiff = true, kFir = false, kState = true, kTone = false;
   using Tail = int32_t*;   // per frame: its last sample
   int32_t prev = 0;
   bool have = false;
@@ -224,7 +227,7 @@ __device__ __forceinline__ int32_t x3l_fir_value(const X3FirTaps& k, int32_t s, 
   return min(max(acc >> k.shift, -32768), 32767);
 }
 struct X3LevFir {
-  static constexpr bool kDiff = false, kFir = true, kState = true;
+  static constexpr bool kDiff = false, kFir = true, kState = true, kTone = false;
   using Tail = X3LevFirTail;
   X3FirTaps k;   // (uniform: the kernel's argument)
   X3FirEdge* edge = nullptr;
@@ -250,6 +253,44 @@ struct X3LevFir {
     edge->n = cnt;
   }
 };
+
+// X3LevTone (x3_tone_levels_dev): a position adds x * cos[k] to the record's first slot (re, where
+// x3_level has sum_sq) and x * sin[k] to its second (im, where sum is), k = ph >> 22 of the 32-bit phase ph = position * step
+// mod 2^32; min, max and n are the samples'.  |x * w| <= 2^30 is formed in 32 bits and added in 64: exact, in any order, and
+// the atomic add of two's-complement re on the unsigned slot is exact too, so X3LevAcc, x3l_merge and x3l_merge_runs serve as
+// they are.  The phase is seeded with the lane's first position -- the product in 64 bits, then truncated -- and steps once
+// per position, counted or not: no history, no seam, no edge record.  The table is 1 024 words of (cos: low half, sin: high
+// half); `tab` is the workgroup's LDS copy in the accumulate kernel (x3l_tone_table) and the caller's array in the fix-up.
+#define X3L_TONE_TABLE 1024
+struct X3LevToneTail {   // the kernels' last argument
+  const uint32_t* table;   // the caller's d_table: X3L_TONE_TABLE words
+  uint32_t step;
+};
+struct X3LevTone {
+  static constexpr bool kDiff = false, kFir = false, kState = true, kTone = true;
+  using Tail = X3LevToneTail;
+  const uint32_t* tab = nullptr;
+  uint32_t step = 0, ph = 0;
+  __device__ __forceinline__ void seed(uint64_t g) { ph = (uint32_t)(g * (uint64_t)step); }
+  __device__ __forceinline__ void add(X3LevAcc& a, uint32_t v) {
+    const int32_t s = (int32_t)(int16_t)(uint16_t)v;
+    const uint32_t w = tab[ph >> 22];
+    ph += step;
+    a.sum_sq += (uint64_t)(int64_t)(s * (int32_t)(int16_t)(uint16_t)w);
+    a.sum += (int64_t)(s * ((int32_t)w >> 16));
+    a.mn = min(a.mn, s);
+    a.mx = max(a.mx, s);
+    ++a.n;
+  }
+  __device__ __forceinline__ void skip(uint32_t) { ph += step; }
+};
+// the accumulate kernel's copy of the table: 4 KB of LDS per workgroup, filled by all its lanes in front of the item loop
+__device__ __forceinline__ const uint32_t* x3l_tone_table(const uint32_t* __restrict__ table) {
+  __shared__ uint32_t s_tab[X3L_TONE_TABLE];
+  for (uint32_t t = threadIdx.x; t < (uint32_t)X3L_TONE_TABLE; t += blockDim.x) s_tab[t] = table[t];
+  __syncthreads();
+  return s_tab;
+}
 
 // The bins of consecutive positions from g on: decode(put_at) hands sample s of a frame to put_at(s, value), in order;
 // the positions with keep(s) go to the signal, bins that fill go to flush, and so does the open one at the end; a position
@@ -390,7 +431,8 @@ x3_levels_scan_kernel(const uint32_t* __restrict__ cnt, uint64_t F, uint64_t cap
 }
 
 // ---- accumulate: a lane per (frame, stretch) into the frame's own rows.  Signal: X3LevSamples, or X3LevDiff, whose lanes
-// take the stretch's seed from x3w_stretch and whose lane at the frame's end stores the frame's last sample to tail[f]
+// take the stretch's seed from x3w_stretch and whose lane at the frame's end stores the frame's last sample to tail[f], or
+// X3LevTone, whose workgroups copy the table to LDS first and whose lanes seed the phase with their first position
 template <class Signal>
 __global__ void __launch_bounds__(256)
 x3_levels_accum_kernel(const uint8_t* __restrict__ x3, uint64_t len, const uint64_t* __restrict__ frame_off, uint64_t F,
@@ -402,6 +444,8 @@ x3_levels_accum_kernel(const uint8_t* __restrict__ x3, uint64_t len, const uint6
   const uint64_t bl = x3l_bin_len(bin_len);
   const uint64_t n_items = F * ns;
   const uint64_t lanes = (uint64_t)gridDim.x * blockDim.x;
+  [[maybe_unused]] const uint32_t* tone_tab = nullptr;
+  if constexpr (Signal::kTone) tone_tab = x3l_tone_table(tail.table);
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_items; i += lanes) {
     const uint64_t f = i / ns;
     const uint32_t j = (uint32_t)(i - f * ns);
@@ -413,7 +457,17 @@ x3_levels_accum_kernel(const uint8_t* __restrict__ x3, uint64_t len, const uint6
       if (bin < nlim) x3l_merge(mine + (bin - b0), a);
     };
     // a stretch's samples come in order, from sample 0 or from the first sample of block sb * j
-    if constexpr (Signal::kFir) {
+    if constexpr (Signal::kTone) {
+      const uint64_t g = fr.pos + (j ? 1u + (uint64_t)sb * j * p.block_len : 0u);
+      Signal sig;
+      sig.tab = tone_tab;
+      sig.step = tail.step;
+      sig.seed(g);
+      const int r = x3l_bin_samples(
+          g, bl, [&](auto put_at) { return x3w_stretch(x3, len, frame_off[f], p, idx, segd, sb, nseg, f, j, put_at); },
+          X3LevKeepAll{}, flush, &sig);
+      if (r < 0) atomicOr(&fst[f], X3W_FLAG);
+    } else if constexpr (Signal::kFir) {
       Signal sig;
       sig.k = tail.k;
       sig.edge = tail.edges + (f * tail.stride + j);   // (j < ns <= stride: below F * stride)
@@ -462,7 +516,13 @@ x3_levels_fixup_kernel(const uint8_t* __restrict__ x3, const uint64_t* __restric
         auto flush = [&](uint64_t bin, const X3LevAcc& a) {
           if (bin < fr.nlim) x3l_merge(levels + fr.obase + bin, a);
         };
-        if constexpr (Signal::kFir) {   // the frame is ONE stretch now: its record is its stretch 0's (X3L_DONE says so)
+        if constexpr (Signal::kTone) {
+          Signal sig;
+          sig.tab = tail.table;
+          sig.step = tail.step;
+          sig.seed(fr.pos);
+          (void)x3l_bin_samples(fr.pos, bl, [&](auto put_at) { return x3w_replay_frame(payload, p, blk, put_at); }, X3LevKeepAll{}, flush, &sig);
+        } else if constexpr (Signal::kFir) {   // the frame is ONE stretch now: its record is its stretch 0's (X3L_DONE says so)
           Signal sig;
           sig.k = tail.k;
           sig.edge = tail.edges + f * tail.stride;
@@ -642,5 +702,40 @@ x3_levels_fir_seam_kernel(uint64_t F, uint32_t block_len, const uint2* __restric
       }
     }
     x3l_merge_runs(levels, key, a, lane);
+  }
+}
+
+// ---- the adapter (x3_tone_power_levels_dev): a lane per record, x3_tone_level (re, im in x3_level's
+// first two slots) -> the x3_level of the band's level, in place or into rows that do not overlap.  Integers only:
+//   e = max(0, bitlen(n) - 15); a = re >> (15 + e), b = im >> (15 + e) (arithmetic); P = a * a + b * b, below 2^62 for a
+//   record the tone call wrote (|re|, |im| <= n * 2^30); m = n >> e (1 .. 2^15 - 1, or n itself);
+//   ms = min(2^30, (2 * P / m) / m); peak = min(32767, isqrt(2 * ms)); -> {ms * n, 0, -peak, peak, n, 0}; n == 0: X3L_IDENTITY.
+// Records that no tone call wrote cannot fault anything: the products wrap in 64 unsigned bits and ms is clamped.
+__device__ __forceinline__ uint32_t x3l_isqrt(uint64_t x) {   // floor square root, x < 2^32
+  uint32_t r = 0;
+#pragma unroll
+  for (int b = 15; b >= 0; --b) {
+    const uint32_t t = r | (1u << b);
+    if ((uint64_t)t * t <= x) r = t;
+  }
+  return r;
+}
+
+__global__ void __launch_bounds__(256)
+x3_tone_power_kernel(const x3_level* tone, uint64_t n_rows, x3_level* levels) {   // (in place: no __restrict__)
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_rows; i += (uint64_t)gridDim.x * blockDim.x) {
+    const x3_level r = tone[i];
+    x3_level o = X3L_IDENTITY;
+    if (r.n) {
+      const uint32_t bits = 32u - (uint32_t)__clz((int)r.n);
+      const uint32_t e = bits > 15u ? bits - 15u : 0u;
+      const uint64_t a = (uint64_t)((int64_t)r.sum_sq >> (15u + e)), b = (uint64_t)(r.sum >> (15u + e));
+      const uint64_t P = a * a + b * b;
+      const uint64_t m = r.n >> e;
+      const uint64_t ms = min((2u * P / m) / m, (uint64_t)1 << 30);
+      const int32_t peak = (int32_t)min(x3l_isqrt(2u * ms), 32767u);
+      o = x3_level{ms * r.n, 0, -peak, peak, r.n, 0};
+    }
+    levels[i] = o;
   }
 }

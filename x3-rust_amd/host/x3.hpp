@@ -29,6 +29,7 @@
 // kernels too (x3_bits.h) -- they exist for callers of the reference's building blocks, the frame kernels
 // do not go through them.
 #pragma once
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -821,6 +822,49 @@ inline X3Error levels(Context& ctx, const EncodedStream& s, const Parameters& pa
   return static_cast<X3Error>(rc);
 }
 
+// One oscillator in front of the levels (x3_level_tone): position i has the phase (i * step) mod 2^32, and a bin's record
+// (x3_tone_level) holds re and im, the sums of sample times cos and sin of the phase's table pair, and the samples' min, max
+// and n.  d_table: 1 024 (cos, sin) int16 pairs in device memory, the caller's, alive until the call has run; usual_table()
+// is the one the Python mirror supplies.  step = round(f / fs * 2^32) puts the oscillator at f.
+struct Tone {
+  uint32_t step = 0;
+  const int16_t* d_table = nullptr;
+  x3_level_tone c_tone() const { return x3_level_tone{step, 0, d_table}; }
+  static std::vector<int16_t> usual_table() {   // (round(32767 cos(2 pi k / 1024)), round(32767 sin(2 pi k / 1024))) at pair k
+    std::vector<int16_t> t(2048);
+    const double two_pi = 6.283185307179586476925286766559;
+    for (int k = 0; k < 1024; ++k) {
+      t[2 * k] = static_cast<int16_t>(std::lround(32767.0 * std::cos(two_pi * k / 1024.0)));
+      t[2 * k + 1] = static_cast<int16_t>(std::lround(32767.0 * std::sin(two_pi * k / 1024.0)));
+    }
+    return t;
+  }
+};
+
+// Tone levels (x3_tone_levels_dev): device::levels' arguments with tone records and a Tone.  Waits for the call.
+inline X3Error tone_levels(Context& ctx, const EncodedStream& s, const Parameters& params, const Buffer& d_sample_offsets,
+                           uint64_t bin_len, x3_tone_level* d_levels, uint64_t n_bins, int32_t* d_frame_status,
+                           WindowsResult* res, const Tone& tone) {
+  if (!s.bytes.ok() || !s.frame_offsets.ok() || !d_sample_offsets.ok()) return X3Error::BadArg;
+  const x3_params c = params.c_params();
+  const x3_level_tone t = tone.c_tone();
+  int rc = x3_tone_levels_dev(ctx.raw(), s.bytes.as<uint8_t>(), s.len, s.frame_offsets.as<uint64_t>(),
+                              d_sample_offsets.as<uint64_t>(), s.n_frames, &c, s.seg_blocks ? s.seg_index.as<uint64_t>() : nullptr,
+                              s.seg_blocks, bin_len, d_levels, n_bins, d_frame_status, &t);
+  if (rc != X3_OK) return static_cast<X3Error>(rc);
+  WindowsResult r;
+  rc = x3_levels_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status);
+  if (res) *res = r;
+  return static_cast<X3Error>(rc);
+}
+
+// The adapter into the chain (x3_tone_power_levels_dev): n_rows tone records -> the level records of the band, which
+// device::events and the quantiles calls take; d_levels may be d_tone's bytes (in place).  Asynchronous on the context's
+// stream: the calls behind it are ordered after it.
+inline X3Error tone_power_levels(Context& ctx, const x3_tone_level* d_tone, uint64_t n_rows, x3_level* d_levels) {
+  return static_cast<X3Error>(x3_tone_power_levels_dev(ctx.raw(), d_tone, n_rows, d_levels));
+}
+
 // Events (x3_events_dev): the runs of hot bins of n_bins level records (as device::levels writes them; bins of bin_len
 // positions) under `rule`, as cap slots of (d_starts, d_lens, d_event_levels or nullptr); d_count receives the number found,
 // which may exceed cap; every slot behind the events is a zero-length range, so the arrays go to device::decode_ranges with
@@ -1031,6 +1075,18 @@ class Corpus {
                  WindowsResult* res, const Fir& fir) const {
     const x3_level_fir f = fir.c_fir();
     int rc = x3_corpus_fir_levels_dev(ctx.raw(), raw_, bin_len, d_levels, n_rows, d_frame_status, &f);
+    if (rc != X3_OK) return static_cast<X3Error>(rc);
+    WindowsResult r;
+    rc = x3_levels_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status);
+    if (res) *res = r;
+    return static_cast<X3Error>(rc);
+  }
+  // Tone levels of every entry (x3_corpus_tone_levels_dev): levels()' rows as tone records; the phase restarts at 0 with
+  // every entry.  Waits for the call.
+  X3Error tone_levels(Context& ctx, uint64_t bin_len, x3_tone_level* d_levels, uint64_t n_rows, int32_t* d_frame_status,
+                      WindowsResult* res, const Tone& tone) const {
+    const x3_level_tone t = tone.c_tone();
+    int rc = x3_corpus_tone_levels_dev(ctx.raw(), raw_, bin_len, d_levels, n_rows, d_frame_status, &t);
     if (rc != X3_OK) return static_cast<X3Error>(rc);
     WindowsResult r;
     rc = x3_levels_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status);

@@ -79,6 +79,27 @@ pub mod ffi {
         pub shift: u32,
         pub taps: [i16; 8],
     }
+    /// `x3_level_tone`: the oscillator of `x3_tone_levels_dev` / `x3_corpus_tone_levels_dev` (16 bytes); `d_table` is a
+    /// device array of 1 024 (cos, sin) `i16` pairs, 4-byte aligned; `reserved` must be 0
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, PartialEq, Eq)]
+    pub struct x3_level_tone {
+        pub step: u32,
+        pub reserved: u32,
+        pub d_table: *const i16,
+    }
+    /// `x3_tone_level`: one bin of `x3_tone_levels_dev` / `x3_corpus_tone_levels_dev` (32 bytes, `x3_level`'s layout slot for
+    /// slot)
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+    pub struct x3_tone_level {
+        pub re: i64,
+        pub im: i64,
+        pub min: i32,
+        pub max: i32,
+        pub n: u32,
+        pub reserved: u32,
+    }
     /// `x3_event_rule`: which bins are hot and how runs of them become events (`x3_events_dev`; 32 bytes)
     #[repr(C)]
     #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
@@ -245,6 +266,13 @@ pub mod ffi {
                                  fir: *const x3_level_fir) -> c_int;
         pub fn x3_corpus_fir_levels_dev(ctx: *mut x3_ctx, corpus: *const x3_corpus, bin_len: u64, d_levels: *mut x3_level,
                                         n_rows: u64, d_frame_status: *mut i32, fir: *const x3_level_fir) -> c_int;
+        pub fn x3_tone_levels_dev(ctx: *mut x3_ctx, d_x3: *const u8, x3_len: u64, d_frame_offsets: *const u64,
+                                  d_sample_offsets: *const u64, n_frames: u64, p: *const x3_params, d_seg_index: *const u64,
+                                  seg_blocks: u32, bin_len: u64, d_levels: *mut x3_tone_level, n_bins: u64,
+                                  d_frame_status: *mut i32, tone: *const x3_level_tone) -> c_int;
+        pub fn x3_corpus_tone_levels_dev(ctx: *mut x3_ctx, corpus: *const x3_corpus, bin_len: u64, d_levels: *mut x3_tone_level,
+                                         n_rows: u64, d_frame_status: *mut i32, tone: *const x3_level_tone) -> c_int;
+        pub fn x3_tone_power_levels_dev(ctx: *mut x3_ctx, d_tone: *const x3_tone_level, n_rows: u64, d_levels: *mut x3_level) -> c_int;
         pub fn x3_events_dev(ctx: *mut x3_ctx, d_levels: *const x3_level, n_bins: u64, bin_len: u64, d_total: *const u64,
                              rule: *const x3_event_rule, d_starts: *mut u64, d_lens: *mut u32, d_event_levels: *mut x3_level,
                              cap: u64, d_count: *mut u64) -> c_int;
@@ -1503,6 +1531,76 @@ pub mod device {
         Ok((n_bad, first_bad, st))
     }
 
+    /// One bin of `tone_levels` / `Corpus::tone_levels` (`x3_tone_level`): `re` and `im`, the sums of sample times cos and
+    /// sin of the oscillator's phase, and the samples' `min`, `max` and `n`
+    pub type ToneLevel = ffi::x3_tone_level;
+
+    /// The oscillator of `tone_levels` (`x3_level_tone`): position `i` has the phase `(i * step) mod 2^32`, whose top ten bits
+    /// pick the table pair.  The table is 1 024 (cos, sin) `i16` pairs in a device buffer of the caller's (`tone_table()`
+    /// uploaded, or any other contents)
+    #[derive(Clone, Copy)]
+    pub struct Tone<'a, 'g> {
+        pub step: u32,
+        pub table: &'a Buffer<'g>,
+    }
+
+    impl Tone<'_, '_> {
+        fn c(&self) -> error::Result<ffi::x3_level_tone> {
+            if self.table.len() < 4096 {
+                return Err(X3Error::BadArg);
+            }
+            Ok(ffi::x3_level_tone { step: self.step, reserved: 0, d_table: self.table.as_ptr::<i16>() as *const i16 })
+        }
+    }
+
+    /// The usual table: `(round(32767 cos(2 pi k / 1024)), round(32767 sin(2 pi k / 1024)))` at pair `k`, 2 048 values
+    pub fn tone_table() -> Vec<i16> {
+        let mut t = Vec::with_capacity(2048);
+        for k in 0..1024 {
+            let a = 2.0 * core::f64::consts::PI * (k as f64) / 1024.0;
+            t.push((32767.0 * a.cos()).round() as i16);
+            t.push((32767.0 * a.sin()).round() as i16);
+        }
+        t
+    }
+
+    /// Tone levels (`x3_tone_levels_dev`; not in the reference crate): arguments and result as `levels`, the records
+    /// `ToneLevel`s
+    #[allow(clippy::too_many_arguments)]
+    pub fn tone_levels<'g>(gpu: &'g Gpu, s: &EncodedStream<'g>, params: &x3::Parameters, sample_offsets: &Buffer<'g>, bin_len: u64,
+                           d_levels: &mut Buffer<'g>, n_bins: usize, d_frame_status: Option<&mut Buffer<'g>>, tone: &Tone<'_, 'g>)
+                           -> error::Result<(u64, u64, i32)> {
+        if d_levels.len() < core::mem::size_of::<ToneLevel>() * n_bins || d_frame_status.as_ref().map_or(false, |b| b.len() < 4 * s.n_frames) {
+            return Err(X3Error::BadArg);
+        }
+        let p = params.c()?;
+        let t = tone.c()?;
+        let idx = match &s.seg_index { Some(i) => i.as_ptr::<u64>() as *const u64, None => core::ptr::null() };
+        let st_ptr = match d_frame_status { Some(b) => b.as_ptr::<i32>(), None => core::ptr::null_mut() };
+        error::check(unsafe {
+            ffi::x3_tone_levels_dev(gpu.raw(), s.bytes.as_ptr::<u8>(), s.len as u64, s.frame_offsets.as_ptr::<u64>(),
+                                    sample_offsets.as_ptr::<u64>(), s.n_frames as u64, &p, idx, s.seg_blocks, bin_len,
+                                    d_levels.as_ptr::<ToneLevel>(), n_bins as u64, st_ptr, &t)
+        })?;
+        let (mut n_bad, mut first_bad, mut st) = (0u64, 0u64, 0);
+        error::check(unsafe { ffi::x3_levels_result(gpu.raw(), &mut n_bad, &mut first_bad, &mut st) })?;
+        Ok((n_bad, first_bad, st))
+    }
+
+    /// The adapter into the chain (`x3_tone_power_levels_dev`): the first `n_rows` tone records of `d_tone` -> the `Level`
+    /// records of the band in `d_levels` (`None`: in place), which `events` and the quantiles calls take.  Asynchronous on the
+    /// context's stream
+    pub fn tone_power_levels<'g>(gpu: &'g Gpu, d_tone: &mut Buffer<'g>, n_rows: usize, d_levels: Option<&mut Buffer<'g>>)
+                                 -> error::Result<()> {
+        let bytes = core::mem::size_of::<Level>() * n_rows;
+        if d_tone.len() < bytes || d_levels.as_ref().map_or(false, |b| b.len() < bytes) {
+            return Err(X3Error::BadArg);
+        }
+        let src = d_tone.as_ptr::<ToneLevel>();
+        let dst = match d_levels { Some(b) => b.as_ptr::<Level>(), None => src as *mut Level };
+        error::check(unsafe { ffi::x3_tone_power_levels_dev(gpu.raw(), src as *const ToneLevel, n_rows as u64, dst) })
+    }
+
     /// The rule of `events` / `Corpus::events` (`x3_event_rule`): a bin is hot when `sum_sq >= mean_sq_min * n` or `max(max,
     /// -min) >= peak_min` (0: off); hot bins with at most `join_bins` cold ones between them are one run; runs of fewer than
     /// `min_bins` bins are dropped; `pad_bins` on both sides (`2 * pad_bins <= join_bins`); pieces of `max_bins` (0: no cut)
@@ -1848,6 +1946,24 @@ pub mod device {
             let st_ptr = match d_frame_status { Some(b) => b.as_ptr::<i32>(), None => core::ptr::null_mut() };
             error::check(unsafe {
                 ffi::x3_corpus_fir_levels_dev(self.gpu.raw(), self.raw, bin_len, d_levels.as_ptr::<Level>(), n_rows as u64, st_ptr, fir)
+            })?;
+            let (mut n_bad, mut first_bad, mut st) = (0u64, 0u64, 0);
+            error::check(unsafe { ffi::x3_levels_result(self.gpu.raw(), &mut n_bad, &mut first_bad, &mut st) })?;
+            Ok((n_bad, first_bad, st))
+        }
+
+        /// Tone levels of every entry (`x3_corpus_tone_levels_dev`): `levels`' rows as `ToneLevel`s; the phase restarts at 0
+        /// with every entry
+        pub fn tone_levels(&self, bin_len: u64, d_levels: &mut Buffer<'g>, n_rows: usize, d_frame_status: Option<&mut Buffer<'g>>,
+                           tone: &Tone<'_, 'g>) -> error::Result<(u64, u64, i32)> {
+            if d_levels.len() < core::mem::size_of::<ToneLevel>() * n_rows
+                || d_frame_status.as_ref().map_or(false, |b| b.len() < 4 * self.info().1 as usize) {
+                return Err(X3Error::BadArg);
+            }
+            let t = tone.c()?;
+            let st_ptr = match d_frame_status { Some(b) => b.as_ptr::<i32>(), None => core::ptr::null_mut() };
+            error::check(unsafe {
+                ffi::x3_corpus_tone_levels_dev(self.gpu.raw(), self.raw, bin_len, d_levels.as_ptr::<ToneLevel>(), n_rows as u64, st_ptr, &t)
             })?;
             let (mut n_bad, mut first_bad, mut st) = (0u64, 0u64, 0);
             error::check(unsafe { ffi::x3_levels_result(self.gpu.raw(), &mut n_bad, &mut first_bad, &mut st) })?;

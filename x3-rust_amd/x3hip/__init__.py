@@ -63,6 +63,7 @@ SYMBOLS = [
     "x3_corpus_destroy",
     "x3_levels_dev", "x3_levels_result", "x3_corpus_levels_rows", "x3_corpus_levels_dev",
     "x3_signal_levels_dev", "x3_corpus_signal_levels_dev", "x3_fir_levels_dev", "x3_corpus_fir_levels_dev",
+    "x3_tone_levels_dev", "x3_corpus_tone_levels_dev", "x3_tone_power_levels_dev",
     "x3_events_dev", "x3_corpus_events_dev", "x3_events_result",
     "x3_level_quantiles_dev", "x3_corpus_level_quantiles_dev", "x3_level_quantiles_result",
     "x3_level_thresholds_dev", "x3_corpus_level_thresholds_dev", "x3_events_adaptive_dev", "x3_corpus_events_adaptive_dev",
@@ -125,6 +126,56 @@ class Fir:
         return LevelFir(len(self.taps), self.shift, (C.c_int16 * 8)(*self.taps))
 
 
+class LevelTone(C.Structure):
+    """x3_level_tone: the oscillator of x3_tone_levels_dev / x3_corpus_tone_levels_dev; d_table is a device pointer"""
+    _fields_ = [("step", C.c_uint32), ("reserved", C.c_uint32), ("d_table", C.c_void_p)]
+
+
+TONE_TABLE_PAIRS = 1024   # (cos, sin) int16 pairs of a tone table: 4 096 bytes
+
+
+def tone_table():
+    """-> the usual table, np.int16 [1024, 2]: (round(32767 cos(2 pi k / 1024)), round(32767 sin(2 pi k / 1024))) at pair k"""
+    a = 2.0 * np.pi * np.arange(TONE_TABLE_PAIRS) / TONE_TABLE_PAIRS
+    return np.stack([np.rint(32767.0 * np.cos(a)), np.rint(32767.0 * np.sin(a))], axis=1).astype(np.int16)
+
+
+class Tone:
+    """One oscillator in front of the levels: position i has the phase (i * step) mod 2^32, and a bin's record holds the
+    quadrature sums of its samples against the usual table (tone_table(); x3_tone_levels_dev).  step: 0 .. 2^32 - 1, the
+    frequency in units of sample_rate / 2^32; immutable, checked here.  tone_levels() returns the sums; wherever `signal=`
+    goes a Tone means those sums through tone_power_levels_dev: the level records of the band."""
+    __slots__ = ("step",)
+
+    def __init__(self, step):
+        if isinstance(step, bool) or not isinstance(step, (int, np.integer)) or not 0 <= int(step) <= 0xFFFFFFFF:
+            raise ValueError("Tone: an integer step, 0 .. 2^32 - 1")
+        object.__setattr__(self, "step", int(step))
+
+    @classmethod
+    def at(cls, freq, sample_rate):
+        """the Tone nearest to `freq` at `sample_rate` (0 <= freq < sample_rate): step = round(freq / sample_rate * 2^32),
+        and 2^32 - 1, the last step below the sample rate, where that rounds to 2^32 (which would be step 0: DC)"""
+        if not sample_rate > 0 or not 0 <= freq < sample_rate:
+            raise ValueError("Tone.at: 0 <= freq < sample_rate")
+        return cls(min(int(round(float(freq) / float(sample_rate) * 4294967296.0)), 0xFFFFFFFF))
+
+    def __setattr__(self, name, value):
+        raise AttributeError("Tone is immutable")
+
+    def __delattr__(self, name):
+        raise AttributeError("Tone is immutable")
+
+    def __eq__(self, other):
+        return isinstance(other, Tone) and self.step == other.step
+
+    def __hash__(self):
+        return hash(("Tone", self.step))
+
+    def __repr__(self):
+        return "Tone(step=%d)" % self.step
+
+
 def level_signal(signal, fir=True):
     """the keyword `signal` of the levels methods ("samples" | "diff", or a LEVEL_SIGNAL_* value) -> the C ABI's int; a
     Fir is handed through (fir=False: to the range-levels keyword, which takes no Fir and raises; fir_range_levels does)"""
@@ -132,13 +183,20 @@ def level_signal(signal, fir=True):
         if not fir:
             raise ValueError("signal: range levels of a Fir signal are not built yet on this keyword: call fir_range_levels")
         return signal
+    if isinstance(signal, Tone):
+        if not fir:
+            raise ValueError("signal: range levels of a Tone signal are not built yet (levels, events, level_quantiles and adaptive_events take one)")
+        return signal
     if signal in LEVEL_SIGNALS:
         return LEVEL_SIGNALS[signal]
     if signal in LEVEL_SIGNALS.values() and not isinstance(signal, bool):
         return int(signal)
-    raise ValueError('signal: "samples", "diff" or a Fir')
+    raise ValueError('signal: "samples", "diff", a Fir or a Tone')
 
 
+# x3_tone_level: one bin of x3_tone_levels_dev / x3_corpus_tone_levels_dev (32 bytes, x3_level's layout slot for slot)
+TONE_DTYPE = np.dtype([("re", np.int64), ("im", np.int64), ("min", np.int32), ("max", np.int32), ("n", np.uint32),
+                       ("reserved", np.uint32)])
 # x3_level: one bin of x3_levels_dev / x3_corpus_levels_dev (32 bytes)
 LEVEL_DTYPE = np.dtype([("sum_sq", np.uint64), ("sum", np.int64), ("min", np.int32), ("max", np.int32), ("n", np.uint32),
                         ("reserved", np.uint32)])
@@ -348,6 +406,9 @@ def lib():
     L.x3_corpus_signal_levels_dev.argtypes = [vp, vp, u64, vp, u64, vp, C.c_int]
     L.x3_fir_levels_dev.argtypes = [vp, vp, u64, vp, vp, u64, PP, vp, u32, u64, vp, u64, vp, C.POINTER(LevelFir)]
     L.x3_corpus_fir_levels_dev.argtypes = [vp, vp, u64, vp, u64, vp, C.POINTER(LevelFir)]
+    L.x3_tone_levels_dev.argtypes = [vp, vp, u64, vp, vp, u64, PP, vp, u32, u64, vp, u64, vp, C.POINTER(LevelTone)]
+    L.x3_corpus_tone_levels_dev.argtypes = [vp, vp, u64, vp, u64, vp, C.POINTER(LevelTone)]
+    L.x3_tone_power_levels_dev.argtypes = [vp, vp, u64, vp]
     L.x3_events_dev.argtypes = [vp, vp, u64, u64, vp, C.POINTER(EventRule), vp, vp, vp, u64, vp]
     L.x3_corpus_events_dev.argtypes = [vp, vp, vp, u64, u64, C.POINTER(EventRule), vp, vp, vp, vp, u64, vp]
     L.x3_events_result.argtypes = [vp, C.POINTER(u64)]
@@ -750,6 +811,9 @@ class Context:
 
     def close(self):
         if self._h:
+            if getattr(self, "_tone_table", None):
+                self.free(self._tone_table)
+                self._tone_table = None
             lib().x3_ctx_destroy(self._h)
             self._h = C.c_void_p()
 
@@ -1114,6 +1178,42 @@ class Context:
     def corpus_fir_levels_dev(self, corpus, bin_len, d_levels, n_rows, d_frame_status=None, fir=None):
         """x3_corpus_fir_levels_dev: corpus_levels_dev behind an integer FIR filter; asynchronous, levels_result waits"""
         return lib().x3_corpus_fir_levels_dev(self._h, corpus._h, bin_len, d_levels, n_rows, d_frame_status, self._fir_arg(fir))
+
+    def tone_table_dev(self):
+        """-> the device pointer of the usual table (tone_table()), made at the first call and kept until close()"""
+        if not getattr(self, "_tone_table", None):
+            t = tone_table()
+            p = self.alloc(t.nbytes)
+            try:
+                self.upload(p, t)
+            except X3Error:
+                self.free(p)
+                raise
+            self._tone_table = p
+        return self._tone_table
+
+    def _tone_arg(self, tone):
+        """a Tone (with the context's usual table), a LevelTone as it is, or None (NULL, which the library refuses)"""
+        if tone is None:
+            return None
+        return C.byref(LevelTone(tone.step, 0, self.tone_table_dev()) if isinstance(tone, Tone) else tone)
+
+    def tone_levels_dev(self, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, params, bin_len, d_levels, n_bins,
+                        d_frame_status=None, d_seg_index=None, seg_blocks=0, tone=None):
+        """x3_tone_levels_dev: n_bins x3_tone_level records (TONE_DTYPE), the quadrature sums of the bins' samples against
+        one oscillator (tone: a Tone, or a LevelTone as it is); asynchronous, levels_result waits"""
+        return lib().x3_tone_levels_dev(self._h, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, C.byref(params),
+                                        d_seg_index, seg_blocks, bin_len, d_levels, n_bins, d_frame_status, self._tone_arg(tone))
+
+    def corpus_tone_levels_dev(self, corpus, bin_len, d_levels, n_rows, d_frame_status=None, tone=None):
+        """x3_corpus_tone_levels_dev: corpus_levels_dev's rows as tone records, the phase restarting at every entry;
+        asynchronous, levels_result waits"""
+        return lib().x3_corpus_tone_levels_dev(self._h, corpus._h, bin_len, d_levels, n_rows, d_frame_status, self._tone_arg(tone))
+
+    def tone_power_levels_dev(self, d_tone, n_rows, d_levels):
+        """x3_tone_power_levels_dev: n_rows tone records -> the x3_level records of the band's level (d_levels == d_tone: in
+        place); asynchronous on the context's stream, no result call"""
+        return lib().x3_tone_power_levels_dev(self._h, d_tone, n_rows, d_levels)
 
     def levels_result(self):
         """-> (rc, n_bad_frames, first_bad, first_bad_status) of the last levels_dev / corpus_levels_dev"""
@@ -1652,7 +1752,11 @@ class WindowSource:
 
     def levels_into(self, bin_len, d_levels, n_bins, d_frame_status=None, signal=LEVEL_SIGNAL_SAMPLES):
         """enqueue x3_signal_levels_dev over this source (device pointers; signal: a LEVEL_SIGNAL_* value), or
-        x3_fir_levels_dev (signal: a Fir); -> rc; Context.levels_result waits"""
+        x3_fir_levels_dev (signal: a Fir), or x3_tone_levels_dev and the adapter in place behind it (signal: a Tone); -> rc;
+        Context.levels_result waits"""
+        if isinstance(signal, Tone):
+            return (self.tone_levels_into(bin_len, signal, d_levels, n_bins, d_frame_status)
+                    or self.ctx.tone_power_levels_dev(d_levels, n_bins, d_levels))
         if isinstance(signal, Fir):
             return self.ctx.fir_levels_dev(self.d_x3, self.x3_len, self.d_frame_offsets, self.d_sample_offsets, self.n_frames,
                                            self.params, bin_len, d_levels, n_bins, d_frame_status, self.d_seg_index,
@@ -1661,27 +1765,49 @@ class WindowSource:
                                           self.params, bin_len, d_levels, n_bins, d_frame_status, self.d_seg_index,
                                           self.seg_blocks, signal)
 
-    def levels(self, bin_len, n_bins=None, *, signal="samples"):
-        """-> (records np.ndarray of LEVEL_DTYPE [n_bins], frame statuses np.int32 [n_frames]): min, max, n, sum and sum of
-        squares per bin of bin_len positions (0: one bin); n_bins: as many as cover the stream unless given.
-        signal: "samples", or "diff" -- the samples' first difference, clamped to 16 bits (x3_signal_levels_dev) -- or a
-        Fir: the samples behind an integer FIR filter (x3_fir_levels_dev)"""
-        sig = level_signal(signal)
+    def tone_levels_into(self, bin_len, tone, d_levels, n_bins, d_frame_status=None):
+        """enqueue x3_tone_levels_dev over this source (device pointers; tone: a Tone or a LevelTone); -> rc;
+        Context.levels_result waits"""
+        return self.ctx.tone_levels_dev(self.d_x3, self.x3_len, self.d_frame_offsets, self.d_sample_offsets, self.n_frames,
+                                        self.params, bin_len, d_levels, n_bins, d_frame_status, self.d_seg_index,
+                                        self.seg_blocks, tone)
+
+    def _levels_np(self, what, bin_len, n_bins, dtype, enqueue):
+        """the host side of levels() / tone_levels(): enqueue(d_levels, d_status) -> rc, then the result and both downloads"""
         if n_bins is None:
             n_bins = max(1, -(-self.total // bin_len)) if bin_len else 1
-        d_lv, d_st = self.ctx.alloc(LEVEL_DTYPE.itemsize * n_bins), self.ctx.alloc(4 * self.n_frames)
+        d_lv, d_st = self.ctx.alloc(dtype.itemsize * n_bins), self.ctx.alloc(4 * self.n_frames)
         try:
-            rc = self.levels_into(bin_len, d_lv, n_bins, d_st, sig)
+            rc = enqueue(d_lv, n_bins, d_st)
             if rc:
-                raise X3Error(rc, "x3_signal_levels_dev: " + self.ctx.last_error())
+                raise X3Error(rc, what + ": " + self.ctx.last_error())
             rc = self.ctx.levels_result()[0]
             if rc:
                 raise X3Error(rc, "x3_levels_result: " + self.ctx.last_error())
-            return (self.ctx.download(d_lv, LEVEL_DTYPE.itemsize * n_bins, LEVEL_DTYPE),
+            return (self.ctx.download(d_lv, dtype.itemsize * n_bins, dtype),
                     self.ctx.download(d_st, 4 * self.n_frames, np.int32))
         finally:
             for p in (d_lv, d_st):
                 self.ctx.free(p)
+
+    def tone_levels(self, bin_len, tone, n_bins=None):
+        """-> (records np.ndarray of TONE_DTYPE [n_bins], frame statuses np.int32 [n_frames]): re, im -- the sums of sample
+        times cos and sin of the oscillator's phase -- and the samples' min, max, n per bin of bin_len positions (0: one bin).
+        tone: a Tone (x3_tone_levels_dev with the usual table)"""
+        if not isinstance(tone, Tone):
+            raise ValueError("tone: a Tone")
+        return self._levels_np("x3_tone_levels_dev", bin_len, n_bins, TONE_DTYPE,
+                               lambda d_lv, nb, d_st: self.tone_levels_into(bin_len, tone, d_lv, nb, d_st))
+
+    def levels(self, bin_len, n_bins=None, *, signal="samples"):
+        """-> (records np.ndarray of LEVEL_DTYPE [n_bins], frame statuses np.int32 [n_frames]): min, max, n, sum and sum of
+        squares per bin of bin_len positions (0: one bin); n_bins: as many as cover the stream unless given.
+        signal: "samples", or "diff" -- the samples' first difference, clamped to 16 bits (x3_signal_levels_dev) -- or a
+        Fir: the samples behind an integer FIR filter (x3_fir_levels_dev) -- or a Tone: the level of the band at one
+        oscillator (x3_tone_levels_dev, then x3_tone_power_levels_dev in place)"""
+        sig = level_signal(signal)
+        return self._levels_np("x3_signal_levels_dev", bin_len, n_bins, LEVEL_DTYPE,
+                               lambda d_lv, nb, d_st: self.levels_into(bin_len, d_lv, nb, d_st, sig))
 
     def events_into(self, d_levels, n_bins, bin_len, rule, d_starts, d_lens, d_event_levels, cap, d_count):
         """enqueue x3_events_dev over n_bins records this source's levels_dev wrote (device pointers; the sample count is the
@@ -2022,9 +2148,13 @@ class Corpus:
 
     def levels_into(self, bin_len, d_levels, n_rows, d_frame_status=None, signal=LEVEL_SIGNAL_SAMPLES):
         """enqueue x3_corpus_signal_levels_dev (device pointers; signal: a LEVEL_SIGNAL_* value), or
-        x3_corpus_fir_levels_dev (signal: a Fir); -> rc; Context.levels_result waits"""
+        x3_corpus_fir_levels_dev (signal: a Fir), or x3_corpus_tone_levels_dev and the adapter in place behind it (signal: a
+        Tone); -> rc; Context.levels_result waits"""
         if self._h is None:
             raise ValueError("the corpus is closed")
+        if isinstance(signal, Tone):
+            return (self.tone_levels_into(bin_len, signal, d_levels, n_rows, d_frame_status)
+                    or self.ctx.tone_power_levels_dev(d_levels, n_rows, d_levels))
         if isinstance(signal, Fir):
             return self.ctx.corpus_fir_levels_dev(self, bin_len, d_levels, n_rows, d_frame_status, signal)
         return self.ctx.corpus_signal_levels_dev(self, bin_len, d_levels, n_rows, d_frame_status, signal)
@@ -2032,23 +2162,50 @@ class Corpus:
     def levels(self, bin_len, *, signal="samples"):
         """-> (records np.ndarray of LEVEL_DTYPE [rows], row_first np.uint64 [n_entries + 1], frame statuses np.int32
         [n_frames]): the levels of every entry, positions relative to the entry, bins of bin_len positions (0: one bin).
-        signal: "samples", or "diff" -- the samples' first difference, clamped to 16 bits (x3_signal_levels_dev) -- or a Fir (x3_corpus_fir_levels_dev); no difference and no filter history crosses from one entry into the next"""
+        signal: "samples";
+        "diff" -- the samples' first difference, clamped to 16 bits (x3_corpus_signal_levels_dev);
+        a Fir -- the samples behind an integer FIR filter (x3_corpus_fir_levels_dev);
+        a Tone -- the level of the band at one oscillator (x3_corpus_tone_levels_dev, then x3_tone_power_levels_dev in
+        place).
+        Every entry stands alone: no difference and no filter history crosses from one entry into the next, and a Tone's
+        phase is 0 at every entry's start"""
         sig = level_signal(signal)
+        return self._levels_np("x3_corpus_signal_levels_dev", bin_len, LEVEL_DTYPE,
+                               lambda d_lv, n_rows, d_st: self.levels_into(bin_len, d_lv, n_rows, d_st, sig))
+
+    def _levels_np(self, what, bin_len, dtype, enqueue):
+        """the host side of levels() / tone_levels(): enqueue(d_levels, n_rows, d_status) -> rc, then the result and the
+        downloads"""
         rf = self.levels_rows(bin_len)
         n_rows = int(rf[-1])
-        d_lv, d_st = self.ctx.alloc(LEVEL_DTYPE.itemsize * n_rows), self.ctx.alloc(4 * max(self.n_frames, 1))
+        d_lv, d_st = self.ctx.alloc(dtype.itemsize * n_rows), self.ctx.alloc(4 * max(self.n_frames, 1))
         try:
-            rc = self.levels_into(bin_len, d_lv, n_rows, d_st, sig)
+            rc = enqueue(d_lv, n_rows, d_st)
             if rc:
-                raise X3Error(rc, "x3_corpus_signal_levels_dev: " + self.ctx.last_error())
+                raise X3Error(rc, what + ": " + self.ctx.last_error())
             rc = self.ctx.levels_result()[0]
             if rc:
                 raise X3Error(rc, "x3_levels_result: " + self.ctx.last_error())
             st = self.ctx.download(d_st, 4 * self.n_frames, np.int32) if self.n_frames else np.zeros(0, dtype=np.int32)
-            return self.ctx.download(d_lv, LEVEL_DTYPE.itemsize * n_rows, LEVEL_DTYPE), rf, st
+            return self.ctx.download(d_lv, dtype.itemsize * n_rows, dtype), rf, st
         finally:
             for p in (d_lv, d_st):
                 self.ctx.free(p)
+
+    def tone_levels_into(self, bin_len, tone, d_levels, n_rows, d_frame_status=None):
+        """enqueue x3_corpus_tone_levels_dev (device pointers; tone: a Tone or a LevelTone); -> rc; Context.levels_result
+        waits"""
+        if self._h is None:
+            raise ValueError("the corpus is closed")
+        return self.ctx.corpus_tone_levels_dev(self, bin_len, d_levels, n_rows, d_frame_status, tone)
+
+    def tone_levels(self, bin_len, tone):
+        """-> (records np.ndarray of TONE_DTYPE [rows], row_first, frame statuses) as levels(): the quadrature sums of every
+        entry's bins against one oscillator, whose phase restarts at 0 with every entry (x3_corpus_tone_levels_dev)"""
+        if not isinstance(tone, Tone):
+            raise ValueError("tone: a Tone")
+        return self._levels_np("x3_corpus_tone_levels_dev", bin_len, TONE_DTYPE,
+                               lambda d_lv, n_rows, d_st: self.tone_levels_into(bin_len, tone, d_lv, n_rows, d_st))
 
     def events_into(self, d_levels, n_rows, bin_len, rule, d_entries, d_starts, d_lens, d_event_levels, cap, d_count):
         """enqueue x3_corpus_events_dev over the n_rows records Context.corpus_levels_dev wrote (device pointers); -> rc;
