@@ -906,7 +906,9 @@ int x3_corpus_tone_levels_dev(x3_ctx* ctx, const x3_corpus* corpus, uint64_t bin
  * For a tone of amplitude A at the oscillator's frequency ms is about A * A / 2, the tone's mean square, and peak about A.
  * At DC (step 0) and at Nyquist (step 2^31) the two quadrature sums do not halve the power between them: the estimate is
  * TWICE the component's mean square there.  |min|, |max| <= 32768 and sum_sq / n <= 2^30 hold as for any x3_level record;
- * merged event records then carry the event's mean band level. */
+ * merged event records then carry the event's mean band level.  The records of x3_tone_range_levels_dev /
+ * x3_corpus_tone_range_levels_dev, packed or padded, go through this call unchanged: n_rows of them, whatever range they
+ * belong to; a padded layout's rows behind a range's last are empty records (n == 0) and come out as the identity. */
 int x3_tone_power_levels_dev(x3_ctx* ctx, const x3_tone_level* d_tone, uint64_t n_rows, x3_level* d_levels);
 /* ---- EVENTS (no counterpart in the reference): runs of loud bins of level records as ranges (entry, start, len), found on
  * the device -- the link between the levels calls and the ranges calls, with no host trip.
@@ -1146,6 +1148,40 @@ int x3_corpus_fir_range_levels_dev(x3_ctx* ctx, const x3_corpus* corpus, const u
                                    const uint32_t* d_lens, uint64_t n_ranges, uint64_t bin_len, uint64_t row_stride,
                                    x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status,
                                    const x3_level_fir* fir);
+/* ---- TONE RANGE LEVELS: the range-levels calls on the tone signal of x3_tone_levels_dev, so that events found in a band
+ * can be looked at again, at finer bins, in that band.  The arguments of x3_range_levels_dev /
+ * x3_corpus_range_levels_dev with x3_tone_level records and a last `tone`, validated by the rule of x3_tone_levels_dev: a
+ * NULL tone, a NULL or misaligned (4 bytes) d_table or reserved != 0 is X3_ERR_BAD_ARG with nothing enqueued, tested before
+ * every other argument.  The struct is copied at the call; the table is read when the kernels run.
+ *   ONE RULE -- the call cuts the stream's (or entry's) tone signal; it does NOT restart the oscillator at the range.
+ * Position i of the stream or entry that holds the range has the phase ph(i) = (i * step) mod 2^32 and the table pair
+ * k(i) = ph(i) >> 22, exactly as in x3_tone_levels_dev: every corpus entry starts at phase 0 and i is counted from the entry's
+ * first position.  Range w = (start, len) has the records of x3_range_levels_dev with
+ *     re = sum of x[start + r] * cos[k(start + r)],  im = sum of x[start + r] * sin[k(start + r)]
+ * over the positions of a bin that lie in frames with status 0, and min, max, n field for field those of the SAMPLES
+ * range-levels record.  An empty bin is {0, 0, 32767, -32768, 0, 0}.
+ *   - The range (0, total) at bin length b equals x3_tone_levels_dev at b, record for record, damaged frames included.
+ *   - A range whose start and length are multiples of b equals the slice of those records, the last record cut to the range.
+ *   - A table of all (1, 0) gives re == the sum of the SAMPLES range-levels record and im == 0, with its min, max and n;
+ *     step 0 with the usual table gives re == 32767 * that sum.
+ *   - d_status[w], row offsets, R(w), packed and padded layouts, rows_cap rules, refusals, zero-length ranges and identities
+ *     are x3_range_levels_dev's byte for byte; the status never depends on the tone.
+ *   - THE PHASE IS THE STREAM'S: two ranges of equal length at different starts over identical samples differ in re and im
+ *     (by the rotation through the phase between their starts, up to the table's rounding).  Across ranges compare BAND
+ *     POWER -- re^2 + im^2, or the records x3_tone_power_levels_dev makes of them -- never the raw sums.
+ *   x3_range_levels_result, the pending slot, the workspace and the options "last_range_levels_replays" /
+ * "last_range_levels_overflow" are shared with the other forms; P is the SAMPLES form's (there are no lead frames) and there
+ * is no workspace beyond it.  Packed or padded, the records go through x3_tone_power_levels_dev unchanged. */
+int x3_tone_range_levels_dev(x3_ctx* ctx, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
+                             const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
+                             const uint64_t* d_seg_index, uint32_t seg_blocks, const uint64_t* d_starts,
+                             const uint32_t* d_lens, uint64_t n_ranges, uint64_t bin_len, uint64_t row_stride,
+                             x3_tone_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status,
+                             const x3_level_tone* tone);
+int x3_corpus_tone_range_levels_dev(x3_ctx* ctx, const x3_corpus* corpus, const uint32_t* d_entries, const uint64_t* d_starts,
+                                    const uint32_t* d_lens, uint64_t n_ranges, uint64_t bin_len, uint64_t row_stride,
+                                    x3_tone_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status,
+                                    const x3_level_tone* tone);
 void x3_corpus_destroy(x3_corpus* corpus);
 
 /* ------------------------------------------------------------------ multi-GPU (no reference analogue) */

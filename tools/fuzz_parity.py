@@ -29,7 +29,10 @@ Families: (e) the single-pass encoders on block_len 20 with mixed content, many 
           (x3_tone_levels_dev / x3_corpus_tone_levels_dev): a random step -- 0, 2^30, 2^31 and 2^32 - 1 among them -- and the
           usual table or a random one, GPU == tests/tone_levels_ref.py; the adapter (x3_tone_power_levels_dev, by
           levels(signal=Tone)) against the reference on the same records; a table of all (1, 0) against x3_levels_dev's sums
-          (not in the default family set)."""
+          (not in the default family set); (p) family (r) against a random Tone (x3_tone_range_levels_dev): a random step
+          and the usual table or a random one, with starts drawn to frame and stretch boundaries +- 1 (the phase seeds of
+          lanes and fix-up), as a stream and as a corpus of random entries (x3_corpus_tone_range_levels_dev: the phase is 0
+          at every entry), GPU == tests/tone_range_levels_ref.py (not in the default family set)."""
 import argparse, ctypes as C, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "x3-rust_amd"))
@@ -810,9 +813,10 @@ fams["c"] = fam_c
 fams["x"] = fam_x
 
 
-def fam_r(rng, tag, diff=False, fir=None):
+def fam_r(rng, tag, diff=False, fir=None, tone=False):
     """range levels (diff: of the first difference, against signal_range_levels_ref -- family (l); fir: behind that filter,
-    against fir_range_levels_ref -- family (t)): the records, row offsets and statuses of random ranges of a random stream -- any geometry, damaged
+    against fir_range_levels_ref -- family (t); tone: against a drawn oscillator, tone_range_levels_ref, then the same
+    frames as a corpus of random entries -- family (p)): the records, row offsets and statuses of random ranges of a random stream -- any geometry, damaged
     frames, a damaged or walk-built index, packed (exact, cut or roomy capacity) and padded -- against range_levels_ref on
     the oracle's frame verdicts; the output arrays are filled with 0x5A and what no call may write must keep it"""
     import range_levels_ref as RL
@@ -885,6 +889,14 @@ def fam_r(rng, tag, diff=False, fir=None):
                 at = int(rng.integers(0, len(offs))) * spf + int(rng.choice([0, 1, 1 + 4 * p.block_len, 1 + 32 * p.block_len]))
                 at += int(rng.choice([-(T - 1), -1, 0, 1, T - 2, T - 1, T]))
                 starts[w] = max(0, min(at, n - lens[w]))
+    if tone:   # ... one either side of a frame's or a stretch's first sample; the oscillator
+        for w in range(nr):
+            if rng.random() < 0.5:
+                at = int(rng.integers(0, len(offs))) * spf + int(rng.choice([0, 1, 1 + 4 * p.block_len, 1 + 32 * p.block_len]))
+                at += int(rng.choice([-1, 0, 1]))
+                starts[w] = max(0, min(at, n - lens[w]))
+        step = int(rng.choice([0, 1 << 22, 1 << 31, (1 << 32) - 1, int(rng.integers(0, 1 << 32)), int(rng.integers(0, 1 << 32)) | 1]))
+        tab = None if rng.random() < 0.5 else rng.integers(-32768, 32768, (1024, 2)).astype(np.int16)
     wild = [n, n + 1, 2 ** 63, 2 ** 64 - 1, int(rng.integers(n + 1, 2 ** 62))]
     for _ in range(int(rng.integers(0, 3))):
         w = int(rng.integers(0, nr))
@@ -906,7 +918,10 @@ def fam_r(rng, tag, diff=False, fir=None):
     else:
         stride = int(rng.choice([1, max(rows), max(1, max(rows) // 2), max(rows) + 3]))
         cap = nr * stride + int(rng.integers(0, 3))
-    if fir is not None:
+    if tone:
+        import tone_range_levels_ref as TRL
+        want = TRL.range_levels(verdicts, so_a, starts, lens, bin_len, stride, cap, step, tab)
+    elif fir is not None:
         import fir_range_levels_ref as FRL
         want = FRL.range_levels(verdicts, so_a, starts, lens, bin_len, stride, cap, fir.taps, fir.shift)
     elif diff:
@@ -938,7 +953,14 @@ def fam_r(rng, tag, diff=False, fir=None):
             ctx.upload(q, np.full(v + guard, 0x5A, dtype=np.uint8))
         ctx.upload(bufs[3], np.array(starts, dtype=np.uint64))
         ctx.upload(bufs[4], np.array(lens, dtype=np.uint32))
-        if fir is not None:
+        if tone:
+            d_tab = ctx.tone_table_dev()
+            if tab is not None:
+                d_tab = ctx.alloc(4096); d.append(d_tab)
+                ctx.upload(d_tab, tab)
+            level_tone = x3hip.LevelTone(step, 0, d_tab)
+            rc = src.tone_range_levels_into(bufs[3], bufs[4], nr, bin_len, stride, bufs[0], cap, bufs[1], bufs[2], level_tone)
+        elif fir is not None:
             rc = src.fir_range_levels_into(bufs[3], bufs[4], nr, bin_len, stride, bufs[0], cap, bufs[1], bufs[2], fir)
         else:
             rc = src.range_levels_into(bufs[3], bufs[4], nr, bin_len, stride, bufs[0], cap, bufs[1], bufs[2],
@@ -955,6 +977,71 @@ def fam_r(rng, tag, diff=False, fir=None):
         assert np.array_equal(got, want[0]), (tag, "records", np.flatnonzero((got != want[0]).any(axis=1))[:8].tolist(), bin_len, stride, cap)
         nbad = np.flatnonzero(st)
         assert res == (0, nbad.size, int(nbad[0]) if nbad.size else nr, int(st[nbad[0]]) if nbad.size else 0, sum(rows)), (tag, res)
+        if tone and bin_len <= 0xFFFFFFFF:
+            # the same bytes as a corpus: the frames cut into entries at random frame boundaries, ranges of random entries
+            # with starts counted from the entry -- each against the reference on that entry alone (phase 0 at its start)
+            F = len(offs)
+            cuts = sorted(set([0, F] + [int(v) for v in rng.integers(0, F + 1, int(rng.integers(0, 5)))]))
+            ends = offs + [stream.size]
+            e_off = [ends[a] for a in cuts[:-1]]
+            e_len = [ends[b] - ends[a] for a, b in zip(cuts[:-1], cuts[1:])]
+            try:
+                corpus = x3hip.Corpus(ctx, bad, e_off, e_len, params=p, seg_blocks=src.seg_blocks or 8, index="walk")
+            except x3hip.X3Error:   # (a geometry the corpus build refuses an index for)
+                return
+            try:
+                if corpus.entries["n_frames"].tolist() != [b - a for a, b in zip(cuts[:-1], cuts[1:])]:
+                    return
+                ne = len(cuts) - 1
+                ent = [int(rng.integers(0, ne)) if rng.random() < 0.95 else int(rng.choice([ne, 2 ** 32 - 1])) for _ in range(nr)]
+                c_starts, c_lens = [], []
+                for w in range(nr):   # the stream's range moved into the entry that holds its start, or as it is
+                    e = ent[w]
+                    base = so[cuts[e]] if e < ne else 0
+                    size = so[cuts[e + 1]] - base if e < ne else 0
+                    if starts[w] >= base and starts[w] - base <= size and rng.random() < 0.7:
+                        c_starts.append(starts[w] - base)
+                    else:
+                        c_starts.append(int(rng.integers(0, size + 1)) if rng.random() < 0.9 else starts[w])
+                    c_lens.append(lens[w] if rng.random() < 0.5 else min(lens[w], max(0, size - min(c_starts[-1], size))))
+                c_rows = [RL.rows_of(v, bin_len) for v in c_lens]
+                if sum(c_rows) > 1 << 21:
+                    return
+                c_stride = 0 if rng.random() < 0.5 else max(1, max(c_rows) - int(rng.integers(0, 2)))
+                c_cap = nr * c_stride or sum(c_rows)
+                sizes = (32 * c_cap, 8 * (nr + 1), 4 * nr)
+                cb = [ctx.alloc(v + guard) for v in sizes] + [ctx.alloc(8 * nr), ctx.alloc(4 * nr), ctx.alloc(4 * nr)]
+                d.extend(cb)
+                for q, v in zip(cb[:3], sizes):
+                    ctx.upload(q, np.full(v + guard, 0x5A, dtype=np.uint8))
+                ctx.upload(cb[3], np.array(c_starts, dtype=np.uint64))
+                ctx.upload(cb[4], np.array(c_lens, dtype=np.uint32))
+                ctx.upload(cb[5], np.array(ent, dtype=np.uint32))
+                rc = corpus.tone_range_levels_into(cb[5], cb[3], cb[4], nr, bin_len, c_stride, cb[0], c_cap, cb[1], cb[2], level_tone)
+                assert rc == 0, (tag, "corpus rc", rc, ctx.last_error())
+                res = ctx.range_levels_result()
+                raw = [ctx.download(q, v + guard) for q, v in zip(cb[:3], sizes)]
+                for name, a, v in zip(("levels", "offsets", "status"), raw, sizes):
+                    assert (a[v:] == 0x5A).all(), (tag, "corpus canary", name)
+                assert res[0] == 0 and res[4] == sum(c_rows), (tag, "corpus result", res)
+                st = raw[2][:sizes[2]].view(np.int32)
+                got = raw[0][:sizes[0]].reshape(c_cap, 32)
+                at = 0
+                for w in range(nr):
+                    rows_w = c_stride or c_rows[w]
+                    mine = got[w * c_stride:(w + 1) * c_stride] if c_stride else got[at:at + rows_w]
+                    at += c_rows[w]
+                    e = ent[w]
+                    if e >= ne or cuts[e + 1] == cuts[e]:
+                        assert st[w] == RL.ERR_BAD_ARG, (tag, "corpus entry", w, e, int(st[w]))
+                        continue
+                    a, b = cuts[e], cuts[e + 1]
+                    e_so = np.array([so[f] - so[a] for f in range(a, b + 1)], dtype=np.uint64)
+                    w_rec, _, w_st = TRL.range_levels(verdicts[a:b], e_so, [c_starts[w]], [c_lens[w]], bin_len, c_stride, rows_w, step, tab)
+                    assert st[w] == w_st[0], (tag, "corpus status", w, e, c_starts[w], c_lens[w], int(st[w]), int(w_st[0]))
+                    assert np.array_equal(mine, w_rec), (tag, "corpus records", w, e, c_starts[w], c_lens[w], bin_len, c_stride, cuts)
+            finally:
+                corpus.close()
     finally:
         for q in d:
             ctx.free(q)
@@ -1141,6 +1228,7 @@ fams["h"] = fam_h
 fams["o"] = lambda rng, tag: fam_h(rng, tag, tone=True)
 fams["i"] = lambda rng, tag: fam_h(rng, tag, fir=True)
 fams["t"] = lambda rng, tag: fam_r(rng, tag, fir=draw_fir(rng))
+fams["p"] = lambda rng, tag: fam_r(rng, tag, tone=True)
 
 
 def run(seed=1, minutes=None, trials=None, families="egdbaf", only=-1, context=None):

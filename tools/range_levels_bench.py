@@ -23,9 +23,15 @@ x3_corpus_fir_range_levels_dev).  Route a decodes every range with the T - 1 sam
 start, where the first positions count nothing), runs torch's conv1d in float64 over the packed buffer (exact: the sums stay
 inside 2^30), shifts, clamps and reduces; case 3 sums T gathers of its padded rows instead.  Route b is the FIR levels call,
 and case 3's events are found on the FIR levels.
+--signal tone [--step 350898828]: the same cases against one oscillator (x3_tone_range_levels_dev /
+x3_corpus_tone_range_levels_dev with the usual table), records x3_tone_level.  Route a decodes the ranges as they are and
+forms, in torch's int64, every position's phase ((position in the stream or entry) * step mod 2^32 -- the positions are
+made once, outside the timed part), gathers the table pair, multiplies and sums, with min and max of the samples.  Route b is
+the tone levels call; case 3's events are found on the band's levels (the tone levels call and the adapter in place), and
+its merged band records are no tone records, so case 3 compares the call with route a only.
 Every route's records are compared with == at the end of every case and the tool fails otherwise.  Kernel times: run it under
 `rocprofv3 --kernel-trace --stats -- python3 tools/range_levels_bench.py ...`.  Prints one JSON line.
-    python3 tools/range_levels_bench.py [--signal samples|diff|fir] [--taps c0,c1,..] [--shift k] [--samples N] [--reps 10] [--warmup 2] [--cap 4096]
+    python3 tools/range_levels_bench.py [--signal samples|diff|fir|tone] [--taps c0,c1,..] [--shift k] [--step s] [--samples N] [--reps 10] [--warmup 2] [--cap 4096]
                                         [--cases config3,corpus] [--out file.json]"""
 import argparse, ctypes as C, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -43,6 +49,7 @@ class Source:
 
     def __init__(self, ctx, name, rate, n_samples, range_levels, ranges, levels, events, levels_rows):
         self.ctx, self.name, self.rate, self.n_samples = ctx, name, rate, n_samples
+        self.band = lambda d_lv, rows: ctx.tone_power_levels_dev(d_lv, rows, d_lv)      # (--signal tone: records -> band levels)
         self.range_levels, self.ranges, self.levels, self.events, self.levels_rows = range_levels, ranges, levels, events, levels_rows
 
 
@@ -54,6 +61,19 @@ def as_records(mn, mx, sm, sq, n):
     out = np.zeros(len(n), dtype=x3hip.LEVEL_DTYPE)
     out["min"], out["max"], out["sum"], out["sum_sq"], out["n"] = mn, mx, sm, sq, n
     return out
+
+
+def tone_records(re, im, mn, mx, n):
+    out = np.zeros(len(n), dtype=x3hip.TONE_DTYPE)
+    out["re"], out["im"], out["min"], out["max"], out["n"] = re, im, mn, mx, n
+    out["min"][out["n"] == 0], out["max"][out["n"] == 0] = 32767, -32768
+    return out
+
+
+def tone_pairs(a, pos):
+    """route a, tone: (cos, sin) int64 of the positions pos (int64, in the stream or entry)"""
+    k = ((pos * a.step) & 0xFFFFFFFF) >> 22          # (pos < 2^31, step < 2^32: the product stays inside int64)
+    return a.table[k, 0], a.table[k, 1]
 
 
 def filtered(a, w):
@@ -95,6 +115,8 @@ def bins_case(src, a, results, info, case, ent, starts, lens, bin_len):
         for f, v, k in zip(np.concatenate([[0], np.cumsum(lens)[:-1]]), lens, pre):   # the positions without their history
             ok[f:f + min(hist - k, v)] = False
         valid = torch.from_numpy(ok).cuda().view(total_rows, bin_len)
+    if a.tone:    # every sample's position in its stream or entry, in route a's packed order
+        pos = torch.from_numpy(np.concatenate([s + np.arange(v, dtype=np.int64) for s, v in zip(starts, lens)])).cuda()
     rf = src.levels_rows(bin_len)
     full_rows = int(rf[-1])
     full = torch.empty((full_rows, 32), dtype=torch.uint8, device="cuda") if 64 * full_rows < a.levels_bytes else None
@@ -118,6 +140,11 @@ def bins_case(src, a, results, info, case, ent, starts, lens, bin_len):
             red = (torch.where(valid, y, 32767).min(1).values, torch.where(valid, y, -32768).max(1).values,
                    torch.where(valid, y, 0).sum(1, dtype=torch.int64), torch.where(valid, y * y, 0).sum(1, dtype=torch.int64),
                    valid.sum(1))
+        elif a.tone:
+            x = buf.view(total_rows, bin_len)
+            w = buf.to(torch.int64)
+            cs, sn = tone_pairs(a, pos)
+            red = ((w * cs).view(total_rows, bin_len).sum(1), (w * sn).view(total_rows, bin_len).sum(1), x.min(1).values, x.max(1).values)
         else:
             x = buf.view(total_rows, bin_len)
             w = x.to(torch.int32)
@@ -135,8 +162,8 @@ def bins_case(src, a, results, info, case, ent, starts, lens, bin_len):
             timed(results, name + "_route_b", rep, a.warmup, now() - t4)
     got = records(lv)
     counts = red[4].cpu().numpy().astype(np.uint32) if hist_on else np.full(total_rows, bin_len, dtype=np.uint32)
-    want_a = as_records(*(t.cpu().numpy() for t in red[:4]), counts)
-    same = np.array_equal(got, want_a) and not st.cpu().numpy().any()
+    want_a = (tone_records if a.tone else as_records)(*(t.cpu().numpy() for t in red[:4]), counts)
+    same = got.tobytes() == want_a.tobytes() and not st.cpu().numpy().any()
     if full is not None:
         frec = records(full)
         pick = np.concatenate([int(rf[e]) + s // bin_len + np.arange(k) for e, s, k in zip(ent, starts, rows)])
@@ -165,7 +192,9 @@ def events_case(src, a, results, info, bin_len):
     width = stride + hist                        # route a, diff / fir: columns for the samples in front of the range
     buf = torch.empty((cap, width), dtype=torch.int16, device="cuda")
     torch.cuda.synchronize()
-    assert src.levels(bin_len, full.data_ptr(), n_rows) == 0 and ctx.levels_result()[0] == 0
+    assert src.levels(bin_len, full.data_ptr(), n_rows) == 0 and (not a.tone or src.band(full.data_ptr(), n_rows) == 0)
+    assert ctx.levels_result()[0] == 0
+    ctx.sync()
     rec = records(full)
     q = 100.0 * (1.0 - min(0.002, cap / (4.0 * n_rows)))
     peak_min = int(min(max(np.percentile(np.maximum(rec["max"], -rec["min"])[rec["n"] != 0], q) + 1, 1), 32768))
@@ -173,7 +202,7 @@ def events_case(src, a, results, info, bin_len):
     assert src.events(full.data_ptr(), n_rows, bin_len, rule, ent.data_ptr(), st.data_ptr(), ln.data_ptr(), ev_lv.data_ptr(), cap,
                       cnt.data_ptr()) == 0
     rc, found = ctx.events_result()
-    assert rc == 0 and found > 0 and (found <= cap or hist_on), (rc, found)   # (diff: peaks saturate, ties at the
+    assert rc == 0 and found > 0 and (found <= cap or hist_on or a.tone), (rc, found)   # (diff: peaks saturate, ties at the
     # threshold can make more events than slots; the slots then hold the first `cap` of them and no filler)
     col = torch.arange(stride, device="cuda")[None, :]
     red = None
@@ -208,12 +237,17 @@ def events_case(src, a, results, info, bin_len):
             red = (torch.where(mask, y, 32767).min(1).values, torch.where(mask, y, -32768).max(1).values,
                    torch.where(mask, y, 0).sum(1, dtype=torch.int64), torch.where(mask, y * y, 0).sum(1, dtype=torch.int64),
                    mask.sum(1))
+        elif a.tone:   # (the rows behind a range's length hold zeros: they add nothing)
+            cs, sn = tone_pairs(a, st[:, None] + col)
+            w64 = w.to(torch.int64)
+            red = ((w64 * cs).sum(1), (w64 * sn).sum(1), torch.where(mask, w, 32767).min(1).values,
+                   torch.where(mask, w, -32768).max(1).values)
         else:
             red = (torch.where(mask, w, 32767).min(1).values, torch.where(mask, w, -32768).max(1).values,
                    w.sum(1, dtype=torch.int64), (w * w).sum(1, dtype=torch.int64))
         torch.cuda.synchronize()
         t3 = now()
-        assert src.levels(bin_len, full.data_ptr(), n_rows) == 0
+        assert src.levels(bin_len, full.data_ptr(), n_rows) == 0 and (not a.tone or src.band(full.data_ptr(), n_rows) == 0)
         assert src.events(full.data_ptr(), n_rows, bin_len, rule, ent.data_ptr(), st.data_ptr(), ln.data_ptr(), ev_lv2.data_ptr(),
                           cap, cnt.data_ptr()) == 0
         assert ctx.events_result()[0] == 0 and ctx.levels_result()[0] == 0
@@ -225,9 +259,12 @@ def events_case(src, a, results, info, bin_len):
         timed(results, name + "_route_b", rep, a.warmup, t4 - t3)
     got = records(lv)
     counts = red[4].cpu().numpy().astype(np.uint32) if hist_on else ln.cpu().numpy().view(np.uint32)
-    want_a = as_records(*(t.cpu().numpy() for t in red[:4]), counts)
-    same = np.array_equal(got, want_a) and np.array_equal(got, records(ev_lv)) and np.array_equal(got, records(ev_lv2)) and \
-        not status.cpu().numpy().any()
+    want_a = (tone_records if a.tone else as_records)(*(t.cpu().numpy() for t in red[:4]), counts)
+    same = got.tobytes() == want_a.tobytes() and not status.cpu().numpy().any()
+    if a.tone:     # (the events' merged records are band records; both passes found the same events)
+        same = same and np.array_equal(records(ev_lv), records(ev_lv2))
+    else:
+        same = same and np.array_equal(got, records(ev_lv)) and np.array_equal(got, records(ev_lv2))
     if not same:
         raise SystemExit("%s: the routes' records differ" % name)
     info[name] = {"signal": a.signal, "ranges": cap, "events": int(found), "bin_len": 0, "events_bin_len": bin_len, "peak_min": peak_min,
@@ -258,7 +295,7 @@ def cases(src, a, results, info):
 
 def config3(ctx, a, results, info):
     lib = x3hip.lib()
-    n, p, sig = a.samples, x3hip.Params.default(), a.fir or x3hip.level_signal(a.signal)
+    n, p, sig = a.samples, x3hip.Params.default(), a.fir or a.tone or x3hip.level_signal(a.signal)
     wav = torch.empty(n + 32, dtype=torch.int16, device="cuda")
     ctx.synth_dev(2, 0x58330003, 0, n, wav.data_ptr())
     ctx.sync()
@@ -279,11 +316,15 @@ def config3(ctx, a, results, info):
         (lambda d_e, d_s, d_l, k, bl, stride, d_lv, c, d_off, d_st: ctx.fir_range_levels_dev(*s, d_s, d_l, k, bl, stride, d_lv, c,
                                                                                              d_off, d_st, idx.data_ptr(), 32, sig))
         if a.fir else
+        (lambda d_e, d_s, d_l, k, bl, stride, d_lv, c, d_off, d_st: ctx.tone_range_levels_dev(*s, d_s, d_l, k, bl, stride, d_lv, c,
+                                                                                              d_off, d_st, idx.data_ptr(), 32, sig))
+        if a.tone else
         (lambda d_e, d_s, d_l, k, bl, stride, d_lv, c, d_off, d_st: ctx.signal_range_levels_dev(*s, d_s, d_l, k, bl, stride, d_lv, c,
                                                                                                 d_off, d_st, idx.data_ptr(), 32, sig)),
         lambda d_e, d_s, d_l, k, stride, d_out, oc, d_off, d_st: ctx.decode_ranges_dev(*s, d_s, d_l, k, stride, d_out, oc, 0, d_off,
                                                                                        d_st, idx.data_ptr(), 32),
         (lambda bl, d_lv, rows: ctx.fir_levels_dev(*s, bl, d_lv, rows, None, idx.data_ptr(), 32, sig)) if a.fir else
+        (lambda bl, d_lv, rows: ctx.tone_levels_dev(*s, bl, d_lv, rows, None, idx.data_ptr(), 32, sig)) if a.tone else
         (lambda bl, d_lv, rows: ctx.signal_levels_dev(*s, bl, d_lv, rows, None, idx.data_ptr(), 32, sig)),
         lambda d_lv, rows, bl, rule, d_e, d_s, d_l, d_el, c, d_c: ctx.events_dev(d_lv, rows, bl, so.data_ptr() + 8 * F, rule, d_s, d_l,
                                                                                 d_el, c, d_c),
@@ -318,16 +359,20 @@ def corpus_a(ctx, a, results, info):
     offs = [int(fo[first[c]]) for c in range(n_clips)]
     lens = [int(fo[first[c + 1]]) - offs[c] for c in range(n_clips)]
     corpus = x3hip.Corpus(ctx, (d_x3, pos), offs, lens, seg_blocks=32)
-    sig = a.fir or x3hip.level_signal(a.signal)
+    sig = a.fir or a.tone or x3hip.level_signal(a.signal)
     src = Source(
         ctx, "corpus_a", 44_100, ns,
         (lambda d_e, d_s, d_l, k, bl, stride, d_lv, c, d_o, d_st: corpus.fir_range_levels_into(d_e, d_s, d_l, k, bl, stride, d_lv, c, d_o,
                                                                                                d_st, sig))
         if a.fir else
+        (lambda d_e, d_s, d_l, k, bl, stride, d_lv, c, d_o, d_st: corpus.tone_range_levels_into(d_e, d_s, d_l, k, bl, stride, d_lv, c, d_o,
+                                                                                                d_st, sig))
+        if a.tone else
         (lambda d_e, d_s, d_l, k, bl, stride, d_lv, c, d_o, d_st: corpus.range_levels_into(d_e, d_s, d_l, k, bl, stride, d_lv, c, d_o,
                                                                                            d_st, signal=sig)),
         lambda d_e, d_s, d_l, k, stride, d_out, oc, d_o, d_st: corpus.ranges_into(d_e, d_s, d_l, k, stride, d_out, oc, 0, d_o, d_st),
         (lambda bl, d_lv, rows: ctx.corpus_fir_levels_dev(corpus, bl, d_lv, rows, None, sig)) if a.fir else
+        (lambda bl, d_lv, rows: ctx.corpus_tone_levels_dev(corpus, bl, d_lv, rows, None, sig)) if a.tone else
         (lambda bl, d_lv, rows: ctx.corpus_signal_levels_dev(corpus, bl, d_lv, rows, None, sig)),
         lambda d_lv, rows, bl, rule, d_e, d_s, d_l, d_el, c, d_c: corpus.events_into(d_lv, rows, bl, rule, d_e, d_s, d_l, d_el, c, d_c),
         lambda bl: corpus.levels_rows(bl))
@@ -344,24 +389,28 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--cap", type=int, default=4096)
     ap.add_argument("--cases", default="config3,corpus")
-    ap.add_argument("--signal", default="samples", choices=["samples", "diff", "fir"])
+    ap.add_argument("--signal", default="samples", choices=["samples", "diff", "fir", "tone"])
     ap.add_argument("--taps", default="1,-2,1", help="--signal fir: the taps c[0], c[1], ..")
     ap.add_argument("--shift", type=int, default=0)
+    ap.add_argument("--step", type=int, default=350_898_828, help="--signal tone: the oscillator's step (0.0817 of the sample rate)")
     ap.add_argument("--levels-bytes", type=float, default=16e9, help="route b runs where its records and workspace fit in this")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     a.taps = [int(c) for c in a.taps.split(",")]
     a.fir = x3hip.Fir(a.taps, a.shift) if a.signal == "fir" else None
-    a.hist = {"samples": 0, "diff": 1, "fir": len(a.taps) - 1}[a.signal]      # samples in front of a position that its value takes
+    a.hist = {"samples": 0, "diff": 1, "fir": len(a.taps) - 1, "tone": 0}[a.signal]      # samples in front of a position that its value takes
     torch.cuda.init()
     ctx = x3hip.Context(0)
+    a.tone = x3hip.Tone(a.step) if a.signal == "tone" else None
+    if a.tone:
+        a.table = torch.from_numpy(x3hip.tone_table().astype(np.int64)).cuda()
     results, info = {}, {}
     if "config3" in a.cases:
         config3(ctx, a, results, info)
     if "corpus" in a.cases:
         corpus_a(ctx, a, results, info)
     out = {"samples": a.samples, "reps": a.reps, "signal": a.signal, "cases": info,
-           **({"taps": a.taps, "shift": a.shift} if a.fir else {}),
+           **({"taps": a.taps, "shift": a.shift} if a.fir else {}), **({"step": a.step} if a.tone else {}),
            "ms_median": {k: round(float(np.median(v)), 4) for k, v in results.items()},
            "ms_min": {k: round(float(np.min(v)), 4) for k, v in results.items()},
            "ms_max": {k: round(float(np.max(v)), 4) for k, v in results.items()}}

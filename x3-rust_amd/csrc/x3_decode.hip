@@ -2517,12 +2517,16 @@ size_t range_levels_carve(char* base, uint64_t n, uint64_t F, uint64_t P, uint64
 // a signal (x3_fir_range_levels_dev / x3_corpus_fir_range_levels_dev): the lead kernel for T taps, the
 // X3RLevFir instance of the accumulate kernel, which leaves an edge record per (frame, stretch) in fir_ws as in levels_launch,
 // a fix-up of its own and x3_range_levels_fir_seam_kernel behind the merge.  The workspace is the DIFF call's (lead[]).
+// tone (checked: levels_tone_arg; starts: the CALLER'S array) instead of either (x3_tone_range_levels_dev /
+// x3_corpus_tone_range_levels_dev): the X3RLevTone instance of the accumulate and fix-up kernels and
+// nothing else -- no lead frame, no kernel behind the merge, the SAMPLES call's P and workspace.
 template <class Plan>
 static int range_levels_launch(x3_ctx* c, const FrameSource& s, const uint32_t* d_lens, uint64_t n, uint64_t bin_len,
                                uint64_t row_stride, x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets,
                                int32_t* d_status, int signal, const x3_corpus_entry* d_ent, uint64_t n_ent,
-                               const uint32_t* d_entries, Plan plan_step, const X3FirTaps* fir = nullptr) {
-  const bool diff = !fir && signal == X3_LEVEL_SIGNAL_DIFF, lead = diff || fir;
+                               const uint32_t* d_entries, Plan plan_step, const X3FirTaps* fir = nullptr,
+                               const X3RLevToneTail* tone = nullptr) {
+  const bool diff = !fir && !tone && signal == X3_LEVEL_SIGNAL_DIFF, lead = diff || fir;
   const uint64_t lead_frames = fir ? fir->T - 1 : diff ? 1 : 0;   // what a range's plan may hold in front of its covering frames
   HIPCHK(c, hipSetDevice(c->device));
   const uint64_t P = range_levels_pairs(n, s.F, s.max_frames, lead_frames), cap = rows_cap + P;
@@ -2585,7 +2589,8 @@ static int range_levels_launch(x3_ctx* c, const FrameSource& s, const uint32_t* 
                        s.nseg, bin_len, (const unsigned long long*)w.cov_off, (const unsigned long long*)w.row_off,
                        (const uint32_t*)w.erows, row_stride, P, cap, (const unsigned long long*)w.prow, (const int32_t*)w.fst,
                        d_levels, d_status, w.scratch, scratch_per, w.sum, ft, (const uint32_t*)w.lead);
-  } else if (diff) decode(X3LevDiff{}, w.tail);
+  } else if (tone) decode(X3RLevTone{}, *tone);
+  else if (diff) decode(X3LevDiff{}, w.tail);
   else decode(X3LevSamples{}, X3LevNoTail{});
   hipLaunchKernelGGL(x3_range_levels_merge_kernel, dim3(grid_for(rec_hint + cov_hint, 256)), dim3(256), 0, c->stream,
                      (const X3RLevPair*)w.pairs, (const unsigned long long*)w.cov_off, n, P, cap, (const unsigned long long*)w.prow,
@@ -2608,25 +2613,27 @@ static int range_levels_launch(x3_ctx* c, const FrameSource& s, const uint32_t* 
   return X3_OK;
 }
 
-// the stream form of the range-levels calls behind the check of the signal or the taps (fir != NULL: the FIR call)
+// the stream form of the range-levels calls behind the check of the signal, the taps (fir != NULL: the FIR call) or the
+// oscillator (tone != NULL: the tone call)
 static int stream_range_levels_call(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
                                     const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
                                     const uint64_t* d_seg_index, uint32_t seg_blocks, const uint64_t* d_starts,
                                     const uint32_t* d_lens, uint64_t n_ranges, uint64_t bin_len, uint64_t row_stride,
                                     x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status, int signal,
-                                    const X3FirTaps* fir) {
+                                    const X3FirTaps* fir, const X3LevToneTail* tone = nullptr) {
   if (!range_levels_args_ok(c, d_starts, d_lens, n_ranges, row_stride, d_levels, rows_cap, d_row_offsets, d_status))
     return X3_ERR_BAD_ARG;
   FrameSource s;
   const int rc = stream_source(d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, p, d_seg_index, seg_blocks, &s);
   if (rc) return rc;
+  const X3RLevToneTail tt{tone ? tone->table : nullptr, tone ? tone->step : 0u, d_starts};
   return range_levels_launch(c, s, d_lens, n_ranges, bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status, signal,
                              nullptr, 0, nullptr,
                              [&](dim3 grid, X3WinPlan* plan, uint64_t*, X3WinSummary* sum) -> const uint64_t* {
                                hipLaunchKernelGGL(x3_range_plan_kernel, grid, dim3(256), 0, c->stream, d_sample_offsets, n_frames,
                                                   d_starts, d_lens, n_ranges, plan, sum);
                                return d_starts;
-                             }, fir);
+                             }, fir, tone ? &tt : nullptr);
 }
 
 extern "C" int x3_signal_range_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
@@ -2653,6 +2660,19 @@ extern "C" int x3_fir_range_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t 
                                   X3_LEVEL_SIGNAL_SAMPLES, &k);
 }
 
+extern "C" int x3_tone_range_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
+                                        const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
+                                        const uint64_t* d_seg_index, uint32_t seg_blocks, const uint64_t* d_starts,
+                                        const uint32_t* d_lens, uint64_t n_ranges, uint64_t bin_len, uint64_t row_stride,
+                                        x3_tone_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status,
+                                        const x3_level_tone* tone) {
+  X3LevToneTail t;
+  if (!c || !levels_tone_arg(tone, &t)) return X3_ERR_BAD_ARG;
+  return stream_range_levels_call(c, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, p, d_seg_index, seg_blocks, d_starts,
+                                  d_lens, n_ranges, bin_len, row_stride, reinterpret_cast<x3_level*>(d_levels), rows_cap,
+                                  d_row_offsets, d_status, X3_LEVEL_SIGNAL_SAMPLES, nullptr, &t);
+}
+
 extern "C" int x3_range_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
                                    const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
                                    const uint64_t* d_seg_index, uint32_t seg_blocks, const uint64_t* d_starts,
@@ -2667,13 +2687,15 @@ extern "C" int x3_range_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_l
 static int corpus_range_levels_call(x3_ctx* c, const x3_corpus* k, const char* entry, const uint32_t* d_entries,
                                     const uint64_t* d_starts, const uint32_t* d_lens, uint64_t n_ranges, uint64_t bin_len,
                                     uint64_t row_stride, x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets,
-                                    int32_t* d_status, int signal, const X3FirTaps* fir = nullptr) {
+                                    int32_t* d_status, int signal, const X3FirTaps* fir = nullptr,
+                                    const X3LevToneTail* tone = nullptr) {
   if (!c || !levels_signal_ok(signal) || !k || !d_entries || (reinterpret_cast<uintptr_t>(d_entries) & 3u)) return X3_ERR_BAD_ARG;
   if (!range_levels_args_ok(c, d_starts, d_lens, n_ranges, row_stride, d_levels, rows_cap, d_row_offsets, d_status))
     return X3_ERR_BAD_ARG;
   FrameSource s;
   const int rc = corpus_source(c, k, entry, &s);
   if (rc) return rc;
+  const X3RLevToneTail tt{tone ? tone->table : nullptr, tone ? tone->step : 0u, d_starts};   // (entry-relative: the caller's)
   return range_levels_launch(c, s, d_lens, n_ranges, bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status, signal,
                              (const x3_corpus_entry*)k->d_ent, k->n, d_entries,
                              [&](dim3 grid, X3WinPlan* plan, uint64_t* gstart, X3WinSummary* sum) -> const uint64_t* {
@@ -2681,7 +2703,7 @@ static int corpus_range_levels_call(x3_ctx* c, const x3_corpus* k, const char* e
                                                   s.d_sample_offsets, s.F, d_entries, d_starts, d_lens, n_ranges, plan, gstart,
                                                   sum);
                                return gstart;
-                             }, fir);
+                             }, fir, tone ? &tt : nullptr);
 }
 
 extern "C" int x3_corpus_range_levels_dev(x3_ctx* c, const x3_corpus* k, const uint32_t* d_entries, const uint64_t* d_starts,
@@ -2707,6 +2729,17 @@ extern "C" int x3_corpus_fir_range_levels_dev(x3_ctx* c, const x3_corpus* k, con
   if (!c || !levels_fir_taps(fir, &taps)) return X3_ERR_BAD_ARG;
   return corpus_range_levels_call(c, k, "x3_corpus_fir_range_levels_dev", d_entries, d_starts, d_lens, n_ranges, bin_len, row_stride,
                                   d_levels, rows_cap, d_row_offsets, d_status, X3_LEVEL_SIGNAL_SAMPLES, &taps);
+}
+
+extern "C" int x3_corpus_tone_range_levels_dev(x3_ctx* c, const x3_corpus* k, const uint32_t* d_entries, const uint64_t* d_starts,
+                                               const uint32_t* d_lens, uint64_t n_ranges, uint64_t bin_len, uint64_t row_stride,
+                                               x3_tone_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets,
+                                               int32_t* d_status, const x3_level_tone* tone) {
+  X3LevToneTail t;
+  if (!c || !levels_tone_arg(tone, &t)) return X3_ERR_BAD_ARG;
+  return corpus_range_levels_call(c, k, "x3_corpus_tone_range_levels_dev", d_entries, d_starts, d_lens, n_ranges, bin_len, row_stride,
+                                  reinterpret_cast<x3_level*>(d_levels), rows_cap, d_row_offsets, d_status, X3_LEVEL_SIGNAL_SAMPLES,
+                                  nullptr, &t);
 }
 
 extern "C" int x3_range_levels_result(x3_ctx* c, uint64_t* n_bad, uint64_t* first_bad, int* first_bad_status,

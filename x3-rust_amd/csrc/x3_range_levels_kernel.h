@@ -35,6 +35,9 @@
 //  x3_range_levels_fir_lead_kernel  -- behind the plan: up to T - 1 frames in front of a range that starts early in its frame
 //  x3_range_levels_fir_fixup_kernel -- x3_range_levels_fixup_kernel with the last seven samples carried from frame to frame
 //  x3_range_levels_fir_seam_kernel  -- behind the merge: a lane per (pair, stretch), the stretch's first T - 1 positions
+// x3_tone_range_levels_dev / x3_corpus_tone_range_levels_dev run the fourth instance of both templates,
+// X3RLevTone: X3LevTone with the phase seeded from the position in the STREAM OR ENTRY, not in the range (TONE RANGE LEVELS,
+// in front of the accumulate kernel); no kernel of its own.
 //
 // CAPACITY.  The workspace holds P pairs and cap = rows_cap + P partial rows, both sized on the host.  A pair with q >= P or
 // whose rows end behind cap has no rows: accumulate and merge skip it (x3rl_no_rows, recomputed from q and the scan) and the
@@ -159,11 +162,29 @@ x3_range_levels_init_kernel(const unsigned long long* __restrict__ cov_off, uint
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < used; i += (uint64_t)gridDim.x * blockDim.x) rows[i] = id;
 }
 
+// ---- TONE RANGE LEVELS (x3_tone_range_levels_dev / x3_corpus_tone_range_levels_dev)
+// The call cuts the stream's or entry's tone signal: bins are counted from the range, the phase from the entry.  Sample lo of
+// pair (w, f) is position starts[w] + r0 of its stream or entry -- `starts` the CALLER'S array, entry-relative in the corpus
+// form too, where the kernels otherwise see the plan's stream positions -- so sample s of the frame is position
+// starts[w] + r0 - lo + s, whatever the range holds of it.  An accumulate lane seeds with its first sample's position and
+// x3l_bin_samples lets skip() step the phase over the samples outside [lo, hi); the fix-up seeds with sample 0's.  All of it
+// is arithmetic mod 2^64, then mod 2^32, on untrusted words: a wrong start changes sums, never an address (ph >> 22 < 1 024).
+struct X3RLevToneTail {   // the kernels' last argument
+  const uint32_t* table;    // the caller's d_table: X3L_TONE_TABLE words
+  uint32_t step;
+  const uint64_t* starts;   // the caller's d_starts: n words
+};
+struct X3RLevTone : X3LevTone {
+  using Tail = X3RLevToneTail;
+};
+
 // ---- accumulate: a lane per (pair, stretch) into the pair's own rows.  Signal: X3LevSamples; X3RLevFir, whose lanes add the
 // positions whose T samples they decoded themselves, inside or in front of [lo, hi), and leave the edge record of their
 // (frame, stretch) -- several pairs of one frame write the same values; or X3LevDiff, whose lanes take
 // the stretch's seed from x3w_stretch, see the samples outside [lo, hi) without counting them (the sample in front of lo is
-// sample lo's `prev`), and whose lane at the frame's end stores the frame's last sample to tail[f].  A pair with an empty cut
+// sample lo's `prev`), and whose lane at the frame's end stores the frame's last sample to tail[f]; or X3RLevTone, whose
+// workgroups copy the table to LDS first (every lane, in front of the item loop) and whose lanes seed the phase with the
+// entry-relative position of their first sample.  A pair with an empty cut
 // (a lead frame) runs its stretches for the proof and the tail and touches no row: cnt is 0.
 template <class Signal>
 __global__ void __launch_bounds__(256)
@@ -177,6 +198,8 @@ x3_range_levels_accum_kernel(const uint8_t* __restrict__ x3, uint64_t len, const
   const uint64_t bl = x3l_bin_len(bin_len);
   const uint64_t n_items = min((uint64_t)cov_off[n], P) * ns;
   const uint64_t lanes = (uint64_t)gridDim.x * blockDim.x;
+  [[maybe_unused]] const uint32_t* tone_tab = nullptr;
+  if constexpr (Signal::kTone) tone_tab = x3l_tone_table(tail.table);
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_items; i += lanes) {
     const uint64_t q = i / ns;
     const uint32_t j = (uint32_t)(i - q * ns);
@@ -195,6 +218,11 @@ x3_range_levels_accum_kernel(const uint8_t* __restrict__ x3, uint64_t len, const
     if constexpr (Signal::kFir) {
       sig.k = tail.k;
       sig.edge = tail.edges + (pr.f * tail.stride + j);   // (pr.f < F, j < ns <= stride: below F * stride)
+    }
+    if constexpr (Signal::kTone) {
+      sig.tab = tone_tab;
+      sig.step = tail.step;
+      sig.seed(tail.starts[pr.w] + pr.r0 - lo + s0);   // (pr.w < n: the prep kernel's owner of q)
     }
     const int r = x3l_bin_samples<Signal>(
         (uint64_t)pr.r0 + (s0 > lo ? s0 - lo : 0u), bl,
@@ -215,6 +243,7 @@ x3_range_levels_accum_kernel(const uint8_t* __restrict__ x3, uint64_t len, const
 // X3LevDiff: the wave carries the frame in front -- its final status, its last sample, whether its pair went the fast way
 // (x3rl_fast) -- and adds the seams x3_range_levels_seam_kernel leaves; a lead frame (lead[w]: the plan's first frame lies in
 // front of the range) never gives the range its status; tail[f] of every frame it replays to status 0.
+// X3RLevTone: the replay into the records seeds the phase with the position of the frame's sample 0 and reads the caller's table.
 __device__ __forceinline__ bool x3rl_fast(int32_t word, const unsigned long long* __restrict__ prow, uint64_t q, uint64_t P, uint64_t cap) {
   return word == X3D_OK && !x3rl_no_rows(prow, q, P, cap);
 }
@@ -266,6 +295,11 @@ x3_range_levels_fixup_kernel(const uint8_t* __restrict__ x3, const uint64_t* __r
             };
             const uint32_t span = hi - lo;
             [[maybe_unused]] Signal sig;
+            if constexpr (Signal::kTone) {
+              sig.tab = tail.table;
+              sig.step = tail.step;
+              sig.seed(tail.starts[w] + r0 - lo);
+            }
             (void)x3l_bin_samples<Signal>(
                 r0, bl, [&](auto put_at) { return x3w_replay_frame(payload, p, blk, put_at); },
                 [&](uint32_t s) { return s - lo < span; }, flush, &sig);
@@ -455,7 +489,7 @@ __device__ __forceinline__ int32_t x3rl_fir_value(const X3FirTaps& k, int32_t s,
 // is the caller's to keep from frame to frame, and cnt is how many of the samples in d[] are valid.
 template <bool kEdge>
 struct X3RLevFirT {
-  static constexpr bool kDiff = false, kFir = true, kState = true;
+  static constexpr bool kDiff = false, kFir = true, kState = true, kTone = false;
   using Tail = X3LevFirTail;
   X3FirTaps k;   // (uniform: the kernel's argument)
   X3FirEdge* edge = nullptr;

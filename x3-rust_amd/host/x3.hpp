@@ -969,6 +969,28 @@ inline X3Error fir_range_levels(Context& ctx, const EncodedStream& s, const Para
   if (res) *res = r;
   return static_cast<X3Error>(rc);
 }
+// Tone range levels (x3_tone_range_levels_dev): range_levels with tone records, the stream's tone signal (device::tone_levels)
+// cut to the ranges -- the call cuts the stream's signal, it does not restart the oscillator: position i of the stream has the
+// phase (i * step) mod 2^32 wherever the range begins, so compare band power (tone_power_levels), not raw sums, across
+// ranges; statuses are the Samples form's.  A Tone without a table is BadArg.  Packed or padded, the records go through
+// tone_power_levels unchanged.
+inline X3Error tone_range_levels(Context& ctx, const EncodedStream& s, const Parameters& params, const Buffer& d_sample_offsets,
+                                 const uint64_t* d_starts, const uint32_t* d_lens, size_t n_ranges, uint64_t bin_len,
+                                 uint64_t row_stride, x3_tone_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets,
+                                 int32_t* d_status, const Tone& tone, RangeLevelsResult* res) {
+  if (!s.bytes.ok() || !s.frame_offsets.ok() || !d_sample_offsets.ok()) return X3Error::BadArg;
+  const x3_params c = params.c_params();
+  const x3_level_tone t = tone.c_tone();
+  int rc = x3_tone_range_levels_dev(ctx.raw(), s.bytes.as<uint8_t>(), s.len, s.frame_offsets.as<uint64_t>(),
+                                    d_sample_offsets.as<uint64_t>(), s.n_frames, &c,
+                                    s.seg_blocks ? s.seg_index.as<uint64_t>() : nullptr, s.seg_blocks, d_starts, d_lens, n_ranges,
+                                    bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status, &t);
+  if (rc != X3_OK) return static_cast<X3Error>(rc);
+  RangeLevelsResult r;
+  rc = x3_range_levels_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status, &r.total_rows);
+  if (res) *res = r;
+  return static_cast<X3Error>(rc);
+}
 
 // A batch of independent streams (x3_decode_streams_dev): entry s = bytes [offsets[s], offsets[s] + lengths[s]) of d_x3 (flags:
 // X3_STREAMS_ARCHIVE_FRAMES for the frame parts of .x3a archives), decoded into row s of d_out (offsets.size() rows of row_len
@@ -1157,6 +1179,20 @@ class Corpus {
     const x3_level_fir f = fir.c_fir();
     int rc = x3_corpus_fir_range_levels_dev(ctx.raw(), raw_, d_entries, d_starts, d_lens, n_ranges, bin_len, row_stride, d_levels,
                                             rows_cap, d_row_offsets, d_status, &f);
+    if (rc != X3_OK) return static_cast<X3Error>(rc);
+    RangeLevelsResult r;
+    rc = x3_range_levels_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status, &r.total_rows);
+    if (res) *res = r;
+    return static_cast<X3Error>(rc);
+  }
+  // Tone range levels of entries (x3_corpus_tone_range_levels_dev): as device::tone_range_levels; starts count from the
+  // entry's first position and so does the phase, 0 there.  Waits for the call.
+  X3Error tone_range_levels(Context& ctx, const uint32_t* d_entries, const uint64_t* d_starts, const uint32_t* d_lens,
+                            uint64_t n_ranges, uint64_t bin_len, uint64_t row_stride, x3_tone_level* d_levels, uint64_t rows_cap,
+                            uint64_t* d_row_offsets, int32_t* d_status, const Tone& tone, RangeLevelsResult* res) const {
+    const x3_level_tone t = tone.c_tone();
+    int rc = x3_corpus_tone_range_levels_dev(ctx.raw(), raw_, d_entries, d_starts, d_lens, n_ranges, bin_len, row_stride, d_levels,
+                                             rows_cap, d_row_offsets, d_status, &t);
     if (rc != X3_OK) return static_cast<X3Error>(rc);
     RangeLevelsResult r;
     rc = x3_range_levels_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status, &r.total_rows);

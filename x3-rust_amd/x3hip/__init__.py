@@ -70,6 +70,7 @@ SYMBOLS = [
     "x3_range_levels_dev", "x3_corpus_range_levels_dev", "x3_range_levels_result",
     "x3_signal_range_levels_dev", "x3_corpus_signal_range_levels_dev",
     "x3_fir_range_levels_dev", "x3_corpus_fir_range_levels_dev",
+    "x3_tone_range_levels_dev", "x3_corpus_tone_range_levels_dev",
     "x3_tune_candidate", "x3_tuner_create", "x3_tuner_add_dev", "x3_tuner_result", "x3_tuner_max_payloads",
     "x3_tuner_reset", "x3_tuner_destroy", "x3_tune", "x3_x3a_encode_tuned",
 ]
@@ -178,14 +179,15 @@ class Tone:
 
 def level_signal(signal, fir=True):
     """the keyword `signal` of the levels methods ("samples" | "diff", or a LEVEL_SIGNAL_* value) -> the C ABI's int; a
-    Fir is handed through (fir=False: to the range-levels keyword, which takes no Fir and raises; fir_range_levels does)"""
+    Fir or a Tone is handed through (fir=False: to the range-levels keyword, which takes neither and raises;
+    fir_range_levels and tone_range_levels do)"""
     if isinstance(signal, Fir):
         if not fir:
             raise ValueError("signal: range levels of a Fir signal are not built yet on this keyword: call fir_range_levels")
         return signal
     if isinstance(signal, Tone):
         if not fir:
-            raise ValueError("signal: range levels of a Tone signal are not built yet (levels, events, level_quantiles and adaptive_events take one)")
+            raise ValueError("signal: range levels of a Tone signal are not built yet on this keyword: call tone_range_levels")
         return signal
     if signal in LEVEL_SIGNALS:
         return LEVEL_SIGNALS[signal]
@@ -426,6 +428,9 @@ def lib():
     L.x3_fir_range_levels_dev.argtypes = [vp, vp, u64, vp, vp, u64, PP, vp, u32, vp, vp, u64, u64, u64, vp, u64, vp, vp,
                                           C.POINTER(LevelFir)]
     L.x3_corpus_fir_range_levels_dev.argtypes = [vp, vp, vp, vp, vp, u64, u64, u64, vp, u64, vp, vp, C.POINTER(LevelFir)]
+    L.x3_tone_range_levels_dev.argtypes = [vp, vp, u64, vp, vp, u64, PP, vp, u32, vp, vp, u64, u64, u64, vp, u64, vp, vp,
+                                           C.POINTER(LevelTone)]
+    L.x3_corpus_tone_range_levels_dev.argtypes = [vp, vp, vp, vp, vp, u64, u64, u64, vp, u64, vp, vp, C.POINTER(LevelTone)]
     L.x3_range_levels_result.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(i32), C.POINTER(u64)]
     L.x3_corpus_destroy.restype = None
     L.x3_synth.argtypes = [i32, u64, u64, u64, vp]
@@ -1329,6 +1334,23 @@ class Context:
         return lib().x3_corpus_fir_range_levels_dev(self._h, corpus._h, d_entries, d_starts, d_lens, n_ranges, bin_len,
                                                     row_stride, d_levels, rows_cap, d_row_offsets, d_status, self._fir_arg(fir))
 
+    def tone_range_levels_dev(self, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, params, d_starts, d_lens,
+                              n_ranges, bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status, d_seg_index=None,
+                              seg_blocks=0, tone=None):
+        """x3_tone_range_levels_dev: range_levels_dev with x3_tone_level records (TONE_DTYPE), the stream's tone signal
+        (tone: a Tone, or a LevelTone as it is) cut to the ranges -- the phase is the stream's, not the range's;
+        asynchronous, range_levels_result waits"""
+        return lib().x3_tone_range_levels_dev(self._h, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames,
+                                              C.byref(params), d_seg_index, seg_blocks, d_starts, d_lens, n_ranges, bin_len,
+                                              row_stride, d_levels, rows_cap, d_row_offsets, d_status, self._tone_arg(tone))
+
+    def corpus_tone_range_levels_dev(self, corpus, d_entries, d_starts, d_lens, n_ranges, bin_len, row_stride, d_levels,
+                                     rows_cap, d_row_offsets, d_status, tone=None):
+        """x3_corpus_tone_range_levels_dev: corpus_range_levels_dev with tone records, the phase 0 at every entry's first
+        position; asynchronous"""
+        return lib().x3_corpus_tone_range_levels_dev(self._h, corpus._h, d_entries, d_starts, d_lens, n_ranges, bin_len,
+                                                     row_stride, d_levels, rows_cap, d_row_offsets, d_status, self._tone_arg(tone))
+
     def range_levels_result(self):
         """-> (rc, n_bad, first_bad, first_bad_status, total_rows) of the last range_levels_dev / corpus_range_levels_dev"""
         nb, fb, st, tot = C.c_uint64(0), C.c_uint64(0), C.c_int32(0), C.c_uint64(0)
@@ -1462,10 +1484,13 @@ def _ranges_torch(ctx, enqueue, what, starts, lens, padded_to, capacity, dtype, 
     return out[:cap] if padded_to is None else out, offsets, status
 
 
-def _range_levels_torch(ctx, enqueue, what, starts, lens, bin_len, padded_to, capacity, entries=None):
+def _range_levels_torch(ctx, enqueue, what, starts, lens, bin_len, padded_to, capacity, entries=None, band=False):
     """The torch side of WindowSource.range_levels / Corpus.range_levels: device tensors in, (levels uint8 [rows, 32],
     row_offsets int64 [n + 1], status int32 [n]) device tensors out (levels: see event_levels_view).
-    enqueue(d_entries, d_starts, d_lens, n, bin_len, stride, d_levels, cap, d_off, d_status) -> rc."""
+    enqueue(d_entries, d_starts, d_lens, n, bin_len, stride, d_levels, cap, d_off, d_status) -> rc.
+    band (the tone calls): the records tensor is allocated zeroed and x3_tone_power_levels_dev runs in place over all of it
+    behind the call -- a zero record has n == 0, which the adapter turns into the identity, so the records of ranges
+    without room are defined too."""
     import torch
     dev = torch.device("cuda", torch.cuda.current_device())
     bin_len = int(bin_len)
@@ -1504,7 +1529,7 @@ def _range_levels_torch(ctx, enqueue, what, starts, lens, bin_len, padded_to, ca
         else:   # (the one host trip: the sum of max(1, ceil(len / bin_len)))
             ln = lens.to(torch.int64) & 0xFFFFFFFF
             cap = int(torch.clamp((ln + (bin_len - 1)) // bin_len, min=1).sum().item())
-    levels = torch.empty((max(cap, 1), LEVEL_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    levels = (torch.zeros if band else torch.empty)((max(cap, 1), LEVEL_DTYPE.itemsize), dtype=torch.uint8, device=dev)
     offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
     status = torch.empty(n, dtype=torch.int32, device=dev)
     torch.cuda.current_stream().synchronize()    # (the context's stream is not torch's: the inputs are ready from here)
@@ -1512,9 +1537,15 @@ def _range_levels_torch(ctx, enqueue, what, starts, lens, bin_len, padded_to, ca
                  status.data_ptr())
     if rc:
         raise X3Error(rc, what + ": " + ctx.last_error())
+    if band and cap > 0:   # (behind the call on the context's stream, in front of the wait)
+        rc = ctx.tone_power_levels_dev(levels.data_ptr(), cap, levels.data_ptr())
+        if rc:
+            raise X3Error(rc, "x3_tone_power_levels_dev: " + ctx.last_error())
     rc = ctx.range_levels_result()[0]
     if rc:
         raise X3Error(rc, "x3_range_levels_result: " + ctx.last_error())
+    if band:
+        ctx.sync()
     return levels[:cap], offsets, status
 
 
@@ -1712,9 +1743,10 @@ class WindowSource:
                           signal=LEVEL_SIGNAL_SAMPLES):
         """enqueue the level records of n ranges (device pointers: d_starts n x u64, d_lens n x u32, d_levels rows_cap x
         x3_level, d_row_offsets (n + 1) x u64 or None when padded, d_status n x i32); row_stride 0: packed; signal: a
-        LEVEL_SIGNAL_* value (a Fir raises, "not built yet" on this keyword: fir_range_levels_into takes it); -> rc;
+        LEVEL_SIGNAL_* value (a Fir or a Tone raises, "not built yet" on this keyword: fir_range_levels_into and
+        tone_range_levels_into take them); -> rc;
         Context.range_levels_result waits"""
-        if isinstance(signal, Fir):
+        if isinstance(signal, (Fir, Tone)):
             level_signal(signal, fir=False)
         return self.ctx.signal_range_levels_dev(self.d_x3, self.x3_len, self.d_frame_offsets, self.d_sample_offsets,
                                                 self.n_frames, self.params, d_starts, d_lens, n, bin_len, row_stride, d_levels,
@@ -1749,6 +1781,26 @@ class WindowSource:
             raise ValueError("fir: a Fir")
         return _range_levels_torch(self.ctx, lambda e, *a: self.fir_range_levels_into(*a, fir), "x3_fir_range_levels_dev",
                                    starts, lens, bin_len, padded_to, capacity)
+
+    def tone_range_levels_into(self, d_starts, d_lens, n, bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status, tone):
+        """range_levels_into on the stream's tone signal, records x3_tone_level (tone: a Tone or a LevelTone;
+        x3_tone_range_levels_dev); -> rc; Context.range_levels_result waits"""
+        return self.ctx.tone_range_levels_dev(self.d_x3, self.x3_len, self.d_frame_offsets, self.d_sample_offsets, self.n_frames,
+                                              self.params, d_starts, d_lens, n, bin_len, row_stride, d_levels, rows_cap,
+                                              d_row_offsets, d_status, self.d_seg_index, self.seg_blocks, tone)
+
+    def tone_range_levels(self, starts, lens, bin_len, tone, *, padded_to=None, capacity=None, band=False):
+        """range_levels of the stream's tone signal (tone_levels()) cut to the ranges -> (levels, row_offsets, status) as
+        range_levels, the records x3_tone_level (TONE_DTYPE: re, im, min, max, n).  The call cuts the stream's signal, it
+        does not restart the oscillator: position i of the stream has the phase (i * step) mod 2^32 wherever the range
+        begins, so equal samples at different starts give different re and im -- compare band power across ranges, not
+        the raw sums.  band=True: x3_tone_power_levels_dev in place behind the call, the records are x3_level records of the
+        band's level (LEVEL_DTYPE) and go into events and quantiles; those of ranges without room are the identity.
+        tone: a Tone; the tensors events(signal=tone) returns go in as they are (x3_tone_range_levels_dev)"""
+        if not isinstance(tone, Tone):
+            raise ValueError("tone: a Tone")
+        return _range_levels_torch(self.ctx, lambda e, *a: self.tone_range_levels_into(*a, tone), "x3_tone_range_levels_dev",
+                                   starts, lens, bin_len, padded_to, capacity, band=band)
 
     def levels_into(self, bin_len, d_levels, n_bins, d_frame_status=None, signal=LEVEL_SIGNAL_SAMPLES):
         """enqueue x3_signal_levels_dev over this source (device pointers; signal: a LEVEL_SIGNAL_* value), or
@@ -2107,7 +2159,7 @@ class Corpus:
         WindowSource.range_levels_into); -> rc; Context.range_levels_result waits"""
         if self._h is None:
             raise ValueError("the corpus is closed")
-        if isinstance(signal, Fir):
+        if isinstance(signal, (Fir, Tone)):
             level_signal(signal, fir=False)   # (raises: "not built yet" on this keyword; fir_range_levels_into takes a Fir)
         return self.ctx.corpus_signal_range_levels_dev(self, d_entries, d_starts, d_lens, n, bin_len, row_stride, d_levels,
                                                        rows_cap, d_row_offsets, d_status, signal)
@@ -2135,6 +2187,22 @@ class Corpus:
             raise ValueError("fir: a Fir")
         return _range_levels_torch(self.ctx, lambda *a: self.fir_range_levels_into(*a, fir), "x3_corpus_fir_range_levels_dev",
                                    starts, lens, bin_len, padded_to, capacity, entries=entries)
+
+    def tone_range_levels_into(self, d_entries, d_starts, d_lens, n, bin_len, row_stride, d_levels, rows_cap, d_row_offsets,
+                               d_status, tone):
+        """range_levels_into on each entry's tone signal, records x3_tone_level (tone: a Tone or a LevelTone;
+        x3_corpus_tone_range_levels_dev); -> rc"""
+        if self._h is None:
+            raise ValueError("the corpus is closed")
+        return self.ctx.corpus_tone_range_levels_dev(self, d_entries, d_starts, d_lens, n, bin_len, row_stride, d_levels,
+                                                     rows_cap, d_row_offsets, d_status, tone)
+
+    def tone_range_levels(self, entries, starts, lens, bin_len, tone, *, padded_to=None, capacity=None, band=False):
+        """WindowSource.tone_range_levels for ranges of entries; the phase is 0 at every entry's first position"""
+        if not isinstance(tone, Tone):
+            raise ValueError("tone: a Tone")
+        return _range_levels_torch(self.ctx, lambda *a: self.tone_range_levels_into(*a, tone), "x3_corpus_tone_range_levels_dev",
+                                   starts, lens, bin_len, padded_to, capacity, entries=entries, band=band)
 
     def levels_rows(self, bin_len):
         """-> row_first np.uint64 [n_entries + 1]: entry e's rows of levels() are [row_first[e], row_first[e + 1])"""
