@@ -910,6 +910,38 @@ int x3_corpus_tone_levels_dev(x3_ctx* ctx, const x3_corpus* corpus, uint64_t bin
  * x3_corpus_tone_range_levels_dev, packed or padded, go through this call unchanged: n_rows of them, whatever range they
  * belong to; a padded layout's rows behind a range's last are empty records (n == 0) and come out as the identity. */
 int x3_tone_power_levels_dev(x3_ctx* ctx, const x3_tone_level* d_tone, uint64_t n_rows, x3_level* d_levels);
+/* ---- TONE BANK LEVELS: up to X3_TONE_BANK_MAX oscillators against ONE table in ONE pass over the stream -- a band spectrum
+ * per bin (third-octave levels, a pinger at one of several frequencies) for one decode instead of one per band (DESIGN.md
+ * section 26).  `bank` is a host struct, copied at the call; d_table is x3_level_tone's, read when the kernels run.
+ *   ONE RULE: the bank is n_tones tone calls laid PLANE BY PLANE.  d_levels holds n_tones * n_bins records (n_tones * n_rows
+ * for a corpus); plane t is the n_bins records at d_levels + t * n_bins, byte for byte what x3_tone_levels_dev /
+ * x3_corpus_tone_levels_dev writes for {steps[t], 0, d_table} with the same other arguments: re, im, the samples' min, max
+ * and n, reserved 0.  In a corpus every entry starts at phase 0 in every plane, and the rows of an entry are those of the
+ * single call (x3_corpus_levels_rows) in every plane.  So every plane goes as it lies into x3_events_dev, the quantile and
+ * threshold calls and their corpus forms, and ALL planes go through x3_tone_power_levels_dev in one launch of
+ * n_tones * n_bins rows.  Equal steps in two slots are legal and give equal planes.  n_tones == 1 IS the single call.
+ *   d_frame_status, x3_levels_result, the pending slot, "last_levels_replays", "every record is written", a failed frame
+ * adding nothing (to no plane), the segment index as a hint only and the asynchronous contract are the single call's; the
+ * statuses never depend on the bank.  X3_ERR_BAD_ARG with nothing enqueued, checked before every other argument: a NULL
+ * bank, n_tones 0 or above X3_TONE_BANK_MAX, reserved != 0, a NULL or misaligned (4 bytes) d_table.  Also refused:
+ * n_tones * n_bins > 2^31 - 1, and everything the single call refuses.  The workspace holds n_tones planes of partial rows.
+ *   COST (one MI355X): a bank of 2 / 4 / 8 tones takes 1.13 x / 1.38 x / 1.87 x the single call's time
+ * where as many single calls take 2 x / 4 x / 8 x.  A call with 3 or 5 .. 7 tones runs the kernel of 4 or 8 and costs what
+ * that costs.  X3_TONE_BANK_MAX is 8 because the 8-tone kernel, at 4 waves per SIMD, still measured 1.5 x FASTER than two
+ * calls of 4; the call does not split wide banks. */
+#define X3_TONE_BANK_MAX 8
+typedef struct x3_level_tone_bank {
+  uint32_t n_tones;                  /* 1 .. X3_TONE_BANK_MAX */
+  uint32_t reserved;                 /* 0 */
+  const int16_t* d_table;            /* device: x3_level_tone's table, ONE for all tones */
+  uint32_t steps[X3_TONE_BANK_MAX];  /* steps[t], t < n_tones; the rest is never read */
+} x3_level_tone_bank;
+int x3_tone_bank_levels_dev(x3_ctx* ctx, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
+                            const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
+                            const uint64_t* d_seg_index, uint32_t seg_blocks, uint64_t bin_len,
+                            x3_tone_level* d_levels, uint64_t n_bins, int32_t* d_frame_status, const x3_level_tone_bank* bank);
+int x3_corpus_tone_bank_levels_dev(x3_ctx* ctx, const x3_corpus* corpus, uint64_t bin_len, x3_tone_level* d_levels,
+                                   uint64_t n_rows, int32_t* d_frame_status, const x3_level_tone_bank* bank);
 /* ---- EVENTS (no counterpart in the reference): runs of loud bins of level records as ranges (entry, start, len), found on
  * the device -- the link between the levels calls and the ranges calls, with no host trip.
  *   Row b of d_levels is a bin of bin_len positions as x3_levels_dev / x3_corpus_levels_dev write it.  A bin is HOT when

@@ -32,7 +32,11 @@ Families: (e) the single-pass encoders on block_len 20 with mixed content, many 
           (not in the default family set); (p) family (r) against a random Tone (x3_tone_range_levels_dev): a random step
           and the usual table or a random one, with starts drawn to frame and stretch boundaries +- 1 (the phase seeds of
           lanes and fix-up), as a stream and as a corpus of random entries (x3_corpus_tone_range_levels_dev: the phase is 0
-          at every entry), GPU == tests/tone_range_levels_ref.py (not in the default family set)."""
+          at every entry), GPU == tests/tone_range_levels_ref.py (not in the default family set); (q) family (h) against a
+          random tone bank (x3_tone_bank_levels_dev / x3_corpus_tone_bank_levels_dev): 1 .. 8 drawn steps, equal ones among
+          them, the usual table or a random one, garbage in the struct's spare steps; every plane GPU ==
+          tests/tone_bank_levels_ref.py and == the single call's bytes, the adapter over all planes at once, then the same
+          frames as a corpus (not in the default family set)."""
 import argparse, ctypes as C, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "x3-rust_amd"))
@@ -1064,7 +1068,7 @@ def draw_fir(rng):
     return x3hip.Fir([int(c) for c in taps], int(rng.choice([0, 0, 1, 7, 15, int(rng.integers(0, 16))])))
 
 
-def fam_h(rng, tag, fir=False, tone=False):
+def fam_h(rng, tag, fir=False, tone=False, bank=False):
     """signal levels: the DIFF records and frame statuses of a random stream -- any geometry, damaged frames, a damaged or
     walk-built index or none -- against diff_levels_ref on the oracle's frame verdicts; then the same frames as a corpus of
     random entries, where no difference may cross from one entry into the next; SAMPLES against x3_levels_dev byte for byte"""
@@ -1101,6 +1105,31 @@ def fam_h(rng, tag, fir=False, tone=False):
                                                            lambda d_lv, n_, d_st: src.tone_levels_into(bl, level_tone(tab), d_lv, n_, d_st))
         corpus_levels = lambda corpus, bl: corpus._levels_np("x3_corpus_tone_levels_dev", bl, x3hip.TONE_DTYPE,
                                                              lambda d_lv, n_, d_st: corpus.tone_levels_into(bl, level_tone(tab), d_lv, n_, d_st))
+    if bank:   # family (q): the planes of a drawn tone bank and table, against tone_bank_levels_ref
+        import tone_bank_levels_ref as TB
+        import tone_levels_ref as TR
+        n_tones = int(rng.integers(1, 9))
+        steps = [int(rng.choice([0, 1 << 30, 1 << 31, (1 << 32) - 1, int(rng.integers(0, 1 << 32)), int(rng.integers(0, 1 << 32)) | 1]))
+                 for _ in range(n_tones)]
+        if n_tones > 1 and rng.random() < 0.3:
+            steps[-1] = steps[0]   # equal steps, equal planes
+        tab = None if rng.random() < 0.5 else rng.integers(-32768, 32768, (1024, 2)).astype(np.int16)
+
+        def level_bank():   # an x3_level_tone_bank of a table in device memory (freed behind the trial); spare steps: garbage
+            d_tab = ctx.tone_table_dev()
+            if tab is not None:
+                tone_tabs.append(ctx.alloc(4096))
+                ctx.upload(tone_tabs[-1], tab)
+                d_tab = tone_tabs[-1]
+            return x3hip.LevelToneBank(n_tones, 0, d_tab, (C.c_uint32 * 8)(*(steps + [0xDEADBEEF] * (8 - n_tones))))
+        ref_stream = lambda fr, st, so_, bl, nb: TB.tone_bank_levels(fr, st, so_, bl, nb, steps, tab)
+        ref_corpus = lambda ref, bl: TB.corpus_tone_bank_levels(ref, bl, steps, tab)
+        stream_levels = lambda src, bl, nb: src._levels_np(
+            "x3_tone_bank_levels_dev", bl, nb, x3hip.TONE_DTYPE,
+            lambda d_lv, n_, d_st: src.tone_bank_levels_into(bl, level_bank(), d_lv, n_, d_st), planes=n_tones)
+        corpus_levels = lambda corpus, bl: corpus._levels_np(
+            "x3_corpus_tone_bank_levels_dev", bl, x3hip.TONE_DTYPE,
+            lambda d_lv, n_, d_st: corpus.tone_bank_levels_into(bl, level_bank(), d_lv, n_, d_st), planes=n_tones)
     r = rng.random()
     if r < 0.5:
         p = x3hip.Params.default()
@@ -1186,7 +1215,17 @@ def fam_h(rng, tag, fir=False, tone=False):
         for k in want.dtype.names:
             assert np.array_equal(got[k], want[k]), (tag, "stream", k, bin_len, n_bins, np.flatnonzero(got[k] != want[k])[:8].tolist())
         old, _ = src.levels(bin_len, n_bins)
-        if tone:   # a table of all (1, 0): the sums of the levels call; the adapter on the usual table's records
+        if bank:   # every plane is the single call's bytes; the adapter over all planes at once on the usual table's records
+            for t, step in enumerate(steps):
+                one, _ = src._levels_np("x3_tone_levels_dev", bin_len, n_bins, x3hip.TONE_DTYPE,
+                                        lambda d_lv, n_, d_st: src.tone_levels_into(
+                                            bin_len, x3hip.LevelTone(step, 0, tone_tabs[-1] if tab is not None else ctx.tone_table_dev()),
+                                            d_lv, n_, d_st))
+                assert one.tobytes() == got[t].tobytes(), (tag, "plane is not the single call", t)
+            if tab is None:
+                band, _ = src.tone_bank_levels(bin_len, [x3hip.Tone(v) for v in steps], n_bins, band=True)
+                assert all(band[t].tobytes() == TR.tone_power_levels(want[t]).tobytes() for t in range(n_tones)), (tag, "adapter")
+        elif tone:   # a table of all (1, 0): the sums of the levels call; the adapter on the usual table's records
             same, _ = src._levels_np("x3_tone_levels_dev", bin_len, n_bins, x3hip.TONE_DTYPE,
                                      lambda d_lv, n_, d_st: src.tone_levels_into(bin_len, level_tone(ones), d_lv, n_, d_st))
             assert np.array_equal(same["re"], old["sum"]) and not same["im"].any(), (tag, "ones")
@@ -1229,6 +1268,7 @@ fams["o"] = lambda rng, tag: fam_h(rng, tag, tone=True)
 fams["i"] = lambda rng, tag: fam_h(rng, tag, fir=True)
 fams["t"] = lambda rng, tag: fam_r(rng, tag, fir=draw_fir(rng))
 fams["p"] = lambda rng, tag: fam_r(rng, tag, tone=True)
+fams["q"] = lambda rng, tag: fam_h(rng, tag, bank=True)
 
 
 def run(seed=1, minutes=None, trials=None, families="egdbaf", only=-1, context=None):

@@ -12,9 +12,16 @@ Cases: config3_20_<bin> -- the stream kbench.py makes (691.2 M hydrophone sample
 index), bin_len 1920 and 0; corpus_a_0 -- 4 000 clips of 10-15 s at 44.1 kHz, one record per clip.  The records of the tone
 call and of decode_torch are compared with == (every field).  Device memory of both sides goes into the line.  Kernel times:
 run it with --no-torch under `rocprofv3 --kernel-trace --stats -- python3 tools/tone_levels_bench.py --no-torch ...`.
+--tones K (2 .. 8): the tone bank call (x3_tone_bank_levels_dev / x3_corpus_tone_bank_levels_dev) on
+the same cases instead, K oscillators at BANK_FREQS[:K]:
+  bank            one bank call of K tones
+  singles         K single-tone calls of the same build, one per plane
+  tone            one single-tone call (the first tone)
+  decode_torch    decode into a sample buffer once, then the torch reduction above once per tone
+The planes of `bank` are compared with == against `singles` (bytes) and against decode_torch (every field, every plane).
 Prints one JSON line.   (X3HIP_LIB=/path/to/variant.so to measure another build)
     python3 tools/tone_levels_bench.py [--samples N] [--clips N] [--reps 10] [--warmup 2] [--cases config3,corpus] [--no-torch]
-                                       [--out file.json]"""
+                                       [--tones K] [--out file.json]"""
 import argparse, ctypes as C, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "x3-rust_amd"))
@@ -27,10 +34,11 @@ if os.environ.get("X3HIP_LIB"):
 now = time.perf_counter
 TONE = x3hip.Tone.at(0.0817, 1.0)
 FIR3 = x3hip.Fir([1, -2, 1])
+BANK_FREQS = (0.0817, 0.2310, 0.15, 0.41, 0.02, 0.33, 0.275, 0.4999)   # --tones K: the first K, in units of fs
 CHUNK = 1 << 25   # positions per pass of the flat case: a few int64 temporaries of 256 MB each
 
 
-def tone_flat(x, bin_len, tab):
+def tone_flat(x, bin_len, tab, step=TONE.step):
     """x: int16 [n] -> (re, im, min, max, n) per bin of bin_len positions (whole bins) or over everything"""
     n = x.numel()
     if bin_len:
@@ -41,7 +49,7 @@ def tone_flat(x, bin_len, tab):
         for r0 in range(0, rows, per):
             r1 = min(rows, r0 + per)
             pos = torch.arange(r0 * bin_len, r1 * bin_len, dtype=torch.int64, device=x.device)
-            k = ((pos * TONE.step) & 0xFFFFFFFF) >> 22
+            k = ((pos * step) & 0xFFFFFFFF) >> 22
             v = x[r0 * bin_len:r1 * bin_len]
             v64 = v.to(torch.int64)
             re[r0:r1] = (v64 * tab[k, 0]).view(-1, bin_len).sum(1)
@@ -53,7 +61,7 @@ def tone_flat(x, bin_len, tab):
         for a in range(0, n, CHUNK):
             b = min(n, a + CHUNK)
             pos = torch.arange(a, b, dtype=torch.int64, device=x.device)
-            k = ((pos * TONE.step) & 0xFFFFFFFF) >> 22
+            k = ((pos * step) & 0xFFFFFFFF) >> 22
             v64 = x[a:b].to(torch.int64)
             re += (v64 * tab[k, 0]).sum()
             im += (v64 * tab[k, 1]).sum()
@@ -92,7 +100,58 @@ def config3(ctx, a, results, mem, checks):
     del wav
     tab = torch.from_numpy(x3hip.tone_table().astype(np.int64)).cuda()
     src = (out.data_ptr(), pos, off.data_ptr(), so.data_ptr(), F, p)
-    for bin_len in (1920, 0):
+    for bin_len in (1920, 0) if a.tones else ():
+        n_bins = -(-n // bin_len) if bin_len else 1
+        K, tones = a.tones, x3hip.Tone.bank(BANK_FREQS[:a.tones], 1.0)
+        lv = {k: torch.empty(4 * K * n_bins, dtype=torch.int64, device="cuda") for k in ("bank", "singles")}
+        one = torch.empty(4 * n_bins, dtype=torch.int64, device="cuda")
+        name = "config3_20_%d" % bin_len
+        peak, red = 0, None
+        for rep in range(a.warmup + a.reps):
+            t = {}
+
+            def bank():
+                assert ctx.tone_bank_levels_dev(*src, bin_len, lv["bank"].data_ptr(), n_bins, None, idx.data_ptr(), 32, tones) == 0
+                r = ctx.levels_result()
+                assert r[:2] == (0, 0) and ctx.get_option("last_levels_replays") == 0, r
+
+            def singles():
+                for k, tone in enumerate(tones):
+                    assert ctx.tone_levels_dev(*src, bin_len, lv["singles"].data_ptr() + 32 * n_bins * k, n_bins, None, idx.data_ptr(), 32, tone) == 0
+                    r = ctx.levels_result()
+                    assert r[:2] == (0, 0), r
+
+            def tone():
+                assert ctx.tone_levels_dev(*src, bin_len, one.data_ptr(), n_bins, None, idx.data_ptr(), 32, tones[0]) == 0
+                r = ctx.levels_result()
+                assert r[:2] == (0, 0), r
+            sides = [("bank", bank), ("singles", singles), ("tone", tone)]
+            for side, fn in (sides if rep % 2 == 0 else sides[::-1]):      # (the sides alternate rep by rep)
+                t0 = now()
+                fn()
+                t[side] = now() - t0
+            if not a.no_torch:
+                red = None
+                torch.cuda.reset_peak_memory_stats()
+                base = torch.cuda.memory_allocated()
+                t0 = now()
+                assert ctx.decode_dev_seg(out.data_ptr(), pos, off.data_ptr(), F, p, back.data_ptr(), n, idx.data_ptr(), 32, n_per_clip=n) == 0
+                assert ctx.decode_result()[0] == 0
+                red = [tone_flat(back, bin_len, tab, tn.step) for tn in tones]
+                t["decode_torch"] = now() - t0
+                peak = max(peak, torch.cuda.max_memory_allocated() - base)
+            if rep >= a.warmup:
+                for side, v in t.items():
+                    results.setdefault(name + "_" + side, []).append(v * 1e3)
+        checks[name + "_bank_is_singles"] = bool(torch.equal(lv["bank"], lv["singles"]))
+        if red is not None:
+            rec = lv["bank"].cpu().numpy().view(x3hip.TONE_DTYPE).reshape(K, n_bins)
+            checks[name + "_bank"] = all(equal(rec[k], red[k], n // bin_len if bin_len else 1) for k in range(K))
+        mem[name] = {"bank_workspace_bytes": 32 * K * (n_bins + F) + 48 * F, "bank_records_bytes": 32 * K * n_bins,
+                     "single_workspace_bytes": 32 * (n_bins + F) + 48 * F, "tone_table_bytes": 4096,
+                     "decode_torch_bytes": 2 * n + int(peak), "stream_bytes": int(pos), "frames": int(F)}
+        del lv, red, one
+    for bin_len in () if a.tones else (1920, 0):
         n_bins = -(-n // bin_len) if bin_len else 1
         lv = {k: torch.empty(4 * n_bins, dtype=torch.int64, device="cuda") for k in ("samples", "fir3", "tone", "tone_power")}
         name = "config3_20_%d" % bin_len
@@ -173,6 +232,8 @@ def corpus_a(ctx, a, results, mem, checks):
     corpus = x3hip.Corpus(ctx, (d_x3, pos), offs, lens, seg_blocks=32)
     n_rows = int(corpus.levels_rows(0)[-1])
     lv = {k: torch.empty(4 * n_rows, dtype=torch.int64, device="cuda") for k in ("samples", "fir3", "tone", "tone_power")}
+    if a.tones:
+        return corpus_bank(ctx, a, results, mem, checks, corpus, ns, p, d_x3, pos, offs, lens, F)
     row_len = (max(ns) + 3) // 4 * 4
     rows = torch.empty(n_clips * row_len, dtype=torch.int16, device="cuda")
     res = torch.empty(24 * n_clips, dtype=torch.uint8, device="cuda")
@@ -237,6 +298,82 @@ def corpus_a(ctx, a, results, mem, checks):
     corpus.close()
 
 
+def corpus_bank(ctx, a, results, mem, checks, corpus, ns, p, d_x3, pos, offs, lens, F):
+    """--tones K on corpus_a's corpus: one record per clip and tone"""
+    n_clips, total = len(ns), int(sum(ns))
+    n_rows = int(corpus.levels_rows(0)[-1])
+    K, tones = a.tones, x3hip.Tone.bank(BANK_FREQS[:a.tones], 1.0)
+    lv = {k: torch.empty(4 * K * n_rows, dtype=torch.int64, device="cuda") for k in ("bank", "singles")}
+    one = torch.empty(4 * n_rows, dtype=torch.int64, device="cuda")
+    row_len = (max(ns) + 3) // 4 * 4
+    rows = torch.empty(n_clips * row_len, dtype=torch.int16, device="cuda")
+    res = torch.empty(24 * n_clips, dtype=torch.uint8, device="cuda")
+    t_ns = torch.tensor(ns, device="cuda").view(-1, 1)
+    tab = torch.from_numpy(x3hip.tone_table().astype(np.int64)).cuda()
+    col = torch.arange(row_len, dtype=torch.int64, device="cuda")
+
+    def reduce(step):
+        k = ((col * step) & 0xFFFFFFFF) >> 22              # (every clip starts at phase 0)
+        wc, wsn = tab[k, 0].view(1, -1), tab[k, 1].view(1, -1)
+        parts = []
+        for c0 in range(0, n_clips, 100):          # (100 clips: 0.5 GB of int64 per temporary)
+            x = rows.view(n_clips, row_len)[c0:c0 + 100]
+            inside = col.view(1, -1) < t_ns[c0:c0 + 100]
+            v = torch.where(inside, x.to(torch.int64), torch.zeros((), dtype=torch.int64, device="cuda"))
+            mn = torch.where(inside, x, torch.full_like(x, 32767)).min(1).values
+            mx = torch.where(inside, x, torch.full_like(x, -32768)).max(1).values
+            parts.append(((v * wc).sum(1), (v * wsn).sum(1), mn, mx))
+            del x, v, inside
+        return tuple(torch.cat([q[j] for q in parts]) for j in range(4)) + (torch.tensor(ns, dtype=torch.int64),)
+    peak, red = 0, None
+    for rep in range(a.warmup + a.reps):
+        t = {}
+
+        def bank():
+            assert ctx.corpus_tone_bank_levels_dev(corpus, 0, lv["bank"].data_ptr(), n_rows, None, tones) == 0
+            r = ctx.levels_result()
+            assert r[:2] == (0, 0), r
+
+        def singles():
+            for k, tone in enumerate(tones):
+                assert ctx.corpus_tone_levels_dev(corpus, 0, lv["singles"].data_ptr() + 32 * n_rows * k, n_rows, None, tone) == 0
+                r = ctx.levels_result()
+                assert r[:2] == (0, 0), r
+
+        def tone():
+            assert ctx.corpus_tone_levels_dev(corpus, 0, one.data_ptr(), n_rows, None, tones[0]) == 0
+            r = ctx.levels_result()
+            assert r[:2] == (0, 0), r
+        sides = [("bank", bank), ("singles", singles), ("tone", tone)]
+        for side, fn in (sides if rep % 2 == 0 else sides[::-1]):
+            t0 = now()
+            fn()
+            t[side] = now() - t0
+        if not a.no_torch:
+            red = None
+            torch.cuda.reset_peak_memory_stats()
+            base_mem = torch.cuda.memory_allocated()
+            t0 = now()
+            assert ctx.decode_streams_dev(d_x3, pos, offs, lens, p, rows.data_ptr(), row_len, 0, res.data_ptr()) == 0
+            assert ctx.decode_streams_result()[0] == 0
+            red = [reduce(tn.step) for tn in tones]
+            torch.cuda.synchronize()
+            t["decode_torch"] = now() - t0
+            peak = max(peak, torch.cuda.max_memory_allocated() - base_mem)
+        if rep >= a.warmup:
+            for side, v in t.items():
+                results.setdefault("corpus_a_0_" + side, []).append(v * 1e3)
+    checks["corpus_a_0_bank_is_singles"] = bool(torch.equal(lv["bank"], lv["singles"]))
+    if red is not None:
+        rec = lv["bank"].cpu().numpy().view(x3hip.TONE_DTYPE).reshape(K, n_rows)
+        checks["corpus_a_0_bank"] = all(equal(rec[k], red[k], n_rows) for k in range(K))
+    mem["corpus_a_0"] = {"bank_workspace_bytes": 32 * K * (n_rows + F) + 48 * F + 8 * (n_clips + 1), "bank_records_bytes": 32 * K * n_rows,
+                         "single_workspace_bytes": 32 * (n_rows + F) + 48 * F + 8 * (n_clips + 1), "tone_table_bytes": 4096,
+                         "decode_torch_bytes": 2 * n_clips * row_len + int(peak), "stream_bytes": int(pos), "frames": int(F),
+                         "clips": n_clips, "samples": total}
+    corpus.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--samples", type=int, default=691_200_000)
@@ -245,6 +382,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--cases", default="config3,corpus")
     ap.add_argument("--no-torch", action="store_true")
+    ap.add_argument("--tones", type=int, default=0, choices=[0, 2, 3, 4, 5, 6, 7, 8])
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     torch.cuda.init()
@@ -255,7 +393,7 @@ def main():
     if "corpus" in a.cases:
         corpus_a(ctx, a, results, mem, checks)
     out = {"samples": a.samples, "clips": a.clips, "reps": a.reps, "tone_equal_to_torch": checks, "memory": mem,
-           "step": TONE.step, "library": os.path.basename(os.path.dirname(os.environ["X3HIP_LIB"])) if os.environ.get("X3HIP_LIB") else "tree",
+           "step": TONE.step, "tones": a.tones, "steps": [t.step for t in x3hip.Tone.bank(BANK_FREQS[:a.tones], 1.0)], "library": os.path.basename(os.path.dirname(os.environ["X3HIP_LIB"])) if os.environ.get("X3HIP_LIB") else "tree",
            "ms_median": {k: round(float(np.median(v)), 4) for k, v in results.items()},
            "ms_min": {k: round(float(np.min(v)), 4) for k, v in results.items()},
            "ms_max": {k: round(float(np.max(v)), 4) for k, v in results.items()}}

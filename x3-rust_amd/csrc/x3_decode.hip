@@ -1303,13 +1303,14 @@ uint64_t levels_fix_waves(uint64_t F, uint32_t scratch_per) {
   return std::max<uint64_t>(1, std::min<uint64_t>({(F + 3) / 4 * 4, 4096, (32ull << 20) / (2ull * scratch_per) / 4 * 4}));
 }
 
-size_t levels_carve(char* base, uint64_t F, uint64_t n_rows, uint64_t fix_waves, uint32_t scratch_per, uint64_t n_ent, LevWs* w) {
+size_t levels_carve(char* base, uint64_t F, uint64_t n_rows, uint64_t fix_waves, uint32_t scratch_per, uint64_t n_ent, LevWs* w,
+                    uint64_t planes) {
   BlockCarver k{base, 0};
   w->fst = k.take<int32_t>(F);
   w->frames = k.take<X3LevFrame>(F);
   w->cnt = k.take<uint32_t>(F);
   w->row = k.take<unsigned long long>(F + 1);
-  w->rows = k.take<x3_level>(n_rows + F);
+  w->rows = k.take<x3_level>(planes * (n_rows + F));   // (a tone bank: a plane of n_rows + F rows per tone)
   w->scratch = k.take<int16_t>(std::max<uint64_t>(fix_waves, 4) * scratch_per);
   w->sum = k.take<X3LevSummary>(1);
   w->row_first = k.take<unsigned long long>(n_ent + 1, 1);
@@ -1325,41 +1326,51 @@ size_t levels_carve(char* base, uint64_t F, uint64_t n_rows, uint64_t fix_waves,
 // in a workspace of its own (fir_ws; lev_ws keeps its layout), and x3_levels_fir_seam_kernel behind the merge.
 // tone (checked: levels_tone_arg) instead of either: the X3LevTone instance, whose records hold re and im in x3_level's first
 // two slots; no workspace of its own and no kernel behind the merge.
+// bank (checked: levels_tone_bank_arg, two tones or more) instead of any: the X3LevToneBank<NT> instances.  d_levels and the
+// partial rows hold bank->n_tones PLANES of n_rows and n_rows + F records; the accumulate instance is the smallest of NT = 2,
+// 4, 8 that holds the tones, the fix-up's is NT = 8, and the merge kernel runs once per plane.
 template <class Prep>
 static int levels_launch(x3_ctx* c, const FrameSource& s, uint64_t bin_len, x3_level* d_levels, uint64_t n_rows,
                          int32_t* d_frame_status, uint64_t n_ent, int signal, Prep prep, const X3FirTaps* fir = nullptr,
-                         const X3LevToneTail* tone = nullptr) {
-  const bool diff = !fir && !tone && signal == X3_LEVEL_SIGNAL_DIFF;
+                         const X3LevToneTail* tone = nullptr, const X3LevToneBankTail* bank = nullptr) {
+  const bool diff = !fir && !tone && !bank && signal == X3_LEVEL_SIGNAL_DIFF;
   HIPCHK(c, hipSetDevice(c->device));
-  const uint64_t F = s.F, cap = n_rows + F;
+  const uint64_t F = s.F, cap = n_rows + F, planes = bank ? bank->n_tones : 1;
   const uint32_t scratch_per = levels_scratch_per(s.dp.block_len);
   const uint64_t fix_waves = levels_fix_waves(F, scratch_per);
   LevWs w;
   int rc;
-  if ((rc = ensure(c, c->lev_ws, levels_carve(nullptr, F, n_rows, fix_waves, scratch_per, n_ent, &w)))) return rc;
-  levels_carve((char*)c->lev_ws.p, F, n_rows, fix_waves, scratch_per, n_ent, &w);
+  if ((rc = ensure(c, c->lev_ws, levels_carve(nullptr, F, n_rows, fix_waves, scratch_per, n_ent, &w, planes)))) return rc;
+  levels_carve((char*)c->lev_ws.p, F, n_rows, fix_waves, scratch_per, n_ent, &w, planes);
   if (fir && (rc = ensure(c, c->fir_ws, (size_t)(F * s.nseg) * sizeof(X3FirEdge)))) return rc;
-  hipLaunchKernelGGL(x3_levels_init_kernel, dim3(grid_for(n_rows + cap, 256)), dim3(256), 0, c->stream, d_levels, n_rows, w.rows,
-                     cap, w.sum);
+  hipLaunchKernelGGL(x3_levels_init_kernel, dim3(grid_for(planes * (n_rows + cap), 256)), dim3(256), 0, c->stream, d_levels,
+                     planes * n_rows, w.rows, planes * cap, w.sum);
   hipLaunchKernelGGL(x3_levels_check_kernel, dim3(grid_for(F, 4)), dim3(256), 0, c->stream, s.d_x3, s.x3_len, s.d_frame_offsets,
                      s.d_sample_offsets, F, w.fst);
   prep(dim3(grid_for(F, 256)), w.row_first, (const int32_t*)w.fst, w.frames, w.cnt);
   hipLaunchKernelGGL(x3_levels_scan_kernel, dim3(1), dim3(1024), 0, c->stream, (const uint32_t*)w.cnt, F, cap, w.row, w.fst);
-  auto decode = [&](auto sig, auto tail) {   // the two kernels that decode, for a signal
-    using Signal = decltype(sig);
-    hipLaunchKernelGGL(x3_levels_accum_kernel<Signal>, dim3(grid_for(F * s.nseg, 256)), dim3(256), 0, c->stream, s.d_x3, s.x3_len,
+  auto decode = [&](auto sig, auto fix, auto tail) {   // the two kernels that decode, for a signal
+    hipLaunchKernelGGL(x3_levels_accum_kernel<decltype(sig)>, dim3(grid_for(F * s.nseg, 256)), dim3(256), 0, c->stream, s.d_x3, s.x3_len,
                        s.d_frame_offsets, F, s.dp, s.idx, s.seg_blocks, s.nseg, bin_len, (const X3LevFrame*)w.frames,
                        (const unsigned long long*)w.row, w.rows, w.fst, tail);
-    hipLaunchKernelGGL(x3_levels_fixup_kernel<Signal>, dim3((unsigned)((fix_waves + 3) / 4)), dim3(256), 0, c->stream, s.d_x3,
+    hipLaunchKernelGGL(x3_levels_fixup_kernel<decltype(fix)>, dim3((unsigned)((fix_waves + 3) / 4)), dim3(256), 0, c->stream, s.d_x3,
                        s.d_frame_offsets, F, s.dp, bin_len, (const X3LevFrame*)w.frames, w.fst, d_levels, d_frame_status,
                        w.scratch, scratch_per, w.sum, tail);
   };
-  if (tone) decode(X3LevTone{}, *tone);
-  else if (fir) decode(X3LevFir{}, X3LevFirTail{*fir, (X3FirEdge*)c->fir_ws.p, s.nseg});
-  else if (diff) decode(X3LevDiff{}, w.tail);
-  else decode(X3LevSamples{}, X3LevNoTail{});
-  hipLaunchKernelGGL(x3_levels_merge_kernel, dim3(grid_for(cap, 256)), dim3(256), 0, c->stream, (const X3LevFrame*)w.frames,
-                     (const unsigned long long*)w.row, F, cap, (const x3_level*)w.rows, (const int32_t*)w.fst, d_levels);
+  if (bank) {
+    X3LevToneBankTail t = *bank;
+    t.rows_stride = cap, t.levels_stride = n_rows;
+    if (t.n_tones <= 2) decode(X3LevToneBank<2>{}, X3LevToneBank<X3L_TONE_BANK>{}, t);
+    else if (t.n_tones <= 4) decode(X3LevToneBank<4>{}, X3LevToneBank<X3L_TONE_BANK>{}, t);
+    else decode(X3LevToneBank<X3L_TONE_BANK>{}, X3LevToneBank<X3L_TONE_BANK>{}, t);
+  } else if (tone) decode(X3LevTone{}, X3LevTone{}, *tone);
+  else if (fir) decode(X3LevFir{}, X3LevFir{}, X3LevFirTail{*fir, (X3FirEdge*)c->fir_ws.p, s.nseg});
+  else if (diff) decode(X3LevDiff{}, X3LevDiff{}, w.tail);
+  else decode(X3LevSamples{}, X3LevSamples{}, X3LevNoTail{});
+  for (uint64_t t = 0; t < planes; ++t)   // (a plane's rows and records: the same frames, row scan and verdicts)
+    hipLaunchKernelGGL(x3_levels_merge_kernel, dim3(grid_for(cap, 256)), dim3(256), 0, c->stream, (const X3LevFrame*)w.frames,
+                       (const unsigned long long*)w.row, F, cap, (const x3_level*)w.rows + t * cap, (const int32_t*)w.fst,
+                       d_levels + t * n_rows);
   if (diff && F > 1)
     hipLaunchKernelGGL(x3_levels_seam_kernel, dim3(grid_for(F, 256)), dim3(256), 0, c->stream, s.d_x3, s.x3_len, s.d_frame_offsets,
                        F, bin_len, (const X3LevFrame*)w.frames, (const int32_t*)w.fst, (const int32_t*)w.tail, d_levels);
@@ -1395,6 +1406,25 @@ static bool levels_tone_arg(const x3_level_tone* tone, X3LevToneTail* t) {
   t->step = tone->step;
   return true;
 }
+
+// x3_level_tone_bank as the kernels take it, the steps at and behind n_tones zero; false: NULL, n_tones not 1 .. 8,
+// reserved != 0, a NULL or misaligned table.  One tone is the single call's tail (*one).
+static bool levels_tone_bank_arg(const x3_level_tone_bank* bank, X3LevToneBankTail* t, X3LevToneTail* one) {
+  if (!bank || bank->n_tones < 1 || bank->n_tones > X3_TONE_BANK_MAX || bank->reserved != 0 || !bank->d_table ||
+      (reinterpret_cast<uintptr_t>(bank->d_table) & 3u) != 0)
+    return false;
+  t->table = one->table = reinterpret_cast<const uint32_t*>(bank->d_table);
+  t->n_tones = bank->n_tones;
+  for (uint32_t i = 0; i < X3L_TONE_BANK; ++i) t->steps[i] = i < bank->n_tones ? bank->steps[i] : 0;
+  t->rows_stride = t->levels_stride = 0;   // (levels_launch's)
+  one->step = bank->steps[0];
+  return true;
+}
+static_assert(X3_TONE_BANK_MAX == X3L_TONE_BANK, "the header's bank is the kernels'");
+// all planes of a bank in one launch of the adapter: n_tones * n_rows <= 2^31 - 1 (n_rows itself: levels_args_ok)
+static bool levels_planes_ok(const X3LevToneBankTail* bank, uint64_t n_rows) {
+  return !bank || n_rows <= 0x7FFFFFFFull / bank->n_tones;
+}
 static_assert(sizeof(x3_tone_level) == sizeof(x3_level) && alignof(x3_tone_level) == alignof(x3_level) &&
                   offsetof(x3_tone_level, re) == offsetof(x3_level, sum_sq) && offsetof(x3_tone_level, im) == offsetof(x3_level, sum) &&
                   offsetof(x3_tone_level, min) == offsetof(x3_level, min) && offsetof(x3_tone_level, max) == offsetof(x3_level, max) &&
@@ -1406,8 +1436,9 @@ static_assert(sizeof(x3_tone_level) == sizeof(x3_level) && alignof(x3_tone_level
 static int stream_levels_call(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
                               const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p, const uint64_t* d_seg_index,
                               uint32_t seg_blocks, uint64_t bin_len, x3_level* d_levels, uint64_t n_bins, int32_t* d_frame_status,
-                              int signal, const X3FirTaps* fir, const X3LevToneTail* tone = nullptr) {
-  if (!levels_args_ok(c, d_levels, n_bins, d_frame_status)) return X3_ERR_BAD_ARG;
+                              int signal, const X3FirTaps* fir, const X3LevToneTail* tone = nullptr,
+                              const X3LevToneBankTail* bank = nullptr) {
+  if (!levels_args_ok(c, d_levels, n_bins, d_frame_status) || !levels_planes_ok(bank, n_bins)) return X3_ERR_BAD_ARG;
   FrameSource s;
   const int rc = stream_source(d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, p, d_seg_index, seg_blocks, &s);
   if (rc) return rc;
@@ -1415,7 +1446,7 @@ static int stream_levels_call(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, c
                        [&](dim3 grid, unsigned long long*, const int32_t* fst, X3LevFrame* frames, uint32_t* cnt) {
                          hipLaunchKernelGGL(x3_levels_prep_kernel, grid, dim3(256), 0, c->stream, d_sample_offsets, n_frames,
                                             bin_len, n_bins, fst, frames, cnt);
-                       }, fir, tone);
+                       }, fir, tone, bank);
 }
 
 extern "C" int x3_signal_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
@@ -1445,6 +1476,20 @@ extern "C" int x3_tone_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_le
   if (!c || !levels_tone_arg(tone, &t)) return X3_ERR_BAD_ARG;
   return stream_levels_call(c, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, p, d_seg_index, seg_blocks, bin_len,
                             reinterpret_cast<x3_level*>(d_levels), n_bins, d_frame_status, X3_LEVEL_SIGNAL_SAMPLES, nullptr, &t);
+}
+
+// the bank: n_tones tone calls plane by plane in one pass; one tone IS the tone call
+extern "C" int x3_tone_bank_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
+                                       const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
+                                       const uint64_t* d_seg_index, uint32_t seg_blocks, uint64_t bin_len, x3_tone_level* d_levels,
+                                       uint64_t n_bins, int32_t* d_frame_status, const x3_level_tone_bank* bank) {
+  X3LevToneBankTail t;
+  X3LevToneTail one;
+  if (!c || !levels_tone_bank_arg(bank, &t, &one)) return X3_ERR_BAD_ARG;
+  const bool single = t.n_tones == 1;
+  return stream_levels_call(c, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, p, d_seg_index, seg_blocks, bin_len,
+                            reinterpret_cast<x3_level*>(d_levels), n_bins, d_frame_status, X3_LEVEL_SIGNAL_SAMPLES, nullptr,
+                            single ? &one : nullptr, single ? nullptr : &t);
 }
 
 // the adapter: tone records -> the level records of the band (x3_tone_power_kernel); in place, or rows that do not overlap
@@ -2133,8 +2178,9 @@ static void corpus_row_prefix(x3_ctx* c, const x3_corpus* k, uint64_t bin_len, u
 
 static int corpus_levels_call(x3_ctx* c, const x3_corpus* k, const char* entry, uint64_t bin_len, x3_level* d_levels,
                               uint64_t n_rows, int32_t* d_frame_status, int signal, const X3FirTaps* fir = nullptr,
-                              const X3LevToneTail* tone = nullptr) {
-  if (!c || !k || !levels_signal_ok(signal) || !levels_args_ok(c, d_levels, n_rows, d_frame_status)) return X3_ERR_BAD_ARG;
+                              const X3LevToneTail* tone = nullptr, const X3LevToneBankTail* bank = nullptr) {
+  if (!c || !k || !levels_signal_ok(signal) || !levels_args_ok(c, d_levels, n_rows, d_frame_status) || !levels_planes_ok(bank, n_rows))
+    return X3_ERR_BAD_ARG;
   FrameSource s;
   X3EvRows q;
   int rc;
@@ -2146,7 +2192,7 @@ static int corpus_levels_call(x3_ctx* c, const x3_corpus* k, const char* entry, 
                          hipLaunchKernelGGL(x3_corpus_levels_prep_kernel, grid, dim3(256), 0, c->stream,
                                             k->d_ent, k->n, (const unsigned long long*)row_first,
                                             s.d_sample_offsets, s.F, bin_len, n_rows, fst, frames, cnt);
-                       }, fir, tone);
+                       }, fir, tone, bank);
 }
 
 extern "C" int x3_corpus_levels_dev(x3_ctx* c, const x3_corpus* k, uint64_t bin_len, x3_level* d_levels, uint64_t n_rows,
@@ -2173,6 +2219,16 @@ extern "C" int x3_corpus_tone_levels_dev(x3_ctx* c, const x3_corpus* k, uint64_t
   if (!c || !levels_tone_arg(tone, &t)) return X3_ERR_BAD_ARG;
   return corpus_levels_call(c, k, "x3_corpus_tone_levels_dev", bin_len, reinterpret_cast<x3_level*>(d_levels), n_rows,
                             d_frame_status, X3_LEVEL_SIGNAL_SAMPLES, nullptr, &t);
+}
+
+extern "C" int x3_corpus_tone_bank_levels_dev(x3_ctx* c, const x3_corpus* k, uint64_t bin_len, x3_tone_level* d_levels,
+                                              uint64_t n_rows, int32_t* d_frame_status, const x3_level_tone_bank* bank) {
+  X3LevToneBankTail t;
+  X3LevToneTail one;
+  if (!c || !levels_tone_bank_arg(bank, &t, &one)) return X3_ERR_BAD_ARG;
+  const bool single = t.n_tones == 1;
+  return corpus_levels_call(c, k, "x3_corpus_tone_bank_levels_dev", bin_len, reinterpret_cast<x3_level*>(d_levels), n_rows,
+                            d_frame_status, X3_LEVEL_SIGNAL_SAMPLES, nullptr, single ? &one : nullptr, single ? nullptr : &t);
 }
 
 // ------------------------------------------------------------------------------------------------

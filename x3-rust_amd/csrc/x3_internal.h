@@ -460,7 +460,8 @@ struct WinWs {
 X3_INTERNAL uint32_t windows_scratch_per(uint32_t block_len);
 X3_INTERNAL size_t windows_carve(char* base, uint64_t n, uint64_t F, uint32_t scratch_per, bool ranges, WinWs* w);
 // ... and of a levels call (lev_ws; x3_levels_kernel.h): F frames, n_rows records of the caller's (the partial rows are
-// n_rows + F), `fix_waves` waves of the fix-up with `scratch_per` samples each, the row prefix of n_ent corpus entries
+// n_rows + F), `fix_waves` waves of the fix-up with `scratch_per` samples each, the row prefix of n_ent corpus entries;
+// `planes` planes of partial rows (a tone bank's: one per tone; one plane is every other call's layout)
 struct X3LevFrame;
 struct X3LevSummary;
 struct LevWs {
@@ -472,7 +473,7 @@ struct LevWs {
 X3_INTERNAL uint32_t levels_scratch_per(uint32_t block_len);
 X3_INTERNAL uint64_t levels_fix_waves(uint64_t F, uint32_t scratch_per);
 X3_INTERNAL size_t levels_carve(char* base, uint64_t F, uint64_t n_rows, uint64_t fix_waves, uint32_t scratch_per, uint64_t n_ent,
-                                LevWs* w);
+                                LevWs* w, uint64_t planes = 1);
 // ... and of an events call (ev_ws; x3_events_kernel.h): n_rows records in tiles of X3_EVENTS_TILE_ROWS, the row prefix of
 // n_ent corpus entries.  A row starts at most one run: the run tables and the piece scan hold n_rows (+ 1) words.
 #define X3_EVENTS_TILE_ROWS 256

@@ -30,7 +30,8 @@
 //  x3_tone_power_kernel      -- x3_tone_power_levels_dev: a lane per tone record, the record of the band's level
 // The accumulate and fix-up kernels are templates over the SIGNAL, what a position adds to its bin: X3LevSamples (the levels
 // calls), X3LevDiff (x3_signal_levels_dev), X3LevFir (x3_fir_levels_dev) or
-// X3LevTone (x3_tone_levels_dev).
+// X3LevTone (x3_tone_levels_dev); X3LevToneBank<NT> (x3_tone_bank_levels_dev)
+// is NT of the last in one pass, whose records go to NT planes of the partial rows and of the caller's records.
 //
 // What the range levels, events and quantiles kernels (x3_range_levels_kernel.h, x3_events_kernel.h, x3_quantiles_kernel.h)
 // share with these: X3L_IDENTITY, the record of an empty bin; X3LevAcc, a record in registers (load, record, join);
@@ -158,16 +159,16 @@ struct X3LevBinner {
 // and is x3_levels_seam_kernel's.  seed(v): the sample in front of a stretch (x3w_stretch's watch).  Tail: the kernels'
 // last argument, the per-frame array of last samples that only X3LevDiff has.
 // kState: the signal has registers of its own and is the caller's, at x3l_bin_samples' `sig`; kFir: it is X3LevFir, kTone:
-// it is X3LevTone (both below).
+// it is X3LevTone, kBank: it is X3LevToneBank<NT> (all below).
 struct X3LevNoTail {};
 struct X3LevSamples {
-  static constexpr bool kDiff = false, kFir = false, kState = false, kTone = false;
+  static constexpr bool kDiff = false, kFir = false, kState = false, kTone = false, kBank = false;
   using Tail = X3LevNoTail;
   __device__ __forceinline__ void add(X3LevAcc& a, uint32_t v) { a.add(v); }
 };
 __device__ __forceinline__ int32_t x3l_diff(int32_t s, int32_t prev) { return min(max(s - prev, -32768), 32767); }
 struct X3LevDiff {
-  static constexpr bool kDiff = true, kFir = false, kState = true, kTone = false;
+  static constexpr bool kDiff = true, kFir = false, kState = true, kTone = false, kBank = false;
   using Tail = int32_t*;   // per frame: its last sample
   int32_t prev = 0;
   bool have = false;
@@ -227,7 +228,7 @@ __device__ __forceinline__ int32_t x3l_fir_value(const X3FirTaps& k, int32_t s, 
   return min(max(acc >> k.shift, -32768), 32767);
 }
 struct X3LevFir {
-  static constexpr bool kDiff = false, kFir = true, kState = true, kTone = false;
+  static constexpr bool kDiff = false, kFir = true, kState = true, kTone = false, kBank = false;
   using Tail = X3LevFirTail;
   X3FirTaps k;   // (uniform: the kernel's argument)
   X3FirEdge* edge = nullptr;
@@ -267,7 +268,7 @@ struct X3LevToneTail {   // the kernels' last argument
   uint32_t step;
 };
 struct X3LevTone {
-  static constexpr bool kDiff = false, kFir = false, kState = true, kTone = true;
+  static constexpr bool kDiff = false, kFir = false, kState = true, kTone = true, kBank = false;
   using Tail = X3LevToneTail;
   const uint32_t* tab = nullptr;
   uint32_t step = 0, ph = 0;
@@ -291,6 +292,77 @@ __device__ __forceinline__ const uint32_t* x3l_tone_table(const uint32_t* __rest
   __syncthreads();
   return s_tab;
 }
+
+// X3LevToneBank<NT> (x3_tone_bank_levels_dev): NT oscillators against the one table in one pass over
+// the stretch.  Slot t has a phase and a pair of int64 sums of its own, formed as X3LevTone forms its one pair; min, max and n
+// are the samples' and live once, in the binner's X3LevAcc, whose two sums stay 0.  NT is a compile-time count and every loop
+// over it is unrolled, so every slot index is a constant: registers, no scratch.  The steps are the tail's (uniform); a call with fewer
+// than NT tones has step 0 in its spare slots, which store() never writes.  A flush stores slot t < n_tones of the open bin
+// to the same record of PLANE t -- `r` is plane 0's record, the planes lie `stride` records apart -- through x3l_merge, and
+// clears the sums: one plane is X3LevTone's record byte for byte.
+#define X3L_TONE_BANK 8
+struct X3LevToneBankTail {   // the kernels' last argument
+  const uint32_t* table;   // the caller's d_table: X3L_TONE_TABLE words
+  uint32_t n_tones;        // 2 .. X3L_TONE_BANK planes are stored
+  uint32_t steps[X3L_TONE_BANK];
+  uint64_t rows_stride;    // plane stride of the partial rows (the accumulate kernel): n_rows + F
+  uint64_t levels_stride;  // plane stride of the caller's records (the fix-up kernel): n_rows
+};
+template <uint32_t NT>
+struct X3LevToneBank {
+  static_assert(NT >= 2 && NT <= X3L_TONE_BANK, "2 .. X3L_TONE_BANK slots");
+  static constexpr bool kDiff = false, kFir = false, kState = true, kTone = false, kBank = true;
+  using Tail = X3LevToneBankTail;
+  const uint32_t* tab = nullptr;
+  uint32_t step[NT], ph[NT];
+  uint64_t re[NT];
+  int64_t im[NT];
+  __device__ __forceinline__ void seed(const X3LevToneBankTail& tail, uint64_t g) {
+#pragma unroll
+    for (uint32_t t = 0; t < NT; ++t) {
+      step[t] = tail.steps[t];
+      ph[t] = (uint32_t)(g * (uint64_t)step[t]);
+      re[t] = 0;
+      im[t] = 0;
+    }
+  }
+  __device__ __forceinline__ void add(X3LevAcc& a, uint32_t v) {
+    const int32_t s = (int32_t)(int16_t)(uint16_t)v;
+#pragma unroll
+    for (uint32_t t = 0; t < NT; ++t) {
+      const uint32_t w = tab[ph[t] >> 22];
+      ph[t] += step[t];
+      re[t] += (uint64_t)(int64_t)(s * (int32_t)(int16_t)(uint16_t)w);
+      im[t] += (int64_t)(s * ((int32_t)w >> 16));
+    }
+    a.mn = min(a.mn, s);
+    a.mx = max(a.mx, s);
+    ++a.n;
+  }
+  __device__ __forceinline__ void skip(uint32_t) {
+#pragma unroll
+    for (uint32_t t = 0; t < NT; ++t) ph[t] += step[t];
+  }
+  // the open bin (a: its min, max, n) into record r of plane 0 .. n_tones - 1; t * stride < n_tones * stride: inside the planes
+  __device__ __forceinline__ void store(x3_level* __restrict__ r, uint64_t stride, uint32_t n_tones, const X3LevAcc& a) const {
+#pragma unroll
+    for (uint32_t t = 0; t < NT; ++t) {
+      if (t < n_tones) {
+        X3LevAcc b = a;
+        b.sum_sq = re[t];
+        b.sum = im[t];
+        x3l_merge(r + t * stride, b);
+      }
+    }
+  }
+  __device__ __forceinline__ void clear() {
+#pragma unroll
+    for (uint32_t t = 0; t < NT; ++t) {
+      re[t] = 0;
+      im[t] = 0;
+    }
+  }
+};
 
 // The bins of consecutive positions from g on: decode(put_at) hands sample s of a frame to put_at(s, value), in order;
 // the positions with keep(s) go to the signal, bins that fill go to flush, and so does the open one at the end; a position
@@ -432,7 +504,8 @@ x3_levels_scan_kernel(const uint32_t* __restrict__ cnt, uint64_t F, uint64_t cap
 
 // ---- accumulate: a lane per (frame, stretch) into the frame's own rows.  Signal: X3LevSamples, or X3LevDiff, whose lanes
 // take the stretch's seed from x3w_stretch and whose lane at the frame's end stores the frame's last sample to tail[f], or
-// X3LevTone, whose workgroups copy the table to LDS first and whose lanes seed the phase with their first position
+// X3LevTone, whose workgroups copy the table to LDS first and whose lanes seed the phase with their first position, or
+// X3LevToneBank<NT>, the same with NT phases
 template <class Signal>
 __global__ void __launch_bounds__(256)
 x3_levels_accum_kernel(const uint8_t* __restrict__ x3, uint64_t len, const uint64_t* __restrict__ frame_off, uint64_t F,
@@ -445,7 +518,7 @@ x3_levels_accum_kernel(const uint8_t* __restrict__ x3, uint64_t len, const uint6
   const uint64_t n_items = F * ns;
   const uint64_t lanes = (uint64_t)gridDim.x * blockDim.x;
   [[maybe_unused]] const uint32_t* tone_tab = nullptr;
-  if constexpr (Signal::kTone) tone_tab = x3l_tone_table(tail.table);
+  if constexpr (Signal::kTone || Signal::kBank) tone_tab = x3l_tone_table(tail.table);
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_items; i += lanes) {
     const uint64_t f = i / ns;
     const uint32_t j = (uint32_t)(i - f * ns);
@@ -457,7 +530,20 @@ x3_levels_accum_kernel(const uint8_t* __restrict__ x3, uint64_t len, const uint6
       if (bin < nlim) x3l_merge(mine + (bin - b0), a);
     };
     // a stretch's samples come in order, from sample 0 or from the first sample of block sb * j
-    if constexpr (Signal::kTone) {
+    if constexpr (Signal::kBank) {   // (plane t's partial rows: rows + t * rows_stride, the same row index in each)
+      const uint64_t g = fr.pos + (j ? 1u + (uint64_t)sb * j * p.block_len : 0u);
+      Signal sig;
+      sig.tab = tone_tab;
+      sig.seed(tail, g);
+      auto flush_bank = [&](uint64_t bin, const X3LevAcc& a) {
+        if (bin < nlim) sig.store(mine + (bin - b0), tail.rows_stride, tail.n_tones, a);
+        sig.clear();
+      };
+      const int r = x3l_bin_samples(
+          g, bl, [&](auto put_at) { return x3w_stretch(x3, len, frame_off[f], p, idx, segd, sb, nseg, f, j, put_at); },
+          X3LevKeepAll{}, flush_bank, &sig);
+      if (r < 0) atomicOr(&fst[f], X3W_FLAG);
+    } else if constexpr (Signal::kTone) {
       const uint64_t g = fr.pos + (j ? 1u + (uint64_t)sb * j * p.block_len : 0u);
       Signal sig;
       sig.tab = tone_tab;
@@ -516,7 +602,16 @@ x3_levels_fixup_kernel(const uint8_t* __restrict__ x3, const uint64_t* __restric
         auto flush = [&](uint64_t bin, const X3LevAcc& a) {
           if (bin < fr.nlim) x3l_merge(levels + fr.obase + bin, a);
         };
-        if constexpr (Signal::kTone) {
+        if constexpr (Signal::kBank) {   // (plane t's records: levels + t * levels_stride, the same record index in each)
+          Signal sig;
+          sig.tab = tail.table;
+          sig.seed(tail, fr.pos);
+          auto flush_bank = [&](uint64_t bin, const X3LevAcc& a) {
+            if (bin < fr.nlim) sig.store(levels + fr.obase + bin, tail.levels_stride, tail.n_tones, a);
+            sig.clear();
+          };
+          (void)x3l_bin_samples(fr.pos, bl, [&](auto put_at) { return x3w_replay_frame(payload, p, blk, put_at); }, X3LevKeepAll{}, flush_bank, &sig);
+        } else if constexpr (Signal::kTone) {
           Signal sig;
           sig.tab = tail.table;
           sig.step = tail.step;

@@ -858,6 +858,37 @@ inline X3Error tone_levels(Context& ctx, const EncodedStream& s, const Parameter
   return static_cast<X3Error>(rc);
 }
 
+// Up to X3_TONE_BANK_MAX oscillators against one table in one pass (x3_level_tone_bank): plane t of the records is what
+// tone_levels writes for Tone{steps[t], d_table}.
+struct ToneBank {
+  std::vector<uint32_t> steps;   // 1 .. X3_TONE_BANK_MAX
+  const int16_t* d_table = nullptr;
+  bool ok() const { return !steps.empty() && steps.size() <= X3_TONE_BANK_MAX; }
+  x3_level_tone_bank c_bank() const {   // (ok() only)
+    x3_level_tone_bank b{static_cast<uint32_t>(steps.size()), 0, d_table, {0}};
+    for (size_t t = 0; t < steps.size(); ++t) b.steps[t] = steps[t];
+    return b;
+  }
+};
+
+// Tone bank levels (x3_tone_bank_levels_dev): tone_levels' arguments with bank.steps.size() planes of n_bins records in
+// d_levels, plane t at d_levels + t * n_bins.  All planes go through tone_power_levels at once.  Waits for the call.
+inline X3Error tone_bank_levels(Context& ctx, const EncodedStream& s, const Parameters& params, const Buffer& d_sample_offsets,
+                                uint64_t bin_len, x3_tone_level* d_levels, uint64_t n_bins, int32_t* d_frame_status,
+                                WindowsResult* res, const ToneBank& bank) {
+  if (!s.bytes.ok() || !s.frame_offsets.ok() || !d_sample_offsets.ok() || !bank.ok()) return X3Error::BadArg;
+  const x3_params c = params.c_params();
+  const x3_level_tone_bank b = bank.c_bank();
+  int rc = x3_tone_bank_levels_dev(ctx.raw(), s.bytes.as<uint8_t>(), s.len, s.frame_offsets.as<uint64_t>(),
+                                   d_sample_offsets.as<uint64_t>(), s.n_frames, &c, s.seg_blocks ? s.seg_index.as<uint64_t>() : nullptr,
+                                   s.seg_blocks, bin_len, d_levels, n_bins, d_frame_status, &b);
+  if (rc != X3_OK) return static_cast<X3Error>(rc);
+  WindowsResult r;
+  rc = x3_levels_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status);
+  if (res) *res = r;
+  return static_cast<X3Error>(rc);
+}
+
 // The adapter into the chain (x3_tone_power_levels_dev): n_rows tone records -> the level records of the band, which
 // device::events and the quantiles calls take; d_levels may be d_tone's bytes (in place).  Asynchronous on the context's
 // stream: the calls behind it are ordered after it.
@@ -1109,6 +1140,19 @@ class Corpus {
                       WindowsResult* res, const Tone& tone) const {
     const x3_level_tone t = tone.c_tone();
     int rc = x3_corpus_tone_levels_dev(ctx.raw(), raw_, bin_len, d_levels, n_rows, d_frame_status, &t);
+    if (rc != X3_OK) return static_cast<X3Error>(rc);
+    WindowsResult r;
+    rc = x3_levels_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status);
+    if (res) *res = r;
+    return static_cast<X3Error>(rc);
+  }
+  // Tone bank levels of every entry (x3_corpus_tone_bank_levels_dev): bank.steps.size() planes of tone_levels()' n_rows
+  // records, plane t at d_levels + t * n_rows; every entry starts at phase 0 in every plane.  Waits for the call.
+  X3Error tone_bank_levels(Context& ctx, uint64_t bin_len, x3_tone_level* d_levels, uint64_t n_rows, int32_t* d_frame_status,
+                           WindowsResult* res, const ToneBank& bank) const {
+    if (!bank.ok()) return X3Error::BadArg;
+    const x3_level_tone_bank b = bank.c_bank();
+    int rc = x3_corpus_tone_bank_levels_dev(ctx.raw(), raw_, bin_len, d_levels, n_rows, d_frame_status, &b);
     if (rc != X3_OK) return static_cast<X3Error>(rc);
     WindowsResult r;
     rc = x3_levels_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status);

@@ -88,6 +88,16 @@ pub mod ffi {
         pub reserved: u32,
         pub d_table: *const i16,
     }
+    /// `x3_level_tone_bank`: the oscillators of `x3_tone_bank_levels_dev` / `x3_corpus_tone_bank_levels_dev` against one
+    /// table (48 bytes); `steps` behind `n_tones` (1 ..= 8) are never read; `reserved` must be 0
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, PartialEq, Eq)]
+    pub struct x3_level_tone_bank {
+        pub n_tones: u32,
+        pub reserved: u32,
+        pub d_table: *const i16,
+        pub steps: [u32; 8],
+    }
     /// `x3_tone_level`: one bin of `x3_tone_levels_dev` / `x3_corpus_tone_levels_dev` (32 bytes, `x3_level`'s layout slot for
     /// slot)
     #[repr(C)]
@@ -272,6 +282,12 @@ pub mod ffi {
                                   d_frame_status: *mut i32, tone: *const x3_level_tone) -> c_int;
         pub fn x3_corpus_tone_levels_dev(ctx: *mut x3_ctx, corpus: *const x3_corpus, bin_len: u64, d_levels: *mut x3_tone_level,
                                          n_rows: u64, d_frame_status: *mut i32, tone: *const x3_level_tone) -> c_int;
+        pub fn x3_tone_bank_levels_dev(ctx: *mut x3_ctx, d_x3: *const u8, x3_len: u64, d_frame_offsets: *const u64,
+                                       d_sample_offsets: *const u64, n_frames: u64, p: *const x3_params, d_seg_index: *const u64,
+                                       seg_blocks: u32, bin_len: u64, d_levels: *mut x3_tone_level, n_bins: u64,
+                                       d_frame_status: *mut i32, bank: *const x3_level_tone_bank) -> c_int;
+        pub fn x3_corpus_tone_bank_levels_dev(ctx: *mut x3_ctx, corpus: *const x3_corpus, bin_len: u64, d_levels: *mut x3_tone_level,
+                                              n_rows: u64, d_frame_status: *mut i32, bank: *const x3_level_tone_bank) -> c_int;
         pub fn x3_tone_power_levels_dev(ctx: *mut x3_ctx, d_tone: *const x3_tone_level, n_rows: u64, d_levels: *mut x3_level) -> c_int;
         pub fn x3_events_dev(ctx: *mut x3_ctx, d_levels: *const x3_level, n_bins: u64, bin_len: u64, d_total: *const u64,
                              rule: *const x3_event_rule, d_starts: *mut u64, d_lens: *mut u32, d_event_levels: *mut x3_level,
@@ -1596,6 +1612,50 @@ pub mod device {
         Ok((n_bad, first_bad, st))
     }
 
+    /// The oscillators of `tone_bank_levels` (`x3_level_tone_bank`): 1 ..= 8 steps against one table, a device buffer as
+    /// `Tone`'s
+    #[derive(Clone, Copy)]
+    pub struct ToneBank<'a, 'g> {
+        pub steps: &'a [u32],
+        pub table: &'a Buffer<'g>,
+    }
+
+    impl ToneBank<'_, '_> {
+        fn c(&self) -> error::Result<ffi::x3_level_tone_bank> {
+            if self.steps.is_empty() || self.steps.len() > 8 || self.table.len() < 4096 {
+                return Err(X3Error::BadArg);
+            }
+            let mut steps = [0u32; 8];
+            steps[..self.steps.len()].copy_from_slice(self.steps);
+            Ok(ffi::x3_level_tone_bank { n_tones: self.steps.len() as u32, reserved: 0, d_table: self.table.as_ptr::<i16>() as *const i16, steps })
+        }
+    }
+
+    /// Tone bank levels (`x3_tone_bank_levels_dev`; not in the reference crate): `tone_levels` for every step of the bank in
+    /// one pass over the stream; `d_levels` holds `bank.steps.len()` planes of `n_bins` `ToneLevel`s, plane `t` what
+    /// `tone_levels` writes for step `t`
+    #[allow(clippy::too_many_arguments)]
+    pub fn tone_bank_levels<'g>(gpu: &'g Gpu, s: &EncodedStream<'g>, params: &x3::Parameters, sample_offsets: &Buffer<'g>, bin_len: u64,
+                                d_levels: &mut Buffer<'g>, n_bins: usize, d_frame_status: Option<&mut Buffer<'g>>,
+                                bank: &ToneBank<'_, 'g>) -> error::Result<(u64, u64, i32)> {
+        let b = bank.c()?;
+        if d_levels.len() < core::mem::size_of::<ToneLevel>() * n_bins * bank.steps.len()
+            || d_frame_status.as_ref().map_or(false, |b| b.len() < 4 * s.n_frames) {
+            return Err(X3Error::BadArg);
+        }
+        let p = params.c()?;
+        let idx = match &s.seg_index { Some(i) => i.as_ptr::<u64>() as *const u64, None => core::ptr::null() };
+        let st_ptr = match d_frame_status { Some(b) => b.as_ptr::<i32>(), None => core::ptr::null_mut() };
+        error::check(unsafe {
+            ffi::x3_tone_bank_levels_dev(gpu.raw(), s.bytes.as_ptr::<u8>(), s.len as u64, s.frame_offsets.as_ptr::<u64>(),
+                                         sample_offsets.as_ptr::<u64>(), s.n_frames as u64, &p, idx, s.seg_blocks, bin_len,
+                                         d_levels.as_ptr::<ToneLevel>(), n_bins as u64, st_ptr, &b)
+        })?;
+        let (mut n_bad, mut first_bad, mut st) = (0u64, 0u64, 0);
+        error::check(unsafe { ffi::x3_levels_result(gpu.raw(), &mut n_bad, &mut first_bad, &mut st) })?;
+        Ok((n_bad, first_bad, st))
+    }
+
     /// The adapter into the chain (`x3_tone_power_levels_dev`): the first `n_rows` tone records of `d_tone` -> the `Level`
     /// records of the band in `d_levels` (`None`: in place), which `events` and the quantiles calls take.  Asynchronous on the
     /// context's stream
@@ -2002,6 +2062,24 @@ pub mod device {
             let st_ptr = match d_frame_status { Some(b) => b.as_ptr::<i32>(), None => core::ptr::null_mut() };
             error::check(unsafe {
                 ffi::x3_corpus_tone_levels_dev(self.gpu.raw(), self.raw, bin_len, d_levels.as_ptr::<ToneLevel>(), n_rows as u64, st_ptr, &t)
+            })?;
+            let (mut n_bad, mut first_bad, mut st) = (0u64, 0u64, 0);
+            error::check(unsafe { ffi::x3_levels_result(self.gpu.raw(), &mut n_bad, &mut first_bad, &mut st) })?;
+            Ok((n_bad, first_bad, st))
+        }
+
+        /// Tone bank levels of every entry (`x3_corpus_tone_bank_levels_dev`): `bank.steps.len()` planes of `tone_levels`'
+        /// `n_rows` records; every entry starts at phase 0 in every plane
+        pub fn tone_bank_levels(&self, bin_len: u64, d_levels: &mut Buffer<'g>, n_rows: usize, d_frame_status: Option<&mut Buffer<'g>>,
+                                bank: &ToneBank<'_, 'g>) -> error::Result<(u64, u64, i32)> {
+            let b = bank.c()?;
+            if d_levels.len() < core::mem::size_of::<ToneLevel>() * n_rows * bank.steps.len()
+                || d_frame_status.as_ref().map_or(false, |b| b.len() < 4 * self.info().1 as usize) {
+                return Err(X3Error::BadArg);
+            }
+            let st_ptr = match d_frame_status { Some(b) => b.as_ptr::<i32>(), None => core::ptr::null_mut() };
+            error::check(unsafe {
+                ffi::x3_corpus_tone_bank_levels_dev(self.gpu.raw(), self.raw, bin_len, d_levels.as_ptr::<ToneLevel>(), n_rows as u64, st_ptr, &b)
             })?;
             let (mut n_bad, mut first_bad, mut st) = (0u64, 0u64, 0);
             error::check(unsafe { ffi::x3_levels_result(self.gpu.raw(), &mut n_bad, &mut first_bad, &mut st) })?;

@@ -64,6 +64,7 @@ SYMBOLS = [
     "x3_levels_dev", "x3_levels_result", "x3_corpus_levels_rows", "x3_corpus_levels_dev",
     "x3_signal_levels_dev", "x3_corpus_signal_levels_dev", "x3_fir_levels_dev", "x3_corpus_fir_levels_dev",
     "x3_tone_levels_dev", "x3_corpus_tone_levels_dev", "x3_tone_power_levels_dev",
+    "x3_tone_bank_levels_dev", "x3_corpus_tone_bank_levels_dev",
     "x3_events_dev", "x3_corpus_events_dev", "x3_events_result",
     "x3_level_quantiles_dev", "x3_corpus_level_quantiles_dev", "x3_level_quantiles_result",
     "x3_level_thresholds_dev", "x3_corpus_level_thresholds_dev", "x3_events_adaptive_dev", "x3_corpus_events_adaptive_dev",
@@ -132,6 +133,16 @@ class LevelTone(C.Structure):
     _fields_ = [("step", C.c_uint32), ("reserved", C.c_uint32), ("d_table", C.c_void_p)]
 
 
+TONE_BANK_MAX = 8   # X3_TONE_BANK_MAX: the oscillators of one tone bank call
+
+
+class LevelToneBank(C.Structure):
+    """x3_level_tone_bank: the oscillators of x3_tone_bank_levels_dev / x3_corpus_tone_bank_levels_dev against one table;
+    d_table is a device pointer, steps behind n_tones are never read"""
+    _fields_ = [("n_tones", C.c_uint32), ("reserved", C.c_uint32), ("d_table", C.c_void_p),
+                ("steps", C.c_uint32 * TONE_BANK_MAX)]
+
+
 TONE_TABLE_PAIRS = 1024   # (cos, sin) int16 pairs of a tone table: 4 096 bytes
 
 
@@ -161,6 +172,11 @@ class Tone:
             raise ValueError("Tone.at: 0 <= freq < sample_rate")
         return cls(min(int(round(float(freq) / float(sample_rate) * 4294967296.0)), 0xFFFFFFFF))
 
+    @classmethod
+    def bank(cls, freqs, sample_rate):
+        """-> the tuple of Tone.at(f, sample_rate) for f in freqs: the `tones` of tone_bank_levels (1 .. TONE_BANK_MAX)"""
+        return tuple(cls.at(f, sample_rate) for f in freqs)
+
     def __setattr__(self, name, value):
         raise AttributeError("Tone is immutable")
 
@@ -175,6 +191,19 @@ class Tone:
 
     def __repr__(self):
         return "Tone(step=%d)" % self.step
+
+
+def tone_bank(tones):
+    """the `tones` of the tone bank calls -> a tuple of 1 .. TONE_BANK_MAX Tone, or ValueError"""
+    if isinstance(tones, Tone):
+        raise ValueError("tones: a sequence of 1 .. %d Tone (one Tone: tone_levels)" % TONE_BANK_MAX)
+    try:
+        tones = tuple(tones)
+    except TypeError:
+        raise ValueError("tones: a sequence of 1 .. %d Tone" % TONE_BANK_MAX) from None
+    if not 1 <= len(tones) <= TONE_BANK_MAX or not all(isinstance(t, Tone) for t in tones):
+        raise ValueError("tones: a sequence of 1 .. %d Tone" % TONE_BANK_MAX)
+    return tones
 
 
 def level_signal(signal, fir=True):
@@ -411,6 +440,8 @@ def lib():
     L.x3_tone_levels_dev.argtypes = [vp, vp, u64, vp, vp, u64, PP, vp, u32, u64, vp, u64, vp, C.POINTER(LevelTone)]
     L.x3_corpus_tone_levels_dev.argtypes = [vp, vp, u64, vp, u64, vp, C.POINTER(LevelTone)]
     L.x3_tone_power_levels_dev.argtypes = [vp, vp, u64, vp]
+    L.x3_tone_bank_levels_dev.argtypes = [vp, vp, u64, vp, vp, u64, PP, vp, u32, u64, vp, u64, vp, C.POINTER(LevelToneBank)]
+    L.x3_corpus_tone_bank_levels_dev.argtypes = [vp, vp, u64, vp, u64, vp, C.POINTER(LevelToneBank)]
     L.x3_events_dev.argtypes = [vp, vp, u64, u64, vp, C.POINTER(EventRule), vp, vp, vp, u64, vp]
     L.x3_corpus_events_dev.argtypes = [vp, vp, vp, u64, u64, C.POINTER(EventRule), vp, vp, vp, vp, u64, vp]
     L.x3_events_result.argtypes = [vp, C.POINTER(u64)]
@@ -1215,6 +1246,31 @@ class Context:
         asynchronous, levels_result waits"""
         return lib().x3_corpus_tone_levels_dev(self._h, corpus._h, bin_len, d_levels, n_rows, d_frame_status, self._tone_arg(tone))
 
+    def _tone_bank_arg(self, tones):
+        """a sequence of 1 .. TONE_BANK_MAX Tone (with the context's usual table), a LevelToneBank as it is, or None (NULL,
+        which the library refuses)"""
+        if tones is None:
+            return None
+        if isinstance(tones, LevelToneBank):
+            return C.byref(tones)
+        tones = tone_bank(tones)
+        return C.byref(LevelToneBank(len(tones), 0, self.tone_table_dev(), (C.c_uint32 * TONE_BANK_MAX)(*[t.step for t in tones])))
+
+    def tone_bank_levels_dev(self, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, params, bin_len, d_levels, n_bins,
+                             d_frame_status=None, d_seg_index=None, seg_blocks=0, tones=None):
+        """x3_tone_bank_levels_dev: len(tones) planes of n_bins x3_tone_level records (TONE_DTYPE), plane t what
+        tone_levels_dev writes for tones[t], in one pass over the stream (tones: 1 .. TONE_BANK_MAX Tone, or a
+        LevelToneBank as it is); asynchronous, levels_result waits"""
+        return lib().x3_tone_bank_levels_dev(self._h, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, C.byref(params),
+                                             d_seg_index, seg_blocks, bin_len, d_levels, n_bins, d_frame_status,
+                                             self._tone_bank_arg(tones))
+
+    def corpus_tone_bank_levels_dev(self, corpus, bin_len, d_levels, n_rows, d_frame_status=None, tones=None):
+        """x3_corpus_tone_bank_levels_dev: len(tones) planes of corpus_tone_levels_dev's n_rows records, every entry at phase
+        0 in every plane; asynchronous, levels_result waits"""
+        return lib().x3_corpus_tone_bank_levels_dev(self._h, corpus._h, bin_len, d_levels, n_rows, d_frame_status,
+                                                    self._tone_bank_arg(tones))
+
     def tone_power_levels_dev(self, d_tone, n_rows, d_levels):
         """x3_tone_power_levels_dev: n_rows tone records -> the x3_level records of the band's level (d_levels == d_tone: in
         place); asynchronous on the context's stream, no result call"""
@@ -1824,11 +1880,13 @@ class WindowSource:
                                         self.params, bin_len, d_levels, n_bins, d_frame_status, self.d_seg_index,
                                         self.seg_blocks, tone)
 
-    def _levels_np(self, what, bin_len, n_bins, dtype, enqueue):
-        """the host side of levels() / tone_levels(): enqueue(d_levels, d_status) -> rc, then the result and both downloads"""
+    def _levels_np(self, what, bin_len, n_bins, dtype, enqueue, planes=None):
+        """the host side of levels() / tone_levels(): enqueue(d_levels, d_status) -> rc, then the result and both downloads;
+        planes (tone_bank_levels): so many planes of n_bins records, returned as [planes, n_bins]"""
         if n_bins is None:
             n_bins = max(1, -(-self.total // bin_len)) if bin_len else 1
-        d_lv, d_st = self.ctx.alloc(dtype.itemsize * n_bins), self.ctx.alloc(4 * self.n_frames)
+        n_rec = n_bins * (planes or 1)
+        d_lv, d_st = self.ctx.alloc(dtype.itemsize * n_rec), self.ctx.alloc(4 * self.n_frames)
         try:
             rc = enqueue(d_lv, n_bins, d_st)
             if rc:
@@ -1836,11 +1894,32 @@ class WindowSource:
             rc = self.ctx.levels_result()[0]
             if rc:
                 raise X3Error(rc, "x3_levels_result: " + self.ctx.last_error())
-            return (self.ctx.download(d_lv, dtype.itemsize * n_bins, dtype),
+            rec = self.ctx.download(d_lv, dtype.itemsize * n_rec, dtype)
+            return (rec.reshape(planes, n_bins) if planes else rec,
                     self.ctx.download(d_st, 4 * self.n_frames, np.int32))
         finally:
             for p in (d_lv, d_st):
                 self.ctx.free(p)
+
+    def tone_bank_levels_into(self, bin_len, tones, d_levels, n_bins, d_frame_status=None, *, band=False):
+        """enqueue x3_tone_bank_levels_dev over this source (device pointers; tones: 1 .. TONE_BANK_MAX Tone or a
+        LevelToneBank; d_levels: that many planes of n_bins records), band=True: and the adapter in place over all planes
+        behind it; -> rc; Context.levels_result waits"""
+        k = tones.n_tones if isinstance(tones, LevelToneBank) else len(tone_bank(tones))
+        rc = self.ctx.tone_bank_levels_dev(self.d_x3, self.x3_len, self.d_frame_offsets, self.d_sample_offsets, self.n_frames,
+                                           self.params, bin_len, d_levels, n_bins, d_frame_status, self.d_seg_index,
+                                           self.seg_blocks, tones)
+        return rc or (self.ctx.tone_power_levels_dev(d_levels, k * n_bins, d_levels) if band else 0)
+
+    def tone_bank_levels(self, bin_len, tones, n_bins=None, *, band=False):
+        """-> (records np.ndarray of TONE_DTYPE [K, n_bins], frame statuses np.int32 [n_frames]): plane t is
+        tone_levels(bin_len, tones[t], n_bins), all K = len(tones) of them (1 .. TONE_BANK_MAX Tone) from one pass over
+        the stream (x3_tone_bank_levels_dev).  band=True: x3_tone_power_levels_dev in place over all planes behind the
+        call; the records are then LEVEL_DTYPE, the level of each band, which events() takes plane by plane"""
+        tones = tone_bank(tones)
+        return self._levels_np("x3_tone_bank_levels_dev", bin_len, n_bins, LEVEL_DTYPE if band else TONE_DTYPE,
+                               lambda d_lv, nb, d_st: self.tone_bank_levels_into(bin_len, tones, d_lv, nb, d_st, band=band),
+                               planes=len(tones))
 
     def tone_levels(self, bin_len, tone, n_bins=None):
         """-> (records np.ndarray of TONE_DTYPE [n_bins], frame statuses np.int32 [n_frames]): re, im -- the sums of sample
@@ -2241,12 +2320,13 @@ class Corpus:
         return self._levels_np("x3_corpus_signal_levels_dev", bin_len, LEVEL_DTYPE,
                                lambda d_lv, n_rows, d_st: self.levels_into(bin_len, d_lv, n_rows, d_st, sig))
 
-    def _levels_np(self, what, bin_len, dtype, enqueue):
+    def _levels_np(self, what, bin_len, dtype, enqueue, planes=None):
         """the host side of levels() / tone_levels(): enqueue(d_levels, n_rows, d_status) -> rc, then the result and the
-        downloads"""
+        downloads; planes (tone_bank_levels): so many planes of n_rows records, returned as [planes, n_rows]"""
         rf = self.levels_rows(bin_len)
         n_rows = int(rf[-1])
-        d_lv, d_st = self.ctx.alloc(dtype.itemsize * n_rows), self.ctx.alloc(4 * max(self.n_frames, 1))
+        n_rec = n_rows * (planes or 1)
+        d_lv, d_st = self.ctx.alloc(dtype.itemsize * n_rec), self.ctx.alloc(4 * max(self.n_frames, 1))
         try:
             rc = enqueue(d_lv, n_rows, d_st)
             if rc:
@@ -2255,7 +2335,8 @@ class Corpus:
             if rc:
                 raise X3Error(rc, "x3_levels_result: " + self.ctx.last_error())
             st = self.ctx.download(d_st, 4 * self.n_frames, np.int32) if self.n_frames else np.zeros(0, dtype=np.int32)
-            return self.ctx.download(d_lv, dtype.itemsize * n_rows, dtype), rf, st
+            rec = self.ctx.download(d_lv, dtype.itemsize * n_rec, dtype)
+            return (rec.reshape(planes, n_rows) if planes else rec), rf, st
         finally:
             for p in (d_lv, d_st):
                 self.ctx.free(p)
@@ -2266,6 +2347,26 @@ class Corpus:
         if self._h is None:
             raise ValueError("the corpus is closed")
         return self.ctx.corpus_tone_levels_dev(self, bin_len, d_levels, n_rows, d_frame_status, tone)
+
+    def tone_bank_levels_into(self, bin_len, tones, d_levels, n_rows, d_frame_status=None, *, band=False):
+        """enqueue x3_corpus_tone_bank_levels_dev (device pointers; tones: 1 .. TONE_BANK_MAX Tone or a LevelToneBank;
+        d_levels: that many planes of n_rows records), band=True: and the adapter in place over all planes behind it; -> rc;
+        Context.levels_result waits"""
+        if self._h is None:
+            raise ValueError("the corpus is closed")
+        k = tones.n_tones if isinstance(tones, LevelToneBank) else len(tone_bank(tones))
+        rc = self.ctx.corpus_tone_bank_levels_dev(self, bin_len, d_levels, n_rows, d_frame_status, tones)
+        return rc or (self.ctx.tone_power_levels_dev(d_levels, k * n_rows, d_levels) if band else 0)
+
+    def tone_bank_levels(self, bin_len, tones, *, band=False):
+        """-> (records np.ndarray of TONE_DTYPE [K, rows], row_first, frame statuses): plane t is tone_levels(bin_len,
+        tones[t])'s records, all K = len(tones) of them (1 .. TONE_BANK_MAX Tone) from one pass over the corpus
+        (x3_corpus_tone_bank_levels_dev); row_first is the single call's, in every plane.  band=True: the adapter in place
+        over all planes, the records are LEVEL_DTYPE"""
+        tones = tone_bank(tones)
+        return self._levels_np("x3_corpus_tone_bank_levels_dev", bin_len, LEVEL_DTYPE if band else TONE_DTYPE,
+                               lambda d_lv, n_rows, d_st: self.tone_bank_levels_into(bin_len, tones, d_lv, n_rows, d_st, band=band),
+                               planes=len(tones))
 
     def tone_levels(self, bin_len, tone):
         """-> (records np.ndarray of TONE_DTYPE [rows], row_first, frame statuses) as levels(): the quadrature sums of every
