@@ -314,7 +314,7 @@ def test_corpus_entries_are_each_the_stream_call_alone_in_every_plane(ctx, x3, i
             fst = [CRC if (e == 4 and f == 1) else ost[f] for f in range(len(fo))]
             lens_f = [int(s[o + 4]) << 8 | int(s[o + 5]) for o in fo]
             ref_entries.append((frames, fst, np.concatenate([[0], np.cumsum(lens_f)])[:-1], sum(lens_f)))
-        for k in (1, 3, 8):
+        for k in (1, 2, 3, 8):                                         # the single call and each of the three bank instances
             tones = tuple(x3.Tone(s) for s in POOL[:k])
             for bin_len in (0, 1, 100):
                 rows, rf, st = corpus.tone_bank_levels(bin_len, tones)

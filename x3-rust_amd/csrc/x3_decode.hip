@@ -1318,73 +1318,6 @@ size_t levels_carve(char* base, uint64_t F, uint64_t n_rows, uint64_t fix_waves,
   return k.at;
 }
 
-// The launch set of a levels call behind its prep step: prep(grid, row_first, fst, frames, cnt) enqueues the kernels that
-// give every frame its position, its records and its row count.  n_ent: entries of a corpus call (their row prefix lives
-// in the workspace), 0 for a stream.  signal: X3_LEVEL_SIGNAL_SAMPLES, or X3_LEVEL_SIGNAL_DIFF -- the other instance of the
-// accumulate and fix-up kernels, which leave every good frame's last sample in the workspace, and the seam kernel behind them.
-// fir (checked: levels_fir_taps) instead of a signal: the X3LevFir instance, which leaves an edge record per (frame, stretch)
-// in a workspace of its own (fir_ws; lev_ws keeps its layout), and x3_levels_fir_seam_kernel behind the merge.
-// tone (checked: levels_tone_arg) instead of either: the X3LevTone instance, whose records hold re and im in x3_level's first
-// two slots; no workspace of its own and no kernel behind the merge.
-// bank (checked: levels_tone_bank_arg, two tones or more) instead of any: the X3LevToneBank<NT> instances.  d_levels and the
-// partial rows hold bank->n_tones PLANES of n_rows and n_rows + F records; the accumulate instance is the smallest of NT = 2,
-// 4, 8 that holds the tones, the fix-up's is NT = 8, and the merge kernel runs once per plane.
-template <class Prep>
-static int levels_launch(x3_ctx* c, const FrameSource& s, uint64_t bin_len, x3_level* d_levels, uint64_t n_rows,
-                         int32_t* d_frame_status, uint64_t n_ent, int signal, Prep prep, const X3FirTaps* fir = nullptr,
-                         const X3LevToneTail* tone = nullptr, const X3LevToneBankTail* bank = nullptr) {
-  const bool diff = !fir && !tone && !bank && signal == X3_LEVEL_SIGNAL_DIFF;
-  HIPCHK(c, hipSetDevice(c->device));
-  const uint64_t F = s.F, cap = n_rows + F, planes = bank ? bank->n_tones : 1;
-  const uint32_t scratch_per = levels_scratch_per(s.dp.block_len);
-  const uint64_t fix_waves = levels_fix_waves(F, scratch_per);
-  LevWs w;
-  int rc;
-  if ((rc = ensure(c, c->lev_ws, levels_carve(nullptr, F, n_rows, fix_waves, scratch_per, n_ent, &w, planes)))) return rc;
-  levels_carve((char*)c->lev_ws.p, F, n_rows, fix_waves, scratch_per, n_ent, &w, planes);
-  if (fir && (rc = ensure(c, c->fir_ws, (size_t)(F * s.nseg) * sizeof(X3FirEdge)))) return rc;
-  hipLaunchKernelGGL(x3_levels_init_kernel, dim3(grid_for(planes * (n_rows + cap), 256)), dim3(256), 0, c->stream, d_levels,
-                     planes * n_rows, w.rows, planes * cap, w.sum);
-  hipLaunchKernelGGL(x3_levels_check_kernel, dim3(grid_for(F, 4)), dim3(256), 0, c->stream, s.d_x3, s.x3_len, s.d_frame_offsets,
-                     s.d_sample_offsets, F, w.fst);
-  prep(dim3(grid_for(F, 256)), w.row_first, (const int32_t*)w.fst, w.frames, w.cnt);
-  hipLaunchKernelGGL(x3_levels_scan_kernel, dim3(1), dim3(1024), 0, c->stream, (const uint32_t*)w.cnt, F, cap, w.row, w.fst);
-  auto decode = [&](auto sig, auto fix, auto tail) {   // the two kernels that decode, for a signal
-    hipLaunchKernelGGL(x3_levels_accum_kernel<decltype(sig)>, dim3(grid_for(F * s.nseg, 256)), dim3(256), 0, c->stream, s.d_x3, s.x3_len,
-                       s.d_frame_offsets, F, s.dp, s.idx, s.seg_blocks, s.nseg, bin_len, (const X3LevFrame*)w.frames,
-                       (const unsigned long long*)w.row, w.rows, w.fst, tail);
-    hipLaunchKernelGGL(x3_levels_fixup_kernel<decltype(fix)>, dim3((unsigned)((fix_waves + 3) / 4)), dim3(256), 0, c->stream, s.d_x3,
-                       s.d_frame_offsets, F, s.dp, bin_len, (const X3LevFrame*)w.frames, w.fst, d_levels, d_frame_status,
-                       w.scratch, scratch_per, w.sum, tail);
-  };
-  if (bank) {
-    X3LevToneBankTail t = *bank;
-    t.rows_stride = cap, t.levels_stride = n_rows;
-    if (t.n_tones <= 2) decode(X3LevToneBank<2>{}, X3LevToneBank<X3L_TONE_BANK>{}, t);
-    else if (t.n_tones <= 4) decode(X3LevToneBank<4>{}, X3LevToneBank<X3L_TONE_BANK>{}, t);
-    else decode(X3LevToneBank<X3L_TONE_BANK>{}, X3LevToneBank<X3L_TONE_BANK>{}, t);
-  } else if (tone) decode(X3LevTone{}, X3LevTone{}, *tone);
-  else if (fir) decode(X3LevFir{}, X3LevFir{}, X3LevFirTail{*fir, (X3FirEdge*)c->fir_ws.p, s.nseg});
-  else if (diff) decode(X3LevDiff{}, X3LevDiff{}, w.tail);
-  else decode(X3LevSamples{}, X3LevSamples{}, X3LevNoTail{});
-  for (uint64_t t = 0; t < planes; ++t)   // (a plane's rows and records: the same frames, row scan and verdicts)
-    hipLaunchKernelGGL(x3_levels_merge_kernel, dim3(grid_for(cap, 256)), dim3(256), 0, c->stream, (const X3LevFrame*)w.frames,
-                       (const unsigned long long*)w.row, F, cap, (const x3_level*)w.rows + t * cap, (const int32_t*)w.fst,
-                       d_levels + t * n_rows);
-  if (diff && F > 1)
-    hipLaunchKernelGGL(x3_levels_seam_kernel, dim3(grid_for(F, 256)), dim3(256), 0, c->stream, s.d_x3, s.x3_len, s.d_frame_offsets,
-                       F, bin_len, (const X3LevFrame*)w.frames, (const int32_t*)w.fst, (const int32_t*)w.tail, d_levels);
-  if (fir && fir->T > 1)
-    hipLaunchKernelGGL(x3_levels_fir_seam_kernel, dim3(grid_for(F * s.nseg, 256)), dim3(256), 0, c->stream, F, s.dp.block_len, s.idx,
-                       s.seg_blocks, s.nseg, bin_len, (const X3LevFrame*)w.frames, (const int32_t*)w.fst,
-                       (const X3FirEdge*)c->fir_ws.p, s.nseg, *fir, d_levels);
-  HIPCHK(c, hipGetLastError());
-  c->levels.pending = true;
-  c->levels.count = F;
-  c->levels.sum_off = (size_t)((char*)w.sum - (char*)c->lev_ws.p);
-  return X3_OK;
-}
-
 static bool levels_signal_ok(int signal) { return signal == X3_LEVEL_SIGNAL_SAMPLES || signal == X3_LEVEL_SIGNAL_DIFF; }
 
 // x3_level_fir as the kernels take it, the taps at and behind T zero; false: not 1 <= T <= 8, shift <= 15, sum |c| <= 32768
@@ -1408,45 +1341,135 @@ static bool levels_tone_arg(const x3_level_tone* tone, X3LevToneTail* t) {
 }
 
 // x3_level_tone_bank as the kernels take it, the steps at and behind n_tones zero; false: NULL, n_tones not 1 .. 8,
-// reserved != 0, a NULL or misaligned table.  One tone is the single call's tail (*one).
-static bool levels_tone_bank_arg(const x3_level_tone_bank* bank, X3LevToneBankTail* t, X3LevToneTail* one) {
+// reserved != 0, a NULL or misaligned table
+static bool levels_tone_bank_arg(const x3_level_tone_bank* bank, X3LevToneBankTail* t) {
   if (!bank || bank->n_tones < 1 || bank->n_tones > X3_TONE_BANK_MAX || bank->reserved != 0 || !bank->d_table ||
       (reinterpret_cast<uintptr_t>(bank->d_table) & 3u) != 0)
     return false;
-  t->table = one->table = reinterpret_cast<const uint32_t*>(bank->d_table);
+  t->table = reinterpret_cast<const uint32_t*>(bank->d_table);
   t->n_tones = bank->n_tones;
   for (uint32_t i = 0; i < X3L_TONE_BANK; ++i) t->steps[i] = i < bank->n_tones ? bank->steps[i] : 0;
   t->rows_stride = t->levels_stride = 0;   // (levels_launch's)
-  one->step = bank->steps[0];
   return true;
 }
 static_assert(X3_TONE_BANK_MAX == X3L_TONE_BANK, "the header's bank is the kernels'");
-// all planes of a bank in one launch of the adapter: n_tones * n_rows <= 2^31 - 1 (n_rows itself: levels_args_ok)
-static bool levels_planes_ok(const X3LevToneBankTail* bank, uint64_t n_rows) {
-  return !bank || n_rows <= 0x7FFFFFFFull / bank->n_tones;
-}
 static_assert(sizeof(x3_tone_level) == sizeof(x3_level) && alignof(x3_tone_level) == alignof(x3_level) &&
                   offsetof(x3_tone_level, re) == offsetof(x3_level, sum_sq) && offsetof(x3_tone_level, im) == offsetof(x3_level, sum) &&
                   offsetof(x3_tone_level, min) == offsetof(x3_level, min) && offsetof(x3_tone_level, max) == offsetof(x3_level, max) &&
                   offsetof(x3_tone_level, n) == offsetof(x3_level, n),
               "x3_tone_level has x3_level's layout slot for slot");
 
-// the stream form of the levels calls behind the check of the signal, the taps (fir != NULL: the FIR call) or the
-// oscillator (tone != NULL: the tone call)
+// The signal of a levels or range-levels call: its kind and that kind's payload as the kernels take it.  Built only from an
+// argument one of the four checks above has passed, so the launchers and the *_call helpers ask it and check nothing again.
+struct LevSignal {
+  enum Kind { SAMPLES, DIFF, FIR, TONE, BANK } kind;
+  X3FirTaps fir{};            // FIR
+  X3LevToneTail tone{};       // TONE: records hold re and im in x3_level's first two slots
+  X3LevToneBankTail bank{};   // BANK, two tones or more: d_levels and the partial rows hold n_tones PLANES
+  explicit LevSignal(int signal) : kind(signal == X3_LEVEL_SIGNAL_DIFF ? DIFF : SAMPLES) {}
+  explicit LevSignal(const X3FirTaps& k) : kind(FIR), fir(k) {}
+  explicit LevSignal(const X3LevToneTail& t) : kind(TONE), tone(t) {}
+  // (a bank of one tone IS the tone call: here and nowhere else)
+  explicit LevSignal(const X3LevToneBankTail& b) : kind(b.n_tones == 1 ? TONE : BANK), tone{b.table, b.steps[0]}, bank(b) {}
+
+  uint64_t planes() const { return kind == BANK ? bank.n_tones : 1; }
+  // a range's plan: a lead kernel behind it and tail[], lead[] in the workspace; the frames it may hold in front
+  bool lead() const { return kind == DIFF || kind == FIR; }
+  uint64_t lead_frames() const { return kind == FIR ? fir.T - 1 : kind == DIFF ? 1 : 0; }
+  bool fir_ws() const { return kind == FIR; }   // an edge record per (frame, stretch) in a workspace of its own
+  bool seam() const { return kind == DIFF || (kind == FIR && fir.T > 1); }   // a seam kernel behind the merge
+};
+
+// all planes of a bank in one launch of the adapter: n_tones * n_rows <= 2^31 - 1 (n_rows itself: levels_args_ok)
+static bool levels_planes_ok(const LevSignal& g, uint64_t n_rows) { return n_rows <= 0x7FFFFFFFull / g.planes(); }
+
+// The launch set of a levels call behind its prep step: prep(grid, row_first, fst, frames, cnt) enqueues the kernels that
+// give every frame its position, its records and its row count.  n_ent: entries of a corpus call (their row prefix lives
+// in the workspace), 0 for a stream.  g picks the instance of the accumulate and fix-up kernels and the seam kernel behind
+// the merge, in the switch below: DIFF leaves every good frame's last sample in the workspace, FIR its edge records in
+// fir_ws (lev_ws keeps its layout); a bank's accumulate instance is the smallest of NT = 2, 4, 8 that holds the tones, its
+// fix-up's is NT = 8, and the merge kernel runs once per plane.
+template <class Prep>
+static int levels_launch(x3_ctx* c, const FrameSource& s, uint64_t bin_len, x3_level* d_levels, uint64_t n_rows,
+                         int32_t* d_frame_status, uint64_t n_ent, const LevSignal& g, Prep prep) {
+  HIPCHK(c, hipSetDevice(c->device));
+  const uint64_t F = s.F, cap = n_rows + F, planes = g.planes();
+  const uint32_t scratch_per = levels_scratch_per(s.dp.block_len);
+  const uint64_t fix_waves = levels_fix_waves(F, scratch_per);
+  LevWs w;
+  int rc;
+  if ((rc = ensure(c, c->lev_ws, levels_carve(nullptr, F, n_rows, fix_waves, scratch_per, n_ent, &w, planes)))) return rc;
+  levels_carve((char*)c->lev_ws.p, F, n_rows, fix_waves, scratch_per, n_ent, &w, planes);
+  if (g.fir_ws() && (rc = ensure(c, c->fir_ws, (size_t)(F * s.nseg) * sizeof(X3FirEdge)))) return rc;
+  hipLaunchKernelGGL(x3_levels_init_kernel, dim3(grid_for(planes * (n_rows + cap), 256)), dim3(256), 0, c->stream, d_levels,
+                     planes * n_rows, w.rows, planes * cap, w.sum);
+  hipLaunchKernelGGL(x3_levels_check_kernel, dim3(grid_for(F, 4)), dim3(256), 0, c->stream, s.d_x3, s.x3_len, s.d_frame_offsets,
+                     s.d_sample_offsets, F, w.fst);
+  prep(dim3(grid_for(F, 256)), w.row_first, (const int32_t*)w.fst, w.frames, w.cnt);
+  hipLaunchKernelGGL(x3_levels_scan_kernel, dim3(1), dim3(1024), 0, c->stream, (const uint32_t*)w.cnt, F, cap, w.row, w.fst);
+  // the two kernels that decode, for a signal; the merge; the signal's seam kernel
+  auto run = [&](auto sig, auto fix, auto tail, auto seam) {
+    hipLaunchKernelGGL(x3_levels_accum_kernel<decltype(sig)>, dim3(grid_for(F * s.nseg, 256)), dim3(256), 0, c->stream, s.d_x3, s.x3_len,
+                       s.d_frame_offsets, F, s.dp, s.idx, s.seg_blocks, s.nseg, bin_len, (const X3LevFrame*)w.frames,
+                       (const unsigned long long*)w.row, w.rows, w.fst, tail);
+    hipLaunchKernelGGL(x3_levels_fixup_kernel<decltype(fix)>, dim3((unsigned)((fix_waves + 3) / 4)), dim3(256), 0, c->stream, s.d_x3,
+                       s.d_frame_offsets, F, s.dp, bin_len, (const X3LevFrame*)w.frames, w.fst, d_levels, d_frame_status,
+                       w.scratch, scratch_per, w.sum, tail);
+    for (uint64_t t = 0; t < planes; ++t)   // (a plane's rows and records: the same frames, row scan and verdicts)
+      hipLaunchKernelGGL(x3_levels_merge_kernel, dim3(grid_for(cap, 256)), dim3(256), 0, c->stream, (const X3LevFrame*)w.frames,
+                         (const unsigned long long*)w.row, F, cap, (const x3_level*)w.rows + t * cap, (const int32_t*)w.fst,
+                         d_levels + t * n_rows);
+    if (g.seam()) seam();
+  };
+  auto no_seam = [] {};
+  switch (g.kind) {
+    case LevSignal::BANK: {
+      X3LevToneBankTail t = g.bank;
+      t.rows_stride = cap, t.levels_stride = n_rows;
+      if (t.n_tones <= 2) run(X3LevToneBank<2>{}, X3LevToneBank<X3L_TONE_BANK>{}, t, no_seam);
+      else if (t.n_tones <= 4) run(X3LevToneBank<4>{}, X3LevToneBank<X3L_TONE_BANK>{}, t, no_seam);
+      else run(X3LevToneBank<X3L_TONE_BANK>{}, X3LevToneBank<X3L_TONE_BANK>{}, t, no_seam);
+      break;
+    }
+    case LevSignal::TONE: run(X3LevTone{}, X3LevTone{}, g.tone, no_seam); break;
+    case LevSignal::FIR:
+      run(X3LevFir{}, X3LevFir{}, X3LevFirTail{g.fir, (X3FirEdge*)c->fir_ws.p, s.nseg}, [&] {
+        hipLaunchKernelGGL(x3_levels_fir_seam_kernel, dim3(grid_for(F * s.nseg, 256)), dim3(256), 0, c->stream, F, s.dp.block_len,
+                           s.idx, s.seg_blocks, s.nseg, bin_len, (const X3LevFrame*)w.frames, (const int32_t*)w.fst,
+                           (const X3FirEdge*)c->fir_ws.p, s.nseg, g.fir, d_levels);
+      });
+      break;
+    case LevSignal::DIFF:
+      run(X3LevDiff{}, X3LevDiff{}, w.tail, [&] {
+        if (F > 1)   // (one frame has no seam)
+          hipLaunchKernelGGL(x3_levels_seam_kernel, dim3(grid_for(F, 256)), dim3(256), 0, c->stream, s.d_x3, s.x3_len,
+                             s.d_frame_offsets, F, bin_len, (const X3LevFrame*)w.frames, (const int32_t*)w.fst,
+                             (const int32_t*)w.tail, d_levels);
+      });
+      break;
+    case LevSignal::SAMPLES: run(X3LevSamples{}, X3LevSamples{}, X3LevNoTail{}, no_seam); break;
+  }
+  HIPCHK(c, hipGetLastError());
+  c->levels.pending = true;
+  c->levels.count = F;
+  c->levels.sum_off = (size_t)((char*)w.sum - (char*)c->lev_ws.p);
+  return X3_OK;
+}
+
+// the stream form of the levels calls behind the check of the signal
 static int stream_levels_call(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
                               const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p, const uint64_t* d_seg_index,
                               uint32_t seg_blocks, uint64_t bin_len, x3_level* d_levels, uint64_t n_bins, int32_t* d_frame_status,
-                              int signal, const X3FirTaps* fir, const X3LevToneTail* tone = nullptr,
-                              const X3LevToneBankTail* bank = nullptr) {
-  if (!levels_args_ok(c, d_levels, n_bins, d_frame_status) || !levels_planes_ok(bank, n_bins)) return X3_ERR_BAD_ARG;
+                              const LevSignal& g) {
+  if (!levels_args_ok(c, d_levels, n_bins, d_frame_status) || !levels_planes_ok(g, n_bins)) return X3_ERR_BAD_ARG;
   FrameSource s;
   const int rc = stream_source(d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, p, d_seg_index, seg_blocks, &s);
   if (rc) return rc;
-  return levels_launch(c, s, bin_len, d_levels, n_bins, d_frame_status, 0, signal,
+  return levels_launch(c, s, bin_len, d_levels, n_bins, d_frame_status, 0, g,
                        [&](dim3 grid, unsigned long long*, const int32_t* fst, X3LevFrame* frames, uint32_t* cnt) {
                          hipLaunchKernelGGL(x3_levels_prep_kernel, grid, dim3(256), 0, c->stream, d_sample_offsets, n_frames,
                                             bin_len, n_bins, fst, frames, cnt);
-                       }, fir, tone, bank);
+                       });
 }
 
 extern "C" int x3_signal_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
@@ -1455,7 +1478,7 @@ extern "C" int x3_signal_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_
                                     uint64_t n_bins, int32_t* d_frame_status, int signal) {
   if (!c || !levels_signal_ok(signal)) return X3_ERR_BAD_ARG;
   return stream_levels_call(c, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, p, d_seg_index, seg_blocks, bin_len,
-                            d_levels, n_bins, d_frame_status, signal, nullptr);
+                            d_levels, n_bins, d_frame_status, LevSignal(signal));
 }
 
 extern "C" int x3_fir_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
@@ -1465,7 +1488,7 @@ extern "C" int x3_fir_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len
   X3FirTaps k;
   if (!c || !levels_fir_taps(fir, &k)) return X3_ERR_BAD_ARG;
   return stream_levels_call(c, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, p, d_seg_index, seg_blocks, bin_len,
-                            d_levels, n_bins, d_frame_status, X3_LEVEL_SIGNAL_SAMPLES, &k);
+                            d_levels, n_bins, d_frame_status, LevSignal(k));
 }
 
 extern "C" int x3_tone_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
@@ -1475,21 +1498,18 @@ extern "C" int x3_tone_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_le
   X3LevToneTail t;
   if (!c || !levels_tone_arg(tone, &t)) return X3_ERR_BAD_ARG;
   return stream_levels_call(c, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, p, d_seg_index, seg_blocks, bin_len,
-                            reinterpret_cast<x3_level*>(d_levels), n_bins, d_frame_status, X3_LEVEL_SIGNAL_SAMPLES, nullptr, &t);
+                            reinterpret_cast<x3_level*>(d_levels), n_bins, d_frame_status, LevSignal(t));
 }
 
-// the bank: n_tones tone calls plane by plane in one pass; one tone IS the tone call
+// the bank: n_tones tone calls plane by plane in one pass
 extern "C" int x3_tone_bank_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
                                        const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
                                        const uint64_t* d_seg_index, uint32_t seg_blocks, uint64_t bin_len, x3_tone_level* d_levels,
                                        uint64_t n_bins, int32_t* d_frame_status, const x3_level_tone_bank* bank) {
   X3LevToneBankTail t;
-  X3LevToneTail one;
-  if (!c || !levels_tone_bank_arg(bank, &t, &one)) return X3_ERR_BAD_ARG;
-  const bool single = t.n_tones == 1;
+  if (!c || !levels_tone_bank_arg(bank, &t)) return X3_ERR_BAD_ARG;
   return stream_levels_call(c, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, p, d_seg_index, seg_blocks, bin_len,
-                            reinterpret_cast<x3_level*>(d_levels), n_bins, d_frame_status, X3_LEVEL_SIGNAL_SAMPLES, nullptr,
-                            single ? &one : nullptr, single ? nullptr : &t);
+                            reinterpret_cast<x3_level*>(d_levels), n_bins, d_frame_status, LevSignal(t));
 }
 
 // the adapter: tone records -> the level records of the band (x3_tone_power_kernel); in place, or rows that do not overlap
@@ -2177,40 +2197,39 @@ static void corpus_row_prefix(x3_ctx* c, const x3_corpus* k, uint64_t bin_len, u
 }
 
 static int corpus_levels_call(x3_ctx* c, const x3_corpus* k, const char* entry, uint64_t bin_len, x3_level* d_levels,
-                              uint64_t n_rows, int32_t* d_frame_status, int signal, const X3FirTaps* fir = nullptr,
-                              const X3LevToneTail* tone = nullptr, const X3LevToneBankTail* bank = nullptr) {
-  if (!c || !k || !levels_signal_ok(signal) || !levels_args_ok(c, d_levels, n_rows, d_frame_status) || !levels_planes_ok(bank, n_rows))
-    return X3_ERR_BAD_ARG;
+                              uint64_t n_rows, int32_t* d_frame_status, const LevSignal& g) {
+  if (!c || !k || !levels_args_ok(c, d_levels, n_rows, d_frame_status) || !levels_planes_ok(g, n_rows)) return X3_ERR_BAD_ARG;
   FrameSource s;
   X3EvRows q;
   int rc;
   if ((rc = corpus_source(c, k, entry, &s))) return rc;
   if ((rc = corpus_rows(c, k, d_levels, n_rows, bin_len, entry, &q))) return rc;
-  return levels_launch(c, s, bin_len, d_levels, n_rows, d_frame_status, k->n, signal,
+  return levels_launch(c, s, bin_len, d_levels, n_rows, d_frame_status, k->n, g,
                        [&](dim3 grid, unsigned long long* row_first, const int32_t* fst, X3LevFrame* frames, uint32_t* cnt) {
                          corpus_row_prefix(c, k, bin_len, row_first);
                          hipLaunchKernelGGL(x3_corpus_levels_prep_kernel, grid, dim3(256), 0, c->stream,
                                             k->d_ent, k->n, (const unsigned long long*)row_first,
                                             s.d_sample_offsets, s.F, bin_len, n_rows, fst, frames, cnt);
-                       }, fir, tone, bank);
+                       });
 }
 
 extern "C" int x3_corpus_levels_dev(x3_ctx* c, const x3_corpus* k, uint64_t bin_len, x3_level* d_levels, uint64_t n_rows,
                                     int32_t* d_frame_status) {
-  return corpus_levels_call(c, k, "x3_corpus_levels_dev", bin_len, d_levels, n_rows, d_frame_status, X3_LEVEL_SIGNAL_SAMPLES);
+  return corpus_levels_call(c, k, "x3_corpus_levels_dev", bin_len, d_levels, n_rows, d_frame_status,
+                            LevSignal(X3_LEVEL_SIGNAL_SAMPLES));
 }
 
 extern "C" int x3_corpus_signal_levels_dev(x3_ctx* c, const x3_corpus* k, uint64_t bin_len, x3_level* d_levels, uint64_t n_rows,
                                            int32_t* d_frame_status, int signal) {
-  return corpus_levels_call(c, k, "x3_corpus_signal_levels_dev", bin_len, d_levels, n_rows, d_frame_status, signal);
+  if (!c || !levels_signal_ok(signal)) return X3_ERR_BAD_ARG;
+  return corpus_levels_call(c, k, "x3_corpus_signal_levels_dev", bin_len, d_levels, n_rows, d_frame_status, LevSignal(signal));
 }
 
 extern "C" int x3_corpus_fir_levels_dev(x3_ctx* c, const x3_corpus* k, uint64_t bin_len, x3_level* d_levels, uint64_t n_rows,
                                         int32_t* d_frame_status, const x3_level_fir* fir) {
   X3FirTaps taps;
   if (!c || !levels_fir_taps(fir, &taps)) return X3_ERR_BAD_ARG;
-  return corpus_levels_call(c, k, "x3_corpus_fir_levels_dev", bin_len, d_levels, n_rows, d_frame_status, X3_LEVEL_SIGNAL_SAMPLES,
-                            &taps);
+  return corpus_levels_call(c, k, "x3_corpus_fir_levels_dev", bin_len, d_levels, n_rows, d_frame_status, LevSignal(taps));
 }
 
 extern "C" int x3_corpus_tone_levels_dev(x3_ctx* c, const x3_corpus* k, uint64_t bin_len, x3_tone_level* d_levels, uint64_t n_rows,
@@ -2218,17 +2237,15 @@ extern "C" int x3_corpus_tone_levels_dev(x3_ctx* c, const x3_corpus* k, uint64_t
   X3LevToneTail t;
   if (!c || !levels_tone_arg(tone, &t)) return X3_ERR_BAD_ARG;
   return corpus_levels_call(c, k, "x3_corpus_tone_levels_dev", bin_len, reinterpret_cast<x3_level*>(d_levels), n_rows,
-                            d_frame_status, X3_LEVEL_SIGNAL_SAMPLES, nullptr, &t);
+                            d_frame_status, LevSignal(t));
 }
 
 extern "C" int x3_corpus_tone_bank_levels_dev(x3_ctx* c, const x3_corpus* k, uint64_t bin_len, x3_tone_level* d_levels,
                                               uint64_t n_rows, int32_t* d_frame_status, const x3_level_tone_bank* bank) {
   X3LevToneBankTail t;
-  X3LevToneTail one;
-  if (!c || !levels_tone_bank_arg(bank, &t, &one)) return X3_ERR_BAD_ARG;
-  const bool single = t.n_tones == 1;
+  if (!c || !levels_tone_bank_arg(bank, &t)) return X3_ERR_BAD_ARG;
   return corpus_levels_call(c, k, "x3_corpus_tone_bank_levels_dev", bin_len, reinterpret_cast<x3_level*>(d_levels), n_rows,
-                            d_frame_status, X3_LEVEL_SIGNAL_SAMPLES, nullptr, single ? &one : nullptr, single ? nullptr : &t);
+                            d_frame_status, LevSignal(t));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2566,33 +2583,26 @@ size_t range_levels_carve(char* base, uint64_t n, uint64_t F, uint64_t P, uint64
 }
 
 // The launch set of a range-levels call behind its plan step: plan(grid, plan, gstart, sum) enqueues the ranges' plan kernel
-// and returns the starts the later kernels read (the caller's, or the plan's gstart), as in windows_launch.  signal:
-// X3_LEVEL_SIGNAL_SAMPLES, or X3_LEVEL_SIGNAL_DIFF -- the lead kernel behind the plan (d_ent, n_ent, d_entries: the corpus's
-// table and the caller's entries, NULL for a stream), the other instance of the accumulate and fix-up kernels, which leave
-// every good frame's last sample in the workspace, and the seam kernel behind them.  fir (checked: levels_fir_taps) instead of
-// a signal (x3_fir_range_levels_dev / x3_corpus_fir_range_levels_dev): the lead kernel for T taps, the
-// X3RLevFir instance of the accumulate kernel, which leaves an edge record per (frame, stretch) in fir_ws as in levels_launch,
-// a fix-up of its own and x3_range_levels_fir_seam_kernel behind the merge.  The workspace is the DIFF call's (lead[]).
-// tone (checked: levels_tone_arg; starts: the CALLER'S array) instead of either (x3_tone_range_levels_dev /
-// x3_corpus_tone_range_levels_dev): the X3RLevTone instance of the accumulate and fix-up kernels and
-// nothing else -- no lead frame, no kernel behind the merge, the SAMPLES call's P and workspace.
+// and returns the starts the later kernels read (the caller's, or the plan's gstart), as in windows_launch.  d_starts: the
+// CALLER'S array, which the tone kernels read beside them.  d_ent, n_ent, d_entries: the corpus's table and the caller's
+// entries for the lead kernels, NULL for a stream.  g picks the lead kernel, the instance of the accumulate and fix-up
+// kernels and the seam kernel, in the switch below; DIFF and FIR share a workspace (tail[], lead[]), FIR leaves its edge
+// records in fir_ws as in levels_launch and has a fix-up of its own; TONE has the SAMPLES call's P and workspace.
 template <class Plan>
-static int range_levels_launch(x3_ctx* c, const FrameSource& s, const uint32_t* d_lens, uint64_t n, uint64_t bin_len,
-                               uint64_t row_stride, x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets,
-                               int32_t* d_status, int signal, const x3_corpus_entry* d_ent, uint64_t n_ent,
-                               const uint32_t* d_entries, Plan plan_step, const X3FirTaps* fir = nullptr,
-                               const X3RLevToneTail* tone = nullptr) {
-  const bool diff = !fir && !tone && signal == X3_LEVEL_SIGNAL_DIFF, lead = diff || fir;
-  const uint64_t lead_frames = fir ? fir->T - 1 : diff ? 1 : 0;   // what a range's plan may hold in front of its covering frames
+static int range_levels_launch(x3_ctx* c, const FrameSource& s, const uint64_t* d_starts, const uint32_t* d_lens, uint64_t n,
+                               uint64_t bin_len, uint64_t row_stride, x3_level* d_levels, uint64_t rows_cap,
+                               uint64_t* d_row_offsets, int32_t* d_status, const LevSignal& g, const x3_corpus_entry* d_ent,
+                               uint64_t n_ent, const uint32_t* d_entries, Plan plan_step) {
+  const uint64_t lead_frames = g.lead_frames();
   HIPCHK(c, hipSetDevice(c->device));
   const uint64_t P = range_levels_pairs(n, s.F, s.max_frames, lead_frames), cap = rows_cap + P;
   const uint32_t scratch_per = levels_scratch_per(s.dp.block_len);
   const uint64_t fix_waves = levels_fix_waves(n, scratch_per);
   RLevWs w;
   int rc;
-  if ((rc = ensure(c, c->rlev_ws, range_levels_carve(nullptr, n, s.F, P, rows_cap, fix_waves, scratch_per, &w, lead)))) return rc;
-  range_levels_carve((char*)c->rlev_ws.p, n, s.F, P, rows_cap, fix_waves, scratch_per, &w, lead);
-  if (fir && (rc = ensure(c, c->fir_ws, (size_t)(s.F * s.nseg) * sizeof(X3FirEdge)))) return rc;
+  if ((rc = ensure(c, c->rlev_ws, range_levels_carve(nullptr, n, s.F, P, rows_cap, fix_waves, scratch_per, &w, g.lead())))) return rc;
+  range_levels_carve((char*)c->rlev_ws.p, n, s.F, P, rows_cap, fix_waves, scratch_per, &w, g.lead());
+  if (g.fir_ws() && (rc = ensure(c, c->fir_ws, (size_t)(s.F * s.nseg) * sizeof(X3FirEdge)))) return rc;
   // grids: the counts are on the device and every kernel walks them grid-stride.  What a range has on average is at most
   // rows_cap / n rows (or the stride) of bin_len positions: the caller's words, possibly far above what is drawn, so a range
   // covers no more frames than the stream (or the longest entry) has and a call no more pairs than P.
@@ -2605,63 +2615,72 @@ static int range_levels_launch(x3_ctx* c, const FrameSource& s, const uint32_t* 
   const uint64_t drawn_rows = row_stride ? rows_hint
                               : bin_len && bin_len <= 0xFFFFFFFFull ? std::min(rows_hint, frames_per * (s.spf ? s.spf : 1) / bin_len + 1) : 1;
   const uint64_t rec_hint = std::min(n * drawn_rows, rows_cap);
-  const uint64_t* d_starts = plan_step(dim3(grid_for(n, 256)), w.plan, w.gstart, &w.sum->w);
-  if (diff)
-    hipLaunchKernelGGL(x3_range_levels_lead_kernel, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, s.d_sample_offsets, d_ent, n_ent,
-                       d_entries, d_starts, d_lens, n, w.plan, w.lead);
-  if (fir)
-    hipLaunchKernelGGL(x3_range_levels_fir_lead_kernel, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, s.d_sample_offsets, d_ent,
-                       n_ent, d_entries, d_starts, d_lens, n, (uint32_t)lead_frames, w.plan, w.lead);
-  hipLaunchKernelGGL(x3_range_levels_scan_kernel, dim3(1), dim3(1024), 0, c->stream, w.plan, n, d_lens, bin_len, row_stride, rows_cap,
-                     w.cov_off, w.row_off, w.erows, d_row_offsets, w.sum);
-  hipLaunchKernelGGL(x3_window_check_kernel, dim3(grid_for(cov_hint, 4)), dim3(256), 0, c->stream, s.d_x3, s.x3_len, s.d_frame_offsets,
-                     s.d_sample_offsets, (const X3WinPlan*)w.plan, n, (const unsigned long long*)w.cov_off, w.fst);
-  hipLaunchKernelGGL(x3_range_levels_prep_kernel, dim3(grid_for(std::max(cov_hint, rec_hint), 256)), dim3(256), 0, c->stream,
-                     s.d_sample_offsets, d_starts, d_lens, (const X3WinPlan*)w.plan, n, (const unsigned long long*)w.cov_off,
-                     (const unsigned long long*)w.row_off, (const uint32_t*)w.erows, bin_len, row_stride, rows_cap, P,
-                     (const int32_t*)w.fst, w.pairs, d_levels);
-  hipLaunchKernelGGL(x3_range_levels_pair_scan_kernel, dim3(1), dim3(1024), 0, c->stream, (const X3RLevPair*)w.pairs,
-                     (const unsigned long long*)w.cov_off, n, P, cap, w.prow, w.sum);
-  hipLaunchKernelGGL(x3_range_levels_init_kernel, dim3(grid_for(rec_hint + cov_hint, 256)), dim3(256), 0, c->stream,
-                     (const unsigned long long*)w.cov_off, n, P, cap, (const unsigned long long*)w.prow, w.rows);
-  auto decode = [&](auto sig, auto tail) {   // the two kernels that decode, for a signal
+  const uint64_t* d_gstarts = plan_step(dim3(grid_for(n, 256)), w.plan, w.gstart, &w.sum->w);
+  // everything behind the plan, for a signal: its lead kernel, the kernels all share, the two that decode, the merge, its seam
+  auto run = [&](auto lead, auto sig, auto tail, auto seam) {
     using Signal = decltype(sig);
+    lead();
+    hipLaunchKernelGGL(x3_range_levels_scan_kernel, dim3(1), dim3(1024), 0, c->stream, w.plan, n, d_lens, bin_len, row_stride, rows_cap,
+                       w.cov_off, w.row_off, w.erows, d_row_offsets, w.sum);
+    hipLaunchKernelGGL(x3_window_check_kernel, dim3(grid_for(cov_hint, 4)), dim3(256), 0, c->stream, s.d_x3, s.x3_len, s.d_frame_offsets,
+                       s.d_sample_offsets, (const X3WinPlan*)w.plan, n, (const unsigned long long*)w.cov_off, w.fst);
+    hipLaunchKernelGGL(x3_range_levels_prep_kernel, dim3(grid_for(std::max(cov_hint, rec_hint), 256)), dim3(256), 0, c->stream,
+                       s.d_sample_offsets, d_gstarts, d_lens, (const X3WinPlan*)w.plan, n, (const unsigned long long*)w.cov_off,
+                       (const unsigned long long*)w.row_off, (const uint32_t*)w.erows, bin_len, row_stride, rows_cap, P,
+                       (const int32_t*)w.fst, w.pairs, d_levels);
+    hipLaunchKernelGGL(x3_range_levels_pair_scan_kernel, dim3(1), dim3(1024), 0, c->stream, (const X3RLevPair*)w.pairs,
+                       (const unsigned long long*)w.cov_off, n, P, cap, w.prow, w.sum);
+    hipLaunchKernelGGL(x3_range_levels_init_kernel, dim3(grid_for(rec_hint + cov_hint, 256)), dim3(256), 0, c->stream,
+                       (const unsigned long long*)w.cov_off, n, P, cap, (const unsigned long long*)w.prow, w.rows);
     hipLaunchKernelGGL(x3_range_levels_accum_kernel<Signal>, dim3(grid_for(item_hint, 256)), dim3(256), 0, c->stream, s.d_x3, s.x3_len,
                        s.d_frame_offsets, s.dp, s.idx, s.seg_blocks, s.nseg, bin_len, (const unsigned long long*)w.cov_off, n, P, cap,
                        (const X3RLevPair*)w.pairs, (const unsigned long long*)w.prow, w.rows, w.fst, tail);
-    hipLaunchKernelGGL(x3_range_levels_fixup_kernel<Signal>, dim3((unsigned)((fix_waves + 3) / 4)), dim3(256), 0, c->stream, s.d_x3,
-                       s.d_frame_offsets, s.d_sample_offsets, d_starts, d_lens, (const X3WinPlan*)w.plan, n, s.dp, bin_len,
-                       (const unsigned long long*)w.cov_off, (const unsigned long long*)w.row_off, (const uint32_t*)w.erows,
-                       row_stride, P, cap, (const unsigned long long*)w.prow, (const int32_t*)w.fst, d_levels, d_status, w.scratch,
-                       scratch_per, w.sum, tail, (const uint32_t*)w.lead);
+    auto fixup = [&](auto* kernel, auto... seg) {   // seg: what the FIR call's fix-up takes behind s.dp
+      hipLaunchKernelGGL(kernel, dim3((unsigned)((fix_waves + 3) / 4)), dim3(256), 0, c->stream, s.d_x3, s.d_frame_offsets,
+                         s.d_sample_offsets, d_gstarts, d_lens, (const X3WinPlan*)w.plan, n, s.dp, seg..., bin_len,
+                         (const unsigned long long*)w.cov_off, (const unsigned long long*)w.row_off, (const uint32_t*)w.erows,
+                         row_stride, P, cap, (const unsigned long long*)w.prow, (const int32_t*)w.fst, d_levels, d_status, w.scratch,
+                         scratch_per, w.sum, tail, (const uint32_t*)w.lead);
+    };
+    if constexpr (std::is_same_v<Signal, X3RLevFir>) fixup(x3_range_levels_fir_fixup_kernel, s.idx, s.seg_blocks, s.nseg);
+    else fixup(x3_range_levels_fixup_kernel<Signal>);
+    hipLaunchKernelGGL(x3_range_levels_merge_kernel, dim3(grid_for(rec_hint + cov_hint, 256)), dim3(256), 0, c->stream,
+                       (const X3RLevPair*)w.pairs, (const unsigned long long*)w.cov_off, n, P, cap, (const unsigned long long*)w.prow,
+                       (const unsigned long long*)w.row_off, (const uint32_t*)w.erows, row_stride, (const x3_level*)w.rows,
+                       (const int32_t*)w.fst, d_levels);
+    if (g.seam()) seam();
   };
-  if (fir) {
-    const X3LevFirTail ft{*fir, (X3FirEdge*)c->fir_ws.p, s.nseg};
-    hipLaunchKernelGGL(x3_range_levels_accum_kernel<X3RLevFir>, dim3(grid_for(item_hint, 256)), dim3(256), 0, c->stream, s.d_x3,
-                       s.x3_len, s.d_frame_offsets, s.dp, s.idx, s.seg_blocks, s.nseg, bin_len, (const unsigned long long*)w.cov_off, n,
-                       P, cap, (const X3RLevPair*)w.pairs, (const unsigned long long*)w.prow, w.rows, w.fst, ft);
-    hipLaunchKernelGGL(x3_range_levels_fir_fixup_kernel, dim3((unsigned)((fix_waves + 3) / 4)), dim3(256), 0, c->stream, s.d_x3,
-                       s.d_frame_offsets, s.d_sample_offsets, d_starts, d_lens, (const X3WinPlan*)w.plan, n, s.dp, s.idx, s.seg_blocks,
-                       s.nseg, bin_len, (const unsigned long long*)w.cov_off, (const unsigned long long*)w.row_off,
-                       (const uint32_t*)w.erows, row_stride, P, cap, (const unsigned long long*)w.prow, (const int32_t*)w.fst,
-                       d_levels, d_status, w.scratch, scratch_per, w.sum, ft, (const uint32_t*)w.lead);
-  } else if (tone) decode(X3RLevTone{}, *tone);
-  else if (diff) decode(X3LevDiff{}, w.tail);
-  else decode(X3LevSamples{}, X3LevNoTail{});
-  hipLaunchKernelGGL(x3_range_levels_merge_kernel, dim3(grid_for(rec_hint + cov_hint, 256)), dim3(256), 0, c->stream,
-                     (const X3RLevPair*)w.pairs, (const unsigned long long*)w.cov_off, n, P, cap, (const unsigned long long*)w.prow,
-                     (const unsigned long long*)w.row_off, (const uint32_t*)w.erows, row_stride, (const x3_level*)w.rows,
-                     (const int32_t*)w.fst, d_levels);
-  if (diff)
-    hipLaunchKernelGGL(x3_range_levels_seam_kernel, dim3(grid_for(cov_hint, 256)), dim3(256), 0, c->stream, s.d_x3, s.x3_len,
-                       s.d_frame_offsets, bin_len, (const X3RLevPair*)w.pairs, (const unsigned long long*)w.cov_off, n, P, cap,
-                       (const unsigned long long*)w.prow, (const unsigned long long*)w.row_off, (const uint32_t*)w.erows, row_stride,
-                       (const int32_t*)w.fst, (const int32_t*)w.tail, d_levels);
-  if (fir && fir->T > 1)
-    hipLaunchKernelGGL(x3_range_levels_fir_seam_kernel, dim3(grid_for(item_hint, 256)), dim3(256), 0, c->stream, s.dp.block_len, s.idx,
-                       s.seg_blocks, s.nseg, bin_len, (const X3RLevPair*)w.pairs, (const unsigned long long*)w.cov_off, n, P, cap,
-                       (const unsigned long long*)w.prow, (const unsigned long long*)w.row_off, (const uint32_t*)w.erows, row_stride,
-                       (const int32_t*)w.fst, (const X3FirEdge*)c->fir_ws.p, s.nseg, *fir, d_levels);
+  auto none = [] {};
+  switch (g.kind) {
+    case LevSignal::FIR:
+      run([&] {
+            hipLaunchKernelGGL(x3_range_levels_fir_lead_kernel, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, s.d_sample_offsets,
+                               d_ent, n_ent, d_entries, d_gstarts, d_lens, n, (uint32_t)lead_frames, w.plan, w.lead);
+          },
+          X3RLevFir{}, X3LevFirTail{g.fir, (X3FirEdge*)c->fir_ws.p, s.nseg}, [&] {
+            hipLaunchKernelGGL(x3_range_levels_fir_seam_kernel, dim3(grid_for(item_hint, 256)), dim3(256), 0, c->stream,
+                               s.dp.block_len, s.idx, s.seg_blocks, s.nseg, bin_len, (const X3RLevPair*)w.pairs,
+                               (const unsigned long long*)w.cov_off, n, P, cap, (const unsigned long long*)w.prow,
+                               (const unsigned long long*)w.row_off, (const uint32_t*)w.erows, row_stride, (const int32_t*)w.fst,
+                               (const X3FirEdge*)c->fir_ws.p, s.nseg, g.fir, d_levels);
+          });
+      break;
+    case LevSignal::TONE: run(none, X3RLevTone{}, X3RLevToneTail{g.tone.table, g.tone.step, d_starts}, none); break;
+    case LevSignal::DIFF:
+      run([&] {
+            hipLaunchKernelGGL(x3_range_levels_lead_kernel, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, s.d_sample_offsets, d_ent,
+                               n_ent, d_entries, d_gstarts, d_lens, n, w.plan, w.lead);
+          },
+          X3LevDiff{}, w.tail, [&] {
+            hipLaunchKernelGGL(x3_range_levels_seam_kernel, dim3(grid_for(cov_hint, 256)), dim3(256), 0, c->stream, s.d_x3, s.x3_len,
+                               s.d_frame_offsets, bin_len, (const X3RLevPair*)w.pairs, (const unsigned long long*)w.cov_off, n, P, cap,
+                               (const unsigned long long*)w.prow, (const unsigned long long*)w.row_off, (const uint32_t*)w.erows,
+                               row_stride, (const int32_t*)w.fst, (const int32_t*)w.tail, d_levels);
+          });
+      break;
+    case LevSignal::SAMPLES: run(none, X3LevSamples{}, X3LevNoTail{}, none); break;
+    case LevSignal::BANK: return X3_ERR_BAD_ARG;   // (no entry point builds it: DESIGN.md section 26)
+  }
   HIPCHK(c, hipGetLastError());
   c->range_levels.pending = true;
   c->range_levels.count = n;
@@ -2669,27 +2688,25 @@ static int range_levels_launch(x3_ctx* c, const FrameSource& s, const uint32_t* 
   return X3_OK;
 }
 
-// the stream form of the range-levels calls behind the check of the signal, the taps (fir != NULL: the FIR call) or the
-// oscillator (tone != NULL: the tone call)
+// the stream form of the range-levels calls behind the check of the signal
 static int stream_range_levels_call(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
                                     const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
                                     const uint64_t* d_seg_index, uint32_t seg_blocks, const uint64_t* d_starts,
                                     const uint32_t* d_lens, uint64_t n_ranges, uint64_t bin_len, uint64_t row_stride,
-                                    x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status, int signal,
-                                    const X3FirTaps* fir, const X3LevToneTail* tone = nullptr) {
+                                    x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status,
+                                    const LevSignal& g) {
   if (!range_levels_args_ok(c, d_starts, d_lens, n_ranges, row_stride, d_levels, rows_cap, d_row_offsets, d_status))
     return X3_ERR_BAD_ARG;
   FrameSource s;
   const int rc = stream_source(d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, p, d_seg_index, seg_blocks, &s);
   if (rc) return rc;
-  const X3RLevToneTail tt{tone ? tone->table : nullptr, tone ? tone->step : 0u, d_starts};
-  return range_levels_launch(c, s, d_lens, n_ranges, bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status, signal,
+  return range_levels_launch(c, s, d_starts, d_lens, n_ranges, bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status, g,
                              nullptr, 0, nullptr,
                              [&](dim3 grid, X3WinPlan* plan, uint64_t*, X3WinSummary* sum) -> const uint64_t* {
                                hipLaunchKernelGGL(x3_range_plan_kernel, grid, dim3(256), 0, c->stream, d_sample_offsets, n_frames,
                                                   d_starts, d_lens, n_ranges, plan, sum);
                                return d_starts;
-                             }, fir, tone ? &tt : nullptr);
+                             });
 }
 
 extern "C" int x3_signal_range_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
@@ -2700,7 +2717,8 @@ extern "C" int x3_signal_range_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64
                                           int signal) {
   if (!c || !levels_signal_ok(signal)) return X3_ERR_BAD_ARG;
   return stream_range_levels_call(c, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, p, d_seg_index, seg_blocks, d_starts,
-                                  d_lens, n_ranges, bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status, signal, nullptr);
+                                  d_lens, n_ranges, bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status,
+                                  LevSignal(signal));
 }
 
 extern "C" int x3_fir_range_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
@@ -2712,8 +2730,7 @@ extern "C" int x3_fir_range_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t 
   X3FirTaps k;
   if (!c || !levels_fir_taps(fir, &k)) return X3_ERR_BAD_ARG;
   return stream_range_levels_call(c, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, p, d_seg_index, seg_blocks, d_starts,
-                                  d_lens, n_ranges, bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status,
-                                  X3_LEVEL_SIGNAL_SAMPLES, &k);
+                                  d_lens, n_ranges, bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status, LevSignal(k));
 }
 
 extern "C" int x3_tone_range_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
@@ -2726,7 +2743,7 @@ extern "C" int x3_tone_range_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t
   if (!c || !levels_tone_arg(tone, &t)) return X3_ERR_BAD_ARG;
   return stream_range_levels_call(c, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, p, d_seg_index, seg_blocks, d_starts,
                                   d_lens, n_ranges, bin_len, row_stride, reinterpret_cast<x3_level*>(d_levels), rows_cap,
-                                  d_row_offsets, d_status, X3_LEVEL_SIGNAL_SAMPLES, nullptr, &t);
+                                  d_row_offsets, d_status, LevSignal(t));
 }
 
 extern "C" int x3_range_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
@@ -2739,42 +2756,41 @@ extern "C" int x3_range_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_l
                                     X3_LEVEL_SIGNAL_SAMPLES);
 }
 
-// (entry: the name errors carry -- the call the caller made)
+// (entry: the name errors carry -- the call the caller made; d_starts are entry-relative)
 static int corpus_range_levels_call(x3_ctx* c, const x3_corpus* k, const char* entry, const uint32_t* d_entries,
                                     const uint64_t* d_starts, const uint32_t* d_lens, uint64_t n_ranges, uint64_t bin_len,
                                     uint64_t row_stride, x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets,
-                                    int32_t* d_status, int signal, const X3FirTaps* fir = nullptr,
-                                    const X3LevToneTail* tone = nullptr) {
-  if (!c || !levels_signal_ok(signal) || !k || !d_entries || (reinterpret_cast<uintptr_t>(d_entries) & 3u)) return X3_ERR_BAD_ARG;
+                                    int32_t* d_status, const LevSignal& g) {
+  if (!c || !k || !d_entries || (reinterpret_cast<uintptr_t>(d_entries) & 3u)) return X3_ERR_BAD_ARG;
   if (!range_levels_args_ok(c, d_starts, d_lens, n_ranges, row_stride, d_levels, rows_cap, d_row_offsets, d_status))
     return X3_ERR_BAD_ARG;
   FrameSource s;
   const int rc = corpus_source(c, k, entry, &s);
   if (rc) return rc;
-  const X3RLevToneTail tt{tone ? tone->table : nullptr, tone ? tone->step : 0u, d_starts};   // (entry-relative: the caller's)
-  return range_levels_launch(c, s, d_lens, n_ranges, bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status, signal,
+  return range_levels_launch(c, s, d_starts, d_lens, n_ranges, bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status, g,
                              (const x3_corpus_entry*)k->d_ent, k->n, d_entries,
                              [&](dim3 grid, X3WinPlan* plan, uint64_t* gstart, X3WinSummary* sum) -> const uint64_t* {
                                hipLaunchKernelGGL(x3_corpus_range_plan_kernel, grid, dim3(256), 0, c->stream, k->d_ent, k->n,
                                                   s.d_sample_offsets, s.F, d_entries, d_starts, d_lens, n_ranges, plan, gstart,
                                                   sum);
                                return gstart;
-                             }, fir, tone ? &tt : nullptr);
+                             });
 }
 
 extern "C" int x3_corpus_range_levels_dev(x3_ctx* c, const x3_corpus* k, const uint32_t* d_entries, const uint64_t* d_starts,
                                           const uint32_t* d_lens, uint64_t n_ranges, uint64_t bin_len, uint64_t row_stride,
                                           x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status) {
   return corpus_range_levels_call(c, k, "x3_corpus_range_levels_dev", d_entries, d_starts, d_lens, n_ranges, bin_len, row_stride,
-                                  d_levels, rows_cap, d_row_offsets, d_status, X3_LEVEL_SIGNAL_SAMPLES);
+                                  d_levels, rows_cap, d_row_offsets, d_status, LevSignal(X3_LEVEL_SIGNAL_SAMPLES));
 }
 
 extern "C" int x3_corpus_signal_range_levels_dev(x3_ctx* c, const x3_corpus* k, const uint32_t* d_entries, const uint64_t* d_starts,
                                                  const uint32_t* d_lens, uint64_t n_ranges, uint64_t bin_len, uint64_t row_stride,
                                                  x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status,
                                                  int signal) {
+  if (!c || !levels_signal_ok(signal)) return X3_ERR_BAD_ARG;
   return corpus_range_levels_call(c, k, "x3_corpus_signal_range_levels_dev", d_entries, d_starts, d_lens, n_ranges, bin_len,
-                                  row_stride, d_levels, rows_cap, d_row_offsets, d_status, signal);
+                                  row_stride, d_levels, rows_cap, d_row_offsets, d_status, LevSignal(signal));
 }
 
 extern "C" int x3_corpus_fir_range_levels_dev(x3_ctx* c, const x3_corpus* k, const uint32_t* d_entries, const uint64_t* d_starts,
@@ -2784,7 +2800,7 @@ extern "C" int x3_corpus_fir_range_levels_dev(x3_ctx* c, const x3_corpus* k, con
   X3FirTaps taps;
   if (!c || !levels_fir_taps(fir, &taps)) return X3_ERR_BAD_ARG;
   return corpus_range_levels_call(c, k, "x3_corpus_fir_range_levels_dev", d_entries, d_starts, d_lens, n_ranges, bin_len, row_stride,
-                                  d_levels, rows_cap, d_row_offsets, d_status, X3_LEVEL_SIGNAL_SAMPLES, &taps);
+                                  d_levels, rows_cap, d_row_offsets, d_status, LevSignal(taps));
 }
 
 extern "C" int x3_corpus_tone_range_levels_dev(x3_ctx* c, const x3_corpus* k, const uint32_t* d_entries, const uint64_t* d_starts,
@@ -2794,8 +2810,7 @@ extern "C" int x3_corpus_tone_range_levels_dev(x3_ctx* c, const x3_corpus* k, co
   X3LevToneTail t;
   if (!c || !levels_tone_arg(tone, &t)) return X3_ERR_BAD_ARG;
   return corpus_range_levels_call(c, k, "x3_corpus_tone_range_levels_dev", d_entries, d_starts, d_lens, n_ranges, bin_len, row_stride,
-                                  reinterpret_cast<x3_level*>(d_levels), rows_cap, d_row_offsets, d_status, X3_LEVEL_SIGNAL_SAMPLES,
-                                  nullptr, &t);
+                                  reinterpret_cast<x3_level*>(d_levels), rows_cap, d_row_offsets, d_status, LevSignal(t));
 }
 
 extern "C" int x3_range_levels_result(x3_ctx* c, uint64_t* n_bad, uint64_t* first_bad, int* first_bad_status,

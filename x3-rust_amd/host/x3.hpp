@@ -769,6 +769,39 @@ inline X3Error decode_ranges(Context& ctx, const EncodedStream& s, const Paramet
   return static_cast<X3Error>(rc);
 }
 
+struct RangeLevelsResult : WindowsResult {   // (device::range_levels, below)
+  uint64_t total_rows = 0;
+};
+
+namespace detail {
+// the second half of every levels and range-levels wrapper: rc is the call's; on X3_OK waits for its result into *res
+inline X3Error levels_result(Context& ctx, int rc, WindowsResult* res) {
+  if (rc != X3_OK) return static_cast<X3Error>(rc);
+  WindowsResult r;
+  rc = x3_levels_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status);
+  if (res) *res = r;
+  return static_cast<X3Error>(rc);
+}
+inline X3Error levels_result(Context& ctx, int rc, RangeLevelsResult* res) {
+  if (rc != X3_OK) return static_cast<X3Error>(rc);
+  RangeLevelsResult r;
+  rc = x3_range_levels_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status, &r.total_rows);
+  if (res) *res = r;
+  return static_cast<X3Error>(rc);
+}
+// the stream forms: call(the nine arguments every stream entry point begins with) -> rc, then levels_result
+template <class Result, class Call>
+X3Error stream_levels(Context& ctx, const EncodedStream& s, const Parameters& params, const Buffer& d_sample_offsets, Result* res,
+                      Call call) {
+  if (!s.bytes.ok() || !s.frame_offsets.ok() || !d_sample_offsets.ok()) return X3Error::BadArg;
+  const x3_params c = params.c_params();
+  return levels_result(ctx,
+                       call(ctx.raw(), s.bytes.as<uint8_t>(), s.len, s.frame_offsets.as<uint64_t>(), d_sample_offsets.as<uint64_t>(),
+                            s.n_frames, &c, s.seg_blocks ? s.seg_index.as<uint64_t>() : nullptr, s.seg_blocks),
+                       res);
+}
+}   // namespace detail
+
 // Levels (x3_levels_dev): min, max, count, sum and sum of squares of the samples per bin of bin_len positions (0: one bin),
 // n_bins records in d_levels, every one written; d_frame_status (n_frames int32, may be nullptr): a frame with a status
 // other than 0 adds nothing.  No sample buffer.  Waits for the call: res = frames with status != 0, the first, its status.
@@ -779,16 +812,9 @@ enum class LevelSignal : int { Samples = X3_LEVEL_SIGNAL_SAMPLES, Diff = X3_LEVE
 inline X3Error levels(Context& ctx, const EncodedStream& s, const Parameters& params, const Buffer& d_sample_offsets,
                       uint64_t bin_len, x3_level* d_levels, uint64_t n_bins, int32_t* d_frame_status, WindowsResult* res,
                       LevelSignal signal = LevelSignal::Samples) {
-  if (!s.bytes.ok() || !s.frame_offsets.ok() || !d_sample_offsets.ok()) return X3Error::BadArg;
-  const x3_params c = params.c_params();
-  int rc = x3_signal_levels_dev(ctx.raw(), s.bytes.as<uint8_t>(), s.len, s.frame_offsets.as<uint64_t>(),
-                                d_sample_offsets.as<uint64_t>(), s.n_frames, &c, s.seg_blocks ? s.seg_index.as<uint64_t>() : nullptr,
-                                s.seg_blocks, bin_len, d_levels, n_bins, d_frame_status, static_cast<int>(signal));
-  if (rc != X3_OK) return static_cast<X3Error>(rc);
-  WindowsResult r;
-  rc = x3_levels_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status);
-  if (res) *res = r;
-  return static_cast<X3Error>(rc);
+  return detail::stream_levels(ctx, s, params, d_sample_offsets, res, [&](auto... st) {
+    return x3_signal_levels_dev(st..., bin_len, d_levels, n_bins, d_frame_status, static_cast<int>(signal));
+  });
 }
 
 // An integer FIR filter in front of the levels (x3_fir_levels_dev): y[i] = clamp((sum over t of taps[t] * x[i - t]) >> shift,
@@ -809,17 +835,10 @@ struct Fir {
 inline X3Error levels(Context& ctx, const EncodedStream& s, const Parameters& params, const Buffer& d_sample_offsets,
                       uint64_t bin_len, x3_level* d_levels, uint64_t n_bins, int32_t* d_frame_status, WindowsResult* res,
                       const Fir& fir) {
-  if (!s.bytes.ok() || !s.frame_offsets.ok() || !d_sample_offsets.ok()) return X3Error::BadArg;
-  const x3_params c = params.c_params();
   const x3_level_fir f = fir.c_fir();
-  int rc = x3_fir_levels_dev(ctx.raw(), s.bytes.as<uint8_t>(), s.len, s.frame_offsets.as<uint64_t>(),
-                             d_sample_offsets.as<uint64_t>(), s.n_frames, &c, s.seg_blocks ? s.seg_index.as<uint64_t>() : nullptr,
-                             s.seg_blocks, bin_len, d_levels, n_bins, d_frame_status, &f);
-  if (rc != X3_OK) return static_cast<X3Error>(rc);
-  WindowsResult r;
-  rc = x3_levels_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status);
-  if (res) *res = r;
-  return static_cast<X3Error>(rc);
+  return detail::stream_levels(ctx, s, params, d_sample_offsets, res, [&](auto... st) {
+    return x3_fir_levels_dev(st..., bin_len, d_levels, n_bins, d_frame_status, &f);
+  });
 }
 
 // One oscillator in front of the levels (x3_level_tone): position i has the phase (i * step) mod 2^32, and a bin's record
@@ -845,17 +864,10 @@ struct Tone {
 inline X3Error tone_levels(Context& ctx, const EncodedStream& s, const Parameters& params, const Buffer& d_sample_offsets,
                            uint64_t bin_len, x3_tone_level* d_levels, uint64_t n_bins, int32_t* d_frame_status,
                            WindowsResult* res, const Tone& tone) {
-  if (!s.bytes.ok() || !s.frame_offsets.ok() || !d_sample_offsets.ok()) return X3Error::BadArg;
-  const x3_params c = params.c_params();
   const x3_level_tone t = tone.c_tone();
-  int rc = x3_tone_levels_dev(ctx.raw(), s.bytes.as<uint8_t>(), s.len, s.frame_offsets.as<uint64_t>(),
-                              d_sample_offsets.as<uint64_t>(), s.n_frames, &c, s.seg_blocks ? s.seg_index.as<uint64_t>() : nullptr,
-                              s.seg_blocks, bin_len, d_levels, n_bins, d_frame_status, &t);
-  if (rc != X3_OK) return static_cast<X3Error>(rc);
-  WindowsResult r;
-  rc = x3_levels_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status);
-  if (res) *res = r;
-  return static_cast<X3Error>(rc);
+  return detail::stream_levels(ctx, s, params, d_sample_offsets, res, [&](auto... st) {
+    return x3_tone_levels_dev(st..., bin_len, d_levels, n_bins, d_frame_status, &t);
+  });
 }
 
 // Up to X3_TONE_BANK_MAX oscillators against one table in one pass (x3_level_tone_bank): plane t of the records is what
@@ -876,17 +888,11 @@ struct ToneBank {
 inline X3Error tone_bank_levels(Context& ctx, const EncodedStream& s, const Parameters& params, const Buffer& d_sample_offsets,
                                 uint64_t bin_len, x3_tone_level* d_levels, uint64_t n_bins, int32_t* d_frame_status,
                                 WindowsResult* res, const ToneBank& bank) {
-  if (!s.bytes.ok() || !s.frame_offsets.ok() || !d_sample_offsets.ok() || !bank.ok()) return X3Error::BadArg;
-  const x3_params c = params.c_params();
+  if (!bank.ok()) return X3Error::BadArg;
   const x3_level_tone_bank b = bank.c_bank();
-  int rc = x3_tone_bank_levels_dev(ctx.raw(), s.bytes.as<uint8_t>(), s.len, s.frame_offsets.as<uint64_t>(),
-                                   d_sample_offsets.as<uint64_t>(), s.n_frames, &c, s.seg_blocks ? s.seg_index.as<uint64_t>() : nullptr,
-                                   s.seg_blocks, bin_len, d_levels, n_bins, d_frame_status, &b);
-  if (rc != X3_OK) return static_cast<X3Error>(rc);
-  WindowsResult r;
-  rc = x3_levels_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status);
-  if (res) *res = r;
-  return static_cast<X3Error>(rc);
+  return detail::stream_levels(ctx, s, params, d_sample_offsets, res, [&](auto... st) {
+    return x3_tone_bank_levels_dev(st..., bin_len, d_levels, n_bins, d_frame_status, &b);
+  });
 }
 
 // The adapter into the chain (x3_tone_power_levels_dev): n_rows tone records -> the level records of the band, which
@@ -960,25 +966,14 @@ inline X3Error events_adaptive(Context& ctx, const x3_level* d_levels, uint64_t 
 // arrays device::events wrote go in as they are.  Waits for the call: res = ranges with status != 0, the first, its status,
 // and the sum of all row counts.  signal (x3_signal_range_levels_dev): LevelSignal::Diff gives the records of the stream's
 // first difference cut to the ranges -- the difference at a range's first position counts, statuses are the Samples form's.
-struct RangeLevelsResult : WindowsResult {
-  uint64_t total_rows = 0;
-};
 inline X3Error range_levels(Context& ctx, const EncodedStream& s, const Parameters& params, const Buffer& d_sample_offsets,
                             const uint64_t* d_starts, const uint32_t* d_lens, size_t n_ranges, uint64_t bin_len,
                             uint64_t row_stride, x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status,
                             RangeLevelsResult* res, LevelSignal signal = LevelSignal::Samples) {
-  if (!s.bytes.ok() || !s.frame_offsets.ok() || !d_sample_offsets.ok()) return X3Error::BadArg;
-  const x3_params c = params.c_params();
-  int rc = x3_signal_range_levels_dev(ctx.raw(), s.bytes.as<uint8_t>(), s.len, s.frame_offsets.as<uint64_t>(),
-                                      d_sample_offsets.as<uint64_t>(), s.n_frames, &c,
-                                      s.seg_blocks ? s.seg_index.as<uint64_t>() : nullptr, s.seg_blocks, d_starts, d_lens,
-                                      n_ranges, bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status,
-                                      static_cast<int>(signal));
-  if (rc != X3_OK) return static_cast<X3Error>(rc);
-  RangeLevelsResult r;
-  rc = x3_range_levels_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status, &r.total_rows);
-  if (res) *res = r;
-  return static_cast<X3Error>(rc);
+  return detail::stream_levels(ctx, s, params, d_sample_offsets, res, [&](auto... st) {
+    return x3_signal_range_levels_dev(st..., d_starts, d_lens, n_ranges, bin_len, row_stride, d_levels, rows_cap, d_row_offsets,
+                                      d_status, static_cast<int>(signal));
+  });
 }
 // FIR range levels (x3_fir_range_levels_dev): range_levels of the stream's FIR signal (device::levels with a Fir) cut to the
 // ranges -- the call cuts the filtered stream, it does not filter the cut: a range's first T - 1 positions count, their
@@ -987,18 +982,11 @@ inline X3Error fir_range_levels(Context& ctx, const EncodedStream& s, const Para
                                 const uint64_t* d_starts, const uint32_t* d_lens, size_t n_ranges, uint64_t bin_len,
                                 uint64_t row_stride, x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets,
                                 int32_t* d_status, const Fir& fir, RangeLevelsResult* res) {
-  if (!s.bytes.ok() || !s.frame_offsets.ok() || !d_sample_offsets.ok()) return X3Error::BadArg;
-  const x3_params c = params.c_params();
   const x3_level_fir f = fir.c_fir();
-  int rc = x3_fir_range_levels_dev(ctx.raw(), s.bytes.as<uint8_t>(), s.len, s.frame_offsets.as<uint64_t>(),
-                                   d_sample_offsets.as<uint64_t>(), s.n_frames, &c,
-                                   s.seg_blocks ? s.seg_index.as<uint64_t>() : nullptr, s.seg_blocks, d_starts, d_lens, n_ranges,
-                                   bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status, &f);
-  if (rc != X3_OK) return static_cast<X3Error>(rc);
-  RangeLevelsResult r;
-  rc = x3_range_levels_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status, &r.total_rows);
-  if (res) *res = r;
-  return static_cast<X3Error>(rc);
+  return detail::stream_levels(ctx, s, params, d_sample_offsets, res, [&](auto... st) {
+    return x3_fir_range_levels_dev(st..., d_starts, d_lens, n_ranges, bin_len, row_stride, d_levels, rows_cap, d_row_offsets,
+                                   d_status, &f);
+  });
 }
 // Tone range levels (x3_tone_range_levels_dev): range_levels with tone records, the stream's tone signal (device::tone_levels)
 // cut to the ranges -- the call cuts the stream's signal, it does not restart the oscillator: position i of the stream has the
@@ -1009,18 +997,11 @@ inline X3Error tone_range_levels(Context& ctx, const EncodedStream& s, const Par
                                  const uint64_t* d_starts, const uint32_t* d_lens, size_t n_ranges, uint64_t bin_len,
                                  uint64_t row_stride, x3_tone_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets,
                                  int32_t* d_status, const Tone& tone, RangeLevelsResult* res) {
-  if (!s.bytes.ok() || !s.frame_offsets.ok() || !d_sample_offsets.ok()) return X3Error::BadArg;
-  const x3_params c = params.c_params();
   const x3_level_tone t = tone.c_tone();
-  int rc = x3_tone_range_levels_dev(ctx.raw(), s.bytes.as<uint8_t>(), s.len, s.frame_offsets.as<uint64_t>(),
-                                    d_sample_offsets.as<uint64_t>(), s.n_frames, &c,
-                                    s.seg_blocks ? s.seg_index.as<uint64_t>() : nullptr, s.seg_blocks, d_starts, d_lens, n_ranges,
-                                    bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status, &t);
-  if (rc != X3_OK) return static_cast<X3Error>(rc);
-  RangeLevelsResult r;
-  rc = x3_range_levels_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status, &r.total_rows);
-  if (res) *res = r;
-  return static_cast<X3Error>(rc);
+  return detail::stream_levels(ctx, s, params, d_sample_offsets, res, [&](auto... st) {
+    return x3_tone_range_levels_dev(st..., d_starts, d_lens, n_ranges, bin_len, row_stride, d_levels, rows_cap, d_row_offsets,
+                                    d_status, &t);
+  });
 }
 
 // A batch of independent streams (x3_decode_streams_dev): entry s = bytes [offsets[s], offsets[s] + lengths[s]) of d_x3 (flags:
@@ -1115,36 +1096,24 @@ class Corpus {
   }
   X3Error levels(Context& ctx, uint64_t bin_len, x3_level* d_levels, uint64_t n_rows, int32_t* d_frame_status,
                  WindowsResult* res, LevelSignal signal = LevelSignal::Samples) const {
-    int rc = x3_corpus_signal_levels_dev(ctx.raw(), raw_, bin_len, d_levels, n_rows, d_frame_status, static_cast<int>(signal));
-    if (rc != X3_OK) return static_cast<X3Error>(rc);
-    WindowsResult r;
-    rc = x3_levels_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status);
-    if (res) *res = r;
-    return static_cast<X3Error>(rc);
+    return detail::levels_result(ctx, x3_corpus_signal_levels_dev(ctx.raw(), raw_, bin_len, d_levels, n_rows, d_frame_status,
+                                  static_cast<int>(signal)), res);
   }
   // ... behind an integer FIR filter (x3_corpus_fir_levels_dev): as device::levels with a Fir; no history crosses from one
   // entry into the next.
   X3Error levels(Context& ctx, uint64_t bin_len, x3_level* d_levels, uint64_t n_rows, int32_t* d_frame_status,
                  WindowsResult* res, const Fir& fir) const {
     const x3_level_fir f = fir.c_fir();
-    int rc = x3_corpus_fir_levels_dev(ctx.raw(), raw_, bin_len, d_levels, n_rows, d_frame_status, &f);
-    if (rc != X3_OK) return static_cast<X3Error>(rc);
-    WindowsResult r;
-    rc = x3_levels_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status);
-    if (res) *res = r;
-    return static_cast<X3Error>(rc);
+    return detail::levels_result(ctx, x3_corpus_fir_levels_dev(ctx.raw(), raw_, bin_len, d_levels, n_rows, d_frame_status, &f),
+                                  res);
   }
   // Tone levels of every entry (x3_corpus_tone_levels_dev): levels()' rows as tone records; the phase restarts at 0 with
   // every entry.  Waits for the call.
   X3Error tone_levels(Context& ctx, uint64_t bin_len, x3_tone_level* d_levels, uint64_t n_rows, int32_t* d_frame_status,
                       WindowsResult* res, const Tone& tone) const {
     const x3_level_tone t = tone.c_tone();
-    int rc = x3_corpus_tone_levels_dev(ctx.raw(), raw_, bin_len, d_levels, n_rows, d_frame_status, &t);
-    if (rc != X3_OK) return static_cast<X3Error>(rc);
-    WindowsResult r;
-    rc = x3_levels_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status);
-    if (res) *res = r;
-    return static_cast<X3Error>(rc);
+    return detail::levels_result(ctx, x3_corpus_tone_levels_dev(ctx.raw(), raw_, bin_len, d_levels, n_rows, d_frame_status, &t),
+                                  res);
   }
   // Tone bank levels of every entry (x3_corpus_tone_bank_levels_dev): bank.steps.size() planes of tone_levels()' n_rows
   // records, plane t at d_levels + t * n_rows; every entry starts at phase 0 in every plane.  Waits for the call.
@@ -1152,12 +1121,8 @@ class Corpus {
                            WindowsResult* res, const ToneBank& bank) const {
     if (!bank.ok()) return X3Error::BadArg;
     const x3_level_tone_bank b = bank.c_bank();
-    int rc = x3_corpus_tone_bank_levels_dev(ctx.raw(), raw_, bin_len, d_levels, n_rows, d_frame_status, &b);
-    if (rc != X3_OK) return static_cast<X3Error>(rc);
-    WindowsResult r;
-    rc = x3_levels_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status);
-    if (res) *res = r;
-    return static_cast<X3Error>(rc);
+    return detail::levels_result(ctx, x3_corpus_tone_bank_levels_dev(ctx.raw(), raw_, bin_len, d_levels, n_rows, d_frame_status,
+                                  &b), res);
   }
   // Events of every entry (x3_corpus_events_dev) over the n_rows records levels() wrote: as device::events, with the events'
   // entries in d_entries; the arrays go to ranges() with n_ranges = cap as they are.  Waits for the call.
@@ -1207,13 +1172,8 @@ class Corpus {
                        uint64_t n_ranges, uint64_t bin_len, uint64_t row_stride, x3_level* d_levels, uint64_t rows_cap,
                        uint64_t* d_row_offsets, int32_t* d_status, RangeLevelsResult* res,
                        LevelSignal signal = LevelSignal::Samples) const {
-    int rc = x3_corpus_signal_range_levels_dev(ctx.raw(), raw_, d_entries, d_starts, d_lens, n_ranges, bin_len, row_stride,
-                                               d_levels, rows_cap, d_row_offsets, d_status, static_cast<int>(signal));
-    if (rc != X3_OK) return static_cast<X3Error>(rc);
-    RangeLevelsResult r;
-    rc = x3_range_levels_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status, &r.total_rows);
-    if (res) *res = r;
-    return static_cast<X3Error>(rc);
+    return detail::levels_result(ctx, x3_corpus_signal_range_levels_dev(ctx.raw(), raw_, d_entries, d_starts, d_lens, n_ranges,
+                                  bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status, static_cast<int>(signal)), res);
   }
   // FIR range levels of entries (x3_corpus_fir_range_levels_dev): as device::fir_range_levels; no filter history crosses from
   // one entry into the next.  Waits for the call.
@@ -1221,13 +1181,8 @@ class Corpus {
                            uint64_t n_ranges, uint64_t bin_len, uint64_t row_stride, x3_level* d_levels, uint64_t rows_cap,
                            uint64_t* d_row_offsets, int32_t* d_status, const Fir& fir, RangeLevelsResult* res) const {
     const x3_level_fir f = fir.c_fir();
-    int rc = x3_corpus_fir_range_levels_dev(ctx.raw(), raw_, d_entries, d_starts, d_lens, n_ranges, bin_len, row_stride, d_levels,
-                                            rows_cap, d_row_offsets, d_status, &f);
-    if (rc != X3_OK) return static_cast<X3Error>(rc);
-    RangeLevelsResult r;
-    rc = x3_range_levels_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status, &r.total_rows);
-    if (res) *res = r;
-    return static_cast<X3Error>(rc);
+    return detail::levels_result(ctx, x3_corpus_fir_range_levels_dev(ctx.raw(), raw_, d_entries, d_starts, d_lens, n_ranges,
+                                  bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status, &f), res);
   }
   // Tone range levels of entries (x3_corpus_tone_range_levels_dev): as device::tone_range_levels; starts count from the
   // entry's first position and so does the phase, 0 there.  Waits for the call.
@@ -1235,13 +1190,8 @@ class Corpus {
                             uint64_t n_ranges, uint64_t bin_len, uint64_t row_stride, x3_tone_level* d_levels, uint64_t rows_cap,
                             uint64_t* d_row_offsets, int32_t* d_status, const Tone& tone, RangeLevelsResult* res) const {
     const x3_level_tone t = tone.c_tone();
-    int rc = x3_corpus_tone_range_levels_dev(ctx.raw(), raw_, d_entries, d_starts, d_lens, n_ranges, bin_len, row_stride, d_levels,
-                                             rows_cap, d_row_offsets, d_status, &t);
-    if (rc != X3_OK) return static_cast<X3Error>(rc);
-    RangeLevelsResult r;
-    rc = x3_range_levels_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status, &r.total_rows);
-    if (res) *res = r;
-    return static_cast<X3Error>(rc);
+    return detail::levels_result(ctx, x3_corpus_tone_range_levels_dev(ctx.raw(), raw_, d_entries, d_starts, d_lens, n_ranges,
+                                  bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status, &t), res);
   }
   // the recorded segment index (device memory the corpus owns), nullptr and 0 words without one
   const uint64_t* seg_index(uint64_t* n_words) const {

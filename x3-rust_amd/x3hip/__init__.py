@@ -1677,6 +1677,48 @@ def _adaptive_events_torch(ctx, n_rows, n_ent, capacity, with_entries, enqueue_l
     return _events_torch(ctx, n_rows, capacity, with_entries, enqueue_levels, both) + (thr,)
 
 
+def _levels_np(src, what, bin_len, n_rows, dtype, enqueue, planes=None):
+    """the host side of levels() / tone_levels() / tone_bank_levels() of src, a WindowSource or a Corpus: enqueue(d_levels,
+    n_rows, d_status) -> rc, then the result and both downloads -> (records, frame statuses), a Corpus's row_first between
+    them; n_rows: src's own count unless given; planes (tone_bank_levels): so many planes of n_rows records, returned as
+    [planes, n_rows]"""
+    ctx, n_frames = src.ctx, src.n_frames
+    rows, rf = src._levels_rows(bin_len)
+    if n_rows is None:
+        n_rows = rows
+    n_rec = n_rows * (planes or 1)
+    d_lv, d_st = ctx.alloc(dtype.itemsize * n_rec), ctx.alloc(4 * max(n_frames, 1))
+    try:
+        rc = enqueue(d_lv, n_rows, d_st)
+        if rc:
+            raise X3Error(rc, what + ": " + ctx.last_error())
+        rc = ctx.levels_result()[0]
+        if rc:
+            raise X3Error(rc, "x3_levels_result: " + ctx.last_error())
+        st = ctx.download(d_st, 4 * n_frames, np.int32) if n_frames else np.zeros(0, dtype=np.int32)
+        rec = ctx.download(d_lv, dtype.itemsize * n_rec, dtype)
+        rec = rec.reshape(planes, n_rows) if planes else rec
+        return (rec, st) if rf is None else (rec, rf, st)
+    finally:
+        for p in (d_lv, d_st):
+            ctx.free(p)
+
+
+def _levels_chain(src, bin_len, signal):
+    """what events(), level_quantiles() and adaptive_events() of a WindowSource or a Corpus begin with -> (the rows of the
+    levels of `signal`, enqueue_levels(d_levels) -> rc)"""
+    if not 0 < bin_len <= 0xFFFFFFFF:
+        raise ValueError("bin_len: 1 .. 2^32 - 1")
+    sig = level_signal(signal)
+    n_rows = src._levels_rows(bin_len)[0]
+    return n_rows, lambda d_lv: src.levels_into(bin_len, d_lv, n_rows, None, sig)
+
+
+def _bank_planes(tones):
+    """the planes tone_bank_levels_into writes: tones as it takes them"""
+    return tones.n_tones if isinstance(tones, LevelToneBank) else len(tone_bank(tones))
+
+
 class WindowSource:
     """Random access to one mono stream in HBM: windows of samples [start, start + length) as rows of a batch.
 
@@ -1865,50 +1907,29 @@ class WindowSource:
         if isinstance(signal, Tone):
             return (self.tone_levels_into(bin_len, signal, d_levels, n_bins, d_frame_status)
                     or self.ctx.tone_power_levels_dev(d_levels, n_bins, d_levels))
-        if isinstance(signal, Fir):
-            return self.ctx.fir_levels_dev(self.d_x3, self.x3_len, self.d_frame_offsets, self.d_sample_offsets, self.n_frames,
-                                           self.params, bin_len, d_levels, n_bins, d_frame_status, self.d_seg_index,
-                                           self.seg_blocks, signal)
-        return self.ctx.signal_levels_dev(self.d_x3, self.x3_len, self.d_frame_offsets, self.d_sample_offsets, self.n_frames,
-                                          self.params, bin_len, d_levels, n_bins, d_frame_status, self.d_seg_index,
-                                          self.seg_blocks, signal)
+        call = self.ctx.fir_levels_dev if isinstance(signal, Fir) else self.ctx.signal_levels_dev
+        return self._levels_call(call, bin_len, d_levels, n_bins, d_frame_status, signal)
+
+    def _levels_call(self, call, bin_len, d_levels, n_bins, d_frame_status, signal):
+        """call: the Context's signal_levels_dev, fir_levels_dev, tone_levels_dev or tone_bank_levels_dev, over this source"""
+        return call(self.d_x3, self.x3_len, self.d_frame_offsets, self.d_sample_offsets, self.n_frames, self.params, bin_len,
+                    d_levels, n_bins, d_frame_status, self.d_seg_index, self.seg_blocks, signal)
+
+    def _levels_rows(self, bin_len):
+        """-> (the bins that cover the stream, no row_first)"""
+        return (max(1, -(-self.total // bin_len)) if bin_len else 1), None
 
     def tone_levels_into(self, bin_len, tone, d_levels, n_bins, d_frame_status=None):
         """enqueue x3_tone_levels_dev over this source (device pointers; tone: a Tone or a LevelTone); -> rc;
         Context.levels_result waits"""
-        return self.ctx.tone_levels_dev(self.d_x3, self.x3_len, self.d_frame_offsets, self.d_sample_offsets, self.n_frames,
-                                        self.params, bin_len, d_levels, n_bins, d_frame_status, self.d_seg_index,
-                                        self.seg_blocks, tone)
-
-    def _levels_np(self, what, bin_len, n_bins, dtype, enqueue, planes=None):
-        """the host side of levels() / tone_levels(): enqueue(d_levels, d_status) -> rc, then the result and both downloads;
-        planes (tone_bank_levels): so many planes of n_bins records, returned as [planes, n_bins]"""
-        if n_bins is None:
-            n_bins = max(1, -(-self.total // bin_len)) if bin_len else 1
-        n_rec = n_bins * (planes or 1)
-        d_lv, d_st = self.ctx.alloc(dtype.itemsize * n_rec), self.ctx.alloc(4 * self.n_frames)
-        try:
-            rc = enqueue(d_lv, n_bins, d_st)
-            if rc:
-                raise X3Error(rc, what + ": " + self.ctx.last_error())
-            rc = self.ctx.levels_result()[0]
-            if rc:
-                raise X3Error(rc, "x3_levels_result: " + self.ctx.last_error())
-            rec = self.ctx.download(d_lv, dtype.itemsize * n_rec, dtype)
-            return (rec.reshape(planes, n_bins) if planes else rec,
-                    self.ctx.download(d_st, 4 * self.n_frames, np.int32))
-        finally:
-            for p in (d_lv, d_st):
-                self.ctx.free(p)
+        return self._levels_call(self.ctx.tone_levels_dev, bin_len, d_levels, n_bins, d_frame_status, tone)
 
     def tone_bank_levels_into(self, bin_len, tones, d_levels, n_bins, d_frame_status=None, *, band=False):
         """enqueue x3_tone_bank_levels_dev over this source (device pointers; tones: 1 .. TONE_BANK_MAX Tone or a
         LevelToneBank; d_levels: that many planes of n_bins records), band=True: and the adapter in place over all planes
         behind it; -> rc; Context.levels_result waits"""
-        k = tones.n_tones if isinstance(tones, LevelToneBank) else len(tone_bank(tones))
-        rc = self.ctx.tone_bank_levels_dev(self.d_x3, self.x3_len, self.d_frame_offsets, self.d_sample_offsets, self.n_frames,
-                                           self.params, bin_len, d_levels, n_bins, d_frame_status, self.d_seg_index,
-                                           self.seg_blocks, tones)
+        k = _bank_planes(tones)
+        rc = self._levels_call(self.ctx.tone_bank_levels_dev, bin_len, d_levels, n_bins, d_frame_status, tones)
         return rc or (self.ctx.tone_power_levels_dev(d_levels, k * n_bins, d_levels) if band else 0)
 
     def tone_bank_levels(self, bin_len, tones, n_bins=None, *, band=False):
@@ -1917,9 +1938,9 @@ class WindowSource:
         the stream (x3_tone_bank_levels_dev).  band=True: x3_tone_power_levels_dev in place over all planes behind the
         call; the records are then LEVEL_DTYPE, the level of each band, which events() takes plane by plane"""
         tones = tone_bank(tones)
-        return self._levels_np("x3_tone_bank_levels_dev", bin_len, n_bins, LEVEL_DTYPE if band else TONE_DTYPE,
-                               lambda d_lv, nb, d_st: self.tone_bank_levels_into(bin_len, tones, d_lv, nb, d_st, band=band),
-                               planes=len(tones))
+        return _levels_np(self, "x3_tone_bank_levels_dev", bin_len, n_bins, LEVEL_DTYPE if band else TONE_DTYPE,
+                          lambda d_lv, nb, d_st: self.tone_bank_levels_into(bin_len, tones, d_lv, nb, d_st, band=band),
+                          planes=len(tones))
 
     def tone_levels(self, bin_len, tone, n_bins=None):
         """-> (records np.ndarray of TONE_DTYPE [n_bins], frame statuses np.int32 [n_frames]): re, im -- the sums of sample
@@ -1927,8 +1948,8 @@ class WindowSource:
         tone: a Tone (x3_tone_levels_dev with the usual table)"""
         if not isinstance(tone, Tone):
             raise ValueError("tone: a Tone")
-        return self._levels_np("x3_tone_levels_dev", bin_len, n_bins, TONE_DTYPE,
-                               lambda d_lv, nb, d_st: self.tone_levels_into(bin_len, tone, d_lv, nb, d_st))
+        return _levels_np(self, "x3_tone_levels_dev", bin_len, n_bins, TONE_DTYPE,
+                          lambda d_lv, nb, d_st: self.tone_levels_into(bin_len, tone, d_lv, nb, d_st))
 
     def levels(self, bin_len, n_bins=None, *, signal="samples"):
         """-> (records np.ndarray of LEVEL_DTYPE [n_bins], frame statuses np.int32 [n_frames]): min, max, n, sum and sum of
@@ -1937,8 +1958,8 @@ class WindowSource:
         Fir: the samples behind an integer FIR filter (x3_fir_levels_dev) -- or a Tone: the level of the band at one
         oscillator (x3_tone_levels_dev, then x3_tone_power_levels_dev in place)"""
         sig = level_signal(signal)
-        return self._levels_np("x3_signal_levels_dev", bin_len, n_bins, LEVEL_DTYPE,
-                               lambda d_lv, nb, d_st: self.levels_into(bin_len, d_lv, nb, d_st, sig))
+        return _levels_np(self, "x3_signal_levels_dev", bin_len, n_bins, LEVEL_DTYPE,
+                          lambda d_lv, nb, d_st: self.levels_into(bin_len, d_lv, nb, d_st, sig))
 
     def events_into(self, d_levels, n_bins, bin_len, rule, d_starts, d_lens, d_event_levels, cap, d_count):
         """enqueue x3_events_dev over n_bins records this source's levels_dev wrote (device pointers; the sample count is the
@@ -1951,13 +1972,10 @@ class WindowSource:
         device -> (starts int64 [capacity], lens int32 [capacity], count 0-d int64, event_levels uint8 [capacity, 32]),
         torch tensors on the device.  Slots behind the events are zero-length ranges: ranges(starts, lens, padded_to=...)
         takes the tensors as they are.  count may exceed capacity: repeat with more."""
-        if not 0 < bin_len <= 0xFFFFFFFF:
-            raise ValueError("bin_len: 1 .. 2^32 - 1")
-        sig = level_signal(signal)
-        n_bins = max(1, -(-self.total // bin_len))
+        n_bins, enqueue_levels = _levels_chain(self, bin_len, signal)
         return _events_torch(
             self.ctx, n_bins, capacity, False,
-            lambda d_lv: self.levels_into(bin_len, d_lv, n_bins, None, sig),
+            enqueue_levels,
             lambda d_lv, d_e, d_s, d_l, d_el, d_c: self.events_into(d_lv, n_bins, bin_len, rule, d_s, d_l, d_el, capacity, d_c))
 
     def level_quantiles_into(self, d_levels, n_bins, bin_len, key, q_ppm, d_values, d_counted):
@@ -1979,25 +1997,19 @@ class WindowSource:
     def level_quantiles(self, bin_len, key, q_ppm, *, signal="samples"):
         """Levels (of `signal`, as in levels()) of bins of bin_len positions, then the quantiles q_ppm (millionths) of their keys, on the device ->
         (values int32 [1, len(q_ppm)], counted int32 [1]) torch tensors"""
-        if not 0 < bin_len <= 0xFFFFFFFF:
-            raise ValueError("bin_len: 1 .. 2^32 - 1")
-        sig = level_signal(signal)
-        n_bins = max(1, -(-self.total // bin_len))
+        n_bins, enqueue_levels = _levels_chain(self, bin_len, signal)
         return _level_quantiles_torch(
             self.ctx, n_bins, 1, len(q_ppm),
-            lambda d_lv: self.levels_into(bin_len, d_lv, n_bins, None, sig),
+            enqueue_levels,
             lambda d_lv, d_v, d_k: self.level_quantiles_into(d_lv, n_bins, bin_len, key, q_ppm, d_v, d_k))
 
     def adaptive_events(self, bin_len, threshold_rule, rule, capacity, *, signal="samples"):
         """events() with the rule's two values (both 0 in `rule`) chosen on the device by `threshold_rule` (a ThresholdRule)
         -> (starts, lens, count, event_levels, thresholds uint8 [1, 16])"""
-        if not 0 < bin_len <= 0xFFFFFFFF:
-            raise ValueError("bin_len: 1 .. 2^32 - 1")
-        sig = level_signal(signal)
-        n_bins = max(1, -(-self.total // bin_len))
+        n_bins, enqueue_levels = _levels_chain(self, bin_len, signal)
         return _adaptive_events_torch(
             self.ctx, n_bins, 1, capacity, False,
-            lambda d_lv: self.levels_into(bin_len, d_lv, n_bins, None, sig),
+            enqueue_levels,
             lambda d_lv, d_t: self.level_thresholds_into(d_lv, n_bins, bin_len, threshold_rule, d_t),
             lambda d_lv, d_t, d_e, d_s, d_l, d_el, d_c: self.adaptive_events_into(d_lv, n_bins, bin_len, rule, d_t, d_s, d_l, d_el,
                                                                                   capacity, d_c))
@@ -2302,9 +2314,13 @@ class Corpus:
         if isinstance(signal, Tone):
             return (self.tone_levels_into(bin_len, signal, d_levels, n_rows, d_frame_status)
                     or self.ctx.tone_power_levels_dev(d_levels, n_rows, d_levels))
-        if isinstance(signal, Fir):
-            return self.ctx.corpus_fir_levels_dev(self, bin_len, d_levels, n_rows, d_frame_status, signal)
-        return self.ctx.corpus_signal_levels_dev(self, bin_len, d_levels, n_rows, d_frame_status, signal)
+        call = self.ctx.corpus_fir_levels_dev if isinstance(signal, Fir) else self.ctx.corpus_signal_levels_dev
+        return call(self, bin_len, d_levels, n_rows, d_frame_status, signal)
+
+    def _levels_rows(self, bin_len):
+        """-> (the rows of all entries, row_first)"""
+        rf = self.levels_rows(bin_len)
+        return int(rf[-1]), rf
 
     def levels(self, bin_len, *, signal="samples"):
         """-> (records np.ndarray of LEVEL_DTYPE [rows], row_first np.uint64 [n_entries + 1], frame statuses np.int32
@@ -2317,29 +2333,8 @@ class Corpus:
         Every entry stands alone: no difference and no filter history crosses from one entry into the next, and a Tone's
         phase is 0 at every entry's start"""
         sig = level_signal(signal)
-        return self._levels_np("x3_corpus_signal_levels_dev", bin_len, LEVEL_DTYPE,
-                               lambda d_lv, n_rows, d_st: self.levels_into(bin_len, d_lv, n_rows, d_st, sig))
-
-    def _levels_np(self, what, bin_len, dtype, enqueue, planes=None):
-        """the host side of levels() / tone_levels(): enqueue(d_levels, n_rows, d_status) -> rc, then the result and the
-        downloads; planes (tone_bank_levels): so many planes of n_rows records, returned as [planes, n_rows]"""
-        rf = self.levels_rows(bin_len)
-        n_rows = int(rf[-1])
-        n_rec = n_rows * (planes or 1)
-        d_lv, d_st = self.ctx.alloc(dtype.itemsize * n_rec), self.ctx.alloc(4 * max(self.n_frames, 1))
-        try:
-            rc = enqueue(d_lv, n_rows, d_st)
-            if rc:
-                raise X3Error(rc, what + ": " + self.ctx.last_error())
-            rc = self.ctx.levels_result()[0]
-            if rc:
-                raise X3Error(rc, "x3_levels_result: " + self.ctx.last_error())
-            st = self.ctx.download(d_st, 4 * self.n_frames, np.int32) if self.n_frames else np.zeros(0, dtype=np.int32)
-            rec = self.ctx.download(d_lv, dtype.itemsize * n_rec, dtype)
-            return (rec.reshape(planes, n_rows) if planes else rec), rf, st
-        finally:
-            for p in (d_lv, d_st):
-                self.ctx.free(p)
+        return _levels_np(self, "x3_corpus_signal_levels_dev", bin_len, None, LEVEL_DTYPE,
+                          lambda d_lv, n_rows, d_st: self.levels_into(bin_len, d_lv, n_rows, d_st, sig))
 
     def tone_levels_into(self, bin_len, tone, d_levels, n_rows, d_frame_status=None):
         """enqueue x3_corpus_tone_levels_dev (device pointers; tone: a Tone or a LevelTone); -> rc; Context.levels_result
@@ -2354,7 +2349,7 @@ class Corpus:
         Context.levels_result waits"""
         if self._h is None:
             raise ValueError("the corpus is closed")
-        k = tones.n_tones if isinstance(tones, LevelToneBank) else len(tone_bank(tones))
+        k = _bank_planes(tones)
         rc = self.ctx.corpus_tone_bank_levels_dev(self, bin_len, d_levels, n_rows, d_frame_status, tones)
         return rc or (self.ctx.tone_power_levels_dev(d_levels, k * n_rows, d_levels) if band else 0)
 
@@ -2364,17 +2359,17 @@ class Corpus:
         (x3_corpus_tone_bank_levels_dev); row_first is the single call's, in every plane.  band=True: the adapter in place
         over all planes, the records are LEVEL_DTYPE"""
         tones = tone_bank(tones)
-        return self._levels_np("x3_corpus_tone_bank_levels_dev", bin_len, LEVEL_DTYPE if band else TONE_DTYPE,
-                               lambda d_lv, n_rows, d_st: self.tone_bank_levels_into(bin_len, tones, d_lv, n_rows, d_st, band=band),
-                               planes=len(tones))
+        return _levels_np(self, "x3_corpus_tone_bank_levels_dev", bin_len, None, LEVEL_DTYPE if band else TONE_DTYPE,
+                          lambda d_lv, n_rows, d_st: self.tone_bank_levels_into(bin_len, tones, d_lv, n_rows, d_st, band=band),
+                          planes=len(tones))
 
     def tone_levels(self, bin_len, tone):
         """-> (records np.ndarray of TONE_DTYPE [rows], row_first, frame statuses) as levels(): the quadrature sums of every
         entry's bins against one oscillator, whose phase restarts at 0 with every entry (x3_corpus_tone_levels_dev)"""
         if not isinstance(tone, Tone):
             raise ValueError("tone: a Tone")
-        return self._levels_np("x3_corpus_tone_levels_dev", bin_len, TONE_DTYPE,
-                               lambda d_lv, n_rows, d_st: self.tone_levels_into(bin_len, tone, d_lv, n_rows, d_st))
+        return _levels_np(self, "x3_corpus_tone_levels_dev", bin_len, None, TONE_DTYPE,
+                          lambda d_lv, n_rows, d_st: self.tone_levels_into(bin_len, tone, d_lv, n_rows, d_st))
 
     def events_into(self, d_levels, n_rows, bin_len, rule, d_entries, d_starts, d_lens, d_event_levels, cap, d_count):
         """enqueue x3_corpus_events_dev over the n_rows records Context.corpus_levels_dev wrote (device pointers); -> rc;
@@ -2388,13 +2383,10 @@ class Corpus:
         """Levels (of `signal`, as in levels()) of every entry, then the runs of hot bins under `rule` as ranges, all on the device -> (entries int32,
         starts int64, lens int32 [capacity each], count 0-d int64, event_levels uint8 [capacity, 32]), as
         WindowSource.events; ranges(entries, starts, lens, padded_to=...) takes the tensors as they are."""
-        if not 0 < bin_len <= 0xFFFFFFFF:
-            raise ValueError("bin_len: 1 .. 2^32 - 1")
-        sig = level_signal(signal)
-        n_rows = int(self.levels_rows(bin_len)[-1])
+        n_rows, enqueue_levels = _levels_chain(self, bin_len, signal)
         return _events_torch(
             self.ctx, n_rows, capacity, True,
-            lambda d_lv: self.levels_into(bin_len, d_lv, n_rows, None, sig),
+            enqueue_levels,
             lambda d_lv, d_e, d_s, d_l, d_el, d_c: self.events_into(d_lv, n_rows, bin_len, rule, d_e, d_s, d_l, d_el, capacity, d_c))
 
     def level_quantiles_into(self, d_levels, n_rows, bin_len, key, q_ppm, d_values, d_counted):
@@ -2421,25 +2413,19 @@ class Corpus:
     def level_quantiles(self, bin_len, key, q_ppm, *, signal="samples"):
         """Levels (of `signal`, as in levels()) of every entry, then per entry the quantiles q_ppm (millionths) of their keys, on the device ->
         (values int32 [n_entries, len(q_ppm)], counted int32 [n_entries]) torch tensors"""
-        if not 0 < bin_len <= 0xFFFFFFFF:
-            raise ValueError("bin_len: 1 .. 2^32 - 1")
-        sig = level_signal(signal)
-        n_rows = int(self.levels_rows(bin_len)[-1])
+        n_rows, enqueue_levels = _levels_chain(self, bin_len, signal)
         return _level_quantiles_torch(
             self.ctx, n_rows, self.n_entries, len(q_ppm),
-            lambda d_lv: self.levels_into(bin_len, d_lv, n_rows, None, sig),
+            enqueue_levels,
             lambda d_lv, d_v, d_k: self.level_quantiles_into(d_lv, n_rows, bin_len, key, q_ppm, d_v, d_k))
 
     def adaptive_events(self, bin_len, threshold_rule, rule, capacity, *, signal="samples"):
         """events() with a threshold per entry chosen on the device by `threshold_rule` -> (entries, starts, lens, count,
         event_levels, thresholds uint8 [n_entries, 16])"""
-        if not 0 < bin_len <= 0xFFFFFFFF:
-            raise ValueError("bin_len: 1 .. 2^32 - 1")
-        sig = level_signal(signal)
-        n_rows = int(self.levels_rows(bin_len)[-1])
+        n_rows, enqueue_levels = _levels_chain(self, bin_len, signal)
         return _adaptive_events_torch(
             self.ctx, n_rows, self.n_entries, capacity, True,
-            lambda d_lv: self.levels_into(bin_len, d_lv, n_rows, None, sig),
+            enqueue_levels,
             lambda d_lv, d_t: self.level_thresholds_into(d_lv, n_rows, bin_len, threshold_rule, d_t),
             lambda d_lv, d_t, d_e, d_s, d_l, d_el, d_c: self.adaptive_events_into(d_lv, n_rows, bin_len, rule, d_t, d_e, d_s, d_l,
                                                                                   d_el, capacity, d_c))
