@@ -1214,6 +1214,44 @@ int x3_corpus_tone_range_levels_dev(x3_ctx* ctx, const x3_corpus* corpus, const 
                                     const uint32_t* d_lens, uint64_t n_ranges, uint64_t bin_len, uint64_t row_stride,
                                     x3_tone_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status,
                                     const x3_level_tone* tone);
+/* ---- TONE BANK RANGE LEVELS: the range-levels calls on up to X3_TONE_BANK_MAX tones at once, so that events found in
+ * several bands by one x3_tone_bank_levels_dev pass can be looked at again, at finer bins, in ALL those bands for one decode
+ * of the covering frames instead of one per band.  The arguments of x3_tone_range_levels_dev /
+ * x3_corpus_tone_range_levels_dev with `bank` (x3_level_tone_bank, above) where `tone` stands.
+ *   ONE RULE: the bank is n_tones tone-range calls laid PLANE BY PLANE, with plane stride rows_cap.  d_levels holds
+ * n_tones * rows_cap x3_tone_level records; plane t is the rows_cap records at d_levels + t * rows_cap, byte for byte what
+ * x3_tone_range_levels_dev (or the corpus form) writes into a buffer of rows_cap records for {steps[t], 0, d_table} with the
+ * same other arguments.  Records a call does not write stay untouched in EVERY plane: those of ranges without room when
+ * packed, those behind n_ranges * row_stride when padded.
+ *   - d_row_offsets, d_status and x3_range_levels_result exist once and are the single call's; total_rows is ONE plane's.
+ *     The status never depends on the bank; "last_range_levels_replays" and "last_range_levels_overflow" have the values of
+ *     one tone call with the same arguments.
+ *   - The oscillators are not restarted at a range: position i of the stream or entry has the phase (i * steps[t]) mod 2^32
+ *     in plane t, and every corpus entry starts at phase 0.  (The product is formed in 64 bits and truncated per slot as in
+ *     the single call; positions past 2^32 are the single call's, per slot.)
+ *   - A plane does not depend on the other steps; permuting the steps permutes the planes; equal steps give equal planes;
+ *     min, max and n are the same in all planes.  n_tones == 1 IS x3_tone_range_levels_dev.
+ *   - The range (0, total) at bin length b equals x3_tone_bank_levels_dev at b, plane for plane, damaged frames included.
+ *   - All planes go through x3_tone_power_levels_dev in ONE launch of n_tones * rows_cap rows -- when every record of
+ *     every plane is defined: the untouched ones are the caller's bytes (zero them first: a zero record has n == 0 and comes
+ *     out as the identity).
+ *   X3_ERR_BAD_ARG with nothing enqueued, tested before every other argument: a NULL bank, n_tones 0 or above
+ * X3_TONE_BANK_MAX, reserved != 0, a NULL or misaligned (4 bytes) d_table; then n_tones * rows_cap > 2^31 - 1; then
+ * everything x3_range_levels_dev refuses.  The struct is copied at the call, steps behind n_tones are never read, and the
+ * table is read when the kernels run.  The pending slot, the asynchronous contract and "a failed frame adds nothing, to no
+ * plane" are the other forms'.  The workspace is shared with them and holds n_tones * (rows_cap + P) partial rows, P the
+ * SAMPLES form's: there are no lead frames.  A call with 3 or 5 .. 7 tones runs the kernel of 4 or 8 (DESIGN.md section 27
+ * has the cost). */
+int x3_tone_bank_range_levels_dev(x3_ctx* ctx, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
+                                  const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
+                                  const uint64_t* d_seg_index, uint32_t seg_blocks, const uint64_t* d_starts,
+                                  const uint32_t* d_lens, uint64_t n_ranges, uint64_t bin_len, uint64_t row_stride,
+                                  x3_tone_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status,
+                                  const x3_level_tone_bank* bank);
+int x3_corpus_tone_bank_range_levels_dev(x3_ctx* ctx, const x3_corpus* corpus, const uint32_t* d_entries,
+                                         const uint64_t* d_starts, const uint32_t* d_lens, uint64_t n_ranges, uint64_t bin_len,
+                                         uint64_t row_stride, x3_tone_level* d_levels, uint64_t rows_cap,
+                                         uint64_t* d_row_offsets, int32_t* d_status, const x3_level_tone_bank* bank);
 void x3_corpus_destroy(x3_corpus* corpus);
 
 /* ------------------------------------------------------------------ multi-GPU (no reference analogue) */

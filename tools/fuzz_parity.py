@@ -36,7 +36,12 @@ Families: (e) the single-pass encoders on block_len 20 with mixed content, many 
           random tone bank (x3_tone_bank_levels_dev / x3_corpus_tone_bank_levels_dev): 1 .. 8 drawn steps, equal ones among
           them, the usual table or a random one, garbage in the struct's spare steps; every plane GPU ==
           tests/tone_bank_levels_ref.py and == the single call's bytes, the adapter over all planes at once, then the same
-          frames as a corpus (not in the default family set)."""
+          frames as a corpus (not in the default family set); (u) family (p) with a random tone bank on top
+          (x3_tone_bank_range_levels_dev / x3_corpus_tone_bank_range_levels_dev): 1 .. 8 steps -- 0, 2^30, 2^31, 2^32 - 1 and
+          equal ones among them, the family's own step in one slot -- against the same table, garbage in the spare steps;
+          every plane GPU == tests/tone_range_levels_ref.py at its step and == the single call's bytes, what no call writes
+          keeps its fill in every plane, then the same ranges on the corpus, plane by plane the single corpus call's bytes
+          (not in the default family set)."""
 import argparse, ctypes as C, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "x3-rust_amd"))
@@ -817,7 +822,7 @@ fams["c"] = fam_c
 fams["x"] = fam_x
 
 
-def fam_r(rng, tag, diff=False, fir=None, tone=False):
+def fam_r(rng, tag, diff=False, fir=None, tone=False, bank=False):
     """range levels (diff: of the first difference, against signal_range_levels_ref -- family (l); fir: behind that filter,
     against fir_range_levels_ref -- family (t); tone: against a drawn oscillator, tone_range_levels_ref, then the same
     frames as a corpus of random entries -- family (p)): the records, row offsets and statuses of random ranges of a random stream -- any geometry, damaged
@@ -901,6 +906,13 @@ def fam_r(rng, tag, diff=False, fir=None, tone=False):
                 starts[w] = max(0, min(at, n - lens[w]))
         step = int(rng.choice([0, 1 << 22, 1 << 31, (1 << 32) - 1, int(rng.integers(0, 1 << 32)), int(rng.integers(0, 1 << 32)) | 1]))
         tab = None if rng.random() < 0.5 else rng.integers(-32768, 32768, (1024, 2)).astype(np.int16)
+    if bank:   # family (u): a bank around the family's step
+        n_tones = int(rng.integers(1, 9))
+        steps = [int(rng.choice([0, 1 << 30, 1 << 31, (1 << 32) - 1, int(rng.integers(0, 1 << 32)), int(rng.integers(0, 1 << 32)) | 1]))
+                 for _ in range(n_tones)]
+        steps[int(rng.integers(0, n_tones))] = step
+        if n_tones > 1 and rng.random() < 0.3:
+            steps[-1] = steps[0]   # equal steps, equal planes
     wild = [n, n + 1, 2 ** 63, 2 ** 64 - 1, int(rng.integers(n + 1, 2 ** 62))]
     for _ in range(int(rng.integers(0, 3))):
         w = int(rng.integers(0, nr))
@@ -963,6 +975,8 @@ def fam_r(rng, tag, diff=False, fir=None, tone=False):
                 d_tab = ctx.alloc(4096); d.append(d_tab)
                 ctx.upload(d_tab, tab)
             level_tone = x3hip.LevelTone(step, 0, d_tab)
+            if bank:   # (spare steps: garbage)
+                level_bank = x3hip.LevelToneBank(n_tones, 0, d_tab, (C.c_uint32 * 8)(*(steps + [0xDEADBEEF] * (8 - n_tones))))
             rc = src.tone_range_levels_into(bufs[3], bufs[4], nr, bin_len, stride, bufs[0], cap, bufs[1], bufs[2], level_tone)
         elif fir is not None:
             rc = src.fir_range_levels_into(bufs[3], bufs[4], nr, bin_len, stride, bufs[0], cap, bufs[1], bufs[2], fir)
@@ -981,6 +995,32 @@ def fam_r(rng, tag, diff=False, fir=None, tone=False):
         assert np.array_equal(got, want[0]), (tag, "records", np.flatnonzero((got != want[0]).any(axis=1))[:8].tolist(), bin_len, stride, cap)
         nbad = np.flatnonzero(st)
         assert res == (0, nbad.size, int(nbad[0]) if nbad.size else nr, int(st[nbad[0]]) if nbad.size else 0, sum(rows)), (tag, res)
+        if bank and n_tones * cap <= 1 << 22:   # (128 MB of records at most) the bank: every plane against the definition at its step and the single call's bytes, shared results once
+            counters = (ctx.get_option("last_range_levels_replays"), ctx.get_option("last_range_levels_overflow"))
+            bsize = 32 * n_tones * cap
+            bb = [ctx.alloc(bsize + guard), ctx.alloc(sizes[1] + guard), ctx.alloc(sizes[2] + guard)]
+            d.extend(bb)
+            for q, v in zip(bb, (bsize, sizes[1], sizes[2])):
+                ctx.upload(q, np.full(v + guard, 0x5A, dtype=np.uint8))
+            rc = src.tone_bank_range_levels_into(bufs[3], bufs[4], nr, bin_len, stride, bb[0], cap, bb[1], bb[2], level_bank)
+            assert rc == 0, (tag, "bank rc", rc, ctx.last_error())
+            assert ctx.range_levels_result() == res, (tag, "bank result")
+            assert (ctx.get_option("last_range_levels_replays"), ctx.get_option("last_range_levels_overflow")) == counters, (tag, "bank counters")
+            braw = [ctx.download(q, v + guard) for q, v in zip(bb, (bsize, sizes[1], sizes[2]))]
+            for name, a, v in zip(("levels", "offsets", "status"), braw, (bsize, sizes[1], sizes[2])):
+                assert (a[v:] == 0x5A).all(), (tag, "bank canary", name)
+            assert np.array_equal(braw[1], raw[1]) and np.array_equal(braw[2], raw[2]), (tag, "bank offsets or status")
+            planes = braw[0][:bsize].reshape(n_tones, cap, 32)
+            for t, v in enumerate(steps):
+                w_t = want[0] if v == step else TRL.range_levels(verdicts, so_a, starts, lens, bin_len, stride, cap, v, tab)[0]
+                assert np.array_equal(planes[t], w_t), (tag, "bank plane", t, v, np.flatnonzero((planes[t] != w_t).any(axis=1))[:8].tolist(),
+                                                        bin_len, stride, cap, steps)
+                if v != step:   # (the family's own step: `got` above)
+                    ctx.upload(bufs[0], np.full(sizes[0] + guard, 0x5A, dtype=np.uint8))
+                    rc = src.tone_range_levels_into(bufs[3], bufs[4], nr, bin_len, stride, bufs[0], cap, bufs[1], bufs[2],
+                                                    x3hip.LevelTone(v, 0, d_tab))
+                    assert rc == 0 and ctx.range_levels_result() == res, (tag, "single", v)
+                    assert np.array_equal(planes[t], ctx.download(bufs[0], sizes[0]).reshape(cap, 32)), (tag, "plane is not the single call", t)
         if tone and bin_len <= 0xFFFFFFFF:
             # the same bytes as a corpus: the frames cut into entries at random frame boundaries, ranges of random entries
             # with starts counted from the entry -- each against the reference on that entry alone (phase 0 at its start)
@@ -1044,6 +1084,26 @@ def fam_r(rng, tag, diff=False, fir=None, tone=False):
                     w_rec, _, w_st = TRL.range_levels(verdicts[a:b], e_so, [c_starts[w]], [c_lens[w]], bin_len, c_stride, rows_w, step, tab)
                     assert st[w] == w_st[0], (tag, "corpus status", w, e, c_starts[w], c_lens[w], int(st[w]), int(w_st[0]))
                     assert np.array_equal(mine, w_rec), (tag, "corpus records", w, e, c_starts[w], c_lens[w], bin_len, c_stride, cuts)
+                if bank and n_tones * c_cap <= 1 << 22:   # the corpus form of the bank: plane by plane the single corpus call's bytes
+                    cres = res
+                    csize = 32 * n_tones * c_cap
+                    d_cb = ctx.alloc(csize + guard); d.append(d_cb)
+                    ctx.upload(d_cb, np.full(csize + guard, 0x5A, dtype=np.uint8))
+                    rc = corpus.tone_bank_range_levels_into(cb[5], cb[3], cb[4], nr, bin_len, c_stride, d_cb, c_cap, cb[1], cb[2], level_bank)
+                    assert rc == 0 and ctx.range_levels_result() == cres, (tag, "corpus bank rc", rc, ctx.last_error())
+                    craw = ctx.download(d_cb, csize + guard)
+                    assert (craw[csize:] == 0x5A).all(), (tag, "corpus bank canary")
+                    assert np.array_equal(ctx.download(cb[2], sizes[2]).view(np.int32), st), (tag, "corpus bank status")
+                    cplanes = craw[:csize].reshape(n_tones, c_cap, 32)
+                    for t, v in enumerate(steps):
+                        one = got
+                        if v != step:
+                            ctx.upload(cb[0], np.full(sizes[0] + guard, 0x5A, dtype=np.uint8))
+                            rc = corpus.tone_range_levels_into(cb[5], cb[3], cb[4], nr, bin_len, c_stride, cb[0], c_cap, cb[1], cb[2],
+                                                               x3hip.LevelTone(v, 0, d_tab))
+                            assert rc == 0 and ctx.range_levels_result() == cres, (tag, "corpus single", v)
+                            one = ctx.download(cb[0], sizes[0]).reshape(c_cap, 32)
+                        assert np.array_equal(cplanes[t], one), (tag, "corpus plane is not the single call", t, v)
             finally:
                 corpus.close()
     finally:
@@ -1269,6 +1329,7 @@ fams["i"] = lambda rng, tag: fam_h(rng, tag, fir=True)
 fams["t"] = lambda rng, tag: fam_r(rng, tag, fir=draw_fir(rng))
 fams["p"] = lambda rng, tag: fam_r(rng, tag, tone=True)
 fams["q"] = lambda rng, tag: fam_h(rng, tag, bank=True)
+fams["u"] = lambda rng, tag: fam_r(rng, tag, tone=True, bank=True)
 
 
 def run(seed=1, minutes=None, trials=None, families="egdbaf", only=-1, context=None):

@@ -29,10 +29,18 @@ forms, in torch's int64, every position's phase ((position in the stream or entr
 made once, outside the timed part), gathers the table pair, multiplies and sums, with min and max of the samples.  Route b is
 the tone levels call; case 3's events are found on the band's levels (the tone levels call and the adapter in place), and
 its merged band records are no tone records, so case 3 compares the call with route a only.
+--signal tone --tones K (2 .. 8): the tone bank call beside them (x3_tone_bank_range_levels_dev /
+x3_corpus_tone_bank_range_levels_dev), K oscillators at BANK_FREQS[:K] (the first is --step's default):
+  bank            one bank call of K tones, K planes of records
+  singles         K single tone-range calls of the same build, one per plane
+  range_levels    one single tone-range call (the first tone), as without --tones
+  route_a         the ranges call once, then the torch reduction above once per tone
+`bank` and `singles` alternate in order rep by rep.  The planes of `bank` are compared with == against `singles` (bytes) and
+against route a (every plane).
 Every route's records are compared with == at the end of every case and the tool fails otherwise.  Kernel times: run it under
 `rocprofv3 --kernel-trace --stats -- python3 tools/range_levels_bench.py ...`.  Prints one JSON line.
-    python3 tools/range_levels_bench.py [--signal samples|diff|fir|tone] [--taps c0,c1,..] [--shift k] [--step s] [--samples N] [--reps 10] [--warmup 2] [--cap 4096]
-                                        [--cases config3,corpus] [--out file.json]"""
+    python3 tools/range_levels_bench.py [--signal samples|diff|fir|tone] [--taps c0,c1,..] [--shift k] [--step s] [--tones K] [--samples N] [--reps 10] [--warmup 2] [--cap 4096]
+                                        [--cases config3,corpus] [--no-route-a] [--out file.json]"""
 import argparse, ctypes as C, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "x3-rust_amd"))
@@ -42,13 +50,15 @@ import x3hip
 
 now = time.perf_counter
 JOIN, MIN_BINS, PAD, MAX_BINS = 5, 1, 2, 25      # tools/events_bench.py's rule
+BANK_FREQS = (0.0817, 0.2310, 0.15, 0.41, 0.02, 0.33, 0.275, 0.4999)   # --tones K: the first K, in units of fs (tone_levels_bench.py's)
 
 
 class Source:
     """what a case needs of a stream or a corpus: the three calls, the entries' sample counts and their rows of a levels call"""
 
-    def __init__(self, ctx, name, rate, n_samples, range_levels, ranges, levels, events, levels_rows):
+    def __init__(self, ctx, name, rate, n_samples, range_levels, ranges, levels, events, levels_rows, tone_call=None, bank_call=None):
         self.ctx, self.name, self.rate, self.n_samples = ctx, name, rate, n_samples
+        self.tone_call, self.bank_call = tone_call, bank_call      # (--tones: range_levels' arguments and a Tone / the bank behind them)
         self.band = lambda d_lv, rows: ctx.tone_power_levels_dev(d_lv, rows, d_lv)      # (--signal tone: records -> band levels)
         self.range_levels, self.ranges, self.levels, self.events, self.levels_rows = range_levels, ranges, levels, events, levels_rows
 
@@ -70,10 +80,41 @@ def tone_records(re, im, mn, mx, n):
     return out
 
 
-def tone_pairs(a, pos):
+def tone_pairs(a, pos, step=None):
     """route a, tone: (cos, sin) int64 of the positions pos (int64, in the stream or entry)"""
-    k = ((pos * a.step) & 0xFFFFFFFF) >> 22          # (pos < 2^31, step < 2^32: the product stays inside int64)
+    k = ((pos * (a.step if step is None else step)) & 0xFFFFFFFF) >> 22          # (pos < 2^31, step < 2^32: the product stays inside int64)
     return a.table[k, 0], a.table[k, 1]
+
+
+def bank_sides(src, a, results, name, rep, args, rows, blv, slv, expect):
+    """--tones: the bank call and the K single calls, timed in alternating order; args: the call's arguments in front of
+    d_levels, (d_off, d_st) behind rows_cap"""
+    ctx, (front, back) = src.ctx, args
+
+    def bank():
+        assert src.bank_call(*front, blv.data_ptr(), rows, *back) == 0, ctx.last_error()
+        r = ctx.range_levels_result()
+        assert r == expect, r
+
+    def singles():
+        for k, tone in enumerate(a.tones):
+            assert src.tone_call(*front, slv.data_ptr() + 32 * rows * k, rows, *back, tone) == 0, ctx.last_error()
+            r = ctx.range_levels_result()
+            assert r == expect, r
+    sides = [("bank", bank), ("singles", singles)]
+    for side, fn in (sides if rep % 2 == 0 else sides[::-1]):
+        t = now()
+        fn()
+        timed(results, name + "_" + side, rep, a.warmup, now() - t)
+
+
+def bank_equal(a, blv, slv, reds, counts):
+    """--tones: the bank's planes == the single calls' bytes and, where route a ran, == its records plane by plane"""
+    same = bool(torch.equal(blv, slv))
+    for k, red in enumerate(reds or []):
+        want = tone_records(*(t.cpu().numpy() for t in red[:4]), counts)
+        same = same and blv[k].cpu().numpy().tobytes() == want.tobytes()
+    return same
 
 
 def filtered(a, w):
@@ -120,15 +161,23 @@ def bins_case(src, a, results, info, case, ent, starts, lens, bin_len):
     rf = src.levels_rows(bin_len)
     full_rows = int(rf[-1])
     full = torch.empty((full_rows, 32), dtype=torch.uint8, device="cuda") if 64 * full_rows < a.levels_bytes else None
+    if a.tones:
+        blv, slv = (torch.empty((len(a.tones), total_rows, 32), dtype=torch.uint8, device="cuda") for _ in range(2))
     torch.cuda.synchronize()
-    red = None
+    red = reds = None
     for rep in range(a.warmup + a.reps):
+        if a.tones:
+            bank_sides(src, a, results, name, rep, ((d_ent.data_ptr(), d_st.data_ptr(), d_ln.data_ptr(), n, bin_len, 0),
+                                                    (off.data_ptr(), st.data_ptr())), total_rows, blv, slv, (0, 0, n, 0, total_rows))
         t0 = now()
         assert src.range_levels(d_ent.data_ptr(), d_st.data_ptr(), d_ln.data_ptr(), n, bin_len, 0, lv.data_ptr(), total_rows,
                                 off.data_ptr(), st.data_ptr()) == 0, ctx.last_error()
         r = ctx.range_levels_result()
         t1 = now()
         assert r == (0, 0, n, 0, total_rows), r
+        if a.no_route_a:
+            timed(results, name + "_range_levels", rep, a.warmup, t1 - t0)
+            continue
         assert src.ranges(d_ent.data_ptr(), d_st_a.data_ptr(), d_ln_a.data_ptr(), n, 0, buf.data_ptr(), total_a, off2.data_ptr(),
                           st2.data_ptr()) == 0, ctx.last_error()
         r = ctx.decode_ranges_result()
@@ -143,8 +192,12 @@ def bins_case(src, a, results, info, case, ent, starts, lens, bin_len):
         elif a.tone:
             x = buf.view(total_rows, bin_len)
             w = buf.to(torch.int64)
-            cs, sn = tone_pairs(a, pos)
-            red = ((w * cs).view(total_rows, bin_len).sum(1), (w * sn).view(total_rows, bin_len).sum(1), x.min(1).values, x.max(1).values)
+            reds = []
+            for tone in a.tones or (a.tone,):
+                cs, sn = tone_pairs(a, pos, tone.step)
+                reds.append(((w * cs).view(total_rows, bin_len).sum(1), (w * sn).view(total_rows, bin_len).sum(1), x.min(1).values,
+                             x.max(1).values))
+            red = reds[0]
         else:
             x = buf.view(total_rows, bin_len)
             w = x.to(torch.int32)
@@ -161,17 +214,21 @@ def bins_case(src, a, results, info, case, ent, starts, lens, bin_len):
             assert ctx.levels_result()[0] == 0
             timed(results, name + "_route_b", rep, a.warmup, now() - t4)
     got = records(lv)
-    counts = red[4].cpu().numpy().astype(np.uint32) if hist_on else np.full(total_rows, bin_len, dtype=np.uint32)
-    want_a = (tone_records if a.tone else as_records)(*(t.cpu().numpy() for t in red[:4]), counts)
-    same = got.tobytes() == want_a.tobytes() and not st.cpu().numpy().any()
-    if full is not None:
+    same = not st.cpu().numpy().any()
+    if red is not None:
+        counts = red[4].cpu().numpy().astype(np.uint32) if hist_on else np.full(total_rows, bin_len, dtype=np.uint32)
+        want_a = (tone_records if a.tone else as_records)(*(t.cpu().numpy() for t in red[:4]), counts)
+        same = same and got.tobytes() == want_a.tobytes()
+    if a.tones:
+        same = same and bank_equal(a, blv, slv, reds, counts if reds else None) and blv[0].cpu().numpy().tobytes() == got.tobytes()
+    if full is not None and red is not None:
         frec = records(full)
         pick = np.concatenate([int(rf[e]) + s // bin_len + np.arange(k) for e, s, k in zip(ent, starts, rows)])
         same = same and np.array_equal(got, frec[pick])
     if not same:
         raise SystemExit("%s: the routes' records differ" % name)
     info[name] = {"signal": a.signal, "ranges": n, "bin_len": bin_len, "rows": total_rows, "samples": total, "levels_rows": full_rows,
-                  "route_b": full is not None, "equal": bool(same),
+                  "route_b": full is not None and red is not None, "equal": bool(same),
                   "replays": ctx.get_option("last_range_levels_replays"), "overflow": ctx.get_option("last_range_levels_overflow")}
 
 
@@ -205,14 +262,22 @@ def events_case(src, a, results, info, bin_len):
     assert rc == 0 and found > 0 and (found <= cap or hist_on or a.tone), (rc, found)   # (diff: peaks saturate, ties at the
     # threshold can make more events than slots; the slots then hold the first `cap` of them and no filler)
     col = torch.arange(stride, device="cuda")[None, :]
-    red = None
+    red = reds = None
+    if a.tones:
+        blv, slv = (torch.empty((len(a.tones), cap, 32), dtype=torch.uint8, device="cuda") for _ in range(2))
     for rep in range(a.warmup + a.reps):
+        if a.tones:
+            bank_sides(src, a, results, name, rep, ((ent.data_ptr(), st.data_ptr(), ln.data_ptr(), cap, 0, 0),
+                                                    (off.data_ptr(), status.data_ptr())), cap, blv, slv, (0, 0, cap, 0, cap))
         t0 = now()
         assert src.range_levels(ent.data_ptr(), st.data_ptr(), ln.data_ptr(), cap, 0, 0, lv.data_ptr(), cap, off.data_ptr(),
                                 status.data_ptr()) == 0, ctx.last_error()
         r = ctx.range_levels_result()
         t1 = now()
         assert r == (0, 0, cap, 0, cap), r
+        if a.no_route_a:
+            timed(results, name + "_range_levels", rep, a.warmup, t1 - t0)
+            continue
         if hist_on:   # (start - 1, len + 1) where there is a sample in front; position r of the range is column r + pre
             pre = torch.where(ln > 0, st.clamp(max=hist), 0)
             st_a, ln_a = st - pre, ln + pre.to(torch.int32)
@@ -238,10 +303,13 @@ def events_case(src, a, results, info, bin_len):
                    torch.where(mask, y, 0).sum(1, dtype=torch.int64), torch.where(mask, y * y, 0).sum(1, dtype=torch.int64),
                    mask.sum(1))
         elif a.tone:   # (the rows behind a range's length hold zeros: they add nothing)
-            cs, sn = tone_pairs(a, st[:, None] + col)
             w64 = w.to(torch.int64)
-            red = ((w64 * cs).sum(1), (w64 * sn).sum(1), torch.where(mask, w, 32767).min(1).values,
-                   torch.where(mask, w, -32768).max(1).values)
+            reds = []
+            for tone in a.tones or (a.tone,):
+                cs, sn = tone_pairs(a, st[:, None] + col, tone.step)
+                reds.append(((w64 * cs).sum(1), (w64 * sn).sum(1), torch.where(mask, w, 32767).min(1).values,
+                             torch.where(mask, w, -32768).max(1).values))
+            red = reds[0]
         else:
             red = (torch.where(mask, w, 32767).min(1).values, torch.where(mask, w, -32768).max(1).values,
                    w.sum(1, dtype=torch.int64), (w * w).sum(1, dtype=torch.int64))
@@ -258,13 +326,17 @@ def events_case(src, a, results, info, bin_len):
         timed(results, name + "_route_a_torch", rep, a.warmup, t3 - t2)
         timed(results, name + "_route_b", rep, a.warmup, t4 - t3)
     got = records(lv)
-    counts = red[4].cpu().numpy().astype(np.uint32) if hist_on else ln.cpu().numpy().view(np.uint32)
-    want_a = (tone_records if a.tone else as_records)(*(t.cpu().numpy() for t in red[:4]), counts)
-    same = got.tobytes() == want_a.tobytes() and not status.cpu().numpy().any()
-    if a.tone:     # (the events' merged records are band records; both passes found the same events)
-        same = same and np.array_equal(records(ev_lv), records(ev_lv2))
-    else:
-        same = same and np.array_equal(got, records(ev_lv)) and np.array_equal(got, records(ev_lv2))
+    same = not status.cpu().numpy().any()
+    if red is not None:
+        counts = red[4].cpu().numpy().astype(np.uint32) if hist_on else ln.cpu().numpy().view(np.uint32)
+        want_a = (tone_records if a.tone else as_records)(*(t.cpu().numpy() for t in red[:4]), counts)
+        same = same and got.tobytes() == want_a.tobytes()
+        if a.tone:     # (the events' merged records are band records; both passes found the same events)
+            same = same and np.array_equal(records(ev_lv), records(ev_lv2))
+        else:
+            same = same and np.array_equal(got, records(ev_lv)) and np.array_equal(got, records(ev_lv2))
+    if a.tones:
+        same = same and bank_equal(a, blv, slv, reds, counts if reds else None) and blv[0].cpu().numpy().tobytes() == got.tobytes()
     if not same:
         raise SystemExit("%s: the routes' records differ" % name)
     info[name] = {"signal": a.signal, "ranges": cap, "events": int(found), "bin_len": 0, "events_bin_len": bin_len, "peak_min": peak_min,
@@ -328,7 +400,11 @@ def config3(ctx, a, results, info):
         (lambda bl, d_lv, rows: ctx.signal_levels_dev(*s, bl, d_lv, rows, None, idx.data_ptr(), 32, sig)),
         lambda d_lv, rows, bl, rule, d_e, d_s, d_l, d_el, c, d_c: ctx.events_dev(d_lv, rows, bl, so.data_ptr() + 8 * F, rule, d_s, d_l,
                                                                                 d_el, c, d_c),
-        lambda bl: np.array([0, -(-n // bl)], dtype=np.uint64))
+        lambda bl: np.array([0, -(-n // bl)], dtype=np.uint64),
+        lambda d_e, d_s, d_l, k, bl, stride, d_lv, c, d_off, d_st, tone: ctx.tone_range_levels_dev(*s, d_s, d_l, k, bl, stride, d_lv, c,
+                                                                                                  d_off, d_st, idx.data_ptr(), 32, tone),
+        lambda d_e, d_s, d_l, k, bl, stride, d_lv, c, d_off, d_st: ctx.tone_bank_range_levels_dev(*s, d_s, d_l, k, bl, stride, d_lv, c,
+                                                                                                 d_off, d_st, idx.data_ptr(), 32, a.tones))
     cases(src, a, results, info)
 
 
@@ -375,7 +451,11 @@ def corpus_a(ctx, a, results, info):
         (lambda bl, d_lv, rows: ctx.corpus_tone_levels_dev(corpus, bl, d_lv, rows, None, sig)) if a.tone else
         (lambda bl, d_lv, rows: ctx.corpus_signal_levels_dev(corpus, bl, d_lv, rows, None, sig)),
         lambda d_lv, rows, bl, rule, d_e, d_s, d_l, d_el, c, d_c: corpus.events_into(d_lv, rows, bl, rule, d_e, d_s, d_l, d_el, c, d_c),
-        lambda bl: corpus.levels_rows(bl))
+        lambda bl: corpus.levels_rows(bl),
+        lambda d_e, d_s, d_l, k, bl, stride, d_lv, c, d_o, d_st, tone: corpus.tone_range_levels_into(d_e, d_s, d_l, k, bl, stride, d_lv,
+                                                                                                    c, d_o, d_st, tone),
+        lambda d_e, d_s, d_l, k, bl, stride, d_lv, c, d_o, d_st: corpus.tone_bank_range_levels_into(d_e, d_s, d_l, k, bl, stride, d_lv, c,
+                                                                                                   d_o, d_st, a.tones))
     cases(src, a, results, info)
     corpus.close()
     for q in (d_x3, d_off):
@@ -393,6 +473,8 @@ def main():
     ap.add_argument("--taps", default="1,-2,1", help="--signal fir: the taps c[0], c[1], ..")
     ap.add_argument("--shift", type=int, default=0)
     ap.add_argument("--step", type=int, default=350_898_828, help="--signal tone: the oscillator's step (0.0817 of the sample rate)")
+    ap.add_argument("--tones", type=int, default=0, choices=[0, 2, 3, 4, 5, 6, 7, 8], help="--signal tone: the bank call of K tones beside it")
+    ap.add_argument("--no-route-a", action="store_true", help="the calls alone: no ranges + torch, no levels call (for kernel traces)")
     ap.add_argument("--levels-bytes", type=float, default=16e9, help="route b runs where its records and workspace fit in this")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -402,6 +484,12 @@ def main():
     torch.cuda.init()
     ctx = x3hip.Context(0)
     a.tone = x3hip.Tone(a.step) if a.signal == "tone" else None
+    if a.tones and a.signal != "tone":
+        ap.error("--tones goes with --signal tone")
+    a.tones = x3hip.Tone.bank(BANK_FREQS[:a.tones], 1.0) if a.tones else None
+    if a.tones:
+        a.tone = a.tones[0]
+        a.step = a.tone.step
     if a.tone:
         a.table = torch.from_numpy(x3hip.tone_table().astype(np.int64)).cuda()
     results, info = {}, {}
@@ -411,6 +499,7 @@ def main():
         corpus_a(ctx, a, results, info)
     out = {"samples": a.samples, "reps": a.reps, "signal": a.signal, "cases": info,
            **({"taps": a.taps, "shift": a.shift} if a.fir else {}), **({"step": a.step} if a.tone else {}),
+           **({"tones": len(a.tones), "steps": [t.step for t in a.tones]} if a.tones else {}),
            "ms_median": {k: round(float(np.median(v)), 4) for k, v in results.items()},
            "ms_min": {k: round(float(np.min(v)), 4) for k, v in results.items()},
            "ms_max": {k: round(float(np.max(v)), 4) for k, v in results.items()}}

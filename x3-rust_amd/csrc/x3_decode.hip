@@ -2564,7 +2564,7 @@ uint64_t range_levels_pairs(uint64_t n, uint64_t F, uint64_t max_frames, uint64_
 // frame the verdicts; per pair its cut, the scan of the bin counts; the partial rows; replay scratch; the summary; diff
 // (X3_LEVEL_SIGNAL_DIFF, and the FIR calls) only, behind it: per frame its last sample, per range its plan's lead frames
 size_t range_levels_carve(char* base, uint64_t n, uint64_t F, uint64_t P, uint64_t rows_cap, uint64_t fix_waves,
-                          uint32_t scratch_per, RLevWs* w, bool diff) {
+                          uint32_t scratch_per, RLevWs* w, bool diff, uint64_t planes) {
   BlockCarver k{base, 0};
   w->plan = k.take<X3WinPlan>(n);
   w->cov_off = k.take<unsigned long long>(n + 1);
@@ -2574,7 +2574,7 @@ size_t range_levels_carve(char* base, uint64_t n, uint64_t F, uint64_t P, uint64
   w->fst = k.take<int32_t>(F);
   w->pairs = k.take<X3RLevPair>(P);
   w->prow = k.take<unsigned long long>(P + 1);
-  w->rows = k.take<x3_level>(rows_cap + P);
+  w->rows = k.take<x3_level>(planes * (rows_cap + P));   // (a tone bank: a plane of rows_cap + P rows per tone)
   w->scratch = k.take<int16_t>(std::max<uint64_t>(fix_waves, 4) * scratch_per);
   w->sum = k.take<X3RLevSummary>(1, diff ? 256 : 1);
   w->tail = diff ? k.take<int32_t>(F) : nullptr;
@@ -2588,6 +2588,10 @@ size_t range_levels_carve(char* base, uint64_t n, uint64_t F, uint64_t P, uint64
 // entries for the lead kernels, NULL for a stream.  g picks the lead kernel, the instance of the accumulate and fix-up
 // kernels and the seam kernel, in the switch below; DIFF and FIR share a workspace (tail[], lead[]), FIR leaves its edge
 // records in fir_ws as in levels_launch and has a fix-up of its own; TONE has the SAMPLES call's P and workspace.
+// BANK is TONE over g.planes() PLANES: d_levels holds that many planes of rows_cap records, the partial rows as many of cap;
+// pairs, scans and verdicts are one plane's.  The accumulate instance is the smallest of NT = 2, 4, 8 that holds the tones,
+// the fix-up's is NT = 8; x3_range_levels_planes_kernel writes the identities of the caller's planes 1 and up, and the init
+// and merge kernels run once per plane on offset pointers.
 template <class Plan>
 static int range_levels_launch(x3_ctx* c, const FrameSource& s, const uint64_t* d_starts, const uint32_t* d_lens, uint64_t n,
                                uint64_t bin_len, uint64_t row_stride, x3_level* d_levels, uint64_t rows_cap,
@@ -2595,13 +2599,14 @@ static int range_levels_launch(x3_ctx* c, const FrameSource& s, const uint64_t* 
                                uint64_t n_ent, const uint32_t* d_entries, Plan plan_step) {
   const uint64_t lead_frames = g.lead_frames();
   HIPCHK(c, hipSetDevice(c->device));
-  const uint64_t P = range_levels_pairs(n, s.F, s.max_frames, lead_frames), cap = rows_cap + P;
+  const uint64_t P = range_levels_pairs(n, s.F, s.max_frames, lead_frames), cap = rows_cap + P, planes = g.planes();
   const uint32_t scratch_per = levels_scratch_per(s.dp.block_len);
   const uint64_t fix_waves = levels_fix_waves(n, scratch_per);
   RLevWs w;
   int rc;
-  if ((rc = ensure(c, c->rlev_ws, range_levels_carve(nullptr, n, s.F, P, rows_cap, fix_waves, scratch_per, &w, g.lead())))) return rc;
-  range_levels_carve((char*)c->rlev_ws.p, n, s.F, P, rows_cap, fix_waves, scratch_per, &w, g.lead());
+  if ((rc = ensure(c, c->rlev_ws, range_levels_carve(nullptr, n, s.F, P, rows_cap, fix_waves, scratch_per, &w, g.lead(), planes))))
+    return rc;
+  range_levels_carve((char*)c->rlev_ws.p, n, s.F, P, rows_cap, fix_waves, scratch_per, &w, g.lead(), planes);
   if (g.fir_ws() && (rc = ensure(c, c->fir_ws, (size_t)(s.F * s.nseg) * sizeof(X3FirEdge)))) return rc;
   // grids: the counts are on the device and every kernel walks them grid-stride.  What a range has on average is at most
   // rows_cap / n rows (or the stride) of bin_len positions: the caller's words, possibly far above what is drawn, so a range
@@ -2617,7 +2622,7 @@ static int range_levels_launch(x3_ctx* c, const FrameSource& s, const uint64_t* 
   const uint64_t rec_hint = std::min(n * drawn_rows, rows_cap);
   const uint64_t* d_gstarts = plan_step(dim3(grid_for(n, 256)), w.plan, w.gstart, &w.sum->w);
   // everything behind the plan, for a signal: its lead kernel, the kernels all share, the two that decode, the merge, its seam
-  auto run = [&](auto lead, auto sig, auto tail, auto seam) {
+  auto run = [&](auto lead, auto sig, auto fix, auto tail, auto seam) {
     using Signal = decltype(sig);
     lead();
     hipLaunchKernelGGL(x3_range_levels_scan_kernel, dim3(1), dim3(1024), 0, c->stream, w.plan, n, d_lens, bin_len, row_stride, rows_cap,
@@ -2628,10 +2633,15 @@ static int range_levels_launch(x3_ctx* c, const FrameSource& s, const uint64_t* 
                        s.d_sample_offsets, d_gstarts, d_lens, (const X3WinPlan*)w.plan, n, (const unsigned long long*)w.cov_off,
                        (const unsigned long long*)w.row_off, (const uint32_t*)w.erows, bin_len, row_stride, rows_cap, P,
                        (const int32_t*)w.fst, w.pairs, d_levels);
+    if (planes > 1)
+      hipLaunchKernelGGL(x3_range_levels_planes_kernel, dim3(grid_for(rec_hint, 256)), dim3(256), 0, c->stream, n,
+                         (const unsigned long long*)w.row_off, (const uint32_t*)w.erows, row_stride, rows_cap, (uint32_t)planes,
+                         d_levels);
     hipLaunchKernelGGL(x3_range_levels_pair_scan_kernel, dim3(1), dim3(1024), 0, c->stream, (const X3RLevPair*)w.pairs,
                        (const unsigned long long*)w.cov_off, n, P, cap, w.prow, w.sum);
-    hipLaunchKernelGGL(x3_range_levels_init_kernel, dim3(grid_for(rec_hint + cov_hint, 256)), dim3(256), 0, c->stream,
-                       (const unsigned long long*)w.cov_off, n, P, cap, (const unsigned long long*)w.prow, w.rows);
+    for (uint64_t t = 0; t < planes; ++t)   // (a plane's rows and records: the same pairs, scans and verdicts)
+      hipLaunchKernelGGL(x3_range_levels_init_kernel, dim3(grid_for(rec_hint + cov_hint, 256)), dim3(256), 0, c->stream,
+                         (const unsigned long long*)w.cov_off, n, P, cap, (const unsigned long long*)w.prow, w.rows + t * cap);
     hipLaunchKernelGGL(x3_range_levels_accum_kernel<Signal>, dim3(grid_for(item_hint, 256)), dim3(256), 0, c->stream, s.d_x3, s.x3_len,
                        s.d_frame_offsets, s.dp, s.idx, s.seg_blocks, s.nseg, bin_len, (const unsigned long long*)w.cov_off, n, P, cap,
                        (const X3RLevPair*)w.pairs, (const unsigned long long*)w.prow, w.rows, w.fst, tail);
@@ -2643,11 +2653,12 @@ static int range_levels_launch(x3_ctx* c, const FrameSource& s, const uint64_t* 
                          scratch_per, w.sum, tail, (const uint32_t*)w.lead);
     };
     if constexpr (std::is_same_v<Signal, X3RLevFir>) fixup(x3_range_levels_fir_fixup_kernel, s.idx, s.seg_blocks, s.nseg);
-    else fixup(x3_range_levels_fixup_kernel<Signal>);
-    hipLaunchKernelGGL(x3_range_levels_merge_kernel, dim3(grid_for(rec_hint + cov_hint, 256)), dim3(256), 0, c->stream,
-                       (const X3RLevPair*)w.pairs, (const unsigned long long*)w.cov_off, n, P, cap, (const unsigned long long*)w.prow,
-                       (const unsigned long long*)w.row_off, (const uint32_t*)w.erows, row_stride, (const x3_level*)w.rows,
-                       (const int32_t*)w.fst, d_levels);
+    else fixup(x3_range_levels_fixup_kernel<decltype(fix)>);
+    for (uint64_t t = 0; t < planes; ++t)
+      hipLaunchKernelGGL(x3_range_levels_merge_kernel, dim3(grid_for(rec_hint + cov_hint, 256)), dim3(256), 0, c->stream,
+                         (const X3RLevPair*)w.pairs, (const unsigned long long*)w.cov_off, n, P, cap,
+                         (const unsigned long long*)w.prow, (const unsigned long long*)w.row_off, (const uint32_t*)w.erows,
+                         row_stride, (const x3_level*)w.rows + t * cap, (const int32_t*)w.fst, d_levels + t * rows_cap);
     if (g.seam()) seam();
   };
   auto none = [] {};
@@ -2657,7 +2668,7 @@ static int range_levels_launch(x3_ctx* c, const FrameSource& s, const uint64_t* 
             hipLaunchKernelGGL(x3_range_levels_fir_lead_kernel, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, s.d_sample_offsets,
                                d_ent, n_ent, d_entries, d_gstarts, d_lens, n, (uint32_t)lead_frames, w.plan, w.lead);
           },
-          X3RLevFir{}, X3LevFirTail{g.fir, (X3FirEdge*)c->fir_ws.p, s.nseg}, [&] {
+          X3RLevFir{}, X3RLevFir{}, X3LevFirTail{g.fir, (X3FirEdge*)c->fir_ws.p, s.nseg}, [&] {
             hipLaunchKernelGGL(x3_range_levels_fir_seam_kernel, dim3(grid_for(item_hint, 256)), dim3(256), 0, c->stream,
                                s.dp.block_len, s.idx, s.seg_blocks, s.nseg, bin_len, (const X3RLevPair*)w.pairs,
                                (const unsigned long long*)w.cov_off, n, P, cap, (const unsigned long long*)w.prow,
@@ -2665,21 +2676,29 @@ static int range_levels_launch(x3_ctx* c, const FrameSource& s, const uint64_t* 
                                (const X3FirEdge*)c->fir_ws.p, s.nseg, g.fir, d_levels);
           });
       break;
-    case LevSignal::TONE: run(none, X3RLevTone{}, X3RLevToneTail{g.tone.table, g.tone.step, d_starts}, none); break;
+    case LevSignal::TONE: run(none, X3RLevTone{}, X3RLevTone{}, X3RLevToneTail{g.tone.table, g.tone.step, d_starts}, none); break;
     case LevSignal::DIFF:
       run([&] {
             hipLaunchKernelGGL(x3_range_levels_lead_kernel, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, s.d_sample_offsets, d_ent,
                                n_ent, d_entries, d_gstarts, d_lens, n, w.plan, w.lead);
           },
-          X3LevDiff{}, w.tail, [&] {
+          X3LevDiff{}, X3LevDiff{}, w.tail, [&] {
             hipLaunchKernelGGL(x3_range_levels_seam_kernel, dim3(grid_for(cov_hint, 256)), dim3(256), 0, c->stream, s.d_x3, s.x3_len,
                                s.d_frame_offsets, bin_len, (const X3RLevPair*)w.pairs, (const unsigned long long*)w.cov_off, n, P, cap,
                                (const unsigned long long*)w.prow, (const unsigned long long*)w.row_off, (const uint32_t*)w.erows,
                                row_stride, (const int32_t*)w.fst, (const int32_t*)w.tail, d_levels);
           });
       break;
-    case LevSignal::SAMPLES: run(none, X3LevSamples{}, X3LevNoTail{}, none); break;
-    case LevSignal::BANK: return X3_ERR_BAD_ARG;   // (no entry point builds it: DESIGN.md section 26)
+    case LevSignal::SAMPLES: run(none, X3LevSamples{}, X3LevSamples{}, X3LevNoTail{}, none); break;
+    case LevSignal::BANK: {
+      X3RLevToneBankTail t{g.bank, d_starts};
+      t.bank.rows_stride = cap, t.bank.levels_stride = rows_cap;
+      using Fix = X3RLevToneBank<X3L_TONE_BANK>;
+      if (t.bank.n_tones <= 2) run(none, X3RLevToneBank<2>{}, Fix{}, t, none);
+      else if (t.bank.n_tones <= 4) run(none, X3RLevToneBank<4>{}, Fix{}, t, none);
+      else run(none, Fix{}, Fix{}, t, none);
+      break;
+    }
   }
   HIPCHK(c, hipGetLastError());
   c->range_levels.pending = true;
@@ -2744,6 +2763,22 @@ extern "C" int x3_tone_range_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t
   return stream_range_levels_call(c, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, p, d_seg_index, seg_blocks, d_starts,
                                   d_lens, n_ranges, bin_len, row_stride, reinterpret_cast<x3_level*>(d_levels), rows_cap,
                                   d_row_offsets, d_status, LevSignal(t));
+}
+
+// the bank: n_tones tone-range calls plane by plane (plane stride rows_cap) in one pass over the covering frames
+extern "C" int x3_tone_bank_range_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
+                                             const uint64_t* d_sample_offsets, uint64_t n_frames, const x3_params* p,
+                                             const uint64_t* d_seg_index, uint32_t seg_blocks, const uint64_t* d_starts,
+                                             const uint32_t* d_lens, uint64_t n_ranges, uint64_t bin_len, uint64_t row_stride,
+                                             x3_tone_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets,
+                                             int32_t* d_status, const x3_level_tone_bank* bank) {
+  X3LevToneBankTail t;
+  if (!c || !levels_tone_bank_arg(bank, &t)) return X3_ERR_BAD_ARG;
+  const LevSignal g(t);
+  if (!levels_planes_ok(g, rows_cap)) return X3_ERR_BAD_ARG;
+  return stream_range_levels_call(c, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, p, d_seg_index, seg_blocks, d_starts,
+                                  d_lens, n_ranges, bin_len, row_stride, reinterpret_cast<x3_level*>(d_levels), rows_cap,
+                                  d_row_offsets, d_status, g);
 }
 
 extern "C" int x3_range_levels_dev(x3_ctx* c, const uint8_t* d_x3, uint64_t x3_len, const uint64_t* d_frame_offsets,
@@ -2811,6 +2846,19 @@ extern "C" int x3_corpus_tone_range_levels_dev(x3_ctx* c, const x3_corpus* k, co
   if (!c || !levels_tone_arg(tone, &t)) return X3_ERR_BAD_ARG;
   return corpus_range_levels_call(c, k, "x3_corpus_tone_range_levels_dev", d_entries, d_starts, d_lens, n_ranges, bin_len, row_stride,
                                   reinterpret_cast<x3_level*>(d_levels), rows_cap, d_row_offsets, d_status, LevSignal(t));
+}
+
+extern "C" int x3_corpus_tone_bank_range_levels_dev(x3_ctx* c, const x3_corpus* k, const uint32_t* d_entries,
+                                                    const uint64_t* d_starts, const uint32_t* d_lens, uint64_t n_ranges,
+                                                    uint64_t bin_len, uint64_t row_stride, x3_tone_level* d_levels,
+                                                    uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status,
+                                                    const x3_level_tone_bank* bank) {
+  X3LevToneBankTail t;
+  if (!c || !levels_tone_bank_arg(bank, &t)) return X3_ERR_BAD_ARG;
+  const LevSignal g(t);
+  if (!levels_planes_ok(g, rows_cap)) return X3_ERR_BAD_ARG;
+  return corpus_range_levels_call(c, k, "x3_corpus_tone_bank_range_levels_dev", d_entries, d_starts, d_lens, n_ranges, bin_len,
+                                  row_stride, reinterpret_cast<x3_level*>(d_levels), rows_cap, d_row_offsets, d_status, g);
 }
 
 extern "C" int x3_range_levels_result(x3_ctx* c, uint64_t* n_bad, uint64_t* first_bad, int* first_bad_status,

@@ -487,7 +487,8 @@ struct EvWs {
 X3_INTERNAL size_t events_carve(char* base, uint64_t n_rows, uint64_t n_ent, EvWs* w);
 // ... and of a range-levels call (rlev_ws; x3_range_levels_kernel.h): n ranges over F frames, P pairs (range, covering
 // frame) with rows_cap + P partial rows, `fix_waves` waves of the fix-up with `scratch_per` samples each; diff
-// (X3_LEVEL_SIGNAL_DIFF): behind the summary, a word per frame (its last sample) and per range (a lead frame in its plan)
+// (X3_LEVEL_SIGNAL_DIFF): behind the summary, a word per frame (its last sample) and per range (a lead frame in its plan);
+// `planes` planes of partial rows (a tone bank's: one per tone; one plane is every other call's layout byte for byte)
 struct X3RLevPair;
 struct X3RLevSummary;
 struct RLevWs {
@@ -499,7 +500,7 @@ struct RLevWs {
 };
 X3_INTERNAL uint64_t range_levels_pairs(uint64_t n, uint64_t F, uint64_t max_frames, uint64_t lead_frames = 0);
 X3_INTERNAL size_t range_levels_carve(char* base, uint64_t n, uint64_t F, uint64_t P, uint64_t rows_cap, uint64_t fix_waves,
-                                      uint32_t scratch_per, RLevWs* w, bool diff = false);
+                                      uint32_t scratch_per, RLevWs* w, bool diff = false, uint64_t planes = 1);
 // ... and of a quantiles or thresholds call (q_ws; x3_quantiles_kernel.h): n_rows records, n_ent entries (1 for a stream),
 // n_q quantiles of each
 struct X3QSlot;

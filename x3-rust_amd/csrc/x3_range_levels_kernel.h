@@ -38,6 +38,10 @@
 // x3_tone_range_levels_dev / x3_corpus_tone_range_levels_dev run the fourth instance of both templates,
 // X3RLevTone: X3LevTone with the phase seeded from the position in the STREAM OR ENTRY, not in the range (TONE RANGE LEVELS,
 // in front of the accumulate kernel); no kernel of its own.
+// x3_tone_bank_range_levels_dev / x3_corpus_tone_bank_range_levels_dev run the fifth,
+// X3RLevToneBank<NT>: X3LevToneBank<NT> seeded the same way, whose flushes go to n_tones PLANES of the partial rows and of the
+// caller's records; the init and merge kernels run once per plane on offset pointers, and one kernel of its own:
+//  x3_range_levels_planes_kernel -- behind the prep: the identities of the caller's records in planes 1 and up
 //
 // CAPACITY.  The workspace holds P pairs and cap = rows_cap + P partial rows, both sized on the host.  A pair with q >= P or
 // whose rows end behind cap has no rows: accumulate and merge skip it (x3rl_no_rows, recomputed from q and the scan) and the
@@ -178,13 +182,46 @@ struct X3RLevTone : X3LevTone {
   using Tail = X3RLevToneTail;
 };
 
+// ---- TONE BANK RANGE LEVELS (x3_tone_bank_range_levels_dev / x3_corpus_tone_bank_range_levels_dev)
+// The bank is n_tones tone-range calls laid plane by plane: X3LevToneBank<NT> with X3RLevTone's seed in every slot -- the same
+// position, truncated per slot as X3LevTone::seed truncates it -- and skip() stepping all phases over the samples outside
+// [lo, hi).  Pairs, scans, verdicts and row indices are one plane's and serve all: plane t's partial rows are
+// rows + t * bank.rows_stride (cap), its records levels + t * bank.levels_stride (rows_cap), and a flush stores slot
+// t < n_tones at the row or record index the single call would use, so the bounds of one plane hold in each.
+struct X3RLevToneBankTail {   // the kernels' last argument
+  X3LevToneBankTail bank;   // table, n_tones, steps (0 in the spare slots); rows_stride = cap, levels_stride = rows_cap
+  const uint64_t* starts;   // the caller's d_starts: n words
+};
+template <uint32_t NT>
+struct X3RLevToneBank : X3LevToneBank<NT> {
+  using Tail = X3RLevToneBankTail;
+};
+
+// ---- planes: the identities of the caller's records in planes 1 .. planes - 1, where x3_range_levels_prep_kernel wrote plane
+// 0's -- the same records by the same tests (packed: those of ranges that have room; padded: all n * stride), one owner
+// search per record for all planes.  Bounds: i < rows_cap (n * stride <= rows_cap: the host), t < planes: below planes * rows_cap.
+__global__ void __launch_bounds__(256)
+x3_range_levels_planes_kernel(uint64_t n, const unsigned long long* __restrict__ row_off, const uint32_t* __restrict__ erows,
+                              uint64_t stride, uint64_t rows_cap, uint32_t planes, x3_level* __restrict__ levels) {
+  const x3_level id = X3L_IDENTITY;
+  const uint64_t n_rec = stride ? n * stride : min((uint64_t)row_off[n], rows_cap);
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_rec; i += (uint64_t)gridDim.x * blockDim.x) {
+    if (!stride) {
+      const uint64_t w = x3w_owner(row_off, n, i);
+      if (i - row_off[w] >= erows[w]) continue;   // (no room: not this call's to write, in any plane)
+    }
+    for (uint32_t t = 1; t < planes; ++t) levels[t * rows_cap + i] = id;
+  }
+}
+
 // ---- accumulate: a lane per (pair, stretch) into the pair's own rows.  Signal: X3LevSamples; X3RLevFir, whose lanes add the
 // positions whose T samples they decoded themselves, inside or in front of [lo, hi), and leave the edge record of their
 // (frame, stretch) -- several pairs of one frame write the same values; or X3LevDiff, whose lanes take
 // the stretch's seed from x3w_stretch, see the samples outside [lo, hi) without counting them (the sample in front of lo is
 // sample lo's `prev`), and whose lane at the frame's end stores the frame's last sample to tail[f]; or X3RLevTone, whose
 // workgroups copy the table to LDS first (every lane, in front of the item loop) and whose lanes seed the phase with the
-// entry-relative position of their first sample.  A pair with an empty cut
+// entry-relative position of their first sample; or X3RLevToneBank<NT>, the same with NT phases, whose flush stores the
+// open bin to the pair's rows in every plane (no store in the sample loop).  A pair with an empty cut
 // (a lead frame) runs its stretches for the proof and the tail and touches no row: cnt is 0.
 template <class Signal>
 __global__ void __launch_bounds__(256)
@@ -200,6 +237,7 @@ x3_range_levels_accum_kernel(const uint8_t* __restrict__ x3, uint64_t len, const
   const uint64_t lanes = (uint64_t)gridDim.x * blockDim.x;
   [[maybe_unused]] const uint32_t* tone_tab = nullptr;
   if constexpr (Signal::kTone) tone_tab = x3l_tone_table(tail.table);
+  if constexpr (Signal::kBank) tone_tab = x3l_tone_table(tail.bank.table);
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_items; i += lanes) {
     const uint64_t q = i / ns;
     const uint32_t j = (uint32_t)(i - q * ns);
@@ -208,13 +246,18 @@ x3_range_levels_accum_kernel(const uint8_t* __restrict__ x3, uint64_t len, const
     if (x3rl_no_rows(prow, q, P, cap)) continue;   // (the fix-up's)
     x3_level* const mine = rows + prow[q];
     const uint32_t b0 = pr.b0, cnt = pr.cnt, lo = pr.lo, span = pr.hi - pr.lo;
+    [[maybe_unused]] Signal sig;
     auto flush = [&](uint64_t bin, const X3LevAcc& a) {
-      if (bin - b0 < (uint64_t)cnt) x3l_merge(mine + (bin - b0), a);
+      if constexpr (Signal::kBank) {   // (plane t's rows: rows + t * rows_stride, the same row index in each)
+        if (bin - b0 < (uint64_t)cnt) sig.store(mine + (bin - b0), tail.bank.rows_stride, tail.bank.n_tones, a);
+        sig.clear();
+      } else {
+        if (bin - b0 < (uint64_t)cnt) x3l_merge(mine + (bin - b0), a);
+      }
     };
     // a stretch's samples come in order, from sample 0 or from the first sample of block sb * j; the first of them inside
     // the range, if any, is sample max(s0, lo)
     const uint64_t s0 = j ? 1u + (uint64_t)sb * j * p.block_len : 0u;
-    [[maybe_unused]] Signal sig;
     if constexpr (Signal::kFir) {
       sig.k = tail.k;
       sig.edge = tail.edges + (pr.f * tail.stride + j);   // (pr.f < F, j < ns <= stride: below F * stride)
@@ -223,6 +266,10 @@ x3_range_levels_accum_kernel(const uint8_t* __restrict__ x3, uint64_t len, const
       sig.tab = tone_tab;
       sig.step = tail.step;
       sig.seed(tail.starts[pr.w] + pr.r0 - lo + s0);   // (pr.w < n: the prep kernel's owner of q)
+    }
+    if constexpr (Signal::kBank) {
+      sig.tab = tone_tab;
+      sig.seed(tail.bank, tail.starts[pr.w] + pr.r0 - lo + s0);
     }
     const int r = x3l_bin_samples<Signal>(
         (uint64_t)pr.r0 + (s0 > lo ? s0 - lo : 0u), bl,
@@ -244,6 +291,7 @@ x3_range_levels_accum_kernel(const uint8_t* __restrict__ x3, uint64_t len, const
 // (x3rl_fast) -- and adds the seams x3_range_levels_seam_kernel leaves; a lead frame (lead[w]: the plan's first frame lies in
 // front of the range) never gives the range its status; tail[f] of every frame it replays to status 0.
 // X3RLevTone: the replay into the records seeds the phase with the position of the frame's sample 0 and reads the caller's table.
+// X3RLevToneBank<NT>: the same with NT phases, into the range's records in every plane.
 __device__ __forceinline__ bool x3rl_fast(int32_t word, const unsigned long long* __restrict__ prow, uint64_t q, uint64_t P, uint64_t cap) {
   return word == X3D_OK && !x3rl_no_rows(prow, q, P, cap);
 }
@@ -290,15 +338,24 @@ x3_range_levels_fixup_kernel(const uint8_t* __restrict__ x3, const uint64_t* __r
           }
           uint32_t lo, hi, r0;
           if (fs == X3D_OK && x3rl_cut(so, f, start, L, lo, hi, r0)) {   // every block decodes: once more, into the records
+            [[maybe_unused]] Signal sig;
             auto flush = [&](uint64_t bin, const X3LevAcc& a) {
-              if (bin < (uint64_t)R) x3l_merge(mine + bin, a);
+              if constexpr (Signal::kBank) {   // (plane t's records: levels + t * levels_stride, the same index in each)
+                if (bin < (uint64_t)R) sig.store(mine + bin, tail.bank.levels_stride, tail.bank.n_tones, a);
+                sig.clear();
+              } else {
+                if (bin < (uint64_t)R) x3l_merge(mine + bin, a);
+              }
             };
             const uint32_t span = hi - lo;
-            [[maybe_unused]] Signal sig;
             if constexpr (Signal::kTone) {
               sig.tab = tail.table;
               sig.step = tail.step;
               sig.seed(tail.starts[w] + r0 - lo);
+            }
+            if constexpr (Signal::kBank) {
+              sig.tab = tail.bank.table;
+              sig.seed(tail.bank, tail.starts[w] + r0 - lo);
             }
             (void)x3l_bin_samples<Signal>(
                 r0, bl, [&](auto put_at) { return x3w_replay_frame(payload, p, blk, put_at); },
@@ -489,7 +546,7 @@ __device__ __forceinline__ int32_t x3rl_fir_value(const X3FirTaps& k, int32_t s,
 // is the caller's to keep from frame to frame, and cnt is how many of the samples in d[] are valid.
 template <bool kEdge>
 struct X3RLevFirT {
-  static constexpr bool kDiff = false, kFir = true, kState = true, kTone = false;
+  static constexpr bool kDiff = false, kFir = true, kState = true, kTone = false, kBank = false;
   using Tail = X3LevFirTail;
   X3FirTaps k;   // (uniform: the kernel's argument)
   X3FirEdge* edge = nullptr;

@@ -1003,6 +1003,22 @@ inline X3Error tone_range_levels(Context& ctx, const EncodedStream& s, const Par
                                     d_status, &t);
   });
 }
+// Tone bank range levels (x3_tone_bank_range_levels_dev): tone_range_levels for every step of the bank from one decode of the
+// covering frames.  d_levels holds bank.steps.size() planes of rows_cap records, plane t at d_levels + t * rows_cap what
+// tone_range_levels writes for Tone{steps[t], d_table}; row offsets, statuses and the result exist once (total_rows is one
+// plane's).  Records the call does not write stay untouched in every plane; where every record is defined, all planes go
+// through tone_power_levels at once.  Waits for the call.
+inline X3Error tone_bank_range_levels(Context& ctx, const EncodedStream& s, const Parameters& params, const Buffer& d_sample_offsets,
+                                      const uint64_t* d_starts, const uint32_t* d_lens, size_t n_ranges, uint64_t bin_len,
+                                      uint64_t row_stride, x3_tone_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets,
+                                      int32_t* d_status, const ToneBank& bank, RangeLevelsResult* res) {
+  if (!bank.ok()) return X3Error::BadArg;
+  const x3_level_tone_bank b = bank.c_bank();
+  return detail::stream_levels(ctx, s, params, d_sample_offsets, res, [&](auto... st) {
+    return x3_tone_bank_range_levels_dev(st..., d_starts, d_lens, n_ranges, bin_len, row_stride, d_levels, rows_cap,
+                                         d_row_offsets, d_status, &b);
+  });
+}
 
 // A batch of independent streams (x3_decode_streams_dev): entry s = bytes [offsets[s], offsets[s] + lengths[s]) of d_x3 (flags:
 // X3_STREAMS_ARCHIVE_FRAMES for the frame parts of .x3a archives), decoded into row s of d_out (offsets.size() rows of row_len
@@ -1192,6 +1208,18 @@ class Corpus {
     const x3_level_tone t = tone.c_tone();
     return detail::levels_result(ctx, x3_corpus_tone_range_levels_dev(ctx.raw(), raw_, d_entries, d_starts, d_lens, n_ranges,
                                   bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status, &t), res);
+  }
+  // Tone bank range levels of entries (x3_corpus_tone_bank_range_levels_dev): as device::tone_bank_range_levels --
+  // bank.steps.size() planes of rows_cap records; starts count from the entry's first position and so does the phase, 0
+  // there in every plane.  Waits for the call.
+  X3Error tone_bank_range_levels(Context& ctx, const uint32_t* d_entries, const uint64_t* d_starts, const uint32_t* d_lens,
+                                 uint64_t n_ranges, uint64_t bin_len, uint64_t row_stride, x3_tone_level* d_levels,
+                                 uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status, const ToneBank& bank,
+                                 RangeLevelsResult* res) const {
+    if (!bank.ok()) return X3Error::BadArg;
+    const x3_level_tone_bank b = bank.c_bank();
+    return detail::levels_result(ctx, x3_corpus_tone_bank_range_levels_dev(ctx.raw(), raw_, d_entries, d_starts, d_lens, n_ranges,
+                                  bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status, &b), res);
   }
   // the recorded segment index (device memory the corpus owns), nullptr and 0 words without one
   const uint64_t* seg_index(uint64_t* n_words) const {

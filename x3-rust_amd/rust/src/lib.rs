@@ -348,6 +348,17 @@ pub mod ffi {
                                                d_starts: *const u64, d_lens: *const u32, n_ranges: u64, bin_len: u64,
                                                row_stride: u64, d_levels: *mut x3_tone_level, rows_cap: u64,
                                                d_row_offsets: *mut u64, d_status: *mut i32, tone: *const x3_level_tone) -> c_int;
+        pub fn x3_tone_bank_range_levels_dev(ctx: *mut x3_ctx, d_x3: *const u8, x3_len: u64, d_frame_offsets: *const u64,
+                                             d_sample_offsets: *const u64, n_frames: u64, p: *const x3_params,
+                                             d_seg_index: *const u64, seg_blocks: u32, d_starts: *const u64, d_lens: *const u32,
+                                             n_ranges: u64, bin_len: u64, row_stride: u64, d_levels: *mut x3_tone_level,
+                                             rows_cap: u64, d_row_offsets: *mut u64, d_status: *mut i32,
+                                             bank: *const x3_level_tone_bank) -> c_int;
+        pub fn x3_corpus_tone_bank_range_levels_dev(ctx: *mut x3_ctx, corpus: *const x3_corpus, d_entries: *const u32,
+                                                    d_starts: *const u64, d_lens: *const u32, n_ranges: u64, bin_len: u64,
+                                                    row_stride: u64, d_levels: *mut x3_tone_level, rows_cap: u64,
+                                                    d_row_offsets: *mut u64, d_status: *mut i32,
+                                                    bank: *const x3_level_tone_bank) -> c_int;
         pub fn x3_range_levels_result(ctx: *mut x3_ctx, n_bad: *mut u64, first_bad: *mut u64, first_bad_status: *mut c_int,
                                       total_rows: *mut u64) -> c_int;
         pub fn x3_corpus_destroy(corpus: *mut x3_corpus);
@@ -1876,6 +1887,36 @@ pub mod device {
         Ok((n_bad, first_bad, st, total))
     }
 
+    /// `tone_range_levels` for every step of a bank from one decode of the covering frames (`x3_tone_bank_range_levels_dev`;
+    /// not in the reference crate): `d_levels` holds `bank.steps.len()` planes of `rows_cap` `ToneLevel`s, plane `t` -- at
+    /// record `t * rows_cap` -- what `tone_range_levels` writes for step `t`; row offsets, statuses and the result exist once
+    /// (the total is one plane's).  Records the call does not write stay untouched in every plane
+    #[allow(clippy::too_many_arguments)]
+    pub fn tone_bank_range_levels<'g>(gpu: &'g Gpu, s: &EncodedStream<'g>, params: &x3::Parameters, sample_offsets: &Buffer<'g>,
+                                      d_starts: &Buffer<'g>, d_lens: &Buffer<'g>, n_ranges: usize, bin_len: u64, row_stride: u64,
+                                      d_levels: &mut Buffer<'g>, rows_cap: u64, d_row_offsets: Option<&mut Buffer<'g>>,
+                                      d_status: &mut Buffer<'g>, bank: &ToneBank<'_, 'g>) -> error::Result<(u64, u64, i32, u64)> {
+        let b = bank.c()?;
+        if d_starts.len() < 8 * n_ranges || d_lens.len() < 4 * n_ranges
+            || (d_levels.len() as u64) < core::mem::size_of::<ToneLevel>() as u64 * rows_cap * bank.steps.len() as u64
+            || d_status.len() < 4 * n_ranges || d_row_offsets.as_ref().map_or(false, |b| b.len() < 8 * (n_ranges + 1)) {
+            return Err(X3Error::BadArg);
+        }
+        let p = params.c()?;
+        let idx = match &s.seg_index { Some(i) => i.as_ptr::<u64>() as *const u64, None => core::ptr::null() };
+        let off = d_row_offsets.map_or(core::ptr::null_mut(), |b| b.as_ptr::<u64>());
+        error::check(unsafe {
+            ffi::x3_tone_bank_range_levels_dev(gpu.raw(), s.bytes.as_ptr::<u8>(), s.len as u64, s.frame_offsets.as_ptr::<u64>(),
+                                               sample_offsets.as_ptr::<u64>(), s.n_frames as u64, &p, idx, s.seg_blocks,
+                                               d_starts.as_ptr::<u64>(), d_lens.as_ptr::<u32>(), n_ranges as u64, bin_len,
+                                               row_stride, d_levels.as_ptr::<ToneLevel>(), rows_cap, off,
+                                               d_status.as_ptr::<i32>(), &b)
+        })?;
+        let (mut n_bad, mut first_bad, mut st, mut total) = (0u64, 0u64, 0, 0u64);
+        error::check(unsafe { ffi::x3_range_levels_result(gpu.raw(), &mut n_bad, &mut first_bad, &mut st, &mut total) })?;
+        Ok((n_bad, first_bad, st, total))
+    }
+
     /// `decode_streams` flag: the entries are the frame part of .x3a archives (walked with the reader's 8 phantom bytes)
     pub const STREAMS_ARCHIVE_FRAMES: u32 = 1;
     /// `Corpus::build` flag: the segment index by `x3_seg_index_build_dev` -- for every parameter set, not only where a
@@ -2248,6 +2289,31 @@ pub mod device {
                 ffi::x3_corpus_tone_range_levels_dev(self.gpu.raw(), self.raw, d_entries.as_ptr::<u32>(), d_starts.as_ptr::<u64>(),
                                                      d_lens.as_ptr::<u32>(), n as u64, bin_len, row_stride,
                                                      d_levels.as_ptr::<ToneLevel>(), rows_cap, off, d_status.as_ptr::<i32>(), &t)
+            })?;
+            let (mut n_bad, mut first_bad, mut st, mut total) = (0u64, 0u64, 0, 0u64);
+            error::check(unsafe { ffi::x3_range_levels_result(self.gpu.raw(), &mut n_bad, &mut first_bad, &mut st, &mut total) })?;
+            Ok((n_bad, first_bad, st, total))
+        }
+
+        /// `tone_range_levels` for every step of a bank (`x3_corpus_tone_bank_range_levels_dev`): `bank.steps.len()` planes of
+        /// `rows_cap` `ToneLevel`s; starts count from the entry's first position and so does the phase, in every plane
+        #[allow(clippy::too_many_arguments)]
+        pub fn tone_bank_range_levels(&self, d_entries: &Buffer<'g>, d_starts: &Buffer<'g>, d_lens: &Buffer<'g>, n: usize,
+                                      bin_len: u64, row_stride: u64, d_levels: &mut Buffer<'g>, rows_cap: u64,
+                                      d_row_offsets: Option<&mut Buffer<'g>>, d_status: &mut Buffer<'g>,
+                                      bank: &ToneBank<'_, 'g>) -> error::Result<(u64, u64, i32, u64)> {
+            let b = bank.c()?;
+            if d_entries.len() < 4 * n || d_starts.len() < 8 * n || d_lens.len() < 4 * n
+                || (d_levels.len() as u64) < core::mem::size_of::<ToneLevel>() as u64 * rows_cap * bank.steps.len() as u64
+                || d_status.len() < 4 * n || d_row_offsets.as_ref().map_or(false, |b| b.len() < 8 * (n + 1)) {
+                return Err(X3Error::BadArg);
+            }
+            let off = d_row_offsets.map_or(core::ptr::null_mut(), |b| b.as_ptr::<u64>());
+            error::check(unsafe {
+                ffi::x3_corpus_tone_bank_range_levels_dev(self.gpu.raw(), self.raw, d_entries.as_ptr::<u32>(),
+                                                          d_starts.as_ptr::<u64>(), d_lens.as_ptr::<u32>(), n as u64, bin_len,
+                                                          row_stride, d_levels.as_ptr::<ToneLevel>(), rows_cap, off,
+                                                          d_status.as_ptr::<i32>(), &b)
             })?;
             let (mut n_bad, mut first_bad, mut st, mut total) = (0u64, 0u64, 0, 0u64);
             error::check(unsafe { ffi::x3_range_levels_result(self.gpu.raw(), &mut n_bad, &mut first_bad, &mut st, &mut total) })?;

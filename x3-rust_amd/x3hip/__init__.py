@@ -72,6 +72,7 @@ SYMBOLS = [
     "x3_signal_range_levels_dev", "x3_corpus_signal_range_levels_dev",
     "x3_fir_range_levels_dev", "x3_corpus_fir_range_levels_dev",
     "x3_tone_range_levels_dev", "x3_corpus_tone_range_levels_dev",
+    "x3_tone_bank_range_levels_dev", "x3_corpus_tone_bank_range_levels_dev",
     "x3_tune_candidate", "x3_tuner_create", "x3_tuner_add_dev", "x3_tuner_result", "x3_tuner_max_payloads",
     "x3_tuner_reset", "x3_tuner_destroy", "x3_tune", "x3_x3a_encode_tuned",
 ]
@@ -209,7 +210,9 @@ def tone_bank(tones):
 def level_signal(signal, fir=True):
     """the keyword `signal` of the levels methods ("samples" | "diff", or a LEVEL_SIGNAL_* value) -> the C ABI's int; a
     Fir or a Tone is handed through (fir=False: to the range-levels keyword, which takes neither and raises;
-    fir_range_levels and tone_range_levels do)"""
+    fir_range_levels and tone_range_levels do, and tone_bank_range_levels takes a bank of Tones)"""
+    if not fir and isinstance(signal, (tuple, list, LevelToneBank)):
+        raise ValueError("signal: range levels of a tone bank are not built on this keyword: call tone_bank_range_levels")
     if isinstance(signal, Fir):
         if not fir:
             raise ValueError("signal: range levels of a Fir signal are not built yet on this keyword: call fir_range_levels")
@@ -462,6 +465,10 @@ def lib():
     L.x3_tone_range_levels_dev.argtypes = [vp, vp, u64, vp, vp, u64, PP, vp, u32, vp, vp, u64, u64, u64, vp, u64, vp, vp,
                                            C.POINTER(LevelTone)]
     L.x3_corpus_tone_range_levels_dev.argtypes = [vp, vp, vp, vp, vp, u64, u64, u64, vp, u64, vp, vp, C.POINTER(LevelTone)]
+    L.x3_tone_bank_range_levels_dev.argtypes = [vp, vp, u64, vp, vp, u64, PP, vp, u32, vp, vp, u64, u64, u64, vp, u64, vp, vp,
+                                                C.POINTER(LevelToneBank)]
+    L.x3_corpus_tone_bank_range_levels_dev.argtypes = [vp, vp, vp, vp, vp, u64, u64, u64, vp, u64, vp, vp,
+                                                       C.POINTER(LevelToneBank)]
     L.x3_range_levels_result.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(i32), C.POINTER(u64)]
     L.x3_corpus_destroy.restype = None
     L.x3_synth.argtypes = [i32, u64, u64, u64, vp]
@@ -1407,6 +1414,26 @@ class Context:
         return lib().x3_corpus_tone_range_levels_dev(self._h, corpus._h, d_entries, d_starts, d_lens, n_ranges, bin_len,
                                                      row_stride, d_levels, rows_cap, d_row_offsets, d_status, self._tone_arg(tone))
 
+    def tone_bank_range_levels_dev(self, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, params, d_starts, d_lens,
+                                   n_ranges, bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status, d_seg_index=None,
+                                   seg_blocks=0, tones=None):
+        """x3_tone_bank_range_levels_dev: len(tones) planes of rows_cap x3_tone_level records (TONE_DTYPE), plane t -- at
+        d_levels + t * rows_cap -- what tone_range_levels_dev writes for tones[t], in one pass over the covering frames
+        (tones: 1 .. TONE_BANK_MAX Tone, or a LevelToneBank as it is); row offsets, statuses and the result are the single
+        call's; asynchronous, range_levels_result waits"""
+        return lib().x3_tone_bank_range_levels_dev(self._h, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames,
+                                                   C.byref(params), d_seg_index, seg_blocks, d_starts, d_lens, n_ranges, bin_len,
+                                                   row_stride, d_levels, rows_cap, d_row_offsets, d_status,
+                                                   self._tone_bank_arg(tones))
+
+    def corpus_tone_bank_range_levels_dev(self, corpus, d_entries, d_starts, d_lens, n_ranges, bin_len, row_stride, d_levels,
+                                          rows_cap, d_row_offsets, d_status, tones=None):
+        """x3_corpus_tone_bank_range_levels_dev: len(tones) planes of corpus_tone_range_levels_dev's rows_cap records, the
+        phase 0 at every entry's first position in every plane; asynchronous"""
+        return lib().x3_corpus_tone_bank_range_levels_dev(self._h, corpus._h, d_entries, d_starts, d_lens, n_ranges, bin_len,
+                                                          row_stride, d_levels, rows_cap, d_row_offsets, d_status,
+                                                          self._tone_bank_arg(tones))
+
     def range_levels_result(self):
         """-> (rc, n_bad, first_bad, first_bad_status, total_rows) of the last range_levels_dev / corpus_range_levels_dev"""
         nb, fb, st, tot = C.c_uint64(0), C.c_uint64(0), C.c_int32(0), C.c_uint64(0)
@@ -1540,13 +1567,15 @@ def _ranges_torch(ctx, enqueue, what, starts, lens, padded_to, capacity, dtype, 
     return out[:cap] if padded_to is None else out, offsets, status
 
 
-def _range_levels_torch(ctx, enqueue, what, starts, lens, bin_len, padded_to, capacity, entries=None, band=False):
+def _range_levels_torch(ctx, enqueue, what, starts, lens, bin_len, padded_to, capacity, entries=None, band=False, planes=None):
     """The torch side of WindowSource.range_levels / Corpus.range_levels: device tensors in, (levels uint8 [rows, 32],
     row_offsets int64 [n + 1], status int32 [n]) device tensors out (levels: see event_levels_view).
     enqueue(d_entries, d_starts, d_lens, n, bin_len, stride, d_levels, cap, d_off, d_status) -> rc.
     band (the tone calls): the records tensor is allocated zeroed and x3_tone_power_levels_dev runs in place over all of it
     behind the call -- a zero record has n == 0, which the adapter turns into the identity, so the records of ranges
-    without room are defined too."""
+    without room are defined too.
+    planes (the tone bank calls): levels is uint8 [planes, rows, 32], so many planes of `rows` records with plane stride
+    rows_cap = rows, and the adapter of band=True runs once over all planes * rows of them."""
     import torch
     dev = torch.device("cuda", torch.cuda.current_device())
     bin_len = int(bin_len)
@@ -1585,7 +1614,7 @@ def _range_levels_torch(ctx, enqueue, what, starts, lens, bin_len, padded_to, ca
         else:   # (the one host trip: the sum of max(1, ceil(len / bin_len)))
             ln = lens.to(torch.int64) & 0xFFFFFFFF
             cap = int(torch.clamp((ln + (bin_len - 1)) // bin_len, min=1).sum().item())
-    levels = (torch.zeros if band else torch.empty)((max(cap, 1), LEVEL_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    levels = (torch.zeros if band else torch.empty)((planes or 1, max(cap, 1), LEVEL_DTYPE.itemsize), dtype=torch.uint8, device=dev)
     offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
     status = torch.empty(n, dtype=torch.int32, device=dev)
     torch.cuda.current_stream().synchronize()    # (the context's stream is not torch's: the inputs are ready from here)
@@ -1594,7 +1623,7 @@ def _range_levels_torch(ctx, enqueue, what, starts, lens, bin_len, padded_to, ca
     if rc:
         raise X3Error(rc, what + ": " + ctx.last_error())
     if band and cap > 0:   # (behind the call on the context's stream, in front of the wait)
-        rc = ctx.tone_power_levels_dev(levels.data_ptr(), cap, levels.data_ptr())
+        rc = ctx.tone_power_levels_dev(levels.data_ptr(), (planes or 1) * cap, levels.data_ptr())
         if rc:
             raise X3Error(rc, "x3_tone_power_levels_dev: " + ctx.last_error())
     rc = ctx.range_levels_result()[0]
@@ -1602,7 +1631,7 @@ def _range_levels_torch(ctx, enqueue, what, starts, lens, bin_len, padded_to, ca
         raise X3Error(rc, "x3_range_levels_result: " + ctx.last_error())
     if band:
         ctx.sync()
-    return levels[:cap], offsets, status
+    return (levels[:, :cap] if planes else levels[0, :cap]), offsets, status
 
 
 def _events_torch(ctx, n_rows, capacity, with_entries, enqueue_levels, enqueue_events):
@@ -1899,6 +1928,28 @@ class WindowSource:
             raise ValueError("tone: a Tone")
         return _range_levels_torch(self.ctx, lambda e, *a: self.tone_range_levels_into(*a, tone), "x3_tone_range_levels_dev",
                                    starts, lens, bin_len, padded_to, capacity, band=band)
+
+    def tone_bank_range_levels_into(self, d_starts, d_lens, n, bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status,
+                                    tones):
+        """tone_range_levels_into for a bank (tones: 1 .. TONE_BANK_MAX Tone or a LevelToneBank): d_levels holds that many
+        planes of rows_cap records, plane t at d_levels + 32 * t * rows_cap what tone_range_levels_into writes for tones[t];
+        offsets and statuses exist once (x3_tone_bank_range_levels_dev); -> rc; Context.range_levels_result waits"""
+        return self.ctx.tone_bank_range_levels_dev(self.d_x3, self.x3_len, self.d_frame_offsets, self.d_sample_offsets,
+                                                   self.n_frames, self.params, d_starts, d_lens, n, bin_len, row_stride, d_levels,
+                                                   rows_cap, d_row_offsets, d_status, self.d_seg_index, self.seg_blocks, tones)
+
+    def tone_bank_range_levels(self, starts, lens, bin_len, tones, *, padded_to=None, capacity=None, band=False):
+        """tone_range_levels for K = len(tones) oscillators (1 .. TONE_BANK_MAX Tone, as tone_bank_levels takes them) from one
+        decode of the covering frames -> (levels uint8 [K, rows, 32], row_offsets, status): levels[t] is
+        tone_range_levels(starts, lens, bin_len, tones[t], ...)'s records, row_offsets and status are the single call's and
+        hold in every plane.  The oscillators are not restarted at a range.  band=True: x3_tone_power_levels_dev in place
+        over all planes behind the call, the records are x3_level records of each band's level; those of ranges without
+        room are the identity.  The tensors events() returns for any plane go in as they are
+        (x3_tone_bank_range_levels_dev)"""
+        tones = tone_bank(tones)
+        return _range_levels_torch(self.ctx, lambda e, *a: self.tone_bank_range_levels_into(*a, tones),
+                                   "x3_tone_bank_range_levels_dev", starts, lens, bin_len, padded_to, capacity, band=band,
+                                   planes=len(tones))
 
     def levels_into(self, bin_len, d_levels, n_bins, d_frame_status=None, signal=LEVEL_SIGNAL_SAMPLES):
         """enqueue x3_signal_levels_dev over this source (device pointers; signal: a LEVEL_SIGNAL_* value), or
@@ -2294,6 +2345,23 @@ class Corpus:
             raise ValueError("tone: a Tone")
         return _range_levels_torch(self.ctx, lambda *a: self.tone_range_levels_into(*a, tone), "x3_corpus_tone_range_levels_dev",
                                    starts, lens, bin_len, padded_to, capacity, entries=entries, band=band)
+
+    def tone_bank_range_levels_into(self, d_entries, d_starts, d_lens, n, bin_len, row_stride, d_levels, rows_cap, d_row_offsets,
+                                    d_status, tones):
+        """tone_range_levels_into for a bank (tones: 1 .. TONE_BANK_MAX Tone or a LevelToneBank): that many planes of
+        rows_cap records in d_levels (x3_corpus_tone_bank_range_levels_dev); -> rc"""
+        if self._h is None:
+            raise ValueError("the corpus is closed")
+        return self.ctx.corpus_tone_bank_range_levels_dev(self, d_entries, d_starts, d_lens, n, bin_len, row_stride, d_levels,
+                                                          rows_cap, d_row_offsets, d_status, tones)
+
+    def tone_bank_range_levels(self, entries, starts, lens, bin_len, tones, *, padded_to=None, capacity=None, band=False):
+        """WindowSource.tone_bank_range_levels for ranges of entries; the phase is 0 at every entry's first position in every
+        plane"""
+        tones = tone_bank(tones)
+        return _range_levels_torch(self.ctx, lambda *a: self.tone_bank_range_levels_into(*a, tones),
+                                   "x3_corpus_tone_bank_range_levels_dev", starts, lens, bin_len, padded_to, capacity,
+                                   entries=entries, band=band, planes=len(tones))
 
     def levels_rows(self, bin_len):
         """-> row_first np.uint64 [n_entries + 1]: entry e's rows of levels() are [row_first[e], row_first[e + 1])"""
