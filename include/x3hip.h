@@ -1056,6 +1056,58 @@ int x3_corpus_events_adaptive_dev(x3_ctx* ctx, const x3_corpus* corpus, const x3
                                   uint64_t bin_len, const x3_event_rule* rule, const x3_event_threshold* d_thr,
                                   uint32_t* d_entries, uint64_t* d_starts, uint32_t* d_lens, x3_level* d_event_levels,
                                   uint64_t cap, uint64_t* d_count);
+/* ---- PLANE EVENTS (no counterpart in the reference): runs of bins that are loud in at least k of K planes of level records
+ * -- the bands of a tone bank, or the samples' records beside their first difference's -- as ONE ordered, disjoint list of
+ * ranges (entry, start, len), found on the device.  One rule: plane events are the EVENTS above on
+ * one synthetic row verdict; everything behind "hot" is x3_events_dev's definition word for word.
+ *   INPUT.  d_levels holds n_planes (1 .. X3_EVENT_PLANES_MAX) planes of x3_level records: plane t is the n_bins records
+ * (n_rows for a corpus) at d_levels + t * plane_stride, plane_stride >= n_bins, in records -- what x3_tone_bank_levels_dev
+ * and x3_tone_power_levels_dev over all planes write with plane_stride = n_bins.  Every plane has the rows and entries of
+ * the events calls: the stream form one entry of min(n_bins, ceil(*d_total / bin_len)) rows, the corpus form
+ * x3_corpus_levels_rows' layout.  Records between n_bins and plane_stride are never read.
+ *   LOUD.  Plane t is loud at row b when record (t, b) has n != 0 and sum_sq >= mean_sq_min[t] * n (mean_sq_min[t] != 0) or
+ * max(max, -min) >= peak_min[t] (peak_min[t] != 0).  A plane with both values 0 is never loud.
+ *   HOT.  Row b is hot when it lies in an entry and at least min_planes planes are loud at b: min_planes == 1 is the union of
+ * the planes' loud rows, min_planes == n_planes their intersection.  Runs, join_bins, min_bins, pad_bins, clipping to the
+ * entry, pieces of max_bins, start, len, order and disjointness, d_count possibly above cap and the fillers are the EVENTS'
+ * on these hot rows.
+ *   PER EVENT, beside entry, start and len: d_event_planes[i] (uint32, cap elements, may be NULL): bit t is set when plane t
+ * is loud in at least one row of the piece, padding rows included -- a padding row loud in fewer than min_planes planes still
+ * sets its bits; a piece of a cut run that holds padding or gap rows alone may have no bit set.  d_event_levels (may be
+ * NULL): n_planes planes of cap records, plane stride cap; record (t, i) is the merge of plane t's records over the piece's
+ * rows.  Fillers: mask 0 and the identity record in every plane.
+ *   THRESHOLDS PER ENTRY.  d_thr is NULL or a device array (8-byte aligned) of x3_event_threshold laid plane-major:
+ * n_planes records for the stream form, n_planes * n_entries for the corpus form, d_thr[t * n_entries + e] for plane t of
+ * entry e -- what n_planes calls of x3_level_thresholds_dev / x3_corpus_level_thresholds_dev write at d_thr + t * n_entries
+ * (they may be enqueued back to back; their pending slot is simply overwritten).  With d_thr the rule's mean_sq_min[] and
+ * peak_min[] must all be 0.  d_thr is untrusted exactly as in x3_events_adaptive_dev: a value above its limit makes that
+ * criterion never loud, both values 0 leave that plane of that entry never loud, counted is ignored.
+ *   n_planes == 1, min_planes == 1 gives byte for byte the arrays of x3_events_dev / x3_corpus_events_dev with the rule
+ * {mean_sq_min[0], peak_min[0], ...}, and with d_thr those of the adaptive calls.
+ *   Asynchronous on the context's stream: one launch set, no host trip.  The calls share the events' pending slot and
+ * workspace, as the adaptive calls do (x3_events_result waits); the workspace does not depend on n_planes.  The rule is
+ * copied at the call; records and d_thr are read when the kernels run.  X3_ERR_BAD_ARG with nothing enqueued, and an earlier
+ * pending result left as it was, for everything x3_events_dev / x3_corpus_events_dev refuses, n_planes 0 or above 8,
+ * min_planes 0 or above n_planes, reserved != 0, plane_stride < n_bins or above 0x7FFFFFFF, a mean_sq_min[t] above 1 << 30 or a peak_min[t] above
+ * 32768 for t < n_planes, without d_thr fewer than min_planes planes with a criterion on, with d_thr any non-zero value in
+ * the rule or a misaligned d_thr, and a misaligned d_event_planes (4 bytes).  Values behind n_planes are never read. */
+#define X3_EVENT_PLANES_MAX 8
+typedef struct x3_plane_event_rule {          /* 128 bytes */
+  uint32_t n_planes;                          /* 1 .. X3_EVENT_PLANES_MAX */
+  uint32_t min_planes;                        /* 1 .. n_planes: a row is hot when so many planes are loud at it */
+  uint32_t join_bins, min_bins, pad_bins, max_bins;   /* x3_event_rule's, same meaning and limits */
+  uint32_t reserved[2];                       /* 0 */
+  uint64_t mean_sq_min[X3_EVENT_PLANES_MAX];  /* per plane; 0: off; entries behind n_planes are never read */
+  uint32_t peak_min[X3_EVENT_PLANES_MAX];     /* per plane; 0: off */
+} x3_plane_event_rule;
+int x3_plane_events_dev(x3_ctx* ctx, const x3_level* d_levels, uint64_t plane_stride, uint64_t n_bins, uint64_t bin_len,
+                        const uint64_t* d_total, const x3_plane_event_rule* rule, const x3_event_threshold* d_thr,
+                        uint64_t* d_starts, uint32_t* d_lens, uint32_t* d_event_planes, x3_level* d_event_levels,
+                        uint64_t cap, uint64_t* d_count);
+int x3_corpus_plane_events_dev(x3_ctx* ctx, const x3_corpus* corpus, const x3_level* d_levels, uint64_t plane_stride,
+                               uint64_t n_rows, uint64_t bin_len, const x3_plane_event_rule* rule,
+                               const x3_event_threshold* d_thr, uint32_t* d_entries, uint64_t* d_starts, uint32_t* d_lens,
+                               uint32_t* d_event_planes, x3_level* d_event_levels, uint64_t cap, uint64_t* d_count);
 /* ---- RANGE LEVELS (no counterpart in the reference): the level records of ranges (entry, start, len), bins counted from
  * each range's own start -- a second look inside events at finer bins, a zoomed overview, peak and RMS of any sample-exact
  * cut.  The work follows the ranges (their covering frames), not the stream.

@@ -41,7 +41,12 @@ Families: (e) the single-pass encoders on block_len 20 with mixed content, many 
           equal ones among them, the family's own step in one slot -- against the same table, garbage in the spare steps;
           every plane GPU == tests/tone_range_levels_ref.py at its step and == the single call's bytes, what no call writes
           keeps its fill in every plane, then the same ranges on the corpus, plane by plane the single corpus call's bytes
-          (not in the default family set)."""
+          (not in the default family set); (v) plane events (x3_plane_events_dev / x3_corpus_plane_events_dev) on the band
+          planes of a drawn tone bank over a random, possibly damaged stream: random K, min_planes, per-plane values (keys of
+          the planes' own records, planes switched off), plane stride with loud records in the slack, rule, cap, NULL
+          outputs, d_thr per (plane, entry) or none -- values off and above their limits among them -- GPU ==
+          tests/plane_events_ref.py in every slot; bank_events (no host trip) on the same rule; then the same frames as a
+          corpus of random entries (not in the default family set)."""
 import argparse, ctypes as C, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "x3-rust_amd"))
@@ -1330,6 +1335,198 @@ fams["t"] = lambda rng, tag: fam_r(rng, tag, fir=draw_fir(rng))
 fams["p"] = lambda rng, tag: fam_r(rng, tag, tone=True)
 fams["q"] = lambda rng, tag: fam_h(rng, tag, bank=True)
 fams["u"] = lambda rng, tag: fam_r(rng, tag, tone=True, bank=True)
+
+
+def _plane_events_check(rng, tag, what, planes, bin_len, corpus, d_total, n_samples, total):
+    """one drawn plane events call on the K planes `planes` (np, LEVEL_DTYPE [K, rows]) against plane_events_ref: a drawn
+    rule whose values are keys of the planes' own records, min_planes, a plane stride with loud records in the slack, d_thr
+    per (plane, entry) or none, a drawn cap, outputs left out now and then; every slot of every output with =="""
+    import levels_ref as LR
+    import plane_events_ref as PE
+    K, n_rows = planes.shape
+    n_ent = len(n_samples) if corpus is not None else 1
+    join = int(rng.choice([0, 1, 2, 5, 40]))
+    mb = int(rng.choice([0, 0, 1, 3, 64, 200]))
+    if mb * bin_len > 0xFFFFFFFF:
+        mb = 0
+    use_thr = rng.random() < 0.4
+
+    def values(t):   # the two values of plane t: keys of its own counting records, so that some rows are loud; or off
+        rec = planes[t][planes[t]["n"] != 0]
+        if rec.size == 0 or rng.random() < 0.1:
+            return 0, 0
+        r = rec[int(rng.integers(0, rec.size))]
+        m = min(max(int(r["sum_sq"]) // int(r["n"]), 1), 1 << 30)
+        p = min(max(int(r["max"]), -int(r["min"]), 1), 32768)
+        c = int(rng.integers(0, 3))
+        return (m if c != 0 else 0), (p if c != 1 else 0)
+    vals = [values(t) for t in range(K)]
+    on = sum(1 for m, p in vals if m or p)
+    if on == 0:
+        vals[0], on = (1, 0), 1
+    mp = int(rng.integers(1, K + 1))
+    thr = None
+    if use_thr:   # per (plane, entry): the plane's values, or off, or above a limit; counted is garbage
+        def one(t):
+            m, p = vals[t]
+            how = rng.random()
+            return ((m, p) if how < 0.7 else (0, 0) if how < 0.8 else ((1 << 30) + 1, p) if how < 0.9 else (m, 32769)) + \
+                (int(rng.integers(0, 1 << 32)),)
+        thr = [[one(t) for _ in range(n_ent)] for t in range(K)]
+        vals = [(0, 0)] * K
+    else:
+        mp = min(mp, on)
+    rule = PE.PlaneRule([m for m, _ in vals], [p for _, p in vals], mp, join, int(rng.choice([0, 1, 2, 9])),
+                        int(rng.integers(0, join // 2 + 1)), mb)
+    if corpus is None:
+        ev, elv = PE.stream_plane_events(planes, total, bin_len, rule, None if thr is None else [t[0] for t in thr])
+    else:
+        ev, elv = PE.corpus_plane_events(planes, n_samples, bin_len, rule, thr)
+    cap = int(rng.choice([1, 3, max(len(ev), 1), len(ev) + 2]))
+    went, wst, wln, wmk, wlv = PE.slots(ev, elv, cap, corpus is not None)
+    stride = n_rows + int(rng.choice([0, 0, 5]))
+    up = np.stack([LR.empty(stride) for _ in range(K)])
+    up["n"], up["max"], up["sum_sq"] = 1, 32767, 1 << 30                # (the slack: loud under every rule, never read)
+    up[:, :n_rows] = planes
+    r = x3hip.PlaneEventRule.make(list(rule.mean_sq_min), list(rule.peak_min), mp, join, rule.min_bins, rule.pad_bins, mb)
+    for t in range(K, 8):                                               # garbage behind n_planes
+        r.mean_sq_min[t], r.peak_min[t] = int(rng.integers(0, 1 << 62)), int(rng.integers(0, 1 << 32))
+    with_mask, with_levels = rng.random() < 0.85, rng.random() < 0.85
+    sizes = [4 * cap, 8 * cap, 4 * cap, 4 * cap, 32 * K * cap, 8]
+    d = [ctx.alloc(32 * K * stride)] + [ctx.alloc(s) for s in sizes] + [ctx.alloc(16 * K * n_ent)]
+    try:
+        d_lv, d_ent, d_st, d_ln, d_mk, d_el, d_cnt, d_thr = d
+        ctx.upload(d_lv, up)
+        for q, s in zip(d[1:7], sizes):
+            ctx.upload(q, np.full(s, 0xA5, dtype=np.uint8))
+        if thr is not None:
+            a = np.zeros(K * n_ent, dtype=x3hip.EVENT_THRESHOLD_DTYPE)
+            a[:] = [v for t in thr for v in t]
+            ctx.upload(d_thr, a)
+        args = (r, d_thr if thr is not None else None)
+        outs = (d_st, d_ln, d_mk if with_mask else None, d_el if with_levels else None, cap, d_cnt)
+        if corpus is None:
+            rc = ctx.plane_events_dev(d_lv, stride, n_rows, bin_len, d_total, *args, *outs)
+        else:
+            rc = corpus.plane_events_into(d_lv, stride, n_rows, bin_len, *args, d_ent, *outs)
+        assert rc == 0, (tag, what, "rc", rc, ctx.last_error())
+        assert ctx.events_result() == (0, len(ev)), (tag, what, "count", len(ev))
+        got = [ctx.download(q, s) for q, s in zip(d[1:7], sizes)]
+        assert int(got[5].view(np.uint64)[0]) == len(ev), (tag, what, "d_count")
+        if corpus is not None:
+            assert np.array_equal(got[0].view(np.uint32), went), (tag, what, "entries")
+        else:
+            assert (got[0] == 0xA5).all(), (tag, what, "a stream call wrote entries")
+        assert np.array_equal(got[1].view(np.uint64), wst), (tag, what, "starts", rule, got[1].view(np.uint64)[:6], wst[:6])
+        assert np.array_equal(got[2].view(np.uint32), wln), (tag, what, "lens", rule)
+        if with_mask:
+            assert np.array_equal(got[3].view(np.uint32), wmk), (tag, what, "masks", rule, got[3].view(np.uint32)[:6], wmk[:6])
+        else:
+            assert (got[3] == 0xA5).all(), (tag, what, "a NULL mask array was written")
+        if with_levels:
+            assert got[4].tobytes() == wlv.tobytes(), (tag, what, "event levels", rule)
+        else:
+            assert (got[4] == 0xA5).all(), (tag, what, "a NULL event levels array was written")
+    finally:
+        for q in d:
+            ctx.free(q)
+    return rule, thr, ev, elv
+
+
+def fam_v(rng, tag):
+    """plane events: the band planes of a drawn tone bank over a random stream -- any geometry, damaged frames, whose bins
+    count nothing and are never loud -- held against tone_bank_levels_ref, then x3_plane_events_dev on them with a drawn K,
+    min_planes, per-plane values, plane stride, rule and d_thr or none, GPU == tests/plane_events_ref.py in every slot; the
+    chain bank levels -> plane events with no host trip (bank_events) on the same rule; then the same frames as a corpus of
+    random entries (x3_corpus_plane_events_dev, thresholds per plane and entry)"""
+    import levels_ref as LR
+    import plane_events_ref as PE
+    import tone_bank_levels_ref as TB
+    import tone_levels_ref as TR
+    p = x3hip.Params.default() if rng.random() < 0.6 else x3hip.Params.make(int(rng.choice([10, 20, 40])), int(rng.choice([25, 100, 256])))
+    spf = p.block_len * p.blocks_per_frame
+    n = int(rng.integers(1, 12 * min(spf, 4000) + 100))
+    wav = content(rng, n)
+    rc, stream, _ = O.encode(wav, oparams(p))
+    if rc != 0:
+        return
+    offs = frame_offsets(stream)
+    so = [0]
+    for off in offs:
+        so.append(so[-1] + (int(stream[off + 4]) << 8 | int(stream[off + 5])))
+    if so[-1] != n:
+        return
+    F = len(offs)
+    bad = stream.copy()
+    if rng.random() < 0.6:
+        for _ in range(int(rng.integers(1, 4))):
+            off = offs[int(rng.integers(0, F))]
+            plen = int(stream[off + 6]) << 8 | int(stream[off + 7])
+            if rng.random() < 0.5 and plen > 2:   # payload bits, CRC refreshed (a decode error or other samples) or not
+                q = off + 20 + int(rng.integers(2, plen))
+                k = min(int(rng.integers(1, 12)), off + 20 + plen - q)
+                bad[q:q + k] = rng.integers(0, 256, size=k, dtype=np.uint8)
+                if rng.random() < 0.7:
+                    refresh_crcs(bad, off)
+            else:                                 # a header byte other than the sample count and the payload length
+                bad[off + int(rng.choice([0, 1, 2, 3, 8, 12, 16, 17, 18, 19]))] ^= np.uint8(1 << int(rng.integers(0, 8)))
+    verdicts = _frame_verdicts(bad, offs, p)
+    statuses = [v for v, _ in verdicts]
+    frames = [w if v == 0 else np.zeros(0, dtype=np.int16) for v, w in verdicts]
+    bin_len = int(rng.choice([7, p.block_len, spf, spf + 1, max(1, n // int(rng.integers(1, 400)))]))
+    bin_len = max(bin_len, -(-n // 4000))          # (the reference walks every row of every plane in Python)
+    n_bins = max(1, LR.n_bins_for(n, bin_len) + int(rng.choice([0, 0, -1, 3])))
+    K = int(rng.integers(1, 9))
+    steps = [int(rng.choice([0, 1 << 30, int(rng.integers(0, 1 << 32)), int(rng.integers(0, 1 << 32)) | 1])) for _ in range(K)]
+    if K > 1 and rng.random() < 0.3:
+        steps[-1] = steps[0]                       # equal steps, equal planes
+    tones = [x3hip.Tone(s) for s in steps]
+    d = []
+    try:
+        d_off = ctx.alloc(8 * (F + 1)); d.append(d_off)
+        ctx.upload(d_off, np.array(offs + [stream.size], dtype=np.uint64))
+        src = x3hip.WindowSource(ctx, bad, p, seg_blocks=int(rng.choice([0, 8, 32])), frame_offsets=d_off, n_frames=F)
+        d.extend(src._own); src._own = []
+        planes, st = src.tone_bank_levels(bin_len, tones, n_bins, band=True)
+        assert st.tolist() == statuses, (tag, "statuses")
+        want = TB.tone_bank_levels(frames, statuses, so[:-1], bin_len, n_bins, steps)
+        assert all(planes[t].tobytes() == TR.tone_power_levels(want[t]).tobytes() for t in range(K)), (tag, "band planes")
+        rule, thr, ev, elv = _plane_events_check(rng, tag, "stream", planes, bin_len, None, src.d_sample_offsets + 8 * F, None, n)
+        if thr is None and n_bins == LR.n_bins_for(n, bin_len):   # the chain with no host trip, on the source's own bins
+            cap = len(ev) + 1
+            r = x3hip.PlaneEventRule.make(list(rule.mean_sq_min), list(rule.peak_min), rule.min_planes, rule.join_bins,
+                                          rule.min_bins, rule.pad_bins, rule.max_bins)
+            t_st, t_ln, t_cnt, t_mk, t_el = src.bank_events(bin_len, tones, r, cap)
+            _, wst, wln, wmk, wlv = PE.slots(ev, elv, cap, False)
+            assert int(t_cnt) == len(ev) and np.array_equal(t_st.cpu().numpy().view(np.uint64), wst), (tag, "bank_events starts")
+            assert np.array_equal(t_ln.cpu().numpy().view(np.uint32), wln) and np.array_equal(t_mk.cpu().numpy().view(np.uint32), wmk), \
+                (tag, "bank_events lens, masks")
+            assert t_el.cpu().numpy().tobytes() == wlv.tobytes(), (tag, "bank_events levels")
+        # the same bytes as a corpus: the frames cut into entries at random frame boundaries
+        cuts = sorted(set([0, F] + [int(v) for v in rng.integers(0, F + 1, int(rng.integers(0, 5)))]))
+        ends = offs + [stream.size]
+        try:
+            corpus = x3hip.Corpus(ctx, bad, [ends[a] for a in cuts[:-1]], [ends[b] - ends[a] for a, b in zip(cuts[:-1], cuts[1:])],
+                                  params=p, seg_blocks=8, index="walk")
+        except x3hip.X3Error:   # (a geometry the corpus build refuses an index for)
+            return
+        try:
+            if corpus.entries["n_frames"].tolist() == [b - a for a, b in zip(cuts[:-1], cuts[1:])]:
+                rows, rf, cst = corpus.tone_bank_levels(bin_len, tones, band=True)
+                ref = [(frames[a:b], statuses[a:b], [so[f] - so[a] for f in range(a, b)], so[b] - so[a])
+                       for a, b in zip(cuts[:-1], cuts[1:])]
+                wrows, wrf = TB.corpus_tone_bank_levels(ref, bin_len, steps)
+                assert np.array_equal(rf, wrf) and cst.tolist() == statuses, (tag, "corpus layout")
+                assert all(rows[t].tobytes() == TR.tone_power_levels(wrows[t]).tobytes() for t in range(K)), (tag, "corpus band planes")
+                _plane_events_check(rng, tag, "corpus", rows, bin_len, corpus, None, [e[3] for e in ref], None)
+        finally:
+            corpus.close()
+    finally:
+        for q in d:
+            ctx.free(q)
+
+
+fams["v"] = fam_v
 
 
 def run(seed=1, minutes=None, trials=None, families="egdbaf", only=-1, context=None):

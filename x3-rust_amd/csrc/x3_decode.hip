@@ -11,6 +11,7 @@
 #include "x3_seg_index_kernel.h"
 #include "x3_levels_kernel.h"
 #include "x3_events_kernel.h"
+#include "x3_plane_events_kernel.h"
 #include "x3_quantiles_kernel.h"
 #include "x3_range_levels_kernel.h"
 
@@ -2292,9 +2293,11 @@ static bool events_args_ok(const x3_ctx* c, const x3_level* d_levels, uint64_t n
 // The launch set of an events call.  q: the rows (its row_first is set here); k: the corpus of a corpus call, whose row
 // prefix the levels' kernel computes into the workspace first.  d_thr: the thresholds of an adaptive call, which differs in
 // its flag kernel alone (the other six take join_bins, min_bins, pad_bins and max_bins of the rule, never its two values).
+//   pl: the planes of a plane events call (x3_plane_events_kernel.h), which differs in its flag and emit kernels alone: the
+// five in between work on the hot bytes and the tile words, whatever made them.
 static int events_launch(x3_ctx* c, X3EvRows q, const x3_corpus* k, const x3_event_rule& rule, const x3_event_threshold* d_thr,
                          uint32_t* d_entries, uint64_t* d_starts, uint32_t* d_lens, x3_level* d_event_levels, uint64_t cap,
-                         uint64_t* d_count) {
+                         uint64_t* d_count, const X3EvPlanes* pl = nullptr, uint32_t* d_event_planes = nullptr) {
   HIPCHK(c, hipSetDevice(c->device));
   EvWs w;
   int rc;
@@ -2303,7 +2306,13 @@ static int events_launch(x3_ctx* c, X3EvRows q, const x3_corpus* k, const x3_eve
   const uint64_t n_tiles = (q.n_rows + X3E_TILE - 1) / X3E_TILE;
   const dim3 g_tiles(grid_for(n_tiles, 1));
   corpus_row_prefix(c, k, q.bin_len, w.row_first, &q);
-  if (d_thr)
+  if (pl && pl->thr)
+    hipLaunchKernelGGL(x3_plane_events_flag_kernel<true>, g_tiles, dim3(256), 0, c->stream, q, *pl, n_tiles, w.hot, w.tile_prev,
+                       w.tile_next);
+  else if (pl)
+    hipLaunchKernelGGL(x3_plane_events_flag_kernel<false>, g_tiles, dim3(256), 0, c->stream, q, *pl, n_tiles, w.hot, w.tile_prev,
+                       w.tile_next);
+  else if (d_thr)
     hipLaunchKernelGGL(x3_events_adaptive_flag_kernel, g_tiles, dim3(256), 0, c->stream, q, d_thr, n_tiles, w.hot, w.tile_prev,
                        w.tile_next);
   else
@@ -2317,9 +2326,14 @@ static int events_launch(x3_ctx* c, X3EvRows q, const x3_corpus* k, const x3_eve
   hipLaunchKernelGGL(x3_events_runs_kernel, dim3(1), dim3(1024), 0, c->stream, q, rule, w.run_first, w.run_last, w.piece_off, w.sum,
                      d_count);
   // (the count is on the device: a wave per slot of the caller's arrays at most, grid-stride)
-  hipLaunchKernelGGL(x3_events_emit_kernel, dim3(grid_for(cap, 4)), dim3(256), 0, c->stream, q, rule, (const uint32_t*)w.run_first,
-                     (const uint32_t*)w.run_last, (const unsigned long long*)w.piece_off, (const X3EvSummary*)w.sum, cap, d_entries,
-                     d_starts, d_lens, d_event_levels);
+  if (pl)
+    hipLaunchKernelGGL(x3_plane_events_emit_kernel, dim3(grid_for(cap, 4)), dim3(256), 0, c->stream, q, *pl,
+                       (const uint32_t*)w.run_first, (const uint32_t*)w.run_last, (const unsigned long long*)w.piece_off,
+                       (const X3EvSummary*)w.sum, cap, d_entries, d_starts, d_lens, d_event_planes, d_event_levels);
+  else
+    hipLaunchKernelGGL(x3_events_emit_kernel, dim3(grid_for(cap, 4)), dim3(256), 0, c->stream, q, rule, (const uint32_t*)w.run_first,
+                       (const uint32_t*)w.run_last, (const unsigned long long*)w.piece_off, (const X3EvSummary*)w.sum, cap, d_entries,
+                       d_starts, d_lens, d_event_levels);
   HIPCHK(c, hipGetLastError());
   c->events.pending = true;
   c->events.count = cap;
@@ -2373,6 +2387,72 @@ extern "C" int x3_corpus_events_adaptive_dev(x3_ctx* c, const x3_corpus* k, cons
                                              uint64_t cap, uint64_t* d_count) {
   return events_call(c, k, "x3_corpus_events_adaptive_dev", d_levels, n_rows, bin_len, nullptr, rule, true, d_thr, d_entries,
                      d_starts, d_lens, d_event_levels, cap, d_count);
+}
+
+// plane events: the events of one synthetic row verdict over K planes of records (x3_plane_events_kernel.h; DESIGN.md
+// section 28).  The checks are events_args_ok's on the rule's four run values, then the planes' own.
+static_assert(sizeof(x3_plane_event_rule) == 128 && offsetof(x3_plane_event_rule, min_planes) == 4 &&
+                  offsetof(x3_plane_event_rule, join_bins) == 8 && offsetof(x3_plane_event_rule, max_bins) == 20 &&
+                  offsetof(x3_plane_event_rule, reserved) == 24 && offsetof(x3_plane_event_rule, mean_sq_min) == 32 &&
+                  offsetof(x3_plane_event_rule, peak_min) == 96,
+              "include/x3hip.h states this layout");
+
+static int plane_events_call(x3_ctx* c, const x3_corpus* k, const char* corpus_entry, const x3_level* d_levels,
+                             uint64_t plane_stride, uint64_t n_rows, uint64_t bin_len, const uint64_t* d_total,
+                             const x3_plane_event_rule* rule, const x3_event_threshold* d_thr, uint32_t* d_entries,
+                             uint64_t* d_starts, uint32_t* d_lens, uint32_t* d_event_planes, x3_level* d_event_levels,
+                             uint64_t cap, uint64_t* d_count) {
+  if (!rule || (corpus_entry && !k)) return X3_ERR_BAD_ARG;
+  const x3_event_rule runs{0, 0, rule->join_bins, rule->min_bins, rule->pad_bins, rule->max_bins, 0};
+  x3_event_rule eff;
+  if (!events_args_ok(c, d_levels, n_rows, bin_len, &runs, d_starts, d_lens, d_event_levels, cap, d_count, &eff, true))
+    return X3_ERR_BAD_ARG;
+  if (rule->n_planes == 0 || rule->n_planes > X3_EVENT_PLANES_MAX || rule->min_planes == 0 || rule->min_planes > rule->n_planes ||
+      rule->reserved[0] || rule->reserved[1] || plane_stride < n_rows || plane_stride > 0x7FFFFFFFull)   // (n_rows' own limit:
+    return X3_ERR_BAD_ARG;                                     //  t * plane_stride + r stays below 2^34 records, 2^39 bytes)
+  uint32_t on = 0;
+  for (uint32_t t = 0; t < rule->n_planes; ++t) {
+    if (rule->mean_sq_min[t] > (1ull << 30) || rule->peak_min[t] > 32768u) return X3_ERR_BAD_ARG;
+    on += (rule->mean_sq_min[t] || rule->peak_min[t]) ? 1u : 0u;
+  }
+  if (d_thr ? (on != 0 || (reinterpret_cast<uintptr_t>(d_thr) & 7u)) : on < rule->min_planes) return X3_ERR_BAD_ARG;
+  if (reinterpret_cast<uintptr_t>(d_event_planes) & 3u) return X3_ERR_BAD_ARG;
+  if (corpus_entry && (!d_entries || (reinterpret_cast<uintptr_t>(d_entries) & 3u))) return X3_ERR_BAD_ARG;
+  X3EvRows q;
+  const int rc = corpus_entry ? corpus_rows(c, k, d_levels, n_rows, bin_len, corpus_entry, &q)
+                              : stream_rows(d_levels, n_rows, bin_len, d_total, &q);
+  if (rc) return rc;
+  X3EvPlanes pl{};                                  // (the values behind n_planes stay 0: never copied, never read)
+  pl.rule.n_planes = rule->n_planes;
+  pl.rule.min_planes = rule->min_planes;
+  pl.rule.join_bins = eff.join_bins;
+  pl.rule.min_bins = eff.min_bins;
+  pl.rule.pad_bins = eff.pad_bins;
+  pl.rule.max_bins = eff.max_bins;
+  for (uint32_t t = 0; t < rule->n_planes; ++t) {
+    pl.rule.mean_sq_min[t] = rule->mean_sq_min[t];
+    pl.rule.peak_min[t] = rule->peak_min[t];
+  }
+  pl.stride = plane_stride;
+  pl.thr = d_thr;
+  return events_launch(c, q, k, eff, nullptr, d_entries, d_starts, d_lens, d_event_levels, cap, d_count, &pl, d_event_planes);
+}
+
+extern "C" int x3_plane_events_dev(x3_ctx* c, const x3_level* d_levels, uint64_t plane_stride, uint64_t n_bins, uint64_t bin_len,
+                                   const uint64_t* d_total, const x3_plane_event_rule* rule, const x3_event_threshold* d_thr,
+                                   uint64_t* d_starts, uint32_t* d_lens, uint32_t* d_event_planes, x3_level* d_event_levels,
+                                   uint64_t cap, uint64_t* d_count) {
+  return plane_events_call(c, nullptr, nullptr, d_levels, plane_stride, n_bins, bin_len, d_total, rule, d_thr, nullptr, d_starts,
+                           d_lens, d_event_planes, d_event_levels, cap, d_count);
+}
+
+extern "C" int x3_corpus_plane_events_dev(x3_ctx* c, const x3_corpus* k, const x3_level* d_levels, uint64_t plane_stride,
+                                          uint64_t n_rows, uint64_t bin_len, const x3_plane_event_rule* rule,
+                                          const x3_event_threshold* d_thr, uint32_t* d_entries, uint64_t* d_starts,
+                                          uint32_t* d_lens, uint32_t* d_event_planes, x3_level* d_event_levels, uint64_t cap,
+                                          uint64_t* d_count) {
+  return plane_events_call(c, k, "x3_corpus_plane_events_dev", d_levels, plane_stride, n_rows, bin_len, nullptr, rule, d_thr,
+                           d_entries, d_starts, d_lens, d_event_planes, d_event_levels, cap, d_count);
 }
 
 extern "C" int x3_events_result(x3_ctx* c, uint64_t* count) {

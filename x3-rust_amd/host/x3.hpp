@@ -958,6 +958,54 @@ inline X3Error events_adaptive(Context& ctx, const x3_level* d_levels, uint64_t 
   return static_cast<X3Error>(x3_events_result(ctx.raw(), count));
 }
 
+// The rule of plane_events (x3_plane_event_rule): a row is hot when at least min_planes planes are loud at it, plane t under
+// mean_sq_min[t] and peak_min[t] (0: off; both empty: the values come from d_thr); the other four as in x3_event_rule.
+// planes: the number of planes when there are no values.
+struct PlaneEventRule {
+  std::vector<uint64_t> mean_sq_min;
+  std::vector<uint32_t> peak_min;
+  uint32_t min_planes = 1, join_bins = 0, min_bins = 0, pad_bins = 0, max_bins = 0, planes = 0;
+  size_t n_planes() const {
+    const size_t k = mean_sq_min.size() > peak_min.size() ? mean_sq_min.size() : peak_min.size();
+    return k > planes ? k : planes;
+  }
+  bool ok() const {
+    const size_t k = n_planes();
+    return k >= 1 && k <= X3_EVENT_PLANES_MAX && (mean_sq_min.empty() || mean_sq_min.size() == k) &&
+           (peak_min.empty() || peak_min.size() == k);
+  }
+  x3_plane_event_rule c_rule() const {
+    x3_plane_event_rule r{};
+    r.n_planes = (uint32_t)n_planes();
+    r.min_planes = min_planes;
+    r.join_bins = join_bins;
+    r.min_bins = min_bins;
+    r.pad_bins = pad_bins;
+    r.max_bins = max_bins;
+    for (size_t t = 0; t < mean_sq_min.size() && t < X3_EVENT_PLANES_MAX; ++t) r.mean_sq_min[t] = mean_sq_min[t];
+    for (size_t t = 0; t < peak_min.size() && t < X3_EVENT_PLANES_MAX; ++t) r.peak_min[t] = peak_min[t];
+    return r;
+  }
+};
+
+// Plane events (x3_plane_events_dev): the events of the rows that are loud in at least rule.min_planes of the rule's planes
+// of n_bins level records, plane t at d_levels + t * plane_stride records (what device::tone_bank_levels and
+// tone_power_levels over all planes write with plane_stride = n_bins).  d_thr: nullptr, or one x3_event_threshold per plane
+// and a rule without values.  Beside device::events' outputs: d_event_planes (uint32, cap elements, or nullptr): bit t set
+// when plane t is loud in the event; d_event_levels (or nullptr): a plane of cap merged records per plane.  Waits for the
+// call: *count = the events found.
+inline X3Error plane_events(Context& ctx, const x3_level* d_levels, uint64_t plane_stride, uint64_t n_bins, uint64_t bin_len,
+                            const uint64_t* d_total, const PlaneEventRule& rule, const x3_event_threshold* d_thr,
+                            uint64_t* d_starts, uint32_t* d_lens, uint32_t* d_event_planes, x3_level* d_event_levels, uint64_t cap,
+                            uint64_t* d_count, uint64_t* count) {
+  if (!rule.ok()) return X3Error::BadArg;
+  const x3_plane_event_rule r = rule.c_rule();
+  int rc = x3_plane_events_dev(ctx.raw(), d_levels, plane_stride, n_bins, bin_len, d_total, &r, d_thr, d_starts, d_lens,
+                               d_event_planes, d_event_levels, cap, d_count);
+  if (rc != X3_OK) return static_cast<X3Error>(rc);
+  return static_cast<X3Error>(x3_events_result(ctx.raw(), count));
+}
+
 // Range levels (x3_range_levels_dev): the x3_level records of range w = positions [d_starts[w], d_starts[w] + d_lens[w]), bins
 // of bin_len positions counted from the range's own start (0: one bin), max(1, ceil(len / bin_len)) rows each; a frame with a
 // status other than 0 adds nothing and gives the range its status.  row_stride 0: rows packed at the exclusive sum of all row
@@ -1178,6 +1226,20 @@ class Corpus {
                           x3_level* d_event_levels, uint64_t cap, uint64_t* d_count, uint64_t* count) const {
     int rc = x3_corpus_events_adaptive_dev(ctx.raw(), raw_, d_levels, n_rows, bin_len, &rule, d_thr, d_entries, d_starts, d_lens,
                                            d_event_levels, cap, d_count);
+    if (rc != X3_OK) return static_cast<X3Error>(rc);
+    return static_cast<X3Error>(x3_events_result(ctx.raw(), count));
+  }
+  // Plane events of every entry (x3_corpus_plane_events_dev) over the rule's planes of the n_rows records levels() lays: as
+  // device::plane_events, with the events' entries in d_entries; d_thr: nullptr, or n_planes * n_entries records laid
+  // plane-major.  Waits for the call.
+  X3Error plane_events(Context& ctx, const x3_level* d_levels, uint64_t plane_stride, uint64_t n_rows, uint64_t bin_len,
+                       const PlaneEventRule& rule, const x3_event_threshold* d_thr, uint32_t* d_entries, uint64_t* d_starts,
+                       uint32_t* d_lens, uint32_t* d_event_planes, x3_level* d_event_levels, uint64_t cap, uint64_t* d_count,
+                       uint64_t* count) const {
+    if (!rule.ok()) return X3Error::BadArg;
+    const x3_plane_event_rule r = rule.c_rule();
+    int rc = x3_corpus_plane_events_dev(ctx.raw(), raw_, d_levels, plane_stride, n_rows, bin_len, &r, d_thr, d_entries, d_starts,
+                                        d_lens, d_event_planes, d_event_levels, cap, d_count);
     if (rc != X3_OK) return static_cast<X3Error>(rc);
     return static_cast<X3Error>(x3_events_result(ctx.raw(), count));
   }

@@ -144,6 +144,21 @@ pub mod ffi {
         pub peak_min: u32,
         pub counted: u32,
     }
+    /// `x3_plane_event_rule`: a row is hot when at least `min_planes` of `n_planes` planes are loud at it, each plane under
+    /// its own two values (`x3_plane_events_dev`; 128 bytes)
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+    pub struct x3_plane_event_rule {
+        pub n_planes: u32,
+        pub min_planes: u32,
+        pub join_bins: u32,
+        pub min_bins: u32,
+        pub pad_bins: u32,
+        pub max_bins: u32,
+        pub reserved: [u32; 2],
+        pub mean_sq_min: [u64; 8],
+        pub peak_min: [u32; 8],
+    }
     #[repr(C)]
     #[derive(Clone, Copy, Debug)]
     pub struct x3_rice_code {
@@ -313,6 +328,15 @@ pub mod ffi {
                                              bin_len: u64, rule: *const x3_event_rule, d_thr: *const x3_event_threshold,
                                              d_entries: *mut u32, d_starts: *mut u64, d_lens: *mut u32,
                                              d_event_levels: *mut x3_level, cap: u64, d_count: *mut u64) -> c_int;
+        pub fn x3_plane_events_dev(ctx: *mut x3_ctx, d_levels: *const x3_level, plane_stride: u64, n_bins: u64, bin_len: u64,
+                                   d_total: *const u64, rule: *const x3_plane_event_rule, d_thr: *const x3_event_threshold,
+                                   d_starts: *mut u64, d_lens: *mut u32, d_event_planes: *mut u32,
+                                   d_event_levels: *mut x3_level, cap: u64, d_count: *mut u64) -> c_int;
+        pub fn x3_corpus_plane_events_dev(ctx: *mut x3_ctx, corpus: *const x3_corpus, d_levels: *const x3_level, plane_stride: u64,
+                                          n_rows: u64, bin_len: u64, rule: *const x3_plane_event_rule,
+                                          d_thr: *const x3_event_threshold, d_entries: *mut u32, d_starts: *mut u64,
+                                          d_lens: *mut u32, d_event_planes: *mut u32, d_event_levels: *mut x3_level, cap: u64,
+                                          d_count: *mut u64) -> c_int;
         pub fn x3_range_levels_dev(ctx: *mut x3_ctx, d_x3: *const u8, x3_len: u64, d_frame_offsets: *const u64,
                                    d_sample_offsets: *const u64, n_frames: u64, p: *const x3_params, d_seg_index: *const u64,
                                    seg_blocks: u32, d_starts: *const u64, d_lens: *const u32, n_ranges: u64, bin_len: u64,
@@ -1788,6 +1812,44 @@ pub mod device {
         Ok(count)
     }
 
+    /// The rule of `plane_events` / `corpus_plane_events` (`x3_plane_event_rule`): a row is hot when at least `min_planes` of
+    /// `n_planes` planes are loud at it, plane t under `mean_sq_min[t]` and `peak_min[t]`; the other four as in `EventRule`
+    pub type PlaneEventRule = ffi::x3_plane_event_rule;
+
+    /// Plane events (`x3_plane_events_dev`; not in the reference crate): the events of the rows that are loud in at least
+    /// `rule.min_planes` of `rule.n_planes` planes of `n_bins` level records, plane t at `d_levels + t * plane_stride` records.
+    /// `d_thr`: `None`, or an `EventThreshold` per plane (then `rule` carries no values).  Beside `events`' outputs:
+    /// `d_event_planes` (u32, `cap` elements, optional): bit t set when plane t is loud in the event; `d_event_levels`
+    /// (optional): `n_planes` planes of `cap` records.  Waits: -> the events found
+    #[allow(clippy::too_many_arguments)]
+    pub fn plane_events<'g>(gpu: &'g Gpu, d_levels: &Buffer<'g>, plane_stride: usize, n_bins: usize, bin_len: u64,
+                            sample_offsets: &Buffer<'g>, n_frames: usize, rule: &PlaneEventRule, d_thr: Option<&Buffer<'g>>,
+                            d_starts: &mut Buffer<'g>, d_lens: &mut Buffer<'g>, d_event_planes: Option<&mut Buffer<'g>>,
+                            d_event_levels: Option<&mut Buffer<'g>>, cap: usize, d_count: &mut Buffer<'g>) -> error::Result<u64> {
+        let k = rule.n_planes as usize;
+        if k == 0 || k > 8 || plane_stride < n_bins
+            || d_levels.len() < core::mem::size_of::<Level>() * ((k - 1) * plane_stride + n_bins)
+            || sample_offsets.len() < 8 * (n_frames + 1)
+            || d_thr.as_ref().map_or(false, |b| b.len() < core::mem::size_of::<EventThreshold>() * k)
+            || d_starts.len() < 8 * cap || d_lens.len() < 4 * cap || d_count.len() < 8
+            || d_event_planes.as_ref().map_or(false, |b| b.len() < 4 * cap)
+            || d_event_levels.as_ref().map_or(false, |b| b.len() < core::mem::size_of::<Level>() * k * cap) {
+            return Err(X3Error::BadArg);
+        }
+        let thr_ptr = match d_thr { Some(b) => b.as_ptr::<EventThreshold>() as *const EventThreshold, None => core::ptr::null() };
+        let ep_ptr = match d_event_planes { Some(b) => b.as_ptr::<u32>(), None => core::ptr::null_mut() };
+        let el_ptr = match d_event_levels { Some(b) => b.as_ptr::<Level>(), None => core::ptr::null_mut() };
+        error::check(unsafe {
+            ffi::x3_plane_events_dev(gpu.raw(), d_levels.as_ptr::<Level>() as *const Level, plane_stride as u64, n_bins as u64,
+                                     bin_len, (sample_offsets.as_ptr::<u64>() as *const u64).add(n_frames), rule, thr_ptr,
+                                     d_starts.as_ptr::<u64>(), d_lens.as_ptr::<u32>(), ep_ptr, el_ptr, cap as u64,
+                                     d_count.as_ptr::<u64>())
+        })?;
+        let mut count = 0u64;
+        error::check(unsafe { ffi::x3_events_result(gpu.raw(), &mut count) })?;
+        Ok(count)
+    }
+
     /// Range levels (`x3_range_levels_dev`; not in the reference crate): the `Level` records of range w = positions
     /// `[starts[w], starts[w] + lens[w])`, bins of `bin_len` positions counted from the range's own start (0: one bin), max(1,
     /// ceil(len / bin_len)) rows each.  A frame with a status other than 0 adds nothing and gives the range its status.
@@ -2213,6 +2275,38 @@ pub mod device {
             error::check(unsafe { ffi::x3_events_result(self.gpu.raw(), &mut count) })?;
             Ok(count)
         }
+    }
+
+    /// Plane events of every entry (`x3_corpus_plane_events_dev`) over `rule.n_planes` planes of the `n_rows` records
+    /// `Corpus::levels` lays: as `device::plane_events`, with the events' entries in `d_entries`; `d_thr`: `None`, or
+    /// `n_planes * n_entries` records laid plane-major.  Waits: -> the events found
+    #[allow(clippy::too_many_arguments)]
+    pub fn corpus_plane_events<'g>(corpus: &Corpus<'g>, d_levels: &Buffer<'g>, plane_stride: usize, n_rows: usize, bin_len: u64,
+                                   rule: &PlaneEventRule, d_thr: Option<&Buffer<'g>>, d_entries: &mut Buffer<'g>,
+                                   d_starts: &mut Buffer<'g>, d_lens: &mut Buffer<'g>, d_event_planes: Option<&mut Buffer<'g>>,
+                                   d_event_levels: Option<&mut Buffer<'g>>, cap: usize,
+                                   d_count: &mut Buffer<'g>) -> error::Result<u64> {
+        let (k, n_ent) = (rule.n_planes as usize, corpus.info().0 as usize);
+        if k == 0 || k > 8 || plane_stride < n_rows
+            || d_levels.len() < core::mem::size_of::<Level>() * ((k - 1) * plane_stride + n_rows)
+            || d_thr.as_ref().map_or(false, |b| b.len() < core::mem::size_of::<EventThreshold>() * k * n_ent)
+            || d_entries.len() < 4 * cap || d_starts.len() < 8 * cap || d_lens.len() < 4 * cap || d_count.len() < 8
+            || d_event_planes.as_ref().map_or(false, |b| b.len() < 4 * cap)
+            || d_event_levels.as_ref().map_or(false, |b| b.len() < core::mem::size_of::<Level>() * k * cap) {
+            return Err(X3Error::BadArg);
+        }
+        let thr_ptr = match d_thr { Some(b) => b.as_ptr::<EventThreshold>() as *const EventThreshold, None => core::ptr::null() };
+        let ep_ptr = match d_event_planes { Some(b) => b.as_ptr::<u32>(), None => core::ptr::null_mut() };
+        let el_ptr = match d_event_levels { Some(b) => b.as_ptr::<Level>(), None => core::ptr::null_mut() };
+        error::check(unsafe {
+            ffi::x3_corpus_plane_events_dev(corpus.gpu.raw(), corpus.raw, d_levels.as_ptr::<Level>() as *const Level,
+                                            plane_stride as u64, n_rows as u64, bin_len, rule, thr_ptr, d_entries.as_ptr::<u32>(),
+                                            d_starts.as_ptr::<u64>(), d_lens.as_ptr::<u32>(), ep_ptr, el_ptr, cap as u64,
+                                            d_count.as_ptr::<u64>())
+        })?;
+        let mut count = 0u64;
+        error::check(unsafe { ffi::x3_events_result(corpus.gpu.raw(), &mut count) })?;
+        Ok(count)
     }
 
     impl<'g> Corpus<'g> {

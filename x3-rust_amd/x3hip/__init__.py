@@ -68,6 +68,7 @@ SYMBOLS = [
     "x3_events_dev", "x3_corpus_events_dev", "x3_events_result",
     "x3_level_quantiles_dev", "x3_corpus_level_quantiles_dev", "x3_level_quantiles_result",
     "x3_level_thresholds_dev", "x3_corpus_level_thresholds_dev", "x3_events_adaptive_dev", "x3_corpus_events_adaptive_dev",
+    "x3_plane_events_dev", "x3_corpus_plane_events_dev",
     "x3_range_levels_dev", "x3_corpus_range_levels_dev", "x3_range_levels_result",
     "x3_signal_range_levels_dev", "x3_corpus_signal_range_levels_dev",
     "x3_fir_range_levels_dev", "x3_corpus_fir_range_levels_dev",
@@ -248,6 +249,30 @@ class EventRule(C.Structure):
 
 EVENT_RULE_DTYPE = np.dtype([("mean_sq_min", "<u8"), ("peak_min", "<u4"), ("join_bins", "<u4"), ("min_bins", "<u4"),
                              ("pad_bins", "<u4"), ("max_bins", "<u4"), ("reserved", "<u4")])
+
+
+EVENT_PLANES_MAX = 8   # X3_EVENT_PLANES_MAX: the planes of one plane events call
+
+
+class PlaneEventRule(C.Structure):
+    """x3_plane_event_rule: a row is hot when at least min_planes of n_planes planes are loud at it, each plane under its own
+    two values; join_bins, min_bins, pad_bins and max_bins are EventRule's (x3_plane_events_dev)"""
+    _fields_ = [("n_planes", C.c_uint32), ("min_planes", C.c_uint32), ("join_bins", C.c_uint32), ("min_bins", C.c_uint32),
+                ("pad_bins", C.c_uint32), ("max_bins", C.c_uint32), ("reserved", C.c_uint32 * 2),
+                ("mean_sq_min", C.c_uint64 * EVENT_PLANES_MAX), ("peak_min", C.c_uint32 * EVENT_PLANES_MAX)]
+
+    @classmethod
+    def make(cls, mean_sq_min=None, peak_min=None, min_planes=1, join_bins=0, min_bins=0, pad_bins=0, max_bins=0, n_planes=None):
+        """mean_sq_min, peak_min: a value per plane (one of them may be left out: all 0); n_planes: their length unless
+        given, which a rule for thresholds per entry needs (no values at all)"""
+        ms, pk = list(mean_sq_min or []), list(peak_min or [])
+        k = max(len(ms), len(pk)) if n_planes is None else int(n_planes)
+        if not 1 <= k <= EVENT_PLANES_MAX or len(ms) not in (0, k) or len(pk) not in (0, k):
+            raise ValueError("1 .. %d planes, a value per plane" % EVENT_PLANES_MAX)
+        r = cls(k, min_planes, join_bins, min_bins, pad_bins, max_bins)
+        for t in range(k):
+            r.mean_sq_min[t], r.peak_min[t] = (ms[t] if ms else 0), (pk[t] if pk else 0)
+        return r
 
 
 LEVEL_KEY_PEAK, LEVEL_KEY_MEAN_SQ = 0, 1   # x3_level_quantiles_dev: max(max, -min) / floor(sum_sq / n)
@@ -455,6 +480,8 @@ def lib():
     L.x3_corpus_level_thresholds_dev.argtypes = [vp, vp, vp, u64, u64, C.POINTER(ThresholdRule), vp]
     L.x3_events_adaptive_dev.argtypes = [vp, vp, u64, u64, vp, C.POINTER(EventRule), vp, vp, vp, vp, u64, vp]
     L.x3_corpus_events_adaptive_dev.argtypes = [vp, vp, vp, u64, u64, C.POINTER(EventRule), vp, vp, vp, vp, vp, u64, vp]
+    L.x3_plane_events_dev.argtypes = [vp, vp, u64, u64, u64, vp, C.POINTER(PlaneEventRule), vp, vp, vp, vp, vp, u64, vp]
+    L.x3_corpus_plane_events_dev.argtypes = [vp, vp, vp, u64, u64, u64, C.POINTER(PlaneEventRule), vp, vp, vp, vp, vp, vp, u64, vp]
     L.x3_range_levels_dev.argtypes = [vp, vp, u64, vp, vp, u64, PP, vp, u32, vp, vp, u64, u64, u64, vp, u64, vp, vp]
     L.x3_corpus_range_levels_dev.argtypes = [vp, vp, vp, vp, vp, u64, u64, u64, vp, u64, vp, vp]
     L.x3_signal_range_levels_dev.argtypes = [vp, vp, u64, vp, vp, u64, PP, vp, u32, vp, vp, u64, u64, u64, vp, u64, vp, vp, C.c_int]
@@ -1353,6 +1380,22 @@ class Context:
         return lib().x3_corpus_events_adaptive_dev(self._h, corpus._h, d_levels, n_rows, bin_len, C.byref(rule), d_thr, d_entries,
                                                    d_starts, d_lens, d_event_levels, cap, d_count)
 
+    def plane_events_dev(self, d_levels, plane_stride, n_bins, bin_len, d_total, rule, d_thr, d_starts, d_lens, d_event_planes,
+                         d_event_levels, cap, d_count):
+        """x3_plane_events_dev: the runs of bins loud in at least rule.min_planes of rule.n_planes planes of n_bins level
+        records (plane t at d_levels + t * plane_stride records; rule: a PlaneEventRule) as cap slots of (start u64, len u32,
+        mask of the planes loud in the event u32 or None, merged x3_level [n_planes, cap] or None); d_thr: None, or the
+        EVENT_THRESHOLD_DTYPE record of every plane (then the rule has no values); asynchronous; events_result waits"""
+        return lib().x3_plane_events_dev(self._h, d_levels, plane_stride, n_bins, bin_len, d_total, C.byref(rule), d_thr, d_starts,
+                                         d_lens, d_event_planes, d_event_levels, cap, d_count)
+
+    def corpus_plane_events_dev(self, corpus, d_levels, plane_stride, n_rows, bin_len, rule, d_thr, d_entries, d_starts, d_lens,
+                                d_event_planes, d_event_levels, cap, d_count):
+        """x3_corpus_plane_events_dev: the same over planes of the rows of Context.corpus_levels_dev, d_entries (u32) as well;
+        d_thr: None, or records [n_planes, n_entries]; asynchronous"""
+        return lib().x3_corpus_plane_events_dev(self._h, corpus._h, d_levels, plane_stride, n_rows, bin_len, C.byref(rule), d_thr,
+                                                d_entries, d_starts, d_lens, d_event_planes, d_event_levels, cap, d_count)
+
     def range_levels_dev(self, d_x3, x3_len, d_frame_offsets, d_sample_offsets, n_frames, params, d_starts, d_lens, n_ranges,
                          bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status, d_seg_index=None, seg_blocks=0):
         """x3_range_levels_dev: the x3_level records of range w = [d_starts[w], d_starts[w] + d_lens[w]), bins of bin_len
@@ -1704,6 +1747,77 @@ def _adaptive_events_torch(ctx, n_rows, n_ent, capacity, with_entries, enqueue_l
         rq = ctx.level_quantiles_result()[0]    # (its own slot: read whatever the events call said)
         return rc or rq
     return _events_torch(ctx, n_rows, capacity, with_entries, enqueue_levels, both) + (thr,)
+
+
+def _plane_events_torch(src, levels, n_planes, bin_len, rule, capacity, with_entries, enqueue_events, *, thresholds=None,
+                        enqueue_levels=None, enqueue_thresholds=None):
+    """The torch side of plane_events / bank_events / adaptive_bank_events of src, a WindowSource or a Corpus.
+    levels: a uint8 [K, rows, 32] device tensor of records of any origin, or None: K = n_planes planes of src's own rows
+    that enqueue_levels(d_levels, n_rows) -> rc fills.  thresholds: None or a uint8 [K, n_entries, 16] device tensor;
+    enqueue_thresholds(d_plane, n_rows, d_thr) -> rc, called per plane, fills one made here, which is then returned too.
+    enqueue_events(d_levels, n_rows, d_thr, d_entries, d_starts, d_lens, d_event_planes, d_event_levels, d_count) -> rc.
+    Everything is enqueued back to back on the context's stream ->
+    ([entries,] starts, lens, count, planes int32 [capacity], event_levels uint8 [K, capacity, 32][, thresholds])"""
+    import torch
+    ctx = src.ctx
+    capacity = int(capacity)
+    if capacity <= 0:
+        raise ValueError("capacity: at least one slot")
+    if not 0 < bin_len <= 0xFFFFFFFF:
+        raise ValueError("bin_len: 1 .. 2^32 - 1")
+    rec = LEVEL_DTYPE.itemsize
+    if levels is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+        levels = torch.empty((n_planes, src._levels_rows(bin_len)[0], rec), dtype=torch.uint8, device=dev)
+    elif not (isinstance(levels, torch.Tensor) and levels.is_cuda and levels.dtype == torch.uint8 and levels.dim() == 3 and
+              1 <= levels.shape[0] <= EVENT_PLANES_MAX and levels.shape[1] > 0 and levels.shape[2] == rec):
+        raise ValueError("levels: a uint8 tensor [K, rows, 32] on the device, K 1 .. %d" % EVENT_PLANES_MAX)
+    elif levels.shape[1] != src._levels_rows(bin_len)[0]:   # (fewer would cut the detection short, more are never looked at)
+        raise ValueError("levels: %d rows, but bins of %d positions over this source are %d rows"
+                         % (levels.shape[1], bin_len, src._levels_rows(bin_len)[0]))
+    levels = levels.contiguous()
+    dev, k, n_rows = levels.device, levels.shape[0], levels.shape[1]
+    if rule.n_planes != k:
+        raise ValueError("the rule is one of %d planes, the records have %d" % (rule.n_planes, k))
+    n_ent = src.n_entries if with_entries else 1
+    thr_rec = EVENT_THRESHOLD_DTYPE.itemsize
+    if enqueue_thresholds is not None:
+        thresholds = torch.empty((k, n_ent, thr_rec), dtype=torch.uint8, device=dev)
+    elif thresholds is not None:
+        if not (isinstance(thresholds, torch.Tensor) and thresholds.is_cuda and thresholds.dtype == torch.uint8 and
+                tuple(thresholds.shape) == (k, n_ent, thr_rec)):
+            raise ValueError("thresholds: a uint8 tensor [%d, %d, 16] on the device" % (k, n_ent))
+        thresholds = thresholds.contiguous()
+    entries = torch.empty(capacity, dtype=torch.int32, device=dev) if with_entries else None
+    starts = torch.empty(capacity, dtype=torch.int64, device=dev)
+    lens = torch.empty(capacity, dtype=torch.int32, device=dev)
+    planes = torch.empty(capacity, dtype=torch.int32, device=dev)
+    event_levels = torch.empty((k, capacity, rec), dtype=torch.uint8, device=dev)
+    count = torch.empty((), dtype=torch.int64, device=dev)
+    torch.cuda.current_stream().synchronize()    # (the context's stream is not torch's)
+    d_lv = levels.data_ptr()
+    if enqueue_levels is not None:
+        rc = enqueue_levels(d_lv, n_rows)
+        if rc:
+            raise X3Error(rc, "levels: " + ctx.last_error())
+    rc = 0
+    if enqueue_thresholds is not None:
+        for t in range(k):       # (their pending slot is simply overwritten: one result call serves all K)
+            rc = rc or enqueue_thresholds(d_lv + t * n_rows * rec, n_rows, thresholds.data_ptr() + t * n_ent * thr_rec)
+    rc = rc or enqueue_events(d_lv, n_rows, thresholds.data_ptr() if thresholds is not None else None,
+                              entries.data_ptr() if with_entries else None, starts.data_ptr(), lens.data_ptr(),
+                              planes.data_ptr(), event_levels.data_ptr(), count.data_ptr())
+    # (every slot this call has made pending is read, whatever an earlier one said)
+    r_ev = 0 if rc else ctx.events_result()[0]
+    r_q = ctx.level_quantiles_result()[0] if enqueue_thresholds is not None else 0
+    r_lv = ctx.levels_result()[0] if enqueue_levels is not None else 0
+    ctx.sync()
+    rc = rc or r_ev or r_q or r_lv
+    if rc:
+        raise X3Error(rc, "plane events: " + ctx.last_error())
+    out = (starts, lens, count, planes, event_levels)
+    out = (entries,) + out if with_entries else out
+    return out + (thresholds,) if enqueue_thresholds is not None else out
 
 
 def _levels_np(src, what, bin_len, n_rows, dtype, enqueue, planes=None):
@@ -2064,6 +2178,44 @@ class WindowSource:
             lambda d_lv, d_t: self.level_thresholds_into(d_lv, n_bins, bin_len, threshold_rule, d_t),
             lambda d_lv, d_t, d_e, d_s, d_l, d_el, d_c: self.adaptive_events_into(d_lv, n_bins, bin_len, rule, d_t, d_s, d_l, d_el,
                                                                                   capacity, d_c))
+
+    def plane_events_into(self, d_levels, plane_stride, n_bins, bin_len, rule, d_thr, d_starts, d_lens, d_event_planes,
+                          d_event_levels, cap, d_count):
+        """enqueue x3_plane_events_dev over rule.n_planes planes of n_bins records of this source (device pointers; rule: a
+        PlaneEventRule; d_thr: None or a record per plane); -> rc; Context.events_result waits"""
+        return self.ctx.plane_events_dev(d_levels, plane_stride, n_bins, bin_len, self.d_sample_offsets + 8 * self.n_frames, rule,
+                                         d_thr, d_starts, d_lens, d_event_planes, d_event_levels, cap, d_count)
+
+    def _plane_events(self, levels, n_planes, bin_len, rule, capacity, **kw):
+        return _plane_events_torch(
+            self, levels, n_planes, bin_len, rule, capacity, False,
+            lambda d_lv, n, d_t, d_e, d_s, d_l, d_p, d_el, d_c: self.plane_events_into(d_lv, n, n, bin_len, rule, d_t, d_s, d_l,
+                                                                                      d_p, d_el, capacity, d_c), **kw)
+
+    def plane_events(self, levels, bin_len, rule, capacity, *, thresholds=None):
+        """The runs of bins that are loud in at least rule.min_planes of K planes of level records (levels: a uint8 torch
+        tensor [K, bins, 32] on the device, records of any origin over this source's bins of bin_len positions -- exactly
+        as many rows as cover the stream, anything else is a ValueError; rule: a
+        PlaneEventRule; thresholds: None, or uint8 [K, 1, 16] records on the device and a rule without values) as ONE
+        ordered, disjoint list of ranges -> (starts int64 [capacity], lens int32 [capacity], count 0-d int64, planes int32
+        [capacity]: bit t set when plane t is loud in the event, event_levels uint8 [K, capacity, 32]) on the device"""
+        return self._plane_events(levels, None, bin_len, rule, capacity, thresholds=thresholds)
+
+    def bank_events(self, bin_len, tones, rule, capacity):
+        """tone_bank_levels_into(..., band=True), then plane_events over its planes, no wait in between -> as plane_events;
+        tone_bank_range_levels(starts, lens, ...) takes the tensors as they are"""
+        tones = tone_bank(tones)
+        return self._plane_events(None, len(tones), bin_len, rule, capacity,
+                                  enqueue_levels=lambda d_lv, n: self.tone_bank_levels_into(bin_len, tones, d_lv, n, band=True))
+
+    def adaptive_bank_events(self, bin_len, tones, threshold_rule, rule, capacity):
+        """bank_events with the two values of every plane (none in `rule`) chosen on the device by `threshold_rule` (a
+        ThresholdRule), a thresholds call per plane in between -> as plane_events, and thresholds uint8 [K, 1, 16]"""
+        tones = tone_bank(tones)
+        return self._plane_events(None, len(tones), bin_len, rule, capacity,
+                                  enqueue_levels=lambda d_lv, n: self.tone_bank_levels_into(bin_len, tones, d_lv, n, band=True),
+                                  enqueue_thresholds=lambda d_lv, n, d_t: self.level_thresholds_into(d_lv, n, bin_len,
+                                                                                                     threshold_rule, d_t))
 
     def close(self):
         for p in self._own:
@@ -2497,6 +2649,43 @@ class Corpus:
             lambda d_lv, d_t: self.level_thresholds_into(d_lv, n_rows, bin_len, threshold_rule, d_t),
             lambda d_lv, d_t, d_e, d_s, d_l, d_el, d_c: self.adaptive_events_into(d_lv, n_rows, bin_len, rule, d_t, d_e, d_s, d_l,
                                                                                   d_el, capacity, d_c))
+
+    def plane_events_into(self, d_levels, plane_stride, n_rows, bin_len, rule, d_thr, d_entries, d_starts, d_lens, d_event_planes,
+                          d_event_levels, cap, d_count):
+        """enqueue x3_corpus_plane_events_dev over rule.n_planes planes of the n_rows records Context.corpus_levels_dev wrote
+        (device pointers; d_thr: None or records [n_planes, n_entries]); -> rc; Context.events_result waits"""
+        if self._h is None:
+            raise ValueError("the corpus is closed")
+        return self.ctx.corpus_plane_events_dev(self, d_levels, plane_stride, n_rows, bin_len, rule, d_thr, d_entries, d_starts,
+                                                d_lens, d_event_planes, d_event_levels, cap, d_count)
+
+    def _plane_events(self, levels, n_planes, bin_len, rule, capacity, **kw):
+        return _plane_events_torch(
+            self, levels, n_planes, bin_len, rule, capacity, True,
+            lambda d_lv, n, d_t, d_e, d_s, d_l, d_p, d_el, d_c: self.plane_events_into(d_lv, n, n, bin_len, rule, d_t, d_e, d_s,
+                                                                                      d_l, d_p, d_el, capacity, d_c), **kw)
+
+    def plane_events(self, levels, bin_len, rule, capacity, *, thresholds=None):
+        """WindowSource.plane_events over K planes of the rows of levels() (levels: uint8 [K, rows, 32]; thresholds: None or
+        uint8 [K, n_entries, 16]); runs never cross an entry -> (entries int32, starts int64, lens int32 [capacity each],
+        count 0-d int64, planes int32 [capacity], event_levels uint8 [K, capacity, 32]) on the device"""
+        return self._plane_events(levels, None, bin_len, rule, capacity, thresholds=thresholds)
+
+    def bank_events(self, bin_len, tones, rule, capacity):
+        """tone_bank_levels_into(..., band=True), then plane_events over its planes, no wait in between -> as plane_events;
+        tone_bank_range_levels(entries, starts, lens, ...) takes the tensors as they are"""
+        tones = tone_bank(tones)
+        return self._plane_events(None, len(tones), bin_len, rule, capacity,
+                                  enqueue_levels=lambda d_lv, n: self.tone_bank_levels_into(bin_len, tones, d_lv, n, band=True))
+
+    def adaptive_bank_events(self, bin_len, tones, threshold_rule, rule, capacity):
+        """bank_events with the two values of every plane of every entry (none in `rule`) chosen on the device by
+        `threshold_rule`, a thresholds call per plane in between -> as plane_events, and thresholds uint8 [K, n_entries, 16]"""
+        tones = tone_bank(tones)
+        return self._plane_events(None, len(tones), bin_len, rule, capacity,
+                                  enqueue_levels=lambda d_lv, n: self.tone_bank_levels_into(bin_len, tones, d_lv, n, band=True),
+                                  enqueue_thresholds=lambda d_lv, n, d_t: self.level_thresholds_into(d_lv, n, bin_len,
+                                                                                                     threshold_rule, d_t))
 
     def close(self):
         if self._h is not None:
