@@ -1166,9 +1166,9 @@ def fam_h(rng, tag, fir=False, tone=False, bank=False):
             return x3hip.LevelTone(step, 0, tone_tabs[-1])
         ref_stream = lambda fr, st, so_, bl, nb: TR.tone_levels(fr, st, so_, bl, nb, step, tab)
         ref_corpus = lambda ref, bl: TR.corpus_tone_levels(ref, bl, step, tab)
-        stream_levels = lambda src, bl, nb: src._levels_np("x3_tone_levels_dev", bl, nb, x3hip.TONE_DTYPE,
+        stream_levels = lambda src, bl, nb: x3hip._levels_np(src, "x3_tone_levels_dev", bl, nb, x3hip.TONE_DTYPE,
                                                            lambda d_lv, n_, d_st: src.tone_levels_into(bl, level_tone(tab), d_lv, n_, d_st))
-        corpus_levels = lambda corpus, bl: corpus._levels_np("x3_corpus_tone_levels_dev", bl, x3hip.TONE_DTYPE,
+        corpus_levels = lambda corpus, bl: x3hip._levels_np(corpus, "x3_corpus_tone_levels_dev", bl, None, x3hip.TONE_DTYPE,
                                                              lambda d_lv, n_, d_st: corpus.tone_levels_into(bl, level_tone(tab), d_lv, n_, d_st))
     if bank:   # family (q): the planes of a drawn tone bank and table, against tone_bank_levels_ref
         import tone_bank_levels_ref as TB
@@ -1189,11 +1189,11 @@ def fam_h(rng, tag, fir=False, tone=False, bank=False):
             return x3hip.LevelToneBank(n_tones, 0, d_tab, (C.c_uint32 * 8)(*(steps + [0xDEADBEEF] * (8 - n_tones))))
         ref_stream = lambda fr, st, so_, bl, nb: TB.tone_bank_levels(fr, st, so_, bl, nb, steps, tab)
         ref_corpus = lambda ref, bl: TB.corpus_tone_bank_levels(ref, bl, steps, tab)
-        stream_levels = lambda src, bl, nb: src._levels_np(
-            "x3_tone_bank_levels_dev", bl, nb, x3hip.TONE_DTYPE,
+        stream_levels = lambda src, bl, nb: x3hip._levels_np(
+            src, "x3_tone_bank_levels_dev", bl, nb, x3hip.TONE_DTYPE,
             lambda d_lv, n_, d_st: src.tone_bank_levels_into(bl, level_bank(), d_lv, n_, d_st), planes=n_tones)
-        corpus_levels = lambda corpus, bl: corpus._levels_np(
-            "x3_corpus_tone_bank_levels_dev", bl, x3hip.TONE_DTYPE,
+        corpus_levels = lambda corpus, bl: x3hip._levels_np(
+            corpus, "x3_corpus_tone_bank_levels_dev", bl, None, x3hip.TONE_DTYPE,
             lambda d_lv, n_, d_st: corpus.tone_bank_levels_into(bl, level_bank(), d_lv, n_, d_st), planes=n_tones)
     r = rng.random()
     if r < 0.5:
@@ -1282,7 +1282,7 @@ def fam_h(rng, tag, fir=False, tone=False, bank=False):
         old, _ = src.levels(bin_len, n_bins)
         if bank:   # every plane is the single call's bytes; the adapter over all planes at once on the usual table's records
             for t, step in enumerate(steps):
-                one, _ = src._levels_np("x3_tone_levels_dev", bin_len, n_bins, x3hip.TONE_DTYPE,
+                one, _ = x3hip._levels_np(src, "x3_tone_levels_dev", bin_len, n_bins, x3hip.TONE_DTYPE,
                                         lambda d_lv, n_, d_st: src.tone_levels_into(
                                             bin_len, x3hip.LevelTone(step, 0, tone_tabs[-1] if tab is not None else ctx.tone_table_dev()),
                                             d_lv, n_, d_st))
@@ -1291,7 +1291,7 @@ def fam_h(rng, tag, fir=False, tone=False, bank=False):
                 band, _ = src.tone_bank_levels(bin_len, [x3hip.Tone(v) for v in steps], n_bins, band=True)
                 assert all(band[t].tobytes() == TR.tone_power_levels(want[t]).tobytes() for t in range(n_tones)), (tag, "adapter")
         elif tone:   # a table of all (1, 0): the sums of the levels call; the adapter on the usual table's records
-            same, _ = src._levels_np("x3_tone_levels_dev", bin_len, n_bins, x3hip.TONE_DTYPE,
+            same, _ = x3hip._levels_np(src, "x3_tone_levels_dev", bin_len, n_bins, x3hip.TONE_DTYPE,
                                      lambda d_lv, n_, d_st: src.tone_levels_into(bin_len, level_tone(ones), d_lv, n_, d_st))
             assert np.array_equal(same["re"], old["sum"]) and not same["im"].any(), (tag, "ones")
             assert all(np.array_equal(same[k], old[k]) for k in ("min", "max", "n")), (tag, "ones: min, max, n")
@@ -1393,10 +1393,11 @@ def _plane_events_check(rng, tag, what, planes, bin_len, corpus, d_total, n_samp
         r.mean_sq_min[t], r.peak_min[t] = int(rng.integers(0, 1 << 62)), int(rng.integers(0, 1 << 32))
     with_mask, with_levels = rng.random() < 0.85, rng.random() < 0.85
     sizes = [4 * cap, 8 * cap, 4 * cap, 4 * cap, 32 * K * cap, 8]
-    d = [ctx.alloc(32 * K * stride)] + [ctx.alloc(s) for s in sizes] + [ctx.alloc(16 * K * n_ent)]
+    held = (K - 1) * stride + n_rows   # (the header's minimum: plane t is the n_rows records at t * stride, no slack behind the last)
+    d = [ctx.alloc(32 * held)] + [ctx.alloc(s) for s in sizes] + [ctx.alloc(16 * K * n_ent)]
     try:
         d_lv, d_ent, d_st, d_ln, d_mk, d_el, d_cnt, d_thr = d
-        ctx.upload(d_lv, up)
+        ctx.upload(d_lv, up.reshape(-1)[:held])
         for q, s in zip(d[1:7], sizes):
             ctx.upload(q, np.full(s, 0xA5, dtype=np.uint8))
         if thr is not None:

@@ -14,8 +14,11 @@ int ensure(x3_ctx* c, DevBuf& b, size_t bytes) {
   if (b.p) HIPCHK(c, x3_dfree(b.p));
   b.p = nullptr;
   b.cap = 0;
-  size_t want = std::max(bytes, (size_t)4096);
-  want = (want + 255) & ~(size_t)255;
+  size_t want = bytes;
+  if (!x3_fence_tight()) {   // (X3HIP_FENCE_TIGHT under X3HIP_FENCE: exactly `bytes`, the workspace's last piece ends the mapping)
+    want = std::max(bytes, (size_t)4096);
+    want = (want + 255) & ~(size_t)255;
+  }
   HIPCHK(c, x3_dmalloc(&b.p, want));
   b.cap = want;
   return X3_OK;

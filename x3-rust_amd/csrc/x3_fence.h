@@ -11,6 +11,15 @@
 // Kernels of this library read their input in aligned 16-byte chunks, so up to 15 bytes behind the last byte of a buffer
 // are read by design (never across a 16-byte line, hence never across a page): <align> = 16 is the tightest fence that
 // design passes.
+//
+// The library's own workspaces (ensure(), x3_ctx.hip) are rounded up to 256 bytes with a floor of 4 096, so an overrun
+// behind the last piece of a carved workspace stays inside the mapping even under the fence.  X3HIP_FENCE_TIGHT=1 (read
+// once, like X3HIP_FENCE, and without meaning unless the fence is on) makes ensure() ask for exactly the bytes a call
+// needs: the fence's own rounding to <align> then puts the end of the last carved piece on the mapping's last line.
+// Growth is unchanged (only when a call needs more than the buffer holds, never shrinking), so a context's first large
+// call still sizes what later small ones run in: tests/test_gpu_fence_analysis.py starts a fresh context per group.
+// What the fence cannot see: bytes IN FRONT of a buffer's first byte (up to a granule of them are mapped), pieces of a
+// workspace other than its last, and the device memory that does not come from x3_dmalloc (a corpus's own tables).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -32,6 +41,14 @@ inline size_t x3_fence_align() {
     return v;
   }();
   return a;
+}
+// X3HIP_FENCE_TIGHT=1 (read once; means nothing without X3HIP_FENCE): ensure() asks for exactly the bytes of a workspace
+inline bool x3_fence_tight() {
+  static const bool t = [] {
+    const char* e = getenv("X3HIP_FENCE_TIGHT");
+    return x3_fence_align() != 0 && e && *e && strtoull(e, nullptr, 10) != 0;
+  }();
+  return t;
 }
 inline std::mutex& x3_fence_mutex() { static std::mutex m; return m; }
 inline std::unordered_map<void*, X3FenceRec>& x3_fence_map() { static std::unordered_map<void*, X3FenceRec> m; return m; }

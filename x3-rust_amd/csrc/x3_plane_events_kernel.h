@@ -13,8 +13,10 @@
 // LOUD is x3e_loud on the rule's values, which the host has held to their limits, and x3q_loud (x3_quantiles_kernel.h) on
 // d_thr's, which nobody has: each value is tested against its limit first.  The emit kernel uses x3q_loud for both.
 //
-// Bounds.  A record is read at t * plane_stride + r in 64 bits with r < n_rows <= plane_stride < 2^31 and t < n_planes <= 8, inside
-// the n_planes * plane_stride records the caller vouches for; thr at t * n_ent + e with e < n_ent by x3w_owner (n_ent 1 and
+// Bounds.  A record is read at t * plane_stride + r in 64 bits with r < n_rows <= plane_stride < 2^31 and t < n_planes <= 8: plane
+// t is the n_rows records at d_levels + t * plane_stride, so the (n_planes - 1) * plane_stride + n_rows records the header asks
+// the caller for hold every read -- the records between n_rows and plane_stride are never read, behind the last plane they
+// need not exist; thr at t * n_ent + e with e < n_ent by x3w_owner (n_ent 1 and
 // e 0 in the stream form); an event level is written at t * cap + i with i < cap; the mask at i < cap.
 #pragma once
 #include "x3_quantiles_kernel.h"
