@@ -1304,6 +1304,56 @@ int x3_corpus_tone_bank_range_levels_dev(x3_ctx* ctx, const x3_corpus* corpus, c
                                          const uint64_t* d_starts, const uint32_t* d_lens, uint64_t n_ranges, uint64_t bin_len,
                                          uint64_t row_stride, x3_tone_level* d_levels, uint64_t rows_cap,
                                          uint64_t* d_row_offsets, int32_t* d_status, const x3_level_tone_bank* bank);
+/* ---- SPECTRA (no counterpart in the reference): the exact integer STFT of int16 rows that lie in HBM as
+ * x3_decode_ranges_dev / x3_corpus_ranges_dev wrote them -- what an event looks like, every bin of every frame, where the
+ * tone bank stops at eight frequencies.  The products run on the matrix cores
+ * (v_mfma_i32_16x16x64_i8: a 16 x 16 bit product is four 8 x 8 bit ones), the results are integers held with ==.
+ *   THE RULE is a host struct, copied at the call: n_fft = N in {64, 128, 256, 512, 1024}, hop = H in 1 .. 2^31 - 1, and
+ * d_table, x3_level_tone's caller-owned device table of 1 024 (cos, sin) int16 pairs, read when the kernels run; any
+ * contents are legal.  B = N / 2 + 1 bins.  For a row of len samples x[0 .. len):
+ *     R = 0 when len < N, else (len - N) / H + 1 frames -- whole frames only, there is no partial last frame;
+ *     frame r is x[r * H .. r * H + N);  bin k <= N / 2 of it is
+ *     re = sum over n < N of x[r * H + n] * cos[((n * k) mod N) * (1024 / N)],   im = the same against sin,
+ * int64 and exact, |re| <= N * 2^30.  THE OSCILLATOR RESTARTS AT EVERY FRAME, as in any STFT: unlike the tone range-levels
+ * calls, which cut the stream's phase, equal samples give equal spectra wherever the row begins.  When a frame's first
+ * sample sits at a position p0 of its stream or entry with p0 mod N == 0, bin k equals re and im of
+ * x3_tone_range_levels_dev on the range (p0, N) with bin_len = N, step = k * 2^32 / N and the same table (and plane t of
+ * the bank call with steps[t] = k_t * 2^32 / N); a table of all (1, 0) gives re == the frame's sum of samples, im == 0.
+ *   FORMATS.  X3_SPECTRA_SUMS: an output row is B pairs (re, im) of int64, 16 * B bytes.  X3_SPECTRA_POWER: B uint32,
+ * each x3_tone_power_levels_dev's ms at n = N, word for word: a = re >> 15; b = im >> 15; P = a * a + b * b;
+ * ms = min(2^30, floor(floor(2 * P / N) / N)) -- on an aligned frame that record's sum_sq / n.
+ *   ROWS IN.  Row w is d_lens[w] samples at d_samples + d_offsets[w]; d_offsets[n_ranges] is never read, so a padded
+ * layout's w * stride serves as well as a packed call's offsets.  d_in_status is the ranges call's status array, or NULL
+ * for "all 0"; it may equal d_status (in place).  Offsets, lengths and statuses are device data and untrusted.
+ *   d_status[w] is, in this order: the in-status when it is not 0; X3_ERR_BAD_ARG when d_offsets[w] + d_lens[w] >
+ * samples_cap; X3_ERR_BAD_ARG when the range's rows do not fit (below); else 0.  A range whose status is not 0 has rows
+ * of zeros only -- the zeros the ranges call leaves behind a failed frame are never transformed -- and R(w) follows from
+ * the length alone, for such ranges too.
+ *   ROWS OUT, by x3_range_levels_dev's layout rules.  PACKED (row_stride == 0): range w's rows begin at row
+ * d_row_offsets[w], the exclusive sum of all R(w) (n_ranges + 1 words, required); a range that ends past rows_cap is
+ * X3_ERR_BAD_ARG and nothing of it is written; x3_spectra_result reports the total, so a caller grows d_out and repeats.
+ * PADDED (row_stride > 0): rows begin at w * row_stride, rows [R(w), row_stride) are zeros; R(w) > row_stride is
+ * X3_ERR_BAD_ARG and a row block of zeros; n_ranges * row_stride > rows_cap fails the call; d_row_offsets may be NULL.
+ *   Nothing outside d_out[0 .. rows_cap) rows, d_status[0 .. n_ranges) and d_row_offsets[0 .. n_ranges] is written,
+ * nothing outside d_samples[0 .. samples_cap) and the table is read.  Asynchronous on the context's stream: one launch set,
+ * no host trip, nothing allocated after the first call of a size; the call has its own pending slot and workspace and
+ * leaves the states of every other call alone.  x3_spectra_result waits: ranges with status != 0, the first of them
+ * (n_ranges if none) with its status, and the sum of all R(w); X3_ERR_BAD_ARG when no call is pending.
+ *   X3_ERR_BAD_ARG with nothing enqueued, the rule's checks before every other argument: a NULL rule, an n_fft outside
+ * the five values, hop == 0 or above 2^31 - 1, an unknown format, reserved != 0, a NULL or misaligned (4 bytes) d_table;
+ * then n_ranges == 0 or above 0x7FFFFFFF, rows_cap == 0 or above 0x7FFFFFFF, a NULL or misaligned pointer (d_samples: 2
+ * bytes; d_lens, d_in_status, d_status: 4; d_offsets, d_out, d_row_offsets: 8; d_row_offsets NULL only when padded), a
+ * context that is recording a graph.  No window function, no transform above 1 024 or off the powers of two. */
+#define X3_SPECTRA_SUMS  0
+#define X3_SPECTRA_POWER 1
+typedef struct x3_spectra_rule {   /* 24 bytes, host struct, copied at the call */
+  uint32_t n_fft, hop, format, reserved /* 0 */;
+  const int16_t* d_table;          /* device, 4-byte aligned, read when the kernels run */
+} x3_spectra_rule;
+int x3_spectra_rows_dev(x3_ctx* ctx, const int16_t* d_samples, uint64_t samples_cap, const uint64_t* d_offsets,
+                        const uint32_t* d_lens, const int32_t* d_in_status, uint64_t n_ranges, const x3_spectra_rule* rule,
+                        uint64_t row_stride, void* d_out, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status);
+int x3_spectra_result(x3_ctx* ctx, uint64_t* n_bad, uint64_t* first_bad, int* first_bad_status, uint64_t* total_rows);
 void x3_corpus_destroy(x3_corpus* corpus);
 
 /* ------------------------------------------------------------------ multi-GPU (no reference analogue) */

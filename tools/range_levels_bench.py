@@ -365,7 +365,8 @@ def cases(src, a, results, info):
     torch.cuda.empty_cache()
 
 
-def config3(ctx, a, results, info):
+def config3(ctx, a, results, info, run=None):
+    """run: what to do with the source (default: this tool's cases); other tools take the source from here"""
     lib = x3hip.lib()
     n, p, sig = a.samples, x3hip.Params.default(), a.fir or a.tone or x3hip.level_signal(a.signal)
     wav = torch.empty(n + 32, dtype=torch.int16, device="cuda")
@@ -405,10 +406,10 @@ def config3(ctx, a, results, info):
                                                                                                   d_off, d_st, idx.data_ptr(), 32, tone),
         lambda d_e, d_s, d_l, k, bl, stride, d_lv, c, d_off, d_st: ctx.tone_bank_range_levels_dev(*s, d_s, d_l, k, bl, stride, d_lv, c,
                                                                                                  d_off, d_st, idx.data_ptr(), 32, a.tones))
-    cases(src, a, results, info)
+    (run or cases)(src, a, results, info)
 
 
-def corpus_a(ctx, a, results, info):
+def corpus_a(ctx, a, results, info, run=None):
     lib = x3hip.lib()
     rng = np.random.default_rng(7)
     ns = [int(v) for v in rng.integers(441_000, 661_500 + 1, 4000)]
@@ -456,7 +457,7 @@ def corpus_a(ctx, a, results, info):
                                                                                                     c, d_o, d_st, tone),
         lambda d_e, d_s, d_l, k, bl, stride, d_lv, c, d_o, d_st: corpus.tone_bank_range_levels_into(d_e, d_s, d_l, k, bl, stride, d_lv, c,
                                                                                                    d_o, d_st, a.tones))
-    cases(src, a, results, info)
+    (run or cases)(src, a, results, info)
     corpus.close()
     for q in (d_x3, d_off):
         ctx.free(q)

@@ -298,7 +298,7 @@ extern "C" void x3_ctx_destroy(x3_ctx* c) {
   if (c->fcache) x3_reader_close(c->fcache);
   for (DevBuf* b : {&c->in, &c->out, &c->in_more[0], &c->in_more[1], &c->out_more[0], &c->out_more[1], &c->frame_bytes, &c->frame_off, &c->dec_status, &c->dec_cstatus, &c->dec_meta, &c->wav_off,
                     &c->seg_crc, &c->desc, &c->idx_cand, &c->idx_keys, &c->idx_vals, &c->idx_J, &c->idx_S,
-                    &c->idx_L, &c->idx_sum, &c->idx_wg, &c->idx_sorted, &c->idx_scan, &c->dense_list, &c->lb_desc, &c->src_tab, &c->win_ws, &c->lev_ws, &c->fir_ws, &c->ev_ws, &c->q_ws, &c->rlev_ws, &c->st_walk, &c->st_ws,
+                    &c->idx_L, &c->idx_sum, &c->idx_wg, &c->idx_sorted, &c->idx_scan, &c->dense_list, &c->lb_desc, &c->src_tab, &c->win_ws, &c->lev_ws, &c->fir_ws, &c->ev_ws, &c->q_ws, &c->rlev_ws, &c->spec_ws, &c->st_walk, &c->st_ws,
                     &c->st_one, &c->st_row})
     if (b->p) (void)x3_dfree(b->p);
   for (auto& t : c->timers) {

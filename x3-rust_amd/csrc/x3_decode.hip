@@ -14,6 +14,7 @@
 #include "x3_plane_events_kernel.h"
 #include "x3_quantiles_kernel.h"
 #include "x3_range_levels_kernel.h"
+#include "x3_spectra_kernel.h"
 
 // ------------------------------------------------------------------------------------------------
 // decode
@@ -2951,5 +2952,90 @@ extern "C" int x3_range_levels_result(x3_ctx* c, uint64_t* n_bad, uint64_t* firs
   c->last_range_levels_overflow = h.overflow;
   first_bad_of(h.w.n_bad, h.w.first, c->range_levels.count, n_bad, first_bad, first_bad_status);
   if (total_rows) *total_rows = h.w.total;
+  return X3_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// spectra: the exact integer STFT of int16 rows in HBM, on the matrix cores (x3_spectra_kernel.h)
+// ------------------------------------------------------------------------------------------------
+static_assert(sizeof(x3_spectra_rule) == 24 && offsetof(x3_spectra_rule, hop) == 4 && offsetof(x3_spectra_rule, format) == 8 &&
+                  offsetof(x3_spectra_rule, reserved) == 12 && offsetof(x3_spectra_rule, d_table) == 16,
+              "include/x3hip.h states this layout");
+
+// The workspace (SpecWs, x3_internal.h): per range the scan of the rows, the rows that are transformed and those that have
+// room; the B operand of the rule's n_fft -- 2 * KT tiles of N / 64 steps, two planes of 64 lanes x 16 bytes each -- and its
+// column sums; the summary
+size_t spectra_carve(char* base, uint64_t n, uint32_t n_fft, SpecWs* w) {
+  BlockCarver k{base, 0};
+  const uint64_t tiles = 2ull * ((n_fft / 2 + 1 + 15) / 16);
+  w->row_off = k.take<unsigned long long>(n + 1);
+  w->live = k.take<uint32_t>(n);
+  w->wr = k.take<uint32_t>(n);
+  w->basis = k.take<uint4>(tiles * (n_fft / 64) * 128);
+  w->colsum = k.take<int32_t>(tiles * 16);
+  w->sum = k.take<X3WinSummary>(1, 1);
+  return k.at;
+}
+
+extern "C" int x3_spectra_rows_dev(x3_ctx* c, const int16_t* d_samples, uint64_t samples_cap, const uint64_t* d_offsets,
+                                   const uint32_t* d_lens, const int32_t* d_in_status, uint64_t n_ranges,
+                                   const x3_spectra_rule* rule, uint64_t row_stride, void* d_out, uint64_t rows_cap,
+                                   uint64_t* d_row_offsets, int32_t* d_status) {
+  // the rule first
+  if (!c || !rule) return X3_ERR_BAD_ARG;
+  const uint32_t N = rule->n_fft;
+  if ((N != 64 && N != 128 && N != 256 && N != 512 && N != 1024) || rule->hop == 0 || rule->hop > 0x7FFFFFFFu ||
+      (rule->format != X3_SPECTRA_SUMS && rule->format != X3_SPECTRA_POWER) || rule->reserved || !rule->d_table ||
+      (reinterpret_cast<uintptr_t>(rule->d_table) & 3u))
+    return X3_ERR_BAD_ARG;
+  if (n_ranges == 0 || n_ranges > 0x7FFFFFFFull || rows_cap == 0 || rows_cap > 0x7FFFFFFFull) return X3_ERR_BAD_ARG;
+  if (!d_samples || !d_offsets || !d_lens || !d_out || !d_status || c->capturing) return X3_ERR_BAD_ARG;
+  if (row_stride ? row_stride > rows_cap / n_ranges : !d_row_offsets) return X3_ERR_BAD_ARG;
+  if ((reinterpret_cast<uintptr_t>(d_samples) & 1u) ||
+      ((reinterpret_cast<uintptr_t>(d_lens) | reinterpret_cast<uintptr_t>(d_in_status) | reinterpret_cast<uintptr_t>(d_status)) & 3u) ||
+      ((reinterpret_cast<uintptr_t>(d_offsets) | reinterpret_cast<uintptr_t>(d_out) | reinterpret_cast<uintptr_t>(d_row_offsets)) & 7u))
+    return X3_ERR_BAD_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  SpecWs w;
+  int rc;
+  if ((rc = ensure(c, c->spec_ws, spectra_carve(nullptr, n_ranges, N, &w)))) return rc;
+  spectra_carve((char*)c->spec_ws.p, n_ranges, N, &w);
+  X3SpGeo g{};
+  g.N = N;
+  while ((1u << g.lgN) < N) ++g.lgN;
+  g.H = rule->hop;
+  g.B = N / 2 + 1;
+  g.KT = (g.B + 15) / 16;
+  g.format = rule->format;
+  hipLaunchKernelGGL(x3_spectra_plan_kernel, dim3(1), dim3(1024), 0, c->stream, d_offsets, d_lens, d_in_status, n_ranges,
+                     samples_cap, g, row_stride, rows_cap, w.row_off, w.live, w.wr, d_row_offsets, d_status, w.sum);
+  hipLaunchKernelGGL(x3_spectra_basis_kernel, dim3(grid_for(2ull * g.KT * (N / 64) * 64, 256)), dim3(256), 0, c->stream,
+                     rule->d_table, g, w.basis, w.colsum);
+  // (the rows are counted on the device: a workgroup per 16 or 32 of what the caller's rows hold at most, grid-stride.
+  //  Packed, that is rows_cap -- the caller's word, possibly far above the rows that exist: the surplus workgroups, 4 096 at
+  //  most, read row_off[n], find no tile of theirs and end)
+  const uint64_t rows_hint = row_stride ? n_ranges * row_stride : rows_cap;
+  auto transform = [&](auto* kernel, uint32_t row_tiles) {
+    const size_t lds = 2u * 16u * (size_t)row_tiles * (N + 16u);
+    hipLaunchKernelGGL(kernel, dim3(grid_for(rows_hint, 16u * row_tiles)), dim3(256), lds, c->stream, d_samples, d_offsets, n_ranges,
+                       g, row_stride, rows_cap, (const unsigned long long*)w.row_off, (const uint32_t*)w.live,
+                       (const uint32_t*)w.wr, (const uint4*)w.basis, (const int32_t*)w.colsum, d_out);
+  };
+  if (N <= 512) transform(x3_spectra_transform_kernel<2>, 2);   // (two row tiles share a load of the B operand; LDS: 33 KB at most)
+  else transform(x3_spectra_transform_kernel<1>, 1);
+  HIPCHK(c, hipGetLastError());
+  c->spectra.pending = true;
+  c->spectra.count = n_ranges;
+  c->spectra.sum_off = (size_t)((char*)w.sum - (char*)c->spec_ws.p);
+  return X3_OK;
+}
+
+extern "C" int x3_spectra_result(x3_ctx* c, uint64_t* n_bad, uint64_t* first_bad, int* first_bad_status, uint64_t* total_rows) {
+  if (!c) return X3_ERR_BAD_ARG;
+  X3WinSummary h{0, 0, 0, 0};
+  const int rc = pending_fetch(c, c->spectra, c->spec_ws, &h, sizeof h);
+  if (rc) return rc;
+  first_bad_of(h.n_bad, h.first, c->spectra.count, n_bad, first_bad, first_bad_status);
+  if (total_rows) *total_rows = h.total;
   return X3_OK;
 }

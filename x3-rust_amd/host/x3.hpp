@@ -1068,6 +1068,79 @@ inline X3Error tone_bank_range_levels(Context& ctx, const EncodedStream& s, cons
   });
 }
 
+// The rule of spectra_rows (x3_spectra_rule): n_fft in {64, 128, 256, 512, 1024}, hop 1 .. 2^31 - 1, power: rows of uint32
+// band powers (X3_SPECTRA_POWER) or of (re, im) int64 pairs (X3_SPECTRA_SUMS); d_table: a device table of 1 024 (cos, sin)
+// int16 pairs, Tone's.  bins() = n_fft / 2 + 1 words or pairs a row; rows(len) = the whole frames of a row of len samples.
+struct SpectraRule {
+  uint32_t n_fft = 256, hop = 256;
+  bool power = true;
+  const int16_t* d_table = nullptr;
+  uint32_t bins() const { return n_fft / 2 + 1; }
+  uint64_t rows(uint64_t len) const { return len < n_fft || !hop ? 0 : (len - n_fft) / hop + 1; }
+  x3_spectra_rule c_rule() const {
+    x3_spectra_rule r{};
+    r.n_fft = n_fft, r.hop = hop, r.format = power ? X3_SPECTRA_POWER : X3_SPECTRA_SUMS, r.d_table = d_table;
+    return r;
+  }
+};
+struct SpectraResult : WindowsResult {
+  uint64_t total_rows = 0;
+};
+// Spectra (x3_spectra_rows_dev): the exact integer STFT of the int16 rows d_lens[w] samples at d_samples + d_offsets[w], as
+// decode_ranges wrote them (d_in_status: its statuses or nullptr; may equal d_status).  The oscillator restarts at every
+// frame.  row_stride 0: range w's rows packed at d_row_offsets[w] (n_ranges + 1 words, required), a range without room in
+// rows_cap rows is BadArg and not written; row_stride > 0: rows at w * row_stride, zeros behind the range's last.  A range
+// with a status has rows of zeros only.  Waits for the call: res = ranges with status != 0, the first, its status, all rows.
+inline X3Error spectra_rows(Context& ctx, const int16_t* d_samples, uint64_t samples_cap, const uint64_t* d_offsets,
+                            const uint32_t* d_lens, const int32_t* d_in_status, uint64_t n_ranges, const SpectraRule& rule,
+                            uint64_t row_stride, void* d_out, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status,
+                            SpectraResult* res) {
+  const x3_spectra_rule r = rule.c_rule();
+  int rc = x3_spectra_rows_dev(ctx.raw(), d_samples, samples_cap, d_offsets, d_lens, d_in_status, n_ranges, &r, row_stride, d_out,
+                               rows_cap, d_row_offsets, d_status);
+  if (rc != X3_OK) return static_cast<X3Error>(rc);
+  SpectraResult q;
+  rc = x3_spectra_result(ctx.raw(), &q.n_bad, &q.first_bad, &q.first_bad_status, &q.total_rows);
+  if (res) *res = q;
+  return static_cast<X3Error>(rc);
+}
+namespace detail {
+// the ranges call (packed int16) has been enqueued with rc: the spectra call behind it on the same stream, in place on its
+// statuses, no wait in between; then both results
+inline X3Error spectra_behind_ranges(Context& ctx, int rc, int16_t* d_samples, uint64_t samples_cap, const uint64_t* d_sample_offsets,
+                                     const uint32_t* d_lens, uint64_t n_ranges, const SpectraRule& rule, uint64_t row_stride,
+                                     void* d_out, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status, SpectraResult* res) {
+  if (rc != X3_OK) return static_cast<X3Error>(rc);
+  const x3_spectra_rule r = rule.c_rule();
+  const int rc2 = x3_spectra_rows_dev(ctx.raw(), d_samples, samples_cap, d_sample_offsets, d_lens, d_status, n_ranges, &r, row_stride,
+                                      d_out, rows_cap, d_row_offsets, d_status);
+  RangesResult rr;
+  rc = x3_decode_ranges_result(ctx.raw(), &rr.n_bad, &rr.first_bad, &rr.first_bad_status, &rr.total_samples);
+  if (rc2 != X3_OK) return static_cast<X3Error>(rc2);
+  if (rc != X3_OK) return static_cast<X3Error>(rc);
+  SpectraResult q;
+  rc = x3_spectra_result(ctx.raw(), &q.n_bad, &q.first_bad, &q.first_bad_status, &q.total_rows);
+  if (res) *res = q;
+  return static_cast<X3Error>(rc);
+}
+}  // namespace detail
+// Range spectra: decode_ranges (packed int16 into d_samples, samples_cap samples, offsets to d_sample_row_offsets, n_ranges + 1
+// words) and spectra_rows on those rows behind it, no host trip and no wait in between; the caller keeps the cut samples.
+// d_status holds the ranges call's statuses first and the spectra call's at the end.  Waits for both.
+inline X3Error range_spectra(Context& ctx, const EncodedStream& s, const Parameters& params, const Buffer& d_sample_offsets,
+                             const uint64_t* d_starts, const uint32_t* d_lens, size_t n_ranges, const SpectraRule& rule,
+                             int16_t* d_samples, uint64_t samples_cap, uint64_t* d_sample_row_offsets, uint64_t row_stride,
+                             void* d_out, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status, SpectraResult* res) {
+  if (!s.bytes.ok() || !s.frame_offsets.ok() || !d_sample_offsets.ok()) return X3Error::BadArg;
+  const x3_params c = params.c_params();
+  const int rc = x3_decode_ranges_dev(ctx.raw(), s.bytes.as<uint8_t>(), s.len, s.frame_offsets.as<uint64_t>(),
+                                      d_sample_offsets.as<uint64_t>(), s.n_frames, &c,
+                                      s.seg_blocks ? s.seg_index.as<uint64_t>() : nullptr, s.seg_blocks, d_starts, d_lens, n_ranges,
+                                      0, d_samples, samples_cap, X3_WINDOW_I16, d_sample_row_offsets, d_status);
+  return detail::spectra_behind_ranges(ctx, rc, d_samples, samples_cap, d_sample_row_offsets, d_lens, n_ranges, rule, row_stride,
+                                       d_out, rows_cap, d_row_offsets, d_status, res);
+}
+
 // A batch of independent streams (x3_decode_streams_dev): entry s = bytes [offsets[s], offsets[s] + lengths[s]) of d_x3 (flags:
 // X3_STREAMS_ARCHIVE_FRAMES for the frame parts of .x3a archives), decoded into row s of d_out (offsets.size() rows of row_len
 // samples, X3_WINDOW_I16 / X3_WINDOW_F32, zeros behind each entry's samples); d_results[s] = x3_decode_stream_dev's results on
@@ -1149,6 +1222,16 @@ class Corpus {
     rc = x3_decode_ranges_result(ctx.raw(), &r.n_bad, &r.first_bad, &r.first_bad_status, &r.total_samples);
     if (res) *res = r;
     return static_cast<X3Error>(rc);
+  }
+  // Range spectra of entries: ranges (packed int16) and device::spectra_rows behind it, as device::range_spectra.
+  X3Error range_spectra(Context& ctx, const uint32_t* d_entries, const uint64_t* d_starts, const uint32_t* d_lens, uint64_t n_ranges,
+                        const SpectraRule& rule, int16_t* d_samples, uint64_t samples_cap, uint64_t* d_sample_row_offsets,
+                        uint64_t row_stride, void* d_out, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status,
+                        SpectraResult* res) const {
+    const int rc = x3_corpus_ranges_dev(ctx.raw(), raw_, d_entries, d_starts, d_lens, n_ranges, 0, d_samples, samples_cap,
+                                        X3_WINDOW_I16, d_sample_row_offsets, d_status);
+    return detail::spectra_behind_ranges(ctx, rc, d_samples, samples_cap, d_sample_row_offsets, d_lens, n_ranges, rule, row_stride,
+                                         d_out, rows_cap, d_row_offsets, d_status, res);
   }
   // Levels of every entry (x3_corpus_levels_dev): entry e's records are [row_first[e], row_first[e + 1]) of d_levels, positions
   // relative to the entry; levels_rows(bin_len) is that prefix, d_levels holds its last word of records.  Waits for the call.

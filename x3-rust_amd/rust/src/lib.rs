@@ -159,6 +159,17 @@ pub mod ffi {
         pub mean_sq_min: [u64; 8],
         pub peak_min: [u32; 8],
     }
+    /// `x3_spectra_rule`: the transform of `x3_spectra_rows_dev` -- `n_fft` in 64 .. 1024 (a power of two), `hop` >= 1,
+    /// `format` `X3_SPECTRA_SUMS` (0) or `X3_SPECTRA_POWER` (1), `d_table` a device table of 1 024 (cos, sin) i16 pairs (24 bytes)
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug)]
+    pub struct x3_spectra_rule {
+        pub n_fft: u32,
+        pub hop: u32,
+        pub format: u32,
+        pub reserved: u32,
+        pub d_table: *const i16,
+    }
     #[repr(C)]
     #[derive(Clone, Copy, Debug)]
     pub struct x3_rice_code {
@@ -385,6 +396,12 @@ pub mod ffi {
                                                     bank: *const x3_level_tone_bank) -> c_int;
         pub fn x3_range_levels_result(ctx: *mut x3_ctx, n_bad: *mut u64, first_bad: *mut u64, first_bad_status: *mut c_int,
                                       total_rows: *mut u64) -> c_int;
+        pub fn x3_spectra_rows_dev(ctx: *mut x3_ctx, d_samples: *const i16, samples_cap: u64, d_offsets: *const u64,
+                                   d_lens: *const u32, d_in_status: *const i32, n_ranges: u64, rule: *const x3_spectra_rule,
+                                   row_stride: u64, d_out: *mut c_void, rows_cap: u64, d_row_offsets: *mut u64,
+                                   d_status: *mut i32) -> c_int;
+        pub fn x3_spectra_result(ctx: *mut x3_ctx, n_bad: *mut u64, first_bad: *mut u64, first_bad_status: *mut c_int,
+                                 total_rows: *mut u64) -> c_int;
         pub fn x3_corpus_destroy(corpus: *mut x3_corpus);
         pub fn x3_place_buffers(ctx: *mut x3_ctx, d_wav: *const i16, n: u64, p: *const x3_params, d_streams: *const *mut u8,
                                 n_streams: u32, cap: u64, d_frame_offsets: *mut u64, d_backs: *const *mut i16, n_backs: u32,
@@ -1976,6 +1993,103 @@ pub mod device {
         })?;
         let (mut n_bad, mut first_bad, mut st, mut total) = (0u64, 0u64, 0, 0u64);
         error::check(unsafe { ffi::x3_range_levels_result(gpu.raw(), &mut n_bad, &mut first_bad, &mut st, &mut total) })?;
+        Ok((n_bad, first_bad, st, total))
+    }
+
+    /// `spectra_rows` format: rows of `n_fft / 2 + 1` (re, im) i64 pairs
+    pub const SPECTRA_SUMS: u32 = 0;
+    /// `spectra_rows` format: rows of `n_fft / 2 + 1` u32 band powers, the tone adapter's `ms` at `n = n_fft`
+    pub const SPECTRA_POWER: u32 = 1;
+
+    /// The rule of `spectra_rows` / `range_spectra` (`x3_spectra_rule`): `n_fft` in {64, 128, 256, 512, 1024}, `hop` in
+    /// 1 ..= 2^31 - 1, `power` for `SPECTRA_POWER` rows, and a device table of 1 024 (cos, sin) i16 pairs (`Tone`'s)
+    #[derive(Clone, Copy)]
+    pub struct SpectraRule<'t, 'g> {
+        pub n_fft: u32,
+        pub hop: u32,
+        pub power: bool,
+        pub table: &'t Buffer<'g>,
+    }
+
+    impl<'t, 'g> SpectraRule<'t, 'g> {
+        /// bins of a row: `n_fft / 2 + 1`
+        pub fn bins(&self) -> usize { self.n_fft as usize / 2 + 1 }
+        /// bytes of a row
+        pub fn row_bytes(&self) -> usize { self.bins() * if self.power { 4 } else { 16 } }
+        /// whole frames of a row of `len` samples
+        pub fn rows(&self, len: u64) -> u64 {
+            if len < self.n_fft as u64 || self.hop == 0 { 0 } else { (len - self.n_fft as u64) / self.hop as u64 + 1 }
+        }
+        fn c(&self) -> error::Result<ffi::x3_spectra_rule> {
+            if self.table.len() < 4096 { return Err(X3Error::BadArg); }
+            Ok(ffi::x3_spectra_rule { n_fft: self.n_fft, hop: self.hop, format: if self.power { SPECTRA_POWER } else { SPECTRA_SUMS },
+                                      reserved: 0, d_table: self.table.as_ptr::<i16>() as *const i16 })
+        }
+    }
+
+    /// Spectra (`x3_spectra_rows_dev`; not in the reference crate): the exact integer STFT of the i16 rows `d_lens[w]` samples
+    /// at `d_samples + d_offsets[w]`, as `decode_ranges` wrote them, on the matrix cores; the oscillator restarts at every
+    /// frame.  `d_in_status`: the ranges call's statuses or `None`.  `row_stride` 0: range w's rows packed at
+    /// `d_row_offsets[w]` (`n_ranges + 1` u64s, required); > 0: rows at `w * row_stride`, zeros behind the range's last.  A
+    /// range with a status has rows of zeros only.  Waits: -> (ranges with status != 0, the first of them, its status, all rows)
+    #[allow(clippy::too_many_arguments)]
+    pub fn spectra_rows<'g>(gpu: &'g Gpu, d_samples: &Buffer<'g>, samples_cap: u64, d_offsets: &Buffer<'g>, d_lens: &Buffer<'g>,
+                            d_in_status: Option<&Buffer<'g>>, n_ranges: usize, rule: &SpectraRule<'_, 'g>, row_stride: u64,
+                            d_out: &mut Buffer<'g>, rows_cap: u64, d_row_offsets: Option<&mut Buffer<'g>>,
+                            d_status: &mut Buffer<'g>) -> error::Result<(u64, u64, i32, u64)> {
+        let r = rule.c()?;
+        if (d_samples.len() as u64) < 2 * samples_cap || d_offsets.len() < 8 * n_ranges || d_lens.len() < 4 * n_ranges
+            || (d_out.len() as u64) < rule.row_bytes() as u64 * rows_cap || d_status.len() < 4 * n_ranges
+            || d_in_status.map_or(false, |b| b.len() < 4 * n_ranges)
+            || d_row_offsets.as_ref().map_or(false, |b| b.len() < 8 * (n_ranges + 1)) {
+            return Err(X3Error::BadArg);
+        }
+        let ins = d_in_status.map_or(core::ptr::null(), |b| b.as_ptr::<i32>() as *const i32);
+        let off = d_row_offsets.map_or(core::ptr::null_mut(), |b| b.as_ptr::<u64>());
+        error::check(unsafe {
+            ffi::x3_spectra_rows_dev(gpu.raw(), d_samples.as_ptr::<i16>(), samples_cap, d_offsets.as_ptr::<u64>(),
+                                     d_lens.as_ptr::<u32>(), ins, n_ranges as u64, &r, row_stride, d_out.as_ptr::<c_void>(),
+                                     rows_cap, off, d_status.as_ptr::<i32>())
+        })?;
+        let (mut n_bad, mut first_bad, mut st, mut total) = (0u64, 0u64, 0, 0u64);
+        error::check(unsafe { ffi::x3_spectra_result(gpu.raw(), &mut n_bad, &mut first_bad, &mut st, &mut total) })?;
+        Ok((n_bad, first_bad, st, total))
+    }
+
+    /// Range spectra: `x3_decode_ranges_dev` (packed i16 into `d_samples`, offsets to `d_sample_row_offsets`) and
+    /// `x3_spectra_rows_dev` on those rows behind it on the same stream, in place on `d_status`, no host trip and no wait in
+    /// between; the caller keeps the cut samples.  Waits for both: -> as `spectra_rows`
+    #[allow(clippy::too_many_arguments)]
+    pub fn range_spectra<'g>(gpu: &'g Gpu, s: &EncodedStream<'g>, params: &x3::Parameters, sample_offsets: &Buffer<'g>,
+                             d_starts: &Buffer<'g>, d_lens: &Buffer<'g>, n_ranges: usize, rule: &SpectraRule<'_, 'g>,
+                             d_samples: &mut Buffer<'g>, samples_cap: u64, d_sample_row_offsets: &mut Buffer<'g>, row_stride: u64,
+                             d_out: &mut Buffer<'g>, rows_cap: u64, d_row_offsets: Option<&mut Buffer<'g>>,
+                             d_status: &mut Buffer<'g>) -> error::Result<(u64, u64, i32, u64)> {
+        let r = rule.c()?;
+        if d_starts.len() < 8 * n_ranges || d_lens.len() < 4 * n_ranges || (d_samples.len() as u64) < 2 * samples_cap
+            || d_sample_row_offsets.len() < 8 * (n_ranges + 1) || (d_out.len() as u64) < rule.row_bytes() as u64 * rows_cap
+            || d_status.len() < 4 * n_ranges || d_row_offsets.as_ref().map_or(false, |b| b.len() < 8 * (n_ranges + 1)) {
+            return Err(X3Error::BadArg);
+        }
+        let p = params.c()?;
+        let idx = match &s.seg_index { Some(i) => i.as_ptr::<u64>() as *const u64, None => core::ptr::null() };
+        let off = d_row_offsets.map_or(core::ptr::null_mut(), |b| b.as_ptr::<u64>());
+        error::check(unsafe {
+            ffi::x3_decode_ranges_dev(gpu.raw(), s.bytes.as_ptr::<u8>(), s.len as u64, s.frame_offsets.as_ptr::<u64>(),
+                                      sample_offsets.as_ptr::<u64>(), s.n_frames as u64, &p, idx, s.seg_blocks,
+                                      d_starts.as_ptr::<u64>(), d_lens.as_ptr::<u32>(), n_ranges as u64, 0,
+                                      d_samples.as_ptr::<c_void>(), samples_cap, WINDOW_I16, d_sample_row_offsets.as_ptr::<u64>(),
+                                      d_status.as_ptr::<i32>())
+        })?;
+        let rc = unsafe {
+            ffi::x3_spectra_rows_dev(gpu.raw(), d_samples.as_ptr::<i16>(), samples_cap, d_sample_row_offsets.as_ptr::<u64>(),
+                                     d_lens.as_ptr::<u32>(), d_status.as_ptr::<i32>(), n_ranges as u64, &r, row_stride,
+                                     d_out.as_ptr::<c_void>(), rows_cap, off, d_status.as_ptr::<i32>())
+        };
+        let (mut n_bad, mut first_bad, mut st, mut total) = (0u64, 0u64, 0, 0u64);
+        error::check(unsafe { ffi::x3_decode_ranges_result(gpu.raw(), &mut n_bad, &mut first_bad, &mut st, &mut total) })?;
+        error::check(rc)?;
+        error::check(unsafe { ffi::x3_spectra_result(gpu.raw(), &mut n_bad, &mut first_bad, &mut st, &mut total) })?;
         Ok((n_bad, first_bad, st, total))
     }
 

@@ -74,6 +74,7 @@ SYMBOLS = [
     "x3_fir_range_levels_dev", "x3_corpus_fir_range_levels_dev",
     "x3_tone_range_levels_dev", "x3_corpus_tone_range_levels_dev",
     "x3_tone_bank_range_levels_dev", "x3_corpus_tone_bank_range_levels_dev",
+    "x3_spectra_rows_dev", "x3_spectra_result",
     "x3_tune_candidate", "x3_tuner_create", "x3_tuner_add_dev", "x3_tuner_result", "x3_tuner_max_payloads",
     "x3_tuner_reset", "x3_tuner_destroy", "x3_tune", "x3_x3a_encode_tuned",
 ]
@@ -146,6 +147,21 @@ class LevelToneBank(C.Structure):
 
 
 TONE_TABLE_PAIRS = 1024   # (cos, sin) int16 pairs of a tone table: 4 096 bytes
+
+SPECTRA_SUMS, SPECTRA_POWER = 0, 1   # X3_SPECTRA_*: rows of (re, im) int64 pairs / of uint32 band powers
+SPECTRA_NFFTS = (64, 128, 256, 512, 1024)
+
+
+class SpectraRule(C.Structure):
+    """x3_spectra_rule: the transform of x3_spectra_rows_dev -- n_fft in SPECTRA_NFFTS, hop >= 1, format SPECTRA_SUMS or
+    SPECTRA_POWER, reserved 0; d_table is a device pointer to a tone table (24 bytes, copied at the call)"""
+    _fields_ = [("n_fft", C.c_uint32), ("hop", C.c_uint32), ("format", C.c_uint32), ("reserved", C.c_uint32),
+                ("d_table", C.c_void_p)]
+
+
+def spectra_n_rows(length, n_fft, hop):
+    """R of a row of `length` samples: whole frames only"""
+    return 0 if length < n_fft else (length - n_fft) // hop + 1
 
 
 def tone_table():
@@ -497,6 +513,8 @@ def lib():
     L.x3_corpus_tone_bank_range_levels_dev.argtypes = [vp, vp, vp, vp, vp, u64, u64, u64, vp, u64, vp, vp,
                                                        C.POINTER(LevelToneBank)]
     L.x3_range_levels_result.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(i32), C.POINTER(u64)]
+    L.x3_spectra_rows_dev.argtypes = [vp, vp, u64, vp, vp, vp, u64, C.POINTER(SpectraRule), u64, vp, u64, vp, vp]
+    L.x3_spectra_result.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(i32), C.POINTER(u64)]
     L.x3_corpus_destroy.restype = None
     L.x3_synth.argtypes = [i32, u64, u64, u64, vp]
     L.x3_synth_dev.argtypes = [vp, i32, u64, u64, u64, vp]
@@ -1483,6 +1501,23 @@ class Context:
         rc = lib().x3_range_levels_result(self._h, C.byref(nb), C.byref(fb), C.byref(st), C.byref(tot))
         return rc, nb.value, fb.value, st.value, tot.value
 
+    def spectra_rows_dev(self, d_samples, samples_cap, d_offsets, d_lens, d_in_status, n_ranges, rule, row_stride, d_out,
+                         rows_cap, d_row_offsets, d_status):
+        """x3_spectra_rows_dev: the exact integer STFT (rule: a SpectraRule, None: NULL, which the library refuses) of the
+        int16 rows d_lens[w] samples at d_samples + d_offsets[w], as decode_ranges_dev / Corpus.ranges_into wrote them;
+        d_in_status: that call's statuses or None, may equal d_status; row_stride 0: packed rows at d_row_offsets[w], else
+        rows at w * row_stride; d_out: rows_cap rows of B = n_fft / 2 + 1 (re, im) int64 pairs (SPECTRA_SUMS) or uint32
+        powers (SPECTRA_POWER); asynchronous, spectra_result waits"""
+        return lib().x3_spectra_rows_dev(self._h, d_samples, samples_cap, d_offsets, d_lens, d_in_status, n_ranges,
+                                         C.byref(rule) if rule is not None else None, row_stride, d_out, rows_cap,
+                                         d_row_offsets, d_status)
+
+    def spectra_result(self):
+        """-> (rc, n_bad, first_bad, first_bad_status, total_rows) of the last spectra_rows_dev"""
+        nb, fb, st, tot = C.c_uint64(0), C.c_uint64(0), C.c_int32(0), C.c_uint64(0)
+        rc = lib().x3_spectra_result(self._h, C.byref(nb), C.byref(fb), C.byref(st), C.byref(tot))
+        return rc, nb.value, fb.value, st.value, tot.value
+
     def decode_streams_dev(self, d_x3, x3_len, offsets, lengths, params, d_out, row_len, out_format, d_results, flags=0):
         """x3_decode_streams_dev: entry s = bytes [offsets[s], offsets[s] + lengths[s]) of d_x3 -> row s of d_out
         (len(offsets) x row_len samples) and d_results[s] (asynchronous; offsets / lengths: host sequences)"""
@@ -1608,6 +1643,96 @@ def _ranges_torch(ctx, enqueue, what, starts, lens, padded_to, capacity, dtype, 
     if rc:
         raise X3Error(rc, "x3_decode_ranges_result: " + ctx.last_error())
     return out[:cap] if padded_to is None else out, offsets, status
+
+
+def _range_spectra_torch(ctx, enqueue, what, starts, lens, n_fft, hop, power, table, padded_to, capacity, sample_capacity,
+                         entries=None):
+    """The torch side of WindowSource.range_spectra / Corpus.range_spectra: the ranges call (packed int16) and the spectra
+    call behind it on the context's stream, no wait and no host trip in between -> (spectra, row_offsets, status, samples,
+    sample_offsets) device tensors.  enqueue(d_entries, d_starts, d_lens, n, rule, d_samples, samples_cap, d_sample_offsets,
+    stride, d_out, rows_cap, d_row_offsets, d_status) -> (rc of the ranges call, rc of the spectra call or None)."""
+    import torch
+    dev = torch.device("cuda", torch.cuda.current_device())
+    n_fft = int(n_fft)
+    hop = n_fft if hop is None else int(hop)
+    if n_fft not in SPECTRA_NFFTS or not 1 <= hop <= 0x7FFFFFFF:
+        raise ValueError("n_fft: one of %s; hop: 1 .. 2^31 - 1" % (SPECTRA_NFFTS,))
+
+    def on_dev(a, dt):   # (as in _ranges_torch: unsigned words travel as the signed tensors of the same bits)
+        signed = {np.uint64: torch.int64, np.uint32: torch.int32}[dt]
+        if not isinstance(a, torch.Tensor):
+            a = torch.from_numpy(np.ascontiguousarray(a, dtype=dt).view(np.int64 if dt is np.uint64 else np.int32))
+        elif a.dtype.itemsize == signed.itemsize and not a.dtype.is_floating_point:
+            a = a.view(signed)
+        else:
+            a = a.to(signed)
+        return a.to(dev).contiguous()
+    starts, lens = on_dev(starts, np.uint64), on_dev(lens, np.uint32)
+    n = starts.numel()
+    if starts.dim() != 1 or lens.shape != starts.shape or n == 0:
+        raise ValueError("starts and lens: 1-D, non-empty, of one length")
+    d_ent = None
+    if entries is not None:
+        entries = on_dev(entries, np.uint32)
+        if entries.shape != starts.shape:
+            raise ValueError("entries: as many as starts")
+        d_ent = entries.data_ptr()
+    if padded_to is not None and padded_to <= 0:
+        raise ValueError("padded_to: a positive row stride")
+    stride = int(padded_to) if padded_to is not None else 0
+    rows_cap = n * stride if stride else (int(capacity) if capacity is not None else None)
+    samples_cap = int(sample_capacity) if sample_capacity is not None else None
+    if rows_cap is None or samples_cap is None:   # (the one host trip: the lengths; both sums come from them)
+        ln = (lens.to(torch.int64) & 0xFFFFFFFF).cpu().numpy()
+        if samples_cap is None:
+            samples_cap = int(ln.sum())
+        if rows_cap is None:
+            rows_cap = int(np.where(ln < n_fft, 0, (ln - n_fft) // hop + 1).sum())
+    if table is None:
+        d_table = ctx.tone_table_dev()
+    else:
+        if not isinstance(table, torch.Tensor):
+            table = torch.from_numpy(np.ascontiguousarray(table, dtype=np.int16))
+        if table.dtype != torch.int16 or table.numel() != 2 * TONE_TABLE_PAIRS:
+            raise ValueError("table: %d (cos, sin) int16 pairs" % TONE_TABLE_PAIRS)
+        table = table.to(dev).contiguous()
+        d_table = table.data_ptr()
+    nb = n_fft // 2 + 1
+    rule = SpectraRule(n_fft, hop, SPECTRA_POWER if power else SPECTRA_SUMS, 0, d_table)
+    samples = torch.empty(max(samples_cap, 1), dtype=torch.int16, device=dev)
+    sample_offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    spectra = torch.empty((max(rows_cap, 1), nb) if power else (max(rows_cap, 1), nb, 2),
+                          dtype=torch.int32 if power else torch.int64, device=dev)
+    row_offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    torch.cuda.current_stream().synchronize()    # (the context's stream is not torch's: the inputs are ready from here)
+    rc, rc2 = enqueue(d_ent, starts.data_ptr(), lens.data_ptr(), n, rule, samples.data_ptr(), max(samples_cap, 1),
+                      sample_offsets.data_ptr(), stride, spectra.data_ptr(), max(rows_cap, 1), row_offsets.data_ptr(),
+                      status.data_ptr())
+    if rc:
+        raise X3Error(rc, what + ": " + ctx.last_error())
+    rc = ctx.decode_ranges_result()[0]   # (waits for both: one stream)
+    if rc:
+        raise X3Error(rc, "x3_decode_ranges_result: " + ctx.last_error())
+    if rc2:
+        raise X3Error(rc2, "x3_spectra_rows_dev: " + ctx.last_error())
+    rc = ctx.spectra_result()[0]
+    if rc:
+        raise X3Error(rc, "x3_spectra_result: " + ctx.last_error())
+    return spectra[:rows_cap], row_offsets, status, samples[:samples_cap], sample_offsets
+
+
+def _range_spectra_enqueue(ctx, ranges_into):
+    """the enqueue of _range_spectra_torch and the body of the range_spectra_into forms: ranges_into(d_starts-or-entries
+    ..., packed int16) then x3_spectra_rows_dev in place on its statuses"""
+    def enqueue(d_ent, d_starts, d_lens, n, rule, d_samples, samples_cap, d_sample_offsets, stride, d_out, rows_cap, d_row_offsets,
+                d_status):
+        rc = ranges_into(d_ent, d_starts, d_lens, n, 0, d_samples, samples_cap, WINDOW_I16, d_sample_offsets, d_status)
+        if rc:
+            return rc, None
+        return 0, ctx.spectra_rows_dev(d_samples, samples_cap, d_sample_offsets, d_lens, d_status, n, rule, stride, d_out, rows_cap,
+                                       d_row_offsets, d_status)
+    return enqueue
 
 
 def _range_levels_torch(ctx, enqueue, what, starts, lens, bin_len, padded_to, capacity, entries=None, band=False, planes=None):
@@ -1979,6 +2104,30 @@ class WindowSource:
         import torch
         return _ranges_torch(self.ctx, lambda e, *a: self.ranges_into(*a), "x3_decode_ranges_dev", starts, lens, padded_to,
                              capacity, dtype or torch.int16)
+
+    def range_spectra_into(self, d_starts, d_lens, n, rule, d_samples, samples_cap, d_sample_offsets, row_stride, d_out, rows_cap,
+                           d_row_offsets, d_status):
+        """enqueue ranges_into (packed int16 into d_samples, offsets to d_sample_offsets) and, behind it with no wait,
+        Context.spectra_rows_dev on those rows under rule (a SpectraRule), in place on d_status (device pointers)
+        -> (rc of the ranges call, rc of the spectra call or None); decode_ranges_result and spectra_result wait"""
+        return _range_spectra_enqueue(self.ctx, lambda e, *a: self.ranges_into(*a))(
+            None, d_starts, d_lens, n, rule, d_samples, samples_cap, d_sample_offsets, row_stride, d_out, rows_cap, d_row_offsets,
+            d_status)
+
+    def range_spectra(self, starts, lens, n_fft, hop=None, *, power=True, table=None, padded_to=None, capacity=None,
+                      sample_capacity=None):
+        """The spectrogram of the ranges [starts[w], starts[w] + lens[w]): their samples (ranges(), packed int16) and, with
+        no host trip in between, the exact integer STFT of every whole frame of n_fft samples at multiples of hop (None:
+        n_fft) from each range's start (x3_spectra_rows_dev) -> (spectra, row_offsets, status, samples, sample_offsets),
+        torch tensors on the device.  power=True: spectra is int32 [rows, n_fft / 2 + 1], the band power of every bin as
+        the tone adapter forms it; False: int64 [rows, n_fft / 2 + 1, 2], the sums (re, im).  Range w's rows are
+        spectra[row_offsets[w]:row_offsets[w + 1]] (packed; `capacity` rows when given), or begin at w * padded_to with
+        zeros behind the range's last.  A range with a status (a damaged frame, no room) has rows of zeros only.  table:
+        None for tone_table(), or 1 024 (cos, sin) int16 pairs.  Without capacity / sample_capacity the one host trip
+        is the ranges' lengths.  The oscillator restarts at every frame, unlike tone_range_levels."""
+        return _range_spectra_torch(self.ctx, _range_spectra_enqueue(self.ctx, lambda e, *a: self.ranges_into(*a)),
+                                    "x3_decode_ranges_dev", starts, lens, n_fft, hop, power, table, padded_to, capacity,
+                                    sample_capacity)
 
     def range_levels_into(self, d_starts, d_lens, n, bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status,
                           signal=LEVEL_SIGNAL_SAMPLES):
@@ -2446,6 +2595,19 @@ class Corpus:
         import torch
         return _ranges_torch(self.ctx, self.ranges_into, "x3_corpus_ranges_dev", starts, lens, padded_to, capacity,
                              dtype or torch.int16, entries=entries)
+
+    def range_spectra_into(self, d_entries, d_starts, d_lens, n, rule, d_samples, samples_cap, d_sample_offsets, row_stride,
+                           d_out, rows_cap, d_row_offsets, d_status):
+        """WindowSource.range_spectra_into on ranges of entries (d_entries n x u32)"""
+        return _range_spectra_enqueue(self.ctx, self.ranges_into)(
+            d_entries, d_starts, d_lens, n, rule, d_samples, samples_cap, d_sample_offsets, row_stride, d_out, rows_cap,
+            d_row_offsets, d_status)
+
+    def range_spectra(self, entries, starts, lens, n_fft, hop=None, *, power=True, table=None, padded_to=None, capacity=None,
+                      sample_capacity=None):
+        """WindowSource.range_spectra on the ranges [starts[w], starts[w] + lens[w]) of entry entries[w]"""
+        return _range_spectra_torch(self.ctx, _range_spectra_enqueue(self.ctx, self.ranges_into), "x3_corpus_ranges_dev", starts,
+                                    lens, n_fft, hop, power, table, padded_to, capacity, sample_capacity, entries=entries)
 
     def range_levels_into(self, d_entries, d_starts, d_lens, n, bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status,
                           signal=LEVEL_SIGNAL_SAMPLES):
