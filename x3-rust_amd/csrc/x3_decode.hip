@@ -2733,7 +2733,7 @@ static int range_levels_launch(x3_ctx* c, const FrameSource& s, const uint64_t* 
                          row_stride, P, cap, (const unsigned long long*)w.prow, (const int32_t*)w.fst, d_levels, d_status, w.scratch,
                          scratch_per, w.sum, tail, (const uint32_t*)w.lead);
     };
-    if constexpr (std::is_same_v<Signal, X3RLevFir>) fixup(x3_range_levels_fir_fixup_kernel, s.idx, s.seg_blocks, s.nseg);
+    if constexpr (std::is_same_v<Signal, X3LevFir>) fixup(x3_range_levels_fir_fixup_kernel, s.idx, s.seg_blocks, s.nseg);
     else fixup(x3_range_levels_fixup_kernel<decltype(fix)>);
     for (uint64_t t = 0; t < planes; ++t)
       hipLaunchKernelGGL(x3_range_levels_merge_kernel, dim3(grid_for(rec_hint + cov_hint, 256)), dim3(256), 0, c->stream,
@@ -2746,10 +2746,10 @@ static int range_levels_launch(x3_ctx* c, const FrameSource& s, const uint64_t* 
   switch (g.kind) {
     case LevSignal::FIR:
       run([&] {
-            hipLaunchKernelGGL(x3_range_levels_fir_lead_kernel, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, s.d_sample_offsets,
+            hipLaunchKernelGGL(x3_range_levels_lead_kernel, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, s.d_sample_offsets,
                                d_ent, n_ent, d_entries, d_gstarts, d_lens, n, (uint32_t)lead_frames, w.plan, w.lead);
           },
-          X3RLevFir{}, X3RLevFir{}, X3LevFirTail{g.fir, (X3FirEdge*)c->fir_ws.p, s.nseg}, [&] {
+          X3LevFir{}, X3LevFir{}, X3LevFirTail{g.fir, (X3FirEdge*)c->fir_ws.p, s.nseg}, [&] {
             hipLaunchKernelGGL(x3_range_levels_fir_seam_kernel, dim3(grid_for(item_hint, 256)), dim3(256), 0, c->stream,
                                s.dp.block_len, s.idx, s.seg_blocks, s.nseg, bin_len, (const X3RLevPair*)w.pairs,
                                (const unsigned long long*)w.cov_off, n, P, cap, (const unsigned long long*)w.prow,
@@ -2757,11 +2757,11 @@ static int range_levels_launch(x3_ctx* c, const FrameSource& s, const uint64_t* 
                                (const X3FirEdge*)c->fir_ws.p, s.nseg, g.fir, d_levels);
           });
       break;
-    case LevSignal::TONE: run(none, X3RLevTone{}, X3RLevTone{}, X3RLevToneTail{g.tone.table, g.tone.step, d_starts}, none); break;
+    case LevSignal::TONE: run(none, X3LevTone{}, X3LevTone{}, X3LevToneTail{g.tone.table, g.tone.step, d_starts}, none); break;
     case LevSignal::DIFF:
       run([&] {
             hipLaunchKernelGGL(x3_range_levels_lead_kernel, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, s.d_sample_offsets, d_ent,
-                               n_ent, d_entries, d_gstarts, d_lens, n, w.plan, w.lead);
+                               n_ent, d_entries, d_gstarts, d_lens, n, (uint32_t)lead_frames, w.plan, w.lead);
           },
           X3LevDiff{}, X3LevDiff{}, w.tail, [&] {
             hipLaunchKernelGGL(x3_range_levels_seam_kernel, dim3(grid_for(cov_hint, 256)), dim3(256), 0, c->stream, s.d_x3, s.x3_len,
@@ -2772,11 +2772,11 @@ static int range_levels_launch(x3_ctx* c, const FrameSource& s, const uint64_t* 
       break;
     case LevSignal::SAMPLES: run(none, X3LevSamples{}, X3LevSamples{}, X3LevNoTail{}, none); break;
     case LevSignal::BANK: {
-      X3RLevToneBankTail t{g.bank, d_starts};
-      t.bank.rows_stride = cap, t.bank.levels_stride = rows_cap;
-      using Fix = X3RLevToneBank<X3L_TONE_BANK>;
-      if (t.bank.n_tones <= 2) run(none, X3RLevToneBank<2>{}, Fix{}, t, none);
-      else if (t.bank.n_tones <= 4) run(none, X3RLevToneBank<4>{}, Fix{}, t, none);
+      X3LevToneBankTail t = g.bank;
+      t.rows_stride = cap, t.levels_stride = rows_cap, t.starts = d_starts;
+      using Fix = X3LevToneBank<X3L_TONE_BANK>;
+      if (t.n_tones <= 2) run(none, X3LevToneBank<2>{}, Fix{}, t, none);
+      else if (t.n_tones <= 4) run(none, X3LevToneBank<4>{}, Fix{}, t, none);
       else run(none, Fix{}, Fix{}, t, none);
       break;
     }

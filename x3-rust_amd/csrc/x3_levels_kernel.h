@@ -28,10 +28,11 @@
 //  x3_levels_seam_kernel     -- X3_LEVEL_SIGNAL_DIFF only: a lane per frame, the one difference across the frame's front seam
 //  x3_levels_fir_seam_kernel -- x3_fir_levels_dev only: a lane per (frame, stretch), the stretch's first T - 1 positions
 //  x3_tone_power_kernel      -- x3_tone_power_levels_dev: a lane per tone record, the record of the band's level
-// The accumulate and fix-up kernels are templates over the SIGNAL, what a position adds to its bin: X3LevSamples (the levels
-// calls), X3LevDiff (x3_signal_levels_dev), X3LevFir (x3_fir_levels_dev) or
-// X3LevTone (x3_tone_levels_dev); X3LevToneBank<NT> (x3_tone_bank_levels_dev)
-// is NT of the last in one pass, whose records go to NT planes of the partial rows and of the caller's records.
+// The accumulate and fix-up kernels are templates over the SIGNAL, what a position adds to its bin, and call it by THE SIGNAL
+// PROTOCOL (below, in front of the signals): X3LevSamples (the levels calls), X3LevDiff (x3_signal_levels_dev; DESIGN.md
+// section 20), X3LevFir (x3_fir_levels_dev; section 22), X3LevTone (x3_tone_levels_dev; section 24) or X3LevToneBank<NT>
+// (x3_tone_bank_levels_dev; section 26), NT of the last in one pass, whose records go to NT planes of the partial rows and of
+// the caller's records.  x3_range_levels_kernel.h runs the same signals over ranges.
 //
 // What the range levels, events and quantiles kernels (x3_range_levels_kernel.h, x3_events_kernel.h, x3_quantiles_kernel.h)
 // share with these: X3L_IDENTITY, the record of an empty bin; X3LevAcc, a record in registers (load, record, join);
@@ -153,57 +154,93 @@ struct X3LevBinner {
   }
 };
 
-// THE SIGNAL (x3_signal_levels_dev): what a position adds to its bin.
-// X3LevSamples: the sample.  X3LevDiff: the sample minus the one in front of it, clamped to 16 bits -- `prev` in a register;
-// the first sample a lane sees without a seed (sample 0 of a frame) adds nothing: that difference crosses the frame's seam
-// and is x3_levels_seam_kernel's.  seed(v): the sample in front of a stretch (x3w_stretch's watch).  Tail: the kernels'
-// last argument, the per-frame array of last samples that only X3LevDiff has.
-// kState: the signal has registers of its own and is the caller's, at x3l_bin_samples' `sig`; kFir: it is X3LevFir, kTone:
-// it is X3LevTone, kBank: it is X3LevToneBank<NT> (all below).
+// THE SIGNAL PROTOCOL.  A signal is what a position adds to its bin.  The accumulate and fix-up kernels of this file and of
+// x3_range_levels_kernel.h are templates over it; they call the members below and never ask which signal they hold, so a new
+// signal is a struct here and a case in the host's two switches.
+//   Tail                -- the kernels' last argument: what the signal takes from the call
+//   lds_table(tail)     -- the accumulate kernels, every lane in front of the item loop: the workgroup's LDS copy of the
+//                          signal's table (NULL: it has none); table(tail): the caller's array, which the fix-ups read
+//   origin(tail, w)     -- the range kernels only: the position in the stream or entry that range w's positions count from
+//                          (0: the signal counts from the range's start)
+//   begin(tail, at)     -- the set-up of a lane's (accumulate) or a wave's (fix-up) signal at X3LevAt
+//   watch()             -- what x3w_stretch takes as its watch
+//   add(a, v) / skip(v) -- a position of the open bin `a`, and one the lane sees that its bins do not hold (in front of or
+//                          behind a range's cut of the frame): history and phase move all the same
+//   flush(r, a)         -- the open bin to record r, which other lanes add to as well; drop(): the bin is no record's
+//   end(frame)          -- behind the last sample of the stretch, or (frame) of the whole frame a fix-up replayed
+//   kSeam               -- the one flag: the difference across a frame's front seam, which x3_range_levels_fixup_kernel books
+//                          frame by frame (there is why it is a flag)
+// X3LevPlain has the members of a signal without table, watch, state or end; the signals below replace what differs.
+struct X3LevAt {
+  uint64_t f;            // the frame
+  uint32_t j;            // the stretch (a replayed frame is one stretch: 0)
+  uint64_t g;            // position of the first sample the signal sees (the levels calls: in the stream or entry; the range
+                         // calls: origin() plus its position behind the range's start)
+  const uint32_t* tab;   // lds_table() or table()
+  bool rows;             // flushes go to partial rows (accumulate), not to the caller's records (fix-up)
+};
 struct X3LevNoTail {};
-struct X3LevSamples {
-  static constexpr bool kDiff = false, kFir = false, kState = false, kTone = false, kBank = false;
+struct X3LevPlain {
+  static constexpr bool kSeam = false;
+  template <class T> static __device__ __forceinline__ const uint32_t* lds_table(const T&) { return nullptr; }
+  template <class T> static __device__ __forceinline__ const uint32_t* table(const T&) { return nullptr; }
+  template <class T> static __device__ __forceinline__ uint64_t origin(const T&, uint64_t) { return 0; }
+  template <class T> __device__ __forceinline__ void begin(const T&, const X3LevAt&) {}
+  __device__ __forceinline__ X3WNoWatch watch() { return X3WNoWatch{}; }
+  __device__ __forceinline__ void skip(uint32_t) {}
+  __device__ __forceinline__ void flush(x3_level* __restrict__ r, const X3LevAcc& a) { x3l_merge(r, a); }
+  __device__ __forceinline__ void drop() {}
+  __device__ __forceinline__ void end(bool) {}
+};
+
+// X3LevSamples (the levels calls): the sample
+struct X3LevSamples : X3LevPlain {
   using Tail = X3LevNoTail;
   __device__ __forceinline__ void add(X3LevAcc& a, uint32_t v) { a.add(v); }
 };
+
+// X3LevDiff (x3_signal_levels_dev): the sample minus the one in front of it, clamped to 16 bits -- `prev`
+// in a register; the first sample a lane sees without a seed (sample 0 of a frame) adds nothing: that difference crosses the
+// frame's seam and is x3_levels_seam_kernel's.  The watch hands over the stretch's seed, the sample in front of it, and stores
+// the frame's last sample to its word of the tails, the per-frame array that is this signal's Tail; a replayed frame's is end()'s.
 __device__ __forceinline__ int32_t x3l_diff(int32_t s, int32_t prev) { return min(max(s - prev, -32768), 32767); }
-struct X3LevDiff {
-  static constexpr bool kDiff = true, kFir = false, kState = true, kTone = false, kBank = false;
-  using Tail = int32_t*;   // per frame: its last sample
-  int32_t prev = 0;
-  bool have = false;
-  __device__ __forceinline__ void seed(uint32_t v) {
-    prev = (int32_t)(int16_t)(uint16_t)v;
-    have = true;
-  }
-  __device__ __forceinline__ void add(X3LevAcc& a, uint32_t v) {
-    const int32_t s = (int32_t)(int16_t)(uint16_t)v;
-    if (have) a.add_value(x3l_diff(s, prev));
-    prev = s;
-    have = true;
-  }
-  // a position the lane sees and its bins do not hold (in front of or behind a range's cut of the frame): it is the next
-  // position's `prev` all the same
-  __device__ __forceinline__ void skip(uint32_t v) {
-    prev = (int32_t)(int16_t)(uint16_t)v;
-    have = true;
-  }
-};
-// x3w_stretch's watch for X3LevDiff: the stretch's seed into the signal, the frame's last sample to its word of the tails
+struct X3LevDiff;
 struct X3LevDiffWatch {
   X3LevDiff& sig;
   int32_t* at;
-  __device__ __forceinline__ void seed(uint32_t v) const { sig.seed(v); }
+  __device__ __forceinline__ void seed(uint32_t v) const;
   __device__ __forceinline__ void end(uint32_t v) const { *at = (int32_t)(int16_t)(uint16_t)v; }
 };
+struct X3LevDiff : X3LevPlain {
+  static constexpr bool kSeam = true;
+  using Tail = int32_t*;   // per frame: its last sample
+  int32_t* last = nullptr;
+  int32_t prev = 0;
+  bool have = false;
+  __device__ __forceinline__ void begin(Tail tail, const X3LevAt& at) { last = tail + at.f; }
+  __device__ __forceinline__ X3LevDiffWatch watch() { return X3LevDiffWatch{*this, last}; }
+  __device__ __forceinline__ void add(X3LevAcc& a, uint32_t v) {
+    const int32_t s = (int32_t)(int16_t)(uint16_t)v;
+    if (have) a.add_value(x3l_diff(s, prev));
+    skip(v);
+  }
+  __device__ __forceinline__ void skip(uint32_t v) {   // (the next position's `prev`; a seed is the same)
+    prev = (int32_t)(int16_t)(uint16_t)v;
+    have = true;
+  }
+  __device__ __forceinline__ void end(bool frame) {
+    if (frame) *last = prev;
+  }
+};
+__device__ __forceinline__ void X3LevDiffWatch::seed(uint32_t v) const { sig.skip(v); }
 
 // X3LevFir (x3_fir_levels_dev): y = clamp((sum over t < T of c[t] * x[i - t]) >> shift, 16 bits).  The
 // taps come uniform from a kernel argument, those at and behind T zero, so that one instance serves every T; sum |c| <= 32768
 // (the host's check) keeps the sum inside 2^30, and taps and samples inside the 24 bits of the multiply.  The lane holds the
 // seven samples in front of the current one in registers and counts the samples it has seen: a position adds y once the lane
 // has decoded T samples of its own.  It takes no seed: nothing rests on the index's sample field.  The positions a lane cannot
-// form -- the first T - 1 of its stretch -- are x3_levels_fir_seam_kernel's, from the EDGE RECORD the lane leaves: the
-// stretch's first and last min(n, 7) samples and n.  The heads are stored as they pass, the rest by end().
+// form -- the first T - 1 of its stretch -- are the FIR seam kernels', from the EDGE RECORD the lane leaves: the stretch's
+// first and last min(n, 7) samples and n.  The heads are stored as they pass, the rest by end().
 #define X3L_FIR_TAPS 8
 #define X3L_FIR_HIST (X3L_FIR_TAPS - 1)
 struct X3FirTaps {
@@ -221,21 +258,39 @@ struct X3LevFirTail {   // the kernels' last argument
   X3FirEdge* edges;   // F * stride records
   uint32_t stride;    // records per frame: the stretches of a frame at most
 };
+// THE MULTIPLY.  Taps (16 bits by the host's check) and samples are sign-extended from 24 bits in the open and multiplied
+// plainly: the compiler picks the full-rate v_mul_i32_i24 by itself, in every FIR kernel of both files (the listing record in
+// profiles/levels_protocol/ counts them).  The other form the family had, HIP's __mul24, is a static inline wrapper of the HIP
+// headers that is not force-inlined: how the compiler treats it in one kernel depended on how many others called it (one
+// multiply came out in another encoding when the range kernels were added; profiles/fir_range_levels/isa_compare.txt), so a
+// kernel's instructions could change with a kernel added elsewhere.  The taps' extension is scalar and loop-invariant.
+__device__ __forceinline__ int32_t x3l_mul24(int32_t c, int32_t v) {
+  return ((int32_t)((uint32_t)c << 8) >> 8) * ((int32_t)((uint32_t)v << 8) >> 8);
+}
 __device__ __forceinline__ int32_t x3l_fir_value(const X3FirTaps& k, int32_t s, const int32_t (&d)[X3L_FIR_HIST]) {
-  int32_t acc = __mul24(k.c[0], s);
+  int32_t acc = x3l_mul24(k.c[0], s);
 #pragma unroll
-  for (int t = 1; t < X3L_FIR_TAPS; ++t) acc += __mul24(k.c[t], d[t - 1]);
+  for (int t = 1; t < X3L_FIR_TAPS; ++t) acc += x3l_mul24(k.c[t], d[t - 1]);
   return min(max(acc >> k.shift, -32768), 32767);
 }
-struct X3LevFir {
-  static constexpr bool kDiff = false, kFir = true, kState = true, kTone = false, kBank = false;
+// The delay line, in ONE copy.  kEdge (X3LevFir: the accumulate kernels of both files and the levels fix-up): the lane leaves
+// the edge record of its (frame, stretch).  Without (X3LevFirCarry: x3_range_levels_fir_fixup_kernel): no record is touched,
+// the history is the caller's to keep from frame to frame, and cnt is how many of the samples in d[] are valid.
+template <bool kEdge>
+struct X3LevFirT : X3LevPlain {
   using Tail = X3LevFirTail;
   X3FirTaps k;   // (uniform: the kernel's argument)
   X3FirEdge* edge = nullptr;
   int32_t d[X3L_FIR_HIST] = {0, 0, 0, 0, 0, 0, 0};   // d[t]: the sample t + 1 positions in front of the current one
-  uint32_t cnt = 0;                                  // samples seen
+  uint32_t cnt = 0;                                  // samples seen (what counts is cnt >= T - 1)
+  __device__ __forceinline__ void begin(const Tail& tail, const X3LevAt& at) {
+    k = tail.k;
+    if constexpr (kEdge) edge = tail.edges + (at.f * tail.stride + at.j);   // (f < F, j < ns <= stride: below F * stride)
+  }
   __device__ __forceinline__ void push(int32_t s) {
-    if (cnt < (uint32_t)X3L_FIR_HIST) edge->head[cnt] = (int16_t)s;
+    if constexpr (kEdge) {
+      if (cnt < (uint32_t)X3L_FIR_HIST) edge->head[cnt] = (int16_t)s;
+    }
     ++cnt;
 #pragma unroll
     for (int t = X3L_FIR_HIST - 1; t >= 1; --t) d[t] = d[t - 1];
@@ -243,36 +298,63 @@ struct X3LevFir {
   }
   __device__ __forceinline__ void add(X3LevAcc& a, uint32_t v) {
     const int32_t s = (int32_t)(int16_t)(uint16_t)v;
-    if (cnt + 1u >= k.T) a.add_value(x3l_fir_value(k, s, d));
+    if (cnt + 1u >= k.T) a.add_value(x3l_fir_value(k, s, d));   // THE HISTORY RULE: T samples of the lane's own
     push(s);
   }
   __device__ __forceinline__ void skip(uint32_t v) { push((int32_t)(int16_t)(uint16_t)v); }
-  // behind the stretch's or frame's last sample: the rest of the edge record
-  __device__ __forceinline__ void end() const {
+  // behind the stretch's or the replayed frame's last sample: the rest of the edge record
+  __device__ __forceinline__ void end(bool) const {
+    static_assert(kEdge, "only a signal with an edge record has an end");
 #pragma unroll
     for (int t = 0; t < X3L_FIR_HIST; ++t) edge->tail[t] = (int16_t)d[t];
     edge->n = cnt;
   }
 };
+using X3LevFir = X3LevFirT<true>;
+using X3LevFirCarry = X3LevFirT<false>;
+
+// out[at] = v without a dynamic register index (the FIR seam kernels and the range FIR fix-up, collecting samples from
+// edge records, here and in x3_range_levels_kernel.h)
+__device__ __forceinline__ void x3l_fir_set(int32_t (&out)[X3L_FIR_HIST], uint32_t at, int32_t v) {
+#pragma unroll
+  for (int q = 0; q < X3L_FIR_HIST; ++q) out[q] = (uint32_t)q == at ? v : out[q];
+}
 
 // X3LevTone (x3_tone_levels_dev): a position adds x * cos[k] to the record's first slot (re, where
 // x3_level has sum_sq) and x * sin[k] to its second (im, where sum is), k = ph >> 22 of the 32-bit phase ph = position * step
 // mod 2^32; min, max and n are the samples'.  |x * w| <= 2^30 is formed in 32 bits and added in 64: exact, in any order, and
 // the atomic add of two's-complement re on the unsigned slot is exact too, so X3LevAcc, x3l_merge and x3l_merge_runs serve as
-// they are.  The phase is seeded with the lane's first position -- the product in 64 bits, then truncated -- and steps once
-// per position, counted or not: no history, no seam, no edge record.  The table is 1 024 words of (cos: low half, sin: high
-// half); `tab` is the workgroup's LDS copy in the accumulate kernel (x3l_tone_table) and the caller's array in the fix-up.
+// they are.  THE PHASE is seeded by begin() with the position of the first sample the signal sees -- the product in 64 bits,
+// then truncated -- and steps once per position, counted or not: no history, no seam, no edge record.  In the range calls
+//  the position is in the STREAM OR ENTRY, not in the range: `starts` is the CALLER'S d_starts,
+// entry-relative in the corpus form too, where the kernels otherwise see the plan's stream positions; arithmetic mod 2^64,
+// then mod 2^32, on untrusted words: a wrong start changes sums, never an address (ph >> 22 < 1 024).  The table is 1 024
+// words of (cos: low half, sin: high half): the workgroup's LDS copy in the accumulate kernels, the caller's array in the fix-ups.
 #define X3L_TONE_TABLE 1024
 struct X3LevToneTail {   // the kernels' last argument
   const uint32_t* table;   // the caller's d_table: X3L_TONE_TABLE words
   uint32_t step;
+  const uint64_t* starts = nullptr;   // the range calls: the caller's d_starts, n words
 };
-struct X3LevTone {
-  static constexpr bool kDiff = false, kFir = false, kState = true, kTone = true, kBank = false;
+// the accumulate kernels' copy of the table: 4 KB of LDS per workgroup, filled by all its lanes in front of the item loop
+__device__ __forceinline__ const uint32_t* x3l_tone_table(const uint32_t* __restrict__ table) {
+  __shared__ uint32_t s_tab[X3L_TONE_TABLE];
+  for (uint32_t t = threadIdx.x; t < (uint32_t)X3L_TONE_TABLE; t += blockDim.x) s_tab[t] = table[t];
+  __syncthreads();
+  return s_tab;
+}
+struct X3LevTone : X3LevPlain {
   using Tail = X3LevToneTail;
   const uint32_t* tab = nullptr;
   uint32_t step = 0, ph = 0;
-  __device__ __forceinline__ void seed(uint64_t g) { ph = (uint32_t)(g * (uint64_t)step); }
+  static __device__ __forceinline__ const uint32_t* lds_table(const Tail& tail) { return x3l_tone_table(tail.table); }
+  static __device__ __forceinline__ const uint32_t* table(const Tail& tail) { return tail.table; }
+  static __device__ __forceinline__ uint64_t origin(const Tail& tail, uint64_t w) { return tail.starts[w]; }
+  __device__ __forceinline__ void begin(const Tail& tail, const X3LevAt& at) {
+    tab = at.tab;
+    step = tail.step;
+    ph = (uint32_t)(at.g * (uint64_t)step);
+  }
   __device__ __forceinline__ void add(X3LevAcc& a, uint32_t v) {
     const int32_t s = (int32_t)(int16_t)(uint16_t)v;
     const uint32_t w = tab[ph >> 22];
@@ -285,46 +367,47 @@ struct X3LevTone {
   }
   __device__ __forceinline__ void skip(uint32_t) { ph += step; }
 };
-// the accumulate kernel's copy of the table: 4 KB of LDS per workgroup, filled by all its lanes in front of the item loop
-__device__ __forceinline__ const uint32_t* x3l_tone_table(const uint32_t* __restrict__ table) {
-  __shared__ uint32_t s_tab[X3L_TONE_TABLE];
-  for (uint32_t t = threadIdx.x; t < (uint32_t)X3L_TONE_TABLE; t += blockDim.x) s_tab[t] = table[t];
-  __syncthreads();
-  return s_tab;
-}
 
 // X3LevToneBank<NT> (x3_tone_bank_levels_dev): NT oscillators against the one table in one pass over
-// the stretch.  Slot t has a phase and a pair of int64 sums of its own, formed as X3LevTone forms its one pair; min, max and n
-// are the samples' and live once, in the binner's X3LevAcc, whose two sums stay 0.  NT is a compile-time count and every loop
-// over it is unrolled, so every slot index is a constant: registers, no scratch.  The steps are the tail's (uniform); a call with fewer
-// than NT tones has step 0 in its spare slots, which store() never writes.  A flush stores slot t < n_tones of the open bin
-// to the same record of PLANE t -- `r` is plane 0's record, the planes lie `stride` records apart -- through x3l_merge, and
-// clears the sums: one plane is X3LevTone's record byte for byte.
+// the stretch.  Slot t has a phase and a pair of int64 sums of its own, formed as X3LevTone forms its one pair and seeded with
+// the same position; min, max and n are the samples' and live once, in the binner's X3LevAcc, whose two sums stay 0.  NT is a
+// compile-time count and every loop over it is unrolled, so every slot index is a constant: registers, no scratch.  The steps
+// are the tail's (uniform); a call with fewer than NT tones has step 0 in its spare slots, which flush() never writes.
+// THE PLANE STORE: flush() adds slot t < n_tones of the open bin to the same record of PLANE t -- `r` is plane 0's record, the
+// planes lie `stride` records apart (partial rows or the caller's records: X3LevAt::rows) -- through x3l_merge, and the sums
+// start anew either way: one plane is X3LevTone's record byte for byte, and the bounds of one plane hold in each.
 #define X3L_TONE_BANK 8
 struct X3LevToneBankTail {   // the kernels' last argument
   const uint32_t* table;   // the caller's d_table: X3L_TONE_TABLE words
   uint32_t n_tones;        // 2 .. X3L_TONE_BANK planes are stored
   uint32_t steps[X3L_TONE_BANK];
-  uint64_t rows_stride;    // plane stride of the partial rows (the accumulate kernel): n_rows + F
-  uint64_t levels_stride;  // plane stride of the caller's records (the fix-up kernel): n_rows
+  uint64_t rows_stride;    // plane stride of the partial rows (the accumulate kernels)
+  uint64_t levels_stride;  // plane stride of the caller's records (the fix-up kernels)
+  const uint64_t* starts = nullptr;   // the range calls: the caller's d_starts, n words
 };
 template <uint32_t NT>
-struct X3LevToneBank {
+struct X3LevToneBank : X3LevPlain {
   static_assert(NT >= 2 && NT <= X3L_TONE_BANK, "2 .. X3L_TONE_BANK slots");
-  static constexpr bool kDiff = false, kFir = false, kState = true, kTone = false, kBank = true;
   using Tail = X3LevToneBankTail;
   const uint32_t* tab = nullptr;
+  uint64_t stride = 0;
+  uint32_t n_tones = 0;
   uint32_t step[NT], ph[NT];
   uint64_t re[NT];
   int64_t im[NT];
-  __device__ __forceinline__ void seed(const X3LevToneBankTail& tail, uint64_t g) {
+  static __device__ __forceinline__ const uint32_t* lds_table(const Tail& tail) { return x3l_tone_table(tail.table); }
+  static __device__ __forceinline__ const uint32_t* table(const Tail& tail) { return tail.table; }
+  static __device__ __forceinline__ uint64_t origin(const Tail& tail, uint64_t w) { return tail.starts[w]; }
+  __device__ __forceinline__ void begin(const Tail& tail, const X3LevAt& at) {
+    tab = at.tab;
+    stride = at.rows ? tail.rows_stride : tail.levels_stride;
+    n_tones = tail.n_tones;
 #pragma unroll
     for (uint32_t t = 0; t < NT; ++t) {
       step[t] = tail.steps[t];
-      ph[t] = (uint32_t)(g * (uint64_t)step[t]);
-      re[t] = 0;
-      im[t] = 0;
+      ph[t] = (uint32_t)(at.g * (uint64_t)step[t]);
     }
+    drop();
   }
   __device__ __forceinline__ void add(X3LevAcc& a, uint32_t v) {
     const int32_t s = (int32_t)(int16_t)(uint16_t)v;
@@ -343,8 +426,8 @@ struct X3LevToneBank {
 #pragma unroll
     for (uint32_t t = 0; t < NT; ++t) ph[t] += step[t];
   }
-  // the open bin (a: its min, max, n) into record r of plane 0 .. n_tones - 1; t * stride < n_tones * stride: inside the planes
-  __device__ __forceinline__ void store(x3_level* __restrict__ r, uint64_t stride, uint32_t n_tones, const X3LevAcc& a) const {
+  // (a: the open bin's min, max, n; t * stride < n_tones * stride: inside the planes)
+  __device__ __forceinline__ void flush(x3_level* __restrict__ r, const X3LevAcc& a) {
 #pragma unroll
     for (uint32_t t = 0; t < NT; ++t) {
       if (t < n_tones) {
@@ -354,8 +437,9 @@ struct X3LevToneBank {
         x3l_merge(r + t * stride, b);
       }
     }
+    drop();
   }
-  __device__ __forceinline__ void clear() {
+  __device__ __forceinline__ void drop() {
 #pragma unroll
     for (uint32_t t = 0; t < NT; ++t) {
       re[t] = 0;
@@ -365,21 +449,15 @@ struct X3LevToneBank {
 };
 
 // The bins of consecutive positions from g on: decode(put_at) hands sample s of a frame to put_at(s, value), in order;
-// the positions with keep(s) go to the signal, bins that fill go to flush, and so does the open one at the end; a position
-// without keep(s) counts in no bin, and a signal with history (X3LevDiff) still sees its sample.  Returns decode's.  A
-// signal with state (X3LevDiff) is the caller's, at `sig`; X3LevSamples has none and nothing of it is captured.
-template <class Signal = X3LevSamples, class Decode, class Keep, class Flush>
-__device__ __forceinline__ int32_t x3l_bin_samples(uint64_t g, uint64_t bl, Decode decode, Keep keep, Flush flush,
-                                                   Signal* sig = nullptr) {
+// the positions with keep(s) go to the signal's add(), the others to its skip() and count in no bin; bins that fill go to
+// flush(bin, acc), and so does the open one at the end.  Returns decode's.
+template <class Signal, class Decode, class Keep, class Flush>
+__device__ __forceinline__ int32_t x3l_bin_samples(uint64_t g, uint64_t bl, Decode decode, Keep keep, Flush flush, Signal& sig) {
   X3LevBinner bn;
   bn.open(g, bl);
   const int32_t r = decode([&](uint32_t s, uint32_t v) {
-    if (keep(s)) {
-      if constexpr (Signal::kState) bn.put(*sig, v, flush);
-      else bn.put(Signal{}, v, flush);
-    } else if constexpr (Signal::kState) {
-      sig->skip(v);
-    }
+    if (keep(s)) bn.put(sig, v, flush);
+    else sig.skip(v);
   });
   flush(bn.bin, bn.a);
   return r;
@@ -502,10 +580,7 @@ x3_levels_scan_kernel(const uint32_t* __restrict__ cnt, uint64_t F, uint64_t cap
   if (threadIdx.x == 0) row[F] = total;
 }
 
-// ---- accumulate: a lane per (frame, stretch) into the frame's own rows.  Signal: X3LevSamples, or X3LevDiff, whose lanes
-// take the stretch's seed from x3w_stretch and whose lane at the frame's end stores the frame's last sample to tail[f], or
-// X3LevTone, whose workgroups copy the table to LDS first and whose lanes seed the phase with their first position, or
-// X3LevToneBank<NT>, the same with NT phases
+// ---- accumulate: a lane per (frame, stretch) into the frame's own rows -- a bank's planes of them -- by the signal protocol
 template <class Signal>
 __global__ void __launch_bounds__(256)
 x3_levels_accum_kernel(const uint8_t* __restrict__ x3, uint64_t len, const uint64_t* __restrict__ frame_off, uint64_t F,
@@ -517,8 +592,7 @@ x3_levels_accum_kernel(const uint8_t* __restrict__ x3, uint64_t len, const uint6
   const uint64_t bl = x3l_bin_len(bin_len);
   const uint64_t n_items = F * ns;
   const uint64_t lanes = (uint64_t)gridDim.x * blockDim.x;
-  [[maybe_unused]] const uint32_t* tone_tab = nullptr;
-  if constexpr (Signal::kTone || Signal::kBank) tone_tab = x3l_tone_table(tail.table);
+  const uint32_t* const tab = Signal::lds_table(tail);
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_items; i += lanes) {
     const uint64_t f = i / ns;
     const uint32_t j = (uint32_t)(i - f * ns);
@@ -526,61 +600,24 @@ x3_levels_accum_kernel(const uint8_t* __restrict__ x3, uint64_t len, const uint6
     const X3LevFrame fr = frames[f];
     x3_level* const mine = rows + row[f];
     const uint64_t nlim = fr.nlim, b0 = fr.b0;
-    auto flush = [&](uint64_t bin, const X3LevAcc& a) {
-      if (bin < nlim) x3l_merge(mine + (bin - b0), a);
-    };
     // a stretch's samples come in order, from sample 0 or from the first sample of block sb * j
-    if constexpr (Signal::kBank) {   // (plane t's partial rows: rows + t * rows_stride, the same row index in each)
-      const uint64_t g = fr.pos + (j ? 1u + (uint64_t)sb * j * p.block_len : 0u);
-      Signal sig;
-      sig.tab = tone_tab;
-      sig.seed(tail, g);
-      auto flush_bank = [&](uint64_t bin, const X3LevAcc& a) {
-        if (bin < nlim) sig.store(mine + (bin - b0), tail.rows_stride, tail.n_tones, a);
-        sig.clear();
-      };
-      const int r = x3l_bin_samples(
-          g, bl, [&](auto put_at) { return x3w_stretch(x3, len, frame_off[f], p, idx, segd, sb, nseg, f, j, put_at); },
-          X3LevKeepAll{}, flush_bank, &sig);
-      if (r < 0) atomicOr(&fst[f], X3W_FLAG);
-    } else if constexpr (Signal::kTone) {
-      const uint64_t g = fr.pos + (j ? 1u + (uint64_t)sb * j * p.block_len : 0u);
-      Signal sig;
-      sig.tab = tone_tab;
-      sig.step = tail.step;
-      sig.seed(g);
-      const int r = x3l_bin_samples(
-          g, bl, [&](auto put_at) { return x3w_stretch(x3, len, frame_off[f], p, idx, segd, sb, nseg, f, j, put_at); },
-          X3LevKeepAll{}, flush, &sig);
-      if (r < 0) atomicOr(&fst[f], X3W_FLAG);
-    } else if constexpr (Signal::kFir) {
-      Signal sig;
-      sig.k = tail.k;
-      sig.edge = tail.edges + (f * tail.stride + j);   // (j < ns <= stride: below F * stride)
-      const int r = x3l_bin_samples(
-          fr.pos + (j ? 1u + (uint64_t)sb * j * p.block_len : 0u), bl,
-          [&](auto put_at) { return x3w_stretch(x3, len, frame_off[f], p, idx, segd, sb, nseg, f, j, put_at); }, X3LevKeepAll{}, flush,
-          &sig);
-      sig.end();
-      if (r < 0) atomicOr(&fst[f], X3W_FLAG);
-    } else if constexpr (Signal::kDiff) {
-      Signal sig;
-      const int r = x3l_bin_samples(
-          fr.pos + (j ? 1u + (uint64_t)sb * j * p.block_len : 0u), bl,
-          [&](auto put_at) { return x3w_stretch(x3, len, frame_off[f], p, idx, segd, sb, nseg, f, j, put_at, X3LevDiffWatch{sig, tail + f}); },
-          X3LevKeepAll{}, flush, &sig);
-      if (r < 0) atomicOr(&fst[f], X3W_FLAG);
-    } else {
-      const int r = x3l_bin_samples(
-          fr.pos + (j ? 1u + (uint64_t)sb * j * p.block_len : 0u), bl,
-          [&](auto put_at) { return x3w_stretch(x3, len, frame_off[f], p, idx, segd, sb, nseg, f, j, put_at); }, X3LevKeepAll{}, flush);
-      if (r < 0) atomicOr(&fst[f], X3W_FLAG);
-    }
+    const uint64_t g = fr.pos + (j ? 1u + (uint64_t)sb * j * p.block_len : 0u);
+    Signal sig;
+    sig.begin(tail, X3LevAt{f, j, g, tab, true});
+    auto flush = [&](uint64_t bin, const X3LevAcc& a) {
+      if (bin < nlim) sig.flush(mine + (bin - b0), a);
+      else sig.drop();
+    };
+    const int r = x3l_bin_samples(
+        g, bl, [&](auto put_at) { return x3w_stretch(x3, len, frame_off[f], p, idx, segd, sb, nseg, f, j, put_at, sig.watch()); },
+        X3LevKeepAll{}, flush, sig);
+    sig.end(false);
+    if (r < 0) atomicOr(&fst[f], X3W_FLAG);
   }
 }
 
-// ---- fix-up: a wave per frame (lane 0 works); scratch: a block's samples per wave of the grid.  X3LevDiff: tail[f] of
-// every frame it replays to status 0
+// ---- fix-up: a wave per frame (lane 0 works); scratch: a block's samples per wave of the grid.  A frame it replays to
+// status 0 is ONE stretch, at its stretch 0 (X3L_DONE says so), straight into the caller's records
 template <class Signal>
 __global__ void __launch_bounds__(256)
 x3_levels_fixup_kernel(const uint8_t* __restrict__ x3, const uint64_t* __restrict__ frame_off, uint64_t F, X3DevParams p,
@@ -599,37 +636,15 @@ x3_levels_fixup_kernel(const uint8_t* __restrict__ x3, const uint64_t* __restric
       fs = x3w_replay_frame(payload, p, blk, [](uint32_t, uint32_t) {});
       if (fs == X3D_OK) {   // every block decodes: once more, now into the caller's bins
         const X3LevFrame fr = frames[f];
+        Signal sig;
+        sig.begin(tail, X3LevAt{f, 0u, fr.pos, Signal::table(tail), false});
         auto flush = [&](uint64_t bin, const X3LevAcc& a) {
-          if (bin < fr.nlim) x3l_merge(levels + fr.obase + bin, a);
+          if (bin < fr.nlim) sig.flush(levels + fr.obase + bin, a);
+          else sig.drop();
         };
-        if constexpr (Signal::kBank) {   // (plane t's records: levels + t * levels_stride, the same record index in each)
-          Signal sig;
-          sig.tab = tail.table;
-          sig.seed(tail, fr.pos);
-          auto flush_bank = [&](uint64_t bin, const X3LevAcc& a) {
-            if (bin < fr.nlim) sig.store(levels + fr.obase + bin, tail.levels_stride, tail.n_tones, a);
-            sig.clear();
-          };
-          (void)x3l_bin_samples(fr.pos, bl, [&](auto put_at) { return x3w_replay_frame(payload, p, blk, put_at); }, X3LevKeepAll{}, flush_bank, &sig);
-        } else if constexpr (Signal::kTone) {
-          Signal sig;
-          sig.tab = tail.table;
-          sig.step = tail.step;
-          sig.seed(fr.pos);
-          (void)x3l_bin_samples(fr.pos, bl, [&](auto put_at) { return x3w_replay_frame(payload, p, blk, put_at); }, X3LevKeepAll{}, flush, &sig);
-        } else if constexpr (Signal::kFir) {   // the frame is ONE stretch now: its record is its stretch 0's (X3L_DONE says so)
-          Signal sig;
-          sig.k = tail.k;
-          sig.edge = tail.edges + f * tail.stride;
-          (void)x3l_bin_samples(fr.pos, bl, [&](auto put_at) { return x3w_replay_frame(payload, p, blk, put_at); }, X3LevKeepAll{}, flush, &sig);
-          sig.end();
-        } else if constexpr (Signal::kDiff) {
-          Signal sig;
-          (void)x3l_bin_samples(fr.pos, bl, [&](auto put_at) { return x3w_replay_frame(payload, p, blk, put_at); }, X3LevKeepAll{}, flush, &sig);
-          tail[f] = sig.prev;
-        } else {
-          (void)x3l_bin_samples(fr.pos, bl, [&](auto put_at) { return x3w_replay_frame(payload, p, blk, put_at); }, X3LevKeepAll{}, flush);
-        }
+        (void)x3l_bin_samples(fr.pos, bl, [&](auto put_at) { return x3w_replay_frame(payload, p, blk, put_at); }, X3LevKeepAll{},
+                              flush, sig);
+        sig.end(true);
       }
       fst[f] = fs | X3L_DONE;
       atomicAdd(&sum->replays, 1ull);
@@ -768,8 +783,7 @@ x3_levels_fir_seam_kernel(uint64_t F, uint32_t block_len, const uint2* __restric
 #pragma unroll
           for (int t = 0; t < X3L_FIR_HIST; ++t) {
             if ((uint32_t)t < m && H < need) {
-#pragma unroll
-              for (int q = 0; q < X3L_FIR_HIST; ++q) hist[q] = (uint32_t)q == H ? (int32_t)h.tail[t] : hist[q];
+              x3l_fir_set(hist, H, (int32_t)h.tail[t]);
               ++H;
             }
           }

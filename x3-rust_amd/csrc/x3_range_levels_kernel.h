@@ -25,23 +25,22 @@
 //  x3_range_levels_fixup_kernel  -- a wave per range, frames in order: flagged frames and pairs without rows through the
 //      reference's reader; the range's status; the summary
 //  x3_range_levels_merge_kernel  -- a lane per partial row, rows of one record side by side in a wave joined first
-// The accumulate and fix-up kernels are templates over the SIGNAL (x3_levels_kernel.h): X3LevSamples (the range-levels calls) or
-// X3LevDiff (x3_signal_range_levels_dev / x3_corpus_signal_range_levels_dev), which has two kernels more:
-//  x3_range_levels_lead_kernel   -- behind the plan: a range that starts at a frame's first sample gets the frame in front
-//  x3_range_levels_seam_kernel   -- behind the accumulate kernel: a lane per pair, the difference across the frame's front seam
-// (both at the end of this file)
-// x3_fir_range_levels_dev / x3_corpus_fir_range_levels_dev run the accumulate kernel's third instance,
-// X3RLevFir, between a lead kernel, a fix-up and a seam kernel of their own (FIR RANGE LEVELS, at the end of this file):
-//  x3_range_levels_fir_lead_kernel  -- behind the plan: up to T - 1 frames in front of a range that starts early in its frame
-//  x3_range_levels_fir_fixup_kernel -- x3_range_levels_fixup_kernel with the last seven samples carried from frame to frame
-//  x3_range_levels_fir_seam_kernel  -- behind the merge: a lane per (pair, stretch), the stretch's first T - 1 positions
-// x3_tone_range_levels_dev / x3_corpus_tone_range_levels_dev run the fourth instance of both templates,
-// X3RLevTone: X3LevTone with the phase seeded from the position in the STREAM OR ENTRY, not in the range (TONE RANGE LEVELS,
-// in front of the accumulate kernel); no kernel of its own.
-// x3_tone_bank_range_levels_dev / x3_corpus_tone_bank_range_levels_dev run the fifth,
-// X3RLevToneBank<NT>: X3LevToneBank<NT> seeded the same way, whose flushes go to n_tones PLANES of the partial rows and of the
-// caller's records; the init and merge kernels run once per plane on offset pointers, and one kernel of its own:
-//  x3_range_levels_planes_kernel -- behind the prep: the identities of the caller's records in planes 1 and up
+// The accumulate and fix-up kernels are templates over the SIGNAL and call it by THE SIGNAL PROTOCOL of x3_levels_kernel.h,
+// around one x3l_bin_samples each: X3LevSamples (the range-levels calls), X3LevDiff (x3_signal_range_levels_dev /
+// x3_corpus_signal_range_levels_dev), X3LevFir (x3_fir_range_levels_dev / x3_corpus_fir_range_levels_dev;
+// section 23; the accumulate kernel only), X3LevTone (x3_tone_range_levels_dev / x3_corpus_tone_range_levels_dev; section 25)
+// and X3LevToneBank<NT> (x3_tone_bank_range_levels_dev / x3_corpus_tone_bank_range_levels_dev; section 27), whose flushes go to
+// n_tones PLANES of the partial rows and of the caller's records.  What this file adds for a signal is only what is a
+// property of the ranges' walk, not of a sample:
+//  x3_range_levels_lead_kernel   -- X3LevDiff (need 1) and X3LevFir (need T - 1), behind the plan: the frames in front of a
+//      range that starts early in its first frame
+//  x3_range_levels_seam_kernel   -- X3LevDiff, behind the accumulate kernel: a lane per pair, the difference across the
+//      frame's front seam; the fix-up's share of the seams is behind its one flag, kSeam
+//  x3_range_levels_fir_fixup_kernel -- X3LevFir: x3_range_levels_fixup_kernel with the last seven samples carried from frame
+//      to frame (X3LevFirCarry), a different walk
+//  x3_range_levels_fir_seam_kernel  -- X3LevFir, behind the merge: a lane per (pair, stretch), the stretch's first T - 1 positions
+//  x3_range_levels_planes_kernel -- X3LevToneBank, behind the prep: the identities of the caller's records in planes 1 and up;
+//      the init and merge kernels run once per plane on offset pointers
 //
 // CAPACITY.  The workspace holds P pairs and cap = rows_cap + P partial rows, both sized on the host.  A pair with q >= P or
 // whose rows end behind cap has no rows: accumulate and merge skip it (x3rl_no_rows, recomputed from q and the scan) and the
@@ -166,37 +165,6 @@ x3_range_levels_init_kernel(const unsigned long long* __restrict__ cov_off, uint
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < used; i += (uint64_t)gridDim.x * blockDim.x) rows[i] = id;
 }
 
-// ---- TONE RANGE LEVELS (x3_tone_range_levels_dev / x3_corpus_tone_range_levels_dev)
-// The call cuts the stream's or entry's tone signal: bins are counted from the range, the phase from the entry.  Sample lo of
-// pair (w, f) is position starts[w] + r0 of its stream or entry -- `starts` the CALLER'S array, entry-relative in the corpus
-// form too, where the kernels otherwise see the plan's stream positions -- so sample s of the frame is position
-// starts[w] + r0 - lo + s, whatever the range holds of it.  An accumulate lane seeds with its first sample's position and
-// x3l_bin_samples lets skip() step the phase over the samples outside [lo, hi); the fix-up seeds with sample 0's.  All of it
-// is arithmetic mod 2^64, then mod 2^32, on untrusted words: a wrong start changes sums, never an address (ph >> 22 < 1 024).
-struct X3RLevToneTail {   // the kernels' last argument
-  const uint32_t* table;    // the caller's d_table: X3L_TONE_TABLE words
-  uint32_t step;
-  const uint64_t* starts;   // the caller's d_starts: n words
-};
-struct X3RLevTone : X3LevTone {
-  using Tail = X3RLevToneTail;
-};
-
-// ---- TONE BANK RANGE LEVELS (x3_tone_bank_range_levels_dev / x3_corpus_tone_bank_range_levels_dev)
-// The bank is n_tones tone-range calls laid plane by plane: X3LevToneBank<NT> with X3RLevTone's seed in every slot -- the same
-// position, truncated per slot as X3LevTone::seed truncates it -- and skip() stepping all phases over the samples outside
-// [lo, hi).  Pairs, scans, verdicts and row indices are one plane's and serve all: plane t's partial rows are
-// rows + t * bank.rows_stride (cap), its records levels + t * bank.levels_stride (rows_cap), and a flush stores slot
-// t < n_tones at the row or record index the single call would use, so the bounds of one plane hold in each.
-struct X3RLevToneBankTail {   // the kernels' last argument
-  X3LevToneBankTail bank;   // table, n_tones, steps (0 in the spare slots); rows_stride = cap, levels_stride = rows_cap
-  const uint64_t* starts;   // the caller's d_starts: n words
-};
-template <uint32_t NT>
-struct X3RLevToneBank : X3LevToneBank<NT> {
-  using Tail = X3RLevToneBankTail;
-};
-
 // ---- planes: the identities of the caller's records in planes 1 .. planes - 1, where x3_range_levels_prep_kernel wrote plane
 // 0's -- the same records by the same tests (packed: those of ranges that have room; padded: all n * stride), one owner
 // search per record for all planes.  Bounds: i < rows_cap (n * stride <= rows_cap: the host), t < planes: below planes * rows_cap.
@@ -214,15 +182,12 @@ x3_range_levels_planes_kernel(uint64_t n, const unsigned long long* __restrict__
   }
 }
 
-// ---- accumulate: a lane per (pair, stretch) into the pair's own rows.  Signal: X3LevSamples; X3RLevFir, whose lanes add the
-// positions whose T samples they decoded themselves, inside or in front of [lo, hi), and leave the edge record of their
-// (frame, stretch) -- several pairs of one frame write the same values; or X3LevDiff, whose lanes take
-// the stretch's seed from x3w_stretch, see the samples outside [lo, hi) without counting them (the sample in front of lo is
-// sample lo's `prev`), and whose lane at the frame's end stores the frame's last sample to tail[f]; or X3RLevTone, whose
-// workgroups copy the table to LDS first (every lane, in front of the item loop) and whose lanes seed the phase with the
-// entry-relative position of their first sample; or X3RLevToneBank<NT>, the same with NT phases, whose flush stores the
-// open bin to the pair's rows in every plane (no store in the sample loop).  A pair with an empty cut
-// (a lead frame) runs its stretches for the proof and the tail and touches no row: cnt is 0.
+// ---- accumulate: a lane per (pair, stretch) into the pair's own rows -- a bank's planes of them -- by the signal protocol
+// (x3_levels_kernel.h).  The lane sees every sample of its stretch and keeps those of the pair's cut [lo, hi): the others go
+// to the signal's skip(), so the sample in front of lo is sample lo's history and the phase steps over it; its first position
+// is origin() + r0 - lo + s0 for a signal that counts from the stream or entry (pr.w < n: the prep kernel's owner of q).  What
+// end() and the watch leave per frame (the edge record, the frame's last sample) several pairs of one frame write with the
+// same values.  A pair with an empty cut (a lead frame) runs its stretches for the proof and those, and touches no row: cnt is 0.
 template <class Signal>
 __global__ void __launch_bounds__(256)
 x3_range_levels_accum_kernel(const uint8_t* __restrict__ x3, uint64_t len, const uint64_t* __restrict__ frame_off, X3DevParams p,
@@ -235,9 +200,7 @@ x3_range_levels_accum_kernel(const uint8_t* __restrict__ x3, uint64_t len, const
   const uint64_t bl = x3l_bin_len(bin_len);
   const uint64_t n_items = min((uint64_t)cov_off[n], P) * ns;
   const uint64_t lanes = (uint64_t)gridDim.x * blockDim.x;
-  [[maybe_unused]] const uint32_t* tone_tab = nullptr;
-  if constexpr (Signal::kTone) tone_tab = x3l_tone_table(tail.table);
-  if constexpr (Signal::kBank) tone_tab = x3l_tone_table(tail.bank.table);
+  const uint32_t* const tab = Signal::lds_table(tail);
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_items; i += lanes) {
     const uint64_t q = i / ns;
     const uint32_t j = (uint32_t)(i - q * ns);
@@ -246,52 +209,34 @@ x3_range_levels_accum_kernel(const uint8_t* __restrict__ x3, uint64_t len, const
     if (x3rl_no_rows(prow, q, P, cap)) continue;   // (the fix-up's)
     x3_level* const mine = rows + prow[q];
     const uint32_t b0 = pr.b0, cnt = pr.cnt, lo = pr.lo, span = pr.hi - pr.lo;
-    [[maybe_unused]] Signal sig;
-    auto flush = [&](uint64_t bin, const X3LevAcc& a) {
-      if constexpr (Signal::kBank) {   // (plane t's rows: rows + t * rows_stride, the same row index in each)
-        if (bin - b0 < (uint64_t)cnt) sig.store(mine + (bin - b0), tail.bank.rows_stride, tail.bank.n_tones, a);
-        sig.clear();
-      } else {
-        if (bin - b0 < (uint64_t)cnt) x3l_merge(mine + (bin - b0), a);
-      }
-    };
     // a stretch's samples come in order, from sample 0 or from the first sample of block sb * j; the first of them inside
     // the range, if any, is sample max(s0, lo)
     const uint64_t s0 = j ? 1u + (uint64_t)sb * j * p.block_len : 0u;
-    if constexpr (Signal::kFir) {
-      sig.k = tail.k;
-      sig.edge = tail.edges + (pr.f * tail.stride + j);   // (pr.f < F, j < ns <= stride: below F * stride)
-    }
-    if constexpr (Signal::kTone) {
-      sig.tab = tone_tab;
-      sig.step = tail.step;
-      sig.seed(tail.starts[pr.w] + pr.r0 - lo + s0);   // (pr.w < n: the prep kernel's owner of q)
-    }
-    if constexpr (Signal::kBank) {
-      sig.tab = tone_tab;
-      sig.seed(tail.bank, tail.starts[pr.w] + pr.r0 - lo + s0);
-    }
-    const int r = x3l_bin_samples<Signal>(
+    Signal sig;
+    sig.begin(tail, X3LevAt{pr.f, j, Signal::origin(tail, pr.w) + pr.r0 - lo + s0, tab, true});
+    auto flush = [&](uint64_t bin, const X3LevAcc& a) {
+      if (bin - b0 < (uint64_t)cnt) sig.flush(mine + (bin - b0), a);
+      else sig.drop();
+    };
+    const int r = x3l_bin_samples(
         (uint64_t)pr.r0 + (s0 > lo ? s0 - lo : 0u), bl,
-        [&](auto put_at) {
-          if constexpr (Signal::kDiff)
-            return x3w_stretch(x3, len, frame_off[pr.f], p, idx, segd, sb, nseg, pr.f, j, put_at, X3LevDiffWatch{sig, tail + pr.f});
-          else
-            return x3w_stretch(x3, len, frame_off[pr.f], p, idx, segd, sb, nseg, pr.f, j, put_at);
-        },
-        [&](uint32_t s) { return s - lo < span; }, flush, &sig);
-    if constexpr (Signal::kFir) sig.end();
+        [&](auto put_at) { return x3w_stretch(x3, len, frame_off[pr.f], p, idx, segd, sb, nseg, pr.f, j, put_at, sig.watch()); },
+        [&](uint32_t s) { return s - lo < span; }, flush, sig);
+    sig.end(false);
     if (r < 0) atomicOr(&fst[pr.f], X3W_FLAG);
   }
 }
 
 // ---- fix-up: a wave per range (lane 0 works), frames in order; scratch: a block's samples per wave of the grid.  The
-// frame words are read, never written: a frame may lie under other ranges, whose waves read it too.
-// X3LevDiff: the wave carries the frame in front -- its final status, its last sample, whether its pair went the fast way
-// (x3rl_fast) -- and adds the seams x3_range_levels_seam_kernel leaves; a lead frame (lead[w]: the plan's first frame lies in
-// front of the range) never gives the range its status; tail[f] of every frame it replays to status 0.
-// X3RLevTone: the replay into the records seeds the phase with the position of the frame's sample 0 and reads the caller's table.
-// X3RLevToneBank<NT>: the same with NT phases, into the range's records in every plane.
+// frame words are read, never written: a frame may lie under other ranges, whose waves read it too -- and for the same
+// reason the signal's end() is not called: what a frame leaves behind its last sample belongs to the pairs that went the
+// fast way (x3rl_fast).  The replay into the records begins the signal at the frame's sample 0 and reads the caller's table.
+// kSeam (X3LevDiff): the wave carries the frame in front -- its final status, its last sample, whether its pair went the fast
+// way -- adds the seams x3_range_levels_seam_kernel leaves, stores tail[f] of every frame it replays to status 0, and a lead
+// frame (k < lead[w]: the plan's first frames lie in front of the range) never gives the range its status.  This is the one
+// place where a kernel asks for a signal by a flag, and it stays a flag, not a member of the protocol: what it guards is state
+// of THIS walk -- the loop's k, the previous frame's verdict, the plan's lead -- and no property of a sample; a hook would take
+// all of that as arguments and be the same lines at a distance.
 __device__ __forceinline__ bool x3rl_fast(int32_t word, const unsigned long long* __restrict__ prow, uint64_t q, uint64_t P, uint64_t cap) {
   return word == X3D_OK && !x3rl_no_rows(prow, q, P, cap);
 }
@@ -319,8 +264,10 @@ x3_range_levels_fixup_kernel(const uint8_t* __restrict__ x3, const uint64_t* __r
     if (st == X3D_OK) {
       const uint64_t start = starts[w], q0 = cov_off[w];
       const uint32_t L = lens[w], R = erows[w];
+      uint32_t ld = 0;   // the plan's lead frames (only a signal with a seam has a lead kernel)
+      if constexpr (Signal::kSeam) ld = lead[w];
       x3_level* const mine = levels + x3rl_base(row_off, stride, w);
-      // X3LevDiff: the frame in front -- its final status (none yet: not X3D_OK), its last sample, the way its pair went
+      // kSeam: the frame in front -- its final status (none yet: not X3D_OK), its last sample, the way its pair went
       [[maybe_unused]] int32_t pfs = X3D_BAD_ARG, ptail = 0;
       [[maybe_unused]] bool pfast = false;
       for (uint32_t k = 0; k < pl.ncov; ++k) {
@@ -330,7 +277,7 @@ x3_range_levels_fixup_kernel(const uint8_t* __restrict__ x3, const uint64_t* __r
         [[maybe_unused]] const bool fast = x3rl_fast(fs, prow, q0 + k, P, cap);
         if (fs == X3W_FLAG || (fs == X3D_OK && x3rl_no_rows(prow, q0 + k, P, cap))) {
           const uint8_t* const payload = x3 + frame_off[f] + 20u;
-          if constexpr (Signal::kDiff) {
+          if constexpr (Signal::kSeam) {
             fs = x3w_replay_frame(payload, p, blk, [&](uint32_t, uint32_t v) { ftail = (int32_t)(int16_t)(uint16_t)v; });
             if (fs == X3D_OK) tail[f] = ftail;
           } else {
@@ -338,34 +285,22 @@ x3_range_levels_fixup_kernel(const uint8_t* __restrict__ x3, const uint64_t* __r
           }
           uint32_t lo, hi, r0;
           if (fs == X3D_OK && x3rl_cut(so, f, start, L, lo, hi, r0)) {   // every block decodes: once more, into the records
-            [[maybe_unused]] Signal sig;
+            Signal sig;
+            sig.begin(tail, X3LevAt{f, 0u, Signal::origin(tail, w) + r0 - lo, Signal::table(tail), false});
             auto flush = [&](uint64_t bin, const X3LevAcc& a) {
-              if constexpr (Signal::kBank) {   // (plane t's records: levels + t * levels_stride, the same index in each)
-                if (bin < (uint64_t)R) sig.store(mine + bin, tail.bank.levels_stride, tail.bank.n_tones, a);
-                sig.clear();
-              } else {
-                if (bin < (uint64_t)R) x3l_merge(mine + bin, a);
-              }
+              if (bin < (uint64_t)R) sig.flush(mine + bin, a);
+              else sig.drop();
             };
             const uint32_t span = hi - lo;
-            if constexpr (Signal::kTone) {
-              sig.tab = tail.table;
-              sig.step = tail.step;
-              sig.seed(tail.starts[w] + r0 - lo);
-            }
-            if constexpr (Signal::kBank) {
-              sig.tab = tail.bank.table;
-              sig.seed(tail.bank, tail.starts[w] + r0 - lo);
-            }
-            (void)x3l_bin_samples<Signal>(
+            (void)x3l_bin_samples(
                 r0, bl, [&](auto put_at) { return x3w_replay_frame(payload, p, blk, put_at); },
-                [&](uint32_t s) { return s - lo < span; }, flush, &sig);
+                [&](uint32_t s) { return s - lo < span; }, flush, sig);
           }
           ++replayed;
-        } else if constexpr (Signal::kDiff) {
+        } else if constexpr (Signal::kSeam) {
           if (fast) ftail = tail[f];   // (the accumulate kernel's: every stretch of the frame is proven, the last one stored it)
         }
-        if constexpr (Signal::kDiff) {
+        if constexpr (Signal::kSeam) {
           // the seam in front of frame f: both frames end with status 0, sample 0 of f lies in the range; the seam kernel has
           // it iff both pairs went the fast way (the same tests there)
           uint32_t lo, hi, r0;
@@ -381,10 +316,10 @@ x3_range_levels_fixup_kernel(const uint8_t* __restrict__ x3, const uint64_t* __r
           pfs = fs;
           ptail = ftail;
           pfast = fast;
-          if (fs != X3D_OK && st == X3D_OK && k >= (lead[w] ? 1u : 0u)) st = fs;   // (the first COVERING frame in frame order)
-        } else {
-          if (fs != X3D_OK && st == X3D_OK) st = fs;   // (the first in frame order; the frames behind it still count)
         }
+        // THE STATUS RULE (this kernel's and x3_range_levels_fir_fixup_kernel's): the first COVERING frame in frame order
+        // that ends with a status gives it to the range; the frames behind it still count
+        if (fs != X3D_OK && st == X3D_OK && k >= ld) st = fs;
       }
     }
     if (replayed) atomicAdd(&sum->w.replays, (unsigned long long)replayed);
@@ -427,22 +362,34 @@ x3_range_levels_merge_kernel(const X3RLevPair* __restrict__ pairs, const unsigne
   }
 }
 
-// ---- X3_LEVEL_SIGNAL_DIFF (x3_signal_range_levels_dev / x3_corpus_signal_range_levels_dev)
-// THE LEAD FRAME.  The difference at a range's first position needs the sample in front of it.  Inside a frame a lane has
-// it: it decodes the frame from its start or takes a seed.  A range with len > 0 that starts at sample 0 of its first
-// covering frame fa, with fa not the first frame of its stream or entry, needs frame fa - 1: checked, proven by all its
-// stretches, its last sample known.  x3_range_levels_lead_kernel, behind the plan kernel and in front of the range scan, widens
-// such a plan by that one frame (fa - 1, ncov + 1) and notes it in lead[w]; the frame is then an ordinary pair whose cut is
-// empty (x3rl_cut false, cnt 0).  ent: the corpus's entry table (first: the entry's first frame), NULL for a stream (0).
-// Bounds: fa - 1 >= first >= 0 and fa - 1 < fa, a frame of the table the plan searched; ncov + 1 <= F.
+// ---- THE LEAD FRAMES (the signals with history: X3LevDiff, need = 1; X3LevFir, need = T - 1, section 23)
+// The first positions of a range need the `need` samples in front of them.  Inside a frame a lane has them: it decodes the
+// frame from its start or from a stretch in front.  A range with len > 0 that starts less than `need` samples behind the first
+// sample of its first covering frame fa needs the frames in front: checked, proven by all their stretches, their last samples
+// known.  This kernel, behind the plan kernel and in front of the range scan, widens such a plan by ld frames (fa - ld,
+// ncov + ld), ld the smallest count with start - so[fa - ld] >= need, not past the first frame of its stream or entry, and
+// notes it in lead[w]; the frames are then ordinary pairs whose cut is empty (x3rl_cut false, cnt 0).  At most
+// min(need, 7) steps whatever so[] says (a checked frame has a sample; one that fails its check ends the history anyway).
+// ent: the corpus's entry table (first: the entry's first frame), NULL for a stream (0).
+// Bounds: fa - ld >= first >= 0, frames of the table the plan searched; ncov + ld <= F.
+// ONE KERNEL FOR BOTH.  The difference had a kernel of its own, whose rule was: one frame, iff fa > first and
+// so[fa] == start.  With need = 1 the loop below runs at most once, iff fa > first, and takes the frame unless
+// so[fa] <= start and start - so[fa] >= 1, that is iff so[fa] >= start.  The two differ only where so[fa] > start, and no plan
+// has that: fa is x3w_search's result (x3w_plan_stream, x3w_plan_entry), whose lower bound moves only to an f with
+// so[f] <= start and begins at one the plan has tested (a stream: so[0] <= start; a corpus: `starts` here is the plan's
+// gstart, g = so[first_frame] + the caller's entry-relative start, which does not wrap, so so[first_frame] <= g), so
+// so[fa] <= start holds for every so[], one that lies included -- the search may then name a wrong frame, never one that
+// begins behind the start.  A plan without status 0 or without covering frames passes both rules untouched.  So lead[w] and
+// the widened plan are the same word for word, and lead[w] is 0 or 1 when need is 1.
 __global__ void __launch_bounds__(256)
 x3_range_levels_lead_kernel(const uint64_t* __restrict__ so, const x3_corpus_entry* __restrict__ ent, uint64_t n_ent,
                             const uint32_t* __restrict__ entries, const uint64_t* __restrict__ starts,
-                            const uint32_t* __restrict__ lens, uint64_t n, X3WinPlan* __restrict__ plan, uint32_t* __restrict__ lead) {
+                            const uint32_t* __restrict__ lens, uint64_t n, uint32_t need, X3WinPlan* __restrict__ plan,
+                            uint32_t* __restrict__ lead) {
   for (uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; w < n; w += (uint64_t)gridDim.x * blockDim.x) {
     X3WinPlan pl = plan[w];
     uint32_t ld = 0;
-    if (pl.status == X3D_OK && pl.ncov && lens[w]) {
+    if (pl.status == X3D_OK && pl.ncov && lens[w] && need) {
       uint64_t first = 0;
       bool known = true;
       if (ent) {
@@ -450,11 +397,19 @@ x3_range_levels_lead_kernel(const uint64_t* __restrict__ so, const x3_corpus_ent
         known = e < n_ent;   // (the plan has refused the others)
         if (known) first = ent[e].first_frame;
       }
-      if (known && pl.fa > first && so[pl.fa] == starts[w]) {
-        --pl.fa;
-        ++pl.ncov;
-        ld = 1u;
-        plan[w] = pl;
+      const uint64_t start = starts[w];
+      if (known && pl.fa >= first) {
+        const uint32_t most = (uint32_t)min((uint64_t)min(need, (uint32_t)X3L_FIR_HIST), pl.fa - first);
+        while (ld < most) {
+          const uint64_t pos = so[pl.fa - ld];
+          if (pos <= start && start - pos >= (uint64_t)need) break;
+          ++ld;
+        }
+        if (ld) {
+          pl.fa -= ld;
+          pl.ncov += ld;
+          plan[w] = pl;
+        }
       }
     }
     lead[w] = ld;
@@ -525,64 +480,10 @@ x3_range_levels_seam_kernel(const uint8_t* __restrict__ x3, uint64_t len, const 
 // pair's own lanes ran every stretch to its proof and stored all ns records; index f * stride + j with f a frame of the
 // plan (< F) and j < ns <= stride.
 
-// x3l_fir_value without HIP's __mul24: that wrapper is a static inline function of the HIP headers, and every further kernel
-// that calls it changes how the compiler treats it in the kernels that already did -- the X3LevFir instances of the levels
-// kernels came out with other register numbers and one other multiply, and they are to stay the parent's instruction for
-// instruction.  Taps (16 bits by the host's check) and samples are sign-extended from 24 bits in the open, which is what
-// lets the compiler pick the full-rate 24-bit multiply by itself; the taps' extension is scalar and loop-invariant.
-__device__ __forceinline__ int32_t x3rl_mul24(int32_t c, int32_t v) {
-  return ((int32_t)((uint32_t)c << 8) >> 8) * ((int32_t)((uint32_t)v << 8) >> 8);
-}
-__device__ __forceinline__ int32_t x3rl_fir_value(const X3FirTaps& k, int32_t s, const int32_t (&d)[X3L_FIR_HIST]) {
-  int32_t acc = x3rl_mul24(k.c[0], s);
-#pragma unroll
-  for (int t = 1; t < X3L_FIR_TAPS; ++t) acc += x3rl_mul24(k.c[t], d[t - 1]);
-  return min(max(acc >> k.shift, -32768), 32767);
-}
-
-// The FIR signal of these kernels: X3LevFir's delay line and count (x3_levels_kernel.h) with x3rl_fir_value, in ONE copy for
-// both of its users.  kEdge (X3RLevFir, the accumulate kernel's): the lane leaves the edge record of its (frame, stretch) --
-// the heads stored as they pass, the rest by end().  Without (X3LevFirCarry, the fix-up's): no record is touched, the history
-// is the caller's to keep from frame to frame, and cnt is how many of the samples in d[] are valid.
-template <bool kEdge>
-struct X3RLevFirT {
-  static constexpr bool kDiff = false, kFir = true, kState = true, kTone = false, kBank = false;
-  using Tail = X3LevFirTail;
-  X3FirTaps k;   // (uniform: the kernel's argument)
-  X3FirEdge* edge = nullptr;
-  int32_t d[X3L_FIR_HIST] = {0, 0, 0, 0, 0, 0, 0};   // d[t]: the sample t + 1 positions in front of the current one
-  uint32_t cnt = 0;                                  // samples seen (what counts is cnt >= T - 1)
-  __device__ __forceinline__ void push(int32_t s) {
-    if constexpr (kEdge) {
-      if (cnt < (uint32_t)X3L_FIR_HIST) edge->head[cnt] = (int16_t)s;
-    }
-    ++cnt;
-#pragma unroll
-    for (int t = X3L_FIR_HIST - 1; t >= 1; --t) d[t] = d[t - 1];
-    d[0] = s;
-  }
-  __device__ __forceinline__ void add(X3LevAcc& a, uint32_t v) {
-    const int32_t s = (int32_t)(int16_t)(uint16_t)v;
-    if (cnt + 1u >= k.T) a.add_value(x3rl_fir_value(k, s, d));
-    push(s);
-  }
-  __device__ __forceinline__ void skip(uint32_t v) { push((int32_t)(int16_t)(uint16_t)v); }
-  // behind the stretch's last sample: the rest of the edge record
-  __device__ __forceinline__ void end() const {
-    static_assert(kEdge, "only the accumulate kernel's signal has an edge record");
-#pragma unroll
-    for (int t = 0; t < X3L_FIR_HIST; ++t) edge->tail[t] = (int16_t)d[t];
-    edge->n = cnt;
-  }
-};
-using X3RLevFir = X3RLevFirT<true>;
-using X3LevFirCarry = X3RLevFirT<false>;
-
-// hist[H] = v without a dynamic register index
-__device__ __forceinline__ void x3rl_fir_set(int32_t (&hist)[X3L_FIR_HIST], uint32_t H, int32_t v) {
-#pragma unroll
-  for (int q = 0; q < X3L_FIR_HIST; ++q) hist[q] = (uint32_t)q == H ? v : hist[q];
-}
+// The signal, its multiply and x3l_fir_set are x3_levels_kernel.h's.  The loops that collect samples from edge records and
+// x3rl_fir_front below are written out in these kernels as they were before the signal protocol: a shared gather and a
+// shared front helper were measured in their place, and x3_range_levels_fir_fixup_kernel came out 8 % and the seam kernel
+// 5 % slower with no cause visible in the source, so these two kernels are reverted to that form (profiles/levels_protocol/).
 
 // y at the consecutive samples s_first + c, c < m <= 7, of a frame: hd[c] the samples, hist[h] the sample h + 1 in front of
 // s_first (h < H).  A position counts when its history is complete (c + H >= T - 1), s_from <= s < s_to and s lies in the
@@ -607,49 +508,9 @@ __device__ __forceinline__ void x3rl_fir_front(const X3FirTaps& k, const int32_t
           a.reset();
           cur = bin;
         }
-        a.add_value(x3rl_fir_value(k, hd[c], d));
+        a.add_value(x3l_fir_value(k, hd[c], d));
       }
     }
-  }
-}
-
-// ---- lead: x3_range_levels_lead_kernel for T taps.  A range with len > 0 gets the ld frames in front of its first covering
-// frame fa, ld the smallest count with start - so[fa - ld] >= T - 1, not past the first frame of its stream or entry: those
-// frames hold the samples under the taps of the range's first positions.  At most T - 1 <= 7 steps whatever so[] says (a
-// checked frame has a sample; one that fails its check ends the history anyway).  lead[w] = ld; the frames are ordinary pairs
-// with an empty cut.  Bounds: fa - ld >= first >= 0, frames of the table the plan searched; ncov + ld <= F.
-__global__ void __launch_bounds__(256)
-x3_range_levels_fir_lead_kernel(const uint64_t* __restrict__ so, const x3_corpus_entry* __restrict__ ent, uint64_t n_ent,
-                                const uint32_t* __restrict__ entries, const uint64_t* __restrict__ starts,
-                                const uint32_t* __restrict__ lens, uint64_t n, uint32_t need, X3WinPlan* __restrict__ plan,
-                                uint32_t* __restrict__ lead) {
-  for (uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; w < n; w += (uint64_t)gridDim.x * blockDim.x) {
-    X3WinPlan pl = plan[w];
-    uint32_t ld = 0;
-    if (pl.status == X3D_OK && pl.ncov && lens[w] && need) {
-      uint64_t first = 0;
-      bool known = true;
-      if (ent) {
-        const uint32_t e = entries[w];
-        known = e < n_ent;   // (the plan has refused the others)
-        if (known) first = ent[e].first_frame;
-      }
-      const uint64_t start = starts[w];
-      if (known && pl.fa >= first) {
-        const uint32_t most = (uint32_t)min((uint64_t)min(need, (uint32_t)X3L_FIR_HIST), pl.fa - first);
-        while (ld < most) {
-          const uint64_t pos = so[pl.fa - ld];
-          if (pos <= start && start - pos >= (uint64_t)need) break;
-          ++ld;
-        }
-        if (ld) {
-          pl.fa -= ld;
-          pl.ncov += ld;
-          plan[w] = pl;
-        }
-      }
-    }
-    lead[w] = ld;
   }
 }
 
@@ -700,9 +561,9 @@ x3_range_levels_fir_fixup_kernel(const uint8_t* __restrict__ x3, const uint64_t*
             auto flush = [&](uint64_t bin, const X3LevAcc& a) {
               if (bin < (uint64_t)R) x3l_merge(mine + bin, a);
             };
-            (void)x3l_bin_samples<X3LevFirCarry>(
+            (void)x3l_bin_samples(
                 r0, bl, [&](auto put_at) { return x3w_replay_frame(payload, p, blk, put_at); },
-                [&](uint32_t s) { return s - lo < span; }, flush, &hs);
+                [&](uint32_t s) { return s - lo < span; }, flush, hs);
           }
           ++replayed;
         } else if (fs == X3D_OK) {   // fast: every stretch proven, its edge records stored by this pair's own lanes
@@ -716,7 +577,7 @@ x3_range_levels_fir_fixup_kernel(const uint8_t* __restrict__ x3, const uint64_t*
 #pragma unroll
               for (int t = 0; t < X3L_FIR_HIST; ++t) {
                 if ((uint32_t)t < c && m < need) {
-                  x3rl_fir_set(hd, m, (int32_t)e.head[t]);
+                  x3l_fir_set(hd, m, (int32_t)e.head[t]);
                   ++m;
                 }
               }
@@ -736,7 +597,7 @@ x3_range_levels_fir_fixup_kernel(const uint8_t* __restrict__ x3, const uint64_t*
 #pragma unroll
             for (int t = 0; t < X3L_FIR_HIST; ++t) {
               if ((uint32_t)t < c && tc < (uint32_t)X3L_FIR_HIST) {
-                x3rl_fir_set(tl, tc, (int32_t)e.tail[t]);
+                x3l_fir_set(tl, tc, (int32_t)e.tail[t]);
                 ++tc;
               }
             }
@@ -800,7 +661,7 @@ x3_range_levels_fir_seam_kernel(uint32_t block_len, const uint2* __restrict__ id
 #pragma unroll
             for (int t = 0; t < X3L_FIR_HIST; ++t) {
               if ((uint32_t)t < c && H < need) {
-                x3rl_fir_set(hist, H, (int32_t)h.tail[t]);
+                x3l_fir_set(hist, H, (int32_t)h.tail[t]);
                 ++H;
               }
             }
