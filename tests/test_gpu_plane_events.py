@@ -231,9 +231,9 @@ def test_empty_records_and_off_planes(ctx, x3, T):
     assert check(ctx, x3, lv, off._replace(min_planes=1), 4, total=BL * n) == [(BL * 3, BL, 4), (BL * T, BL, 5)]
 
 
-def single_events(ctx, x3, lv, rule, cap, total=None, corpus=None, thr=None):
+def single_events(ctx, x3, lv, rule, cap, total=None, corpus=None, thr=None, levels=True):
     """x3_events_dev / x3_corpus_events_dev / the adaptive calls on one plane -> the raw bytes of (entries, starts, lens,
-    event levels, count)"""
+    event levels, count); levels=False: d_event_levels is NULL and its array must stay as it was"""
     n = lv.size
     d_lv, d_tot, d_thr = ctx.alloc(32 * n), ctx.alloc(8), ctx.alloc(16 * (len(thr) if thr else 1))
     g = Guarded(ctx, [4 * cap, 8 * cap, 4 * cap, 32 * cap, 8])
@@ -243,6 +243,8 @@ def single_events(ctx, x3, lv, rule, cap, total=None, corpus=None, thr=None):
         if thr:
             ctx.upload(d_thr, thr_array(x3, [thr]))
         d_ent, d_st, d_ln, d_el, d_cnt = g.ptr
+        if not levels:
+            d_el = None
         r = x3.EventRule.make(0 if thr else rule.mean_sq_min[0], 0 if thr else rule.peak_min[0], rule.join_bins, rule.min_bins,
                               rule.pad_bins, rule.max_bins)
         if corpus is None and not thr:
@@ -254,7 +256,9 @@ def single_events(ctx, x3, lv, rule, cap, total=None, corpus=None, thr=None):
         else:
             rc = corpus.adaptive_events_into(d_lv, n, BL, r, d_thr, d_ent, d_st, d_ln, d_el, cap, d_cnt)
         assert rc == 0 and ctx.events_result()[0] == 0
-        return g.read()
+        out = g.read()
+        assert levels or (out[3] == CANARY).all()
+        return out
     finally:
         g.close()
         for q in (d_lv, d_tot, d_thr):
@@ -291,6 +295,10 @@ def _close_corpora():
 
 
 def test_one_plane_is_the_events_call_byte_for_byte(ctx, x3, T):
+    # An events call IS a plane events call of one plane in the library (one descriptor, one launch set): both sides of this
+    # comparison run the same flag instance, and differ only in the emit kernel the mask asks for.  What it still pins is the
+    # host-side mapping of the two rule structs onto that descriptor.  The independent check of the kernels is
+    # events_ref.py / plane_events_ref.py, which every check() here uses.
     rng = np.random.default_rng(5)
     n, cap = 2 * T + 1, 9
     lv = planes_of([rng.random(n) < 0.2], rng, empty_at=[7, T])
@@ -379,6 +387,113 @@ def test_count_above_cap_and_null_outputs(ctx, x3, T):
     for masks, levels in ((False, True), (True, False), (False, False)):
         check(ctx, x3, lv, rule, full + 2, total=BL * n, masks=masks, levels=levels)
         check(ctx, x3, lv, rule, 2, total=BL * n, masks=masks, levels=levels)
+
+
+# ------------------------------------------------------------------------------------------------ the shared flag and emit steps
+def check_single(ctx, x3, lv, rule, cap, total=None, corpus=None, n_samples=None, thr=None, levels=True, what=None):
+    """the four events entry points on one plane against plane_events_ref with K = 1; thr: None or a record per entry"""
+    ent, st, ln, el, cnt = single_events(ctx, x3, lv, rule, cap, total=total, corpus=corpus, thr=thr, levels=levels)
+    if corpus is None:
+        ev, elv = P.stream_plane_events(lv[None], total, BL, rule, None if thr is None else [thr[0]])
+    else:
+        ev, elv = P.corpus_plane_events(lv[None], n_samples, BL, rule, None if thr is None else [thr])
+    w_ent, w_st, w_ln, _, w_el = P.slots(ev, elv, cap, corpus is not None)
+    assert int(cnt.view(np.uint64)[0]) == len(ev), (what, len(ev))
+    if corpus is None:
+        assert (ent == CANARY).all(), what
+    else:
+        assert ent.tobytes() == w_ent.tobytes(), what
+    assert st.tobytes() == w_st.tobytes() and ln.tobytes() == w_ln.tobytes(), what
+    assert not levels or el.tobytes() == w_el[0].tobytes(), what
+    return ev
+
+
+@pytest.mark.parametrize("max_bins", [65, 130])
+def test_one_plane_through_all_six_entry_points(ctx, x3, T, max_bins):
+    """K = 1 where the piece walk, the wave join and the fillers are shared: pieces longer than one wave turn, every
+    combination of NULL optional outputs, stream and corpus, the rule's values and d_thr's"""
+    rows = [230, 2, 25]
+    corpus, ns = layout_corpus(ctx, x3, rows)
+    n = sum(rows)
+    hot = np.zeros(n, bool)
+    hot[10:215] = True                                               # 205 hot rows: pieces of 65 or 130 rows and a rest
+    hot[[231, 240, 241, 256]] = True
+    lv = planes_of([hot], np.random.default_rng(max_bins))
+    rule = P.PlaneRule([0], [1000], 1, 1, 0, 0, max_bins)
+    thr = [(0, 1000, 1), (2_000_000, 0, 2), (0, 1200, 3)]
+    cap = 12
+    for form in ("stream", "corpus", "stream thr", "corpus thr"):
+        c = corpus if "corpus" in form else None
+        th = None if "thr" not in form else (thr if c else thr[:1])
+        kw = dict(total=None if c else BL * n - 1, corpus=c, n_samples=ns if c else None)
+        for levels in (True, False):
+            ev = check_single(ctx, x3, lv[0], rule, cap, thr=th, levels=levels, what=(form, levels), **kw)
+            assert len(ev) >= 4 and max(e[-2] for e in ev) == max_bins * BL
+            for masks in (True, False):
+                check(ctx, x3, lv, rule, cap, thr=None if th is None else [th], masks=masks, levels=levels,
+                      what=(form, masks, levels), **kw)
+        check(ctx, x3, lv, rule, 2, thr=None if th is None else [th], what=(form, "cap 2"), **kw)   # the fillers' own start
+        check_single(ctx, x3, lv[0], rule, 2, thr=th, what=(form, "cap 2"), **kw)
+
+
+LIMIT_MS, LIMIT_PK = 1 << 30, 32768
+# (mean_sq_min, peak_min) of a plane and the records that stand at its edge: hot rows meet the value exactly, the others
+# miss it by one -- or would meet the criterion above its limit, had nobody tested the limit
+EDGE_KINDS = {
+    "ms at its limit": (LIMIT_MS, 0),
+    "pk at its limit": (0, LIMIT_PK),
+    "ms above its limit": (LIMIT_MS + 1, 1000),
+    "pk above its limit": (500_000, LIMIT_PK + 1),
+    "plain": (0, 1000),
+}
+
+
+def edge_records(hot, kind):
+    lv = records(hot)
+    if kind == "ms at its limit":
+        lv["max"], lv["min"] = 10, -3
+        lv["sum_sq"] = np.where(hot, LIMIT_MS * BL, LIMIT_MS * BL - 1).astype(np.uint64)
+    elif kind == "pk at its limit":
+        lv["max"] = 32767
+        lv["min"] = np.where(hot, -32768, -32767)
+    elif kind == "ms above its limit":                               # a cold row's sum_sq would pass (2^30 + 1) * n
+        lv["sum_sq"] = np.where(hot, 200, (1 << 33) + np.arange(hot.size)).astype(np.uint64)
+    elif kind == "pk above its limit":                               # a cold row's peak is the largest there is
+        lv["max"] = 10
+        lv["min"] = np.where(hot, -3, -32768)
+        lv["sum_sq"] = np.where(hot, 500_000 * BL, 500_000 * BL - 1).astype(np.uint64)
+    return lv
+
+
+@pytest.mark.parametrize("k", [1, 8])
+@pytest.mark.parametrize("thr", [False, True], ids=["rule", "thr"])
+def test_each_flag_instance_at_its_edges(ctx, x3, T, thr, k):
+    """rule / d_thr x K in {1, 8} with min_planes = K, so that every plane's load and test decides the verdict: n_rows round
+    the tile, a corpus whose entry edges fall inside a wave, values at their limits and (d_thr only: the host refuses them
+    in a rule) above them"""
+    kinds = list(EDGE_KINDS) if thr else ["ms at its limit", "pk at its limit", "plain"]
+    corpus, ns = layout_corpus(ctx, x3, [1, T - 1, 2])
+    for n, c in ((T - 1, None), (T, None), (T + 1, None), (T + 2, corpus)):
+        for first in range(len(kinds) if k == 1 else 1):             # K = 1: every kind in its own call
+            of = [kinds[(first + t) % len(kinds)] for t in range(k)]
+            rng = np.random.default_rng(1000 * n + 10 * k + first)
+            hots = [rng.random(n) < 0.85 for _ in range(k)]
+            for t in range(k):                                       # plane t alone keeps row t + 2 cold; the edges are hot
+                for u in range(k):
+                    hots[u][t + 2] = u != t
+                hots[t][[0, 1, n - 2, n - 1]] = True
+            lv = np.stack([edge_records(hots[t], of[t]) for t in range(k)])
+            vals = [EDGE_KINDS[kd] for kd in of]
+            rule = P.PlaneRule([0] * k if thr else [v[0] for v in vals], [0] * k if thr else [v[1] for v in vals], k, 0, 0, 0, 0)
+            th = None
+            if thr:                                                  # the same values in every entry, counted garbage
+                th = [[(v[0], v[1], 7 + e) for e in range(3 if c else 1)] for v in vals]
+            ev = check(ctx, x3, lv, rule, n, total=None if c else BL * n, corpus=c, n_samples=ns if c else None, thr=th,
+                       pad=3, what=(n, of))
+            all_hot = np.logical_and.reduce(hots)
+            assert len(ev) >= 2 and not all_hot[2:2 + k].any() and all_hot[[0, 1, n - 2, n - 1]].all()
+            if k == 1 and c is None:
+                check_single(ctx, x3, lv[0], rule, n, total=BL * n, thr=None if th is None else th[0], what=(n, of))
 
 
 # ------------------------------------------------------------------------------------------------ corpus form

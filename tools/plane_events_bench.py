@@ -16,8 +16,8 @@ The bank is K tones spread over the band; the rule is mean_sq_min per plane at a
 squares (taken from a first levels call outside the timing, so that the hot rows stay below a quarter of --cap),
 min_planes = --min-planes, join 5 bins, 2 bins of padding, pieces of 25 bins; the range levels are at bin_len / 8.
 Kernel times: run it under `rocprofv3 --kernel-trace --stats -- python3 tools/plane_events_bench.py ...`; with --single the
-device route also runs x3_events_dev on plane 0 once per rep, so that x3_events_flag_kernel / x3_events_emit_kernel stand
-in the same trace as the yardstick.  Prints one JSON line.
+device route also runs x3_events_dev on plane 0 once per rep, so that the one-plane instance x3_events_flag_kernel<false, 1>
+and x3_events_emit_kernel stand in the same trace as the yardstick.  Prints one JSON line.
     python3 tools/plane_events_bench.py [--planes 4] [--min-planes 1] [--samples N] [--reps 9] [--warmup 2] [--cap 4096]
                                         [--cases config3,corpus] [--single] [--only-device] [--out file.json]"""
 import argparse, ctypes as C, json, os, sys, time

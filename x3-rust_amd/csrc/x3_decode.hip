@@ -11,7 +11,6 @@
 #include "x3_seg_index_kernel.h"
 #include "x3_levels_kernel.h"
 #include "x3_events_kernel.h"
-#include "x3_plane_events_kernel.h"
 #include "x3_quantiles_kernel.h"
 #include "x3_range_levels_kernel.h"
 #include "x3_spectra_kernel.h"
@@ -2191,6 +2190,12 @@ static int corpus_rows(x3_ctx* c, const x3_corpus* k, const x3_level* d_levels, 
   return X3_OK;
 }
 
+// ... of either: corpus_entry is the entry point's name of a corpus form (k), NULL for a stream form (d_total)
+static int rows_of(x3_ctx* c, const x3_corpus* k, const char* corpus_entry, const x3_level* d_levels, uint64_t n_rows,
+                   uint64_t bin_len, const uint64_t* d_total, X3EvRows* q) {
+  return corpus_entry ? corpus_rows(c, k, d_levels, n_rows, bin_len, corpus_entry, q) : stream_rows(d_levels, n_rows, bin_len, d_total, q);
+}
+
 // the row prefix of a corpus call (k != NULL) by the device into its workspace, and into the call's rows
 static void corpus_row_prefix(x3_ctx* c, const x3_corpus* k, uint64_t bin_len, unsigned long long* row_first, X3EvRows* q = nullptr) {
   if (!k) return;
@@ -2273,32 +2278,98 @@ size_t events_carve(char* base, uint64_t n_rows, uint64_t n_ent, EvWs* w) {
   return k.at;
 }
 
-// the argument checks x3_events_dev and x3_corpus_events_dev share; *eff: the rule the kernels take (max_bins never 0)
-static bool events_args_ok(const x3_ctx* c, const x3_level* d_levels, uint64_t n_rows, uint64_t bin_len, const x3_event_rule* rule,
-                           const uint64_t* d_starts, const uint32_t* d_lens, const x3_level* d_event_levels, uint64_t cap,
-                           const uint64_t* d_count, x3_event_rule* eff, bool adaptive = false) {
-  if (!c || !d_levels || !rule || !d_starts || !d_lens || !d_count || c->capturing) return false;
-  if (bin_len == 0 || bin_len > 0xFFFFFFFFull || n_rows == 0 || n_rows > 0x7FFFFFFFull || cap == 0 || cap > 0x7FFFFFFFull) return false;
-  if (adaptive ? (rule->mean_sq_min != 0 || rule->peak_min != 0)   // (the two values come from d_thr, per entry)
-               : ((rule->mean_sq_min == 0 && rule->peak_min == 0) || rule->mean_sq_min > (1ull << 30) || rule->peak_min > 32768u))
-    return false;
-  if (2ull * rule->pad_bins > rule->join_bins || (uint64_t)rule->max_bins * bin_len > 0xFFFFFFFFull || rule->reserved) return false;
-  const uintptr_t p8 = reinterpret_cast<uintptr_t>(d_levels) | reinterpret_cast<uintptr_t>(d_starts) |
-                       reinterpret_cast<uintptr_t>(d_event_levels) | reinterpret_cast<uintptr_t>(d_count);
-  if ((p8 & 7u) || (reinterpret_cast<uintptr_t>(d_lens) & 3u)) return false;
-  *eff = *rule;
-  if (!eff->max_bins) eff->max_bins = (uint32_t)(0xFFFFFFFFull / bin_len);
-  return true;
-}
+// The verdict of an events call with its four run values, checked, as the kernels take it (X3EvPlanes; LevSignal's
+// counterpart): built at the entry point from the caller's rule, each constructor with the checks of its rule alone.  The
+// run values' checks need bin_len, the planes' n_rows; ok stays false where anything is refused.
+struct EvVerdict {
+  X3EvPlanes pl{};   // (the values behind n_planes stay 0: never read)
+  bool ok = false;
+
+  // an x3_event_rule is one plane, needed, at the stride n_rows: plain (its own two values, not both 0, within their
+  // limits) or adaptive (no values of its own; d_thr per entry)
+  EvVerdict(const x3_event_rule* rule, bool adaptive, const x3_event_threshold* d_thr, uint64_t n_rows, uint64_t bin_len) {
+    if (!rule || rule->reserved || !runs(rule->join_bins, rule->min_bins, rule->pad_bins, rule->max_bins, bin_len)) return;
+    if (adaptive ? (rule->mean_sq_min != 0 || rule->peak_min != 0 || !thr(d_thr))
+                 : ((rule->mean_sq_min == 0 && rule->peak_min == 0) || !values(rule->mean_sq_min, rule->peak_min)))
+      return;
+    pl.rule.n_planes = pl.rule.min_planes = 1;
+    pl.rule.mean_sq_min[0] = rule->mean_sq_min;
+    pl.rule.peak_min[0] = rule->peak_min;
+    pl.stride = n_rows;
+    ok = true;
+  }
+
+  // an x3_plane_event_rule: 1 .. 8 planes at plane_stride >= n_rows (n_rows' own limit: t * plane_stride + r stays below
+  // 2^34 records, 2^39 bytes); min_planes of them `on` with the rule's values, or none with d_thr's
+  EvVerdict(const x3_plane_event_rule* rule, const x3_event_threshold* d_thr, uint64_t plane_stride, uint64_t n_rows, uint64_t bin_len) {
+    if (!rule || rule->reserved[0] || rule->reserved[1] ||
+        !runs(rule->join_bins, rule->min_bins, rule->pad_bins, rule->max_bins, bin_len))
+      return;
+    if (rule->n_planes == 0 || rule->n_planes > X3_EVENT_PLANES_MAX || rule->min_planes == 0 || rule->min_planes > rule->n_planes ||
+        plane_stride < n_rows || plane_stride > 0x7FFFFFFFull)
+      return;
+    uint32_t on = 0;
+    for (uint32_t t = 0; t < rule->n_planes; ++t) {
+      if (!values(rule->mean_sq_min[t], rule->peak_min[t])) return;
+      on += (rule->mean_sq_min[t] || rule->peak_min[t]) ? 1u : 0u;
+      pl.rule.mean_sq_min[t] = rule->mean_sq_min[t];
+      pl.rule.peak_min[t] = rule->peak_min[t];
+    }
+    if (d_thr ? (on != 0 || !thr(d_thr)) : on < rule->min_planes) return;
+    pl.rule.n_planes = rule->n_planes;
+    pl.rule.min_planes = rule->min_planes;
+    pl.stride = plane_stride;
+    ok = true;
+  }
+
+  // what the five kernels between flag and emit take of it
+  x3_event_rule run_rule() const { return x3_event_rule{0, 0, pl.rule.join_bins, pl.rule.min_bins, pl.rule.pad_bins, pl.rule.max_bins, 0}; }
+
+ private:
+  bool runs(uint32_t join_bins, uint32_t min_bins, uint32_t pad_bins, uint32_t max_bins, uint64_t bin_len) {
+    if (bin_len == 0 || bin_len > 0xFFFFFFFFull || 2ull * pad_bins > join_bins || (uint64_t)max_bins * bin_len > 0xFFFFFFFFull) return false;
+    pl.rule.join_bins = join_bins;
+    pl.rule.min_bins = min_bins;
+    pl.rule.pad_bins = pad_bins;
+    pl.rule.max_bins = max_bins ? max_bins : (uint32_t)(0xFFFFFFFFull / bin_len);   // (never 0)
+    return true;
+  }
+  static bool values(uint64_t mean_sq_min, uint32_t peak_min) { return mean_sq_min <= X3E_MEAN_SQ_MAX && peak_min <= X3E_PEAK_MAX; }
+  bool thr(const x3_event_threshold* d_thr) {
+    pl.thr = d_thr;
+    return d_thr && !(reinterpret_cast<uintptr_t>(d_thr) & 7u);
+  }
+};
+
+// The outputs of an events call: cap slots each (d_event_levels: per plane); d_entries of a corpus form alone; the mask
+// and the event levels may be NULL
+struct EvOut {
+  uint32_t* d_entries;
+  uint64_t* d_starts;
+  uint32_t* d_lens;
+  uint32_t* d_event_planes;
+  x3_level* d_event_levels;
+  uint64_t cap;
+  uint64_t* d_count;
+  bool ok(bool corpus) const {
+    if (!d_starts || !d_lens || !d_count || (corpus && !d_entries) || cap == 0 || cap > 0x7FFFFFFFull) return false;
+    const uintptr_t p8 = reinterpret_cast<uintptr_t>(d_starts) | reinterpret_cast<uintptr_t>(d_event_levels) |
+                         reinterpret_cast<uintptr_t>(d_count);
+    const uintptr_t p4 = reinterpret_cast<uintptr_t>(d_entries) | reinterpret_cast<uintptr_t>(d_lens) |
+                         reinterpret_cast<uintptr_t>(d_event_planes);
+    return !(p8 & 7u) && !(p4 & 3u);
+  }
+};
 
 // The launch set of an events call.  q: the rows (its row_first is set here); k: the corpus of a corpus call, whose row
-// prefix the levels' kernel computes into the workspace first.  d_thr: the thresholds of an adaptive call, which differs in
-// its flag kernel alone (the other six take join_bins, min_bins, pad_bins and max_bins of the rule, never its two values).
-//   pl: the planes of a plane events call (x3_plane_events_kernel.h), which differs in its flag and emit kernels alone: the
-// five in between work on the hot bytes and the tile words, whatever made them.
-static int events_launch(x3_ctx* c, X3EvRows q, const x3_corpus* k, const x3_event_rule& rule, const x3_event_threshold* d_thr,
-                         uint32_t* d_entries, uint64_t* d_starts, uint32_t* d_lens, x3_level* d_event_levels, uint64_t cap,
-                         uint64_t* d_count, const X3EvPlanes* pl = nullptr, uint32_t* d_event_planes = nullptr) {
+// prefix the levels' kernel computes into the workspace first.  The verdict picks the flag instance -- the values' source
+// and the bound of the plane loop -- and the emit kernel; the five in between work on the hot bytes and the tile words,
+// whatever made them, and take the four run values alone.
+static int events_launch(x3_ctx* c, X3EvRows q, const x3_corpus* k, const EvVerdict& v, const EvOut& o) {
+  using Flag = void (*)(X3EvRows, X3EvPlanes, uint64_t, uint8_t*, uint32_t*, uint32_t*);
+  static const Flag flag[2][2] = {   // [the values are d_thr's][more planes than one]
+      {x3_events_flag_kernel<false, 1>, x3_events_flag_kernel<false, X3_EVENT_PLANES_MAX>},
+      {x3_events_flag_kernel<true, 1>, x3_events_flag_kernel<true, X3_EVENT_PLANES_MAX>}};
   HIPCHK(c, hipSetDevice(c->device));
   EvWs w;
   int rc;
@@ -2306,18 +2377,12 @@ static int events_launch(x3_ctx* c, X3EvRows q, const x3_corpus* k, const x3_eve
   events_carve((char*)c->ev_ws.p, q.n_rows, q.n_ent, &w);
   const uint64_t n_tiles = (q.n_rows + X3E_TILE - 1) / X3E_TILE;
   const dim3 g_tiles(grid_for(n_tiles, 1));
+  const X3EvPlanes& pl = v.pl;
+  const x3_event_rule rule = v.run_rule();
+  const bool planes = pl.rule.n_planes > 1;
   corpus_row_prefix(c, k, q.bin_len, w.row_first, &q);
-  if (pl && pl->thr)
-    hipLaunchKernelGGL(x3_plane_events_flag_kernel<true>, g_tiles, dim3(256), 0, c->stream, q, *pl, n_tiles, w.hot, w.tile_prev,
-                       w.tile_next);
-  else if (pl)
-    hipLaunchKernelGGL(x3_plane_events_flag_kernel<false>, g_tiles, dim3(256), 0, c->stream, q, *pl, n_tiles, w.hot, w.tile_prev,
-                       w.tile_next);
-  else if (d_thr)
-    hipLaunchKernelGGL(x3_events_adaptive_flag_kernel, g_tiles, dim3(256), 0, c->stream, q, d_thr, n_tiles, w.hot, w.tile_prev,
-                       w.tile_next);
-  else
-    hipLaunchKernelGGL(x3_events_flag_kernel, g_tiles, dim3(256), 0, c->stream, q, rule, n_tiles, w.hot, w.tile_prev, w.tile_next);
+  hipLaunchKernelGGL(flag[pl.thr != nullptr][planes], g_tiles, dim3(256), 0, c->stream, q, pl, n_tiles, w.hot, w.tile_prev,
+                     w.tile_next);
   hipLaunchKernelGGL(x3_events_near_kernel, dim3(1), dim3(1024), 0, c->stream, n_tiles, w.tile_prev, w.tile_next);
   hipLaunchKernelGGL(x3_events_mark_kernel, g_tiles, dim3(256), 0, c->stream, q, rule.join_bins, n_tiles, w.hot,
                      (const uint32_t*)w.tile_prev, (const uint32_t*)w.tile_next, w.tile_ns, w.tile_ne);
@@ -2325,126 +2390,78 @@ static int events_launch(x3_ctx* c, X3EvRows q, const x3_corpus* k, const x3_eve
   hipLaunchKernelGGL(x3_events_table_kernel, g_tiles, dim3(256), 0, c->stream, q.n_rows, n_tiles, (const uint8_t*)w.hot,
                      (const uint32_t*)w.tile_ns, (const uint32_t*)w.tile_ne, w.run_first, w.run_last);
   hipLaunchKernelGGL(x3_events_runs_kernel, dim3(1), dim3(1024), 0, c->stream, q, rule, w.run_first, w.run_last, w.piece_off, w.sum,
-                     d_count);
-  // (the count is on the device: a wave per slot of the caller's arrays at most, grid-stride)
-  if (pl)
-    hipLaunchKernelGGL(x3_plane_events_emit_kernel, dim3(grid_for(cap, 4)), dim3(256), 0, c->stream, q, *pl,
+                     o.d_count);
+  // (the count is on the device: a wave per slot of the caller's arrays at most, grid-stride.  One plane and no mask: the
+  // emit kernel that tests no record)
+  if (planes || o.d_event_planes)
+    hipLaunchKernelGGL(x3_plane_events_emit_kernel, dim3(grid_for(o.cap, 4)), dim3(256), 0, c->stream, q, pl,
                        (const uint32_t*)w.run_first, (const uint32_t*)w.run_last, (const unsigned long long*)w.piece_off,
-                       (const X3EvSummary*)w.sum, cap, d_entries, d_starts, d_lens, d_event_planes, d_event_levels);
+                       (const X3EvSummary*)w.sum, o.cap, o.d_entries, o.d_starts, o.d_lens, o.d_event_planes, o.d_event_levels);
   else
-    hipLaunchKernelGGL(x3_events_emit_kernel, dim3(grid_for(cap, 4)), dim3(256), 0, c->stream, q, rule, (const uint32_t*)w.run_first,
-                       (const uint32_t*)w.run_last, (const unsigned long long*)w.piece_off, (const X3EvSummary*)w.sum, cap, d_entries,
-                       d_starts, d_lens, d_event_levels);
+    hipLaunchKernelGGL(x3_events_emit_kernel, dim3(grid_for(o.cap, 4)), dim3(256), 0, c->stream, q, rule, (const uint32_t*)w.run_first,
+                       (const uint32_t*)w.run_last, (const unsigned long long*)w.piece_off, (const X3EvSummary*)w.sum, o.cap,
+                       o.d_entries, o.d_starts, o.d_lens, o.d_event_levels);
   HIPCHK(c, hipGetLastError());
   c->events.pending = true;
-  c->events.count = cap;
+  c->events.count = o.cap;
   c->events.sum_off = (size_t)((char*)w.sum - (char*)c->ev_ws.p);
   return X3_OK;
 }
 
-// One checked events call.  corpus_entry: the entry point's name of a corpus form (k, d_entries), NULL for a stream form
-// (d_total); d_thr: the thresholds of an adaptive form, whose rule carries no values of its own.
+// One checked events call: the verdict and the outputs as the entry point has built them.  corpus_entry: the entry
+// point's name of a corpus form (k, o.d_entries), NULL for a stream form (d_total).
 static int events_call(x3_ctx* c, const x3_corpus* k, const char* corpus_entry, const x3_level* d_levels, uint64_t n_rows,
-                       uint64_t bin_len, const uint64_t* d_total, const x3_event_rule* rule, bool adaptive,
-                       const x3_event_threshold* d_thr, uint32_t* d_entries, uint64_t* d_starts, uint32_t* d_lens,
-                       x3_level* d_event_levels, uint64_t cap, uint64_t* d_count) {
-  x3_event_rule eff;
-  if ((corpus_entry && !k) ||
-      !events_args_ok(c, d_levels, n_rows, bin_len, rule, d_starts, d_lens, d_event_levels, cap, d_count, &eff, adaptive))
-    return X3_ERR_BAD_ARG;
-  if (corpus_entry && (!d_entries || (reinterpret_cast<uintptr_t>(d_entries) & 3u))) return X3_ERR_BAD_ARG;
-  if (adaptive && (!d_thr || (reinterpret_cast<uintptr_t>(d_thr) & 7u))) return X3_ERR_BAD_ARG;
+                       uint64_t bin_len, const uint64_t* d_total, const EvVerdict& v, const EvOut& o) {
+  if (!c || c->capturing || (corpus_entry && !k) || !d_levels || (reinterpret_cast<uintptr_t>(d_levels) & 7u)) return X3_ERR_BAD_ARG;
+  if (n_rows == 0 || n_rows > 0x7FFFFFFFull || !v.ok || !o.ok(corpus_entry != nullptr)) return X3_ERR_BAD_ARG;
   X3EvRows q;
-  const int rc = corpus_entry ? corpus_rows(c, k, d_levels, n_rows, bin_len, corpus_entry, &q)
-                              : stream_rows(d_levels, n_rows, bin_len, d_total, &q);
+  const int rc = rows_of(c, k, corpus_entry, d_levels, n_rows, bin_len, d_total, &q);
   if (rc) return rc;
-  return events_launch(c, q, k, eff, d_thr, d_entries, d_starts, d_lens, d_event_levels, cap, d_count);
+  return events_launch(c, q, k, v, o);
 }
 
 extern "C" int x3_events_dev(x3_ctx* c, const x3_level* d_levels, uint64_t n_bins, uint64_t bin_len, const uint64_t* d_total,
                              const x3_event_rule* rule, uint64_t* d_starts, uint32_t* d_lens, x3_level* d_event_levels,
                              uint64_t cap, uint64_t* d_count) {
-  return events_call(c, nullptr, nullptr, d_levels, n_bins, bin_len, d_total, rule, false, nullptr, nullptr, d_starts, d_lens,
-                     d_event_levels, cap, d_count);
+  return events_call(c, nullptr, nullptr, d_levels, n_bins, bin_len, d_total, EvVerdict(rule, false, nullptr, n_bins, bin_len),
+                     EvOut{nullptr, d_starts, d_lens, nullptr, d_event_levels, cap, d_count});
 }
 
 extern "C" int x3_corpus_events_dev(x3_ctx* c, const x3_corpus* k, const x3_level* d_levels, uint64_t n_rows, uint64_t bin_len,
                                     const x3_event_rule* rule, uint32_t* d_entries, uint64_t* d_starts, uint32_t* d_lens,
                                     x3_level* d_event_levels, uint64_t cap, uint64_t* d_count) {
-  return events_call(c, k, "x3_corpus_events_dev", d_levels, n_rows, bin_len, nullptr, rule, false, nullptr, d_entries, d_starts,
-                     d_lens, d_event_levels, cap, d_count);
+  return events_call(c, k, "x3_corpus_events_dev", d_levels, n_rows, bin_len, nullptr, EvVerdict(rule, false, nullptr, n_rows, bin_len),
+                     EvOut{d_entries, d_starts, d_lens, nullptr, d_event_levels, cap, d_count});
 }
 
 extern "C" int x3_events_adaptive_dev(x3_ctx* c, const x3_level* d_levels, uint64_t n_bins, uint64_t bin_len, const uint64_t* d_total,
                                       const x3_event_rule* rule, const x3_event_threshold* d_thr, uint64_t* d_starts,
                                       uint32_t* d_lens, x3_level* d_event_levels, uint64_t cap, uint64_t* d_count) {
-  return events_call(c, nullptr, nullptr, d_levels, n_bins, bin_len, d_total, rule, true, d_thr, nullptr, d_starts, d_lens,
-                     d_event_levels, cap, d_count);
+  return events_call(c, nullptr, nullptr, d_levels, n_bins, bin_len, d_total, EvVerdict(rule, true, d_thr, n_bins, bin_len),
+                     EvOut{nullptr, d_starts, d_lens, nullptr, d_event_levels, cap, d_count});
 }
 
 extern "C" int x3_corpus_events_adaptive_dev(x3_ctx* c, const x3_corpus* k, const x3_level* d_levels, uint64_t n_rows,
                                              uint64_t bin_len, const x3_event_rule* rule, const x3_event_threshold* d_thr,
                                              uint32_t* d_entries, uint64_t* d_starts, uint32_t* d_lens, x3_level* d_event_levels,
                                              uint64_t cap, uint64_t* d_count) {
-  return events_call(c, k, "x3_corpus_events_adaptive_dev", d_levels, n_rows, bin_len, nullptr, rule, true, d_thr, d_entries,
-                     d_starts, d_lens, d_event_levels, cap, d_count);
+  return events_call(c, k, "x3_corpus_events_adaptive_dev", d_levels, n_rows, bin_len, nullptr,
+                     EvVerdict(rule, true, d_thr, n_rows, bin_len), EvOut{d_entries, d_starts, d_lens, nullptr, d_event_levels, cap, d_count});
 }
 
-// plane events: the events of one synthetic row verdict over K planes of records (x3_plane_events_kernel.h; DESIGN.md
-// section 28).  The checks are events_args_ok's on the rule's four run values, then the planes' own.
+// plane events: the same call on K planes of records
 static_assert(sizeof(x3_plane_event_rule) == 128 && offsetof(x3_plane_event_rule, min_planes) == 4 &&
                   offsetof(x3_plane_event_rule, join_bins) == 8 && offsetof(x3_plane_event_rule, max_bins) == 20 &&
                   offsetof(x3_plane_event_rule, reserved) == 24 && offsetof(x3_plane_event_rule, mean_sq_min) == 32 &&
                   offsetof(x3_plane_event_rule, peak_min) == 96,
               "include/x3hip.h states this layout");
 
-static int plane_events_call(x3_ctx* c, const x3_corpus* k, const char* corpus_entry, const x3_level* d_levels,
-                             uint64_t plane_stride, uint64_t n_rows, uint64_t bin_len, const uint64_t* d_total,
-                             const x3_plane_event_rule* rule, const x3_event_threshold* d_thr, uint32_t* d_entries,
-                             uint64_t* d_starts, uint32_t* d_lens, uint32_t* d_event_planes, x3_level* d_event_levels,
-                             uint64_t cap, uint64_t* d_count) {
-  if (!rule || (corpus_entry && !k)) return X3_ERR_BAD_ARG;
-  const x3_event_rule runs{0, 0, rule->join_bins, rule->min_bins, rule->pad_bins, rule->max_bins, 0};
-  x3_event_rule eff;
-  if (!events_args_ok(c, d_levels, n_rows, bin_len, &runs, d_starts, d_lens, d_event_levels, cap, d_count, &eff, true))
-    return X3_ERR_BAD_ARG;
-  if (rule->n_planes == 0 || rule->n_planes > X3_EVENT_PLANES_MAX || rule->min_planes == 0 || rule->min_planes > rule->n_planes ||
-      rule->reserved[0] || rule->reserved[1] || plane_stride < n_rows || plane_stride > 0x7FFFFFFFull)   // (n_rows' own limit:
-    return X3_ERR_BAD_ARG;                                     //  t * plane_stride + r stays below 2^34 records, 2^39 bytes)
-  uint32_t on = 0;
-  for (uint32_t t = 0; t < rule->n_planes; ++t) {
-    if (rule->mean_sq_min[t] > (1ull << 30) || rule->peak_min[t] > 32768u) return X3_ERR_BAD_ARG;
-    on += (rule->mean_sq_min[t] || rule->peak_min[t]) ? 1u : 0u;
-  }
-  if (d_thr ? (on != 0 || (reinterpret_cast<uintptr_t>(d_thr) & 7u)) : on < rule->min_planes) return X3_ERR_BAD_ARG;
-  if (reinterpret_cast<uintptr_t>(d_event_planes) & 3u) return X3_ERR_BAD_ARG;
-  if (corpus_entry && (!d_entries || (reinterpret_cast<uintptr_t>(d_entries) & 3u))) return X3_ERR_BAD_ARG;
-  X3EvRows q;
-  const int rc = corpus_entry ? corpus_rows(c, k, d_levels, n_rows, bin_len, corpus_entry, &q)
-                              : stream_rows(d_levels, n_rows, bin_len, d_total, &q);
-  if (rc) return rc;
-  X3EvPlanes pl{};                                  // (the values behind n_planes stay 0: never copied, never read)
-  pl.rule.n_planes = rule->n_planes;
-  pl.rule.min_planes = rule->min_planes;
-  pl.rule.join_bins = eff.join_bins;
-  pl.rule.min_bins = eff.min_bins;
-  pl.rule.pad_bins = eff.pad_bins;
-  pl.rule.max_bins = eff.max_bins;
-  for (uint32_t t = 0; t < rule->n_planes; ++t) {
-    pl.rule.mean_sq_min[t] = rule->mean_sq_min[t];
-    pl.rule.peak_min[t] = rule->peak_min[t];
-  }
-  pl.stride = plane_stride;
-  pl.thr = d_thr;
-  return events_launch(c, q, k, eff, nullptr, d_entries, d_starts, d_lens, d_event_levels, cap, d_count, &pl, d_event_planes);
-}
-
 extern "C" int x3_plane_events_dev(x3_ctx* c, const x3_level* d_levels, uint64_t plane_stride, uint64_t n_bins, uint64_t bin_len,
                                    const uint64_t* d_total, const x3_plane_event_rule* rule, const x3_event_threshold* d_thr,
                                    uint64_t* d_starts, uint32_t* d_lens, uint32_t* d_event_planes, x3_level* d_event_levels,
                                    uint64_t cap, uint64_t* d_count) {
-  return plane_events_call(c, nullptr, nullptr, d_levels, plane_stride, n_bins, bin_len, d_total, rule, d_thr, nullptr, d_starts,
-                           d_lens, d_event_planes, d_event_levels, cap, d_count);
+  return events_call(c, nullptr, nullptr, d_levels, n_bins, bin_len, d_total, EvVerdict(rule, d_thr, plane_stride, n_bins, bin_len),
+                     EvOut{nullptr, d_starts, d_lens, d_event_planes, d_event_levels, cap, d_count});
 }
 
 extern "C" int x3_corpus_plane_events_dev(x3_ctx* c, const x3_corpus* k, const x3_level* d_levels, uint64_t plane_stride,
@@ -2452,8 +2469,9 @@ extern "C" int x3_corpus_plane_events_dev(x3_ctx* c, const x3_corpus* k, const x
                                           const x3_event_threshold* d_thr, uint32_t* d_entries, uint64_t* d_starts,
                                           uint32_t* d_lens, uint32_t* d_event_planes, x3_level* d_event_levels, uint64_t cap,
                                           uint64_t* d_count) {
-  return plane_events_call(c, k, "x3_corpus_plane_events_dev", d_levels, plane_stride, n_rows, bin_len, nullptr, rule, d_thr,
-                           d_entries, d_starts, d_lens, d_event_planes, d_event_levels, cap, d_count);
+  return events_call(c, k, "x3_corpus_plane_events_dev", d_levels, n_rows, bin_len, nullptr,
+                     EvVerdict(rule, d_thr, plane_stride, n_rows, bin_len),
+                     EvOut{d_entries, d_starts, d_lens, d_event_planes, d_event_levels, cap, d_count});
 }
 
 extern "C" int x3_events_result(x3_ctx* c, uint64_t* count) {
@@ -2556,8 +2574,7 @@ static int quantiles_call(x3_ctx* c, const x3_corpus* k, const char* corpus_entr
                           const x3_threshold_rule* trule, x3_event_threshold* d_thr) {
   if ((corpus_entry && !k) || !quantiles_args_ok(c, d_levels, n_rows, bin_len) || !n_runs) return X3_ERR_BAD_ARG;
   X3EvRows q;
-  const int rc = corpus_entry ? corpus_rows(c, k, d_levels, n_rows, bin_len, corpus_entry, &q)
-                              : stream_rows(d_levels, n_rows, bin_len, d_total, &q);
+  const int rc = rows_of(c, k, corpus_entry, d_levels, n_rows, bin_len, d_total, &q);
   if (rc) return rc;
   return quantiles_launch(c, q, k, runs, n_runs, d_counted, trule, d_thr);
 }

@@ -94,6 +94,19 @@ struct X3LevAcc {
     mx = max(mx, o.mx);
     n += o.n;
   }
+  // ... of the 64 lanes of a wave: every lane calls and holds the sum
+  __device__ __forceinline__ void join_wave() {
+#pragma unroll
+    for (uint32_t d = 32; d >= 1u; d >>= 1) {
+      X3LevAcc o;
+      o.sum_sq = (uint64_t)__shfl_xor((long long)sum_sq, d, X3_WAVE);
+      o.sum = (int64_t)__shfl_xor((long long)sum, d, X3_WAVE);
+      o.mn = __shfl_xor(mn, d, X3_WAVE);
+      o.mx = __shfl_xor(mx, d, X3_WAVE);
+      o.n = (uint32_t)__shfl_xor((int)n, d, X3_WAVE);
+      join(o);
+    }
+  }
 };
 
 // ... into a record that other lanes add to as well

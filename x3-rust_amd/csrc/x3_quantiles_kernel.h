@@ -1,6 +1,6 @@
-// x3_quantiles_kernel.h -- QUANTILES of level records per entry, thresholds from them, and the events' flag step with a
-// threshold per entry (x3_level_quantiles_dev, x3_level_thresholds_dev, x3_events_adaptive_dev and their corpus forms;
-// DESIGN.md section 19).
+// x3_quantiles_kernel.h -- QUANTILES of level records per entry and thresholds from them (x3_level_quantiles_dev,
+// x3_level_thresholds_dev and their corpus forms).  The events calls that take the thresholds
+// (d_thr) are x3_events_kernel.h's: this header includes it for rows and entries, and for the limits of the two values.
 //
 // Rows and entries are the events calls' (x3e_entry_of).  A row COUNTS for its entry when it lies in one and its n != 0;
 // its KEY is max(max, -min) clamped to 0 .. 32 768 (X3_LEVEL_KEY_PEAK) or min(floor(sum_sq / n), 2^30)
@@ -22,8 +22,6 @@
 //                                 the rank becomes the rank inside that bin, the bins are cleared for the next pass.  After
 //                                 the last pass the prefix is the value.
 //  x3_quantiles_map_kernel     -- a lane per entry: x3_event_threshold from the two values by x3_threshold_rule
-//  x3_events_adaptive_flag_kernel -- x3_events_flag_kernel's body (x3e_flag_tiles) with the rule's two values taken from
-//                                 d_thr[entry]
 //
 // Workspace (q_ws), from host-known arguments: 8 * n_rows bytes of (key, entry) + 4 * n_ent * n_q * 256 bytes of
 // histograms + 8 * n_ent * n_q bytes of (prefix, rank) + 3 * 4 * n_ent bytes (the two values and K of a thresholds call) +
@@ -39,8 +37,8 @@
 #define X3Q_DIGIT_BITS 8u
 #define X3Q_BINS 256u                  // 1 << X3Q_DIGIT_BITS; = X3E_TILE, so a lane of a tile owns a bin at the flush
 #define X3Q_MAX_Q 8u
-#define X3Q_PEAK_MAX 32768u
-#define X3Q_MEAN_SQ_MAX (1u << 30)
+#define X3Q_PEAK_MAX X3E_PEAK_MAX       // a key's largest value is its threshold's limit
+#define X3Q_MEAN_SQ_MAX X3E_MEAN_SQ_MAX
 #define X3Q_DEAD 0xFFFFFFFFu           // a slot's rank: the entry has no counting row (ranks are below 2^31)
 
 struct X3QSlot {                       // per (entry, j)
@@ -203,26 +201,4 @@ x3_quantiles_map_kernel(uint64_t n_ent, x3_threshold_rule rule, const uint32_t* 
       t.mean_sq_min = x3q_map(val_mean_sq[e], rule.mean_sq_mul, rule.mean_sq_div, rule.mean_sq_add, X3Q_MEAN_SQ_MAX);
     thr[e] = t;
   }
-}
-
-// ---- the events' flag step with the thresholds of the row's entry.  d_thr is untrusted: a value above its limit makes
-// its criterion never hot (tested in front of the multiply, so mean_sq_min * n stays below 2^62), both 0 leaves the entry
-// without hot rows.
-__device__ __forceinline__ bool x3q_loud(const x3_level& r, uint64_t mean_sq_min, uint32_t peak_min) {
-  if (r.n == 0u) return false;
-  const int64_t peak = max((int64_t)r.max, -(int64_t)r.min);
-  return (mean_sq_min && mean_sq_min <= X3Q_MEAN_SQ_MAX && r.sum_sq >= mean_sq_min * (uint64_t)r.n) ||
-         (peak_min && peak_min <= X3Q_PEAK_MAX && peak >= (int64_t)peak_min);
-}
-
-// (the entry first: its thresholds are the rule)
-__global__ void __launch_bounds__(256)
-x3_events_adaptive_flag_kernel(X3EvRows q, const x3_event_threshold* __restrict__ thr, uint64_t n_tiles, uint8_t* __restrict__ hot,
-                               uint32_t* __restrict__ tile_prev, uint32_t* __restrict__ tile_next) {
-  x3e_flag_tiles(q, [&](const X3EvRows& q, uint64_t r) {
-    X3EvEntry en;
-    if (!x3e_entry_of(q, r, &en)) return false;   // (en.e: below n_ent, 0 in the stream form)
-    const x3_event_threshold k = thr[en.e];
-    return x3q_loud(q.levels[r], k.mean_sq_min, k.peak_min);
-  }, n_tiles, hot, tile_prev, tile_next);
 }

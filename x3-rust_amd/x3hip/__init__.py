@@ -1802,41 +1802,8 @@ def _range_levels_torch(ctx, enqueue, what, starts, lens, bin_len, padded_to, ca
     return (levels[:, :cap] if planes else levels[0, :cap]), offsets, status
 
 
-def _events_torch(ctx, n_rows, capacity, with_entries, enqueue_levels, enqueue_events):
-    """The torch side of WindowSource.events / Corpus.events: the levels call and the events call back to back on the
-    context's stream, no host trip in between -> ([entries,] starts, lens, count, event_levels), device tensors of `capacity`
-    slots (count: 0-d; event_levels: [capacity, 32] uint8, see event_levels_view).  enqueue_levels(d_levels) -> rc,
-    enqueue_events(d_levels, d_entries, d_starts, d_lens, d_event_levels, d_count) -> rc."""
-    import torch
-    capacity = int(capacity)
-    if capacity <= 0:
-        raise ValueError("capacity: at least one slot")
-    dev = torch.device("cuda", torch.cuda.current_device())
-    levels = torch.empty((n_rows, LEVEL_DTYPE.itemsize), dtype=torch.uint8, device=dev)
-    entries = torch.empty(capacity, dtype=torch.int32, device=dev) if with_entries else None
-    starts = torch.empty(capacity, dtype=torch.int64, device=dev)
-    lens = torch.empty(capacity, dtype=torch.int32, device=dev)
-    event_levels = torch.empty((capacity, LEVEL_DTYPE.itemsize), dtype=torch.uint8, device=dev)
-    count = torch.empty((), dtype=torch.int64, device=dev)
-    torch.cuda.current_stream().synchronize()    # (the context's stream is not torch's)
-    rc = enqueue_levels(levels.data_ptr())
-    if rc:
-        raise X3Error(rc, "levels: " + ctx.last_error())
-    rc = enqueue_events(levels.data_ptr(), entries.data_ptr() if with_entries else None, starts.data_ptr(), lens.data_ptr(),
-                        event_levels.data_ptr(), count.data_ptr())
-    if rc:
-        ctx.levels_result()
-        raise X3Error(rc, "events: " + ctx.last_error())
-    rc_ev, rc_lv = ctx.events_result()[0], ctx.levels_result()[0]   # (both slots are read, whatever the first says)
-    rc = rc_ev or rc_lv
-    if rc:
-        raise X3Error(rc, "x3_events_result: " + ctx.last_error())
-    out = (starts, lens, count, event_levels)
-    return (entries,) + out if with_entries else out
-
-
 def _level_quantiles_torch(ctx, n_rows, n_ent, n_q, enqueue_levels, enqueue_quantiles):
-    """The torch side of WindowSource.level_quantiles / Corpus.level_quantiles: the levels call and the quantiles call back
+    """The torch side of level_quantiles of a WindowSource or a Corpus: the levels call and the quantiles call back
     to back -> (values int32 [n_ent, n_q], counted int32 [n_ent]) on the device (the bits of the uint32 words)."""
     import torch
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -1844,7 +1811,7 @@ def _level_quantiles_torch(ctx, n_rows, n_ent, n_q, enqueue_levels, enqueue_quan
     values = torch.empty((n_ent, n_q), dtype=torch.int32, device=dev)
     counted = torch.empty(n_ent, dtype=torch.int32, device=dev)
     torch.cuda.current_stream().synchronize()    # (the context's stream is not torch's)
-    rc = enqueue_levels(levels.data_ptr())
+    rc = enqueue_levels(levels.data_ptr(), n_rows)
     if rc:
         raise X3Error(rc, "levels: " + ctx.last_error())
     rc = enqueue_quantiles(levels.data_ptr(), values.data_ptr(), counted.data_ptr())
@@ -1857,34 +1824,21 @@ def _level_quantiles_torch(ctx, n_rows, n_ent, n_q, enqueue_levels, enqueue_quan
     return values, counted
 
 
-def _adaptive_events_torch(ctx, n_rows, n_ent, capacity, with_entries, enqueue_levels, enqueue_thresholds, enqueue_events):
-    """The torch side of WindowSource.adaptive_events / Corpus.adaptive_events: levels, thresholds and events back to back,
-    no host trip in between -> what _events_torch returns plus thresholds uint8 [n_ent, 16] (EVENT_THRESHOLD_DTYPE records)."""
-    import torch
-    dev = torch.device("cuda", torch.cuda.current_device())
-    thr = torch.empty((n_ent, EVENT_THRESHOLD_DTYPE.itemsize), dtype=torch.uint8, device=dev)
-
-    def both(d_lv, d_e, d_s, d_l, d_el, d_c):
-        rc = enqueue_thresholds(d_lv, thr.data_ptr())
-        if rc:
-            return rc
-        rc = enqueue_events(d_lv, thr.data_ptr(), d_e, d_s, d_l, d_el, d_c)
-        rq = ctx.level_quantiles_result()[0]    # (its own slot: read whatever the events call said)
-        return rc or rq
-    return _events_torch(ctx, n_rows, capacity, with_entries, enqueue_levels, both) + (thr,)
-
-
-def _plane_events_torch(src, levels, n_planes, bin_len, rule, capacity, with_entries, enqueue_events, *, thresholds=None,
-                        enqueue_levels=None, enqueue_thresholds=None):
-    """The torch side of plane_events / bank_events / adaptive_bank_events of src, a WindowSource or a Corpus.
+def _detect_torch(src, what, levels, n_planes, bin_len, capacity, enqueue_events, *, rule_planes=None, thresholds=None,
+                  enqueue_levels=None, enqueue_thresholds=None, mask=True, sync=True, result_what=None):
+    """The torch side of every detection call of src, a WindowSource or a Corpus: the chain levels (optional), thresholds
+    (optional, per plane), events, enqueued back to back on the context's stream with no host trip in between.
     levels: a uint8 [K, rows, 32] device tensor of records of any origin, or None: K = n_planes planes of src's own rows
     that enqueue_levels(d_levels, n_rows) -> rc fills.  thresholds: None or a uint8 [K, n_entries, 16] device tensor;
-    enqueue_thresholds(d_plane, n_rows, d_thr) -> rc, called per plane, fills one made here, which is then returned too.
-    enqueue_events(d_levels, n_rows, d_thr, d_entries, d_starts, d_lens, d_event_planes, d_event_levels, d_count) -> rc.
-    Everything is enqueued back to back on the context's stream ->
-    ([entries,] starts, lens, count, planes int32 [capacity], event_levels uint8 [K, capacity, 32][, thresholds])"""
+    enqueue_thresholds(d_plane, n_rows, d_thr) -> rc, called per plane, fills one made here, which is then returned.
+    enqueue_events(d_levels, n_rows, d_thr, d_entries, d_starts, d_lens, d_event_planes, d_event_levels, d_count) -> rc;
+    d_entries is None for a WindowSource, d_event_planes without `mask`.  rule_planes: the planes the caller's rule is of.
+    sync: wait for the context's stream behind the result calls.  An X3Error names `what`, or `result_what` where the events'
+    or the levels' result call reports the failure.
+    -> (([entries,] starts, lens, count), planes int32 [capacity] or None, event_levels uint8 [K, capacity, 32],
+    thresholds or None): device tensors of `capacity` slots, count 0-d; the callers shape their tuples from it"""
     import torch
-    ctx = src.ctx
+    ctx, with_entries = src.ctx, src._has_entries
     capacity = int(capacity)
     if capacity <= 0:
         raise ValueError("capacity: at least one slot")
@@ -1902,8 +1856,8 @@ def _plane_events_torch(src, levels, n_planes, bin_len, rule, capacity, with_ent
                          % (levels.shape[1], bin_len, src._levels_rows(bin_len)[0]))
     levels = levels.contiguous()
     dev, k, n_rows = levels.device, levels.shape[0], levels.shape[1]
-    if rule.n_planes != k:
-        raise ValueError("the rule is one of %d planes, the records have %d" % (rule.n_planes, k))
+    if rule_planes is not None and rule_planes != k:
+        raise ValueError("the rule is one of %d planes, the records have %d" % (rule_planes, k))
     n_ent = src.n_entries if with_entries else 1
     thr_rec = EVENT_THRESHOLD_DTYPE.itemsize
     if enqueue_thresholds is not None:
@@ -1916,7 +1870,7 @@ def _plane_events_torch(src, levels, n_planes, bin_len, rule, capacity, with_ent
     entries = torch.empty(capacity, dtype=torch.int32, device=dev) if with_entries else None
     starts = torch.empty(capacity, dtype=torch.int64, device=dev)
     lens = torch.empty(capacity, dtype=torch.int32, device=dev)
-    planes = torch.empty(capacity, dtype=torch.int32, device=dev)
+    planes = torch.empty(capacity, dtype=torch.int32, device=dev) if mask else None
     event_levels = torch.empty((k, capacity, rec), dtype=torch.uint8, device=dev)
     count = torch.empty((), dtype=torch.int64, device=dev)
     torch.cuda.current_stream().synchronize()    # (the context's stream is not torch's)
@@ -1931,18 +1885,19 @@ def _plane_events_torch(src, levels, n_planes, bin_len, rule, capacity, with_ent
             rc = rc or enqueue_thresholds(d_lv + t * n_rows * rec, n_rows, thresholds.data_ptr() + t * n_ent * thr_rec)
     rc = rc or enqueue_events(d_lv, n_rows, thresholds.data_ptr() if thresholds is not None else None,
                               entries.data_ptr() if with_entries else None, starts.data_ptr(), lens.data_ptr(),
-                              planes.data_ptr(), event_levels.data_ptr(), count.data_ptr())
+                              planes.data_ptr() if mask else None, event_levels.data_ptr(), count.data_ptr())
     # (every slot this call has made pending is read, whatever an earlier one said)
     r_ev = 0 if rc else ctx.events_result()[0]
     r_q = ctx.level_quantiles_result()[0] if enqueue_thresholds is not None else 0
     r_lv = ctx.levels_result()[0] if enqueue_levels is not None else 0
-    ctx.sync()
-    rc = rc or r_ev or r_q or r_lv
-    if rc:
-        raise X3Error(rc, "plane events: " + ctx.last_error())
-    out = (starts, lens, count, planes, event_levels)
-    out = (entries,) + out if with_entries else out
-    return out + (thresholds,) if enqueue_thresholds is not None else out
+    if sync:
+        ctx.sync()
+    if rc or r_q:
+        raise X3Error(rc or r_q, what + ": " + ctx.last_error())
+    if r_ev or r_lv:
+        raise X3Error(r_ev or r_lv, (result_what or what) + ": " + ctx.last_error())
+    head = (starts, lens, count)
+    return ((entries,) + head if with_entries else head), planes, event_levels, thresholds if enqueue_thresholds is not None else None
 
 
 def _levels_np(src, what, bin_len, n_rows, dtype, enqueue, planes=None):
@@ -1974,12 +1929,12 @@ def _levels_np(src, what, bin_len, n_rows, dtype, enqueue, planes=None):
 
 def _levels_chain(src, bin_len, signal):
     """what events(), level_quantiles() and adaptive_events() of a WindowSource or a Corpus begin with -> (the rows of the
-    levels of `signal`, enqueue_levels(d_levels) -> rc)"""
+    levels of `signal`, enqueue_levels(d_levels, n_rows) -> rc)"""
     if not 0 < bin_len <= 0xFFFFFFFF:
         raise ValueError("bin_len: 1 .. 2^32 - 1")
     sig = level_signal(signal)
     n_rows = src._levels_rows(bin_len)[0]
-    return n_rows, lambda d_lv: src.levels_into(bin_len, d_lv, n_rows, None, sig)
+    return n_rows, lambda d_lv, n: src.levels_into(bin_len, d_lv, n, None, sig)
 
 
 def _bank_planes(tones):
@@ -1987,7 +1942,91 @@ def _bank_planes(tones):
     return tones.n_tones if isinstance(tones, LevelToneBank) else len(tone_bank(tones))
 
 
-class WindowSource:
+class _Detection:
+    """The detection methods of WindowSource and Corpus, written once over what differs between the two: the rows of a bin
+    length (_levels_rows), the entry count (n_entries; 1 where _has_entries is False), whether a call has an `entries`
+    output (_has_entries: a Corpus's *_into enqueuers take d_entries in front of d_starts), and the *_into enqueuers
+    themselves, which stay on each class.  All results are torch tensors on the device."""
+    _has_entries = False
+
+    def _ent(self, d_entries):
+        return (d_entries,) if self._has_entries else ()
+
+    def events(self, bin_len, rule, capacity, *, signal="samples"):
+        """Levels (of `signal`, as in levels()) of bins of bin_len positions -- of every entry of a Corpus --, then the runs
+        of hot bins under `rule` (an EventRule) as ranges, all on the device -> (starts int64 [capacity], lens int32
+        [capacity], count 0-d int64, event_levels uint8 [capacity, 32]), a Corpus: entries int32 [capacity] in front.  Slots
+        behind the events are zero-length ranges: ranges([entries,] starts, lens, padded_to=...) takes the tensors as they
+        are.  count may exceed capacity: repeat with more."""
+        _, enqueue_levels = _levels_chain(self, bin_len, signal)
+        head, _, event_levels, _ = _detect_torch(
+            self, "events", None, 1, bin_len, capacity,
+            lambda d_lv, n, d_t, d_e, d_s, d_l, d_p, d_el, d_c: self.events_into(d_lv, n, bin_len, rule, *self._ent(d_e), d_s, d_l,
+                                                                                 d_el, capacity, d_c),
+            enqueue_levels=enqueue_levels, mask=False, sync=False, result_what="x3_events_result")
+        return head + (event_levels[0],)
+
+    def level_quantiles(self, bin_len, key, q_ppm, *, signal="samples"):
+        """Levels (of `signal`, as in levels()) of bins of bin_len positions, then per entry the quantiles q_ppm (millionths)
+        of their keys, on the device -> (values int32 [n_entries, len(q_ppm)], counted int32 [n_entries]); a WindowSource
+        is one entry"""
+        n_rows, enqueue_levels = _levels_chain(self, bin_len, signal)
+        return _level_quantiles_torch(
+            self.ctx, n_rows, self.n_entries if self._has_entries else 1, len(q_ppm), enqueue_levels,
+            lambda d_lv, d_v, d_k: self.level_quantiles_into(d_lv, n_rows, bin_len, key, q_ppm, d_v, d_k))
+
+    def adaptive_events(self, bin_len, threshold_rule, rule, capacity, *, signal="samples"):
+        """events() with the rule's two values (both 0 in `rule`) chosen on the device, per entry, by `threshold_rule` (a
+        ThresholdRule) -> what events() returns, and thresholds uint8 [n_entries, 16] (EVENT_THRESHOLD_DTYPE records; one
+        for a WindowSource)"""
+        _, enqueue_levels = _levels_chain(self, bin_len, signal)
+        head, _, event_levels, thr = _detect_torch(
+            self, "events", None, 1, bin_len, capacity,
+            lambda d_lv, n, d_t, d_e, d_s, d_l, d_p, d_el, d_c: self.adaptive_events_into(d_lv, n, bin_len, rule, d_t,
+                                                                                          *self._ent(d_e), d_s, d_l, d_el, capacity, d_c),
+            enqueue_levels=enqueue_levels,
+            enqueue_thresholds=lambda d_lv, n, d_t: self.level_thresholds_into(d_lv, n, bin_len, threshold_rule, d_t),
+            mask=False, sync=False, result_what="x3_events_result")
+        return head + (event_levels[0], thr[0])
+
+    def _plane_events(self, levels, n_planes, bin_len, rule, capacity, **kw):
+        head, planes, event_levels, thr = _detect_torch(
+            self, "plane events", levels, n_planes, bin_len, capacity,
+            lambda d_lv, n, d_t, d_e, d_s, d_l, d_p, d_el, d_c: self.plane_events_into(d_lv, n, n, bin_len, rule, d_t, *self._ent(d_e),
+                                                                                      d_s, d_l, d_p, d_el, capacity, d_c),
+            rule_planes=rule.n_planes, **kw)
+        out = head + (planes, event_levels)
+        return out if thr is None else out + (thr,)
+
+    def plane_events(self, levels, bin_len, rule, capacity, *, thresholds=None):
+        """The runs of bins that are loud in at least rule.min_planes of K planes of level records (levels: a uint8 torch
+        tensor [K, rows, 32] on the device, records of any origin over this source's bins of bin_len positions -- exactly
+        as many rows as cover the stream, or as levels() gives for a Corpus; anything else is a ValueError; rule: a
+        PlaneEventRule; thresholds: None, or uint8 [K, n_entries, 16] records on the device, n_entries 1 for a WindowSource,
+        and a rule without values) as ONE ordered, disjoint list of ranges; runs never cross an entry ->
+        (starts int64 [capacity], lens int32 [capacity], count 0-d int64, planes int32 [capacity]: bit t set when plane t is
+        loud in the event, event_levels uint8 [K, capacity, 32]) on the device, a Corpus: entries int32 [capacity] in front"""
+        return self._plane_events(levels, None, bin_len, rule, capacity, thresholds=thresholds)
+
+    def bank_events(self, bin_len, tones, rule, capacity):
+        """tone_bank_levels_into(..., band=True), then plane_events over its planes, no wait in between -> as plane_events;
+        tone_bank_range_levels([entries,] starts, lens, ...) takes the tensors as they are"""
+        tones = tone_bank(tones)
+        return self._plane_events(None, len(tones), bin_len, rule, capacity,
+                                  enqueue_levels=lambda d_lv, n: self.tone_bank_levels_into(bin_len, tones, d_lv, n, band=True))
+
+    def adaptive_bank_events(self, bin_len, tones, threshold_rule, rule, capacity):
+        """bank_events with the two values of every plane of every entry (none in `rule`) chosen on the device by
+        `threshold_rule` (a ThresholdRule), a thresholds call per plane in between -> as plane_events, and thresholds uint8
+        [K, n_entries, 16] (n_entries 1 for a WindowSource)"""
+        tones = tone_bank(tones)
+        return self._plane_events(None, len(tones), bin_len, rule, capacity,
+                                  enqueue_levels=lambda d_lv, n: self.tone_bank_levels_into(bin_len, tones, d_lv, n, band=True),
+                                  enqueue_thresholds=lambda d_lv, n, d_t: self.level_thresholds_into(d_lv, n, bin_len,
+                                                                                                     threshold_rule, d_t))
+
+
+class WindowSource(_Detection):
     """Random access to one mono stream in HBM: windows of samples [start, start + length) as rows of a batch.
 
     `stream`: host bytes (uploaded once) or (d_x3, x3_len) of a device stream.  Without `frame_offsets` (a device pointer to
@@ -2281,17 +2320,6 @@ class WindowSource:
         return self.ctx.events_dev(d_levels, n_bins, bin_len, self.d_sample_offsets + 8 * self.n_frames, rule, d_starts, d_lens,
                                    d_event_levels, cap, d_count)
 
-    def events(self, bin_len, rule, capacity, *, signal="samples"):
-        """Levels (of `signal`, as in levels()) of bins of bin_len positions, then the runs of hot bins under `rule` (an EventRule) as ranges, all on the
-        device -> (starts int64 [capacity], lens int32 [capacity], count 0-d int64, event_levels uint8 [capacity, 32]),
-        torch tensors on the device.  Slots behind the events are zero-length ranges: ranges(starts, lens, padded_to=...)
-        takes the tensors as they are.  count may exceed capacity: repeat with more."""
-        n_bins, enqueue_levels = _levels_chain(self, bin_len, signal)
-        return _events_torch(
-            self.ctx, n_bins, capacity, False,
-            enqueue_levels,
-            lambda d_lv, d_e, d_s, d_l, d_el, d_c: self.events_into(d_lv, n_bins, bin_len, rule, d_s, d_l, d_el, capacity, d_c))
-
     def level_quantiles_into(self, d_levels, n_bins, bin_len, key, q_ppm, d_values, d_counted):
         """enqueue x3_level_quantiles_dev over n_bins records this source's levels_dev wrote (device pointers); -> rc;
         Context.level_quantiles_result waits"""
@@ -2308,63 +2336,12 @@ class WindowSource:
         return self.ctx.events_adaptive_dev(d_levels, n_bins, bin_len, self.d_sample_offsets + 8 * self.n_frames, rule, d_thr,
                                             d_starts, d_lens, d_event_levels, cap, d_count)
 
-    def level_quantiles(self, bin_len, key, q_ppm, *, signal="samples"):
-        """Levels (of `signal`, as in levels()) of bins of bin_len positions, then the quantiles q_ppm (millionths) of their keys, on the device ->
-        (values int32 [1, len(q_ppm)], counted int32 [1]) torch tensors"""
-        n_bins, enqueue_levels = _levels_chain(self, bin_len, signal)
-        return _level_quantiles_torch(
-            self.ctx, n_bins, 1, len(q_ppm),
-            enqueue_levels,
-            lambda d_lv, d_v, d_k: self.level_quantiles_into(d_lv, n_bins, bin_len, key, q_ppm, d_v, d_k))
-
-    def adaptive_events(self, bin_len, threshold_rule, rule, capacity, *, signal="samples"):
-        """events() with the rule's two values (both 0 in `rule`) chosen on the device by `threshold_rule` (a ThresholdRule)
-        -> (starts, lens, count, event_levels, thresholds uint8 [1, 16])"""
-        n_bins, enqueue_levels = _levels_chain(self, bin_len, signal)
-        return _adaptive_events_torch(
-            self.ctx, n_bins, 1, capacity, False,
-            enqueue_levels,
-            lambda d_lv, d_t: self.level_thresholds_into(d_lv, n_bins, bin_len, threshold_rule, d_t),
-            lambda d_lv, d_t, d_e, d_s, d_l, d_el, d_c: self.adaptive_events_into(d_lv, n_bins, bin_len, rule, d_t, d_s, d_l, d_el,
-                                                                                  capacity, d_c))
-
     def plane_events_into(self, d_levels, plane_stride, n_bins, bin_len, rule, d_thr, d_starts, d_lens, d_event_planes,
                           d_event_levels, cap, d_count):
         """enqueue x3_plane_events_dev over rule.n_planes planes of n_bins records of this source (device pointers; rule: a
         PlaneEventRule; d_thr: None or a record per plane); -> rc; Context.events_result waits"""
         return self.ctx.plane_events_dev(d_levels, plane_stride, n_bins, bin_len, self.d_sample_offsets + 8 * self.n_frames, rule,
                                          d_thr, d_starts, d_lens, d_event_planes, d_event_levels, cap, d_count)
-
-    def _plane_events(self, levels, n_planes, bin_len, rule, capacity, **kw):
-        return _plane_events_torch(
-            self, levels, n_planes, bin_len, rule, capacity, False,
-            lambda d_lv, n, d_t, d_e, d_s, d_l, d_p, d_el, d_c: self.plane_events_into(d_lv, n, n, bin_len, rule, d_t, d_s, d_l,
-                                                                                      d_p, d_el, capacity, d_c), **kw)
-
-    def plane_events(self, levels, bin_len, rule, capacity, *, thresholds=None):
-        """The runs of bins that are loud in at least rule.min_planes of K planes of level records (levels: a uint8 torch
-        tensor [K, bins, 32] on the device, records of any origin over this source's bins of bin_len positions -- exactly
-        as many rows as cover the stream, anything else is a ValueError; rule: a
-        PlaneEventRule; thresholds: None, or uint8 [K, 1, 16] records on the device and a rule without values) as ONE
-        ordered, disjoint list of ranges -> (starts int64 [capacity], lens int32 [capacity], count 0-d int64, planes int32
-        [capacity]: bit t set when plane t is loud in the event, event_levels uint8 [K, capacity, 32]) on the device"""
-        return self._plane_events(levels, None, bin_len, rule, capacity, thresholds=thresholds)
-
-    def bank_events(self, bin_len, tones, rule, capacity):
-        """tone_bank_levels_into(..., band=True), then plane_events over its planes, no wait in between -> as plane_events;
-        tone_bank_range_levels(starts, lens, ...) takes the tensors as they are"""
-        tones = tone_bank(tones)
-        return self._plane_events(None, len(tones), bin_len, rule, capacity,
-                                  enqueue_levels=lambda d_lv, n: self.tone_bank_levels_into(bin_len, tones, d_lv, n, band=True))
-
-    def adaptive_bank_events(self, bin_len, tones, threshold_rule, rule, capacity):
-        """bank_events with the two values of every plane (none in `rule`) chosen on the device by `threshold_rule` (a
-        ThresholdRule), a thresholds call per plane in between -> as plane_events, and thresholds uint8 [K, 1, 16]"""
-        tones = tone_bank(tones)
-        return self._plane_events(None, len(tones), bin_len, rule, capacity,
-                                  enqueue_levels=lambda d_lv, n: self.tone_bank_levels_into(bin_len, tones, d_lv, n, band=True),
-                                  enqueue_thresholds=lambda d_lv, n, d_t: self.level_thresholds_into(d_lv, n, bin_len,
-                                                                                                     threshold_rule, d_t))
 
     def close(self):
         for p in self._own:
@@ -2464,7 +2441,7 @@ def decode_archives(ctx, archives, row_len=None, fmt=WINDOW_I16):
     return rows, results, rates
 
 
-class Corpus:
+class Corpus(_Detection):
     """Windows of many streams in HBM (x3_corpus_build / x3_corpus_windows_dev): an index built once over the entries of
     one device buffer, windows addressed as (entry, start).
 
@@ -2473,6 +2450,7 @@ class Corpus:
     segment index (0: none; it is only ever a hint).  index: "decode" = recorded by a decode of the corpus (block length
     20 and the default codes; none elsewhere), "walk" = built by x3_seg_index_build_dev for any parameters
     (CORPUS_INDEX_WALK).  `.entries`: the entry table (CORPUS_ENTRY_DTYPE)."""
+    _has_entries = True   # (_Detection: the calls have an `entries` output)
 
     def __init__(self, ctx, stream, offsets, lengths, params=None, flags=0, seg_blocks=32, index="decode"):
         self.ctx, self.params, self._h, self._own = ctx, params or Params.default(), None, []
@@ -2761,16 +2739,6 @@ class Corpus:
         return self.ctx.corpus_events_dev(self, d_levels, n_rows, bin_len, rule, d_entries, d_starts, d_lens, d_event_levels,
                                           cap, d_count)
 
-    def events(self, bin_len, rule, capacity, *, signal="samples"):
-        """Levels (of `signal`, as in levels()) of every entry, then the runs of hot bins under `rule` as ranges, all on the device -> (entries int32,
-        starts int64, lens int32 [capacity each], count 0-d int64, event_levels uint8 [capacity, 32]), as
-        WindowSource.events; ranges(entries, starts, lens, padded_to=...) takes the tensors as they are."""
-        n_rows, enqueue_levels = _levels_chain(self, bin_len, signal)
-        return _events_torch(
-            self.ctx, n_rows, capacity, True,
-            enqueue_levels,
-            lambda d_lv, d_e, d_s, d_l, d_el, d_c: self.events_into(d_lv, n_rows, bin_len, rule, d_e, d_s, d_l, d_el, capacity, d_c))
-
     def level_quantiles_into(self, d_levels, n_rows, bin_len, key, q_ppm, d_values, d_counted):
         """enqueue x3_corpus_level_quantiles_dev over the n_rows records Context.corpus_levels_dev wrote; -> rc;
         Context.level_quantiles_result waits"""
@@ -2792,26 +2760,6 @@ class Corpus:
         return self.ctx.corpus_events_adaptive_dev(self, d_levels, n_rows, bin_len, rule, d_thr, d_entries, d_starts, d_lens,
                                                    d_event_levels, cap, d_count)
 
-    def level_quantiles(self, bin_len, key, q_ppm, *, signal="samples"):
-        """Levels (of `signal`, as in levels()) of every entry, then per entry the quantiles q_ppm (millionths) of their keys, on the device ->
-        (values int32 [n_entries, len(q_ppm)], counted int32 [n_entries]) torch tensors"""
-        n_rows, enqueue_levels = _levels_chain(self, bin_len, signal)
-        return _level_quantiles_torch(
-            self.ctx, n_rows, self.n_entries, len(q_ppm),
-            enqueue_levels,
-            lambda d_lv, d_v, d_k: self.level_quantiles_into(d_lv, n_rows, bin_len, key, q_ppm, d_v, d_k))
-
-    def adaptive_events(self, bin_len, threshold_rule, rule, capacity, *, signal="samples"):
-        """events() with a threshold per entry chosen on the device by `threshold_rule` -> (entries, starts, lens, count,
-        event_levels, thresholds uint8 [n_entries, 16])"""
-        n_rows, enqueue_levels = _levels_chain(self, bin_len, signal)
-        return _adaptive_events_torch(
-            self.ctx, n_rows, self.n_entries, capacity, True,
-            enqueue_levels,
-            lambda d_lv, d_t: self.level_thresholds_into(d_lv, n_rows, bin_len, threshold_rule, d_t),
-            lambda d_lv, d_t, d_e, d_s, d_l, d_el, d_c: self.adaptive_events_into(d_lv, n_rows, bin_len, rule, d_t, d_e, d_s, d_l,
-                                                                                  d_el, capacity, d_c))
-
     def plane_events_into(self, d_levels, plane_stride, n_rows, bin_len, rule, d_thr, d_entries, d_starts, d_lens, d_event_planes,
                           d_event_levels, cap, d_count):
         """enqueue x3_corpus_plane_events_dev over rule.n_planes planes of the n_rows records Context.corpus_levels_dev wrote
@@ -2820,34 +2768,6 @@ class Corpus:
             raise ValueError("the corpus is closed")
         return self.ctx.corpus_plane_events_dev(self, d_levels, plane_stride, n_rows, bin_len, rule, d_thr, d_entries, d_starts,
                                                 d_lens, d_event_planes, d_event_levels, cap, d_count)
-
-    def _plane_events(self, levels, n_planes, bin_len, rule, capacity, **kw):
-        return _plane_events_torch(
-            self, levels, n_planes, bin_len, rule, capacity, True,
-            lambda d_lv, n, d_t, d_e, d_s, d_l, d_p, d_el, d_c: self.plane_events_into(d_lv, n, n, bin_len, rule, d_t, d_e, d_s,
-                                                                                      d_l, d_p, d_el, capacity, d_c), **kw)
-
-    def plane_events(self, levels, bin_len, rule, capacity, *, thresholds=None):
-        """WindowSource.plane_events over K planes of the rows of levels() (levels: uint8 [K, rows, 32]; thresholds: None or
-        uint8 [K, n_entries, 16]); runs never cross an entry -> (entries int32, starts int64, lens int32 [capacity each],
-        count 0-d int64, planes int32 [capacity], event_levels uint8 [K, capacity, 32]) on the device"""
-        return self._plane_events(levels, None, bin_len, rule, capacity, thresholds=thresholds)
-
-    def bank_events(self, bin_len, tones, rule, capacity):
-        """tone_bank_levels_into(..., band=True), then plane_events over its planes, no wait in between -> as plane_events;
-        tone_bank_range_levels(entries, starts, lens, ...) takes the tensors as they are"""
-        tones = tone_bank(tones)
-        return self._plane_events(None, len(tones), bin_len, rule, capacity,
-                                  enqueue_levels=lambda d_lv, n: self.tone_bank_levels_into(bin_len, tones, d_lv, n, band=True))
-
-    def adaptive_bank_events(self, bin_len, tones, threshold_rule, rule, capacity):
-        """bank_events with the two values of every plane of every entry (none in `rule`) chosen on the device by
-        `threshold_rule`, a thresholds call per plane in between -> as plane_events, and thresholds uint8 [K, n_entries, 16]"""
-        tones = tone_bank(tones)
-        return self._plane_events(None, len(tones), bin_len, rule, capacity,
-                                  enqueue_levels=lambda d_lv, n: self.tone_bank_levels_into(bin_len, tones, d_lv, n, band=True),
-                                  enqueue_thresholds=lambda d_lv, n, d_t: self.level_thresholds_into(d_lv, n, bin_len,
-                                                                                                     threshold_rule, d_t))
 
     def close(self):
         if self._h is not None:
