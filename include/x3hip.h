@@ -1354,6 +1354,44 @@ int x3_spectra_rows_dev(x3_ctx* ctx, const int16_t* d_samples, uint64_t samples_
                         const uint32_t* d_lens, const int32_t* d_in_status, uint64_t n_ranges, const x3_spectra_rule* rule,
                         uint64_t row_stride, void* d_out, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status);
 int x3_spectra_result(x3_ctx* ctx, uint64_t* n_bad, uint64_t* first_bad, int* first_bad_status, uint64_t* total_rows);
+/* ---- SPECTRA, BAND LEVELS: the POWER words of x3_spectra_rows_dev folded into bands and summed over consecutive frames,
+ * written as planes of x3_level -- the record x3_events_dev, x3_plane_events_dev, the quantiles and the thresholds calls
+ * take -- and no row per frame anywhere.  The rule, B = n_fft / 2 + 1, R(w) and the POWER word
+ * ms[w][r][k] of frame r, bin k are x3_spectra_rows_dev's; rule->format must be X3_SPECTRA_POWER.
+ *   THE FOLD is a host struct, copied at the call: frames_per_bin = M in 1 .. 2^31 - 1, n_bands = K in 1 .. B, and
+ * d_bin_band, B uint32 words in device memory (4-byte aligned, read when the kernels run): word k is the band of bin k, any
+ * value >= K means "bin k is in no band".  Any contents are legal; bands need not be contiguous; a band may have no bin.
+ *   Range w has T(w) = ceil(R(w) / M) time bins; time bin j holds frames [j * M, min((j + 1) * M, R(w))), the last one
+ * possibly fewer than M.  For band b and frame r
+ *     bp[r][b] = min(2^30, sum over k with bin_band[k] == b of ms[w][r][k])       (the sum in 64 bits, the clamp per frame)
+ * and the record of (w, j, b) is n = the frames of the time bin, sum_sq = the sum of their bp, sum = 0,
+ * max = min(32767, isqrt(2 * the largest bp among them)), min = -max, reserved = 0: the tone adapter's shape
+ * (x3_tone_power_levels_dev), the peak taken over frames, sum_sq / n <= 2^30.  With M = 1 and bin_band[k] = k a record's
+ * sum_sq is the POWER word, and on an aligned frame sum_sq / n, max and min are the adapter's at that step (which counts
+ * the frame's n_fft samples where this call counts one frame).  Where the call owns a
+ * record and no frame falls into it, it holds the identity {0, 0, 32767, -32768, 0, 0}.
+ *   LAYOUT.  The rows of a range are its time bins, laid by x3_spectra_rows_dev's rules with T(w) for R(w): packed at the
+ * exclusive sum of T(w) (d_row_offsets, n_ranges + 1 words), or padded to row_stride with identity records behind T(w);
+ * a range whose rows have no room is X3_ERR_BAD_ARG.  The K bands are K planes, plane b at d_levels + b * plane_stride
+ * records; plane_stride 0 means rows_cap.  In every plane the call writes every record of rows [0, min(total, rows_cap))
+ * when packed and of [0, n_ranges * row_stride) when padded; a range with a status has identity records only; records
+ * between rows_cap and plane_stride are never touched.  Statuses, d_in_status (in place allowed), d_row_offsets, the
+ * untrusted offsets and lengths and the asynchronous contract are x3_spectra_rows_dev's, word for word; the pending slot
+ * and the workspace are shared with it, and x3_spectra_result serves the result with total_rows = the sum of T(w).
+ *   X3_ERR_BAD_ARG with nothing enqueued, in this order: the rule's checks (and a format other than X3_SPECTRA_POWER);
+ * then a NULL fold, frames_per_bin == 0 or above 2^31 - 1, n_bands == 0 or above B, a NULL or misaligned d_bin_band,
+ * reserved != 0, a non-zero plane_stride below rows_cap, n_bands * max(plane_stride, rows_cap) > 2^31 - 1; then everything
+ * x3_spectra_rows_dev refuses (d_levels in the place of d_out). */
+typedef struct x3_spectra_fold {     /* 32 bytes, host struct, copied at the call */
+  uint32_t frames_per_bin, n_bands;
+  uint64_t plane_stride;             /* records; 0: rows_cap */
+  const uint32_t* d_bin_band;        /* device, n_fft / 2 + 1 words, 4-byte aligned, read when the kernels run */
+  uint64_t reserved;                 /* 0 */
+} x3_spectra_fold;
+int x3_spectra_levels_dev(x3_ctx* ctx, const int16_t* d_samples, uint64_t samples_cap, const uint64_t* d_offsets,
+                          const uint32_t* d_lens, const int32_t* d_in_status, uint64_t n_ranges, const x3_spectra_rule* rule,
+                          const x3_spectra_fold* fold, uint64_t row_stride, x3_level* d_levels, uint64_t rows_cap,
+                          uint64_t* d_row_offsets, int32_t* d_status);
 void x3_corpus_destroy(x3_corpus* corpus);
 
 /* ------------------------------------------------------------------ multi-GPU (no reference analogue) */

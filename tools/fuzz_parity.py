@@ -48,7 +48,10 @@ Families: (e) the single-pass encoders on block_len 20 with mixed content, many 
           tests/plane_events_ref.py in every slot; bank_events (no host trip) on the same rule; then the same frames as a
           corpus of random entries (not in the default family set); (y) spectra (x3_spectra_rows_dev): int16 rows in HBM at
           drawn offsets x n_fft x hop x format x layout x capacities x table x in-statuses, lengths round n_fft and round
-          whole frames, GPU == tests/spectra_ref.py in every word (not in the default family set; (w) is the files')."""
+          whole frames, GPU == tests/spectra_ref.py in every word (not in the default family set; (w) is the files'); (z) band
+          levels (x3_spectra_levels_dev): (y)'s rows, lengths round whole time bins as well, x frames_per_bin x n_bands x band
+          maps with wild words and empty bands x plane strides, GPU == tests/spectra_levels_ref.py in every record of every
+          plane (not in the default family set)."""
 import argparse, ctypes as C, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "x3-rust_amd"))
@@ -1607,6 +1610,98 @@ def fam_y(rng, tag):
 
 
 fams["y"] = fam_y
+
+
+def fam_z(rng, tag):
+    """band levels (x3_spectra_levels_dev): fam_y's rows -- lengths round n_fft, round whole frames and round whole time bins
+    -- x n_fft x hop x frames_per_bin x n_bands x band maps with wild words and empty bands x layout x row capacities x plane
+    strides x tables x in-statuses (none, separate, in place); every record of every plane GPU == tests/spectra_levels_ref.py,
+    what the call may not write -- the records between rows_cap and plane_stride among them -- keeps its fill; the result call"""
+    import spectra_levels_ref as SL
+    import spectra_ref as SP
+    n_fft = int(rng.choice(SP.NFFTS))
+    nb = SP.n_bins(n_fft)
+    hop = int(rng.choice([1, 3, 48, n_fft // 2, n_fft, n_fft + 5, int(rng.integers(1, 3 * n_fft))]))
+    per_bin = int(rng.choice([1, 2, 3, 7, 16, 33, int(rng.integers(1, 50)), 0x7FFFFFFF]))
+    n = int(rng.integers(1, 12))
+    max_rows = int(rng.choice([1, 3, 20, 70]))
+    lens, offsets, at = [], [], int(rng.integers(0, 4))
+    for _ in range(n):
+        r = int(rng.integers(0, max_rows + 1))
+        if r and per_bin < 100 and rng.random() < 0.5:                      # a frame round a whole number of time bins
+            r = max(1, (r // per_bin) * per_bin + int(rng.integers(-1, 2)))
+        ln = int(rng.choice([0, n_fft - 1, int(rng.integers(0, n_fft))])) if r == 0 else n_fft + (r - 1) * hop + int(rng.choice([0, hop - 1, int(rng.integers(0, hop))]))
+        ln = min(ln, 60_000)
+        offsets.append(at)
+        lens.append(ln)
+        at += int(rng.choice([ln, ln + 1, ln // 2]))     # (rows may overlap: they are only read)
+    cap_s = max(o + l for o, l in zip(offsets, lens)) + int(rng.integers(0, 3))
+    x = rng.integers(-32768, 32768, max(cap_s, 1)).astype(np.int16)
+    if rng.random() < 0.3:
+        x[:] = rng.choice(np.array([-32768, 32767, -129, -128, -1, 0, 127, 128, 255, 256], dtype=np.int16), x.size)
+    if rng.random() < 0.3:
+        cap_s = max(cap_s - int(rng.integers(1, n_fft)), 0)            # the last rows end behind samples_cap
+    if rng.random() < 0.2:
+        offsets[int(rng.integers(0, n))] = [1 << 63, (1 << 64) - 1, cap_s + 1][int(rng.integers(0, 3))]
+    bins = [SL.n_bins_of(SP.n_rows(v, n_fft, hop), per_bin) for v in lens]
+    if rng.random() < 0.5:
+        stride = max(1, max(bins) + int(rng.choice([0, 0, 1, -1])))
+        rows_cap = n * stride + int(rng.integers(0, 3))
+    else:
+        stride = 0
+        rows_cap = max(1, sum(bins) + int(rng.choice([0, 0, 2, -1, -sum(bins) // 2])))
+    n_bands = int(rng.choice([1, 2, 8, nb, int(rng.integers(1, nb + 1))]))
+    bin_band = rng.integers(0, n_bands + int(rng.integers(0, 3)), nb).astype(np.uint32)     # (words of K, K + 1: no band)
+    wild = rng.random(nb) < 0.1
+    bin_band[wild] = rng.choice(np.array([n_bands, 0x7FFFFFFF, 0x80000000, 0xFFFFFFFF], dtype=np.uint32), int(wild.sum()))
+    if rng.random() < 0.2:
+        bin_band[:] = int(rng.integers(0, n_bands))                        # every bin in one band, the others empty
+    plane_stride = int(rng.choice([0, rows_cap, rows_cap + 1, rows_cap + int(rng.integers(0, 40))]))
+    ps = plane_stride or rows_cap
+    kind = int(rng.integers(0, 3))
+    tab = None if kind == 0 else rng.integers(-32768, 32768, (SP.PAIRS, 2)).astype(np.int16)
+    if kind == 2:
+        tab[:] = (32767, 0)                                                # every bin of a loud frame at its clamp
+    mode = int(rng.integers(0, 3))                                       # no in-status, a separate array, in place
+    ins = None if mode == 0 else [int(rng.choice([0, 0, 0, 14, 21, 24])) for _ in range(n)]
+    null_off = bool(stride) and rng.random() < 0.3
+    sizes = (32 * ((n_bands - 1) * ps + rows_cap), 8 * (n + 1), 4 * n)    # (the last plane ends at its rows_cap)
+    d = [ctx.alloc(v) for v in sizes] + [ctx.alloc(max(2 * x.size, 2)), ctx.alloc(8 * n), ctx.alloc(4 * n), ctx.alloc(4 * n),
+                                         ctx.alloc(4 * SP.PAIRS), ctx.alloc(4 * nb)]
+    d_out, d_ro, d_st, d_x, d_off, d_len, d_in, d_tab, d_map = d
+    try:
+        for q, v in zip(d[:3], sizes):
+            ctx.upload(q, np.full(v, 0x5A, dtype=np.uint8))
+        ctx.upload(d_x, x)
+        ctx.upload(d_off, np.array(offsets, dtype=np.uint64))
+        ctx.upload(d_len, np.array(lens, dtype=np.uint32))
+        ctx.upload(d_tab, SP.table() if tab is None else tab)
+        ctx.upload(d_map, bin_band)
+        if ins is not None:
+            ctx.upload(d_st if mode == 2 else d_in, np.array(ins, dtype=np.int32))
+        rule = x3hip.SpectraRule(n_fft, hop, SP.POWER, 0, d_tab)
+        fold = x3hip.SpectraFold(per_bin, n_bands, plane_stride, d_map, 0)
+        rc = ctx.spectra_levels_dev(d_x, cap_s, d_off, d_len, None if ins is None else (d_st if mode == 2 else d_in), n, rule, fold,
+                                    stride, d_out, rows_cap, None if null_off else d_ro, d_st)
+        C.memset(C.byref(rule), 0xEE, C.sizeof(rule))
+        C.memset(C.byref(fold), 0xEE, C.sizeof(fold))
+        assert rc == 0, (tag, rc, ctx.last_error())
+        res = ctx.spectra_result()
+        want = SL.spectra_levels(x[:cap_s], offsets, lens, ins, n_fft, hop, per_bin, bin_band, n_bands, stride, rows_cap, plane_stride, tab)
+        got = ctx.download(d_out, sizes[0])
+        assert got.tobytes() == want[0].tobytes()[:sizes[0]], (tag, "records", n_fft, hop, per_bin, n_bands, stride, rows_cap, plane_stride)
+        off = ctx.download(d_ro, sizes[1], np.uint64)
+        assert (off.view(np.uint8) == 0x5A).all() if null_off else np.array_equal(off, want[1]), (tag, "row offsets")
+        st = ctx.download(d_st, sizes[2], np.int32)
+        assert np.array_equal(st, want[2]), (tag, "statuses", st, want[2])
+        bad = np.flatnonzero(st)
+        assert res == (0, bad.size, int(bad[0]) if bad.size else n, int(st[bad[0]]) if bad.size else 0, want[3]), (tag, res)
+    finally:
+        for q in d:
+            ctx.free(q)
+
+
+fams["z"] = fam_z
 
 
 def run(seed=1, minutes=None, trials=None, families="egdbaf", only=-1, context=None):

@@ -132,8 +132,9 @@ def spectra_case(src, a, results, info, case, ent, starts, lens):
     torch.cuda.empty_cache()
 
 
-def cases(src, a, results, info):
-    """tools/range_levels_bench.py's three cases: its 1 024 ranges, its 10 s range, the slots of its events call"""
+def cases(src, a, results, info, spectra_case=spectra_case):
+    """tools/range_levels_bench.py's three cases: its 1 024 ranges, its 10 s range, the slots of its events call
+    (spectra_case: what runs on each; tools/band_levels_bench.py brings its own)"""
     rng = np.random.default_rng(11)
     ms, ns = src.rate // 1000, src.n_samples
     ent, starts, lens = [], [], []

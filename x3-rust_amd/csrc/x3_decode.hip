@@ -14,6 +14,7 @@
 #include "x3_quantiles_kernel.h"
 #include "x3_range_levels_kernel.h"
 #include "x3_spectra_kernel.h"
+#include "x3_spectra_levels_kernel.h"
 
 // ------------------------------------------------------------------------------------------------
 // decode
@@ -2982,7 +2983,7 @@ static_assert(sizeof(x3_spectra_rule) == 24 && offsetof(x3_spectra_rule, hop) ==
 // The workspace (SpecWs, x3_internal.h): per range the scan of the rows, the rows that are transformed and those that have
 // room; the B operand of the rule's n_fft -- 2 * KT tiles of N / 64 steps, two planes of 64 lanes x 16 bytes each -- and its
 // column sums; the summary
-size_t spectra_carve(char* base, uint64_t n, uint32_t n_fft, SpecWs* w) {
+size_t spectra_carve(char* base, uint64_t n, uint32_t n_fft, SpecWs* w, bool frames) {
   BlockCarver k{base, 0};
   const uint64_t tiles = 2ull * ((n_fft / 2 + 1 + 15) / 16);
   w->row_off = k.take<unsigned long long>(n + 1);
@@ -2990,40 +2991,56 @@ size_t spectra_carve(char* base, uint64_t n, uint32_t n_fft, SpecWs* w) {
   w->wr = k.take<uint32_t>(n);
   w->basis = k.take<uint4>(tiles * (n_fft / 64) * 128);
   w->colsum = k.take<int32_t>(tiles * 16);
+  w->frame_off = frames ? k.take<unsigned long long>(n + 1) : nullptr;
   w->sum = k.take<X3WinSummary>(1, 1);
   return k.at;
+}
+
+// what both calls refuse, in the header's order: the rule first, then everything else (d_out: the rows or the records)
+static bool spectra_rule_ok(const x3_spectra_rule* rule) {
+  if (!rule) return false;
+  const uint32_t N = rule->n_fft;
+  return !((N != 64 && N != 128 && N != 256 && N != 512 && N != 1024) || rule->hop == 0 || rule->hop > 0x7FFFFFFFu ||
+           (rule->format != X3_SPECTRA_SUMS && rule->format != X3_SPECTRA_POWER) || rule->reserved || !rule->d_table ||
+           (reinterpret_cast<uintptr_t>(rule->d_table) & 3u));
+}
+
+static bool spectra_args_ok(const x3_ctx* c, const int16_t* d_samples, const uint64_t* d_offsets, const uint32_t* d_lens,
+                            const int32_t* d_in_status, uint64_t n_ranges, uint64_t row_stride, const void* d_out,
+                            uint64_t rows_cap, const uint64_t* d_row_offsets, const int32_t* d_status) {
+  if (n_ranges == 0 || n_ranges > 0x7FFFFFFFull || rows_cap == 0 || rows_cap > 0x7FFFFFFFull) return false;
+  if (!d_samples || !d_offsets || !d_lens || !d_out || !d_status || c->capturing) return false;
+  if (row_stride ? row_stride > rows_cap / n_ranges : !d_row_offsets) return false;
+  return !((reinterpret_cast<uintptr_t>(d_samples) & 1u) ||
+           ((reinterpret_cast<uintptr_t>(d_lens) | reinterpret_cast<uintptr_t>(d_in_status) | reinterpret_cast<uintptr_t>(d_status)) & 3u) ||
+           ((reinterpret_cast<uintptr_t>(d_offsets) | reinterpret_cast<uintptr_t>(d_out) | reinterpret_cast<uintptr_t>(d_row_offsets)) & 7u));
+}
+
+static X3SpGeo spectra_geo(const x3_spectra_rule* rule) {
+  X3SpGeo g{};
+  g.N = rule->n_fft;
+  while ((1u << g.lgN) < g.N) ++g.lgN;
+  g.H = rule->hop;
+  g.B = g.N / 2 + 1;
+  g.KT = (g.B + 15) / 16;
+  g.format = rule->format;
+  return g;
 }
 
 extern "C" int x3_spectra_rows_dev(x3_ctx* c, const int16_t* d_samples, uint64_t samples_cap, const uint64_t* d_offsets,
                                    const uint32_t* d_lens, const int32_t* d_in_status, uint64_t n_ranges,
                                    const x3_spectra_rule* rule, uint64_t row_stride, void* d_out, uint64_t rows_cap,
                                    uint64_t* d_row_offsets, int32_t* d_status) {
-  // the rule first
-  if (!c || !rule) return X3_ERR_BAD_ARG;
+  if (!c || !spectra_rule_ok(rule)) return X3_ERR_BAD_ARG;
+  if (!spectra_args_ok(c, d_samples, d_offsets, d_lens, d_in_status, n_ranges, row_stride, d_out, rows_cap, d_row_offsets, d_status))
+    return X3_ERR_BAD_ARG;
   const uint32_t N = rule->n_fft;
-  if ((N != 64 && N != 128 && N != 256 && N != 512 && N != 1024) || rule->hop == 0 || rule->hop > 0x7FFFFFFFu ||
-      (rule->format != X3_SPECTRA_SUMS && rule->format != X3_SPECTRA_POWER) || rule->reserved || !rule->d_table ||
-      (reinterpret_cast<uintptr_t>(rule->d_table) & 3u))
-    return X3_ERR_BAD_ARG;
-  if (n_ranges == 0 || n_ranges > 0x7FFFFFFFull || rows_cap == 0 || rows_cap > 0x7FFFFFFFull) return X3_ERR_BAD_ARG;
-  if (!d_samples || !d_offsets || !d_lens || !d_out || !d_status || c->capturing) return X3_ERR_BAD_ARG;
-  if (row_stride ? row_stride > rows_cap / n_ranges : !d_row_offsets) return X3_ERR_BAD_ARG;
-  if ((reinterpret_cast<uintptr_t>(d_samples) & 1u) ||
-      ((reinterpret_cast<uintptr_t>(d_lens) | reinterpret_cast<uintptr_t>(d_in_status) | reinterpret_cast<uintptr_t>(d_status)) & 3u) ||
-      ((reinterpret_cast<uintptr_t>(d_offsets) | reinterpret_cast<uintptr_t>(d_out) | reinterpret_cast<uintptr_t>(d_row_offsets)) & 7u))
-    return X3_ERR_BAD_ARG;
   HIPCHK(c, hipSetDevice(c->device));
   SpecWs w;
   int rc;
   if ((rc = ensure(c, c->spec_ws, spectra_carve(nullptr, n_ranges, N, &w)))) return rc;
   spectra_carve((char*)c->spec_ws.p, n_ranges, N, &w);
-  X3SpGeo g{};
-  g.N = N;
-  while ((1u << g.lgN) < N) ++g.lgN;
-  g.H = rule->hop;
-  g.B = N / 2 + 1;
-  g.KT = (g.B + 15) / 16;
-  g.format = rule->format;
+  const X3SpGeo g = spectra_geo(rule);
   hipLaunchKernelGGL(x3_spectra_plan_kernel, dim3(1), dim3(1024), 0, c->stream, d_offsets, d_lens, d_in_status, n_ranges,
                      samples_cap, g, row_stride, rows_cap, w.row_off, w.live, w.wr, d_row_offsets, d_status, w.sum);
   hipLaunchKernelGGL(x3_spectra_basis_kernel, dim3(grid_for(2ull * g.KT * (N / 64) * 64, 256)), dim3(256), 0, c->stream,
@@ -3040,6 +3057,64 @@ extern "C" int x3_spectra_rows_dev(x3_ctx* c, const int16_t* d_samples, uint64_t
   };
   if (N <= 512) transform(x3_spectra_transform_kernel<2>, 2);   // (two row tiles share a load of the B operand; LDS: 33 KB at most)
   else transform(x3_spectra_transform_kernel<1>, 1);
+  HIPCHK(c, hipGetLastError());
+  c->spectra.pending = true;
+  c->spectra.count = n_ranges;
+  c->spectra.sum_off = (size_t)((char*)w.sum - (char*)c->spec_ws.p);
+  return X3_OK;
+}
+
+// band levels (x3_spectra_levels_kernel.h): the rows call's pending slot and workspace, its basis kernel
+// as it is, a plan, an init and a transform of its own
+static_assert(sizeof(x3_spectra_fold) == 32 && offsetof(x3_spectra_fold, n_bands) == 4 && offsetof(x3_spectra_fold, plane_stride) == 8 &&
+                  offsetof(x3_spectra_fold, d_bin_band) == 16 && offsetof(x3_spectra_fold, reserved) == 24,
+              "include/x3hip.h states this layout");
+
+extern "C" int x3_spectra_levels_dev(x3_ctx* c, const int16_t* d_samples, uint64_t samples_cap, const uint64_t* d_offsets,
+                                     const uint32_t* d_lens, const int32_t* d_in_status, uint64_t n_ranges,
+                                     const x3_spectra_rule* rule, const x3_spectra_fold* fold, uint64_t row_stride,
+                                     x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status) {
+  if (!c || !spectra_rule_ok(rule) || rule->format != X3_SPECTRA_POWER) return X3_ERR_BAD_ARG;
+  const uint32_t N = rule->n_fft, B = N / 2 + 1;
+  if (!fold || fold->frames_per_bin == 0 || fold->frames_per_bin > 0x7FFFFFFFu || fold->n_bands == 0 || fold->n_bands > B ||
+      !fold->d_bin_band || (reinterpret_cast<uintptr_t>(fold->d_bin_band) & 3u) || fold->reserved ||
+      (fold->plane_stride && fold->plane_stride < rows_cap))
+    return X3_ERR_BAD_ARG;
+  // (K <= 513: the product cannot wrap below plane strides of 2^54, and above 2^31 it fails the test either way)
+  if (std::max(fold->plane_stride, rows_cap) > 0x7FFFFFFFull / fold->n_bands) return X3_ERR_BAD_ARG;
+  if (!spectra_args_ok(c, d_samples, d_offsets, d_lens, d_in_status, n_ranges, row_stride, d_levels, rows_cap, d_row_offsets, d_status))
+    return X3_ERR_BAD_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  SpecWs w;
+  int rc;
+  if ((rc = ensure(c, c->spec_ws, spectra_carve(nullptr, n_ranges, N, &w, true)))) return rc;
+  spectra_carve((char*)c->spec_ws.p, n_ranges, N, &w, true);
+  const X3SpGeo g = spectra_geo(rule);
+  const X3SpFold fd{fold->frames_per_bin, fold->n_bands, fold->plane_stride ? fold->plane_stride : rows_cap};
+  // LDS: the planes and 16 * MT * K accumulators of 8 bytes -- 99 584 bytes at n_fft 512 and 98 944 at 1 024 with K = B, past the
+  // 64 KB a kernel gets unasked: the limit is raised before anything is enqueued
+  const uint32_t row_tiles = N <= 512 ? 2u : 1u;   // (as the rows call: two row tiles share a load of the B operand)
+  const size_t lds = 2u * 16u * (size_t)row_tiles * (N + 16u) + 16u * (size_t)row_tiles * fd.K * 8u;
+  const void* const kernel = row_tiles == 2u ? reinterpret_cast<const void*>(x3_spectra_levels_transform_kernel<2>)
+                                             : reinterpret_cast<const void*>(x3_spectra_levels_transform_kernel<1>);
+  if (lds > 65536u) HIPCHK(c, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(x3_spectra_levels_plan_kernel, dim3(1), dim3(1024), 0, c->stream, d_offsets, d_lens, d_in_status, n_ranges,
+                     samples_cap, g, fd.M, row_stride, rows_cap, w.row_off, w.frame_off, w.live, w.wr, d_row_offsets, d_status, w.sum);
+  hipLaunchKernelGGL(x3_spectra_basis_kernel, dim3(grid_for(2ull * g.KT * (N / 64) * 64, 256)), dim3(256), 0, c->stream,
+                     rule->d_table, g, w.basis, w.colsum);
+  const uint64_t rows_hint = row_stride ? n_ranges * row_stride : rows_cap;
+  hipLaunchKernelGGL(x3_spectra_levels_init_kernel, dim3(grid_for(rows_hint, 256), std::min<uint32_t>(fd.K, 16u)), dim3(256), 0,
+                     c->stream, (const unsigned long long*)w.row_off, n_ranges, row_stride, rows_cap, fd, d_levels);
+  // (the frames are counted on the device, at most frames_per_bin for each of the rows the caller's buffer holds: the surplus
+  //  workgroups, 4 096 at most, read frame_off[n], find no tile of theirs and end)
+  const uint64_t frames_hint = rows_hint * (uint64_t)fd.M;   // (below 2^62)
+  auto transform = [&](auto* k) {
+    hipLaunchKernelGGL(k, dim3(grid_for(frames_hint, 16u * row_tiles)), dim3(256), lds, c->stream, d_samples, d_offsets, n_ranges, g,
+                       fd, row_stride, (const unsigned long long*)w.row_off, (const unsigned long long*)w.frame_off,
+                       (const uint4*)w.basis, (const int32_t*)w.colsum, fold->d_bin_band, d_levels);
+  };
+  if (row_tiles == 2u) transform(x3_spectra_levels_transform_kernel<2>);
+  else transform(x3_spectra_levels_transform_kernel<1>);
   HIPCHK(c, hipGetLastError());
   c->spectra.pending = true;
   c->spectra.count = n_ranges;

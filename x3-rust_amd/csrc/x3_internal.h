@@ -157,7 +157,7 @@ struct x3_ctx {
   DevBuf ev_ws;    // x3_events_dev / x3_corpus_events_dev: row flags, tile totals, run tables, piece scan, summary, row prefix (x3_events_kernel.h)
   DevBuf q_ws;     // x3_level_quantiles_dev / x3_level_thresholds_dev and their corpus forms: (key, entry) per row, histograms, select state, summary, row prefix (x3_quantiles_kernel.h)
   DevBuf rlev_ws;  // x3_range_levels_dev / x3_corpus_range_levels_dev: plans, scans, verdicts, pairs, their partial rows, replay scratch, summary (x3_range_levels_kernel.h)
-  DevBuf spec_ws;  // x3_spectra_rows_dev: the scan of the rows, the rows transformed and written, the B operand and its column sums, summary (x3_spectra_kernel.h)
+  DevBuf spec_ws;  // x3_spectra_rows_dev / x3_spectra_levels_dev: the scan of the rows, the rows transformed and written, the B operand and its column sums, summary (x3_spectra_kernel.h)
   DevBuf win_ws;   // x3_decode_windows_dev: plans, scans, per-frame verdicts, replay scratch, summary (x3_decode_window_kernel.h)
   // x3_decode_streams_dev (x3_streams_kernel.h): the call's block (the segmented walk's workspace and the call's own words:
   // streams_carve, x3_decode.hip), the int16 rows of a float32 call, an entry the general walk takes (aligned copy, int16 row)
@@ -195,7 +195,7 @@ struct x3_ctx {
   PendingCall events;      // x3_events_dev / x3_corpus_events_dev: ev_ws (count: the call's cap)
   PendingCall quantiles;   // the quantiles and thresholds calls: q_ws (count: the entries)
   PendingCall range_levels;   // x3_range_levels_dev / x3_corpus_range_levels_dev: rlev_ws (count: the ranges)
-  PendingCall spectra;        // x3_spectra_rows_dev: spec_ws (count: the ranges)
+  PendingCall spectra;        // x3_spectra_rows_dev / x3_spectra_levels_dev: spec_ws (count: the ranges)
   bool force_two_pass = false;
   // Contexts that encode concurrently on ONE GPU (the file pipeline's workers) share this gate: the single-pass encoders
   // are persistent grids whose workgroups wait for each other, so only one of them may be in flight on a device.  A
@@ -514,13 +514,15 @@ struct QWs {
   X3QSummary* sum; unsigned long long* row_first;
 };
 X3_INTERNAL size_t quantiles_carve(char* base, uint64_t n_rows, uint64_t n_ent, uint32_t n_q, QWs* w);
-// ... and of a spectra call (spec_ws; x3_spectra_kernel.h): n ranges, the B operand of n_fft
+// ... and of a spectra call (spec_ws; x3_spectra_kernel.h): n ranges, the B operand of n_fft; frames: the levels call's scan
+// of the frames as well (x3_spectra_levels_kernel.h)
 struct SpecWs {
   unsigned long long* row_off; uint32_t* live; uint32_t* wr;   // per range (row_off: n + 1 words)
   uint4* basis; int32_t* colsum;                               // per (tile, step, plane, lane); per column
+  unsigned long long* frame_off;                               // per range, n + 1 words (x3_spectra_levels_dev only)
   X3WinSummary* sum;
 };
-X3_INTERNAL size_t spectra_carve(char* base, uint64_t n, uint32_t n_fft, SpecWs* w);
+X3_INTERNAL size_t spectra_carve(char* base, uint64_t n, uint32_t n_fft, SpecWs* w, bool frames = false);
 // ---- x3_files.hip (x3_reader.h)
 // the RIFF/WAVE header parser of x3_wav_to_x3a on an open file, for the sanitised host tests (tests/host_cpp/fuzz_host_parsers.cpp)
 X3_INTERNAL int x3_wav_parse_fd_for_tests(int fd, uint64_t file_len, uint32_t* sample_rate, uint16_t* channels, uint16_t* bits,

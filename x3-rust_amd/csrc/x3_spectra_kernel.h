@@ -24,6 +24,10 @@
 //                                 layout and the rows of a range with a status are stored as zeros by the same epilogue,
 //                                 and a tile without a live row skips the staging and the matrix work.
 //
+// x3_spectra_levels_kernel.h (band levels, x3_spectra_levels_dev) takes from here the basis kernel as it is, x3sp_plan -- the
+// plan kernel's body, with what a range takes in the output as a parameter -- x3sp_power, and x3sp_transform_tiles, the
+// transform's tile loop with the row lookup and the epilogue's store as parameters.
+//
 // OPERAND LAYOUT (v_mfma_i32_16x16x64_i8): lane l holds A[row l & 15][16 bytes of K, group l >> 4] and
 // B[the same 16 of K][column l & 15]; D[row 4 * (l >> 4) + j][column l & 15] in slot j.  A and B take their K from the same
 // positions n = 64 * s + 16 * (l >> 4) + byte, so the order of K inside a step cannot matter.
@@ -54,17 +58,19 @@ __device__ __forceinline__ uint32_t x3sp_rows(uint32_t len, uint32_t N, uint32_t
 
 // ---- plan: one workgroup.  live[w]: the rows of range w that are transformed (0 for a range with a status); wr[w]: the
 // rows of a packed range that are this call's to write (0: no room).  in_status may be status (in place): a thread reads
-// its range's word before it writes it.
-__global__ void __launch_bounds__(1024)
-x3_spectra_plan_kernel(const uint64_t* __restrict__ offsets, const uint32_t* __restrict__ lens, const int32_t* in_status,
-                       uint64_t n, uint64_t samples_cap, X3SpGeo g, uint64_t stride, uint64_t rows_cap,
-                       unsigned long long* __restrict__ row_off, uint32_t* __restrict__ live, uint32_t* __restrict__ wr,
-                       uint64_t* __restrict__ out_off, int32_t* status, X3WinSummary* __restrict__ sum) {
-  __shared__ unsigned long long s[1024];
+// its range's word before it writes it.  x3sp_plan is the body of both plan kernels: items(R) is what the range's R frames
+// take in the output -- R rows here, ceil(R / M) time bins in x3_spectra_levels_kernel.h -- and the scan, the fits rule, the
+// statuses, the offsets and the summary run on that; live[w] stays the frames.  s: 1 024 words of LDS.
+template <class Items>
+__device__ __forceinline__ void x3sp_plan(const uint64_t* __restrict__ offsets, const uint32_t* __restrict__ lens,
+                                          const int32_t* in_status, uint64_t n, uint64_t samples_cap, const X3SpGeo& g,
+                                          uint64_t stride, uint64_t rows_cap, unsigned long long* __restrict__ row_off,
+                                          uint32_t* __restrict__ live, uint32_t* __restrict__ wr, uint64_t* __restrict__ out_off,
+                                          int32_t* status, X3WinSummary* __restrict__ sum, unsigned long long* s, Items items) {
   unsigned long long bad = 0, first = ~0ull;
-  unsigned long long R = 0;
+  unsigned long long F = 0, R = 0;   // the range's frames, and its rows in the output
   const unsigned long long total = x3w_scan_items(
-      n, s, [&](uint64_t w) { return R = x3sp_rows(lens[w], g.N, g.H); },
+      n, s, [&](uint64_t w) { return R = items(F = x3sp_rows(lens[w], g.N, g.H)); },
       [&](uint64_t w, unsigned long long run) {
         const bool fits = stride ? R <= stride : (run <= rows_cap && R <= rows_cap - run);
         const uint64_t off = offsets[w], len = lens[w];
@@ -74,7 +80,7 @@ x3_spectra_plan_kernel(const uint64_t* __restrict__ offsets, const uint32_t* __r
         status[w] = st;
         row_off[w] = run;
         if (out_off) out_off[w] = stride ? w * stride : run;
-        live[w] = st == X3D_OK ? (uint32_t)R : 0u;
+        live[w] = st == X3D_OK ? (uint32_t)F : 0u;
         wr[w] = fits ? (uint32_t)R : 0u;
         if (st != X3D_OK) {
           ++bad;
@@ -99,6 +105,16 @@ x3_spectra_plan_kernel(const uint64_t* __restrict__ offsets, const uint32_t* __r
     sum->replays = 0;
     sum->total = total;
   }
+}
+
+__global__ void __launch_bounds__(1024)
+x3_spectra_plan_kernel(const uint64_t* __restrict__ offsets, const uint32_t* __restrict__ lens, const int32_t* in_status,
+                       uint64_t n, uint64_t samples_cap, X3SpGeo g, uint64_t stride, uint64_t rows_cap,
+                       unsigned long long* __restrict__ row_off, uint32_t* __restrict__ live, uint32_t* __restrict__ wr,
+                       uint64_t* __restrict__ out_off, int32_t* status, X3WinSummary* __restrict__ sum) {
+  __shared__ unsigned long long s[1024];
+  x3sp_plan(offsets, lens, in_status, n, samples_cap, g, stride, rows_cap, row_off, live, wr, out_off, status, sum, s,
+            [](unsigned long long R) { return R; });
 }
 
 // ---- basis: a lane per (tile T, step s, operand lane l): its 16 bytes of either plane; the first 32 * KT lanes also sum
@@ -156,6 +172,8 @@ __device__ __forceinline__ uint32_t x3sp_power(int64_t re, int64_t im, uint32_t 
 
 // LDS: the rows' samples as two int8 planes, a row RS = N + 16 bytes apart (16 rows of one operand read then hit 16
 // different 16-byte slots of the banks); dynamic, 2 * 16 * MT * RS bytes.
+// THE TILE LOOP BELOW HAS A TWIN: x3sp_transform_tiles, behind this kernel, is the same loop with the row lookup and the
+// store as parameters (the band levels' kernels run it).  A change to the staging, the sums or the K loop is made in both.
 template <int MT>
 __global__ void __launch_bounds__(256)
 x3_spectra_transform_kernel(const int16_t* __restrict__ samples, const uint64_t* __restrict__ offsets, uint64_t n, X3SpGeo g,
@@ -300,5 +318,136 @@ x3_spectra_transform_kernel(const int16_t* __restrict__ samples, const uint64_t*
         }
       }
     }
+  }
+}
+
+// x3sp_transform_tiles: the tile loop above -- the tiles grid-stride, the staging, the frames' own sums, the K loop and the
+// int64 sums of every (row, bin) -- with what a row is and what becomes of a bin as parameters, for the kernels that do not
+// store a row per frame (x3_spectra_levels_kernel.h):
+//   rows(f, &src) -> the flags of flat row f < n_flat and, for a live one, the sample position of its frame (called by
+//                    thread f mod ROWS);
+//   sink.word(tile, row, k, flags, re, im) takes bin k < B of a row that has X3SP_ROW_WRITE (re = im = 0 unless it is live);
+//   sink.tile_done(tile) runs once behind a tile's last word, by every thread.
+// s_src, s_flags: ROWS words of LDS each.  x3_spectra_transform_kernel keeps its own text: instantiated through this
+// template the compiler orders its prologue differently (seven instructions more), and the rows call's kernels stay what
+// they were, instruction for instruction.
+template <int MT, class Rows, class Sink>
+__device__ __forceinline__ void x3sp_transform_tiles(const int16_t* __restrict__ samples, const X3SpGeo g, uint64_t n_flat,
+                                                     const uint4* __restrict__ basis, const int32_t* __restrict__ colsum,
+                                                     uint8_t* planes, uint64_t* s_src, uint32_t* s_flags, Rows rows, Sink sink) {
+  constexpr uint32_t ROWS = 16u * MT;
+  const uint32_t RS = g.N + 16u, S = g.N >> 6;
+  uint8_t* const plane_h = planes;
+  uint8_t* const plane_l = planes + (size_t)ROWS * RS;
+  const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+  const uint32_t lc = lane & 15u, lg = lane >> 4;
+  const uint64_t n_tiles = (n_flat + ROWS - 1u) / ROWS;
+  for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    __syncthreads();   // (the tile before is read out of LDS)
+    uint32_t flags = 0;
+    if (t < ROWS) {
+      const uint64_t f = tile * ROWS + t;
+      uint64_t src = 0;
+      if (f < n_flat) flags = rows(f, src);
+      s_src[t] = src;
+      s_flags[t] = flags;
+    }
+    const int any_live = __syncthreads_or((int)(flags & X3SP_ROW_LIVE));
+    x3sp_v4i sx[MT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) sx[m] = x3sp_v4i{0, 0, 0, 0};
+    if (any_live) {
+      // staging: 16 threads a row, four samples a thread and step; a row without a frame holds zeros
+#pragma unroll
+      for (int m = 0; m < MT; ++m) {
+        const uint32_t row = (uint32_t)m * 16u + (t >> 4);
+        const bool lv = (s_flags[row] & X3SP_ROW_LIVE) != 0u;
+        const int16_t* const x = samples + s_src[row];
+        for (uint32_t q = t & 15u; q < (g.N >> 2); q += 16u) {
+          uint32_t h = 0, lo = 0;
+          if (lv) {
+#pragma unroll
+            for (uint32_t j = 0; j < 4u; ++j) {
+              const uint32_t v = (uint16_t)x[4u * q + j];
+              h |= (v >> 8) << (8u * j);
+              lo |= ((v & 0xFFu) ^ 0x80u) << (8u * j);
+            }
+          }
+          *reinterpret_cast<uint32_t*>(plane_h + (size_t)row * RS + 4u * q) = h;
+          *reinterpret_cast<uint32_t*>(plane_l + (size_t)row * RS + 4u * q) = lo;
+        }
+      }
+      __syncthreads();
+      // sX of the lane's four frames per row tile: the two planes against ones
+      const x3sp_v4i ones = x3sp_v4i{0x01010101, 0x01010101, 0x01010101, 0x01010101};
+#pragma unroll
+      for (int m = 0; m < MT; ++m) {
+        x3sp_v4i sh = x3sp_v4i{0, 0, 0, 0}, sl = x3sp_v4i{0, 0, 0, 0};
+        const size_t at = (size_t)((uint32_t)m * 16u + lc) * RS + 16u * lg;
+        for (uint32_t s = 0; s < S; ++s) {
+          sh = x3sp_mfma(*reinterpret_cast<const x3sp_v4i*>(plane_h + at + 64u * s), ones, sh);
+          sl = x3sp_mfma(*reinterpret_cast<const x3sp_v4i*>(plane_l + at + 64u * s), ones, sl);
+        }
+        sx[m] = sh * 256 + sl;
+      }
+    }
+    for (uint32_t tp = wave; tp < g.KT; tp += 4u) {
+      x3sp_v4i acc[MT][2][4];   // [row tile][cos, sin][hh, hl, lh, ll]
+#pragma unroll
+      for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+#pragma unroll
+          for (int c = 0; c < 4; ++c) acc[m][p][c] = x3sp_v4i{0, 0, 0, 0};
+      if (any_live) {
+        const uint4* const bt = basis + (size_t)(2u * tp) * S * 128u + lane;   // (tile 2 * tp; the sin tile S * 128 behind it)
+        for (uint32_t s = 0; s < S; ++s) {
+          x3sp_v4i b[2][2];   // [cos, sin][ch, cl]
+#pragma unroll
+          for (int p = 0; p < 2; ++p)
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+              const uint4 v = bt[((size_t)p * S + s) * 128u + (size_t)q * 64u];
+              b[p][q] = x3sp_v4i{(int)v.x, (int)v.y, (int)v.z, (int)v.w};
+            }
+#pragma unroll
+          for (int m = 0; m < MT; ++m) {
+            const size_t at = (size_t)((uint32_t)m * 16u + lc) * RS + 16u * lg + 64u * s;
+            const x3sp_v4i ah = *reinterpret_cast<const x3sp_v4i*>(plane_h + at);
+            const x3sp_v4i al = *reinterpret_cast<const x3sp_v4i*>(plane_l + at);
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+              acc[m][p][0] = x3sp_mfma(ah, b[p][0], acc[m][p][0]);
+              acc[m][p][1] = x3sp_mfma(ah, b[p][1], acc[m][p][1]);
+              acc[m][p][2] = x3sp_mfma(al, b[p][0], acc[m][p][2]);
+              acc[m][p][3] = x3sp_mfma(al, b[p][1], acc[m][p][3]);
+            }
+          }
+        }
+      }
+      // epilogue: slot j of the lane is (row 4 * lg + j of the row tile, bin 16 * tp + lc) in the cos and the sin tile
+      const uint32_t k = tp * 16u + lc;
+      if (k < g.B) {
+        const int64_t fix_re = 128ll * colsum[(2u * tp) * 16u + lc] + 16384ll * g.N;
+        const int64_t fix_im = 128ll * colsum[(2u * tp + 1u) * 16u + lc] + 16384ll * g.N;
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const uint32_t row = (uint32_t)m * 16u + 4u * lg + (uint32_t)j;
+            const uint32_t fl = s_flags[row];
+            if (!(fl & X3SP_ROW_WRITE)) continue;
+            int64_t re = 0, im = 0;
+            if (fl & X3SP_ROW_LIVE) {
+              const int64_t fx = 128ll * sx[m][j];
+              re = 65536ll * acc[m][0][0][j] + 256ll * ((int64_t)acc[m][0][1][j] + acc[m][0][2][j]) + acc[m][0][3][j] + fx + fix_re;
+              im = 65536ll * acc[m][1][0][j] + 256ll * ((int64_t)acc[m][1][1][j] + acc[m][1][2][j]) + acc[m][1][3][j] + fx + fix_im;
+            }
+            sink.word(tile, row, k, fl, re, im);
+          }
+        }
+      }
+    }
+    sink.tile_done(tile);
   }
 }

@@ -1104,16 +1104,53 @@ inline X3Error spectra_rows(Context& ctx, const int16_t* d_samples, uint64_t sam
   if (res) *res = q;
   return static_cast<X3Error>(rc);
 }
+// The fold of spectra_levels (x3_spectra_fold): frames_per_bin consecutive frames make a time bin, bin k of a frame goes to
+// band d_bin_band[k] (a device array of rule.bins() uint32 words; a word >= n_bands: no band), plane b of the records lies
+// plane_stride records behind plane b - 1 (0: rows_cap).  time_bins(rows) = the time bins of a range of `rows` frames.
+struct SpectraFold {
+  uint32_t frames_per_bin = 1, n_bands = 1;
+  uint64_t plane_stride = 0;
+  const uint32_t* d_bin_band = nullptr;
+  uint64_t time_bins(uint64_t rows) const { return frames_per_bin ? (rows + frames_per_bin - 1) / frames_per_bin : 0; }
+  x3_spectra_fold c_fold() const {
+    x3_spectra_fold f{};
+    f.frames_per_bin = frames_per_bin, f.n_bands = n_bands, f.plane_stride = plane_stride, f.d_bin_band = d_bin_band;
+    return f;
+  }
+};
+// Band levels (x3_spectra_levels_dev): spectra_rows' POWER words (rule.power must be true) folded into fold.n_bands bands and
+// summed over fold.frames_per_bin consecutive frames, one x3_level per (time bin, band) and no row per frame: n = the frames,
+// sum_sq = the sum of their band powers (each clamped to 2^30), max = -min = the loudest frame's peak.  The rows of a range
+// are its time bins, laid as spectra_rows lays its rows; plane b is band b, at d_levels + b * plane_stride.  Every record the
+// call owns is written, the identity where no frame falls.  Waits for the call: res as spectra_rows, total_rows = all time bins.
+inline X3Error spectra_levels(Context& ctx, const int16_t* d_samples, uint64_t samples_cap, const uint64_t* d_offsets,
+                              const uint32_t* d_lens, const int32_t* d_in_status, uint64_t n_ranges, const SpectraRule& rule,
+                              const SpectraFold& fold, uint64_t row_stride, x3_level* d_levels, uint64_t rows_cap,
+                              uint64_t* d_row_offsets, int32_t* d_status, SpectraResult* res) {
+  const x3_spectra_rule r = rule.c_rule();
+  const x3_spectra_fold f = fold.c_fold();
+  int rc = x3_spectra_levels_dev(ctx.raw(), d_samples, samples_cap, d_offsets, d_lens, d_in_status, n_ranges, &r, &f, row_stride,
+                                 d_levels, rows_cap, d_row_offsets, d_status);
+  if (rc != X3_OK) return static_cast<X3Error>(rc);
+  SpectraResult q;
+  rc = x3_spectra_result(ctx.raw(), &q.n_bad, &q.first_bad, &q.first_bad_status, &q.total_rows);
+  if (res) *res = q;
+  return static_cast<X3Error>(rc);
+}
 namespace detail {
-// the ranges call (packed int16) has been enqueued with rc: the spectra call behind it on the same stream, in place on its
-// statuses, no wait in between; then both results
+// the ranges call (packed int16) has been enqueued with rc: the spectra call -- the levels call when there is a fold, d_out
+// then being its records -- behind it on the same stream, in place on its statuses, no wait in between; then both results
 inline X3Error spectra_behind_ranges(Context& ctx, int rc, int16_t* d_samples, uint64_t samples_cap, const uint64_t* d_sample_offsets,
                                      const uint32_t* d_lens, uint64_t n_ranges, const SpectraRule& rule, uint64_t row_stride,
-                                     void* d_out, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status, SpectraResult* res) {
+                                     void* d_out, uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status, SpectraResult* res,
+                                     const SpectraFold* fold = nullptr) {
   if (rc != X3_OK) return static_cast<X3Error>(rc);
   const x3_spectra_rule r = rule.c_rule();
-  const int rc2 = x3_spectra_rows_dev(ctx.raw(), d_samples, samples_cap, d_sample_offsets, d_lens, d_status, n_ranges, &r, row_stride,
-                                      d_out, rows_cap, d_row_offsets, d_status);
+  const x3_spectra_fold f = fold ? fold->c_fold() : x3_spectra_fold{};
+  const int rc2 = fold ? x3_spectra_levels_dev(ctx.raw(), d_samples, samples_cap, d_sample_offsets, d_lens, d_status, n_ranges, &r, &f,
+                                               row_stride, static_cast<x3_level*>(d_out), rows_cap, d_row_offsets, d_status)
+                       : x3_spectra_rows_dev(ctx.raw(), d_samples, samples_cap, d_sample_offsets, d_lens, d_status, n_ranges, &r,
+                                             row_stride, d_out, rows_cap, d_row_offsets, d_status);
   RangesResult rr;
   rc = x3_decode_ranges_result(ctx.raw(), &rr.n_bad, &rr.first_bad, &rr.first_bad_status, &rr.total_samples);
   if (rc2 != X3_OK) return static_cast<X3Error>(rc2);
@@ -1139,6 +1176,22 @@ inline X3Error range_spectra(Context& ctx, const EncodedStream& s, const Paramet
                                       0, d_samples, samples_cap, X3_WINDOW_I16, d_sample_row_offsets, d_status);
   return detail::spectra_behind_ranges(ctx, rc, d_samples, samples_cap, d_sample_row_offsets, d_lens, n_ranges, rule, row_stride,
                                        d_out, rows_cap, d_row_offsets, d_status, res);
+}
+// Range band levels: range_spectra with spectra_levels in the place of spectra_rows -- the records of the ranges' time bins
+// and bands in d_levels, fold.n_bands planes.  (The whole-stream loop over chunks of ranges is the Python mirror's only.)
+inline X3Error range_band_levels(Context& ctx, const EncodedStream& s, const Parameters& params, const Buffer& d_sample_offsets,
+                                 const uint64_t* d_starts, const uint32_t* d_lens, size_t n_ranges, const SpectraRule& rule,
+                                 const SpectraFold& fold, int16_t* d_samples, uint64_t samples_cap, uint64_t* d_sample_row_offsets,
+                                 uint64_t row_stride, x3_level* d_levels, uint64_t rows_cap, uint64_t* d_row_offsets,
+                                 int32_t* d_status, SpectraResult* res) {
+  if (!s.bytes.ok() || !s.frame_offsets.ok() || !d_sample_offsets.ok()) return X3Error::BadArg;
+  const x3_params c = params.c_params();
+  const int rc = x3_decode_ranges_dev(ctx.raw(), s.bytes.as<uint8_t>(), s.len, s.frame_offsets.as<uint64_t>(),
+                                      d_sample_offsets.as<uint64_t>(), s.n_frames, &c,
+                                      s.seg_blocks ? s.seg_index.as<uint64_t>() : nullptr, s.seg_blocks, d_starts, d_lens, n_ranges,
+                                      0, d_samples, samples_cap, X3_WINDOW_I16, d_sample_row_offsets, d_status);
+  return detail::spectra_behind_ranges(ctx, rc, d_samples, samples_cap, d_sample_row_offsets, d_lens, n_ranges, rule, row_stride,
+                                       d_levels, rows_cap, d_row_offsets, d_status, res, &fold);
 }
 
 // A batch of independent streams (x3_decode_streams_dev): entry s = bytes [offsets[s], offsets[s] + lengths[s]) of d_x3 (flags:
@@ -1232,6 +1285,16 @@ class Corpus {
                                         X3_WINDOW_I16, d_sample_row_offsets, d_status);
     return detail::spectra_behind_ranges(ctx, rc, d_samples, samples_cap, d_sample_row_offsets, d_lens, n_ranges, rule, row_stride,
                                          d_out, rows_cap, d_row_offsets, d_status, res);
+  }
+  // Range band levels of entries: ranges (packed int16) and device::spectra_levels behind it, as device::range_band_levels.
+  X3Error range_band_levels(Context& ctx, const uint32_t* d_entries, const uint64_t* d_starts, const uint32_t* d_lens,
+                            uint64_t n_ranges, const SpectraRule& rule, const SpectraFold& fold, int16_t* d_samples,
+                            uint64_t samples_cap, uint64_t* d_sample_row_offsets, uint64_t row_stride, x3_level* d_levels,
+                            uint64_t rows_cap, uint64_t* d_row_offsets, int32_t* d_status, SpectraResult* res) const {
+    const int rc = x3_corpus_ranges_dev(ctx.raw(), raw_, d_entries, d_starts, d_lens, n_ranges, 0, d_samples, samples_cap,
+                                        X3_WINDOW_I16, d_sample_row_offsets, d_status);
+    return detail::spectra_behind_ranges(ctx, rc, d_samples, samples_cap, d_sample_row_offsets, d_lens, n_ranges, rule, row_stride,
+                                         d_levels, rows_cap, d_row_offsets, d_status, res, &fold);
   }
   // Levels of every entry (x3_corpus_levels_dev): entry e's records are [row_first[e], row_first[e + 1]) of d_levels, positions
   // relative to the entry; levels_rows(bin_len) is that prefix, d_levels holds its last word of records.  Waits for the call.

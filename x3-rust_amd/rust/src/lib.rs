@@ -170,6 +170,18 @@ pub mod ffi {
         pub reserved: u32,
         pub d_table: *const i16,
     }
+    /// `x3_spectra_fold`: how `x3_spectra_levels_dev` folds the POWER words -- `frames_per_bin` consecutive frames into a time
+    /// bin, bin k of a frame into band `d_bin_band[k]` (a device array of `n_fft / 2 + 1` u32 words, a word >= `n_bands`: no
+    /// band), plane b of the records `b * plane_stride` records in (0: `rows_cap`) (32 bytes)
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug)]
+    pub struct x3_spectra_fold {
+        pub frames_per_bin: u32,
+        pub n_bands: u32,
+        pub plane_stride: u64,
+        pub d_bin_band: *const u32,
+        pub reserved: u64,
+    }
     #[repr(C)]
     #[derive(Clone, Copy, Debug)]
     pub struct x3_rice_code {
@@ -400,6 +412,10 @@ pub mod ffi {
                                    d_lens: *const u32, d_in_status: *const i32, n_ranges: u64, rule: *const x3_spectra_rule,
                                    row_stride: u64, d_out: *mut c_void, rows_cap: u64, d_row_offsets: *mut u64,
                                    d_status: *mut i32) -> c_int;
+        pub fn x3_spectra_levels_dev(ctx: *mut x3_ctx, d_samples: *const i16, samples_cap: u64, d_offsets: *const u64,
+                                     d_lens: *const u32, d_in_status: *const i32, n_ranges: u64, rule: *const x3_spectra_rule,
+                                     fold: *const x3_spectra_fold, row_stride: u64, d_levels: *mut x3_level, rows_cap: u64,
+                                     d_row_offsets: *mut u64, d_status: *mut i32) -> c_int;
         pub fn x3_spectra_result(ctx: *mut x3_ctx, n_bad: *mut u64, first_bad: *mut u64, first_bad_status: *mut c_int,
                                  total_rows: *mut u64) -> c_int;
         pub fn x3_corpus_destroy(corpus: *mut x3_corpus);
@@ -2085,6 +2101,101 @@ pub mod device {
             ffi::x3_spectra_rows_dev(gpu.raw(), d_samples.as_ptr::<i16>(), samples_cap, d_sample_row_offsets.as_ptr::<u64>(),
                                      d_lens.as_ptr::<u32>(), d_status.as_ptr::<i32>(), n_ranges as u64, &r, row_stride,
                                      d_out.as_ptr::<c_void>(), rows_cap, off, d_status.as_ptr::<i32>())
+        };
+        let (mut n_bad, mut first_bad, mut st, mut total) = (0u64, 0u64, 0, 0u64);
+        error::check(unsafe { ffi::x3_decode_ranges_result(gpu.raw(), &mut n_bad, &mut first_bad, &mut st, &mut total) })?;
+        error::check(rc)?;
+        error::check(unsafe { ffi::x3_spectra_result(gpu.raw(), &mut n_bad, &mut first_bad, &mut st, &mut total) })?;
+        Ok((n_bad, first_bad, st, total))
+    }
+
+    /// The fold of `spectra_levels` / `range_band_levels` (`x3_spectra_fold`): `frames_per_bin` in 1 ..= 2^31 - 1 consecutive
+    /// frames make a time bin, `n_bands` in 1 ..= `n_fft / 2 + 1` bands, `bin_band` a device array of `n_fft / 2 + 1` u32 words
+    /// (the band of every bin; a word >= `n_bands`: no band), `plane_stride` records between two planes (0: `rows_cap`)
+    #[derive(Clone, Copy)]
+    pub struct SpectraFold<'t, 'g> {
+        pub frames_per_bin: u32,
+        pub n_bands: u32,
+        pub plane_stride: u64,
+        pub bin_band: &'t Buffer<'g>,
+    }
+
+    impl<'t, 'g> SpectraFold<'t, 'g> {
+        /// time bins of a range of `rows` frames
+        pub fn time_bins(&self, rows: u64) -> u64 {
+            if self.frames_per_bin == 0 { 0 } else { (rows + self.frames_per_bin as u64 - 1) / self.frames_per_bin as u64 }
+        }
+        /// bytes of the records: `n_bands` planes, the last one `rows_cap` records long
+        pub fn level_bytes(&self, rows_cap: u64) -> u64 {
+            let ps = if self.plane_stride == 0 { rows_cap } else { self.plane_stride };
+            32 * ((self.n_bands as u64).saturating_sub(1) * ps + rows_cap)
+        }
+        fn c(&self, rule: &SpectraRule<'_, 'g>) -> error::Result<ffi::x3_spectra_fold> {
+            if self.bin_band.len() < 4 * rule.bins() || !rule.power { return Err(X3Error::BadArg); }
+            Ok(ffi::x3_spectra_fold { frames_per_bin: self.frames_per_bin, n_bands: self.n_bands, plane_stride: self.plane_stride,
+                                      d_bin_band: self.bin_band.as_ptr::<u32>() as *const u32, reserved: 0 })
+        }
+    }
+
+    /// Band levels (`x3_spectra_levels_dev`; not in the reference crate): `spectra_rows`' POWER words (`rule.power`) folded
+    /// into `fold.n_bands` bands and summed over `fold.frames_per_bin` consecutive frames, one `x3_level` per (time bin, band)
+    /// and no row per frame.  The rows of a range are its time bins, laid as `spectra_rows` lays its rows; plane b is band b at
+    /// `b * plane_stride` records of `d_levels`; every record the call owns is written, the identity where no frame falls.
+    /// Waits: -> (ranges with status != 0, the first of them, its status, all time bins)
+    #[allow(clippy::too_many_arguments)]
+    pub fn spectra_levels<'g>(gpu: &'g Gpu, d_samples: &Buffer<'g>, samples_cap: u64, d_offsets: &Buffer<'g>, d_lens: &Buffer<'g>,
+                              d_in_status: Option<&Buffer<'g>>, n_ranges: usize, rule: &SpectraRule<'_, 'g>,
+                              fold: &SpectraFold<'_, 'g>, row_stride: u64, d_levels: &mut Buffer<'g>, rows_cap: u64,
+                              d_row_offsets: Option<&mut Buffer<'g>>, d_status: &mut Buffer<'g>) -> error::Result<(u64, u64, i32, u64)> {
+        let r = rule.c()?;
+        let f = fold.c(rule)?;
+        if (d_samples.len() as u64) < 2 * samples_cap || d_offsets.len() < 8 * n_ranges || d_lens.len() < 4 * n_ranges
+            || (d_levels.len() as u64) < fold.level_bytes(rows_cap) || d_status.len() < 4 * n_ranges
+            || d_in_status.map_or(false, |b| b.len() < 4 * n_ranges)
+            || d_row_offsets.as_ref().map_or(false, |b| b.len() < 8 * (n_ranges + 1)) {
+            return Err(X3Error::BadArg);
+        }
+        let ins = d_in_status.map_or(core::ptr::null(), |b| b.as_ptr::<i32>() as *const i32);
+        let off = d_row_offsets.map_or(core::ptr::null_mut(), |b| b.as_ptr::<u64>());
+        error::check(unsafe {
+            ffi::x3_spectra_levels_dev(gpu.raw(), d_samples.as_ptr::<i16>(), samples_cap, d_offsets.as_ptr::<u64>(),
+                                       d_lens.as_ptr::<u32>(), ins, n_ranges as u64, &r, &f, row_stride,
+                                       d_levels.as_ptr::<ffi::x3_level>(), rows_cap, off, d_status.as_ptr::<i32>())
+        })?;
+        let (mut n_bad, mut first_bad, mut st, mut total) = (0u64, 0u64, 0, 0u64);
+        error::check(unsafe { ffi::x3_spectra_result(gpu.raw(), &mut n_bad, &mut first_bad, &mut st, &mut total) })?;
+        Ok((n_bad, first_bad, st, total))
+    }
+
+    /// Range band levels: `range_spectra` with `x3_spectra_levels_dev` in the place of `x3_spectra_rows_dev`.  (The whole-stream
+    /// loop over chunks of ranges, `band_levels`, is the Python mirror's only.)  Waits for both: -> as `spectra_levels`
+    #[allow(clippy::too_many_arguments)]
+    pub fn range_band_levels<'g>(gpu: &'g Gpu, s: &EncodedStream<'g>, params: &x3::Parameters, sample_offsets: &Buffer<'g>,
+                                 d_starts: &Buffer<'g>, d_lens: &Buffer<'g>, n_ranges: usize, rule: &SpectraRule<'_, 'g>,
+                                 fold: &SpectraFold<'_, 'g>, d_samples: &mut Buffer<'g>, samples_cap: u64,
+                                 d_sample_row_offsets: &mut Buffer<'g>, row_stride: u64, d_levels: &mut Buffer<'g>, rows_cap: u64,
+                                 d_row_offsets: Option<&mut Buffer<'g>>, d_status: &mut Buffer<'g>) -> error::Result<(u64, u64, i32, u64)> {
+        let r = rule.c()?;
+        let f = fold.c(rule)?;
+        if d_starts.len() < 8 * n_ranges || d_lens.len() < 4 * n_ranges || (d_samples.len() as u64) < 2 * samples_cap
+            || d_sample_row_offsets.len() < 8 * (n_ranges + 1) || (d_levels.len() as u64) < fold.level_bytes(rows_cap)
+            || d_status.len() < 4 * n_ranges || d_row_offsets.as_ref().map_or(false, |b| b.len() < 8 * (n_ranges + 1)) {
+            return Err(X3Error::BadArg);
+        }
+        let p = params.c()?;
+        let idx = match &s.seg_index { Some(i) => i.as_ptr::<u64>() as *const u64, None => core::ptr::null() };
+        let off = d_row_offsets.map_or(core::ptr::null_mut(), |b| b.as_ptr::<u64>());
+        error::check(unsafe {
+            ffi::x3_decode_ranges_dev(gpu.raw(), s.bytes.as_ptr::<u8>(), s.len as u64, s.frame_offsets.as_ptr::<u64>(),
+                                      sample_offsets.as_ptr::<u64>(), s.n_frames as u64, &p, idx, s.seg_blocks,
+                                      d_starts.as_ptr::<u64>(), d_lens.as_ptr::<u32>(), n_ranges as u64, 0,
+                                      d_samples.as_ptr::<c_void>(), samples_cap, WINDOW_I16, d_sample_row_offsets.as_ptr::<u64>(),
+                                      d_status.as_ptr::<i32>())
+        })?;
+        let rc = unsafe {
+            ffi::x3_spectra_levels_dev(gpu.raw(), d_samples.as_ptr::<i16>(), samples_cap, d_sample_row_offsets.as_ptr::<u64>(),
+                                       d_lens.as_ptr::<u32>(), d_status.as_ptr::<i32>(), n_ranges as u64, &r, &f, row_stride,
+                                       d_levels.as_ptr::<ffi::x3_level>(), rows_cap, off, d_status.as_ptr::<i32>())
         };
         let (mut n_bad, mut first_bad, mut st, mut total) = (0u64, 0u64, 0, 0u64);
         error::check(unsafe { ffi::x3_decode_ranges_result(gpu.raw(), &mut n_bad, &mut first_bad, &mut st, &mut total) })?;

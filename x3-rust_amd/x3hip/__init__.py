@@ -74,7 +74,7 @@ SYMBOLS = [
     "x3_fir_range_levels_dev", "x3_corpus_fir_range_levels_dev",
     "x3_tone_range_levels_dev", "x3_corpus_tone_range_levels_dev",
     "x3_tone_bank_range_levels_dev", "x3_corpus_tone_bank_range_levels_dev",
-    "x3_spectra_rows_dev", "x3_spectra_result",
+    "x3_spectra_rows_dev", "x3_spectra_result", "x3_spectra_levels_dev",
     "x3_tune_candidate", "x3_tuner_create", "x3_tuner_add_dev", "x3_tuner_result", "x3_tuner_max_payloads",
     "x3_tuner_reset", "x3_tuner_destroy", "x3_tune", "x3_x3a_encode_tuned",
 ]
@@ -157,6 +157,61 @@ class SpectraRule(C.Structure):
     SPECTRA_POWER, reserved 0; d_table is a device pointer to a tone table (24 bytes, copied at the call)"""
     _fields_ = [("n_fft", C.c_uint32), ("hop", C.c_uint32), ("format", C.c_uint32), ("reserved", C.c_uint32),
                 ("d_table", C.c_void_p)]
+
+
+class SpectraFold(C.Structure):
+    """x3_spectra_fold: how x3_spectra_levels_dev folds the POWER words -- frames_per_bin consecutive frames into a time bin,
+    the bins k of a frame into band d_bin_band[k] (a device pointer to n_fft / 2 + 1 uint32 words; a word >= n_bands: no
+    band), plane b of the records at b * plane_stride records (0: rows_cap), reserved 0 (32 bytes, copied at the call)"""
+    _fields_ = [("frames_per_bin", C.c_uint32), ("n_bands", C.c_uint32), ("plane_stride", C.c_uint64),
+                ("d_bin_band", C.c_void_p), ("reserved", C.c_uint64)]
+
+
+def band_edges_third_octave(n_fft, sample_rate, f_lo, f_hi):
+    """The bin edges of the third-octave bands (base two: centre frequencies 1 000 * 2^(i / 3) Hz, a band from
+    fc * 2^(-1/6) to fc * 2^(1/6)) whose centres lie in [f_lo, f_hi], for range_band_levels(bands=...) -> a list of K + 1
+    ascending ints: band b holds the bins [edges[b], edges[b + 1]) of n_fft / 2 + 1, bin k at k * sample_rate / n_fft Hz
+    and counted to the band that holds its centre frequency.  A band narrower than a bin holds no bin; a ValueError when
+    no centre lies in the interval or below sample_rate / 2."""
+    import math
+    nb, df = n_fft // 2 + 1, float(sample_rate) / n_fft
+    if not 0 < f_lo <= f_hi:
+        raise ValueError("0 < f_lo <= f_hi")
+    i0, i1 = math.ceil(3 * math.log2(f_lo / 1000.0) - 1e-9), math.floor(3 * math.log2(f_hi / 1000.0) + 1e-9)
+    cuts = [1000.0 * 2.0 ** ((2 * i - 1) / 6.0) for i in range(i0, i1 + 2)]    # lower edge of band i; the last: the upper of i1
+    edges = [min(nb, max(0, math.ceil(c / df - 1e-9))) for c in cuts]
+    while len(edges) > 1 and edges[-2] >= nb:                                  # (bands wholly above the last bin)
+        edges.pop()
+    if len(edges) < 2:
+        raise ValueError("no third-octave centre in [f_lo, f_hi] below sample_rate / 2")
+    return edges
+
+
+def spectra_bin_band(n_fft, bands):
+    """bands of range_band_levels -> (bin_band np.uint32 [n_fft / 2 + 1], K).  None: one band per bin.  A torch tensor or
+    numpy array of exactly n_fft / 2 + 1 integers: the band of every bin as it is (any word, as the library takes them),
+    K = the largest index below n_fft / 2 + 1, plus one.  Any other sequence: K + 1 ascending bin edges, band b the bins
+    [edges[b], edges[b + 1]), every other bin in no band."""
+    nb = n_fft // 2 + 1
+    if bands is None:
+        return np.arange(nb, dtype=np.uint32), nb
+    is_array = hasattr(bands, "cpu") or isinstance(bands, np.ndarray)
+    a = np.asarray(bands.cpu().numpy() if hasattr(bands, "cpu") else bands)
+    if a.ndim != 1 or a.dtype.kind not in "iu":
+        raise ValueError("bands: K + 1 ascending bin edges, or an array of n_fft / 2 + 1 band indices")
+    if is_array and a.size == nb:
+        m = a.astype(np.int64) & 0xFFFFFFFF
+        inside = m[m < nb]
+        if inside.size == 0:
+            raise ValueError("bands: no bin in any band")
+        return m.astype(np.uint32), int(inside.max()) + 1
+    e = a.astype(np.int64)
+    if e.size < 2 or e.size - 1 > nb or (np.diff(e) < 0).any() or e[0] < 0 or e[-1] > nb:
+        raise ValueError("bands: K + 1 ascending bin edges in 0 .. n_fft / 2 + 1, K in 1 .. n_fft / 2 + 1")
+    m = np.full(nb, 0xFFFFFFFF, dtype=np.uint32)
+    for b in range(e.size - 1):
+        m[e[b]:e[b + 1]] = b
+    return m, e.size - 1
 
 
 def spectra_n_rows(length, n_fft, hop):
@@ -514,6 +569,8 @@ def lib():
                                                        C.POINTER(LevelToneBank)]
     L.x3_range_levels_result.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(i32), C.POINTER(u64)]
     L.x3_spectra_rows_dev.argtypes = [vp, vp, u64, vp, vp, vp, u64, C.POINTER(SpectraRule), u64, vp, u64, vp, vp]
+    L.x3_spectra_levels_dev.argtypes = [vp, vp, u64, vp, vp, vp, u64, C.POINTER(SpectraRule), C.POINTER(SpectraFold), u64, vp, u64,
+                                        vp, vp]
     L.x3_spectra_result.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(i32), C.POINTER(u64)]
     L.x3_corpus_destroy.restype = None
     L.x3_synth.argtypes = [i32, u64, u64, u64, vp]
@@ -1512,8 +1569,19 @@ class Context:
                                          C.byref(rule) if rule is not None else None, row_stride, d_out, rows_cap,
                                          d_row_offsets, d_status)
 
+    def spectra_levels_dev(self, d_samples, samples_cap, d_offsets, d_lens, d_in_status, n_ranges, rule, fold, row_stride,
+                           d_levels, rows_cap, d_row_offsets, d_status):
+        """x3_spectra_levels_dev: spectra_rows_dev's POWER words (rule: a SpectraRule with SPECTRA_POWER) folded by fold (a
+        SpectraFold; None: NULL, which the library refuses) into bands and time bins of frames_per_bin frames, as n_bands
+        planes of x3_level records at d_levels + b * plane_stride records; the rows are the time bins, laid as
+        spectra_rows_dev lays its rows; asynchronous, spectra_result waits (total_rows: the time bins)"""
+        return lib().x3_spectra_levels_dev(self._h, d_samples, samples_cap, d_offsets, d_lens, d_in_status, n_ranges,
+                                           C.byref(rule) if rule is not None else None,
+                                           C.byref(fold) if fold is not None else None, row_stride, d_levels, rows_cap,
+                                           d_row_offsets, d_status)
+
     def spectra_result(self):
-        """-> (rc, n_bad, first_bad, first_bad_status, total_rows) of the last spectra_rows_dev"""
+        """-> (rc, n_bad, first_bad, first_bad_status, total_rows) of the last spectra_rows_dev / spectra_levels_dev"""
         nb, fb, st, tot = C.c_uint64(0), C.c_uint64(0), C.c_int32(0), C.c_uint64(0)
         rc = lib().x3_spectra_result(self._h, C.byref(nb), C.byref(fb), C.byref(st), C.byref(tot))
         return rc, nb.value, fb.value, st.value, tot.value
@@ -1645,18 +1713,41 @@ def _ranges_torch(ctx, enqueue, what, starts, lens, padded_to, capacity, dtype, 
     return out[:cap] if padded_to is None else out, offsets, status
 
 
+class _BandFold:
+    """What the range_band_levels forms hand to _range_spectra_torch: frames_per_bin and bands as the caller gave them; and,
+    WindowSource.band_levels' only, `into` = (planes uint8 [K, R, 32] on the device, first row) -- the records go to rows
+    [first row, first row + capacity) of those planes, plane stride R -- and `device_map` = (the int32 tensor of the band map on
+    the device, K) in the place of bands"""
+    __slots__ = ("frames_per_bin", "bands", "into", "device_map")
+
+    def __init__(self, frames_per_bin, bands, into=None, device_map=None):
+        self.frames_per_bin, self.bands, self.into, self.device_map = int(frames_per_bin), bands, into, device_map
+
+
 def _range_spectra_torch(ctx, enqueue, what, starts, lens, n_fft, hop, power, table, padded_to, capacity, sample_capacity,
-                         entries=None):
+                         entries=None, fold=None):
     """The torch side of WindowSource.range_spectra / Corpus.range_spectra: the ranges call (packed int16) and the spectra
     call behind it on the context's stream, no wait and no host trip in between -> (spectra, row_offsets, status, samples,
     sample_offsets) device tensors.  enqueue(d_entries, d_starts, d_lens, n, rule, d_samples, samples_cap, d_sample_offsets,
-    stride, d_out, rows_cap, d_row_offsets, d_status) -> (rc of the ranges call, rc of the spectra call or None)."""
+    stride, d_out, rows_cap, d_row_offsets, d_status, fold=None) -> (rc of the ranges call, rc of the spectra call or None).
+    fold (the range_band_levels forms): a _BandFold -- the rows are time bins of fold.frames_per_bin frames, the output is
+    levels uint8 [K, rows, 32], enqueue gets the SpectraFold made from it as `fold`, and -> (levels, row_offsets, status)."""
     import torch
     dev = torch.device("cuda", torch.cuda.current_device())
     n_fft = int(n_fft)
     hop = n_fft if hop is None else int(hop)
     if n_fft not in SPECTRA_NFFTS or not 1 <= hop <= 0x7FFFFFFF:
         raise ValueError("n_fft: one of %s; hop: 1 .. 2^31 - 1" % (SPECTRA_NFFTS,))
+    per_bin = 1
+    if fold is not None:
+        per_bin = fold.frames_per_bin
+        if not 1 <= per_bin <= 0x7FFFFFFF:
+            raise ValueError("frames_per_bin: 1 .. 2^31 - 1")
+        if fold.device_map is not None:
+            bin_band, n_bands = fold.device_map  # (band_levels: the map is on the device already, with its K)
+        else:
+            m, n_bands = spectra_bin_band(n_fft, fold.bands)
+            bin_band = torch.from_numpy(m.view(np.int32)).to(dev)
 
     def on_dev(a, dt):   # (as in _ranges_torch: unsigned words travel as the signed tensors of the same bits)
         signed = {np.uint64: torch.int64, np.uint32: torch.int32}[dt]
@@ -1687,7 +1778,7 @@ def _range_spectra_torch(ctx, enqueue, what, starts, lens, n_fft, hop, power, ta
         if samples_cap is None:
             samples_cap = int(ln.sum())
         if rows_cap is None:
-            rows_cap = int(np.where(ln < n_fft, 0, (ln - n_fft) // hop + 1).sum())
+            rows_cap = int((-(-np.where(ln < n_fft, 0, (ln - n_fft) // hop + 1) // per_bin)).sum())
     if table is None:
         d_table = ctx.tone_table_dev()
     else:
@@ -1701,35 +1792,56 @@ def _range_spectra_torch(ctx, enqueue, what, starts, lens, n_fft, hop, power, ta
     rule = SpectraRule(n_fft, hop, SPECTRA_POWER if power else SPECTRA_SUMS, 0, d_table)
     samples = torch.empty(max(samples_cap, 1), dtype=torch.int16, device=dev)
     sample_offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
-    spectra = torch.empty((max(rows_cap, 1), nb) if power else (max(rows_cap, 1), nb, 2),
-                          dtype=torch.int32 if power else torch.int64, device=dev)
+    spectra = None if fold is not None else torch.empty((max(rows_cap, 1), nb) if power else (max(rows_cap, 1), nb, 2),
+                                                        dtype=torch.int32 if power else torch.int64, device=dev)
     row_offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
     status = torch.empty(n, dtype=torch.int32, device=dev)
+    c_fold = None
+    if fold is not None:
+        if fold.into is None:
+            spectra = torch.empty((n_bands, max(rows_cap, 1), 32), dtype=torch.uint8, device=dev)
+            d_out, plane_stride = spectra.data_ptr(), 0
+        else:
+            planes, first = fold.into
+            if (planes.dtype != torch.uint8 or planes.dim() != 3 or planes.shape[0] != n_bands or planes.shape[2] != 32
+                    or not planes.is_contiguous() or not 0 <= first <= planes.shape[1] - max(rows_cap, 1)):
+                raise ValueError("into: contiguous uint8 planes [K, R, 32] with first + capacity <= R")
+            spectra = planes
+            d_out, plane_stride = planes.data_ptr() + 32 * first, planes.shape[1]
+        c_fold = SpectraFold(per_bin, n_bands, plane_stride, bin_band.data_ptr(), 0)
+    else:
+        d_out = spectra.data_ptr()
     torch.cuda.current_stream().synchronize()    # (the context's stream is not torch's: the inputs are ready from here)
     rc, rc2 = enqueue(d_ent, starts.data_ptr(), lens.data_ptr(), n, rule, samples.data_ptr(), max(samples_cap, 1),
-                      sample_offsets.data_ptr(), stride, spectra.data_ptr(), max(rows_cap, 1), row_offsets.data_ptr(),
-                      status.data_ptr())
+                      sample_offsets.data_ptr(), stride, d_out, max(rows_cap, 1), row_offsets.data_ptr(),
+                      status.data_ptr(), **({} if c_fold is None else {"fold": c_fold}))
     if rc:
         raise X3Error(rc, what + ": " + ctx.last_error())
     rc = ctx.decode_ranges_result()[0]   # (waits for both: one stream)
     if rc:
         raise X3Error(rc, "x3_decode_ranges_result: " + ctx.last_error())
     if rc2:
-        raise X3Error(rc2, "x3_spectra_rows_dev: " + ctx.last_error())
+        raise X3Error(rc2, ("x3_spectra_rows_dev: " if fold is None else "x3_spectra_levels_dev: ") + ctx.last_error())
     rc = ctx.spectra_result()[0]
     if rc:
         raise X3Error(rc, "x3_spectra_result: " + ctx.last_error())
+    if fold is not None:
+        return (spectra[:, :rows_cap] if fold.into is None else spectra), row_offsets, status
     return spectra[:rows_cap], row_offsets, status, samples[:samples_cap], sample_offsets
 
 
 def _range_spectra_enqueue(ctx, ranges_into):
-    """the enqueue of _range_spectra_torch and the body of the range_spectra_into forms: ranges_into(d_starts-or-entries
-    ..., packed int16) then x3_spectra_rows_dev in place on its statuses"""
+    """the enqueue of _range_spectra_torch and the body of the range_spectra_into / range_band_levels_into forms:
+    ranges_into(d_starts-or-entries ..., packed int16) then x3_spectra_rows_dev -- or, with a SpectraFold as `fold`,
+    x3_spectra_levels_dev -- in place on its statuses"""
     def enqueue(d_ent, d_starts, d_lens, n, rule, d_samples, samples_cap, d_sample_offsets, stride, d_out, rows_cap, d_row_offsets,
-                d_status):
+                d_status, fold=None):
         rc = ranges_into(d_ent, d_starts, d_lens, n, 0, d_samples, samples_cap, WINDOW_I16, d_sample_offsets, d_status)
         if rc:
             return rc, None
+        if fold is not None:          # the range_band_levels forms
+            return 0, ctx.spectra_levels_dev(d_samples, samples_cap, d_sample_offsets, d_lens, d_status, n, rule, fold, stride,
+                                             d_out, rows_cap, d_row_offsets, d_status)
         return 0, ctx.spectra_rows_dev(d_samples, samples_cap, d_sample_offsets, d_lens, d_status, n, rule, stride, d_out, rows_cap,
                                        d_row_offsets, d_status)
     return enqueue
@@ -2168,6 +2280,77 @@ class WindowSource(_Detection):
                                     "x3_decode_ranges_dev", starts, lens, n_fft, hop, power, table, padded_to, capacity,
                                     sample_capacity)
 
+    def range_band_levels_into(self, d_starts, d_lens, n, rule, fold, d_samples, samples_cap, d_sample_offsets, row_stride,
+                               d_levels, rows_cap, d_row_offsets, d_status):
+        """range_spectra_into with Context.spectra_levels_dev behind the ranges call: rule a SpectraRule with SPECTRA_POWER,
+        fold a SpectraFold, d_levels n_bands planes of x3_level records -> (rc of the ranges call, rc of the levels call or
+        None); decode_ranges_result and spectra_result wait"""
+        return _range_spectra_enqueue(self.ctx, lambda e, *a: self.ranges_into(*a))(
+            None, d_starts, d_lens, n, rule, d_samples, samples_cap, d_sample_offsets, row_stride, d_levels, rows_cap,
+            d_row_offsets, d_status, fold=fold)
+
+    def range_band_levels(self, starts, lens, n_fft, hop=None, *, frames_per_bin=1, bands=None, table=None, padded_to=None,
+                          capacity=None, sample_capacity=None):
+        """Band levels of the ranges [starts[w], starts[w] + lens[w]): range_spectra's POWER words folded into bands and
+        summed over frames_per_bin consecutive frames, with no row per frame stored (x3_spectra_levels_dev) -> (levels
+        uint8 [K, rows, 32], row_offsets, status) on the device.  Range w's rows are its ceil(R / frames_per_bin) time
+        bins (the last one possibly of fewer frames), in every plane at row_offsets[w] (packed; `capacity` rows when
+        given) or w * padded_to with identity records behind them; plane b is band b.  A record (event_levels_view): n
+        = the frames, sum_sq = the sum of the frames' band powers (each clamped to 2^30), max = -min = the peak of the
+        loudest frame.  bands: None (one band per bin), K + 1 ascending bin edges (band_edges_third_octave gives some),
+        or an array of n_fft / 2 + 1 band indices (spectra_bin_band).  A range with a status has identity records only.
+        The planes go as they are into plane_events (eight at a time), events, level_quantiles and the thresholds."""
+        return self._range_band_levels(starts, lens, n_fft, hop, _BandFold(frames_per_bin, bands), table, padded_to, capacity,
+                                       sample_capacity)
+
+    def _range_band_levels(self, starts, lens, n_fft, hop, fold, table, padded_to, capacity, sample_capacity):
+        """range_band_levels and the chunks of band_levels; fold: a _BandFold"""
+        return _range_spectra_torch(self.ctx, _range_spectra_enqueue(self.ctx, lambda e, *a: self.ranges_into(*a)),
+                                    "x3_decode_ranges_dev", starts, lens, n_fft, hop, True, table, padded_to, capacity,
+                                    sample_capacity, fold=fold)
+
+    def band_levels(self, n_fft, hop=None, *, frames_per_bin, bands=None, table=None, chunk_samples=1 << 26, q=4):
+        """Band levels of the whole stream -> levels uint8 [K, ceil(total / (frames_per_bin * hop)), 32] on the device (one
+        identity row for a stream without a sample, as levels() gives one bin then):
+        row i of plane b covers the positions [i * bin_len, (i + 1) * bin_len) with bin_len = frames_per_bin * hop and
+        holds the frames that START there, n = frames_per_bin of them where they all fit into the stream; the trailing
+        rows without a whole frame are the identity.  The planes go into plane_events(levels, bin_len, ...), events,
+        level_quantiles and the thresholds as they are.
+          Filled by a loop over chunks of ranges, the ranges' samples in a buffer of at most chunk_samples whatever the
+        stream's length, one wait per chunk: range g begins at g * q * bin_len and is (q * frames_per_bin - 1) * hop +
+        n_fft samples long (the last one cut at the stream's end), so it holds exactly the frames of q rows.  A DAMAGED
+        FRAME of the stream therefore costs the q rows of every range that touches it -- they stay the identity -- where
+        levels() loses only the samples of that frame; q is small for that reason.  hop > n_fft skips samples, as in
+        range_spectra."""
+        import torch
+        n_fft = int(n_fft)
+        hop = n_fft if hop is None else int(hop)
+        per_bin, q = int(frames_per_bin), int(q)
+        if n_fft not in SPECTRA_NFFTS or not 1 <= hop <= 0x7FFFFFFF or not 1 <= per_bin <= 0x7FFFFFFF or q < 1:
+            raise ValueError("n_fft: one of %s; hop, frames_per_bin: 1 .. 2^31 - 1; q >= 1" % (SPECTRA_NFFTS,))
+        bin_len = per_bin * hop
+        range_len = (q * per_bin - 1) * hop + n_fft
+        if range_len > 0xFFFFFFFF or range_len > chunk_samples:
+            raise ValueError("a range of q * frames_per_bin frames (%d samples) does not fit chunk_samples" % range_len)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        m, n_bands = spectra_bin_band(n_fft, bands)
+        bin_band = torch.from_numpy(m.view(np.int32)).to(dev)
+        rows = max(1, -(-self.total // bin_len))
+        identity = np.frombuffer(np.array([(0, 0, 32767, -32768, 0, 0)], dtype=LEVEL_DTYPE).tobytes(), dtype=np.uint8).copy()
+        planes = torch.from_numpy(identity).to(dev).expand(n_bands, rows, 32).contiguous()
+        n_ranges = -(-self.total // (q * bin_len))
+        per_chunk = max(1, int(chunk_samples) // range_len)
+        for g0 in range(0, n_ranges, per_chunk):
+            g = np.arange(g0, min(g0 + per_chunk, n_ranges), dtype=np.int64)
+            starts = g * (q * bin_len)
+            lens = np.minimum(range_len, self.total - starts)
+            first = g0 * q
+            cap = min(g.size * q, rows - first)     # (a range's rows: q, the last range's at most that)
+            self._range_band_levels(starts, lens, n_fft, hop, _BandFold(per_bin, None, (planes, first), (bin_band, n_bands)),
+                                    table, None,
+                                    cap, int(lens.sum()))
+        return planes
+
     def range_levels_into(self, d_starts, d_lens, n, bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status,
                           signal=LEVEL_SIGNAL_SAMPLES):
         """enqueue the level records of n ranges (device pointers: d_starts n x u64, d_lens n x u32, d_levels rows_cap x
@@ -2586,6 +2769,20 @@ class Corpus(_Detection):
         """WindowSource.range_spectra on the ranges [starts[w], starts[w] + lens[w]) of entry entries[w]"""
         return _range_spectra_torch(self.ctx, _range_spectra_enqueue(self.ctx, self.ranges_into), "x3_corpus_ranges_dev", starts,
                                     lens, n_fft, hop, power, table, padded_to, capacity, sample_capacity, entries=entries)
+
+    def range_band_levels_into(self, d_entries, d_starts, d_lens, n, rule, fold, d_samples, samples_cap, d_sample_offsets,
+                               row_stride, d_levels, rows_cap, d_row_offsets, d_status):
+        """WindowSource.range_band_levels_into on ranges of entries (d_entries n x u32)"""
+        return _range_spectra_enqueue(self.ctx, self.ranges_into)(
+            d_entries, d_starts, d_lens, n, rule, d_samples, samples_cap, d_sample_offsets, row_stride, d_levels, rows_cap,
+            d_row_offsets, d_status, fold=fold)
+
+    def range_band_levels(self, entries, starts, lens, n_fft, hop=None, *, frames_per_bin=1, bands=None, table=None,
+                          padded_to=None, capacity=None, sample_capacity=None):
+        """WindowSource.range_band_levels on the ranges [starts[w], starts[w] + lens[w]) of entry entries[w]"""
+        return _range_spectra_torch(self.ctx, _range_spectra_enqueue(self.ctx, self.ranges_into), "x3_corpus_ranges_dev", starts,
+                                    lens, n_fft, hop, True, table, padded_to, capacity, sample_capacity, entries=entries,
+                                    fold=_BandFold(frames_per_bin, bands))
 
     def range_levels_into(self, d_entries, d_starts, d_lens, n, bin_len, row_stride, d_levels, rows_cap, d_row_offsets, d_status,
                           signal=LEVEL_SIGNAL_SAMPLES):
