@@ -10,16 +10,21 @@ tile 2 stands at the place that holds byte 2^32 and at the place that holds samp
 than any other tile has) at the last place: an access that wraps modulo 2^32 lands on other content.
 
 Everything a test needs is closed-form in kind[] and the tiles: the bytes of any span, the samples of any span, the frame
-and sample offset tables, and the level records of every bin at any bin length that divides a tile, for the samples and for
-their first difference (seams between places included), at any phase of the bins against the tiles.  Damage is one flipped
-bit in chosen frames; the reference then follows the contract (include/x3hip.h): a failed frame adds nothing to levels,
-takes both of its seams with it in the first difference, and leaves zeros from its first sample on in a window."""
+and sample offset tables, and the level records of every bin at any bin length that divides a tile, for the samples, for
+their first difference and for a FIR-filtered signal (fir(): seams between places included, the history taken from the
+last frame of the tile in front), at any phase of the bins against the tiles.  Damage is one flipped bit in chosen frames;
+the reference then follows the contract (include/x3hip.h): a failed frame adds nothing to levels, takes both of its seams
+with it in the first difference and the T - 1 positions behind it in a FIR signal of T taps, and leaves zeros from its
+first sample on in a window.  Tone records are NOT periodic in the places -- the phase of position i is (i * step) mod
+2^32 -- so tone_records walks the samples of a slice; the whole stream is compared on the device."""
 import numpy as np
 
 import diff_levels_ref as DR
+import fir_levels_ref as FL
 import levels_ref as LR
 import oracle_lib as O
 import ranges_ref as RR
+import tone_levels_ref as TL
 
 SPF, FPT = 10000, 64                  # samples a frame, frames a tile
 TS = SPF * FPT                        # samples a tile
@@ -30,6 +35,49 @@ SAMPLES, DIFF = DR.SAMPLES, DR.DIFF
 BAD_ARG = RR.ERR_BAD_ARG
 LOUD_MEAN_SQ = 600_000_000            # only tile 3 has bins of 10 000 samples above this mean square
 QUIET, ORDINARY, DENSE, LOUD = range(4)
+FIR_HIST = 7                          # X3L_FIR_HIST: a FIR value reaches at most so many samples back
+
+
+def fir(taps, shift=0):
+    """the `signal` of a FIR-filtered signal (fir_levels_ref's contract): hashable, so that it keys the records' cache"""
+    assert FL.check(taps, shift)
+    return ("fir", tuple(int(c) for c in taps), int(shift))
+
+
+# eight taps of mixed signs and a shift: a gain of 323 / 256, so full-scale noise clamps at some positions and not at most
+FIR8 = fir((-12, 50, -90, 70, 30, -40, 25, -6), 8)
+FIR_DIFF = fir((1, -1))               # x[i] - x[i - 1]: DIFF's records wherever both count a position
+
+
+def is_fir(signal):
+    return isinstance(signal, tuple) and signal[0] == "fir"
+
+
+def _signal_levels(frames, st, so, bin_len, n_bins, signal):
+    """the records of the three kinds of signal over frames at sample offsets so"""
+    if is_fir(signal):
+        return FL.fir_levels(frames, st, so, bin_len, n_bins, signal[1], signal[2])
+    return DR.signal_levels(frames, st, so, bin_len, n_bins, signal)
+
+
+def tone_records_of(x, counted, pos0, bin_len, step, tab=None):
+    """the x3_tone_level records of samples x at the absolute positions pos0 .. pos0 + len(x) - 1 (those with counted False add
+    nothing), bins of bin_len counted from pos0, a last one of fewer positions included.  The phase is by absolute position:
+    pair ((i mod 2^32) * step mod 2^32) >> 22, in uint64 whose product stays below 2^64 -- never a wrapped int64 product"""
+    assert 0 <= step <= 0xFFFFFFFF and pos0 >= 0 and bin_len > 0
+    tab = (TL.table() if tab is None else np.asarray(tab, dtype=np.int16).reshape(TL.PAIRS, 2)).astype(np.int64)
+    n = len(x)
+    pos = (np.arange(n, dtype=np.uint64) + np.uint64(pos0 % EDGE)) & np.uint64(EDGE - 1)      # i mod 2^32, exact
+    k = (((pos * np.uint64(step)) & np.uint64(EDGE - 1)) >> np.uint64(22)).astype(np.int64)
+    x = np.asarray(x, dtype=np.int64)
+    out = TL.empty(max(1, -(-n // bin_len)) if n else 0)
+    for j in range(out.size):
+        s = slice(j * bin_len, min((j + 1) * bin_len, n))
+        ok = np.asarray(counted[s], dtype=bool)
+        v, kk = x[s][ok], k[s][ok]
+        if v.size:
+            out[j] = (int(np.sum(v * tab[kk, 0])), int(np.sum(v * tab[kk, 1])), v.min(), v.max(), v.size, 0)
+    return out
 
 
 class Tile:
@@ -213,6 +261,14 @@ class Case:
         fr = pos // SPF
         if signal == SAMPLES:
             return self.samples(g0, g1).astype(np.int64), good[fr]
+        if is_fir(signal):     # (the T positions i - T + 1 .. i lie in at most two frames: T - 1 < SPF)
+            _, taps, shift = signal
+            T = len(taps)
+            x = np.concatenate([np.zeros(T - 1, dtype=np.int64), self.samples(max(g0 - (T - 1), 0), g1).astype(np.int64)])
+            x = x[x.size - (g1 - g0) - (T - 1):]                 # x[j + T - 1 - t] is the sample at position g0 + j - t
+            acc = sum(int(c) * x[T - 1 - t:x.size - t] for t, c in enumerate(taps))
+            ok = (pos >= T - 1) & good[fr] & good[np.maximum(pos - (T - 1), 0) // SPF]
+            return np.clip(acc >> shift, -32768, 32767), ok
         x = self.samples(max(g0 - 1, 0), g1).astype(np.int64)
         if g0 == 0:
             x = np.concatenate([[0], x])
@@ -229,6 +285,13 @@ class Case:
             out["n"], out["sum"], out["sum_sq"] = v.size, v.sum(), np.sum((v * v).astype(np.uint64), dtype=np.uint64)
             out["min"], out["max"] = v.min(), v.max()
         return out
+
+    def tone_records(self, g0, g1, bin_len, step, tab=None):
+        """the x3_tone_level records of positions [g0, g1): bins of bin_len counted from g0 (a last one of fewer positions
+        included), a failed frame adds nothing, the phase by absolute position.  For slices: it walks the samples"""
+        good = np.ones(self.F, dtype=bool)
+        good[np.array(sorted(self.bad), dtype=np.int64)] = False
+        return tone_records_of(self.samples(g0, g1), good[np.arange(g0, g1, dtype=np.int64) // SPF], g0, bin_len, step, tab)
 
     # ---- damage
     def damage(self, frames, where="payload", bit=3):
@@ -274,7 +337,8 @@ class Case:
         shift = (-(lead + phase)) % bin_len                 # the place's sample `phase` falls on a bin boundary
         so = np.concatenate([[0], np.cumsum([len(w) for w in frames])])[:-1] + shift
         b0, nb = (lead + phase + shift) // bin_len, TS // bin_len
-        rec = DR.signal_levels(frames, st, so, bin_len, b0 + nb, signal)[b0:]
+        # (a FIR value reaches FIR_HIST < SPF samples back: the one frame in front carries all the history a place needs)
+        rec = _signal_levels(frames, st, so, bin_len, b0 + nb, signal)[b0:]
         self._cache[key] = rec
         return rec
 

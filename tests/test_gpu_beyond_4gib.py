@@ -7,7 +7,13 @@ encodes, 5.1 GB and 4.43 G samples, with another tile at the place that holds by
 and at the last one.  The reference is closed-form in the tiles (tests/test_big_cases.py proves it on the CPU); what is large
 is compared on the device with torch.equal, what is small is downloaded.  One module-scoped fixture builds the stream; tests
 that damage it flip the bits back.  Peak device memory stays below 40 GB: the large buffers of a test are freed before the
-next one allocates."""
+next one allocates.
+
+Sections E2, E3 and F (the FIR, tone and tone bank forms of the levels, range levels and corpus calls) and S (the spectra
+rows from a sample buffer of more than 2^32 elements and into an output of more than 2^32 words, the band levels into
+planes past byte 2^33 and over the whole stream, plane events on those) came later.  Tone records are not periodic in the
+places, so their reference for the whole stream is built by torch on the device from the virtual signal and itself held to
+the numpy definition at the marked places."""
 import contextlib
 import ctypes as C
 import time
@@ -18,12 +24,19 @@ import pytest
 import big_cases as B
 import diff_levels_ref as DR
 import events_ref as ER
+import fir_levels_ref as FL
+import fir_range_levels_ref as FRL
 import frame_walk_ref as FW
 import levels_ref as LR
 import oracle_lib as O
+import plane_events_ref as PE
 import quantiles_ref as QR
 import ranges_ref as RR
 import seg_index_ref as SR
+import spectra_levels_ref as SL
+import spectra_ref as S
+import tone_levels_ref as TL
+import tone_range_levels_ref as TRL
 
 pytestmark = pytest.mark.gpu
 
@@ -46,6 +59,7 @@ class Big:
         self.stream = self.lay(c)
         self.fo, self.so = self.u64(c.frame_offsets()), self.u64(c.sample_offsets())
         self._virtual = self._seg = None
+        self.refs = {}         # references a later case reuses (device tensors among them): released with the fixture
         self.low_free = torch.cuda.mem_get_info(self.dev)[0]
         torch.cuda.synchronize(self.dev)
         self.build_s = time.perf_counter() - t0
@@ -126,6 +140,7 @@ class Big:
 
     def close(self):
         self.ready()
+        self.refs.clear()
         self.ctx.close()
 
 
@@ -581,6 +596,341 @@ def test_chain_levels_events_ranges(big):
     assert not rows[len(ev):].any()
 
 
+# ------------------------------------------------------------------------------------------------ E2. FIR, tone and bank levels
+
+TONE_STEP = 276168143                     # Tone.at(12 345.678, 192 000)'s step made odd: no period in the places
+BANK_STEPS = (TONE_STEP, 0, 1 << 30, 1 << 31, 0xFFFFFFFF, 1, 3 * 5 * 7 * 11 * 13 * 17 * 19 + 2, 0x9E3779B1)
+M32 = 0xFFFFFFFF
+
+
+def seam_bad(c):
+    """test_levels' damage: three_bad, and a place's last frame with a later place's first one (the seams between tiles)"""
+    m = EDGE // TS
+    return three_bad(c) + [(m, FPT - 1), (m + 3, 0)]
+
+
+def _signal_levels(big, call, arg, bin_len, n_bins, use_seg, planes=1):
+    """one x3_fir_levels_dev / x3_tone_levels_dev / x3_tone_bank_levels_dev (call: the Context's method, arg: its Fir, Tone
+    or Tones) -> (the records on the device uint8 [planes * n_bins, 32], frame statuses, x3_levels_result)"""
+    torch, ctx = big.torch, big.ctx
+    lv = big.full((planes * n_bins, 32), 0x5A, torch.uint8)
+    st = big.full((big.case.F,), -1, torch.int32)
+    seg = big.seg_args(use_seg)
+    big.ready()
+    rc = getattr(ctx, call)(*big.args(), bin_len, lv.data_ptr(), n_bins, st.data_ptr(), *seg, arg)
+    assert rc == 0, ctx.last_error()
+    return lv, st, ctx.levels_result()
+
+
+def _level_records(lv):
+    return lv.cpu().numpy().reshape(-1).view(LR.LEVEL_DTYPE)
+
+
+def _tone_words(lv):
+    """tone records on the device uint8 [..., n, 32] as int64 [..., n, 4]: re, im, (min, max), (n, reserved)"""
+    import torch
+    return lv.view(torch.int64)
+
+
+def _check_result(c, st, res, torch, what):
+    b = sorted(c.bad)
+    assert res == ((0, len(b), b[0], c.bad[b[0]]) if b else (0, 0, c.F, 0)), (what, res)
+    assert torch.nonzero(st).reshape(-1).cpu().tolist() == b, what
+
+
+def _tone_bins(big, good, g0, n_bins, bin_len, steps):
+    """the torch reference of tone records on the device, from the virtual signal: n_bins bins of bin_len positions from g0,
+    for every step -> int64 [len(steps), n_bins, 4] as _tone_words gives them.  good: None, or a bool tensor per frame (a
+    failed frame adds nothing).  All in int64 without a wrap: the pair of position i is (((i mod 2^32) * step) mod 2^32) >> 22
+    with the step split into halves of 16 bits, so that no product exceeds 2^48"""
+    torch = big.torch
+    virt = big.virtual()
+    tab = torch.from_numpy(TL.table().astype(np.int32)).to(big.dev)
+    out = torch.empty((len(steps), n_bins, 4), dtype=torch.int64, device=big.dev)
+    per = max(1, (1 << 25) // bin_len)
+    for b in range(0, n_bins, per):
+        nb = min(per, n_bins - b)
+        a, n = g0 + b * bin_len, nb * bin_len
+        x = virt[a:a + n].to(torch.int32)
+        pos = torch.arange(a, a + n, dtype=torch.int64, device=big.dev)
+        if good is None:
+            mn, mx = x, x
+            cnt = torch.full((nb,), bin_len, dtype=torch.int64, device=big.dev)
+        else:
+            ok = good[pos // SPF]
+            mn, mx = torch.where(ok, x, 32767), torch.where(ok, x, -32768)
+            x = torch.where(ok, x, 0)
+            cnt = ok.view(nb, bin_len).sum(dim=1, dtype=torch.int64)
+        mn, mx = mn.view(nb, bin_len).amin(dim=1).to(torch.int64), mx.view(nb, bin_len).amax(dim=1).to(torch.int64)
+        p = pos & M32
+        del pos
+        for t, step in enumerate(steps):
+            lo, hi = step & 0xFFFF, step >> 16
+            k = (((p * lo) + (((p * hi) & 0xFFFF) << 16)) & M32) >> 22
+            cs = tab[k]
+            out[t, b:b + nb, 0] = (x * cs[:, 0]).view(nb, bin_len).sum(dim=1, dtype=torch.int64)   # (|product| <= 2^30: int32 holds it)
+            out[t, b:b + nb, 1] = (x * cs[:, 1]).view(nb, bin_len).sum(dim=1, dtype=torch.int64)
+            out[t, b:b + nb, 2] = (mn & M32) | (mx << 32)
+            out[t, b:b + nb, 3] = cnt
+            del k, cs
+    return out
+
+
+def _good_frames(big, c):
+    good = big.torch.ones(c.F, dtype=big.torch.bool, device=big.dev)
+    for f in c.bad:
+        good[f] = False
+    return good
+
+
+def _tone_ref(big, c, g0, n_bins, bin_len, steps):
+    """_tone_bins of the clean stream, computed once for (g0, n_bins, bin_len, steps); for a damaged case the bins that a
+    failed frame touches are computed again with the mask -> a tensor the caller must not write to"""
+    key = (g0, n_bins, bin_len, tuple(steps))
+    key = ("tone",) + key
+    if key not in big.refs:
+        big.refs[key] = _tone_bins(big, None, g0, n_bins, bin_len, steps)
+    ref = big.refs[key]
+    if c.bad:
+        ref = ref.clone()
+        good = _good_frames(big, c)
+        for f in sorted(c.bad):
+            j0, j1 = (f * SPF - g0) // bin_len, ((f + 1) * SPF - 1 - g0) // bin_len
+            j0, j1 = max(j0, 0), min(j1, n_bins - 1)
+            if j0 <= j1:
+                ref[:, j0:j1 + 1] = _tone_bins(big, good, g0 + j0 * bin_len, j1 - j0 + 1, bin_len, steps)
+    return ref
+
+
+def _fold(big, ref, k):
+    """the records of bins k times as long, from reference records [T, n, 4] with n a multiple of k"""
+    torch = big.torch
+    T, n, _ = ref.shape
+    r = ref.view(T, n // k, k, 4)
+    mn = (r[..., 2] << 32 >> 32).amin(dim=2)
+    mx = (r[..., 2] >> 32).amax(dim=2)
+    return torch.stack([r[..., 0].sum(dim=2), r[..., 1].sum(dim=2), (mn & M32) | (mx << 32), r[..., 3].sum(dim=2)], dim=2)
+
+
+def _same_words(torch, got, want, what):
+    if not torch.equal(got, want):
+        d = torch.nonzero((got != want).any(dim=-1)).reshape(-1)
+        i = int(d[0])
+        raise AssertionError((what, "records differ: %d, the first at %d" % (d.numel(), i), got[i].tolist(), want[i].tolist()))
+
+
+def _edge_places(c):
+    return sorted({c.place_of_byte(EDGE), EDGE // TS, c.M - 1})
+
+
+def _words_to_records(w):
+    return np.ascontiguousarray(w.cpu().numpy()).reshape(-1).view(TL.TONE_DTYPE)
+
+
+@pytest.mark.parametrize("use_seg", [False, True], ids=["no_index", "index"])
+@pytest.mark.parametrize("damage", [False, True], ids=["clean", "damaged"])
+def test_fir_levels(big, damage, use_seg):
+    """x3_fir_levels_dev at bin lengths 10 000 and 640 000: every record of the stream, eight taps against the closed form,
+    taps (1, -1) against DIFF's records, which tests/test_big_cases.py proves equal"""
+    x3 = big.x3
+    with big.damaged(seam_bad(big.case) if damage else []) as c:
+        for bin_len in (10000, 640000):
+            n_bins = c.total // bin_len
+            for sig, ref in ((B.FIR8, B.FIR8), (B.FIR_DIFF, B.DIFF)):
+                lv, st, res = _signal_levels(big, "fir_levels_dev", x3.Fir(sig[1], sig[2]), bin_len, n_bins, use_seg)
+                what = "FIR levels: bin length %d, taps %s" % (bin_len, sig[1])
+                got = _level_records(lv)
+                _same_records(got, c.levels(bin_len, signal=ref), what)
+                _check_result(c, st, res, big.torch, what)
+                if not damage:
+                    assert int(got["n"].sum()) == c.total - (len(sig[1]) - 1)
+
+
+@pytest.mark.parametrize("use_seg", [False, True], ids=["no_index", "index"])
+@pytest.mark.parametrize("damage", [False, True], ids=["clean", "damaged"])
+def test_tone_levels(big, damage, use_seg):
+    """x3_tone_levels_dev at one odd step: every record of the stream against the torch reference on the device, the bins of
+    the three marked places against Case.tone_records as well, and x3_tone_power_levels_dev in place on those"""
+    x3, torch, ctx = big.x3, big.torch, big.ctx
+    assert x3.Tone.at(12345.678, 192000).step | 1 == TONE_STEP
+    with big.damaged(seam_bad(big.case) if damage else []) as c:
+        ref = _tone_ref(big, c, 0, c.total // SPF, SPF, BANK_STEPS)[0:1]
+        for bin_len in (10000, 640000):
+            n_bins = c.total // bin_len
+            lv, st, res = _signal_levels(big, "tone_levels_dev", x3.Tone(TONE_STEP), bin_len, n_bins, use_seg)
+            what = "tone levels: bin length %d" % bin_len
+            want = _fold(big, ref, bin_len // SPF)[0]
+            got = _tone_words(lv)
+            _same_words(torch, got, want, what)
+            _check_result(c, st, res, torch, what)
+            per = TS // bin_len
+            for m in _edge_places(c):
+                rec = _words_to_records(got[m * per:(m + 1) * per])
+                cpu = c.tone_records(m * TS, (m + 1) * TS, bin_len, TONE_STEP)
+                assert np.array_equal(rec, cpu), (what, "place %d" % m, first_diff(rec, cpu))
+                part = lv[m * per:(m + 1) * per].clone()
+                big.ready()
+                assert ctx.tone_power_levels_dev(part.data_ptr(), per, part.data_ptr()) == 0, ctx.last_error()
+                ctx.sync()
+                _same_records(_level_records(part), TL.tone_power_levels(cpu), what + ": the band's level, place %d" % m)
+
+
+@pytest.mark.parametrize("use_seg", [False, True], ids=["no_index", "index"])
+@pytest.mark.parametrize("damage", [False, True], ids=["clean", "damaged"])
+def test_tone_bank_levels(big, damage, use_seg):
+    """x3_tone_bank_levels_dev with eight steps (0, 2^30, 2^31, 2^32 - 1 and the tone's among them): plane t is the single
+    call's records for step t, from the same reference"""
+    x3, torch = big.x3, big.torch
+    tones = [x3.Tone(s) for s in BANK_STEPS]
+    with big.damaged(seam_bad(big.case) if damage else []) as c:
+        ref = _tone_ref(big, c, 0, c.total // SPF, SPF, BANK_STEPS)
+        for bin_len in (10000, 640000):
+            n_bins = c.total // bin_len
+            lv, st, res = _signal_levels(big, "tone_bank_levels_dev", tones, bin_len, n_bins, use_seg, planes=len(tones))
+            what = "tone bank levels: bin length %d" % bin_len
+            _same_words(torch, _tone_words(lv).view(len(tones), n_bins, 4), _fold(big, ref, bin_len // SPF), what)
+            _check_result(c, st, res, torch, what)
+
+
+@pytest.mark.parametrize("use_seg", [False, True], ids=["no_index", "index"])
+def test_signal_levels_one_bin_and_a_bin_short_of_2_32(big, use_seg):
+    """as test_levels_one_bin_and_a_bin_short_of_2_32, for the FIR, the tone and the bank: bin_len 0 is one record whose n
+    counts modulo 2^32; n_bins that end one bin short of position 2^32 count nothing from 4 294 960 000 on"""
+    x3, torch, c = big.x3, big.torch, big.case
+    tones = [x3.Tone(s) for s in BANK_STEPS]
+    ref = _tone_ref(big, c, 0, c.total // SPF, SPF, BANK_STEPS)
+    short = EDGE // 10000
+    # FIR
+    fir = x3.Fir(B.FIR8[1], B.FIR8[2])
+    lv, _, res = _signal_levels(big, "fir_levels_dev", fir, 0, 1, use_seg)
+    assert res == (0, 0, c.F, 0)
+    got = _level_records(lv)
+    _same_records(got, c.levels(0, signal=B.FIR8), "FIR: one bin for everything")
+    assert int(got["n"][0]) == (c.total - 7) & M32
+    lv, _, _ = _signal_levels(big, "fir_levels_dev", fir, 10000, short, use_seg)
+    got = _level_records(lv)
+    _same_records(got, c.levels(10000, short, B.FIR8), "FIR: bins that stop short of position 2^32")
+    assert int(got["n"].sum(dtype=np.uint64)) == short * 10000 - 7
+    # tone and bank: one record is the fold of all, n modulo 2^32
+    one = _fold(big, ref, ref.shape[1])
+    assert int(one[0, 0, 3]) == c.total
+    one[:, :, 3] &= M32
+    lv, _, _ = _signal_levels(big, "tone_levels_dev", tones[0], 0, 1, use_seg)
+    _same_words(torch, _tone_words(lv), one[0], "tone: one bin for everything")
+    lv, _, _ = _signal_levels(big, "tone_bank_levels_dev", tones, 0, 1, use_seg, planes=len(tones))
+    _same_words(torch, _tone_words(lv).view(len(tones), 1, 4), one, "tone bank: one bin for everything")
+    lv, _, _ = _signal_levels(big, "tone_levels_dev", tones[0], 10000, short, use_seg)
+    _same_words(torch, _tone_words(lv), ref[0, :short], "tone: bins that stop short of position 2^32")
+    lv, _, _ = _signal_levels(big, "tone_bank_levels_dev", tones, 10000, short, use_seg, planes=len(tones))
+    _same_words(torch, _tone_words(lv).view(len(tones), short, 4), ref[:, :short].contiguous(), "tone bank: bins short of 2^32")
+
+
+# ------------------------------------------------------------------------------------------------ E3. their range forms
+
+def _signal_range_levels(big, call, arg, starts, lens, bin_len, use_seg, planes=1):
+    """one x3_fir_range_levels_dev / x3_tone_range_levels_dev / x3_tone_bank_range_levels_dev, packed -> (records on the
+    device uint8 [planes, cap, 32], rows of every range, statuses, x3_range_levels_result); two records of 0x5A behind every
+    plane's last must survive"""
+    torch, ctx = big.torch, big.ctx
+    n = len(starts)
+    rows = [max(1, -(-x // bin_len)) for x in lens]
+    cap = sum(rows)
+    lv = big.full((planes * cap + 2, 32), 0x5A, torch.uint8)
+    off = big.full((n + 1,), -1, torch.int64)
+    st = big.full((n,), -1, torch.int32)
+    d_starts, d_lens = big.u64(starts), big.u32(lens)
+    seg = big.seg_args(use_seg)
+    big.ready()
+    rc = getattr(ctx, call)(*big.args(), d_starts.data_ptr(), d_lens.data_ptr(), n, bin_len, 0, lv.data_ptr(), cap, off.data_ptr(),
+                            st.data_ptr(), *seg, arg)
+    assert rc == 0, ctx.last_error()
+    res = ctx.range_levels_result()
+    assert bool((lv[planes * cap:] == 0x5A).all()), "written behind the last plane's rows_cap"
+    assert off.cpu().numpy().tolist() == np.concatenate([[0], np.cumsum(rows)]).tolist()
+    return lv[:planes * cap].view(planes, cap, 32), rows, st.cpu().numpy(), res
+
+
+def _range_cases(c):
+    """test_range_levels' ranges: both sides of 2^32, 2^31 + 7 samples across it, 14 samples across it, the stream's end"""
+    return ([EDGE - 5000, EDGE + 5000, (1 << 31) + 12345, EDGE - 7, c.total - 20001], [30000, 30000, (1 << 31) + 7, 14, 20001])
+
+
+def _range_damage(c):
+    return three_bad(c) + [(EDGE // TS, EDGE // SPF % FPT)]
+
+
+def _check_range_status(c, starts, lens, rows, st, res):
+    want_st = [c.range_status(s, n) for s, n in zip(starts, lens)]
+    assert st.tolist() == want_st and (res[0], res[1], res[4]) == (0, sum(1 for v in want_st if v), sum(rows)), (st, want_st, res)
+
+
+@pytest.mark.parametrize("use_seg", [False, True], ids=["no_index", "index"])
+@pytest.mark.parametrize("damage", [False, True], ids=["clean", "damaged"])
+def test_fir_range_levels(big, damage, use_seg):
+    """x3_fir_range_levels_dev: the filtered stream cut to ranges on both sides of 2^32, bins from each range's own start"""
+    x3 = big.x3
+    with big.damaged(_range_damage(big.case) if damage else []) as c:
+        starts, lens = _range_cases(c)
+        for sig, ref in ((B.FIR8, B.FIR8), (B.FIR_DIFF, B.DIFF)):
+            lv, rows, st, res = _signal_range_levels(big, "fir_range_levels_dev", x3.Fir(sig[1], sig[2]), starts, lens, 10000, use_seg)
+            _check_range_status(c, starts, lens, rows, st, res)
+            got, at = _level_records(lv[0]), 0
+            for w, (s, n) in enumerate(zip(starts, lens)):
+                _same_records(got[at:at + rows[w]], c.range_levels(s, n, 10000, ref), "FIR range (%d, %d), taps %s" % (s, n, sig[1]))
+                at += rows[w]
+
+
+def _tone_range_check(big, c, lv, rows, starts, lens, steps, what):
+    """planes of tone range records [T, cap, 32] against Case.tone_records (the short ranges, and the last, short bin of the
+    long one) and against the device reference at the range's own phase (the whole bins of the long one)"""
+    torch = big.torch
+    words = _tone_words(lv).view(len(steps), -1, 4)
+    at = 0
+    for w, (s, n) in enumerate(zip(starts, lens)):
+        got = words[:, at:at + rows[w]]
+        full = n // 10000 if n > 100000 else 0
+        if full:
+            assert tuple(steps) == BANK_STEPS[:len(steps)]
+            ref = _tone_ref(big, c, s, full, 10000, BANK_STEPS)[:len(steps)]
+            _same_words(torch, got[:, :full], ref, "%s: range (%d, %d)" % (what, s, n))
+        for t, step in enumerate(steps):
+            rec = _words_to_records(got[t, full:])
+            cpu = c.tone_records(s + full * 10000, s + n, 10000, step)
+            assert np.array_equal(rec, cpu), ("%s: range (%d, %d), step %d" % (what, s, n, step), first_diff(rec, cpu))
+        at += rows[w]
+
+
+@pytest.mark.parametrize("use_seg", [False, True], ids=["no_index", "index"])
+@pytest.mark.parametrize("damage", [False, True], ids=["clean", "damaged"])
+def test_tone_range_levels(big, damage, use_seg):
+    """x3_tone_range_levels_dev and x3_tone_bank_range_levels_dev: the oscillators do not restart at a range, so a start past
+    2^32 decides the phase"""
+    x3 = big.x3
+    with big.damaged(_range_damage(big.case) if damage else []) as c:
+        starts, lens = _range_cases(c)
+        lv, rows, st, res = _signal_range_levels(big, "tone_range_levels_dev", x3.Tone(TONE_STEP), starts, lens, 10000, use_seg)
+        _check_range_status(c, starts, lens, rows, st, res)
+        _tone_range_check(big, c, lv, rows, starts, lens, BANK_STEPS[:1], "tone")
+        tones = [x3.Tone(s) for s in BANK_STEPS]
+        lv, rows, st, res = _signal_range_levels(big, "tone_bank_range_levels_dev", tones, starts, lens, 10000, use_seg, planes=8)
+        _check_range_status(c, starts, lens, rows, st, res)
+        _tone_range_check(big, c, lv, rows, starts, lens, BANK_STEPS, "tone bank")
+
+
+def test_signal_range_levels_of_everything_equal_levels(big):
+    """test_range_levels_of_everything_equal_levels for the FIR and the tone: three ranges back to back, each a multiple of the
+    bin length, give the levels call's records, record for record"""
+    x3, torch, c = big.x3, big.torch, big.case
+    lens = [2_000_000_000, 2_000_000_000, c.total - 4_000_000_000]
+    starts = [0, lens[0], lens[0] + lens[1]]
+    n_bins = c.total // 10000
+    for what, arg in (("fir", x3.Fir(B.FIR8[1], B.FIR8[2])), ("tone", x3.Tone(TONE_STEP))):
+        got, rows, st, res = _signal_range_levels(big, what + "_range_levels_dev", arg, starts, lens, 10000, True)
+        assert st.tolist() == [0, 0, 0] and sum(rows) == n_bins
+        lv, _, _ = _signal_levels(big, what + "_levels_dev", arg, 10000, n_bins, True)
+        assert torch.equal(got[0], lv), "ranges against the levels call: " + what
+
+
 # ------------------------------------------------------------------------------------------------ F. entries of one buffer
 
 def entry_table(c):
@@ -665,6 +1015,33 @@ def _corpus_levels(c, ents, signal):
     return np.concatenate(parts)
 
 
+def _corpus_signal_refs(big, c, ents):
+    """fir_levels_ref.corpus_fir_levels and tone_levels_ref.corpus_tone_levels on the entries' own samples at bin length
+    10 000 (computed once: both index forms see the same entries), and the bank's planes [8, rows]: plane 0 is the tone's, the
+    others Case's tone_records_of from each entry's first position, which tests/test_big_cases.py holds to the same reference"""
+    if "corpus" not in big.refs:
+        entries = []
+        for g, k in ents:
+            st = [c.bad.get(g + i, 0) for i in range(k)]
+            entries.append(([c.samples((g + i) * SPF, (g + i + 1) * SPF) for i in range(k)], st, [i * SPF for i in range(k)], k * SPF))
+        fir = FL.corpus_fir_levels(entries, SPF, B.FIR8[1], B.FIR8[2])[0]
+        tone = TL.corpus_tone_levels(entries, SPF, TONE_STEP)[0]
+        bank = np.stack([tone] + [np.concatenate([B.tone_records_of(np.concatenate(fr), np.repeat(np.array(st) == 0, SPF), 0, SPF, step)
+                                                  for fr, st, _, _ in entries]) for step in BANK_STEPS[1:]])
+        big.refs["corpus"] = (fir, tone, bank)
+    return big.refs["corpus"]
+
+
+def _entry_frames(c, ents, e, s, n):
+    """(frames, sample offsets) of the frames of entry e that cover the range (s, n), and the one in front of them (a FIR
+    value reaches 7 samples back), as the range references take them: positions relative to the entry"""
+    g, k = ents[e]
+    a, b = max(s // SPF - 1, 0), min((s + max(n, 1) - 1) // SPF, k - 1)
+    st = [c.bad.get(g + j, 0) for j in range(a, b + 1)]
+    frames = [(v, None if v else c.samples((g + j) * SPF, (g + j + 1) * SPF)) for v, j in zip(st, range(a, b + 1))]
+    return frames, np.arange(a, b + 2, dtype=np.uint64) * np.uint64(SPF)
+
+
 @pytest.mark.parametrize("index", ["decode", "walk"])
 def test_corpus(big, index):
     """x3_corpus_build over the entry table (seg_blocks 32, recorded by a decode or built by the walk) and every corpus call
@@ -746,8 +1123,333 @@ def test_corpus(big, index):
                     assert st[i] == (BAD if over else c.range_status(g * SPF + int(s), int(n))), (name, i)
                     _same_records(got[roff[i]:roff[i + 1]], want, "corpus range levels %d of entry %d, %s" % (i, e, name))
                 assert st[0] == BAD and st[-1] == c.bad[ents[ENTRY_BAD][0] + 4]
+            # the FIR, tone and bank forms: the filter's history and the oscillators' phase restart at every entry
+            fir, tone = x3.Fir(B.FIR8[1], B.FIR8[2]), x3.Tone(TONE_STEP)
+            tones = [x3.Tone(v) for v in BANK_STEPS]
+            want_fir, want_tone, want_bank = _corpus_signal_refs(big, c, ents)
+            rec, rf, st = corpus.levels(SPF, signal=fir)
+            assert rf.tolist() == first.tolist() and st.tolist() == fst
+            _same_records(rec, want_fir, "corpus FIR levels")
+            rec, rf, st = corpus.tone_levels(SPF, tone)
+            assert rf.tolist() == first.tolist() and st.tolist() == fst
+            _same_records(rec, want_tone, "corpus tone levels")
+            rec, rf, st = corpus.tone_bank_levels(SPF, tones)
+            assert rf.tolist() == first.tolist() and st.tolist() == fst and rec.shape == want_bank.shape
+            for t in range(len(tones)):
+                _same_records(rec[t], want_bank[t], "corpus tone bank levels, plane %d" % t)
+            sub = [_entry_frames(c, ents, int(e), int(s), int(n)) for e, s, n in zip(ke, ks, kl)]
+            over = [s + n > ns[e] for e, s, n in zip(ke, ks, kl)]
+            want_st = [BAD if o else c.range_status(ents[e][0] * SPF + int(s), int(n)) for o, e, s, n in zip(over, ke, ks, kl)]
+            rows = [max(1, -(-int(n) // 2000)) for n in kl]
+            lvs, roff, st = corpus.fir_range_levels(ke, ks, kl, 2000, fir)
+            got, roff = x3.event_levels_view(lvs), roff.cpu().numpy()
+            assert st.cpu().numpy().tolist() == want_st
+            for i, (s, n) in enumerate(zip(ks, kl)):
+                want = LR.empty(rows[i]) if over[i] else FRL.one(*sub[i], int(s), int(n), 2000, B.FIR8[1], B.FIR8[2])[0]
+                _same_records(got[roff[i]:roff[i + 1]], want, "corpus FIR range levels %d of entry %d" % (i, ke[i]))
+            tab = TL.table()
+            lvs, roff, st = corpus.tone_range_levels(ke, ks, kl, 2000, tone)
+            got, roff = lvs.cpu().numpy().reshape(-1).view(TL.TONE_DTYPE), roff.cpu().numpy()
+            assert st.cpu().numpy().tolist() == want_st
+            lvb, roffb, stb = corpus.tone_bank_range_levels(ke, ks, kl, 2000, tones)
+            gotb = lvb.cpu().numpy().reshape(len(tones), -1).view(TL.TONE_DTYPE)
+            assert stb.cpu().numpy().tolist() == want_st and roffb.cpu().numpy().tolist() == roff.tolist() and gotb.shape[1] == got.size
+            for i, (s, n) in enumerate(zip(ks, kl)):
+                for t, step in enumerate(BANK_STEPS):
+                    want = TL.empty(rows[i]) if over[i] else TRL.one(*sub[i], int(s), int(n), 2000, step, tab)[0]
+                    _same_records(gotb[t, roff[i]:roff[i + 1]], want, "corpus tone bank range levels %d of entry %d, plane %d" % (i, ke[i], t))
+                    if t == 0:
+                        _same_records(got[roff[i]:roff[i + 1]], want, "corpus tone range levels %d of entry %d" % (i, ke[i]))
         finally:
             corpus.close()
+
+
+# ------------------------------------------------------------------------------------------------ S. spectra and band levels
+
+FILL64 = 0x5A5A5A5A5A5A5A5A
+
+
+def _spectra_ranges(c, n_fft):
+    """(offset, len) into the virtual signal as a sample buffer of c.total elements: around element 2^31, below, across and
+    above element 2^32, the buffer's end, two that run off it, lengths N - 1, N and 0"""
+    N = n_fft
+    return [(5, 2100), ((1 << 31) - 100, 2200), (EDGE - 1 - 2500, 2500), (EDGE - 700, 3000), (EDGE, 2500), (EDGE + 12345, 3001),
+            (c.total - 2222, 2222), (c.total - 2000, 2001), (c.total + 1, 100), (EDGE - N + 6, N - 1), (EDGE - N // 2, N),
+            (EDGE + (1 << 27) + 7, 4000), (EDGE + 1, 0)]
+
+
+def _compact(c, ranges):
+    """the ranges' samples back to back on the host -> (samples, remapped offsets, lens, in_status): a range that runs off the
+    buffer keeps its length and carries BAD_ARG in, as the call gives it"""
+    parts, offs, at, st = [], [], 0, []
+    for o, n in ranges:
+        off_end = o > c.total or n > c.total - o
+        st.append(BAD if off_end else 0)
+        offs.append(at)
+        if not off_end:
+            parts.append(c.samples(o, o + n))
+            at += n
+    return np.concatenate(parts + [np.zeros(4096, dtype=np.int16)]), offs, [n for _, n in ranges], st
+
+
+def _spectra_call(big, ranges, n_fft, hop, fmt, stride, rows_cap, fold=None, out=None):
+    """x3_spectra_rows_dev, or with fold = (per_bin, n_bands, plane_stride, bin_band) x3_spectra_levels_dev into out, on
+    the virtual signal -> (out on the device, row offsets, statuses, x3_spectra_result)"""
+    torch, ctx, x3 = big.torch, big.ctx, big.x3
+    n = len(ranges)
+    virt = big.virtual()
+    d_off, d_len = big.u64([o for o, _ in ranges]), big.u32([l for _, l in ranges])
+    ro, st = big.full((n + 1,), -1, torch.int64), big.full((n,), -1, torch.int32)
+    rule = x3.SpectraRule(n_fft, hop, fmt, 0, ctx.tone_table_dev())
+    if fold is None:
+        words = (n_fft // 2 + 1) * (2 if fmt == S.SUMS else 1)
+        if out is None:
+            out = big.full((rows_cap + 1, words), FILL64 if fmt == S.SUMS else 0x5A5A5A5A, torch.int64 if fmt == S.SUMS else torch.int32)
+        big.ready()
+        rc = ctx.spectra_rows_dev(virt.data_ptr(), big.case.total, d_off.data_ptr(), d_len.data_ptr(), None, n, rule, stride,
+                                  out.data_ptr(), rows_cap, ro.data_ptr(), st.data_ptr())
+    else:
+        d_map = big.u32(fold[3])
+        f = x3.SpectraFold(fold[0], fold[1], fold[2], d_map.data_ptr(), 0)
+        big.ready()
+        rc = ctx.spectra_levels_dev(virt.data_ptr(), big.case.total, d_off.data_ptr(), d_len.data_ptr(), None, n, rule, f, stride,
+                                    out.data_ptr(), rows_cap, ro.data_ptr(), st.data_ptr())
+    assert rc == 0, ctx.last_error()
+    res = ctx.spectra_result()
+    return out, ro.cpu().numpy().view(np.uint64), st.cpu().numpy(), res
+
+
+def _spectra_result_of(want_st, total):
+    bad = np.flatnonzero(want_st)
+    return (0, bad.size, int(bad[0]) if bad.size else len(want_st), int(want_st[bad[0]]) & 0xFF if bad.size else 0, total)
+
+
+@pytest.mark.parametrize("padded", [False, True], ids=["packed", "padded"])
+@pytest.mark.parametrize("fmt", [S.SUMS, S.POWER], ids=["sums", "power"])
+@pytest.mark.parametrize("n_fft,hop", [(64, 1), (1024, 1029)])
+def test_spectra_rows_of_a_buffer_past_2_32_elements(big, n_fft, hop, fmt, padded):
+    """x3_spectra_rows_dev on the virtual signal, samples_cap 4.43 G: offsets below, across, at and above element 2^32, the
+    buffer's last samples and past them, against spectra_ref on a compacted host copy of the same slices"""
+    c = big.case
+    assert B.modulo_conditions(c)["samples"] and c.kind[EDGE // TS] == 2      # (a wrapped offset reads another tile)
+    ranges = _spectra_ranges(c, n_fft)
+    rows = [S.n_rows(l, n_fft, hop) for _, l in ranges]
+    assert rows[9] == 0 and rows[10] == 1 and ranges[2][0] + ranges[2][1] == EDGE - 1 and ranges[6][0] + ranges[6][1] == c.total
+    r = (EDGE - 1 - ranges[3][0]) // hop              # a frame of the fourth range begins below element 2^32 and ends above it
+    assert ranges[7][0] + ranges[7][1] == c.total + 1 and r < rows[3] and ranges[3][0] + r * hop < EDGE < ranges[3][0] + r * hop + n_fft
+    stride = max(rows) if padded else 0
+    cap = (len(ranges) * stride if padded else sum(rows)) + 3
+    host, offs, lens, in_st = _compact(c, ranges)
+    want, w_off, w_st, w_total = S.spectra_rows(host, offs, lens, in_st, n_fft, hop, fmt, stride, cap)
+    assert w_st.tolist() == [0] * 7 + [BAD, BAD] + [0] * 4
+    out, ro, st, res = _spectra_call(big, ranges, n_fft, hop, fmt, stride, cap)
+    assert st.tolist() == w_st.tolist() and np.array_equal(ro, w_off), (st, ro, w_off)
+    assert res == _spectra_result_of(w_st, w_total), res
+    got = out.cpu().numpy()
+    got = got.view(np.int64).reshape(cap + 1, -1, 2) if fmt == S.SUMS else got.view(np.uint32)
+    assert (got[cap:].view(np.uint8) == 0x5A).all(), "written behind rows_cap"
+    if not np.array_equal(got[:cap], want):
+        r = np.flatnonzero((got[:cap] != want).reshape(cap, -1).any(axis=1))
+        w = int(np.searchsorted(w_off.astype(np.int64), r[0], side="right")) - 1
+        raise AssertionError("N %d hop %d: %d rows differ, the first %d (range %d %s)" % (n_fft, hop, r.size, r[0], w, ranges[min(w, len(ranges) - 1)]))
+
+
+def _band_map(n_fft):
+    """three bands, band 1 empty: the bins go to band 0 and 2 in turn, every fifth to no band (a word above K, a wild one)"""
+    m = np.where(np.arange(n_fft // 2 + 1) % 2, 2, 0).astype(np.uint32)
+    m[::5] = 7
+    m[3] = 0xFFFFFFFF
+    return m
+
+
+@pytest.mark.parametrize("padded", [False, True], ids=["packed", "padded"])
+@pytest.mark.parametrize("n_fft,hop", [(64, 1), (1024, 1029)])
+def test_spectra_levels_planes_past_byte_2_33(big, n_fft, hop, padded):
+    """x3_spectra_levels_dev on the ranges above with plane_stride 2^27 + 5 records: planes 1 and 2 begin past byte 2^32 and
+    2^33 of a 12.9 GB buffer.  The records the call owns against spectra_levels_ref, every other byte still 0x5A"""
+    c, torch = big.case, big.torch
+    K, M, ps = 3, 3, (1 << 27) + 5
+    assert 32 * ps > EDGE and 64 * ps > 2 * EDGE
+    ranges = _spectra_ranges(c, n_fft)
+    bins = [SL.n_bins_of(S.n_rows(l, n_fft, hop), M) for _, l in ranges]
+    stride = max(bins) if padded else 0
+    cap = (len(ranges) * stride if padded else sum(bins)) + 2
+    host, offs, lens, in_st = _compact(c, ranges)
+    want, w_off, w_st, w_total = SL.spectra_levels(host, offs, lens, in_st, n_fft, hop, M, _band_map(n_fft), K, stride, cap)
+    buf = big.full((K * ps, 4), FILL64, torch.int64)
+    out, ro, st, res = _spectra_call(big, ranges, n_fft, hop, S.POWER, stride, cap, fold=(M, K, ps, _band_map(n_fft)), out=buf)
+    assert st.tolist() == w_st.tolist() and np.array_equal(ro, w_off), (st, ro, w_off)
+    assert res == _spectra_result_of(w_st, w_total), res
+    for b in range(K):
+        got = buf[b * ps:b * ps + cap].cpu().numpy().reshape(-1).view(SL.LEVEL)
+        d = first_diff(got, want[b])
+        assert not d, ("plane %d" % b, d, got[d[:1]], want[b][d[:1]])
+        assert int((buf[b * ps + cap:(b + 1) * ps] != FILL64).sum()) == 0, "written between rows_cap and plane_stride of plane %d" % b
+    if not padded:
+        assert (want[:, w_total:].view(np.uint8) == 0x5A).all() and w_total == cap - 2    # (so were the records behind the total)
+
+
+def _sums_ref(big, a, n_rows, n_fft, hop):
+    """the SUMS rows of the frames at a + r * hop, r < n_rows, of the virtual signal by a float64 matmul on the device ->
+    int64 [n_rows, B, 2].  Exact: every term is an integer below 2^30 in magnitude and a frame has at most 2^10 of them, so
+    every partial sum, in any order, stays below 2^40, far inside the 2^53 a float64 holds exactly"""
+    torch = big.torch
+    basis = torch.from_numpy(S.basis(n_fft).astype(np.float64).reshape(n_fft, -1)).to(big.dev)
+    x = big.virtual()[a:a + (n_rows - 1) * hop + n_fft].to(torch.float64).unfold(0, n_fft, hop)
+    return (x @ basis).to(torch.int64).view(n_rows, n_fft // 2 + 1, 2)
+
+
+def _power_ref(big, sums, n_fft):
+    """spectra_ref.power_of's integer formula on the device -> int64 [rows, B]"""
+    a, b = sums[..., 0] >> 15, sums[..., 1] >> 15
+    return (2 * (a * a + b * b) // n_fft // n_fft).clamp_(max=1 << 30)
+
+
+@pytest.mark.parametrize("fmt", [S.POWER, S.SUMS], ids=["power_past_word_2_32", "sums_past_byte_2_32"])
+def test_spectra_rows_output_past_2_32(big, fmt):
+    """x3_spectra_rows_dev, n_fft 64 and hop 1, packed.  POWER: 130 150 500 rows of a range that straddles sample 2^32, then
+    100 rows of the last place, which begin 24 rows below word 2^32 of the 17.2 GB output and end behind it: windows of 2^20
+    rows at the first rows, around words 2^30 and 2^31 and at the first range's last rows, which end 796 words below word
+    2^32 -- the crossing itself is held by the second range's 100 rows, the output's last.  SUMS: 8 200 000 rows, 4.33 GB, for
+    the byte offset: the first 2^20 rows, the last, and 2^20 rows around byte 2^32 (only 65 593 rows lie behind that byte, so
+    this window ends 32 768 rows behind it and overlaps the last).  SUMS past element 2^32 would need 34 GB: left out.  The
+    windows against a float64 matmul on the device, 64 rows of each against spectra_ref on the CPU; a canary row behind
+    rows_cap survives"""
+    c, torch = big.case, big.torch
+    N, nb, W = 64, 33, 1 << 20
+    if fmt == S.POWER:
+        R1 = 130_150_500
+        ranges = [(EDGE - 65_000_000, R1 + N - 1), (c.total - 5000, 100 + N - 1)]
+        assert R1 + N - 1 < EDGE and R1 * nb < EDGE < (R1 + 100) * nb
+        windows = [(0, 0, W), (0, (1 << 30) // nb - W // 2, W), (0, (1 << 31) // nb - W // 2, W), (0, R1 - W, W), (1, 0, 100)]
+    else:
+        R1 = 8_200_000
+        ranges = [(EDGE - 4_100_000, R1 + N - 1)]
+        rb = EDGE // (nb * 16)                                 # the row that holds byte 2^32 of the output
+        assert R1 - W < rb < R1 - 32768
+        windows = [(0, 0, W), (0, rb + 32768 - W, W), (0, R1 - W, W)]
+    rows = [S.n_rows(l, N, 1) for _, l in ranges]
+    total = sum(rows)
+    pre = np.concatenate([[0], np.cumsum(rows)])
+    out, ro, st, res = _spectra_call(big, ranges, N, 1, fmt, 0, total)
+    assert ro.tolist() == pre.tolist() and st.tolist() == [0] * len(ranges) and res == (0, 0, len(ranges), 0, total), (ro, st, res)
+    assert int((out[total] != (FILL64 if fmt == S.SUMS else 0x5A5A5A5A)).sum()) == 0, "the canary row behind rows_cap"
+    for w, r0, n in windows:
+        a = ranges[w][0] + r0
+        want = _sums_ref(big, a, n, N, 1)
+        got = out[int(pre[w]) + r0:int(pre[w]) + r0 + n]
+        if fmt == S.POWER:
+            want = _power_ref(big, want, N).to(torch.int32)
+        else:
+            got = got.view(n, nb, 2)
+        if not torch.equal(got, want):
+            d = torch.nonzero((got != want).reshape(n, -1).any(dim=1)).reshape(-1)
+            raise AssertionError("range %d, rows from %d: %d rows differ, the first at %d" % (w, r0, d.numel(), r0 + int(d[0])))
+        k = min(n, 64)
+        cpu = S.sums(c.samples(a + n - k, a + n + N - 1), N, 1)
+        cpu = S.power_of(cpu, N).astype(np.int64) if fmt == S.POWER else cpu
+        assert np.array_equal(want[n - k:].cpu().numpy().astype(np.int64), cpu), "the device reference, range %d rows from %d" % (w, r0 + n - k)
+
+
+BL_N, BL_M, BL_EDGES = 256, 32, [1, 9, 40, 41, 129]      # n_fft = hop, frames a row, four bands (the third one bin wide)
+BL_LEN = BL_N * BL_M                                       # 8 192 positions a row
+
+
+def _band_levels_ref(big):
+    """WindowSource.band_levels(256, 256, frames_per_bin=32, bands=BL_EDGES) of the clean stream by torch on the device,
+    from the virtual signal in chunks of 2^13 rows -> int64 [4, rows, 4]: the words of the level records (sum_sq, sum = 0,
+    (min, max), (n, reserved = 0)).  The float64 matmul is exact (sums below 2^38, see _sums_ref)"""
+    if "band" in big.refs:
+        return big.refs["band"]
+    torch, c = big.torch, big.case
+    K = len(BL_EDGES) - 1
+    m = big.x3.spectra_bin_band(BL_N, BL_EDGES)[0].astype(np.int64)
+    keep = torch.from_numpy(np.flatnonzero(m < K)).to(big.dev)
+    band = torch.from_numpy(m[m < K]).to(big.dev)
+    frames = c.total // BL_N
+    rows = -(-c.total // BL_LEN)
+    assert frames * BL_N == c.total and frames % BL_M
+    out = torch.zeros((K, rows, 4), dtype=torch.int64, device=big.dev)
+    for r0 in range(0, rows, 1 << 13):
+        nr = min(1 << 13, rows - r0)
+        nf = min(nr * BL_M, frames - r0 * BL_M)
+        ms = _power_ref(big, _sums_ref(big, r0 * BL_LEN, nf, BL_N, BL_N), BL_N)
+        bp = torch.zeros((nr * BL_M, K), dtype=torch.int64, device=big.dev)          # (frames of zeros change neither sum nor max)
+        bp[:nf] = torch.zeros((nf, K), dtype=torch.int64, device=big.dev).index_add_(1, band, ms[:, keep]).clamp_(max=1 << 30)
+        bp = bp.view(nr, BL_M, K)
+        v = 2 * bp.amax(dim=1)
+        s = torch.sqrt(v.to(torch.float64)).to(torch.int64)                         # floor square root, in integers from here
+        s = s - (s * s > v).to(torch.int64)
+        s = s + ((s + 1) * (s + 1) <= v).to(torch.int64)
+        assert bool(((s * s <= v) & ((s + 1) * (s + 1) > v)).all())
+        peak = s.clamp_(max=32767)
+        out[:, r0:r0 + nr, 0] = bp.sum(dim=1).T
+        out[:, r0:r0 + nr, 2] = (((-peak) & M32) | (peak << 32)).T
+        out[:, r0:r0 + nr, 3] = (frames - torch.arange(r0, r0 + nr, device=big.dev) * BL_M).clamp_(max=BL_M)[None, :]
+    big.refs["band"] = out
+    return out
+
+
+def _band_source(big):
+    c = big.case
+    return big.x3.WindowSource(big.ctx, (big.stream.data_ptr(), c.total_bytes), big.p, seg_blocks=SB, frame_offsets=big.fo.data_ptr(),
+                               n_frames=c.F, seg_index=big.seg().data_ptr())
+
+
+@pytest.mark.parametrize("damage", [False, True], ids=["clean", "damaged"])
+def test_band_levels_of_the_whole_stream(big, damage):
+    """WindowSource.band_levels over 4.43 G samples (its range starts are computed on the host): every record of the four
+    planes against the torch reference; the rows of the three marked places against spectra_levels_ref on the CPU; with one
+    damaged frame above 2^32 exactly the q rows of each range that touches it are the identity.  Then x3_plane_events_dev on
+    the planes under a rule that only the loud tile passes: starts above 2^32, equal to plane_events_ref on the reference"""
+    torch, c, x3 = big.torch, big.case, big.x3
+    K, q = len(BL_EDGES) - 1, 4
+    ref = _band_levels_ref(big)
+    rows = ref.shape[1]
+    f_bad = EDGE // SPF + 3 * FPT + 5
+    with big.damaged([divmod(f_bad, FPT)] if damage else []):
+        big.ready()
+        src = _band_source(big)
+        try:
+            assert src.total == c.total
+            planes = src.band_levels(BL_N, BL_N, frames_per_bin=BL_M, bands=BL_EDGES, q=q)
+            assert tuple(planes.shape) == (K, rows, 32)
+            got = planes.view(torch.int64)
+            want = ref
+            if damage:
+                g0, g1 = f_bad * SPF // (q * BL_LEN), ((f_bad + 1) * SPF - 1) // (q * BL_LEN)
+                assert f_bad * SPF > EDGE and g1 >= g0
+                want = ref.clone()
+                want[:, q * g0:q * (g1 + 1)] = torch.tensor([0, 0, (32767 & M32) | (-32768 << 32), 0], dtype=torch.int64, device=big.dev)
+            _same_words(torch, got.reshape(K * rows, 4), want.reshape(K * rows, 4), "band levels of the whole stream")
+            if damage:
+                return
+            m = x3.spectra_bin_band(BL_N, BL_EDGES)[0]
+            for p in _edge_places(c):            # (past position 2^32 the rows hold tile 2's, then the ordinary tiles' content)
+                i0, i1 = -(-p * TS // BL_LEN), min((p + 1) * TS // BL_LEN, rows)
+                cpu = SL.levels_of(c.samples(i0 * BL_LEN, min(i1 * BL_LEN, c.total)), BL_N, BL_N, BL_M, m, K)
+                rec = planes[:, i0:i1].cpu().numpy().reshape(K, -1).view(SL.LEVEL)
+                assert np.array_equal(rec, cpu), ("place %d" % p, first_diff(rec.reshape(-1), cpu.reshape(-1)))
+            # plane events: a mean square that, in any band, only rows of the last place reach
+            i_last = (c.M - 1) * TS // BL_LEN
+            ms = ref[:, :, 0] // ref[:, :, 3].clamp(min=1)
+            thr = [int(v) + 1 for v in ms[:, :i_last].amax(dim=1).cpu()]
+            assert bool((ms[:, i_last + 1:] >= torch.tensor(thr, device=big.dev)[:, None]).any())
+            rule = PE.PlaneRule(mean_sq_min=thr, peak_min=[0] * K, min_planes=1, join_bins=2, pad_bins=1)
+            r0 = i_last - 16      # (no row below i_last is loud and pad_bins is 1: the rows from r0 on decide every event)
+            cpu_planes = np.ascontiguousarray(ref[:, r0:].cpu().numpy()).reshape(K, -1).view(LR.LEVEL_DTYPE)
+            ev, elv = PE.stream_plane_events(cpu_planes, c.total - r0 * BL_LEN, BL_LEN, rule)
+            ev = [(s + r0 * BL_LEN, n, mask) for s, n, mask in ev]
+            cap = len(ev) + 5
+            assert 1 <= len(ev) and all(s > EDGE for s, _, _ in ev)
+            r = src.plane_events(planes, BL_LEN, x3.PlaneEventRule.make(mean_sq_min=thr, min_planes=1, join_bins=2, pad_bins=1), cap)
+            _, w_st, w_ln, w_mk, w_lv = PE.slots(ev, elv, cap, False)
+            assert int(r[2]) == len(ev)
+            assert np.array_equal(r[0].cpu().numpy().view(np.uint64), w_st) and np.array_equal(r[1].cpu().numpy().view(np.uint32), w_ln)
+            assert np.array_equal(r[3].cpu().numpy().view(np.uint32), w_mk)
+            assert np.array_equal(r[4].cpu().numpy().reshape(K, -1).view(LR.LEVEL_DTYPE), w_lv)
+        finally:
+            src.close()
 
 
 # ------------------------------------------------------------------------------------------------ G. encoders
